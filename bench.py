@@ -8,8 +8,11 @@ One process per GPU; every rank decodes its own shard of utterances (weak scalin
 exchange is the gather of the 1-best word sequences to rank 0 over RCCL.  Rank 0 prints ONE JSON line.
 Steps are independent batches and are pipelined over two pipe objects on two HIP streams (step k+1's front end under the
 tail of step k's decode); all K timed steps are enqueued and collected between the two barriers.  --serial: one after the other.
+A plain run sets up (models, input, beam), warms up, times the K steps and prints the line; --full adds, after the timed steps, the CPU
+baseline, the mode-2-vs-mode-0 check, the stage table of an extra step and (multi-GPU) the strong-scaling region.  --dump-outputs DIR
+writes what the last timed step returned (dump_outputs).
 
-  python bench.py --gpus 1 --steps 3 --warmup 1
+  python bench.py --gpus 1 --steps 3 --warmup 1 [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 ...
 """
 import argparse
@@ -96,6 +99,32 @@ def tune_beam(dsr, torch, mdl, scores, nfr, target=5000.0):
         if abs(act - target) / target < 0.05:
             break
     return best
+
+
+DUMP_MAX_BYTES = 60 * 1000 * 1000          # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def dump_outputs(path, res, arcs, words):
+    """--dump-outputs: what Pipe.collect handed the caller for the last timed step, as path/<name>.npy in float64 (exact for every field): one
+    file per DecodeResult field (score, ac, lm, frames, status, nArcs, nWords, ...; one entry per utterance), arcs and words (the 1-best arc and
+    word sequences, one row per utterance, cut to the longest one, -1 past an utterance's nArcs / nWords) and utt_index (the utterance of each
+    row).  Above DUMP_MAX_BYTES in all, the rows are a fixed seeded sample of the utterances."""
+    os.makedirs(path, exist_ok=True)
+    U = len(res)
+    fields = [f for f, _ in type(res[0])._fields_ if not f.endswith("_")]
+    cols = {f: np.array([getattr(r, f) for r in res], np.float64) for f in fields}
+    na, nw = cols["nArcs"].astype(np.int64), cols["nWords"].astype(np.int64)
+    La = max(1, min(arcs.shape[1], int(na.max()))); Lw = max(1, min(words.shape[1], int(nw.max())))
+    row_bytes = 8 * (len(fields) + La + Lw + 1)
+    keep = np.arange(U)
+    if U * row_bytes > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(U, DUMP_MAX_BYTES // row_bytes, replace=False))
+    out = {f: v[keep] for f, v in cols.items()}
+    out["arcs"] = np.where(np.arange(La) < na[keep, None], arcs[keep, :La], -1).astype(np.float64)
+    out["words"] = np.where(np.arange(Lw) < nw[keep, None], words[keep, :Lw], -1).astype(np.float64)
+    out["utt_index"] = keep.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(mdl, x_host, nsamp, beam, max_seconds=12.0, threads=1):
@@ -185,16 +214,21 @@ def main():
     ap.add_argument("--utts", type=int, default=1000, help="utterances per GPU per step (weak scaling, the default)")
     ap.add_argument("--total-utts", type=int, default=0, help="strong scaling: this many utterances in all, sharded u -> rank u mod world "
                     "(BASELINE configs[3]: --total-utts 1000); 0 = weak scaling with --utts per GPU")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need, after the timed steps: the CPU baseline "
+                    "(--no-cpu drops it), the mode-2-vs-mode-0 agreement run (--no-verify drops it), the stage table of one extra untimed step alone on the GPU "
+                    "(config.serial_step_ms; with --serial the timed steps give the stage table without --full) and, on a multi-GPU run, the strong-scaling region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned to its caller as DIR/<name>.npy (float64): "
+                    "the per-utterance decode results and the 1-best arc and word sequences (rank 0's utterances; see dump_outputs)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="host cores of the N-core CPU baseline leg (0 = all the process may use, at most 16)")
     ap.add_argument("--secs", type=float, default=10.0, help="seconds of audio per utterance")
     ap.add_argument("--states", type=int, default=50000)
     ap.add_argument("--dists", type=int, default=1024)
     ap.add_argument("--beam", type=float, default=0.0, help="0 = tune to ~5k active tokens")
     ap.add_argument("--gmm-mode", type=int, default=2, help="2: MFMA contraction + candidate search in the accumulator layout + exact re-score inside the rounding bound (argmin = mode 0 on every frame, cost rel <= 2e-6; config.gmm_mode2_vs_mode0 reports the agreement on the full batch); 0: exact VALU kernel")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--strong-total", type=int, default=1000, help="multi-GPU runs: after the weak-scaling region, time this many utterances sharded over the "
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline; --workload config5 without its one-stream CPU sample")
+    ap.add_argument("--strong-total", type=int, default=1000, help="multi-GPU runs with --full: after the weak-scaling region, time this many utterances sharded over the "
                     "ranks as a second region (BASELINE configs[3] as stated) and report it as config.strong; 0 = skip")
-    ap.add_argument("--no-verify", action="store_true", help="skip the untimed mode-2-vs-mode-0 agreement run")
+    ap.add_argument("--no-verify", action="store_true", help="--full without the untimed mode-2-vs-mode-0 agreement run")
     ap.add_argument("--pipes", type=int, default=2, help="pipe objects / HIP streams the steps rotate over (default 2; --serial: 1)")
     ap.add_argument("--overlap", action="store_true", help="(default) two pipe objects on two HIP streams: a step is enqueued whole while the step before is still decoding, "
                     "so the front end of step k+1 runs on the CUs the persistent decode workgroups of step k free as its utterances finish (+8 %% throughput; every step "
@@ -206,6 +240,8 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend of the multi-rank run: nccl (= RCCL, the default) or gloo -- gloo with "
                     "DSR_BENCH_DEVICE=0 rehearses the multi-rank control flow with several ranks on ONE GPU (collectives on host tensors)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "pipe":
+        ap.error("--dump-outputs: the pipe workload only")
     if args.steps is None:
         args.steps = 60 if args.workload == "config5" else 5
     if args.warmup is None:
@@ -278,7 +314,7 @@ def main():
 
     def collect(i):
         res, arcs, words = pipes[i].collect(reuse=True); inflight[i] = False          # (the host arrays of a pipe are reused step after step)
-        return res, words, pipes[i].stage_ms()
+        return res, words, pipes[i].stage_ms(), arcs
 
     def gather(r):
         # the path's only exchange: gather the 1-best word sequences on rank 0 (RCCL over xGMI)
@@ -330,32 +366,35 @@ def main():
     sync(); t0 = time.time()
     done = run_steps(args.steps)
     sync(); dt = time.time() - t0
-    # stage table: one more step, untimed and alone on the GPU (in the timed region the front end of a step shares the GPU with
+    if args.dump_outputs and rank == 0:                                     # before anything else reuses the pipes' host arrays
+        res_, words_, _, arcs_ = done[-1]
+        dump_outputs(args.dump_outputs, res_, arcs_, words_)
+    # --full, stage table: one more step, untimed and alone on the GPU (in the timed region the front end of a step shares the GPU with
     # the end of the previous step's decode, so its event intervals include waiting); the roofline entry of the dominant
     # kernel below uses the event intervals of the timed steps themselves
     serial_ms = None; serial_step_ms = None
-    if npipes > 1:
+    if npipes > 1 and args.full:
         sync(); ts = time.time(); submit(0); serial_ms = finish(0)[2]; sync(); serial_step_ms = 1000.0 * (time.time() - ts)
     # ---- configs[3] as literally stated ("1k-utterance batch sharded over N GPUs"): a second timed region of the same run.  Every rank decodes the
     # utterances u = rank mod world of a 1000-utterance batch; at world = 1 that is the region above.  speedup = the weak region's step (one GPU,
     # 1000 utterances) over this one.  The decode runs one utterance per workgroup per CU (time-sliced when there are more utterances than workgroups):
     # a shard costs max(1, shard / 256) utterance-durations, so 125 utterances (8 GPUs) cost as much as 250 (4 GPUs).
     strong2 = None
-    if world > 1 and not strong and args.strong_total > 0:
+    if world > 1 and not strong and args.strong_total > 0 and args.full:
         ids = shard_utterances(args.strong_total, world, rank); Us = min(len(ids), U)
         if Us >= 1:
             batch[0], batch[1], batch[2] = x[:Us].contiguous(), ns_dev[:Us].contiguous(), ns_host[:Us]
             run_steps(1)                                                    # untimed: the shapes of the smaller batch
             sync(); ts = time.time(); done2 = run_steps(args.steps); sync(); dts = time.time() - ts
             tm2 = torch.tensor([dts], dtype=torch.float64, device=cdev); dist.all_reduce(tm2, op=dist.ReduceOp.MAX); dts = float(tm2.item())
-            bad2 = sum(1 for res, _, _ in done2 for r in res if r.status != 0)
+            bad2 = sum(1 for res, _, _, _ in done2 for r in res if r.status != 0)
             strong2 = dict(total_utts=args.strong_total, utts_this_rank=Us, ms_per_step=1000.0 * dts / args.steps,
                            value=args.strong_total * args.secs / 3600.0 / (dts / args.steps), unit="audio_hours/s", failed_utts_rank0=bad2,
                            decode_rounds=round(max(1.0, Us / 256.0), 2), note="shard u -> rank u mod world; one workgroup per CU decodes an utterance: a shard of more than 256 utterances is time-sliced and "
                                 "costs shard/256 utterance-durations, a smaller one costs one")
             batch[0], batch[1], batch[2] = x, ns_dev, ns_host
     stage = np.zeros(6); placements = 0; active = 0; bad = 0; frames = 0
-    for res, words, sms in done:
+    for res, words, sms, _ in done:
         stage += np.array(sms)
         if os.environ.get("DSR_BENCH_VERBOSE") and rank == 0:
             print("step stage ms: " + " ".join("%.2f" % v for v in sms), file=sys.stderr, flush=True)
@@ -407,40 +446,43 @@ def main():
         except (OSError, ValueError, KeyError):
             pass
         roof["launch_ms"] = stage_ms[dom]
-        stages = {}
-        tbl_ms = serial_ms if serial_ms is not None else stage_ms
-        for i, nm in enumerate(names):
-            if nm == "beamform" and fusedFE:
-                continue                                                # no such kernel in this mode: the analysis entry covers it
-            k, a = alg[nm]; s = tbl_ms[i] / 1000.0
-            byteq = k in ("hbm", "lds", "fp64")
-            stages[nm] = dict(ms=round(tbl_ms[i], 3), bound=k,
-                              achieved=round(a / s / (1e9 if byteq else 1e12), 3) if s > 0 else None,
-                              unit=("GB/s" if k == "hbm" else "GB/s of HBM bytes (not the bound)") if byteq else "TFLOP/s")
-            if k == "hbm" and s > 0:
-                stages[nm]["frac_of_hbm_peak"] = round(a / s / 1e9 / HBM_PEAK_GBS, 3)
-            if nm == "analysis" and fusedFE and s > 0:
-                stages[nm]["bytes"] = "SURVEY 8d, fused variant: (C * 512 + 1032) B per frame"
-                try:                                                    # what the counters saw for this kernel (separate --pmc passes of this workload)
-                    kb = tj["kernels"].get("k_analysis_bf_q256")
-                    if kb and same:
-                        stages[nm]["counter_GBs"] = round(kb["bytes_per_launch"] / s / 1e9, 1); stages[nm]["counter_over_algorithmic"] = round(kb["bytes_per_launch"] / a, 2)
-                except NameError:
-                    pass
+        # stage table: the extra step alone on the GPU (--full), or the timed steps themselves when they ran one after the other (--serial)
+        stages = None
+        tbl_ms = serial_ms if serial_ms is not None else (stage_ms if npipes == 1 else None)
+        if tbl_ms is not None:
+            stages = {}
+            for i, nm in enumerate(names):
+                if nm == "beamform" and fusedFE:
+                    continue                                                # no such kernel in this mode: the analysis entry covers it
+                k, a = alg[nm]; s = tbl_ms[i] / 1000.0
+                byteq = k in ("hbm", "lds", "fp64")
+                stages[nm] = dict(ms=round(tbl_ms[i], 3), bound=k,
+                                  achieved=round(a / s / (1e9 if byteq else 1e12), 3) if s > 0 else None,
+                                  unit=("GB/s" if k == "hbm" else "GB/s of HBM bytes (not the bound)") if byteq else "TFLOP/s")
+                if k == "hbm" and s > 0:
+                    stages[nm]["frac_of_hbm_peak"] = round(a / s / 1e9 / HBM_PEAK_GBS, 3)
+                if nm == "analysis" and fusedFE and s > 0:
+                    stages[nm]["bytes"] = "SURVEY 8d, fused variant: (C * 512 + 1032) B per frame"
+                    try:                                                    # what the counters saw for this kernel (separate --pmc passes of this workload)
+                        kb = tj["kernels"].get("k_analysis_bf_q256")
+                        if kb and same:
+                            stages[nm]["counter_GBs"] = round(kb["bytes_per_launch"] / s / 1e9, 1); stages[nm]["counter_over_algorithmic"] = round(kb["bytes_per_launch"] / a, 2)
+                    except NameError:
+                        pass
         gmm_check = None
-        if args.gmm_mode == 2 and world == 1 and not args.no_verify:
+        if args.full and args.gmm_mode == 2 and world == 1 and not args.no_verify:
             # the MFMA scoring path against the exact one on this very batch: same decoder, same features, scores from mode 0
             dec0 = dsr.Decoder(beam=beam, lmScale=12.0, maxActive=65536); dec0.set(mdl["gd"])
             p0 = dsr.Pipe(mdl["ana"], mdl["syn"], mdl["bf"], dsr.Mfcc(lda=mdl["lda"]), mdl["gm"], dec0, gmmMode=0, fused=not args.no_fuse)
             r0, _, w0 = p0.run(x, ns_dev, ns_host, maxPath=maxPath, want_paths=True)
-            res2, words2, _ = done[-1]
+            res2, words2 = done[-1][:2]
             same1 = sum(1 for u in range(U) if r0[u].nWords == res2[u].nWords and np.array_equal(w0[u, :r0[u].nWords], words2[u, :res2[u].nWords]))
             sdiff = max(abs(r0[u].score - res2[u].score) / max(1.0, abs(r0[u].score)) for u in range(U))
             gmm_check = dict(one_best_agree="%d/%d" % (same1, U), max_rel_score_diff=float(sdiff),
                              note="GMM mode 2 (MFMA, argmin = mode 0 on every frame, cost rel <= 2e-6) against mode 0 (reference order, bit exact) through the same decoder")
             del p0, dec0
         cpu = None
-        if not args.no_cpu and world == 1:                               # the CPU baseline is a 1-GPU-run item (rank 0 at N = 1 only)
+        if args.full and not args.no_cpu and world == 1:                 # the CPU baseline is a 1-GPU-run item (rank 0 at N = 1 only)
             try:
                 ncores = len(os.sched_getaffinity(0))
             except AttributeError:
@@ -477,7 +519,7 @@ def main():
                                 front_end="analysis bank + MVDR in one kernel (channel snapshots never written; stage 'analysis' covers both, bytes = samples in x 23/16 + beamformed rows out)" if fusedFE
                                 else "analysis bank and beamformer as two kernels",
                                 step_overlap=("two pipe objects on two HIP streams: step k+1 is enqueued while step k decodes, its front end runs on the CUs step k's persistent "
-                                              "decode workgroups free as utterances finish; `stages` and serial_step_ms are one extra, untimed step alone on the GPU "
+                                              "decode workgroups free as utterances finish; `stages` and serial_step_ms (--full) are one extra, untimed step alone on the GPU "
                                               "(their sum exceeds ms_per_step by what the overlap hides); --serial runs the steps one after the other") if npipes > 1 else "none",
                                 serial_step_ms=serial_step_ms, strong=strong2, gmm_mode2_vs_mode0=gmm_check),
                     roofline=roof, stages=stages, cpu_baseline=cpu)

@@ -13,6 +13,8 @@ Outputs:
   linpack_csvdc.npz         seeded complex matrices (2x2 .. 64x64: random, diffuse-field coherence matrices of 8/16/64-microphone
                             arrays, rank deficient, zero) and the singular values, U, V and pseudo-inverse that the reference's own
                             LINPACK csvdc (oracle/_ref) produces for them; six rectangular matrices (2x8 .. 8x2, 2x64) the same way
+  linpack_csvdc_live.npz    the seeded matrices of test_linpack_ref_live (1x1 .. 40x40, square / wide / tall / rank deficient) and
+                            the info, singular values, U and V of the reference's csvdc for them
 """
 import os, sys, wave, shutil
 import numpy as np
@@ -101,4 +103,21 @@ for i, (name, n, p_) in enumerate(rect):
 out["rnames"] = np.array([c[0] for c in rect])
 out["names"] = np.array([c[0] for c in cases])
 np.savez_compressed(f"{HERE}/linpack_csvdc.npz", **out)
+
+# the matrices of test_linpack_ref_live (seed 99: square, wide, tall, 1x1, rank deficient) with what the reference's csvdc returns for them
+rng = np.random.default_rng(99)
+live = {}
+i = 0
+for n, p_ in ((6, 6), (1, 1), (5, 9), (9, 5), (17, 17), (40, 40)):
+    for k in range(3):
+        A = rng.standard_normal((n, p_)) + 1j * rng.standard_normal((n, p_))
+        if k == 2 and n == p_ and n > 2:
+            B = rng.standard_normal((n, n - 2)); A = (B @ B.T).astype(np.complex128)         # rank deficient, real symmetric
+        info, s, u, v = O.ref_csvdc(A)
+        live["A%d" % i] = A; live["info%d" % i] = np.int32(info); live["s%d" % i] = s
+        live["U%d" % i] = np.ascontiguousarray(u); live["V%d" % i] = np.ascontiguousarray(v)
+        live["case%d" % i] = np.array([n, p_, k], np.int32)
+        i += 1
+live["count"] = np.int32(i)
+np.savez_compressed(f"{HERE}/linpack_csvdc_live.npz", **live)
 print("fixtures written to", HERE)

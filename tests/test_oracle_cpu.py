@@ -120,21 +120,22 @@ def test_rectangular_csvdc_pinned_by_linpack(oracle):
 
 
 def test_linpack_ref_live(oracle):
-    """When the reference sources are present (authoring container) run csvdc itself again, on fresh matrices: same bits."""
-    if oracle.build_ref() is None:
-        pytest.skip("/root/reference not present")
-    rng = np.random.default_rng(99)
-    for n, p in ((6, 6), (1, 1), (5, 9), (9, 5), (17, 17), (40, 40)):
-        for k in range(3):
-            A = rng.standard_normal((n, p)) + 1j * rng.standard_normal((n, p))
-            if k == 2 and n == p and n > 2:
-                B = rng.standard_normal((n, n - 2)); A = (B @ B.T).astype(np.complex128)         # rank deficient, real symmetric
-            ir, sr, ur, vr = oracle.ref_csvdc(A)
-            io, so, uo, vo = oracle.csvdc(A)
-            assert ir == io
-            assert np.array_equal(sr.view(np.float32), so.view(np.float32)), (n, p, k)
-            assert np.array_equal(np.ascontiguousarray(ur).view(np.float32), np.ascontiguousarray(uo).view(np.float32)), (n, p, k)
-            assert np.array_equal(np.ascontiguousarray(vr).view(np.float32), np.ascontiguousarray(vo).view(np.float32)), (n, p, k)
+    """The reference's csvdc on fresh matrices (square, wide, tall, 1x1, rank deficient; its outputs committed as tests/golden/linpack_csvdc_live.npz
+    by tests/golden/make_fixtures.py): the restatement gives the same bits.  Where build() made oracle/_ref, csvdc itself runs again on them too."""
+    z = np.load(os.path.join(GOLDEN, "linpack_csvdc_live.npz"))
+    assert int(z["count"]) == 18
+    live = oracle.ref_linpack() is not None
+    for i in range(int(z["count"])):
+        A = z["A%d" % i]; case = tuple(z["case%d" % i])
+        refs = [(int(z["info%d" % i]), z["s%d" % i], z["U%d" % i], z["V%d" % i])]
+        if live:
+            refs.append(oracle.ref_csvdc(A))
+        io, so, uo, vo = oracle.csvdc(A)
+        for ir, sr, ur, vr in refs:
+            assert ir == io, case
+            assert np.array_equal(sr.view(np.float32), so.view(np.float32)), case
+            assert np.array_equal(np.ascontiguousarray(ur).view(np.float32), np.ascontiguousarray(uo).view(np.float32)), case
+            assert np.array_equal(np.ascontiguousarray(vr).view(np.float32), np.ascontiguousarray(vo).view(np.float32)), case
 
 
 def test_mvdr_weights_properties(oracle):

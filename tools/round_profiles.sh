@@ -3,7 +3,7 @@
 # (kernel trace only, as the pool requires) for HBM traffic and the decoder's issue/wait split.  Output under gpurun_out/r03/.
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r03; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python3 $R/bench.py --no-cpu --no-verify > $O/bench_traced.json 2> $O/bench_traced.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python3 $R/bench.py --full --no-cpu --no-verify > $O/bench_traced.json 2> $O/bench_traced.err || exit 1
 cp $(find $O/trace -name "*kernel_stats.csv" | head -n 1) $O/bench_kernel_stats.csv
 python3 - $O <<'PY'
 import csv, glob, sys

@@ -148,8 +148,8 @@ __global__ __launch_bounds__(256) void k_wpe_series(const float2* __restrict__ Y
 
 template <bool YLDS>
 __global__ __launch_bounds__(256) void k_wpe_multi(const float2* __restrict__ Y, const float2* __restrict__ Yt, const int* __restrict__ nframesArr,
-                                                   double2* __restrict__ gnOut, int U, int C, int Nmax, int F, int M, int lowerN, int P, int iterationsN,
-                                                   double loadFactor, int lowerBW)
+                                                   double2* gnOut, int U, int C, int Nmax, int F, int M, int lowerN, int P, int iterationsN,
+                                                   double loadFactor, int lowerBW, const double2* gnIn)      // (gnIn and gnOut may be ONE buffer -- dsr_wpe_multi_continue: no __restrict__)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int PT = P * C, nEnt = PT * (PT + 1) / 2;
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) void k_wpe_multi(const float2* __restrict__ Y,
   if (YLDS) for (int i = tid; i < C * N; i += nthr) { const int ch = i / N, n = i - ch * N; yl[ch * Nmax + n] = Y[(((long) u * C + ch) * Nmax + n) * F + b]; }
   const float2* y = YLDS ? yl : Yt + ((long) u * F + b) * C * Nmax;      // [C][Nmax] either way (two instantiations: no pointer select at run time)
   auto tri = [](int i, int j) { return i * (i + 1) / 2 + j; };
-  for (int l = tid; l < PT; l += nthr) g[l] = make_double2(0.0, 0.0);
+  for (int l = tid; l < PT; l += nthr) g[l] = gnIn ? gnIn[(((long) u * C + c0) * F + b) * PT + l] : make_double2(0.0, 0.0);   // reset() keeps _Gn (:341-354)
   if (tid == 0) s_fail = 0;
   __syncthreads();
   for (int it = 0; it < iterationsN; it++) {
@@ -276,6 +276,10 @@ __global__ __launch_bounds__(256) void k_wpe_multi_out(const float2* __restrict_
   out[i] = make_float2((float) cr, (float) ci);
 }
 
+// past the LDS working set: k_wpe_tiled.hip
+void wpe_multi_tiled(const float2* Yt, const int32_t* nframes, int U, int C, int Nmax, int fftLen, int lowerN, int P, int iterationsN, double loadFactor,
+                     int lowerBW, int filterChan, float2* out, double2* gn, bool warm, hipStream_t st);
+
 }  // namespace dsr
 
 using namespace dsr;
@@ -320,9 +324,20 @@ static dsr_status wpe_single_impl(const float* Y_dev, const int32_t* nframes_dev
 // gn_dev [U][C][M/2+1][C*P] complex128 (required: the filters are handed from the estimation kernel to the output kernel through it).
 // filterChan < 0: every channel is filtered with its own prediction filter; >= 0: all channels with that channel's filter, which is what
 // the reference's getOutput does for the channel whose feature asks for a frame first (:381).  A (subband, channel) whose loaded matrix is
-// not positive definite yields NaNs.
+// not positive definite yields NaNs.  Shapes whose packed matrix does not fit the LDS working set (C P above about 133) take the tiled path
+// (k_wpe_tiled.hip) up to C P = 1024; DSR_WPE_MULTI_TILED=1 forces that path at any size.
+static dsr_status wpe_multi_impl(const float* Y_dev, const int32_t* nframes_dev, int U, int chanN, int Nmax, int fftLen, int lowerN, int upperN, int iterationsN,
+                                 double loadDb, double bandWidth, double sampleRate, int filterChan, float* out_dev, double* gn_dev, bool warm, void* stream);
 dsr_status dsr_wpe_multi(const float* Y_dev, const int32_t* nframes_dev, int U, int chanN, int Nmax, int fftLen, int lowerN, int upperN, int iterationsN,
                          double loadDb, double bandWidth, double sampleRate, int filterChan, float* out_dev, double* gn_dev, void* stream)
+{ return wpe_multi_impl(Y_dev, nframes_dev, U, chanN, Nmax, fftLen, lowerN, upperN, iterationsN, loadDb, bandWidth, sampleRate, filterChan, out_dev, gn_dev, false, stream); }
+// the next block of a long stream (or the next utterance) of an object that was reset() but not nextSpeaker()-ed (dereverberation.cc:341-354, :575-583):
+// gn_dev holds the filters the call before left; they seed the first theta_n of every channel and are replaced by this call's
+dsr_status dsr_wpe_multi_continue(const float* Y_dev, const int32_t* nframes_dev, int U, int chanN, int Nmax, int fftLen, int lowerN, int upperN, int iterationsN,
+                                  double loadDb, double bandWidth, double sampleRate, int filterChan, float* out_dev, double* gn_dev, void* stream)
+{ return wpe_multi_impl(Y_dev, nframes_dev, U, chanN, Nmax, fftLen, lowerN, upperN, iterationsN, loadDb, bandWidth, sampleRate, filterChan, out_dev, gn_dev, true, stream); }
+static dsr_status wpe_multi_impl(const float* Y_dev, const int32_t* nframes_dev, int U, int chanN, int Nmax, int fftLen, int lowerN, int upperN, int iterationsN,
+                                 double loadDb, double bandWidth, double sampleRate, int filterChan, float* out_dev, double* gn_dev, bool warm, void* stream)
 {
   return guard([&] {
     if (!Y_dev || !nframes_dev || !out_dev || !gn_dev) throw Error(DSR_E_PARAMETER, "null argument");
@@ -335,21 +350,34 @@ dsr_status dsr_wpe_multi(const float* Y_dev, const int32_t* nframes_dev, int U, 
     // LDS: packed triangle + r + g + 1 / theta_n, and the series of all channels when they fit beside them; otherwise the series come from a
     // transposed copy of the snapshots in memory (one per stream: the copy is handed from its kernel to the estimation kernel of the same stream)
     const size_t ldsCore = ((size_t) PT * (PT + 1) / 2 + 2 * (size_t) PT) * 16 + (size_t) Nmax * 8, ldsSeries = (size_t) chanN * Nmax * 8, ldsCap = 150 * 1024;
-    if (ldsCore > ldsCap) throw Error(DSR_E_DIMENSION, "WPE: %d channels x %d taps (a %d x %d matrix) and %d frames do not fit the LDS working set", chanN, P, PT, PT, Nmax);
-    const bool yLds = ldsCore + ldsSeries <= ldsCap && !getenv("DSR_WPE_SERIES_MEM");
+    const char* forceTiled = getenv("DSR_WPE_MULTI_TILED");
     hipStream_t st = (hipStream_t) stream;
+    const double2* gnIn = warm ? (const double2*) gn_dev : nullptr;
+    if (ldsCore > ldsCap || (forceTiled && forceTiled[0] && strcmp(forceTiled, "0") != 0)) {
+      // tiled path: the matrices in an HBM workspace, built and factorised on the fp64 MFMA, from the transposed copy of the snapshots
+      if (PT > 1024) throw Error(DSR_E_DIMENSION, "WPE: %d channels x %d taps = %d stacked lags; the multi-channel WPE handles at most 1024", chanN, P, PT);
+      float2* Yt = nullptr;
+      DSR_HIP(hipMallocAsync((void**) &Yt, sizeof(float2) * (size_t) U * F * chanN * Nmax, st));
+      hipLaunchKernelGGL(k_wpe_series, dim3((F + 31) / 32, (Nmax + 31) / 32, U * chanN), dim3(256), 0, st, (const float2*) Y_dev, Yt, chanN, Nmax, F);
+      DSR_HIP(hipGetLastError());
+      wpe_multi_tiled(Yt, nframes_dev, U, chanN, Nmax, fftLen, lowerN, P, iterationsN, pow(10.0, loadDb / 10.0), lowerBW, filterChan, (float2*) out_dev,
+                      (double2*) gn_dev, warm, st);
+      DSR_HIP(hipFreeAsync(Yt, st));
+      return;
+    }
+    const bool yLds = ldsCore + ldsSeries <= ldsCap && !getenv("DSR_WPE_SERIES_MEM");
     if (yLds) {
       const size_t lds = ldsCore + ldsSeries;
       DSR_HIP(hipFuncSetAttribute((const void*) k_wpe_multi<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
       hipLaunchKernelGGL(k_wpe_multi<true>, dim3(F, chanN, U), dim3(256), lds, st, (const float2*) Y_dev, (const float2*) nullptr, nframes_dev, (double2*) gn_dev,
-                         U, chanN, Nmax, F, fftLen, lowerN, P, iterationsN, pow(10.0, loadDb / 10.0), lowerBW);
+                         U, chanN, Nmax, F, fftLen, lowerN, P, iterationsN, pow(10.0, loadDb / 10.0), lowerBW, gnIn);
     } else {
       float2* Yt = nullptr;                                          // stream-ordered scratch: lives from here to the end of the estimation kernel on this stream
       DSR_HIP(hipMallocAsync((void**) &Yt, sizeof(float2) * (size_t) U * F * chanN * Nmax, st));
       hipLaunchKernelGGL(k_wpe_series, dim3((F + 31) / 32, (Nmax + 31) / 32, U * chanN), dim3(256), 0, st, (const float2*) Y_dev, Yt, chanN, Nmax, F);
       DSR_HIP(hipFuncSetAttribute((const void*) k_wpe_multi<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsCore));
       hipLaunchKernelGGL(k_wpe_multi<false>, dim3(F, chanN, U), dim3(256), ldsCore, st, (const float2*) Y_dev, (const float2*) Yt, nframes_dev, (double2*) gn_dev,
-                         U, chanN, Nmax, F, fftLen, lowerN, P, iterationsN, pow(10.0, loadDb / 10.0), lowerBW);
+                         U, chanN, Nmax, F, fftLen, lowerN, P, iterationsN, pow(10.0, loadDb / 10.0), lowerBW, gnIn);
       DSR_HIP(hipFreeAsync(Yt, st));
     }
     DSR_HIP(hipGetLastError());

@@ -454,15 +454,22 @@ def wpe_single(Y, fftLen, lowerN, upperN, iterationsN=2, loadDb=-20.0, bandWidth
     return (out, gn) if want_filters else out
 
 
-def wpe_multi(Y, fftLen, lowerN, upperN, iterationsN=2, loadDb=-20.0, bandWidth=0.0, sampleRate=16000.0, nframes=None, filterChan=-1):
-    """Multi-channel WPE (dereverberation.cc:281-586): Y cuda complex64 [U][C][N][M/2+1] -> (out, filters [U][C][M/2+1][C*P] complex128).
-    filterChan >= 0: all channels through that channel's filter (the reference's getOutput when that channel's feature pulls first)."""
+def wpe_multi(Y, fftLen, lowerN, upperN, iterationsN=2, loadDb=-20.0, bandWidth=0.0, sampleRate=16000.0, nframes=None, filterChan=-1, gn=None):
+    """Multi-channel WPE (dereverberation.cc:281-620): Y cuda complex64 [U][C][N][M/2+1] -> (out, filters [U][C][M/2+1][C*P] complex128).
+    filterChan >= 0: all channels through that channel's filter (the reference's getOutput when that channel's feature pulls first).
+    gn: the filters of the utterance / block before (reset() keeps them in the reference): used as the start and overwritten."""
     import torch
     load()
     U, Cn, N, F = Y.shape
     if nframes is None:
         nframes = torch.full((U,), N, dtype=torch.int32, device=Y.device)
     out = torch.zeros((U, Cn, N, F), dtype=torch.complex64, device=Y.device)
+    if gn is not None:
+        if tuple(gn.shape) != (U, Cn, F, Cn * (upperN - lowerN + 1)) or gn.dtype != torch.complex128 or not gn.is_contiguous():
+            raise ValueError("gn: contiguous complex128 [U][C][M/2+1][C*P] expected")
+        check(_lib.dsr_wpe_multi_continue(_dev(Y.contiguous()), _dev(nframes), U, Cn, N, fftLen, lowerN, upperN, iterationsN, loadDb, bandWidth, sampleRate,
+                                          int(filterChan), _dev(out), _dev(gn), cur_stream()))
+        return out, gn
     gn = torch.zeros((U, Cn, F, Cn * (upperN - lowerN + 1)), dtype=torch.complex128, device=Y.device)
     check(_lib.dsr_wpe_multi(_dev(Y.contiguous()), _dev(nframes), U, Cn, N, fftLen, lowerN, upperN, iterationsN, loadDb, bandWidth, sampleRate, int(filterChan),
                              _dev(out), _dev(gn), cur_stream()))

@@ -602,9 +602,17 @@ dsr_status dsr_wpe_single_continue(const float* Y_dev, const int32_t* nframes_de
                                    int iterationsN, double loadDb, double bandWidth, double sampleRate, float* out_dev, double* gn_dev, void* stream);
 /* MultiChannelWPEDereverberation (dereverberation.h:89-157, dereverberation.cc:281-586): Y_dev [U][chanN][Nmax][fftLen/2+1] complex64 -> out_dev same shape;
  * gn_dev [U][chanN][fftLen/2+1][chanN*(upperN-lowerN+1)] complex128 (required).  filterChan < 0: own filter per channel; >= 0: all channels through that
- * channel's filter = the reference's getOutput when that channel's feature asks for the frame first (dereverberation.cc:381) */
+ * channel's filter = the reference's getOutput when that channel's feature asks for the frame first (dereverberation.cc:381).  The filters start from zero
+ * (nextSpeaker() semantics).  Two paths: while the packed chanN P x chanN P matrix fits the LDS working set (chanN P up to about 133) one workgroup per
+ * (utterance, subband, channel) does it all; above that, up to chanN P = 1024 (64 channels x 16 taps), the matrices are built and factorised in a device
+ * workspace on the fp64 MFMA; beyond 1024 DSR_E_DIMENSION.  The environment variable DSR_WPE_MULTI_TILED=1 takes the second path at any size. */
 dsr_status dsr_wpe_multi(const float* Y_dev, const int32_t* nframes_dev, int U, int chanN, int Nmax, int fftLen, int lowerN, int upperN, int iterationsN,
                          double loadDb, double bandWidth, double sampleRate, int filterChan, float* out_dev, double* gn_dev, void* stream);
+/* the next block of a long stream -- or the next utterance -- of an object that was reset() but not nextSpeaker()-ed (dereverberation.cc:341-354, :575-583:
+ * reset() keeps _Gn): gn_dev (required) holds the filters the call before left; they seed the first theta_n and are replaced by this call's */
+dsr_status dsr_wpe_multi_continue(const float* Y_dev, const int32_t* nframes_dev, int U, int chanN, int Nmax, int fftLen, int lowerN, int upperN,
+                                  int iterationsN, double loadDb, double bandWidth, double sampleRate, int filterChan, float* out_dev, double* gn_dev,
+                                  void* stream);
 
 /* =====================================================================================
  * 6b. LPC / MVDR spectral envelopes  (btk/feature/lpc.cc:44-207, lpc.h:134-195,291-331:

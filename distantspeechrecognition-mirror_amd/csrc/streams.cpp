@@ -226,6 +226,81 @@ struct MmiOp : BfOp {                // SubbandMMI as a stream (beamformer.cc:19
   }
 };
 
+struct DoaOp : BfOp {                // DOAEstimatorSRPDSBLA as a stream (beamformer.cc:3188-3283); channels through dsr_subband_bf_set_channel
+  dsr_doa* doa = nullptr; unsigned gen = 0, seenGen = ~0u; int T = 0, nT = 0, F = 0;
+  std::vector<float> E; std::vector<double> RP; std::vector<float2> Yh;              // the materialised utterance: energy, rp, last unit's bins
+  // the reference object's observable state
+  std::vector<double> acc, rpMat, nbRp, nbDoa, vec; float energy = 0.f; bool haveAcc = false;
+  DevBuf<float> dE; DevBuf<double> dRP, dAcc, dNbR; DevBuf<int> dNbI, nf; DevBuf<float2> dY; int rangeUsed[2] = {-1, -1};
+  void compute() override {
+    const int C = (int) ups.size();
+    if (C == 0 || C != dsr_doa_chan_n(doa)) throw Error(DSR_E_DIMENSION, "Number of channels (%d) does not match the estimator (%d)", C, dsr_doa_chan_n(doa));
+    T = ups[0]->nFrames; for (int c = 1; c < C; c++) if (ups[c]->nFrames < T) T = ups[c]->nFrames;
+    nFrames = T; F = M / 2 + 1; range(rangeUsed[0], rangeUsed[1]);
+    dsr_status st = dsr_doa_build_table(doa); if (st) throw Error(st, "%s", dsr_last_error());
+    st = dsr_doa_theta_n(doa, &nT); if (st) throw Error(st, "%s", dsr_last_error());
+    if (T <= 0) return;
+    const int nB = dsr_doa_nbest(doa);
+    X.reserve((size_t) C * T * F); dY.reserve((size_t) T * F); dE.reserve(T); dRP.reserve((size_t) T * nT); dAcc.reserve(nT);
+    dNbR.reserve((size_t) T * nB); dNbI.reserve((size_t) T * nB);
+    for (int c = 0; c < C; c++) op_pack_bins(ups[c]->d<double2>(), T, F, M, X.p + (size_t) c * T * F, S0);
+    nf.upload(&T, 1);
+    DSR_HIP(hipMemsetAsync(dY.p, 0, sizeof(float2) * (size_t) T * F, S0)); DSR_HIP(hipMemsetAsync(dAcc.p, 0, sizeof(double) * nT, S0));
+    st = dsr_doa_srp(doa, (const float*) X.p, nf.p, 1, T, dE.p, dRP.p, dNbR.p, dNbI.p, dAcc.p, (float*) dY.p, nullptr, S0);
+    if (st) throw Error(st, "%s", dsr_last_error());
+    E.resize(T); RP.resize((size_t) T * nT); Yh.resize((size_t) T * F);
+    DSR_HIP(hipMemcpy(E.data(), dE.p, sizeof(float) * T, hipMemcpyDeviceToHost));
+    DSR_HIP(hipMemcpy(RP.data(), dRP.p, sizeof(double) * RP.size(), hipMemcpyDeviceToHost));
+    DSR_HIP(hipMemcpy(Yh.data(), dY.p, sizeof(float2) * Yh.size(), hipMemcpyDeviceToHost));
+  }
+  void sync_table() {                 // a new steering table: _accRPs and _rpMat start from zero (:3128-3130, :3148-3149)
+    const unsigned g = dsr_doa_table_generation(doa);
+    if (g != seenGen) { acc.assign(nT, 0.0); rpMat.assign(nT, 0.0); haveAcc = true; seenGen = g; }
+  }
+  void reset_nbest() {
+    const int nB = dsr_doa_nbest(doa); nbRp.assign(nB, -10e10); nbDoa.assign((size_t) 2 * nB, -M_PI);
+  }
+  const void* next(int fx) override {
+    if (vec.empty()) vec.assign((size_t) 2 * M, 0.0);
+    if (fx == frameX && frameX >= 0) return vec.data();
+    reset_nbest();                                          // before anything else, the end of the stream included (:3192-3196)
+    int fmin = 0, fmax = 0; range(fmin, fmax);
+    if (ready && (gen != dsr_doa_table_generation(doa) || !dsr_doa_has_table(doa) || fmin != rangeUsed[0] || fmax != rangeUsed[1]))
+      ready = false;                                        // setSearchParam (a new table) or setFrequencyRange since: the rest of the utterance anew
+    if (!ready) {
+      require_device();
+      for (size_t i = 0; i < ups.size(); i++) ups[i]->materialize();
+      compute(); gen = dsr_doa_table_generation(doa); ready = true;
+    }
+    sync_table();
+    if (frameX + 1 >= nFrames) { endOfSamples = true; throw Error(DSR_E_ITERATOR, "end of samples!"); }
+    frameX++;
+    const int t = frameX;
+    energy = E[t];
+    if (energy < dsr_doa_energy_threshold(doa)) return vec.data();     // gated: no accumulation, no N-best, _vector as it was (:3215-3221)
+    const int nB = dsr_doa_nbest(doa);
+    std::vector<double> th(nT); dsr_status st = dsr_doa_thetas(doa, th.data(), nT); if (st) throw Error(st, "%s", dsr_last_error());
+    const double* r = RP.data() + (size_t) t * nT;
+    for (int k = 0; k < nT; k++) {                                    // :3223-3245
+      const double v = r[k];
+      acc[k] += v; rpMat[k] = v;
+      if (!(v > nbRp[nB - 1])) continue;
+      for (int n1 = 0; n1 < nB; n1++)
+        if (v > nbRp[n1]) {
+          for (int n2 = nB - 1; n2 > n1; n2--) { nbRp[n2] = nbRp[n2 - 1]; nbDoa[2 * n2] = nbDoa[2 * n2 - 2]; nbDoa[2 * n2 + 1] = nbDoa[2 * n2 - 1]; }
+          nbRp[n1] = v; nbDoa[2 * n1] = th[k]; nbDoa[2 * n1 + 1] = 0.0; break;
+        }
+    }
+    const float2* y = Yh.data() + (size_t) t * F;
+    for (int f = fmin; f <= fmax; f++) {                              // the last unit's bins and their conjugate mirror (:3166-3176)
+      vec[2 * f] = y[f].x; vec[2 * f + 1] = y[f].y;
+      if (f > 0 && f < M / 2) { vec[2 * (M - f)] = y[f].x; vec[2 * (M - f) + 1] = -(double) y[f].y; }   // bin 0's mirror would be index M: not written
+    }
+    return vec.data();
+  }
+  void range(int& fmin, int& fmax) { dsr_status st = dsr_doa_frequency_range(doa, &fmin, &fmax); if (st) throw Error(st, "%s", dsr_last_error()); }
+};
+
 struct OrthOp : dsr_stream {         // SubbandOrthogonalizer(beamformer, outChanX) (beamformer.cc:2817-2849): ups[0] = the SubbandMVDRGSC operator
   int outChanX = 0; DevBuf<float2> Z;
   void compute() override {
@@ -596,6 +671,50 @@ dsr_status dsr_subband_mmi_stream_create(dsr_mmi* weights, int fftLen, const cha
   return guard([&] {
     if (!weights || !out) throw Error(DSR_E_PARAMETER, "null argument");
     MmiOp* s = mk<MmiOp>(name, "SubbandMMI", fftLen, DSR_T_COMPLEX); s->w = nullptr; s->mm = weights; s->M = fftLen; s->checkOrder = false; *out = s;
+  });
+}
+dsr_status dsr_doa_stream_create(dsr_doa* doa, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    if (!doa || !out) throw Error(DSR_E_PARAMETER, "null argument");
+    DoaOp* s = mk<DoaOp>(name, "DOAEstimatorSRPDSBLAPtr", dsr_doa_fft_len(doa), DSR_T_COMPLEX); s->w = nullptr; s->doa = doa; s->M = dsr_doa_fft_len(doa);
+    s->checkOrder = false; *out = s;
+  });
+}
+dsr_status dsr_doa_stream_get(dsr_stream* s, int what, double* out, size_t outDoubles, size_t* n)
+{
+  return guard([&] {
+    DoaOp* q = dynamic_cast<DoaOp*>(s); if (!q || !out || !n) throw Error(DSR_E_PARAMETER, "not a DOAEstimatorSRPDSBLA");
+    if (q->nbRp.empty()) q->reset_nbest();
+    const std::vector<double> e(1, (double) q->energy);
+    const std::vector<double> none;                          // setSearchParam freed _accRPs and _rpMat until the next table (:2962-2984)
+    const bool live = q->haveAcc && dsr_doa_has_table(q->doa) && q->seenGen == dsr_doa_table_generation(q->doa);
+    const std::vector<double>& v = what == 0 ? q->nbRp : what == 1 ? q->nbDoa : what == 2 ? (live ? q->rpMat : none) : what == 3 ? (live ? q->acc : none) : e;
+    if (what < 0 || what > 4) throw Error(DSR_E_PARAMETER, "what %d", what);
+    if (outDoubles < v.size()) throw Error(DSR_E_DIMENSION, "output holds %zu doubles, %zu needed", outDoubles, v.size());
+    std::copy(v.begin(), v.end(), out); *n = v.size();
+  });
+}
+dsr_status dsr_doa_stream_init_accs(dsr_stream* s)
+{
+  return guard([&] {                                        // _initAccs (:3027-3041)
+    DoaOp* q = dynamic_cast<DoaOp*>(s); if (!q) throw Error(DSR_E_PARAMETER, "not a DOAEstimatorSRPDSBLA");
+    std::fill(q->acc.begin(), q->acc.end(), 0.0); std::fill(q->rpMat.begin(), q->rpMat.end(), 0.0); q->reset_nbest();
+  });
+}
+dsr_status dsr_doa_stream_final_nbest(dsr_stream* s)
+{
+  return guard([&] {                                        // _getNBestHypothesesFromACCRP (:2986-3025): the DOA is (theta_k, _minPhi = 0)
+    DoaOp* q = dynamic_cast<DoaOp*>(s); if (!q) throw Error(DSR_E_PARAMETER, "not a DOAEstimatorSRPDSBLA");
+    if (!q->haveAcc || !dsr_doa_has_table(q->doa) || q->seenGen != dsr_doa_table_generation(q->doa))
+      throw Error(DSR_E_ERROR, "no accumulators: run the estimator after construction / setSearchParam first");
+    const int nB = dsr_doa_nbest(q->doa), nT = (int) q->acc.size();
+    std::vector<double> R(nB), th(nT); std::vector<int32_t> I(nB);
+    dsr_status st = dsr_doa_final_nbest(q->doa, q->acc.data(), 1, R.data(), I.data()); if (st) throw Error(st, "%s", dsr_last_error());
+    st = dsr_doa_thetas(q->doa, th.data(), nT); if (st) throw Error(st, "%s", dsr_last_error());
+    q->reset_nbest();
+    for (int n = 0; n < nB; n++) if (I[n] >= 0) { q->nbRp[n] = R[n]; q->nbDoa[2 * n] = th[I[n]]; q->nbDoa[2 * n + 1] = 0.0; }
+    q->rpMat = q->acc;
   });
 }
 dsr_status dsr_subband_orthogonalizer_create(dsr_stream* beamformer, int outChanX, const char* name, dsr_stream** out)

@@ -476,6 +476,78 @@ def wpe_multi(Y, fftLen, lowerN, upperN, iterationsN=2, loadDb=-20.0, bandWidth=
     return out, gn
 
 
+class DoaSRP:
+    """DOAEstimatorSRPDSBLA (btk/beamformer/beamformer.h:462-560, beamformer.cc:2920-3283) over a batch: settings and steering table on the
+    host, the response powers of X [U][C][T][M/2+1] on the fp64 MFMA (dsr_doa_srp).  The accumulators belong to the caller."""
+
+    def __init__(self, nBest, sampleRate, fftLen, chanN):
+        L = load(); self.h = vp(); self.nBest, self.M, self.C = nBest, fftLen, chanN
+        check(L.dsr_doa_create(int(nBest), int(sampleRate), int(fftLen), int(chanN), C.byref(self.h)))
+
+    def __del__(self):
+        if _lib is not None and getattr(self, "h", None):
+            _lib.dsr_doa_destroy(self.h)
+
+    def setArrayGeometry(self, positions):
+        p = _np(positions, np.float64).ravel()
+        check(_lib.dsr_doa_set_array_geometry(self.h, _ptr(p), p.size))
+
+    def setSearchParam(self, minTheta=-np.pi / 2, maxTheta=np.pi / 2, widthTheta=0.1):
+        check(_lib.dsr_doa_set_search_param(self.h, float(minTheta), float(maxTheta), float(widthTheta)))
+
+    def setFrequencyRange(self, fbinMin, fbinMax):
+        check(_lib.dsr_doa_set_frequency_range(self.h, int(fbinMin), int(fbinMax)))
+
+    def frequencyRange(self):
+        a, b = C.c_int(), C.c_int(); check(_lib.dsr_doa_frequency_range(self.h, C.byref(a), C.byref(b))); return a.value, b.value
+
+    def setEnergyThreshold(self, threshold):
+        check(_lib.dsr_doa_set_energy_threshold(self.h, float(threshold)))
+
+    def thetaN(self):
+        n = C.c_int(); check(_lib.dsr_doa_theta_n(self.h, C.byref(n))); return n.value
+
+    def thetas(self):
+        n = self.thetaN(); out = np.zeros(n, np.float64); check(_lib.dsr_doa_thetas(self.h, _ptr(out), n)); return out
+
+    def lookDelays(self, theta):
+        out = np.zeros(self.C, np.float64); check(_lib.dsr_doa_look_delays(self.h, float(theta), _ptr(out))); return out
+
+    def steering(self, thetaX):
+        out = np.zeros((self.M // 2 + 1, self.C), np.complex128)
+        check(_lib.dsr_doa_steering(self.h, int(thetaX), _ptr(out), out.size * 2)); return out
+
+    def srp(self, X, nframes=None, acc=None, want_rp=False, want_y=False):
+        """X cuda complex64 [U][C][T][M/2+1] -> dict(energy [U][T] f32, nbest_rp [U][T][nBest] f64, nbest_idx [U][T][nBest] i32, gated [U][T] i32,
+        acc [U][nTheta] f64 (the one passed in, added to), rp [U][T][nTheta] f64 and y [U][T][M/2+1] complex64 on request).  Frames past
+        nframes[u] keep the zeros they start with."""
+        import torch
+        U, Cn, T, F = X.shape
+        dev = X.device; nT = self.thetaN()
+        if nframes is None:
+            nframes = torch.full((U,), T, dtype=torch.int32, device=dev)
+        if acc is None:
+            acc = torch.zeros((U, nT), dtype=torch.float64, device=dev)
+        elif tuple(acc.shape) != (U, nT) or acc.dtype != torch.float64 or not acc.is_contiguous():
+            raise ValueError("acc: contiguous float64 [U][nTheta] expected")
+        r = dict(energy=torch.zeros((U, T), dtype=torch.float32, device=dev), nbest_rp=torch.zeros((U, T, self.nBest), dtype=torch.float64, device=dev),
+                 nbest_idx=torch.zeros((U, T, self.nBest), dtype=torch.int32, device=dev), gated=torch.zeros((U, T), dtype=torch.int32, device=dev), acc=acc)
+        r["rp"] = torch.zeros((U, T, nT), dtype=torch.float64, device=dev) if want_rp else None
+        r["y"] = torch.zeros((U, T, F), dtype=torch.complex64, device=dev) if want_y else None
+        Xc = torch.view_as_real(X.contiguous())
+        check(_lib.dsr_doa_srp(self.h, _dev(Xc), _dev(nframes), U, T, _dev(r["energy"]), _dev(r["rp"]) if want_rp else None, _dev(r["nbest_rp"]),
+                               _dev(r["nbest_idx"]), _dev(acc), _dev(r["y"]) if want_y else None, _dev(r["gated"]), cur_stream()))
+        return r
+
+    def finalNBest(self, acc):
+        """getFinalNBestHypotheses for each row of acc [U][nTheta] (host or device) -> (rp [U][nBest], theta index [U][nBest], -1 = empty)"""
+        a = np.ascontiguousarray(acc.detach().cpu().numpy() if hasattr(acc, "detach") else acc, np.float64)
+        a = a.reshape(-1, a.shape[-1]); U = a.shape[0]
+        R = np.zeros((U, self.nBest), np.float64); I = np.zeros((U, self.nBest), np.int32)
+        check(_lib.dsr_doa_final_nbest(self.h, _ptr(a), U, _ptr(R), _ptr(I)))
+        return R, I
+
+
 class ZelinskiPostFilter:
     """Zelinski post-filter (postfilter.cc:8-221,350-493); manifold [M/2+1][C] complex = arrayManifold() (or wq() with type | 8)."""
 

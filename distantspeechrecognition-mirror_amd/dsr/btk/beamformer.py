@@ -1,4 +1,7 @@
-"""btk.beamformer: SubbandDSPtr / SubbandGSCPtr / SubbandGSCRLSPtr / SubbandMMIPtr / SubbandMVDRPtr (beamformer.i:227-323) as streams."""
+"""btk.beamformer: SubbandDSPtr / SubbandGSCPtr / SubbandGSCRLSPtr / SubbandMMIPtr / SubbandMVDRPtr (beamformer.i:227-323) and
+DOAEstimatorSRPDSBLAPtr (beamformer.i:479-513) as streams."""
+import ctypes as C
+
 import numpy as np
 
 from .. import _capi as K
@@ -188,3 +191,92 @@ class SubbandOrthogonalizerPtr(FeatureStreamPtr):
         beamformer._weights()
         h, _ = _new(lib().dsr_subband_orthogonalizer_create, beamformer._h, int(outChanX), nm.encode())
         FeatureStreamPtr.__init__(self, h, keep=(beamformer,))
+
+
+class DOAEstimatorSRPDSBLAPtr(FeatureStreamPtr):
+    """beamformer.i:479-513 (DOAEstimatorSRPDSBLA, beamformer.cc:2920-3283): steered-response-power DOA estimation on a linear array.
+    setChannel(analysis stream) per channel, setArrayGeometry(x positions), then iterate: next() returns the last search direction's
+    delay-and-sum frame; getNBestRPs / getNBestDOAs / getEnergy / getResponsePowerMatrix describe the frame just returned,
+    getFinalNBestHypotheses ranks the accumulated powers.  The constructor searches (-pi/2, pi/2, 0.1); setSearchParam() without
+    arguments (0, pi/2, 0.1), as the two defaults of the reference differ."""
+
+    def __init__(self, nBest, sampleRate, fftLen, nm="DOAEstimatorSRPDSBLAPtr"):
+        self._nBest, self._fs, self._fftLen, self._nm = nBest, sampleRate, fftLen, nm
+        self._chans = []; self._est = None; self._set = []; FeatureStreamPtr.__init__(self, None)
+
+    def _estimator(self):
+        if self._est is None:
+            self._est = K.DoaSRP(self._nBest, self._fs, self._fftLen, len(self._chans))
+            for fn, args in self._set:
+                getattr(self._est, fn)(*args)
+            h, _ = _new(lib().dsr_doa_stream_create, self._est.h, self._nm.encode()); self._h = h
+            for c in self._chans:
+                K.check(lib().dsr_subband_bf_set_channel(self._h, c._h))
+        return self._est
+
+    def _apply(self, fn, *args):
+        if self._est is None:
+            self._set.append((fn, args))
+        else:
+            getattr(self._est, fn)(*args)
+
+    def setChannel(self, chan):
+        if self._est is not None:
+            raise K.DsrError(5, "channels must be set before the first frame")
+        self._chans.append(chan)
+
+    def chanN(self):
+        return len(self._chans)
+
+    def setArrayGeometry(self, positions):
+        self._apply("setArrayGeometry", np.array(positions, np.float64))
+
+    def setSearchParam(self, minTheta=0.0, maxTheta=np.pi / 2, widthTheta=0.1):
+        self._apply("setSearchParam", minTheta, maxTheta, widthTheta)
+
+    def setFrequencyRange(self, fbinMin, fbinMax):
+        self._apply("setFrequencyRange", fbinMin, fbinMax)
+
+    def setEnergyThreshold(self, engeryThreshold):
+        self._apply("setEnergyThreshold", engeryThreshold)
+
+    def _get(self, what, n):
+        self._estimator()
+        out = np.zeros(max(n, 1), np.float64); got = C.c_size_t()
+        K.check(lib().dsr_doa_stream_get(self._h, what, K._ptr(out), out.size, C.byref(got)))
+        return out[:got.value]
+
+    def getNBestRPs(self):
+        return self._get(0, self._nBest)
+
+    def getNBestDOAs(self):
+        return self._get(1, 2 * self._nBest).reshape(self._nBest, 2)
+
+    def getEnergy(self):
+        return float(np.float32(self._get(4, 1)[0]))
+
+    def getResponsePowerMatrix(self):
+        """[nTheta][1]: the last ungated frame's response powers (the accumulators after getFinalNBestHypotheses); None before the first frame"""
+        v = self._get(2, self._estimator().thetaN())
+        return v.reshape(-1, 1) if v.size else None
+
+    def getAccumulators(self):
+        return self._get(3, self._estimator().thetaN())
+
+    def getFinalNBestHypotheses(self):
+        self._estimator(); K.check(lib().dsr_doa_stream_final_nbest(self._h))
+
+    def initAccs(self):
+        self._estimator(); K.check(lib().dsr_doa_stream_init_accs(self._h))
+
+    def reset(self):
+        self._estimator(); FeatureStreamPtr.reset(self)
+
+    def next(self, frameX=-5):
+        self._estimator()
+        return FeatureStreamPtr.next(self, frameX)
+
+    __next__ = next
+
+    def __iter__(self):
+        self.reset(); return self

@@ -190,6 +190,62 @@ dsr_status dsr_bf_apply(dsr_bf*, const float* X_dev, int U, int Tmax, float* Y_d
 dsr_status dsr_bf_apply_frames(dsr_bf*, const float* X_dev, const int32_t* nframes_dev, int U, int Tmax, float* Y_dev, void* stream);
 
 /* =====================================================================================
+ * 2b. Steered-response-power direction of arrival for a linear array
+ *     replaces DOAEstimatorSRPDSBLA (btk/beamformer/beamformer.h:462-560, beamformer.i:479-513,
+ *     beamformer.cc:2920-3283)
+ * The handle holds the estimator's settings and its steering table; the accumulators are the caller's.  The table is built by the
+ * first use after create / set_search_param (_calcSteeringUnitTable :3105-3152) with the geometry and frequency range of that moment
+ * and kept until the next set_search_param, as in the reference: later geometry or range changes do not rebuild it.  Table work is
+ * host-side and needs no GPU.  Defaults: search (-pi/2, pi/2, 0.1) (the constructor's setSearchParam, beamformer.h:531), range
+ * [1, fftLen/2], threshold 0.  Deviations: where the reference reads out of bounds (fewer positions than channels, fbinMax beyond
+ * the table or fftLen/2) the call fails with DSR_E_DIMENSION; a missing geometry is DSR_E_ERROR; widthTheta <= 0, an empty grid
+ * or nBest < 1 are DSR_E_PARAMETER.
+ * ===================================================================================== */
+typedef struct dsr_doa dsr_doa;
+/* DOAEstimatorSRPDSBLA(nBest, sampleRate, fftLen) (beamformer.cc:3078-3086) over chanN channels (chanN <= 128) */
+dsr_status dsr_doa_create(int nBest, int sampleRate, int fftLen, int chanN, dsr_doa** out);
+void       dsr_doa_destroy(dsr_doa*);
+int        dsr_doa_nbest(const dsr_doa*);
+int        dsr_doa_chan_n(const dsr_doa*);
+int        dsr_doa_fft_len(const dsr_doa*);
+/* how many times the steering table was built (each build zeroes the reference's accumulators, :3128-3130); has_table: 1 while one is built */
+unsigned   dsr_doa_table_generation(const dsr_doa*);
+int        dsr_doa_has_table(const dsr_doa*);
+/* setArrayGeometry(positions) (:3094-3103): n x coordinates; only x is used, through |x_c - x_0| (in seconds of travel: no speed of sound) */
+dsr_status dsr_doa_set_array_geometry(dsr_doa*, const double* positions, int n);
+/* setSearchParam(minTheta, maxTheta, widthTheta) (beamformer.h:531-547): swapped when minTheta > maxTheta; clears the table */
+dsr_status dsr_doa_set_search_param(dsr_doa*, double minTheta, double maxTheta, double widthTheta);
+/* setFrequencyRange(fbinMin, fbinMax) (beamformer.h:529) */
+dsr_status dsr_doa_set_frequency_range(dsr_doa*, int fbinMin, int fbinMax);
+dsr_status dsr_doa_frequency_range(const dsr_doa*, int* fbinMin, int* fbinMax);
+/* setEnergyThreshold(threshold) (beamformer.h:525-527): frames whose energy is below it are not accumulated */
+dsr_status dsr_doa_set_energy_threshold(dsr_doa*, float threshold);
+float      dsr_doa_energy_threshold(const dsr_doa*);
+/* the grid: n = (unsigned)((maxTheta - minTheta) / widthTheta + 0.5) directions (:3113), theta_k accumulated as theta += widthTheta */
+dsr_status dsr_doa_theta_n(dsr_doa*, int* n);
+dsr_status dsr_doa_thetas(dsr_doa*, double* out, int n);
+/* setLookDirection's delays for theta (:3257-3271): delays[chanN], feed them to dsr_bf_calc_array_manifold to steer a beamformer there */
+dsr_status dsr_doa_look_delays(dsr_doa*, double theta, double* delays);
+/* build the steering table now (the SRP call and dsr_doa_steering build it when needed) */
+dsr_status dsr_doa_build_table(dsr_doa*);
+/* steering weights of direction thetaX: out [fftLen/2+1][chanN] complex128 = wq_f for the table's bins, (1, 0) at bin 0 unless the table was
+   built with fbinMin = 0, zero elsewhere (:3138-3146) */
+dsr_status dsr_doa_steering(dsr_doa*, int thetaX, double* out, size_t outDoubles);
+/* next() over a batch (:3188-3245).  X_dev [U][chanN][Tmax][fftLen/2+1] complex64, nframes_dev [U]; per frame t < nframes[u]:
+ *   energy_dev [U][Tmax] float: calcEnergy (:3043-3074), the reference's float accumulation bit for bit
+ *   rp_dev (optional) [U][Tmax][nTheta] double: the response power of every direction, written for gated frames too
+ *   nbest_rp_dev [U][Tmax][nBest] double, nbest_idx_dev [U][Tmax][nBest] int32: the frame's N-best (theta index, -1 = empty rank with rp -10e10;
+ *                the reference reports theta_k and 0 as its DOA); all empty when the frame is gated
+ *   acc_dev [U][nTheta] double: the caller's accumulators, ADDED to with the rp of every ungated frame (carry them from block to block)
+ *   Y_dev (optional) [U][Tmax][fftLen/2+1] complex64: the last direction's beamformed bins fbinMin..fbinMax (the reference's _vector)
+ *   gated_dev (optional) [U][Tmax] int32: 1 where energy < threshold
+ * Frames from nframes[u] on are not touched. */
+dsr_status dsr_doa_srp(dsr_doa*, const float* X_dev, const int32_t* nframes_dev, int U, int Tmax, float* energy_dev, double* rp_dev,
+                       double* nbest_rp_dev, int32_t* nbest_idx_dev, double* acc_dev, float* Y_dev, int32_t* gated_dev, void* stream);
+/* getFinalNBestHypotheses (:2986-3025) for U utterances: acc [U][nTheta] host -> nbest_rp [U][nBest], nbest_idx [U][nBest] host (DOA = (theta_k, 0)) */
+dsr_status dsr_doa_final_nbest(dsr_doa*, const double* acc, int U, double* nbest_rp, int32_t* nbest_idx);
+
+/* =====================================================================================
  * 3. MFCC feature chain
  *    replaces SampleFeature(block framing) -> PreemphasisFeature -> HammingFeature -> FFTFeature ->
  *    SpectralPowerFeature -> VTLNFeature -> MelFeature -> LogFeature -> CepstralFeature ->
@@ -707,6 +763,15 @@ dsr_status dsr_subband_mmi_stream_create(dsr_mmi* weights, int fftLen, const cha
  * outChanX <= 0: the beamformer's output; > 0: column outChanX-1 of the blocking matrices applied to the same snapshots (bins above M/2 as the
  * reference leaves them: the beamformer output's mirror) */
 dsr_status dsr_subband_orthogonalizer_create(dsr_stream* beamformer, int outChanX, const char* name, dsr_stream** out);
+/* DOAEstimatorSRPDSBLA as a stream (beamformer.i:479-513) over a dsr_doa handle (not owned): channels through dsr_subband_bf_set_channel; next()
+ * returns the last direction's beamformed frame, the previous frame's where the energy gate held (bins outside [fbinMin, fbinMax] are never
+ * written).  The accumulators survive reset() and are zeroed by a new steering table (after setSearchParam) and by init_accs.
+ *   get: what 0 getNBestRPs [nBest], 1 getNBestDOAs [nBest][2], 2 getResponsePowerMatrix [nTheta][1], 3 the accumulators [nTheta],
+ *        4 getEnergy [1]; *n = the count written (0 before the first frame for 2 and 3) */
+dsr_status dsr_doa_stream_create(dsr_doa* doa, const char* name, dsr_stream** out);
+dsr_status dsr_doa_stream_get(dsr_stream* s, int what, double* out, size_t outDoubles, size_t* n);
+dsr_status dsr_doa_stream_init_accs(dsr_stream* s);
+dsr_status dsr_doa_stream_final_nbest(dsr_stream* s);
 dsr_status dsr_preemphasis_create(dsr_stream* samp, double mu, const char* name, dsr_stream** out);
 dsr_status dsr_hamming_create(dsr_stream* samp, const char* name, dsr_stream** out);
 dsr_status dsr_fft_create(dsr_stream* samp, int fftLen, const char* name, dsr_stream** out);

@@ -19,7 +19,7 @@
 //   k_doa_acc    acc[u][theta] += rp of every ungated frame, frame by frame in order (caller-owned: block streaming carries it)
 // v_mfma_f64_16x16x4_f64 lane map: lane l holds A[l & 15][k = l >> 4] and B[k = l >> 4][l & 15]; result register q of lane l is
 // C[(l >> 4) + 4 q][l & 15] (tools/probes/probe_f64_mfma.hip).
-#include "common.h"
+#include "srp_common.h"
 #include <algorithm>
 #include <cmath>
 #include <complex>
@@ -28,27 +28,7 @@ using namespace dsr;
 
 typedef std::complex<double> zc;
 
-struct dsr_doa {
-  int nBest = 1, M = 0, C = 0; unsigned sampleRate = 16000;
-  std::vector<double> pos;                                   // setArrayGeometry: the x coordinates
-  double minTheta = -M_PI / 2, maxTheta = M_PI / 2, widthTheta = 0.1;   // the constructor's setSearchParam() (beamformer.h:531)
-  int fbinMin = 1, fbinMax = 0; float threshold = 0.0f;
-  // the steering table as built by the first use after construction / setSearchParam (the reference keeps it until then)
-  bool tbl = false; unsigned tableGen = 0; int nTheta = 0, tblFbinMax = 0;
-  std::vector<double> thetas; std::vector<zc> W;             // W [tblFbinMax+1][nTheta][C]
-  DevBuf<double2> dW; bool dDirty = true; int NT = 0, KS = 0;
-  PerStream<DevBuf<double>> ws;                              // rp when the caller does not ask for it
-};
-
 namespace {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ d4 mfma64(double a, double b, d4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ void cmfma(double ar, double ai, double br, double bi, d4& cr, d4& ci)
-{
-  cr = mfma64(ar, br, cr); cr = mfma64(-ai, bi, cr); ci = mfma64(ar, bi, ci); ci = mfma64(ai, br, ci);
-}
 
 constexpr int FB = 64;                                       // frames per workgroup (16 per wave)
 #ifndef DOA_LDS_ROWS
@@ -92,14 +72,7 @@ __global__ __launch_bounds__(256) void k_doa_srp(const float2* __restrict__ X, c
       xs[(c * FB + t) * BP + b] = v;
     }
     __syncthreads();
-    if (doEnergy) {                                          // calcEnergy (:3043-3074): rp += g_f |zdotc(X_f, X_f)|^2 in a float
-      for (int b = 0; b < nb; b++) {
-        double s = 0.0;
-        for (int c = 0; c < C; c++) { const float2 v = xs[(c * FB + threadIdx.x) * BP + b]; const double a = v.x, q = v.y; s = s + (a * a + q * q); }
-        const double g = f0 + b < M2 ? 2.0 : 1.0;
-        e = (float) ((double) e + g * (s * s));           // the imaginary part of x^H x is exactly 0
-      }
-    }
+    if (doEnergy) e = srp_energy_chunk(xs, C, FB, BP, threadIdx.x, f0, nb, M2, e);   // calcEnergy (:3043-3074)
     for (int b = 0; b < nb; b++) {
       const int f = f0 + b;
       const double g = f < M2 ? 2.0 : 1.0;
@@ -151,7 +124,7 @@ __global__ __launch_bounds__(256) void k_doa_srp(const float2* __restrict__ X, c
       if (r < nTheta && tw < N) rpOut[((long) u * Tmax + tw) * nTheta + r] = rp[tg][q] / nbins;
     }
   }
-  if (doEnergy && t0 + (int) threadIdx.x < N) energy[(long) u * Tmax + t0 + threadIdx.x] = e / (float) (2u * (unsigned) M2 * (unsigned) C);
+  if (doEnergy && t0 + (int) threadIdx.x < N) energy[(long) u * Tmax + t0 + threadIdx.x] = srp_energy_final(e, M2, C);
 }
 
 // per frame: gate + N-best of the frame (DOAEstimatorSRPDSBLA::next :3188-3245); nbIdx -1 = an empty rank (rp -10e10, DOA (-pi, -pi))
@@ -277,6 +250,25 @@ void launch_srp(const dsr_doa& s, const float* X, const int* nf, int U, int Tmax
 
 }  // namespace
 
+namespace dsr {
+
+void doa_launch_rp(dsr_doa& s, const float* X, const int* nf, int U, int Tmax, double* rp, float* en, float* Y, hipStream_t st)
+{
+  upload_table(s, st);
+  const int ng = s.NT;
+  if (ng >= 4) launch_srp<4>(s, X, nf, U, Tmax, rp, en, Y, st);
+  else if (ng >= 2) launch_srp<2>(s, X, nf, U, Tmax, rp, en, Y, st);
+  else launch_srp<1>(s, X, nf, U, Tmax, rp, en, Y, st);
+}
+
+void doa_launch_acc(const double* rp, const float* en, const int* nf, int U, int Tmax, int nUnits, float thr, double* acc, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_doa_acc, dim3(cdiv((long) U * nUnits, 256)), dim3(256), 0, st, rp, en, nf, U, Tmax, nUnits, thr, acc);
+  DSR_HIP(hipGetLastError());
+}
+
+}  // namespace dsr
+
 extern "C" {
 
 dsr_status dsr_doa_create(int nBest, int sampleRate, int fftLen, int chanN, dsr_doa** out)
@@ -377,19 +369,14 @@ dsr_status dsr_doa_srp(dsr_doa* s, const float* X_dev, const int32_t* nframes_de
     require_device();
     if (U == 0 || Tmax == 0) return;
     hipStream_t st = (hipStream_t) stream;
-    upload_table(*s, st);
     double* rp = rp_dev;
     if (!rp) { DevBuf<double>& w = s->ws.at(st); w.reserve((size_t) U * Tmax * s->nTheta); rp = w.p; }
-    const int ng = s->NT;
-    if (ng >= 4) launch_srp<4>(*s, X_dev, nframes_dev, U, Tmax, rp, energy_dev, Y_dev, st);
-    else if (ng >= 2) launch_srp<2>(*s, X_dev, nframes_dev, U, Tmax, rp, energy_dev, Y_dev, st);
-    else launch_srp<1>(*s, X_dev, nframes_dev, U, Tmax, rp, energy_dev, Y_dev, st);
+    doa_launch_rp(*s, X_dev, nframes_dev, U, Tmax, rp, energy_dev, Y_dev, st);
     const long nfT = (long) U * Tmax;
     hipLaunchKernelGGL(k_doa_frame, dim3(cdiv(nfT, 256)), dim3(256), 0, st, rp, energy_dev, nframes_dev, U, Tmax, s->nTheta, s->nBest, s->threshold,
                        nbest_rp_dev, nbest_idx_dev, gated_dev);
     DSR_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_doa_acc, dim3(cdiv((long) U * s->nTheta, 256)), dim3(256), 0, st, rp, energy_dev, nframes_dev, U, Tmax, s->nTheta, s->threshold, acc_dev);
-    DSR_HIP(hipGetLastError());
+    doa_launch_acc(rp, energy_dev, nframes_dev, U, Tmax, s->nTheta, s->threshold, acc_dev, st);
   });
 }
 

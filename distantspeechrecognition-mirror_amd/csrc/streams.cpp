@@ -301,6 +301,126 @@ struct DoaOp : BfOp {                // DOAEstimatorSRPDSBLA as a stream (beamfo
   void range(int& fmin, int& fmax) { dsr_status st = dsr_doa_frequency_range(doa, &fmin, &fmax); if (st) throw Error(st, "%s", dsr_last_error()); }
 };
 
+struct SphBfOp : BfOp {              // EigenBeamformer / SphericalDSBeamformer as a stream (modalBeamformer.cc:347-399)
+  // the utterance is materialised at the first pull; a geometry, look-direction, sigma2 or gain change since (the handle's settings generation)
+  // recomputes it at the next pull, the frame counter kept.  The eigenbeams (getSnapShotArray) are computed on the device only when asked for.
+  dsr_sph* sph = nullptr; int T = 0, F = 0, dim = 0; DevBuf<int> nf; DevBuf<float2> dF, dYs; unsigned setGen = ~0u; bool eigenDone = false;
+  int eigenFrame = -1; bool eigenRange = false; int eigenLo = 0, eigenHi = 0;
+  void pack() {                       // X [C][T][F] of the channels' frames
+    const int C = (int) ups.size();
+    if (C == 0 || C != dsr_sph_chan_n(sph)) throw Error(DSR_E_DIMENSION, "Number of channels (%d) does not match the beamformer (%d)", C, dsr_sph_chan_n(sph));
+    T = ups[0]->nFrames; for (int c = 1; c < C; c++) if (ups[c]->nFrames < T) T = ups[c]->nFrames;
+    F = M / 2 + 1; dim = dsr_sph_dim(sph); eigenDone = false; setGen = dsr_sph_settings_generation(sph);
+    if (T <= 0) return;
+    X.reserve((size_t) C * T * F);
+    for (int c = 0; c < C; c++) op_pack_bins(ups[c]->d<double2>(), T, F, M, X.p + (size_t) c * T * F, S0);
+    nf.upload(&T, 1);
+  }
+  void compute() override {
+    pack(); alloc(T); if (T <= 0) return;
+    Y.reserve((size_t) T * F);
+    dsr_status st = dsr_sph_apply(sph, (const float*) X.p, nf.p, 1, T, (float*) Y.p, nullptr, S0); if (st) throw Error(st, "%s", dsr_last_error());
+    op_expand_bins(Y.p, T, F, M, d<double2>(), S0);
+  }
+  bool settings_moved() const { return ready && setGen != dsr_sph_settings_generation(sph); }
+  const void* next(int fx) override {
+    if (!(fx == frameX && frameX >= 0) && settings_moved()) ready = false;
+    const void* r = BfOp::next(fx); eigenFrame = frameX; return r;
+  }
+  void eigenbeams(double* out) {                            // the current frame's F [F][dim] (zero before the first frame; the DOA op: its range only)
+    std::vector<float2> fr((size_t) F * dim, make_float2(0.f, 0.f));
+    if (eigenFrame >= 0 && eigenFrame < T) {
+      if (!eigenDone) {
+        dF.reserve((size_t) T * F * dim); dYs.reserve((size_t) T * F);
+        dsr_status st = dsr_sph_apply(sph, (const float*) X.p, nf.p, 1, T, (float*) dYs.p, (float*) dF.p, S0); if (st) throw Error(st, "%s", dsr_last_error());
+        eigenDone = true;
+      }
+      DSR_HIP(hipMemcpy(fr.data(), dF.p + (size_t) eigenFrame * F * dim, sizeof(float2) * fr.size(), hipMemcpyDeviceToHost));
+    }
+    for (int f = 0; f < F; f++)
+      for (int d = 0; d < dim; d++) {
+        const bool have = !eigenRange || (f >= eigenLo && f <= eigenHi);
+        const float2 v = have ? fr[(size_t) f * dim + d] : make_float2(0.f, 0.f);
+        out[((size_t) f * dim + d) * 2] = v.x; out[((size_t) f * dim + d) * 2 + 1] = v.y;
+      }
+  }
+};
+
+struct SphDoaOp : SphBfOp {          // DOAEstimatorSRPEB / DOAEstimatorSRPSphDSB as a stream (modalBeamformer.cc:860-950, :1284-1370)
+  unsigned gen = 0, seenGen = ~0u; int nU = 0, nT = 0, nP = 0;
+  std::vector<float> E; std::vector<double> RP; std::vector<float2> Yh;              // the materialised utterance: energy, rp, last unit's bins
+  std::vector<double> acc, rpMat, nbRp, nbDoa, vec, gth, gph; float energy = 0.f; bool haveAcc = false;
+  DevBuf<float> dE; DevBuf<double> dRP, dAcc, dNbR; DevBuf<int> dNbI; DevBuf<float2> dY; int rangeUsed[2] = {-1, -1};
+  void compute() override {
+    const int C = (int) ups.size();
+    if (C == 0 || C != dsr_sph_chan_n(sph)) throw Error(DSR_E_DIMENSION, "Number of channels (%d) does not match the estimator (%d)", C, dsr_sph_chan_n(sph));
+    range(rangeUsed[0], rangeUsed[1]);
+    dsr_status st = dsr_sph_build_table(sph); if (st) throw Error(st, "%s", dsr_last_error());
+    st = dsr_sph_grid_n(sph, &nT, &nP); if (st) throw Error(st, "%s", dsr_last_error());
+    nU = nT * nP; gth.assign(nU, 0.0); gph.assign(nU, 0.0);
+    st = dsr_sph_grid(sph, gth.data(), gph.data(), nU); if (st) throw Error(st, "%s", dsr_last_error());
+    pack();                                                  // X packed; the eigenbeams only when getSnapShotArray asks
+    nFrames = T; eigenRange = true; eigenLo = rangeUsed[0]; eigenHi = rangeUsed[1];
+    if (T <= 0) return;
+    const int nB = dsr_sph_nbest(sph);
+    dY.reserve((size_t) T * F); dE.reserve(T); dRP.reserve((size_t) T * nU); dAcc.reserve(nU);
+    dNbR.reserve((size_t) T * nB); dNbI.reserve((size_t) T * nB);
+    DSR_HIP(hipMemsetAsync(dY.p, 0, sizeof(float2) * (size_t) T * F, S0)); DSR_HIP(hipMemsetAsync(dAcc.p, 0, sizeof(double) * nU, S0));
+    st = dsr_sph_srp(sph, (const float*) X.p, nf.p, 1, T, dE.p, dRP.p, dNbR.p, dNbI.p, dAcc.p, (float*) dY.p, nullptr, S0);
+    if (st) throw Error(st, "%s", dsr_last_error());
+    E.resize(T); RP.resize((size_t) T * nU); Yh.resize((size_t) T * F);
+    DSR_HIP(hipMemcpy(E.data(), dE.p, sizeof(float) * T, hipMemcpyDeviceToHost));
+    DSR_HIP(hipMemcpy(RP.data(), dRP.p, sizeof(double) * RP.size(), hipMemcpyDeviceToHost));
+    DSR_HIP(hipMemcpy(Yh.data(), dY.p, sizeof(float2) * Yh.size(), hipMemcpyDeviceToHost));
+  }
+  void sync_table() {                 // a new steering table: _accRPs and _rpMat start from zero (:818-820, allocDebugWorkSapce)
+    const unsigned g = dsr_sph_table_generation(sph);
+    if (g != seenGen) { acc.assign(nU, 0.0); rpMat.assign(nU, 0.0); haveAcc = true; seenGen = g; }
+  }
+  void reset_nbest() {
+    const int nB = dsr_sph_nbest(sph); nbRp.assign(nB, -10e10); nbDoa.assign((size_t) 2 * nB, -M_PI);
+  }
+  const void* next(int fx) override {
+    if (vec.empty()) vec.assign((size_t) 2 * M, 0.0);
+    if (fx == frameX && frameX >= 0) return vec.data();
+    reset_nbest();                                          // before anything else, the end of the stream included (:866-870)
+    int fmin = 0, fmax = 0; range(fmin, fmax);
+    if (ready && (gen != dsr_sph_table_generation(sph) || !dsr_sph_has_table(sph) || fmin != rangeUsed[0] || fmax != rangeUsed[1] || settings_moved()))
+      ready = false;                                        // setSearchParam (a new table), setFrequencyRange or a new geometry since: the rest of the utterance anew
+    if (!ready) {
+      require_device();
+      for (size_t i = 0; i < ups.size(); i++) ups[i]->materialize();
+      const int keep = eigenFrame; compute(); eigenFrame = keep; gen = dsr_sph_table_generation(sph); ready = true;
+    }
+    sync_table();
+    if (frameX + 1 >= nFrames) { endOfSamples = true; throw Error(DSR_E_ITERATOR, "end of samples!"); }
+    frameX++;
+    const int t = frameX;
+    energy = E[t];
+    if (energy < dsr_sph_energy_threshold(sph)) return vec.data();     // gated: no accumulation, no N-best, _vector and the eigenbeams as they were
+    eigenFrame = t;
+    const int nB = dsr_sph_nbest(sph);
+    const double* r = RP.data() + (size_t) t * nU;
+    for (int k = 0; k < nU; k++) {                                    // :922-946
+      const double v = r[k];
+      acc[k] += v; rpMat[k] = v;
+      if (!(v > nbRp[nB - 1])) continue;
+      for (int n1 = 0; n1 < nB; n1++)
+        if (v > nbRp[n1]) {
+          for (int n2 = nB - 1; n2 > n1; n2--) { nbRp[n2] = nbRp[n2 - 1]; nbDoa[2 * n2] = nbDoa[2 * n2 - 2]; nbDoa[2 * n2 + 1] = nbDoa[2 * n2 - 1]; }
+          nbRp[n1] = v; nbDoa[2 * n1] = gth[k]; nbDoa[2 * n1 + 1] = gph[k]; break;
+        }
+    }
+    const float2* y = Yh.data() + (size_t) t * F;
+    for (int f = fmin; f <= fmax; f++) {                              // the last unit's bins and their conjugate mirror (_calcResponsePower :874-889)
+      vec[2 * f] = y[f].x; vec[2 * f + 1] = y[f].y;
+      if (f > 0 && f < M / 2) { vec[2 * (M - f)] = y[f].x; vec[2 * (M - f) + 1] = -(double) y[f].y; }
+    }
+    return vec.data();
+  }
+  void range(int& fmin, int& fmax) { dsr_status st = dsr_sph_frequency_range(sph, &fmin, &fmax); if (st) throw Error(st, "%s", dsr_last_error()); }
+};
+
 struct OrthOp : dsr_stream {         // SubbandOrthogonalizer(beamformer, outChanX) (beamformer.cc:2817-2849): ups[0] = the SubbandMVDRGSC operator
   int outChanX = 0; DevBuf<float2> Z;
   void compute() override {
@@ -714,6 +834,69 @@ dsr_status dsr_doa_stream_final_nbest(dsr_stream* s)
     st = dsr_doa_thetas(q->doa, th.data(), nT); if (st) throw Error(st, "%s", dsr_last_error());
     q->reset_nbest();
     for (int n = 0; n < nB; n++) if (I[n] >= 0) { q->nbRp[n] = R[n]; q->nbDoa[2 * n] = th[I[n]]; q->nbDoa[2 * n + 1] = 0.0; }
+    q->rpMat = q->acc;
+  });
+}
+dsr_status dsr_sph_bf_stream_create(dsr_sph* sph, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    if (!sph || !out) throw Error(DSR_E_PARAMETER, "null argument");
+    const char* dflt = dsr_sph_kind(sph) == DSR_SPH_DS ? "SphericalDSBeamformer" : "EigenBeamformer";
+    SphBfOp* s = mk<SphBfOp>(name, dflt, dsr_sph_fft_len(sph), DSR_T_COMPLEX); s->w = nullptr; s->sph = sph; s->M = dsr_sph_fft_len(sph);
+    s->checkOrder = false; *out = s;
+  });
+}
+dsr_status dsr_sph_stream_get_eigenbeams(dsr_stream* s, double* out, size_t outDoubles, size_t* n)
+{
+  return guard([&] {
+    SphBfOp* q = dynamic_cast<SphBfOp*>(s); if (!q || !out || !n) throw Error(DSR_E_PARAMETER, "not a spherical beamformer stream");
+    if (q->F == 0) { q->F = q->M / 2 + 1; q->dim = dsr_sph_dim(q->sph); }
+    const size_t need = (size_t) q->F * q->dim * 2;
+    if (outDoubles < need) throw Error(DSR_E_DIMENSION, "output holds %zu doubles, %zu needed", outDoubles, need);
+    q->eigenbeams(out); *n = need;
+  });
+}
+dsr_status dsr_sph_doa_stream_create(dsr_sph* sph, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    if (!sph || !out) throw Error(DSR_E_PARAMETER, "null argument");
+    const char* dflt = "DirectionEstimatorSRPMB";               // both classes' default name (beamformer.i:539, :624)
+    SphDoaOp* s = mk<SphDoaOp>(name, dflt, dsr_sph_fft_len(sph), DSR_T_COMPLEX); s->w = nullptr; s->sph = sph; s->M = dsr_sph_fft_len(sph);
+    s->checkOrder = false; *out = s;
+  });
+}
+dsr_status dsr_sph_doa_stream_get(dsr_stream* s, int what, double* out, size_t outDoubles, size_t* n)
+{
+  return guard([&] {
+    SphDoaOp* q = dynamic_cast<SphDoaOp*>(s); if (!q || !out || !n) throw Error(DSR_E_PARAMETER, "not a spherical DOA estimator");
+    if (q->nbRp.empty()) q->reset_nbest();
+    const std::vector<double> e(1, (double) q->energy);
+    const std::vector<double> none;                          // setSearchParam freed _accRPs and _rpMat until the next table (clearTable)
+    const bool live = q->haveAcc && dsr_sph_has_table(q->sph) && q->seenGen == dsr_sph_table_generation(q->sph);
+    if (what < 0 || what > 4) throw Error(DSR_E_PARAMETER, "what %d", what);
+    const std::vector<double>& v = what == 0 ? q->nbRp : what == 1 ? q->nbDoa : what == 2 ? (live ? q->rpMat : none) : what == 3 ? (live ? q->acc : none) : e;
+    if (outDoubles < v.size()) throw Error(DSR_E_DIMENSION, "output holds %zu doubles, %zu needed", outDoubles, v.size());
+    std::copy(v.begin(), v.end(), out); *n = v.size();
+  });
+}
+dsr_status dsr_sph_doa_stream_init_accs(dsr_stream* s)
+{
+  return guard([&] {                                        // _initAccs (beamformer.cc:3027-3041)
+    SphDoaOp* q = dynamic_cast<SphDoaOp*>(s); if (!q) throw Error(DSR_E_PARAMETER, "not a spherical DOA estimator");
+    std::fill(q->acc.begin(), q->acc.end(), 0.0); std::fill(q->rpMat.begin(), q->rpMat.end(), 0.0); q->reset_nbest();
+  });
+}
+dsr_status dsr_sph_doa_stream_final_nbest(dsr_stream* s)
+{
+  return guard([&] {                                        // _getNBestHypothesesFromACCRP (beamformer.cc:2986-3025): the DOA is (theta, phi) of the unit
+    SphDoaOp* q = dynamic_cast<SphDoaOp*>(s); if (!q) throw Error(DSR_E_PARAMETER, "not a spherical DOA estimator");
+    if (!q->haveAcc || !dsr_sph_has_table(q->sph) || q->seenGen != dsr_sph_table_generation(q->sph))
+      throw Error(DSR_E_ERROR, "no accumulators: run the estimator after construction / setSearchParam first");
+    const int nB = dsr_sph_nbest(q->sph);
+    std::vector<double> R(nB); std::vector<int32_t> I(nB);
+    dsr_status st = dsr_sph_final_nbest(q->sph, q->acc.data(), 1, R.data(), I.data()); if (st) throw Error(st, "%s", dsr_last_error());
+    q->reset_nbest();
+    for (int n = 0; n < nB; n++) if (I[n] >= 0) { q->nbRp[n] = R[n]; q->nbDoa[2 * n] = q->gth[I[n]]; q->nbDoa[2 * n + 1] = q->gph[I[n]]; }
     q->rpMat = q->acc;
   });
 }

@@ -548,6 +548,144 @@ class DoaSRP:
         return R, I
 
 
+class _Sph:
+    """the dsr_sph handle (modalBeamformer.{h,cc}): kind "EB" (EigenBeamformer weights) or "DS" (SphericalDSBeamformer weights); settings,
+    geometry and tables on the host"""
+    KINDS = {"EB": 0, "DS": 1}
+
+    def __init__(self, kind, nBest, sampleRate, fftLen, chanN, maxOrder, normalizeWeight=False, halfBandShift=False, NC=1):
+        L = load(); self.h = vp(); self.nBest, self.M, self.C = nBest, fftLen, chanN
+        k = self.KINDS[kind] if isinstance(kind, str) else int(kind)
+        check(L.dsr_sph_create(k, int(nBest), int(sampleRate), int(fftLen), int(bool(halfBandShift)), int(NC), int(maxOrder), int(bool(normalizeWeight)),
+                               int(chanN), C.byref(self.h)))
+        self.dim = L.dsr_sph_dim(self.h)
+
+    def __del__(self):
+        if _lib is not None and getattr(self, "h", None):
+            _lib.dsr_sph_destroy(self.h)
+
+    def _table(self, fn, shape, *args):
+        out = np.zeros(shape, np.complex128); check(fn(self.h, *args, _ptr(out), out.size * 2)); return out
+
+    def setArrayGeometry(self, a, theta_s, phi_s):
+        t = _np(theta_s, np.float64).ravel(); p = _np(phi_s, np.float64).ravel()
+        if t.size != p.size:
+            raise DsrError(E_DIMENSION, "theta_s and phi_s differ in length")
+        check(_lib.dsr_sph_set_array_geometry(self.h, float(a), _ptr(t), _ptr(p), t.size))
+
+    def setEigenMikeGeometry(self):
+        check(_lib.dsr_sph_set_eigenmike_geometry(self.h))
+
+    def getArrayGeometry(self, type):
+        out = np.zeros(self.C, np.float64); check(_lib.dsr_sph_array_geometry(self.h, int(type), _ptr(out), self.C)); return out
+
+    def setLookDirection(self, theta, phi):
+        check(_lib.dsr_sph_set_look_direction(self.h, float(theta), float(phi)))
+
+    def setSigma2(self, sigma2):
+        check(_lib.dsr_sph_set_sigma2(self.h, float(sigma2)))
+
+    def setWeightGain(self, wgain):
+        check(_lib.dsr_sph_set_weight_gain(self.h, float(wgain)))
+
+    def modeAmplitudes(self):
+        return self._table(_lib.dsr_sph_mode_amplitudes, (self.M // 2 + 1, _lib.dsr_sph_max_order(self.h)))
+
+    def harmonics(self):
+        return self._table(_lib.dsr_sph_harmonics, (self.dim, self.C))
+
+    def lookWeights(self):
+        return self._table(_lib.dsr_sph_look_weights, (self.M // 2 + 1, self.dim))
+
+    def calcWNG(self):
+        out = np.zeros(self.M // 2 + 1, np.float64); check(_lib.dsr_sph_calc_wng(self.h, _ptr(out), out.size)); return out
+
+    def apply(self, X, nframes=None, want_F=False):
+        """X cuda complex64 [U][C][T][M/2+1] -> (y [U][T][M/2+1] complex64, F [U][T][M/2+1][dim] complex64 or None); frames past nframes[u] stay 0"""
+        import torch
+        U, Cn, T, F = X.shape
+        dev = X.device
+        if nframes is None:
+            nframes = torch.full((U,), T, dtype=torch.int32, device=dev)
+        y = torch.zeros((U, T, F), dtype=torch.complex64, device=dev)
+        Fo = torch.zeros((U, T, F, self.dim), dtype=torch.complex64, device=dev) if want_F else None
+        Xc = torch.view_as_real(X.contiguous())
+        check(_lib.dsr_sph_apply(self.h, _dev(Xc), _dev(nframes), U, T, _dev(y), _dev(Fo) if want_F else None, cur_stream()))
+        return y, Fo
+
+
+class SphBeamformer(_Sph):
+    """EigenBeamformer (kind "EB") / SphericalDSBeamformer (kind "DS") over a batch (dsr_sph_apply)"""
+
+    def __init__(self, kind, sampleRate, fftLen, chanN, maxOrder, normalizeWeight=False, halfBandShift=False, NC=1):
+        _Sph.__init__(self, kind, 1, sampleRate, fftLen, chanN, maxOrder, normalizeWeight, halfBandShift, NC)
+
+
+class SphDoaSRP(_Sph):
+    """DOAEstimatorSRPEB (kind "EB") / DOAEstimatorSRPSphDSB (kind "DS") over a batch: the (theta, phi) grid and steering table on the host, the
+    response powers of X [U][C][T][M/2+1] on the fp64 MFMA (dsr_sph_srp).  The accumulators belong to the caller."""
+
+    def setSearchParam(self, minTheta=0.0, maxTheta=np.pi, minPhi=-np.pi, maxPhi=np.pi, widthTheta=0.1, widthPhi=0.1):
+        check(_lib.dsr_sph_set_search_param(self.h, float(minTheta), float(maxTheta), float(minPhi), float(maxPhi), float(widthTheta), float(widthPhi)))
+
+    def setFrequencyRange(self, fbinMin, fbinMax):
+        check(_lib.dsr_sph_set_frequency_range(self.h, int(fbinMin), int(fbinMax)))
+
+    def frequencyRange(self):
+        a, b = C.c_int(), C.c_int(); check(_lib.dsr_sph_frequency_range(self.h, C.byref(a), C.byref(b))); return a.value, b.value
+
+    def setEnergyThreshold(self, threshold):
+        check(_lib.dsr_sph_set_energy_threshold(self.h, float(threshold)))
+
+    def gridN(self):
+        a, b = C.c_int(), C.c_int(); check(_lib.dsr_sph_grid_n(self.h, C.byref(a), C.byref(b))); return a.value, b.value
+
+    def grid(self):
+        """(theta [units], phi [units]), unit = iTheta nPhi + iPhi"""
+        nT, nP = self.gridN(); th = np.zeros(nT * nP); ph = np.zeros(nT * nP)
+        check(_lib.dsr_sph_grid(self.h, _ptr(th), _ptr(ph), nT * nP)); return th, ph
+
+    def units(self):
+        nT, nP = self.gridN(); return nT * nP
+
+    def steering(self, unit):
+        return self._table(_lib.dsr_sph_steering, (self.M // 2 + 1, self.dim), int(unit))
+
+    def path(self):
+        p = _lib.dsr_sph_srp_path(self.h)
+        if p < 0:
+            raise DsrError(1, (_lib.dsr_last_error() or b"").decode(errors="replace"))
+        return ("fused", "folded")[p]
+
+    def srp(self, X, nframes=None, acc=None, want_rp=False, want_y=False):
+        """as DoaSRP.srp, units in place of theta: dict(energy, nbest_rp, nbest_idx, gated, acc [U][units], rp, y)"""
+        import torch
+        U, Cn, T, F = X.shape
+        dev = X.device; nU = self.units()
+        if nframes is None:
+            nframes = torch.full((U,), T, dtype=torch.int32, device=dev)
+        if acc is None:
+            acc = torch.zeros((U, nU), dtype=torch.float64, device=dev)
+        elif tuple(acc.shape) != (U, nU) or acc.dtype != torch.float64 or not acc.is_contiguous():
+            raise ValueError("acc: contiguous float64 [U][units] expected")
+        r = dict(energy=torch.zeros((U, T), dtype=torch.float32, device=dev), nbest_rp=torch.zeros((U, T, self.nBest), dtype=torch.float64, device=dev),
+                 nbest_idx=torch.zeros((U, T, self.nBest), dtype=torch.int32, device=dev), gated=torch.zeros((U, T), dtype=torch.int32, device=dev), acc=acc)
+        r["rp"] = torch.zeros((U, T, nU), dtype=torch.float64, device=dev) if want_rp else None
+        r["y"] = torch.zeros((U, T, F), dtype=torch.complex64, device=dev) if want_y else None
+        Xc = torch.view_as_real(X.contiguous())
+        check(_lib.dsr_sph_srp(self.h, _dev(Xc), _dev(nframes), U, T, _dev(r["energy"]), _dev(r["rp"]) if want_rp else None, _dev(r["nbest_rp"]),
+                               _dev(r["nbest_idx"]), _dev(acc), _dev(r["y"]) if want_y else None, _dev(r["gated"]), cur_stream()))
+        return r
+
+    def finalNBest(self, acc):
+        """getFinalNBestHypotheses for each row of acc [U][units] -> (rp [U][nBest], unit index [U][nBest], -1 = empty)"""
+        a = np.ascontiguousarray(acc.detach().cpu().numpy() if hasattr(acc, "detach") else acc, np.float64)
+        a = a.reshape(-1, a.shape[-1]); U = a.shape[0]
+        R = np.zeros((U, self.nBest), np.float64); I = np.zeros((U, self.nBest), np.int32)
+        check(_lib.dsr_sph_final_nbest(self.h, _ptr(a), U, _ptr(R), _ptr(I)))
+        return R, I
+
+
 class ZelinskiPostFilter:
     """Zelinski post-filter (postfilter.cc:8-221,350-493); manifold [M/2+1][C] complex = arrayManifold() (or wq() with type | 8)."""
 

@@ -1,5 +1,6 @@
 """btk.beamformer: SubbandDSPtr / SubbandGSCPtr / SubbandGSCRLSPtr / SubbandMMIPtr / SubbandMVDRPtr (beamformer.i:227-323) and
-DOAEstimatorSRPDSBLAPtr (beamformer.i:479-513) as streams."""
+DOAEstimatorSRPDSBLAPtr (beamformer.i:479-513), EigenBeamformerPtr / SphericalDSBeamformerPtr / DOAEstimatorSRPEBPtr /
+DOAEstimatorSRPSphDSBPtr (beamformer.i:416-633) as streams."""
 import ctypes as C
 
 import numpy as np
@@ -280,3 +281,181 @@ class DOAEstimatorSRPDSBLAPtr(FeatureStreamPtr):
 
     def __iter__(self):
         self.reset(); return self
+
+
+class _Spherical(FeatureStreamPtr):
+    """the spherical-array family (modalBeamformer.{h,cc}) over one dsr_sph handle, made at the first frame once the channels are known;
+    settings made before that are replayed on it"""
+    _KIND, _DOA = "EB", False
+
+    def __init__(self, nBest, sampleRate, fftLen, halfBandShift, NC, maxOrder, normalizeWeight, nm):
+        if halfBandShift:
+            raise K.DsrError(K.E_PARAMETER, "_halfBandShift == true is not implemented yet")        # modalBeamformer.cc:391-394
+        self._args = (nBest, sampleRate, fftLen, NC, maxOrder, normalizeWeight)
+        self._fftLen, self._maxOrder, self._nBest, self._nm = fftLen, maxOrder, nBest, nm
+        self._chans = []; self._sph = None; self._set = []; FeatureStreamPtr.__init__(self, None)
+
+    def _handle(self):
+        if self._sph is None:
+            nBest, fs, M, NC, mo, nw = self._args
+            self._sph = (K.SphDoaSRP if self._DOA else K._Sph)(self._KIND, nBest, fs, M, len(self._chans), mo, nw, False, NC)
+            for fn, args in self._set:
+                getattr(self._sph, fn)(*args)
+            create = lib().dsr_sph_doa_stream_create if self._DOA else lib().dsr_sph_bf_stream_create
+            h, _ = _new(create, self._sph.h, self._nm.encode()); self._h = h
+            for c in self._chans:
+                K.check(lib().dsr_subband_bf_set_channel(self._h, c._h))
+        return self._sph
+
+    def _query(self):
+        """the handle for the geometry getters: before setChannel (the reference allows them once a geometry is set) a throw-away handle over
+        as many channels as the last geometry has sensors, with the settings so far; without a geometry its getters fail with DSR_E_ERROR"""
+        if self._sph is not None or self._chans:
+            return self._handle()
+        n = 1
+        for fn, args in self._set:
+            if fn == "setEigenMikeGeometry":
+                n = 32
+            elif fn == "setArrayGeometry":
+                n = len(args[1])
+        nBest, fs, M, NC, mo, nw = self._args
+        q = K._Sph(self._KIND, nBest, fs, M, n, mo, nw, False, NC)
+        for fn, args in self._set:
+            if hasattr(q, fn):
+                getattr(q, fn)(*args)
+        return q
+
+    def _apply(self, fn, *args):
+        if self._sph is None:
+            self._set.append((fn, args))
+        else:
+            getattr(self._sph, fn)(*args)
+
+    def setChannel(self, chan):
+        if self._sph is not None:
+            raise K.DsrError(5, "channels must be set before the first frame")
+        self._chans.append(chan)
+
+    def chanN(self):
+        return len(self._chans)
+
+    def dim(self):
+        return self._maxOrder * self._maxOrder
+
+    def setEigenMikeGeometry(self):
+        self._apply("setEigenMikeGeometry")
+
+    def setArrayGeometry(self, a, theta_s, phi_s):
+        self._apply("setArrayGeometry", float(a), np.array(theta_s, np.float64), np.array(phi_s, np.float64))
+
+    def setLookDirection(self, theta, phi):
+        self._apply("setLookDirection", float(theta), float(phi))
+
+    def setSigma2(self, sigma2):
+        self._apply("setSigma2", sigma2)
+
+    def setWeightGain(self, wgain):
+        self._apply("setWeightGain", wgain)
+
+    def getModeAmplitudes(self):
+        return self._query().modeAmplitudes()
+
+    def getArrayGeometry(self, type):
+        return self._query().getArrayGeometry(type)
+
+    def getSnapShotArray(self):
+        """the current frame's eigenbeams [fftLen/2+1][dim] (the reference's _sphericalTransformSnapShotArray)"""
+        self._handle(); D = self.dim(); out = np.zeros((self._fftLen // 2 + 1) * D * 2, np.float64); got = C.c_size_t()
+        K.check(lib().dsr_sph_stream_get_eigenbeams(self._h, K._ptr(out), out.size, C.byref(got)))
+        return out.view(np.complex128).reshape(self._fftLen // 2 + 1, D)
+
+    def reset(self):
+        self._handle(); FeatureStreamPtr.reset(self)
+
+    def next(self, frameX=-5):
+        self._handle()
+        return FeatureStreamPtr.next(self, frameX)
+
+    __next__ = next
+
+    def __iter__(self):
+        self.reset(); return self
+
+
+class EigenBeamformerPtr(_Spherical):
+    """beamformer.i:416-455 (EigenBeamformer, modalBeamformer.cc:219-399): the phase-mode (HMDI) beamformer in the eigenbeam domain"""
+
+    def __init__(self, sampleRate, fftLen=512, halfBandShift=False, NC=1, maxOrder=8, normalizeWeight=False, nm="EigenBeamformer"):
+        _Spherical.__init__(self, 1, sampleRate, fftLen, halfBandShift, NC, maxOrder, normalizeWeight, nm)
+
+
+class SphericalDSBeamformerPtr(_Spherical):
+    """beamformer.i:551-575 (SphericalDSBeamformer, modalBeamformer.cc:990-1091): delay-and-sum modal weights"""
+    _KIND = "DS"
+
+    def __init__(self, sampleRate, fftLen=512, halfBandShift=False, NC=1, maxOrder=3, normalizeWeight=False, nm="SphericalDSBeamformer"):
+        _Spherical.__init__(self, 1, sampleRate, fftLen, halfBandShift, NC, maxOrder, normalizeWeight, nm)
+
+    def calcWNG(self):
+        return self._query().calcWNG()
+
+
+class _SphericalDOA(_Spherical):
+    _DOA = True
+
+    def setSearchParam(self, minTheta=0.0, maxTheta=np.pi, minPhi=-np.pi, maxPhi=np.pi, widthTheta=0.1, widthPhi=0.1):
+        self._apply("setSearchParam", minTheta, maxTheta, minPhi, maxPhi, widthTheta, widthPhi)
+
+    def setFrequencyRange(self, fbinMin, fbinMax):
+        self._apply("setFrequencyRange", fbinMin, fbinMax)
+
+    def setEnergyThreshold(self, engeryThreshold):
+        self._apply("setEnergyThreshold", engeryThreshold)
+
+    def _get(self, what, n):
+        self._handle()
+        out = np.zeros(max(n, 1), np.float64); got = C.c_size_t()
+        K.check(lib().dsr_sph_doa_stream_get(self._h, what, K._ptr(out), out.size, C.byref(got)))
+        return out[:got.value]
+
+    def getNBestRPs(self):
+        return self._get(0, self._nBest)
+
+    def getNBestDOAs(self):
+        """[nBest][2]: (theta, phi) of each rank"""
+        return self._get(1, 2 * self._nBest).reshape(self._nBest, 2)
+
+    def getEnergy(self):
+        return float(np.float32(self._get(4, 1)[0]))
+
+    def getResponsePowerMatrix(self):
+        """[nTheta][nPhi]: the last ungated frame's response powers (the accumulators after getFinalNBestHypotheses); None before the first frame"""
+        nT, nP = self._handle().gridN()
+        v = self._get(2, nT * nP)
+        return v.reshape(nT, nP) if v.size else None
+
+    def getAccumulators(self):
+        return self._get(3, self._handle().units())
+
+    def getFinalNBestHypotheses(self):
+        self._handle(); K.check(lib().dsr_sph_doa_stream_final_nbest(self._h))
+
+    def initAccs(self):
+        self._handle(); K.check(lib().dsr_sph_doa_stream_init_accs(self._h))
+
+
+class DOAEstimatorSRPEBPtr(_SphericalDOA):
+    """beamformer.i:515-550 (DOAEstimatorSRPEB, modalBeamformer.cc:762-988): 2-D SRP over (theta, phi) with EigenBeamformer weights.  The
+    constructor searches (-pi, pi) x (-pi, pi) by 0.25; setSearchParam() without arguments (0, pi, -pi, pi, 0.1, 0.1)."""
+
+    def __init__(self, nBest, sampleRate, fftLen=512, halfBandShift=False, NC=1, maxOrder=8, normalizeWeight=False, nm="DirectionEstimatorSRPMB"):
+        _Spherical.__init__(self, nBest, sampleRate, fftLen, halfBandShift, NC, maxOrder, normalizeWeight, nm)
+
+
+class DOAEstimatorSRPSphDSBPtr(_SphericalDOA):
+    """beamformer.i:601-633 (DOAEstimatorSRPSphDSB, modalBeamformer.cc:1170-1385): 2-D SRP with SphericalDSBeamformer weights.  The defaults
+    are those of the Python constructor (%extend, beamformer.i:624): maxOrder 8, name "DirectionEstimatorSRPMB"."""
+    _KIND = "DS"
+
+    def __init__(self, nBest, sampleRate, fftLen=512, halfBandShift=False, NC=1, maxOrder=8, normalizeWeight=False, nm="DirectionEstimatorSRPMB"):
+        _Spherical.__init__(self, nBest, sampleRate, fftLen, halfBandShift, NC, maxOrder, normalizeWeight, nm)

@@ -246,6 +246,94 @@ dsr_status dsr_doa_srp(dsr_doa*, const float* X_dev, const int32_t* nframes_dev,
 dsr_status dsr_doa_final_nbest(dsr_doa*, const double* acc, int U, double* nbest_rp, int32_t* nbest_idx);
 
 /* =====================================================================================
+ * 2c. Spherical-array (modal) beamformers and 2-D steered-response-power direction of arrival
+ *     replaces EigenBeamformer, SphericalDSBeamformer, DOAEstimatorSRPEB, DOAEstimatorSRPSphDSB
+ *     (btk/beamformer/modalBeamformer.h:98-311, beamformer.i:416-633, modalBeamformer.cc:37-1385)
+ * One handle serves all four: kind DSR_SPH_EB (phase-mode / HMDI weights, _calcWeights :304-345) or DSR_SPH_DS (delay-and-sum modal
+ * weights, :1022-1058).  It holds the settings, the geometry, the mode amplitudes, the harmonics at the sensors, the look-direction
+ * weights and the (theta, phi) steering table; the accumulators are the caller's.  As in dsr_doa the table is built by the first use
+ * after create / set_search_param with the frequency range of that moment, and kept until the next set_search_param.  Table work is
+ * host-side and needs no GPU.  Defaults: search theta, phi in (-pi, pi) by 0.25 (DOAEstimatorSRPBase, beamformer.cc:2922-2938), range
+ * [1, fftLen/2], threshold 0, look direction (0, 0), sigma2 0, weight gain 1.  Deviations: a geometry whose sensor count differs
+ * from chanN, maxOrder above 8 (dim = maxOrder^2 above 64), fbinMax beyond the table or a grid whose steering table would exceed 2^27
+ * entries ((fbinMax+1) x units x max(dim, chanN)) is DSR_E_DIMENSION; a missing geometry or a
+ * radius of 0 is DSR_E_ERROR (the reference throws or reads a null pointer); halfBandShift, widths <= 0, an empty grid or nBest < 1 are
+ * DSR_E_PARAMETER.  minTheta > maxTheta is not swapped (unlike dsr_doa, as in modalBeamformer.h:197-205).
+ * ===================================================================================== */
+typedef struct dsr_sph dsr_sph;
+#define DSR_SPH_EB 0
+#define DSR_SPH_DS 1
+/* EigenBeamformer / DOAEstimatorSRPEB (kind EB) or SphericalDSBeamformer / DOAEstimatorSRPSphDSB (kind DS) (modalBeamformer.cc:219-246,
+   :769-777, :990-995, :1177-1182) over chanN channels (<= 128); NC is accepted and ignored (the reference only passes it on) */
+dsr_status dsr_sph_create(int kind, int nBest, int sampleRate, int fftLen, int halfBandShift, int NC, int maxOrder, int normalizeWeight, int chanN, dsr_sph** out);
+void       dsr_sph_destroy(dsr_sph*);
+int        dsr_sph_kind(const dsr_sph*);
+int        dsr_sph_nbest(const dsr_sph*);
+int        dsr_sph_chan_n(const dsr_sph*);
+int        dsr_sph_fft_len(const dsr_sph*);
+/* dim() = maxOrder^2 (:245) */
+int        dsr_sph_dim(const dsr_sph*);
+int        dsr_sph_max_order(const dsr_sph*);
+/* how many times the steering table was built (each build zeroes the reference's accumulators, :818-820); has_table: 1 while one is built */
+unsigned   dsr_sph_table_generation(const dsr_sph*);
+int        dsr_sph_has_table(const dsr_sph*);
+/* bumped by every set_array_geometry / set_eigenmike_geometry / set_look_direction / set_sigma2 / set_weight_gain: the stream operators
+   recompute the rest of the utterance when it moves */
+unsigned   dsr_sph_settings_generation(const dsr_sph*);
+/* setArrayGeometry(a, theta_s, phi_s) (:538-564): radius a in mm (SSPEED 343740 mm/s, beamformer.h:47), n = chanN sensor angles; computes the
+   harmonics at the sensors (:566-601); the steering table is not rebuilt */
+dsr_status dsr_sph_set_array_geometry(dsr_sph*, double a, const double* theta_s, const double* phi_s, int n);
+/* setEigenMikeGeometry() (:414-536): the 32 capsules of the EigenMike, a = 42 */
+dsr_status dsr_sph_set_eigenmike_geometry(dsr_sph*);
+/* getArrayGeometry(type) (:639-645): type 0 theta_s, else phi_s -> out [chanN] */
+dsr_status dsr_sph_array_geometry(const dsr_sph*, int type, double* out, int n);
+double     dsr_sph_radius(const dsr_sph*);
+/* setLookDirection(theta, phi) (:608-625), setSigma2 / setWeightGain (modalBeamformer.h:111-112): the beamformer's weights */
+dsr_status dsr_sph_set_look_direction(dsr_sph*, double theta, double phi);
+dsr_status dsr_sph_set_sigma2(dsr_sph*, float sigma2);
+dsr_status dsr_sph_set_weight_gain(dsr_sph*, float wgain);
+/* getModeAmplitudes() (:627-637, modeAmplitude :37-170): out [fftLen/2+1][maxOrder] complex128, ka = 2 pi f a fs / (fftLen SSPEED) */
+dsr_status dsr_sph_mode_amplitudes(dsr_sph*, double* out, size_t outDoubles);
+/* the conjugated harmonics at the sensors _sh_s (:566-601): out [dim][chanN] complex128 */
+dsr_status dsr_sph_harmonics(dsr_sph*, double* out, size_t outDoubles);
+/* the look direction's weights (_calcSteeringUnit :716-746): out [fftLen/2+1][dim] complex128, bin 0 the DC weights (calcDCWeights :219-233) */
+dsr_status dsr_sph_look_weights(dsr_sph*, double* out, size_t outDoubles);
+/* SphericalDSBeamformer::calcWNG (:997-1020): out [fftLen/2+1] (either kind) */
+dsr_status dsr_sph_calc_wng(dsr_sph*, double* out, int n);
+/* setSearchParam(minTheta, maxTheta, minPhi, maxPhi, widthTheta, widthPhi) (modalBeamformer.h:197-205): no swap; clears the table */
+dsr_status dsr_sph_set_search_param(dsr_sph*, double minTheta, double maxTheta, double minPhi, double maxPhi, double widthTheta, double widthPhi);
+/* setFrequencyRange(fbinMin, fbinMax) (modalBeamformer.h:196) */
+dsr_status dsr_sph_set_frequency_range(dsr_sph*, int fbinMin, int fbinMax);
+dsr_status dsr_sph_frequency_range(const dsr_sph*, int* fbinMin, int* fbinMax);
+/* setEnergyThreshold(threshold): frames whose energy is below it are not accumulated */
+dsr_status dsr_sph_set_energy_threshold(dsr_sph*, float threshold);
+float      dsr_sph_energy_threshold(const dsr_sph*);
+/* the grid (:803-804): nTheta = (unsigned)((maxTheta - minTheta) / widthTheta + 0.5), likewise nPhi; unit = iTheta nPhi + iPhi, theta and phi
+   accumulated by repeated addition (:829-832) -> theta [units], phi [units] */
+dsr_status dsr_sph_grid_n(dsr_sph*, int* nTheta, int* nPhi);
+dsr_status dsr_sph_grid(dsr_sph*, double* theta, double* phi, int n);
+/* build the steering table now (the SRP call and dsr_sph_steering build it when needed) */
+dsr_status dsr_sph_build_table(dsr_sph*);
+/* steering weights of one unit: out [fftLen/2+1][dim] complex128 = _calcWeights for the table's bins, (1, 0) at bin 0 unless the table was built
+   with fbinMin = 0, zero elsewhere (:833-841) */
+dsr_status dsr_sph_steering(dsr_sph*, int unit, double* out, size_t outDoubles);
+/* the SRP path dsr_sph_srp takes: 0 the fused kernel, 1 the folded table through the linear estimator's kernel; -1 on error */
+int        dsr_sph_srp_path(dsr_sph*);
+/* the beamformer's next() (:347-399) over a batch: X_dev [U][chanN][Tmax][fftLen/2+1] complex64, nframes_dev [U] ->
+ *   Y_dev [U][Tmax][fftLen/2+1] complex64: y = w_f^H (sh_s X_f), bin 0 with the DC weights
+ *   F_dev (optional) [U][Tmax][fftLen/2+1][dim] complex64: the eigenbeams (getSnapShotArray, modalBeamformer.h:126)
+ * Frames from nframes[u] on are not touched. */
+dsr_status dsr_sph_apply(dsr_sph*, const float* X_dev, const int32_t* nframes_dev, int U, int Tmax, float* Y_dev, float* F_dev, void* stream);
+/* next() of the DOA classes (:860-950, :1284-1370) over a batch, with dsr_doa_srp's outputs and contract, units in place of theta:
+ *   energy_dev [U][Tmax] float (calcEnergy, bit for bit), rp_dev (optional) [U][Tmax][units] double, nbest_rp_dev / nbest_idx_dev
+ *   [U][Tmax][nBest] (unit index, -1 = empty rank with rp -10e10), acc_dev [U][units] ADDED to, Y_dev (optional) [U][Tmax][fftLen/2+1]
+ *   the last unit's bins fbinMin..fbinMax, gated_dev (optional) [U][Tmax] */
+dsr_status dsr_sph_srp(dsr_sph*, const float* X_dev, const int32_t* nframes_dev, int U, int Tmax, float* energy_dev, double* rp_dev,
+                       double* nbest_rp_dev, int32_t* nbest_idx_dev, double* acc_dev, float* Y_dev, int32_t* gated_dev, void* stream);
+/* getFinalNBestHypotheses (beamformer.cc:2986-3025) for U utterances: acc [U][units] host -> nbest_rp [U][nBest], nbest_idx [U][nBest] host */
+dsr_status dsr_sph_final_nbest(dsr_sph*, const double* acc, int U, double* nbest_rp, int32_t* nbest_idx);
+
+/* =====================================================================================
  * 3. MFCC feature chain
  *    replaces SampleFeature(block framing) -> PreemphasisFeature -> HammingFeature -> FFTFeature ->
  *    SpectralPowerFeature -> VTLNFeature -> MelFeature -> LogFeature -> CepstralFeature ->
@@ -772,6 +860,20 @@ dsr_status dsr_doa_stream_create(dsr_doa* doa, const char* name, dsr_stream** ou
 dsr_status dsr_doa_stream_get(dsr_stream* s, int what, double* out, size_t outDoubles, size_t* n);
 dsr_status dsr_doa_stream_init_accs(dsr_stream* s);
 dsr_status dsr_doa_stream_final_nbest(dsr_stream* s);
+/* EigenBeamformer / SphericalDSBeamformer as a stream (beamformer.i:416-455, :551-575) over a dsr_sph handle (not owned): channels through
+ * dsr_subband_bf_set_channel; next() returns bins 0..fftLen/2 of y = w^H (sh_s X) and their conjugate mirror (:366-390).
+ *   get_eigenbeams: the current frame's eigenbeams F [fftLen/2+1][dim] complex128 (getSnapShotArray) */
+dsr_status dsr_sph_bf_stream_create(dsr_sph* sph, const char* name, dsr_stream** out);
+dsr_status dsr_sph_stream_get_eigenbeams(dsr_stream* s, double* out, size_t outDoubles, size_t* n);
+/* DOAEstimatorSRPEB / DOAEstimatorSRPSphDSB as a stream (beamformer.i:515-550, :601-633) over a dsr_sph handle (not owned), with the pull-by-pull
+ * state of dsr_doa_stream_create: next() returns the last unit's bins fbinMin..fbinMax and their mirror, the previous frame's where the gate held;
+ * the N-best is reset on every pull; the accumulators survive reset() and are zeroed by a new table and by init_accs.
+ *   get: what 0 getNBestRPs [nBest], 1 getNBestDOAs [nBest][2] (theta, phi), 2 getResponsePowerMatrix [nTheta][nPhi], 3 the accumulators
+ *        [units], 4 getEnergy [1]; *n = the count written (0 before the first frame for 2 and 3) */
+dsr_status dsr_sph_doa_stream_create(dsr_sph* sph, const char* name, dsr_stream** out);
+dsr_status dsr_sph_doa_stream_get(dsr_stream* s, int what, double* out, size_t outDoubles, size_t* n);
+dsr_status dsr_sph_doa_stream_init_accs(dsr_stream* s);
+dsr_status dsr_sph_doa_stream_final_nbest(dsr_stream* s);
 dsr_status dsr_preemphasis_create(dsr_stream* samp, double mu, const char* name, dsr_stream** out);
 dsr_status dsr_hamming_create(dsr_stream* samp, const char* name, dsr_stream** out);
 dsr_status dsr_fft_create(dsr_stream* samp, int fftLen, const char* name, dsr_stream** out);

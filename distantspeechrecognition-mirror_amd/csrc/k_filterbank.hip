@@ -910,8 +910,13 @@ template <int M, int MT> static void launch_analysis_w(const FbPlan& p, const Fb
 {
   int TF = 32; const int waves = 4;
   if (const char* e = getenv("DSR_FB_TF")) { const int v = atoi(e); if (v >= 4 && v <= 256) TF = v; }
-  const int winLen = (TF - 1) * p.D + MT * M;
-  size_t lds = sizeof(float2) * M + sizeof(float) * ((winLen + 3) & ~3) + sizeof(float2) * (size_t) waves * (M / 2 + M / 16);
+  // [tw][window of the tile's TF frames][one strip per wave]; a tile whose window does not fit (M = 1024, m = 4, r = 0 at TF = 32: 169 984 bytes)
+  // is halved until it does -- four frames (one per wave) fit at every M and m this kernel is built for
+  auto ldsOf = [&](int tf) { const int winLen = (tf - 1) * p.D + MT * M;
+                             return sizeof(float2) * M + sizeof(float) * ((winLen + 3) & ~3) + sizeof(float2) * (size_t) waves * (M / 2 + M / 16); };
+  while (TF > 4 && ldsOf(TF) > 160 * 1024) TF >>= 1;
+  size_t lds = ldsOf(TF);
+  if (lds > 160 * 1024) throw Error(DSR_E_DIMENSION, "analysis bank M=%d m=%d needs %zu bytes of LDS", M, MT, lds);
   if (const char* e = getenv("DSR_FB_PADLDS")) lds += (size_t) atoi(e);          // occupancy experiments
   DSR_HIP(hipFuncSetAttribute((const void*) k_analysis_w<M, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
   dim3 grid(cdiv(Tmax, TF), C, U);

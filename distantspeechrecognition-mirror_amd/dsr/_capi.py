@@ -149,6 +149,7 @@ class FilterBank:
         check(L.dsr_fb_create(_ptr(p), M, m, r, int(synthesis), delayCompensationType, gainFactor, C.byref(self.h)))
         self.M, self.m, self.r, self.D, self.synthesis = M, m, r, M >> r, synthesis
         self.pd = L.dsr_fb_processing_delay(self.h)
+        self.laN = (m << r) // 2 - 1 if (delayCompensationType == 2 and not synthesis) else 0      # look-ahead in blocks of D (modulated.cc:289)
 
     def __del__(self):
         if _lib is not None and getattr(self, "h", None):
@@ -204,6 +205,7 @@ class FilterBankState:
 
     def __init__(self, fb, U, C=1):
         L = load(); self.h = vp(); self.fb, self.U, self.C = fb, U, C
+        self._started = False
         check(L.dsr_fb_state_create(fb.h, U, C, C_.byref(self.h)))
 
     def __del__(self):
@@ -212,12 +214,17 @@ class FilterBankState:
 
     def reset(self):
         check(_lib.dsr_fb_state_reset(self.h))
+        self._started = False
 
     def analysis_block(self, x, nsamp=None, last=False):
         """x: cuda float32 [U][C][N] = the block's new samples -> complex64 [U][C][T][M/2+1], T = the frames this block yields"""
         import torch
         U, Cn, N = x.shape
         ns = [N] * U if nsamp is None else [int(v) for v in nsamp]
+        # include/dsr.h: the look-ahead of delayCompensationType 2 is spent inside a stream's first block, which must hold it
+        if not self._started and not last and min(ns) < self.fb.laN * self.fb.D:
+            raise DsrError(E_DIMENSION, "the first block of a stream must hold at least %d samples (the look-ahead)" % (self.fb.laN * self.fb.D))
+        self._started = True
         nd = torch.tensor(ns, dtype=torch.int32, device=x.device)
         T = max(1, max(_lib.dsr_fb_analysis_block_frames(self.fb.h, self.h, n, int(last)) for n in ns))
         X = torch.empty((U, Cn, T, self.fb.M // 2 + 1, 2), dtype=torch.float32, device=x.device)

@@ -100,7 +100,9 @@ dsr_status dsr_fb_analysis_beamform(const dsr_fb*, struct dsr_bf*, const float* 
  * stream.  All U streams advance in step: every block but a stream's last holds a multiple of D samples.
  *   analysis_block : x_dev [U][C][sampStride] the block's new samples, nsamp_dev [U]; last != 0 appends the processingDelay zero-input frames
  *                    (modulated.cc:493-501).  Frames written per stream: dsr_fb_analysis_block_frames(plan, state, nsamp, last), asked BEFORE the call
- *                    (the stream's first block spends the look-ahead of delayCompensationType 2).  X_dev [U][C][Tmax][M/2+1].
+ *                    (the stream's first block spends the look-ahead of delayCompensationType 2: unless it is also the last one it must hold at
+ *                    least m*R/2 - 1 blocks of D samples in every stream -- the call cannot see a shorter one, its counts are on the device, and
+ *                    the frames of the stream would then come out m*R/2 - 1 blocks late).  X_dev [U][C][Tmax][M/2+1].
  *   synthesis_block: Y_dev [U][Tmax][M/2+1], nframes_dev [U] (nframesHostMax = their maximum); output blocks per stream:
  *                    dsr_fb_synthesis_block_blocks(plan, state, nframes), asked before the call (the first call keeps processingDelay frames of
  *                    look-ahead back, modulated.cc:631-634, and needs at least processingDelay + R*m frames).  y_dev [U][outStride]. */

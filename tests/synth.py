@@ -25,6 +25,19 @@ def array_signal(nsamp, C=8, seed=7, az_deg=30.0, fs=16000.0, sigma=3000.0, nois
     return out
 
 
+def fb_prototype(M, m, r, seed):
+    """Analysis / synthesis prototypes (h, g), float64 [m*M] each, for filter-bank designs the reference ships no prototype for: a Hann-windowed
+    sinc low-pass with its cutoff at the decimated Nyquist (pi / D) and unit DC gain, every tap multiplied by a seeded jitter in [0.9, 1.1]
+    (g's drawn independently of h's).  The jitter breaks the symmetry: a linear-phase prototype cannot see a reversed tap index.  Perfect
+    reconstruction is not a goal -- these are inputs for parity tests."""
+    L, D = m * M, M >> r
+    rng = np.random.default_rng(seed)
+    n = np.arange(L) - (L - 1) / 2.0
+    p = np.sinc(n / D) * (0.5 - 0.5 * np.cos(2.0 * np.pi * (np.arange(L) + 0.5) / L))
+    p /= p.sum()
+    return p * rng.uniform(0.9, 1.1, L), p * rng.uniform(0.9, 1.1, L)
+
+
 def gmm_model(K, R, D, seed=12):
     rng = np.random.default_rng(seed)
     G = K * R

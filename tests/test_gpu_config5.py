@@ -108,7 +108,8 @@ def test_64ch_blockwise_front_end_matches_the_one_shot_oracle(dsr, oracle, cuda,
 
 @pytest.mark.parametrize("M,m,r,name", [(512, 2, 2, "M512-m2-r2"), (512, 2, 3, "M512-m2-r3")])
 def test_blockwise_filterbanks_other_designs(dsr, oracle, cuda, M, m, r, name):
-    """the wave-per-frame and generic kernels, decimation R = 4 and 8 (synthesis history R*m - 1 = 7 / 15 frames), delayCompensationType 0/1/2"""
+    """the wave-per-frame kernel k_analysis_w<512, 2> (both designs; the generic kernel is reached by tests/test_gpu_filterbank_designs.py) and
+    k_synthesis<512>, decimation R = 4 and 8 (synthesis history R*m - 1 = 7 / 15 frames), delayCompensationType 0/1/2"""
     import torch
     h, g = load_proto(name)
     D = M >> r; F = M // 2 + 1

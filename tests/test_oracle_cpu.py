@@ -12,7 +12,7 @@ import os
 import numpy as np
 import pytest
 
-from tests import synth
+from tests import fb_np, synth
 from tests.conftest import GOLDEN
 
 
@@ -62,6 +62,85 @@ def test_analysis_matches_closed_form(oracle, protos):
         u = (h * seg).reshape(m, M).sum(0)
         ref = np.fft.ifft(u) * M
         assert np.abs(X[t] - ref).max() < 1e-9 * (1 + np.abs(ref).max())
+
+
+def _sweep_proto(design):
+    from tests.conftest import load_proto
+    M, m, r = design
+    return load_proto(fb_np.SHIPPED[design]) if design in fb_np.SHIPPED else synth.fb_prototype(M, m, r, seed=M + 7 * m + r)
+
+
+_SWEEP = [(d, dct) for d in fb_np.DESIGNS + sorted(fb_np.SHIPPED) for dct in (0, 1, 2) if fb_np.dct_defined(d[1], d[2], dct)]
+
+
+@pytest.mark.parametrize("design,dct", _SWEEP)
+def test_filterbank_oracle_matches_closed_forms_over_the_design_sweep(oracle, design, dct):
+    """The oracle's analysis and synthesis banks against the closed forms of SURVEY.md Appendix A.1 / A.2 (tests/fb_np.py, float64 numpy, written
+    from the reference's loops) at every design of the GPU sweep -- odd tap counts, critical sampling r = 0, D = 1, M = 16 .. 2048 -- with
+    delayCompensationType 0/1/2 (the analysis frame index shifts by the look-ahead) and gainFactor 3: the yardstick of
+    tests/test_gpu_filterbank_designs.py is looked at before it is used.
+    Analysis: every frame, 1e-9 (1 + max |ref|) as test_analysis_matches_closed_form.
+    Synthesis: the oracle adds the R overlapping segments in a float vector as the reference does (modulated.cc:654-658), so it differs from
+    the float64 closed form by float32 rounding of an R-term sum.  Measured over this sweep: at most 1.27e-6 of the output RMS ((128,2,7),
+    R = 128; 3e-7 .. 9e-7 elsewhere); bound = 4 x that."""
+    M, m, r = design
+    D = M >> r
+    h, g = _sweep_proto(design)
+    rng = np.random.default_rng(M * m + r)
+    x = (rng.standard_normal(max(40 * D + 3, 3 * m * M + 3)) * 1000).astype(np.float32)    # long enough for the synthesis output to leave the taps' tails
+    X = oracle.analysis_bank(x, h, M, m, r, dct, 3)
+    ref = fb_np.analysis_closed_form(x, h, M, m, r, dct, 3)
+    assert X.shape == ref.shape == (oracle.analysis_num_frames(len(x), M, m, r, dct), M) and X.shape[0] > 0
+    assert np.abs(X - ref).max() < 1e-9 * (1 + np.abs(ref).max())
+    assert np.abs(3 * oracle.analysis_bank(x, h, M, m, r, dct) - X).max() <= 1e-12 * np.abs(X).max()       # gainFactor is a plain factor
+    y = oracle.synthesis_bank(X, g, M, m, r, dct, 3)
+    yr = fb_np.synthesis_closed_form(X, g, M, m, r, dct, 3)
+    assert y.shape == yr.shape and len(yr) == (X.shape[0] - fb_np.delays(m, r, dct, True)[0]) * D
+    rms = np.sqrt(np.mean(yr ** 2))
+    assert rms > 1.0
+    assert np.abs(y - yr).max() < max(4 * 1.27e-6, 1e-6) * rms
+
+
+def test_filterbank_closed_forms_edges(oracle):
+    """no frames when the input is shorter than the look-ahead; no output when there are no more frames than the processing delay; the
+    float32 evaluation of the analysis closed form stays within float32 rounding of the float64 one"""
+    M, m, r = 128, 2, 7
+    h, g = synth.fb_prototype(M, m, r, seed=3)
+    x = np.random.default_rng(0).standard_normal(43).astype(np.float32)
+    assert oracle.analysis_bank(x, h, M, m, r, 2).shape == fb_np.analysis_closed_form(x, h, M, m, r, 2).shape == (0, M)
+    X = fb_np.analysis_closed_form(x, h, M, m, r, 1)
+    pd = fb_np.delays(m, r, 1, True)[0]
+    assert len(oracle.synthesis_bank(X[:pd], g, M, m, r, 1)) == len(fb_np.synthesis_closed_form(X[:pd], g, M, m, r, 1)) == 0
+    for M, m, r in ((16, 2, 1), (1024, 3, 1)):
+        h, g = synth.fb_prototype(M, m, r, seed=4)
+        x = (np.random.default_rng(M).standard_normal(20 * (M >> r)) * 1000).astype(np.float32)
+        a, b = fb_np.analysis_closed_form(x, h, M, m, r, 0, 3), fb_np.analysis_closed_form(x, h, M, m, r, 0, 3, dtype=np.float32)
+        assert b.dtype == np.complex64 and np.abs(a - b).max() < 2e-5 * np.sqrt(np.mean(np.abs(a) ** 2))
+
+
+def test_fb_prototype_is_seeded_lowpass_and_not_symmetric():
+    h, g = synth.fb_prototype(64, 3, 2, seed=5)
+    h2, g2 = synth.fb_prototype(64, 3, 2, seed=5)
+    assert h.dtype == np.float64 and h.shape == g.shape == (192,) and np.array_equal(h, h2) and np.array_equal(g, g2)
+    assert not np.array_equal(h, g) and np.abs(h - h[::-1]).max() > 1e-4 * np.abs(h).max()      # a reversed tap index is visible
+    assert abs(h.sum() - 1.0) < 0.1 and abs(g.sum() - 1.0) < 0.1                                 # unit DC gain up to the jitter
+    H = np.abs(np.fft.rfft(h, 4096))
+    assert H[4096 // 16 * 3:].max() < 0.05 * H[0]                                                # stop band beyond three times the cutoff pi / D
+
+
+def test_filterbank_lds_arithmetic_names_the_designs_that_do_not_fit():
+    """The launchers' LDS requests redone on the host (tests/fb_np.py): of the sweep, synthesis cannot serve exactly (128,2,7), (1024,4,3) and
+    (2048,1,4); (2048,4,3) synthesis and (2048,8,0) analysis do not fit either; the wave-per-frame analysis kernel at its tile of 32 frames does
+    not fit (1024,4,0) -- the launcher lowers the tile there -- while the generic kernel fits every design of the sweep."""
+    over = {d: fb_np.synthesis_lds(*d)[0] for d in fb_np.DESIGNS + sorted(fb_np.SHIPPED) if fb_np.synthesis_lds(*d)[0] > fb_np.LDS_MAX}
+    assert over == {(128, 2, 7): 165888, (1024, 4, 3): 188416, (2048, 1, 4): 188416}
+    assert set(over) == fb_np.SYNTHESIS_REFUSED
+    assert fb_np.synthesis_lds(2048, 4, 3)[0] > fb_np.LDS_MAX and fb_np.analysis_generic_lds(2048, 8, 0) > fb_np.LDS_MAX
+    assert fb_np.synthesis_lds(1024, 2, 2)[1] < 32 and fb_np.synthesis_lds(256, 4, 1)[1] == 32            # the TO halving loop runs for M >= 1024
+    assert fb_np.analysis_wave_lds(1024, 4, 0) == 169984 and fb_np.analysis_wave_lds(1024, 2, 0) == 161792
+    assert [d for d in fb_np.WAVE if fb_np.analysis_wave_lds(*d) > fb_np.LDS_MAX] == [(1024, 4, 0)]
+    assert fb_np.analysis_wave_lds(1024, 4, 0, TF=16) <= fb_np.LDS_MAX
+    assert all(fb_np.analysis_generic_lds(*d) <= fb_np.LDS_MAX for d in fb_np.DESIGNS)
 
 
 def test_normal_fft_bank(oracle):

@@ -15,7 +15,7 @@
 
 using namespace dsr;
 
-struct dsr_fb; struct dsr_bf; struct dsr_lpc; struct dsr_stft; struct dsr_prfb; struct dsr_zelinski; struct dsr_gmm; struct dsr_decoder;
+struct dsr_aec; struct dsr_fb; struct dsr_bf; struct dsr_lpc; struct dsr_stft; struct dsr_prfb; struct dsr_zelinski; struct dsr_gmm; struct dsr_decoder;
 
 struct dsr_stream {
   int refs = 1; std::string name; int size_ = 0; int type = DSR_T_FLOAT; int frameX = -1; bool endOfSamples = false;
@@ -460,6 +460,30 @@ struct WpeMultiOp : dsr_stream {     // MultiChannelWPEDereverberationFeature(so
     op_expand_bins(O.p + (size_t) channelX * T * F, T, F, M, d<double2>(), S0);
   }
 };
+struct AecOp : dsr_stream {          // the echo cancellers of btk/cancelVP as a stream (cancelVP.cc:57-104, :141-209, :287-383, :1121-1198): ups = played, recorded
+  dsr_aec* aec = nullptr; int M = 0, frameMode = 0; DevBuf<float2> P, Rc, O; DevBuf<int> nf; DevBuf<unsigned char> state; bool haveState = false;
+  void ensure_state() {
+    if (haveState) return;
+    state.reserve(dsr_aec_state_bytes(aec, 1));
+    dsr_status s = dsr_aec_state_init(aec, state.p, 1, S0); if (s) throw Error(s, "%s", dsr_last_error());
+    haveState = true;
+  }
+  void reset() override {                // cancelVP.h:60, :98, :134-142: filter coefficients only (NLMS, Kalman) or nothing (block variants)
+    dsr_stream::reset();
+    if (haveState) { dsr_status s = dsr_aec_reset_filter(aec, state.p, 1, S0); if (s) throw Error(s, "%s", dsr_last_error()); }
+  }
+  const void* next(int fx) override { if (!ready) frameMode = fx < 0 ? 1 : 0; return dsr_stream::next(fx); }
+  void compute() override {
+    const int T = ups[0]->nFrames < ups[1]->nFrames ? ups[0]->nFrames : ups[1]->nFrames; alloc(T); if (T <= 0) return;
+    ensure_state();
+    const int F = M / 2 + 1; P.reserve((size_t) T * F); Rc.reserve((size_t) T * F); O.reserve((size_t) T * F);
+    op_pack_bins(ups[0]->d<double2>(), T, F, M, P.p, S0); op_pack_bins(ups[1]->d<double2>(), T, F, M, Rc.p, S0); nf.upload(&T, 1);
+    dsr_status s = dsr_aec_set_frame_mode(aec, dsr_aec_kind(aec) == DSR_AEC_DTD ? frameMode : 0);
+    if (!s) s = dsr_aec_apply(aec, (const float*) P.p, (const float*) Rc.p, nf.p, 1, T, 0, (float*) O.p, state.p, S0);
+    if (s) throw Error(s, "%s", dsr_last_error());
+    op_expand_bins(O.p, T, F, M, d<double2>(), S0);
+  }
+};
 struct ZelinskiOp : dsr_stream {     // ZelinskiPostFilter (postfilter.cc:350-493): ups[0] = beamformer output, ups[1..] = the snapshot array's channels
   dsr_zelinski* plan = nullptr; int M = 0; double alpha = 0.6; int ptype = 2, minFrames = 0; std::vector<std::vector<double>> manifold; int chanSet = 0;
   int kind = 0; float threshold = 0.99f;                   // kind 1: McCowanPostFilter (the plan then also carries the noise coherence matrices)
@@ -710,6 +734,28 @@ dsr_status dsr_wpe_multi_feature_create(dsr_stream* const* channels, int channel
     s->M = channels[0]->size_; s->channelX = channelX; s->lowerN = lowerN; s->upperN = upperN; s->iterationsN = iterationsN; s->loadDb = loadDb; s->bandWidth = bandWidth; s->sampleRate = sampleRate;
     for (int c = 0; c < channelsN; c++) s->add_up(channels[c]);
     s->checkOrder = true; *out = s;                      // getOutput: jindex_error on out-of-order requests (:371-372)
+  });
+}
+dsr_status dsr_aec_stream_create(dsr_aec* aec, dsr_stream* played, dsr_stream* recorded, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    if (!aec || !out) throw Error(DSR_E_PARAMETER, "null argument");
+    need(played, DSR_T_COMPLEX, "EchoCancellationFeature"); need(recorded, DSR_T_COMPLEX, "EchoCancellationFeature");
+    if (played->size_ != dsr_aec_fft_len(aec) || recorded->size_ != played->size_)
+      throw Error(DSR_E_DIMENSION, "played has %d subbands, recorded %d, the echo canceller %d", played->size_, recorded->size_, dsr_aec_fft_len(aec));
+    AecOp* s = mk<AecOp>(name, "AEC", played->size_, DSR_T_COMPLEX);
+    s->aec = aec; s->M = played->size_; s->add_up(played); s->add_up(recorded); *out = s;
+  });
+}
+dsr_status dsr_aec_stream_get(dsr_stream* s, int what, double* out, size_t outDoubles, size_t* n)
+{
+  return guard([&] {
+    AecOp* q = dynamic_cast<AecOp*>(s); if (!q || !out) throw Error(DSR_E_PARAMETER, "not an echo cancellation stream");
+    require_device(); q->ensure_state();
+    const size_t F = (size_t) q->M / 2 + 1, L = (size_t) dsr_aec_sample_n(q->aec);
+    const size_t cnt = what == DSR_AEC_STATE_K ? F * L * L * 2 : what == DSR_AEC_STATE_SIGMA2V ? F : what == DSR_AEC_STATE_DTD ? 3 : F * L * 2;
+    dsr_status st = dsr_aec_state_read(q->aec, q->state.p, 1, what, out, outDoubles); if (st) throw Error(st, "%s", dsr_last_error());
+    if (n) *n = cnt;
   });
 }
 dsr_status dsr_wpe_multi_feature_set_filter_channel(dsr_stream* feature, int filterChan)

@@ -483,6 +483,66 @@ def wpe_multi(Y, fftLen, lowerN, upperN, iterationsN=2, loadDb=-20.0, bandWidth=
     return out, gn
 
 
+class Aec:
+    """Subband echo cancellers of btk/cancelVP (include/dsr.h section 2d): kind "nlms", "kalman", "block" or "dtd".  The handle holds the
+    parameters (SWIG defaults of cancelVP.i unless given); the adaptive state is a device buffer of the caller (newState) that apply()
+    continues from and leaves behind.  played, recorded: cuda complex64 [U][T][M/2+1]."""
+    KINDS = {"nlms": 0, "kalman": 1, "block": 2, "dtd": 3}
+    FILTER, K, SIGMA2V, DTD, HISTORY = 0, 1, 2, 3, 4
+
+    def __init__(self, kind, fftLen, sampleN=1, delta=100.0, epsilon=1.0e-4, threshold=100.0, beta=0.95, sigma2=5.0, sigmau2=10e-4, sigmak2=5.0,
+                 amp4play=1.0, snrTh=2.0, engTh=100.0, smooth=0.9, frameMode=0):
+        L = load(); self.h = vp(); self.kind = self.KINDS[kind] if isinstance(kind, str) else int(kind); self.M = int(fftLen)
+        check(L.dsr_aec_create(self.kind, int(fftLen), int(sampleN), C.byref(self.h)))
+        self.L = L.dsr_aec_sample_n(self.h); self.F = self.M // 2 + 1
+        if self.kind == 0:
+            check(L.dsr_aec_set_nlms(self.h, float(delta), float(epsilon), float(threshold)))
+        elif self.kind == 1:
+            check(L.dsr_aec_set_kalman(self.h, float(beta), float(sigma2), float(threshold)))
+        else:
+            check(L.dsr_aec_set_block(self.h, float(beta), float(sigmau2), float(sigmak2), float(threshold), float(amp4play)))
+        if self.kind == 3:
+            check(L.dsr_aec_set_dtd(self.h, float(snrTh), float(engTh), float(smooth)))
+            check(L.dsr_aec_set_frame_mode(self.h, int(frameMode)))
+
+    def __del__(self):
+        if _lib is not None and getattr(self, "h", None):
+            _lib.dsr_aec_destroy(self.h)
+
+    def setFrameMode(self, mode):
+        check(_lib.dsr_aec_set_frame_mode(self.h, int(mode)))
+
+    def stateBytes(self, U):
+        return int(_lib.dsr_aec_state_bytes(self.h, int(U)))
+
+    def newState(self, U, device="cuda:0"):
+        import torch
+        st = torch.zeros((self.stateBytes(U) + 7) // 8, dtype=torch.float64, device=device)
+        check(_lib.dsr_aec_state_init(self.h, _dev(st), int(U), cur_stream()))
+        return st
+
+    def apply(self, played, recorded, nframes=None, state=None, frame0=0):
+        """-> the residual E [U][T][M/2+1] complex64; frames from nframes[u] on are zero and leave the state alone.  state None: a fresh one, discarded."""
+        import torch
+        U, T, F = played.shape
+        if F != self.F or tuple(recorded.shape) != (U, T, F) or played.dtype != torch.complex64 or recorded.dtype != torch.complex64:
+            raise ValueError("played, recorded: complex64 [U][T][%d] expected" % self.F)
+        out = torch.zeros((U, T, F), dtype=torch.complex64, device=played.device)
+        check(_lib.dsr_aec_apply(self.h, _dev(played.contiguous()), _dev(recorded.contiguous()), _dev(nframes) if nframes is not None else None, U, T,
+                                 int(frame0), _dev(out), _dev(state) if state is not None else None, cur_stream()))
+        return out
+
+    def read(self, state, U, what):
+        F, L = self.F, self.L
+        shape = {0: (U, F, L), 1: (U, F, L, L), 2: (U, F), 3: (U, 3), 4: (U, F, L)}[what]
+        out = np.zeros(shape, np.float64 if what in (2, 3) else np.complex128)
+        check(_lib.dsr_aec_state_read(self.h, _dev(state), int(U), int(what), _ptr(out), out.size * (1 if what in (2, 3) else 2)))
+        return out
+
+    def resetFilter(self, state, U):
+        check(_lib.dsr_aec_reset_filter(self.h, _dev(state), int(U), cur_stream()))
+
+
 class DoaSRP:
     """DOAEstimatorSRPDSBLA (btk/beamformer/beamformer.h:462-560, beamformer.cc:2920-3283) over a batch: settings and steering table on the
     host, the response powers of X [U][C][T][M/2+1] on the fp64 MFMA (dsr_doa_srp).  The accumulators belong to the caller."""

@@ -336,6 +336,69 @@ dsr_status dsr_sph_srp(dsr_sph*, const float* X_dev, const int32_t* nframes_dev,
 dsr_status dsr_sph_final_nbest(dsr_sph*, const double* acc, int U, double* nbest_rp, int32_t* nbest_idx);
 
 /* =====================================================================================
+ * 2d. Subband acoustic echo (voice prompt) cancellation
+ *     replaces NLMSAcousticEchoCancellationFeature, KalmanFilterEchoCancellationFeature, BlockKalmanFilterEchoCancellationFeature and
+ *     DTDBlockKalmanFilterEchoCancellationFeature (btk/cancelVP/cancelVP.h:41-143,428-462, cancelVP.i:62-254, cancelVP.cc:35-383,1056-1198)
+ * One handle serves all four.  It holds the kind, fftLen, sampleN and the parameters; the adaptive state (filter coefficients, covariances,
+ * noise variances, played history, the DTD scalars) is caller-owned device memory, like the accumulators of dsr_doa_srp.  The device works
+ * on the half spectrum [U][Tmax][fftLen/2+1] complex64: the reference computes bins 0..fftLen/2 and mirrors the rest (cancelVP.cc:74-77).
+ * Host-side pieces (create, setters, sizes, errors) need no GPU.  Initial state: NLMS R = 0 (the reference allocates it uninitialised and
+ * relies on __iter__'s reset()); Kalman sigma2_v = K = sigma2 and sigma2_u = sigma2 (cancelVP.cc:109-122); block variants sigma2_v = sigmau2,
+ * K = sigmak2 I, Sigma_u = sigmau2 I, R = 0, history zero (:216-247); DTD scalars zero (:1062).  Not reproduced: the printf dumps at bin 20,
+ * the DTD constructor's debug file (:1065, :1102-1107).  InformationFilter... and SquareRootInformationFilter... are not provided.
+ * ===================================================================================== */
+typedef struct dsr_aec dsr_aec;
+#define DSR_AEC_NLMS   0
+#define DSR_AEC_KALMAN 1
+#define DSR_AEC_BLOCK  2
+#define DSR_AEC_DTD    3
+#define DSR_AEC_MAX_SAMPLE_N 32
+/* fftLen = played->size() (cancelVP.cc:41): odd or non-positive is DSR_E_PARAMETER (no power of two needed).  sampleN: the taps per bin of the
+   block variants (cancelVP.i:141), 1..DSR_AEC_MAX_SAMPLE_N, otherwise DSR_E_PARAMETER (a covariance above 32 x 32 does not fit a wave's
+   registers and there is no slower path); NLMS and Kalman take and ignore it (they have one tap). */
+dsr_status dsr_aec_create(int kind, int fftLen, int sampleN, dsr_aec** out);
+void       dsr_aec_destroy(dsr_aec*);
+int        dsr_aec_kind(const dsr_aec*);
+int        dsr_aec_fft_len(const dsr_aec*);
+int        dsr_aec_sample_n(const dsr_aec*);
+/* one setter per parameter group, defaults = the SWIG defaults; a setter of another kind is DSR_E_PARAMETER.
+   NLMS (cancelVP.i:80-81): delta 100, epsilon 1e-4, threshold 100 */
+dsr_status dsr_aec_set_nlms(dsr_aec*, double delta, double epsilon, double threshold);
+/* Kalman (cancelVP.i:108-113): beta 0.95, sigma2 5, threshold 100 (the SWIG constructor's sigmau2 and crossCorrTh never reach the object);
+   beta outside (0, 1] is DSR_E_PARAMETER */
+dsr_status dsr_aec_set_kalman(dsr_aec*, double beta, double sigma2, double threshold);
+/* block and DTD (cancelVP.i:140-144, :241-246): beta 0.95, sigmau2 10e-4, sigmak2 5, threshold 100, amp4play 1; DTD ignores threshold here (its
+   base-class threshold is snrTh, cancelVP.cc:1061) */
+dsr_status dsr_aec_set_block(dsr_aec*, double beta, double sigmau2, double sigmak2, double threshold, double amp4play);
+/* DTD only (cancelVP.i:242-243): snrTh 2, engTh 100, smooth 0.9 */
+dsr_status dsr_aec_set_dtd(dsr_aec*, double snrTh, double engTh, double smooth);
+/* DTD only: which frameX _updateBand sees (cancelVP.cc:1077-1087, :1158).  0 (default) = the running frame index frame0 + t, a driver that
+   calls next(t); 1 = the constant -5 of a driver that iterates (`for x in aec`), which stays in the first-100-frames branch for ever */
+dsr_status dsr_aec_set_frame_mode(dsr_aec*, int mode);
+/* the caller's state for U utterances: bytes to allocate (0 for a bad argument), and the initial state written into it */
+size_t     dsr_aec_state_bytes(const dsr_aec*, int U);
+dsr_status dsr_aec_state_init(const dsr_aec*, void* state_dev, int U, void* stream);
+/* next() over a batch: played_dev, recorded_dev [U][Tmax][fftLen/2+1] complex64, nframes_dev (optional) [U] -> out_dev same shape, the residual
+ * E.  Frames from nframes[u] on are written as zero and do not touch the state.  state_dev: the state the call continues from and leaves
+ * behind -- block-wise processing gives the bits of one call; NULL = a fresh initial state, discarded.  frame0: the index of the call's first
+ * frame (DTD, frame mode 0).  The block variants' reset() resets nothing, so carrying the state from utterance to utterance is the reference's
+ * behaviour; starting afresh is state_init.  DTD: fftLen above 2046 is DSR_E_DIMENSION (one workgroup keeps a frame's per-bin scalars in LDS). */
+dsr_status dsr_aec_apply(const dsr_aec*, const float* played_dev, const float* recorded_dev, const int32_t* nframes_dev, int U, int Tmax, int frame0,
+                         float* out_dev, void* state_dev, void* stream);
+/* read a part of the state back (synchronous): what FILTER [U][fftLen/2+1][L] complex128, K [U][fftLen/2+1][L][L] complex128, SIGMA2V
+   [U][fftLen/2+1], DTD [U][3] (_EkEnergy, _SkEnergy, _snr), HISTORY [U][fftLen/2+1][L] complex128 (entry k = the scaled played sample k frames
+   back); L = 1 for NLMS and Kalman (K real).  A part the kind does not have is DSR_E_PARAMETER, a short buffer DSR_E_DIMENSION. */
+#define DSR_AEC_STATE_FILTER  0
+#define DSR_AEC_STATE_K       1
+#define DSR_AEC_STATE_SIGMA2V 2
+#define DSR_AEC_STATE_DTD     3
+#define DSR_AEC_STATE_HISTORY 4
+dsr_status dsr_aec_state_read(const dsr_aec*, const void* state_dev, int U, int what, double* host_out, size_t outDoubles);
+/* reset() of NLMS and Kalman (cancelVP.h:60, :98): the filter coefficients become zero, sigma2_v and K live on.  For the block variants it
+   does nothing, as their reset() does (cancelVP.h:134-142). */
+dsr_status dsr_aec_reset_filter(const dsr_aec*, void* state_dev, int U, void* stream);
+
+/* =====================================================================================
  * 3. MFCC feature chain
  *    replaces SampleFeature(block framing) -> PreemphasisFeature -> HammingFeature -> FFTFeature ->
  *    SpectralPowerFeature -> VTLNFeature -> MelFeature -> LogFeature -> CepstralFeature ->
@@ -844,6 +907,15 @@ dsr_status dsr_wpe_single_stream_create(dsr_stream* samples, int lowerN, int upp
 dsr_status dsr_wpe_multi_feature_create(dsr_stream* const* channels, int channelsN, int channelX, int lowerN, int upperN, int iterationsN, double loadDb,
                                         double bandWidth, double sampleRate, const char* name, dsr_stream** out);
 dsr_status dsr_wpe_multi_feature_set_filter_channel(dsr_stream* feature, int filterChan);
+/* NLMS / Kalman / BlockKalman / DTDBlockKalman...EchoCancellationFeature(played, recorded, ...) as a stream (cancelVP.i:62-254) over a dsr_aec
+ * handle (not owned; its parameters are read when an utterance is computed).  Serves all fftLen bins, bin fftLen-k = conj(bin k); ends when
+ * either upstream ends; a skipped frameX is DSR_E_INDEX, a repeated one returns the cached vector (cancelVP.cc:59-63).  The operator owns its
+ * adaptive state and keeps it across reset() as the reference does: NLMS and Kalman zero their filter coefficients, the block variants keep
+ * everything.  Unlike the reference, whose reset() forgets to rewind its frame counter (cancelVP.h:60), reset() restarts at frame 0.  DTD: the
+ * frameX of the first next() after a reset decides the frame mode of the utterance (< 0: the constant -5).
+ *   get: what = DSR_AEC_STATE_* -> out as dsr_aec_state_read with U = 1; *n = the doubles written */
+dsr_status dsr_aec_stream_create(dsr_aec* aec, dsr_stream* played, dsr_stream* recorded, const char* name, dsr_stream** out);
+dsr_status dsr_aec_stream_get(dsr_stream* s, int what, double* out, size_t outDoubles, size_t* n);
 /* SubbandDS/GSC/MVDR as a stream: channels are analysis-bank streams (setChannel) */
 dsr_status dsr_subband_bf_create(dsr_bf* weights, const char* name, dsr_stream** out);
 dsr_status dsr_subband_bf_set_channel(dsr_stream* bf, dsr_stream* chan);

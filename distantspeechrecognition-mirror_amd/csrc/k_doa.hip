@@ -17,8 +17,7 @@
 //                theta writes that unit's beamformed bins (the reference's _vector after next()).
 //   k_doa_frame  per frame: the energy gate and the frame's N-best (strict >: on a tie the earlier theta wins; :3207-3239)
 //   k_doa_acc    acc[u][theta] += rp of every ungated frame, frame by frame in order (caller-owned: block streaming carries it)
-// v_mfma_f64_16x16x4_f64 lane map: lane l holds A[l & 15][k = l >> 4] and B[k = l >> 4][l & 15]; result register q of lane l is
-// C[(l >> 4) + 4 q][l & 15] (tools/probes/probe_f64_mfma.hip).
+// The MFMA's lane map: csrc/mfma64.h.
 #include "srp_common.h"
 #include <algorithm>
 #include <cmath>
@@ -29,20 +28,6 @@ using namespace dsr;
 typedef std::complex<double> zc;
 
 namespace {
-
-constexpr int FB = 64;                                       // frames per workgroup (16 per wave)
-#ifndef DOA_LDS_ROWS
-#define DOA_LDS_ROWS 128
-#endif
-constexpr int LDS_ROWS = DOA_LDS_ROWS;                       // 128: at most 64 KB of staged snapshots (measured: 80 rows, 40 KB, is no faster at 8 channels and a third slower at 64)
-
-// LDS row of one (channel, frame): BC bins, padded by one from 4 bins up so that the 16 frames a read touches fall in distinct banks
-__host__ __device__ inline int bin_pitch(int BC) { return BC >= 4 ? BC + 1 : BC; }
-static int bin_chunk(int C)
-{
-  for (int BC = 16; BC > 1; BC >>= 1) if (C * bin_pitch(BC) <= LDS_ROWS) return BC;   // C * pitch * FB * 8 bytes <= LDS_ROWS / 2 KB
-  return 1;
-}
 
 template <int TG>
 __global__ __launch_bounds__(256) void k_doa_srp(const float2* __restrict__ X, const int* __restrict__ nframes, const double2* __restrict__ Wp,
@@ -64,14 +49,7 @@ __global__ __launch_bounds__(256) void k_doa_srp(const float2* __restrict__ X, c
   float e = 0.0f;
   for (int f0 = fbinMin; f0 <= fbinMax; f0 += BC) {
     const int nb = fbinMax - f0 + 1 < BC ? fbinMax - f0 + 1 : BC;
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < C * FB * BC; idx += 256) {
-      const int b = idx % BC, r = idx / BC, t = r % FB, c = r / FB;
-      float2 v = make_float2(0.f, 0.f);
-      if (b < nb && t0 + t < N) v = Xu[((long) c * Tmax + t0 + t) * F + f0 + b];
-      xs[(c * FB + t) * BP + b] = v;
-    }
-    __syncthreads();
+    srp_stage_chunk(xs, Xu, C, Tmax, F, BC, BP, t0, N, f0, nb);
     if (doEnergy) e = srp_energy_chunk(xs, C, FB, BP, threadIdx.x, f0, nb, M2, e);   // calcEnergy (:3043-3074)
     for (int b = 0; b < nb; b++) {
       const int f = f0 + b;
@@ -103,27 +81,11 @@ __global__ __launch_bounds__(256) void k_doa_srp(const float2* __restrict__ X, c
           const float2 x = ks * 4 + kq < C ? xb[ks * 4 * FB * BP] : make_float2(0.f, 0.f);
           cmfma(a.x, a.y, (double) x.x, (double) x.y, cr, ci);
         }
-#pragma unroll
-        for (int q = 0; q < 4; q++) rp[tg][q] += g * (cr[q] * cr[q] + ci[q] * ci[q]);
-        if (Y && th == lastTile) {                           // the last unit's beamformed value of bin f
-#pragma unroll
-          for (int q = 0; q < 4; q++)
-            if (kq + 4 * q == lastRow && tw < N) Y[((long) u * Tmax + tw) * F + f] = make_float2((float) cr[q], (float) ci[q]);
-        }
+        srp_accumulate(rp[tg], cr, ci, g, Y, th == lastTile, lastRow, kq, tw < N, (long) u * Tmax + tw, F, f);
       }
     }
   }
-  const double nbins = (double) (fbinMax - fbinMin + 1);
-#pragma unroll
-  for (int tg = 0; tg < TG; tg++) {
-    const int th = th0 + tg;
-    if (th >= NT) break;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int r = th * 16 + kq + 4 * q;
-      if (r < nTheta && tw < N) rpOut[((long) u * Tmax + tw) * nTheta + r] = rp[tg][q] / nbins;
-    }
-  }
+  srp_write_rp(rp, th0, NT, kq, nTheta, tw < N, (long) u * Tmax + tw, fbinMin, fbinMax, rpOut);
   if (doEnergy && t0 + (int) threadIdx.x < N) energy[(long) u * Tmax + t0 + threadIdx.x] = srp_energy_final(e, M2, C);
 }
 
@@ -136,20 +98,12 @@ __global__ void k_doa_frame(const double* __restrict__ rp, const float* __restri
   const int u = (int) (k / Tmax), t = (int) (k - (long) u * Tmax);
   if (t >= nframes[u]) return;
   double* R = nbRp + k * nBest; int* I = nbIdx + k * nBest;
-  for (int n = 0; n < nBest; n++) { R[n] = -10e10; I[n] = -1; }
+  nbest_reset(R, I, nBest);
   const bool gate = energy[k] < thr;
   if (gated) gated[k] = gate ? 1 : 0;
   if (gate) return;
   const double* r = rp + k * nTheta;
-  for (int th = 0; th < nTheta; th++) {
-    const double v = r[th];
-    if (!(v > R[nBest - 1])) continue;
-    for (int n1 = 0; n1 < nBest; n1++)
-      if (v > R[n1]) {
-        for (int n2 = nBest - 1; n2 > n1; n2--) { R[n2] = R[n2 - 1]; I[n2] = I[n2 - 1]; }
-        R[n1] = v; I[n1] = th; break;
-      }
-  }
+  for (int th = 0; th < nTheta; th++) nbest_insert(R, I, nBest, r[th], th);
 }
 
 // acc[u][theta] += rp[u][t][theta] over the ungated frames t < nframes[u], in frame order (_accRPs, :3201)
@@ -185,18 +139,10 @@ void look_delays(const dsr_doa& s, double theta, double* d)   // setLookDirectio
   for (int c = 1; c < s.C; c++) { double dist = s.pos[c] - ref; if (dist < 0) dist = -dist; d[c] = dist * cos(theta); }
 }
 
-void check_range(const dsr_doa& s, int fbinMax)
-{
-  if (s.fbinMin < 0 || s.fbinMin > s.fbinMax || s.fbinMax > s.M / 2)
-    throw Error(DSR_E_DIMENSION, "frequency range [%d, %d] outside [0, %d]", s.fbinMin, s.fbinMax, s.M / 2);
-  if (s.fbinMax > fbinMax)                                   // the table's bins end at the fbinMax it was built with (:3125-3127)
-    throw Error(DSR_E_DIMENSION, "fbinMax %d beyond the steering table built for bins up to %d (setSearchParam rebuilds it)", s.fbinMax, fbinMax);
-}
-
 void build_table(dsr_doa& s)                                 // _calcSteeringUnitTable (:3105-3152)
 {
   if (s.tbl) return;
-  check_range(s, s.M / 2);
+  check_range(s.fbinMin, s.fbinMax, s.M, s.M / 2);
   const int nT = theta_n(s), C = s.C, M = s.M, M2 = M / 2;
   if (nT < 1 || nT > 65536) throw Error(DSR_E_PARAMETER, "search grid of %d directions (minTheta %g, maxTheta %g, widthTheta %g)", nT, s.minTheta, s.maxTheta, s.widthTheta);
   std::vector<double> d(C);
@@ -365,7 +311,7 @@ dsr_status dsr_doa_srp(dsr_doa* s, const float* X_dev, const int32_t* nframes_de
     if (!s || !X_dev || !nframes_dev || !energy_dev || !nbest_rp_dev || !nbest_idx_dev || !acc_dev) throw Error(DSR_E_PARAMETER, "null argument");
     if (U < 0 || Tmax < 0) throw Error(DSR_E_DIMENSION, "U %d, Tmax %d", U, Tmax);
     build_table(*s);
-    check_range(*s, s->tblFbinMax);
+    check_range(s->fbinMin, s->fbinMax, s->M, s->tblFbinMax);
     require_device();
     if (U == 0 || Tmax == 0) return;
     hipStream_t st = (hipStream_t) stream;
@@ -385,20 +331,7 @@ dsr_status dsr_doa_final_nbest(dsr_doa* s, const double* acc, int U, double* nbe
   return guard([&] {
     if (!s || !acc || !nbest_rp || !nbest_idx) throw Error(DSR_E_PARAMETER, "null argument");
     if (!s->tbl) throw Error(DSR_E_ERROR, "no steering table: run the estimator after construction / setSearchParam first");
-    const int nB = s->nBest, nT = s->nTheta;
-    for (int u = 0; u < U; u++) {                            // _getNBestHypothesesFromACCRP (:2986-3025)
-      double* R = nbest_rp + (size_t) u * nB; int32_t* I = nbest_idx + (size_t) u * nB;
-      for (int n = 0; n < nB; n++) { R[n] = -10e10; I[n] = -1; }
-      for (int th = 0; th < nT; th++) {
-        const double v = acc[(size_t) u * nT + th];
-        if (!(v > R[nB - 1])) continue;
-        for (int n1 = 0; n1 < nB; n1++)
-          if (v > R[n1]) {
-            for (int n2 = nB - 1; n2 > n1; n2--) { R[n2] = R[n2 - 1]; I[n2] = I[n2 - 1]; }
-            R[n1] = v; I[n1] = th; break;
-          }
-      }
-    }
+    final_nbest(acc, U, s->nTheta, s->nBest, nbest_rp, nbest_idx);      // _getNBestHypothesesFromACCRP (:2986-3025)
   });
 }
 

@@ -22,8 +22,7 @@
 //   k_sph_frame  per frame, one wave: the gate and the frame's N-best by (rp descending, unit ascending), which is the reference's strict-">"
 //                insertion (:922-943) since every rp >= 0 > -10e10; nBest rounds of a wave arg-max over the frame's row
 //   k_doa_acc    (csrc/k_doa.hip) acc[u][unit] += rp of every ungated frame, frame by frame in order
-// v_mfma_f64_16x16x4_f64 lane map: lane l holds A[l & 15][k = l >> 4] and B[k = l >> 4][l & 15]; result register q of lane l is
-// C[(l >> 4) + 4 q][l & 15] (tools/probes/probe_f64_mfma.hip).
+// The MFMA's lane map: csrc/mfma64.h; the frame tiling (FB, bin_chunk) and the shared kernel parts: csrc/srp_common.h.
 #include "srp_common.h"
 #include <algorithm>
 #include <cmath>
@@ -275,18 +274,10 @@ int grid_n(double mn, double mx, double w)                   // (unsigned)((max 
   return v >= 1.0 && v < 1e9 ? (int) (unsigned) v : 0;
 }
 
-void check_range(const dsr_sph& s, int fbinMax)
-{
-  if (s.fbinMin < 0 || s.fbinMin > s.fbinMax || s.fbinMax > s.M / 2)
-    throw Error(DSR_E_DIMENSION, "frequency range [%d, %d] outside [0, %d]", s.fbinMin, s.fbinMax, s.M / 2);
-  if (s.fbinMax > fbinMax)
-    throw Error(DSR_E_DIMENSION, "fbinMax %d beyond the steering table built for bins up to %d (setSearchParam rebuilds it)", s.fbinMax, fbinMax);
-}
-
 void build_table(dsr_sph& s)                                 // _calcSteeringUnitTable (:793-858 / :1190-1246)
 {
   if (s.tbl) return;
-  check_range(s, s.M / 2);
+  check_range(s.fbinMin, s.fbinMax, s.M, s.M / 2);
   const int nT = grid_n(s.minTheta, s.maxTheta, s.widthTheta), nP = grid_n(s.minPhi, s.maxPhi, s.widthPhi);
   if (nT >= 1 && nP >= 1 && (long) nT * nP * (s.fbinMax + 1) * std::max(s.dim, s.C) > MAX_TABLE)
     throw Error(DSR_E_DIMENSION, "search grid of %d x %d directions: the steering table of bins 0..%d would hold %ld entries, at most %ld are supported",
@@ -314,15 +305,6 @@ void build_table(dsr_sph& s)                                 // _calcSteeringUni
 int units(const dsr_sph& s) { return s.nTheta * s.nPhi; }
 
 // ---- device ----
-
-constexpr int FB = 64;                                       // frames per workgroup (16 per wave), as k_doa_srp
-constexpr int LDS_ROWS = 128;                                // at most 64 KB of staged snapshots
-__host__ __device__ inline int bin_pitch(int BC) { return BC >= 4 ? BC + 1 : BC; }
-int bin_chunk(int C)
-{
-  for (int BC = 16; BC > 1; BC >>= 1) if (C * bin_pitch(BC) <= LDS_ROWS) return BC;
-  return 1;
-}
 
 // y[u][t][f] = w_f^H (S X_f), Fo[u][t][f][d] = (S X_f)_d (optional), for t < nframes[u], f = 0..M/2
 __global__ __launch_bounds__(256) void k_sph_apply(const float2* __restrict__ X, const int* __restrict__ nframes, const double2* __restrict__ S,
@@ -383,14 +365,7 @@ __global__ __launch_bounds__(256) void k_sph_srp(const float2* __restrict__ X, c
   float e = 0.0f;
   for (int f0 = fbinMin; f0 <= fbinMax; f0 += BC) {
     const int nb = fbinMax - f0 + 1 < BC ? fbinMax - f0 + 1 : BC;
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < C * FB * BC; idx += 256) {
-      const int b = idx % BC, r = idx / BC, t = r % FB, c = r / FB;
-      float2 v = make_float2(0.f, 0.f);
-      if (b < nb && t0 + t < N) v = Xu[((long) c * Tmax + t0 + t) * F + f0 + b];
-      xs[(c * FB + t) * BP + b] = v;
-    }
-    __syncthreads();
+    srp_stage_chunk(xs, Xu, C, Tmax, F, BC, BP, t0, N, f0, nb);
     if (doEnergy) e = srp_energy_chunk(xs, C, FB, BP, threadIdx.x, f0, nb, M2, e);   // calcEnergy (beamformer.cc:3043-3074)
     for (int b = 0; b < nb; b++) {
       const int f = f0 + b;
@@ -430,27 +405,11 @@ __global__ __launch_bounds__(256) void k_sph_srp(const float2* __restrict__ X, c
 #pragma unroll
           for (int q = 0; q < 4; q++) cmfma(a[q].x, a[q].y, Fr[dt][q], Fi[dt][q], cr, ci);
         }
-#pragma unroll
-        for (int q = 0; q < 4; q++) rp[tg][q] += g * (cr[q] * cr[q] + ci[q] * ci[q]);
-        if (Y && th == lastTile) {                           // the last unit's beamformed value of bin f
-#pragma unroll
-          for (int q = 0; q < 4; q++)
-            if (kq + 4 * q == lastRow && tw < N) Y[((long) u * Tmax + tw) * F + f] = make_float2((float) cr[q], (float) ci[q]);
-        }
+        srp_accumulate(rp[tg], cr, ci, g, Y, th == lastTile, lastRow, kq, tw < N, (long) u * Tmax + tw, F, f);
       }
     }
   }
-  const double nbins = (double) (fbinMax - fbinMin + 1);
-#pragma unroll
-  for (int tg = 0; tg < TG; tg++) {
-    const int th = th0 + tg;
-    if (th >= NT) break;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int r = th * 16 + kq + 4 * q;
-      if (r < nUnits && tw < N) rpOut[((long) u * Tmax + tw) * nUnits + r] = rp[tg][q] / nbins;
-    }
-  }
+  srp_write_rp(rp, th0, NT, kq, nUnits, tw < N, (long) u * Tmax + tw, fbinMin, fbinMax, rpOut);
   if (doEnergy && t0 + (int) threadIdx.x < N) energy[(long) u * Tmax + t0 + threadIdx.x] = srp_energy_final(e, M2, C);
 }
 
@@ -807,7 +766,7 @@ dsr_status dsr_sph_srp(dsr_sph* s, const float* X_dev, const int32_t* nframes_de
     if (!s || !X_dev || !nframes_dev || !energy_dev || !nbest_rp_dev || !nbest_idx_dev || !acc_dev) throw Error(DSR_E_PARAMETER, "null argument");
     if (U < 0 || Tmax < 0) throw Error(DSR_E_DIMENSION, "U %d, Tmax %d", U, Tmax);
     build_table(*s);
-    check_range(*s, s->tblFbinMax);
+    check_range(s->fbinMin, s->fbinMax, s->M, s->tblFbinMax);
     const int path = pick_path(*s);
     require_device();
     if (U == 0 || Tmax == 0) return;
@@ -837,20 +796,7 @@ dsr_status dsr_sph_final_nbest(dsr_sph* s, const double* acc, int U, double* nbe
   return guard([&] {
     if (!s || !acc || !nbest_rp || !nbest_idx) throw Error(DSR_E_PARAMETER, "null argument");
     if (!s->tbl) throw Error(DSR_E_ERROR, "no steering table: run the estimator after construction / setSearchParam first");
-    const int nB = s->nBest, nU = units(*s);
-    for (int u = 0; u < U; u++) {                            // _getNBestHypothesesFromACCRP (beamformer.cc:2986-3025)
-      double* R = nbest_rp + (size_t) u * nB; int32_t* I = nbest_idx + (size_t) u * nB;
-      for (int n = 0; n < nB; n++) { R[n] = -10e10; I[n] = -1; }
-      for (int k = 0; k < nU; k++) {
-        const double v = acc[(size_t) u * nU + k];
-        if (!(v > R[nB - 1])) continue;
-        for (int n1 = 0; n1 < nB; n1++)
-          if (v > R[n1]) {
-            for (int n2 = nB - 1; n2 > n1; n2--) { R[n2] = R[n2 - 1]; I[n2] = I[n2 - 1]; }
-            R[n1] = v; I[n1] = k; break;
-          }
-      }
-    }
+    final_nbest(acc, U, units(*s), s->nBest, nbest_rp, nbest_idx);      // _getNBestHypothesesFromACCRP (beamformer.cc:2986-3025)
   });
 }
 

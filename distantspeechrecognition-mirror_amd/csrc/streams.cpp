@@ -11,11 +11,10 @@
 #include "common.h"
 #include "ops.h"
 #include "lattice.h"
+#include "srp_common.h"
 #include <cmath>
 
 using namespace dsr;
-
-struct dsr_aec; struct dsr_fb; struct dsr_bf; struct dsr_lpc; struct dsr_stft; struct dsr_prfb; struct dsr_zelinski; struct dsr_gmm; struct dsr_decoder;
 
 struct dsr_stream {
   int refs = 1; std::string name; int size_ = 0; int type = DSR_T_FLOAT; int frameX = -1; bool endOfSamples = false;
@@ -56,6 +55,21 @@ struct dsr_stream {
 namespace {
 
 hipStream_t S0 = nullptr;
+
+void ok(dsr_status s) { if (s) throw Error(s, "%s", dsr_last_error()); }      // a failed call of the library's own C-ABI: its status and message go on
+
+// the frame count of the shortest of the C upstreams from `first` on (the reference's loops end with the first channel that ends)
+int shortest(const dsr_stream* s, int first, int C)
+{
+  int T = s->ups[first]->nFrames;
+  for (int c = 1; c < C; c++) if (s->ups[first + c]->nFrames < T) T = s->ups[first + c]->nFrames;
+  return T;
+}
+// X [C][T][F] complex64: bins 0..F-1 of the first T frames (M bins each) of the C upstreams from `first` on
+void pack_channels(const dsr_stream* s, int first, int C, int T, int F, int M, float2* X)
+{
+  for (int c = 0; c < C; c++) op_pack_bins(s->ups[first + c]->d<double2>(), T, F, M, X + (size_t) c * T * F, S0);
+}
 
 struct SampleSrc : dsr_stream {      // SampleFeature (feature.cc:222-689)
   int blockLen, shiftLen, padZeros; std::vector<float> samples; DevBuf<float> dx; int sampleRate = 16000, nChan = 1;
@@ -118,7 +132,7 @@ struct LpcOp : dsr_stream {         // WarpMVDR/BurgMVDR/WarpLPC/BurgLPC feature
   ~LpcOp() override { if (plan) dsr_lpc_destroy(plan); }
   void compute() override {
     alloc(ups[0]->nFrames);
-    if (nFrames > 0) { dsr_status s = dsr_lpc_run(plan, ups[0]->d<float>(), nFrames, d<double>(), S0); if (s) throw Error(s, "%s", dsr_last_error()); }
+    if (nFrames > 0) ok(dsr_lpc_run(plan, ups[0]->d<float>(), nFrames, d<double>(), S0));
   }
 };
 struct CmnOp : dsr_stream {          // MeanSubtractionFeature(src, weight, devNormFactor, runon): ups[1] (optional) = the weight stream, element 0 of each frame
@@ -134,192 +148,253 @@ struct AdjOp : dsr_stream {
   int delta;
   void compute() override { int T = ups[0]->nFrames; if (delta > 0 && T < delta) T = 0; alloc(T); op_adjacent(ups[0]->d<float>(), T, ups[0]->size_, delta, d<float>(), S0); }
 };
-struct AnalysisOp : dsr_stream {     // OverSampledDFTAnalysisBank
-  dsr_fb* fb = nullptr; int M, D; DevBuf<float> x; DevBuf<float2> X; DevBuf<int> ns;
+// The block-fed analysis banks.  The upstream delivers blocks of D samples (blockLen = shiftLen = D, padZeros): concatenate them again, run the
+// bank into `bins` complex64 bins a frame, widen to the size_ complex128 subbands of a frame.
+struct BlockAnalysisOp : dsr_stream {
+  int bins = 0; bool skipEmpty = false; DevBuf<float> x; DevBuf<float2> X; DevBuf<int> ns;
+  virtual int frames(int n) = 0;       // frames for n samples
+  virtual dsr_status run(int n, int T) = 0;                  // x [n] (ns = n) -> X [T][bins]
+  void compute() override {
+    dsr_stream* u = ups[0]; const int n = u->nFrames * u->size_;
+    const int T = frames(n); alloc(T);
+    x.reserve(n > 0 ? n : 1); if (n > 0) DSR_HIP(hipMemcpy(x.p, u->dev.p, (size_t) n * sizeof(float), hipMemcpyDeviceToDevice));
+    ns.upload(&n, 1);
+    if (skipEmpty && T <= 0) return;
+    X.reserve((size_t) T * bins);
+    ok(run(n, T));
+    op_expand_bins(X.p, T, bins, size_, d<double2>(), S0);
+  }
+};
+struct AnalysisOp : BlockAnalysisOp {  // OverSampledDFTAnalysisBank: M/2+1 bins, nothing to run for an empty utterance
+  dsr_fb* fb = nullptr;
   ~AnalysisOp() override { if (fb) dsr_fb_destroy(fb); }
-  void compute() override {
-    // upstream delivers blocks of D samples (blockLen = shiftLen = D, padZeros): concatenate them again
-    dsr_stream* u = ups[0]; const int nblk = u->nFrames; const int n = nblk * D;
-    int T = dsr_fb_analysis_frames(fb, n); alloc(T);
-    x.reserve(n > 0 ? n : 1); if (n > 0) DSR_HIP(hipMemcpy(x.p, u->dev.p, (size_t) n * sizeof(float), hipMemcpyDeviceToDevice));
-    ns.upload(&n, 1);
-    if (T > 0) {
-      X.reserve((size_t) T * (M / 2 + 1));
-      dsr_status s = dsr_fb_analysis(fb, x.p, ns.p, 1, 1, n > 0 ? n : 1, T, (float*) X.p, S0); if (s) throw Error(s, "%s", dsr_last_error());
-      op_expand_bins(X.p, T, M / 2 + 1, M, d<double2>(), S0);
-    }
-  }
+  int frames(int n) override { return dsr_fb_analysis_frames(fb, n); }
+  dsr_status run(int n, int T) override { return dsr_fb_analysis(fb, x.p, ns.p, 1, 1, n > 0 ? n : 1, T, (float*) X.p, S0); }
 };
-struct StftOp : dsr_stream {         // NormalFFTAnalysisBank (modulated.cc:121-257)
-  dsr_stft* plan = nullptr; int M, D; DevBuf<float> x; DevBuf<float2> X; DevBuf<int> ns;
+struct StftOp : BlockAnalysisOp {      // NormalFFTAnalysisBank (modulated.cc:121-257): all M bins
+  dsr_stft* plan = nullptr;
   ~StftOp() override { if (plan) dsr_stft_destroy(plan); }
-  void compute() override {
-    dsr_stream* u = ups[0]; const int nblk = u->nFrames; const int n = nblk * D;
-    const int T = dsr_stft_frames(plan, n); alloc(T);
-    x.reserve(n > 0 ? n : 1); if (n > 0) DSR_HIP(hipMemcpy(x.p, u->dev.p, (size_t) n * sizeof(float), hipMemcpyDeviceToDevice));
-    ns.upload(&n, 1);
-    X.reserve((size_t) T * M);
-    dsr_status s = dsr_stft_analysis(plan, x.p, ns.p, 1, 1, n > 0 ? n : 1, T, (float*) X.p, S0); if (s) throw Error(s, "%s", dsr_last_error());
-    op_expand_bins(X.p, T, M, M, d<double2>(), S0);          // all M bins are already there: widen to complex128
-  }
+  int frames(int n) override { return dsr_stft_frames(plan, n); }
+  dsr_status run(int n, int T) override { return dsr_stft_analysis(plan, x.p, ns.p, 1, 1, n > 0 ? n : 1, T, (float*) X.p, S0); }
 };
-struct SynthesisOp : dsr_stream {    // OverSampledDFTSynthesisBank
-  dsr_fb* fb = nullptr; int M, D; DevBuf<float2> Y; DevBuf<int> nf;
-  ~SynthesisOp() override { if (fb) dsr_fb_destroy(fb); }
-  void compute() override {
-    dsr_stream* u = ups[0]; const int Tin = u->nFrames; const int nb = dsr_fb_synthesis_blocks(fb, Tin); alloc(nb);
-    if (nb <= 0) return;
-    Y.reserve((size_t) Tin * (M / 2 + 1)); op_pack_hermitian(u->d<double2>(), Tin, M, Y.p, S0);      // frames need not be conjugate-symmetric (SubbandMMI + APAB)
-    nf.upload(&Tin, 1);
-    dsr_status s = dsr_fb_synthesis(fb, (const float*) Y.p, nf.p, 1, Tin, (int64_t) nb * D, d<float>(), S0); if (s) throw Error(s, "%s", dsr_last_error());
-  }
-};
-struct PrAnalysisOp : dsr_stream {   // PerfectReconstructionFFTAnalysisBank (modulated.cc:686-818)
-  dsr_prfb* fb = nullptr; int M2, D; DevBuf<float> x; DevBuf<float2> X; DevBuf<int> ns;
+struct PrAnalysisOp : BlockAnalysisOp {  // PerfectReconstructionFFTAnalysisBank (modulated.cc:686-818): all 2M bins
+  dsr_prfb* fb = nullptr;
   ~PrAnalysisOp() override { if (fb) dsr_prfb_destroy(fb); }
+  int frames(int n) override { return dsr_prfb_analysis_frames(fb, n); }
+  dsr_status run(int n, int T) override { return dsr_prfb_analysis(fb, x.p, ns.p, 1, 1, n > 0 ? n : 1, T, (float*) X.p, S0); }
+};
+// The synthesis banks: `bins` complex64 bins of every upstream frame in, blocks of size_ samples out.
+struct BlockSynthesisOp : dsr_stream {
+  int bins = 0; bool hermitian = false; DevBuf<float2> Y; DevBuf<int> nf;
+  virtual int blocks(int Tin) = 0;
+  virtual dsr_status run(int Tin, int nb) = 0;               // Y [Tin][bins] (nf = Tin) -> nb blocks
   void compute() override {
-    dsr_stream* u = ups[0]; const int nblk = u->nFrames; const int n = nblk * D;
-    const int T = dsr_prfb_analysis_frames(fb, n); alloc(T);
-    x.reserve(n > 0 ? n : 1); if (n > 0) DSR_HIP(hipMemcpy(x.p, u->dev.p, (size_t) n * sizeof(float), hipMemcpyDeviceToDevice));
-    ns.upload(&n, 1); X.reserve((size_t) T * M2);
-    dsr_status s = dsr_prfb_analysis(fb, x.p, ns.p, 1, 1, n > 0 ? n : 1, T, (float*) X.p, S0); if (s) throw Error(s, "%s", dsr_last_error());
-    op_expand_bins(X.p, T, M2, M2, d<double2>(), S0);
+    dsr_stream* u = ups[0]; const int Tin = u->nFrames; const int nb = blocks(Tin); alloc(nb);
+    if (nb <= 0) return;
+    Y.reserve((size_t) Tin * bins);
+    if (hermitian) op_pack_hermitian(u->d<double2>(), Tin, u->size_, Y.p, S0);      // frames need not be conjugate-symmetric (SubbandMMI + APAB)
+    else op_pack_bins(u->d<double2>(), Tin, bins, u->size_, Y.p, S0);
+    nf.upload(&Tin, 1);
+    ok(run(Tin, nb));
   }
 };
-struct PrSynthesisOp : dsr_stream {  // PerfectReconstructionFFTSynthesisBank (modulated.cc:820-970)
-  dsr_prfb* fb = nullptr; int M2, D; DevBuf<float2> Y; DevBuf<int> nf;
+struct SynthesisOp : BlockSynthesisOp {  // OverSampledDFTSynthesisBank
+  dsr_fb* fb = nullptr;
+  ~SynthesisOp() override { if (fb) dsr_fb_destroy(fb); }
+  int blocks(int Tin) override { return dsr_fb_synthesis_blocks(fb, Tin); }
+  dsr_status run(int Tin, int nb) override { return dsr_fb_synthesis(fb, (const float*) Y.p, nf.p, 1, Tin, (int64_t) nb * size_, d<float>(), S0); }
+};
+struct PrSynthesisOp : BlockSynthesisOp {  // PerfectReconstructionFFTSynthesisBank (modulated.cc:820-970)
+  dsr_prfb* fb = nullptr;
   ~PrSynthesisOp() override { if (fb) dsr_prfb_destroy(fb); }
-  void compute() override {
-    dsr_stream* u = ups[0]; const int Tin = u->nFrames; const int nb = dsr_prfb_synthesis_blocks(fb, Tin); alloc(nb);
-    if (nb <= 0) return;
-    Y.reserve((size_t) Tin * M2); op_pack_bins(u->d<double2>(), Tin, M2, M2, Y.p, S0);
-    nf.upload(&Tin, 1);
-    dsr_status s = dsr_prfb_synthesis(fb, (const float*) Y.p, nf.p, 1, Tin, (int64_t) nb * D, d<float>(), S0); if (s) throw Error(s, "%s", dsr_last_error());
-  }
+  int blocks(int Tin) override { return dsr_prfb_synthesis_blocks(fb, Tin); }
+  dsr_status run(int Tin, int nb) override { return dsr_prfb_synthesis(fb, (const float*) Y.p, nf.p, 1, Tin, (int64_t) nb * size_, d<float>(), S0); }
 };
 struct BfOp : dsr_stream {           // SubbandDS / SubbandGSC / SubbandMVDR as a stream
   dsr_bf* w; int M; DevBuf<float2> X, Y;
+  int T = 0, F = 0; DevBuf<int> nf;  // of the operators built on this one that keep the packed utterance
   void compute() override {
     const int C = (int) ups.size();
     if (C == 0 || C != dsr_bf_chan_n(w)) throw Error(DSR_E_DIMENSION, "Number of channels (%d) does not match the weights (%d)", C, dsr_bf_chan_n(w));
-    int T = ups[0]->nFrames; for (int c = 1; c < C; c++) if (ups[c]->nFrames < T) T = ups[c]->nFrames;
+    const int T = shortest(this, 0, C);
     alloc(T); if (T <= 0) return;
     const int F = dsr_bf_bins(w); X.reserve((size_t) C * T * F); Y.reserve((size_t) T * F);       // M/2+1 unique bins, or all M with halfBandShift
-    for (int c = 0; c < C; c++) op_pack_bins(ups[c]->d<double2>(), T, F, M, X.p + (size_t) c * T * F, S0);
-    dsr_status s = dsr_bf_apply(w, (const float*) X.p, 1, T, (float*) Y.p, S0); if (s) throw Error(s, "%s", dsr_last_error());
+    pack_channels(this, 0, C, T, F, M, X.p);
+    ok(dsr_bf_apply(w, (const float*) X.p, 1, T, (float*) Y.p, S0));
     op_expand_bins(Y.p, T, F, M, d<double2>(), S0);
+  }
+  void pack_half() {                  // T, F = M/2+1, X [C][T][F] of the channels' frames, nf = T
+    const int C = (int) ups.size();
+    T = shortest(this, 0, C); F = M / 2 + 1;
+    if (T <= 0) return;
+    X.reserve((size_t) C * T * F); pack_channels(this, 0, C, T, F, M, X.p); nf.upload(&T, 1);
   }
 };
 
 struct MmiOp : BfOp {                // SubbandMMI as a stream (beamformer.cc:1973-2072); channels through dsr_subband_bf_set_channel
-  dsr_mmi* mm = nullptr; DevBuf<int> nf;
+  dsr_mmi* mm = nullptr;
   void compute() override {
     const int C = (int) ups.size();
     if (C == 0 || C != dsr_mmi_chan_n(mm)) throw Error(DSR_E_DIMENSION, "Number of channels (%d) does not match the weights (%d)", C, dsr_mmi_chan_n(mm));
-    int T = ups[0]->nFrames; for (int c = 1; c < C; c++) if (ups[c]->nFrames < T) T = ups[c]->nFrames;
+    const int T = shortest(this, 0, C);
     alloc(T); if (T <= 0) return;
     const int F = dsr_mmi_bins(mm), Fo = dsr_mmi_out_bins(mm); X.reserve((size_t) C * T * F); Y.reserve((size_t) T * Fo);   // Fo = M: halfBandShift, or APAB's full frames
-    for (int c = 0; c < C; c++) op_pack_bins(ups[c]->d<double2>(), T, F, M, X.p + (size_t) c * T * F, S0);
+    pack_channels(this, 0, C, T, F, M, X.p);
     nf.upload(&T, 1);
-    dsr_status s = dsr_mmi_apply(mm, (const float*) X.p, nf.p, 1, T, (float*) Y.p, S0); if (s) throw Error(s, "%s", dsr_last_error());
+    ok(dsr_mmi_apply(mm, (const float*) X.p, nf.p, 1, T, (float*) Y.p, S0));
     op_expand_bins(Y.p, T, Fo, M, d<double2>(), S0);
   }
 };
 
-struct DoaOp : BfOp {                // DOAEstimatorSRPDSBLA as a stream (beamformer.cc:3188-3283); channels through dsr_subband_bf_set_channel
-  dsr_doa* doa = nullptr; unsigned gen = 0, seenGen = ~0u; int T = 0, nT = 0, F = 0;
+// The SRP estimators' stream face: DOAEstimatorSRPDSBLA (beamformer.cc:3188-3283) over a BfOp, DOAEstimatorSRPEB / DOAEstimatorSRPSphDSB
+// (modalBeamformer.cc:860-950, :1284-1370) over a SphBfOp; channels through dsr_subband_bf_set_channel.  H names the handle's calls; a binding
+// packs the channels (pack_frames: X, nf, T, F) and may add to the re-materialise condition (moved) and note an ungated frame (served).
+template <class Base, class H> struct SrpFace : Base {
+  typedef H Calls;
+  typename H::Handle* est = nullptr; unsigned gen = 0, seenGen = ~0u; int nU = 0;
   std::vector<float> E; std::vector<double> RP; std::vector<float2> Yh;              // the materialised utterance: energy, rp, last unit's bins
+  std::vector<double> gth, gph;                                                      // the table's units: (theta, phi)
   // the reference object's observable state
-  std::vector<double> acc, rpMat, nbRp, nbDoa, vec; float energy = 0.f; bool haveAcc = false;
-  DevBuf<float> dE; DevBuf<double> dRP, dAcc, dNbR; DevBuf<int> dNbI, nf; DevBuf<float2> dY; int rangeUsed[2] = {-1, -1};
+  std::vector<double> acc, rpMat, nbRp, nbDoa, vec; std::vector<int> nbIdx; float energy = 0.f; bool haveAcc = false;
+  DevBuf<float> dE; DevBuf<double> dRP, dAcc, dNbR; DevBuf<int> dNbI; DevBuf<float2> dY; int rangeUsed[2] = {-1, -1};
+  virtual void pack_frames() = 0;
+  virtual bool moved() const { return false; }
+  virtual void served(int) {}
   void compute() override {
-    const int C = (int) ups.size();
-    if (C == 0 || C != dsr_doa_chan_n(doa)) throw Error(DSR_E_DIMENSION, "Number of channels (%d) does not match the estimator (%d)", C, dsr_doa_chan_n(doa));
-    T = ups[0]->nFrames; for (int c = 1; c < C; c++) if (ups[c]->nFrames < T) T = ups[c]->nFrames;
-    nFrames = T; F = M / 2 + 1; range(rangeUsed[0], rangeUsed[1]);
-    dsr_status st = dsr_doa_build_table(doa); if (st) throw Error(st, "%s", dsr_last_error());
-    st = dsr_doa_theta_n(doa, &nT); if (st) throw Error(st, "%s", dsr_last_error());
+    const int C = (int) this->ups.size();
+    if (C == 0 || C != H::chan_n(est)) throw Error(DSR_E_DIMENSION, "Number of channels (%d) does not match the estimator (%d)", C, H::chan_n(est));
+    range(rangeUsed[0], rangeUsed[1]);
+    ok(H::build_table(est)); H::grid(est, gth, gph); nU = (int) gth.size();
+    pack_frames();
+    const int T = this->T, F = this->F; this->nFrames = T;
     if (T <= 0) return;
-    const int nB = dsr_doa_nbest(doa);
-    X.reserve((size_t) C * T * F); dY.reserve((size_t) T * F); dE.reserve(T); dRP.reserve((size_t) T * nT); dAcc.reserve(nT);
+    const int nB = H::nbest(est);
+    dY.reserve((size_t) T * F); dE.reserve(T); dRP.reserve((size_t) T * nU); dAcc.reserve(nU);
     dNbR.reserve((size_t) T * nB); dNbI.reserve((size_t) T * nB);
-    for (int c = 0; c < C; c++) op_pack_bins(ups[c]->d<double2>(), T, F, M, X.p + (size_t) c * T * F, S0);
-    nf.upload(&T, 1);
-    DSR_HIP(hipMemsetAsync(dY.p, 0, sizeof(float2) * (size_t) T * F, S0)); DSR_HIP(hipMemsetAsync(dAcc.p, 0, sizeof(double) * nT, S0));
-    st = dsr_doa_srp(doa, (const float*) X.p, nf.p, 1, T, dE.p, dRP.p, dNbR.p, dNbI.p, dAcc.p, (float*) dY.p, nullptr, S0);
-    if (st) throw Error(st, "%s", dsr_last_error());
-    E.resize(T); RP.resize((size_t) T * nT); Yh.resize((size_t) T * F);
+    DSR_HIP(hipMemsetAsync(dY.p, 0, sizeof(float2) * (size_t) T * F, S0)); DSR_HIP(hipMemsetAsync(dAcc.p, 0, sizeof(double) * nU, S0));
+    ok(H::srp(est, (const float*) this->X.p, this->nf.p, 1, T, dE.p, dRP.p, dNbR.p, dNbI.p, dAcc.p, (float*) dY.p, nullptr, S0));
+    E.resize(T); RP.resize((size_t) T * nU); Yh.resize((size_t) T * F);
     DSR_HIP(hipMemcpy(E.data(), dE.p, sizeof(float) * T, hipMemcpyDeviceToHost));
     DSR_HIP(hipMemcpy(RP.data(), dRP.p, sizeof(double) * RP.size(), hipMemcpyDeviceToHost));
     DSR_HIP(hipMemcpy(Yh.data(), dY.p, sizeof(float2) * Yh.size(), hipMemcpyDeviceToHost));
   }
-  void sync_table() {                 // a new steering table: _accRPs and _rpMat start from zero (:3128-3130, :3148-3149)
-    const unsigned g = dsr_doa_table_generation(doa);
-    if (g != seenGen) { acc.assign(nT, 0.0); rpMat.assign(nT, 0.0); haveAcc = true; seenGen = g; }
+  void sync_table() {                 // a new steering table: _accRPs and _rpMat start from zero (beamformer.cc:3128-3130, :3148-3149; modalBeamformer.cc:818-820)
+    const unsigned g = H::generation(est);
+    if (g != seenGen) { acc.assign(nU, 0.0); rpMat.assign(nU, 0.0); haveAcc = true; seenGen = g; }
+  }
+  bool live() const { return haveAcc && H::has_table(est) && seenGen == H::generation(est); }   // setSearchParam freed _accRPs and _rpMat until the next table
+  void set_doas() {                   // the ranks' (theta, phi): an empty rank is (-pi, -pi)
+    nbDoa.resize(2 * nbIdx.size());
+    for (size_t n = 0; n < nbIdx.size(); n++) { const int k = nbIdx[n]; nbDoa[2 * n] = k < 0 ? -M_PI : gth[k]; nbDoa[2 * n + 1] = k < 0 ? -M_PI : gph[k]; }
   }
   void reset_nbest() {
-    const int nB = dsr_doa_nbest(doa); nbRp.assign(nB, -10e10); nbDoa.assign((size_t) 2 * nB, -M_PI);
+    const int nB = H::nbest(est); nbRp.resize(nB); nbIdx.resize(nB); nbest_reset(nbRp.data(), nbIdx.data(), nB); set_doas();
   }
   const void* next(int fx) override {
+    const int M = this->M;
     if (vec.empty()) vec.assign((size_t) 2 * M, 0.0);
-    if (fx == frameX && frameX >= 0) return vec.data();
-    reset_nbest();                                          // before anything else, the end of the stream included (:3192-3196)
+    if (fx == this->frameX && this->frameX >= 0) return vec.data();
+    reset_nbest();                                          // before anything else, the end of the stream included (:3192-3196, :866-870)
     int fmin = 0, fmax = 0; range(fmin, fmax);
-    if (ready && (gen != dsr_doa_table_generation(doa) || !dsr_doa_has_table(doa) || fmin != rangeUsed[0] || fmax != rangeUsed[1]))
-      ready = false;                                        // setSearchParam (a new table) or setFrequencyRange since: the rest of the utterance anew
-    if (!ready) {
+    if (this->ready && (gen != H::generation(est) || !H::has_table(est) || fmin != rangeUsed[0] || fmax != rangeUsed[1] || moved()))
+      this->ready = false;                                  // setSearchParam (a new table), setFrequencyRange or what the binding watches since: the rest of the utterance anew
+    if (!this->ready) {
       require_device();
-      for (size_t i = 0; i < ups.size(); i++) ups[i]->materialize();
-      compute(); gen = dsr_doa_table_generation(doa); ready = true;
+      for (size_t i = 0; i < this->ups.size(); i++) this->ups[i]->materialize();
+      compute(); gen = H::generation(est); this->ready = true;
     }
     sync_table();
-    if (frameX + 1 >= nFrames) { endOfSamples = true; throw Error(DSR_E_ITERATOR, "end of samples!"); }
-    frameX++;
-    const int t = frameX;
+    if (this->frameX + 1 >= this->nFrames) { this->endOfSamples = true; throw Error(DSR_E_ITERATOR, "end of samples!"); }
+    const int t = ++this->frameX;
     energy = E[t];
-    if (energy < dsr_doa_energy_threshold(doa)) return vec.data();     // gated: no accumulation, no N-best, _vector as it was (:3215-3221)
-    const int nB = dsr_doa_nbest(doa);
-    std::vector<double> th(nT); dsr_status st = dsr_doa_thetas(doa, th.data(), nT); if (st) throw Error(st, "%s", dsr_last_error());
-    const double* r = RP.data() + (size_t) t * nT;
-    for (int k = 0; k < nT; k++) {                                    // :3223-3245
-      const double v = r[k];
-      acc[k] += v; rpMat[k] = v;
-      if (!(v > nbRp[nB - 1])) continue;
-      for (int n1 = 0; n1 < nB; n1++)
-        if (v > nbRp[n1]) {
-          for (int n2 = nB - 1; n2 > n1; n2--) { nbRp[n2] = nbRp[n2 - 1]; nbDoa[2 * n2] = nbDoa[2 * n2 - 2]; nbDoa[2 * n2 + 1] = nbDoa[2 * n2 - 1]; }
-          nbRp[n1] = v; nbDoa[2 * n1] = th[k]; nbDoa[2 * n1 + 1] = 0.0; break;
-        }
+    if (energy < H::threshold(est)) return vec.data();     // gated: no accumulation, no N-best, _vector as it was (:3215-3221)
+    served(t);
+    const int nB = H::nbest(est);
+    const double* r = RP.data() + (size_t) t * nU;
+    for (int k = 0; k < nU; k++) {                          // :3223-3245, :922-946
+      acc[k] += r[k]; rpMat[k] = r[k];
+      nbest_insert(nbRp.data(), nbIdx.data(), nB, r[k], k);
     }
-    const float2* y = Yh.data() + (size_t) t * F;
-    for (int f = fmin; f <= fmax; f++) {                              // the last unit's bins and their conjugate mirror (:3166-3176)
+    set_doas();
+    const float2* y = Yh.data() + (size_t) t * this->F;
+    for (int f = fmin; f <= fmax; f++) {                    // the last unit's bins and their conjugate mirror (:3166-3176, _calcResponsePower :874-889)
       vec[2 * f] = y[f].x; vec[2 * f + 1] = y[f].y;
       if (f > 0 && f < M / 2) { vec[2 * (M - f)] = y[f].x; vec[2 * (M - f) + 1] = -(double) y[f].y; }   // bin 0's mirror would be index M: not written
     }
     return vec.data();
   }
-  void range(int& fmin, int& fmax) { dsr_status st = dsr_doa_frequency_range(doa, &fmin, &fmax); if (st) throw Error(st, "%s", dsr_last_error()); }
+  void range(int& fmin, int& fmax) { ok(H::range(est, &fmin, &fmax)); }
+  // getNBestRPs, getNBestDOAs, getResponsePowerMatrix, getAccumulators, getEnergy
+  void get(int what, double* out, size_t outDoubles, size_t* n) {
+    if (nbRp.empty()) reset_nbest();
+    if (what < 0 || what > 4) throw Error(DSR_E_PARAMETER, "what %d", what);
+    const std::vector<double> e(1, (double) energy), none;
+    const std::vector<double>& v = what == 0 ? nbRp : what == 1 ? nbDoa : what == 2 ? (live() ? rpMat : none) : what == 3 ? (live() ? acc : none) : e;
+    if (outDoubles < v.size()) throw Error(DSR_E_DIMENSION, "output holds %zu doubles, %zu needed", outDoubles, v.size());
+    std::copy(v.begin(), v.end(), out); *n = v.size();
+  }
+  void init_accs() {                  // _initAccs (beamformer.cc:3027-3041)
+    std::fill(acc.begin(), acc.end(), 0.0); std::fill(rpMat.begin(), rpMat.end(), 0.0); reset_nbest();
+  }
+  void final_nbest() {                // _getNBestHypothesesFromACCRP (beamformer.cc:2986-3025): the DOA is the unit's (theta, phi)
+    if (!live()) throw Error(DSR_E_ERROR, "no accumulators: run the estimator after construction / setSearchParam first");
+    reset_nbest();
+    ok(H::final_nbest(est, acc.data(), 1, nbRp.data(), nbIdx.data()));
+    set_doas(); rpMat = acc;
+  }
 };
+
+struct LinSrp {                      // the calls of a dsr_doa; a unit is (theta_k, _minPhi = 0)
+  typedef dsr_doa Handle;
+  static constexpr const char* notThis = "not a DOAEstimatorSRPDSBLA";
+  static int chan_n(const Handle* h) { return dsr_doa_chan_n(h); }
+  static int nbest(const Handle* h) { return dsr_doa_nbest(h); }
+  static unsigned generation(const Handle* h) { return dsr_doa_table_generation(h); }
+  static bool has_table(const Handle* h) { return dsr_doa_has_table(h) != 0; }
+  static float threshold(const Handle* h) { return dsr_doa_energy_threshold(h); }
+  static dsr_status range(const Handle* h, int* lo, int* hi) { return dsr_doa_frequency_range(h, lo, hi); }
+  static dsr_status build_table(Handle* h) { return dsr_doa_build_table(h); }
+  static void grid(Handle* h, std::vector<double>& th, std::vector<double>& ph) {
+    int n = 0; ok(dsr_doa_theta_n(h, &n)); th.assign(n, 0.0); ph.assign(n, 0.0); ok(dsr_doa_thetas(h, th.data(), n));
+  }
+  static constexpr auto srp = dsr_doa_srp;
+  static constexpr auto final_nbest = dsr_doa_final_nbest;
+};
+struct SphSrp {                      // the calls of a dsr_sph; the units are the (theta, phi) grid, theta-major
+  typedef dsr_sph Handle;
+  static constexpr const char* notThis = "not a spherical DOA estimator";
+  static int chan_n(const Handle* h) { return dsr_sph_chan_n(h); }
+  static int nbest(const Handle* h) { return dsr_sph_nbest(h); }
+  static unsigned generation(const Handle* h) { return dsr_sph_table_generation(h); }
+  static bool has_table(const Handle* h) { return dsr_sph_has_table(h) != 0; }
+  static float threshold(const Handle* h) { return dsr_sph_energy_threshold(h); }
+  static dsr_status range(const Handle* h, int* lo, int* hi) { return dsr_sph_frequency_range(h, lo, hi); }
+  static dsr_status build_table(Handle* h) { return dsr_sph_build_table(h); }
+  static void grid(Handle* h, std::vector<double>& th, std::vector<double>& ph) {
+    int nT = 0, nP = 0; ok(dsr_sph_grid_n(h, &nT, &nP)); th.assign((size_t) nT * nP, 0.0); ph.assign((size_t) nT * nP, 0.0);
+    ok(dsr_sph_grid(h, th.data(), ph.data(), nT * nP));
+  }
+  static constexpr auto srp = dsr_sph_srp;
+  static constexpr auto final_nbest = dsr_sph_final_nbest;
+};
+
+struct DoaOp : SrpFace<BfOp, LinSrp> { void pack_frames() override { pack_half(); } };
 
 struct SphBfOp : BfOp {              // EigenBeamformer / SphericalDSBeamformer as a stream (modalBeamformer.cc:347-399)
   // the utterance is materialised at the first pull; a geometry, look-direction, sigma2 or gain change since (the handle's settings generation)
   // recomputes it at the next pull, the frame counter kept.  The eigenbeams (getSnapShotArray) are computed on the device only when asked for.
-  dsr_sph* sph = nullptr; int T = 0, F = 0, dim = 0; DevBuf<int> nf; DevBuf<float2> dF, dYs; unsigned setGen = ~0u; bool eigenDone = false;
+  dsr_sph* sph = nullptr; int dim = 0; DevBuf<float2> dF, dYs; unsigned setGen = ~0u; bool eigenDone = false;
   int eigenFrame = -1; bool eigenRange = false; int eigenLo = 0, eigenHi = 0;
   void pack() {                       // X [C][T][F] of the channels' frames
     const int C = (int) ups.size();
     if (C == 0 || C != dsr_sph_chan_n(sph)) throw Error(DSR_E_DIMENSION, "Number of channels (%d) does not match the beamformer (%d)", C, dsr_sph_chan_n(sph));
-    T = ups[0]->nFrames; for (int c = 1; c < C; c++) if (ups[c]->nFrames < T) T = ups[c]->nFrames;
-    F = M / 2 + 1; dim = dsr_sph_dim(sph); eigenDone = false; setGen = dsr_sph_settings_generation(sph);
-    if (T <= 0) return;
-    X.reserve((size_t) C * T * F);
-    for (int c = 0; c < C; c++) op_pack_bins(ups[c]->d<double2>(), T, F, M, X.p + (size_t) c * T * F, S0);
-    nf.upload(&T, 1);
+    dim = dsr_sph_dim(sph); eigenDone = false; setGen = dsr_sph_settings_generation(sph);
+    pack_half();
   }
   void compute() override {
     pack(); alloc(T); if (T <= 0) return;
     Y.reserve((size_t) T * F);
-    dsr_status st = dsr_sph_apply(sph, (const float*) X.p, nf.p, 1, T, (float*) Y.p, nullptr, S0); if (st) throw Error(st, "%s", dsr_last_error());
+    ok(dsr_sph_apply(sph, (const float*) X.p, nf.p, 1, T, (float*) Y.p, nullptr, S0));
     op_expand_bins(Y.p, T, F, M, d<double2>(), S0);
   }
   bool settings_moved() const { return ready && setGen != dsr_sph_settings_generation(sph); }
@@ -332,7 +407,7 @@ struct SphBfOp : BfOp {              // EigenBeamformer / SphericalDSBeamformer 
     if (eigenFrame >= 0 && eigenFrame < T) {
       if (!eigenDone) {
         dF.reserve((size_t) T * F * dim); dYs.reserve((size_t) T * F);
-        dsr_status st = dsr_sph_apply(sph, (const float*) X.p, nf.p, 1, T, (float*) dYs.p, (float*) dF.p, S0); if (st) throw Error(st, "%s", dsr_last_error());
+        ok(dsr_sph_apply(sph, (const float*) X.p, nf.p, 1, T, (float*) dYs.p, (float*) dF.p, S0));
         eigenDone = true;
       }
       DSR_HIP(hipMemcpy(fr.data(), dF.p + (size_t) eigenFrame * F * dim, sizeof(float2) * fr.size(), hipMemcpyDeviceToHost));
@@ -346,79 +421,11 @@ struct SphBfOp : BfOp {              // EigenBeamformer / SphericalDSBeamformer 
   }
 };
 
-struct SphDoaOp : SphBfOp {          // DOAEstimatorSRPEB / DOAEstimatorSRPSphDSB as a stream (modalBeamformer.cc:860-950, :1284-1370)
-  unsigned gen = 0, seenGen = ~0u; int nU = 0, nT = 0, nP = 0;
-  std::vector<float> E; std::vector<double> RP; std::vector<float2> Yh;              // the materialised utterance: energy, rp, last unit's bins
-  std::vector<double> acc, rpMat, nbRp, nbDoa, vec, gth, gph; float energy = 0.f; bool haveAcc = false;
-  DevBuf<float> dE; DevBuf<double> dRP, dAcc, dNbR; DevBuf<int> dNbI; DevBuf<float2> dY; int rangeUsed[2] = {-1, -1};
-  void compute() override {
-    const int C = (int) ups.size();
-    if (C == 0 || C != dsr_sph_chan_n(sph)) throw Error(DSR_E_DIMENSION, "Number of channels (%d) does not match the estimator (%d)", C, dsr_sph_chan_n(sph));
-    range(rangeUsed[0], rangeUsed[1]);
-    dsr_status st = dsr_sph_build_table(sph); if (st) throw Error(st, "%s", dsr_last_error());
-    st = dsr_sph_grid_n(sph, &nT, &nP); if (st) throw Error(st, "%s", dsr_last_error());
-    nU = nT * nP; gth.assign(nU, 0.0); gph.assign(nU, 0.0);
-    st = dsr_sph_grid(sph, gth.data(), gph.data(), nU); if (st) throw Error(st, "%s", dsr_last_error());
-    pack();                                                  // X packed; the eigenbeams only when getSnapShotArray asks
-    nFrames = T; eigenRange = true; eigenLo = rangeUsed[0]; eigenHi = rangeUsed[1];
-    if (T <= 0) return;
-    const int nB = dsr_sph_nbest(sph);
-    dY.reserve((size_t) T * F); dE.reserve(T); dRP.reserve((size_t) T * nU); dAcc.reserve(nU);
-    dNbR.reserve((size_t) T * nB); dNbI.reserve((size_t) T * nB);
-    DSR_HIP(hipMemsetAsync(dY.p, 0, sizeof(float2) * (size_t) T * F, S0)); DSR_HIP(hipMemsetAsync(dAcc.p, 0, sizeof(double) * nU, S0));
-    st = dsr_sph_srp(sph, (const float*) X.p, nf.p, 1, T, dE.p, dRP.p, dNbR.p, dNbI.p, dAcc.p, (float*) dY.p, nullptr, S0);
-    if (st) throw Error(st, "%s", dsr_last_error());
-    E.resize(T); RP.resize((size_t) T * nU); Yh.resize((size_t) T * F);
-    DSR_HIP(hipMemcpy(E.data(), dE.p, sizeof(float) * T, hipMemcpyDeviceToHost));
-    DSR_HIP(hipMemcpy(RP.data(), dRP.p, sizeof(double) * RP.size(), hipMemcpyDeviceToHost));
-    DSR_HIP(hipMemcpy(Yh.data(), dY.p, sizeof(float2) * Yh.size(), hipMemcpyDeviceToHost));
-  }
-  void sync_table() {                 // a new steering table: _accRPs and _rpMat start from zero (:818-820, allocDebugWorkSapce)
-    const unsigned g = dsr_sph_table_generation(sph);
-    if (g != seenGen) { acc.assign(nU, 0.0); rpMat.assign(nU, 0.0); haveAcc = true; seenGen = g; }
-  }
-  void reset_nbest() {
-    const int nB = dsr_sph_nbest(sph); nbRp.assign(nB, -10e10); nbDoa.assign((size_t) 2 * nB, -M_PI);
-  }
-  const void* next(int fx) override {
-    if (vec.empty()) vec.assign((size_t) 2 * M, 0.0);
-    if (fx == frameX && frameX >= 0) return vec.data();
-    reset_nbest();                                          // before anything else, the end of the stream included (:866-870)
-    int fmin = 0, fmax = 0; range(fmin, fmax);
-    if (ready && (gen != dsr_sph_table_generation(sph) || !dsr_sph_has_table(sph) || fmin != rangeUsed[0] || fmax != rangeUsed[1] || settings_moved()))
-      ready = false;                                        // setSearchParam (a new table), setFrequencyRange or a new geometry since: the rest of the utterance anew
-    if (!ready) {
-      require_device();
-      for (size_t i = 0; i < ups.size(); i++) ups[i]->materialize();
-      const int keep = eigenFrame; compute(); eigenFrame = keep; gen = dsr_sph_table_generation(sph); ready = true;
-    }
-    sync_table();
-    if (frameX + 1 >= nFrames) { endOfSamples = true; throw Error(DSR_E_ITERATOR, "end of samples!"); }
-    frameX++;
-    const int t = frameX;
-    energy = E[t];
-    if (energy < dsr_sph_energy_threshold(sph)) return vec.data();     // gated: no accumulation, no N-best, _vector and the eigenbeams as they were
-    eigenFrame = t;
-    const int nB = dsr_sph_nbest(sph);
-    const double* r = RP.data() + (size_t) t * nU;
-    for (int k = 0; k < nU; k++) {                                    // :922-946
-      const double v = r[k];
-      acc[k] += v; rpMat[k] = v;
-      if (!(v > nbRp[nB - 1])) continue;
-      for (int n1 = 0; n1 < nB; n1++)
-        if (v > nbRp[n1]) {
-          for (int n2 = nB - 1; n2 > n1; n2--) { nbRp[n2] = nbRp[n2 - 1]; nbDoa[2 * n2] = nbDoa[2 * n2 - 2]; nbDoa[2 * n2 + 1] = nbDoa[2 * n2 - 1]; }
-          nbRp[n1] = v; nbDoa[2 * n1] = gth[k]; nbDoa[2 * n1 + 1] = gph[k]; break;
-        }
-    }
-    const float2* y = Yh.data() + (size_t) t * F;
-    for (int f = fmin; f <= fmax; f++) {                              // the last unit's bins and their conjugate mirror (_calcResponsePower :874-889)
-      vec[2 * f] = y[f].x; vec[2 * f + 1] = y[f].y;
-      if (f > 0 && f < M / 2) { vec[2 * (M - f)] = y[f].x; vec[2 * (M - f) + 1] = -(double) y[f].y; }
-    }
-    return vec.data();
-  }
-  void range(int& fmin, int& fmax) { dsr_status st = dsr_sph_frequency_range(sph, &fmin, &fmax); if (st) throw Error(st, "%s", dsr_last_error()); }
+// the eigenbeams of the DOA operator: its range only, of the last ungated frame (a re-materialisation keeps it), anew after a settings change
+struct SphDoaOp : SrpFace<SphBfOp, SphSrp> {
+  void pack_frames() override { pack(); eigenRange = true; eigenLo = rangeUsed[0]; eigenHi = rangeUsed[1]; }   // the eigenbeams themselves only when getSnapShotArray asks
+  bool moved() const override { return settings_moved(); }
+  void served(int t) override { eigenFrame = t; }
 };
 
 struct OrthOp : dsr_stream {         // SubbandOrthogonalizer(beamformer, outChanX) (beamformer.cc:2817-2849): ups[0] = the SubbandMVDRGSC operator
@@ -428,7 +435,7 @@ struct OrthOp : dsr_stream {         // SubbandOrthogonalizer(beamformer, outCha
     const int T = bf->nFrames; alloc(T); if (T <= 0) return;
     if (outChanX <= 0) { DSR_HIP(hipMemcpyAsync(d<double2>(), bf->d<double2>(), sizeof(double2) * (size_t) T * size_, hipMemcpyDeviceToDevice, S0)); return; }
     const int F = bf->M / 2 + 1; Z.reserve((size_t) T * F);
-    dsr_status s = dsr_bf_blocking_matrix_output(bf->w, (const float*) bf->X.p, 1, T, outChanX - 1, (float*) Z.p, S0); if (s) throw Error(s, "%s", dsr_last_error());
+    ok(dsr_bf_blocking_matrix_output(bf->w, (const float*) bf->X.p, 1, T, outChanX - 1, (float*) Z.p, S0));
     op_orth_assemble(Z.p, bf->d<double2>(), T, F, bf->M, d<double2>(), S0);
   }
 };
@@ -438,8 +445,7 @@ struct WpeOp : dsr_stream {          // SingleChannelWPEDereverberationFeature (
     const int T = ups[0]->nFrames; alloc(T); if (T <= 0) return;
     const int F = M / 2 + 1; Y.reserve((size_t) T * F); O.reserve((size_t) T * F);
     op_pack_bins(ups[0]->d<double2>(), T, F, M, Y.p, S0); nf.upload(&T, 1);
-    dsr_status s = dsr_wpe_single((const float*) Y.p, nf.p, 1, T, M, lowerN, upperN, iterationsN, loadDb, bandWidth, sampleRate, (float*) O.p, nullptr, S0);
-    if (s) throw Error(s, "%s", dsr_last_error());
+    ok(dsr_wpe_single((const float*) Y.p, nf.p, 1, T, M, lowerN, upperN, iterationsN, loadDb, bandWidth, sampleRate, (float*) O.p, nullptr, S0));
     op_expand_bins(O.p, T, F, M, d<double2>(), S0);
   }
 };
@@ -448,15 +454,14 @@ struct WpeMultiOp : dsr_stream {     // MultiChannelWPEDereverberationFeature(so
   DevBuf<float2> Y, O; DevBuf<double2> G; DevBuf<int> nf;
   void compute() override {
     const int C = (int) ups.size();
-    int T = ups[0]->nFrames; for (int c = 1; c < C; c++) if (ups[c]->nFrames < T) T = ups[c]->nFrames;      // _fillBuffer stops with the shortest channel (:397-412)
+    const int T = shortest(this, 0, C);                     // _fillBuffer stops with the shortest channel (:397-412)
     alloc(T); if (T <= 0) return;
     const int F = M / 2 + 1, P = upperN - lowerN + 1; Y.reserve((size_t) C * T * F); O.reserve((size_t) C * T * F); G.reserve((size_t) C * F * C * P);
-    for (int c = 0; c < C; c++) op_pack_bins(ups[c]->d<double2>(), T, F, M, Y.p + (size_t) c * T * F, S0);
+    pack_channels(this, 0, C, T, F, M, Y.p);
     nf.upload(&T, 1);
     // all channels of a frame go through the filter of the channel that asked first (:381); on its own a feature asks first itself
     const int fc = filterChan == -2 ? channelX : filterChan;
-    dsr_status s = dsr_wpe_multi((const float*) Y.p, nf.p, 1, C, T, M, lowerN, upperN, iterationsN, loadDb, bandWidth, sampleRate, fc, (float*) O.p, (double*) G.p, S0);
-    if (s) throw Error(s, "%s", dsr_last_error());
+    ok(dsr_wpe_multi((const float*) Y.p, nf.p, 1, C, T, M, lowerN, upperN, iterationsN, loadDb, bandWidth, sampleRate, fc, (float*) O.p, (double*) G.p, S0));
     op_expand_bins(O.p + (size_t) channelX * T * F, T, F, M, d<double2>(), S0);
   }
 };
@@ -465,12 +470,12 @@ struct AecOp : dsr_stream {          // the echo cancellers of btk/cancelVP as a
   void ensure_state() {
     if (haveState) return;
     state.reserve(dsr_aec_state_bytes(aec, 1));
-    dsr_status s = dsr_aec_state_init(aec, state.p, 1, S0); if (s) throw Error(s, "%s", dsr_last_error());
+    ok(dsr_aec_state_init(aec, state.p, 1, S0));
     haveState = true;
   }
   void reset() override {                // cancelVP.h:60, :98, :134-142: filter coefficients only (NLMS, Kalman) or nothing (block variants)
     dsr_stream::reset();
-    if (haveState) { dsr_status s = dsr_aec_reset_filter(aec, state.p, 1, S0); if (s) throw Error(s, "%s", dsr_last_error()); }
+    if (haveState) ok(dsr_aec_reset_filter(aec, state.p, 1, S0));
   }
   const void* next(int fx) override { if (!ready) frameMode = fx < 0 ? 1 : 0; return dsr_stream::next(fx); }
   void compute() override {
@@ -478,9 +483,8 @@ struct AecOp : dsr_stream {          // the echo cancellers of btk/cancelVP as a
     ensure_state();
     const int F = M / 2 + 1; P.reserve((size_t) T * F); Rc.reserve((size_t) T * F); O.reserve((size_t) T * F);
     op_pack_bins(ups[0]->d<double2>(), T, F, M, P.p, S0); op_pack_bins(ups[1]->d<double2>(), T, F, M, Rc.p, S0); nf.upload(&T, 1);
-    dsr_status s = dsr_aec_set_frame_mode(aec, dsr_aec_kind(aec) == DSR_AEC_DTD ? frameMode : 0);
-    if (!s) s = dsr_aec_apply(aec, (const float*) P.p, (const float*) Rc.p, nf.p, 1, T, 0, (float*) O.p, state.p, S0);
-    if (s) throw Error(s, "%s", dsr_last_error());
+    ok(dsr_aec_set_frame_mode(aec, dsr_aec_kind(aec) == DSR_AEC_DTD ? frameMode : 0));
+    ok(dsr_aec_apply(aec, (const float*) P.p, (const float*) Rc.p, nf.p, 1, T, 0, (float*) O.p, state.p, S0));
     op_expand_bins(O.p, T, F, M, d<double2>(), S0);
   }
 };
@@ -490,9 +494,8 @@ struct ZelinskiOp : dsr_stream {     // ZelinskiPostFilter (postfilter.cc:350-49
   double minSV = 1e-8; int fbinX1 = 0;                     // kind 2: LefkimmiatisPostFilter
   void ensure_plan(int C) {
     if (plan) return;
-    dsr_status s = kind == 2 ? dsr_lefkimmiatis_create(M, C, minSV, fbinX1, alpha, ptype, minFrames, threshold, &plan)
-                 : kind ? dsr_mccowan_create(M, C, alpha, ptype, minFrames, threshold, &plan) : dsr_zelinski_create(M, C, alpha, ptype, minFrames, &plan);
-    if (s) throw Error(s, "%s", dsr_last_error());
+    ok(kind == 2 ? dsr_lefkimmiatis_create(M, C, minSV, fbinX1, alpha, ptype, minFrames, threshold, &plan)
+       : kind ? dsr_mccowan_create(M, C, alpha, ptype, minFrames, threshold, &plan) : dsr_zelinski_create(M, C, alpha, ptype, minFrames, &plan));
   }
   DevBuf<float2> X, Y, O; DevBuf<int> nf;
   ~ZelinskiOp() override { if (plan) dsr_zelinski_destroy(plan); }
@@ -500,20 +503,34 @@ struct ZelinskiOp : dsr_stream {     // ZelinskiPostFilter (postfilter.cc:350-49
     const int C = (int) ups.size() - 1;
     if (C < 1 || chanSet == 0) throw Error(DSR_E_ERROR, "set beamformer's weights");                     // postfilter.cc:447-450
     if (chanSet != C) throw Error(DSR_E_DIMENSION, "array manifold has %d channels, the snapshot array %d", chanSet, C);
-    int T = ups[0]->nFrames; for (int c = 1; c <= C; c++) if (ups[c]->nFrames < T) T = ups[c]->nFrames;
+    const int T = shortest(this, 0, C + 1);
     alloc(T); if (T <= 0) return;
-    ensure_plan(C); dsr_status s;
+    ensure_plan(C);
     for (int f = 0; f <= M / 2; f++) if (!manifold[f].empty()) dsr_zelinski_set_manifold(plan, f, manifold[f].data());
     const int F = M / 2 + 1; X.reserve((size_t) C * T * F); Y.reserve((size_t) T * F); O.reserve((size_t) T * F);
-    for (int c = 0; c < C; c++) op_pack_bins(ups[c + 1]->d<double2>(), T, F, M, X.p + (size_t) c * T * F, S0);
+    pack_channels(this, 1, C, T, F, M, X.p);
     op_pack_bins(ups[0]->d<double2>(), T, F, M, Y.p, S0);
     nf.upload(&T, 1);
-    s = dsr_zelinski_apply(plan, (const float*) X.p, (const float*) Y.p, nf.p, 1, T, (float*) O.p, nullptr, S0); if (s) throw Error(s, "%s", dsr_last_error());
+    ok(dsr_zelinski_apply(plan, (const float*) X.p, (const float*) Y.p, nf.p, 1, T, (float*) O.p, nullptr, S0));
     op_expand_bins(O.p, T, F, M, d<double2>(), S0);
   }
 };
 
 template <class T> T* mk(const char* name, const char* dflt, int size, int type) { T* s = new T(); s->name = (name && *name) ? name : dflt; s->size_ = size; s->type = type; return s; }
+// what the filter-bank operators' create functions share: the operator (order unchecked, `bins` bins a frame on the bank's side) owns the plan
+// that `plan` creates into it, and is handed out on top of `up` only when that succeeded
+template <class Op, class Plan> void bank_create(dsr_stream* up, const char* name, const char* dflt, int size, int type, int bins, dsr_stream** out, Plan plan)
+{
+  std::unique_ptr<Op> s(mk<Op>(name, dflt, size, type)); s->bins = bins; s->checkOrder = false;
+  ok(plan(*s));
+  s->add_up(up); *out = s.release();
+}
+// a stream handle as the operator Op, or Op's own refusal
+template <class Op> Op& srp_op(dsr_stream* s, bool argsOk = true)
+{
+  Op* q = dynamic_cast<Op*>(s); if (!q || !argsOk) throw Error(DSR_E_PARAMETER, "%s", Op::Calls::notThis);
+  return *q;
+}
 dsr_stream* need(dsr_stream* s, int type, const char* what) {
   if (!s) throw Error(DSR_E_PARAMETER, "null upstream for %s", what);
   if (s->type != type) throw Error(DSR_E_TYPE, "%s needs an upstream of element type %d, got %d", what, type, s->type);
@@ -662,9 +679,8 @@ dsr_status dsr_analysis_bank_create(dsr_stream* samp, const double* prototype, i
     need(samp, DSR_T_FLOAT, "OverSampledDFTAnalysisBank"); if (!out || !prototype) throw Error(DSR_E_PARAMETER, "null argument");
     const int D = M >> r;
     if (samp->size_ != D) throw Error(DSR_E_DIMENSION, "Input block length (%d) != _D (%d)", samp->size_, D);      // modulated.cc:373-374
-    AnalysisOp* s = mk<AnalysisOp>(name, "OverSampledDFTAnalysisBank", M, DSR_T_COMPLEX); s->M = M; s->D = D; s->checkOrder = false;
-    dsr_status st = dsr_fb_create(prototype, M, m, r, 0, dct, 1, &s->fb); if (st) { delete s; throw Error(st, "%s", dsr_last_error()); }
-    s->add_up(samp); *out = s;
+    bank_create<AnalysisOp>(samp, name, "OverSampledDFTAnalysisBank", M, DSR_T_COMPLEX, M / 2 + 1, out,
+                            [&](AnalysisOp& s) { s.skipEmpty = true; return dsr_fb_create(prototype, M, m, r, 0, dct, 1, &s.fb); });
   });
 }
 dsr_status dsr_pr_analysis_bank_create(dsr_stream* samp, const double* prototype, int M, int m, int r, const char* name, dsr_stream** out)
@@ -673,9 +689,8 @@ dsr_status dsr_pr_analysis_bank_create(dsr_stream* samp, const double* prototype
     need(samp, DSR_T_FLOAT, "PerfectReconstructionFFTAnalysisBank"); if (!out || !prototype) throw Error(DSR_E_PARAMETER, "null argument");
     const int D = M >> r;
     if (samp->size_ != D) throw Error(DSR_E_DIMENSION, "Input block length (%d) != _D (%d)", samp->size_, D);
-    PrAnalysisOp* s = mk<PrAnalysisOp>(name, "PerfectReconstructionFFTAnalysisBank", 2 * M, DSR_T_COMPLEX); s->M2 = 2 * M; s->D = D; s->checkOrder = false;
-    dsr_status st = dsr_prfb_create(prototype, M, m, r, &s->fb); if (st) { delete s; throw Error(st, "%s", dsr_last_error()); }
-    s->add_up(samp); *out = s;
+    bank_create<PrAnalysisOp>(samp, name, "PerfectReconstructionFFTAnalysisBank", 2 * M, DSR_T_COMPLEX, 2 * M, out,
+                              [&](PrAnalysisOp& s) { return dsr_prfb_create(prototype, M, m, r, &s.fb); });
   });
 }
 dsr_status dsr_pr_synthesis_bank_create(dsr_stream* samp, const double* prototype, int M, int m, int r, const char* name, dsr_stream** out)
@@ -683,9 +698,8 @@ dsr_status dsr_pr_synthesis_bank_create(dsr_stream* samp, const double* prototyp
   return guard([&] {
     need(samp, DSR_T_COMPLEX, "PerfectReconstructionFFTSynthesisBank"); if (!out || !prototype) throw Error(DSR_E_PARAMETER, "null argument");
     if (samp->size_ != 2 * M) throw Error(DSR_E_DIMENSION, "Input size (%d) != 2M (%d)", samp->size_, 2 * M);
-    PrSynthesisOp* s = mk<PrSynthesisOp>(name, "PerfectReconstructionFFTSynthesisBank", M >> r, DSR_T_FLOAT); s->M2 = 2 * M; s->D = M >> r; s->checkOrder = false;
-    dsr_status st = dsr_prfb_create(prototype, M, m, r, &s->fb); if (st) { delete s; throw Error(st, "%s", dsr_last_error()); }
-    s->add_up(samp); *out = s;
+    bank_create<PrSynthesisOp>(samp, name, "PerfectReconstructionFFTSynthesisBank", M >> r, DSR_T_FLOAT, 2 * M, out,
+                               [&](PrSynthesisOp& s) { return dsr_prfb_create(prototype, M, m, r, &s.fb); });
   });
 }
 dsr_status dsr_normal_fft_bank_create(dsr_stream* samp, int M, int r, int windowType, const char* name, dsr_stream** out)
@@ -694,9 +708,7 @@ dsr_status dsr_normal_fft_bank_create(dsr_stream* samp, int M, int r, int window
     need(samp, DSR_T_FLOAT, "NormalFFTAnalysisBank"); if (!out) throw Error(DSR_E_PARAMETER, "null argument");
     const int D = M >> r;
     if (samp->size_ != D) throw Error(DSR_E_DIMENSION, "Input block length (%d) != _D (%d)", samp->size_, D);      // modulated.cc:138-139
-    StftOp* s = mk<StftOp>(name, "NormalFFTAnalysisBank", M, DSR_T_COMPLEX); s->M = M; s->D = D; s->checkOrder = false;
-    dsr_status st = dsr_stft_create(M, r, windowType, &s->plan); if (st) { delete s; throw Error(st, "%s", dsr_last_error()); }
-    s->add_up(samp); *out = s;
+    bank_create<StftOp>(samp, name, "NormalFFTAnalysisBank", M, DSR_T_COMPLEX, M, out, [&](StftOp& s) { return dsr_stft_create(M, r, windowType, &s.plan); });
   });
 }
 dsr_status dsr_synthesis_bank_create(dsr_stream* samp, const double* prototype, int M, int m, int r, int dct, int gain, const char* name, dsr_stream** out)
@@ -704,9 +716,8 @@ dsr_status dsr_synthesis_bank_create(dsr_stream* samp, const double* prototype, 
   return guard([&] {
     need(samp, DSR_T_COMPLEX, "OverSampledDFTSynthesisBank"); if (!out || !prototype) throw Error(DSR_E_PARAMETER, "null argument");
     if (samp->size_ != M) throw Error(DSR_E_DIMENSION, "Input size (%d) != M (%d)", samp->size_, M);
-    SynthesisOp* s = mk<SynthesisOp>(name, "OverSampledDFTSynthesisBank", M >> r, DSR_T_FLOAT); s->M = M; s->D = M >> r; s->checkOrder = false;
-    dsr_status st = dsr_fb_create(prototype, M, m, r, 1, dct, gain, &s->fb); if (st) { delete s; throw Error(st, "%s", dsr_last_error()); }
-    s->add_up(samp); *out = s;
+    bank_create<SynthesisOp>(samp, name, "OverSampledDFTSynthesisBank", M >> r, DSR_T_FLOAT, M / 2 + 1, out,
+                             [&](SynthesisOp& s) { s.hermitian = true; return dsr_fb_create(prototype, M, m, r, 1, dct, gain, &s.fb); });
   });
 }
 dsr_status dsr_wpe_single_stream_create(dsr_stream* samples, int lowerN, int upperN, int iterationsN, double loadDb, double bandWidth, double sampleRate,
@@ -754,7 +765,7 @@ dsr_status dsr_aec_stream_get(dsr_stream* s, int what, double* out, size_t outDo
     require_device(); q->ensure_state();
     const size_t F = (size_t) q->M / 2 + 1, L = (size_t) dsr_aec_sample_n(q->aec);
     const size_t cnt = what == DSR_AEC_STATE_K ? F * L * L * 2 : what == DSR_AEC_STATE_SIGMA2V ? F : what == DSR_AEC_STATE_DTD ? 3 : F * L * 2;
-    dsr_status st = dsr_aec_state_read(q->aec, q->state.p, 1, what, out, outDoubles); if (st) throw Error(st, "%s", dsr_last_error());
+    ok(dsr_aec_state_read(q->aec, q->state.p, 1, what, out, outDoubles));
     if (n) *n = cnt;
   });
 }
@@ -804,7 +815,7 @@ dsr_status dsr_mccowan_stream_set_noise(dsr_stream* pf, int what, int fbinX, con
     case 3: s = dsr_mccowan_divide_nondiagonal(q->plan, (float) a); break;
     default: throw Error(DSR_E_PARAMETER, "bad selector %d", what);
     }
-    if (s) throw Error(s, "%s", dsr_last_error());
+    ok(s);
     q->ready = false;
   });
 }
@@ -843,46 +854,14 @@ dsr_status dsr_doa_stream_create(dsr_doa* doa, const char* name, dsr_stream** ou
 {
   return guard([&] {
     if (!doa || !out) throw Error(DSR_E_PARAMETER, "null argument");
-    DoaOp* s = mk<DoaOp>(name, "DOAEstimatorSRPDSBLAPtr", dsr_doa_fft_len(doa), DSR_T_COMPLEX); s->w = nullptr; s->doa = doa; s->M = dsr_doa_fft_len(doa);
+    DoaOp* s = mk<DoaOp>(name, "DOAEstimatorSRPDSBLAPtr", dsr_doa_fft_len(doa), DSR_T_COMPLEX); s->w = nullptr; s->est = doa; s->M = dsr_doa_fft_len(doa);
     s->checkOrder = false; *out = s;
   });
 }
 dsr_status dsr_doa_stream_get(dsr_stream* s, int what, double* out, size_t outDoubles, size_t* n)
-{
-  return guard([&] {
-    DoaOp* q = dynamic_cast<DoaOp*>(s); if (!q || !out || !n) throw Error(DSR_E_PARAMETER, "not a DOAEstimatorSRPDSBLA");
-    if (q->nbRp.empty()) q->reset_nbest();
-    const std::vector<double> e(1, (double) q->energy);
-    const std::vector<double> none;                          // setSearchParam freed _accRPs and _rpMat until the next table (:2962-2984)
-    const bool live = q->haveAcc && dsr_doa_has_table(q->doa) && q->seenGen == dsr_doa_table_generation(q->doa);
-    const std::vector<double>& v = what == 0 ? q->nbRp : what == 1 ? q->nbDoa : what == 2 ? (live ? q->rpMat : none) : what == 3 ? (live ? q->acc : none) : e;
-    if (what < 0 || what > 4) throw Error(DSR_E_PARAMETER, "what %d", what);
-    if (outDoubles < v.size()) throw Error(DSR_E_DIMENSION, "output holds %zu doubles, %zu needed", outDoubles, v.size());
-    std::copy(v.begin(), v.end(), out); *n = v.size();
-  });
-}
-dsr_status dsr_doa_stream_init_accs(dsr_stream* s)
-{
-  return guard([&] {                                        // _initAccs (:3027-3041)
-    DoaOp* q = dynamic_cast<DoaOp*>(s); if (!q) throw Error(DSR_E_PARAMETER, "not a DOAEstimatorSRPDSBLA");
-    std::fill(q->acc.begin(), q->acc.end(), 0.0); std::fill(q->rpMat.begin(), q->rpMat.end(), 0.0); q->reset_nbest();
-  });
-}
-dsr_status dsr_doa_stream_final_nbest(dsr_stream* s)
-{
-  return guard([&] {                                        // _getNBestHypothesesFromACCRP (:2986-3025): the DOA is (theta_k, _minPhi = 0)
-    DoaOp* q = dynamic_cast<DoaOp*>(s); if (!q) throw Error(DSR_E_PARAMETER, "not a DOAEstimatorSRPDSBLA");
-    if (!q->haveAcc || !dsr_doa_has_table(q->doa) || q->seenGen != dsr_doa_table_generation(q->doa))
-      throw Error(DSR_E_ERROR, "no accumulators: run the estimator after construction / setSearchParam first");
-    const int nB = dsr_doa_nbest(q->doa), nT = (int) q->acc.size();
-    std::vector<double> R(nB), th(nT); std::vector<int32_t> I(nB);
-    dsr_status st = dsr_doa_final_nbest(q->doa, q->acc.data(), 1, R.data(), I.data()); if (st) throw Error(st, "%s", dsr_last_error());
-    st = dsr_doa_thetas(q->doa, th.data(), nT); if (st) throw Error(st, "%s", dsr_last_error());
-    q->reset_nbest();
-    for (int n = 0; n < nB; n++) if (I[n] >= 0) { q->nbRp[n] = R[n]; q->nbDoa[2 * n] = th[I[n]]; q->nbDoa[2 * n + 1] = 0.0; }
-    q->rpMat = q->acc;
-  });
-}
+{ return guard([&] { srp_op<DoaOp>(s, out && n).get(what, out, outDoubles, n); }); }
+dsr_status dsr_doa_stream_init_accs(dsr_stream* s) { return guard([&] { srp_op<DoaOp>(s).init_accs(); }); }
+dsr_status dsr_doa_stream_final_nbest(dsr_stream* s) { return guard([&] { srp_op<DoaOp>(s).final_nbest(); }); }
 dsr_status dsr_sph_bf_stream_create(dsr_sph* sph, const char* name, dsr_stream** out)
 {
   return guard([&] {
@@ -907,45 +886,14 @@ dsr_status dsr_sph_doa_stream_create(dsr_sph* sph, const char* name, dsr_stream*
   return guard([&] {
     if (!sph || !out) throw Error(DSR_E_PARAMETER, "null argument");
     const char* dflt = "DirectionEstimatorSRPMB";               // both classes' default name (beamformer.i:539, :624)
-    SphDoaOp* s = mk<SphDoaOp>(name, dflt, dsr_sph_fft_len(sph), DSR_T_COMPLEX); s->w = nullptr; s->sph = sph; s->M = dsr_sph_fft_len(sph);
+    SphDoaOp* s = mk<SphDoaOp>(name, dflt, dsr_sph_fft_len(sph), DSR_T_COMPLEX); s->w = nullptr; s->sph = s->est = sph; s->M = dsr_sph_fft_len(sph);
     s->checkOrder = false; *out = s;
   });
 }
 dsr_status dsr_sph_doa_stream_get(dsr_stream* s, int what, double* out, size_t outDoubles, size_t* n)
-{
-  return guard([&] {
-    SphDoaOp* q = dynamic_cast<SphDoaOp*>(s); if (!q || !out || !n) throw Error(DSR_E_PARAMETER, "not a spherical DOA estimator");
-    if (q->nbRp.empty()) q->reset_nbest();
-    const std::vector<double> e(1, (double) q->energy);
-    const std::vector<double> none;                          // setSearchParam freed _accRPs and _rpMat until the next table (clearTable)
-    const bool live = q->haveAcc && dsr_sph_has_table(q->sph) && q->seenGen == dsr_sph_table_generation(q->sph);
-    if (what < 0 || what > 4) throw Error(DSR_E_PARAMETER, "what %d", what);
-    const std::vector<double>& v = what == 0 ? q->nbRp : what == 1 ? q->nbDoa : what == 2 ? (live ? q->rpMat : none) : what == 3 ? (live ? q->acc : none) : e;
-    if (outDoubles < v.size()) throw Error(DSR_E_DIMENSION, "output holds %zu doubles, %zu needed", outDoubles, v.size());
-    std::copy(v.begin(), v.end(), out); *n = v.size();
-  });
-}
-dsr_status dsr_sph_doa_stream_init_accs(dsr_stream* s)
-{
-  return guard([&] {                                        // _initAccs (beamformer.cc:3027-3041)
-    SphDoaOp* q = dynamic_cast<SphDoaOp*>(s); if (!q) throw Error(DSR_E_PARAMETER, "not a spherical DOA estimator");
-    std::fill(q->acc.begin(), q->acc.end(), 0.0); std::fill(q->rpMat.begin(), q->rpMat.end(), 0.0); q->reset_nbest();
-  });
-}
-dsr_status dsr_sph_doa_stream_final_nbest(dsr_stream* s)
-{
-  return guard([&] {                                        // _getNBestHypothesesFromACCRP (beamformer.cc:2986-3025): the DOA is (theta, phi) of the unit
-    SphDoaOp* q = dynamic_cast<SphDoaOp*>(s); if (!q) throw Error(DSR_E_PARAMETER, "not a spherical DOA estimator");
-    if (!q->haveAcc || !dsr_sph_has_table(q->sph) || q->seenGen != dsr_sph_table_generation(q->sph))
-      throw Error(DSR_E_ERROR, "no accumulators: run the estimator after construction / setSearchParam first");
-    const int nB = dsr_sph_nbest(q->sph);
-    std::vector<double> R(nB); std::vector<int32_t> I(nB);
-    dsr_status st = dsr_sph_final_nbest(q->sph, q->acc.data(), 1, R.data(), I.data()); if (st) throw Error(st, "%s", dsr_last_error());
-    q->reset_nbest();
-    for (int n = 0; n < nB; n++) if (I[n] >= 0) { q->nbRp[n] = R[n]; q->nbDoa[2 * n] = q->gth[I[n]]; q->nbDoa[2 * n + 1] = q->gph[I[n]]; }
-    q->rpMat = q->acc;
-  });
-}
+{ return guard([&] { srp_op<SphDoaOp>(s, out && n).get(what, out, outDoubles, n); }); }
+dsr_status dsr_sph_doa_stream_init_accs(dsr_stream* s) { return guard([&] { srp_op<SphDoaOp>(s).init_accs(); }); }
+dsr_status dsr_sph_doa_stream_final_nbest(dsr_stream* s) { return guard([&] { srp_op<SphDoaOp>(s).final_nbest(); }); }
 dsr_status dsr_subband_orthogonalizer_create(dsr_stream* beamformer, int outChanX, const char* name, dsr_stream** out)
 {
   return guard([&] {
@@ -1018,11 +966,11 @@ dsr_status dsr_mel_create(dsr_stream* mag, int powN, float rate, float low, floa
 {
   return guard([&] {
     need(mag, DSR_T_DOUBLE, "MelFeature"); const int P = powN == 0 ? mag->size_ : powN;
-    MelOp* s = mk<MelOp>(name, "MelFFT", filterN, DSR_T_DOUBLE); SparseRowsF r; build_mel_rows(P, rate, low, up, filterN, version, r);
-    if (mag->size_ < r.nReq) { delete s; throw Error(DSR_E_CONSISTENCY, "Matrix columns differ: %d and %d.", mag->size_, r.nReq); }
-    for (size_t i = 0; i < r.start.size(); i++) if (r.start[i] + r.count[i] > mag->size_) { delete s; throw Error(DSR_E_CONSISTENCY, "mel filter %zu reads past the input", i); }
+    std::unique_ptr<MelOp> s(mk<MelOp>(name, "MelFFT", filterN, DSR_T_DOUBLE)); SparseRowsF r; build_mel_rows(P, rate, low, up, filterN, version, r);
+    if (mag->size_ < r.nReq) throw Error(DSR_E_CONSISTENCY, "Matrix columns differ: %d and %d.", mag->size_, r.nReq);
+    for (size_t i = 0; i < r.start.size(); i++) if (r.start[i] + r.count[i] > mag->size_) throw Error(DSR_E_CONSISTENCY, "mel filter %zu reads past the input", i);
     require_device(); s->s.upload(r.start); s->c.upload(r.count); s->o.upload(r.off); s->coef.upload(r.coef); s->inN = mag->size_;
-    s->add_up(mag); *out = s;
+    s->add_up(mag); *out = s.release();
   });
 }
 dsr_status dsr_log_create(dsr_stream* mel, double m, double a, int sphinx, const char* name, dsr_stream** out)
@@ -1040,7 +988,7 @@ dsr_status dsr_lpc_feature_create(dsr_stream* src, int order, int correlate, flo
   return guard([&] {
     need(src, DSR_T_FLOAT, kind ? "LPCFeature" : "MVDRFeature");
     dsr_lpc* plan = nullptr;
-    dsr_status s0 = dsr_lpc_create(src->size_, order, correlate, warp, method, kind, &plan); if (s0) throw Error(s0, "%s", dsr_last_error());
+    ok(dsr_lpc_create(src->size_, order, correlate, warp, method, kind, &plan));
     LpcOp* s = mk<LpcOp>(name, kind ? "LPC" : "MVDR", src->size_ / 2 + 1, DSR_T_DOUBLE); s->plan = plan; s->add_up(src); *out = s;
   });
 }
@@ -1082,7 +1030,7 @@ dsr_status dsr_linear_transform_load(dsr_stream* s, const char* fileName, int ol
     GemvOp* q = dynamic_cast<GemvOp*>(s); if (!q || !fileName) throw Error(DSR_E_PARAMETER, "not a linear transform");
     const int rows = q->size_, cols = q->ups[0]->size_;
     std::vector<float> m((size_t) rows * cols, 0.0f); int r2 = 0, c2 = 0;
-    const dsr_status st = dsr_fmat_load(fileName, old, rows, cols, m.data(), &r2, &c2); if (st) throw Error(st, "%s", dsr_last_error());
+    ok(dsr_fmat_load(fileName, old, rows, cols, m.data(), &r2, &c2));
     if (r2 < rows) throw Error(DSR_E_DIMENSION, "Cannot resize from %d to %d", r2, rows);           // the crop back to (size x srcSize)
     if (c2 < cols) throw Error(DSR_E_DIMENSION, "Cannot resize from %d to %d", c2, cols);
     q->hA = m; q->A.upload(q->hA); q->ready = false;
@@ -1164,7 +1112,7 @@ dsr_status dsr_distribset_score(dsr_distribset* d, int distX, int frameX, float*
       const int t = d->feat->frameX;
       d->d_row.reserve((size_t) K); d->row.resize((size_t) K);
       const float* x = reinterpret_cast<const float*>(d->feat->dev.p) + (size_t) t * d->feat->size_;
-      const dsr_status s = dsr_gmm_score(d->gmm, x, 1, d->mode, d->d_row.p, nullptr, S0); if (s) throw Error(s, "%s", dsr_last_error());
+      ok(dsr_gmm_score(d->gmm, x, 1, d->mode, d->d_row.p, nullptr, S0));
       DSR_HIP(hipMemcpy(d->row.data(), d->d_row.p, sizeof(float) * (size_t) K, hipMemcpyDeviceToHost));
       d->cachedFrame = t;
     }
@@ -1182,8 +1130,8 @@ dsr_status dsr_decoder_decode_stream(dsr_decoder* dec, dsr_distribset* d, dsr_de
     const int T = d->feat->nFrames, K = dsr_gmm_num_dists(d->gmm);
     if (T <= 0) { d->feat->endOfSamples = true; throw Error(DSR_E_ITERATOR, "end of samples!"); }
     d->d_scores.reserve((size_t) T * K); d->d_T.upload(&T, 1);
-    dsr_status s = dsr_gmm_score(d->gmm, reinterpret_cast<const float*>(d->feat->dev.p), (int64_t) T, d->mode, d->d_scores.p, nullptr, S0); if (s) throw Error(s, "%s", dsr_last_error());
-    s = dsr_decoder_decode_batch(dec, d->d_scores.p, d->d_T.p, 1, T, K, res, arcs_out, words_out, maxPath, S0); if (s) throw Error(s, "%s", dsr_last_error());
+    ok(dsr_gmm_score(d->gmm, reinterpret_cast<const float*>(d->feat->dev.p), (int64_t) T, d->mode, d->d_scores.p, nullptr, S0));
+    ok(dsr_decoder_decode_batch(dec, d->d_scores.p, d->d_T.p, 1, T, K, res, arcs_out, words_out, maxPath, S0));
     d->feat->frameX = T - 1; d->feat->endOfSamples = true;                   // the reference has pulled the stream to its end
     if (res->status != DSR_OK) throw Error(res->status, "decode failed (status %d)", res->status);
   });
@@ -1219,7 +1167,7 @@ dsr_status dsr_lattice_gamma_probs_dist(dsr_lattice* L, dsr_distribset* d, doubl
     if (!link.empty()) {
       if (T <= 0) throw Error(DSR_E_ITERATOR, "end of samples!");
       d->d_scores.reserve((size_t) T * K);
-      const dsr_status s = dsr_gmm_score(d->gmm, reinterpret_cast<const float*>(d->feat->dev.p), (int64_t) T, d->mode, d->d_scores.p, nullptr, S0); if (s) throw Error(s, "%s", dsr_last_error());
+      ok(dsr_gmm_score(d->gmm, reinterpret_cast<const float*>(d->feat->dev.p), (int64_t) T, d->mode, d->d_scores.p, nullptr, S0));
       DevBuf<int> dd, ds, de; DevBuf<double> dout; dd.upload(dist); ds.upload(start); de.upload(end); dout.reserve(link.size());
       op_link_ac(d->d_scores.p, K, dd.p, ds.p, de.p, (int) link.size(), dout.p, S0);
       DSR_HIP(hipGetLastError());

@@ -488,6 +488,63 @@ struct AecOp : dsr_stream {          // the echo cancellers of btk/cancelVP as a
     op_expand_bins(O.p, T, F, M, d<double2>(), S0);
   }
 };
+struct CctdeOp : dsr_stream {        // CCTDE (CCTDE.h:60-101, CCTDE.cc:46-342): ups = the two SampleFeatures; a row = the nHeldMaxCC delays in seconds
+  int N = 0, nHeld = 1, lower = -1, upper = -1;      // the band limits are kept and, as in the reference, never used (CCTDE.cc:186-205 cannot be reached)
+  std::vector<int> allArgs, args; std::vector<double> allVals, vals, vec; DevBuf<double> dVals, dOne; DevBuf<int> dArgs, dArg1; DevBuf<float> pad; bool whole = false;
+  int rate() const { return static_cast<const SampleSrc*>(ups[0])->sampleRate; }
+  void reset() override { dsr_stream::reset(); whole = false; }
+  // every block pair of the utterance in one call; next() then serves rows while the two sources move together
+  void compute() override {
+    const int T = shortest(this, 0, 2); alloc(T); allArgs.assign((size_t) T * nHeld, 0); allVals.assign((size_t) T * nHeld, 0.0); if (T <= 0) return;
+    dVals.reserve((size_t) T * nHeld); dArgs.reserve((size_t) T * nHeld);
+    ok(dsr_cctde_run(ups[0]->d<float>(), ups[1]->d<float>(), T, ups[0]->size_, N, nHeld, rate(), d<double>(), dArgs.p, dVals.p, S0));
+    DSR_HIP(hipMemcpy(allArgs.data(), dArgs.p, allArgs.size() * sizeof(int), hipMemcpyDeviceToHost));
+    DSR_HIP(hipMemcpy(allVals.data(), dVals.p, allVals.size() * 8, hipMemcpyDeviceToHost));
+  }
+  // one pair of blocks that is not a row of the batch: the sources stand at different frames (nextX), or a whole recording (allsamples)
+  const void* one(const float* a, const float* b, int blockLen, int fftLen) {
+    dOne.reserve(2 * (size_t) nHeld); dArg1.reserve(nHeld); args.assign(nHeld, 0); vals.assign(nHeld, 0.0); vec.assign(nHeld, 0.0);
+    ok(dsr_cctde_run(a, b, 1, blockLen, fftLen, nHeld, rate(), dOne.p, dArg1.p, dOne.p + nHeld, S0));
+    DSR_HIP(hipMemcpy(vec.data(), dOne.p, (size_t) nHeld * 8, hipMemcpyDeviceToHost)); DSR_HIP(hipMemcpy(vals.data(), dOne.p + nHeld, (size_t) nHeld * 8, hipMemcpyDeviceToHost));
+    DSR_HIP(hipMemcpy(args.data(), dArg1.p, (size_t) nHeld * sizeof(int), hipMemcpyDeviceToHost));
+    return vec.data();
+  }
+  const void* serve() {
+    const int f0 = ups[0]->frameX, f1 = ups[1]->frameX, L = ups[0]->size_;
+    if (f0 != f1) return one(ups[0]->d<float>() + (size_t) f0 * L, ups[1]->d<float>() + (size_t) f1 * L, L, N);
+    materialize();
+    args.assign(allArgs.begin() + (size_t) f0 * nHeld, allArgs.begin() + (size_t) (f0 + 1) * nHeld);
+    vals.assign(allVals.begin() + (size_t) f0 * nHeld, allVals.begin() + (size_t) (f0 + 1) * nHeld);
+    const double* r = (const double*) row(f0); vec.assign(r, r + nHeld);
+    return vec.data();
+  }
+  const void* next(int fx) override {                      // CCTDE.cc:146-155: both sources move on
+    if (fx == frameX && (frameX >= 0 || whole)) return vec.data();
+    try { ups[0]->next(fx); ups[1]->next(fx); } catch (const Error&) { endOfSamples = true; throw; }
+    whole = false; frameX++;
+    return serve();
+  }
+  const void* nextX(int chanX, int fx) {                   // CCTDE.cc:262-302: source chanX moves on, the other one's current block is used again
+    if (chanX < 0 || chanX > 1) throw Error(DSR_E_INDEX, "channel %d of 2", chanX);
+    if (ups[1 - chanX]->frameX < 0) throw Error(DSR_E_CONSISTENCY, "Frame index (%d) < 0.", ups[1 - chanX]->frameX);
+    try { ups[chanX]->next(fx); } catch (const Error&) { endOfSamples = true; throw; }
+    whole = false; if (chanX == 0) frameX++;
+    return serve();
+  }
+  void allsamples(int fftLen) {                            // CCTDE.cc:304-342: the two recordings as one block pair; the FFT length stays changed
+    const SampleSrc* s0 = static_cast<const SampleSrc*>(ups[0]); const SampleSrc* s1 = static_cast<const SampleSrc*>(ups[1]);
+    const size_t n0 = s0->samples.size(), n1 = s1->samples.size(), nmax = n0 > n1 ? n0 : n1;
+    int L = fftLen;
+    if (L < 0) { size_t p2 = 1; while (p2 < nmax) p2 *= 2; if (p2 > (size_t) 1 << 30) throw Error(DSR_E_DIMENSION, "%zu samples", nmax); L = (int) p2; }
+    ok(dsr_cctde_check(L, nHeld)); require_device();
+    N = L;
+    const size_t bl = nmax < (size_t) L ? (nmax ? nmax : 1) : (size_t) L;
+    std::vector<float> h(2 * bl, 0.0f);
+    std::copy(s0->samples.begin(), s0->samples.begin() + (n0 < bl ? n0 : bl), h.begin()); std::copy(s1->samples.begin(), s1->samples.begin() + (n1 < bl ? n1 : bl), h.begin() + bl);
+    pad.upload(h.data(), h.size());
+    one(pad.p, pad.p + bl, (int) bl, L); whole = true;
+  }
+};
 struct ZelinskiOp : dsr_stream {     // ZelinskiPostFilter (postfilter.cc:350-493): ups[0] = beamformer output, ups[1..] = the snapshot array's channels
   dsr_zelinski* plan = nullptr; int M = 0; double alpha = 0.6; int ptype = 2, minFrames = 0; std::vector<std::vector<double>> manifold; int chanSet = 0;
   int kind = 0; float threshold = 0.99f;                   // kind 1: McCowanPostFilter (the plan then also carries the noise coherence matrices)
@@ -649,6 +706,13 @@ dsr_status dsr_sample_feature_read(dsr_stream* s, const char* fn, int format, in
   });
 }
 int dsr_sample_feature_sample_rate(const dsr_stream* s) { const SampleSrc* q = dynamic_cast<const SampleSrc*>(s); return q ? q->sampleRate : 0; }
+dsr_status dsr_sample_feature_data(const dsr_stream* s, const float** data, size_t* n)
+{
+  return guard([&] {
+    const SampleSrc* q = dynamic_cast<const SampleSrc*>(s); if (!q || !data || !n) throw Error(DSR_E_PARAMETER, "not a SampleFeature");
+    *data = q->samples.data(); *n = q->samples.size();
+  });
+}
 
 dsr_status dsr_frame_source_create(int type, int size, const char* name, dsr_stream** out)
 {
@@ -758,6 +822,34 @@ dsr_status dsr_aec_stream_create(dsr_aec* aec, dsr_stream* played, dsr_stream* r
     s->aec = aec; s->M = played->size_; s->add_up(played); s->add_up(recorded); *out = s;
   });
 }
+dsr_status dsr_cctde_stream_create(dsr_stream* samp1, dsr_stream* samp2, int fftLen, int nHeldMaxCC, int freqLowerLimit, int freqUpperLimit, const char* name,
+                                   dsr_stream** out)
+{
+  return guard([&] {
+    if (!out) throw Error(DSR_E_PARAMETER, "null argument");
+    const SampleSrc* a = dynamic_cast<const SampleSrc*>(samp1); const SampleSrc* b = dynamic_cast<const SampleSrc*>(samp2);
+    if (!a || !b) throw Error(DSR_E_TYPE, "CCTDE needs two SampleFeatures");
+    if (a->sampleRate != b->sampleRate) throw Error(DSR_E_DIMENSION, "The sampling rates must be the same but %d != %d", a->sampleRate, b->sampleRate);   // CCTDE.cc:76-80
+    if (a->size_ != b->size_) throw Error(DSR_E_DIMENSION, "Block sizes must be the same but %d != %d", a->size_, b->size_);
+    (void) fftLen;                                                       // ignored there too: the length is the power of two that holds a block (CCTDE.cc:62-63)
+    int N = 1; while (N < a->size_) N *= 2;
+    ok(dsr_cctde_check(N, nHeldMaxCC));
+    CctdeOp* s = mk<CctdeOp>(name, "CCTDE", nHeldMaxCC, DSR_T_DOUBLE);
+    s->N = N; s->nHeld = nHeldMaxCC; s->lower = freqLowerLimit; s->upper = freqUpperLimit; s->vec.assign(nHeldMaxCC, 0.0); s->args.assign(nHeldMaxCC, 0); s->vals.assign(nHeldMaxCC, 0.0);
+    s->checkOrder = false; s->add_up(samp1); s->add_up(samp2); *out = s;
+  });
+}
+namespace { CctdeOp* cctde_op(dsr_stream* s) { CctdeOp* q = dynamic_cast<CctdeOp*>(s); if (!q) throw Error(DSR_E_PARAMETER, "not a CCTDE stream"); return q; } }
+dsr_status dsr_cctde_stream_next_x(dsr_stream* s, int chanX, int frameX, const void** data, size_t* n)
+{ return guard([&] { CctdeOp& q = *cctde_op(s); if (!data) throw Error(DSR_E_PARAMETER, "null argument"); *data = q.nextX(chanX, frameX); if (n) *n = (size_t) q.nHeld; }); }
+dsr_status dsr_cctde_stream_allsamples(dsr_stream* s, int fftLen) { return guard([&] { cctde_op(s)->allsamples(fftLen); }); }
+dsr_status dsr_cctde_stream_get_sample_delays(dsr_stream* s, const int32_t** lags, size_t* n)
+{ return guard([&] { CctdeOp& q = *cctde_op(s); if (!lags) throw Error(DSR_E_PARAMETER, "null argument"); *lags = q.args.data(); if (n) *n = q.args.size(); }); }
+dsr_status dsr_cctde_stream_get_cc_values(dsr_stream* s, const double** values, size_t* n)
+{ return guard([&] { CctdeOp& q = *cctde_op(s); if (!values) throw Error(DSR_E_PARAMETER, "null argument"); *values = q.vals.data(); if (n) *n = q.vals.size(); }); }
+dsr_status dsr_cctde_stream_set_target_frequency_range(dsr_stream* s, int freqLowerLimit, int freqUpperLimit)
+{ return guard([&] { CctdeOp& q = *cctde_op(s); q.lower = freqLowerLimit; q.upper = freqUpperLimit; }); }
+int dsr_cctde_stream_fft_len(const dsr_stream* s) { const CctdeOp* q = dynamic_cast<const CctdeOp*>(s); return q ? q->N : 0; }
 dsr_status dsr_aec_stream_get(dsr_stream* s, int what, double* out, size_t outDoubles, size_t* n)
 {
   return guard([&] {

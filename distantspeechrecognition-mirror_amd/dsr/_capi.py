@@ -543,6 +543,99 @@ class Aec:
         check(_lib.dsr_aec_reset_filter(self.h, _dev(state), int(U), cur_stream()))
 
 
+class Gcc:
+    """The GCC family of btk/localization (include/dsr.h section 2e): kind "raw", "gnnsub", "phat", "gnnsubphat", "mlrraw" or "mlrgnnsub".
+    The handle holds the pair list [P][2] and the parameters (defaults of localization.h:123); what the estimator carries from frame to
+    frame is a device buffer of the caller (newState) that run() continues from and leaves behind."""
+    KINDS = {"raw": 0, "gnnsub": 1, "phat": 2, "gnnsubphat": 3, "mlrraw": 4, "mlrgnnsub": 5}
+    HUGE = float(np.finfo(np.float32).max)                       # <math.h> HUGE, findMaximum's default window (localization.h:126)
+    NOISE_POWER, NOISE_CROSS, CROSS, CORRELATION = 0, 1, 2, 3
+
+    def __init__(self, kind, pairs, sampleRate=44100.0, fftLen=2048, nChan=16, alpha=0.95, beta=0.5, q=0.3, interpolate=True, noisereduction=True):
+        L = load(); self.h = vp(); self.kind = self.KINDS[kind] if isinstance(kind, str) else int(kind)
+        self.pairs = _np(pairs, np.int32).reshape(-1, 2); self.P = self.pairs.shape[0]; self.C = int(nChan); self.N = int(fftLen); self.F = self.N // 2 + 1
+        self.sampleRate = float(sampleRate)
+        check(L.dsr_gcc_create(self.kind, float(sampleRate), int(fftLen), int(nChan), _ptr(self.pairs), self.P, float(alpha), float(beta), float(q),
+                               int(bool(interpolate)), int(bool(noisereduction)), C.byref(self.h)))
+
+    def __del__(self):
+        if _lib is not None and getattr(self, "h", None):
+            _lib.dsr_gcc_destroy(self.h)
+
+    def setAlpha(self, alpha):
+        check(_lib.dsr_gcc_set_alpha(self.h, float(alpha)))
+
+    def getAlpha(self):
+        return float(_lib.dsr_gcc_alpha(self.h))
+
+    def stateBytes(self, U):
+        return int(_lib.dsr_gcc_state_bytes(self.h, int(U)))
+
+    def newState(self, U, device="cuda:0"):
+        import torch
+        st = torch.zeros((self.stateBytes(U) + 7) // 8, dtype=torch.float64, device=device)
+        check(_lib.dsr_gcc_state_init(self.h, _dev(st), int(U), cur_stream()))
+        return st
+
+    def run(self, X, sad, timestamp, state, nframes=None, smooth=True, minDelay=None, maxDelay=None, want_corr=False, want_xspec=False):
+        """X cuda complex64 or complex128 [U][C][T][fftLen/2+1], sad [U][T] (non-zero = speech), timestamp [U][T] float64 ->
+        dict(result [U][T][P][3] = delay, maxCorr, ratio; valid [U][T][P] int32; corr [U][T][P][fftLen] and xspec [U][T][P][fftLen/2+1] on request)"""
+        import torch
+        U, Cn, T, F = X.shape
+        if Cn != self.C or F != self.F or X.dtype not in (torch.complex64, torch.complex128):
+            raise ValueError("X: complex64 or complex128 [U][%d][T][%d] expected" % (self.C, self.F))
+        dev = X.device
+        sad = sad.to(device=dev, dtype=torch.int32).contiguous(); timestamp = timestamp.to(device=dev, dtype=torch.float64).contiguous()
+        if tuple(sad.shape) != (U, T) or tuple(timestamp.shape) != (U, T):
+            raise ValueError("sad, timestamp: [U][T] expected")
+        r = dict(result=torch.zeros((U, T, self.P, 3), dtype=torch.float64, device=dev), valid=torch.zeros((U, T, self.P), dtype=torch.int32, device=dev))
+        r["corr"] = torch.zeros((U, T, self.P, self.N), dtype=torch.float64, device=dev) if want_corr else None
+        r["xspec"] = torch.zeros((U, T, self.P, F), dtype=torch.complex128, device=dev) if want_xspec else None
+        Xc = torch.view_as_real(X.contiguous())
+        check(_lib.dsr_gcc_run(self.h, _dev(Xc), int(X.dtype == torch.complex128), _dev(nframes) if nframes is not None else None, _dev(sad), _dev(timestamp),
+                               int(bool(smooth)), float(-self.HUGE if minDelay is None else minDelay), float(self.HUGE if maxDelay is None else maxDelay), U, T,
+                               _dev(state), _dev(r["result"]), _dev(r["valid"]), _dev(r["corr"]) if want_corr else None,
+                               _dev(torch.view_as_real(r["xspec"])) if want_xspec else None, cur_stream()))
+        return r
+
+    def findMaximum(self, state, U, minDelay=None, maxDelay=None):
+        """findMaximum over the carried correlations -> (result [U][P][3], valid [U][P]) on the device"""
+        import torch
+        res = torch.zeros((U, self.P, 3), dtype=torch.float64, device=state.device); valid = torch.zeros((U, self.P), dtype=torch.int32, device=state.device)
+        check(_lib.dsr_gcc_find_maximum(self.h, float(-self.HUGE if minDelay is None else minDelay), float(self.HUGE if maxDelay is None else maxDelay), int(U),
+                                        _dev(state), _dev(res), _dev(valid), cur_stream()))
+        return res, valid
+
+    def read(self, state, U, what, u, index):
+        """-> (array, exists): noise power [F] float64, noise cross-spectrum / cross-spectrum [F] complex128, correlation [fftLen] float64"""
+        cplx = what in (1, 2); n = self.N if what == 3 else self.F
+        out = np.zeros(n, np.complex128 if cplx else np.float64); ex = C.c_int32(0)
+        check(_lib.dsr_gcc_state_read(self.h, _dev(state), int(U), int(what), int(u), int(index), _ptr(out), n * (2 if cplx else 1), C.byref(ex)))
+        return out, bool(ex.value)
+
+    def channelDelays(self, pairDelays):
+        """per-channel delays (channel 0 at zero) for dsr_bf_calc_array_manifold / Beamformer.calcArrayManifoldVectors from the P pair delays"""
+        d = _np(pairDelays, np.float64).ravel()
+        if d.size != self.P:
+            raise DsrError(E_DIMENSION, "%d pair delays for %d pairs" % (d.size, self.P))
+        out = np.zeros(self.C, np.float64); check(_lib.dsr_gcc_channel_delays(self.h, _ptr(d), _ptr(out))); return out
+
+
+def cctde(a, b, fftLen, nHeldMaxCC=1, sampleRate=16000):
+    """CCTDE::next over a batch of block pairs (dsr_cctde_run): a, b cuda float32 [n][blockLen] -> (delays [n][nHeld] seconds, lags as FFT
+    indices [n][nHeld] int32, correlation values [n][nHeld])"""
+    import torch
+    load()
+    a = a.to(torch.float32).contiguous(); b = b.to(torch.float32).contiguous()
+    if a.dim() != 2 or a.shape != b.shape:
+        raise ValueError("a, b: float32 [n][blockLen] of one shape expected")
+    n, bl = a.shape
+    d = torch.zeros((n, nHeldMaxCC), dtype=torch.float64, device=a.device); ar = torch.zeros((n, nHeldMaxCC), dtype=torch.int32, device=a.device)
+    v = torch.zeros((n, nHeldMaxCC), dtype=torch.float64, device=a.device)
+    check(_lib.dsr_cctde_run(_dev(a), _dev(b), int(n), int(bl), int(fftLen), int(nHeldMaxCC), int(sampleRate), _dev(d), _dev(ar), _dev(v), cur_stream()))
+    return d, ar, v
+
+
 class DoaSRP:
     """DOAEstimatorSRPDSBLA (btk/beamformer/beamformer.h:462-560, beamformer.cc:2920-3283) over a batch: settings and steering table on the
     host, the response powers of X [U][C][T][M/2+1] on the fp64 MFMA (dsr_doa_srp).  The accumulators belong to the caller."""

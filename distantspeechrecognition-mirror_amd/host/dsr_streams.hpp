@@ -162,6 +162,71 @@ DSR_LPC_OP(WarpLPCFeature, 0, 1, "LPC")
 DSR_LPC_OP(BurgLPCFeature, 1, 1, "LPC")
 #undef DSR_LPC_OP
 
+// ---- btk/localization/localization.h:118-218 and btk/TDEstimator/CCTDE.h:60-101.  The reference's gsl vectors are pointers to the items here:
+// calculate() takes fftLen complex bins a spectrum, the getters return pointers into the object's own buffers (a null pointer where the
+// reference has none: no noise frame yet), findMaximum() returns {delay, maxCorr, ratio}.
+typedef std::shared_ptr<SampleFeature> SampleFeaturePtr;
+class GCC {
+ public:
+  virtual ~GCC() { if (_g) dsr_gcc_destroy(_g); }
+  void calculate(const std::complex<double>* spectralSample1, unsigned chan1, const std::complex<double>* spectralSample2, unsigned chan2, unsigned pair, double timestamp,
+                 bool sad = false, bool smooth = true) {
+    dsr_throw(dsr_gcc_calculate(_g, (const double*) spectralSample1, (int) _fftLen, (int) chan1, (const double*) spectralSample2, (int) _fftLen, (int) chan2, (int) pair,
+                                timestamp, sad, smooth));
+    _pair = pair;
+  }
+  const double* findMaximum(double minDelay = -3.4028234663852886e+38, double maxDelay = 3.4028234663852886e+38) {     // <math.h> HUGE
+    int32_t valid = 0; dsr_throw(dsr_gcc_peak(_g, (int) _pair, minDelay, maxDelay, _ret, &valid)); return _ret;
+  }
+  double getPeakDelay() { return _ret[0]; }
+  double getPeakCorr() { return _ret[1]; }
+  double getRatio() { return _ret[2]; }
+  const double* getNoisePowerSpectrum(unsigned chan) { return get(DSR_GCC_STATE_NOISE_POWER, chan, _fftLen / 2 + 1, false); }
+  const std::complex<double>* getNoiseCrossSpectrum(unsigned pair) { return (const std::complex<double>*) get(DSR_GCC_STATE_NOISE_CROSS, pair, _fftLen + 2, false); }
+  const std::complex<double>* getCrossSpectrum() { return (const std::complex<double>*) get(DSR_GCC_STATE_CROSS, _pair, _fftLen + 2, true); }
+  const double* getCrossCorrelation() { return get(DSR_GCC_STATE_CORRELATION, _pair, _fftLen, true); }
+  void setAlpha(double alpha) { dsr_throw(dsr_gcc_set_alpha(_g, alpha)); }
+  double getAlpha() { return dsr_gcc_alpha(_g); }
+ protected:
+  GCC(int kind, double sampleRate, unsigned fftLen, unsigned nChan, unsigned pairs, double alpha, double beta, double q, bool interpolate, bool noisereduction)
+  : _g(0), _fftLen(fftLen), _pair(0) {
+    _ret[0] = _ret[1] = _ret[2] = 0.0;
+    std::vector<int32_t> list(2 * (size_t) (pairs ? pairs : 1), 0);                      // calculate() names the channels of a pair
+    dsr_throw(dsr_gcc_create(kind, sampleRate, (int) fftLen, (int) nChan, list.data(), (int) pairs, alpha, beta, q, interpolate, noisereduction, &_g));
+  }
+  const double* get(int what, unsigned index, size_t doubles, bool always) {
+    _buf.assign(doubles, 0.0); int32_t exists = 0;
+    dsr_throw(dsr_gcc_get(_g, what, (int) index, _buf.data(), doubles, &exists));
+    return (exists || always) ? _buf.data() : 0;
+  }
+  dsr_gcc* _g; unsigned _fftLen, _pair; double _ret[3]; std::vector<double> _buf;
+ private:
+  GCC(const GCC&); GCC& operator=(const GCC&);
+};
+#define DSR_GCC(cls, kind) class cls : public GCC { public: \
+  cls(double sampleRate = 44100.0, unsigned fftLen = 2048, unsigned nChan = 16, unsigned pairs = 6, double alpha = 0.95, double beta = 0.5, double q = 0.3, \
+      bool interpolate = true, bool noisereduction = true) : GCC(kind, sampleRate, fftLen, nChan, pairs, alpha, beta, q, interpolate, noisereduction) {} }; \
+  typedef std::shared_ptr<cls> cls##Ptr;
+DSR_GCC(GCCRaw, DSR_GCC_RAW) DSR_GCC(GCCGnnSub, DSR_GCC_GNNSUB) DSR_GCC(GCCPhat, DSR_GCC_PHAT) DSR_GCC(GCCGnnSubPhat, DSR_GCC_GNNSUBPHAT)
+DSR_GCC(GCCMLRRaw, DSR_GCC_MLRRAW) DSR_GCC(GCCMLRGnnSub, DSR_GCC_MLRGNNSUB)
+#undef DSR_GCC
+class CCTDE : public VectorFeatureStream {
+ public:
+  CCTDE(SampleFeaturePtr& samp1, SampleFeaturePtr& samp2, int fftLen = 512, unsigned nHeldMaxCC = 1, int freqLowerLimit = -1, int freqUpperLimit = -1, const String& nm = "CCTDE")
+  : _s1(samp1), _s2(samp2) {
+    DSR_OP(CCTDE, double, dsr_cctde_stream_create(samp1->handle(), samp2->handle(), fftLen, (int) nHeldMaxCC, freqLowerLimit, freqUpperLimit, nm.c_str(), &h))
+  }
+  void setTargetFrequencyRange(int freqLowerLimit, int freqUpperLimit) { dsr_throw(dsr_cctde_stream_set_target_frequency_range(_h, freqLowerLimit, freqUpperLimit)); }
+  void allsamples(int fftLen = -1) { dsr_throw(dsr_cctde_stream_allsamples(_h, fftLen)); }
+  virtual const double* nextX(unsigned chanX = 0, int frameX = -5) {
+    const void* p = 0; size_t n = 0; dsr_throw(dsr_cctde_stream_next_x(_h, (int) chanX, frameX, &p, &n)); return (const double*) p;
+  }
+  const unsigned* getSampleDelays() { const int32_t* p = 0; size_t n = 0; dsr_throw(dsr_cctde_stream_get_sample_delays(_h, &p, &n)); return (const unsigned*) p; }
+  const double* getCCValues() { const double* p = 0; size_t n = 0; dsr_throw(dsr_cctde_stream_get_cc_values(_h, &p, &n)); return p; }
+ private: SampleFeaturePtr _s1, _s2;
+};
+typedef std::shared_ptr<CCTDE> CCTDEPtr;
+
 // ---- btk/dereverberation/dereverberation.h
 class SingleChannelWPEDereverberationFeature : public VectorComplexFeatureStream {
  public:

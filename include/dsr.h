@@ -399,6 +399,93 @@ dsr_status dsr_aec_state_read(const dsr_aec*, const void* state_dev, int U, int 
 dsr_status dsr_aec_reset_filter(const dsr_aec*, void* state_dev, int U, void* stream);
 
 /* =====================================================================================
+ * 2e. Pairwise time-delay estimation: the GCC family and CCTDE
+ *     replaces GCCRaw, GCCGnnSub, GCCPhat, GCCGnnSubPhat, GCCMLRRaw, GCCMLRGnnSub (btk/localization/localization.h:75-218,
+ *     localization.cc:1156-1413, localization.i:94-143) and CCTDE (btk/TDEstimator/CCTDE.h:60-101, CCTDE.cc:46-342, TDEstimator.i)
+ * One handle serves the six weightings.  It holds the kind, the sizes, the pair list and the parameters; for the batch entries, what the
+ * reference keeps between calls (per channel: noise power and last timestamp; per pair: noise cross-spectrum, smoothed cross-spectrum,
+ * correlation) is caller-owned device memory, like the state of dsr_aec_apply, so blocks of a long stream chain exactly, and one handle
+ * may serve several states and streams.  The per-call entries (dsr_gcc_calculate, dsr_gcc_peak, dsr_gcc_get) are the reference's object
+ * as it is: they keep one utterance's state of their own inside the handle, take and return host data, are synchronous, and like that
+ * object are not for two threads at once.  Host-side pieces (create, setters, sizes, dsr_gcc_channel_delays, dsr_cctde_check) need no GPU.  Kept quirks and stated deviations: DESIGN 4.4j.
+ * ===================================================================================== */
+typedef struct dsr_gcc dsr_gcc;
+#define DSR_GCC_RAW        0
+#define DSR_GCC_GNNSUB     1
+#define DSR_GCC_PHAT       2
+#define DSR_GCC_GNNSUBPHAT 3
+#define DSR_GCC_MLRRAW     4
+#define DSR_GCC_MLRGNNSUB  5
+/* GCC(sampleRate, fftLen, nChan, pairs, alpha, beta, q, interpolate, noisereduction) (localization.h:123, localization.cc:1220-1248); the
+   reference's `pairs` is a count and calculate() names the channels, here the list pairs[pairsN][2] comes first.  The constructor's alpha is
+   honoured (the reference's loops that apply it run over an uninitialised index).  fftLen odd, not a power of two or outside [8, 4096] is
+   DSR_E_DIMENSION, a channel outside [0, chanN) DSR_E_INDEX.  noisereduction is stored and unused, as in the reference. */
+dsr_status dsr_gcc_create(int kind, double sampleRate, int fftLen, int chanN, const int32_t* pairs, int pairsN, double alpha, double beta, double q,
+                          int interpolate, int noisereduction, dsr_gcc** out);
+void       dsr_gcc_destroy(dsr_gcc*);
+/* setAlpha / getAlpha (localization.h:134-140) */
+dsr_status dsr_gcc_set_alpha(dsr_gcc*, double alpha);
+double     dsr_gcc_alpha(const dsr_gcc*);
+/* measuring (tools/bench_gcc.py): with timing on, dsr_gcc_run records events around k_gcc_spectrum and around k_gcc_corr; kernel_ms waits for
+   the last run and gives the two times in ms.  Off by default; the results do not change. */
+dsr_status dsr_gcc_set_timing(dsr_gcc*, int on);
+dsr_status dsr_gcc_kernel_ms(const dsr_gcc*, double* ms2);
+int        dsr_gcc_fft_len(const dsr_gcc*);
+int        dsr_gcc_pairs_n(const dsr_gcc*);
+int        dsr_gcc_chan_n(const dsr_gcc*);
+/* the caller's state for U utterances: bytes to allocate (0 for a bad argument), and the initial state (no noise estimate, last timestamps
+   0.0, zero cross-spectrum, no correlation) written into it */
+size_t     dsr_gcc_state_bytes(const dsr_gcc*, int U);
+dsr_status dsr_gcc_state_init(const dsr_gcc*, void* state_dev, int U, void* stream);
+/* The frame loop of a driver -- for every frame t < nframes[u], for every pair p: calculate(X[c1][t], c1, X[c2][t], c2, p, timestamp[t],
+ * sad[t], smooth) then findMaximum(minDelay, maxDelay) (localization.cc:1263-1340).  X_dev [U][chanN][Tmax][fftLen/2+1] complex64, or
+ * complex128 when xIsDouble; nframes_dev [U] (optional); sad_dev [U][Tmax] int32, non-zero = speech = "compute", zero = "learn noise";
+ * timestamp_dev [U][Tmax] double.  result_dev [U][Tmax][P][3] = delay (seconds), maxCorr, ratio; valid_dev [U][Tmax][P] = 0 until the pair's
+ * first speech frame (the reference's correlation is uninitialised until then), result zero there.  A non-speech frame repeats the answer
+ * of the last speech frame, searched with this call's window.  corr_dev (optional) [U][Tmax][P][fftLen] the correlation of every frame,
+ * xspec_dev (optional) [U][Tmax][P][fftLen/2+1] complex128 the cross-spectrum of the speech frames (the other rows are not written);
+ * without it the library keeps that intermediate itself.  Frames from nframes[u] on give zeros and do not touch the state.
+ * GCCGnnSub with a speech frame before any noise frame of its pair is DSR_E_ERROR (the reference dereferences NULL); the state is
+ * undefined afterwards.  The delay of pair (c1, c2) is tau_c1 - tau_c2 for arrival times tau. */
+dsr_status dsr_gcc_run(dsr_gcc*, const void* X_dev, int xIsDouble, const int32_t* nframes_dev, const int32_t* sad_dev, const double* timestamp_dev, int smooth,
+                       double minDelay, double maxDelay, int U, int Tmax, void* state_dev, double* result_dev, int32_t* valid_dev, double* corr_dev,
+                       void* xspec_dev, void* stream);
+/* findMaximum(minDelay, maxDelay) (localization.cc:1297-1340) over the correlation the state carries: result_dev [U][P][3], valid_dev [U][P] */
+dsr_status dsr_gcc_find_maximum(dsr_gcc*, double minDelay, double maxDelay, int U, const void* state_dev, double* result_dev, int32_t* valid_dev, void* stream);
+/* getNoisePowerSpectrum(chan) [fftLen/2+1], getNoiseCrossSpectrum(pair) [fftLen/2+1] complex128, getCrossSpectrum [fftLen/2+1] complex128,
+   getCrossCorrelation [fftLen] (localization.h:130-133) of utterance u (synchronous); index = channel or pair; *exists = 0 where the reference
+   would hand out NULL (no noise frame yet) or uninitialised memory (no speech frame yet).  A short buffer is DSR_E_DIMENSION. */
+#define DSR_GCC_STATE_NOISE_POWER 0
+#define DSR_GCC_STATE_NOISE_CROSS 1
+#define DSR_GCC_STATE_CROSS       2
+#define DSR_GCC_STATE_CORRELATION 3
+dsr_status dsr_gcc_state_read(const dsr_gcc*, const void* state_dev, int U, int what, int u, int index, double* host_out, size_t outDoubles, int32_t* exists);
+/* GCC::calculate(spectralSample1, chan1, spectralSample2, chan2, pair, timestamp, sad, smooth) (localization.h:125, localization.cc:1263-1295)
+   on the handle's own state: spec1, spec2 host complex128 of n1, n2 bins, of which the first fftLen/2+1 are used.  The call names the pair's
+   channels, as there; the handle's pair list is neither read nor changed.  sad != 0 with n1 != fftLen is DSR_E_DIMENSION as there, fewer than
+   fftLen/2+1 bins DSR_E_DIMENSION, a pair or channel out of range DSR_E_INDEX.  It runs the kernels of dsr_gcc_run with U = Tmax = 1. */
+dsr_status dsr_gcc_calculate(dsr_gcc*, const double* spec1, int n1, int chan1, const double* spec2, int n2, int chan2, int pair, double timestamp, int sad, int smooth);
+/* findMaximum(minDelay, maxDelay) of that state's pair -> out3 = delay, maxCorr, ratio (getPeakDelay, getPeakCorr, getRatio); *valid = 0 and
+   zeros before the pair's first speech frame */
+dsr_status dsr_gcc_peak(dsr_gcc*, int pair, double minDelay, double maxDelay, double* out3, int32_t* valid);
+/* the getters of dsr_gcc_state_read on that state */
+dsr_status dsr_gcc_get(dsr_gcc*, int what, int index, double* host_out, size_t outDoubles, int32_t* exists);
+/* Host side: per-channel delays from the pair delays of dsr_gcc_run, delays[0] = 0, by least squares over the pair graph (exact for pairs
+   against channel 0); a graph that does not connect every channel to channel 0 is DSR_E_PARAMETER.  Sign: pairDelays[p] = tau_c1 - tau_c2
+   is what the peak of X_c1 conj(X_c2) reports, and delays[c] = tau_c - tau_0 is the time the wavefront reaches channel c after channel 0 --
+   the convention of dsr_bf_calc_array_manifold (weights e^{-j omega delay}), so the result is handed to it unchanged. */
+dsr_status dsr_gcc_channel_delays(const dsr_gcc*, const double* pairDelays, double* delays);
+/* CCTDE's constructor checks (CCTDE.cc:65-68): nHeldMaxCC >= fftLen, and an fftLen that is not a power of two in [8, 2^22], are
+   DSR_E_DIMENSION.  Up to 4096 a workgroup transforms a block pair in LDS; longer ones (allsamples() over a recording: 2^22 samples are
+   4 min 22 s at 16 kHz) run in global memory, one workgroup per pair, which is meant for the odd call and not for throughput. */
+dsr_status dsr_cctde_check(int fftLen, int nHeldMaxCC);
+/* CCTDE::next for nItems block pairs (CCTDE.cc:146-302): a_dev, b_dev [nItems][blockLen] float, blockLen <= fftLen (zero-padded), Hann window
+   getWindow(2, fftLen), phase-only cross-correlation, the nHeldMaxCC largest values -> delays_dev [nItems][nHeldMaxCC] seconds (computed
+   through float as there), args_dev the lags as FFT indices (getSampleDelays; -1 = empty), values_dev the correlation values (getCCValues) */
+dsr_status dsr_cctde_run(const float* a_dev, const float* b_dev, int nItems, int blockLen, int fftLen, int nHeldMaxCC, int sampleRate, double* delays_dev,
+                         int32_t* args_dev, double* values_dev, void* stream);
+
+/* =====================================================================================
  * 3. MFCC feature chain
  *    replaces SampleFeature(block framing) -> PreemphasisFeature -> HammingFeature -> FFTFeature ->
  *    SpectralPowerFeature -> VTLNFeature -> MelFeature -> LogFeature -> CepstralFeature ->
@@ -864,6 +951,8 @@ dsr_status dsr_sample_feature_set_samples(dsr_stream*, const float* samples, siz
 dsr_status dsr_sample_feature_read(dsr_stream*, const char* fileName, int format, int samplerate, int chX, int chN, int cfrom, int to, int outsamplerate,
                                    float norm, int* nread);
 int        dsr_sample_feature_sample_rate(const dsr_stream*);
+/* SampleFeature::data() / samplesN() (feature.h): the whole sample buffer, owned by the stream, valid until the next read / setSamples */
+dsr_status dsr_sample_feature_data(const dsr_stream*, const float** data, size_t* n);
 /* PyFeatureStream equivalent (btk/stream/pyStream.h:44-130): a source whose frames the caller supplies;
    type is DSR_T_SHORT / DSR_T_FLOAT / DSR_T_DOUBLE / DSR_T_COMPLEX, data = nframes rows of `size` items */
 dsr_status dsr_frame_source_create(int type, int size, const char* name, dsr_stream** out);
@@ -916,6 +1005,24 @@ dsr_status dsr_wpe_multi_feature_set_filter_channel(dsr_stream* feature, int fil
  *   get: what = DSR_AEC_STATE_* -> out as dsr_aec_state_read with U = 1; *n = the doubles written */
 dsr_status dsr_aec_stream_create(dsr_aec* aec, dsr_stream* played, dsr_stream* recorded, const char* name, dsr_stream** out);
 dsr_status dsr_aec_stream_get(dsr_stream* s, int what, double* out, size_t outDoubles, size_t* n);
+/* CCTDE(samp1, samp2, fftLen, nHeldMaxCC, freqLowerLimit, freqUpperLimit, name) (CCTDE.h:60-101, TDEstimator.i): a stream of double rows, the
+ * nHeldMaxCC delays in seconds of a block pair of two SampleFeatures (DSR_E_TYPE otherwise; unequal sampling rates or block sizes and the
+ * refusals of dsr_cctde_check are DSR_E_DIMENSION).  fftLen is ignored as there: the transform length is the power of two that holds a block.
+ * dsr_stream_next moves both sources on; while they stand at the same frame the rows come from one dsr_cctde_run over the whole utterance.
+ *   next_x: nextX(chanX, frameX) -- source chanX moves on, the other one's current block is used again (DSR_E_CONSISTENCY if it has none);
+ *   allsamples: the two recordings as one block pair, fftLen < 0 = the power of two that holds the longer one; the result is what
+ *               dsr_stream_next(frameX()) and the getters return until a source moves; the transform length stays changed, as there;
+ *   get_sample_delays / get_cc_values: the lags as FFT indices (lag >= fftLen/2 stands for lag - fftLen; -1 = empty) and the correlation
+ *               values of the last answer, owned by the stream and valid until its next call;
+ *   set_target_frequency_range: stored and, as in the reference (CCTDE.cc:186-205 cannot be reached), never used. */
+dsr_status dsr_cctde_stream_create(dsr_stream* samp1, dsr_stream* samp2, int fftLen, int nHeldMaxCC, int freqLowerLimit, int freqUpperLimit, const char* name,
+                                   dsr_stream** out);
+dsr_status dsr_cctde_stream_next_x(dsr_stream* s, int chanX, int frameX, const void** data, size_t* n);
+dsr_status dsr_cctde_stream_allsamples(dsr_stream* s, int fftLen);
+dsr_status dsr_cctde_stream_get_sample_delays(dsr_stream* s, const int32_t** lags, size_t* n);
+dsr_status dsr_cctde_stream_get_cc_values(dsr_stream* s, const double** values, size_t* n);
+dsr_status dsr_cctde_stream_set_target_frequency_range(dsr_stream* s, int freqLowerLimit, int freqUpperLimit);
+int        dsr_cctde_stream_fft_len(const dsr_stream* s);
 /* SubbandDS/GSC/MVDR as a stream: channels are analysis-bank streams (setChannel) */
 dsr_status dsr_subband_bf_create(dsr_bf* weights, const char* name, dsr_stream** out);
 dsr_status dsr_subband_bf_set_channel(dsr_stream* bf, dsr_stream* chan);

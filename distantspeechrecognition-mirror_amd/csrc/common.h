@@ -83,6 +83,14 @@ template <class T> struct PinBuf {
   }
 };
 
+#ifdef __HIPCC__
+// one complex value of a kernel's output row: complex128 when isDouble (the stream operators' rows), else complex64
+__device__ __forceinline__ void store_c(void* out, size_t i, double re, double im, int isDouble)
+{
+  if (isDouble) reinterpret_cast<double2*>(out)[i] = make_double2(re, im);
+  else reinterpret_cast<float2*>(out)[i] = make_float2((float) re, (float) im);
+}
+#endif
 static inline int ilog2(unsigned v) { int l = 0; while ((1u << l) < v) l++; return l; }
 static inline bool is_pow2(unsigned v) { return v && !(v & (v - 1)); }
 static inline int cdiv(long a, long b) { return (int) ((a + b - 1) / b); }

@@ -573,6 +573,71 @@ struct ZelinskiOp : dsr_stream {     // ZelinskiPostFilter (postfilter.cc:350-49
   }
 };
 
+// SpectralSubtractor (spectralsubtraction.cc:141-267): ups = the channels of setChannel.  The noise estimates live as long as the operator
+// (reset() never touches them); the state is sized by the first call that needs it, channels are set before that.
+struct SpecSubOp : dsr_stream {
+  dsr_specsub* h = nullptr; int M = 0; DevBuf<float2> X; DevBuf<int> nf; DevBuf<unsigned char> state; int stateC = 0;
+  ~SpecSubOp() override { if (h) dsr_specsub_destroy(h); }
+  void* st() {
+    const int C = (int) ups.size();
+    if (stateC == 0 && C > 0) { require_device(); state.reserve(dsr_specsub_state_bytes(h, 1)); ok(dsr_specsub_state_init(h, state.p, 1, S0)); stateC = C; }
+    if (stateC != C) throw Error(DSR_E_CONSISTENCY, "setChannel() after the noise estimates are in use (%d channels, %d now)", stateC, C);
+    return state.p;
+  }
+  void compute() override {
+    const int C = (int) ups.size(); if (C < 1) throw Error(DSR_E_ERROR, "setChannel() has not been called");
+    const int T = shortest(this, 0, C); alloc(T); if (T <= 0) return;
+    const int F = M / 2 + 1; X.reserve((size_t) C * T * F); pack_channels(this, 0, C, T, F, M, X.p); nf.upload(&T, 1);
+    ok(dsr_specsub_apply(h, (const float*) X.p, nf.p, 1, T, dev.p, M, 1, st(), S0));
+  }
+};
+struct WienerOp : dsr_stream {       // WienerFilter (spectralsubtraction.cc:269-347): ups = target, noise; frame counter and PSD memories outlive reset()
+  dsr_wiener* h = nullptr; int M = 0; DevBuf<float2> S, N; DevBuf<int> nf; DevBuf<unsigned char> state; bool have = false;
+  ~WienerOp() override { if (h) dsr_wiener_destroy(h); }
+  void compute() override {
+    const int T = shortest(this, 0, 2); alloc(T); if (T <= 0) return;
+    if (!have) { state.reserve(dsr_wiener_state_bytes(h, 1)); ok(dsr_wiener_state_init(h, state.p, 1, S0)); have = true; }
+    const int F = M / 2 + 1; S.reserve((size_t) T * F); N.reserve((size_t) T * F);
+    op_pack_bins(ups[0]->d<double2>(), T, F, M, S.p, S0); op_pack_bins(ups[1]->d<double2>(), T, F, M, N.p, S0); nf.upload(&T, 1);
+    ok(dsr_wiener_apply(h, (const float*) S.p, (const float*) N.p, nf.p, 1, T, dev.p, M, 1, state.p, S0));
+  }
+};
+struct MaskOp : dsr_stream {         // BinaryMaskFilter / KimBinaryMaskFilter / IIDBinaryMaskFilter (binauralprocessing.cc:47-211, 431-520): ups = srcL, srcR
+  dsr_binmask* h = nullptr; int M = 0; DevBuf<float2> L, R; DevBuf<int> nf; DevBuf<unsigned char> state; bool have = false;
+  ~MaskOp() override { if (h) dsr_binmask_destroy(h); }
+  void compute() override {
+    const int T = shortest(this, 0, 2); alloc(T); if (T <= 0) return;
+    if (!have) { state.reserve(dsr_binmask_state_bytes(h, 1)); ok(dsr_binmask_state_init(h, state.p, 1, S0)); have = true; }   // _prevMu = 1, untouched by reset()
+    const int F = M / 2 + 1; L.reserve((size_t) T * F); R.reserve((size_t) T * F);
+    op_pack_bins(ups[0]->d<double2>(), T, F, M, L.p, S0); op_pack_bins(ups[1]->d<double2>(), T, F, M, R.p, S0); nf.upload(&T, 1);
+    ok(dsr_binmask_apply(h, (const float*) L.p, (const float*) R.p, nf.p, 1, T, dev.p, M, 1, nullptr, nullptr, state.p, S0));
+  }
+};
+// KimITD / IID / FDIID ThresholdEstimator (binauralprocessing.cc:232-426, 525-683, 702-928): ups = srcL, srcR; the output vector is never written
+// there, so the rows are zeros; reset() clears the accumulators; calcThreshold divides them in place, so a second call differs, as there
+struct ThestOp : dsr_stream {
+  dsr_thest* h = nullptr; int M = 0; DevBuf<float2> L, R; DevBuf<int> nf; DevBuf<unsigned char> state; bool have = false, fresh = false;
+  std::vector<double> acc, cost, thresholds; double threshold = 0.0;
+  ~ThestOp() override { if (h) dsr_thest_destroy(h); }
+  void ensure() { if (!have) { require_device(); state.reserve(dsr_thest_state_bytes(h, 1)); ok(dsr_thest_state_init(h, state.p, 1, S0)); have = true; } }
+  void reset() override { dsr_stream::reset(); if (have) ok(dsr_thest_reset_state(h, state.p, 1, S0)); fresh = false; }
+  void compute() override {
+    const int T = shortest(this, 0, 2); alloc(T); DSR_HIP(hipMemsetAsync(dev.p, 0, (size_t) (T > 0 ? T : 1) * rowBytes(), S0)); fresh = false; if (T <= 0) return;
+    ensure();
+    const int F = M / 2 + 1; L.reserve((size_t) T * F); R.reserve((size_t) T * F);
+    op_pack_bins(ups[0]->d<double2>(), T, F, M, L.p, S0); op_pack_bins(ups[1]->d<double2>(), T, F, M, R.p, S0); nf.upload(&T, 1);
+    ok(dsr_thest_run(h, (const float*) L.p, (const float*) R.p, nf.p, 1, T, state.p, S0));
+  }
+  double calc() {
+    ensure();
+    const size_t n = dsr_thest_acc_doubles(h), F = (size_t) M / 2 + 1, nC = (size_t) dsr_thest_n_cand(h);
+    if (!fresh) { acc.assign(n, 0.0); ok(dsr_thest_state_read(h, state.p, 1, 0, acc.data(), n)); fresh = true; }
+    cost.assign(dsr_thest_kind(h) == DSR_THEST_FDIID ? F * nC : nC, 0.0); thresholds.assign(F, 0.0);
+    ok(dsr_thest_calc_threshold(h, acc.data(), n, 1, &threshold, nullptr, cost.data(), cost.size(), thresholds.data(), (int) F));
+    return threshold;
+  }
+};
+
 template <class T> T* mk(const char* name, const char* dflt, int size, int type) { T* s = new T(); s->name = (name && *name) ? name : dflt; s->size_ = size; s->type = type; return s; }
 // what the filter-bank operators' create functions share: the operator (order unchecked, `bins` bins a frame on the bank's side) owns the plan
 // that `plan` creates into it, and is handed out on top of `up` only when that succeeded
@@ -588,6 +653,7 @@ template <class Op> Op& srp_op(dsr_stream* s, bool argsOk = true)
   Op* q = dynamic_cast<Op*>(s); if (!q || !argsOk) throw Error(DSR_E_PARAMETER, "%s", Op::Calls::notThis);
   return *q;
 }
+template <class Op> Op* as_op(dsr_stream* s, const char* what) { Op* q = dynamic_cast<Op*>(s); if (!q) throw Error(DSR_E_PARAMETER, "not a %s stream", what); return q; }
 dsr_stream* need(dsr_stream* s, int type, const char* what) {
   if (!s) throw Error(DSR_E_PARAMETER, "null upstream for %s", what);
   if (s->type != type) throw Error(DSR_E_TYPE, "%s needs an upstream of element type %d, got %d", what, type, s->type);
@@ -926,6 +992,125 @@ dsr_status dsr_zelinski_stream_set_manifold(dsr_stream* pf, int fbinX, const dou
     if (fbinX < 0 || fbinX >= q->M) throw Error(DSR_E_DIMENSION, "fbinX %d must be less than %d", fbinX, q->M);
     if (fbinX <= q->M / 2) q->manifold[fbinX].assign(vec, vec + 2 * (size_t) chanN);
     q->chanSet = chanN; q->ready = false;
+  });
+}
+// SpectralSubtractorPtr(fftLen, halfBandShift, ft, flooringV, nm) (postfilter.i:182-184)
+dsr_status dsr_specsub_stream_create(int fftLen, int halfBandShift, float ft, float flooringV, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    if (!out) throw Error(DSR_E_PARAMETER, "null argument");
+    std::unique_ptr<SpecSubOp> s(mk<SpecSubOp>(name, "SpectralSubtractor", fftLen, DSR_T_COMPLEX)); s->M = fftLen; s->checkOrder = false;
+    ok(dsr_specsub_create(fftLen, halfBandShift, ft, flooringV, &s->h)); *out = s.release();
+  });
+}
+dsr_status dsr_specsub_stream_set_channel(dsr_stream* ss, dsr_stream* chan, double alpha)
+{
+  return guard([&] {
+    SpecSubOp* q = as_op<SpecSubOp>(ss, "SpectralSubtractor"); need(chan, DSR_T_COMPLEX, "SpectralSubtractor channel");
+    if (chan->size_ != q->M) throw Error(DSR_E_DIMENSION, "channel size %d != fftLen %d", chan->size_, q->M);
+    if (q->stateC) throw Error(DSR_E_CONSISTENCY, "setChannel() after the noise estimates are in use");
+    ok(dsr_specsub_set_channel(q->h, alpha)); q->add_up(chan); q->ready = false;
+  });
+}
+// what: 0 setNoiseOverEstimationFactor(value), 1 startTraining, 2 stopTraining, 3 startNoiseSubtraction, 4 stopNoiseSubtraction, 5 clear,
+// 6 clearNoiseSamples, 7 readNoiseFile(fn, idx), 8 writeNoiseFile(fn, idx) (spectralsubtraction.h:75-118).  The frames of an utterance are
+// computed at its first next(): a call takes effect from the next reset() on.
+dsr_status dsr_specsub_stream_control(dsr_stream* ss, int what, double value, const char* fn, int idx)
+{
+  return guard([&] {
+    SpecSubOp* q = as_op<SpecSubOp>(ss, "SpectralSubtractor");
+    switch (what) {
+    case 0: ok(dsr_specsub_set_noise_over_estimation_factor(q->h, (float) value)); break;
+    case 1: ok(dsr_specsub_start_training(q->h)); break;
+    case 2: ok(dsr_specsub_stop_training(q->h, q->ups.empty() ? nullptr : q->st(), 1, S0)); break;
+    case 3: case 4: ok(dsr_specsub_set_noise_subtraction(q->h, what == 3)); break;
+    case 5: if (!q->ups.empty()) ok(dsr_specsub_clear(q->h, q->st(), 1, S0)); break;
+    case 6: if (!q->ups.empty()) ok(dsr_specsub_clear_noise_samples(q->h, q->st(), 1, S0)); break;
+    case 7: ok(dsr_specsub_read_noise_file(q->h, fn, idx, q->ups.empty() ? nullptr : q->st(), 1)); break;
+    case 8: ok(dsr_specsub_write_noise_file(q->h, fn, idx, q->ups.empty() ? nullptr : q->st(), 1, 0)); break;
+    default: throw Error(DSR_E_PARAMETER, "bad selector %d", what);
+    }
+    q->ready = false;
+  });
+}
+dsr_status dsr_wiener_stream_create(dsr_stream* targetSignal, dsr_stream* noiseSignal, int halfBandShift, float alpha, float flooringV, double beta, const char* name,
+                                    dsr_stream** out)
+{
+  return guard([&] {
+    need(targetSignal, DSR_T_COMPLEX, "WienerFilter"); need(noiseSignal, DSR_T_COMPLEX, "WienerFilter"); if (!out) throw Error(DSR_E_PARAMETER, "null argument");
+    std::unique_ptr<WienerOp> s(mk<WienerOp>(name, "WienerFilter", targetSignal->size_, DSR_T_COMPLEX)); s->M = targetSignal->size_; s->checkOrder = false;
+    ok(dsr_wiener_create(targetSignal->size_, noiseSignal->size_, halfBandShift, alpha, flooringV, beta, &s->h)); ok(dsr_wiener_carry(s->h, 1));
+    s->add_up(targetSignal); s->add_up(noiseSignal); *out = s.release();
+  });
+}
+// what: 0 setNoiseAmplificationFactor(value), 1 startUpdatingNoisePSD, 2 stopUpdatingNoisePSD
+dsr_status dsr_wiener_stream_control(dsr_stream* wf, int what, double value)
+{
+  return guard([&] {
+    WienerOp* q = as_op<WienerOp>(wf, "WienerFilter");
+    if (what == 0) ok(dsr_wiener_set_noise_amplification_factor(q->h, value)); else if (what == 1 || what == 2) ok(dsr_wiener_set_updating_noise_psd(q->h, what == 1));
+    else throw Error(DSR_E_PARAMETER, "bad selector %d", what);
+    q->ready = false;
+  });
+}
+// BinaryMaskFilterPtr / KimBinaryMaskFilterPtr / IIDBinaryMaskFilterPtr(chanX, srcL, srcR, M, threshold, alpha, dEta[, dPowerCoeff], nm) (postfilter.i:274-368)
+dsr_status dsr_binmask_stream_create(int kind, unsigned chanX, dsr_stream* srcL, dsr_stream* srcR, unsigned M, float threshold, float alpha, float dEta,
+                                     float dPowerCoeff, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    need(srcL, DSR_T_COMPLEX, "BinaryMaskFilter"); need(srcR, DSR_T_COMPLEX, "BinaryMaskFilter"); if (!out) throw Error(DSR_E_PARAMETER, "null argument");
+    if (srcL->size_ != (int) M) throw Error(DSR_E_DIMENSION, "Left input block length (%d) != M (%d)", srcL->size_, (int) M);       // binauralprocessing.cc:58-66
+    if (srcR->size_ != (int) M) throw Error(DSR_E_DIMENSION, "Right input block length (%d) != M (%d)", srcR->size_, (int) M);
+    std::unique_ptr<MaskOp> s(mk<MaskOp>(name, kind == 1 ? "KimBinaryMaskFilter" : kind == 2 ? "IIDBinaryMaskFilter" : "BinaryMaskFilter", (int) M, DSR_T_COMPLEX));
+    s->M = (int) M; s->checkOrder = false;
+    ok(dsr_binmask_create(kind, chanX, (int) M, threshold, alpha, dEta, dPowerCoeff, &s->h)); ok(dsr_binmask_carry(s->h, 1));
+    s->add_up(srcL); s->add_up(srcR); *out = s.release();
+  });
+}
+dsr_status dsr_binmask_stream_set_threshold(dsr_stream* m, float threshold)
+{ return guard([&] { MaskOp* q = as_op<MaskOp>(m, "BinaryMaskFilter"); ok(dsr_binmask_set_threshold(q->h, threshold)); q->ready = false; }); }
+dsr_status dsr_binmask_stream_threshold(dsr_stream* m, double* threshold)
+{ return guard([&] { if (!threshold) throw Error(DSR_E_PARAMETER, "null argument"); *threshold = dsr_binmask_threshold(as_op<MaskOp>(m, "BinaryMaskFilter")->h); }); }
+dsr_status dsr_binmask_stream_set_thresholds(dsr_stream* m, const double* thresholds, int n)
+{ return guard([&] { MaskOp* q = as_op<MaskOp>(m, "BinaryMaskFilter"); ok(dsr_binmask_set_thresholds(q->h, thresholds, n)); q->ready = false; }); }
+dsr_status dsr_binmask_stream_thresholds(dsr_stream* m, double* out, int n, int32_t* exists)
+{ return guard([&] { ok(dsr_binmask_thresholds(as_op<MaskOp>(m, "BinaryMaskFilter")->h, out, n, exists)); }); }
+// KimITDThresholdEstimatorPtr / IIDThresholdEstimatorPtr / FDIIDThresholdEstimatorPtr (postfilter.i:332-428)
+dsr_status dsr_thest_stream_create(int kind, dsr_stream* srcL, dsr_stream* srcR, unsigned M, float minThreshold, float maxThreshold, float width, float minFreq,
+                                   float maxFreq, int sampleRate, float dEta, float dPowerCoeff, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    need(srcL, DSR_T_COMPLEX, "ThresholdEstimator"); need(srcR, DSR_T_COMPLEX, "ThresholdEstimator"); if (!out) throw Error(DSR_E_PARAMETER, "null argument");
+    if (srcL->size_ != (int) M) throw Error(DSR_E_DIMENSION, "Left input block length (%d) != M (%d)", srcL->size_, (int) M);
+    if (srcR->size_ != (int) M) throw Error(DSR_E_DIMENSION, "Right input block length (%d) != M (%d)", srcR->size_, (int) M);
+    std::unique_ptr<ThestOp> s(mk<ThestOp>(name, kind == 0 ? "KimITDThresholdEstimator" : kind == 1 ? "IIDThresholdEstimator" : "FDIIDThresholdEstimator", (int) M, DSR_T_COMPLEX));
+    s->M = (int) M; s->checkOrder = false;
+    ok(dsr_thest_create(kind, (int) M, minThreshold, maxThreshold, width, minFreq, maxFreq, sampleRate, dEta, dPowerCoeff, &s->h));
+    s->add_up(srcL); s->add_up(srcR); *out = s.release();
+  });
+}
+dsr_status dsr_thest_stream_calc_threshold(dsr_stream* e, double* threshold)
+{ return guard([&] { if (!threshold) throw Error(DSR_E_PARAMETER, "null argument"); *threshold = as_op<ThestOp>(e, "ThresholdEstimator")->calc(); }); }
+dsr_status dsr_thest_stream_threshold(dsr_stream* e, double* threshold)
+{ return guard([&] { if (!threshold) throw Error(DSR_E_PARAMETER, "null argument"); *threshold = as_op<ThestOp>(e, "ThresholdEstimator")->threshold; }); }
+// getCostFunction() / getCostFunction(freqX) of the last calcThreshold (zeros before one, where the reference prints a warning); FDIID: getThresholds
+dsr_status dsr_thest_stream_get_cost_function(dsr_stream* e, unsigned freqX, double* out, size_t outDoubles, size_t* n)
+{
+  return guard([&] {
+    ThestOp* q = as_op<ThestOp>(e, "ThresholdEstimator"); if (!out || !n) throw Error(DSR_E_PARAMETER, "null argument");
+    const size_t nC = (size_t) dsr_thest_n_cand(q->h); if (outDoubles < nC) throw Error(DSR_E_DIMENSION, "%zu doubles for %zu", outDoubles, nC);
+    const bool fd = dsr_thest_kind(q->h) == DSR_THEST_FDIID;
+    if (fd && freqX > (unsigned) q->M / 2) throw Error(DSR_E_INDEX, "bin %u of %d", freqX, q->M / 2 + 1);
+    std::fill(out, out + nC, 0.0); *n = nC;
+    if (!q->cost.empty()) std::copy(q->cost.begin() + (fd ? freqX * nC : 0), q->cost.begin() + (fd ? freqX * nC : 0) + nC, out);
+  });
+}
+int dsr_thest_stream_n_cand(dsr_stream* e) { ThestOp* q = dynamic_cast<ThestOp*>(e); return q ? dsr_thest_n_cand(q->h) : 0; }
+dsr_status dsr_thest_stream_thresholds(dsr_stream* e, double* out, int n)
+{
+  return guard([&] {
+    ThestOp* q = as_op<ThestOp>(e, "ThresholdEstimator"); if (!out || n < q->M / 2 + 1) throw Error(DSR_E_DIMENSION, "%d doubles for %d bins", n, q->M / 2 + 1);
+    std::fill(out, out + q->M / 2 + 1, 0.0); if (!q->thresholds.empty()) std::copy(q->thresholds.begin(), q->thresholds.end(), out);
   });
 }
 dsr_status dsr_subband_bf_create(dsr_bf* weights, const char* name, dsr_stream** out)

@@ -276,6 +276,105 @@ class LefkimmiatisPostFilter : public McCowanPostFilter {
   void calcInverseNoiseSpatialSpectralMatrix() {}          // implied: refreshed whenever the coherence matrices or the manifold change
 };
 
+// ---- btk/postfilter/spectralsubtraction.h:70-166.  An utterance is computed at its first next(): control calls act from the next reset() on.
+class SpectralSubtractor : public VectorComplexFeatureStream {
+ public:
+  SpectralSubtractor(unsigned fftLen, bool halfBandShift = false, float ft = 1.0f, float flooringV = 0.001f, const String& nm = "SpectralSubtractor")
+  { DSR_OP(SpectralSubtractor, cplx, dsr_specsub_stream_create((int) fftLen, halfBandShift ? 1 : 0, ft, flooringV, nm.c_str(), &h)) }
+  void setChannel(VectorComplexFeatureStreamPtr& chan, double alpha = -1) { dsr_throw(dsr_specsub_stream_set_channel(_h, chan ? chan->handle() : 0, alpha)); _chans.push_back(chan); }
+  void setNoiseOverEstimationFactor(float ft) { ctl(0, ft); }
+  void startTraining() { ctl(1); }
+  void stopTraining() { ctl(2); }
+  void startNoiseSubtraction() { ctl(3); }
+  void stopNoiseSubtraction() { ctl(4); }
+  void clear() { ctl(5); }
+  void clearNoiseSamples() { ctl(6); }
+  bool readNoiseFile(const String& fn, unsigned idx = 0) { ctl(7, 0.0, fn.c_str(), (int) idx); return true; }
+  bool writeNoiseFile(const String& fn, unsigned idx = 0) { ctl(8, 0.0, fn.c_str(), (int) idx); return true; }
+ private:
+  void ctl(int what, double v = 0.0, const char* fn = 0, int idx = 0) { dsr_throw(dsr_specsub_stream_control(_h, what, v, fn, idx)); }
+  std::vector<VectorComplexFeatureStreamPtr> _chans;
+};
+typedef std::shared_ptr<SpectralSubtractor> SpectralSubtractorPtr;
+class WienerFilter : public VectorComplexFeatureStream {
+ public:
+  WienerFilter(VectorComplexFeatureStreamPtr& targetSignal, VectorComplexFeatureStreamPtr& noiseSignal, bool halfBandShift = false, float alpha = 0.0f,
+               float flooringV = 0.001f, double beta = 1.0, const String& nm = "WienerFilter")
+  : _t(targetSignal), _n(noiseSignal)
+  { DSR_OP(WienerFilter, cplx, dsr_wiener_stream_create(_t ? _t->handle() : 0, _n ? _n->handle() : 0, halfBandShift ? 1 : 0, alpha, flooringV, beta, nm.c_str(), &h)) }
+  void setNoiseAmplificationFactor(double beta) { dsr_throw(dsr_wiener_stream_control(_h, 0, beta)); }
+  void startUpdatingNoisePSD() { dsr_throw(dsr_wiener_stream_control(_h, 1, 0.0)); }
+  void stopUpdatingNoisePSD() { dsr_throw(dsr_wiener_stream_control(_h, 2, 0.0)); }
+ private: VectorComplexFeatureStreamPtr _t, _n;
+};
+typedef std::shared_ptr<WienerFilter> WienerFilterPtr;
+
+// ---- btk/postfilter/binauralprocessing.h.  dPowerCoeff: the reference's default `1/15` is integer division, 0.0 -- kept; every cost function is
+// then degenerate, so callers pass a value.
+class BinaryMaskFilter : public VectorComplexFeatureStream {
+ public:
+  BinaryMaskFilter(unsigned chanX, VectorComplexFeatureStreamPtr& srcL, VectorComplexFeatureStreamPtr& srcR, unsigned M, float threshold, float alpha,
+                   float dEta = 0.01f, const String& nm = "BinaryMaskFilter")
+  : _l(srcL), _r(srcR), _M(M) { create(0, chanX, threshold, alpha, dEta, 0.0f, nm); }
+  void setThreshold(float threshold) { dsr_throw(dsr_binmask_stream_set_threshold(_h, threshold)); }
+  void setThresholds(const double* thresholds, unsigned n) { dsr_throw(dsr_binmask_stream_set_thresholds(_h, thresholds, (int) n)); }
+  double getThreshold() { double v = 0.0; dsr_throw(dsr_binmask_stream_threshold(_h, &v)); return v; }
+  bool getThresholds(std::vector<double>& out) { int32_t ex = 0; out.assign(_M / 2 + 1, 0.0); dsr_throw(dsr_binmask_stream_thresholds(_h, out.data(), (int) out.size(), &ex)); return ex != 0; }
+ protected:
+  BinaryMaskFilter(VectorComplexFeatureStreamPtr& srcL, VectorComplexFeatureStreamPtr& srcR, unsigned M) : _l(srcL), _r(srcR), _M(M) {}
+  void create(int kind, unsigned chanX, float threshold, float alpha, float dEta, float dPowerCoeff, const String& nm)
+  { DSR_OP(BinaryMaskFilter, cplx, dsr_binmask_stream_create(kind, chanX, _l ? _l->handle() : 0, _r ? _r->handle() : 0, _M, threshold, alpha, dEta, dPowerCoeff, nm.c_str(), &h)) }
+  VectorComplexFeatureStreamPtr _l, _r; unsigned _M;
+};
+typedef std::shared_ptr<BinaryMaskFilter> BinaryMaskFilterPtr;
+class KimBinaryMaskFilter : public BinaryMaskFilter {
+ public:
+  KimBinaryMaskFilter(unsigned chanX, VectorComplexFeatureStreamPtr& srcL, VectorComplexFeatureStreamPtr& srcR, unsigned M, float threshold, float alpha,
+                      float dEta = 0.01f, float dPowerCoeff = 1 / 15, const String& nm = "KimBinaryMaskFilter")
+  : BinaryMaskFilter(srcL, srcR, M) { create(1, chanX, threshold, alpha, dEta, dPowerCoeff, nm); }
+};
+typedef std::shared_ptr<KimBinaryMaskFilter> KimBinaryMaskFilterPtr;
+class IIDBinaryMaskFilter : public BinaryMaskFilter {
+ public:
+  IIDBinaryMaskFilter(unsigned chanX, VectorComplexFeatureStreamPtr& srcL, VectorComplexFeatureStreamPtr& srcR, unsigned M, float threshold, float alpha,
+                      float dEta = 0.01f, const String& nm = "IIDBinaryMaskFilter")
+  : BinaryMaskFilter(srcL, srcR, M) { create(2, chanX, threshold, alpha, dEta, 0.0f, nm); }
+};
+typedef std::shared_ptr<IIDBinaryMaskFilter> IIDBinaryMaskFilterPtr;
+class KimITDThresholdEstimator : public VectorComplexFeatureStream {
+ public:
+  KimITDThresholdEstimator(VectorComplexFeatureStreamPtr& srcL, VectorComplexFeatureStreamPtr& srcR, unsigned M, float minThreshold = 0, float maxThreshold = 0,
+                           float width = 0.02f, float minFreq = -1, float maxFreq = -1, int sampleRate = -1, float dEta = 0.01f, float dPowerCoeff = 1 / 15,
+                           const String& nm = "KimITDThresholdEstimator")
+  : _l(srcL), _r(srcR), _M(M) { create(0, minThreshold, maxThreshold, width, minFreq, maxFreq, sampleRate, dEta, dPowerCoeff, nm); }
+  double calcThreshold() { double v = 0.0; dsr_throw(dsr_thest_stream_calc_threshold(_h, &v)); return v; }
+  double getThreshold() { double v = 0.0; dsr_throw(dsr_thest_stream_threshold(_h, &v)); return v; }
+  std::vector<double> getCostFunction(unsigned freqX = 0)
+  { std::vector<double> c((size_t) dsr_thest_stream_n_cand(_h) + 1, 0.0); size_t n = 0; dsr_throw(dsr_thest_stream_get_cost_function(_h, freqX, c.data(), c.size(), &n)); c.resize(n); return c; }
+ protected:
+  KimITDThresholdEstimator(VectorComplexFeatureStreamPtr& srcL, VectorComplexFeatureStreamPtr& srcR, unsigned M, int) : _l(srcL), _r(srcR), _M(M) {}
+  void create(int kind, float minT, float maxT, float width, float minFreq, float maxFreq, int sampleRate, float dEta, float dPowerCoeff, const String& nm)
+  { DSR_OP(KimITDThresholdEstimator, cplx, dsr_thest_stream_create(kind, _l ? _l->handle() : 0, _r ? _r->handle() : 0, _M, minT, maxT, width, minFreq, maxFreq, sampleRate, dEta, dPowerCoeff, nm.c_str(), &h)) }
+  VectorComplexFeatureStreamPtr _l, _r; unsigned _M;
+};
+typedef std::shared_ptr<KimITDThresholdEstimator> KimITDThresholdEstimatorPtr;
+class IIDThresholdEstimator : public KimITDThresholdEstimator {
+ public:
+  IIDThresholdEstimator(VectorComplexFeatureStreamPtr& srcL, VectorComplexFeatureStreamPtr& srcR, unsigned M, float minThreshold = 0, float maxThreshold = 0,
+                        float width = 0.02f, float minFreq = -1, float maxFreq = -1, int sampleRate = -1, float dEta = 0.01f, float dPowerCoeff = 1 / 15,
+                        const String& nm = "IIDThresholdEstimator")
+  : KimITDThresholdEstimator(srcL, srcR, M, 0) { create(1, minThreshold, maxThreshold, width, minFreq, maxFreq, sampleRate, dEta, dPowerCoeff, nm); }
+};
+typedef std::shared_ptr<IIDThresholdEstimator> IIDThresholdEstimatorPtr;
+class FDIIDThresholdEstimator : public KimITDThresholdEstimator {
+ public:
+  FDIIDThresholdEstimator(VectorComplexFeatureStreamPtr& srcL, VectorComplexFeatureStreamPtr& srcR, unsigned M, float minThreshold = 0, float maxThreshold = 0,
+                          float width = 1000, float dEta = 0.01f, float dPowerCoeff = 1 / 15, const String& nm = "FDIIDThresholdEstimator")
+  : KimITDThresholdEstimator(srcL, srcR, M, 0) { create(2, minThreshold, maxThreshold, width, -1, -1, -1, dEta, dPowerCoeff, nm); }
+  std::vector<double> getThresholds() { std::vector<double> t(_M / 2 + 1, 0.0); dsr_throw(dsr_thest_stream_thresholds(_h, t.data(), (int) t.size())); return t; }
+};
+typedef std::shared_ptr<FDIIDThresholdEstimator> FDIIDThresholdEstimatorPtr;
+
 // ---- btk/dereverberation/dereverberation.h:89-174
 class MultiChannelWPEDereverberation {
  public:

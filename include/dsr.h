@@ -852,6 +852,129 @@ dsr_status dsr_zelinski_apply_bf(dsr_zelinski*, dsr_bf*, const float* X_dev, con
 dsr_status dsr_zelinski_carry(dsr_zelinski*, int on);
 dsr_status dsr_zelinski_reset_state(dsr_zelinski*);
 
+/* =====================================================================================
+ * 6a-2. Single-channel noise suppression: averagePSDEstimator, SpectralSubtractor, WienerFilter
+ *     (btk/postfilter/spectralsubtraction.h:20-166, spectralsubtraction.cc:6-347, postfilter.i:150-223).  "6b" was taken by the LPC section.
+ * Snapshots X_dev [U][C][Tmax][fftLen/2+1] complex64 (C = the channels of setChannel, in order), or one stream [U][Tmax][fftLen/2+1];
+ * nframes_dev [U] optional; rows t >= nframes[u] are written as zero and leave the state as it is.  Outputs are outBins = fftLen/2+1 or fftLen
+ * bins a row (the latter with the upper half as the reference leaves it), complex64 or, with outIsDouble, complex128.  What the reference
+ * objects keep as long as they live is caller-owned device memory (state_bytes / state_init), so blocks of a long stream chain exactly and one
+ * handle serves several states.  Arithmetic is fp64.  Kept quirks and refusals: DESIGN 4.4k.
+ * ===================================================================================== */
+/* PSDEstimator::writeEstimates / readEstimates (spectralsubtraction.cc:17-49): text, one "%lf" per line; host side, no GPU */
+dsr_status dsr_psd_file_write(const char* fn, const double* est, int n);
+dsr_status dsr_psd_file_read(const char* fn, double* est, int n);
+typedef struct dsr_specsub dsr_specsub;
+/* SpectralSubtractor(fftLen, halfBandShift, ft, flooringV) (spectralsubtraction.cc:141-152): training on, subtraction off */
+dsr_status dsr_specsub_create(int fftLen, int halfBandShift, float ft, float flooringV, dsr_specsub** out);
+void       dsr_specsub_destroy(dsr_specsub*);
+/* setChannel(chan, alpha) (:185-189): one more channel with its own averagePSDEstimator(fftLen/2, alpha); alpha < 0 = average of the stored
+   samples at stopTraining, alpha >= 0 = recursive average.  Channels are added before the state is sized. */
+dsr_status dsr_specsub_set_channel(dsr_specsub*, double alpha);
+int        dsr_specsub_chan_n(const dsr_specsub*);
+int        dsr_specsub_fft_len(const dsr_specsub*);
+dsr_status dsr_specsub_set_noise_over_estimation_factor(dsr_specsub*, float ft);     /* spectralsubtraction.h:75-77 */
+dsr_status dsr_specsub_start_training(dsr_specsub*);                                 /* :83-85 */
+/* stopTraining (:87-91): the flag, and average() of every channel with alpha < 0 in the state.  A channel without a stored sample divides zero by
+   zero in the reference: here DSR_E_ARITHMETIC, the flag is off and no estimate changes.  Synchronous (it reads the sample counts).
+   state_dev NULL: the flag alone. */
+dsr_status dsr_specsub_stop_training(dsr_specsub*, void* state_dev, int U, void* stream);
+dsr_status dsr_specsub_set_noise_subtraction(dsr_specsub*, int on);                  /* start / stopNoiseSubtraction (:103-109) */
+int        dsr_specsub_is_training(const dsr_specsub*);
+int        dsr_specsub_is_subtracting(const dsr_specsub*);
+size_t     dsr_specsub_state_bytes(const dsr_specsub*, int U);
+dsr_status dsr_specsub_state_init(dsr_specsub*, void* state_dev, int U, void* stream);            /* zero estimates, no samples: a new object */
+dsr_status dsr_specsub_clear_noise_samples(dsr_specsub*, void* state_dev, int U, void* stream);   /* clearNoiseSamples (:93-96) */
+dsr_status dsr_specsub_clear(dsr_specsub*, void* state_dev, int U, void* stream);                 /* clear (:98-101): also forgets the first sample */
+/* next() for every frame (spectralsubtraction.cc:198-267): per channel the training sample first, then the subtraction with the current estimate;
+   without subtraction the channel average.  out_dev NULL: training only (averagePSDEstimator::addSample, :89-119). */
+dsr_status dsr_specsub_apply(dsr_specsub*, const float* X_dev, const int32_t* nframes_dev, int U, int Tmax, void* out_dev, int outBins, int outIsDouble,
+                             void* state_dev, void* stream);
+/* what 0: getEstimate() [fftLen/2+1]; 1: the sum of the stored samples [fftLen/2+1]; 2: {stored samples, first sample seen} (synchronous) */
+dsr_status dsr_specsub_state_read(const dsr_specsub*, const void* state_dev, int U, int what, int u, int chan, double* host_out, size_t outDoubles);
+dsr_status dsr_specsub_state_write_estimate(dsr_specsub*, void* state_dev, int U, int u /* < 0: all */, int chan, const double* est);
+/* readNoiseFile(fn, idx) (spectralsubtraction.h:111-114): stops training, then loads channel idx's estimate of every utterance; writeNoiseFile of utterance u */
+dsr_status dsr_specsub_read_noise_file(dsr_specsub*, const char* fn, int idx, void* state_dev, int U);
+dsr_status dsr_specsub_write_noise_file(const dsr_specsub*, const char* fn, int idx, const void* state_dev, int U, int u);
+
+typedef struct dsr_wiener dsr_wiener;
+/* WienerFilter(target, noise, halfBandShift, alpha, flooringV, beta) (spectralsubtraction.cc:269-285); noiseLen != fftLen is DSR_E_DIMENSION as
+   there; halfBandShift is accepted and, as there, refused by the first apply (DSR_E_ERROR).  beta is held as a float, as there. */
+dsr_status dsr_wiener_create(int fftLen, int noiseLen, int halfBandShift, float alpha, float flooringV, double beta, dsr_wiener** out);
+void       dsr_wiener_destroy(dsr_wiener*);
+dsr_status dsr_wiener_set_noise_amplification_factor(dsr_wiener*, double beta);      /* spectralsubtraction.h:146 */
+dsr_status dsr_wiener_set_updating_noise_psd(dsr_wiener*, int on);                   /* start / stopUpdatingNoisePSD (:149-150) */
+/* The reference's frame counter and PSD memories live as long as the object (reset() touches the sources only).  carry = 1: every apply goes on
+   where the state stands; carry = 0 (default): every call starts each utterance like a new object and leaves its end state behind. */
+dsr_status dsr_wiener_carry(dsr_wiener*, int on);
+size_t     dsr_wiener_state_bytes(const dsr_wiener*, int U);
+dsr_status dsr_wiener_state_init(const dsr_wiener*, void* state_dev, int U, void* stream);
+dsr_status dsr_wiener_reset_state(const dsr_wiener*, void* state_dev, int U, void* stream);
+/* next() for every frame (spectralsubtraction.cc:293-341): S_dev, N_dev [U][Tmax][fftLen/2+1] complex64 (N_dev may be NULL while updating is off) */
+dsr_status dsr_wiener_apply(dsr_wiener*, const float* S_dev, const float* N_dev, const int32_t* nframes_dev, int U, int Tmax, void* out_dev, int outBins,
+                            int outIsDouble, void* state_dev, void* stream);
+/* what 0: _prevPSDs [fftLen/2+1]; 1: _prevPSDn [fftLen/2+1]; 2: frames seen [1] */
+dsr_status dsr_wiener_state_read(const dsr_wiener*, const void* state_dev, int U, int what, int u, double* host_out, size_t outDoubles);
+
+/* =====================================================================================
+ * 6a-3. Two-channel binary masks and their threshold estimators: BinaryMaskFilter, KimBinaryMaskFilter, IIDBinaryMaskFilter,
+ *     KimITDThresholdEstimator, IIDThresholdEstimator, FDIIDThresholdEstimator
+ *     (btk/postfilter/binauralprocessing.h, binauralprocessing.cc:12-928, postfilter.i:254-440)
+ * L_dev, R_dev [U][Tmax][fftLen/2+1] complex64.  The masks keep the smoothed mask of the last frame (float [U][fftLen/2+1], initially 1) in
+ * caller-owned memory, with carry as in dsr_wiener_carry.  The estimators add to caller-owned fp64 accumulators that run from block to block
+ * until reset_state; the host-side finaliser turns one utterance's accumulators into the threshold.  Kept quirks and refusals: DESIGN 4.4k.
+ * ===================================================================================== */
+typedef struct dsr_binmask dsr_binmask;
+#define DSR_MASK_BASE 0   /* BinaryMaskFilter: next() only advances, the output stays zero (binauralprocessing.cc:94-98) */
+#define DSR_MASK_KIM  1   /* KimBinaryMaskFilter (:121-176); dPowerCoeff is stored and unused */
+#define DSR_MASK_IID  2   /* IIDBinaryMaskFilter (:431-485) */
+dsr_status dsr_binmask_create(int kind, unsigned chanX, int fftLen, float threshold, float alpha, float dEta, float dPowerCoeff, dsr_binmask** out);
+void       dsr_binmask_destroy(dsr_binmask*);
+dsr_status dsr_binmask_set_threshold(dsr_binmask*, float threshold);                 /* binauralprocessing.h:53 */
+double     dsr_binmask_threshold(const dsr_binmask*);                                /* :55 */
+/* setThresholds (:79-92): the first call only allocates (zeros here, uninitialised there), later calls copy bins 1..fftLen/2.  Once they exist,
+   IIDBinaryMaskFilter uses them, rounded to float, in place of the scalar, which then holds the last bin's value after an apply. */
+dsr_status dsr_binmask_set_thresholds(dsr_binmask*, const double* thresholds, int n);
+dsr_status dsr_binmask_thresholds(const dsr_binmask*, double* out, int n, int32_t* exists);     /* getThresholds; *exists = 0 while NULL there */
+dsr_status dsr_binmask_carry(dsr_binmask*, int on);
+size_t     dsr_binmask_state_bytes(const dsr_binmask*, int U);
+dsr_status dsr_binmask_state_init(const dsr_binmask*, void* state_dev, int U, void* stream);
+dsr_status dsr_binmask_reset_state(const dsr_binmask*, void* state_dev, int U, void* stream);
+/* masking1 for every frame.  mu_dev (optional) float [U][Tmax][fftLen/2+1] the smoothed mask, itd_dev (optional) double, same shape, Kim's ITD */
+dsr_status dsr_binmask_apply(dsr_binmask*, const float* L_dev, const float* R_dev, const int32_t* nframes_dev, int U, int Tmax, void* out_dev, int outBins,
+                             int outIsDouble, float* mu_dev, double* itd_dev, void* state_dev, void* stream);
+dsr_status dsr_binmask_state_read(const dsr_binmask*, const void* state_dev, int U, int u, float* host_out, size_t outFloats);
+
+typedef struct dsr_thest dsr_thest;
+#define DSR_THEST_KIM   0
+#define DSR_THEST_IID   1
+#define DSR_THEST_FDIID 2
+/* The constructors (binauralprocessing.cc:232-287, :525-538, :702-763).  minThreshold == maxThreshold selects the built-in range.  The candidate
+   table is the reference's float loop; a loop that yields more values than the (int)((max-min)/width + 1.5) its arrays hold writes past them
+   there: DSR_E_INDEX here.  A width that does not advance the threshold is DSR_E_PARAMETER, as is sampleRate 0 with a band.  More than 1024 candidates are DSR_E_DIMENSION.  A band beyond fftLen/2+1 bins is DSR_E_DIMENSION
+   (the snapshots hold no more).  FDIID ignores minFreq, maxFreq, sampleRate.  No GPU needed. */
+dsr_status dsr_thest_create(int kind, int fftLen, float minThreshold, float maxThreshold, float width, float minFreq, float maxFreq, int sampleRate, float dEta,
+                            float dPowerCoeff, dsr_thest** out);
+void       dsr_thest_destroy(dsr_thest*);
+int        dsr_thest_kind(const dsr_thest*);
+int        dsr_thest_n_cand(const dsr_thest*);          /* the arrays' length */
+int        dsr_thest_n_loop(const dsr_thest*);          /* the candidates the loop reaches (<= n_cand) */
+dsr_status dsr_thest_candidates(const dsr_thest*, float* out, int n);
+dsr_status dsr_thest_bin_range(const dsr_thest*, int32_t* out2);
+/* per utterance: Kim cost, mean_T, mean_I, sigma_T, sigma_I [nCand] each; IID mean_T, mean_I, sigma_T, sigma_I, Y4_T, Y4_I [nCand] each;
+   FDIID Y4, mean, sigma [fftLen/2+1][nCand] each; then the sample count */
+size_t     dsr_thest_acc_doubles(const dsr_thest*);
+size_t     dsr_thest_state_bytes(const dsr_thest*, int U);
+dsr_status dsr_thest_state_init(const dsr_thest*, void* state_dev, int U, void* stream);
+dsr_status dsr_thest_reset_state(const dsr_thest*, void* state_dev, int U, void* stream);       /* reset() (:409-426, :664-683, :906-928) */
+/* accumStats1 for every frame (:314-353, :549-605, :800-844), added to the accumulators */
+dsr_status dsr_thest_run(dsr_thest*, const float* L_dev, const float* R_dev, const int32_t* nframes_dev, int U, int Tmax, void* state_dev, void* stream);
+dsr_status dsr_thest_state_read(const dsr_thest*, const void* state_dev, int U, int u, double* host_out, size_t outDoubles);
+/* calcThreshold (:382-407, :634-662, :873-904) on the host from one utterance's accumulators; inPlace != 0 divides acc as the reference does (a second
+   call then differs, as there).  cost (optional): getCostFunction, [nCand], FDIID [fftLen/2+1][nCand]; thresholds (optional, FDIID): getThresholds */
+dsr_status dsr_thest_calc_threshold(const dsr_thest*, double* acc, size_t accDoubles, int inPlace, double* threshold, int32_t* index, double* cost,
+                                    size_t costDoubles, double* thresholds, int thresholdsN);
+
 /* SubbandMMI (btk/beamformer/beamformer.h:264-312, beamformer.cc:1753-2319; beamformer.i:255-287): one generalized sidelobe canceller per
  * sound source; the output is the target source's GSC output, Zelinski post-filtered (pfType: postfilter.h:63-69 bits -- 0x01 real part /
  * 0x02 magnitude of the summed cross densities, 0x08 steer with the beamformer's own vector; 0 = no post-filter) and, after
@@ -975,6 +1098,31 @@ dsr_status dsr_normal_fft_bank_create(dsr_stream* samp, int M, int r, int window
    streams (setSnapShotArray / setBeamformer), manifold = setArrayManifoldVector per bin */
 dsr_status dsr_zelinski_stream_create(dsr_stream* output, int fftLen, double alpha, int type, int minFrames, const char* name, dsr_stream** out);
 dsr_status dsr_zelinski_stream_set_channel(dsr_stream* pf, dsr_stream* chan);
+/* The operators of sections 6a-2 and 6a-3 as streams (postfilter.i:182-428).  Rows are fftLen complex values with the upper half as the reference leaves
+ * it.  What the reference objects keep across reset() (noise estimates; Wiener frame counter and PSD memories; the masks' _prevMu) lives as long as the
+ * operator; the estimators' reset() clears their accumulators.  An utterance is computed at its first next(), so a control call acts from the next reset().
+ * specsub control: 0 setNoiseOverEstimationFactor(value), 1 startTraining, 2 stopTraining, 3 startNoiseSubtraction, 4 stopNoiseSubtraction, 5 clear,
+ * 6 clearNoiseSamples, 7 readNoiseFile(fn, idx), 8 writeNoiseFile(fn, idx).  wiener control: 0 setNoiseAmplificationFactor(value), 1 / 2 start /
+ * stopUpdatingNoisePSD.  binmask kind as DSR_MASK_*, thest kind as DSR_THEST_*. */
+dsr_status dsr_specsub_stream_create(int fftLen, int halfBandShift, float ft, float flooringV, const char* name, dsr_stream** out);
+dsr_status dsr_specsub_stream_set_channel(dsr_stream* ss, dsr_stream* chan, double alpha);
+dsr_status dsr_specsub_stream_control(dsr_stream* ss, int what, double value, const char* fn, int idx);
+dsr_status dsr_wiener_stream_create(dsr_stream* targetSignal, dsr_stream* noiseSignal, int halfBandShift, float alpha, float flooringV, double beta, const char* name,
+                                    dsr_stream** out);
+dsr_status dsr_wiener_stream_control(dsr_stream* wf, int what, double value);
+dsr_status dsr_binmask_stream_create(int kind, unsigned chanX, dsr_stream* srcL, dsr_stream* srcR, unsigned M, float threshold, float alpha, float dEta,
+                                     float dPowerCoeff, const char* name, dsr_stream** out);
+dsr_status dsr_binmask_stream_set_threshold(dsr_stream* m, float threshold);
+dsr_status dsr_binmask_stream_threshold(dsr_stream* m, double* threshold);
+dsr_status dsr_binmask_stream_set_thresholds(dsr_stream* m, const double* thresholds, int n);
+dsr_status dsr_binmask_stream_thresholds(dsr_stream* m, double* out, int n, int32_t* exists);
+dsr_status dsr_thest_stream_create(int kind, dsr_stream* srcL, dsr_stream* srcR, unsigned M, float minThreshold, float maxThreshold, float width, float minFreq,
+                                   float maxFreq, int sampleRate, float dEta, float dPowerCoeff, const char* name, dsr_stream** out);
+dsr_status dsr_thest_stream_calc_threshold(dsr_stream* e, double* threshold);
+dsr_status dsr_thest_stream_threshold(dsr_stream* e, double* threshold);
+dsr_status dsr_thest_stream_get_cost_function(dsr_stream* e, unsigned freqX, double* out, size_t outDoubles, size_t* n);
+int        dsr_thest_stream_n_cand(dsr_stream* e);      /* the length of getCostFunction() */
+dsr_status dsr_thest_stream_thresholds(dsr_stream* e, double* out, int n);
 /* McCowanPostFilter(output, fftLen, alpha, type, minFrames, threshold) (postfilter.i:113-126) on the same operator; its noise
    coherence setters: what 0 setNoiseSpatialSpectralMatrix(fbinX, data [C][C] complex), 1 setDiffuseNoiseModel(data = micPos [C][3],
    a = sampleRate, b = sspeed), 2 set(All)Level(s)OfDiagonalLoading(fbinX or -1, a), 3 divideAllNonDiagonalElements(a) */

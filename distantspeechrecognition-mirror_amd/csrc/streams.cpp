@@ -638,6 +638,43 @@ struct ThestOp : dsr_stream {
   }
 };
 
+struct MccOp : dsr_stream {          // MCCLocalizer / MCCCalculator (MCCLocalizer.h:214-301): ups = the channels, a row = the best position / [cost, 0, 0]
+  dsr_mcc* mcc = nullptr; bool calc = false; int normalize = 1; bool haveDelays = false; std::vector<double> delays;
+  int C = 0, S = 1; std::vector<float> hx; DevBuf<float> dx; DevBuf<double> dD; DevBuf<int> dI;
+  std::vector<double> vec, cost, pos, eig, R; std::vector<int> tau;
+  void compute() override {}
+  void init() {
+    C = dsr_mcc_chan_n(mcc); S = calc ? 1 : dsr_mcc_max_source(mcc);
+    vec.assign(3, 0.0); cost.assign(S, 0.0); pos.assign((size_t) S * 3, 0.0); eig.assign((size_t) S * C, 0.0); tau.assign((size_t) S * C, 0); R.assign((size_t) C * C, 0.0);
+  }
+  const void* next(int fx) override {
+    if (fx == frameX && frameX >= 0) return vec.data();
+    if (calc && !haveDelays) { fprintf(stderr, "set time delays with setTimeDelays()\n"); throw Error(DSR_E_ERROR, "set time delays with setTimeDelays()"); }   // MCCLocalizer.cc:540-543
+    if ((int) ups.size() != C) throw Error(DSR_E_DIMENSION, "%zu channels are set, the search grid has %d", ups.size(), C);
+    const int L = ups[0]->size_;
+    hx.resize((size_t) C * L);
+    try { for (int c = 0; c < C; c++) std::memcpy(hx.data() + (size_t) c * L, ups[c]->next(fx), (size_t) L * sizeof(float)); }
+    catch (const Error&) { endOfSamples = true; throw; }
+    ok(dsr_mcc_check_block(mcc, L));                                                                     // "Data samples are insufficient", before anything is allocated
+    const size_t nd = (size_t) S * (1 + 3 + C) + (size_t) C * C;
+    dx.reserve(hx.size()); dD.reserve(nd); dI.reserve((size_t) S * C);
+    double* dCost = dD.p; double* dPos = dCost + S; double* dEig = dPos + (size_t) S * 3; double* dR = dEig + (size_t) S * C;
+    DSR_HIP(hipMemcpy(dx.p, hx.data(), hx.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (calc) ok(dsr_mcc_calc(mcc, dx.p, nullptr, 1, L, L, delays.data(), normalize, nullptr, dCost, tau.data(), dEig, dR, S0));
+    else ok(dsr_mcc_run(mcc, dx.p, nullptr, 1, L, L, nullptr, nullptr, dCost, dI.p, dPos, dEig, nullptr, dR, S0));
+    DSR_HIP(hipStreamSynchronize(S0));
+    DSR_HIP(hipMemcpy(cost.data(), dCost, cost.size() * 8, hipMemcpyDeviceToHost)); DSR_HIP(hipMemcpy(eig.data(), dEig, eig.size() * 8, hipMemcpyDeviceToHost));
+    DSR_HIP(hipMemcpy(R.data(), dR, R.size() * 8, hipMemcpyDeviceToHost));
+    if (calc) { vec[0] = cost[0]; vec[1] = vec[2] = 0.0; }
+    else {
+      DSR_HIP(hipMemcpy(pos.data(), dPos, pos.size() * 8, hipMemcpyDeviceToHost)); DSR_HIP(hipMemcpy(tau.data(), dI.p, tau.size() * sizeof(int), hipMemcpyDeviceToHost));
+      for (int k = 0; k < 3; k++) vec[k] = pos[k];
+    }
+    frameX++;
+    return vec.data();
+  }
+};
+
 template <class T> T* mk(const char* name, const char* dflt, int size, int type) { T* s = new T(); s->name = (name && *name) ? name : dflt; s->size_ = size; s->type = type; return s; }
 // what the filter-bank operators' create functions share: the operator (order unchecked, `bins` bins a frame on the bank's side) owns the plan
 // that `plan` creates into it, and is handed out on top of `up` only when that succeeded
@@ -915,6 +952,53 @@ dsr_status dsr_cctde_stream_get_cc_values(dsr_stream* s, const double** values, 
 { return guard([&] { CctdeOp& q = *cctde_op(s); if (!values) throw Error(DSR_E_PARAMETER, "null argument"); *values = q.vals.data(); if (n) *n = q.vals.size(); }); }
 dsr_status dsr_cctde_stream_set_target_frequency_range(dsr_stream* s, int freqLowerLimit, int freqUpperLimit)
 { return guard([&] { CctdeOp& q = *cctde_op(s); q.lower = freqLowerLimit; q.upper = freqUpperLimit; }); }
+dsr_status dsr_mcc_stream_create(dsr_mcc* mcc, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    if (!mcc || !out) throw Error(DSR_E_PARAMETER, "null argument");
+    MccOp* s = mk<MccOp>(name, "MCCSourceLocalizer", 3, DSR_T_DOUBLE); s->mcc = mcc; s->init(); s->checkOrder = false; *out = s;
+  });
+}
+dsr_status dsr_mcccalc_stream_create(dsr_mcc* mcc, int normalizeVariance, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    if (!mcc || !out) throw Error(DSR_E_PARAMETER, "null argument");
+    MccOp* s = mk<MccOp>(name, "MCCCalculator", 3, DSR_T_DOUBLE); s->mcc = mcc; s->calc = true; s->normalize = normalizeVariance != 0; s->init(); s->checkOrder = false; *out = s;
+  });
+}
+dsr_status dsr_mcc_stream_set_channel(dsr_stream* s, dsr_stream* chan)
+{
+  return guard([&] {
+    MccOp* q = as_op<MccOp>(s, "MCC"); need(chan, DSR_T_FLOAT, "MCCLocalizer");
+    if (!q->ups.empty() && q->ups[0]->size_ != chan->size_) throw Error(DSR_E_DIMENSION, "Block sizes must be the same but %d != %d", q->ups[0]->size_, chan->size_);
+    q->add_up(chan);
+  });
+}
+dsr_status dsr_mcccalc_stream_set_time_delays(dsr_stream* s, const double* delays, int n)
+{
+  return guard([&] {
+    MccOp* q = as_op<MccOp>(s, "MCC"); if (!q->calc || !delays) throw Error(DSR_E_PARAMETER, "not an MCCCalculator stream");
+    if (n != q->C) throw Error(DSR_E_DIMENSION, "%d delays for %d channels", n, q->C);
+    q->delays.assign(delays, delays + n); q->haveDelays = true;
+  });
+}
+dsr_status dsr_mcc_stream_get(dsr_stream* s, int what, int nth, double* out, size_t outDoubles, size_t* n)
+{
+  return guard([&] {
+    MccOp* q = as_op<MccOp>(s, "MCC"); if (!out) throw Error(DSR_E_PARAMETER, "null argument");
+    if (what != DSR_MCC_GET_R && (nth < 0 || nth >= q->S)) throw Error(DSR_E_INDEX, "entry %d of %d", nth, q->S);
+    const size_t C = (size_t) q->C; size_t m = 0;
+    switch (what) {
+      case DSR_MCC_GET_COST: m = 1; break; case DSR_MCC_GET_TAU: case DSR_MCC_GET_EIGEN: m = C; break; case DSR_MCC_GET_POSITION: m = 3; break;
+      case DSR_MCC_GET_R: m = C * C; break; default: throw Error(DSR_E_PARAMETER, "unknown part %d", what);
+    }
+    if (outDoubles < m) throw Error(DSR_E_DIMENSION, "part %d needs %zu doubles, the buffer holds %zu", what, m, outDoubles);
+    for (size_t i = 0; i < m; i++)
+      out[i] = what == DSR_MCC_GET_COST ? q->cost[nth] : what == DSR_MCC_GET_TAU ? (double) q->tau[nth * C + i] : what == DSR_MCC_GET_POSITION ? q->pos[nth * 3 + i]
+             : what == DSR_MCC_GET_EIGEN ? q->eig[nth * C + i] : q->R[i];
+    if (n) *n = m;
+  });
+}
 int dsr_cctde_stream_fft_len(const dsr_stream* s) { const CctdeOp* q = dynamic_cast<const CctdeOp*>(s); return q ? q->N : 0; }
 dsr_status dsr_aec_stream_get(dsr_stream* s, int what, double* out, size_t outDoubles, size_t* n)
 {

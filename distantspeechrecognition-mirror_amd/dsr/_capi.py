@@ -636,6 +636,140 @@ def cctde(a, b, fftLen, nHeldMaxCC=1, sampleRate=16000):
     return d, ar, v
 
 
+class SearchGrid:
+    """SGB4LinearArray / SGB4CircularArray (include/dsr.h section 2f): kind "linear" or "circular"; host code, no GPU needed.  Units are
+    millimetres.  enumerate() walks the whole far-field grid once."""
+    KINDS = {"linear": 0, "circular": 1}
+
+    def __init__(self, kind, nChan, isFarField=True, samplingFreq=16000):
+        L = load(); self.h = vp(); self.kind = self.KINDS[kind] if isinstance(kind, str) else int(kind); self.C = int(nChan); self.fs = int(samplingFreq)
+        check(L.dsr_sgb_create(self.kind, int(nChan), int(bool(isFarField)), int(samplingFreq), C.byref(self.h)))
+
+    def __del__(self):
+        if _lib is not None and getattr(self, "h", None):
+            _lib.dsr_sgb_destroy(self.h)
+
+    def setDistanceBtwMicrophones(self, distance):
+        check(_lib.dsr_sgb_set_distance(self.h, float(distance)))
+
+    def setPositionsOfMicrophones(self, mpos):
+        m = _np(mpos, np.float64); check(_lib.dsr_sgb_set_positions(self.h, _ptr(m), int(m.shape[0])))
+
+    def setRadius(self, radius, height=0.0):
+        check(_lib.dsr_sgb_set_radius(self.h, float(radius), float(height)))
+
+    def reset(self):
+        check(_lib.dsr_sgb_reset(self.h))
+
+    def nextSearchGrid(self):
+        more = C.c_int32(0); check(_lib.dsr_sgb_next(self.h, C.byref(more))); return bool(more.value)
+
+    def getSearchPosition(self):
+        out = np.zeros(3); check(_lib.dsr_sgb_position(self.h, _ptr(out))); return out
+
+    def getTimeDelays(self):
+        out = np.zeros(self.C); check(_lib.dsr_sgb_time_delays(self.h, _ptr(out))); return out
+
+    def maxTimeDelay(self):
+        return float(_lib.dsr_sgb_max_time_delay(self.h))
+
+    def chanN(self):
+        return int(_lib.dsr_sgb_chan_n(self.h))
+
+    def samplingFrequency(self):
+        return int(_lib.dsr_sgb_sampling_frequency(self.h))
+
+    def microphonePositions(self):
+        out = np.zeros((self.C, 3)); check(_lib.dsr_sgb_microphone_positions(self.h, _ptr(out))); return out
+
+    def enumerate(self):
+        """-> (positions [G][3], delays [G][C] seconds, tau [G][C] int32)"""
+        G = C.c_int32(0); check(_lib.dsr_sgb_enumerate(self.h, 0, C.byref(G), None, None, None)); g = G.value
+        pos = np.zeros((g, 3)); d = np.zeros((g, self.C)); tau = np.zeros((g, self.C), np.int32)
+        check(_lib.dsr_sgb_enumerate(self.h, g, C.byref(G), _ptr(pos), _ptr(d), _ptr(tau)))
+        return pos, d, tau
+
+
+def mcc_check(sgb, maxSource=1, blockLen=0):
+    """what MccLocalizer and its run() refuse, checked on the host (dsr_mcc_check)"""
+    load(); check(_lib.dsr_mcc_check(sgb.h, int(maxSource), int(blockLen)))
+
+
+class MccLocalizer:
+    """MCCLocalizer over a batch (include/dsr.h section 2f): the grid of `sgb` is walked once at construction."""
+
+    def __init__(self, sgb, maxSource=1):
+        L = load(); self.h = vp(); self.sgb = sgb
+        check(L.dsr_mcc_create(sgb.h, int(maxSource), C.byref(self.h)))
+        self.C = int(L.dsr_mcc_chan_n(self.h)); self.G = int(L.dsr_mcc_grid_n(self.h)); self.S = int(maxSource); self.D = int(L.dsr_mcc_max_sample_delay(self.h))
+
+    def __del__(self):
+        if _lib is not None and getattr(self, "h", None):
+            _lib.dsr_mcc_destroy(self.h)
+
+    def _x(self, x, blockLen):
+        import torch
+        if x.dim() != 3 or x.shape[1] != self.C or x.dtype != torch.float32:
+            raise ValueError("x: float32 [U][%d][N] expected" % self.C)
+        x = x.contiguous(); U, _, N = x.shape
+        return x, U, N, N // int(blockLen) if blockLen > 0 else 0
+
+    def run(self, x, blockLen, nsamples=None, want_costmap=False, want_R=False, want_eig=True):
+        """x cuda float32 [U][C][N] -> dict(valid [U][B], index [U][B][S], cost [U][B][S], tau [U][B][S][C], position [U][B][S][3],
+        eig [U][B][S][C], costmap [U][B][G] and R [U][B][C][C] on request)"""
+        import torch
+        x, U, N, B = self._x(x, blockLen); dev = x.device; S = self.S; Cn = self.C
+        z = lambda shape, dt=torch.float64: torch.zeros(shape, dtype=dt, device=dev)
+        r = dict(valid=z((U, B), torch.int32), index=z((U, B, S), torch.int32), cost=z((U, B, S)), tau=z((U, B, S, Cn), torch.int32), position=z((U, B, S, 3)),
+                 eig=z((U, B, S, Cn)) if want_eig else None, costmap=z((U, B, self.G)) if want_costmap else None, R=z((U, B, Cn, Cn)) if want_R else None)
+        if nsamples is not None:
+            nsamples = nsamples.to(device=dev, dtype=torch.int32).contiguous()
+        opt = lambda t: _dev(t) if t is not None else None
+        check(_lib.dsr_mcc_run(self.h, _dev(x), opt(nsamples), U, N, int(blockLen), _dev(r["valid"]), _dev(r["index"]), _dev(r["cost"]), _dev(r["tau"]),
+                               _dev(r["position"]), opt(r["eig"]), opt(r["costmap"]), opt(r["R"]), cur_stream()))
+        return r
+
+    def calc(self, x, blockLen, delays, normalizeVariance=True, nsamples=None, want_R=False, want_eig=False):
+        """MCCCalculator over the batch -> dict(valid [U][B], cost [U][B], tau [C] numpy, eig [U][B][C], R [U][B][C][C])"""
+        import torch
+        x, U, N, B = self._x(x, blockLen); dev = x.device; Cn = self.C
+        d = _np(delays, np.float64).ravel()
+        if d.size != Cn:
+            raise DsrError(E_DIMENSION, "%d delays for %d channels" % (d.size, Cn))
+        r = dict(valid=torch.zeros((U, B), dtype=torch.int32, device=dev), cost=torch.zeros((U, B), dtype=torch.float64, device=dev), tau=np.zeros(Cn, np.int32),
+                 eig=torch.zeros((U, B, Cn), dtype=torch.float64, device=dev) if want_eig else None,
+                 R=torch.zeros((U, B, Cn, Cn), dtype=torch.float64, device=dev) if want_R else None)
+        if nsamples is not None:
+            nsamples = nsamples.to(device=dev, dtype=torch.int32).contiguous()
+        opt = lambda t: _dev(t) if t is not None else None
+        check(_lib.dsr_mcc_calc(self.h, _dev(x), opt(nsamples), U, N, int(blockLen), _ptr(d), int(bool(normalizeVariance)), _dev(r["valid"]), _dev(r["cost"]),
+                                _ptr(r["tau"]), opt(r["eig"]), opt(r["R"]), cur_stream()))
+        return r
+
+    def channelDelays(self, tau):
+        """tau [C] samples -> the delays in seconds that Beamformer.calcArrayManifoldVectors takes"""
+        t = _np(tau, np.int32).ravel()
+        if t.size != self.C:
+            raise DsrError(E_DIMENSION, "%d shifts for %d channels" % (t.size, self.C))
+        out = np.zeros(self.C); check(_lib.dsr_mcc_channel_delays(self.h, _ptr(t), _ptr(out))); return out
+
+    def setTiming(self, on=True):
+        check(_lib.dsr_mcc_set_timing(self.h, int(bool(on))))
+
+    def kernelMs(self):
+        out = np.zeros(3); check(_lib.dsr_mcc_kernel_ms(self.h, _ptr(out))); return out
+
+
+class MccCalculator(MccLocalizer):
+    """MCCCalculator over a batch: one candidate from the caller's delays; calling the object is calc() with the constructor's normalizeVariance."""
+
+    def __init__(self, sgb, normalizeVariance=True):
+        MccLocalizer.__init__(self, sgb, 1); self.normalizeVariance = bool(normalizeVariance)
+
+    def __call__(self, x, blockLen, delays, nsamples=None, want_R=False, want_eig=False):
+        return self.calc(x, blockLen, delays, self.normalizeVariance, nsamples, want_R, want_eig)
+
+
 class DoaSRP:
     """DOAEstimatorSRPDSBLA (btk/beamformer/beamformer.h:462-560, beamformer.cc:2920-3283) over a batch: settings and steering table on the
     host, the response powers of X [U][C][T][M/2+1] on the fp64 MFMA (dsr_doa_srp).  The accumulators belong to the caller."""

@@ -2,6 +2,7 @@
 // argument order, pull protocol and exception types, so SWIG interface files written against btk/stream/stream.h,
 // btk/feature/feature.h, btk/modulated/modulated.h and btk/beamformer/beamformer.h keep compiling.
 #pragma once
+#include <cmath>
 #include <complex>
 #include <memory>
 #include <stdexcept>
@@ -226,6 +227,76 @@ class CCTDE : public VectorFeatureStream {
  private: SampleFeaturePtr _s1, _s2;
 };
 typedef std::shared_ptr<CCTDE> CCTDEPtr;
+
+// ---- btk/localization/MCCLocalizer.h:55-301.  Matrices are row-major double arrays here; getR() is nChan x nChan.
+class SearchGridBuilder {
+ public:
+  SearchGridBuilder(int nChan, bool isFarField, unsigned samplingFreq = 16000) : _g(0) { make(DSR_SGB_LINEAR, nChan, isFarField, samplingFreq); }
+  virtual ~SearchGridBuilder() { if (_g) dsr_sgb_destroy(_g); }
+  const double* getSearchPosition() { dsr_throw(dsr_sgb_position(_g, _pos)); return _pos; }
+  float maxTimeDelay() { return (float) dsr_sgb_max_time_delay(_g); }
+  size_t chanN() { return (size_t) dsr_sgb_chan_n(_g); }
+  unsigned samplingFrequency() { return (unsigned) dsr_sgb_sampling_frequency(_g); }
+  void reset() { dsr_throw(dsr_sgb_reset(_g)); }
+  virtual const double* getTimeDelays() { _delays.assign(chanN(), 0.0); dsr_throw(dsr_sgb_time_delays(_g, _delays.data())); return _delays.data(); }
+  virtual bool nextSearchGrid() { int32_t more = 0; dsr_throw(dsr_sgb_next(_g, &more)); return more != 0; }
+  dsr_sgb* handle() const { return _g; }
+ protected:
+  SearchGridBuilder(int kind, int nChan, bool isFarField, unsigned samplingFreq) : _g(0) { make(kind, nChan, isFarField, samplingFreq); }
+  void make(int kind, int nChan, bool isFarField, unsigned samplingFreq) { _pos[0] = _pos[1] = _pos[2] = 0.0; dsr_throw(dsr_sgb_create(kind, nChan, isFarField, samplingFreq, &_g)); }
+  dsr_sgb* _g; double _pos[3]; std::vector<double> _delays;
+ private:
+  SearchGridBuilder(const SearchGridBuilder&); SearchGridBuilder& operator=(const SearchGridBuilder&);
+};
+typedef std::shared_ptr<SearchGridBuilder> SearchGridBuilderPtr;
+class SGB4LinearArray : public SearchGridBuilder {
+ public:
+  SGB4LinearArray(int nChan, bool isFarField, unsigned samplingFreq = 16000) : SearchGridBuilder(DSR_SGB_LINEAR, nChan, isFarField, samplingFreq) {}
+  void setDistanceBtwMicrophones(float distance) { dsr_throw(dsr_sgb_set_distance(_g, distance)); }
+  void setPositionsOfMicrophones(const double* mpos, int rows) { dsr_throw(dsr_sgb_set_positions(_g, mpos, rows)); }
+};
+typedef std::shared_ptr<SGB4LinearArray> SGB4LinearArrayPtr;
+class SGB4CircularArray : public SearchGridBuilder {
+ public:
+  SGB4CircularArray(int nChan, bool isFarField, unsigned samplingFreq = 16000) : SearchGridBuilder(DSR_SGB_CIRCULAR, nChan, isFarField, samplingFreq) {}
+  void setRadius(float radius, float height = 0.0) { dsr_throw(dsr_sgb_set_radius(_g, radius, height)); }
+};
+typedef std::shared_ptr<SGB4CircularArray> SGB4CircularArrayPtr;
+class MCCLocalizer : public VectorFeatureStream {
+ public:
+  MCCLocalizer(const SearchGridBuilderPtr& sgbPtr, size_t maxSource = 1, const String& nm = "MCCSourceLocalizer") : _m(0), _sgb(sgbPtr) {
+    dsr_throw(dsr_mcc_create(sgbPtr->handle(), (int) maxSource, &_m));
+    open(dsr_mcc_stream_create(_m, nm.c_str(), &_h));
+  }
+  virtual ~MCCLocalizer() { if (_h) { dsr_stream_release(_h); _h = 0; } if (_m) dsr_mcc_destroy(_m); }
+  void setChannel(const VectorFloatFeatureStreamPtr& chan) { dsr_throw(dsr_mcc_stream_set_channel(_h, chan->handle())); _chans.push_back(chan); }
+  int getDelayedSample(int chanX) { return getNthBestDelayedSample(0, chanX); }
+  double getMaxMCCC() { return getNthBestMCCC(0); }
+  const double* getPosition() { return getNthBestPosition(0); }
+  int getNthBestDelayedSample(int nth, int chanX) { return (int) get(DSR_MCC_GET_TAU, nth, (size_t) dsr_mcc_chan_n(_m))[chanX]; }
+  double getNthBestMCCC(int nth) { return 1.0 - std::exp(get(DSR_MCC_GET_COST, nth, 1)[0]); }
+  const double* getNthBestPosition(int nth) { return get(DSR_MCC_GET_POSITION, nth, 3); }
+  const double* getEigenValues() { return get(DSR_MCC_GET_EIGEN, 0, (size_t) dsr_mcc_chan_n(_m)); }
+  const double* getR() { const size_t c = (size_t) dsr_mcc_chan_n(_m); return get(DSR_MCC_GET_R, 0, c * c); }
+ protected:
+  MCCLocalizer(const SearchGridBuilderPtr& sgbPtr, bool normalizeVariance, const String& nm, int) : _m(0), _sgb(sgbPtr) {
+    dsr_throw(dsr_mcc_create(sgbPtr->handle(), 1, &_m));
+    open(dsr_mcccalc_stream_create(_m, normalizeVariance, nm.c_str(), &_h));
+  }
+  // a constructor that throws runs no destructor: the plan is freed here when the stream could not be made
+  void open(dsr_status st) { if (st != DSR_OK) { dsr_mcc_destroy(_m); _m = 0; _h = 0; dsr_throw(st); } _name = dsr_stream_name(_h); }
+  const double* get(int what, int nth, size_t doubles) { _buf.assign(doubles, 0.0); size_t n = 0; dsr_throw(dsr_mcc_stream_get(_h, what, nth, _buf.data(), doubles, &n)); return _buf.data(); }
+  dsr_mcc* _m; SearchGridBuilderPtr _sgb; std::vector<VectorFloatFeatureStreamPtr> _chans; std::vector<double> _buf;
+};
+typedef std::shared_ptr<MCCLocalizer> MCCLocalizerPtr;
+class MCCCalculator : public MCCLocalizer {
+ public:
+  MCCCalculator(const SearchGridBuilderPtr& sgbPtr, bool normalizeVariance = true, const String& nm = "MCCCalculator") : MCCLocalizer(sgbPtr, normalizeVariance, nm, 0) {}
+  void setTimeDelays(const double* delays, int n) { dsr_throw(dsr_mcccalc_stream_set_time_delays(_h, delays, n)); }
+  double getCostV() { return get(DSR_MCC_GET_COST, 0, 1)[0]; }
+  double getMCCC() { return 1.0 - std::exp(getCostV()); }
+};
+typedef std::shared_ptr<MCCCalculator> MCCCalculatorPtr;
 
 // ---- btk/dereverberation/dereverberation.h
 class SingleChannelWPEDereverberationFeature : public VectorComplexFeatureStream {

@@ -486,6 +486,81 @@ dsr_status dsr_cctde_run(const float* a_dev, const float* b_dev, int nItems, int
                          int32_t* args_dev, double* values_dev, void* stream);
 
 /* =====================================================================================
+ * 2f. Multichannel cross-correlation source localisation on time-domain blocks
+ *     replaces SearchGridBuilder, SGB4LinearArray, SGB4CircularArray, MCCLocalizer and MCCCalculator (btk/localization/MCCLocalizer.h:55-301,
+ *     MCCLocalizer.cc:10-576; delays: localization.cc:110-142).  RMCCLocalizer is not built: its next() is an empty stub there.
+ * For every block of L samples a channel the localiser walks the search grid; at a grid point the channels are shifted by the point's integer
+ * sample delays tau[c] = (int)(float)(fs delay[c]), R = 1/(L-D) sum_n x_n x_n^T over n in [0, L-D) with x_n[c] = block_c[n + tau[c]] (an
+ * index below zero reads the block's own tail, L + index: the reference refills its sample holder from the current block before it reads
+ * it), D = (size_t)(fs maxTimeDelay), and cost = log det R - sum log R_ii (<= 0; 1 - exp(cost) is the MCCC).  The maxSource smallest costs
+ * are kept, the earlier grid point winning a tie.  Blocks are independent.  The grids are host code and need no GPU; units are millimetres,
+ * the speed of sound is 343740.  Deviations from the reference: set_positions copies every row and measures from microphone 0;
+ * a grid without geometry is DSR_E_INITIALIZATION; the circular walk takes |sin|, |cos| in its polar step and ends when the azimuth reaches
+ * 2 pi (the reference's never ends); the log-determinant comes from a Cholesky factor, a non-positive pivot giving cost 0 as a zero
+ * eigenvalue does there; the eigenvalues of a kept entry are its |lambda| in ascending order.
+ * ===================================================================================== */
+typedef struct dsr_sgb dsr_sgb;
+typedef struct dsr_mcc dsr_mcc;
+#define DSR_SGB_LINEAR   0
+#define DSR_SGB_CIRCULAR 1
+/* SGB4LinearArray / SGB4CircularArray(nChan, isFarField, samplingFreq = 16000) (MCCLocalizer.h:87,101) */
+dsr_status dsr_sgb_create(int kind, int nChan, int isFarField, unsigned samplingFreq, dsr_sgb** out);
+void       dsr_sgb_destroy(dsr_sgb*);
+/* setDistanceBtwMicrophones(distance), setPositionsOfMicrophones(mpos [rows][3]) (linear), setRadius(radius, height) (circular); the other
+   kind is DSR_E_PARAMETER, rows != nChan DSR_E_DIMENSION */
+dsr_status dsr_sgb_set_distance(dsr_sgb*, float distance);
+dsr_status dsr_sgb_set_positions(dsr_sgb*, const double* mpos, int rows);
+dsr_status dsr_sgb_set_radius(dsr_sgb*, float radius, float height);
+/* reset(), nextSearchGrid() (*more = 0: the walk is over, the position stays; a near-field grid prints the reference's "need to be
+   implemented" and is over at once), getSearchPosition() -> pos3, getTimeDelays() -> delays [nChan], maxTimeDelay() (-1 without geometry) */
+dsr_status dsr_sgb_reset(dsr_sgb*);
+dsr_status dsr_sgb_next(dsr_sgb*, int32_t* more);
+dsr_status dsr_sgb_position(const dsr_sgb*, double* pos3);
+dsr_status dsr_sgb_time_delays(dsr_sgb*, double* delays);
+double     dsr_sgb_max_time_delay(const dsr_sgb*);
+int        dsr_sgb_chan_n(const dsr_sgb*);
+int        dsr_sgb_sampling_frequency(const dsr_sgb*);
+dsr_status dsr_sgb_microphone_positions(const dsr_sgb*, double* mpos);
+/* the whole walk from (0, 0, 0), the handle's own position untouched: *G = number of grid points; the first min(G, maxG) rows of
+   positions [.][3], delays [.][nChan] (seconds) and tau [.][nChan] (samples) are written where the pointer is not NULL.  A near-field grid is
+   DSR_E_INITIALIZATION "need to be implemented", more than 65536 points DSR_E_DIMENSION. */
+dsr_status dsr_sgb_enumerate(const dsr_sgb*, int maxG, int32_t* G, double* positions, double* delays, int32_t* tau);
+/* what dsr_mcc_create and dsr_mcc_run refuse, without a GPU: no geometry or a near-field grid DSR_E_INITIALIZATION; nChan outside [2, 64],
+   maxSource outside [1, 64] or a grid point with |tau| > D DSR_E_DIMENSION; blockLen > 0 and < 2 D DSR_E_ERROR "Data samples are
+   insufficient" (MCCLocalizer.cc:324-327) */
+dsr_status dsr_mcc_check(const dsr_sgb*, int maxSource, int blockLen);
+/* MCCLocalizer(sgb, maxSource = 1) (MCCLocalizer.h:216): the grid is walked once, here, and its tables are kept; later changes of the
+   builder do not reach the handle */
+dsr_status dsr_mcc_create(const dsr_sgb*, int maxSource, dsr_mcc** out);
+void       dsr_mcc_destroy(dsr_mcc*);
+/* the block-length check of dsr_mcc_run on its own (host): blockLen < 2 D is DSR_E_ERROR "Data samples are insufficient" */
+dsr_status dsr_mcc_check_block(const dsr_mcc*, int blockLen);
+int        dsr_mcc_grid_n(const dsr_mcc*);
+int        dsr_mcc_chan_n(const dsr_mcc*);
+int        dsr_mcc_max_source(const dsr_mcc*);
+int        dsr_mcc_max_sample_delay(const dsr_mcc*);
+/* measuring (tools/bench_mcc.py): events around k_mcc_cost, k_mcc_nbest and k_mcc_eig of the last call -> ms3 */
+dsr_status dsr_mcc_set_timing(dsr_mcc*, int on);
+dsr_status dsr_mcc_kernel_ms(const dsr_mcc*, double* ms3);
+/* next() over a batch: x_dev [U][nChan][N] fp32, B = N / blockLen blocks an utterance; block b of utterance u is valid when
+ * (b + 1) blockLen <= nsamples[u] (nsamples_dev NULL: all of them).  S = maxSource, G = grid points.  Outputs, each optional:
+ * valid_dev [U][B] int32; index_dev [U][B][S] grid index (-1: fewer than S grid points); cost_dev [U][B][S] (100000 for an empty entry);
+ * tau_dev [U][B][S][nChan]; position_dev [U][B][S][3]; eig_dev [U][B][S][nChan]; costmap_dev [U][B][G]; R_dev [U][B][nChan][nChan] the
+ * covariance of the last grid point, lower triangle, the rest zero (getR()).  An invalid block gives valid = 0 and zeros everywhere.
+ * A tile of the block goes through LDS: any blockLen >= 2 D works; D so large that fewer than 64 samples fit beside the margins
+ * (about 200 at 64 channels) is DSR_E_DIMENSION. */
+dsr_status dsr_mcc_run(dsr_mcc*, const float* x_dev, const int32_t* nsamples_dev, int U, int N, int blockLen, int32_t* valid_dev, int32_t* index_dev, double* cost_dev,
+                       int32_t* tau_dev, double* position_dev, double* eig_dev, double* costmap_dev, double* R_dev, void* stream);
+/* MCCCalculator::next (MCCLocalizer.cc:535-553) over the same batch: one candidate from the caller's delays [nChan] (host, seconds),
+   cost_dev [U][B] with normalizeVariance on or off, tau_host [nChan] (optional) the shifts used; |tau| > D is DSR_E_INDEX (the reference
+   reads outside its buffers).  The kernels of dsr_mcc_run with G = 1.  Synchronous. */
+dsr_status dsr_mcc_calc(dsr_mcc*, const float* x_dev, const int32_t* nsamples_dev, int U, int N, int blockLen, const double* delays, int normalizeVariance,
+                        int32_t* valid_dev, double* cost_dev, int32_t* tau_host, double* eig_dev, double* R_dev, void* stream);
+/* host side: delays[c] = tau[c] / fs in seconds, the doubles dsr_bf_calc_array_manifold takes (a candidate's tau[c] is the arrival time at
+   channel c relative to the array's reference point, the sign convention of that function) */
+dsr_status dsr_mcc_channel_delays(const dsr_mcc*, const int32_t* tau, double* delays);
+
+/* =====================================================================================
  * 3. MFCC feature chain
  *    replaces SampleFeature(block framing) -> PreemphasisFeature -> HammingFeature -> FFTFeature ->
  *    SpectralPowerFeature -> VTLNFeature -> MelFeature -> LogFeature -> CepstralFeature ->
@@ -1171,6 +1246,22 @@ dsr_status dsr_cctde_stream_get_sample_delays(dsr_stream* s, const int32_t** lag
 dsr_status dsr_cctde_stream_get_cc_values(dsr_stream* s, const double** values, size_t* n);
 dsr_status dsr_cctde_stream_set_target_frequency_range(dsr_stream* s, int freqLowerLimit, int freqUpperLimit);
 int        dsr_cctde_stream_fft_len(const dsr_stream* s);
+/* MCCLocalizer / MCCCalculator as streams (section 2f): setChannel takes any float stream, every channel one block a frame; next() pulls
+ * one block from every channel and runs dsr_mcc_run / dsr_mcc_calc with U = B = 1.  The localiser's row is the best position (3 doubles),
+ * the calculator's row has the cost in element 0.  Fewer than 2 D samples a block is DSR_E_ERROR "Data samples are insufficient", a
+ * calculator without delays DSR_E_ERROR "set time delays with setTimeDelays()", a channel count other than the grid's DSR_E_DIMENSION.
+ *   get: what = DSR_MCC_GET_COST (1 double), _TAU (nChan, as doubles), _POSITION (3), _EIGEN (nChan) of the nth best entry of the last
+ *        next(); _R (nChan x nChan, nth ignored): getR(). */
+#define DSR_MCC_GET_COST     0
+#define DSR_MCC_GET_TAU      1
+#define DSR_MCC_GET_POSITION 2
+#define DSR_MCC_GET_EIGEN    3
+#define DSR_MCC_GET_R        4
+dsr_status dsr_mcc_stream_create(dsr_mcc* mcc, const char* name, dsr_stream** out);
+dsr_status dsr_mcccalc_stream_create(dsr_mcc* mcc, int normalizeVariance, const char* name, dsr_stream** out);
+dsr_status dsr_mcc_stream_set_channel(dsr_stream* s, dsr_stream* chan);
+dsr_status dsr_mcccalc_stream_set_time_delays(dsr_stream* s, const double* delays, int n);
+dsr_status dsr_mcc_stream_get(dsr_stream* s, int what, int nth, double* out, size_t outDoubles, size_t* n);
 /* SubbandDS/GSC/MVDR as a stream: channels are analysis-bank streams (setChannel) */
 dsr_status dsr_subband_bf_create(dsr_bf* weights, const char* name, dsr_stream** out);
 dsr_status dsr_subband_bf_set_channel(dsr_stream* bf, dsr_stream* chan);

@@ -11,6 +11,7 @@
 // [chan][frame][bin] layout the analysis kernel writes, weights staged in LDS.
 #include "common.h"
 #include "svd_linpack.h"
+#include "gsc_weights.h"
 #include <complex>
 #include <cmath>
 
@@ -75,30 +76,13 @@ static void calc_mainlobe(BfState& s, double fs, const double* delays)
   s.haveWq = true; s.dirty = true;
 }
 
-static void blocking_matrix(const zc* d, int C, zc* B)       // NC = 1, beamformer.cc:398-479
-{
-  const int bs = C - 1;
-  std::vector<zc> P((size_t) C * C), vec(C);
-  double nrm = 0; for (int i = 0; i < C; i++) nrm += std::norm(d[i]);
-  nrm = std::sqrt(nrm); nrm = nrm * nrm;
-  for (int i = 0; i < C; i++) for (int j = 0; j < C; j++) P[(size_t) i * C + j] = (i == j ? 1.0 : 0.0) + (-1.0 / nrm) * std::conj(d[i]) * d[j];
-  for (int k = 0; k < C * bs; k++) B[k] = zc(0, 0);
-  for (int id = 0; id < bs; id++) {
-    for (int i = 0; i < C; i++) vec[i] = P[(size_t) i * C + id];
-    for (int jd = 0; jd < id; jd++) {
-      zc ip(0, 0); for (int i = 0; i < C; i++) ip += std::conj(B[(size_t) i * bs + jd]) * vec[i];
-      ip = -ip; for (int i = 0; i < C; i++) vec[i] += ip * B[(size_t) i * bs + jd];
-    }
-    double nv = 0; for (int i = 0; i < C; i++) nv += std::norm(vec[i]); nv = std::sqrt(nv);
-    for (int i = 0; i < C; i++) B[(size_t) i * bs + id] = vec[i] * (1.0 / nv);
-  }
-}
+static void blocking_matrix(const zc* d, int C, zc* B) { blocking_matrix_nc(d, C, 1, B); }   // NC = 1, beamformer.cc:398-479 (csrc/gsc_weights.h)
 
 static void update_wl(BfState& s, int f)          // calcSidelobeCancellerP_f / U_f: wl = B wa (beamformer.cc:761-799)
 {
   const int C = s.C, bs = C - 1;
   if (s.wl.size() != (size_t) s.M * C) s.wl.assign((size_t) s.M * C, zc(0, 0));
-  for (int i = 0; i < C; i++) { zc a(0, 0); for (int j = 0; j < bs; j++) a += s.B[((size_t) f * C + i) * bs + j] * s.wa[(size_t) f * bs + j]; s.wl[(size_t) f * C + i] = a; }
+  sidelobe_wl(&s.B[(size_t) f * C * bs], &s.wa[(size_t) f * bs], C, bs, &s.wl[(size_t) f * C]);
 }
 
 static void refresh_effective(BfState& s)

@@ -18,6 +18,7 @@
 // In every other configuration the half spectrum is handed on and the mask's averaged value lands in bin k only.
 #include "common.h"
 #include "svd_linpack.h"
+#include "gsc_weights.h"
 #include <complex>
 #include <cmath>
 
@@ -38,30 +39,6 @@ inline zc gpolar(double r, double th) { return zc(r * std::cos(th), r * std::sin
 inline double gabs2(zc a) { return a.real() * a.real() + a.imag() * a.imag(); }
 
 struct SrcW { std::vector<zc> wq, B, wa, wl, ta; };     // [M][C], [M][C][C-NC], [M][C-NC], [M][C], [M][C]
-
-// _calcBlockingMatrix (beamformer.cc:398-479)
-bool blocking_matrix_nc(const zc* d, int C, int NC, zc* B)
-{
-  const int bs = C - NC;
-  if (bs <= 0) return false;
-  std::vector<zc> P((size_t) C * C), vec(C);
-  double nrm = 0; for (int i = 0; i < C; i++) nrm += gabs2(d[i]);
-  nrm = std::sqrt(nrm); nrm = nrm * nrm;
-  for (int i = 0; i < C; i++) for (int j = 0; j < C; j++) P[(size_t) i * C + j] = zc(i == j ? 1.0 : 0.0, 0.0) + gmul(gmul(zc(-1.0 / nrm, 0.0), std::conj(d[i])), d[j]);
-  for (int k = 0; k < C * bs; k++) B[k] = zc(0, 0);
-  for (int id = 0; id < bs; id++) {
-    for (int i = 0; i < C; i++) vec[i] = P[(size_t) i * C + id];
-    for (int jd = 0; jd < id; jd++) {
-      zc ip(0, 0); for (int i = 0; i < C; i++) ip += gmul(std::conj(B[(size_t) i * bs + jd]), vec[i]);
-      ip = zc(ip.real() * -1.0, ip.imag() * -1.0);
-      for (int i = 0; i < C; i++) vec[i] += gmul(ip, B[(size_t) i * bs + jd]);
-    }
-    double nv = 0; for (int i = 0; i < C; i++) nv += gabs2(vec[i]);
-    nv = std::sqrt(nv);
-    for (int i = 0; i < C; i++) B[(size_t) i * bs + id] = zc(vec[i].real() * (1.0 / nv), vec[i].imag() * (1.0 / nv));
-  }
-  return true;
-}
 
 void put_inverse_mat22(zc* mat)                          // beamformer.cc:202-242
 {
@@ -350,7 +327,7 @@ static void mmi_mainlobe_n(dsr_mmi& m, SrcW& w, double fs, const double* delaysT
 static void mmi_update_wl(dsr_mmi& m, SrcW& w, unsigned f)      // wl = B wa (:761-799)
 {
   const int C = m.C, bs = C - m.NC;
-  for (int i = 0; i < C; i++) { zc acc(0, 0); for (int j = 0; j < bs; j++) acc += gmul(w.B[((size_t) f * C + i) * bs + j], w.wa[(size_t) f * bs + j]); w.wl[(size_t) f * C + i] = acc; }
+  sidelobe_wl(&w.B[(size_t) f * C * bs], &w.wa[(size_t) f * bs], C, bs, &w.wl[(size_t) f * C]);
 }
 
 dsr_status dsr_mmi_create(int fftLen, int chanN, int halfBandShift, int targetSourceX, int nSource, int pfType, double alpha, dsr_mmi** out)

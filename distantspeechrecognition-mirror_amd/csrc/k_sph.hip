@@ -22,8 +22,17 @@
 //   k_sph_frame  per frame, one wave: the gate and the frame's N-best by (rp descending, unit ascending), which is the reference's strict-">"
 //                insertion (:922-943) since every rp >= 0 > -10e10; nBest rounds of a wave arg-max over the frame's row
 //   k_doa_acc    (csrc/k_doa.hip) acc[u][unit] += rp of every ungated frame, frame by frame in order
+//   k_sph_beams_valu / k_sph_beams_mfma   NB <= 16 beams in one pass over X: Y[u][b][t][f] = v_{b,f}^H X[u][:,t,f] with sensor-domain vectors v
+//                (the modal kinds' w_eff^H S folded on the host in fp64, the sensor-domain kinds' weights as they are).  Up to 4 beams: one thread
+//                per (t, f) on the VALU, x read once (the (t, f) plane of a channel is contiguous: coalesced whatever F is), the beams'
+//                accumulators in registers (fp64), conj(v) staged in LDS a few channels at a time.  Above 4: the complex GEMM of k_doa_srp
+//                (rows 16 beams zero padded, columns 16 frames a wave, K = C) without the power reduction; every result is stored.
+// The further kinds (SphericalHWNCBeamformer :1387-1478, SphericalGSCBeamformer :1483-1594, SphericalHWNCGSCBeamformer :1599-1713,
+// SphericalMOENBeamformer :1804-2099, SphericalSpatialDSBeamformer :2106-2270) are host weight designs below; all of them run on the beams kernels.
 // The MFMA's lane map: csrc/mfma64.h; the frame tiling (FB, bin_chunk) and the shared kernel parts: csrc/srp_common.h.
 #include "srp_common.h"
+#include "gsc_weights.h"
+#include "svd_linpack.h"
 #include <algorithm>
 #include <cmath>
 #include <complex>
@@ -36,6 +45,7 @@ namespace {
 
 constexpr double SSPEED = 343740.0;                          // mm/s (beamformer.h:47)
 constexpr int MAX_ORDER = 8;                                 // dim = maxOrder^2 <= 64: four 16-row tiles of the fused kernel
+constexpr int MAX_BEAMS = 16;                               // one MFMA row tile
 constexpr long MAX_TABLE = 1L << 27;                         // (fbinMax+1) units max(dim, C) complex128 entries: 2 GiB per table copy
 
 // the EigenMike's 32 capsules in degrees (setEigenMikeGeometry :414-535), radius 42 mm
@@ -59,6 +69,14 @@ struct dsr_sph {
   DevBuf<double2> dS, dSp, dLook, dWp; bool dSDirty = true, dLookDirty = true, dWDirty = true; int NT = 0, DT = 0, KS = 0;
   dsr_doa fold; unsigned foldGen = ~0u;                      // the folded path's [units][C] table, driven through k_doa_srp
   PerStream<DevBuf<double>> ws;
+  // the further kinds
+  float ratio = 1.0f; int NC = 1; bool lookSet = false;      // HWNC's _ratio; the GSC kinds' number of constraints; setLookDirection called
+  std::vector<zc> Bm, wl;                                    // GSC: B [M/2+1][dim][dim-NC] (bin 0 stays zero), wl [M/2+1][dim] = B wa as last set
+  std::vector<float> diag; bool fixedTerms = false;          // MOEN: _diagonalWeights [M/2+1], _isTermFixed
+  std::vector<zc> fixedW; bool fixedWValid = false;          // MOEN: (A^H A + l I)^+ A^H [M/2+1][C][dim] (bin 0 unused), direction independent
+  double beamTheta[MAX_BEAMS] = {0}, beamPhi[MAX_BEAMS] = {0}; bool beamSet[MAX_BEAMS] = {false}; unsigned beamGen = 0;   // beams 1.. (0 is the look direction)
+  std::vector<zc> V; int vNB = 0; unsigned vSetGen = ~0u, vBeamGen = ~0u;   // V [NB][M/2+1][C]: y = v^H x
+  DevBuf<double2> dV; int dVLayout = -1; bool dVDirty = true; // device copy, conjugated: layout 0 MFMA [F][KS][64], n > 0 VALU [C][n][F]
 };
 
 namespace {
@@ -227,6 +245,26 @@ void ensure_modes(dsr_sph& s)                                // _calcModeAmplitu
   }
 }
 
+inline bool hwnc(int kind) { return kind == DSR_SPH_HWNC || kind == DSR_SPH_HWNCGSC; }
+inline bool gsc_kind(int kind) { return kind == DSR_SPH_GSC || kind == DSR_SPH_HWNCGSC; }
+inline bool sensor_kind(int kind) { return kind == DSR_SPH_SPATIALDS || kind == DSR_SPH_MOEN; }   // weights of length C, no transform
+
+void normalize_weights(zc* w, int n, float wgain)            // normalizeWeights (:23-29): wgain / ||w||_2
+{
+  double ss = 0.0;
+  for (int i = 0; i < n; i++) ss += std::norm(w[i]);
+  const double nrm = wgain / std::sqrt(ss);
+  for (int i = 0; i < n; i++) w[i] = gmulr(w[i], nrm);
+}
+
+double hwnc_wng(const dsr_sph& s, int f)                     // SphericalHWNCBeamformer::calcWNG (:1397-1418): n < maxOrder, as the reference sums
+{
+  const double nrm = s.C / (16 * M_PI * M_PI);
+  double val = 0.0;
+  for (int n = 0; n < s.maxOrder; n++) val += (2 * n + 1) * std::norm(s.B[(size_t) f * s.maxOrder + n]);
+  return nrm * val * s.ratio;
+}
+
 // _calcWeights of bin f for the direction (theta, phi) into w[dim], with the unit's harmonics Y [dim] at that direction precomputed
 void calc_weights(const dsr_sph& s, int f, const zc* Y, zc* w)
 {
@@ -234,7 +272,7 @@ void calc_weights(const dsr_sph& s, int f, const zc* Y, zc* w)
   const unsigned norm = (unsigned) s.dim * (unsigned) s.C;
   for (int n = 0, idx = 0; n < s.maxOrder; n++) {
     const zc bn = s.B[(size_t) f * s.maxOrder + n], in = IN[n % 4];
-    if (s.kind == DSR_SPH_EB) {                             // :304-345, the HMDI beamformer
+    if (s.kind == DSR_SPH_EB || hwnc(s.kind)) {             // :304-345, the HMDI beamformer (:1433-1462 the same)
       const double bn2 = std::norm(bn) + (double) s.sigma2, de = norm * bn2;
       const zc inbn = gmul(in, bn);
       for (int m = -n; m <= n; m++, idx++) w[idx] = gdivr(gmul(gmulr(std::conj(Y[idx]), 4 * M_PI), inbn), de);
@@ -242,13 +280,85 @@ void calc_weights(const dsr_sph& s, int f, const zc* Y, zc* w)
       for (int m = -n; m <= n; m++, idx++) w[idx] = std::conj(gmulr(gmul(Y[idx], std::conj(gmul(in, bn))), 4 * M_PI));
     }
   }
-  if (s.normalize) {                                         // normalizeWeights (:23-29): wgain / ||w||_2
-    double ss = 0.0;
-    for (int i = 0; i < s.dim; i++) ss += std::norm(w[i]);
-    const double nrm = s.wgain / std::sqrt(ss);
-    for (int i = 0; i < s.dim; i++) w[i] = gmulr(w[i], nrm);
+  if (hwnc(s.kind)) {                                        // SphericalHWNCBeamformer::_calcWeights (:1464-1475); no normalizeWeight here
+    if (s.ratio > 0.0f) normalize_weights(w, s.dim, (float) (2 * std::sqrt(M_PI / (s.C * hwnc_wng(s, f)))));   // (normalizeWeights takes a float)
+    else {
+      const double coeff = (16 * M_PI * M_PI) / (s.C * s.maxOrder * s.maxOrder);
+      for (int i = 0; i < s.dim; i++) w[i] = gmulr(w[i], coeff);
+    }
+  } else if (s.normalize) normalize_weights(w, s.dim, s.wgain);
+}
+
+// SphericalSpatialDSBeamformer::_calcWeights (:2119-2172): w [C] of bin f in the sensor domain; Y the harmonics at the direction
+void calc_spatial_ds(const dsr_sph& s, int f, const zc* Y, zc* w)
+{
+  static const zc IN[4] = {zc(1, 0), zc(0, 1), zc(-1, 0), zc(0, -1)};
+  for (int c = 0; c < s.C; c++) {
+    zc weight(0, 0);
+    for (int n = 0, idx = 0; n < s.maxOrder; n++) {
+      const zc inbn = gmul(IN[n % 4], s.B[(size_t) f * s.maxOrder + n]);
+      zc tmp(0, 0);
+      for (int m = -n; m <= n; m++, idx++) tmp += gmul(std::conj(s.SH[(size_t) idx * s.C + c]), std::conj(Y[idx]));
+      weight += gmul(inbn, tmp);
+    }
+    w[c] = gmulr(weight, 4 * M_PI / s.C);
   }
 }
+
+// SphericalMOENBeamformer: _A of bin f (:1949-1981) and (A^H A + l I)^+ A^H (_calcMOENWeights :2003-2027), kept until the geometry or the loading moves
+void ensure_fixed_w(dsr_sph& s)
+{
+  if (s.fixedWValid) return;
+  static const zc IN[4] = {zc(1, 0), zc(0, 1), zc(-1, 0), zc(0, -1)};
+  const int F = s.M / 2 + 1, C = s.C, D = s.dim;
+  s.fixedW.assign((size_t) F * C * D, zc(0, 0));
+  std::vector<zc> A((size_t) D * C), tmp((size_t) C * C), inv((size_t) C * C);
+  for (int f = 1; f < F; f++) {
+    for (int n = 0, idx = 0; n < s.maxOrder; n++) {
+      const zc inbn = gmul(IN[n % 4], s.B[(size_t) f * s.maxOrder + n]);
+      for (int m = -n; m <= n; m++, idx++)
+        for (int c = 0; c < C; c++) A[(size_t) idx * C + c] = gmulr(gmul(s.SH[(size_t) idx * C + c], inbn), 4 * M_PI);
+    }
+    const double beta = (double) s.diag[f];                  // zherk(Upper, ConjTrans, 1, A, l, I), then the lower triangle mirrored (:2009-2013)
+    for (int i = 0; i < C; i++)
+      for (int j = i; j < C; j++) {
+        zc acc(0, 0);
+        for (int d = 0; d < D; d++) acc += gmul(std::conj(A[(size_t) d * C + i]), A[(size_t) d * C + j]);
+        if (i == j) acc = zc(acc.real() + beta, 0.0);
+        tmp[(size_t) i * C + j] = acc; tmp[(size_t) j * C + i] = std::conj(acc);
+      }
+    linpack::pseudoinverse(tmp.data(), inv.data(), C, C, 1.0E-8f);   // the result is taken whatever it returns (:2014-2025)
+    zc* fw = &s.fixedW[(size_t) f * C * D];
+    for (int c = 0; c < C; c++)
+      for (int d = 0; d < D; d++) {
+        zc acc(0, 0);
+        for (int k = 0; k < C; k++) acc += gmul(inv[(size_t) c * C + k], std::conj(A[(size_t) d * C + k]));
+        fw[(size_t) c * D + d] = acc;
+      }
+  }
+  s.fixedWValid = true;
+}
+
+// SphericalMOENBeamformer::_calcWeights (:1937-2040): w [C] = CN fixedW BN, BN = 2 pi conj Y at the direction.  fixTerms(true): the reference
+// frees and zeroes _fixedW before it uses it (:1993-1996, :2031-2034), so every weight is 0 (NaN with normalizeWeight: 0 times wgain / 0).
+void calc_moen(const dsr_sph& s, int f, const zc* Y, zc* w)
+{
+  const int C = s.C, D = s.dim;
+  const double CN = 2.0 / (s.maxOrder * s.maxOrder);
+  for (int c = 0; c < C; c++) {
+    zc acc(0, 0);
+    if (!s.fixedTerms)
+      for (int d = 0; d < D; d++) acc += gmul(s.fixedW[((size_t) f * C + c) * D + d], gmulr(std::conj(Y[d]), 2 * M_PI));
+    w[c] = gmulr(acc, CN);
+  }
+  if (s.normalize) normalize_weights(w, C, s.wgain);
+}
+
+// the weights of every bin for the direction (theta, phi): modal kinds [M/2+1][dim], bin 0 the DC weights (_calcSteeringUnit :703-734);
+// SpatialDS [M/2+1][C] with bin 0 computed like the others (:2244-2270); MOEN [M/2+1][C], bin 0 calcDCWeights written into the C-long
+// vector: (1, 0) then zeros (the vector starts zeroed, beamformer.cc:916; only min(dim, C) entries are written here, the reference writes
+// past the end when dim > C)
+void dir_weights(dsr_sph& s, double theta, double phi, std::vector<zc>& W);
 
 void harmonics_at(const dsr_sph& s, double theta, double phi, zc* Y)
 {
@@ -256,16 +366,105 @@ void harmonics_at(const dsr_sph& s, double theta, double phi, zc* Y)
     for (int m = -n; m <= n; m++, idx++) Y[idx] = sph_harmonic(m, n, theta, phi);
 }
 
+void dir_weights(dsr_sph& s, double theta, double phi, std::vector<zc>& W)
+{
+  const int F = s.M / 2 + 1, D = s.dim, L = sensor_kind(s.kind) ? s.C : D;
+  W.assign((size_t) F * L, zc(0, 0));
+  std::vector<zc> Y(D); harmonics_at(s, theta, phi, Y.data());
+  if (s.kind == DSR_SPH_SPATIALDS) { for (int f = 0; f < F; f++) calc_spatial_ds(s, f, Y.data(), &W[(size_t) f * L]); return; }
+  W[0] = zc(1, 0);                                           // calcDCWeights: 1 for n = 0
+  if (s.kind == DSR_SPH_MOEN) { ensure_fixed_w(s); for (int f = 1; f < F; f++) calc_moen(s, f, Y.data(), &W[(size_t) f * L]); return; }
+  for (int f = 1; f < F; f++) calc_weights(s, f, Y.data(), &W[(size_t) f * D]);
+}
+
 void ensure_look(dsr_sph& s)                                 // _calcSteeringUnit(0): DC weights at bin 0, _calcWeights at 1..M/2
 {
   ensure_modes(s);
   if (!s.lookDirty) return;
   const int F = s.M / 2 + 1, D = s.dim;
-  s.look.assign((size_t) F * D, zc(0, 0));
-  s.look[0] = zc(1, 0);                                      // calcDCWeights: 1 for n = 0
-  std::vector<zc> Y(D); harmonics_at(s, s.lookTheta, s.lookPhi, Y.data());
-  for (int f = 1; f < F; f++) calc_weights(s, f, Y.data(), &s.look[(size_t) f * D]);
+  if (gsc_kind(s.kind) && (s.NC < 1 || s.NC >= D))           // beamformerWeights allocates no B then (beamformer.cc:921-924) and calcBlockingMatrix throws
+    throw Error(DSR_E_PARAMETER, "NC %d: the blocking matrix of a %d-dimensional quiescent vector needs 1 <= NC < %d", s.NC, D, D);
+  dir_weights(s, s.lookTheta, s.lookPhi, s.look);
+  if (gsc_kind(s.kind)) {                                    // calcBlockingMatrix per bin 1..M/2 (_calcSteeringUnit(0, isGSC) :727-729); wl stays as last set
+    // _calcBlockingMatrix projects with I - conj(d) d^T / ||d||^2: its columns are orthogonal to conj(d).  The reference hands it wq itself, so
+    // with the complex modal wq its B does not block wq (|B^H wq| / ||wq|| up to 0.9) and the look direction's eigenbeams, which are
+    // proportional to wq, leak into the sidelobe path.  Here it gets conj(wq): B^H wq = 0, a blocking matrix in fact (a deviation).
+    const int bs = D - s.NC;
+    s.Bm.assign((size_t) F * D * bs, zc(0, 0));
+    if (s.wl.size() != (size_t) F * D) s.wl.assign((size_t) F * D, zc(0, 0));
+    std::vector<zc> cq(D);
+    for (int f = 1; f < F; f++) {
+      for (int d = 0; d < D; d++) cq[d] = std::conj(s.look[(size_t) f * D + d]);
+      zc* B = &s.Bm[(size_t) f * D * bs];
+      if (!blocking_matrix_nc(cq.data(), D, s.NC, B)) throw Error(DSR_E_ERROR, "_calcBlockingMatrix() failed");
+      // its classical Gram-Schmidt loses the orthogonality to wq over many columns (1e-5 of ||wq|| over the 63 of order 8, whose wq spans 20
+      // decades at the low bins): one projection of every column against wq restores it (the columns move by that much, no more)
+      double n2 = 0.0;
+      for (int d = 0; d < D; d++) n2 += std::norm(cq[d]);
+      for (int j = 0; j < bs; j++) {
+        zc ip(0, 0);
+        for (int d = 0; d < D; d++) ip += cq[d] * B[(size_t) d * bs + j];           // wq^H B_j
+        ip = zc(ip.real() / n2, ip.imag() / n2);
+        for (int d = 0; d < D; d++) B[(size_t) d * bs + j] -= ip * std::conj(cq[d]);
+      }
+    }
+  }
   s.lookDirty = false; s.dLookDirty = true;
+}
+
+// what the output applies: the look weights; for the GSC kinds calcOutputOfGSC's (wq - wl), with normalizeWeight divided by ||.|| dim, at bins >= 1
+// (beamformer.cc:1251-1287; SphericalGSCBeamformer::next :1508-1533).  wl: null for a beam other than the look direction (no active weights).
+void effective(const dsr_sph& s, const std::vector<zc>& wq, const zc* wl, std::vector<zc>& eff)
+{
+  eff = wq;
+  if (!gsc_kind(s.kind)) return;
+  const int F = s.M / 2 + 1, D = s.dim;
+  for (int f = 1; f < F; f++) {
+    zc* e = &eff[(size_t) f * D];
+    if (wl) for (int d = 0; d < D; d++) e[d] = e[d] - wl[(size_t) f * D + d];
+    if (s.normalize) {
+      double ss = 0.0;
+      for (int d = 0; d < D; d++) ss += std::norm(e[d]);
+      const double de = std::sqrt(ss) * (unsigned) D;
+      for (int d = 0; d < D; d++) e[d] = gdivr(e[d], de);
+    }
+  }
+}
+
+// v [F][C] = S^H w per bin for modal weights w [F][dim] (v^H x = w^H (S x)); sensor-domain weights are v already
+void fold(const dsr_sph& s, const std::vector<zc>& w, zc* v)
+{
+  const int F = s.M / 2 + 1, D = s.dim, C = s.C;
+  if (sensor_kind(s.kind)) { std::copy(w.begin(), w.end(), v); return; }
+  for (int f = 0; f < F; f++) {
+    zc* vf = v + (size_t) f * C;
+    for (int c = 0; c < C; c++) vf[c] = zc(0, 0);
+    for (int d = 0; d < D; d++) {
+      const zc wd = w[(size_t) f * D + d];
+      if (wd == zc(0, 0)) continue;
+      const zc* sh = &s.SH[(size_t) d * C];
+      for (int c = 0; c < C; c++) vf[c] += wd * std::conj(sh[c]);
+    }
+  }
+}
+
+void ensure_beams(dsr_sph& s, int NB)                        // V [NB][F][C]: beam 0 the look direction with the active weights, beams 1.. as set
+{
+  if (NB < 1 || NB > MAX_BEAMS) throw Error(DSR_E_DIMENSION, "%d beams (1..%d supported)", NB, MAX_BEAMS);
+  for (int b = 1; b < NB; b++) if (!s.beamSet[b]) throw Error(DSR_E_ERROR, "beam %d of %d has no direction (dsr_sph_set_beam)", b, NB);
+  ensure_look(s);
+  if (s.vNB == NB && s.vSetGen == s.settingsGen && s.vBeamGen == s.beamGen) return;
+  const size_t FC = (size_t) (s.M / 2 + 1) * s.C;
+  s.V.assign((size_t) NB * FC, zc(0, 0));
+  std::vector<zc> w, eff;
+  effective(s, s.look, gsc_kind(s.kind) ? s.wl.data() : nullptr, eff);
+  fold(s, eff, s.V.data());
+  for (int b = 1; b < NB; b++) {
+    dir_weights(s, s.beamTheta[b], s.beamPhi[b], w);
+    effective(s, w, nullptr, eff);
+    fold(s, eff, &s.V[(size_t) b * FC]);
+  }
+  s.vNB = NB; s.vSetGen = s.settingsGen; s.vBeamGen = s.beamGen; s.dVDirty = true;
 }
 
 int grid_n(double mn, double mx, double w)                   // (unsigned)((max - min) / width + 0.5) (:803-804)
@@ -277,6 +476,8 @@ int grid_n(double mn, double mx, double w)                   // (unsigned)((max 
 void build_table(dsr_sph& s)                                 // _calcSteeringUnitTable (:793-858 / :1190-1246)
 {
   if (s.tbl) return;
+  if (s.kind > DSR_SPH_DS)                                   // the reference searches with the EB and DS weights only (DOAEstimatorSRPEB, DOAEstimatorSRPSphDSB)
+    throw Error(DSR_E_ERROR, "kind %d has no steering table: the SRP DOA estimators exist for DSR_SPH_EB and DSR_SPH_DS only", s.kind);
   check_range(s.fbinMin, s.fbinMax, s.M, s.M / 2);
   const int nT = grid_n(s.minTheta, s.maxTheta, s.widthTheta), nP = grid_n(s.minPhi, s.maxPhi, s.widthPhi);
   if (nT >= 1 && nP >= 1 && (long) nT * nP * (s.fbinMax + 1) * std::max(s.dim, s.C) > MAX_TABLE)
@@ -450,6 +651,201 @@ __global__ __launch_bounds__(256) void k_sph_frame(const double* __restrict__ rp
   }
 }
 
+// Y[u][b][t][f] = sum_c Vc[c][b][f] X[u][c][t][f] for NB beams (Vc = conj v, [C][NB][F]); one thread per E elements k = t F + f of a channel's
+// contiguous (t, f) plane, so the float2 loads are coalesced whatever F is.  sv: conj(v) of CC channels at a time, [CC][NB][F].  Rows from
+// nframes[u] on are written as zeros.
+template <int NB, int E>
+__global__ __launch_bounds__(256) void k_sph_beams_valu(const float2* __restrict__ X, const int* __restrict__ nframes, const double2* __restrict__ Vc,
+                                                        int C, int Tmax, int F, int CC, int nbOut, float2* __restrict__ Y)
+{
+  extern __shared__ double2 sv[];
+  const int u = blockIdx.y, tid = threadIdx.x;
+  int N = nframes[u]; if (N > Tmax) N = Tmax; if (N < 0) N = 0;
+  const long TF = (long) Tmax * F, live = (long) N * F, base = (long) blockIdx.x * (256 * E);
+  double yr[E][NB], yi[E][NB]; int fe[E]; long ke[E];
+#pragma unroll
+  for (int e = 0; e < E; e++) {
+    ke[e] = base + e * 256 + tid; fe[e] = (int) (ke[e] % F);
+#pragma unroll
+    for (int b = 0; b < NB; b++) { yr[e][b] = 0.0; yi[e][b] = 0.0; }
+  }
+  if (base < live) {                                         // workgroup-uniform
+    const float2* Xu = X + (long) u * C * TF;
+    for (int c0 = 0; c0 < C; c0 += CC) {
+      const int nc = C - c0 < CC ? C - c0 : CC;
+      __syncthreads();
+      for (int idx = tid; idx < nc * NB * F; idx += 256) sv[idx] = Vc[(long) c0 * NB * F + idx];
+      __syncthreads();
+      for (int cc = 0; cc < nc; cc++) {
+        float2 x[E];
+#pragma unroll
+        for (int e = 0; e < E; e++) x[e] = ke[e] < live ? Xu[(long) (c0 + cc) * TF + ke[e]] : make_float2(0.f, 0.f);
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+          const double xr = x[e].x, xi = x[e].y;
+#pragma unroll
+          for (int b = 0; b < NB; b++) {
+            const double2 v = sv[(cc * NB + b) * F + fe[e]];
+            yr[e][b] += v.x * xr - v.y * xi; yi[e][b] += v.x * xi + v.y * xr;
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < E; e++) {
+    if (ke[e] >= TF) continue;
+#pragma unroll
+    for (int b = 0; b < NB; b++)
+      if (b < nbOut) Y[((long) u * nbOut + b) * TF + ke[e]] = make_float2((float) yr[e][b], (float) yi[e][b]);
+  }
+}
+
+// the same as one complex GEMM per bin on v_mfma_f64_16x16x4_f64: the staging and operand layout of k_doa_srp with one row tile (the beams, zero
+// padded to 16), Vp [F][KS][64] = conj v as the A operand; result register q of lane l is beam (l >> 4) + 4 q of frame l & 15.  A chunk's results
+// are kept as float2 and stored a beam row at a time (consecutive bins of one frame).  Frames from nframes[u] on are staged as zeros.
+template <int BCT>
+__global__ __launch_bounds__(256) void k_sph_beams_mfma(const float2* __restrict__ X, const int* __restrict__ nframes, const double2* __restrict__ Vp,
+                                                        int C, int Tmax, int F, int NB, int KS, float2* __restrict__ Y)
+{
+  extern __shared__ float2 xs[];                             // [C][FB][pitch]
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 15, kq = lane >> 4;
+  const int t0 = blockIdx.x * FB, u = blockIdx.y;
+  int N = nframes[u]; if (N > Tmax) N = Tmax; if (N < 0) N = 0;
+  const int BP = bin_pitch(BCT), tw = t0 + wave * 16 + i;
+  const float2* Xu = X + (long) u * C * Tmax * F;
+  if (t0 >= N) {                                             // workgroup-uniform: nothing to read, the rows are zero
+    const int nt = Tmax - t0 < FB ? Tmax - t0 : FB;
+    for (int b = 0; b < NB; b++)
+      for (int idx = threadIdx.x; idx < nt * F; idx += 256) Y[(((long) u * NB + b) * Tmax + t0) * F + idx] = make_float2(0.f, 0.f);
+    return;
+  }
+  for (int f0 = 0; f0 < F; f0 += BCT) {
+    const int nb = F - f0 < BCT ? F - f0 : BCT;
+    srp_stage_chunk(xs, Xu, C, Tmax, F, BCT, BP, t0, N, f0, nb);
+    float2 out[BCT][4];
+#pragma unroll
+    for (int b = 0; b < BCT; b++) {
+      d4 cr = {0.0, 0.0, 0.0, 0.0}, ci = {0.0, 0.0, 0.0, 0.0};
+      if (b < nb) {                                          // uniform
+        const double2* vp = Vp + (long) (f0 + b) * KS * 64 + lane;   // lane: conj(v[beam = l & 15][c = 4 ks + (l >> 4)])
+        const float2* xb = xs + (kq * FB + wave * 16 + i) * BP + b;  // + 4 ks FB BP: channel 4 ks + (l >> 4)
+        int ks = 0;
+        for (; ks + 4 <= KS; ks += 4) {
+          double2 a[4]; float2 x[4];
+#pragma unroll
+          for (int j = 0; j < 4; j++) { a[j] = vp[(ks + j) * 64]; x[j] = ks * 4 + 4 * j + kq < C ? xb[(ks + j) * 4 * FB * BP] : make_float2(0.f, 0.f); }
+#pragma unroll
+          for (int j = 0; j < 4; j++) cmfma(a[j].x, a[j].y, (double) x[j].x, (double) x[j].y, cr, ci);
+        }
+        for (; ks < KS; ks++) {
+          const double2 a = vp[ks * 64];
+          const float2 x = ks * 4 + kq < C ? xb[ks * 4 * FB * BP] : make_float2(0.f, 0.f);
+          cmfma(a.x, a.y, (double) x.x, (double) x.y, cr, ci);
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; q++) out[b][q] = make_float2((float) cr[q], (float) ci[q]);
+    }
+    if (tw < Tmax) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int beam = kq + 4 * q;
+        if (beam >= NB) continue;
+        float2* y = Y + (((long) u * NB + beam) * Tmax + tw) * F + f0;
+#pragma unroll
+        for (int b = 0; b < BCT; b++) if (b < nb) y[b] = out[b][q];
+      }
+    }
+  }
+}
+
+int beams_bin_chunk(int C)                                   // the staged chunk's bins: the power of two <= 8 whose rows fit (srp_common.h: bin_chunk)
+{
+  const int BC = bin_chunk(C);
+  return BC > 8 ? 8 : BC;
+}
+
+int beams_path(int NB)                                       // 0 VALU (NB <= 4), 1 MFMA; DSR_SPH_BEAMS_PATH=valu|mfma forces one (measurements)
+{
+  const char* e = getenv("DSR_SPH_BEAMS_PATH");
+  if (e && *e) {
+    if (!strcmp(e, "valu")) return 0;
+    if (!strcmp(e, "mfma")) return 1;
+    throw Error(DSR_E_PARAMETER, "DSR_SPH_BEAMS_PATH=%s: valu or mfma", e);
+  }
+  return NB <= 4 ? 0 : 1;
+}
+
+constexpr size_t BEAMS_LDS = 48 * 1024;                      // the VALU kernel's staged conj(v): CC channels x NBT beams x F bins
+
+template <int NBT, int E>
+void launch_beams_valu(const dsr_sph& s, const float* X, const int* nf, int U, int Tmax, int NB, float* Y, hipStream_t st)
+{
+  const int F = s.M / 2 + 1;
+  int CC = (int) (BEAMS_LDS / ((size_t) NBT * F * sizeof(double2))); if (CC > s.C) CC = s.C;
+  if (CC < 1) throw Error(DSR_E_DIMENSION, "%d beams x %d bins do not fit the kernel's %zu bytes of LDS", NBT, F, BEAMS_LDS);
+  const size_t lds = (size_t) CC * NBT * F * sizeof(double2);
+  hipLaunchKernelGGL((k_sph_beams_valu<NBT, E>), dim3(cdiv((long) Tmax * F, 256 * E), U), dim3(256), lds, st, (const float2*) X, nf, s.dV.p, s.C, Tmax, F, CC, NB,
+                     (float2*) Y);
+  DSR_HIP(hipGetLastError());
+}
+
+template <int BCT>
+void launch_beams_mfma(const dsr_sph& s, const float* X, const int* nf, int U, int Tmax, int NB, float* Y, hipStream_t st)
+{
+  const size_t lds = (size_t) s.C * FB * bin_pitch(BCT) * sizeof(float2);
+  hipLaunchKernelGGL((k_sph_beams_mfma<BCT>), dim3((Tmax + FB - 1) / FB, U), dim3(256), lds, st, (const float2*) X, nf, s.dV.p, s.C, Tmax, s.M / 2 + 1, NB,
+                     (s.C + 3) / 4, (float2*) Y);
+  DSR_HIP(hipGetLastError());
+}
+
+int valu_rows(int NB) { return NB <= 4 ? NB : NB <= 8 ? 8 : 16; }   // the VALU kernel's instantiations: 1..4 exact, above that zero-padded rows
+
+// the kernel of one call: beams_path, but where one channel of the VALU kernel's staged table (rows x F bins) is more than its LDS holds -- rows F
+// > 3072: fftLen 2048 with 3 or 4 beams, fftLen >= 6144 with one -- the MFMA kernel, which stages snapshots and has no such limit, takes the call
+// (a forced DSR_SPH_BEAMS_PATH=valu is left to fail with DSR_E_DIMENSION: it is for measurements)
+int beams_path_for(int NB, int F)
+{
+  const int path = beams_path(NB);
+  if (path == 0 && (size_t) valu_rows(NB) * F * sizeof(double2) > BEAMS_LDS && !getenv("DSR_SPH_BEAMS_PATH")) return 1;
+  return path;
+}
+
+void upload_beams(dsr_sph& s, int NB, int path, hipStream_t st)   // conj(v): layout 0 [F][KS][64] (MFMA A operand), n > 0 [C][n][F] (VALU, n rows)
+{
+  const int layout = path == 1 ? 0 : valu_rows(NB);
+  if (!s.dVDirty && s.dVLayout == layout) return;
+  const int F = s.M / 2 + 1, C = s.C, KS = (C + 3) / 4;
+  std::vector<double2> h;
+  if (layout == 0) {
+    h.assign((size_t) F * KS * 64, make_double2(0.0, 0.0));
+    for (int f = 0; f < F; f++)
+      for (int ks = 0; ks < KS; ks++)
+        for (int l = 0; l < 64; l++) {
+          const int b = l & 15, c = ks * 4 + (l >> 4);
+          if (b >= NB || c >= C) continue;
+          const zc v = s.V[((size_t) b * F + f) * C + c];
+          h[((size_t) f * KS + ks) * 64 + l] = make_double2(v.real(), -v.imag());
+        }
+  } else {
+    h.assign((size_t) C * layout * F, make_double2(0.0, 0.0));
+    for (int c = 0; c < C; c++)
+      for (int b = 0; b < NB; b++)
+        for (int f = 0; f < F; f++) {
+          const zc v = s.V[((size_t) b * F + f) * C + c];
+          h[((size_t) c * layout + b) * F + f] = make_double2(v.real(), -v.imag());
+        }
+  }
+  s.dV.upload(h, st); s.dVLayout = layout; s.dVDirty = false;
+}
+
+int pattern_n(double mn, double mx, double w)                // (int)(float)((max - min) / width + 0.5 + 1) (:759-766)
+{
+  const float n = (float) ((mx - mn) / w + 0.5 + 1);
+  return n >= 1.0f && n < 1e6f ? (int) n : 0;
+}
+
 const char* forced_path()
 {
   const char* e = getenv("DSR_SPH_SRP_PATH");
@@ -551,7 +947,7 @@ void set_geometry(dsr_sph& s, double a, const double* th, const double* ph, int 
   for (int n_ = 0, idx = 0; n_ < s.maxOrder; n_++)
     for (int m = -n_; m <= n_; m++, idx++)
       for (int c = 0; c < s.C; c++) s.SH[(size_t) idx * s.C + c] = std::conj(sph_harmonic(m, n_, th[c], ph[c]));
-  s.B.clear(); s.lookDirty = true; s.dSDirty = true; s.foldGen = ~0u; s.settingsGen++;   // a new radius: new mode amplitudes (the table is not rebuilt)
+  s.B.clear(); s.lookDirty = true; s.dSDirty = true; s.foldGen = ~0u; s.fixedWValid = false; s.settingsGen++;   // a new radius: new mode amplitudes (the table is not rebuilt)
 }
 
 }  // namespace
@@ -560,10 +956,9 @@ extern "C" {
 
 dsr_status dsr_sph_create(int kind, int nBest, int sampleRate, int fftLen, int halfBandShift, int NC, int maxOrder, int normalizeWeight, int chanN, dsr_sph** out)
 {
-  (void) NC;                                                 // only passed on by the reference (beamformerWeights' NC), never used here
-  return guard([&] {
+  return guard([&] {                                         // NC: beamformerWeights' number of constraints, used by the GSC kinds' blocking matrix only
     if (!out) throw Error(DSR_E_PARAMETER, "null argument");
-    if (kind != DSR_SPH_EB && kind != DSR_SPH_DS) throw Error(DSR_E_PARAMETER, "kind %d (DSR_SPH_EB or DSR_SPH_DS)", kind);
+    if (kind < DSR_SPH_EB || kind > DSR_SPH_MOEN) throw Error(DSR_E_PARAMETER, "kind %d (DSR_SPH_EB .. DSR_SPH_MOEN)", kind);
     if (halfBandShift) throw Error(DSR_E_PARAMETER, "_halfBandShift == true is not implemented yet");    // modalBeamformer.cc:391-394
     if (nBest < 1) throw Error(DSR_E_PARAMETER, "nBest %d < 1", nBest);
     if (fftLen < 2 || (fftLen & 1)) throw Error(DSR_E_PARAMETER, "fftLen %d", fftLen);
@@ -572,6 +967,7 @@ dsr_status dsr_sph_create(int kind, int nBest, int sampleRate, int fftLen, int h
     if (maxOrder < 1 || maxOrder > MAX_ORDER) throw Error(DSR_E_DIMENSION, "maxOrder %d: 1..%d supported (dim = maxOrder^2 <= %d)", maxOrder, MAX_ORDER, MAX_ORDER * MAX_ORDER);
     dsr_sph* s = new dsr_sph(); s->kind = kind; s->nBest = nBest; s->sampleRate = (unsigned) sampleRate; s->M = fftLen; s->C = chanN;
     s->maxOrder = maxOrder; s->dim = maxOrder * maxOrder; s->normalize = normalizeWeight != 0; s->fbinMax = fftLen / 2;
+    s->NC = NC; s->diag.assign((size_t) fftLen / 2 + 1, 0.0f);
     *out = s;
   });
 }
@@ -617,7 +1013,7 @@ dsr_status dsr_sph_set_look_direction(dsr_sph* s, double theta, double phi)
 {
   return guard([&] {
     if (!s) throw Error(DSR_E_PARAMETER, "null argument");
-    s->lookTheta = theta; s->lookPhi = phi; s->lookDirty = true; s->settingsGen++;   // (the reference warns when theta is outside [0, pi] and goes on)
+    s->lookTheta = theta; s->lookPhi = phi; s->lookDirty = true; s->lookSet = true; s->settingsGen++;   // (the reference warns when theta is outside [0, pi] and goes on)
   });
 }
 dsr_status dsr_sph_set_sigma2(dsr_sph* s, float sigma2)
@@ -647,6 +1043,7 @@ dsr_status dsr_sph_look_weights(dsr_sph* s, double* out, size_t outDoubles)
 {
   return guard([&] {
     if (!s || !out) throw Error(DSR_E_PARAMETER, "null argument");
+    if (sensor_kind(s->kind)) throw Error(DSR_E_ERROR, "this kind's weights are in the sensor domain (dsr_sph_sensor_weights)");
     ensure_look(*s);
     if (outDoubles < s->look.size() * 2) throw Error(DSR_E_DIMENSION, "output holds %zu doubles, %zu needed", outDoubles, s->look.size() * 2);
     for (size_t i = 0; i < s->look.size(); i++) { out[2 * i] = s->look[i].real(); out[2 * i + 1] = s->look[i].imag(); }
@@ -661,6 +1058,7 @@ dsr_status dsr_sph_calc_wng(dsr_sph* s, double* out, int n)
     if (n < F) throw Error(DSR_E_DIMENSION, "room for %d bins, %d needed", n, F);
     const double norm = s->C / (M_PI * M_PI);
     for (int f = 0; f < F; f++) {
+      if (hwnc(s->kind)) { out[f] = hwnc_wng(*s, f); continue; }   // SphericalHWNCBeamformer::calcWNG (:1397-1418)
       double val = 0;
       for (int o = 0; o < s->maxOrder; o++) val += (2 * o + 1) * std::norm(s->B[(size_t) f * s->maxOrder + o]);
       out[f] = val * val * norm;
@@ -741,14 +1139,18 @@ dsr_status dsr_sph_apply(dsr_sph* s, const float* X_dev, const int32_t* nframes_
   return guard([&] {
     if (!s || !X_dev || !nframes_dev || !Y_dev) throw Error(DSR_E_PARAMETER, "null argument");
     if (U < 0 || Tmax < 0) throw Error(DSR_E_DIMENSION, "U %d, Tmax %d", U, Tmax);
+    if (sensor_kind(s->kind) && !F_dev) throw Error(DSR_E_ERROR, "this kind has no eigenbeam weights: dsr_sph_beams computes its output");
     ensure_look(*s);
     require_device();
     if (U == 0 || Tmax == 0) return;
     hipStream_t st = (hipStream_t) stream;
     upload_s(*s, st);
-    if (s->dLookDirty) {
-      std::vector<double2> h(s->look.size());
-      for (size_t i = 0; i < h.size(); i++) h[i] = make_double2(s->look[i].real(), s->look[i].imag());
+    if (s->dLookDirty) {                                     // the GSC kinds: (wq - wl); the sensor-domain kinds: zeros (Y_dev is then only a by-product of F_dev)
+      std::vector<zc> eff;
+      if (sensor_kind(s->kind)) eff.assign((size_t) (s->M / 2 + 1) * s->dim, zc(0, 0));
+      else effective(*s, s->look, gsc_kind(s->kind) ? s->wl.data() : nullptr, eff);
+      std::vector<double2> h(eff.size());
+      for (size_t i = 0; i < h.size(); i++) h[i] = make_double2(eff[i].real(), eff[i].imag());
       s->dLook.upload(h, st); s->dLookDirty = false;
     }
     const int F = s->M / 2 + 1;
@@ -756,6 +1158,194 @@ dsr_status dsr_sph_apply(dsr_sph* s, const float* X_dev, const int32_t* nframes_
     hipLaunchKernelGGL(k_sph_apply, dim3(cdiv((long) Tmax * F, 256), U), dim3(256), 0, st, (const float2*) X_dev, nframes_dev, s->dS.p, s->dLook.p,
                        s->C, Tmax, F, s->dim, (float2*) Y_dev, (float2*) F_dev);
     DSR_HIP(hipGetLastError());
+  });
+}
+
+dsr_status dsr_sph_set_wng(dsr_sph* s, float ratio)
+{
+  return guard([&] {                                        // setWNG (modalBeamformer.h:329); the weights follow at once, as with set_sigma2
+    if (!s) throw Error(DSR_E_PARAMETER, "null argument");
+    if (!hwnc(s->kind)) throw Error(DSR_E_ERROR, "setWNG: not a SphericalHWNC(GSC)Beamformer");
+    s->ratio = ratio; s->lookDirty = true; s->settingsGen++;
+  });
+}
+dsr_status dsr_sph_set_active_weights_f(dsr_sph* s, unsigned fbinX, const double* packed, size_t n)
+{
+  return guard([&] {                                        // setActiveWeights_f (:1586-1594) -> calcSidelobeCancellerP_f (beamformer.cc:761-783)
+    if (!s || !packed) throw Error(DSR_E_PARAMETER, "null argument");
+    if (!gsc_kind(s->kind)) throw Error(DSR_E_ERROR, "setActiveWeights_f: not a Spherical(HWNC)GSCBeamformer");
+    if (!s->lookSet) throw Error(DSR_E_ERROR, "call setLookDirection() once");
+    ensure_look(*s);
+    const int D = s->dim, bs = D - s->NC;
+    if (n != (size_t) 2 * bs) throw Error(DSR_E_DIMENSION, "the size of an active weight vector must be %d but it is %zu", 2 * bs, n);
+    if (fbinX > (unsigned) s->M / 2) throw Error(DSR_E_DIMENSION, "Must be a frequency bin %u <= %d", fbinX, s->M / 2);
+    std::vector<zc> wa(bs);
+    for (int c = 0; c < bs; c++) wa[c] = zc(packed[2 * c], packed[2 * c + 1]);
+    sidelobe_wl(&s->Bm[(size_t) fbinX * D * bs], wa.data(), D, bs, &s->wl[(size_t) fbinX * D]);
+    s->dLookDirty = true; s->settingsGen++;
+  });
+}
+dsr_status dsr_sph_set_diagonal_loading(dsr_sph* s, unsigned fbinX, float diagonalWeight)
+{
+  return guard([&] {                                        // setLevelOfDiagonalLoading (:1923-1930); the reference only prints for a bin beyond fftLen/2
+    if (!s) throw Error(DSR_E_PARAMETER, "null argument");
+    if (s->kind != DSR_SPH_MOEN) throw Error(DSR_E_ERROR, "setLevelOfDiagonalLoading: not a SphericalMOENBeamformer");
+    if (fbinX > (unsigned) s->M / 2) throw Error(DSR_E_DIMENSION, "Invalid freq. bin %u (0..%d)", fbinX, s->M / 2);
+    s->diag[fbinX] = diagonalWeight; s->fixedWValid = false; s->lookDirty = true; s->settingsGen++;
+  });
+}
+dsr_status dsr_sph_fix_terms(dsr_sph* s, int flag)
+{
+  return guard([&] {                                        // fixTerms (modalBeamformer.h:443)
+    if (!s) throw Error(DSR_E_PARAMETER, "null argument");
+    if (s->kind != DSR_SPH_MOEN) throw Error(DSR_E_ERROR, "fixTerms: not a SphericalMOENBeamformer");
+    s->fixedTerms = flag != 0; s->lookDirty = true; s->settingsGen++;
+  });
+}
+dsr_status dsr_sph_wl(dsr_sph* s, double* out, size_t outDoubles)
+{
+  return guard([&] {
+    if (!s || !out) throw Error(DSR_E_PARAMETER, "null argument");
+    if (!gsc_kind(s->kind)) throw Error(DSR_E_ERROR, "not a Spherical(HWNC)GSCBeamformer");
+    ensure_look(*s);
+    if (outDoubles < s->wl.size() * 2) throw Error(DSR_E_DIMENSION, "output holds %zu doubles, %zu needed", outDoubles, s->wl.size() * 2);
+    for (size_t i = 0; i < s->wl.size(); i++) { out[2 * i] = s->wl[i].real(); out[2 * i + 1] = s->wl[i].imag(); }
+  });
+}
+dsr_status dsr_sph_blocking_matrix(dsr_sph* s, unsigned fbinX, double* out, size_t outDoubles)
+{
+  return guard([&] {
+    if (!s || !out) throw Error(DSR_E_PARAMETER, "null argument");
+    if (!gsc_kind(s->kind)) throw Error(DSR_E_ERROR, "not a Spherical(HWNC)GSCBeamformer");
+    ensure_look(*s);
+    const size_t n = (size_t) s->dim * (s->dim - s->NC);
+    if (fbinX > (unsigned) s->M / 2) throw Error(DSR_E_DIMENSION, "frequency bin %u (0..%d)", fbinX, s->M / 2);
+    if (outDoubles < n * 2) throw Error(DSR_E_DIMENSION, "output holds %zu doubles, %zu needed", outDoubles, n * 2);
+    const zc* B = &s->Bm[(size_t) fbinX * n];
+    for (size_t i = 0; i < n; i++) { out[2 * i] = B[i].real(); out[2 * i + 1] = B[i].imag(); }
+  });
+}
+dsr_status dsr_sph_set_beam(dsr_sph* s, int b, double theta, double phi)
+{
+  return guard([&] {
+    if (!s) throw Error(DSR_E_PARAMETER, "null argument");
+    if (b < 0 || b >= MAX_BEAMS) throw Error(DSR_E_DIMENSION, "beam %d (0..%d)", b, MAX_BEAMS - 1);
+    if (b == 0) { s->lookTheta = theta; s->lookPhi = phi; s->lookDirty = true; s->lookSet = true; s->settingsGen++; return; }
+    s->beamTheta[b] = theta; s->beamPhi[b] = phi; s->beamSet[b] = true; s->beamGen++;
+  });
+}
+dsr_status dsr_sph_set_beams_nbest(dsr_sph* s, dsr_sph* doa, const int32_t* nbest_idx, int n)
+{
+  return guard([&] {
+    if (!s || !doa || !nbest_idx) throw Error(DSR_E_PARAMETER, "null argument");
+    if (n < 1 || n > MAX_BEAMS) throw Error(DSR_E_DIMENSION, "%d beams (1..%d supported)", n, MAX_BEAMS);
+    if (!doa->tbl) throw Error(DSR_E_ERROR, "no steering table: run the estimator after construction / setSearchParam first");
+    for (int b = 0; b < n; b++)
+      if (nbest_idx[b] < 0 || nbest_idx[b] >= units(*doa)) throw Error(DSR_E_INDEX, "rank %d: unit %d of %d (an empty rank has no direction)", b, nbest_idx[b], units(*doa));
+    for (int b = 0; b < n; b++) {
+      const double th = doa->uTheta[nbest_idx[b]], ph = doa->uPhi[nbest_idx[b]];
+      if (b == 0) { s->lookTheta = th; s->lookPhi = ph; s->lookDirty = true; s->lookSet = true; s->settingsGen++; }
+      else { s->beamTheta[b] = th; s->beamPhi[b] = ph; s->beamSet[b] = true; s->beamGen++; }
+    }
+  });
+}
+dsr_status dsr_sph_beam_weights(dsr_sph* s, int NB, double* out, size_t outDoubles)
+{
+  return guard([&] {
+    if (!s || !out) throw Error(DSR_E_PARAMETER, "null argument");
+    ensure_beams(*s, NB);
+    if (outDoubles < s->V.size() * 2) throw Error(DSR_E_DIMENSION, "output holds %zu doubles, %zu needed", outDoubles, s->V.size() * 2);
+    for (size_t i = 0; i < s->V.size(); i++) { out[2 * i] = s->V[i].real(); out[2 * i + 1] = s->V[i].imag(); }
+  });
+}
+dsr_status dsr_sph_sensor_weights(dsr_sph* s, double* out, size_t outDoubles)
+{
+  return guard([&] {
+    if (!s || !out) throw Error(DSR_E_PARAMETER, "null argument");
+    if (!sensor_kind(s->kind)) throw Error(DSR_E_ERROR, "this kind's weights are modal (dsr_sph_look_weights; dsr_sph_beam_weights folds them)");
+    ensure_look(*s);
+    if (outDoubles < s->look.size() * 2) throw Error(DSR_E_DIMENSION, "output holds %zu doubles, %zu needed", outDoubles, s->look.size() * 2);
+    for (size_t i = 0; i < s->look.size(); i++) { out[2 * i] = s->look[i].real(); out[2 * i + 1] = s->look[i].imag(); }
+  });
+}
+int dsr_sph_beams_path(int NB)
+{
+  try { return beams_path(NB); } catch (const Error& e) { set_last_error(e.msg); return -1; }
+}
+dsr_status dsr_sph_beam_pattern_n(double minTheta, double maxTheta, double minPhi, double maxPhi, double widthTheta, double widthPhi, int* nTheta, int* nPhi)
+{
+  return guard([&] {
+    if (!nTheta || !nPhi) throw Error(DSR_E_PARAMETER, "null argument");
+    if (!(widthTheta > 0.0) || !(widthPhi > 0.0)) throw Error(DSR_E_PARAMETER, "widths %g, %g must be positive", widthTheta, widthPhi);
+    *nTheta = pattern_n(minTheta, maxTheta, widthTheta); *nPhi = pattern_n(minPhi, maxPhi, widthPhi);
+  });
+}
+dsr_status dsr_sph_beam_pattern(dsr_sph* s, unsigned fbinX, double theta, double phi, double minTheta, double maxTheta, double minPhi, double maxPhi,
+                                double widthTheta, double widthPhi, double* out, size_t outDoubles)
+{
+  return guard([&] {                                        // getBeamPattern (:756-787; MOEN :2068-2099)
+    if (!s || !out) throw Error(DSR_E_PARAMETER, "null argument");
+    if (!(widthTheta > 0.0) || !(widthPhi > 0.0)) throw Error(DSR_E_PARAMETER, "widths %g, %g must be positive", widthTheta, widthPhi);
+    if (fbinX > (unsigned) s->M / 2) throw Error(DSR_E_INDEX, "frequency bin %u (0..%d)", fbinX, s->M / 2);
+    need_geometry(*s);
+    const int nT = pattern_n(minTheta, maxTheta, widthTheta), nP = pattern_n(minPhi, maxPhi, widthPhi), C = s->C, D = s->dim;
+    if (nT < 1 || nP < 1) throw Error(DSR_E_PARAMETER, "beam-pattern grid of %d x %d directions", nT, nP);
+    if (outDoubles < (size_t) nT * nP) throw Error(DSR_E_DIMENSION, "output holds %zu doubles, %zu needed", outDoubles, (size_t) nT * nP);
+    s->lookTheta = theta; s->lookPhi = phi; s->lookDirty = true; s->lookSet = true; s->settingsGen++;   // it calls setLookDirection (:768)
+    ensure_look(*s);
+    const bool sensor = sensor_kind(s->kind);
+    const zc* w = &s->look[(size_t) fbinX * (sensor ? C : D)];   // wq_f(fbinX): the quiescent weights, whatever the active ones
+    const double ka = 2.0 * M_PI * fbinX * s->a * s->sampleRate / (s->M * SSPEED);
+    std::vector<zc> p(C);
+    double th = minTheta;
+    for (int it = 0; it < nT; it++, th += widthTheta) {
+      double ph = minPhi;
+      for (int ip = 0; ip < nP; ip++, ph += widthPhi) {
+        for (int c = 0; c < C; c++)                          // planeWaveOnSphericalAperture (:737-747)
+          p[c] = std::polar(1.0, ka * (std::sin(s->thS[c]) * std::sin(th) * std::cos(s->phS[c] - ph) + std::cos(s->thS[c]) * std::cos(th)));
+        zc val(0, 0);
+        if (s->kind == DSR_SPH_MOEN) for (int c = 0; c < C; c++) val += gmul(w[c], p[c]);                  // zdotu (:2091)
+        else if (sensor) for (int c = 0; c < C; c++) val += gmul(std::conj(w[c]), p[c]);                   // SpatialDS: w^H p
+        else
+          for (int d = 0; d < D; d++) {                      // sphericalHarmonicsTransformation (zdotu), then zdotc
+            zc Fd(0, 0);
+            for (int c = 0; c < C; c++) Fd += gmul(p[c], s->SH[(size_t) d * C + c]);
+            val += gmul(std::conj(w[d]), Fd);
+          }
+        out[(size_t) it * nP + ip] = std::hypot(val.real(), val.imag());
+      }
+    }
+  });
+}
+
+dsr_status dsr_sph_beams(dsr_sph* s, const float* X_dev, const int32_t* nframes_dev, int U, int Tmax, int NB, float* Y_dev, void* stream)
+{
+  return guard([&] {
+    if (!s || !X_dev || !nframes_dev || !Y_dev) throw Error(DSR_E_PARAMETER, "null argument");
+    if (U < 0 || Tmax < 0) throw Error(DSR_E_DIMENSION, "U %d, Tmax %d", U, Tmax);
+    ensure_beams(*s, NB);
+    const int F = s->M / 2 + 1, path = beams_path_for(NB, F);
+    if ((long) Tmax * F > 0x7fffffffL) throw Error(DSR_E_DIMENSION, "Tmax %d x %d bins", Tmax, F);
+    require_device();
+    if (U == 0 || Tmax == 0) return;
+    hipStream_t st = (hipStream_t) stream;
+    upload_beams(*s, NB, path, st);
+    if (path == 1) {
+      const int BC = beams_bin_chunk(s->C);
+      if (BC == 8) launch_beams_mfma<8>(*s, X_dev, nframes_dev, U, Tmax, NB, Y_dev, st);
+      else if (BC == 4) launch_beams_mfma<4>(*s, X_dev, nframes_dev, U, Tmax, NB, Y_dev, st);
+      else if (BC == 2) launch_beams_mfma<2>(*s, X_dev, nframes_dev, U, Tmax, NB, Y_dev, st);
+      else launch_beams_mfma<1>(*s, X_dev, nframes_dev, U, Tmax, NB, Y_dev, st);
+    } else {
+      switch (valu_rows(NB)) {
+      case 1: launch_beams_valu<1, 4>(*s, X_dev, nframes_dev, U, Tmax, NB, Y_dev, st); break;
+      case 2: launch_beams_valu<2, 4>(*s, X_dev, nframes_dev, U, Tmax, NB, Y_dev, st); break;
+      case 3: launch_beams_valu<3, 4>(*s, X_dev, nframes_dev, U, Tmax, NB, Y_dev, st); break;
+      case 4: launch_beams_valu<4, 4>(*s, X_dev, nframes_dev, U, Tmax, NB, Y_dev, st); break;
+      case 8: launch_beams_valu<8, 2>(*s, X_dev, nframes_dev, U, Tmax, NB, Y_dev, st); break;
+      default: launch_beams_valu<16, 1>(*s, X_dev, nframes_dev, U, Tmax, NB, Y_dev, st); break;
+      }
+    }
   });
 }
 

@@ -380,7 +380,7 @@ struct SphSrp {                      // the calls of a dsr_sph; the units are th
 
 struct DoaOp : SrpFace<BfOp, LinSrp> { void pack_frames() override { pack_half(); } };
 
-struct SphBfOp : BfOp {              // EigenBeamformer / SphericalDSBeamformer as a stream (modalBeamformer.cc:347-399)
+struct SphBfOp : BfOp {              // EigenBeamformer / SphericalDSBeamformer and the further kinds (:1490-1542, :1858-1906, :2174-2222) as a stream (modalBeamformer.cc:347-399)
   // the utterance is materialised at the first pull; a geometry, look-direction, sigma2 or gain change since (the handle's settings generation)
   // recomputes it at the next pull, the frame counter kept.  The eigenbeams (getSnapShotArray) are computed on the device only when asked for.
   dsr_sph* sph = nullptr; int dim = 0; DevBuf<float2> dF, dYs; unsigned setGen = ~0u; bool eigenDone = false;
@@ -394,7 +394,8 @@ struct SphBfOp : BfOp {              // EigenBeamformer / SphericalDSBeamformer 
   void compute() override {
     pack(); alloc(T); if (T <= 0) return;
     Y.reserve((size_t) T * F);
-    ok(dsr_sph_apply(sph, (const float*) X.p, nf.p, 1, T, (float*) Y.p, nullptr, S0));
+    if (dsr_sph_kind(sph) >= DSR_SPH_HWNC) ok(dsr_sph_beams(sph, (const float*) X.p, nf.p, 1, T, 1, (float*) Y.p, S0));   // the further kinds: one beam, the look direction
+    else ok(dsr_sph_apply(sph, (const float*) X.p, nf.p, 1, T, (float*) Y.p, nullptr, S0));
     op_expand_bins(Y.p, T, F, M, d<double2>(), S0);
   }
   bool settings_moved() const { return ready && setGen != dsr_sph_settings_generation(sph); }
@@ -1227,7 +1228,9 @@ dsr_status dsr_sph_bf_stream_create(dsr_sph* sph, const char* name, dsr_stream**
 {
   return guard([&] {
     if (!sph || !out) throw Error(DSR_E_PARAMETER, "null argument");
-    const char* dflt = dsr_sph_kind(sph) == DSR_SPH_DS ? "SphericalDSBeamformer" : "EigenBeamformer";
+    static const char* const NAMES[] = {"EigenBeamformer", "SphericalDSBeamformer", "SphericalHWNCBeamformer", "SphericalGSCBeamformer",
+                                        "SphericalHWNCGSCBeamformer", "SphericalSpatialDSBeamformer", "SphericalMOENBeamformer"};
+    const char* dflt = NAMES[dsr_sph_kind(sph)];
     SphBfOp* s = mk<SphBfOp>(name, dflt, dsr_sph_fft_len(sph), DSR_T_COMPLEX); s->w = nullptr; s->sph = sph; s->M = dsr_sph_fft_len(sph);
     s->checkOrder = false; *out = s;
   });

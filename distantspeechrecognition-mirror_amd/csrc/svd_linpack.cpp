@@ -169,8 +169,11 @@ int csvdc(cf* x, int ldx, int n, int p, cf* s, cf* e, cf* u, int ldu, cf* v, int
 
   // ---- QR iteration on the real bidiagonal (1-based l, m as in the Users' Guide; entries are s[l-1], e[l-1])
   const int mm = m; int iter = 0, info = 0;
+  // (passes: the deflation cases 1 and 2 do not count as iterations, and on an exactly rank-deficient matrix -- a rank-1 32 x 32 normal matrix
+  // -- they alternate for ever; every input that converges needs at most maxit QR steps and a few deflations per singular value)
+  const long maxPasses = 4L * maxit * (mm + 1) + 64; long passes = 0;
   while (m != 0) {
-    if (iter >= maxit) { info = m; break; }
+    if (iter >= maxit || ++passes > maxPasses) { info = m; break; }
     int l, kase;
     for (l = m - 1; l >= 1; l--) {
       const float test = std::abs(s[l - 1]) + std::abs(s[l]);

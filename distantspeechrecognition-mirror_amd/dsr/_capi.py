@@ -843,20 +843,75 @@ class DoaSRP:
 
 
 class _Sph:
-    """the dsr_sph handle (modalBeamformer.{h,cc}): kind "EB" (EigenBeamformer weights) or "DS" (SphericalDSBeamformer weights); settings,
-    geometry and tables on the host"""
-    KINDS = {"EB": 0, "DS": 1}
+    """the dsr_sph handle (modalBeamformer.{h,cc}): kind "EB" (EigenBeamformer weights), "DS" (SphericalDSBeamformer weights) or one of the
+    further beamformers "HWNC", "GSC", "HWNCGSC", "SPATIALDS", "MOEN"; settings, geometry and tables on the host"""
+    KINDS = {"EB": 0, "DS": 1, "HWNC": 2, "GSC": 3, "HWNCGSC": 4, "SPATIALDS": 5, "MOEN": 6}
 
     def __init__(self, kind, nBest, sampleRate, fftLen, chanN, maxOrder, normalizeWeight=False, halfBandShift=False, NC=1):
         L = load(); self.h = vp(); self.nBest, self.M, self.C = nBest, fftLen, chanN
         k = self.KINDS[kind] if isinstance(kind, str) else int(kind)
         check(L.dsr_sph_create(k, int(nBest), int(sampleRate), int(fftLen), int(bool(halfBandShift)), int(NC), int(maxOrder), int(bool(normalizeWeight)),
                                int(chanN), C.byref(self.h)))
-        self.dim = L.dsr_sph_dim(self.h)
+        self.dim = L.dsr_sph_dim(self.h); self.NC = int(NC)
 
     def __del__(self):
         if _lib is not None and getattr(self, "h", None):
             _lib.dsr_sph_destroy(self.h)
+
+    def setWNG(self, ratio):
+        check(_lib.dsr_sph_set_wng(self.h, float(ratio)))
+
+    def setActiveWeights_f(self, fbinX, packedWeight):
+        p = _np(packedWeight, np.float64).ravel()
+        check(_lib.dsr_sph_set_active_weights_f(self.h, int(fbinX), _ptr(p), p.size))
+
+    def setLevelOfDiagonalLoading(self, fbinX, diagonalWeight):
+        check(_lib.dsr_sph_set_diagonal_loading(self.h, int(fbinX), float(diagonalWeight)))
+
+    def fixTerms(self, flag):
+        check(_lib.dsr_sph_fix_terms(self.h, int(bool(flag))))
+
+    def wl(self):
+        return self._table(_lib.dsr_sph_wl, (self.M // 2 + 1, self.dim))
+
+    def blockingMatrix(self, fbinX):
+        return self._table(_lib.dsr_sph_blocking_matrix, (self.dim, self.dim - self.NC), int(fbinX))
+
+    def sensorWeights(self):
+        return self._table(_lib.dsr_sph_sensor_weights, (self.M // 2 + 1, self.C))
+
+    def setBeam(self, b, theta, phi):
+        check(_lib.dsr_sph_set_beam(self.h, int(b), float(theta), float(phi)))
+
+    def setBeamsFromNBest(self, doa, nbest_idx):
+        """beams 0..n-1 = the directions of doa's (a SphDoaSRP) units nbest_idx [n], e.g. one row of finalNBest's indices"""
+        idx = np.ascontiguousarray(nbest_idx, np.int32).ravel()
+        check(_lib.dsr_sph_set_beams_nbest(self.h, doa.h, _ptr(idx), idx.size)); return idx.size
+
+    def beamWeights(self, NB=1):
+        """V [NB][M/2+1][C]: the sensor-domain vectors of dsr_sph_beams, y = v^H x"""
+        n = max(1, min(int(NB), 16)); out = np.zeros((n, self.M // 2 + 1, self.C), np.complex128)
+        check(_lib.dsr_sph_beam_weights(self.h, int(NB), _ptr(out), out.size * 2)); return out
+
+    def beams(self, X, nframes=None, NB=1):
+        """X cuda complex64 [U][C][T][M/2+1] -> y [U][NB][T][M/2+1] complex64, every beam in one pass over X (dsr_sph_beams); rows past
+        nframes[u] are zero"""
+        import torch
+        U, Cn, T, F = X.shape
+        dev = X.device
+        if nframes is None:
+            nframes = torch.full((U,), T, dtype=torch.int32, device=dev)
+        y = torch.empty((U, max(int(NB), 0), T, F), dtype=torch.complex64, device=dev)
+        Xc = torch.view_as_real(X.contiguous())
+        check(_lib.dsr_sph_beams(self.h, _dev(Xc), _dev(nframes), U, T, int(NB), _dev(y), cur_stream()))
+        return y
+
+    def getBeamPattern(self, fbinX, theta=0.0, phi=0.0, minTheta=-np.pi, maxTheta=np.pi, minPhi=-np.pi, maxPhi=np.pi, widthTheta=0.1, widthPhi=0.1):
+        a, b = C.c_int(), C.c_int()
+        g = (float(minTheta), float(maxTheta), float(minPhi), float(maxPhi), float(widthTheta), float(widthPhi))
+        check(_lib.dsr_sph_beam_pattern_n(*g, C.byref(a), C.byref(b)))
+        out = np.zeros((max(a.value, 0), max(b.value, 0)), np.float64)
+        check(_lib.dsr_sph_beam_pattern(self.h, int(fbinX), float(theta), float(phi), *g, _ptr(out), out.size)); return out
 
     def _table(self, fn, shape, *args):
         out = np.zeros(shape, np.complex128); check(fn(self.h, *args, _ptr(out), out.size * 2)); return out
@@ -909,15 +964,23 @@ class _Sph:
 
 
 class SphBeamformer(_Sph):
-    """EigenBeamformer (kind "EB") / SphericalDSBeamformer (kind "DS") over a batch (dsr_sph_apply)"""
+    """EigenBeamformer (kind "EB") / SphericalDSBeamformer (kind "DS") over a batch (dsr_sph_apply); the further kinds ("HWNC", "GSC",
+    "HWNCGSC", "SPATIALDS", "MOEN") and several beams at once through beams() (dsr_sph_beams).  ratio: the HWNC kinds' setWNG."""
 
-    def __init__(self, kind, sampleRate, fftLen, chanN, maxOrder, normalizeWeight=False, halfBandShift=False, NC=1):
+    def __init__(self, kind, sampleRate, fftLen, chanN, maxOrder, normalizeWeight=False, halfBandShift=False, NC=1, ratio=None):
         _Sph.__init__(self, kind, 1, sampleRate, fftLen, chanN, maxOrder, normalizeWeight, halfBandShift, NC)
+        if ratio is not None:
+            self.setWNG(ratio)
 
 
 class SphDoaSRP(_Sph):
     """DOAEstimatorSRPEB (kind "EB") / DOAEstimatorSRPSphDSB (kind "DS") over a batch: the (theta, phi) grid and steering table on the host, the
     response powers of X [U][C][T][M/2+1] on the fp64 MFMA (dsr_sph_srp).  The accumulators belong to the caller."""
+
+    def __init__(self, kind, *args, **kw):
+        if (self.KINDS.get(kind, -1) if isinstance(kind, str) else int(kind)) not in (0, 1):
+            raise DsrError(1, "SphDoaSRP searches with the EB or DS weights; kind %r has no steering table" % (kind,))
+        _Sph.__init__(self, kind, *args, **kw)
 
     def setSearchParam(self, minTheta=0.0, maxTheta=np.pi, minPhi=-np.pi, maxPhi=np.pi, widthTheta=0.1, widthPhi=0.1):
         check(_lib.dsr_sph_set_search_param(self.h, float(minTheta), float(maxTheta), float(minPhi), float(maxPhi), float(widthTheta), float(widthPhi)))

@@ -360,6 +360,14 @@ class _Spherical(FeatureStreamPtr):
     def getModeAmplitudes(self):
         return self._query().modeAmplitudes()
 
+    def getBeamPattern(self, fbinX, theta=0.0, phi=0.0, minTheta=-np.pi, maxTheta=np.pi, minPhi=-np.pi, maxPhi=np.pi, widthTheta=0.1, widthPhi=0.1):
+        """beamformer.i:434-436, :756-758: [nTheta][nPhi]; it sets the look direction to (theta, phi) as the reference does"""
+        q = self._query()
+        self._lookSet = True                                                                # (the GSC classes' setActiveWeights_f asks for it)
+        if self._sph is None:
+            self._set.append(("setLookDirection", (float(theta), float(phi))))
+        return q.getBeamPattern(fbinX, theta, phi, minTheta, maxTheta, minPhi, maxPhi, widthTheta, widthPhi)
+
     def getArrayGeometry(self, type):
         return self._query().getArrayGeometry(type)
 
@@ -394,6 +402,85 @@ class SphericalDSBeamformerPtr(_Spherical):
     _KIND = "DS"
 
     def __init__(self, sampleRate, fftLen=512, halfBandShift=False, NC=1, maxOrder=3, normalizeWeight=False, nm="SphericalDSBeamformer"):
+        _Spherical.__init__(self, 1, sampleRate, fftLen, halfBandShift, NC, maxOrder, normalizeWeight, nm)
+
+    def calcWNG(self):
+        return self._query().calcWNG()
+
+
+class SphericalHWNCBeamformerPtr(_Spherical):
+    """beamformer.i:648-660 (SphericalHWNCBeamformer, modalBeamformer.cc:1387-1478): HMDI weights held to a white noise gain"""
+    _KIND = "HWNC"
+
+    def __init__(self, sampleRate, fftLen=512, halfBandShift=False, NC=1, maxOrder=3, normalizeWeight=False, ratio=0.1, nm="SphericalHWNCBeamformer"):
+        _Spherical.__init__(self, 1, sampleRate, fftLen, halfBandShift, NC, maxOrder, normalizeWeight, nm)
+        self._apply("setWNG", ratio)
+
+    def setWNG(self, ratio):
+        self._apply("setWNG", ratio)
+
+    def calcWNG(self):
+        return self._query().calcWNG()
+
+
+class _SphericalGSC(_Spherical):
+    def setLookDirection(self, theta, phi):
+        self._lookSet = True; _Spherical.setLookDirection(self, theta, phi)
+
+    def setActiveWeights_f(self, fbinX, packedWeight):
+        if self._sph is None and not getattr(self, "_lookSet", False):
+            raise K.DsrError(1, "call setLookDirection() once")                             # modalBeamformer.cc:1588-1591
+        self._apply("setActiveWeights_f", int(fbinX), np.array(packedWeight, np.float64))
+
+
+class SphericalGSCBeamformerPtr(_SphericalGSC):
+    """beamformer.i:677-689 (SphericalGSCBeamformer, modalBeamformer.cc:1483-1594): the modal GSC, active weights set from outside"""
+    _KIND = "GSC"
+
+    def __init__(self, sampleRate, fftLen=512, halfBandShift=False, NC=1, maxOrder=4, normalizeWeight=False, nm="SphericalGSCBeamformer"):
+        _Spherical.__init__(self, 1, sampleRate, fftLen, halfBandShift, NC, maxOrder, normalizeWeight, nm)
+
+    def calcWNG(self):
+        return self._query().calcWNG()
+
+
+class SphericalHWNCGSCBeamformerPtr(_SphericalGSC):
+    """beamformer.i:706-718 (SphericalHWNCGSCBeamformer, modalBeamformer.cc:1599-1713): the GSC over the HWNC quiescent weights"""
+    _KIND = "HWNCGSC"
+
+    def __init__(self, sampleRate, fftLen=512, halfBandShift=False, NC=1, maxOrder=4, normalizeWeight=False, ratio=1.0, nm="SphericalHWNCGSCBeamformer"):
+        _Spherical.__init__(self, 1, sampleRate, fftLen, halfBandShift, NC, maxOrder, normalizeWeight, nm)
+        self._apply("setWNG", ratio)
+
+    def setWNG(self, ratio):
+        self._apply("setWNG", ratio)
+
+    def calcWNG(self):
+        return self._query().calcWNG()
+
+
+class SphericalMOENBeamformerPtr(_Spherical):
+    """beamformer.i:761-773 (SphericalMOENBeamformer, modalBeamformer.cc:1804-2099): the Li / Duraiswami optimal design in the sensor domain"""
+    _KIND = "MOEN"
+
+    def __init__(self, sampleRate, fftLen=512, halfBandShift=False, NC=1, maxOrder=4, normalizeWeight=False, nm="SphericalMOENBeamformer"):
+        _Spherical.__init__(self, 1, sampleRate, fftLen, halfBandShift, NC, maxOrder, normalizeWeight, nm)
+
+    def setLevelOfDiagonalLoading(self, fbinX, diagonalWeight):
+        self._apply("setLevelOfDiagonalLoading", int(fbinX), float(diagonalWeight))
+
+    def fixTerms(self, flag):
+        self._apply("fixTerms", bool(flag))
+
+    def calcWNG(self):
+        return self._query().calcWNG()
+
+
+class SphericalSpatialDSBeamformerPtr(_Spherical):
+    """beamformer.i:994-1006 (SphericalSpatialDSBeamformer, modalBeamformer.cc:2106-2270): delay-and-sum in the sensor domain"""
+    _KIND = "SPATIALDS"
+
+    def __init__(self, sampleRate, fftLen=512, halfBandShift=False, NC=1, maxOrder=3, normalizeWeight=False, nm="SphericalSpatialDSBeamformer"):
         _Spherical.__init__(self, 1, sampleRate, fftLen, halfBandShift, NC, maxOrder, normalizeWeight, nm)
 
     def calcWNG(self):

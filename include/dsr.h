@@ -148,7 +148,9 @@ dsr_status dsr_bf_set_noise_matrix(dsr_bf*, int fbinX, const double* Rnn /*[C][C
 dsr_status dsr_bf_calc_mvdr_weights(dsr_bf*, double sampleRate, double dThreshold);
 /* pseudoinverse(A, invA, dThreshold) (beamformer.cc:253-305): LINPACK csvdc (btk/matrix/linpack_c.cc:9518, job 11) in complex<float>,
    V diag(1/s) U^H with singular values below dThreshold dropped.  A [rows][cols] complex128 row major (host) -> invA [cols][rows];
-   *ok = the reference's return value (0: a singular value was dropped or csvdc did not converge); svals (optional) min(rows, cols) floats. */
+   *ok = the reference's return value (0: a singular value was dropped or csvdc did not converge); svals (optional) min(rows, cols) floats.
+   On some exactly rank-deficient matrices (c ones(32, 32)) the reference's csvdc never returns: its deflation cases alternate and maxit counts QR
+   steps only.  Here csvdc also ends after 4 maxit (n + 1) + 64 passes of any case: *ok = 0 and invA is NaN then. */
 dsr_status dsr_pseudoinverse(const double* A, int rows, int cols, float dThreshold, double* invA, int* ok, float* svals);
 /* SubbandGSC: calcGSCWeights (blocking matrices), setActiveWeights_f, zeroActiveWeights
    (beamformer.cc:1373-1447, 761-799, 398-479) */
@@ -265,8 +267,15 @@ dsr_status dsr_doa_final_nbest(dsr_doa*, const double* acc, int U, double* nbest
 typedef struct dsr_sph dsr_sph;
 #define DSR_SPH_EB 0
 #define DSR_SPH_DS 1
+/* the further beamformers of the family (modalBeamformer.cc:1387-2270), section 2c': their output is dsr_sph_beams */
+#define DSR_SPH_HWNC 2
+#define DSR_SPH_GSC 3
+#define DSR_SPH_HWNCGSC 4
+#define DSR_SPH_SPATIALDS 5
+#define DSR_SPH_MOEN 6
 /* EigenBeamformer / DOAEstimatorSRPEB (kind EB) or SphericalDSBeamformer / DOAEstimatorSRPSphDSB (kind DS) (modalBeamformer.cc:219-246,
-   :769-777, :990-995, :1177-1182) over chanN channels (<= 128); NC is accepted and ignored (the reference only passes it on) */
+   :769-777, :990-995, :1177-1182) over chanN channels (<= 128); NC is beamformerWeights' number of constraints: the GSC kinds' blocking
+   matrix has dim - NC columns (1 <= NC < dim, checked when the weights are first needed), the other kinds only pass it on */
 dsr_status dsr_sph_create(int kind, int nBest, int sampleRate, int fftLen, int halfBandShift, int NC, int maxOrder, int normalizeWeight, int chanN, dsr_sph** out);
 void       dsr_sph_destroy(dsr_sph*);
 int        dsr_sph_kind(const dsr_sph*);
@@ -279,8 +288,9 @@ int        dsr_sph_max_order(const dsr_sph*);
 /* how many times the steering table was built (each build zeroes the reference's accumulators, :818-820); has_table: 1 while one is built */
 unsigned   dsr_sph_table_generation(const dsr_sph*);
 int        dsr_sph_has_table(const dsr_sph*);
-/* bumped by every set_array_geometry / set_eigenmike_geometry / set_look_direction / set_sigma2 / set_weight_gain: the stream operators
-   recompute the rest of the utterance when it moves */
+/* bumped by every set_array_geometry / set_eigenmike_geometry / set_look_direction / set_sigma2 / set_weight_gain and by the setters of
+   section 2c' (set_wng, set_active_weights_f, set_diagonal_loading, fix_terms, set_beam(0, ..), beam_pattern): the stream operators recompute
+   the rest of the utterance when it moves */
 unsigned   dsr_sph_settings_generation(const dsr_sph*);
 /* setArrayGeometry(a, theta_s, phi_s) (:538-564): radius a in mm (SSPEED 343740 mm/s, beamformer.h:47), n = chanN sensor angles; computes the
    harmonics at the sensors (:566-601); the steering table is not rebuilt */
@@ -300,7 +310,7 @@ dsr_status dsr_sph_mode_amplitudes(dsr_sph*, double* out, size_t outDoubles);
 dsr_status dsr_sph_harmonics(dsr_sph*, double* out, size_t outDoubles);
 /* the look direction's weights (_calcSteeringUnit :716-746): out [fftLen/2+1][dim] complex128, bin 0 the DC weights (calcDCWeights :219-233) */
 dsr_status dsr_sph_look_weights(dsr_sph*, double* out, size_t outDoubles);
-/* SphericalDSBeamformer::calcWNG (:997-1020): out [fftLen/2+1] (either kind) */
+/* SphericalDSBeamformer::calcWNG (:997-1020): out [fftLen/2+1]; the HWNC kinds: SphericalHWNCBeamformer::calcWNG (:1397-1418) with the ratio */
 dsr_status dsr_sph_calc_wng(dsr_sph*, double* out, int n);
 /* setSearchParam(minTheta, maxTheta, minPhi, maxPhi, widthTheta, widthPhi) (modalBeamformer.h:197-205): no swap; clears the table */
 dsr_status dsr_sph_set_search_param(dsr_sph*, double minTheta, double maxTheta, double minPhi, double maxPhi, double widthTheta, double widthPhi);
@@ -314,7 +324,9 @@ float      dsr_sph_energy_threshold(const dsr_sph*);
    accumulated by repeated addition (:829-832) -> theta [units], phi [units] */
 dsr_status dsr_sph_grid_n(dsr_sph*, int* nTheta, int* nPhi);
 dsr_status dsr_sph_grid(dsr_sph*, double* theta, double* phi, int n);
-/* build the steering table now (the SRP call and dsr_sph_steering build it when needed) */
+/* build the steering table now (the SRP call and dsr_sph_steering build it when needed).  Only DSR_SPH_EB and DSR_SPH_DS have one, as the
+   reference's DOAEstimatorSRPEB and DOAEstimatorSRPSphDSB: for the further kinds this, dsr_sph_steering, dsr_sph_srp_path and dsr_sph_srp are
+   DSR_E_ERROR (-1 from dsr_sph_srp_path) */
 dsr_status dsr_sph_build_table(dsr_sph*);
 /* steering weights of one unit: out [fftLen/2+1][dim] complex128 = _calcWeights for the table's bins, (1, 0) at bin 0 unless the table was built
    with fbinMin = 0, zero elsewhere (:833-841) */
@@ -334,6 +346,60 @@ dsr_status dsr_sph_srp(dsr_sph*, const float* X_dev, const int32_t* nframes_dev,
                        double* nbest_rp_dev, int32_t* nbest_idx_dev, double* acc_dev, float* Y_dev, int32_t* gated_dev, void* stream);
 /* getFinalNBestHypotheses (beamformer.cc:2986-3025) for U utterances: acc [U][units] host -> nbest_rp [U][nBest], nbest_idx [U][nBest] host */
 dsr_status dsr_sph_final_nbest(dsr_sph*, const double* acc, int U, double* nbest_rp, int32_t* nbest_idx);
+
+/* -------------------------------------------------------------------------------------
+ * 2c'. The further spherical-array beamformers and the multi-beam apply
+ *     replaces SphericalHWNCBeamformer, SphericalGSCBeamformer, SphericalHWNCGSCBeamformer, SphericalMOENBeamformer,
+ *     SphericalSpatialDSBeamformer (modalBeamformer.h:324-500, beamformer.i:648-770, :994-1010, modalBeamformer.cc:1387-2270) and
+ *     getBeamPattern (:756-787, :2068-2099)
+ * Kinds of dsr_sph_create.  HWNC: the HMDI weights scaled to a white noise gain (ratio > 0: norm 2 sqrt(pi / (chanN wng)), passed through a
+ * float as normalizeWeights takes it; ratio <= 0: times 16 pi^2 / (chanN maxOrder^2)); normalizeWeight is not applied.  GSC / HWNCGSC: the DS /
+ * HWNC weights as the quiescent vector wq, a blocking matrix per bin 1..fftLen/2, wl = B wa from outside; the output is wq^H F at bin 0 and
+ * calcOutputOfGSC (beamformer.cc:1251-1287) above: (wq - wl), with normalizeWeight divided by ||wq - wl|| dim.  A new look direction rebuilds
+ * B and keeps wl as last set, as the reference.  B is _calcBlockingMatrix (beamformer.cc:398-479) of conj(wq), each column then projected
+ * against wq: B^H wq = 0 (the reference passes wq itself to a routine that blocks the conjugate of its argument, so its B does not block wq).
+ * SPATIALDS: sensor-domain weights of length chanN for bins 0..fftLen/2 (no DC special case, no normalizeWeight).  MOEN: sensor-domain weights CN (A^H A + l I)^+ A^H BN through the single-precision LINPACK pseudo-inverse (threshold
+ * 1e-8), CN = 2 / maxOrder^2; bin 0 is (1, 0, 0, ...); after fix_terms(1) every weight is 0 (NaN with normalizeWeight), as the reference, which
+ * zeroes _fixedW before it uses it (:1993-1996, :2031-2034).  Settings take effect at once (the reference: at the next setLookDirection) and
+ * bump the settings generation.  Deviations: set_active_weights_f before any set_look_direction is DSR_E_ERROR, a packed length other than
+ * 2 (dim - NC) or fbinX > fftLen/2 DSR_E_DIMENSION; a setter called on a kind that lacks it is DSR_E_ERROR.
+ * ------------------------------------------------------------------------------------- */
+/* setWNG(ratio) (modalBeamformer.h:329); a new handle has ratio 1 */
+dsr_status dsr_sph_set_wng(dsr_sph*, float ratio);
+/* setActiveWeights_f(fbinX, packedWeight) (:1586-1594, :1702-1710): packed [2 (dim - NC)] (re, im) pairs -> wl[fbinX] = B[fbinX] wa */
+dsr_status dsr_sph_set_active_weights_f(dsr_sph*, unsigned fbinX, const double* packed, size_t n);
+/* setLevelOfDiagonalLoading(fbinX, diagonalWeight) (:1923-1930), fixTerms(flag) (modalBeamformer.h:443) */
+dsr_status dsr_sph_set_diagonal_loading(dsr_sph*, unsigned fbinX, float diagonalWeight);
+dsr_status dsr_sph_fix_terms(dsr_sph*, int flag);
+/* the GSC kinds' wl: out [fftLen/2+1][dim] complex128; the blocking matrix of one bin: out [dim][dim - NC] complex128 (bin 0: zeros) */
+dsr_status dsr_sph_wl(dsr_sph*, double* out, size_t outDoubles);
+dsr_status dsr_sph_blocking_matrix(dsr_sph*, unsigned fbinX, double* out, size_t outDoubles);
+/* the look direction's weights of the sensor-domain kinds (SPATIALDS, MOEN): out [fftLen/2+1][chanN] complex128 (dsr_sph_look_weights is
+   DSR_E_ERROR for them, this call for the modal kinds) */
+dsr_status dsr_sph_sensor_weights(dsr_sph*, double* out, size_t outDoubles);
+/* beam b (0 <= b < 16) points at (theta, phi); beam 0 is the look direction (set_beam(0, ..) = set_look_direction).  The GSC kinds' active weights
+   apply to beam 0 only. */
+dsr_status dsr_sph_set_beam(dsr_sph*, int b, double theta, double phi);
+/* beams 0..n-1 from a DOA handle's N-best: nbest_idx [n] unit indices of doa's steering table (dsr_sph_srp, dsr_sph_final_nbest); an empty
+   rank (-1) is DSR_E_INDEX */
+dsr_status dsr_sph_set_beams_nbest(dsr_sph*, dsr_sph* doa, const int32_t* nbest_idx, int n);
+/* the sensor-domain vectors the device applies: out [NB][fftLen/2+1][chanN] complex128, y = v^H x.  Modal kinds: v = S^H w_eff folded in fp64
+   (w_eff the look weights, for the GSC kinds calcOutputOfGSC's); sensor-domain kinds: the weights.  1 <= NB <= 16, else DSR_E_DIMENSION; a beam
+   below NB without a direction is DSR_E_ERROR.  Host only. */
+dsr_status dsr_sph_beam_weights(dsr_sph*, int NB, double* out, size_t outDoubles);
+/* the multi-beam apply, any kind: X_dev [U][chanN][Tmax][fftLen/2+1] complex64, nframes_dev [U] -> Y_dev [U][NB][Tmax][fftLen/2+1] complex64,
+   Y[u][b][t][f] = v_{b,f}^H X[u][:,t,f] in one pass over X; rows t >= nframes[u] are written as zeros.  NB <= 4 runs on the VALU, above that on
+   v_mfma_f64_16x16x4_f64 (dsr_sph_beams_path: 0 / 1; DSR_SPH_BEAMS_PATH=valu|mfma forces one, -1 for another value); a call whose VALU table
+   does not fit the kernel's LDS (beams x (fftLen/2+1) > 3072) runs on the MFMA kernel too. */
+dsr_status dsr_sph_beams(dsr_sph*, const float* X_dev, const int32_t* nframes_dev, int U, int Tmax, int NB, float* Y_dev, void* stream);
+int        dsr_sph_beams_path(int NB);
+/* getBeamPattern(fbinX, theta, phi, minTheta, maxTheta, minPhi, maxPhi, widthTheta, widthPhi): the grid is (int)(float)((max - min) / width +
+   1.5) a side, theta and phi accumulated by addition; out [nTheta][nPhi] = |wq^H SHT(p)| of a unit plane wave p on the sphere (modal kinds,
+   :756-787), |sum w p| unconjugated (MOEN, :2068-2099), |w^H p| (SPATIALDS: the inherited code dots a chanN-long with a dim-long vector).  It
+   sets the look direction to (theta, phi), as the reference.  Host only. */
+dsr_status dsr_sph_beam_pattern_n(double minTheta, double maxTheta, double minPhi, double maxPhi, double widthTheta, double widthPhi, int* nTheta, int* nPhi);
+dsr_status dsr_sph_beam_pattern(dsr_sph*, unsigned fbinX, double theta, double phi, double minTheta, double maxTheta, double minPhi, double maxPhi,
+                                double widthTheta, double widthPhi, double* out, size_t outDoubles);
 
 /* =====================================================================================
  * 2d. Subband acoustic echo (voice prompt) cancellation

@@ -30,6 +30,17 @@ struct GmmModel {
   PerStream<GmmTieScratch> tie;
 };
 
+// The trust radius of the expanded form as a multiple of S = 2 ivMax |x|^2 + termMax (k_gmm_mfma.hip header): two computed distances further apart
+// than twice the rounding bound (2 dimN + 3) 2^-24 S, plus what the search itself may move a compared value by, keep the order of the exact ones.
+// tagValues: how many index values the search writes into the low mantissa bits of the values it compares (0: none).  Such a value is off its
+// distance by less than tagValues ulp <= tagValues 2^-23 |d| <= tagValues 2^-23 S; twice that is budgeted (the roundings of the test itself).
+// `tuned` is the literal the kernels were measured with: the radius never falls below it, so shapes it covers keep their scores bit for bit.
+inline float gmm_trust_radius(int D, float tuned, int tagValues)
+{
+  const float r = (float) (2.0 * (2 * D + 3) * 0x1p-24 + tagValues * 0x1p-22);
+  return r > tuned ? r : tuned;
+}
+
 // k_gmm_sp.hip: the software-pipelined MFMA shape for codebooks of four Gaussians
 int gmm_sp_frames();
 size_t gmm_sp_lds(const GmmModel& m);

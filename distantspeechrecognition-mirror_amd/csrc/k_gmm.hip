@@ -11,9 +11,10 @@
 //           of non-negative terms are monotone, so it cannot change the strict-'<' argmin.
 //   mode 1  k_gmm_all   : fp64 per-Gaussian distances + log-sum with the -100 exponent floor.
 //   mode 2  k_gmm_mfma  : frame x Gaussian contraction on v_mfma_f32_32x32x2_f32 in the expanded
-//           form  sum_d iv x^2 - 2 mu iv x + (mu^2 iv) ; the per-codebook candidates that could still be
-//           the fp32-ordered minimum (rigorous rounding bound) are re-scored in reference order, so
-//           the output bits equal mode 0.
+//           form  sum_d iv x^2 - 2 mu iv x + (mu^2 iv) ; every (frame, codebook) whose two best candidates
+//           lie inside the trust radius of that form is re-scored in reference order, so the argmin is
+//           mode 0's on every frame; a re-scored entry carries mode 0's score bits, every other score
+//           lies within the rounding bound of mode 0's (k_gmm_mfma.hip header) -- NOT bit-identical.
 // This translation unit is compiled with -ffp-contract=off.
 #include "common.h"
 #include "gmm_model.h"

@@ -12,10 +12,15 @@
 // Numerics: fp32 fmaf chain in k order (exact-f32 MFMA).  The expanded form is off the reference's (mu-x)^2*iv accumulation by at most
 // (n + 2) 2^-24 S per distance, n = 2 dimN + 1 terms, S = sum of the terms' magnitudes <= 2 ivMax |x|^2 + termMax (gmm_model.h: model-wide
 // maxima, |x|^2 per frame) -- the bound grows with the CANCELLED terms, not with the distance (means far from zero: S >> distance).  Every
-// (frame, codebook) whose two best candidates lie within 1e-5 S (>= twice that bound) of each other, or whose bound is no longer small against
-// the distance itself (1e-5 S > 1e-3 |d|), is re-scored in the reference's own arithmetic over ALL Gaussians of the codebook (k_gmm_ties):
-// argmin = mode 0's on every frame; re-scored entries carry mode 0's score bits, the others agree with mode 0 to rel 2e-6 on
-// well-conditioned models (asserted in tests/test_gpu_parity.py) and to 1e-3 by construction.  Mode 0 stays the bit-exact path.
+// (frame, codebook) whose two best candidates lie within r S of each other, or whose bound is no longer small against the distance itself
+// (r0 S > 1e-3 |d|), is re-scored in the reference's own arithmetic over ALL Gaussians of the codebook (k_gmm_ties).  The trust radius r is
+// computed on the host from the model (gmm_trust_radius, gmm_model.h) and handed to the kernels: r = max(1e-5, 2 (2 dimN + 3) 2^-24 + tag),
+// twice the bound plus what the search itself moves a compared value by relative to S (tag = 0 here: k_gmm_mfma and k_gmm_mfma_reg compare
+// the distances as they are; k_gmm_sp.hip compares values that carry an index in their low mantissa bits); r0 is the same without the tag.
+// Up to dimN = 40 that is the 1e-5 these kernels were tuned with, from dimN = 41 on it grows with the depth (1.56e-5 at dimN = 64).
+// Argmin = mode 0's on every frame; re-scored entries carry mode 0's score bits, the others lie within (2 dimN + 3) 2^-24 S of mode 0's distance
+// (half of that, times the codebook scale, in the score; tests/test_gpu_gmm_shapes.py asserts both at every instantiated depth), i.e. rel 2e-6 on
+// well-conditioned models (tests/test_gpu_parity.py) and 1e-3 by construction.  Mode 0 stays the bit-exact path.
 #include "common.h"
 #include "gmm_model.h"
 #include <algorithm>
@@ -62,7 +67,7 @@ __global__ __launch_bounds__(256) void k_gmm_mfma(const float* __restrict__ x, l
                                                   const int* __restrict__ off, const float* __restrict__ Apack,
                                                   const float* __restrict__ mean, const float* __restrict__ ivar, const float* __restrict__ cst,
                                                   const float* __restrict__ val, const float* __restrict__ scale,
-                                                  float* __restrict__ score, unsigned char* __restrict__ argmin, float ivMax2, float termMax)
+                                                  float* __restrict__ score, unsigned char* __restrict__ argmin, float ivMax2, float termMax, float rad)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* Abuf = reinterpret_cast<float*>(smem);                 // [2][S2][64] double buffered
@@ -90,9 +95,9 @@ __global__ __launch_bounds__(256) void k_gmm_mfma(const float* __restrict__ x, l
       b[t][s] = v;
     }
   }
-  // |x|^2 of the scanning thread's own frame -> 1e-5 S, the trust radius of the expanded form (header)
+  // |x|^2 of the scanning thread's own frame -> rad S, the trust radius of the expanded form (header)
   float thrS;
-  { float xx = 0.0f; const long nq = n0 + tid; if (nq < N) for (int d = 0; d < D; d++) { const float q = x[nq * D + d]; xx += q * q; } thrS = 1e-5f * (ivMax2 * xx + termMax); }
+  { float xx = 0.0f; const long nq = n0 + tid; if (nq < N) for (int d = 0; d < D; d++) { const float q = x[nq * D + d]; xx += q * q; } thrS = rad * (ivMax2 * xx + termMax); }
   // scan state: thread tid walks the Gaussians of frame n0+tid in order (all threads in lockstep)
   int curK = 0, cbStart = 0, curEnd = __builtin_amdgcn_readfirstlane(off[1]); float m1 = 1E20f, m2 = 1E20f; int a1 = 0, a2 = 0; int kFlush0 = 0;
   const long nme = n0 + tid;
@@ -253,7 +258,7 @@ __global__ __launch_bounds__(256, 2) void k_gmm_mfma_reg(const float* __restrict
                                                       const float* __restrict__ cst, const float* __restrict__ val, const float* __restrict__ scale, int unitScale,
                                                       float* __restrict__ score, unsigned char* __restrict__ argmin,
                                                       unsigned long long* __restrict__ tieList, unsigned* __restrict__ tieCount, unsigned tieCap, int valInLds, int dbg,
-                                                      float ivMax2, float termMax)
+                                                      float ivMax2, float termMax, float rad)
 {
   constexpr int S2 = 4 * S4;
   constexpr int CPC = 32 / R;                                    // codebooks per 32-row chunk
@@ -288,7 +293,7 @@ __global__ __launch_bounds__(256, 2) void k_gmm_mfma_reg(const float* __restrict
       b[t][s] = v;
     }
   }
-  // 1e-5 S per frame of the two tiles (header): |x|^2 is the sum of the operand's squared half, the lane's steps + its partner's
+  // rad S per frame of the two tiles (header): |x|^2 is the sum of the operand's squared half, the lane's steps + its partner's
   float thrS[2];
 #pragma unroll
   for (int t = 0; t < 2; t++) {
@@ -296,7 +301,7 @@ __global__ __launch_bounds__(256, 2) void k_gmm_mfma_reg(const float* __restrict
 #pragma unroll
     for (int s = 0; s < S2; s++) if (2 * s + kh < D) xx += b[t][s];
     xx += __shfl_xor(xx, 32, 64);
-    thrS[t] = 1e-5f * (ivMax2 * xx + termMax);
+    thrS[t] = rad * (ivMax2 * xx + termMax);
   }
   const float4* Ap4 = reinterpret_cast<const float4*>(Apack) + lane;
   int kFlush0 = 0;                                               // first codebook of the strip
@@ -453,6 +458,7 @@ void gmm_score_mfma(GmmModel& m, const float* x, long N, float* score, unsigned 
 {
   gmm_prepare_mfma(m);
   const int S2 = m.KP / 2;
+  const float rad = gmm_trust_radius(m.D, 1e-5f, 0);               // (both kernels of this file compare untagged distances)
   // codebooks of one size R in {4, 8, 16, 32}: the candidate search stays in the accumulator registers
   int R = m.refN.empty() ? 0 : m.refN[0];
   for (int k = 1; k < m.K; k++) if (m.refN[k] != R) R = 0;
@@ -477,7 +483,7 @@ void gmm_score_mfma(GmmModel& m, const float* x, long N, float* score, unsigned 
     const int dbg = getenv("DSR_GMM_DBG") ? atoi(getenv("DSR_GMM_DBG")) : 0;
 #define LR(SS, RR) { DSR_HIP(hipFuncSetAttribute((const void*) k_gmm_mfma_reg<SS, RR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsR)); \
   hipLaunchKernelGGL((k_gmm_mfma_reg<SS, RR>), gridR, dim3(256), ldsR, st, x, N, m.D, m.Dp, m.K, m.G, m.GT, m.d_bn.p, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, m.d_scale.p, unitScale, \
-                     score, argmin, tieList.p, tieCount.p, cap, valInLds, dbg, 2.0f * m.ivMax, m.termMax); }
+                     score, argmin, tieList.p, tieCount.p, cap, valInLds, dbg, 2.0f * m.ivMax, m.termMax, rad); }
 #define LRS(RR) switch (S4) { case 4: LR(4, RR) break; case 5: LR(5, RR) break; case 9: LR(9, RR) break; case 10: LR(10, RR) break; case 12: LR(12, RR) break; default: LR(17, RR) break; }
     if (sp && gmm_sp_launch(m, R, x, N, score, argmin, ts.masks, tieList.p, tieCount.p, cap, st)) { }
     else if (R == 4) LRS(4) else if (R == 8) LRS(8) else if (R == 16) LRS(16) else LRS(32)
@@ -496,7 +502,7 @@ void gmm_score_mfma(GmmModel& m, const float* x, long N, float* score, unsigned 
   const size_t lds = sizeof(float) * ((size_t) 2 * S2 * 64 + (size_t) FT * TS + (size_t) FT * SC) + (size_t) FT * SC;
   dim3 grid(cdiv(N, FT));
 #define LAUNCH(SS) { DSR_HIP(hipFuncSetAttribute((const void*) k_gmm_mfma<SS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); \
-  hipLaunchKernelGGL(k_gmm_mfma<SS>, grid, dim3(256), lds, st, x, N, m.D, m.Dp, m.K, m.G, m.GT, m.d_off.p, m.d_A.p, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, m.d_scale.p, score, argmin, 2.0f * m.ivMax, m.termMax); }
+  hipLaunchKernelGGL(k_gmm_mfma<SS>, grid, dim3(256), lds, st, x, N, m.D, m.Dp, m.K, m.G, m.GT, m.d_off.p, m.d_A.p, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, m.d_scale.p, score, argmin, 2.0f * m.ivMax, m.termMax, rad); }
   switch (S2) {
     case 16: LAUNCH(16) break; case 20: LAUNCH(20) break; case 36: LAUNCH(36) break;
     case 40: LAUNCH(40) break; case 48: LAUNCH(48) break; default: LAUNCH(68) break;

@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256, 1) void k_gmm_mfma_sp(const float* __restrict_
                                                         const float* __restrict__ Apack, const float* __restrict__ mean, const float* __restrict__ ivar,
                                                         const float* __restrict__ cst, const float* __restrict__ val,
                                                         float* __restrict__ score, unsigned char* __restrict__ argmin,
-                                                        unsigned* __restrict__ tieMasks, float ivMax2, float termMax, int getPhase)
+                                                        unsigned* __restrict__ tieMasks, float ivMax2, float termMax, float rad, float radK, int getPhase)
 {
   constexpr int S2 = 4 * S4;                                     // MFMA groups per chunk (one group: the NT tiles' MFMAs of one contraction step)
   constexpr int FTW = 32 * NT, SCP = 36, ACP = 36;               // frames of a wave; pitch of a strip row (32 staged codebooks, rows 16-byte aligned), of an argmin row (bytes)
@@ -101,10 +101,13 @@ __global__ __launch_bounds__(256, 1) void k_gmm_mfma_sp(const float* __restrict_
   for (int k = 0; k < NSRCH; k++) if (n0 + 32 * (k % NT) + col < N && (R == 4 || kh == 0)) liveBits |= 1u << k;
   // which half of a lane pair the first result of a swap shows (R >= 8)
   unsigned khA = 0u; if constexpr (R != 4) khA = __builtin_amdgcn_permlane32_swap((unsigned) kh, (unsigned) kh, false, false)[0];
-  // The trust radius per frame: 1.1e-5 S, S = 2 ivMax |x|^2 + termMax (k_gmm_mfma.hip header: each distance is off by at most (n + 2) 2^-24 S =
-  // 4.83e-6 S, n = 81 terms; the index in the low bits moves a compared value by < 2^-22 |d| <= 2.4e-7 S; two distances further apart than twice
-  // the sum keep their order).  Nothing else is added to it: k_gmm_mfma_reg's extra 1e-4 (|d| + 1) predates the bound and only lengthens the list
-  // (1.0 M entries of 1.03e9 at the pipe's shape with it, 0.4 M without).  thrK: a thousand times the radius ("the bound is no longer small against d").
+  // The trust radius per frame: rad S, S = 2 ivMax |x|^2 + termMax (k_gmm_mfma.hip header: each distance is off by at most (2 dimN + 3) 2^-24 S;
+  // the index in the low bits moves a compared value by less than 4 (R = 4) or R/2 ulp of d, and |d| <= S; two distances further apart than
+  // twice the bound plus that keep their order).  gmm_sp_launch computes rad = max(1.1e-5, 2 (2 dimN + 3) 2^-24 + tag) -- the 1.1e-5 this kernel
+  // was tuned with up to dimN = 40 at R = 4 and 8; more from dimN = 41 on and, at R = 16 / 32 (eight / sixteen index values), from dimN = 37 / 29 on.
+  // Nothing else is added to it: k_gmm_mfma_reg's extra 1e-4 (|d| + 1) predates the bound and only lengthens the list
+  // (1.0 M entries of 1.03e9 at the pipe's shape with it, 0.4 M without).  thrK = radK S, radK a thousand times the untagged radius
+  // max(1e-5, 2 (2 dimN + 3) 2^-24) ("the bound is no longer small against d").
   float thrS[NT], thrK[NT];
 #pragma unroll
   for (int t = 0; t < NT; t++) {
@@ -112,7 +115,7 @@ __global__ __launch_bounds__(256, 1) void k_gmm_mfma_sp(const float* __restrict_
 #pragma unroll
     for (int s = 0; s < S2; s++) if (2 * s + kh < D) xx += b[t][s];
     xx += __shfl_xor(xx, 32, 64);
-    thrS[t] = 1.1e-5f * (ivMax2 * xx + termMax); thrK[t] = 1000.0f * (1e-5f * (ivMax2 * xx + termMax));
+    thrS[t] = rad * (ivMax2 * xx + termMax); thrK[t] = 1000.0f * (radK * (ivMax2 * xx + termMax));
   }
   // the wave's rows of the two outputs as buffers: what lies beyond its live frames (or beyond K: offset INV) is dropped by the range check
   const long nfr = N - n0; const int frames = nfr <= 0 ? 0 : (nfr < FTW ? (int) nfr : FTW);
@@ -307,11 +310,12 @@ bool gmm_sp_launch(GmmModel& m, int R, const float* x, long N, float* score, uns
   const int S4 = m.KP / 8; const size_t lds = gmm_sp_lds(m);
   if (lds > 160 * 1024 || !gmm_sp_has(S4, R)) return false;
   dim3 grid((unsigned) cdiv(N, (long) gmm_sp_frames()));
+  const float rad = gmm_trust_radius(m.D, 1.1e-5f, R == 4 ? 4 : R / 2), radK = gmm_trust_radius(m.D, 1e-5f, 0);   // (thrK multiplies radK by 1000 in the kernel)
   const int stagger = getenv("DSR_GMM_STAGGER") ? atoi(getenv("DSR_GMM_STAGGER")) : 1;
   masks.reserve((size_t) grid.x * 4 * (size_t) m.GT * 64);       // one flag word per lane and chunk
 #define LSD(SS, RR, DD) { DSR_HIP(hipFuncSetAttribute((const void*) k_gmm_mfma_sp<SS, kSpNT, RR, DD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); \
   hipLaunchKernelGGL((k_gmm_mfma_sp<SS, kSpNT, RR, DD>), grid, dim3(256), lds, st, x, N, m.D, m.Dp, m.K, m.G, m.GT, m.d_bn.p, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, \
-                     score, argmin, masks.p, 2.0f * m.ivMax, m.termMax, stagger); }
+                     score, argmin, masks.p, 2.0f * m.ivMax, m.termMax, rad, radK, stagger); }
   const int dbg = (S4 == 10 && R == 4 && getenv("DSR_GMM_SPDBG")) ? atoi(getenv("DSR_GMM_SPDBG")) : 0;
   if (dbg) {
     if (dbg & 4) DSR_HIP(hipMemsetAsync(masks.p, 0, sizeof(unsigned) * (size_t) grid.x * 4 * (size_t) m.GT * 64, st));   // (no flag words written)

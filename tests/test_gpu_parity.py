@@ -698,8 +698,9 @@ def test_gmm_mfma_mode(dsr, oracle, cuda, K, R, D):
                                             (7, 39, 1000, None, 8), (33, 13, 515, 2, 8), (5, 39, 700, None, 16), (67, 13, 129, None, 16), (130, 39, 300, 5, 16), (3, 39, 1000, None, 32), (37, 13, 640, 4, 32)])
 def test_gmm_mfma_four_gaussian_codebooks(dsr, oracle, cuda, monkeypatch, K, D, N, tiecap, R):
     """Codebooks of four (and, at the depths of 13- and 39-dimensional features, 8 / 16 / 32) Gaussians go through the one-wave-per-SIMD shape (k_gmm_sp.hip): a last chunk that the codebooks do not fill, an odd chunk
-    count (a phantom chunk closes the pair), frame counts that end inside a tile / a wave / a workgroup, a strip of fewer than 32 codebooks, every
-    contraction depth the kernel is instantiated for -- and a tie list that fills up (entries settled in place).  Argmin = the reference's on every
+    count (a phantom chunk closes the pair), frame counts that end inside a tile / a wave / a workgroup, a strip of fewer than 32 codebooks, the
+    contraction depths of 5-, 13-, 20- and 39-dimensional features (tests/test_gpu_gmm_shapes.py runs every depth the kernels are instantiated for, on
+    near-tie frames) -- and a tie list that fills up (entries settled in place).  Argmin = the reference's on every
     frame, scores within the stated tolerance; the other shape (DSR_GMM_SP=0: two waves per SIMD) gives the same argmins and scores within the same
     tolerance (an entry on the edge of the trust radius may be re-scored exactly by one shape and not by the other)."""
     import torch

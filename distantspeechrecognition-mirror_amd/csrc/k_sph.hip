@@ -31,6 +31,7 @@
 // SphericalMOENBeamformer :1804-2099, SphericalSpatialDSBeamformer :2106-2270) are host weight designs below; all of them run on the beams kernels.
 // The MFMA's lane map: csrc/mfma64.h; the frame tiling (FB, bin_chunk) and the shared kernel parts: csrc/srp_common.h.
 #include "srp_common.h"
+#include "sph_math.h"
 #include "gsc_weights.h"
 #include "svd_linpack.h"
 #include <algorithm>
@@ -47,10 +48,6 @@ constexpr double SSPEED = 343740.0;                          // mm/s (beamformer
 constexpr int MAX_ORDER = 8;                                 // dim = maxOrder^2 <= 64: four 16-row tiles of the fused kernel
 constexpr int MAX_BEAMS = 16;                               // one MFMA row tile
 constexpr long MAX_TABLE = 1L << 27;                         // (fbinMax+1) units max(dim, C) complex128 entries: 2 GiB per table copy
-
-// the EigenMike's 32 capsules in degrees (setEigenMikeGeometry :414-535), radius 42 mm
-const int EM_THETA[32] = {69, 90, 111, 90, 32, 55, 90, 125, 148, 125, 90, 55, 21, 58, 121, 159, 69, 90, 111, 90, 32, 55, 90, 125, 148, 125, 90, 55, 21, 58, 122, 159};
-const int EM_PHI[32] = {0, 32, 0, 328, 0, 45, 69, 45, 0, 315, 291, 315, 91, 90, 90, 89, 180, 212, 180, 148, 180, 225, 249, 225, 180, 135, 111, 135, 269, 270, 270, 271};
 
 }  // namespace
 
@@ -81,20 +78,7 @@ struct dsr_sph {
 
 namespace {
 
-// ---- GSL-shaped complex arithmetic (gsl_complex_math.c), so that the closed forms keep the reference's order of operations ----
-inline zc gmul(zc a, zc b) { return zc(a.real() * b.real() - a.imag() * b.imag(), a.real() * b.imag() + a.imag() * b.real()); }
-inline zc gdiv(zc a, zc b)
-{
-  const double s = 1.0 / std::hypot(b.real(), b.imag()), sbr = s * b.real(), sbi = s * b.imag();
-  return zc((a.real() * sbr + a.imag() * sbi) * s, (a.imag() * sbr - a.real() * sbi) * s);
-}
-inline zc gdivr(zc a, double x) { return zc(a.real() / x, a.imag() / x); }
-inline zc gmulr(zc a, double x) { return zc(a.real() * x, a.imag() * x); }
-inline double gsinc(double x)                                // gsl_sf_sinc(x) = sin(pi x) / (pi x)
-{
-  const double y = M_PI * x;
-  return std::fabs(x) < 1e-8 ? 1.0 - y * y / 6.0 : std::sin(y) / y;
-}
+// the GSL-shaped complex arithmetic (gmul, gdiv, gdivr, gmulr, gsinc), sph_plm and the EigenMike tables: csrc/sph_math.h
 
 }  // namespace
 
@@ -195,25 +179,6 @@ zc mode_amplitude(int order, double ka)
     return zc(-gmul(grad, hn).real() + jn, -gmul(grad, hn).imag());
   }
   }
-}
-
-// gsl_sf_legendre_sphPlm(l, m, x), m >= 0: sqrt((2l+1)/(4 pi)) sqrt((l-m)!/(l+m)!) P_l^m(x) with the Condon-Shortley phase, by the normalised recurrence
-double sph_plm(int l, int m, double x)
-{
-  double pmm = 1.0 / std::sqrt(4.0 * M_PI);
-  const double u = std::sqrt((1.0 - x) * (1.0 + x));
-  for (int i = 1; i <= m; i++) pmm *= -u * std::sqrt((2.0 * i + 1.0) / (2.0 * i));
-  if (l == m) return pmm;
-  double p1 = x * std::sqrt(2.0 * m + 3.0) * pmm;
-  if (l == m + 1) return p1;
-  double p0 = pmm;
-  for (int n = m + 2; n <= l; n++) {
-    const double a = std::sqrt((4.0 * n * n - 1.0) / ((double) n * n - (double) m * m));
-    const double b = std::sqrt(((n - 1.0) * (n - 1.0) - (double) m * m) / (4.0 * (n - 1.0) * (n - 1.0) - 1.0));
-    const double p = a * (x * p1 - b * p0);
-    p0 = p1; p1 = p;
-  }
-  return p1;
 }
 
 // sphericalHarmonic(degree m, order n, theta, phi) (:189-217): (-1)^|m| sphPlm(n, |m|) for m < 0, times e^{i m phi}

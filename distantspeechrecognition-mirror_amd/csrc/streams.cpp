@@ -422,6 +422,39 @@ struct SphBfOp : BfOp {              // EigenBeamformer / SphericalDSBeamformer 
   }
 };
 
+// ModalSphericalArrayTracker / SpatialSphericalArrayTracker as a stream (tracker.cc:1280-1345 / :1356-1436) over a dsr_trk handle (not owned):
+// ups = the 32 channels, a row = float (theta, phi).  The filter's state (position, K) belongs to the operator and outlives reset(), as in the
+// reference; nextSpeaker() resets the stream and the state, setInitialPosition() moves the position alone.
+struct TrkOp : dsr_stream {
+  dsr_trk* trk = nullptr; int M = 0; DevBuf<float2> X; DevBuf<int> nf; DevBuf<double> state, p64; DevBuf<int> inf; bool stateReady = false, posPending = false; double pTheta = 0, pPhi = 0;
+  void need_state() {
+    if (!stateReady) { require_device(); state.reserve(dsr_trk_state_doubles(trk)); ok(dsr_trk_init_state(trk, state.p, 1, 0, S0)); stateReady = true; }
+    if (posPending) { ok(dsr_trk_set_initial_position(trk, pTheta, pPhi)); ok(dsr_trk_init_state(trk, state.p, 1, 1, S0)); ok(dsr_trk_next_speaker(trk)); posPending = false; }
+  }
+  void compute() override {
+    const int C = (int) ups.size();
+    if (C != 32) throw Error(DSR_E_ARG, "the tracker needs the EigenMike's 32 channels, %d are set", C);
+    const int T = shortest(this, 0, C), F = M / 2 + 1;
+    alloc(T); if (T <= 0) return;
+    need_state();
+    X.reserve((size_t) C * T * F); pack_channels(this, 0, C, T, F, M, X.p); nf.upload(&T, 1);
+    p64.reserve((size_t) T * 2); inf.reserve(T);
+    ok(dsr_trk_run(trk, (const float*) X.p, nf.p, 1, T, state.p, d<float>(), p64.p, inf.p, S0));
+  }
+};
+// PlaneWaveSimulator(source, modalDecomposition, channelX, theta, phi) (tracker.cc:1444-1488): ups[0] = the source spectrum; rows of fftLen bins
+struct PwsOp : dsr_stream {
+  int M = 0; std::vector<double2> hcoef; DevBuf<double2> coef; DevBuf<float2> src, Y; DevBuf<int> nf;
+  void compute() override {
+    const int T = ups[0]->nFrames, F = M / 2 + 1;
+    alloc(T); if (T <= 0) return;
+    if (!coef.p) coef.upload(hcoef);
+    src.reserve((size_t) T * F); Y.reserve((size_t) T * M); op_pack_bins(ups[0]->d<double2>(), T, F, ups[0]->size_, src.p, S0); nf.upload(&T, 1);
+    ok(dsr_pws_apply((const double*) coef.p, 1, (const float*) src.p, nf.p, 1, T, M, 1, (float*) Y.p, S0));
+    op_expand_bins(Y.p, T, M, M, d<double2>(), S0);
+  }
+};
+
 // the eigenbeams of the DOA operator: its range only, of the last ungated frame (a re-materialisation keeps it), anew after a settings change
 struct SphDoaOp : SrpFace<SphBfOp, SphSrp> {
   void pack_frames() override { pack(); eigenRange = true; eigenLo = rangeUsed[0]; eigenHi = rangeUsed[1]; }   // the eigenbeams themselves only when getSnapShotArray asks
@@ -1243,6 +1276,42 @@ dsr_status dsr_sph_stream_get_eigenbeams(dsr_stream* s, double* out, size_t outD
     const size_t need = (size_t) q->F * q->dim * 2;
     if (outDoubles < need) throw Error(DSR_E_DIMENSION, "output holds %zu doubles, %zu needed", outDoubles, need);
     q->eigenbeams(out); *n = need;
+  });
+}
+dsr_status dsr_trk_stream_create(dsr_trk* trk, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    if (!trk || !out) throw Error(DSR_E_ARG, "null argument");
+    TrkOp* s = mk<TrkOp>(name, "SphericalArrayTracker", 2, DSR_T_FLOAT); s->trk = trk; s->M = dsr_trk_fft_len(trk); s->checkOrder = false; *out = s;
+  });
+}
+dsr_status dsr_trk_stream_set_channel(dsr_stream* s, dsr_stream* chan)
+{
+  return guard([&] {
+    TrkOp* q = as_op<TrkOp>(s, "tracker"); need(chan, DSR_T_COMPLEX, "setChannel");
+    if (chan->size_ != q->M) throw Error(DSR_E_DIMENSION, "channel size %d != fftLen %d", chan->size_, q->M);
+    q->add_up(chan); q->ready = false;
+  });
+}
+dsr_status dsr_trk_stream_next_speaker(dsr_stream* s)
+{ return guard([&] { TrkOp* q = as_op<TrkOp>(s, "tracker"); q->reset(); ok(dsr_trk_next_speaker(q->trk)); q->stateReady = false; q->posPending = false; }); }
+dsr_status dsr_trk_stream_set_initial_position(dsr_stream* s, double theta, double phi)
+{
+  return guard([&] {
+    TrkOp* q = as_op<TrkOp>(s, "tracker"); q->posPending = true; q->pTheta = theta; q->pPhi = phi; q->ready = false;      // applied when the next frame is computed
+  });
+}
+dsr_status dsr_pws_stream_create(dsr_stream* source, const dsr_trk* decomposition, unsigned channelX, double theta, double phi, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    if (!decomposition || !out) throw Error(DSR_E_ARG, "null argument");
+    need(source, DSR_T_COMPLEX, "PlaneWaveSimulator");
+    const int M = dsr_trk_fft_len(decomposition), F = M / 2 + 1;
+    if (channelX >= 32 || source->size_ < F) throw Error(DSR_E_ARG, "channel %u of 32, a source of at least %d bins", channelX, F);
+    std::vector<double> all((size_t) 2 * 32 * F); ok(dsr_pws_coefficients(decomposition, theta, phi, all.data(), all.size()));
+    std::unique_ptr<PwsOp> s(mk<PwsOp>(name, "Plane Wave Simulator", M, DSR_T_COMPLEX)); s->M = M; s->checkOrder = false;
+    const double2* row = reinterpret_cast<const double2*>(all.data()) + (size_t) channelX * F; s->hcoef.assign(row, row + F);
+    s->add_up(source); *out = s.release();
   });
 }
 dsr_status dsr_sph_doa_stream_create(dsr_sph* sph, const char* name, dsr_stream** out)

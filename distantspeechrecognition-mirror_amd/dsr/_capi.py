@@ -1043,6 +1043,131 @@ class SphDoaSRP(_Sph):
         return R, I
 
 
+class SphTracker:
+    """The spherical-array speaker trackers of btk/beamformer/tracker.{h,cc} (include/dsr.h section 2c''): kind "modal" (ModalDecomposition +
+    ModalSphericalArrayTracker) or "spatial" (SpatialDecomposition + SpatialSphericalArrayTracker) over a batch.  The handle holds the
+    decomposition's tables and the tracker's parameters; the filter's state (position, K) is a device buffer of the caller (newState) that
+    run() continues from and leaves behind, so an utterance may come in blocks."""
+    KINDS = {"modal": 0, "spatial": 1}
+    CLAMP, ERROR = 1 << 8, 1 << 9
+
+    def __init__(self, kind, orderN, fftLen, a=42.0, sampleRate=16000.0, useSubbandsN=0, sigma2_u=10.0, sigma2_v=10.0, sigma2_init=10.0, maxLocalN=1,
+                 chanN=32):
+        L = load(); self.h = vp(); self.kind = self.KINDS[kind] if isinstance(kind, str) else int(kind)
+        check(L.dsr_trk_create(self.kind, int(orderN), int(fftLen), float(a), float(sampleRate), int(useSubbandsN), float(sigma2_u), float(sigma2_v),
+                               float(sigma2_init), int(maxLocalN), int(chanN), C.byref(self.h)))
+        self.M, self.F, self.orderN = int(fftLen), int(fftLen) // 2 + 1, int(orderN)
+        self.modesN = L.dsr_trk_modes_n(self.h); self.L = L.dsr_trk_subband_length(self.h); self.useSubbandsN = L.dsr_trk_use_subbands_n(self.h)
+
+    def __del__(self):
+        if _lib is not None and getattr(self, "h", None):
+            _lib.dsr_trk_destroy(self.h)
+
+    @staticmethod
+    def maxRows(kind, orderN, useSubbandsN):
+        return int(load().dsr_trk_max_rows(SphTracker.KINDS[kind] if isinstance(kind, str) else int(kind), int(orderN), int(useSubbandsN)))
+
+    def setV(self, Vk, subbandX):
+        v = _np(Vk, np.complex128)
+        if v.shape != (self.L, self.L):
+            raise DsrError(E_PARAMETER, "Vk: [%d][%d] expected" % (self.L, self.L))
+        check(_lib.dsr_trk_set_v(self.h, _ptr(v), v.size * 2, int(subbandX)))
+
+    def getV(self, subbandX):
+        out = np.zeros((2 * self.L, 2 * self.L), np.float64); check(_lib.dsr_trk_get_v(self.h, int(subbandX), _ptr(out), out.size)); return out
+
+    def setInitialPosition(self, theta, phi):
+        check(_lib.dsr_trk_set_initial_position(self.h, float(theta), float(phi)))
+
+    def nextSpeaker(self):
+        check(_lib.dsr_trk_next_speaker(self.h))
+
+    def bn(self):
+        out = np.zeros((self.F, self.orderN + 1), np.complex128); check(_lib.dsr_trk_bn(self.h, _ptr(out), out.size * 2)); return out
+
+    def sensorHarmonics(self):
+        out = np.zeros((self.modesN, 32), np.complex128); check(_lib.dsr_trk_sensor_harmonics(self.h, _ptr(out), out.size * 2)); return out
+
+    @staticmethod
+    def geometry():
+        t, p = np.zeros(32), np.zeros(32); check(load().dsr_trk_geometry(_ptr(t), _ptr(p), 32)); return t, p
+
+    @staticmethod
+    def _static(fn, *args):
+        out = np.zeros(2, np.float64); load(); check(fn(*args, _ptr(out))); return complex(out[0], out[1])
+
+    @staticmethod
+    def harmonic(order, degree, theta, phi):
+        return SphTracker._static(load().dsr_trk_harmonic, int(order), int(degree), float(theta), float(phi))
+
+    @staticmethod
+    def harmonicDerivPolarAngle(order, degree, theta, phi):
+        return SphTracker._static(load().dsr_trk_harmonic_deriv_polar, int(order), int(degree), float(theta), float(phi))
+
+    @staticmethod
+    def harmonicDerivAzimuth(order, degree, theta, phi):
+        return SphTracker._static(load().dsr_trk_harmonic_deriv_azimuth, int(order), int(degree), float(theta), float(phi))
+
+    @staticmethod
+    def modalCoefficient(order, ka):
+        return SphTracker._static(load().dsr_trk_modal_coefficient, int(order), float(ka))
+
+    def stateDoubles(self):
+        return int(_lib.dsr_trk_state_doubles(self.h))
+
+    def newState(self, U, device="cuda:0"):
+        import torch
+        st = torch.zeros((int(U), self.stateDoubles()), dtype=torch.float64, device=device)
+        self.initState(st); return st
+
+    def initState(self, state, positionOnly=False):
+        """positionOnly False: as nextSpeaker leaves the tracker (the handle's initial position, the initial K); True: setInitialPosition"""
+        check(_lib.dsr_trk_init_state(self.h, _dev(state), int(state.shape[0]), int(bool(positionOnly)), cur_stream()))
+
+    def run(self, X, nframes=None, state=None):
+        """X cuda complex64 [U][32][T][M/2+1] -> (pos [U][T][2] float32, pos64 [U][T][2] float64, info [U][T] int32); rows past nframes[u] are
+        zero.  state None: a fresh one, discarded."""
+        import torch
+        U, Cn, T, F = X.shape
+        if Cn != 32 or F != self.F or X.dtype != torch.complex64:
+            raise ValueError("X: complex64 [U][32][T][%d] expected" % self.F)
+        dev = X.device
+        if nframes is None:
+            nframes = torch.full((U,), T, dtype=torch.int32, device=dev)
+        if state is None:
+            state = self.newState(U, dev)
+        pos = torch.zeros((U, T, 2), dtype=torch.float32, device=dev); pos64 = torch.zeros((U, T, 2), dtype=torch.float64, device=dev)
+        info = torch.zeros((U, T), dtype=torch.int32, device=dev)
+        check(_lib.dsr_trk_run(self.h, _dev(torch.view_as_real(X.contiguous())), _dev(nframes), U, T, _dev(state), _dev(pos), _dev(pos64), _dev(info), cur_stream()))
+        return pos, pos64, info
+
+
+class PlaneWaveSim:
+    """PlaneWaveSimulator (tracker.cc:1444-1488) for all 32 channels at once: coefficients on the host (over a SphTracker's decomposition), the
+    product with the source spectrum on the device"""
+
+    def __init__(self, tracker, theta, phi):
+        self.trk, self.F, self.M = tracker, tracker.F, tracker.M
+        self.coef = np.zeros((32, self.F), np.complex128)
+        check(_lib.dsr_pws_coefficients(tracker.h, float(theta), float(phi), _ptr(self.coef), self.coef.size * 2))
+        self._dev = None
+
+    def apply(self, src, nframes=None, full=False):
+        """src cuda complex64 [U][T][M/2+1] -> [U][32][T][M/2+1] complex64, or rows of M bins with the conjugate mirror (full)"""
+        import torch
+        U, T, F = src.shape
+        if F != self.F or src.dtype != torch.complex64:
+            raise ValueError("src: complex64 [U][T][%d] expected" % self.F)
+        dev = src.device
+        if self._dev is None or self._dev.device != dev:
+            self._dev = torch.view_as_real(torch.from_numpy(self.coef)).contiguous().to(dev)
+        if nframes is None:
+            nframes = torch.full((U,), T, dtype=torch.int32, device=dev)
+        out = torch.zeros((U, 32, T, self.M if full else F), dtype=torch.complex64, device=dev)
+        check(_lib.dsr_pws_apply(_dev(self._dev), 32, _dev(torch.view_as_real(src.contiguous())), _dev(nframes), U, T, self.M, int(bool(full)), _dev(out), cur_stream()))
+        return out
+
+
 class ZelinskiPostFilter:
     """Zelinski post-filter (postfilter.cc:8-221,350-493); manifold [M/2+1][C] complex = arrayManifold() (or wq() with type | 8)."""
 

@@ -546,3 +546,101 @@ class DOAEstimatorSRPSphDSBPtr(_SphericalDOA):
 
     def __init__(self, nBest, sampleRate, fftLen=512, halfBandShift=False, NC=1, maxOrder=8, normalizeWeight=False, nm="DirectionEstimatorSRPMB"):
         _Spherical.__init__(self, nBest, sampleRate, fftLen, halfBandShift, NC, maxOrder, normalizeWeight, nm)
+
+
+class _Decomposition(object):
+    """ModalDecompositionPtr / SpatialDecompositionPtr(orderN, subbandsN, a, sampleRate, useSubbandsN=0) (beamformer.i:820-872): the arguments and
+    the host-side tables; the tracker built on it makes the handle that also holds the tracker's parameters"""
+    _KIND = "modal"
+
+    def __init__(self, orderN, subbandsN, a, sampleRate, useSubbandsN=0):
+        self._args = (int(orderN), int(subbandsN), float(a), float(sampleRate), int(useSubbandsN))
+        self._trk = K.SphTracker(self._KIND, orderN, subbandsN, a, sampleRate, 1)      # the tables only: the tracker's handle checks the observation's length
+
+    def orderN(self):
+        return self._args[0]
+
+    def modesN(self):
+        return self._trk.modesN
+
+    def subbandsN(self):
+        return self._args[1]
+
+    def subbandsN2(self):
+        return self._args[1] // 2
+
+    def useSubbandsN(self):
+        return self._args[4] or self._args[1] // 2 + 1
+
+    def subbandLengthN(self):
+        return self._trk.L
+
+    def reset(self):
+        pass
+
+    def modalCoefficient(self, order, subbandX):
+        return self._trk.bn()[subbandX, order]
+
+    def harmonic(self, order, degree, *at):
+        """harmonic(order, degree, theta, phi), or harmonic(order, degree, channelX): the stored (conjugated) harmonic of a sensor"""
+        if len(at) == 1:
+            return self._trk.sensorHarmonics()[order * order + order + degree, at[0]]
+        return K.SphTracker.harmonic(order, degree, *at)
+
+    harmonicDerivPolarAngle = staticmethod(K.SphTracker.harmonicDerivPolarAngle)
+    harmonicDerivAzimuth = staticmethod(K.SphTracker.harmonicDerivAzimuth)
+
+
+class ModalDecompositionPtr(_Decomposition):
+    _KIND = "modal"
+
+
+class SpatialDecompositionPtr(_Decomposition):
+    _KIND = "spatial"
+
+
+class _SphericalArrayTracker(FeatureStreamPtr):
+    """Modal / SpatialSphericalArrayTrackerPtr(decomposition, sigma2_u=10.0, sigma2_v=10.0, sigma2_init=10.0, maxLocalN=1, nm) (beamformer.i:874-948):
+    a stream of float (theta, phi) over the 32 channels given by setChannel"""
+    _KIND, _NAME = "modal", "ModalSphericalArrayTracker"
+
+    def __init__(self, decomposition, sigma2_u=10.0, sigma2_v=10.0, sigma2_init=10.0, maxLocalN=1, nm=None):
+        if decomposition._KIND != self._KIND:
+            raise K.DsrError(K.E_PARAMETER, "%s needs a %s decomposition" % (self._NAME, self._KIND))
+        o, M, a, fs, use = decomposition._args
+        self._dec = decomposition
+        self._trk = K.SphTracker(self._KIND, o, M, a, fs, use, sigma2_u, sigma2_v, sigma2_init, maxLocalN)
+        self._chans = []
+        h, _ = _new(lib().dsr_trk_stream_create, self._trk.h, (nm or self._NAME).encode())
+        FeatureStreamPtr.__init__(self, h)
+
+    def setChannel(self, chan):
+        K.check(lib().dsr_trk_stream_set_channel(self._h, chan._h)); self._chans.append(chan)
+
+    def chanN(self):
+        return len(self._chans)
+
+    def setV(self, Vk, subbandX):
+        self._trk.setV(Vk, subbandX)
+
+    def setInitialPosition(self, theta, phi):
+        K.check(lib().dsr_trk_stream_set_initial_position(self._h, float(theta), float(phi)))
+
+    def nextSpeaker(self):
+        K.check(lib().dsr_trk_stream_next_speaker(self._h))
+
+
+class ModalSphericalArrayTrackerPtr(_SphericalArrayTracker):
+    _KIND, _NAME = "modal", "ModalSphericalArrayTracker"
+
+
+class SpatialSphericalArrayTrackerPtr(_SphericalArrayTracker):
+    _KIND, _NAME = "spatial", "SpatialSphericalArrayTracker"
+
+
+class PlaneWaveSimulatorPtr(FeatureStreamPtr):
+    """PlaneWaveSimulatorPtr(source, modalDecomposition, channelX, theta, phi, nm="Plane Wave Simulator") (beamformer.i:950-977)"""
+
+    def __init__(self, source, modalDecomposition, channelX, theta, phi, nm="Plane Wave Simulator"):
+        h, _ = _new(lib().dsr_pws_stream_create, source._h, modalDecomposition._trk.h, int(channelX), float(theta), float(phi), nm.encode())
+        FeatureStreamPtr.__init__(self, h, keep=(source, modalDecomposition))

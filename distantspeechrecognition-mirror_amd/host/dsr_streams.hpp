@@ -599,6 +599,78 @@ class SubbandMMI : public VectorComplexFeatureStream {
   unsigned _fftLen; bool _hbs; unsigned _target, _nSource; int _pfType; double _alpha; String _nm; dsr_mmi* _w;
   bool _mask; double _avg; unsigned _fwidth, _mtype; std::vector<VectorComplexFeatureStreamPtr> _channelList;
 };
+// ---- btk/beamformer/tracker.h: ModalDecomposition / SpatialDecomposition (:181-211), Modal / SpatialSphericalArrayTracker (:301-330),
+// PlaneWaveSimulator (:335-359).  A decomposition keeps its arguments and a handle for its tables; the tracker built on it makes its own handle
+// with the filter's parameters.  setV takes the L x L complex block row major (L = subbandLengthN()).
+class BaseDecomposition {
+ public:
+  BaseDecomposition(unsigned orderN, unsigned subbandsN, double a, double sampleRate, unsigned useSubbandsN = 0, bool spatial = false)
+    : _orderN(orderN), _subbandsN(subbandsN), _useSubbandsN(useSubbandsN), _a(a), _sampleRate(sampleRate), _spatial(spatial), _t(0) {
+    dsr_throw(dsr_trk_create(spatial ? DSR_TRK_SPATIAL : DSR_TRK_MODAL, (int) orderN, (int) subbandsN, a, sampleRate, 1, 10.0, 10.0, 10.0, 1, 32, &_t));   // the tables only: the tracker's handle checks the observation's length
+  }
+  virtual ~BaseDecomposition() { if (_t) dsr_trk_destroy(_t); }
+  unsigned orderN() const { return _orderN; }
+  unsigned modesN() const { return (unsigned) dsr_trk_modes_n(_t); }
+  unsigned subbandsN() const { return _subbandsN; }
+  unsigned subbandsN2() const { return _subbandsN / 2; }
+  unsigned useSubbandsN() const { return _useSubbandsN ? _useSubbandsN : _subbandsN / 2 + 1; }
+  unsigned subbandLengthN() const { return (unsigned) dsr_trk_subband_length(_t); }
+  virtual void reset() {}
+  static std::complex<double> harmonic(int order, int degree, double theta, double phi) { double o[2]; dsr_throw(dsr_trk_harmonic(order, degree, theta, phi, o)); return std::complex<double>(o[0], o[1]); }
+  static std::complex<double> harmonicDerivPolarAngle(int order, int degree, double theta, double phi) { double o[2]; dsr_throw(dsr_trk_harmonic_deriv_polar(order, degree, theta, phi, o)); return std::complex<double>(o[0], o[1]); }
+  static std::complex<double> harmonicDerivAzimuth(int order, int degree, double theta, double phi) { double o[2]; dsr_throw(dsr_trk_harmonic_deriv_azimuth(order, degree, theta, phi, o)); return std::complex<double>(o[0], o[1]); }
+  static std::complex<double> modalCoefficient(unsigned order, double ka) { double o[2]; dsr_throw(dsr_trk_modal_coefficient(order, ka, o)); return std::complex<double>(o[0], o[1]); }
+  const dsr_trk* handle() const { return _t; }
+  bool spatial() const { return _spatial; }
+  double a() const { return _a; }
+  double sampleRate() const { return _sampleRate; }
+  unsigned useSubbandsArg() const { return _useSubbandsN; }
+ private:
+  BaseDecomposition(const BaseDecomposition&); BaseDecomposition& operator=(const BaseDecomposition&);
+  unsigned _orderN, _subbandsN, _useSubbandsN; double _a, _sampleRate; bool _spatial; dsr_trk* _t;
+};
+class ModalDecomposition : public BaseDecomposition {
+ public: ModalDecomposition(unsigned orderN, unsigned subbandsN, double a, double sampleRate, unsigned useSubbandsN = 0) : BaseDecomposition(orderN, subbandsN, a, sampleRate, useSubbandsN, false) {}
+};
+class SpatialDecomposition : public BaseDecomposition {
+ public: SpatialDecomposition(unsigned orderN, unsigned subbandsN, double a, double sampleRate, unsigned useSubbandsN = 0) : BaseDecomposition(orderN, subbandsN, a, sampleRate, useSubbandsN, true) {}
+};
+typedef std::shared_ptr<BaseDecomposition> BaseDecompositionPtr;
+typedef std::shared_ptr<ModalDecomposition> ModalDecompositionPtr;
+typedef std::shared_ptr<SpatialDecomposition> SpatialDecompositionPtr;
+class BaseSphericalArrayTracker : public VectorFloatFeatureStream {
+ public:
+  BaseSphericalArrayTracker(const BaseDecomposition& d, double sigma2_u, double sigma2_v, double sigma2_init, unsigned maxLocalN, const String& nm) : _t(0) {
+    dsr_throw(dsr_trk_create(d.spatial() ? DSR_TRK_SPATIAL : DSR_TRK_MODAL, (int) d.orderN(), (int) d.subbandsN(), d.a(), d.sampleRate(), (int) d.useSubbandsArg(), sigma2_u, sigma2_v,
+                             sigma2_init, (int) maxLocalN, 32, &_t));
+    DSR_OP(BaseSphericalArrayTracker, float, dsr_trk_stream_create(_t, nm.c_str(), &h))
+  }
+  ~BaseSphericalArrayTracker() { if (_t) dsr_trk_destroy(_t); }
+  void setChannel(VectorComplexFeatureStreamPtr& chan) { dsr_throw(dsr_trk_stream_set_channel(_h, chan->handle())); _channelList.push_back(chan); }
+  void setV(const std::complex<double>* Vk, unsigned subbandX) { const size_t L = (size_t) dsr_trk_subband_length(_t); dsr_throw(dsr_trk_set_v(_t, reinterpret_cast<const double*>(Vk), 2 * L * L, subbandX)); }
+  unsigned chanN() const { return (unsigned) _channelList.size(); }
+  void nextSpeaker() { dsr_throw(dsr_trk_stream_next_speaker(_h)); }
+  void setInitialPosition(double theta, double phi) { dsr_throw(dsr_trk_stream_set_initial_position(_h, theta, phi)); }
+ private:
+  dsr_trk* _t; std::vector<VectorComplexFeatureStreamPtr> _channelList;
+};
+class ModalSphericalArrayTracker : public BaseSphericalArrayTracker {
+ public: ModalSphericalArrayTracker(ModalDecompositionPtr& modalDecomposition, double sigma2_u = 10.0, double sigma2_v = 10.0, double sigma2_init = 10.0, unsigned maxLocalN = 1,
+                                    const String& nm = "ModalSphericalArrayTracker") : BaseSphericalArrayTracker(*modalDecomposition, sigma2_u, sigma2_v, sigma2_init, maxLocalN, nm) {}
+};
+class SpatialSphericalArrayTracker : public BaseSphericalArrayTracker {
+ public: SpatialSphericalArrayTracker(SpatialDecompositionPtr& spatialDecomposition, double sigma2_u = 10.0, double sigma2_v = 10.0, double sigma2_init = 10.0, unsigned maxLocalN = 1,
+                                      const String& nm = "SpatialSphericalArrayTracker") : BaseSphericalArrayTracker(*spatialDecomposition, sigma2_u, sigma2_v, sigma2_init, maxLocalN, nm) {}
+};
+typedef std::shared_ptr<ModalSphericalArrayTracker> ModalSphericalArrayTrackerPtr;
+typedef std::shared_ptr<SpatialSphericalArrayTracker> SpatialSphericalArrayTrackerPtr;
+class PlaneWaveSimulator : public VectorComplexFeatureStream {
+ public:
+  PlaneWaveSimulator(const VectorComplexFeatureStreamPtr& source, ModalDecompositionPtr& modalDecomposition, unsigned channelX, double theta, double phi, const String& nm = "Plane Wave Simulator")
+    : _s(source), _d(modalDecomposition) { DSR_OP(PlaneWaveSimulator, cplx, dsr_pws_stream_create(source->handle(), modalDecomposition->handle(), channelX, theta, phi, nm.c_str(), &h)) }
+ private: VectorComplexFeatureStreamPtr _s; ModalDecompositionPtr _d;
+};
+typedef std::shared_ptr<PlaneWaveSimulator> PlaneWaveSimulatorPtr;
 #undef DSR_OP
 
 // ======================================================================================================================

@@ -402,6 +402,69 @@ dsr_status dsr_sph_beam_pattern(dsr_sph*, unsigned fbinX, double theta, double p
                                 double widthTheta, double widthPhi, double* out, size_t outDoubles);
 
 /* =====================================================================================
+ * 2c''. Spherical-array speaker trackers and the plane-wave simulator
+ *     replaces ModalDecomposition, SpatialDecomposition (btk/beamformer/tracker.h:181-211), ModalSphericalArrayTracker,
+ *     SpatialSphericalArrayTracker (tracker.h:216-330) and PlaneWaveSimulator (tracker.h:335-359); beamformer.i:820-960.
+ *     An iterated extended Kalman filter in square-root form follows (theta, phi) frame by frame from the subband snapshots of the
+ *     EigenMike's 32 capsules (the geometry is fixed, tracker.cc:195-297).  Argument errors are DSR_E_ARG (= DSR_E_PARAMETER): another
+ *     channel count, an observation longer than the kernel holds, a setV block that is not positive definite.
+ *     The subband sort (tracker.h:68-73, std::sort, ties unspecified there) puts the lower bin first among equal |B|.
+ * ===================================================================================== */
+#define DSR_E_ARG DSR_E_PARAMETER
+typedef struct dsr_trk dsr_trk;
+enum { DSR_TRK_MODAL = 0, DSR_TRK_SPATIAL = 1 };
+/* the decomposition (tracker.h:183 / :201: orderN, subbandsN = fftLen, a [mm], sampleRate, useSubbandsN, 0 = all fftLen/2+1) and its tracker
+   (tracker.h:306 / :323: sigma2_u, sigma2_v, sigma2_init, maxLocalN) in one handle.  chanN must be 32.  2N = 2 useSubbandsN subbandLength
+   (modesN = (orderN+1)^2 modal, 32 spatial) rows above dsr_trk_max_rows are refused. */
+dsr_status dsr_trk_create(int kind, int orderN, int fftLen, double a, double sampleRate, int useSubbandsN, double sigma2_u, double sigma2_v, double sigma2_init,
+                          int maxLocalN, int chanN, dsr_trk** out);
+void       dsr_trk_destroy(dsr_trk*);
+int        dsr_trk_modes_n(const dsr_trk*);            /* tracker.h:114 */
+int        dsr_trk_subband_length(const dsr_trk*);     /* tracker.h:118 */
+int        dsr_trk_use_subbands_n(const dsr_trk*);     /* tracker.h:117 */
+int        dsr_trk_fft_len(const dsr_trk*);            /* tracker.h:116 */
+/* the largest 2N the kernel's LDS (160 KB a workgroup) admits for a kind, order and number of selected bins */
+int64_t    dsr_trk_max_rows(int kind, int orderN, int useSubbandsN);
+/* setV(Vk, subbandX) (tracker.h:229, tracker.cc:961-981): Vk [L][L] complex128, L = subbandLength; the lower triangle is realified as written
+   (entries of the lower-left block above its diagonal keep their contents), the 2L x 2L block replaced by its Cholesky factor.  Defined for one
+   call per subband on a fresh tracker.  Not positive definite: DSR_E_ARG, nothing changed.  get_v: the 2L x 2L block as stored. */
+dsr_status dsr_trk_set_v(dsr_trk*, const double* Vk, size_t nDoubles, unsigned subbandX);
+dsr_status dsr_trk_get_v(const dsr_trk*, unsigned subbandX, double* out, size_t outDoubles);
+/* setInitialPosition (tracker.h:236) / nextSpeaker (tracker.h:235, position (0.5, 0)): the position dsr_trk_init_state writes */
+dsr_status dsr_trk_set_initial_position(dsr_trk*, double theta, double phi);
+dsr_status dsr_trk_next_speaker(dsr_trk*);
+/* the carried state: dsr_trk_state_doubles() doubles an utterance (theta, phi, K row major, frames seen, error flag), a device buffer of the
+   caller.  init_state: positionOnly == 0 as nextSpeaker leaves the tracker (the handle's initial position, K = sqrt(sqrt(sigma2_init)) I: the
+   root is taken twice, tracker.cc:890, :908, :928; frame count and error flag cleared); != 0 the position alone (setInitialPosition). */
+int        dsr_trk_state_doubles(const dsr_trk*);
+dsr_status dsr_trk_init_state(dsr_trk*, double* state_dev, int U, int positionOnly, void* stream);
+/* next() for every frame of a batch (tracker.h:310 / :327, tracker.cc:1280-1345 / :1356-1436): X_dev [U][32][Tmax][fftLen/2+1] complex64 (the
+   layout of dsr_fb_analysis), one workgroup an utterance, the frames in order, fp64.  pos_dev [U][Tmax][2] float32 (the reference's output),
+   pos64_dev the same before rounding, info_dev [U][Tmax] int32: bits 0-7 the local iterations used, bit 8 theta was clamped to [0.01, pi - 0.01],
+   bit 9 a Givens norm was zero (the reference throws there): the utterance's state is frozen and its last position repeated.  Rows beyond
+   nframes[u] are 0.  The state is read and left behind, so an utterance may come in blocks. */
+dsr_status dsr_trk_run(dsr_trk*, const float* X_dev, const int32_t* nframes_dev, int U, int Tmax, double* state_dev, float* pos_dev, double* pos64_dev,
+                       int32_t* info_dev, void* stream);
+/* _bn [fftLen/2+1][orderN+1] = 4 pi i^n b_n(ka) (tracker.cc:106-115), _sphericalComponent [modesN][32] (conjugated, tracker.cc:117-130), the
+   geometry in radians (tracker.cc:195-297): complex128 / doubles */
+dsr_status dsr_trk_bn(const dsr_trk*, double* out, size_t outDoubles);
+dsr_status dsr_trk_sensor_harmonics(const dsr_trk*, double* out, size_t outDoubles);
+dsr_status dsr_trk_geometry(double* theta_s, double* phi_s, int n);
+/* the static functions (tracker.h:124, :126-128): out2 = (re, im).  harmonic is sphPlm(n, |m|, cos theta), the sign flipped for odd negative m,
+   times e^{-i m phi}: the conjugate of dsr_sph_harmonics' convention */
+dsr_status dsr_trk_harmonic(int order, int degree, double theta, double phi, double* out2);
+dsr_status dsr_trk_harmonic_deriv_polar(int order, int degree, double theta, double phi, double* out2);
+dsr_status dsr_trk_harmonic_deriv_azimuth(int order, int degree, double theta, double phi, double* out2);
+dsr_status dsr_trk_modal_coefficient(unsigned order, double ka, double* out2);
+/* PlaneWaveSimulator (tracker.h:337, tracker.cc:1453-1465): the coefficients of every channel for a plane wave from (theta, phi), out
+   [32][fftLen/2+1] complex128, host side.  apply (tracker.cc:1474-1488): src_dev [U][Tmax][fftLen/2+1] complex64 times coef_dev
+   [chanN][fftLen/2+1] complex128 -> out_dev [U][chanN][Tmax][fftLen/2+1] complex64, or with full != 0 rows of fftLen bins, bin fftLen-k the
+   conjugate of bin k; frames beyond nframes[u] are 0. */
+dsr_status dsr_pws_coefficients(const dsr_trk*, double theta, double phi, double* out, size_t outDoubles);
+dsr_status dsr_pws_apply(const double* coef_dev, int chanN, const float* src_dev, const int32_t* nframes_dev, int U, int Tmax, int fftLen, int full, float* out_dev,
+                         void* stream);
+
+/* =====================================================================================
  * 2d. Subband acoustic echo (voice prompt) cancellation
  *     replaces NLMSAcousticEchoCancellationFeature, KalmanFilterEchoCancellationFeature, BlockKalmanFilterEchoCancellationFeature and
  *     DTDBlockKalmanFilterEchoCancellationFeature (btk/cancelVP/cancelVP.h:41-143,428-462, cancelVP.i:62-254, cancelVP.cc:35-383,1056-1198)
@@ -1360,6 +1423,15 @@ dsr_status dsr_sph_doa_stream_create(dsr_sph* sph, const char* name, dsr_stream*
 dsr_status dsr_sph_doa_stream_get(dsr_stream* s, int what, double* out, size_t outDoubles, size_t* n);
 dsr_status dsr_sph_doa_stream_init_accs(dsr_stream* s);
 dsr_status dsr_sph_doa_stream_final_nbest(dsr_stream* s);
+/* ModalSphericalArrayTracker / SpatialSphericalArrayTracker as a stream (beamformer.i:880-940, tracker.h:228-236) over a dsr_trk handle (not owned):
+ * 32 channels of fftLen complex bins through set_channel; next() returns float (theta, phi).  The filter's state belongs to the operator and
+ * outlives reset(); next_speaker = reset() + the initial state (the handle's initial position goes back to (0.5, 0)); set_initial_position moves the
+ * position alone.  PlaneWaveSimulator(source, modalDecomposition, channelX, theta, phi) (beamformer.i:942-960, tracker.h:337): rows of fftLen bins. */
+dsr_status dsr_trk_stream_create(dsr_trk* trk, const char* name, dsr_stream** out);
+dsr_status dsr_trk_stream_set_channel(dsr_stream* s, dsr_stream* chan);
+dsr_status dsr_trk_stream_next_speaker(dsr_stream* s);
+dsr_status dsr_trk_stream_set_initial_position(dsr_stream* s, double theta, double phi);
+dsr_status dsr_pws_stream_create(dsr_stream* source, const dsr_trk* decomposition, unsigned channelX, double theta, double phi, const char* name, dsr_stream** out);
 dsr_status dsr_preemphasis_create(dsr_stream* samp, double mu, const char* name, dsr_stream** out);
 dsr_status dsr_hamming_create(dsr_stream* samp, const char* name, dsr_stream** out);
 dsr_status dsr_fft_create(dsr_stream* samp, int fftLen, const char* name, dsr_stream** out);

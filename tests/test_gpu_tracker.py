@@ -1,0 +1,159 @@
+"""GPU tests of the spherical-array speaker trackers (csrc/k_tracker.hip, include/dsr.h section 2c'') against the numpy restatement
+tests/tracker_np.py on the cases of tests/tracker_cases.py.
+
+The bound on pos64 is max(64 s_case, 1e-12), s_case being the restatement's own float64-vs-long-double difference of the case
+(tests/test_tracker_np_cpu.py prints it): the factor covers another summation order in reductions over up to 32 channels and 2N <= 550 rows."""
+import numpy as np
+import pytest
+
+from tests import tracker_cases as Cs
+from tests import tracker_np as T
+
+pytestmark = pytest.mark.gpu
+
+
+def make(dsr, case):
+    trk = dsr.SphTracker(case["kind"], case["orderN"], Cs.M, Cs.A_MM, Cs.FS, case["useSubbandsN"], Cs.SIGMA2_U, Cs.SIGMA2_V, Cs.SIGMA2_INIT, case["maxLocalN"])
+    Vs = Cs.inputs(case)[2]
+    if Vs is not None:
+        for f in range(Cs.F):
+            trk.setV(Vs[f], f)
+    if case["init"]:
+        trk.setInitialPosition(*case["init"])
+    return trk
+
+
+def run_device(dsr, cuda, case, blocks=None, users=None):
+    """the case on the device, in one call or in blocks of frames (a list of lengths); the mid-utterance nextSpeaker of a case splits there.
+    -> (pos, pos64, info, final state) as numpy"""
+    import torch
+    users = list(range(Cs.U)) if users is None else users
+    X = torch.from_numpy(Cs.inputs(case)[1][users]).to(cuda)
+    nf = np.array([Cs.NFRAMES[u] for u in users])
+    trk = make(dsr, case)
+    state = trk.newState(len(users), cuda)
+    cuts = [0] + list(np.cumsum(blocks if blocks else [Cs.TMAX]))
+    if case["mid"]:
+        cuts = sorted(set(cuts + [case["mid"][0]]))
+    pos, pos64, info = [], [], []
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        if case["mid"] and a == case["mid"][0]:
+            trk.nextSpeaker(); trk.setInitialPosition(*case["mid"][1]); trk.initState(state)
+        n = torch.from_numpy(np.clip(nf - a, 0, b - a).astype(np.int32)).to(cuda)
+        p, p64, i = trk.run(X[:, :, a:b, :].contiguous(), n, state)
+        pos.append(p.cpu().numpy()); pos64.append(p64.cpu().numpy()); info.append(i.cpu().numpy())
+    return np.concatenate(pos, 1), np.concatenate(pos64, 1), np.concatenate(info, 1), state.cpu().numpy()
+
+
+@pytest.fixture(scope="module")
+def device_runs(dsr, cuda):
+    return {c["name"]: run_device(dsr, cuda, c) for c in Cs.CASES}
+
+
+@pytest.mark.parametrize("case", Cs.CASES, ids=[c["name"] for c in Cs.CASES])
+def test_batch_parity(case, device_runs):
+    ref = Cs.reference(case)
+    pos, pos64, info, _ = device_runs[case["name"]]
+    r = ref["ref"]
+    bound = max(64 * ref["s_case"], 1e-12)
+    diff = np.abs(pos64 - r["pos64"].astype(np.float64)).max()
+    truth = Cs.directions(case)
+    err = lambda t: float(np.abs(pos64[0, t] - truth[0, t]).max())
+    print("%s: s_case %.3e bound %.3e device difference %.3e; angular error frame 0 %.4f, last %.4f" % (case["name"], ref["s_case"], bound, diff, err(0), err(Cs.TMAX - 1)))
+    assert np.array_equal(info, r["info"])
+    assert diff <= bound
+    assert np.array_equal(pos, pos64.astype(np.float32))
+    for u in range(Cs.U):
+        n = Cs.NFRAMES[u]
+        assert not pos[u, n:].any() and not pos64[u, n:].any() and not info[u, n:].any()
+    if case["name"] == "modal-clamp":
+        assert (info & 0x100).any()                                      # the case is there for the clamp
+
+
+def test_plane_wave_kernel(dsr, cuda):
+    import torch
+    case = Cs.CASES[0]
+    src = Cs.inputs(case)[0].astype(np.complex64)
+    trk = dsr.SphTracker("modal", Cs.SIM_ORDER, Cs.M, Cs.A_MM, Cs.FS)
+    sim = dsr.PlaneWaveSim(trk, 0.6, 0.2)
+    dec = Cs.sim_decomposition()
+    ref = [T.PlaneWaveSimulator(dec, c, 0.6, 0.2) for c in range(T.CHAN)]
+    assert np.abs(sim.coef - np.stack([r.coef for r in ref])).max() <= 1e-13 * np.abs(sim.coef).max()
+    nf = torch.tensor(Cs.NFRAMES, dtype=torch.int32, device=cuda)
+    full = sim.apply(torch.from_numpy(src).to(cuda), nf, full=True).cpu().numpy()
+    half = sim.apply(torch.from_numpy(src).to(cuda), nf).cpu().numpy()
+    assert np.array_equal(half, full[..., :Cs.F])
+    for u in range(Cs.U):
+        for t in range(Cs.TMAX):
+            if t >= Cs.NFRAMES[u]:
+                assert not full[u, :, t].any()
+                continue
+            for c in (0, 7, 31):
+                want = ref[c].next(src[u, t].astype(np.complex128))
+                assert np.abs(full[u, c, t] - want).max() <= 2e-7 * np.abs(want).max()
+            k = np.arange(1, Cs.M // 2)
+            assert np.array_equal(full[u, :, t, Cs.M - k], np.conj(full[u, :, t, k]))
+
+
+@pytest.mark.parametrize("name", ["modal-o3-s0-l4", "spatial-o2-s4-l4", "modal-setV"])
+def test_carried_state(name, dsr, cuda, device_runs):
+    case = Cs.BY_NAME[name]
+    one = device_runs[name]
+    two = run_device(dsr, cuda, case, blocks=[5, 7])
+    for a, b in zip(one, two):
+        assert np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("name", ["modal-o2-s4-l4", "spatial-o3-s6-l1"])
+def test_utterance_independence(name, dsr, cuda, device_runs):
+    case = Cs.BY_NAME[name]
+    pos, pos64, info, state = device_runs[name]
+    for u in (1, 2):
+        p, p64, i, s = run_device(dsr, cuda, case, users=[u])
+        assert np.array_equal(p64[0], pos64[u]) and np.array_equal(i[0], info[u]) and np.array_equal(p[0], pos[u]) and np.array_equal(s[0], state[u])
+
+
+@pytest.mark.parametrize("kind", ["modal", "spatial"])
+def test_stream_classes(kind, dsr, cuda):
+    """the stream classes pulled frame by frame over PlaneWaveSimulatorPtr channels equal the batch call on the same data"""
+    import torch
+    from dsr.btk import beamformer as B
+    from dsr.btk.stream import PyVectorComplexFeatureStreamPtr
+
+    class Src:
+        def __init__(self, rows):
+            self.rows = rows
+
+        def size(self):
+            return Cs.M
+
+        def reset(self):
+            pass
+
+        def __iter__(self):
+            return iter(self.rows)
+
+    Tn = 6
+    src = Cs.inputs(Cs.CASES[0])[0][0, :Tn].astype(np.complex64)
+    rows = np.zeros((Tn, Cs.M), np.complex128); rows[:, :Cs.F] = src
+    simdec = B.ModalDecompositionPtr(Cs.SIM_ORDER, Cs.M, Cs.A_MM, Cs.FS)
+    dec = (B.ModalDecompositionPtr if kind == "modal" else B.SpatialDecompositionPtr)(2, Cs.M, Cs.A_MM, Cs.FS, 4)
+    trk = (B.ModalSphericalArrayTrackerPtr if kind == "modal" else B.SpatialSphericalArrayTrackerPtr)(dec, Cs.SIGMA2_U, Cs.SIGMA2_V, Cs.SIGMA2_INIT, 2)
+    chans = [B.PlaneWaveSimulatorPtr(PyVectorComplexFeatureStreamPtr(Src(rows)), simdec, c, 0.65, 0.25) for c in range(32)]
+    for c in chans:
+        trk.setChannel(c)
+    first = np.stack([np.array(trk.next()) for _ in range(Tn)])
+    with pytest.raises(StopIteration):
+        trk.next()
+    # the batch call on the same data
+    bt = dsr.SphTracker(kind, 2, Cs.M, Cs.A_MM, Cs.FS, 4, Cs.SIGMA2_U, Cs.SIGMA2_V, Cs.SIGMA2_INIT, 2)
+    X = dsr.PlaneWaveSim(dsr.SphTracker("modal", Cs.SIM_ORDER, Cs.M, Cs.A_MM, Cs.FS), 0.65, 0.25).apply(torch.from_numpy(src[None]).to(cuda))
+    pos, _, info = bt.run(X)
+    assert np.array_equal(first, pos.cpu().numpy()[0]) and (info.cpu().numpy() & 0xff).all()
+    # reset keeps the filter's state (the next pass starts where the first ended); nextSpeaker restores the initial output
+    trk.reset()
+    again = np.stack([np.array(trk.next()) for _ in range(Tn)])
+    assert not np.array_equal(again, first)
+    trk.nextSpeaker()
+    third = np.stack([np.array(trk.next()) for _ in range(Tn)])
+    assert np.array_equal(third, first)

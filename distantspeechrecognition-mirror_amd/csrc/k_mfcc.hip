@@ -339,6 +339,9 @@ __global__ __launch_bounds__(256) void k_mfcc_frames_w(MfccDev P, int melCoefN, 
 }
 
 // mode 1: batch mean/variance (two sequential passes in fp32, as _calcMeanVariance), mode 2: run-on.
+// The deviation is sqrtf(), the correctly rounded square root (the reference's sqrt(float)): __fsqrt_rn is the 1-ulp native instruction in
+// this toolchain, and rounded correctly only where the compiler happens to hoist it out of a loop (it did in the batch branch below, and
+// not in the run-on branch or in k_cmn_lds: with devNormFactor > 0 those two were an ulp off the reference in about a tenth of the dimensions).
 // wgt (optional): per-frame weights [U][Tmax * wStride], element 0 of the weight stream's frames (MeanSubtractionFeature(src, weight, ...), feature.cc:2577-2707)
 __global__ void k_cmn(const float* __restrict__ cep, const int* __restrict__ Tarr, int U, int Tmax, int N, int mode,
                       double devNormFactor, float* __restrict__ out, const float* __restrict__ wgt, int wStride)
@@ -361,7 +364,7 @@ __global__ void k_cmn(const float* __restrict__ cep, const int* __restrict__ Tar
     }
     for (int t = 0; t < T; t++) {
       float r = __fsub_rn(x[(long) t * N], m);
-      if (devNormFactor > 0.0) { float va = v; if (va < 0.0001f) va = 0.0001f; r = (float) ((double) r / __dmul_rn(devNormFactor, (double) __fsqrt_rn(va))); }
+      if (devNormFactor > 0.0) { float va = v; if (va < 0.0001f) va = 0.0001f; r = (float) ((double) r / __dmul_rn(devNormFactor, (double) sqrtf(va))); }
       o[(long) t * N] = r;
     }
   } else {
@@ -379,7 +382,7 @@ __global__ void k_cmn(const float* __restrict__ cep, const int* __restrict__ Tar
       framesN++;
       }
       float r = __fsub_rn(f, m);
-      if (devNormFactor > 0.0) { float va = sm; if (va < 0.0001f) va = 0.0001f; r = (float) ((double) r / __dmul_rn(devNormFactor, (double) __fsqrt_rn(va))); }
+      if (devNormFactor > 0.0) { float va = sm; if (va < 0.0001f) va = 0.0001f; r = (float) ((double) r / __dmul_rn(devNormFactor, (double) sqrtf(va))); }
       o[(long) t * N] = r;
     }
   }
@@ -419,7 +422,7 @@ __global__ __launch_bounds__(256) void k_cmn_lds(const float* __restrict__ cep, 
   for (int j = threadIdx.x; j < n; j += 256) {
     const int i = j % N;
     float r = __fsub_rn(xs[j], s_m[i]);
-    if (devNormFactor > 0.0) r = (float) ((double) r / __dmul_rn(devNormFactor, (double) __fsqrt_rn(s_d[i])));
+    if (devNormFactor > 0.0) r = (float) ((double) r / __dmul_rn(devNormFactor, (double) sqrtf(s_d[i])));
     o[j] = r;
   }
   for (int j = n + threadIdx.x; j < Tmax * N; j += 256) o[j] = 0.0f;
@@ -671,6 +674,47 @@ void build_dct(int ncep, int nmel, int type, std::vector<float>& dct)
 void op_cmn(const float* in, int T, int N, int mode, double devNormFactor, float* out, hipStream_t st, const float* wgt, int wStride)
 { if (T > 0) hipLaunchKernelGGL(k_cmn, dim3(cdiv(N, 64)), dim3(64), 0, st, in, (const int*) nullptr, 1, T, N, mode, devNormFactor, out, wgt, wStride); }
 
+// The three dispatch decisions of dsr_mfcc_run and the sizes they rest on, in one place: dsr_mfcc_run launches what this returns and
+// dsr_mfcc_paths / dsr_mfcc_cfg_paths report it.  The DSR_*_PLAIN switches are read on every call.
+struct MfccPaths {
+  int frames, cmn, lda;                 // DSR_MFCC_FRAMES_*, DSR_MFCC_CMN_*, DSR_MFCC_LDA_*
+  int FPB;                              // plain frames kernel: frames (wavefronts) per workgroup
+  int FB, nG;                           // k_splice_lda: frames per workgroup; k_splice_lda_b: groups of outDim threads
+  size_t lds, ldsW, ldsC, lds2, ldsB;   // dynamic LDS of k_mfcc_frames, k_mfcc_frames_w, k_cmn_lds, k_splice_lda, k_splice_lda_b
+};
+constexpr size_t kCuLds = 160 * 1024;   // LDS of a CU: the most one workgroup can ask for
+constexpr int kLdaFT = 8;               // frames a thread of k_splice_lda_b owns
+
+static MfccPaths mfcc_paths(const dsr_mfcc_cfg& c, int melCoefN, int Tmax)
+{
+  MfccPaths r;
+  // plain frames kernel: a wavefront per frame, as many of them (at most four) as the CU's LDS holds ping-pong buffers for
+  const size_t perFrame = (size_t) 2 * (c.fftLen / 2) * sizeof(double2);
+  r.FPB = (int) std::min<size_t>(4, kCuLds / perFrame);
+  r.lds = r.FPB * perFrame;
+  // tables in LDS + wave-private frames when the lot fits beside three more workgroups on a CU; the plain kernel otherwise (and on request)
+  r.ldsW = (size_t) c.fftLen * sizeof(double2) * (1 + 4) + (size_t) c.blockLen * sizeof(double)
+           + ((size_t) melCoefN + (size_t) c.ncep * c.filterN + 3 * (size_t) c.filterN) * sizeof(float);
+  const bool plainOnly = getenv("DSR_MFCC_PLAIN") != nullptr;
+  r.frames = (!plainOnly && r.ldsW <= 52 * 1024 && (c.fftLen == 256 || c.fftLen == 512)) ? DSR_MFCC_FRAMES_W : DSR_MFCC_FRAMES_PLAIN;
+  r.ldsC = sizeof(float) * (size_t) Tmax * c.ncep;
+  const bool plainCmn = getenv("DSR_CMN_PLAIN") != nullptr;
+  if (c.cmnMode == 0) r.cmn = DSR_MFCC_CMN_NONE;
+  else r.cmn = (c.cmnMode == 1 && c.ncep <= 64 && r.ldsC <= 64 * 1024 && !plainCmn) ? DSR_MFCC_CMN_LDS : DSR_MFCC_CMN_PLAIN;
+  const int Np = (c.ncep + 3) & ~3, S2 = 2 * c.delta + 1;
+  r.FB = getenv("DSR_LDA_FB") ? atoi(getenv("DSR_LDA_FB")) : 64;                      // frames per workgroup (the transform is staged once per workgroup)
+  if (r.FB < 1) r.FB = 64;
+  r.lds2 = c.outDim > 0 ? sizeof(float) * ((size_t) c.outDim * S2 * Np + (size_t) (r.FB + 2 * c.delta) * Np) : 16;
+  // register-blocked product when a group of outDim threads fits the workgroup and the pitched transform fits LDS beside two more workgroups
+  r.nG = c.outDim > 0 ? 256 / c.outDim : 0;
+  r.ldsB = c.outDim > 0 ? sizeof(float) * ((size_t) c.outDim * (S2 * Np + 4) + (size_t) (r.nG * kLdaFT + 2 * c.delta) * Np) : 0;
+  const bool plainLda = getenv("DSR_LDA_PLAIN") != nullptr;
+  if (c.outDim <= 0) r.lda = DSR_MFCC_LDA_SPLICE;
+  else if (r.nG >= 1 && r.ldsB <= 52 * 1024 && !plainLda) r.lda = DSR_MFCC_LDA_B;
+  else r.lda = r.lds2 <= kCuLds ? DSR_MFCC_LDA_PLAIN : DSR_MFCC_LDA_TOO_LARGE;
+  return r;
+}
+
 }  // namespace dsr
 
 using namespace dsr;
@@ -735,6 +779,29 @@ int dsr_mfcc_frames(const dsr_mfcc* p, int nsamp)
 }
 int dsr_mfcc_out_dim(const dsr_mfcc* p) { return p->c.outDim > 0 ? p->c.outDim : (2 * p->c.delta + 1) * p->c.ncep; }
 
+static void mfcc_paths_out(const MfccPaths& r, int paths[3]) { paths[0] = r.frames; paths[1] = r.cmn; paths[2] = r.lda; }
+
+dsr_status dsr_mfcc_paths(const dsr_mfcc* p, int Tmax, int paths[3])
+{
+  return guard([&] {
+    if (!p || !paths) throw Error(DSR_E_PARAMETER, "null argument");
+    mfcc_paths_out(mfcc_paths(p->c, p->melCoefN, Tmax), paths);
+  });
+}
+
+dsr_status dsr_mfcc_cfg_paths(const dsr_mfcc_cfg* cfg, int Tmax, int paths[3], int64_t lds[4])
+{
+  return guard([&] {
+    if (!cfg || !paths) throw Error(DSR_E_PARAMETER, "null argument");
+    std::vector<int> ms, mc, mo; std::vector<float> mco; int nReq = 0;
+    build_mel(*cfg, ms, mc, mo, mco, nReq);
+    if (mco.empty()) mco.push_back(0.f);
+    const MfccPaths r = mfcc_paths(*cfg, (int) mco.size(), Tmax);
+    mfcc_paths_out(r, paths);
+    if (lds) { lds[0] = (int64_t) r.ldsW; lds[1] = (int64_t) r.ldsC; lds[2] = (int64_t) r.ldsB; lds[3] = (int64_t) r.lds2; }
+  });
+}
+
 dsr_status dsr_mfcc_run(dsr_mfcc* p, const float* y, const int32_t* nsamp, int U, int64_t sampStride, int Tmax, int stage,
                         float* feat, void* stream)
 {
@@ -755,25 +822,23 @@ dsr_status dsr_mfcc_run(dsr_mfcc* p, const float* y, const int32_t* nsamp, int U
     P.ham = p->d_ham.p; P.tw = p->d_tw.p; P.vStart = p->d_vStart.p; P.vCount = p->d_vCount.p; P.vOff = p->d_vOff.p;
     P.vCoef = p->d_vCoef.p; P.vDiv = p->d_vDiv.p; P.mStart = p->d_mStart.p; P.mCount = p->d_mCount.p; P.mOff = p->d_mOff.p;
     P.mCoef = p->d_mCoef.p; P.dct = p->d_dct.p;
-    const int FPB = 4;
-    const size_t lds = (size_t) FPB * 2 * (c.fftLen / 2) * sizeof(double2);
+    const MfccPaths pa = mfcc_paths(c, p->melCoefN, Tmax);
+    const int FPB = pa.FPB;
+    const size_t lds = pa.lds;
     dim3 grid(cdiv(Tmax, FPB), U);
     float* powOut = stage == 4 ? feat : nullptr; float* lmOut = stage == 3 ? feat : nullptr;
 #define LAUNCH(FN) { DSR_HIP(hipFuncSetAttribute((const void*) k_mfcc_frames<FN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); \
     hipLaunchKernelGGL(k_mfcc_frames<FN>, grid, dim3(64 * FPB), lds, st, P, y, nsamp, (long) sampStride, Tmax, cepOut, powOut, lmOut); }
-    // tables in LDS + wave-private frames when the lot fits beside three more workgroups on a CU; the plain kernel otherwise (and on request)
 #ifndef DSR_MFCC_FW
 #define DSR_MFCC_FW 8
 #endif
     constexpr int FW = DSR_MFCC_FW;
-    const size_t ldsW = (size_t) c.fftLen * sizeof(double2) * (1 + 4) + (size_t) c.blockLen * sizeof(double)
-                        + ((size_t) p->melCoefN + (size_t) c.ncep * c.filterN + 3 * (size_t) c.filterN) * sizeof(float);
-    static const bool plainOnly = getenv("DSR_MFCC_PLAIN") != nullptr;
-    if (!plainOnly && ldsW <= 52 * 1024 && (c.fftLen == 256 || c.fftLen == 512 || c.fftLen == 1024)) {
+    const size_t ldsW = pa.ldsW;
+    if (pa.frames == DSR_MFCC_FRAMES_W) {
       dim3 gridW(cdiv(Tmax, 4 * FW), U);
 #define LAUNCHW(FN) { DSR_HIP(hipFuncSetAttribute((const void*) k_mfcc_frames_w<FN, FW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsW)); \
     hipLaunchKernelGGL((k_mfcc_frames_w<FN, FW>), gridW, dim3(256), ldsW, st, P, p->melCoefN, y, nsamp, (long) sampStride, Tmax, cepOut, powOut, lmOut); }
-      if (c.fftLen == 256) LAUNCHW(256) else if (c.fftLen == 512) LAUNCHW(512) else LAUNCHW(1024)
+      if (c.fftLen == 256) LAUNCHW(256) else LAUNCHW(512)
 #undef LAUNCHW
     } else
     switch (c.fftLen) { case 32: LAUNCH(32) break; case 64: LAUNCH(64) break; case 128: LAUNCH(128) break; case 256: LAUNCH(256) break;
@@ -785,9 +850,8 @@ dsr_status dsr_mfcc_run(dsr_mfcc* p, const float* y, const int32_t* nsamp, int U
     float* cmnOut = cepOut;
     if (c.cmnMode != 0) {
       cmnOut = (stage == 2) ? feat : (p->w_cmn.reserve(nT * c.ncep), p->w_cmn.p);
-      const size_t ldsC = sizeof(float) * (size_t) Tmax * c.ncep;
-      static const bool plainCmn = getenv("DSR_CMN_PLAIN") != nullptr;
-      if (c.cmnMode == 1 && c.ncep <= 64 && ldsC <= 64 * 1024 && !plainCmn) {
+      const size_t ldsC = pa.ldsC;
+      if (pa.cmn == DSR_MFCC_CMN_LDS) {
         DSR_HIP(hipFuncSetAttribute((const void*) k_cmn_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsC));
         hipLaunchKernelGGL(k_cmn_lds, dim3(U), dim3(256), ldsC, st, cepOut, p->d_T.p, Tmax, c.ncep, c.devNormFactor, cmnOut);
       } else
@@ -795,16 +859,10 @@ dsr_status dsr_mfcc_run(dsr_mfcc* p, const float* y, const int32_t* nsamp, int U
       DSR_HIP(hipGetLastError());
     } else if (stage == 2) { DSR_HIP(hipMemcpyAsync(feat, cepOut, nT * c.ncep * sizeof(float), hipMemcpyDeviceToDevice, st)); }
     if (stage == 2) return;
-    const int Np = (c.ncep + 3) & ~3, S2 = 2 * c.delta + 1;
-    const int FB = getenv("DSR_LDA_FB") ? atoi(getenv("DSR_LDA_FB")) : 64;           // frames per workgroup (the transform is staged once per workgroup)
-    const size_t lds2 = c.outDim > 0 ? sizeof(float) * ((size_t) c.outDim * S2 * Np + (size_t) (FB + 2 * c.delta) * Np) : 16;
-    if (lds2 > 160 * 1024) throw Error(DSR_E_DIMENSION, "linear transform needs %zu bytes of LDS", lds2);
-    // register-blocked product when a group of outDim threads fits the workgroup and the pitched transform fits LDS beside two more workgroups
-    constexpr int FT = 8;
-    const int nG = c.outDim > 0 ? 256 / c.outDim : 0;
-    const size_t ldsB = c.outDim > 0 ? sizeof(float) * ((size_t) c.outDim * (S2 * Np + 4) + (size_t) (nG * FT + 2 * c.delta) * Np) : 0;
-    static const bool plainLda = getenv("DSR_LDA_PLAIN") != nullptr;
-    if (c.outDim > 0 && nG >= 1 && ldsB <= 52 * 1024 && !plainLda) {
+    if (pa.lda == DSR_MFCC_LDA_TOO_LARGE) throw Error(DSR_E_DIMENSION, "linear transform needs %zu bytes of LDS", pa.lds2);
+    constexpr int FT = kLdaFT;
+    const int FB = pa.FB, nG = pa.nG; const size_t lds2 = pa.lds2, ldsB = pa.ldsB;
+    if (pa.lda == DSR_MFCC_LDA_B) {
       const int FBb = nG * FT; const int NB = 4;
       DSR_HIP(hipFuncSetAttribute((const void*) k_splice_lda_b<FT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsB));
       hipLaunchKernelGGL(k_splice_lda_b<FT>, dim3(cdiv(Tmax, FBb * NB), U), dim3(256), ldsB, st, cmnOut, p->d_T.p, Tmax, c.ncep, c.delta, c.outDim, p->d_lda.p, feat, nG, NB);

@@ -1556,6 +1556,22 @@ class LpcEnvelope:
         return out
 
 
+MFCC_FRAMES_PLAIN, MFCC_FRAMES_W = 0, 1
+MFCC_CMN_NONE, MFCC_CMN_PLAIN, MFCC_CMN_LDS = 0, 1, 2
+MFCC_LDA_TOO_LARGE, MFCC_LDA_SPLICE, MFCC_LDA_PLAIN, MFCC_LDA_B = -1, 0, 1, 2
+
+
+def mfcc_cfg_paths(Tmax, **kw):
+    """-> ((frames, cmn, lda), dict of the LDS bytes the gates compare) for the configuration Mfcc(**kw) would have; needs no device"""
+    L = load()
+    cfg = MfccCfg(); L.dsr_mfcc_default_cfg(C.byref(cfg))
+    for k, v in kw.items():
+        setattr(cfg, k, v)
+    out = (C.c_int * 3)(); lds = (C.c_int64 * 4)()
+    check(L.dsr_mfcc_cfg_paths(C.byref(cfg), int(Tmax), out, lds))
+    return tuple(out), dict(zip(("ldsW", "ldsC", "ldsB", "lds2"), lds))
+
+
 class Mfcc:
     def __init__(self, lda=None, **kw):
         L = load()
@@ -1575,6 +1591,12 @@ class Mfcc:
 
     def frames(self, nsamp):
         return _lib.dsr_mfcc_frames(self.h, int(nsamp))
+
+    def paths(self, Tmax):
+        """(frames, cmn, lda) kernels dsr_mfcc_run launches for a batch of Tmax frames: MFCC_FRAMES_*, MFCC_CMN_*, MFCC_LDA_*"""
+        out = (C.c_int * 3)()
+        check(_lib.dsr_mfcc_paths(self.h, int(Tmax), out))
+        return tuple(out)
 
     def run(self, y, nsamp=None, stage=0):
         """y: cuda float32 [U][N] -> float32 [U][Tmax][dim]"""

@@ -719,6 +719,21 @@ int dsr_mfcc_out_dim(const dsr_mfcc*);
    stage: 0 = final, 1 = cepstra before CMN, 2 = after CMN, 3 = log-mel, 4 = power (as float) */
 dsr_status dsr_mfcc_run(dsr_mfcc*, const float* y_dev, const int32_t* nsamp_dev, int U, int64_t sampStride,
                         int Tmax, int stage, float* feat_dev, void* stream);
+/* Which kernel each of the three stages of dsr_mfcc_run launches for a batch of Tmax frames: paths[0] the frames kernel, paths[1] the
+   mean normalisation, paths[2] splice + linear transform.  dsr_mfcc_run takes its decisions from the same helper.  The switches
+   DSR_MFCC_PLAIN, DSR_CMN_PLAIN and DSR_LDA_PLAIN (set to anything: the plain kernel of the pair) are read on every call. */
+enum { DSR_MFCC_FRAMES_PLAIN = 0,      /* k_mfcc_frames<fftLen> */
+       DSR_MFCC_FRAMES_W = 1 };        /* k_mfcc_frames_w<fftLen, 8>: fftLen 256 / 512 and tables within 52 KB of LDS */
+enum { DSR_MFCC_CMN_NONE = 0, DSR_MFCC_CMN_PLAIN = 1,   /* k_cmn */
+       DSR_MFCC_CMN_LDS = 2 };         /* k_cmn_lds: batch mode, ncep <= 64, Tmax * ncep * 4 <= 64 KB */
+enum { DSR_MFCC_LDA_TOO_LARGE = -1,    /* the transform does not fit the LDS of a CU: dsr_mfcc_run returns DSR_E_DIMENSION at stage 0 */
+       DSR_MFCC_LDA_SPLICE = 0,        /* k_splice_lda without a transform (outDim == 0) */
+       DSR_MFCC_LDA_PLAIN = 1,         /* k_splice_lda */
+       DSR_MFCC_LDA_B = 2 };           /* k_splice_lda_b<8>: outDim <= 256 and the pitched transform within 52 KB of LDS */
+dsr_status dsr_mfcc_paths(const dsr_mfcc*, int Tmax, int paths[3]);
+/* the same from a configuration alone (no device needed); lds (optional): the bytes of LDS the four gates compare --
+   k_mfcc_frames_w's tables and buffers, k_cmn_lds's cepstra, k_splice_lda_b's and k_splice_lda's transform and rows */
+dsr_status dsr_mfcc_cfg_paths(const dsr_mfcc_cfg*, int Tmax, int paths[3], int64_t lds[4]);
 
 /* =====================================================================================
  * 4. Diagonal-covariance GMM scoring

@@ -135,6 +135,20 @@ struct LpcOp : dsr_stream {         // WarpMVDR/BurgMVDR/WarpLPC/BurgLPC feature
     if (nFrames > 0) ok(dsr_lpc_run(plan, ups[0]->d<float>(), nFrames, d<double>(), S0));
   }
 };
+struct WtMvdrOp : dsr_stream {      // WarpedTwiceMVDRFeature (lpc.h:205-246, lpc.cc:409-468)
+  dsr_wtmvdr* plan = nullptr;
+  ~WtMvdrOp() override { if (plan) dsr_wtmvdr_destroy(plan); }
+  void compute() override {
+    alloc(ups[0]->nFrames);
+    if (nFrames > 0) ok(dsr_wtmvdr_run(plan, ups[0]->d<float>(), nullptr, nFrames, d<double>(), nullptr, nullptr, S0));
+  }
+};
+struct SpecSmoothOp : dsr_stream {  // SpectralSmoothing (lpc.h:342-358, lpc.cc:485-529): ups[0] = adjustTo, ups[1] = adjustFrom
+  void compute() override {
+    alloc(shortest(this, 0, 2));
+    if (nFrames > 0) ok(dsr_specsmooth_run(ups[0]->d<double>(), ups[1]->d<double>(), nFrames, size_, d<double>(), S0));
+  }
+};
 struct CmnOp : dsr_stream {          // MeanSubtractionFeature(src, weight, devNormFactor, runon): ups[1] (optional) = the weight stream, element 0 of each frame
   int mode; double dnf;
   void compute() override {
@@ -1423,6 +1437,25 @@ dsr_status dsr_lpc_feature_create(dsr_stream* src, int order, int correlate, flo
     dsr_lpc* plan = nullptr;
     ok(dsr_lpc_create(src->size_, order, correlate, warp, method, kind, &plan));
     LpcOp* s = mk<LpcOp>(name, kind ? "LPC" : "MVDR", src->size_ / 2 + 1, DSR_T_DOUBLE); s->plan = plan; s->add_up(src); *out = s;
+  });
+}
+dsr_status dsr_wtmvdr_feature_create(dsr_stream* src, int order, int correlate, float warp, int warpFactorFixed, float sensibility, const char* name,
+                                     dsr_stream** out)
+{
+  return guard([&] {
+    need(src, DSR_T_FLOAT, "WarpedTwiceMVDRFeature");
+    dsr_wtmvdr* plan = nullptr;
+    ok(dsr_wtmvdr_create(src->size_, order, correlate, warp, warpFactorFixed, sensibility, &plan));
+    WtMvdrOp* s = mk<WtMvdrOp>(name, "WTMVDR", src->size_ / 2 + 1, DSR_T_DOUBLE); s->plan = plan; s->add_up(src); *out = s;
+  });
+}
+dsr_status dsr_spectral_smoothing_create(dsr_stream* adjustTo, dsr_stream* adjustFrom, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    need(adjustTo, DSR_T_DOUBLE, "SpectralSmoothing"); need(adjustFrom, DSR_T_DOUBLE, "SpectralSmoothing");
+    if (adjustTo->size_ != adjustFrom->size_) throw Error(DSR_E_DIMENSION, "Feature sizes (%d vs. %d) do not match.", adjustTo->size_, adjustFrom->size_);   // lpc.cc:476-477
+    if (adjustTo->size_ < 2) throw Error(DSR_E_PARAMETER, "SpectralSmoothing needs at least 2 coefficients, got %d", adjustTo->size_);
+    SpecSmoothOp* s = mk<SpecSmoothOp>(name, "Spectral Smoothing", adjustTo->size_, DSR_T_DOUBLE); s->add_up(adjustTo); s->add_up(adjustFrom); *out = s;
   });
 }
 dsr_status dsr_storage_create(dsr_stream* src, const char* name, dsr_stream** out)

@@ -1556,6 +1556,45 @@ class LpcEnvelope:
         return out
 
 
+class WtMvdrEnvelope:
+    """WarpedTwiceMVDRFeature envelopes of windowed frames, lpc.h:205-246, lpc.cc:212-468."""
+
+    def __init__(self, dim, order=60, correlate=0, warp=0.0, warp_factor_fixed=False, sensibility=0.1):
+        L = load(); self.h = vp(); self.dim = dim
+        check(L.dsr_wtmvdr_create(dim, order, correlate, warp, int(bool(warp_factor_fixed)), sensibility, C.byref(self.h)))
+
+    def __del__(self):
+        if _lib is not None and getattr(self, "h", None):
+            _lib.dsr_wtmvdr_destroy(self.h)
+
+    def run(self, frames, warps=None, want_pa=False):
+        """frames: cuda float32 [T][dim], warps: cuda float32 [T] (each frame's first-stage warp) or None -> float64 [T][dim/2+1];
+        with want_pa also PA float32 [T][dim+1] and rewarp float32 [T]"""
+        import torch
+        T, dim = frames.shape
+        assert dim == self.dim and frames.dtype == torch.float32 and frames.is_contiguous()
+        assert warps is None or (warps.dtype == torch.float32 and warps.numel() == T and warps.is_contiguous())
+        out = torch.zeros((T, dim // 2 + 1), dtype=torch.float64, device=frames.device)
+        pa = torch.zeros((T, dim + 1), dtype=torch.float32, device=frames.device) if want_pa else None
+        rw = torch.zeros((T,), dtype=torch.float32, device=frames.device) if want_pa else None
+        check(_lib.dsr_wtmvdr_run(self.h, _dev(frames), _dev(warps) if warps is not None else None, T, _dev(out),
+                                  _dev(pa) if want_pa else None, _dev(rw) if want_pa else None, cur_stream()))
+        return (out, pa, rw) if want_pa else out
+
+
+def spectral_smoothing(to, frm):
+    """SpectralSmoothing::next on a batch (lpc.cc:485-529): to, frm cuda float64 [T][size] -> float64 [T][size]"""
+    import torch
+    load()
+    if tuple(to.shape) != tuple(frm.shape):
+        raise DsrError(E_DIMENSION, "Feature sizes (%d vs. %d) do not match." % (to.shape[-1], frm.shape[-1]))
+    assert to.dtype == torch.float64 and frm.dtype == torch.float64 and to.is_contiguous() and frm.is_contiguous()
+    T, size = to.shape
+    out = torch.zeros_like(to)
+    check(_lib.dsr_specsmooth_run(_dev(to), _dev(frm), T, size, _dev(out), cur_stream()))
+    return out
+
+
 MFCC_FRAMES_PLAIN, MFCC_FRAMES_W = 0, 1
 MFCC_CMN_NONE, MFCC_CMN_PLAIN, MFCC_CMN_LDS = 0, 1, 2
 MFCC_LDA_TOO_LARGE, MFCC_LDA_SPLICE, MFCC_LDA_PLAIN, MFCC_LDA_B = -1, 0, 1, 2

@@ -124,6 +124,22 @@ class BurgLPCFeaturePtr(_LpcBase):
     _method = 1; _kind = 1; _dflt = "LPC"
 
 
+class WarpedTwiceMVDRFeaturePtr(FeatureStreamPtr):
+    """lpc.h:205-246, feature.i:1326: the warped MVDR envelope re-warped by a fixed or per-frame amount."""
+
+    def __init__(self, src, order=60, correlate=0, warp=0.0, warpFactorFixed=False, sensibility=0.1, nm="WTMVDR"):
+        h, _ = _new(lib().dsr_wtmvdr_feature_create, src._h, int(order), int(correlate), float(warp), int(bool(warpFactorFixed)), float(sensibility), _b(nm))
+        FeatureStreamPtr.__init__(self, h, keep=(src,))
+
+
+class SpectralSmoothingPtr(FeatureStreamPtr):
+    """lpc.h:342-358, feature.i:1409: adjustTo scaled to the smoothed peak of adjustFrom."""
+
+    def __init__(self, adjustTo, adjustFrom, nm="Spectral Smoothing"):
+        h, _ = _new(lib().dsr_spectral_smoothing_create, adjustTo._h, adjustFrom._h, _b(nm))
+        FeatureStreamPtr.__init__(self, h, keep=(adjustTo, adjustFrom))
+
+
 class StorageFeaturePtr(_unary(lambda *a: lib().dsr_storage_create(*a), "Storage")):
     def _args(self, src):
         return ()

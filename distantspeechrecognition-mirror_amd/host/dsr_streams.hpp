@@ -162,6 +162,18 @@ DSR_LPC_OP(BurgMVDRFeature, 1, 0, "MVDR")
 DSR_LPC_OP(WarpLPCFeature, 0, 1, "LPC")
 DSR_LPC_OP(BurgLPCFeature, 1, 1, "LPC")
 #undef DSR_LPC_OP
+// WarpedTwiceMVDRFeature (lpc.h:205-246) and SpectralSmoothing (lpc.h:342-358)
+class WarpedTwiceMVDRFeature : public VectorFeatureStream {
+ public: WarpedTwiceMVDRFeature(const VectorFloatFeatureStreamPtr& src, unsigned order = 60, unsigned correlate = 0, float warp = 0.0, bool warpFactorFixed = false,
+                                float sensibility = 0.1, const String& nm = "WTMVDR")
+  : _s(src) { DSR_OP(WarpedTwiceMVDRFeature, double, dsr_wtmvdr_feature_create(src->handle(), (int) order, (int) correlate, warp, warpFactorFixed, sensibility, nm.c_str(), &h)) }
+ private: VectorFloatFeatureStreamPtr _s;
+};
+class SpectralSmoothing : public VectorFeatureStream {
+ public: SpectralSmoothing(const VectorFeatureStreamPtr& adjustTo, const VectorFeatureStreamPtr& adjustFrom, const String& nm = "Spectral Smoothing")
+  : _to(adjustTo), _from(adjustFrom) { DSR_OP(SpectralSmoothing, double, dsr_spectral_smoothing_create(adjustTo->handle(), adjustFrom->handle(), nm.c_str(), &h)) }
+ private: VectorFeatureStreamPtr _to, _from;
+};
 
 // ---- btk/localization/localization.h:118-218 and btk/TDEstimator/CCTDE.h:60-101.  The reference's gsl vectors are pointers to the items here:
 // calculate() takes fftLen complex bins a spectrum, the getters return pointers into the object's own buffers (a null pointer where the

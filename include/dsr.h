@@ -1258,12 +1258,38 @@ dsr_status dsr_wpe_multi_continue(const float* Y_dev, const int32_t* nframes_dev
  *     method 0 = WarpFeature (warped autocorrelation + Levinson-Durbin), 1 = BurgFeature;
  *     kind 0 = MVDR envelope, 1 = LPC envelope.  frames_dev [T][dim] fp32 (the Hamming-windowed
  *     blocks) -> out_dev [T][dim/2+1] fp64.  order >= dim/2+1 => DSR_E_PARAMETER (lpc.h:126-127).
+ *     Below them the header's other two operators: WarpedTwiceMVDRFeature and SpectralSmoothing.
  * ===================================================================================== */
 typedef struct dsr_lpc dsr_lpc;
 dsr_status dsr_lpc_create(int dim, int order, int correlate, float warp, int method, int kind, dsr_lpc** out);
 void       dsr_lpc_destroy(dsr_lpc*);
 int        dsr_lpc_size(const dsr_lpc*);
 dsr_status dsr_lpc_run(dsr_lpc*, const float* frames_dev, int64_t T, double* out_dev, void* stream);
+
+/* WarpedTwiceMVDRFeature (btk/feature/lpc.h:205-246, lpc.cc:212-468): the warped MVDR envelope whose coefficient sequence is warped a second
+ * time, by `_rewarp`, through a chain of dim first-order all-pass stages (trans_longchain, lpc.cc:374-389).  warpFactorFixed: _rewarp follows
+ * from warp and sensibility alone (lpc.cc:352-355); otherwise from |R1/R0| of the frame's first `correlate` samples (lpc.cc:392-407,425-428);
+ * correlate < 10 means dim (lpc.cc:348).  order >= dim/2+1 => DSR_E_PARAMETER (lpc.cc:349-350); correlate > dim => DSR_E_PARAMETER (R1R0 would
+ * read past the frame).  The fp32 part is the reference's operation for operation, double promotions included, with two departures: R holds the
+ * order+2 values that autoCorrelation writes (the reference allocates order+1, lpc.cc:214,260), and the weights of PC (lpc.cc:436) are signed
+ * as in MVDRFeature (lpc.h:156) where the reference's unsigned expression wraps the negative ones around.
+ * run: frames_dev [T][dim] fp32 -> out_dev [T][dim/2+1] fp64.  warp_dev [T] (or NULL: the plan's warp) is each frame's first-stage warp, so
+ * that one batch can hold several speakers.  pa_dev [T][dim+1] and rewarp_dev [T] (either may be NULL) receive the re-warped sequence
+ * PA[0..dim] before fftPower (lpc.cc:447-448) and the frame's _rewarp. */
+typedef struct dsr_wtmvdr dsr_wtmvdr;
+dsr_status dsr_wtmvdr_create(int dim, int order, int correlate, float warp, int warpFactorFixed, float sensibility, dsr_wtmvdr** out);
+void       dsr_wtmvdr_destroy(dsr_wtmvdr*);
+int        dsr_wtmvdr_size(const dsr_wtmvdr*);
+dsr_status dsr_wtmvdr_run(dsr_wtmvdr*, const float* frames_dev, const float* warp_dev, int64_t T, double* out_dev, float* pa_dev, float* rewarp_dev,
+                          void* stream);
+/* measurement (tools/bench_wtmvdr.py): with timing on, dsr_wtmvdr_run brackets its launches with events and waits for them; kernel_ms then gives
+ * the last call's milliseconds in the frame transpose, the autocorrelation/Levinson/PC kernel, the all-pass chain and the transform */
+dsr_status dsr_wtmvdr_set_timing(dsr_wtmvdr*, int on);
+dsr_status dsr_wtmvdr_kernel_ms(const dsr_wtmvdr*, double* ms4);
+/* SpectralSmoothing::next (lpc.h:342-358, lpc.cc:485-529): out = mult * adjust_to, mult = max of the 5-tap smoothed adjust_from over the max of
+ * adjust_to (100 * the former where the latter is below 0.01).  All three [T][size] fp64; out_dev may be adjust_to_dev.  size < 2 =>
+ * DSR_E_PARAMETER (the reference's size()-2 wraps around there, lpc.cc:500,507). */
+dsr_status dsr_specsmooth_run(const double* adjust_to_dev, const double* adjust_from_dev, int64_t T, int size, double* out_dev, void* stream);
 
 /* =====================================================================================
  * 7. Stream/feature-operator API  (FeatureStream<Type,item>::next/reset/size/name/current/isEnd,
@@ -1457,6 +1483,12 @@ dsr_status dsr_log_create(dsr_stream* mel, double m, double a, int sphinxFloorin
 dsr_status dsr_cepstral_create(dsr_stream* mel, int ncep, int type, const char* name, dsr_stream** out);
 /* WarpMVDRFeature / BurgMVDRFeature (kind 0) and WarpLPCFeature / BurgLPCFeature (kind 1), lpc.h:115-128,280-293 */
 dsr_status dsr_lpc_feature_create(dsr_stream* src, int order, int correlate, float warp, int method, int kind, const char* name, dsr_stream** out);
+/* WarpedTwiceMVDRFeature(src, order, correlate, warp, warpFactorFixed, sensibility, nm = "WTMVDR") (lpc.h:205-246, lpc.cc:339-357) */
+dsr_status dsr_wtmvdr_feature_create(dsr_stream* src, int order, int correlate, float warp, int warpFactorFixed, float sensibility, const char* name,
+                                     dsr_stream** out);
+/* SpectralSmoothing(adjustTo, adjustFrom, nm = "Spectral Smoothing") (lpc.h:342-358, lpc.cc:473-478): unequal sizes => DSR_E_DIMENSION; the
+ * stream ends with the shorter of the two */
+dsr_status dsr_spectral_smoothing_create(dsr_stream* adjustTo, dsr_stream* adjustFrom, const char* name, dsr_stream** out);
 dsr_status dsr_storage_create(dsr_stream* src, const char* name, dsr_stream** out);
 dsr_status dsr_mean_subtraction_create(dsr_stream* src, double devNormFactor, int runon, const char* name, dsr_stream** out);
 /* the optional weight stream of MeanSubtractionFeature(src, weight, devNormFactor, runon) (feature.h, feature.cc:2577-2707): element 0 of its frames weighs

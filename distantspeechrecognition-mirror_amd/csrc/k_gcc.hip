@@ -20,11 +20,13 @@
 //                    held value makes the rounds ambiguous).
 //                    fftLen <= 4096 in LDS; longer transforms (allsamples() over a recording) run the same code on a per-workgroup block of
 //                    global memory.
+// The FFT itself (fft_tw_init, fft_run, brev, the split step) lives in fft_lds.h, shared with k_conv.hip.
 // LDS layout of the FFT: real and imaginary parts in separate fp64 arrays, so a half-wave's 32 consecutive elements fill one 256-byte bank
 // row per ds_read_b64; twiddles of the two longest stages come from one table (stride 1 and 2), every shorter stage has a contiguous table
 // of its own, because a power-of-two stride into one table would put a half-wave's twiddles on one bank.  The bit-reversed store that loads
 // the data is conflicted (DESIGN 4.4j gives its cost).
 #include "common.h"
+#include "fft_lds.h"
 #include <cmath>
 
 using namespace dsr;
@@ -175,33 +177,6 @@ __global__ __launch_bounds__(256) void k_gcc_chan(const void* __restrict__ X, co
   if (threadIdx.x == 0) { s.ts[uc] = tsEnd; s.hasN[uc] = hEnd; }
 }
 
-// ---- radix-2 FFT in LDS, shared by k_gcc_corr and k_cctde -----------------------------------------------------------------------------------
-// n points, data in re[] / im[], loaded in bit-reversed order by the caller.  Twiddles exp(+2 pi i j / n): tw[0 .. n/2) serves the stages with
-// half-span h >= n/4; the stage with half-span h < n/4 reads tw[n/2 + h - 1 + k], k < h.  sgn = -1 conjugates them (forward transform).
-__host__ __device__ inline int fft_tw_entries(int n) { return n / 2 + n / 4; }
-__device__ void fft_tw_init(double* twr, double* twi, int n)
-{
-  for (int j = threadIdx.x; j < n / 2; j += blockDim.x) { double sn, cs; sincospi(2.0 * j / n, &sn, &cs); twr[j] = cs; twi[j] = sn; }
-  for (int h = 1; 4 * h < n; h *= 2)
-    for (int k = threadIdx.x; k < h; k += blockDim.x) { double sn, cs; sincospi((double) k / h, &sn, &cs); twr[n / 2 + h - 1 + k] = cs; twi[n / 2 + h - 1 + k] = sn; }
-}
-__device__ void fft_run(double* re, double* im, const double* twr, const double* twi, int n, double sgn)
-{
-  for (int h = 1; h < n; h *= 2) {
-    __syncthreads();
-    for (int j = threadIdx.x; j < n / 2; j += blockDim.x) {
-      const int k = j & (h - 1), i0 = ((j - k) << 1) + k, i1 = i0 + h;
-      const int w = 4 * h >= n ? k * (n / (2 * h)) : n / 2 + h - 1 + k;
-      const double wr = twr[w], wi = sgn * twi[w];
-      const double xr = re[i1], xi = im[i1], tr = xr * wr - xi * wi, ti = xr * wi + xi * wr;
-      const double ar = re[i0], ai = im[i0];
-      re[i0] = ar + tr; im[i0] = ai + ti; re[i1] = ar - tr; im[i1] = ai - ti;
-    }
-  }
-  __syncthreads();
-}
-__device__ __forceinline__ int brev(int k, int logn) { return (int) (__brev((unsigned) k) >> (32 - logn)); }
-
 // ---- findMaximum (localization.cc:1297-1340) as a workgroup reduction ---------------------------------------------------------------------
 // The strict `>` scan over ascending i keeps the first of equal maxima: order (corr descending, i ascending).  maxCorr2 ends as the largest
 // in-window value at any other index: what the running maximum held before the winner, or a later value above it (the two branches).
@@ -266,14 +241,11 @@ __global__ __launch_bounds__(256) void k_gcc_corr(const double2* __restrict__ xs
     __syncthreads();
     // halfComplexPack keeps Re of bins 0 and N/2 only; split step: Z[k] = (X[k] + conj X[n-k]) + i (X[k] - conj X[n-k]) e^{2 pi i k / N}
     for (int k = threadIdx.x; k < n; k += B) {
-      double2 A = Sx[k], Bc = Sx[n - k];
-      if (k == 0) { A.y = 0.0; Bc.y = 0.0; }
-      Bc.y = -Bc.y;
-      const double ex = A.x + Bc.x, ey = A.y + Bc.y, dx = A.x - Bc.x, dy = A.y - Bc.y;
-      double sn, cs; sincospi((double) k / n, &sn, &cs);
-      const double ox = dx * cs - dy * sn, oy = dx * sn + dy * cs;
+      double2 A = Sx[k], Bn = Sx[n - k];
+      if (k == 0) { A.y = 0.0; Bn.y = 0.0; }
+      const double2 z = fft_split_inverse(A, Bn, k, n);
       const int r = brev(k, logn);
-      re[r] = ex - oy; im[r] = ey + ox;
+      re[r] = z.x; im[r] = z.y;
     }
     fft_run(re, im, twr, twi, n, 1.0);
     for (int k = threadIdx.x; k < n; k += B) { re[k] *= inv; im[k] *= inv; }                           // gsl_fft_halfcomplex_radix2_inverse scales by 1/N
@@ -447,7 +419,6 @@ void gcc_upload(dsr_gcc* g)
 // active >= 0: one calculate() call -- that pair alone, bound to the channels (ac1, ac2) for this call
 GPar gpar(const dsr_gcc& g, int U, int T, int xDouble, int smooth, double minDelay, double maxDelay, int active = -1, int ac1 = -1, int ac2 = -1)
 { return GPar{g.kind, U, g.C, g.P, T, g.len, g.N, xDouble, smooth, g.interpolate, active, ac1, ac2, g.alpha, g.beta, g.q, g.sampleRate, minDelay, maxDelay}; }
-int fft_block(int butterflies) { return butterflies < 64 ? 64 : (butterflies > 256 ? 256 : butterflies); }
 
 void gcc_run(dsr_gcc* g, const void* X_dev, int xIsDouble, const int32_t* nframes_dev, const int32_t* sad_dev, const double* timestamp_dev, int smooth,
              double minDelay, double maxDelay, int U, int Tmax, void* state_dev, double* result_dev, int32_t* valid_dev, double* corr_dev,

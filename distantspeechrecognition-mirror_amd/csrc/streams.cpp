@@ -149,6 +149,36 @@ struct SpecSmoothOp : dsr_stream {  // SpectralSmoothing (lpc.h:342-358, lpc.cc:
     if (nFrames > 0) ok(dsr_specsmooth_run(ups[0]->d<double>(), ups[1]->d<double>(), nFrames, size_, d<double>(), S0));
   }
 };
+struct ConvOp : dsr_stream {        // OverlapAdd / OverlapSave (convolution.h:40-104): a plan with one response over the source's blocks
+  dsr_conv* plan = nullptr; DevBuf<float> state;
+  ~ConvOp() override { if (plan) dsr_conv_destroy(plan); }
+  void compute() override {
+    alloc(ups[0]->nFrames);
+    if (nFrames <= 0) return;
+    const size_t sb = dsr_conv_state_bytes(plan, 1);                                 // reset() zeroes the buffer (convolution.cc:166-172)
+    if (sb) { state.reserve(sb / sizeof(float)); ok(dsr_conv_state_init(plan, state.p, 1, S0)); }
+    ok(dsr_conv_apply(plan, ups[0]->d<float>(), nullptr, 1, nFrames, state.p, d<float>(), S0));
+  }
+};
+struct FirOp : dsr_stream {         // FilterFeature (feature.h:1315-1410, feature.cc:3206-3313)
+  std::vector<double> a;
+  void compute() override {
+    const int T = ups[0]->nFrames, lenA = (int) a.size(), Tout = T + (lenA == 1 ? 1 : 0);
+    dev.reserve((size_t) (Tout > 0 ? Tout : 1) * rowBytes()); alloc(dsr_fir_frames_count(T, lenA));
+    if (Tout > 0) ok(dsr_fir_frames_run(ups[0]->d<float>(), nullptr, a.data(), lenA, 1, T, size_, d<float>(), S0));
+  }
+};
+struct MergeOp : dsr_stream {       // MergeFeature (feature.cc:3318-3350): stat, delta, deltaDelta side by side
+  void compute() override {
+    alloc(shortest(this, 0, 3));
+    size_t off = 0;
+    for (int k = 0; k < 3; k++) {
+      const size_t w = ups[k]->rowBytes();
+      if (nFrames > 0) DSR_HIP(hipMemcpy2DAsync(dev.p + off, rowBytes(), ups[k]->dev.p, w, w, (size_t) nFrames, hipMemcpyDeviceToDevice, S0));
+      off += w;
+    }
+  }
+};
 struct CmnOp : dsr_stream {          // MeanSubtractionFeature(src, weight, devNormFactor, runon): ups[1] (optional) = the weight stream, element 0 of each frame
   int mode; double dnf;
   void compute() override {
@@ -1456,6 +1486,51 @@ dsr_status dsr_spectral_smoothing_create(dsr_stream* adjustTo, dsr_stream* adjus
     if (adjustTo->size_ != adjustFrom->size_) throw Error(DSR_E_DIMENSION, "Feature sizes (%d vs. %d) do not match.", adjustTo->size_, adjustFrom->size_);   // lpc.cc:476-477
     if (adjustTo->size_ < 2) throw Error(DSR_E_PARAMETER, "SpectralSmoothing needs at least 2 coefficients, got %d", adjustTo->size_);
     SpecSmoothOp* s = mk<SpecSmoothOp>(name, "Spectral Smoothing", adjustTo->size_, DSR_T_DOUBLE); s->add_up(adjustTo); s->add_up(adjustFrom); *out = s;
+  });
+}
+dsr_status dsr_filter_feature_create(dsr_stream* src, const double* a, int lenA, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    need(src, DSR_T_FLOAT, "FilterFeature");
+    if (!a || !out) throw Error(DSR_E_PARAMETER, "null argument");
+    if (lenA < 1 || lenA % 2 != 1) throw Error(DSR_E_DIMENSION, "Length of filter (%d) is not odd.", lenA);                  // feature.cc:3219-3220
+    FirOp* s = mk<FirOp>(name, "Filter", src->size_, DSR_T_FLOAT); s->a.assign(a, a + lenA); s->add_up(src); *out = s;
+  });
+}
+dsr_status dsr_merge_feature_create(dsr_stream* stat, dsr_stream* delta, dsr_stream* deltaDelta, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    need(stat, DSR_T_FLOAT, "MergeFeature"); need(delta, DSR_T_FLOAT, "MergeFeature"); need(deltaDelta, DSR_T_FLOAT, "MergeFeature");
+    if (!out) throw Error(DSR_E_PARAMETER, "null argument");
+    MergeOp* s = mk<MergeOp>(name, "Merge", stat->size_ + delta->size_ + deltaDelta->size_, DSR_T_FLOAT);
+    s->add_up(stat); s->add_up(delta); s->add_up(deltaDelta); *out = s;
+  });
+}
+namespace {
+void conv_create(int kind, dsr_stream* src, const double* h, int P, int fftLen, const char* name, const char* dflt, dsr_stream** out)
+{
+  need(src, DSR_T_FLOAT, dflt);
+  if (!out) throw Error(DSR_E_PARAMETER, "null argument");
+  if (!h) throw Error(DSR_E_PARAMETER, "null impulse response");
+  dsr_conv* plan = nullptr;
+  ok(dsr_conv_create(kind, src->size_, P, fftLen, 1, &plan));
+  std::unique_ptr<ConvOp> s(mk<ConvOp>(name, dflt, dsr_conv_size(plan), DSR_T_FLOAT)); s->plan = plan;
+  ok(dsr_conv_set_response(plan, h));
+  s->add_up(src); *out = s.release();
+}
+}  // namespace
+dsr_status dsr_overlap_add_create(dsr_stream* src, const double* h, int P, int fftLen, const char* name, dsr_stream** out)
+{ return guard([&] { conv_create(0, src, h, P, fftLen, name, "Overlap Add", out); }); }
+dsr_status dsr_overlap_save_create(dsr_stream* src, const double* h, int P, const char* name, dsr_stream** out)
+{ return guard([&] { conv_create(1, src, h, P, 0, name, "Overlap Save", out); }); }
+dsr_status dsr_overlap_save_update(dsr_stream* s, const double* delta, int n)
+{
+  return guard([&] {
+    ConvOp* q = as_op<ConvOp>(s, "OverlapSave");
+    if (!delta) throw Error(DSR_E_PARAMETER, "null argument");
+    if (n != q->ups[0]->size_)                                                                                                 // convolution.cc:284-286
+      throw Error(DSR_E_DIMENSION, "Dimension of udpate vector (%d) does not match frequency response (%d).", n, q->ups[0]->size_);
+    ok(dsr_conv_update(q->plan, 0, delta));
   });
 }
 dsr_status dsr_storage_create(dsr_stream* src, const char* name, dsr_stream** out)

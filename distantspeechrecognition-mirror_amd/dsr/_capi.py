@@ -1595,6 +1595,80 @@ def spectral_smoothing(to, frm):
     return out
 
 
+class BlockConvolver:
+    """OverlapAdd / OverlapSave of btk/convolution on batches (include/dsr.h section 2g): kind "add" or "save", blocks of L samples, C impulse
+    responses [C][P] (one source gives C output channels).  OverlapAdd's fp32 buffer is a device tensor of the caller (state) that apply()
+    continues from and leaves behind."""
+    KINDS = {"add": 0, "save": 1}
+
+    def __init__(self, kind, L, response, fftLen=0):
+        L_ = load(); self.h = vp()
+        if response is None:
+            raise DsrError(E_PARAMETER, "null impulse response")
+        h = np.ascontiguousarray(np.atleast_2d(np.asarray(response, dtype=np.float64)))
+        self.kind = self.KINDS[kind] if isinstance(kind, str) else int(kind); self.L = int(L); self.C, self.P = h.shape
+        check(L_.dsr_conv_create(self.kind, self.L, self.P, int(fftLen), self.C, C.byref(self.h)))
+        check(L_.dsr_conv_set_response(self.h, _ptr(h)))
+        self.size = int(L_.dsr_conv_size(self.h)); self.fftLen = int(L_.dsr_conv_fft_len(self.h))
+
+    def __del__(self):
+        if _lib is not None and getattr(self, "h", None):
+            _lib.dsr_conv_destroy(self.h)
+
+    def update(self, delta, c=0):
+        """OverlapSave::update: delta complex [L], its bins 0..L/2 are added to response c's spectrum"""
+        d = np.ascontiguousarray(np.asarray(delta, dtype=np.complex128).reshape(-1))
+        if d.size != self.L:
+            raise DsrError(E_DIMENSION, "Dimension of udpate vector (%d) does not match frequency response (%d)." % (d.size, self.L))
+        check(_lib.dsr_conv_update(self.h, int(c), _ptr(d)))
+
+    def state(self, U, device="cuda:0"):
+        import torch
+        st = torch.zeros(max(1, int(_lib.dsr_conv_state_bytes(self.h, int(U))) // 4), dtype=torch.float32, device=device)
+        check(_lib.dsr_conv_state_init(self.h, _dev(st), int(U), cur_stream()))
+        return st
+
+    def apply(self, x, state=None, nframes=None):
+        """x: cuda float32 [U][Tmax][L], nframes: cuda int32 [U] or None, state: from state(U) (OverlapAdd; None starts from zeros and drops
+        what is left) -> float32 [U][C][Tmax][size]"""
+        import torch
+        U, T, L = x.shape
+        assert L == self.L and x.dtype == torch.float32 and x.is_contiguous()
+        assert nframes is None or (nframes.dtype == torch.int32 and nframes.numel() == U and nframes.is_contiguous())
+        if self.kind == 0 and state is None:
+            state = self.state(U, x.device)
+        y = torch.zeros((U, self.C, T, self.size), dtype=torch.float32, device=x.device)
+        check(_lib.dsr_conv_apply(self.h, _dev(x), _dev(nframes) if nframes is not None else None, U, T, _dev(state) if state is not None else None,
+                                  _dev(y), cur_stream()))
+        return y
+
+    def set_timing(self, on=True):
+        check(_lib.dsr_conv_set_timing(self.h, int(bool(on))))
+
+    def kernel_ms(self):
+        """ms of the last apply() in the transform kernel and in the fold"""
+        two = (C.c_double * 2)(); check(_lib.dsr_conv_kernel_ms(self.h, two))
+        return tuple(two)
+
+
+def fir_frames(x, coeffA, nframes=None):
+    """FilterFeature over whole utterances (feature.cc:3206-3313): x cuda float32 [U][Tmax][dim], coeffA odd-length taps, nframes cuda int32 [U] or
+    None -> float32 [U][Tmax + (lenA == 1)][dim]; utterance u has fir_frames_count(nframes[u], lenA) frames, the rest are zero"""
+    import torch
+    load()
+    a = np.ascontiguousarray(np.asarray(coeffA, dtype=np.float64).reshape(-1))
+    U, T, dim = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    assert nframes is None or (nframes.dtype == torch.int32 and nframes.numel() == U and nframes.is_contiguous())
+    y = torch.zeros((U, T + (1 if a.size == 1 else 0), dim), dtype=torch.float32, device=x.device)
+    check(_lib.dsr_fir_frames_run(_dev(x), _dev(nframes) if nframes is not None else None, _ptr(a), int(a.size), U, T, dim, _dev(y), cur_stream()))
+    return y
+
+
+def fir_frames_count(T, lenA):
+    return int(load().dsr_fir_frames_count(int(T), int(lenA)))
+
+
 MFCC_FRAMES_PLAIN, MFCC_FRAMES_W = 0, 1
 MFCC_CMN_NONE, MFCC_CMN_PLAIN, MFCC_CMN_LDS = 0, 1, 2
 MFCC_LDA_TOO_LARGE, MFCC_LDA_SPLICE, MFCC_LDA_PLAIN, MFCC_LDA_B = -1, 0, 1, 2

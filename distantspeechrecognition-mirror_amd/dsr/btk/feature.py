@@ -140,6 +140,23 @@ class SpectralSmoothingPtr(FeatureStreamPtr):
         FeatureStreamPtr.__init__(self, h, keep=(adjustTo, adjustFrom))
 
 
+class FilterFeaturePtr(FeatureStreamPtr):
+    """feature.h:1315-1410, feature.i: an odd-length FIR across frames (the delta and delta-delta filter)."""
+
+    def __init__(self, src, coeffA, nm="Filter"):
+        a = np.ascontiguousarray(np.asarray(coeffA, dtype=np.float64).reshape(-1))
+        h, _ = _new(lib().dsr_filter_feature_create, src._h, K._ptr(a), int(a.size), _b(nm))
+        FeatureStreamPtr.__init__(self, h, keep=(src,))
+
+
+class MergeFeaturePtr(FeatureStreamPtr):
+    """feature.h:1423-1441: static, delta and delta-delta features side by side."""
+
+    def __init__(self, stat, delta, deltaDelta, nm="Merge"):
+        h, _ = _new(lib().dsr_merge_feature_create, stat._h, delta._h, deltaDelta._h, _b(nm))
+        FeatureStreamPtr.__init__(self, h, keep=(stat, delta, deltaDelta))
+
+
 class StorageFeaturePtr(_unary(lambda *a: lib().dsr_storage_create(*a), "Storage")):
     def _args(self, src):
         return ()

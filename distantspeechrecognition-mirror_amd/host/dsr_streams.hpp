@@ -174,6 +174,29 @@ class SpectralSmoothing : public VectorFeatureStream {
   : _to(adjustTo), _from(adjustFrom) { DSR_OP(SpectralSmoothing, double, dsr_spectral_smoothing_create(adjustTo->handle(), adjustFrom->handle(), nm.c_str(), &h)) }
  private: VectorFeatureStreamPtr _to, _from;
 };
+// FilterFeature (feature.h:1315-1410) and MergeFeature (feature.h:1423-1441): coeffA points to lenA (odd) taps
+class FilterFeature : public VectorFloatFeatureStream {
+ public: FilterFeature(const VectorFloatFeatureStreamPtr& src, const double* coeffA, unsigned lenA, const String& nm = "Filter")
+  : _s(src) { DSR_OP(FilterFeature, float, dsr_filter_feature_create(src->handle(), coeffA, (int) lenA, nm.c_str(), &h)) }
+ private: VectorFloatFeatureStreamPtr _s;
+};
+class MergeFeature : public VectorFloatFeatureStream {
+ public: MergeFeature(const VectorFloatFeatureStreamPtr& stat, const VectorFloatFeatureStreamPtr& delta, const VectorFloatFeatureStreamPtr& deltaDelta, const String& nm = "Merge")
+  : _a(stat), _b(delta), _c(deltaDelta) { DSR_OP(MergeFeature, float, dsr_merge_feature_create(stat->handle(), delta->handle(), deltaDelta->handle(), nm.c_str(), &h)) }
+ private: VectorFloatFeatureStreamPtr _a, _b, _c;
+};
+// ---- btk/convolution/convolution.h:40-104: impulseResponse points to P samples
+class OverlapAdd : public VectorFloatFeatureStream {
+ public: OverlapAdd(const VectorFloatFeatureStreamPtr& samp, const double* impulseResponse, unsigned P, unsigned fftLen = 0, const String& nm = "Overlap Add")
+  : _s(samp) { DSR_OP(OverlapAdd, float, dsr_overlap_add_create(samp->handle(), impulseResponse, (int) P, (int) fftLen, nm.c_str(), &h)) }
+ private: VectorFloatFeatureStreamPtr _s;
+};
+class OverlapSave : public VectorFloatFeatureStream {
+ public: OverlapSave(const VectorFloatFeatureStreamPtr& samp, const double* impulseResponse, unsigned P, const String& nm = "Overlap Save")
+  : _s(samp) { DSR_OP(OverlapSave, float, dsr_overlap_save_create(samp->handle(), impulseResponse, (int) P, nm.c_str(), &h)) }
+  void update(const double* delta /* complex[n] */, unsigned n) { dsr_throw(dsr_overlap_save_update(_h, delta, (int) n)); }
+ private: VectorFloatFeatureStreamPtr _s;
+};
 
 // ---- btk/localization/localization.h:118-218 and btk/TDEstimator/CCTDE.h:60-101.  The reference's gsl vectors are pointers to the items here:
 // calculate() takes fftLen complex bins a spectrum, the getters return pointers into the object's own buffers (a null pointer where the

@@ -690,6 +690,52 @@ dsr_status dsr_mcc_calc(dsr_mcc*, const float* x_dev, const int32_t* nsamples_de
 dsr_status dsr_mcc_channel_delays(const dsr_mcc*, const int32_t* tau, double* delays);
 
 /* =====================================================================================
+ * 2g. Block convolution with an impulse response (btk/convolution/convolution.h:40-104, convolution.cc:43-290) and the FIR filter across
+ *     frames of FilterFeature (btk/feature/feature.cc:3206-3313)
+ *
+ * kind 0, OverlapAdd(samp, impulseResponse[P], fftLen): blocks of L samples, N = fftLen or, for fftLen 0, the smallest power of two >= L+P-1
+ * (at least 4, the shortest transform here).  A block is zero-padded to N, transformed, multiplied by the response's spectrum, transformed
+ * back and scaled by 1/N in fp64; its first L+P-1 samples are added into the reference's fp32 buffer, float(double(buffer) + section), oldest
+ * block first.  The buffer's P-1 samples beyond a block are the carried state.
+ * kind 1, OverlapSave(samp, impulseResponse[P]): blocks of L samples (the caller overlaps them), L a power of two above P, N = L; sample
+ * i-P of the output is sample i of the circular convolution for i = P..L-1 (the reference starts at P, not P-1), size L-P, no state.
+ * One plan holds C responses: one source gives C output channels (C = 1 is the reference's object).
+ * Refusals: DSR_E_DIMENSION for an N that is no power of two, below 4 or above 2^22, fftLen < L+P-1 ("Section ... inconsistent with FFT
+ * length"), P >= L for OverlapSave ("Cannot have P = ... and L = ..."), L, P or C below 1; DSR_E_PARAMETER for a null response (the reference
+ * dereferences it) or an unknown kind; DSR_E_CONSISTENCY for apply() or update() before set_response().
+ * ===================================================================================== */
+typedef struct dsr_conv dsr_conv;
+dsr_status dsr_conv_create(int kind /* 0 add, 1 save */, int L, int P, int fftLen, int C, dsr_conv** out);
+void       dsr_conv_destroy(dsr_conv*);
+int        dsr_conv_size(const dsr_conv*);                   /* samples of an output block: L, or L-P */
+int        dsr_conv_fft_len(const dsr_conv*);
+/* h_host [C][P]: the spectra are computed on the host in fp64 (_setImpulseResponse, convolution.cc:60-77,192-209) */
+dsr_status dsr_conv_set_response(dsr_conv*, const double* h_host);
+/* OverlapSave::update (convolution.cc:282-290) for response c: delta_host is complex[L] as there, its bins 0..L/2 are added to the L/2+1
+ * stored ones (the reference's loop runs on to L-1, past the end of its own vector).  Bins 0 and L/2 are multiplied by their real part alone,
+ * as in next(). */
+dsr_status dsr_conv_update(dsr_conv*, int c, const double* delta_host);
+/* OverlapAdd's carried buffer: P-1 floats per (utterance, response), zeros at the start (reset()); 0 bytes for OverlapSave and P = 1, where
+ * state_dev may be NULL */
+size_t     dsr_conv_state_bytes(const dsr_conv*, int U);
+dsr_status dsr_conv_state_init(const dsr_conv*, void* state_dev, int U, void* stream);
+/* x_dev float [U][Tmax][L], nframes_dev int32 [U] (NULL: Tmax each) -> y_dev float [U][C][Tmax][size].  Blocks at or past nframes[u] come out
+ * zero and leave the state alone; a stream run as consecutive calls with the same state_dev equals one call bit for bit. */
+dsr_status dsr_conv_apply(dsr_conv*, const float* x_dev, const int32_t* nframes_dev, int U, int Tmax, void* state_dev, float* y_dev, void* stream);
+/* measurement (tools/bench_conv.py): with timing on, apply brackets its launches with events; kernel_ms waits for them and gives the last
+ * call's milliseconds in the transform kernel and in the fold (with the state copy) */
+dsr_status dsr_conv_set_timing(dsr_conv*, int on);
+dsr_status dsr_conv_kernel_ms(const dsr_conv*, double* ms2);
+/* FilterFeature::next over whole utterances: y[t][c] = float(sum_{i=-o..o} a[i+o] * double(x[t-i][c])), o = (lenA-1)/2, fp64 accumulator, i
+ * ascending, frames outside [0, nframes[u]) read as zero.  An even lenA is DSR_E_DIMENSION "Length of filter (%d) is not odd.".
+ * frames_count: the frames the reference's operator delivers for T source frames -- T for o >= 1 and T >= o, 0 for T < o (its priming loop hits
+ * the end of the source), T+1 for lenA = 1 (it pads once before it looks at its count), the last one zeros.
+ * x_dev float [U][Tmax][dim] -> y_dev float [U][Tout][dim], Tout = Tmax + (lenA == 1); frames past an utterance's count are zero. */
+int        dsr_fir_frames_count(int T, int lenA);
+dsr_status dsr_fir_frames_run(const float* x_dev, const int32_t* nframes_dev, const double* a_host, int lenA, int U, int Tmax, int dim, float* y_dev,
+                              void* stream);
+
+/* =====================================================================================
  * 3. MFCC feature chain
  *    replaces SampleFeature(block framing) -> PreemphasisFeature -> HammingFeature -> FFTFeature ->
  *    SpectralPowerFeature -> VTLNFeature -> MelFeature -> LogFeature -> CepstralFeature ->
@@ -1489,6 +1535,16 @@ dsr_status dsr_wtmvdr_feature_create(dsr_stream* src, int order, int correlate, 
 /* SpectralSmoothing(adjustTo, adjustFrom, nm = "Spectral Smoothing") (lpc.h:342-358, lpc.cc:473-478): unequal sizes => DSR_E_DIMENSION; the
  * stream ends with the shorter of the two */
 dsr_status dsr_spectral_smoothing_create(dsr_stream* adjustTo, dsr_stream* adjustFrom, const char* name, dsr_stream** out);
+/* FilterFeature(src, coeffA, nm = "Filter") (feature.h:1315-1410): whole utterances, frame counts as dsr_fir_frames_count */
+dsr_status dsr_filter_feature_create(dsr_stream* src, const double* a, int lenA, const char* name, dsr_stream** out);
+/* MergeFeature(stat, delta, deltaDelta, nm = "Merge") (feature.h:1423-1441): the three float rows one after the other; ends with the shortest */
+dsr_status dsr_merge_feature_create(dsr_stream* stat, dsr_stream* delta, dsr_stream* deltaDelta, const char* name, dsr_stream** out);
+/* OverlapAdd(samp, impulseResponse, fftLen = 0, nm = "Overlap Add") / OverlapSave(samp, impulseResponse, nm = "Overlap Save")
+ * (convolution.h:40-104): section 2g with C = 1 over the source's blocks; reset() zeroes OverlapAdd's buffer.  update: delta complex[n], n must
+ * be L (DSR_E_DIMENSION otherwise, as there); it holds for the utterances materialised after it. */
+dsr_status dsr_overlap_add_create(dsr_stream* src, const double* h, int P, int fftLen, const char* name, dsr_stream** out);
+dsr_status dsr_overlap_save_create(dsr_stream* src, const double* h, int P, const char* name, dsr_stream** out);
+dsr_status dsr_overlap_save_update(dsr_stream* s, const double* delta, int n);
 dsr_status dsr_storage_create(dsr_stream* src, const char* name, dsr_stream** out);
 dsr_status dsr_mean_subtraction_create(dsr_stream* src, double devNormFactor, int runon, const char* name, dsr_stream** out);
 /* the optional weight stream of MeanSubtractionFeature(src, weight, devNormFactor, runon) (feature.h, feature.cc:2577-2707): element 0 of its frames weighs

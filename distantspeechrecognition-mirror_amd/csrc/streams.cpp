@@ -179,6 +179,55 @@ struct MergeOp : dsr_stream {       // MergeFeature (feature.cc:3318-3350): stat
     }
   }
 };
+// ---- the scalar feature operators of include/dsr.h section 6c (csrc/k_featops.hip), one utterance a call
+struct SignalPowerOp : dsr_stream { void compute() override { alloc(ups[0]->nFrames); if (nFrames > 0) ok(dsr_signal_power_run(ups[0]->d<float>(), nullptr, 1, nFrames, ups[0]->size_, d<float>(), S0)); } };
+struct ZcrOp : dsr_stream { void compute() override { alloc(ups[0]->nFrames); if (nFrames > 0) ok(dsr_zcr_hamming_run(ups[0]->d<float>(), nullptr, 1, nFrames, ups[0]->size_, d<float>(), S0)); } };
+struct YinOp : dsr_stream {
+  unsigned sr = 16000; float tr = 0.5f;
+  void compute() override { alloc(ups[0]->nFrames); if (nFrames > 0) ok(dsr_yin_pitch_run(ups[0]->d<float>(), nullptr, 1, nFrames, ups[0]->size_, sr, tr, d<float>(), nullptr, nullptr, S0)); }
+};
+struct SpikeOp : dsr_stream { int tapN = 3; void compute() override { alloc(ups[0]->nFrames); if (nFrames > 0) ok(dsr_spike_filter_run(ups[0]->d<float>(), nullptr, 1, nFrames, size_, tapN, d<float>(), S0)); } };
+struct Spike2Op : dsr_stream {      // SpikeFilter2 (feature.cc:3701-3776): reset() sets _meanslope = _startslope, _count = 0
+  unsigned width = 3; float maxslope = 7000.0f, startslope = 100.0f, thresh = 15.0f, alpha = 0.2f; unsigned spikes = 0;
+  DevBuf<float> ms; DevBuf<int> cnt;
+  void reset() override { dsr_stream::reset(); spikes = 0; }
+  void compute() override {
+    alloc(ups[0]->nFrames);
+    const int zero = 0; ms.upload(&startslope, 1, S0); cnt.upload(&zero, 1, S0);
+    if (nFrames <= 0) return;
+    ok(dsr_spike_filter2_run(ups[0]->d<float>(), nullptr, 1, nFrames, size_, width, maxslope, thresh, alpha, ms.p, cnt.p, d<float>(), S0));
+    int c = 0; DSR_HIP(hipMemcpy(&c, cnt.p, sizeof c, hipMemcpyDeviceToHost)); spikes = (unsigned) c;
+  }
+};
+struct MinMaxOp : dsr_stream {      // ALogFeature / NormalizeFeature (feature.cc:1383-1514): (min, max) kept across reset() when runon
+  int alog = 0, runon = 0; double p0 = 0.0, p1 = 0.0; bool fresh = true; DevBuf<double> state;
+  void compute() override {
+    alloc(ups[0]->nFrames);
+    state.reserve(2);
+    if (fresh || !runon) { ok(dsr_minmax_state_init(state.p, 1, S0)); fresh = false; }
+    if (nFrames <= 0) return;
+    if (alog) ok(dsr_alog_run(ups[0]->d<float>(), nullptr, 1, nFrames, ups[0]->size_, p0, p1, runon, state.p, d<float>(), S0));
+    else ok(dsr_normalize_run(ups[0]->d<float>(), nullptr, 1, nFrames, size_, p0, p1, runon, state.p, d<float>(), S0));
+  }
+};
+struct ThreshAmpOp : dsr_stream {   // ThresholdFeature (compare -1, 0, 1) and AmplificationFeature (compare 2)
+  double value = 0.0, thresh = 1.0; int compare = 1;
+  void compute() override {
+    alloc(ups[0]->nFrames);
+    if (nFrames <= 0) return;
+    if (compare == 2) ok(dsr_amplify_run(ups[0]->d<float>(), nullptr, 1, nFrames, size_, value, d<float>(), S0));
+    else ok(dsr_threshold_run(ups[0]->d<float>(), nullptr, 1, nFrames, size_, value, thresh, compare, d<float>(), S0));
+  }
+};
+struct ResampleOp : dsr_stream {
+  double ratio = 16.0 / 22.05; int len = 0;
+  void compute() override { alloc(ups[0]->nFrames); if (nFrames > 0) ok(dsr_spectral_resample_run(ups[0]->d<double>(), nullptr, 1, nFrames, ups[0]->size_, ratio, len, d<double>(), S0)); }
+};
+struct SphinxMelOp : dsr_stream {
+  dsr_sphinx_mel* plan = nullptr;
+  ~SphinxMelOp() override { if (plan) dsr_sphinx_mel_destroy(plan); }
+  void compute() override { alloc(ups[0]->nFrames); if (nFrames > 0) ok(dsr_sphinx_mel_apply(plan, ups[0]->d<double>(), nullptr, 1, nFrames, d<double>(), S0)); }
+};
 struct CmnOp : dsr_stream {          // MeanSubtractionFeature(src, weight, devNormFactor, runon): ups[1] (optional) = the weight stream, element 0 of each frame
   int mode; double dnf;
   void compute() override {
@@ -1531,6 +1580,89 @@ dsr_status dsr_overlap_save_update(dsr_stream* s, const double* delta, int n)
     if (n != q->ups[0]->size_)                                                                                                 // convolution.cc:284-286
       throw Error(DSR_E_DIMENSION, "Dimension of udpate vector (%d) does not match frequency response (%d).", n, q->ups[0]->size_);
     ok(dsr_conv_update(q->plan, 0, delta));
+  });
+}
+dsr_status dsr_signal_power_create(dsr_stream* samp, const char* name, dsr_stream** out)
+{ return guard([&] { need(samp, DSR_T_FLOAT, "SignalPowerFeature"); if (!out) throw Error(DSR_E_PARAMETER, "null argument"); SignalPowerOp* s = mk<SignalPowerOp>(name, "Signal Power", 1, DSR_T_FLOAT); s->add_up(samp); *out = s; }); }
+dsr_status dsr_zcr_hamming_create(dsr_stream* samp, const char* name, dsr_stream** out)
+{ return guard([&] { need(samp, DSR_T_FLOAT, "ZeroCrossingRateHammingFeature"); if (!out) throw Error(DSR_E_PARAMETER, "null argument"); ZcrOp* s = mk<ZcrOp>(name, "Zero Crossing Rate Hamming", 1, DSR_T_FLOAT); s->add_up(samp); *out = s; }); }
+dsr_status dsr_yin_pitch_create(dsr_stream* samp, unsigned samplerate, float threshold, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    need(samp, DSR_T_FLOAT, "YINPitchFeature"); if (!out) throw Error(DSR_E_PARAMETER, "null argument");
+    if (samp->size_ < 2) throw Error(DSR_E_DIMENSION, "YIN needs frames of at least 2 samples, got %d.", samp->size_);
+    YinOp* s = mk<YinOp>(name, "YIN Pitch", 1, DSR_T_FLOAT); s->sr = samplerate; s->tr = threshold; s->add_up(samp); *out = s;
+  });
+}
+dsr_status dsr_spike_filter_create(dsr_stream* src, unsigned tapN, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    need(src, DSR_T_FLOAT, "SpikeFilter"); if (!out) throw Error(DSR_E_PARAMETER, "null argument");
+    ok(dsr_spike_filter_check(src->size_, tapN > 0x7fffffffu ? 0x7fffffff : (int) tapN));
+    SpikeOp* s = mk<SpikeOp>(name, "Spike Filter", src->size_, DSR_T_FLOAT); s->tapN = (int) tapN; s->add_up(src); *out = s;
+  });
+}
+dsr_status dsr_spike_filter2_create(dsr_stream* src, unsigned width, float maxslope, float startslope, float thresh, float alpha, unsigned verbose, const char* name,
+                                    dsr_stream** out)
+{
+  return guard([&] {
+    need(src, DSR_T_FLOAT, "SpikeFilter2"); if (!out) throw Error(DSR_E_PARAMETER, "null argument");
+    (void) verbose;                                                                                                            // its printf passes floats to %d
+    if (src->size_ > 16000) throw Error(DSR_E_DIMENSION, "SpikeFilter2 stages a block in LDS: %d samples exceed 16000.", src->size_);
+    Spike2Op* s = mk<Spike2Op>(name, "Spike Filter 2", src->size_, DSR_T_FLOAT);
+    s->width = width; s->maxslope = maxslope; s->startslope = startslope; s->thresh = thresh; s->alpha = alpha; s->add_up(src); *out = s;
+  });
+}
+dsr_status dsr_spike_filter2_spikes(dsr_stream* s, unsigned* n)
+{ return guard([&] { Spike2Op* q = as_op<Spike2Op>(s, "SpikeFilter2"); if (!n) throw Error(DSR_E_PARAMETER, "null argument"); *n = q->spikes; }); }
+dsr_status dsr_alog_create(dsr_stream* samp, double m, double a, int runon, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    need(samp, DSR_T_FLOAT, "ALogFeature"); if (!out) throw Error(DSR_E_PARAMETER, "null argument");
+    MinMaxOp* s = mk<MinMaxOp>(name, "ALog Power", 1, DSR_T_FLOAT); s->alog = 1; s->runon = runon != 0; s->p0 = m; s->p1 = a; s->add_up(samp); *out = s;
+  });
+}
+dsr_status dsr_normalize_create(dsr_stream* samp, double min, double max, int runon, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    need(samp, DSR_T_FLOAT, "NormalizeFeature"); if (!out) throw Error(DSR_E_PARAMETER, "null argument");
+    MinMaxOp* s = mk<MinMaxOp>(name, "Normalize", samp->size_, DSR_T_FLOAT); s->runon = runon != 0; s->p0 = min; s->p1 = max; s->add_up(samp); *out = s;
+  });
+}
+dsr_status dsr_minmax_next_speaker(dsr_stream* s)
+{ return guard([&] { as_op<MinMaxOp>(s, "ALogFeature or NormalizeFeature")->fresh = true; }); }
+dsr_status dsr_threshold_create(dsr_stream* samp, double value, double thresh, const char* mode, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    need(samp, DSR_T_FLOAT, "ThresholdFeature"); if (!out) throw Error(DSR_E_PARAMETER, "null argument");
+    int compare = 0; ok(dsr_threshold_mode(mode, &compare));
+    ThreshAmpOp* s = mk<ThreshAmpOp>(name, "Threshold", samp->size_, DSR_T_FLOAT); s->value = value; s->thresh = thresh; s->compare = compare; s->add_up(samp); *out = s;
+  });
+}
+dsr_status dsr_amplification_create(dsr_stream* src, double amplify, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    need(src, DSR_T_FLOAT, "AmplificationFeature"); if (!out) throw Error(DSR_E_PARAMETER, "null argument");
+    ThreshAmpOp* s = mk<ThreshAmpOp>(name, "Amplification", src->size_, DSR_T_FLOAT); s->value = amplify; s->compare = 2; s->add_up(src); *out = s;
+  });
+}
+dsr_status dsr_spectral_resampling_create(dsr_stream* src, double ratio, unsigned len, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    need(src, DSR_T_DOUBLE, "SpectralResamplingFeature"); if (!out) throw Error(DSR_E_PARAMETER, "null argument");
+    int outN = 0; ok(dsr_spectral_resample_size(src->size_, ratio, (int) len, &outN));
+    ResampleOp* s = mk<ResampleOp>(name, "Resampling", outN, DSR_T_DOUBLE); s->ratio = ratio; s->len = (int) len; s->add_up(src); *out = s;
+  });
+}
+dsr_status dsr_sphinx_mel_feature_create(dsr_stream* mag, unsigned fftN, unsigned powerN, float sampleRate, float lowerF, float upperF, unsigned filterN,
+                                         const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    need(mag, DSR_T_DOUBLE, "SphinxMelFeature"); if (!out) throw Error(DSR_E_PARAMETER, "null argument");
+    const unsigned pN = powerN == 0 ? (unsigned) mag->size_ : powerN;
+    if ((int) pN != mag->size_) throw Error(DSR_E_DIMENSION, "SphinxMelFeature: powerN = %u does not match the source's size %d.", pN, mag->size_);   // gsl_blas_dgemv's own check
+    dsr_sphinx_mel* plan = nullptr; ok(dsr_sphinx_mel_create(fftN, pN, sampleRate, lowerF, upperF, filterN, &plan));
+    SphinxMelOp* s = mk<SphinxMelOp>(name, "Sphinx Mel Filter Bank", (int) filterN, DSR_T_DOUBLE); s->plan = plan; s->add_up(mag); *out = s;
   });
 }
 dsr_status dsr_storage_create(dsr_stream* src, const char* name, dsr_stream** out)

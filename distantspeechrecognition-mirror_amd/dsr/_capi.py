@@ -1669,6 +1669,166 @@ def fir_frames_count(T, lenA):
     return int(load().dsr_fir_frames_count(int(T), int(lenA)))
 
 
+# ---- the scalar feature operators of btk/feature (include/dsr.h section 6c, csrc/k_featops.hip)
+def _batch(x, nframes, dtype=None):
+    import torch
+    assert x.dim() == 3 and x.dtype == (dtype or torch.float32) and x.is_contiguous()
+    assert nframes is None or (nframes.dtype == torch.int32 and nframes.numel() == x.shape[0] and nframes.is_contiguous())
+    return x.shape, (_dev(nframes) if nframes is not None else None)
+
+
+def signal_power(x, nframes=None):
+    """SignalPowerFeature over whole utterances: x cuda float32 [U][Tmax][dim] -> float32 [U][Tmax][1]"""
+    import torch
+    load(); (U, T, dim), nf = _batch(x, nframes)
+    y = torch.zeros((U, T, 1), dtype=torch.float32, device=x.device)
+    check(_lib.dsr_signal_power_run(_dev(x), nf, U, T, dim, _dev(y), cur_stream()))
+    return y
+
+
+def zero_crossing_rate(x, nframes=None):
+    """ZeroCrossingRateHammingFeature: x cuda float32 [U][Tmax][dim] -> float32 [U][Tmax][1]"""
+    import torch
+    load(); (U, T, dim), nf = _batch(x, nframes)
+    y = torch.zeros((U, T, 1), dtype=torch.float32, device=x.device)
+    check(_lib.dsr_zcr_hamming_run(_dev(x), nf, U, T, dim, _dev(y), cur_stream()))
+    return y
+
+
+def yin_pitch(x, samplerate=16000, threshold=0.5, nframes=None, return_value=False, return_chunks=False):
+    """YINPitchFeature: x cuda float32 [U][Tmax][dim] -> pitch float32 [U][Tmax][1]; return_value adds float32 [U][Tmax], y(tau) at the lag where
+    the reference's search returned (y(W-1) where it ran to the end); return_chunks adds int32 [U][Tmax], the chunks of 64 lags evaluated"""
+    import torch
+    load(); (U, T, dim), nf = _batch(x, nframes)
+    p = torch.zeros((U, T, 1), dtype=torch.float32, device=x.device)
+    v = torch.zeros((U, T), dtype=torch.float32, device=x.device) if return_value else None
+    c = torch.zeros((U, T), dtype=torch.int32, device=x.device) if return_chunks else None
+    check(_lib.dsr_yin_pitch_run(_dev(x), nf, U, T, dim, int(samplerate), float(threshold), _dev(p), _dev(v) if return_value else None,
+                                 _dev(c) if return_chunks else None, cur_stream()))
+    out = (p,) + ((v,) if return_value else ()) + ((c,) if return_chunks else ())
+    return out if len(out) > 1 else p
+
+
+def yin_kernel(dim):
+    """frames a workgroup of the YIN kernel a frame length selects (the frame's copies in LDS), 0: the kernel that reads global memory"""
+    return int(load().dsr_yin_kernel(int(dim)))
+
+
+def spike_filter(x, tapN=3, nframes=None):
+    """SpikeFilter: the running median of tapN samples within each block; the last tapN-1 samples of a block stay zero as in the reference"""
+    import torch
+    load(); (U, T, dim), nf = _batch(x, nframes)
+    y = torch.zeros((U, T, dim), dtype=torch.float32, device=x.device)
+    check(_lib.dsr_spike_filter_run(_dev(x), nf, U, T, dim, int(tapN), _dev(y), cur_stream()))
+    return y
+
+
+def spike_filter2_state(U, startslope=100.0, device="cuda:0"):
+    """(meanslope float32 [U], count int32 [U]) as SpikeFilter2::reset() leaves them"""
+    import torch
+    return torch.full((U,), float(startslope), dtype=torch.float32, device=device), torch.zeros((U,), dtype=torch.int32, device=device)
+
+
+def spike_filter2(x, width=3, maxslope=7000.0, startslope=100.0, thresh=15.0, alpha=0.2, state=None, nframes=None):
+    """SpikeFilter2 over the blocks of each utterance in order: x cuda float32 [U][Tmax][dim] -> (y, (meanslope, count)); state: the pair a
+    previous call returned (None: reset())"""
+    import torch
+    load(); (U, T, dim), nf = _batch(x, nframes)
+    if state is None:
+        state = spike_filter2_state(U, startslope, x.device)
+    ms, cnt = state
+    assert ms.dtype == torch.float32 and cnt.dtype == torch.int32 and ms.numel() == U and cnt.numel() == U
+    y = torch.zeros((U, T, dim), dtype=torch.float32, device=x.device)
+    check(_lib.dsr_spike_filter2_run(_dev(x), nf, U, T, dim, int(width), float(maxslope), float(thresh), float(alpha), _dev(ms), _dev(cnt), _dev(y), cur_stream()))
+    return y, (ms, cnt)
+
+
+def minmax_state(U, device="cuda:0"):
+    """(min, max) of ALog / Normalize after nextSpeaker(): float64 [U][2] = (HUGE, -HUGE)"""
+    import torch
+    load(); st = torch.zeros((U, 2), dtype=torch.float64, device=device)
+    check(_lib.dsr_minmax_state_init(_dev(st), U, cur_stream()))
+    return st
+
+
+def alog(x, m=1.0, a=4.0, runon=False, state=None, nframes=None):
+    """ALogFeature: x cuda float32 [U][Tmax][dim] -> float32 [U][Tmax][1].  runon: the running (min, max) continue from state (minmax_state) and
+    are left there; otherwise they are taken over the whole utterance"""
+    import torch
+    load(); (U, T, dim), nf = _batch(x, nframes)
+    y = torch.zeros((U, T, 1), dtype=torch.float32, device=x.device)
+    check(_lib.dsr_alog_run(_dev(x), nf, U, T, dim, float(m), float(a), int(bool(runon)), _dev(state) if state is not None else None, _dev(y), cur_stream()))
+    return y
+
+
+def normalize(x, min=0.0, max=1.0, runon=False, state=None, nframes=None):
+    """NormalizeFeature: x cuda float32 [U][Tmax][dim] -> float32 [U][Tmax][dim]; runon and state as in alog"""
+    import torch
+    load(); (U, T, dim), nf = _batch(x, nframes)
+    y = torch.zeros((U, T, dim), dtype=torch.float32, device=x.device)
+    check(_lib.dsr_normalize_run(_dev(x), nf, U, T, dim, float(min), float(max), int(bool(runon)), _dev(state) if state is not None else None, _dev(y),
+                                 cur_stream()))
+    return y
+
+
+def threshold(x, value=0.0, thresh=1.0, mode="upper", nframes=None):
+    """ThresholdFeature: mode "upper", "lower" or "both" (any other: a key error)"""
+    import torch
+    load(); cmp_ = C.c_int(0)
+    check(_lib.dsr_threshold_mode(mode.encode() if isinstance(mode, str) else mode, C.byref(cmp_)))
+    (U, T, dim), nf = _batch(x, nframes)
+    y = torch.zeros((U, T, dim), dtype=torch.float32, device=x.device)
+    check(_lib.dsr_threshold_run(_dev(x), nf, U, T, dim, float(value), float(thresh), cmp_.value, _dev(y), cur_stream()))
+    return y
+
+
+def amplify(x, amplify=1.0, nframes=None):
+    """AmplificationFeature: float(double(x) * amplify)"""
+    import torch
+    load(); (U, T, dim), nf = _batch(x, nframes)
+    y = torch.zeros((U, T, dim), dtype=torch.float32, device=x.device)
+    check(_lib.dsr_amplify_run(_dev(x), nf, U, T, dim, float(amplify), _dev(y), cur_stream()))
+    return y
+
+
+SPECTRAL_SAMPLE_RATIO = 16.0 / 22.05
+
+
+def spectral_resample(x, ratio=SPECTRAL_SAMPLE_RATIO, len=0, nframes=None):
+    """SpectralResamplingFeature: x cuda float64 [U][Tmax][srcN] -> float64 [U][Tmax][len or srcN]"""
+    import torch
+    load(); (U, T, srcN), nf = _batch(x, nframes, torch.float64)
+    outN = C.c_int(0)
+    check(_lib.dsr_spectral_resample_size(srcN, float(ratio), int(len), C.byref(outN)))
+    y = torch.zeros((U, T, outN.value), dtype=torch.float64, device=x.device)
+    check(_lib.dsr_spectral_resample_run(_dev(x), nf, U, T, srcN, float(ratio), int(len), _dev(y), cur_stream()))
+    return y
+
+
+class SphinxMel:
+    """SphinxMelFeature's filter bank: .filters is the host-built [filterN][powerN] fp64 matrix, apply() multiplies frames by it"""
+
+    def __init__(self, fftN=512, powerN=257, sampleRate=16000.0, lowerF=0.0, upperF=0.0, filterN=30):
+        L_ = load(); self.h = vp()
+        check(L_.dsr_sphinx_mel_create(int(fftN), int(powerN), float(sampleRate), float(lowerF), float(upperF), int(filterN), C.byref(self.h)))
+        self.powerN, self.filterN = int(powerN), int(filterN)
+        self.filters = np.zeros((self.filterN, self.powerN), np.float64)
+        check(L_.dsr_sphinx_mel_filters(self.h, _ptr(self.filters)))
+
+    def __del__(self):
+        if _lib is not None and getattr(self, "h", None):
+            _lib.dsr_sphinx_mel_destroy(self.h)
+
+    def apply(self, x, nframes=None):
+        """x cuda float64 [U][Tmax][powerN] -> float64 [U][Tmax][filterN]"""
+        import torch
+        (U, T, dim), nf = _batch(x, nframes, torch.float64)
+        assert dim == self.powerN
+        y = torch.zeros((U, T, self.filterN), dtype=torch.float64, device=x.device)
+        check(_lib.dsr_sphinx_mel_apply(self.h, _dev(x), nf, U, T, _dev(y), cur_stream()))
+        return y
+
+
 MFCC_FRAMES_PLAIN, MFCC_FRAMES_W = 0, 1
 MFCC_CMN_NONE, MFCC_CMN_PLAIN, MFCC_CMN_LDS = 0, 1, 2
 MFCC_LDA_TOO_LARGE, MFCC_LDA_SPLICE, MFCC_LDA_PLAIN, MFCC_LDA_B = -1, 0, 1, 2

@@ -157,6 +157,95 @@ class MergeFeaturePtr(FeatureStreamPtr):
         FeatureStreamPtr.__init__(self, h, keep=(stat, delta, deltaDelta))
 
 
+class SignalPowerFeaturePtr(FeatureStreamPtr):
+    """feature.i:899: the mean square of a block over (65536^2 / 4), one value a frame."""
+
+    def __init__(self, samp, nm="Signal Power"):
+        h, _ = _new(lib().dsr_signal_power_create, samp._h, _b(nm)); FeatureStreamPtr.__init__(self, h, keep=(samp,))
+
+
+class ALogFeaturePtr(FeatureStreamPtr):
+    """feature.i:928: m log10(max / 10^a + x), max over the utterance or, with runon, over everything seen since nextSpeaker()."""
+
+    def __init__(self, samp, m=1.0, a=4.0, runon=False, nm="ALog Power"):
+        h, _ = _new(lib().dsr_alog_create, samp._h, float(m), float(a), int(bool(runon)), _b(nm)); FeatureStreamPtr.__init__(self, h, keep=(samp,))
+
+    def nextSpeaker(self):
+        K.check(lib().dsr_minmax_next_speaker(self._h))
+
+
+class NormalizeFeaturePtr(FeatureStreamPtr):
+    """feature.i:958: the source's [min, max] mapped onto [min, max] of the arguments."""
+
+    def __init__(self, samp, min=0.0, max=1.0, runon=False, nm="Normalize"):
+        h, _ = _new(lib().dsr_normalize_create, samp._h, float(min), float(max), int(bool(runon)), _b(nm)); FeatureStreamPtr.__init__(self, h, keep=(samp,))
+
+    def nextSpeaker(self):
+        K.check(lib().dsr_minmax_next_speaker(self._h))
+
+
+class ThresholdFeaturePtr(FeatureStreamPtr):
+    """feature.i:986: mode "upper", "lower" or "both"; any other is a key error."""
+
+    def __init__(self, samp, value=0.0, thresh=1.0, mode="upper", nm="Threshold"):
+        h, _ = _new(lib().dsr_threshold_create, samp._h, float(value), float(thresh), _b(mode), _b(nm)); FeatureStreamPtr.__init__(self, h, keep=(samp,))
+
+
+class SpectralResamplingFeaturePtr(FeatureStreamPtr):
+    """feature.i:1016: linear interpolation of a spectrum onto len (0: as many) points at ratio times the source's spacing."""
+
+    def __init__(self, src, ratio=K.SPECTRAL_SAMPLE_RATIO, len=0, nm="Resampling"):
+        h, _ = _new(lib().dsr_spectral_resampling_create, src._h, float(ratio), int(len), _b(nm)); FeatureStreamPtr.__init__(self, h, keep=(src,))
+
+
+class SphinxMelFeaturePtr(FeatureStreamPtr):
+    """feature.i:1148: Sphinx's unnormalised triangular mel filters; the defaults lowerF = upperF = 0 give an all-zero bank, as there."""
+
+    def __init__(self, mag, fftN=512, powerN=0, sampleRate=16000.0, lowerF=0.0, upperF=0.0, filterN=30, nm="Sphinx Mel Filter Bank"):
+        h, _ = _new(lib().dsr_sphinx_mel_feature_create, mag._h, int(fftN), int(powerN), float(sampleRate), float(lowerF), float(upperF), int(filterN), _b(nm))
+        FeatureStreamPtr.__init__(self, h, keep=(mag,))
+
+
+class ZeroCrossingRateHammingFeaturePtr(FeatureStreamPtr):
+    """feature.i:1883: the Hamming-weighted zero-crossing rate of a block."""
+
+    def __init__(self, samp, nm="Zero Crossing Rate Hamming"):
+        h, _ = _new(lib().dsr_zcr_hamming_create, samp._h, _b(nm)); FeatureStreamPtr.__init__(self, h, keep=(samp,))
+
+
+class YINPitchFeaturePtr(FeatureStreamPtr):
+    """feature.i:1908: the YIN fundamental-frequency estimate of a block in Hz, 0 where none is found."""
+
+    def __init__(self, samp, samplerate=16000, threshold=0.5, nm="YIN Pitch"):
+        h, _ = _new(lib().dsr_yin_pitch_create, samp._h, int(samplerate), float(threshold), _b(nm)); FeatureStreamPtr.__init__(self, h, keep=(samp,))
+
+
+class SpikeFilterPtr(FeatureStreamPtr):
+    """feature.i:1936: a running median of tapN (odd, at least 3) samples within each block."""
+
+    def __init__(self, src, tapN=3, nm="Spike Filter"):
+        h, _ = _new(lib().dsr_spike_filter_create, src._h, int(tapN), _b(nm)); FeatureStreamPtr.__init__(self, h, keep=(src,))
+
+
+class SpikeFilter2Ptr(FeatureStreamPtr):
+    """feature.i:1968: steep slopes against a running mean slope mark a spike, which is replaced by a straight line."""
+
+    def __init__(self, src, width=3, maxslope=7000.0, startslope=100.0, thresh=15.0, alpha=0.2, verbose=1, nm="Spike Filter 2"):
+        h, _ = _new(lib().dsr_spike_filter2_create, src._h, int(width), float(maxslope), float(startslope), float(thresh), float(alpha), int(verbose), _b(nm))
+        FeatureStreamPtr.__init__(self, h, keep=(src,))
+
+    def spikesN(self):
+        n = C.c_uint(0); K.check(lib().dsr_spike_filter2_spikes(self._h, C.byref(n)))
+        return n.value
+
+
+class AmplificationFeaturePtr(FeatureStreamPtr):
+    """feature.i:2169: every sample times amplify."""
+
+    def __init__(self, src, amplify=1.0, nm="Amplification"):
+        h, _ = _new(lib().dsr_amplification_create, src._h, float(amplify), _b(nm)); FeatureStreamPtr.__init__(self, h, keep=(src,))
+
+
 class StorageFeaturePtr(_unary(lambda *a: lib().dsr_storage_create(*a), "Storage")):
     def _args(self, src):
         return ()

@@ -185,6 +185,67 @@ class MergeFeature : public VectorFloatFeatureStream {
   : _a(stat), _b(delta), _c(deltaDelta) { DSR_OP(MergeFeature, float, dsr_merge_feature_create(stat->handle(), delta->handle(), deltaDelta->handle(), nm.c_str(), &h)) }
  private: VectorFloatFeatureStreamPtr _a, _b, _c;
 };
+// ---- the scalar feature operators (feature.h:631-777, 933-970, 1594-1702, 1880-1893), include/dsr.h section 6c
+class SignalPowerFeature : public VectorFloatFeatureStream {
+ public: SignalPowerFeature(const VectorFloatFeatureStreamPtr& samp, const String& nm = "Signal Power")
+  : _s(samp) { DSR_OP(SignalPowerFeature, float, dsr_signal_power_create(samp->handle(), nm.c_str(), &h)) }
+ private: VectorFloatFeatureStreamPtr _s;
+};
+class ALogFeature : public VectorFloatFeatureStream {
+ public: ALogFeature(const VectorFloatFeatureStreamPtr& samp, double m = 1.0, double a = 4.0, bool runon = false, const String& nm = "ALog Power")
+  : _s(samp) { DSR_OP(ALogFeature, float, dsr_alog_create(samp->handle(), m, a, runon, nm.c_str(), &h)) }
+  void nextSpeaker() { dsr_throw(dsr_minmax_next_speaker(_h)); }
+ private: VectorFloatFeatureStreamPtr _s;
+};
+class NormalizeFeature : public VectorFloatFeatureStream {
+ public: NormalizeFeature(const VectorFloatFeatureStreamPtr& samp, double min = 0.0, double max = 1.0, bool runon = false, const String& nm = "Normalize")
+  : _s(samp) { DSR_OP(NormalizeFeature, float, dsr_normalize_create(samp->handle(), min, max, runon, nm.c_str(), &h)) }
+  void nextSpeaker() { dsr_throw(dsr_minmax_next_speaker(_h)); }
+ private: VectorFloatFeatureStreamPtr _s;
+};
+class ThresholdFeature : public VectorFloatFeatureStream {
+ public: ThresholdFeature(const VectorFloatFeatureStreamPtr& samp, double value = 0.0, double thresh = 1.0, const String& mode = "upper", const String& nm = "Threshold")
+  : _s(samp) { DSR_OP(ThresholdFeature, float, dsr_threshold_create(samp->handle(), value, thresh, mode.c_str(), nm.c_str(), &h)) }
+ private: VectorFloatFeatureStreamPtr _s;
+};
+class SpectralResamplingFeature : public VectorFeatureStream {
+ public: SpectralResamplingFeature(const VectorFeatureStreamPtr& src, double ratio = 16.0 / 22.05, unsigned len = 0, const String& nm = "Resampling")
+  : _s(src) { DSR_OP(SpectralResamplingFeature, double, dsr_spectral_resampling_create(src->handle(), ratio, len, nm.c_str(), &h)) }
+ private: VectorFeatureStreamPtr _s;
+};
+class SphinxMelFeature : public VectorFeatureStream {
+ public: SphinxMelFeature(const VectorFeatureStreamPtr& mag, unsigned fftN = 512, unsigned powerN = 0, float sampleRate = 16000.0, float lowerF = 0.0, float upperF = 0.0,
+                          unsigned filterN = 30, const String& nm = "Sphinx Mel Filter Bank")
+  : _s(mag) { DSR_OP(SphinxMelFeature, double, dsr_sphinx_mel_feature_create(mag->handle(), fftN, powerN, sampleRate, lowerF, upperF, filterN, nm.c_str(), &h)) }
+ private: VectorFeatureStreamPtr _s;
+};
+class ZeroCrossingRateHammingFeature : public VectorFloatFeatureStream {
+ public: ZeroCrossingRateHammingFeature(const VectorFloatFeatureStreamPtr& samp, const String& nm = "Zero Crossing Rate Hamming")
+  : _s(samp) { DSR_OP(ZeroCrossingRateHammingFeature, float, dsr_zcr_hamming_create(samp->handle(), nm.c_str(), &h)) }
+ private: VectorFloatFeatureStreamPtr _s;
+};
+class YINPitchFeature : public VectorFloatFeatureStream {
+ public: YINPitchFeature(const VectorFloatFeatureStreamPtr& samp, unsigned samplerate = 16000, float threshold = 0.5, const String& nm = "YIN Pitch")
+  : _s(samp) { DSR_OP(YINPitchFeature, float, dsr_yin_pitch_create(samp->handle(), samplerate, threshold, nm.c_str(), &h)) }
+ private: VectorFloatFeatureStreamPtr _s;
+};
+class SpikeFilter : public VectorFloatFeatureStream {
+ public: SpikeFilter(const VectorFloatFeatureStreamPtr& src, unsigned tapN = 3, const String& nm = "Spike Filter")
+  : _s(src) { DSR_OP(SpikeFilter, float, dsr_spike_filter_create(src->handle(), tapN, nm.c_str(), &h)) }
+ private: VectorFloatFeatureStreamPtr _s;
+};
+class SpikeFilter2 : public VectorFloatFeatureStream {
+ public: SpikeFilter2(const VectorFloatFeatureStreamPtr& src, unsigned width = 3, float maxslope = 7000.0, float startslope = 100.0, float thresh = 15.0, float alpha = 0.2,
+                      unsigned verbose = 1, const String& nm = "Spike Filter 2")
+  : _s(src) { DSR_OP(SpikeFilter2, float, dsr_spike_filter2_create(src->handle(), width, maxslope, startslope, thresh, alpha, verbose, nm.c_str(), &h)) }
+  unsigned spikesN() const { unsigned n = 0; dsr_throw(dsr_spike_filter2_spikes(_h, &n)); return n; }
+ private: VectorFloatFeatureStreamPtr _s;
+};
+class AmplificationFeature : public VectorFloatFeatureStream {
+ public: AmplificationFeature(const VectorFloatFeatureStreamPtr& src, double amplify = 1.0, const String& nm = "Amplification")
+  : _s(src) { DSR_OP(AmplificationFeature, float, dsr_amplification_create(src->handle(), amplify, nm.c_str(), &h)) }
+ private: VectorFloatFeatureStreamPtr _s;
+};
 // ---- btk/convolution/convolution.h:40-104: impulseResponse points to P samples
 class OverlapAdd : public VectorFloatFeatureStream {
  public: OverlapAdd(const VectorFloatFeatureStreamPtr& samp, const double* impulseResponse, unsigned P, unsigned fftLen = 0, const String& nm = "Overlap Add")

@@ -1338,6 +1338,78 @@ dsr_status dsr_wtmvdr_kernel_ms(const dsr_wtmvdr*, double* ms4);
 dsr_status dsr_specsmooth_run(const double* adjust_to_dev, const double* adjust_from_dev, int64_t T, int size, double* out_dev, void* stream);
 
 /* =====================================================================================
+ * 6c. The scalar feature operators of btk/feature/feature.{h,cc} (csrc/k_featops.hip): SignalPower, ZeroCrossingRateHamming, YINPitch,
+ *     SpikeFilter, SpikeFilter2, ALog, Normalize, Threshold, Amplification, SpectralResampling, SphinxMel
+ *
+ * Every call takes device arrays [U][Tmax][dim], nframes_dev int32 [U] (NULL: Tmax frames each) and a stream; frames at or past an
+ * utterance's count come out zero.  The operation order and the float / double of every intermediate are the reference's, so the results
+ * equal a restatement of its lines bit for bit (ALog: up to the device's fp64 log10).
+ * ===================================================================================== */
+/* SignalPowerFeature::next (feature.cc:1360-1378): y [U][Tmax][1] = float(sum_i double(x[i])^2 / dim / (65536^2 / 4)), i ascending */
+dsr_status dsr_signal_power_run(const float* x_dev, const int32_t* nframes_dev, int U, int Tmax, int dim, float* y_dev, void* stream);
+/* ZeroCrossingRateHammingFeature::next (feature.cc:3545-3577): y [U][Tmax][1]; the window 0.54 - 0.46 cos(2 pi i / (dim-1)) is built on the
+ * host in fp64, the float sum is widened, added to and rounded back at every step over dim-1 terms, then divided by float(dim); x >= 0 counts
+ * as positive (-0.0 too) */
+dsr_status dsr_zcr_hamming_run(const float* x_dev, const int32_t* nframes_dev, int U, int Tmax, int dim, float* y_dev, void* stream);
+/* YINPitchFeature::next (feature.cc:3584-3634): W = dim/2; d(tau) = sum_{j<W} (x[j] - x[j+tau])^2 in fp32, j ascending; tmp2 += d(tau) and
+ * y(tau) = d(tau) * float(tau) / tmp2 in fp32, tau = 1..W-1, y(0) = 1; the first tau with y(tau) < threshold and y(tau-1) < y(tau) ends the
+ * search with lag tau-1.  pitch_dev [U][Tmax][1] = float(double(samplerate) / double(lag)), 0 without a hit or with lag 0 (a silent frame's
+ * 0/0 fails both comparisons).  value_dev (may be NULL) [U][Tmax] = y at the tau that ended the search, y(W-1) when none did; chunks_dev
+ * (may be NULL) [U][Tmax] = the chunks of 64 lags the frame's wavefront evaluated (tools/bench_featops.py).  dim < 2 => DSR_E_DIMENSION.
+ * dsr_yin_kernel(dim): the kernel a frame length selects -- 4 or 1 frames a workgroup with the frame in LDS, 0 the frame read from global
+ * memory. */
+dsr_status dsr_yin_pitch_run(const float* x_dev, const int32_t* nframes_dev, int U, int Tmax, int dim, unsigned samplerate, float threshold, float* pitch_dev,
+                             float* value_dev, int32_t* chunks_dev, void* stream);
+int        dsr_yin_kernel(int dim);
+/* SpikeFilter::next (feature.cc:3639-3696), q = (tapN-1)/2: y[i] = x[i] for i < q, the median of x[i-q..i+q] for q <= i < dim-2q; y[dim-2q..dim-1]
+ * stays zero as in the reference, which never writes it.  tapN < 3, dim < tapN (the reference's refusals) and an even tapN (its window would
+ * read x[dim]) => DSR_E_DIMENSION; check: the same refusals without a device. */
+dsr_status dsr_spike_filter_check(int dim, int tapN);
+dsr_status dsr_spike_filter_run(const float* x_dev, const int32_t* nframes_dev, int U, int Tmax, int dim, int tapN, float* y_dev, void* stream);
+/* SpikeFilter2::next (feature.cc:3701-3776): the serial spike detector, frames in order, utterances in parallel.  meanslope_dev float [U] and
+ * count_dev int32 [U] are the reference's _meanslope and _count: set them to startslope and 0 for reset(); the call continues from them and
+ * leaves them behind, so an utterance run as consecutive calls equals one call.  A block is staged in LDS: dim > 16000 => DSR_E_DIMENSION. */
+dsr_status dsr_spike_filter2_run(const float* x_dev, const int32_t* nframes_dev, int U, int Tmax, int dim, unsigned width, float maxslope, float thresh, float alpha,
+                                 float* meanslope_dev, int32_t* count_dev, float* y_dev, void* stream);
+/* ALogFeature / NormalizeFeature (feature.cc:1383-1514).  state_dev double [U][2] = (min, max) of the source as the operator holds them;
+ * state_init sets (HUGE, -HUGE), i.e. nextSpeaker().  runon = 0: reset() semantics, the pair is taken over the whole utterance (all dim
+ * elements of every frame) from (HUGE, -HUGE) and every frame is processed with it -- frame t of the output from frame t of the input, what the
+ * reference computes over a random-access source.  runon = 1: the pair continues from state_dev and frame t sees frames 0..t.  Either way the
+ * final pair is left in state_dev (NULL: scratch that starts fresh).
+ * alog: y [U][Tmax][1] = float(m * log10(val)), val = double(float(max / 10^a) + x[t][0]), 1 where val <= 0 (the sum is a float sum, as the
+ * reference's expression types it).  normalize: y [U][Tmax][dim] = float(x * factor + add), factor = (ymax - ymin) / (max - min),
+ * add = ymin - min * factor in fp64; a zero range divides by zero as IEEE does. */
+dsr_status dsr_minmax_state_init(double* state_dev, int U, void* stream);
+dsr_status dsr_alog_run(const float* x_dev, const int32_t* nframes_dev, int U, int Tmax, int dim, double m, double a, int runon, double* state_dev, float* y_dev,
+                        void* stream);
+dsr_status dsr_normalize_run(const float* x_dev, const int32_t* nframes_dev, int U, int Tmax, int dim, double ymin, double ymax, int runon, double* state_dev,
+                             float* y_dev, void* stream);
+/* ThresholdFeature (feature.cc:1519-1560): compare 1 "upper" (v >= thresh -> value), -1 "lower" (v <= thresh -> value), 0 "both" (v >= thresh ->
+ * value, v <= -thresh -> -value); threshold_mode maps the name, any other is DSR_E_KEY.  AmplificationFeature (feature.cc:3927-3941):
+ * y = float(double(x) * amplify). */
+dsr_status dsr_threshold_mode(const char* mode, int* compare);
+dsr_status dsr_threshold_run(const float* x_dev, const int32_t* nframes_dev, int U, int Tmax, int dim, double value, double thresh, int compare, float* y_dev,
+                             void* stream);
+dsr_status dsr_amplify_run(const float* x_dev, const int32_t* nframes_dev, int U, int Tmax, int dim, double amplify, float* y_dev, void* stream);
+/* SpectralResamplingFeature (feature.cc:1565-1602): x double [U][Tmax][srcN] -> y double [U][Tmax][outN], outN = len or, for len 0, srcN;
+ * r = ratio * float(srcN) / float(outN); y[c] = double(float(wgt * x[low] + (1 - wgt) * x[low+1])) with float exact = c r, low = unsigned(c r),
+ * float wgt = (low+1) - exact.  r > 1 => DSR_E_CONSISTENCY.  Where low+1 = srcN the reference reads one element past the end: with weight
+ * exactly 0 that term is taken as 0, with any other weight (or low >= srcN) the configuration is DSR_E_DIMENSION.  size: outN and the refusals,
+ * without a device. */
+dsr_status dsr_spectral_resample_size(int srcN, double ratio, int len, int* outN);
+dsr_status dsr_spectral_resample_run(const double* x_dev, const int32_t* nframes_dev, int U, int Tmax, int srcN, double ratio, int len, double* y_dev, void* stream);
+/* SphinxMelFeature (feature.cc:2303-2385): the filterN x powerN matrix is built on the host in fp64 exactly as written there (unnormalised
+ * triangles, k from 1, the break at the first bin above the right edge; lowerF = upperF = 0 gives an all-zero matrix); upperF above Nyquist is
+ * DSR_E_ERROR.  apply: x double [U][Tmax][powerN] -> y double [U][Tmax][filterN], a row times the frame in fp64, k ascending. */
+typedef struct dsr_sphinx_mel dsr_sphinx_mel;
+dsr_status dsr_sphinx_mel_create(unsigned fftN, unsigned powerN, float sampleRate, float lowerF, float upperF, unsigned filterN, dsr_sphinx_mel** out);
+void       dsr_sphinx_mel_destroy(dsr_sphinx_mel*);
+int        dsr_sphinx_mel_size(const dsr_sphinx_mel*);
+int        dsr_sphinx_mel_power_n(const dsr_sphinx_mel*);
+dsr_status dsr_sphinx_mel_filters(const dsr_sphinx_mel*, double* A_host /* [filterN][powerN] */);
+dsr_status dsr_sphinx_mel_apply(dsr_sphinx_mel*, const double* x_dev, const int32_t* nframes_dev, int U, int Tmax, double* y_dev, void* stream);
+
+/* =====================================================================================
  * 7. Stream/feature-operator API  (FeatureStream<Type,item>::next/reset/size/name/current/isEnd,
  *    btk/stream/stream.h:36-75).  Operators are reference counted handles that hold their
  *    upstream(s); next() returns a pointer to the operator's own output buffer (host memory),
@@ -1545,6 +1617,25 @@ dsr_status dsr_merge_feature_create(dsr_stream* stat, dsr_stream* delta, dsr_str
 dsr_status dsr_overlap_add_create(dsr_stream* src, const double* h, int P, int fftLen, const char* name, dsr_stream** out);
 dsr_status dsr_overlap_save_create(dsr_stream* src, const double* h, int P, const char* name, dsr_stream** out);
 dsr_status dsr_overlap_save_update(dsr_stream* s, const double* delta, int n);
+/* The scalar feature operators of section 6c as streams, names and defaults of feature.i (899, 928, 958, 986, 1016, 1148, 1883, 1908, 1936,
+ * 1968, 2169).  ALog / Normalize: runon keeps (min, max) across reset() until next_speaker(); SpikeFilter2: reset() sets meanslope = startslope
+ * and count = 0 (construction too: the reference leaves both uninitialised), spikes() is the count of the utterance materialised last; verbose is
+ * accepted and ignored.  SpectralResampling and SphinxMel work on double streams; powerN 0 takes the source's size. */
+dsr_status dsr_signal_power_create(dsr_stream* samp, const char* name, dsr_stream** out);
+dsr_status dsr_alog_create(dsr_stream* samp, double m, double a, int runon, const char* name, dsr_stream** out);
+dsr_status dsr_normalize_create(dsr_stream* samp, double min, double max, int runon, const char* name, dsr_stream** out);
+dsr_status dsr_minmax_next_speaker(dsr_stream* alog_or_normalize);
+dsr_status dsr_threshold_create(dsr_stream* samp, double value, double thresh, const char* mode, const char* name, dsr_stream** out);
+dsr_status dsr_spectral_resampling_create(dsr_stream* src, double ratio, unsigned len, const char* name, dsr_stream** out);
+dsr_status dsr_sphinx_mel_feature_create(dsr_stream* mag, unsigned fftN, unsigned powerN, float sampleRate, float lowerF, float upperF, unsigned filterN,
+                                         const char* name, dsr_stream** out);
+dsr_status dsr_zcr_hamming_create(dsr_stream* samp, const char* name, dsr_stream** out);
+dsr_status dsr_yin_pitch_create(dsr_stream* samp, unsigned samplerate, float threshold, const char* name, dsr_stream** out);
+dsr_status dsr_spike_filter_create(dsr_stream* src, unsigned tapN, const char* name, dsr_stream** out);
+dsr_status dsr_spike_filter2_create(dsr_stream* src, unsigned width, float maxslope, float startslope, float thresh, float alpha, unsigned verbose, const char* name,
+                                    dsr_stream** out);
+dsr_status dsr_spike_filter2_spikes(dsr_stream* s, unsigned* n);
+dsr_status dsr_amplification_create(dsr_stream* src, double amplify, const char* name, dsr_stream** out);
 dsr_status dsr_storage_create(dsr_stream* src, const char* name, dsr_stream** out);
 dsr_status dsr_mean_subtraction_create(dsr_stream* src, double devNormFactor, int runon, const char* name, dsr_stream** out);
 /* the optional weight stream of MeanSubtractionFeature(src, weight, devNormFactor, runon) (feature.h, feature.cc:2577-2707): element 0 of its frames weighs

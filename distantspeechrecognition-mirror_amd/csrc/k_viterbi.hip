@@ -57,6 +57,7 @@ static constexpr int kFastC = 24576;               // most placements per frame 
 static constexpr int kFastE = 8190;                // most expanding tokens per frame on the register path
 static constexpr int kP1 = 16;                     // token rounds per wave in the register path's beam pass
 static constexpr int kW = 4;                        // register placements whose P6 loads are in flight together (8: 3 % slower; parked ones: kB)
+static constexpr int kProfN = 48;                  // profiling words per slot: 32 phase ticks + 12 of the size-class histogram
 static constexpr int kSideLds = 496;               // later arrivals kept in LDS (the rest go to memory)
 
 struct GraphDev {
@@ -232,18 +233,24 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
   // needed 444 more scalars than the 102 a wave has, and every use in the hot phases was a v_readlane reload from a spill lane.
   (void) argsInKernarg;
   constexpr bool PROF = (MODES & 1) != 0, EXTRA = (MODES & 2) != 0;      // EXTRA: lattice bookkeeping, topN, token dump compiled in
+  constexpr bool NARROW = (MODES & 4) != 0;                              // the state table is 2 x hashN one-word buckets (below) instead of two arrays of hashN words
   const KP KA = (KP) __builtin_amdgcn_kernarg_segment_ptr();
   KP ka = KA;
 #define RELOAD() do { ka = KA; asm volatile("" : "+s"(ka)); } while (0)
   RELOAD();
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* srow = reinterpret_cast<float*>(smem);                       // [nDist] when useLdsRow
-  // per-frame open-addressing table in LDS: destination state -> first-arrival slot (hashN buckets, 0 = unused).
+  // per-frame open-addressing table in LDS: destination state -> first-arrival slot, 2 x hashN words, 0 = unused.
+  //   wide:   hashN buckets of two words in two arrays -- hkey (state + 1; from P4 on bit31 | newest side record) and hfirst (smallest arrival slot, 0xFFFFFFFF = none)
+  //   narrow: 2 x hashN buckets of one word (graphs of at most 65 535 states) -- bit 31 chain flag (0 while placements are inserted), bits 30..15 state + 1 while
+  //           inserting / the newest side record once the flag is set, bits 14..0 the smallest arrival slot (slots < 24 576 < 2^15).  Same bytes, twice the buckets:
+  //           a register-path frame (at most kFastC = 0.75 x 2 x hashN placements) never needs a second pass, and the status and fold reads are one word.
   // Global atomics execute at the memory side on gfx950 (no L2 residency); the LDS table keeps the recombination
   // traffic on chip.  Frames with more placements than the table can take fall back to the tagged global table.
   const int useLdsRow = ka->useLdsRow, nDist = ka->nDist, hashN = ka->hashN, regionB = ka->regionB, cntCap = ka->cntCap;   // (the LDS layout: live for the whole kernel)
   unsigned* hkey = reinterpret_cast<unsigned*>(srow + (useLdsRow ? ((nDist + 3) & ~3) : 4));
   unsigned* hfirst = hkey + hashN;
+  unsigned* const tab = hkey; const int tabN = NARROW ? 2 * hashN : hashN;      // (narrow: the one-word buckets; tabN: buckets of either kind)
   Side* sideL = reinterpret_cast<Side*>(hfirst + hashN);                        // [regionB / 32] later arrivals at an occupied state
   // [cntCap] expansion counts of the list P6 wrote, by list position: the next frame's P1 scans them without waiting for the tokens to come back from memory
   unsigned short* cntL = reinterpret_cast<unsigned short*>(reinterpret_cast<unsigned char*>(hfirst + hashN) + regionB);
@@ -260,10 +267,13 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
   __shared__ int s_cnt[(kFastK + 32) * kWaves];
   __shared__ int s_err;             // register path: first arrivals per (k, wave) group, then their exclusive prefix
   __shared__ long long s_prof[32]; __shared__ long long s_tlast;
+  // profiling build: the frames by size class -- at most 8 192 placements (all in registers), up to 12 288, more (register path), memory path: frames [0..3], ticks [4..7], placements [8..11]
+  __shared__ long long s_hist[PROF ? 12 : 1]; __shared__ long long s_tfr;
   // per-utterance statistics and the cold loop state (thread 0 updates them once per frame; they used to ride in scalar registers through every phase)
   __shared__ long long s_stat[3];    // activeHypos, placements, registerFrames
   __shared__ int s_maxActive; __shared__ unsigned s_tag; __shared__ long long s_latOff;
   if (PROF && threadIdx.x < 32) s_prof[threadIdx.x] = 0;
+  if (PROF && threadIdx.x < 12) s_hist[threadIdx.x] = 0;
 #define TICK(ix) do { if (PROF && tid == 0) { const long long tn = (long long) wall_clock64(); s_prof[ix] += tn - s_tlast; s_tlast = tn; } } while (0)
   constexpr int nthr = kThreads, nw = kWaves;
   __shared__ int s_u, s_seg, s_help; __shared__ long long s_chunk;
@@ -294,7 +304,8 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
   constexpr int fastCapN = kP1 * 64 * nw;                                   // kP1 rounds of 64 tokens per wave
   const bool fastOK = ka->D.fastOK && hashN >= 8192;
   // capacities that follow from the LDS budget of this launch: table (load <= 0.75 per pass), slot offsets, LDS side records
-  const int tableC = (hashN >> 1) + (hashN >> 2), eCap = kFastE, sideLds = regionB >> 5;
+  // (regC: most placements of a register-path frame -- two passes over the wide table, one over the narrow one: the same number)
+  const int tableC = (tabN >> 1) + (tabN >> 2), regC = NARROW ? tableC : 2 * tableC, eCap = kFastE, sideLds = regionB >> 5;
 
   // time slicing: the XCD this workgroup runs on (HW_REG_XCC_ID, bits 3:0) picks its queue and its share of the utterances (u = xcd mod 8)
   // (segQueues == 1: one queue, any workgroup may take any utterance up -- the hand-over then pays device-scope fences; small grids and the tests)
@@ -341,7 +352,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
     int bufCur = 0, bufNxt = 1, bufSpr = 2;
     int n = 1; long arenaOff = 0, chunkEnd = 0, arenaUsed = 0;             // arenaUsed: back-pointer records of the utterance so far (time slicing: its runs of the pool are not contiguous)
     double thresh = HUGE_VAL, topScore = HUGE_VAL;
-    for (int i = tid; i < 2 * hashN; i += nthr) hkey[i] = (i < hashN) ? 0u : 0xFFFFFFFFu;
+    for (int i = tid; i < 2 * hashN; i += nthr) hkey[i] = (NARROW || i < hashN) ? 0u : 0xFFFFFFFFu;
     if (seg == 0) {
       if (tid == 0) {
         s_stat[0] = 0; s_stat[1] = 0; s_stat[2] = 0; s_maxActive = 0; s_latOff = 0;
@@ -396,7 +407,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
       const float* rowG = sc + (size_t) fr * nDist;                            // the frame's score row in memory
       int numNew = 0, numStat = -1;                                           // tokens written to the new list / tokens the reference's list would hold
       if (fr > 0) TICK(23);                                                   // end of the frame before -> here
-      if (PROF && tid == 0) s_tlast = (long long) wall_clock64();
+      if (PROF && tid == 0) { s_tlast = (long long) wall_clock64(); s_tfr = s_tlast; }
       bool fast = fastOK && mode == 0 && n <= fastCapN && !(EXTRA && (ka->D.latOn || ka->D.topN > 0));   // lattice bookkeeping needs every placement in memory: the memory path has them
       int Cfr = 0;                                                             // placements of this frame (statistics)
 
@@ -464,7 +475,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
           cbase = __builtin_amdgcn_readlane(sa - a, wu); ebase = __builtin_amdgcn_readlane(sb - b, wu);
         }
         TICK(19);
-        if (!(C > fastCapC || E > eCap || C > 2 * tableC)) {
+        if (!(C > fastCapC || E > eCap || C > regC)) {
           // ---- P2: compact list of the expanding tokens (their slot offsets in LDS, the tokens themselves in memory); a bitmap
           // of the slots where a token's run starts and the token count before every group of 64 slots turn "slot -> token"
           // into a population count
@@ -482,7 +493,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
           __syncthreads();
         }
         } else __syncthreads();                                                // (laid out by the frame before; this barrier: the score row is in LDS)
-        if (C > fastCapC || E > eCap || C > 2 * tableC) { fast = false; __syncthreads(); }     // uniform: the memory path redoes the frame
+        if (C > fastCapC || E > eCap || C > regC) { fast = false; __syncthreads(); }     // uniform: the memory path redoes the frame
         else {
           RELOAD();
           const bool ident = (E == n);
@@ -494,8 +505,10 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
           // the frame loop -- hoisted out of it, those hundred-odd invariants would live in scratch memory)
           int tq = tid; asm volatile("" : "+v"(tq)); const int lq = tq & 63, wq = tq >> 6;
           // ---- P3: slots c = k * nthr + tid (neighbouring lanes expand neighbouring arcs of the same few tokens).
-          // A placement is four words: ac, lm, expansion record (bit30: silence arc) and ek = compact token index | table
-          // bucket << 13 (after the fold: bit31 | side index when a later arrival won).  The first kFastK per thread stay in
+          // A placement is four words: ac, lm, expansion record (bit30: silence arc) and ek = compact token index (bits 0..12) | table
+          // bucket << 13 (wide: 14 bits and bit 27 = waits for the second pass; narrow: 15 bits) | bit 28: in the table, not folded yet
+          // (bit 29, between token load and expansion only: the token's edge was a silence edge; after the fold: bit31 | side index when
+          // a later arrival won).  The first kFastK per thread stay in
           // registers for the whole frame; slots beyond (one more batch of eight) are parked in memory between the phases.
           const int K = (C + nthr - 1) / nthr;
           float qac[kFastK], qlm[kFastK]; int qrec[kFastK]; unsigned ek[kFastK];
@@ -509,10 +522,21 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
 #pragma unroll
           for (int k = 0; k < kFastK; k++) { qac[k] = 0.0f; qlm[k] = 0.0f; qrec[k] = 0; ek[k] = 0u; }
 
-          const int nPass = (C > tableC) ? 2 : 1;
+          const int nPass = (!NARROW && C > tableC) ? 2 : 1;
           auto table_insert = [&](const unsigned dst, const unsigned prod, const int c) __attribute__((always_inline)) -> unsigned {
             const unsigned key = dst + 1u;
-            unsigned h = (prod >> 7) & (unsigned) (hashN - 1); int probes = 0;
+            unsigned h = (prod >> 7) & (unsigned) (tabN - 1); int probes = 0;
+            if (NARROW) {
+              const unsigned w = (key << 15) | (unsigned) c;                   // (the flag is clear while placements are inserted: equal keys = equal high bits, the min is over the slot)
+              for (;;) {
+                const unsigned kk = atomicCAS(&tab[h], 0u, w);
+                if (kk == 0u) break;
+                if ((kk >> 15) == key) { atomicMin(&tab[h], w); break; }
+                h = (h + 1u) & (unsigned) (tabN - 1);
+                if (++probes > tabN) { s_err = 1; break; }                     // table full: cannot happen below its capacity; fail loudly, never spin
+              }
+              return h;
+            }
             for (;;) {
               const unsigned kk = atomicCAS(&hkey[h], 0u, key);
               if (kk == 0u || kk == key) break;
@@ -521,6 +545,23 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
             }
             atomicMin(&hfirst[h], (unsigned) c);
             return h;
+          };
+          // what P4 and the fold ask of a bucket, for either table.  Narrow: nothing changes a word's slot field after P3's barrier, so "am I the first arrival"
+          // needs no barrier against the pushes of P4; a push keeps the slot field and retries only when another later arrival of the same state got in between.
+          constexpr unsigned ekBucket = NARROW ? 0x7FFFu : 0x3FFFu;            // the bucket in ek, bits 13.. (wide: bit 27 = the state waits for the second pass)
+          auto in_pass = [&](const unsigned e, const int pass) __attribute__((always_inline)) -> bool { return NARROW || (int) ((e >> 27) & 1u) == pass; };
+          auto is_first = [&](const unsigned h, const int c) __attribute__((always_inline)) -> bool { return NARROW ? (tab[h] & 0x7FFFu) == (unsigned) c : hfirst[h] == (unsigned) c; };
+          auto push_side = [&](const unsigned h, const int sx) __attribute__((always_inline)) -> unsigned {      // -> the record's 'next': bit31 | older side record, or a word without bit31
+            if (NARROW) {
+              unsigned old = tab[h];
+              for (;;) { const unsigned prev = atomicCAS(&tab[h], old, 0x80000000u | ((unsigned) sx << 15) | (old & 0x7FFFu)); if (prev == old) break; old = prev; }
+              return (old & 0x80000000u) ? (0x80000000u | ((old >> 15) & 0xFFFFu)) : 0u;
+            }
+            return atomicExch(&hkey[h], 0x80000000u | (unsigned) sx);
+          };
+          auto chain_head = [&](const unsigned h) __attribute__((always_inline)) -> unsigned {                  // bit31 | newest side record, or a word without bit31
+            if (NARROW) { const unsigned w = tab[h]; return (w & 0x80000000u) ? (0x80000000u | ((w >> 15) & 0xFFFFu)) : 0u; }
+            return hkey[h];
           };
           // slot -> (compact token index, position in its expansion list), then the token: score halves into the placement's own registers,
           // record index = first record of the node + position, bit29 of ek = the token's edge was a silence edge
@@ -609,7 +650,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
                 // state table: claim the bucket, keep the smallest slot (with two passes, the other half of the states waits)
                 if (PROF) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); TICK(29); }
                 const unsigned prod = (unsigned) xd[i].x * 2654435761u;
-                if (nPass > 1 && (prod >> 31)) ek8[i] |= 1u << 27;
+                if (!NARROW && nPass > 1 && (prod >> 31)) ek8[i] |= 1u << 27;
                 else ek8[i] |= (table_insert((unsigned) xd[i].x, prod, c) << 13) | (1u << 28);      // bit28: in the table, not folded yet
                 if (PROF) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); TICK(30); }
               }
@@ -682,12 +723,12 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
 #pragma unroll
             for (int i = 0; i < kB; i++) {
               const int c = (g8 + i) * nthr + tq;
-              if (c < C && (ek8[i] & (1u << 28)) && (int) ((ek8[i] >> 27) & 1u) == pass && !((firstMask >> (g8 + i)) & 1ull)) {
-                const unsigned h = (ek8[i] >> 13) & 0x3FFFu;
-                if (hfirst[h] == (unsigned) c) firstMask |= 1ull << (g8 + i);
+              if (c < C && (ek8[i] & (1u << 28)) && in_pass(ek8[i], pass) && !((firstMask >> (g8 + i)) & 1ull)) {
+                const unsigned h = (ek8[i] >> 13) & ekBucket;
+                if (is_first(h, c)) firstMask |= 1ull << (g8 + i);
                 else if (!((double) __fadd_rn(ac8[i], lm8[i]) > doomT)) {
                   const int sx = atomicAdd(&s_sideN, 1);
-                  const unsigned nx = atomicExch(&hkey[h], 0x80000000u | (unsigned) sx);
+                  const unsigned nx = push_side(h, sx);
                   Side sd; sd.ttl = tt[i]; sd.ac = ac8[i]; sd.lm = lm8[i]; sd.rec = rec8[i]; sd.prevBp = pb[i]; sd.c = c; sd.next = nx;
                   if (sx < sideLds) sideL[sx] = sd; else side[sx] = sd;
                 }
@@ -718,9 +759,9 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
           // the deferred round (its head goes to *defer): there the lanes of a wave replay their chains side by side instead of one
           // placement slot after the other with a single lane at work.
           auto fold1 = [&](const int k, const int pass, float& ac, float& lm, int& rec, unsigned& ekk, unsigned* defer) __attribute__((always_inline)) {
-            const bool mine = ((firstMask >> k) & 1ull) && !(ekk & 0x80000000u) && (ekk & (1u << 28)) && (int) ((ekk >> 27) & 1u) == pass;
+            const bool mine = ((firstMask >> k) & 1ull) && !(ekk & 0x80000000u) && (ekk & (1u << 28)) && in_pass(ekk, pass);
             if (mine) {
-              const unsigned head = hkey[(ekk >> 13) & 0x3FFFu];
+              const unsigned head = chain_head((ekk >> 13) & ekBucket);
               ekk &= 0x1FFFu;
               if (head & 0x80000000u) {
                 int wIdx = -1;
@@ -750,7 +791,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
             }
           };
           for (int pass = 0; pass < nPass; pass++) {
-            if (pass > 0) {
+            if (!NARROW && pass > 0) {
               __syncthreads();                                                 // every chain of the pass before has been folded
               { uint4* h4 = reinterpret_cast<uint4*>(hkey); const int q4 = hashN >> 2;
                 for (int i = tq; i < 2 * q4; i += nthr) { unsigned wv = (i < q4) ? 0u : 0xFFFFFFFFu; asm volatile("" : "+v"(wv)); h4[i] = make_uint4(wv, wv, wv, wv); }   /* (opaque: a hoisted constant vector lived through the whole frame loop, partly in scratch) */ }
@@ -770,10 +811,9 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
               unsigned later = 0u;
 #pragma unroll
               for (int k = 0; k < kFastK; k++) {
-                const bool cand = k < K && k * nthr + tq < C && (ek[k] & (1u << 28)) && (int) ((ek[k] >> 27) & 1u) == pass && !((firstMask >> k) & 1ull);
+                const bool cand = k < K && k * nthr + tq < C && (ek[k] & (1u << 28)) && in_pass(ek[k], pass) && !((firstMask >> k) & 1ull);
                 if (cand) {
-                  const unsigned f1 = hfirst[(ek[k] >> 13) & 0x3FFFu];
-                  if (f1 == (unsigned) (k * nthr + tq)) firstMask |= 1ull << k;
+                  if (is_first((ek[k] >> 13) & ekBucket, k * nthr + tq)) firstMask |= 1ull << k;
                   else if (!((double) __fadd_rn(qac[k], qlm[k]) > doomT)) later |= 1u << k;
                 }
               }
@@ -787,9 +827,9 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
                   for (int j = 1; j < kFastK; j++) ekk = (k == j) ? ek[j] : ekk;
                   const int c = k * nthr + tq;
                   const double tt = ttlS[c]; const uint32_t pb = ctk[ekk & 0x1FFFu].bp;
-                  const unsigned h = (ekk >> 13) & 0x3FFFu;
+                  const unsigned h = (ekk >> 13) & ekBucket;
                   const int sx = atomicAdd(&s_sideN, 1);
-                  const unsigned nx = atomicExch(&hkey[h], 0x80000000u | (unsigned) sx);
+                  const unsigned nx = push_side(h, sx);
                   float ac = qac[0], lm = qlm[0]; int rec = qrec[0];
 #pragma unroll
                   for (int j = 1; j < kFastK; j++) { const bool is = (k == j); ac = is ? qac[j] : ac; lm = is ? qlm[j] : lm; rec = is ? qrec[j] : rec; }
@@ -861,7 +901,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
           TICK(14);
           {                                                                    // every chain has been folded: the state table is dead.  Wiped here, under wave 0's prefix sum
             uint4* h4 = reinterpret_cast<uint4*>(hkey); const int q4 = hashN >> 2;
-            for (int i = tq; i < 2 * q4; i += nthr) { unsigned wv = (i < q4) ? 0u : 0xFFFFFFFFu; asm volatile("" : "+v"(wv)); h4[i] = make_uint4(wv, wv, wv, wv); }
+            for (int i = tq; i < 2 * q4; i += nthr) { unsigned wv = (NARROW || i < q4) ? 0u : 0xFFFFFFFFu; asm volatile("" : "+v"(wv)); h4[i] = make_uint4(wv, wv, wv, wv); }
           }
           if (wq == 0) {                                                       // exclusive prefix over (k, wave) = slot order of the groups
             const int nG = K * nw;                                             // <= 6 * 64
@@ -947,7 +987,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
               for (int i = 0; i < 2; i++) {
                 const int f = f0 + i * nthr + tq; const bool on = f < numNew;
                 en[i] = stage[on ? f : 0];
-                if (on) { unsigned wv = (f < q4) ? 0u : 0xFFFFFFFFu; asm volatile("" : "+v"(wv)); stage[f] = make_uint4(wv, wv, wv, wv); }
+                if (on) { unsigned wv = (NARROW || f < q4) ? 0u : 0xFFFFFFFFu; asm volatile("" : "+v"(wv)); stage[f] = make_uint4(wv, wv, wv, wv); }
               }
 #pragma unroll
               for (int i = 0; i < 2; i++) {
@@ -1074,7 +1114,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
       if (C > ka->D.maxCand) { status = DSR_E_ALLOCATION; break; }
       if (EXTRA && ka->D.latOn && s_latOff + C > ka->D.latCap) { status = DSR_E_ALLOCATION; break; }
       Cfr = C;
-      const bool useHash = hashN > 0 && C <= (hashN >> 1) + (hashN >> 2);        // load factor <= 0.75 even if every placement is a new state
+      const bool useHash = hashN > 0 && C <= tableC;                             // load factor <= 0.75 even if every placement is a new state (narrow: 24 576 -- and every slot fits the word's 15 bits)
       // ---------------- phase A2: absolute offsets + owner fill
       for (int i = tid; i < n; i += nthr) {
         const int cnt = tokCnt[i];
@@ -1136,13 +1176,23 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
         const double ttl = __dadd_rn(ac, lm);
         CandA a2; a2.ttl = ttl; a2.ac = (float) ac; a2.lm = (float) lm; cA[c] = a2;
         if (useHash) {
-          unsigned h = ((unsigned) dst * 2654435761u) >> 7 & (unsigned) (hashN - 1);
-          for (;;) {
-            const unsigned k = atomicCAS(&hkey[h], 0u, (unsigned) dst + 1u);
-            if (k == 0u || k == (unsigned) dst + 1u) break;
-            h = (h + 1u) & (unsigned) (hashN - 1);
+          unsigned h = ((unsigned) dst * 2654435761u) >> 7 & (unsigned) (tabN - 1);
+          if (NARROW) {
+            const unsigned key = (unsigned) dst + 1u, w = (key << 15) | (unsigned) c;
+            for (;;) {
+              const unsigned k = atomicCAS(&tab[h], 0u, w);
+              if (k == 0u) break;
+              if ((k >> 15) == key) { atomicMin(&tab[h], w); break; }
+              h = (h + 1u) & (unsigned) (tabN - 1);
+            }
+          } else {
+            for (;;) {
+              const unsigned k = atomicCAS(&hkey[h], 0u, (unsigned) dst + 1u);
+              if (k == 0u || k == (unsigned) dst + 1u) break;
+              h = (h + 1u) & (unsigned) (hashN - 1);
+            }
+            atomicMin(&hfirst[h], (unsigned) c);
           }
-          atomicMin(&hfirst[h], (unsigned) c);
           rank[c] = (int) h;
         } else atomicMin(&first[dst], tagw | (unsigned) c);
         chead[c] = -1;
@@ -1158,12 +1208,12 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
       // ---------------- phase C0: later arrivals hang themselves on their state's first-arrival placement
       for (int c = tid; c < C; c += nthr) {
         int f;
-        if (useHash) f = (int) hfirst[rank[c]];
+        if (useHash) f = NARROW ? (int) (tab[rank[c]] & 0x7FFFu) : (int) hfirst[rank[c]];
         else { const int dst = cB[c].dst; f = (int) (ld_u32(&first[dst]) & 0x00FFFFFFu); }
         if (f != c) { const int nx = atomicExch(&chead[f], c); cB[c].next = nx; chead[c] = -2; }      // -2: not a first arrival
       }
       __syncthreads();
-      if (useHash) for (int i = tid; i < 2 * hashN; i += nthr) hkey[i] = (i < hashN) ? 0u : 0xFFFFFFFFu;   // ready for the next frame
+      if (useHash) for (int i = tid; i < 2 * hashN; i += nthr) hkey[i] = (NARROW || i < hashN) ? 0u : 0xFFFFFFFFu;   // ready for the next frame
       // ---------------- phase C1: fold per destination state (by its first-arrival thread), count new tokens
       const int chunkC = ((C + nw * 64 - 1) / (nw * 64)) * 64;
       // (as on the register path: tokens above this frame's best emitting total + beam are counted but not written)
@@ -1252,6 +1302,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
       }   // memory path
       __syncthreads();
       TICK(fast ? 7 : 8);
+      if (PROF && tid == 0 && mode == 0) { const int cls = !fast ? 3 : Cfr <= kFastK * nthr ? 0 : Cfr <= 12288 ? 1 : 2; s_hist[cls] += 1; s_hist[4 + cls] += s_tlast - s_tfr; s_hist[8 + cls] += Cfr; }
       RELOAD();
       if (mode == 0) {
         if (dump) {
@@ -1394,7 +1445,8 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
   }
   RELOAD();
   if (tid == 0) ka->D.tags[slot] = s_tag;
-  if (PROF && tid < 32) ka->D.prof[slot * 32 + tid] = s_prof[tid];
+  if (PROF && tid < 32) ka->D.prof[slot * kProfN + tid] = s_prof[tid];
+  if (PROF && tid < 12) ka->D.prof[slot * kProfN + 32 + tid] = s_hist[tid];
 #undef TICK
 #undef RELOAD
 #undef TOKA
@@ -1809,7 +1861,6 @@ dsr_status dsr_decoder_decode_launch(dsr_decoder* d, const float* score, const i
     D.silenceX = d->cfg.silenceX; D.maxTok = d->cfg.maxActive; D.maxCand = d->cfg.maxCandidates; D.arenaCap = d->arenaCap;
     D.tokA = d->d_tokA.p; D.tokB = d->d_tokB.p; D.ctok = d->d_ctok.p; D.side = d->d_side.p; D.fastOK = d->fastOK; D.tokOff = d->d_tokOff.p; D.owner = d->d_owner.p; D.rank = d->d_rank.p; D.cA = d->d_cA.p; D.cB = d->d_cB.p;
     D.first = d->d_first.p; D.tags = d->d_tags.p; D.tokCnt = d->d_tokCnt.p; D.chead = d->d_chead.p; D.arena = d->d_arena.p; D.queue = d->d_queue.p;
-    if (getenv("DSR_VITERBI_SEG_VERBOSE")) fprintf(stderr, "[dsr viterbi] %d utterances on %d workgroups: %s\n", U, slots, segFrames > 0 ? (segQueues == 8 ? "time-sliced, XCD-bound queues" : "time-sliced, one queue") : "run to completion");
     D.segDrop = getenv("DSR_VITERBI_SEG_DROP") ? (int) strtol(getenv("DSR_VITERBI_SEG_DROP"), nullptr, 0) : 0;
     D.segQueues = segQueues; D.segFrames = segFrames; D.segCount = segFrames > 0 ? (Tmax + segFrames) / segFrames : 1;            // segments cover frames 0 .. Tmax (the end expansion is "frame" T)
     D.poolCap = 0; D.poolChunk = 0; D.poolNext = nullptr; D.segState = nullptr; D.segDone = nullptr; D.saveA = nullptr; D.saveB = nullptr;
@@ -1823,7 +1874,7 @@ dsr_status dsr_decoder_decode_launch(dsr_decoder* d, const float* score, const i
     }
     d->lastPoolCap = D.poolCap;
     D.prof = nullptr;
-    if (getenv("DSR_VITERBI_PROF")) { d->d_prof.reserve((size_t) slots * 32); D.prof = d->d_prof.p; }
+    if (getenv("DSR_VITERBI_PROF")) { d->d_prof.reserve((size_t) slots * kProfN); D.prof = d->d_prof.p; }
     D.dumpOn = d->dumpOn; D.dumpCap = d->dumpCap; D.dumpFrameOff = d->d_dumpFrameOff.p; D.dumpNode = d->d_dumpNode.p; D.dumpAc = d->d_dumpAc.p;
     D.dumpLm = d->d_dumpLm.p; D.dumpArc = d->d_dumpArc.p; D.dumpCount = d->d_dumpCount.p;
     D.topN = d->cfg.topN > 0 ? d->cfg.topN : 0; D.tokA3 = nullptr; D.tokB3 = nullptr;
@@ -1837,11 +1888,13 @@ dsr_status dsr_decoder_decode_launch(dsr_decoder* d, const float* score, const i
       D.latCap = (long) cap; D.lat = d->d_lat.p; D.latTtl = d->d_latTtl.p; D.latFrameOff = d->d_latFrameOff.p; D.arenaLat = d->d_arenaLat.p; D.latFinal = d->d_latFinal.p; D.latInfo = d->d_latInfo.p;
       d->latU = U; d->latTmax = Tmax; d->latArenaCap = d->arenaCap;
     } else d->latU = 0;
-    // LDS: [score row][state table: 2 x hashN words][slot offsets of the expanding tokens]; the row stays in global memory
-    // when it would push the state table below the size the register path needs.  One 1024-thread workgroup per CU (16384 buckets).  The region
-    // after the table holds the slot offsets (u16 per expanding token) and later the LDS side records.
-    // instantiations: bit 0 per-phase ticks (DSR_VITERBI_PROF), bit 1 lattice bookkeeping / topN / token dump compiled in
-    const int modes = (D.prof ? 1 : 0) | ((latOn || D.topN > 0 || d->dumpOn) ? 2 : 0);
+    // LDS: [score row][state table: 2 x hashN words][later arrivals' side records][expansion counts]; the row stays in global memory
+    // when it would push the state table below the size the register path needs.  One 1024-thread workgroup per CU.  The table's 2 x hashN words are
+    // hashN = 16 384 two-word buckets (wide: key array + first-arrival array) or, for graphs of at most 65 535 states, 32 768 one-word buckets
+    // (narrow: flag | key or side record | slot) -- the formula below gives the same number of bytes for both, 128 KB at hashN = 16 384.
+    // instantiations: bit 0 per-phase ticks (DSR_VITERBI_PROF), bit 1 lattice bookkeeping / topN / token dump compiled in, bit 2 narrow table
+    // (chosen below, once hashN is known; the static LDS does not depend on it)
+    int modes = (D.prof ? 1 : 0) | ((latOn || D.topN > 0 || d->dumpOn) ? 2 : 0);
     const void* kfn = modes == 0 ? (const void*) k_viterbi<0> : modes == 1 ? (const void*) k_viterbi<1> : modes == 2 ? (const void*) k_viterbi<2> : (const void*) k_viterbi<3>;
     hipFuncAttributes fattr; DSR_HIP(hipFuncGetAttributes(&fattr, kfn));
     const size_t eoffB = (size_t) kSideLds * sizeof(Side); const size_t ldsCap = (size_t) 160 * 1024 - fattr.sharedSizeBytes;      // what the kernel's static LDS leaves of a CU's 160 KB
@@ -1855,12 +1908,19 @@ dsr_status dsr_decoder_decode_launch(dsr_decoder* d, const float* score, const i
     int cntCap = (hashN > 0 && d->maxCnt < 65536 && rowB + (size_t) hashN * 8 + eoffB + 4096 <= ldsCap) ? 2048 : 0;
     if (getenv("DSR_VITERBI_NOCNT")) cntCap = 0;
     const size_t lds = rowB + (size_t) hashN * 8 + eoffB + 2 * (size_t) cntCap;
+    // narrow table: the key field holds state + 1 in 16 bits, the slot field 15 bits = the 24 576 placements 32 768 buckets take at a load of 0.75
+    // (DSR_VITERBI_TABLE=wide: the two-array table whatever the graph -- A/B runs and the tests)
+    const char* const tableEnv = getenv("DSR_VITERBI_TABLE");
+    const bool narrow = d->nNodes <= 65535 && hashN == hashMax && !(tableEnv && !strcmp(tableEnv, "wide"));
+    if (narrow) modes |= 4;
+    if (getenv("DSR_VITERBI_SEG_VERBOSE")) fprintf(stderr, "[dsr viterbi] %d utterances on %d workgroups: %s, %s state table\n", U, slots, segFrames > 0 ? (segQueues == 8 ? "time-sliced, XCD-bound queues" : "time-sliced, one queue") : "run to completion", narrow ? "narrow" : "wide");
     VitArgs A; A.G = G; A.D = D; A.scores = score; A.nframesArr = nframes; A.U = U; A.Tmax = Tmax; A.nDist = nDist; A.res = d->d_res.p;
     A.arcsOut = (arcs_out || words_out) ? d->d_arcs.p : nullptr; A.wordsOut = (arcs_out || words_out) ? d->d_words.p : nullptr; A.maxPath = maxPath;
     A.useLdsRow = useLds; A.hashN = hashN; A.regionB = (int) eoffB; A.cntCap = cntCap;
 #define DSR_LAUNCH_V(MM) { DSR_HIP(hipFuncSetAttribute((const void*) k_viterbi<MM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); \
       hipLaunchKernelGGL(k_viterbi<MM>, dim3(slots), dim3(kThreads), lds, st, A); }
-    switch (modes) { case 0: DSR_LAUNCH_V(0) break; case 1: DSR_LAUNCH_V(1) break; case 2: DSR_LAUNCH_V(2) break; default: DSR_LAUNCH_V(3) break; }
+    switch (modes) { case 0: DSR_LAUNCH_V(0) break; case 1: DSR_LAUNCH_V(1) break; case 2: DSR_LAUNCH_V(2) break; case 3: DSR_LAUNCH_V(3) break;
+                     case 4: DSR_LAUNCH_V(4) break; case 5: DSR_LAUNCH_V(5) break; case 6: DSR_LAUNCH_V(6) break; default: DSR_LAUNCH_V(7) break; }
 #undef DSR_LAUNCH_V
     DSR_HIP(hipGetLastError());
     const size_t nPath = want_paths ? (size_t) U * maxPath : 0;
@@ -1890,16 +1950,23 @@ dsr_status dsr_decoder_decode_collect(dsr_decoder* d, dsr_decode_result* res, in
       fprintf(stderr, "[dsr viterbi] pool of back-pointer records: %.1f M of %.1f M taken\n", used / 1e6, d->lastPoolCap / 1e6);
     }
     if (prof) {
-      std::vector<long long> hp((size_t) slots * 32); DSR_HIP(hipMemcpy(hp.data(), prof, hp.size() * sizeof(long long), hipMemcpyDeviceToHost));
-      double acc[32] = {0}; for (int s2 = 0; s2 < slots; s2++) for (int i = 0; i < 32; i++) acc[i] += (double) hp[(size_t) s2 * 32 + i];
+      std::vector<long long> hp((size_t) slots * kProfN); DSR_HIP(hipMemcpy(hp.data(), prof, hp.size() * sizeof(long long), hipMemcpyDeviceToHost));
+      double acc[32] = {0}; for (int s2 = 0; s2 < slots; s2++) for (int i = 0; i < 32; i++) acc[i] += (double) hp[(size_t) s2 * kProfN + i];
       fprintf(stderr, "[dsr viterbi prof] mean us per slot:");
       for (int i = 0; i < 32; i++) if (i != 15) fprintf(stderr, " p%d=%.0f", i, acc[i] / slots / 100.0);
       fprintf(stderr, "\n");
       double tmin = 1e30, tmax = 0.0, tsum = 0.0;                   // busy time per slot: how even the slots' shares of the batch were
-      for (int s2 = 0; s2 < slots; s2++) { double t = 0.0; for (int i = 0; i < 32; i++) if (i != 15) t += (double) hp[(size_t) s2 * 32 + i]; t /= 100.0; tsum += t; if (t < tmin) tmin = t; if (t > tmax) tmax = t; }
+      for (int s2 = 0; s2 < slots; s2++) { double t = 0.0; for (int i = 0; i < 32; i++) if (i != 15) t += (double) hp[(size_t) s2 * kProfN + i]; t /= 100.0; tsum += t; if (t < tmin) tmin = t; if (t > tmax) tmax = t; }
+      {                                                             // frames by size class: share of the frames, share of their time, us per frame, ns per placement
+        double h[12] = {0}; for (int s2 = 0; s2 < slots; s2++) for (int i = 0; i < 12; i++) h[i] += (double) hp[(size_t) s2 * kProfN + 32 + i];
+        const double nf = h[0] + h[1] + h[2] + h[3], tk = h[4] + h[5] + h[6] + h[7];
+        static const char* const cn[4] = {"<=8192", "<=12288", ">12288", "memory path"};
+        for (int c = 0; c < 4; c++) if (h[c] > 0) fprintf(stderr, "[dsr viterbi prof] frames with %s placements: %.1f %% of the frames, %.1f %% of the frame time, %.1f us per frame, %.2f ns per placement\n",
+                                                          cn[c], 100.0 * h[c] / nf, 100.0 * h[4 + c] / tk, h[4 + c] / 100.0 / h[c], h[4 + c] * 10.0 / h[8 + c]);
+      }
       fprintf(stderr, "[dsr viterbi prof] busy us per slot: mean %.0f min %.0f max %.0f\n", tsum / slots, tmin, tmax);
       if (slots >= 64 && slots % 8 == 0) {                       // by XCD (workgroup i runs on XCD i mod 8): how even the eight queues of the time-sliced decode come out
-        double bx[8] = {0}; for (int s2 = 0; s2 < slots; s2++) { double t = 0.0; for (int i = 0; i < 32; i++) if (i != 15) t += (double) hp[(size_t) s2 * 32 + i]; bx[s2 & 7] += t / 100.0; }
+        double bx[8] = {0}; for (int s2 = 0; s2 < slots; s2++) { double t = 0.0; for (int i = 0; i < 32; i++) if (i != 15) t += (double) hp[(size_t) s2 * kProfN + i]; bx[s2 & 7] += t / 100.0; }
         fprintf(stderr, "[dsr viterbi prof] busy us per slot, by XCD:"); for (int q = 0; q < 8; q++) fprintf(stderr, " %.0f", bx[q] / (slots / 8)); fprintf(stderr, "\n");
       }
     }

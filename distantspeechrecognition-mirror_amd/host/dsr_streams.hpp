@@ -258,6 +258,168 @@ class OverlapSave : public VectorFloatFeatureStream {
   void update(const double* delta /* complex[n] */, unsigned n) { dsr_throw(dsr_overlap_save_update(_h, delta, (int) n)); }
  private: VectorFloatFeatureStreamPtr _s;
 };
+// ---- btk/sad/sadFeature.h: the spectral-shape operators
+class EnergyDiffusionFeature : public VectorFloatFeatureStream {
+ public: EnergyDiffusionFeature(const VectorFloatFeatureStreamPtr& src, const String& nm = "Energy Diffusion")
+  : _s(src) { DSR_OP(EnergyDiffusionFeature, float, dsr_sad_shape_create(src->handle(), 0, 0.0f, 0.0f, nm.c_str(), &h)) }
+ private: VectorFloatFeatureStreamPtr _s;
+};
+class BandEnergyRatioFeature : public VectorFloatFeatureStream {
+ public: BandEnergyRatioFeature(const VectorFloatFeatureStreamPtr& src, float sampleRate, float threshF = 0.0, const String& nm = "Band Energy Ratio")
+  : _s(src) { DSR_OP(BandEnergyRatioFeature, float, dsr_sad_shape_create(src->handle(), 1, sampleRate, threshF, nm.c_str(), &h)) }
+ private: VectorFloatFeatureStreamPtr _s;
+};
+class NegativeEntropyFeature : public VectorFloatFeatureStream {
+ public: NegativeEntropyFeature(const VectorFloatFeatureStreamPtr& src, const String& nm = "Negative Entropy")
+  : _s(src) { DSR_OP(NegativeEntropyFeature, float, dsr_sad_shape_create(src->handle(), 2, 0.0f, 0.0f, nm.c_str(), &h)) }
+ private: VectorFloatFeatureStreamPtr _s;
+};
+class SignificantSubbandsFeature : public VectorFloatFeatureStream {
+ public: SignificantSubbandsFeature(const VectorFloatFeatureStreamPtr& src, float thresh = 0.0, const String& nm = "Significant Subbands")
+  : _s(src) { DSR_OP(SignificantSubbandsFeature, float, dsr_sad_shape_create(src->handle(), 3, 0.0f, thresh, nm.c_str(), &h)) }
+ private: VectorFloatFeatureStreamPtr _s;
+};
+// ---- btk/sad/sad.h: the VAD metrics (:196-470), SimpleEnergyVAD (:109-133) and the hangover segmenters (:698-795) over include/dsr.h section 7b
+class VADMetric {
+ public:
+  virtual ~VADMetric() { if (_m) dsr_sad_metric_release(_m); }
+  virtual double next(int frameX = -5) { double v = 0.0; dsr_throw(dsr_sad_metric_next(_m, frameX, &v)); return v; }
+  virtual void reset() { dsr_throw(dsr_sad_metric_reset(_m)); }
+  virtual void nextSpeaker() { dsr_throw(dsr_sad_metric_next_speaker(_m)); }
+  double score() { double v = 0.0; dsr_throw(dsr_sad_metric_score(_m, &v)); return v; }
+  dsr_vad_metric* handle() const { return _m; }
+ protected:
+  VADMetric() : _m(0) {}
+  dsr_vad_metric* _m;
+ private:
+  VADMetric(const VADMetric&); VADMetric& operator=(const VADMetric&);
+};
+typedef std::shared_ptr<VADMetric> VADMetricPtr;
+class EnergyVADMetric : public VADMetric {
+ public: EnergyVADMetric(const VectorFloatFeatureStreamPtr& source, double initialEnergy = 5.0e+07, double threshold = 0.5, unsigned headN = 4, unsigned tailN = 10,
+                         unsigned energiesN = 200, const String& nm = "Energy VAD Metric")
+  : _s(source) { dsr_throw(dsr_sad_energy_metric_create(source->handle(), initialEnergy, threshold, headN, tailN, energiesN, nm.c_str(), &_m)); }
+  double energyPercentile(double percentile = 50.0) const { double v = 0.0; dsr_throw(dsr_sad_metric_energy_percentile(_m, percentile, &v)); return v; }
+ private: VectorFloatFeatureStreamPtr _s;
+};
+typedef std::shared_ptr<EnergyVADMetric> EnergyVADMetricPtr;
+template <typename ChannelType> class MultiChannelVADMetric : public VADMetric {
+ public:
+  void setChannel(ChannelType& chan) { dsr_throw(dsr_sad_metric_set_channel(_m, chan->handle())); _channelList.push_back(chan); }
+  void clearChannel() { dsr_throw(dsr_sad_metric_clear_channel(_m)); _channelList.clear(); }
+ protected: std::vector<ChannelType> _channelList;
+};
+typedef MultiChannelVADMetric<VectorFloatFeatureStreamPtr> FloatMultiChannelVADMetric;
+typedef MultiChannelVADMetric<VectorComplexFeatureStreamPtr> ComplexMultiChannelVADMetric;
+class PowerSpectrumVADMetric : public FloatMultiChannelVADMetric {
+ public:
+  PowerSpectrumVADMetric(unsigned fftLen, double sampleRate = 16000.0, double lowCutoff = -1.0, double highCutoff = -1.0, const String& nm = "Power Spectrum VAD Metric")
+  { dsr_throw(dsr_sad_power_metric_create(0, fftLen, sampleRate, lowCutoff, highCutoff, nm.c_str(), &_m)); }
+  const std::vector<double>& getMetrics() { _p.assign(_channelList.size(), 0.0); dsr_throw(dsr_sad_metric_powers(_m, _p.data(), (int) _p.size())); return _p; }
+  void setE0(double E0) { dsr_throw(dsr_sad_metric_set_e0(_m, E0)); }
+ protected:
+  PowerSpectrumVADMetric(int kind, unsigned fftLen, double sampleRate, double lowCutoff, double highCutoff, const String& nm)
+  { dsr_throw(dsr_sad_power_metric_create(kind, fftLen, sampleRate, lowCutoff, highCutoff, nm.c_str(), &_m)); }
+  std::vector<double> _p;
+};
+typedef std::shared_ptr<PowerSpectrumVADMetric> PowerSpectrumVADMetricPtr;
+class NormalizedEnergyMetric : public PowerSpectrumVADMetric {
+ public: NormalizedEnergyMetric(unsigned fftLen, double sampleRate = 16000.0, double lowCutoff = -1.0, double highCutoff = -1.0, const String& nm = "NormalizedEnergyMetric")
+  : PowerSpectrumVADMetric(1, fftLen, sampleRate, lowCutoff, highCutoff, nm) {}
+};
+typedef std::shared_ptr<NormalizedEnergyMetric> NormalizedEnergyMetricPtr;
+class TSPSVADMetric : public PowerSpectrumVADMetric {
+ public: TSPSVADMetric(unsigned fftLen, double sampleRate = 16000.0, double lowCutoff = -1.0, double highCutoff = -1.0, const String& nm = "TSPS VAD Metric")
+  : PowerSpectrumVADMetric(2, fftLen, sampleRate, lowCutoff, highCutoff, nm) {}
+};
+typedef std::shared_ptr<TSPSVADMetric> TSPSVADMetricPtr;
+class CCCVADMetric : public ComplexMultiChannelVADMetric {
+ public:
+  CCCVADMetric(unsigned fftLen, unsigned nCand, double sampleRate = 16000.0, double lowCutoff = -1.0, double highCutoff = -1.0, const String& nm = "CCC VAD Metric")
+  { dsr_throw(dsr_sad_ccc_metric_create(fftLen, nCand, sampleRate, lowCutoff, highCutoff, nm.c_str(), &_m)); }
+  void setNCand(unsigned nCand) { dsr_throw(dsr_sad_metric_set_ncand(_m, nCand)); }
+  void setThreshold(double threshold) { dsr_throw(dsr_sad_metric_set_threshold(_m, threshold)); }
+};
+typedef std::shared_ptr<CCCVADMetric> CCCVADMetricPtr;
+class NegentropyVADMetric : public VADMetric {
+ public:
+  NegentropyVADMetric(const VectorComplexFeatureStreamPtr& source, const VectorFloatFeatureStreamPtr& spectralEstimator, const String& shapeFactorFileName = "",
+                      double threshold = 0.5, double sampleRate = 16000.0, double lowCutoff = -1.0, double highCutoff = -1.0, const String& nm = "Negentropy VAD Metric")
+  : _source(source), _spectralEstimator(spectralEstimator)
+  { dsr_throw(dsr_sad_gg_metric_create(0, source->handle(), 0, spectralEstimator->handle(), 0, shapeFactorFileName.c_str(), -1.0, threshold, 0.95, sampleRate, lowCutoff, highCutoff, nm.c_str(), &_m)); }
+ protected:
+  NegentropyVADMetric(int kind, const VectorComplexFeatureStreamPtr& source1, const VectorComplexFeatureStreamPtr& source2, const VectorFloatFeatureStreamPtr& spectralEstimator1,
+                      const VectorFloatFeatureStreamPtr& spectralEstimator2, const String& shapeFactorFileName, double twiddle, double threshold, double beta, double sampleRate,
+                      double lowCutoff, double highCutoff, const String& nm)
+  : _source(source1), _spectralEstimator(spectralEstimator1), _source2(source2), _spectralEstimator2(spectralEstimator2)
+  { dsr_throw(dsr_sad_gg_metric_create(kind, source1->handle(), source2->handle(), spectralEstimator1->handle(), spectralEstimator2->handle(), shapeFactorFileName.c_str(), twiddle,
+                                       threshold, beta, sampleRate, lowCutoff, highCutoff, nm.c_str(), &_m)); }
+  VectorComplexFeatureStreamPtr _source; VectorFloatFeatureStreamPtr _spectralEstimator; VectorComplexFeatureStreamPtr _source2; VectorFloatFeatureStreamPtr _spectralEstimator2;
+};
+typedef std::shared_ptr<NegentropyVADMetric> NegentropyVADMetricPtr;
+class MutualInformationVADMetric : public NegentropyVADMetric {
+ public: MutualInformationVADMetric(const VectorComplexFeatureStreamPtr& source1, const VectorComplexFeatureStreamPtr& source2, const VectorFloatFeatureStreamPtr& spectralEstimator1,
+                                    const VectorFloatFeatureStreamPtr& spectralEstimator2, const String& shapeFactorFileName = "", double twiddle = -1.0, double threshold = 1.3,
+                                    double beta = 0.95, double sampleRate = 16000.0, double lowCutoff = -1.0, double highCutoff = -1.0,
+                                    const String& nm = "Mutual Information VAD Metric")
+  : NegentropyVADMetric(1, source1, source2, spectralEstimator1, spectralEstimator2, shapeFactorFileName, twiddle, threshold, beta, sampleRate, lowCutoff, highCutoff, nm) {}
+};
+typedef std::shared_ptr<MutualInformationVADMetric> MutualInformationVADMetricPtr;
+class LikelihoodRatioVADMetric : public NegentropyVADMetric {
+ public: LikelihoodRatioVADMetric(const VectorComplexFeatureStreamPtr& source1, const VectorComplexFeatureStreamPtr& source2, const VectorFloatFeatureStreamPtr& spectralEstimator1,
+                                  const VectorFloatFeatureStreamPtr& spectralEstimator2, const String& shapeFactorFileName = "", double threshold = 0.0, double sampleRate = 16000.0,
+                                  double lowCutoff = -1.0, double highCutoff = -1.0, const String& nm = "Mutual Information VAD Metric")
+  : NegentropyVADMetric(2, source1, source2, spectralEstimator1, spectralEstimator2, shapeFactorFileName, -1.0, threshold, 0.95, sampleRate, lowCutoff, highCutoff, nm) {}
+};
+typedef std::shared_ptr<LikelihoodRatioVADMetric> LikelihoodRatioVADMetricPtr;
+class SimpleEnergyVAD {
+ public:
+  SimpleEnergyVAD(VectorComplexFeatureStreamPtr& samp, double threshold, double gamma = 0.995) : _s(samp), _m(0) { dsr_throw(dsr_sad_simple_energy_create(samp->handle(), threshold, gamma, &_m)); }
+  ~SimpleEnergyVAD() { if (_m) dsr_sad_metric_release(_m); }
+  bool next(int frameX = -5) { double v = 0.0; dsr_throw(dsr_sad_metric_next(_m, frameX, &v)); return v > 0.5; }
+  void reset() { dsr_throw(dsr_sad_metric_reset(_m)); }
+  void nextSpeaker() { dsr_throw(dsr_sad_metric_next_speaker(_m)); }
+ private:
+  SimpleEnergyVAD(const SimpleEnergyVAD&); SimpleEnergyVAD& operator=(const SimpleEnergyVAD&);
+  VectorComplexFeatureStreamPtr _s; dsr_vad_metric* _m;
+};
+typedef std::shared_ptr<SimpleEnergyVAD> SimpleEnergyVADPtr;
+class HangoverVADFeature : public VectorFloatFeatureStream {
+ public:
+  HangoverVADFeature(const VectorFloatFeatureStreamPtr& source, const VADMetricPtr& metric, double threshold = 0.5, unsigned headN = 4, unsigned tailN = 10,
+                     const String& nm = "Hangover VAD Feature")
+  : _s(source) { _create(source, metric, threshold, headN, tailN, 0, nm); }
+  void nextSpeaker() { dsr_throw(dsr_sad_hangover_next_speaker(_h)); }
+  int prefixN() const { int v = 0; dsr_throw(dsr_sad_hangover_prefix_n(_h, &v)); return v; }
+ protected:
+  HangoverVADFeature(const VectorFloatFeatureStreamPtr& source, const VADMetricPtr& metric, double threshold, unsigned headN, unsigned tailN, int kind, const String& nm)
+  : _s(source) { _create(source, metric, threshold, headN, tailN, kind, nm); }
+  void _add(const VADMetricPtr& metric, double threshold) { dsr_throw(dsr_sad_hangover_add_metric(_h, metric->handle(), threshold)); _metrics.push_back(metric); }
+  int _decisionMetric() const { int v = 0; dsr_throw(dsr_sad_hangover_decision_metric(_h, &v)); return v; }
+ private:
+  void _create(const VectorFloatFeatureStreamPtr& source, const VADMetricPtr& metric, double threshold, unsigned headN, unsigned tailN, int kind, const String& nm)
+  { DSR_OP(HangoverVADFeature, float, dsr_sad_hangover_create(source->handle(), metric->handle(), threshold, headN, tailN, kind, nm.c_str(), &h)) _metrics.push_back(metric); }
+  VectorFloatFeatureStreamPtr _s; std::vector<VADMetricPtr> _metrics;
+};
+typedef std::shared_ptr<HangoverVADFeature> HangoverVADFeaturePtr;
+class HangoverMIVADFeature : public HangoverVADFeature {
+ public:
+  HangoverMIVADFeature(const VectorFloatFeatureStreamPtr& source, const VADMetricPtr& energyMetric, const VADMetricPtr& mutualInformationMetric, const VADMetricPtr& powerMetric,
+                       double energyThreshold = 0.5, double mutualInformationThreshold = 0.5, double powerThreshold = 0.5, unsigned headN = 4, unsigned tailN = 10,
+                       const String& nm = "Hangover MIVAD Feature")
+  : HangoverVADFeature(source, energyMetric, energyThreshold, headN, tailN, 1, nm) { _add(mutualInformationMetric, mutualInformationThreshold); _add(powerMetric, powerThreshold); }
+  int decisionMetric() const { return _decisionMetric(); }
+};
+typedef std::shared_ptr<HangoverMIVADFeature> HangoverMIVADFeaturePtr;
+class HangoverMultiStageVADFeature : public HangoverVADFeature {
+ public:
+  HangoverMultiStageVADFeature(const VectorFloatFeatureStreamPtr& source, const VADMetricPtr& energyMetric, double energyThreshold = 0.5, unsigned headN = 4, unsigned tailN = 10,
+                               const String& nm = "HangoverMultiStageVADFeature")
+  : HangoverVADFeature(source, energyMetric, energyThreshold, headN, tailN, 2, nm) {}
+  int decisionMetric() const { return _decisionMetric(); }
+  void setMetric(const VADMetricPtr& metricPtr, double threshold) { _add(metricPtr, threshold); }
+};
+typedef std::shared_ptr<HangoverMultiStageVADFeature> HangoverMultiStageVADFeaturePtr;
 
 // ---- btk/localization/localization.h:118-218 and btk/TDEstimator/CCTDE.h:60-101.  The reference's gsl vectors are pointers to the items here:
 // calculate() takes fftLen complex bins a spectrum, the getters return pointers into the object's own buffers (a null pointer where the

@@ -1669,6 +1669,137 @@ dsr_status dsr_htk_read_header(const char* fileName, int isBigEndian, int* nSamp
 dsr_status dsr_htk_read(const char* fileName, int isBigEndian, float* data, size_t nFloats);
 
 /* =====================================================================================
+ * 7b. Speech activity detection, btk/sad/sad.{h,cc} (csrc/k_sad.hip; line numbers are sad.cc's)
+ *
+ * Batch entries take device arrays [U][Tmax][...], nframes_dev int32 [U] (NULL: Tmax frames each) and a stream.  Frames at or past an
+ * utterance's count are never read; their outputs are zero.  Every metric returns a decision [U][Tmax] fp64 (the value next() returns) and a
+ * score [U][Tmax] fp64.  A metric with carried state is a function (input, nframes, state in) -> (outputs, state after nframes frames): the
+ * state arrays are read and written in place, and two calls that carry them equal one call.
+ * ===================================================================================== */
+/* EnergyVADMetric (:438-554).  score = the frame's energy, an fp64 sum of squares of the widened floats, i ascending (:486-490); decision 1.0
+ * where it exceeds sorted[unsigned(threshold * energiesN)] of the history, else 0.0 -- evaluated as "more than that many history entries are
+ * below it", without a sort.  hist_dev fp64 [U][energiesN] is a ring (the history's order never decides anything); counters_dev int32 [U][4] =
+ * (aboveThresholdN, belowThresholdN, recognizing, ring position).  The history takes the frame's energy only while !recognizing &&
+ * aboveThresholdN == 0, tested before the frame's counters change (:495); updates_dev (may be NULL) int32 [U] counts those frames.
+ * state_init fills the history with initialEnergy and clears the counters (nextSpeaker, :465-472); countersOnly != 0 clears
+ * (aboveThresholdN, belowThresholdN, recognizing) alone (reset, :459-463: the history survives).  threshold outside [0, 1) indexes one past the
+ * sorted array in the reference: DSR_E_DIMENSION; energiesN outside [1, 8192] likewise. */
+dsr_status dsr_sad_energy_state_init(double* hist_dev, int32_t* counters_dev, int U, int energiesN, double initialEnergy, int countersOnly, void* stream);
+dsr_status dsr_sad_energy_run(const float* x_dev, const int32_t* nframes_dev, int U, int Tmax, int dim, double threshold, unsigned headN, unsigned tailN, int energiesN,
+                              double* hist_dev, int32_t* counters_dev, double* decision_dev, double* score_dev, int32_t* updates_dev, void* stream);
+/* EnergyVADMetric::energyPercentile (:510-519) of one utterance's history on the host: sorted[int(percentile / 100 * energiesN)] / energiesN.
+ * percentile outside [0, 100] as there; 100 reads one past the array there: DSR_E_DIMENSION. */
+dsr_status dsr_sad_energy_percentile(const double* hist_host, int energiesN, double percentile, double* value);
+/* SimpleEnergyVAD::next (:174-194): X_dev complex128 [U][Tmax][fftLen]; e = sum_k |X[k]|^2 over all fftLen bins, E <- gamma E + (1 - gamma) e,
+ * score = e / E, decision 1.0 where it exceeds threshold else 0.0.  E_dev fp64 [U] is the carried state (0 after nextSpeaker, :168-171). */
+dsr_status dsr_sad_simple_energy_run(const void* X_dev, const int32_t* nframes_dev, int U, int Tmax, int fftLen, double threshold, double gamma, double* E_dev,
+                                     double* decision_dev, double* score_dev, void* stream);
+/* MultiChannelVADMetric::_setLowX / _setHighX / _setBinN (:595-629); a cutoff < 0 means none, one >= sampleRate / 2 is DSR_E_DIMENSION */
+dsr_status dsr_sad_band(unsigned fftLen, double sampleRate, double lowCutoff, double highCutoff, unsigned* lowX, unsigned* highX, unsigned* binN);
+/* PowerSpectrumVADMetric (kind 0, :660-705), NormalizedEnergyMetric (1, :743-796), TSPSVADMetric (2, :972-1024).  P_dev float
+ * [U][C][Tmax][fftLen/2+1]; channel 0 is the target.  powers_dev fp64 [U][Tmax][C] (getMetrics()) = the fp64 sum over lowX .. highX ascending,
+ * bin 0 with weight 1 and every other bin, the Nyquist bin too, with weight 2 (fbinX == _fftLen2 + 1 is never true inside the loop), / fftLen.
+ * score = p0 / sum p | sqrt p0 / sum sqrt p | log(p0 / (sum p - p0)) - log(E0 / sum p); decision +-1.0: score > E0 / C (kinds 0, 1), > 0 (2). */
+dsr_status dsr_sad_power_run(const float* P_dev, const int32_t* nframes_dev, int U, int C, int Tmax, unsigned fftLen, unsigned lowX, unsigned highX, int kind, double E0,
+                             double* decision_dev, double* powers_dev, double* score_dev, void* stream);
+/* CCCVADMetric::next (:842-941).  X_dev complex64 (isDouble 0) or complex128 [U][C][Tmax][fftLen].  Per frame a buffer of fftLen complex fp64
+ * is cleared once (:855); for c = 1 .. C-1 in order the PHAT-normalised cross spectrum conj(X0) Xc / |conj(X0) Xc| goes to bins lowX .. highX
+ * and their mirrors, the buffer is transformed in place (inverse radix 2, times 1 / fftLen) and the n-best pass runs over its real parts.  Kept
+ * as written: the buffer is not cleared between channels, and in the insertion loop (:887-903) a value above the last candidate always lands
+ * in slot 0, the others moving down only if it also exceeds slot 0.  score = the mean over the channels of the mean of the nCand slots;
+ * decision 1.0 where score < threshold else -1.0 (a silent frame: NaN and -1.0).  cands_dev (may be NULL) fp64 [U][Tmax][nCand]: the slots as
+ * the last channel leaves them (getMetrics()).  fftLen no power of two in [4, 2048], nCand outside [1, 64],
+ * C < 2: DSR_E_DIMENSION. */
+dsr_status dsr_sad_ccc_run(const void* X_dev, int isDouble, const int32_t* nframes_dev, int U, int C, int Tmax, unsigned fftLen, unsigned lowX, unsigned highX,
+                           unsigned nCand, double threshold, double* decision_dev, double* score_dev, double* cands_dev, void* stream);
+/* DIAGNOSTIC entry, for tools/bench_sad.py only; its score is no metric.  The same kernel without the n-best pass (score = the mean over the channels of sample 0), so that the pass's share of
+ * the time can be taken as a difference */
+dsr_status dsr_sad_ccc_transforms_only(const void* X_dev, int isDouble, int U, int C, int Tmax, unsigned fftLen, unsigned lowX, unsigned highX, double* decision_dev,
+                                       double* score_dev, void* stream);
+/* NegentropyVADMetric (kind 0, :1103-1142), MutualInformationVADMetric (1, :1437-1535), LikelihoodRatioVADMetric (2, :1572-1628).
+ * The model lives on the host (std::lgamma / std::tgamma): per bin the shape factor f, Bc and the normalisation of the marginal generalised
+ * Gaussian (:1038-1049), and with joint != 0 the matched joint shape factor of the bisection _match (:1338-1369), its Bc and normalisation
+ * (:1229-1246) and the fixed part of the decision threshold (:1399-1434).  The reference loops for ever where _match does not converge: here 200
+ * steps, then DSR_E_NUMERIC.  shapeFactors: fftLen/2+1 host doubles (NULL: all 2.0, the Gaussian); read_shape_factors takes them from the
+ * reference's directory of _M-%04d files, second token of the first line (:1077-1095).  table: [fftLen/2+1][6] = (f, Bc, norm, fJ, BJ, normJ).
+ * run: X1 / X2 complex128 [U][Tmax][fftLen], env1 / env2 float [U][Tmax][envDim], envDim >= fftLen/2+1 (kind 0 reads X1 and env1 only).  The
+ * device does the per-bin fp64 work (pow, log, the 2x2 quadratic form of :1253-1284 written out) and the weighted sum over lowX .. highX
+ * ascending (only bin 0 has weight 1), / binN.  score = that sum; decision 1.0 where score > threshold else 0.0.  kind 1 carries rho_dev
+ * complex128 [U][fftLen/2+1]: used before it is updated (:1479, :1504-1510), rescaled to 0.9 where |rho| >= 0.9, zero after nextSpeaker() only;
+ * twiddle < 0 compares with `threshold`, otherwise with _calcTotalThreshold (:1437-1454) of the rho before the frame; threshold_dev (may be NULL)
+ * [U][Tmax] receives the threshold each frame was compared with.  kind 2 uses sqrt((env1 + env2) / 2) of the unrooted envelopes, as written
+ * (:1594-1599).  The reference's per-frame printfs are dropped. */
+typedef struct dsr_sad_gg dsr_sad_gg;
+dsr_status dsr_sad_gg_create(const double* shapeFactors, unsigned fftLen, double sampleRate, double lowCutoff, double highCutoff, int joint, dsr_sad_gg** out);
+void       dsr_sad_gg_destroy(dsr_sad_gg*);
+dsr_status dsr_sad_gg_table(const dsr_sad_gg*, double* table, double* fixedThreshold);
+dsr_status dsr_sad_gg_read_shape_factors(const char* directory, unsigned fftLen, double* shapeFactors);
+dsr_status dsr_sad_gg_run(dsr_sad_gg*, int kind, const void* X1_dev, const void* X2_dev, const float* env1_dev, const float* env2_dev, int envDim,
+                          const int32_t* nframes_dev, int U, int Tmax, double twiddle, double threshold, double beta, void* rho_dev, double* decision_dev,
+                          double* score_dev, double* threshold_dev, void* stream);
+/* The segmenters' rule, HangoverVADFeature::next (:1767-1837), over K metrics' decisions fp64 [K][U][Tmax]: wait for headN consecutive source
+ * frames above threshold, emit from the oldest buffered one, end before the tailN-th consecutive frame below, or where the source ends.
+ * kind 0: HangoverVADFeature (decision 0 > thresholds[0], :1756-1765); 1: HangoverMIVADFeature (K = 3, codes -1, 2, 3, -3, :1853-1879);
+ * 2: HangoverMultiStageVADFeature (:1904-1945; K < 3 is never above).  thresholds: K host doubles.  Per utterance: start = _prefixN - headN,
+ * the first emitted source frame (nframes - headN when the utterance never starts); length, 0 for one that never starts; consumed, the source
+ * frames the reference would have pulled; decision_metric_dev int32 [U][Tmax], _decisionMetric after each pulled source frame (0 for kind 0).
+ * The metrics' decisions are those of a walk over all nframes frames; the reference never evaluates a metric past `consumed`, so a caller
+ * that carries a metric's state runs that metric again with nframes = consumed from the state it started with. */
+dsr_status dsr_sad_hangover_run(const double* decisions_dev, const int32_t* nframes_dev, int K, int U, int Tmax, const double* thresholds, unsigned headN, unsigned tailN,
+                                int kind, int32_t* start_dev, int32_t* length_dev, int32_t* consumed_dev, int32_t* decision_metric_dev, void* stream);
+/* y [U][Tmax][dim]: row j of utterance u = row start[u] + j of x for j < length[u], zeros after */
+dsr_status dsr_sad_gather_run(const float* x_dev, const int32_t* start_dev, const int32_t* length_dev, int U, int Tmax, int dim, float* y_dev, void* stream);
+
+/* The spectral-shape operators of btk/sad/sadFeature.cc, y float [U][Tmax][1].  op 0 EnergyDiffusionFeature (:93-118): -sum nval log10(nval) over
+ * nval = x / |x| > 0 in fp64; 1 BandEnergyRatioFeature (:129-153): sqrt(ssLow / ssHigh), float sums of squares below and from bin
+ * int(floor(threshF / (sampleRate / 2 / dim))), threshF <= 0 meaning sampleRate / 4 (thresh carries threshF; band_ratio_index returns the bin, and
+ * DSR_E_DIMENSION where it lies past the frame, which the reference would read); 2 NegativeEntropyFeature (:205-243): 100 (E ln cosh z - 0.374576)^2
+ * of the rectified frame normalised to zero mean and unit variance, z rounded to float as there, ln and cosh in fp64; 3 SignificantSubbandsFeature
+ * (:253-274): the count of x / sigma > thresh, sigma the float norm() result widened again (:27-39). */
+dsr_status dsr_sad_band_ratio_index(int dim, float sampleRate, float threshF, int* threshX);
+dsr_status dsr_sad_shape_run(const float* x_dev, const int32_t* nframes_dev, int U, int Tmax, int dim, int op, float sampleRate, float thresh, float* y_dev, void* stream);
+
+/* The metrics and segmenters over streams, names and defaults of sad.i.  A metric materialises its sources' utterance at the first next() after
+ * a reset() and serves frame frameX of the batch result (frameX < 0: the next one); DSR_E_ITERATOR past the end.  reset() commits the carried
+ * state of the frames served so far (an EnergyVADMetric keeps its history, :459-463) and resets the sources; next_speaker() refills it.
+ * A segmenter is a float stream; it commits its stateful metrics with the frames it consumed.  In HangoverMultiStageVADFeature the reference
+ * calls a metric at stage >= 2 twice in a frame where that stage fires (:1932-1935), which advances a stateful metric twice: an
+ * EnergyVADMetric or MutualInformationVADMetric there is refused with DSR_E_CONSISTENCY (a SimpleEnergyVAD handle too). */
+typedef struct dsr_vad_metric dsr_vad_metric;
+dsr_status dsr_sad_energy_metric_create(dsr_stream* source, double initialEnergy, double threshold, unsigned headN, unsigned tailN, unsigned energiesN, const char* name,
+                                        dsr_vad_metric** out);
+dsr_status dsr_sad_power_metric_create(int kind, unsigned fftLen, double sampleRate, double lowCutoff, double highCutoff, const char* name, dsr_vad_metric** out);
+dsr_status dsr_sad_ccc_metric_create(unsigned fftLen, unsigned nCand, double sampleRate, double lowCutoff, double highCutoff, const char* name, dsr_vad_metric** out);
+dsr_status dsr_sad_simple_energy_create(dsr_stream* samp, double threshold, double gamma, dsr_vad_metric** out);
+/* kind as dsr_sad_gg_run; source2 / spectralEstimator2 are NULL for kind 0; shapeFactorDir "" or NULL: all 2.0; the spectral estimators are any
+ * float streams of at least fftLen/2+1 elements.  fftLen = the size of source1.  nextSpeaker() zeroes rho (:1543-1550), reset() keeps it. */
+dsr_status dsr_sad_gg_metric_create(int kind, dsr_stream* source1, dsr_stream* source2, dsr_stream* spectralEstimator1, dsr_stream* spectralEstimator2,
+                                    const char* shapeFactorDir, double twiddle, double threshold, double beta, double sampleRate, double lowCutoff, double highCutoff,
+                                    const char* name, dsr_vad_metric** out);
+void       dsr_sad_metric_release(dsr_vad_metric*);
+dsr_status dsr_sad_metric_set_channel(dsr_vad_metric*, dsr_stream* chan);
+dsr_status dsr_sad_metric_clear_channel(dsr_vad_metric*);
+dsr_status dsr_sad_metric_set_e0(dsr_vad_metric*, double E0);
+dsr_status dsr_sad_metric_set_ncand(dsr_vad_metric*, unsigned nCand);
+dsr_status dsr_sad_metric_set_threshold(dsr_vad_metric*, double threshold);
+dsr_status dsr_sad_metric_next(dsr_vad_metric*, int frameX, double* value);
+dsr_status dsr_sad_metric_reset(dsr_vad_metric*);
+dsr_status dsr_sad_metric_next_speaker(dsr_vad_metric*);
+dsr_status dsr_sad_metric_score(dsr_vad_metric*, double* score);
+dsr_status dsr_sad_metric_powers(dsr_vad_metric*, double* powers, int n);
+dsr_status dsr_sad_metric_energy_percentile(dsr_vad_metric*, double percentile, double* value);
+/* kind as dsr_sad_hangover_run.  add_metric: the further metrics of HangoverMIVADFeature's constructor and HangoverMultiStageVADFeature::setMetric */
+dsr_status dsr_sad_hangover_create(dsr_stream* source, dsr_vad_metric* metric, double threshold, unsigned headN, unsigned tailN, int kind, const char* name,
+                                   dsr_stream** out);
+dsr_status dsr_sad_hangover_add_metric(dsr_stream* hangover, dsr_vad_metric* metric, double threshold);
+dsr_status dsr_sad_hangover_next_speaker(dsr_stream* hangover);
+dsr_status dsr_sad_hangover_prefix_n(dsr_stream* hangover, int* prefixN);
+dsr_status dsr_sad_hangover_decision_metric(dsr_stream* hangover, int* decisionMetric);
+/* EnergyDiffusionFeature(src, nm), BandEnergyRatioFeature(src, sampleRate, threshF, nm), NegativeEntropyFeature(src, nm),
+ * SignificantSubbandsFeature(src, thresh, nm) (sadFeature.h): op as dsr_sad_shape_run, one value a frame */
+dsr_status dsr_sad_shape_create(dsr_stream* src, int op, float sampleRate, float thresh, const char* name, dsr_stream** out);
+
+/* =====================================================================================
  * 8. The distribution set as the decoder sees it
  *    replaces Distrib::score(frameX) (asr/gaussian/distribBasic.h:48-50), DistribSet::find (:183-190), resetCache / resetFeature (:177-178) and
  *    the pull chain decoder -> distribution -> codebook -> feature stream (decoder.h:985, codebookBasic.cc:431-465): a GMM model bound to a

@@ -22,82 +22,23 @@
 // One workgroup (1024 threads) owns one utterance at a time and loops over its frames; workgroups pull
 // utterances from a queue.  All arithmetic that decides a comparison is done with explicit
 // non-contracted IEEE operations (this file is compiled with -ffp-contract=off).
-#include "common.h"
-#include "wfst_graph.h"
-#include "lattice.h"
-#include "lexicon.h"
-#include "wordtrace.h"
+#include "viterbi.h"
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
 
 namespace dsr {
 
-struct Tok { int32_t node; float ac; float lm; uint32_t bp; };        // register view; node bit31: edge input == silenceX
-// token lists in memory: what a frame's beam test and expansion need (TokA) apart from what only the end phase needs (TokB)
-struct TokA { float ac; float lm; uint32_t bp; uint32_t xs; };        // xs: first expansion record of the node | bit31: edge input == silenceX
-struct TokB { int32_t node; int32_t cnt; };                           // cnt: number of expansion records of the node
-// expansion record as the register path reads it: what the expansion needs in the first 16 bytes, what the new token needs in the second
-// eps1: cost of the first epsilon hop (meta bit17: it has an output).  Further hops (meta bits 18..30: hop h = 1..13 has an output):
-// a two-hop path carries the second cost in p2 (float bits), longer ones the offset of their hop costs in GraphDev::pathCost;
-// meta bit31: more than 14 hops, walked through the path/arc arrays instead.
-struct XRecD { int32_t dist; float cost; uint32_t meta; float eps1; int32_t dst; int32_t p2; int32_t dstXoff; int32_t dstCnt; };
-struct Side { double ttl; float ac; float lm; int32_t rec; uint32_t prevBp; int32_t c; uint32_t next; };   // a later arrival at an occupied state
-struct CandA { double ttl; float ac; float lm; };
-struct CandB { int32_t dst; int32_t next; int32_t rec; uint32_t prevBp; };   // rec bit30: the emitting arc's input is the silence symbol
-struct Bp { uint32_t prev; uint32_t rec; };
-
+// (the records, the argument block and the constants the host sizes its buffers by -- kThreads, kFastC, kProfN, kSideLds -- are in viterbi.h)
 static constexpr uint32_t kNone = 0xFFFFFFFFu;
 static constexpr uint32_t kEndBit = 0x80000000u;
-static constexpr int kThreads = 1024;             // 16 waves per CU at 128 VGPRs (measured in round 2: 512 x 256 VGPRs 22 % slower, 768 x 168 VGPRs 4 % slower; two 512-thread workgroups per CU 1.2x slower)
 static constexpr int kWaves = kThreads / 64;
 static constexpr int kFastK = 8;
 static constexpr int kB = 2;                        // placements whose loads are in flight together (batch of the register-path phases)                  // placements a thread keeps in registers on the register path
-static constexpr int kFastC = 24576;               // most placements per frame on the register path (those beyond kFastK per thread are parked in memory)
 static constexpr int kFastE = 8190;                // most expanding tokens per frame on the register path
 static constexpr int kP1 = 16;                     // token rounds per wave in the register path's beam pass
 static constexpr int kW = 4;                        // register placements whose P6 loads are in flight together (8: 3 % slower; parked ones: kB)
-static constexpr int kProfN = 48;                  // profiling words per slot: 32 phase ticks + 12 of the size-class histogram
-static constexpr int kSideLds = 496;               // later arrivals kept in LDS (the rest go to memory)
 
-struct GraphDev {
-  int nNodes, initial;
-  const int* xoff; const XRec* xrec; const XRecD* xrecD; const int* xarc; const int* xpathOff;
-  const int* eoff; const ERec* erec; const int* path; const float* pathCost;
-  const float* arcCost; const uint32_t* arcOut; const uint32_t* arcIn;
-  const int* nodeFinal; const float* nodeCost;
-};
-
-// Time slicing (segFrames > 0): a work item is one SEGMENT of an utterance -- segFrames frames -- and the items are taken in the order segment-major, utterance-minor,
-// so all utterances of a batch advance together and end together.  (Run to completion, a workgroup per utterance, the workgroups end over a span of one utterance's
-// duration once the queue is empty: 11 % of the launch at 1000 utterances on 256 CUs.)  Between its segments an utterance is its token list + these scalars.
-struct SegState { int n, status, maxActive, pad; long arenaOff, chunkEnd, arenaUsed; double thresh; long long stat[3]; };
-
-struct DecDev {
-  double beam, lmScale, lmPenalty, silPenalty; uint32_t silenceX; int noPen;
-  // time slicing: frames per segment (0: off), segments per utterance, queues (8: one per XCD, 1: one for all), the pool of back-pointer records and how many of
-  // them an utterance takes at a time (a barrier pair and a device atomic each time: 9 us)
-  int segFrames, segCount, segQueues, segDrop; long poolCap, poolChunk;   /* segDrop (tests): bit x set = the workgroups on XCD x do not serve their own queue */ unsigned long long* poolNext; SegState* segState; int* segDone; TokA* saveA; TokB* saveB;
-  int maxTok, maxCand; long arenaCap;
-  // per-slot scratch (slot s at base + s*stride)
-  TokA* tokA; TokB* tokB; TokA* ctok; Side* side; int fastOK; int* tokOff; int* tokCnt; int* owner; int* rank; int* chead; CandA* cA; CandB* cB; unsigned* first; unsigned* tags; Bp* arena;
-  int* queue; long long* prof;          // prof: optional per-phase wall-clock ticks (DSR_VITERBI_PROF), 16 per slot
-  // dump (slot 0 only)
-  int dumpOn; long dumpCap; long* dumpFrameOff; int* dumpNode; float* dumpAc; float* dumpLm; int* dumpArc; long* dumpCount;
-  // lattice bookkeeping (generateLattice, decoder.h:531-541,805-953): EVERY placement of every frame is kept, per utterance, in arrival order --
-  // {ac, lm, record, parent back pointer} + its unrounded total (the reference's 'worse' chains are an order-dependent function of exactly
-  // these; the host replays them, lattice.cpp) -- plus, per back-pointer record, the placement that won its state, and the final token list.
-  int latOn; long latCap; uint4* lat; double* latTtl; long* latFrameOff; int* arenaLat; int4* latFinal; int* latInfo;
-  // topN > 0 (decoder.h:571-581): a frame expands the topN best tokens of the list in order of their scores and applies no beam; third token buffer
-  int topN; TokA* tokA3; TokB* tokB3;
-};
-
-// every argument of the kernel, one struct in the kernarg segment (read through KP, see k_viterbi)
-struct VitArgs {
-  GraphDev G; DecDev D;
-  const float* scores; const int* nframesArr; int U, Tmax, nDist;
-  dsr_decode_result* res; int* arcsOut; unsigned* wordsOut; int maxPath, useLdsRow, hashN, regionB, cntCap;
-};
 typedef const __attribute__((address_space(4))) VitArgs* KP;
 
 __device__ __forceinline__ unsigned ld_u32(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -1466,655 +1407,30 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
 #undef dump
 }
 
-struct DecoderState {
-  dsr_decoder_cfg cfg; bool haveGraph = false; int nSlots = 0; int nNodes = 0;
-  WfstGraph::Csr csr; WfstGraph::Tables tab;
-  DevBuf<int> d_xoff, d_xarc, d_xpathOff, d_eoff, d_path, d_nodeFinal, d_queue; DevBuf<float> d_pathCost;
-  DevBuf<XRec> d_xrec; DevBuf<ERec> d_erec; DevBuf<float> d_arcCost, d_nodeCost; DevBuf<uint32_t> d_arcOut, d_arcIn;
-  DevBuf<TokA> d_tokA, d_ctok; DevBuf<TokB> d_tokB; DevBuf<Side> d_side; DevBuf<XRecD> d_xrecD; int fastOK = 0; int maxCnt = 0; DevBuf<int> d_tokOff, d_tokCnt, d_owner, d_rank, d_chead; DevBuf<unsigned> d_tags; DevBuf<CandA> d_cA; DevBuf<CandB> d_cB; DevBuf<unsigned> d_first; DevBuf<Bp> d_arena;
-  DevBuf<long long> d_prof; DevBuf<dsr_decode_result> d_res; DevBuf<int> d_arcs; DevBuf<unsigned> d_words;
-  long arenaCap = 0; int initial = 0; unsigned tokenMemoryLimit = 0;
-  long lastPoolCap = 0;
-  DevBuf<SegState> d_segState; DevBuf<int> d_segDone; DevBuf<unsigned long long> d_poolNext; DevBuf<TokA> d_saveA; DevBuf<TokB> d_saveB;   // time slicing (DecDev::segFrames)
-  // DecoderWordTrace mode (cfg.wordTrace): scratch of k_wordtrace.hip
-  DevBuf<WTok> w_tok; DevBuf<WCand> w_cand; DevBuf<int> w_tokOff, w_rank; DevBuf<unsigned long long> w_best; DevBuf<unsigned> w_first; DevBuf<int4> w_traces; size_t w_tablesFor = 0;
-  bool costNegZero = false; double costMinAbs = HUGE_VAL;      // over the arcs of the transducer set last: a cost of -0.0; the smallest non-zero |cost|
-  // lattice bookkeeping of the last decode (cfg.latticeTokens > 0), per utterance
-  DevBuf<uint4> d_lat; DevBuf<double> d_latTtl; DevBuf<long> d_latFrameOff; DevBuf<int> d_arenaLat; DevBuf<int4> d_latFinal; DevBuf<int> d_latInfo;
-  int latU = 0, latTmax = 0; long latArenaCap = 0; WfstGraph graphCopy; DevBuf<TokA> d_tokA3; DevBuf<TokB> d_tokB3;
-  // symbol tables of the transducer set last (borrowed) and the resolved silSymbol / eosSymbol (decoder.h:740-745)
-  const dsr_lexicon* lexIn = nullptr; const dsr_lexicon* lexOut = nullptr; uint32_t eosX = 0; std::string eosSymbol;
-  // what the last collected decode left: per-utterance results and best paths (pinned staging memory), for bestHypo / bestPath / finalStatesN
-  int lastU = 0; size_t lastMaxPath = 0; bool lastPaths = false;
-  PinBuf<dsr_decode_result> h_res; PinBuf<int> h_arcs; PinBuf<unsigned> h_words; hipEvent_t evDone = nullptr;
-  int pendingU = 0; size_t pendingPath = 0; int pendingSlots = 0; long long* pendingProf = nullptr;
-  // dump
-  int dumpOn = 0; long dumpCap = 0; DevBuf<long> d_dumpFrameOff, d_dumpCount; DevBuf<int> d_dumpNode, d_dumpArc; DevBuf<float> d_dumpAc, d_dumpLm;
-  std::vector<int64_t> h_dumpFrameOff; std::vector<int32_t> h_dumpNode, h_dumpArc; std::vector<float> h_dumpAc, h_dumpLm; int64_t h_dumpFrames = 0;
-};
-
 }  // namespace dsr
 
-using namespace dsr;
-struct dsr_wfst : WfstGraph { dsr_lexicon* lexState = nullptr; dsr_lexicon* lexIn = nullptr; dsr_lexicon* lexOut = nullptr; };
-struct dsr_decoder : DecoderState {};
+// Which XCD a workgroup lands on: HW_REG_XCC_ID of workgroup i of a 64-workgroup grid (decoder.cpp, xcd_round_robin)
+extern "C" __global__ void k_xcc_probe(int* out) { if (threadIdx.x == 0) out[blockIdx.x] = (int) (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u); }
 
-extern "C" {
+namespace dsr {
 
-dsr_status dsr_wfst_create(dsr_wfst** out) { return guard([&] { if (!out) throw Error(DSR_E_PARAMETER, "null argument"); *out = new dsr_wfst(); }); }
-// WFSTFlyWeightSortedOutput(statelex, inlex, outlex) (decoder.i; wfstFlyWeight.h:403-424): the same container with every node's arcs kept ordered by
-// (output, input); call on an empty transducer
-dsr_status dsr_wfst_set_sorted_output(dsr_wfst* g, int on)
-{ return guard([&] { if (!g) throw Error(DSR_E_PARAMETER, "null argument"); if (!g->arcs.empty()) throw Error(DSR_E_CONSISTENCY, "the transducer already has arcs"); g->sortedOutput = on != 0; }); }
-void dsr_wfst_destroy(dsr_wfst* g) { delete g; }
-dsr_status dsr_wfst_read(dsr_wfst* g, const char* f, int binary) { return guard([&] { if (!g) throw Error(DSR_E_PARAMETER, "null argument"); g->read(f, binary != 0); }); }
-dsr_status dsr_wfst_read_dynamic(dsr_wfst* g, const char* f, int noSelfLoops) { return guard([&] { if (!g) throw Error(DSR_E_PARAMETER, "null argument"); g->readEx(f, false, noSelfLoops != 0); }); }
-dsr_status dsr_wfst_write(const dsr_wfst* g, const char* f, int binary) { return guard([&] { if (!g) throw Error(DSR_E_PARAMETER, "null argument"); g->write(f, binary != 0); }); }
-// WFSTFlyWeight::write(fileName, binary, useSymbols) (wfstFlyWeight.cc:415-463): with useSymbols every arc line carries the lexica's strings (Edge::write
-// :499-516: states too when the state lexicon is non-empty, costs below 1e-4 left out); final-state lines and -- with binary -- the end marker stay numeric
-dsr_status dsr_wfst_write_symbols(const dsr_wfst* g, const char* f, int binary, int useSymbols)
-{ return guard([&] { if (!g) throw Error(DSR_E_PARAMETER, "null argument"); g->write(f, binary != 0, useSymbols != 0); }); }
-// WFSTFlyWeight::reverse(wfst) (:141-213) and reverseRead(fileName) (:215-297)
-dsr_status dsr_wfst_reverse(dsr_wfst* g, const dsr_wfst* src)
-{ return guard([&] { if (!g || !src) throw Error(DSR_E_PARAMETER, "null argument"); g->reverse(*src); }); }
-dsr_status dsr_wfst_reverse_read(dsr_wfst* g, const char* f)
-{ return guard([&] { if (!g) throw Error(DSR_E_PARAMETER, "null argument"); g->reverseRead(f); }); }
-dsr_status dsr_wfst_add_arc(dsr_wfst* g, unsigned s1, unsigned s2, unsigned in, unsigned out, float cost)
-{ return guard([&] { if (!g) throw Error(DSR_E_PARAMETER, "null argument"); g->addArc(s1, s2, in, out, cost, true); }); }
-dsr_status dsr_wfst_add_final(dsr_wfst* g, unsigned s, float cost) { return guard([&] { if (!g) throw Error(DSR_E_PARAMETER, "null argument"); g->addFinal(s, cost); }); }
-int dsr_wfst_num_nodes(const dsr_wfst* g) { return (int) g->nodes.size(); }
-int dsr_wfst_num_arcs(const dsr_wfst* g) { return (int) g->arcs.size(); }
-dsr_status dsr_wfst_export(const dsr_wfst* g, uint32_t* nodeState, int32_t* nodeFinal, float* nodeCost, int32_t* arcOff,
-                           int32_t* arcDst, uint32_t* arcIn, uint32_t* arcOut, float* arcCost)
+void xcc_probe_launch(int* out64, hipStream_t st) { hipLaunchKernelGGL(k_xcc_probe, dim3(64), dim3(64), 0, st, out64); }
+
+// modes -> instantiation (viterbi.h: bit 0 ticks, bit 1 lattice / topN / dump, bit 2 narrow table)
+typedef void (*VitKernel)(const VitArgs);
+static constexpr VitKernel kVitKernels[8] = { k_viterbi<0>, k_viterbi<1>, k_viterbi<2>, k_viterbi<3>, k_viterbi<4>, k_viterbi<5>, k_viterbi<6>, k_viterbi<7> };
+
+size_t viterbi_static_lds(int modes)
 {
-  return guard([&] {
-    if (!g) throw Error(DSR_E_PARAMETER, "null argument");
-    const WfstGraph::Csr c = g->csr(); const size_t n = g->nodes.size();
-    for (size_t i = 0; i < n; i++) { if (nodeState) nodeState[i] = g->nodes[i].state; if (nodeFinal) nodeFinal[i] = g->nodes[i].final_; if (nodeCost) nodeCost[i] = g->nodes[i].cost; }
-    if (arcOff) for (size_t i = 0; i <= n; i++) arcOff[i] = c.off[i];
-    for (size_t a = 0; a < c.dst.size(); a++) { if (arcDst) arcDst[a] = c.dst[a]; if (arcIn) arcIn[a] = c.in[a]; if (arcOut) arcOut[a] = c.out[a]; if (arcCost) arcCost[a] = c.cost[a]; }
-  });
+  hipFuncAttributes fattr; DSR_HIP(hipFuncGetAttributes(&fattr, (const void*) kVitKernels[modes & 7]));
+  return fattr.sharedSizeBytes;
+}
+void viterbi_launch(int modes, const VitArgs& A, int slots, size_t ldsBytes, hipStream_t st)
+{
+  const VitKernel k = kVitKernels[modes & 7];
+  DSR_HIP(hipFuncSetAttribute((const void*) k, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes));
+  hipLaunchKernelGGL(k, dim3(slots), dim3(kThreads), ldsBytes, st, A);
+  DSR_HIP(hipGetLastError());
 }
 
-// WFSTFlyWeight(statelex, inlex, outlex) (decoder.i:52-70): the lexica are borrowed (the reference holds reference-counted pointers); the text reader
-// looks non-numeric fields up in them (wfstFlyWeight.cc:311-347)
-dsr_status dsr_wfst_set_lexicons(dsr_wfst* g, dsr_lexicon* stateLex, dsr_lexicon* inputLex, dsr_lexicon* outputLex)
-{
-  return guard([&] {
-    if (!g) throw Error(DSR_E_PARAMETER, "null argument");
-    g->lexState = stateLex; g->lexIn = inputLex; g->lexOut = outputLex;
-    g->symbolOf = [g](int which, const char* t) -> uint32_t {
-      dsr_lexicon* l = which == 0 ? g->lexState : which == 1 ? g->lexIn : g->lexOut;
-      if (!l) throw Error(DSR_E_KEY, "field '%s' is not a number and the transducer has no %s lexicon", t, which == 0 ? "state" : which == 1 ? "input" : "output");
-      return l->index(t);
-    };
-    g->nameOf = [g](int which, uint32_t i) -> std::string {
-      const dsr_lexicon* l = which == 0 ? g->lexState : which == 1 ? g->lexIn : g->lexOut;
-      if (!l) throw Error(DSR_E_KEY, "the transducer has no %s lexicon", which == 0 ? "state" : which == 1 ? "input" : "output");
-      return l->symbol(i);
-    };
-    g->stateLexSize = [g]() -> size_t { return g->lexState ? g->lexState->syms.size() : 0; };
-  });
-}
-dsr_lexicon* dsr_wfst_state_lexicon(const dsr_wfst* g) { return g ? g->lexState : nullptr; }
-dsr_lexicon* dsr_wfst_input_lexicon(const dsr_wfst* g) { return g ? g->lexIn : nullptr; }
-dsr_lexicon* dsr_wfst_output_lexicon(const dsr_wfst* g) { return g ? g->lexOut : nullptr; }
-int dsr_wfst_has_final_state(const dsr_wfst* g) { if (!g) return 0; for (size_t i = 0; i < g->nodes.size(); i++) if (g->nodes[i].final_) return 1; return 0; }
-
-void dsr_decoder_default_cfg(dsr_decoder_cfg* c)
-{ memset(c, 0, sizeof(*c)); c->beam = 100.0; c->lmScale = 12.0; c->lmPenalty = 0.0; c->silPenalty = 0.0; c->silenceX = 0xFFFFFFFFu;
-  c->propagateN = 5; c->wordTraceLattice = 1; }                            // DecoderWordTrace's defaults (decoder.i:201-260; only read when wordTrace != 0)
-
-dsr_status dsr_decoder_create(const dsr_decoder_cfg* cfg, dsr_decoder** out)
-{
-  return guard([&] {
-    if (!cfg || !out) throw Error(DSR_E_PARAMETER, "null argument");
-    require_device();
-    dsr_decoder* d = new dsr_decoder(); d->cfg = *cfg;
-    if (d->cfg.maxActive <= 0) d->cfg.maxActive = 65536;
-    if (d->cfg.maxCandidates <= 0) d->cfg.maxCandidates = 8 * d->cfg.maxActive;
-    if (d->cfg.maxCandidates >= (1 << 24)) throw Error(DSR_E_PARAMETER, "maxCandidates must be < 2^24");
-    if (d->cfg.streams <= 0) {
-      hipDeviceProp_t prop; int dev = 0; DSR_HIP(hipGetDevice(&dev)); DSR_HIP(hipGetDeviceProperties(&prop, dev));
-      d->cfg.streams = prop.multiProcessorCount;
-      if (const char* e = getenv("DSR_VITERBI_SLOTS")) { const int t = atoi(e); if (t > 0) d->cfg.streams = t; }
-    }
-    *out = d;
-  });
-}
-void dsr_decoder_destroy(dsr_decoder* d) { if (d && d->evDone) (void) hipEventDestroy(d->evDone); delete d; }
-
-dsr_status dsr_decoder_set(dsr_decoder* d, const dsr_wfst* g)
-{
-  return guard([&] {
-    if (!d || !g) throw Error(DSR_E_PARAMETER, "null argument");
-    if (g->initial < 0) throw Error(DSR_E_CONSISTENCY, "the transducer has no arcs");
-    d->csr = g->csr(); d->tab = g->tables(d->csr, (size_t) 1 << 28);
-    d->nNodes = (int) g->nodes.size(); d->initial = g->initial; d->graphCopy = *g;
-    std::vector<int> nf(d->nNodes); std::vector<float> nc(d->nNodes);
-    for (int i = 0; i < d->nNodes; i++) { nf[i] = g->nodes[i].final_; nc[i] = g->nodes[i].cost; }
-    d->d_xoff.upload(d->tab.xoff); d->d_eoff.upload(d->tab.eoff); d->d_path.upload(d->tab.path);
-    if (d->tab.xrec.empty()) throw Error(DSR_E_CONSISTENCY, "the transducer has no emitting arcs");
-    d->d_xrec.upload(d->tab.xrec); d->d_xarc.upload(d->tab.xarc); d->d_xpathOff.upload(d->tab.xpathOff);
-    {
-      // expansion records with the destination's own expansion range folded in (the register path never reads xoff)
-      const size_t nx = d->tab.xrec.size(); std::vector<XRecD> xd(nx); int maxCnt = 0; std::vector<float> pc(1, 0.0f);
-      for (size_t r = 0; r < nx; r++) {
-        const XRec& x = d->tab.xrec[r]; XRecD& o = xd[r];
-        o.dst = x.dst; o.dist = x.dist; o.cost = x.cost; o.meta = x.meta; o.dstXoff = d->tab.xoff[x.dst]; o.dstCnt = d->tab.xoff[x.dst + 1] - d->tab.xoff[x.dst];
-        const int po = d->tab.xpathOff[r], plen = (int) (x.meta & 0xFFFFu); o.p2 = 0; o.eps1 = 0.0f;
-        if (x.meta >> 18) throw Error(DSR_E_CONSISTENCY, "expansion record %zu: meta bits above 17 are in use", r);
-        if (plen) { const int a0 = d->tab.path[po]; o.eps1 = d->csr.cost[a0]; if (d->csr.out[a0] != 0) o.meta |= 0x20000u; }
-        if (plen > 14) o.meta |= 0x80000000u;
-        else if (plen > 1) {
-          if (plen == 2) { const float c1 = d->csr.cost[d->tab.path[po + 1]]; memcpy(&o.p2, &c1, 4); }
-          else { o.p2 = (int) pc.size(); for (int h = 1; h < plen; h++) pc.push_back(d->csr.cost[d->tab.path[po + h]]); }
-          for (int h = 1; h < plen; h++) if (d->csr.out[d->tab.path[po + h]] != 0) o.meta |= 1u << (17 + h);
-        }
-        if (o.dstCnt > maxCnt) maxCnt = o.dstCnt;
-      }
-      d->d_xrecD.upload(xd); d->d_pathCost.upload(pc);
-      d->fastOK = (maxCnt < (1 << 19) && nx < ((size_t) 1 << 27)) ? 1 : 0; d->maxCnt = maxCnt;       // (2^27 records x 32 bytes: the register path addresses them with 32-bit byte offsets)
-      if (getenv("DSR_VITERBI_NOFAST")) d->fastOK = 0;
-    }
-    { std::vector<ERec> e = d->tab.erec; if (e.empty()) e.push_back(ERec{0, 0, 0, 0}); d->d_erec.upload(e); }
-    d->d_arcCost.upload(d->csr.cost); d->d_arcOut.upload(d->csr.out); d->d_arcIn.upload(d->csr.in);
-    d->costNegZero = false; d->costMinAbs = HUGE_VAL;
-    for (size_t a = 0; a < d->csr.cost.size(); a++) {
-      const float c = d->csr.cost[a]; uint32_t bits; memcpy(&bits, &c, 4);
-      if (bits == 0x80000000u) d->costNegZero = true;
-      if (c != 0.0f && std::fabs((double) c) < d->costMinAbs) d->costMinAbs = std::fabs((double) c);
-    }
-    d->d_nodeFinal.upload(nf); d->d_nodeCost.upload(nc);
-    d->haveGraph = true; d->nSlots = 0;    // scratch is (re)allocated by the first decode
-  });
-}
-// DecoderFlyWeight::set(wfst) = _Decoder::_set (decoder.h:740-745): the network and, through its lexica, the indices of silSymbol (input
-// lexicon) and eosSymbol (output lexicon); a missing symbol is the reference's jkey_error (mlist.h:109-114).  Symbols may be NULL when the
-// transducer carries no lexica (then cfg.silenceX stays as configured).
-dsr_status dsr_decoder_set_symbols(dsr_decoder* d, const dsr_wfst* g, const char* silSymbol, const char* eosSymbol)
-{
-  return guard([&] {
-    if (!d || !g) throw Error(DSR_E_PARAMETER, "null argument");
-    uint32_t silX = d->cfg.silenceX, eosX = 0;
-    if (silSymbol) { if (!g->lexIn) throw Error(DSR_E_KEY, "the transducer has no input lexicon to look '%s' up in", silSymbol); silX = g->lexIn->index(silSymbol); }
-    if (eosSymbol) { if (!g->lexOut) throw Error(DSR_E_KEY, "the transducer has no output lexicon to look '%s' up in", eosSymbol); eosX = g->lexOut->index(eosSymbol); }
-    const dsr_status s = dsr_decoder_set(d, g);
-    if (s != DSR_OK) throw Error(s, "%s", dsr_last_error());
-    d->cfg.silenceX = silX; d->eosX = eosX; d->lexIn = g->lexIn; d->lexOut = g->lexOut; d->eosSymbol = eosSymbol ? eosSymbol : "";
-  });
-}
-uint32_t dsr_decoder_eos_index(const dsr_decoder* d) { return d ? d->eosX : 0; }
-
-// Results of the last collected decode, utterance u.  bestHypo(useInputSymbols) (decoder.h:748-773): the output symbols != 0 along the best path, or
-// the input symbols != 0 with immediate repetitions dropped ("inX != 0 && inX != lastX", walking the path from its END, so a repetition is judged
-// against the symbol after it), each followed by a blank.  bestPath() (:775-797): the names of the distributions along the path = the input
-// symbols != 0, one per line.  Strings need the lexica (DSR_E_KEY without); the id variants do not.
-static void need_last(const dsr_decoder* d, int u, bool paths)
-{
-  if (!d) throw Error(DSR_E_PARAMETER, "null argument");
-  if (d->lastU <= 0) throw Error(DSR_E_CONSISTENCY, "no decode has been collected yet");
-  if (u < 0 || u >= d->lastU) throw Error(DSR_E_INDEX, "utterance %d of %d", u, d->lastU);
-  if (paths && !d->lastPaths) throw Error(DSR_E_CONSISTENCY, "the last decode was collected without its paths");
-  if (d->h_res.p[u].status != DSR_OK) throw Error(d->h_res.p[u].status, "utterance %d was not decoded (status %d)", u, d->h_res.p[u].status);
-}
-// ids: the path's symbol ids in time order (which: 0 outputs != 0; 1 inputs != 0 with repetitions dropped as bestHypo(true); 2 inputs != 0 as bestPath)
-static std::vector<uint32_t> path_ids(const dsr_decoder* d, int u, int which)
-{
-  need_last(d, u, true);
-  const dsr_decode_result& r = d->h_res.p[u];
-  const int n = r.nArcs < (int) d->lastMaxPath ? r.nArcs : (int) d->lastMaxPath;
-  const int* arcs = d->h_arcs.p + (size_t) u * d->lastMaxPath;
-  std::vector<uint32_t> ids;
-  if (which == 1) {                                              // from the end, as the reference walks prev(): keep inX when it differs from the LAST KEPT one
-    uint32_t lastX = 0;
-    for (int i = n - 1; i >= 0; i--) { const uint32_t inX = d->csr.in[arcs[i]]; if (inX != 0 && inX != lastX) { ids.push_back(inX); lastX = inX; } }
-    std::reverse(ids.begin(), ids.end());
-  } else for (int i = 0; i < n; i++) { const uint32_t v = which == 0 ? d->csr.out[arcs[i]] : d->csr.in[arcs[i]]; if (v != 0) ids.push_back(v); }
-  return ids;
-}
-dsr_status dsr_decoder_path_ids(const dsr_decoder* d, int u, int which, uint32_t* ids, int cap, int* n)
-{
-  return guard([&] {
-    if (!n || which < 0 || which > 2) throw Error(DSR_E_PARAMETER, "bad argument");
-    const std::vector<uint32_t> v = path_ids(d, u, which);
-    *n = (int) v.size();
-    if (ids) { if ((int) v.size() > cap) throw Error(DSR_E_DIMENSION, "buffer holds %d ids, the path has %zu", cap, v.size()); if (!v.empty()) memcpy(ids, v.data(), 4 * v.size()); }
-  });
-}
-static void put_string(const std::string& s, char* buf, size_t cap, size_t* need)
-{
-  if (need) *need = s.size() + 1;
-  if (buf) { if (s.size() + 1 > cap) throw Error(DSR_E_DIMENSION, "buffer holds %zu bytes, the string needs %zu", cap, s.size() + 1); memcpy(buf, s.c_str(), s.size() + 1); }
-}
-dsr_status dsr_decoder_best_hypo(const dsr_decoder* d, int u, int useInputSymbols, char* buf, size_t cap, size_t* need)
-{
-  return guard([&] {
-    const std::vector<uint32_t> v = path_ids(d, u, useInputSymbols ? 1 : 0);
-    const dsr_lexicon* lex = useInputSymbols ? d->lexIn : d->lexOut;
-    if (!lex) throw Error(DSR_E_KEY, "the transducer set on this decoder has no %s lexicon", useInputSymbols ? "input" : "output");
-    std::string s; for (size_t i = 0; i < v.size(); i++) { s += lex->symbol(v[i]); s += " "; }
-    put_string(s, buf, cap, need);
-  });
-}
-dsr_status dsr_decoder_best_path(const dsr_decoder* d, int u, char* buf, size_t cap, size_t* need, int* count)
-{
-  return guard([&] {
-    const std::vector<uint32_t> v = path_ids(d, u, 2);
-    if (!d->lexIn) throw Error(DSR_E_KEY, "the transducer set on this decoder has no input lexicon");
-    std::string s; for (size_t i = 0; i < v.size(); i++) { s += d->lexIn->symbol(v[i]); s += "\n"; }
-    if (count) *count = (int) v.size();
-    put_string(s, buf, cap, need);
-  });
-}
-dsr_status dsr_decoder_final_states_n(const dsr_decoder* d, int u, int* n)
-{ return guard([&] { if (!n) throw Error(DSR_E_PARAMETER, "null argument"); need_last(d, u, false); *n = d->h_res.p[u].finalStatesN; }); }
-dsr_status dsr_decoder_trace_back_succeeded(const dsr_decoder* d, int u, int* ok)
-{ return guard([&] { if (!ok) throw Error(DSR_E_PARAMETER, "null argument"); need_last(d, u, false); *ok = d->h_res.p[u].reachedFinal; }); }
-
-// _Decoder::setTokenMemoryLimit(limit) (decoder.h:396) caps the reference's Token memory pool (MemoryManager).  Tokens here live in per-slot
-// arrays sized by cfg.maxActive / maxCandidates / arenaTokens (a decode that outgrows them returns DSR_E_ALLOCATION for that utterance): there
-// is no pool to limit.  The value is accepted and kept so that drivers that set it run unchanged.
-dsr_status dsr_decoder_set_token_memory_limit(dsr_decoder* d, unsigned limit)
-{ return guard([&] { if (!d) throw Error(DSR_E_PARAMETER, "null argument"); d->tokenMemoryLimit = limit; }); }
-unsigned dsr_decoder_token_memory_limit(const dsr_decoder* d) { return d ? d->tokenMemoryLimit : 0u; }
-
-dsr_status dsr_decoder_set_beam(dsr_decoder* d, double beam) { return guard([&] { if (!d) throw Error(DSR_E_PARAMETER, "null argument"); d->cfg.beam = beam; }); }
-
-dsr_status dsr_decoder_enable_dump(dsr_decoder* d, int en) { return guard([&] { if (!d) throw Error(DSR_E_PARAMETER, "null argument"); d->dumpOn = en; }); }
-
-// Which XCD a workgroup lands on: HW_REG_XCC_ID of workgroup i of a 64-workgroup grid.  The XCD-bound queues of the time-sliced decode rest on two properties of the
-// dispatcher that are checked here once per process instead of assumed: eight XCDs numbered 0..7, and workgroup i of a grid on XCD (i mod 8) -- so that a grid of 8 k
-// workgroups serves every queue.
-__global__ void k_xcc_probe(int* out) { if (threadIdx.x == 0) out[blockIdx.x] = (int) (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u); }
-static bool xcd_round_robin(hipStream_t st)
-{
-  static int known = -1;
-  if (known >= 0) return known == 1;
-  DevBuf<int> o; o.reserve(64); int h[64];
-  hipLaunchKernelGGL(k_xcc_probe, dim3(64), dim3(64), 0, st, o.p);
-  DSR_HIP(hipMemcpyAsync(h, o.p, sizeof(h), hipMemcpyDeviceToHost, st)); DSR_HIP(hipStreamSynchronize(st));
-  bool ok = true; unsigned seen = 0;
-  for (int i = 0; i < 64; i++) { if (h[i] < 0 || h[i] > 7 || h[i] != h[i & 7]) ok = false; }
-  for (int i = 0; i < 8 && ok; i++) seen |= 1u << h[i];
-  known = (ok && seen == 0xFFu) ? 1 : 0;
-  return known == 1;
-}
-
-static void ensure_scratch(dsr_decoder* d, int slots, int Tmax, int arenas)
-{
-  const dsr_decoder_cfg& c = d->cfg;
-  long arena = c.arenaTokens > 0 ? (long) c.arenaTokens : (long) 8192 * (long) (Tmax + 2);
-  if (arena > 0x7FFFFFF0L) arena = 0x7FFFFFF0L;
-  if (slots <= d->nSlots && arena <= d->arenaCap && (size_t) (arenas > slots ? arenas : slots) * (size_t) arena <= d->d_arena.n) return;
-  if (slots < d->nSlots) slots = d->nSlots;
-  if (arena < d->arenaCap) arena = d->arenaCap;
-  const size_t S = (size_t) slots;
-  d->d_tokA.reserve(S * 2 * c.maxActive); d->d_tokB.reserve(S * 2 * c.maxActive); d->d_ctok.reserve(S * 8192); d->d_side.reserve(S * kFastC);
-  d->d_tokOff.reserve(S * (c.maxActive + 1));
-  d->d_owner.reserve(S * c.maxCandidates); d->d_rank.reserve(S * c.maxCandidates);
-  d->d_cA.reserve(S * c.maxCandidates); d->d_cB.reserve(S * c.maxCandidates);
-  d->d_first.reserve(S * d->nNodes); d->d_tokCnt.reserve(S * (c.maxActive + 1)); d->d_chead.reserve(S * c.maxCandidates);
-  d->d_tags.reserve(S); DSR_HIP(hipMemset(d->d_tags.p, 0, S * sizeof(unsigned)));          // tag 0 = wipe the table on first use
-  d->d_arena.reserve((size_t) (arenas > slots ? arenas : slots) * (size_t) arena);
-  d->d_queue.reserve(8);
-  d->nSlots = slots; d->arenaCap = arena;
-}
-
-// Asynchronous halves of decode_batch: launch enqueues the kernel and the copies of the results into pinned staging
-// memory on `stream` and returns; collect waits for that work and hands the results out.  One launch may be in flight
-// per decoder object (its scratch memory belongs to the launch).
-dsr_status dsr_decoder_decode_launch(dsr_decoder* d, const float* score, const int32_t* nframes, int U, int Tmax, int nDist,
-                                     int maxPath, int want_paths, void* stream)
-{
-  return guard([&] {
-    if (!d || !score || !nframes) throw Error(DSR_E_PARAMETER, "null argument");
-    if (!d->haveGraph) throw Error(DSR_E_INITIALIZATION, "call set() with a transducer first");
-    if (d->pendingU > 0) throw Error(DSR_E_CONSISTENCY, "a decode is already in flight on this decoder: collect it first");
-    if (U <= 0) return;
-    hipStream_t st = (hipStream_t) stream;
-    if (d->cfg.wordTrace) {
-      // DecoderWordTrace (decoder.h:1146-1304).  With generateLattice -- the reference's default -- _placeOnList merges the worse chains of two tokens and reads
-      // wordTrace()->wordSequenceX() of each (decoder.cc:239); a token that has not crossed a word boundary has a null word trace: undefined behaviour in the
-      // reference on any transducer whose first arcs carry no output symbol.  That search is not built; the 1-best search (generateLattice = false) is.
-      if (d->cfg.wordTraceLattice) throw Error(DSR_E_CONSISTENCY, "DecoderWordTrace with generateLattice: not built (the shipped _placeOnList dereferences the null word trace of "
-                                               "every token that has not crossed a word boundary, decoder.cc:239); construct it with generateLattice = false");
-      if (d->cfg.topN > 0 || d->cfg.latticeTokens > 0 || d->dumpOn) throw Error(DSR_E_PARAMETER, "DecoderWordTrace: no topN (its frame loop has no such branch, decoder.cc:147-183), lattice bookkeeping or dump");
-      for (size_t a = 0; a < d->csr.in.size(); a++) if (d->csr.in[a] > (uint32_t) nDist) throw Error(DSR_E_INDEX, "arc input %u has no distribution (nDist=%d)", d->csr.in[a], nDist);
-      int slots = d->cfg.streams; if (slots > U) slots = U;
-      const dsr_decoder_cfg& c = d->cfg; const size_t S = (size_t) slots;
-      const long maxTraces = c.wordTraces > 0 ? (long) c.wordTraces : (long) 1 << 20;
-      d->w_tok.reserve(S * 2 * c.maxActive); d->w_cand.reserve(S * c.maxCandidates); d->w_tokOff.reserve(S * (c.maxActive + 1)); d->w_rank.reserve(S * c.maxCandidates);
-      d->w_traces.reserve((size_t) U * maxTraces); d->d_queue.reserve(8); d->d_res.reserve(U);
-      if (d->w_tablesFor != S * d->nNodes) {                               // the per-state tables are all ones between frames: set once, the kernel restores them
-        d->w_best.reserve(S * d->nNodes); d->w_first.reserve(S * d->nNodes); d->w_tablesFor = S * d->nNodes;
-        DSR_HIP(hipMemsetAsync(d->w_best.p, 0xFF, sizeof(unsigned long long) * S * d->nNodes, st)); DSR_HIP(hipMemsetAsync(d->w_first.p, 0xFF, sizeof(unsigned) * S * d->nNodes, st));
-      }
-      if (maxPath < 1) maxPath = 1;
-      d->d_arcs.reserve((size_t) U * maxPath); d->d_words.reserve((size_t) U * maxPath);
-      DSR_HIP(hipMemsetAsync(d->d_queue.p, 0, 8 * sizeof(int), st));
-      WtArgs A; A.nNodes = d->nNodes; A.initial = d->initial; A.xoff = d->d_xoff.p; A.xrec = d->d_xrec.p; A.xarc = d->d_xarc.p; A.xpathOff = d->d_xpathOff.p; A.eoff = d->d_eoff.p;
-      A.erec = d->d_erec.p; A.path = d->d_path.p; A.arcCost = d->d_arcCost.p; A.arcOut = d->d_arcOut.p; A.arcIn = d->d_arcIn.p; A.nodeFinal = d->d_nodeFinal.p; A.nodeCost = d->d_nodeCost.p;
-      A.beam = c.beam; A.lmScale = c.lmScale; A.lmPenalty = c.lmPenalty; A.silPenalty = c.silPenalty; A.silenceX = c.silenceX; A.insertSilence = c.insertSilence;
-      A.maxTok = c.maxActive; A.maxCand = c.maxCandidates; A.maxTraces = maxTraces;
-      A.tok = d->w_tok.p; A.cand = d->w_cand.p; A.tokOff = d->w_tokOff.p; A.rank = d->w_rank.p; A.bestKey = d->w_best.p; A.firstSlot = d->w_first.p; A.traces = d->w_traces.p; A.queue = d->d_queue.p;
-      A.scores = score; A.nframes = nframes; A.U = U; A.Tmax = Tmax; A.nDist = nDist; A.res = d->d_res.p; A.arcsOut = d->d_arcs.p; A.wordsOut = d->d_words.p; A.maxPath = maxPath;
-      wordtrace_launch(A, slots, st);
-      const size_t nPath = want_paths ? (size_t) U * maxPath : 0;
-      d->h_res.reserve(U); d->h_arcs.reserve(nPath ? nPath : 1); d->h_words.reserve(nPath ? nPath : 1);
-      DSR_HIP(hipMemcpyAsync(d->h_res.p, d->d_res.p, sizeof(dsr_decode_result) * U, hipMemcpyDeviceToHost, st));
-      if (nPath) DSR_HIP(hipMemcpyAsync(d->h_arcs.p, d->d_arcs.p, sizeof(int) * nPath, hipMemcpyDeviceToHost, st));
-      if (nPath) DSR_HIP(hipMemcpyAsync(d->h_words.p, d->d_words.p, sizeof(unsigned) * nPath, hipMemcpyDeviceToHost, st));
-      if (!d->evDone) DSR_HIP(hipEventCreateWithFlags(&d->evDone, hipEventDisableTiming));
-      DSR_HIP(hipEventRecord(d->evDone, st));
-      d->pendingU = U; d->pendingPath = nPath; d->pendingSlots = slots; d->pendingProf = nullptr; d->latU = 0;
-      return;
-    }
-    int32_t* arcs_out = want_paths ? (int32_t*) 1 : nullptr; uint32_t* words_out = want_paths ? (uint32_t*) 1 : nullptr;     // (only tested for null below)
-    // every input symbol must name a distribution (decoder.h:985: _dist->find(distX-1))
-    for (size_t a = 0; a < d->csr.in.size(); a++) if (d->csr.in[a] > (uint32_t) nDist) throw Error(DSR_E_INDEX, "arc input %u has no distribution (nDist=%d)", d->csr.in[a], nDist);
-    int slots = d->cfg.streams; if (slots > U) slots = U; if (d->dumpOn) slots = 1;
-    const bool latOn = d->cfg.latticeTokens > 0;
-    if (latOn && d->dumpOn) throw Error(DSR_E_PARAMETER, "lattice bookkeeping and the token dump are separate debugging aids: enable one");
-    // Time slicing (DecDev): when there are more utterances than workgroups, in the plain decode mode.  DSR_VITERBI_SEG = frames per segment (0: run every utterance to completion).
-    int segFrames = 0;
-    if (!latOn && !d->dumpOn && d->cfg.topN <= 0 && U > slots) {
-      segFrames = getenv("DSR_VITERBI_SEG") ? atoi(getenv("DSR_VITERBI_SEG")) : 125;
-      if (segFrames < 0 || 2 * segFrames > Tmax + 1) segFrames = 0;
-      // between its segments an utterance's token list waits in a save area of maxActive tokens: with very large lists and very many utterances that is more memory
-      // than the scheduling is worth (DSR_VITERBI_SEG_SAVE_GB, default 16)
-      const double saveGB = (double) U * (double) d->cfg.maxActive * 24.0 / 1e9;
-      if (saveGB > (getenv("DSR_VITERBI_SEG_SAVE_GB") ? atof(getenv("DSR_VITERBI_SEG_SAVE_GB")) : 16.0)) segFrames = 0;
-    }
-    // XCD-bound queues (the cheap hand-over) need workgroups on every XCD: grids of 8 k >= 64 workgroups on a device that deals workgroups out round robin.
-    // Anything else decodes every utterance in one go -- unless DSR_VITERBI_SEG_ANY asks for the one-queue form (device-scope fences at every hand-over: the tests).
-    int segQueues = 8;
-    if (segFrames > 0 && !(slots >= 64 && slots % 8 == 0 && xcd_round_robin((hipStream_t) stream))) { if (getenv("DSR_VITERBI_SEG_ANY")) segQueues = 1; else segFrames = 0; }
-    if (segFrames > 0 && getenv("DSR_VITERBI_SEG_ANY") && atoi(getenv("DSR_VITERBI_SEG_ANY")) == 2) segQueues = 1;
-    // (sliced: one pool of back-pointer records for the batch instead of an arena per slot -- 1536 records per utterance and frame on average, at least what the slots had)
-    const long arenaPer = d->cfg.arenaTokens > 0 ? (long) d->cfg.arenaTokens : (long) 8192 * (long) (Tmax + 2);
-    int poolArenas = 0;
-    if (segFrames > 0) {
-      const double want = (double) U * 1536.0 * (double) (Tmax + 2) / (double) arenaPer;
-      poolArenas = (int) std::min<double>(std::ceil(want), (double) (0xFFFFFFF0u / (unsigned long long) arenaPer));
-      if ((unsigned long long) std::max(poolArenas, slots) * (unsigned long long) arenaPer > 0xFFFFFFF0ull) segFrames = 0;      // back pointers are 32-bit pool indices
-    }
-    ensure_scratch(d, slots, Tmax, latOn ? U : (segFrames > 0 ? poolArenas : 0));
-    d->d_res.reserve(U);
-    if (maxPath < 0) maxPath = 0;
-    if (arcs_out || words_out) { d->d_arcs.reserve((size_t) U * (maxPath > 0 ? maxPath : 1)); d->d_words.reserve((size_t) U * (maxPath > 0 ? maxPath : 1)); }
-    DSR_HIP(hipMemsetAsync(d->d_queue.p, 0, 8 * sizeof(int), st));
-    if (d->dumpOn) {
-      d->dumpCap = (long) d->cfg.maxActive * 64 < (long) 1 << 26 ? (long) 1 << 24 : (long) 1 << 26;
-      d->d_dumpFrameOff.reserve(Tmax + 2); d->d_dumpCount.reserve(2);
-      d->d_dumpNode.reserve(d->dumpCap); d->d_dumpArc.reserve(d->dumpCap); d->d_dumpAc.reserve(d->dumpCap); d->d_dumpLm.reserve(d->dumpCap);
-      DSR_HIP(hipMemsetAsync(d->d_dumpCount.p, 0, 2 * sizeof(long), st));
-    }
-    GraphDev G; G.nNodes = d->nNodes; G.initial = d->initial; G.xoff = d->d_xoff.p; G.xrec = d->d_xrec.p; G.xrecD = d->d_xrecD.p; G.xarc = d->d_xarc.p;
-    G.xpathOff = d->d_xpathOff.p; G.eoff = d->d_eoff.p; G.erec = d->d_erec.p; G.path = d->d_path.p; G.pathCost = d->d_pathCost.p; G.arcCost = d->d_arcCost.p;
-    G.arcOut = d->d_arcOut.p; G.arcIn = d->d_arcIn.p; G.nodeFinal = d->d_nodeFinal.p; G.nodeCost = d->d_nodeCost.p;
-    DecDev D; D.beam = d->cfg.beam; D.lmScale = d->cfg.lmScale; D.lmPenalty = d->cfg.lmPenalty; D.silPenalty = d->cfg.silPenalty;
-    // penalty-free expansion (k_viterbi, expandR): both penalty products zero, and no placement's lm can be -0.0 -- lmScale > 0, no arc cost of -0.0, and every
-    // non-zero lmScale x cost at least 2^-60 in magnitude (a sum float + double of that size is 0 or at least 2^-112: it cannot round to -0.0f)
-    D.noPen = (d->cfg.lmScale > 0.0 && std::isfinite(d->cfg.lmScale) && d->cfg.lmScale * d->cfg.lmPenalty == 0.0 && d->cfg.lmScale * d->cfg.silPenalty == 0.0 &&
-               !d->costNegZero && (d->costMinAbs == HUGE_VAL || d->cfg.lmScale * d->costMinAbs >= 0x1p-60) && !getenv("DSR_VITERBI_PEN")) ? 1 : 0;
-    D.silenceX = d->cfg.silenceX; D.maxTok = d->cfg.maxActive; D.maxCand = d->cfg.maxCandidates; D.arenaCap = d->arenaCap;
-    D.tokA = d->d_tokA.p; D.tokB = d->d_tokB.p; D.ctok = d->d_ctok.p; D.side = d->d_side.p; D.fastOK = d->fastOK; D.tokOff = d->d_tokOff.p; D.owner = d->d_owner.p; D.rank = d->d_rank.p; D.cA = d->d_cA.p; D.cB = d->d_cB.p;
-    D.first = d->d_first.p; D.tags = d->d_tags.p; D.tokCnt = d->d_tokCnt.p; D.chead = d->d_chead.p; D.arena = d->d_arena.p; D.queue = d->d_queue.p;
-    D.segDrop = getenv("DSR_VITERBI_SEG_DROP") ? (int) strtol(getenv("DSR_VITERBI_SEG_DROP"), nullptr, 0) : 0;
-    D.segQueues = segQueues; D.segFrames = segFrames; D.segCount = segFrames > 0 ? (Tmax + segFrames) / segFrames : 1;            // segments cover frames 0 .. Tmax (the end expansion is "frame" T)
-    D.poolCap = 0; D.poolChunk = 0; D.poolNext = nullptr; D.segState = nullptr; D.segDone = nullptr; D.saveA = nullptr; D.saveB = nullptr;
-    if (segFrames > 0) {
-      d->d_segState.reserve(U); d->d_segDone.reserve(U); d->d_poolNext.reserve(1);
-      d->d_saveA.reserve((size_t) U * d->cfg.maxActive); d->d_saveB.reserve((size_t) U * d->cfg.maxActive);
-      DSR_HIP(hipMemsetAsync(d->d_segDone.p, 0, sizeof(int) * (size_t) U, st)); DSR_HIP(hipMemsetAsync(d->d_poolNext.p, 0, sizeof(unsigned long long), st));
-      D.poolCap = (long) ((size_t) std::max(poolArenas, slots) * (size_t) d->arenaCap); if (D.poolCap > (long) 0xFFFFFFF0L) D.poolCap = (long) 0xFFFFFFF0L;
-      D.poolChunk = std::min<long>(262144, std::max<long>(4096, D.poolCap / (4 * (long) U)));      // (what an utterance leaves unused of its last run: at most a quarter of the pool in all)
-      D.poolNext = d->d_poolNext.p; D.segState = d->d_segState.p; D.segDone = d->d_segDone.p; D.saveA = d->d_saveA.p; D.saveB = d->d_saveB.p;
-    }
-    d->lastPoolCap = D.poolCap;
-    D.prof = nullptr;
-    if (getenv("DSR_VITERBI_PROF")) { d->d_prof.reserve((size_t) slots * kProfN); D.prof = d->d_prof.p; }
-    D.dumpOn = d->dumpOn; D.dumpCap = d->dumpCap; D.dumpFrameOff = d->d_dumpFrameOff.p; D.dumpNode = d->d_dumpNode.p; D.dumpAc = d->d_dumpAc.p;
-    D.dumpLm = d->d_dumpLm.p; D.dumpArc = d->d_dumpArc.p; D.dumpCount = d->d_dumpCount.p;
-    D.topN = d->cfg.topN > 0 ? d->cfg.topN : 0; D.tokA3 = nullptr; D.tokB3 = nullptr;
-    if (D.topN > 0) { d->d_tokA3.reserve((size_t) slots * d->cfg.maxActive); d->d_tokB3.reserve((size_t) slots * d->cfg.maxActive); D.tokA3 = d->d_tokA3.p; D.tokB3 = d->d_tokB3.p; }
-    D.latOn = latOn ? 1 : 0; D.latCap = 0; D.lat = nullptr; D.latTtl = nullptr; D.latFrameOff = nullptr; D.arenaLat = nullptr; D.latFinal = nullptr; D.latInfo = nullptr;
-    if (latOn) {
-      const size_t cap = (size_t) d->cfg.latticeTokens;
-      d->d_lat.reserve((size_t) U * cap); d->d_latTtl.reserve((size_t) U * cap); d->d_latFrameOff.reserve((size_t) U * (Tmax + 3));
-      d->d_arenaLat.reserve((size_t) U * (size_t) d->arenaCap); d->d_latFinal.reserve((size_t) U * d->cfg.maxActive); d->d_latInfo.reserve((size_t) 4 * U);
-      DSR_HIP(hipMemsetAsync(d->d_latInfo.p, 0, sizeof(int) * 4 * (size_t) U, st));
-      D.latCap = (long) cap; D.lat = d->d_lat.p; D.latTtl = d->d_latTtl.p; D.latFrameOff = d->d_latFrameOff.p; D.arenaLat = d->d_arenaLat.p; D.latFinal = d->d_latFinal.p; D.latInfo = d->d_latInfo.p;
-      d->latU = U; d->latTmax = Tmax; d->latArenaCap = d->arenaCap;
-    } else d->latU = 0;
-    // LDS: [score row][state table: 2 x hashN words][later arrivals' side records][expansion counts]; the row stays in global memory
-    // when it would push the state table below the size the register path needs.  One 1024-thread workgroup per CU.  The table's 2 x hashN words are
-    // hashN = 16 384 two-word buckets (wide: key array + first-arrival array) or, for graphs of at most 65 535 states, 32 768 one-word buckets
-    // (narrow: flag | key or side record | slot) -- the formula below gives the same number of bytes for both, 128 KB at hashN = 16 384.
-    // instantiations: bit 0 per-phase ticks (DSR_VITERBI_PROF), bit 1 lattice bookkeeping / topN / token dump compiled in, bit 2 narrow table
-    // (chosen below, once hashN is known; the static LDS does not depend on it)
-    int modes = (D.prof ? 1 : 0) | ((latOn || D.topN > 0 || d->dumpOn) ? 2 : 0);
-    const void* kfn = modes == 0 ? (const void*) k_viterbi<0> : modes == 1 ? (const void*) k_viterbi<1> : modes == 2 ? (const void*) k_viterbi<2> : (const void*) k_viterbi<3>;
-    hipFuncAttributes fattr; DSR_HIP(hipFuncGetAttributes(&fattr, kfn));
-    const size_t eoffB = (size_t) kSideLds * sizeof(Side); const size_t ldsCap = (size_t) 160 * 1024 - fattr.sharedSizeBytes;      // what the kernel's static LDS leaves of a CU's 160 KB
-    const int hashMax = 16384;
-    int useLds = (size_t) nDist * sizeof(float) <= 64 * 1024;
-    if (useLds && (size_t) ((nDist + 3) & ~3) * sizeof(float) + (size_t) hashMax * 8 + eoffB > ldsCap) useLds = 0;
-    const size_t rowB = useLds ? (size_t) ((nDist + 3) & ~3) * sizeof(float) : 16;
-    int hashN = hashMax; while (hashN > 0 && rowB + (size_t) hashN * 8 + eoffB > ldsCap) hashN >>= 1;
-    if (getenv("DSR_VITERBI_NOHASH")) hashN = 0;
-    // + the expansion counts of up to 2048 tokens (u16) when the budget and the graph's largest fan-out allow
-    int cntCap = (hashN > 0 && d->maxCnt < 65536 && rowB + (size_t) hashN * 8 + eoffB + 4096 <= ldsCap) ? 2048 : 0;
-    if (getenv("DSR_VITERBI_NOCNT")) cntCap = 0;
-    const size_t lds = rowB + (size_t) hashN * 8 + eoffB + 2 * (size_t) cntCap;
-    // narrow table: the key field holds state + 1 in 16 bits, the slot field 15 bits = the 24 576 placements 32 768 buckets take at a load of 0.75
-    // (DSR_VITERBI_TABLE=wide: the two-array table whatever the graph -- A/B runs and the tests)
-    const char* const tableEnv = getenv("DSR_VITERBI_TABLE");
-    const bool narrow = d->nNodes <= 65535 && hashN == hashMax && !(tableEnv && !strcmp(tableEnv, "wide"));
-    if (narrow) modes |= 4;
-    if (getenv("DSR_VITERBI_SEG_VERBOSE")) fprintf(stderr, "[dsr viterbi] %d utterances on %d workgroups: %s, %s state table\n", U, slots, segFrames > 0 ? (segQueues == 8 ? "time-sliced, XCD-bound queues" : "time-sliced, one queue") : "run to completion", narrow ? "narrow" : "wide");
-    VitArgs A; A.G = G; A.D = D; A.scores = score; A.nframesArr = nframes; A.U = U; A.Tmax = Tmax; A.nDist = nDist; A.res = d->d_res.p;
-    A.arcsOut = (arcs_out || words_out) ? d->d_arcs.p : nullptr; A.wordsOut = (arcs_out || words_out) ? d->d_words.p : nullptr; A.maxPath = maxPath;
-    A.useLdsRow = useLds; A.hashN = hashN; A.regionB = (int) eoffB; A.cntCap = cntCap;
-#define DSR_LAUNCH_V(MM) { DSR_HIP(hipFuncSetAttribute((const void*) k_viterbi<MM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); \
-      hipLaunchKernelGGL(k_viterbi<MM>, dim3(slots), dim3(kThreads), lds, st, A); }
-    switch (modes) { case 0: DSR_LAUNCH_V(0) break; case 1: DSR_LAUNCH_V(1) break; case 2: DSR_LAUNCH_V(2) break; case 3: DSR_LAUNCH_V(3) break;
-                     case 4: DSR_LAUNCH_V(4) break; case 5: DSR_LAUNCH_V(5) break; case 6: DSR_LAUNCH_V(6) break; default: DSR_LAUNCH_V(7) break; }
-#undef DSR_LAUNCH_V
-    DSR_HIP(hipGetLastError());
-    const size_t nPath = want_paths ? (size_t) U * maxPath : 0;
-    d->h_res.reserve(U); d->h_arcs.reserve(nPath ? nPath : 1); d->h_words.reserve(nPath ? nPath : 1);
-    DSR_HIP(hipMemcpyAsync(d->h_res.p, d->d_res.p, sizeof(dsr_decode_result) * U, hipMemcpyDeviceToHost, st));
-    if (nPath) DSR_HIP(hipMemcpyAsync(d->h_arcs.p, d->d_arcs.p, sizeof(int) * nPath, hipMemcpyDeviceToHost, st));
-    if (nPath) DSR_HIP(hipMemcpyAsync(d->h_words.p, d->d_words.p, sizeof(unsigned) * nPath, hipMemcpyDeviceToHost, st));
-    if (!d->evDone) DSR_HIP(hipEventCreateWithFlags(&d->evDone, hipEventDisableTiming));
-    DSR_HIP(hipEventRecord(d->evDone, st));
-    d->pendingU = U; d->pendingPath = nPath; d->pendingSlots = slots; d->pendingProf = D.prof;
-  });
-}
-
-dsr_status dsr_decoder_decode_collect(dsr_decoder* d, dsr_decode_result* res, int32_t* arcs_out, uint32_t* words_out)
-{
-  return guard([&] {
-    if (!d || !res) throw Error(DSR_E_PARAMETER, "null argument");
-    if (d->pendingU <= 0) throw Error(DSR_E_CONSISTENCY, "no decode in flight");
-    const int U = d->pendingU; const size_t nPath = d->pendingPath; const int slots = d->pendingSlots; long long* prof = d->pendingProf;
-    d->pendingU = 0; d->lastU = U; d->lastPaths = nPath > 0; d->lastMaxPath = nPath > 0 ? nPath / (size_t) U : 0;
-    DSR_HIP(hipEventSynchronize(d->evDone));
-    memcpy(res, d->h_res.p, sizeof(dsr_decode_result) * U);
-    if (arcs_out && nPath) memcpy(arcs_out, d->h_arcs.p, sizeof(int) * nPath);
-    if (words_out && nPath) memcpy(words_out, d->h_words.p, sizeof(unsigned) * nPath);
-    if (getenv("DSR_VITERBI_SEG_VERBOSE") && d->d_poolNext.p && d->lastPoolCap > 0) {
-      unsigned long long used = 0; DSR_HIP(hipMemcpy(&used, d->d_poolNext.p, sizeof(used), hipMemcpyDeviceToHost));
-      fprintf(stderr, "[dsr viterbi] pool of back-pointer records: %.1f M of %.1f M taken\n", used / 1e6, d->lastPoolCap / 1e6);
-    }
-    if (prof) {
-      std::vector<long long> hp((size_t) slots * kProfN); DSR_HIP(hipMemcpy(hp.data(), prof, hp.size() * sizeof(long long), hipMemcpyDeviceToHost));
-      double acc[32] = {0}; for (int s2 = 0; s2 < slots; s2++) for (int i = 0; i < 32; i++) acc[i] += (double) hp[(size_t) s2 * kProfN + i];
-      fprintf(stderr, "[dsr viterbi prof] mean us per slot:");
-      for (int i = 0; i < 32; i++) if (i != 15) fprintf(stderr, " p%d=%.0f", i, acc[i] / slots / 100.0);
-      fprintf(stderr, "\n");
-      double tmin = 1e30, tmax = 0.0, tsum = 0.0;                   // busy time per slot: how even the slots' shares of the batch were
-      for (int s2 = 0; s2 < slots; s2++) { double t = 0.0; for (int i = 0; i < 32; i++) if (i != 15) t += (double) hp[(size_t) s2 * kProfN + i]; t /= 100.0; tsum += t; if (t < tmin) tmin = t; if (t > tmax) tmax = t; }
-      {                                                             // frames by size class: share of the frames, share of their time, us per frame, ns per placement
-        double h[12] = {0}; for (int s2 = 0; s2 < slots; s2++) for (int i = 0; i < 12; i++) h[i] += (double) hp[(size_t) s2 * kProfN + 32 + i];
-        const double nf = h[0] + h[1] + h[2] + h[3], tk = h[4] + h[5] + h[6] + h[7];
-        static const char* const cn[4] = {"<=8192", "<=12288", ">12288", "memory path"};
-        for (int c = 0; c < 4; c++) if (h[c] > 0) fprintf(stderr, "[dsr viterbi prof] frames with %s placements: %.1f %% of the frames, %.1f %% of the frame time, %.1f us per frame, %.2f ns per placement\n",
-                                                          cn[c], 100.0 * h[c] / nf, 100.0 * h[4 + c] / tk, h[4 + c] / 100.0 / h[c], h[4 + c] * 10.0 / h[8 + c]);
-      }
-      fprintf(stderr, "[dsr viterbi prof] busy us per slot: mean %.0f min %.0f max %.0f\n", tsum / slots, tmin, tmax);
-      if (slots >= 64 && slots % 8 == 0) {                       // by XCD (workgroup i runs on XCD i mod 8): how even the eight queues of the time-sliced decode come out
-        double bx[8] = {0}; for (int s2 = 0; s2 < slots; s2++) { double t = 0.0; for (int i = 0; i < 32; i++) if (i != 15) t += (double) hp[(size_t) s2 * kProfN + i]; bx[s2 & 7] += t / 100.0; }
-        fprintf(stderr, "[dsr viterbi prof] busy us per slot, by XCD:"); for (int q = 0; q < 8; q++) fprintf(stderr, " %.0f", bx[q] / (slots / 8)); fprintf(stderr, "\n");
-      }
-    }
-    if (d->dumpOn) {
-      long cnt[2]; DSR_HIP(hipMemcpy(cnt, d->d_dumpCount.p, sizeof(cnt), hipMemcpyDeviceToHost));
-      const long N = cnt[0] < d->dumpCap ? cnt[0] : d->dumpCap; d->h_dumpFrames = cnt[1];
-      std::vector<long> fo(cnt[1] + 1); if (cnt[1] > 0) DSR_HIP(hipMemcpy(fo.data(), d->d_dumpFrameOff.p, sizeof(long) * (cnt[1] + 1), hipMemcpyDeviceToHost));
-      d->h_dumpFrameOff.assign(fo.begin(), fo.end());
-      d->h_dumpNode.resize(N); d->h_dumpArc.resize(N); d->h_dumpAc.resize(N); d->h_dumpLm.resize(N);
-      if (N > 0) {
-        DSR_HIP(hipMemcpy(d->h_dumpNode.data(), d->d_dumpNode.p, sizeof(int) * N, hipMemcpyDeviceToHost));
-        DSR_HIP(hipMemcpy(d->h_dumpArc.data(), d->d_dumpArc.p, sizeof(int) * N, hipMemcpyDeviceToHost));
-        DSR_HIP(hipMemcpy(d->h_dumpAc.data(), d->d_dumpAc.p, sizeof(float) * N, hipMemcpyDeviceToHost));
-        DSR_HIP(hipMemcpy(d->h_dumpLm.data(), d->d_dumpLm.p, sizeof(float) * N, hipMemcpyDeviceToHost));
-      }
-    }
-  });
-}
-
-dsr_status dsr_decoder_decode_batch(dsr_decoder* d, const float* score, const int32_t* nframes, int U, int Tmax, int nDist,
-                                    dsr_decode_result* res, int32_t* arcs_out, uint32_t* words_out, int maxPath, void* stream)
-{
-  if (!res) return guard([&] { throw Error(DSR_E_PARAMETER, "null argument"); });
-  if (U <= 0) return DSR_OK;
-  const dsr_status s1 = dsr_decoder_decode_launch(d, score, nframes, U, Tmax, nDist, maxPath, (arcs_out || words_out) ? 1 : 0, stream);
-  if (s1 != DSR_OK) return s1;
-  return dsr_decoder_decode_collect(d, res, arcs_out, words_out);
-}
-
-// _Decoder::lattice() (decoder.h:805-860) for utterance u of the last decode (cfg.latticeTokens > 0)
-// the placement log of utterance u of the last lattice-mode decode, copied to the host
-namespace {
-struct LatHost {
-  std::vector<long> frameOff; std::vector<dsr::LatPlace> place; std::vector<double> ttl; std::vector<dsr::LatBp> arena; std::vector<int> arenaLat; std::vector<dsr::LatFinalTok> fin;
-  dsr::LatInput in;
-};
-void load_lat(dsr_decoder* d, int u, uint32_t eosX, LatHost& H)
-{
-  if (d->latU <= 0) throw Error(DSR_E_CONSISTENCY, "Must enable lattice generation during decoding.");                 // decoder.h:807-808
-  if (d->pendingU > 0) throw Error(DSR_E_CONSISTENCY, "a decode is in flight: collect it first");
-  if (u < 0 || u >= d->latU) throw Error(DSR_E_INDEX, "utterance %d of %d", u, d->latU);
-  int info[4]; DSR_HIP(hipMemcpy(info, d->d_latInfo.p + 4 * (size_t) u, sizeof(info), hipMemcpyDeviceToHost));
-  const int finN = info[0], haveNext = info[1], T = info[3]; const long arenaN = info[2];
-  if (T <= 0) throw Error(DSR_E_CONSISTENCY, "utterance %d was not decoded to its end (status of its decode result)", u);
-  H.frameOff.assign((size_t) T + 2, 0);
-  DSR_HIP(hipMemcpy(H.frameOff.data(), d->d_latFrameOff.p + (size_t) u * (d->latTmax + 3), sizeof(long) * ((size_t) T + 2), hipMemcpyDeviceToHost));
-  const long nP = H.frameOff[(size_t) T + 1];
-  H.place.resize((size_t) (nP > 0 ? nP : 1)); H.ttl.resize((size_t) (nP > 0 ? nP : 1));
-  H.arena.resize((size_t) (arenaN > 0 ? arenaN : 1)); H.arenaLat.resize((size_t) (arenaN > 0 ? arenaN : 1)); H.fin.resize((size_t) (finN > 0 ? finN : 1));
-  const size_t cap = (size_t) d->cfg.latticeTokens;
-  if (nP > 0) { DSR_HIP(hipMemcpy(H.place.data(), d->d_lat.p + (size_t) u * cap, sizeof(LatPlace) * (size_t) nP, hipMemcpyDeviceToHost));
-                DSR_HIP(hipMemcpy(H.ttl.data(), d->d_latTtl.p + (size_t) u * cap, sizeof(double) * (size_t) nP, hipMemcpyDeviceToHost)); }
-  if (arenaN > 0) { DSR_HIP(hipMemcpy(H.arena.data(), d->d_arena.p + (size_t) u * (size_t) d->latArenaCap, sizeof(LatBp) * (size_t) arenaN, hipMemcpyDeviceToHost));
-                    DSR_HIP(hipMemcpy(H.arenaLat.data(), d->d_arenaLat.p + (size_t) u * (size_t) d->latArenaCap, sizeof(int) * (size_t) arenaN, hipMemcpyDeviceToHost)); }
-  if (finN > 0) DSR_HIP(hipMemcpy(H.fin.data(), d->d_latFinal.p + (size_t) u * d->cfg.maxActive, sizeof(LatFinalTok) * (size_t) finN, hipMemcpyDeviceToHost));
-  LatInput& in = H.in; in.graph = &d->graphCopy; in.csr = &d->csr; in.tab = &d->tab; in.lmScale = d->cfg.lmScale; in.lmPenalty = d->cfg.lmPenalty; in.silPenalty = d->cfg.silPenalty;
-  in.silenceX = d->cfg.silenceX; in.eosX = eosX; in.T = T; in.place = H.place.data(); in.ttl = H.ttl.data(); in.frameOff = H.frameOff.data();
-  in.arena = H.arena.data(); in.arenaLat = H.arenaLat.data(); in.arenaN = arenaN; in.fin = H.fin.data(); in.finN = finN; in.haveNext = haveNext;
-}
-}  // namespace
-
-dsr_status dsr_decoder_lattice(dsr_decoder* d, int u, uint32_t eosX, dsr_lattice** out)
-{
-  return guard([&] {
-    if (!d || !out) throw Error(DSR_E_PARAMETER, "null argument");
-    LatHost H; load_lat(d, u, eosX, H);
-    dsr_lattice* L = new dsr_lattice();
-    try { build_lattice(H.in, *L); } catch (...) { delete L; throw; }
-    *out = L;
-  });
-}
-
-// _Decoder::writeGMM(conv, channel, spk, utt, cfrom, score, fileName, frameInterval) (decoder.h:1018-1102; decoder.i:177-178): the 1-best path as
-// runs of equal input symbols -- "# utt cfrom score", then per run "conv channel start duration label score", first run first, the end-of-sentence
-// label skipped.  The walk needs every token of the best path with its frame and scores: the decoder must have run with lattice bookkeeping
-// (latticeTokens > 0, the reference's generateLattice) and symbols set (dsr_decoder_set_symbols: labels come from the input lexicon, :1066).
-// fileName "" or NULL: stdout; files are appended to (:1023).  (spk is accepted and unused, as in the reference.)
-dsr_status dsr_decoder_write_gmm(dsr_decoder* d, int u, const char* conv, const char* channel, const char* spk, const char* utt, double cfrom, double score,
-                                 const char* fileName, double frameInterval)
-{
-  return guard([&] {
-    (void) spk;
-    if (!d || !conv || !channel || !utt) throw Error(DSR_E_PARAMETER, "null argument");
-    if (!d->lexIn) throw Error(DSR_E_KEY, "the transducer set on this decoder has no input lexicon");
-    LatHost H; load_lat(d, u, 0u, H);
-    std::vector<GmmRow> rows;
-    if (!best_path_gmm(H.in, rows)) throw Error(DSR_E_CONSISTENCY, "no best token");       // (the reference dereferences a null token here)
-    FILE* fp = (!fileName || !*fileName) ? stdout : fopen(fileName, "a");
-    if (!fp) throw Error(DSR_E_IO, "could not open %s", fileName);
-    fprintf(fp, "# %s %10.4f %10.4f\n", utt, cfrom, score);
-    for (int i = (int) rows.size() - 1; i >= 0; i--) {
-      if (rows[i].inX >= d->lexIn->syms.size()) { if (fp != stdout) fclose(fp); throw Error(DSR_E_INDEX, "input symbol %u is not in the lexicon", rows[i].inX); }
-      const std::string& lab = d->lexIn->symbol(rows[i].inX); const char* label = lab.c_str();
-      if (lab == d->eosSymbol) continue;
-      const double beg = cfrom + rows[i].startX * frameInterval, len = (rows[i].endX - rows[i].startX + 1) * frameInterval;
-      fprintf(fp, "%s %s %7.2f %7.2f %-20s %7.2f\n", conv, channel, beg, len, label, rows[i].score);
-    }
-    if (fp != stdout) fclose(fp); else fflush(stdout);
-  });
-}
-void dsr_lattice_destroy(dsr_lattice* L) { delete L; }
-int dsr_lattice_num_nodes(const dsr_lattice* L) { return L ? (int) L->nodeFinal.size() : 0; }
-int dsr_lattice_num_edges(const dsr_lattice* L) { return L ? (int) L->from.size() : 0; }
-int dsr_lattice_final_states_n(const dsr_lattice* L) { return L ? L->finalStatesN : 0; }
-dsr_status dsr_lattice_get(const dsr_lattice* L, int32_t* nodeFinal, int32_t* from, int32_t* to, uint32_t* in, uint32_t* out, int32_t* start, int32_t* end, double* ac, double* lm)
-{
-  return guard([&] {
-    if (!L) throw Error(DSR_E_PARAMETER, "null argument");
-    const size_t nE = L->from.size();
-    if (nodeFinal) memcpy(nodeFinal, L->nodeFinal.data(), 4 * L->nodeFinal.size());
-    if (from && nE) memcpy(from, L->from.data(), 4 * nE); if (to && nE) memcpy(to, L->to.data(), 4 * nE);
-    if (in && nE) memcpy(in, L->in.data(), 4 * nE); if (out && nE) memcpy(out, L->out.data(), 4 * nE);
-    if (start && nE) memcpy(start, L->start.data(), 4 * nE); if (end && nE) memcpy(end, L->end.data(), 4 * nE);
-    if (ac && nE) memcpy(ac, L->ac.data(), 8 * nE); if (lm && nE) memcpy(lm, L->lm.data(), 8 * nE);
-  });
-}
-dsr_status dsr_lattice_write(dsr_lattice* L, const char* fileName, int writeData)
-{ return guard([&] { if (!L || !fileName) throw Error(DSR_E_PARAMETER, "null argument"); L->write(fileName, writeData != 0); }); }
-size_t dsr_lattice_pack_size(const dsr_lattice* L) { return L ? 16 + 4 * L->nodeFinal.size() + 40 * L->from.size() : 0; }
-dsr_status dsr_lattice_pack(const dsr_lattice* L, void* buf, size_t bufBytes)
-{
-  return guard([&] {
-    if (!L || !buf) throw Error(DSR_E_PARAMETER, "null argument");
-    const std::vector<unsigned char> b = L->pack();
-    if (b.size() > bufBytes) throw Error(DSR_E_DIMENSION, "buffer holds %zu bytes, the lattice needs %zu", bufBytes, b.size());
-    memcpy(buf, b.data(), b.size());
-  });
-}
-dsr_status dsr_lattice_unpack(const void* buf, size_t bytes, dsr_lattice** out)
-{
-  return guard([&] {
-    if (!buf || !out) throw Error(DSR_E_PARAMETER, "null argument");
-    dsr_lattice* L = new dsr_lattice();
-    try { static_cast<LatticeData&>(*L) = LatticeData::unpack((const unsigned char*) buf, bytes); } catch (...) { delete L; throw; }
-    *out = L;
-  });
-}
-
-dsr_status dsr_decoder_get_dump(dsr_decoder* d, int64_t* nFrames, const int64_t** frameOff, const int32_t** node,
-                                const float** ac, const float** lm, const int32_t** arc)
-{
-  return guard([&] {
-    if (!d) throw Error(DSR_E_PARAMETER, "null argument");
-    if (nFrames) *nFrames = d->h_dumpFrames;
-    if (frameOff) *frameOff = d->h_dumpFrameOff.data();
-    if (node) *node = d->h_dumpNode.data(); if (arc) *arc = d->h_dumpArc.data();
-    if (ac) *ac = d->h_dumpAc.data(); if (lm) *lm = d->h_dumpLm.data();
-  });
-}
-
-}  // extern "C"
+}  // namespace dsr

@@ -61,3 +61,7 @@ struct WfstGraph {
 };
 
 }  // namespace dsr
+
+// the C-ABI's transducer handle (wfst_capi.cpp): the graph and the lexica it borrows (the decoder resolves its symbols in them, decoder.cpp)
+struct dsr_lexicon;
+struct dsr_wfst : dsr::WfstGraph { dsr_lexicon* lexState = nullptr; dsr_lexicon* lexIn = nullptr; dsr_lexicon* lexOut = nullptr; };

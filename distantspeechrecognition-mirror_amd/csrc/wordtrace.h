@@ -1,4 +1,4 @@
-// csrc/wordtrace.h -- what the decoder object (k_viterbi.hip) hands to the DecoderWordTrace search kernel (k_wordtrace.hip)
+// csrc/wordtrace.h -- what the decoder object (decoder.cpp) hands to the DecoderWordTrace search kernel (k_wordtrace.hip)
 #pragma once
 #include "common.h"
 #include "wfst_graph.h"

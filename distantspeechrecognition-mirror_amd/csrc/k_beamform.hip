@@ -260,6 +260,28 @@ __global__ __launch_bounds__(64) void k_gsc_rls(const float2* __restrict__ X, co
 
 struct dsr_bf : BfState {};
 
+// The dispatch of gsc_rls_apply, in one place: the launch below switches on it and dsr_bf_rls_path reports it.  n = C - 1; the precision matrix and the
+// active weights of a thread are n^2 + n complex fp64 values: in registers for the channel counts k_gsc_rls is instantiated for with a compile-time
+// count (RLS_CT_LIST), else in LDS ([entry][lane]) when the 64 lanes' values fit 150 KB (C <= 12), else in memory, in place.  The vectors of a thread
+// have room for 16 channels, or 64 above that.  DSR_RLS_NOREGS / DSR_RLS_MEMSTATE (set to anything) take the first / the first two residences out;
+// both are read on every call.
+#define RLS_CT_LIST(DO) DO(4) DO(6) DO(8)
+struct RlsPath { int ct, cap, residence; size_t stateBytes, ldsBytes; };
+static RlsPath rls_path(int C)
+{
+  RlsPath r; const int n = C - 1;
+  r.ct = 0;
+#define RLS_CT_IS(CTV) if (C == CTV) r.ct = CTV;
+  RLS_CT_LIST(RLS_CT_IS)
+#undef RLS_CT_IS
+  r.cap = C <= 16 ? 16 : 64;
+  r.stateBytes = (size_t) (n * n + n) * 16 * 64;
+  const bool lds = r.stateBytes <= 150 * 1024 && !getenv("DSR_RLS_MEMSTATE");
+  const bool regs = getenv("DSR_RLS_NOREGS") == nullptr && r.ct != 0;
+  r.residence = regs ? DSR_RLS_STATE_REGS : lds ? DSR_RLS_STATE_LDS : DSR_RLS_STATE_MEM;
+  r.ldsBytes = r.residence == DSR_RLS_STATE_LDS ? r.stateBytes : 0;
+  return r;
+}
 
 static void gsc_rls_apply(BfState& s, const float* X, const int32_t* nframes, int U, int Tmax, float* Y, double* waOut, hipStream_t st)
 {
@@ -277,8 +299,9 @@ static void gsc_rls_apply(BfState& s, const float* X, const int32_t* nframes, in
     s.d_wq.upload(a); s.d_B.upload(b); s.d_P0.upload(p); s.d_diag.upload(s.rlsDiag); s.rlsDirty = false;
   }
   const long S = (long) U * F;
-  const size_t ldsB = (size_t) (n * n + n) * 16 * 64; const int ldsState = (ldsB <= 150 * 1024 && !getenv("DSR_RLS_MEMSTATE")) ? 1 : 0;
-  const bool regs = getenv("DSR_RLS_NOREGS") == nullptr && (C == 8 || C == 6 || C == 4);     // precision matrix + active weights in registers (C = 8: 256 VGPRs, no scratch)
+  const RlsPath pa = rls_path(C);
+  const size_t ldsB = pa.stateBytes; const int ldsState = pa.residence == DSR_RLS_STATE_LDS ? 1 : 0;
+  const bool regs = pa.residence == DSR_RLS_STATE_REGS;        // precision matrix + active weights in registers (C = 8: 256 VGPRs, no scratch)
   // carried state: its own array (the register / LDS variants copy in and out; the memory variant works in it directly)
   int carryIn = 0, carryOut = 0; double2* carry = nullptr;
   if (s.rlsCarry) {
@@ -297,8 +320,12 @@ static void gsc_rls_apply(BfState& s, const float* X, const int32_t* nframes, in
 #define RLS_LAUNCH(CTV, CAPV) { if (ldsState) DSR_HIP(hipFuncSetAttribute((const void*) k_gsc_rls<CTV, false, CAPV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsB)); \
   hipLaunchKernelGGL((k_gsc_rls<CTV, false, CAPV>), dim3((unsigned) ((S + 63) / 64)), dim3(64), ldsState ? ldsB : 0, st, RLS_ARGS, ldsState, RLS_TAIL); }
 #define RLS_LAUNCH_REG(CTV) hipLaunchKernelGGL((k_gsc_rls<CTV, true, 16>), dim3((unsigned) ((S + 63) / 64)), dim3(64), 0, st, RLS_ARGS, 0, RLS_TAIL);
-  if (regs && C == 8) { RLS_LAUNCH_REG(8) } else if (regs && C == 6) { RLS_LAUNCH_REG(6) } else if (regs && C == 4) { RLS_LAUNCH_REG(4) }
-  else if (C == 8) RLS_LAUNCH(8, 16) else if (C == 4) RLS_LAUNCH(4, 16) else if (C == 6) RLS_LAUNCH(6, 16) else if (C <= 16) RLS_LAUNCH(0, 16) else RLS_LAUNCH(0, 64)
+  bool launched = false;
+#define RLS_CT_GO(CTV) if (!launched && pa.ct == CTV) { if (regs) { RLS_LAUNCH_REG(CTV) } else RLS_LAUNCH(CTV, 16) launched = true; }
+  RLS_CT_LIST(RLS_CT_GO)
+#undef RLS_CT_GO
+  if (!launched && pa.ct == 0) { if (pa.cap == 16) RLS_LAUNCH(0, 16) else RLS_LAUNCH(0, 64) launched = true; }
+  if (!launched) throw Error(DSR_E_ERROR, "SubbandGSCRLS: no kernel k_gsc_rls<%d, %d, %d>", pa.ct, regs ? 1 : 0, pa.cap);
 #undef RLS_LAUNCH_REG
 #undef RLS_LAUNCH
 #undef RLS_ARGS
@@ -474,7 +501,8 @@ dsr_status dsr_bf_get(const dsr_bf* cs, int kind, double* out, size_t nd)
 
 // the weights k_bf_apply would use, channel-major [C][M/2+2] on the device, for the fused analysis + beamformer kernel (k_filterbank.hip); null when the output is
 // not a fixed linear combination of the channels (SubbandGSCRLS adapting) or when all M bins are computed (halfBandShift)
-namespace dsr { const float2* bf_fixed_weights_dev(dsr_bf* s) { if (!s || s->rlsOn || s->halfBandShift) return nullptr; if (s->dirty) refresh_effective(*s); return s->d_wT.p; } }
+namespace dsr { bool bf_has_fixed_weights(const dsr_bf* s) { return s && !s->rlsOn && !s->halfBandShift; } }
+namespace dsr { const float2* bf_fixed_weights_dev(dsr_bf* s) { if (!bf_has_fixed_weights(s)) return nullptr; if (s->dirty) refresh_effective(*s); return s->d_wT.p; } }
 
 dsr_status dsr_bf_apply(dsr_bf* s, const float* X, int U, int Tmax, float* Y, void* stream)
 {
@@ -544,6 +572,16 @@ dsr_status dsr_bf_gsc_rls(dsr_bf* s, const float* X, const int32_t* nframes_dev,
     if (!s->rlsOn) throw Error(DSR_E_ERROR, "not a SubbandGSCRLS object: call dsr_bf_rls_config first");
     require_device();
     gsc_rls_apply(*s, X, nframes_dev, U, Tmax, Y, wa_out_dev, (hipStream_t) stream);
+  });
+}
+dsr_status dsr_bf_rls_path(int chanN, int path[3], int64_t lds[2])
+{
+  return guard([&] {
+    if (!path) throw Error(DSR_E_PARAMETER, "null argument");
+    if (chanN < 2 || chanN > 64) throw Error(DSR_E_DIMENSION, "SubbandGSCRLS: 2 to 64 channels (%d)", chanN);
+    const RlsPath r = rls_path(chanN);
+    path[0] = r.ct; path[1] = r.cap; path[2] = r.residence;
+    if (lds) { lds[0] = (int64_t) r.stateBytes; lds[1] = (int64_t) r.ldsBytes; }
   });
 }
 // dsr_bf_apply with per-utterance frame counts: rows t >= nframes[u] are zero; an adapting (RLS) object stops adapting there

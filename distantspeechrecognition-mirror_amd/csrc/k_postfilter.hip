@@ -119,10 +119,11 @@ __global__ __launch_bounds__(1024) void k_zel_recur(const double2* __restrict__ 
     }
   }
   s_a[k][lane] = a; s_br[k][lane] = br; s_bi[k][lane] = bi; s_bd[k][lane] = bd;
-  __syncthreads();
-  // ---- the state this stretch starts in: the stream's carried state through the maps of the stretches before
+  // ---- the state this stretch starts in: the stream's carried state through the maps of the stretches before.  The carried state is read BEFORE the barrier:
+  // the last wave writes it back below, and with an empty last stretch (Tmax <= 15 L: Tmax 1, 17, 33 ...) nothing else would order that write after these reads.
   double Sr = 0.0, Si = 0.0, D = 0.0;
   if (live && carryIn) { const double2 s0 = state[n]; Sr = s0.x; Si = s0.y; D = state[S + n].x; }
+  __syncthreads();
   for (int j = 0; j < k; j++) { const double aj = s_a[j][lane]; Sr = aj * Sr + s_br[j][lane]; Si = aj * Si + s_bi[j][lane]; D = aj * D + s_bd[j][lane]; }
   if (!live) return;
   const double scale = 2.0 / ((double) C - 1.0);
@@ -588,10 +589,29 @@ dsr_status dsr_zelinski_set_manifold(dsr_zelinski* p, int fbinX, const double* v
     memcpy(&p->h_wq[(size_t) fbinX * p->C * 2], vec, sizeof(double) * 2 * p->C); p->dirty = true;
   });
 }
-namespace dsr { const float2* bf_fixed_weights_dev(dsr_bf* s); }
+namespace dsr { const float2* bf_fixed_weights_dev(dsr_bf* s); bool bf_has_fixed_weights(const dsr_bf* s); }
+
+// The dispatch of the post-filters, in one place: the launches below switch on it and dsr_zelinski_path reports it.  PF_REG_LIST: the channel counts
+// k_zelinski_reg and k_mccowan are instantiated for with the densities in registers.  kind 0 Zelinski, 1 McCowan, 2 Lefkimmiatis; behindFixedBf: the call
+// is dsr_zelinski_apply_bf with a beamformer of fixed weights.  DSR_PF_SUM, DSR_PF_NOFUSE, DSR_PF_WAVE and DSR_PF_MEMSTATE (set to anything) are read on every call.
+#define PF_REG_LIST(DO) DO(2) DO(3) DO(4) DO(6) DO(8)
+struct PfPath { int cell, targ; };
+static PfPath pf_path(int kind, int C, bool behindFixedBf)
+{
+  bool inSet = false;
+#define PF_REG_IS(CC) if (C == CC) inSet = true;
+  PF_REG_LIST(PF_REG_IS)
+#undef PF_REG_IS
+  // Zelinski: the register kernel for the small arrays it is instantiated for, the two streaming kernels for every other size (and on request)
+  const bool zsum = kind == 0 && (!inSet || getenv("DSR_PF_SUM"));
+  if (zsum) return PfPath{ (behindFixedBf && !getenv("DSR_PF_NOFUSE")) ? DSR_PF_ZEL_SUM_BF : DSR_PF_ZEL_SUM, 0 };
+  if (C > 16 || getenv("DSR_PF_WAVE")) return PfPath{ DSR_PF_WAVE, kind };
+  if (kind >= 1) { const bool regsM = !getenv("DSR_PF_MEMSTATE") && inSet; return PfPath{ regsM ? DSR_PF_MCCOWAN_REG : DSR_PF_MCCOWAN_MEM, regsM ? C : 0 }; }
+  return PfPath{ DSR_PF_ZEL_REG, C };
+}
 // bfW: null -- Y is the beamformer's output; else the channel-major weights of the beamformer (pitch F + 1): the Zelinski streaming pass forms Y itself (into Yscr, or the
 // caller's array when it wants the beamformer's output too)
-static void zelinski_apply_impl(dsr_zelinski* p, const float* X, const float* Y, const float2* bfW, float* Ykeep, const int32_t* nframes_dev, int U, int Tmax, float* out, float* wp1, void* stream)
+static void zelinski_apply_impl(dsr_zelinski* p, const PfPath pa, const float* X, const float* Y, const float2* bfW, float* Ykeep, const int32_t* nframes_dev, int U, int Tmax, float* out, float* wp1, void* stream)
 {
   {
     if (U <= 0 || Tmax <= 0) return;
@@ -604,8 +624,8 @@ static void zelinski_apply_impl(dsr_zelinski* p, const float* X, const float* Y,
       p->wq.upload(w); p->wqT.upload(wt); p->dirty = false; p->dirtyL = true;
     }
     const size_t S = (size_t) U * F, NE = (size_t) C * (C + 1) / 2;
-    // Zelinski: the register kernel for the small arrays it is instantiated for, the two streaming kernels for every other size (and on request)
-    const bool zsum = p->kind == 0 && (!(C == 2 || C == 3 || C == 4 || C == 6 || C == 8) || getenv("DSR_PF_SUM"));
+    const bool zsum = pa.cell == DSR_PF_ZEL_SUM || pa.cell == DSR_PF_ZEL_SUM_BF;
+    if ((pa.cell == DSR_PF_ZEL_SUM_BF) != (bfW != nullptr)) throw Error(DSR_E_ERROR, "post-filter: the fused pass needs the beamformer's weights, and only it takes them");
     // carried state: densities [entry][U x F] + frames seen per stream (double buffered: a call reads one array and writes the other)
     int carryIn = 0, carryOut = 0; const int* seenIn = nullptr; int* seenOut = nullptr;
     if (p->carry) {
@@ -614,7 +634,7 @@ static void zelinski_apply_impl(dsr_zelinski* p, const float* X, const float* Y,
       carryIn = p->haveState ? 1 : 0; carryOut = 1;
       seenIn = p->haveState ? p->seen[p->seenCur].p : nullptr; seenOut = p->seen[p->seenCur ^ 1].p;
     }
-    const bool wave = !zsum && (C > 16 || getenv("DSR_PF_WAVE"));
+    const bool wave = pa.cell == DSR_PF_WAVE;
     if (wave) {
       if (!p->pairIJ.p) { std::vector<unsigned short> t; for (int i = 0; i < C - 1; i++) for (int j = i + 1; j < C; j++) t.push_back((unsigned short) (i | (j << 8))); p->pairIJ.upload(t); }
       if (!p->carry) p->state.reserve(16);
@@ -649,19 +669,26 @@ static void zelinski_apply_impl(dsr_zelinski* p, const float* X, const float* Y,
       if (p->kind == 0) PFW(0); else if (p->kind == 1) PFW(1); else PFW(2);
 #undef PFW
     } else if (p->kind >= 1) {
-      const bool regsM = !getenv("DSR_PF_MEMSTATE") && (C == 2 || C == 3 || C == 4 || C == 6 || C == 8);
+      const bool regsM = pa.cell == DSR_PF_MCCOWAN_REG;
       if (!p->carry) p->state.reserve(regsM ? 16 : S * NE);
       // (state in memory: the working array is the carried one, in place -- the recursions restart by themselves on a stream's first two frames)
 #define MC_LAUNCH(CTV) hipLaunchKernelGGL((k_mccowan<CTV>), dim3((unsigned) ((S + 127) / 128)), dim3(128), 0, st, (const float2*) X, (const float2*) Y, nframes_dev, p->wq.p, p->R.p, p->state.p, \
                          (float2*) out, wp1, U, C, Tmax, F, p->alpha, p->type, p->minFrames, p->threshold, p->kind == 2 ? p->lambda.p : nullptr, p->fbinX1, PF_TAIL);
-      if (!regsM) { MC_LAUNCH(0) } else if (C == 8) { MC_LAUNCH(8) } else if (C == 6) { MC_LAUNCH(6) } else if (C == 4) { MC_LAUNCH(4) } else if (C == 3) { MC_LAUNCH(3) } else { MC_LAUNCH(2) }
+      bool launched = false;
+      if (pa.targ == 0) { MC_LAUNCH(0) launched = true; }
+#define PF_REG_GO(CC) if (!launched && pa.targ == CC) { MC_LAUNCH(CC) launched = true; }
+      PF_REG_LIST(PF_REG_GO)
+#undef PF_REG_GO
 #undef MC_LAUNCH
+      if (!launched) throw Error(DSR_E_ERROR, "post-filter: no kernel k_mccowan<%d>", pa.targ);
     } else {
       if (!p->carry) p->state.reserve(16);
-#define ZREG(CC) if (C == CC) hipLaunchKernelGGL(k_zelinski_reg<CC>, dim3((unsigned) ((S + 63) / 64)), dim3(64), 0, st, (const float2*) X, (const float2*) Y, \
-      nframes_dev, p->wq.p, (float2*) out, wp1, U, Tmax, F, p->alpha, p->type, p->minFrames, seenIn, seenOut, p->state.p, carryIn, carryOut);
-      ZREG(2) ZREG(3) ZREG(4) ZREG(6) ZREG(8)
+      bool launched = false;
+#define ZREG(CC) if (!launched && pa.targ == CC) { hipLaunchKernelGGL(k_zelinski_reg<CC>, dim3((unsigned) ((S + 63) / 64)), dim3(64), 0, st, (const float2*) X, (const float2*) Y, \
+      nframes_dev, p->wq.p, (float2*) out, wp1, U, Tmax, F, p->alpha, p->type, p->minFrames, seenIn, seenOut, p->state.p, carryIn, carryOut); launched = true; }
+      PF_REG_LIST(ZREG)
 #undef ZREG
+      if (!launched) throw Error(DSR_E_ERROR, "post-filter: no kernel k_zelinski_reg<%d>", pa.targ);
     }
 #undef PF_TAIL
     DSR_HIP(hipGetLastError());
@@ -672,7 +699,17 @@ dsr_status dsr_zelinski_apply(dsr_zelinski* p, const float* X, const float* Y, c
 {
   return guard([&] {
     if (!p || !X || !Y || !nframes_dev || !out) throw Error(DSR_E_PARAMETER, "null argument");
-    zelinski_apply_impl(p, X, Y, nullptr, nullptr, nframes_dev, U, Tmax, out, wp1, stream);
+    zelinski_apply_impl(p, pf_path(p->kind, p->C, false), X, Y, nullptr, nullptr, nframes_dev, U, Tmax, out, wp1, stream);
+  });
+}
+dsr_status dsr_zelinski_path(int kind, int chanN, const dsr_bf* bf, int path[2])
+{
+  return guard([&] {
+    if (!path) throw Error(DSR_E_PARAMETER, "null argument");
+    if (kind < 0 || kind > 2) throw Error(DSR_E_PARAMETER, "kind %d: 0 Zelinski, 1 McCowan, 2 Lefkimmiatis", kind);
+    if (chanN <= 1 || chanN > 64) throw Error(DSR_E_DIMENSION, "post-filter kernels: 2 to 64 channels (%d)", chanN);
+    const PfPath r = pf_path(kind, chanN, bf_has_fixed_weights(bf));
+    path[0] = r.cell; path[1] = r.targ;
   });
 }
 // The post-filter behind its beamformer (ZelinskiPostFilter::setBeamformer, postfilter.cc:376-384: the filter takes snapshots and array manifold from the beamformer
@@ -684,13 +721,12 @@ dsr_status dsr_zelinski_apply_bf(dsr_zelinski* p, dsr_bf* bf, const float* X, co
     if (!p || !bf || !X || !nframes_dev || !out) throw Error(DSR_E_PARAMETER, "null argument");
     if (U <= 0 || Tmax <= 0) return;
     const int F = p->M / 2 + 1, C = p->C;
-    const bool zsum = p->kind == 0 && (!(C == 2 || C == 3 || C == 4 || C == 6 || C == 8) || getenv("DSR_PF_SUM"));
-    const float2* w = (zsum && !getenv("DSR_PF_NOFUSE")) ? bf_fixed_weights_dev(bf) : nullptr;
-    if (w) { zelinski_apply_impl(p, X, nullptr, w, Y_dev, nframes_dev, U, Tmax, out, wp1, stream); return; }
+    PfPath pa = pf_path(p->kind, C, bf_has_fixed_weights(bf));
+    if (pa.cell == DSR_PF_ZEL_SUM_BF) { zelinski_apply_impl(p, pa, X, nullptr, bf_fixed_weights_dev(bf), Y_dev, nframes_dev, U, Tmax, out, wp1, stream); return; }
     float* Y = Y_dev;
     if (!Y) { ZelinskiPlan::PE& pe = p->pe.at((hipStream_t) stream); pe.Y.reserve((size_t) U * Tmax * F); Y = (float*) pe.Y.p; }
     { const dsr_status rc = dsr_bf_apply_frames(bf, X, nframes_dev, U, Tmax, Y, stream); if (rc != DSR_OK) throw Error(rc, "%s", dsr_last_error()); }
-    zelinski_apply_impl(p, X, Y, nullptr, nullptr, nframes_dev, U, Tmax, out, wp1, stream);
+    zelinski_apply_impl(p, pa, X, Y, nullptr, nullptr, nframes_dev, U, Tmax, out, wp1, stream);
   });
 }
 // Carried densities (block streaming): carry = 1 makes every apply of the same U continue the recursions of the call before it (stream u of one call

@@ -358,6 +358,10 @@ class Beamformer:
     def rlsResetState(self):
         check(_lib.dsr_bf_rls_reset_state(self.h))
 
+    def rls_path(self):
+        """bf_rls_path(chanN) of this object: the kernel gsc_rls launches and where its adaptation state lives"""
+        return bf_rls_path(self.C)
+
     def bins(self):
         """bins per frame of apply(): fftLen/2+1, or fftLen with halfBandShift"""
         return _lib.dsr_bf_bins(self.h)
@@ -1168,7 +1172,30 @@ class PlaneWaveSim:
         return out
 
 
+RLS_STATE_REGS, RLS_STATE_LDS, RLS_STATE_MEM = 0, 1, 2
+PF_ZEL_REG, PF_ZEL_SUM, PF_ZEL_SUM_BF, PF_MCCOWAN_REG, PF_MCCOWAN_MEM, PF_WAVE = 0, 1, 2, 3, 4, 5
+
+
+def bf_rls_path(chanN):
+    """-> ((CT, CAP, residence), (bytes of the 64 lanes' state, dynamic LDS of the launch)): the k_gsc_rls<CT, REG, CAP> dsr_bf_gsc_rls launches for
+    chanN channels, REG = residence == RLS_STATE_REGS; follows DSR_RLS_NOREGS / DSR_RLS_MEMSTATE; needs no device"""
+    L = load()
+    out = (C.c_int * 3)(); lds = (C.c_int64 * 2)()
+    check(L.dsr_bf_rls_path(int(chanN), out, lds))
+    return tuple(out), tuple(lds)
+
+
+def zelinski_path(kind, chanN, bf=None):
+    """-> (cell, template argument): the kernels a post-filter of that kind (0 Zelinski, 1 McCowan, 2 Lefkimmiatis) launches, behind the beamformer bf
+    (apply_bf) or on its own (apply); PF_*; follows DSR_PF_SUM / DSR_PF_NOFUSE / DSR_PF_WAVE / DSR_PF_MEMSTATE; needs no device"""
+    L = load()
+    out = (C.c_int * 2)()
+    check(L.dsr_zelinski_path(int(kind), int(chanN), bf.h if bf is not None else None, out))
+    return tuple(out)
+
+
 class ZelinskiPostFilter:
+    kind = 0
     """Zelinski post-filter (postfilter.cc:8-221,350-493); manifold [M/2+1][C] complex = arrayManifold() (or wq() with type | 8)."""
 
     def __init__(self, fftLen, chanN, manifold, alpha=0.6, type=2, minFrames=0):
@@ -1214,6 +1241,10 @@ class ZelinskiPostFilter:
 
     def resetState(self):
         check(_lib.dsr_zelinski_reset_state(self.h))
+
+    def path(self, bf=None):
+        """zelinski_path of this filter: what apply (bf None) / apply_bf(bf) launches"""
+        return zelinski_path(self.kind, self.C, bf)
 
 
 def _nf(nframes):
@@ -1499,6 +1530,7 @@ class SubbandMMI:
 
 class McCowanPostFilter(ZelinskiPostFilter):
     """McCowan post-filter (postfilter.cc:502-945): Zelinski's recursions + a noise coherence matrix per bin."""
+    kind = 1
 
     def __init__(self, fftLen, chanN, manifold, alpha=0.6, type=2, minFrames=0, threshold=0.99):
         L = load(); self.h = vp(); self.M, self.C = fftLen, chanN
@@ -1526,6 +1558,7 @@ class McCowanPostFilter(ZelinskiPostFilter):
 class LefkimmiatisPostFilter(McCowanPostFilter):
     """Lefkimmiatis post-filter (postfilter.cc:948-1210): McCowan's clean-signal estimate against the coherence-based noise estimate,
     divided by d^H pinv(R) d from bin fbinX1 on."""
+    kind = 2
 
     def __init__(self, fftLen, chanN, manifold, minSV=1e-8, fbinX1=0, alpha=0.6, type=2, minFrames=0, threshold=0.99):
         L = load(); self.h = vp(); self.M, self.C = fftLen, chanN

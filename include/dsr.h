@@ -183,6 +183,16 @@ dsr_status dsr_bf_gsc_rls(dsr_bf*, const float* X_dev, const int32_t* nframes_de
  * precision-matrix setters) make the next call start from P0 and zero weights again.  carry = 0 (default): every call starts afresh. */
 dsr_status dsr_bf_rls_carry(dsr_bf*, int on);
 dsr_status dsr_bf_rls_reset_state(dsr_bf*);
+/* Which k_gsc_rls<CT, REG, CAP> dsr_bf_gsc_rls launches for chanN channels and where the adaptation state (precision matrix + active weights,
+ * (n^2 + n) complex128 per (utterance, bin), n = chanN - 1) lives: path[0] = CT, the compile-time channel count (4, 6, 8; 0: run-time count),
+ * path[1] = CAP, the capacity of a thread's vectors (16; 64 above 16 channels), path[2] = the residence.  lds (optional): lds[0] the bytes the 64
+ * lanes' state takes, which the 150 KB gate compares (chanN <= 12 fits); lds[1] the dynamic LDS of the launch (lds[0] with the state in LDS, else 0).
+ * The launch takes its decisions from the same helper.  The carried state (dsr_bf_rls_carry) has one layout whatever the residence.  The switches
+ * DSR_RLS_NOREGS (no register residence) and DSR_RLS_MEMSTATE (no LDS residence), set to anything, are read on every call.  Needs no device. */
+enum { DSR_RLS_STATE_REGS = 0,         /* k_gsc_rls<C, true, 16>: chanN 4, 6, 8 */
+       DSR_RLS_STATE_LDS = 1,          /* k_gsc_rls<CT, false, 16> with dynamic LDS */
+       DSR_RLS_STATE_MEM = 2 };        /* k_gsc_rls<CT, false, CAP> working in the state array, in place */
+dsr_status dsr_bf_rls_path(int chanN, int path[3], int64_t lds[2]);
 /* which weight set `apply` uses: 0 = delay-and-sum wq, 1 = MVDR, 2 = GSC (wq - B wa), 3 = GSC normalised, 4 = MVDR-GSC (w_mvdr - wl) */
 dsr_status dsr_bf_select(dsr_bf*, int mode);
 /* read back host copies: kind 0 = wq [fftLen][C], 1 = mvdr [fftLen/2+1][C], 2 = R [fftLen/2+1][C][C],
@@ -1110,6 +1120,19 @@ dsr_status dsr_zelinski_apply(dsr_zelinski*, const float* X_dev, const float* Y_
  * dsr_zelinski_apply.  Y_dev (optional, [U][Tmax][fftLen/2+1] complex64) receives bf(X). */
 dsr_status dsr_zelinski_apply_bf(dsr_zelinski*, dsr_bf*, const float* X_dev, const int32_t* nframes_dev, int U, int Tmax,
                                  float* out_dev, float* wp1_dev, float* Y_dev, void* stream);
+/* Which kernels dsr_zelinski_apply (bf null) / dsr_zelinski_apply_bf (the beamformer the filter sits behind) launch for a filter of that kind
+ * (0 Zelinski, 1 McCowan, 2 Lefkimmiatis) and channel count: path[0] = the cell, path[1] = the kernel's template argument (the channel count of
+ * the register kernels, 0 for k_mccowan<0>, the kind for k_pf_wave, 0 for the sum kernels).  The launches take their decisions from the same helper.
+ * The switches DSR_PF_SUM (Zelinski: the sum kernels at any size), DSR_PF_NOFUSE (no beamformer sum in the filter's pass), DSR_PF_WAVE (the
+ * wave-per-bin kernel at any size) and DSR_PF_MEMSTATE (McCowan / Lefkimmiatis: densities in memory), set to anything, are read on every call.
+ * Needs no device. */
+enum { DSR_PF_ZEL_REG = 0,             /* k_zelinski_reg<C>: Zelinski, chanN 2, 3, 4, 6, 8 */
+       DSR_PF_ZEL_SUM = 1,             /* k_zel_pairs<false> + k_zel_recur: Zelinski at every other size */
+       DSR_PF_ZEL_SUM_BF = 2,          /* k_zel_pairs<true> + k_zel_recur: the same behind a beamformer of fixed weights, its sum formed in the same pass */
+       DSR_PF_MCCOWAN_REG = 3,         /* k_mccowan<C>: McCowan / Lefkimmiatis, chanN 2, 3, 4, 6, 8 */
+       DSR_PF_MCCOWAN_MEM = 4,         /* k_mccowan<0>: the same for any other chanN <= 16 */
+       DSR_PF_WAVE = 5 };              /* k_pf_wave<kind>: chanN > 16 (Zelinski only on request: above 16 channels it takes the sum kernels) */
+dsr_status dsr_zelinski_path(int kind, int chanN, const dsr_bf* bf, int path[2]);
 /* Carried densities for block-wise processing of long streams (BASELINE configs[4]).  The reference operator's auto/cross spectral densities
  * (postfilter.cc:428-497) live as long as the object: carry = 1 makes every apply of the same U continue the recursions where the previous call
  * stopped (stream u of one call = stream u of the next; the start-up alpha = 0 and minFrames count from a stream's own first frame);

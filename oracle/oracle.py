@@ -400,7 +400,9 @@ def pf_diffuse_noise_model(micpos, M, fs, sspeed=343740.0):
 
 
 def mccowan_postfilter(X, Y, wq, R, alpha=0.6, type=2, minFrames=0, threshold=0.99):
-    """McCowanPostFilter (postfilter.cc:568-945): X [C][T][F], Y [T][F], wq [F][C], R [F][C][C] -> (out, wp1)."""
+    """McCowanPostFilter (postfilter.cc:568-945): X [C][T][F], Y [T][F], wq [F][C], R [F][C][C] -> (out, wp1).
+    threshold is taken as given.  The reference keeps _thresholdOfRij as a float (postfilter.h:163) and a clipped pair divides by 1 - threshold:
+    pass float(np.float32(0.99)) for the reference's 0.99 -- 0.99 as a double moves the weights by 1e-6 relative wherever pairs are clipped."""
     X = np.ascontiguousarray(X, np.complex128); Y = np.ascontiguousarray(Y, np.complex128); wq = np.ascontiguousarray(wq, np.complex128)
     R = np.ascontiguousarray(R, np.complex128)
     Cn, T, F = X.shape

@@ -142,7 +142,9 @@ def test_blockwise_filterbanks_other_designs(dsr, oracle, cuda, M, m, r, name):
 
 @pytest.mark.parametrize("kind,Cn", [("zelinski", 64), ("mccowan", 64), ("lefkimmiatis", 64), ("zelinski", 20), ("mccowan", 33)])
 def test_large_array_postfilters(dsr, oracle, cuda, kind, Cn):
-    """the wave-per-bin post-filter kernel (16 < C <= 64) against the oracle, one shot and in two blocks with carried densities"""
+    """the wave-per-bin post-filter kernel (16 < C <= 64) against the oracle, one shot and in two blocks with carried densities
+    (the input s conj(wq_c) C + noise is incoherent after the filter's time alignment conj(d_c) x_c, not a source from the look direction:
+    tests/test_gpu_postfilter_kernels.py has the aligned input)"""
     import torch
     rng = np.random.default_rng(300 + Cn)
     U, T, M = 2, 30, 32

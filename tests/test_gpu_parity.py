@@ -901,7 +901,10 @@ def test_pr_fft_banks(dsr, oracle, cuda, headset, M, m, r):
 @pytest.mark.parametrize("Cn,ptype,alpha,minFrames", [(8, 2, 0.6, 0), (8, 1, 0.6, 3), (4, 10, 0.9, 0), (2, 2, 0.0, 0), (13, 1, 0.5, 1)])
 def test_zelinski_postfilter(dsr, oracle, cuda, Cn, ptype, alpha, minFrames):
     """postfilter.cc:8-221,428-493: fp64 recursions of the auto/cross spectral densities in the reference's order, one thread per
-    (utterance, bin).  Weights agree to 1e-6 relative (they leave as fp32), the filtered output to 1e-6 of its magnitude."""
+    (utterance, bin).  Weights agree to 1e-6 relative (they leave as fp32), the filtered output to 1e-6 of its magnitude.
+    The input s conj(wq_c) C + noise is NOT a source from the look direction: the filter time-aligns with conj(d_c) x_c (postfilter.cc:30-43), so s arrives as
+    s conj(wq_c)^2 C, incoherent across the channels, and the weight sits on or near its floor.  This and the other post-filter tests of this file keep that input;
+    tests/test_gpu_postfilter_kernels.py feeds aligned input (X_c = s d_c C + noise), which moves the weight through its whole range."""
     import torch
     rng = np.random.default_rng(5 + Cn)
     U, T, M = 3, 40, 64

@@ -13,16 +13,10 @@
 //                 walks the frames with three barriers each; the covariances stay in the caller's state between frames.
 // The covariance update is the rank-1 form K = K- - s s^H / sigma2_s with s = K- conj(v): K stays exactly Hermitian (s_i conj(s_j) and
 // s_j conj(s_i) are exact conjugates without FMA contraction), so v^T K- = s^H needs no second reduction.
-#include "common.h"
+// The two information filters of the same directory are k_aec_info.hip; the C entries at the end of this file hand their kinds on (aec.h).
+#include "aec.h"
 
 using namespace dsr;
-
-struct dsr_aec {
-  int kind, M, L, frameMode = 0;
-  double delta = 100.0, epsilon = 1.0e-4, threshold = 100.0;                       // cancelVP.i:80-81
-  double beta = 0.95, sigma2 = 5.0, sigmau2 = 10e-4, sigmak2 = 5.0, amp = 1.0;     // cancelVP.i:108-109, :140-143
-  double engTh = 100.0, smooth = 0.9;                                              // cancelVP.i:241-244 (snrTh is `threshold`, cancelVP.cc:1061)
-};
 
 namespace {
 
@@ -362,7 +356,7 @@ dsr_status dsr_aec_set_block(dsr_aec* a, double beta, double sigmau2, double sig
 {
   return guard([&] {
     if (!a) throw Error(DSR_E_PARAMETER, "null argument");
-    if (a->kind != DSR_AEC_BLOCK && a->kind != DSR_AEC_DTD) throw Error(DSR_E_PARAMETER, "not a block Kalman echo canceller");
+    if (a->kind != DSR_AEC_BLOCK && a->kind != DSR_AEC_DTD && !aec_info::is_info(*a)) throw Error(DSR_E_PARAMETER, "not a block Kalman echo canceller");
     check_beta(beta); a->beta = beta; a->sigmau2 = sigmau2; a->sigmak2 = sigmak2; a->amp = amp4play;
     if (a->kind == DSR_AEC_BLOCK) a->threshold = threshold;                        // DTD: the threshold is snrTh (cancelVP.cc:1061), see dsr_aec_set_dtd
   });
@@ -384,13 +378,15 @@ dsr_status dsr_aec_set_frame_mode(dsr_aec* a, int mode)
   });
 }
 
-size_t dsr_aec_state_bytes(const dsr_aec* a, int U) { return (a && U > 0) ? layout(*a, U).bytes : 0; }
+size_t dsr_aec_state_bytes(const dsr_aec* a, int U) { return (a && U > 0) ? (aec_info::is_info(*a) ? aec_info::state_bytes(*a, U) : layout(*a, U).bytes) : 0; }
 
 dsr_status dsr_aec_state_init(const dsr_aec* a, void* state_dev, int U, void* stream)
 {
   return guard([&] {
     if (!a || !state_dev || U < 1) throw Error(DSR_E_PARAMETER, "null argument");
-    require_device(); init_state(*a, state_dev, U, (hipStream_t) stream);
+    require_device();
+    if (aec_info::is_info(*a)) aec_info::init_state(*a, state_dev, U, (hipStream_t) stream);
+    else init_state(*a, state_dev, U, (hipStream_t) stream);
   });
 }
 
@@ -414,6 +410,10 @@ dsr_status dsr_aec_apply(const dsr_aec* a, const float* played_dev, const float*
     require_device();
     if (Tmax == 0) return;
     hipStream_t st = (hipStream_t) stream;
+    if (aec_info::is_info(*a)) {
+      aec_info::apply(*a, (const float2*) played_dev, (const float2*) recorded_dev, nframes_dev, U, Tmax, frame0, (float2*) out_dev, state_dev, st);
+      return;
+    }
     void* state = state_dev;
     if (!state) { Scratch& sc = g_scratch.at(st); sc.st.reserve(layout(*a, U).bytes); state = sc.st.p; init_state(*a, state, U, st); }
     const St s = carve(*a, state, U);
@@ -439,6 +439,7 @@ dsr_status dsr_aec_state_read(const dsr_aec* a, const void* state_dev, int U, in
 {
   return guard([&] {
     if (!a || !state_dev || !host_out || U < 1) throw Error(DSR_E_PARAMETER, "null argument");
+    if (aec_info::is_info(*a)) { aec_info::read(*a, state_dev, U, what, host_out, outDoubles); return; }
     const Layout l = layout(*a, U); const size_t n = (size_t) U * (a->M / 2 + 1), L = (size_t) a->L;
     size_t off, doubles;
     switch (what) {

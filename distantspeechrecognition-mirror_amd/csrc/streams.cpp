@@ -592,7 +592,7 @@ struct WpeMultiOp : dsr_stream {     // MultiChannelWPEDereverberationFeature(so
     op_expand_bins(O.p + (size_t) channelX * T * F, T, F, M, d<double2>(), S0);
   }
 };
-struct AecOp : dsr_stream {          // the echo cancellers of btk/cancelVP as a stream (cancelVP.cc:57-104, :141-209, :287-383, :1121-1198): ups = played, recorded
+struct AecOp : dsr_stream {          // the echo cancellers of btk/cancelVP as a stream (cancelVP.cc:57-104, :141-209, :287-383, :513-650, :748-855, :1121-1198): ups = played, recorded
   dsr_aec* aec = nullptr; int M = 0, frameMode = 0; DevBuf<float2> P, Rc, O; DevBuf<int> nf; DevBuf<unsigned char> state; bool haveState = false;
   void ensure_state() {
     if (haveState) return;
@@ -610,7 +610,7 @@ struct AecOp : dsr_stream {          // the echo cancellers of btk/cancelVP as a
     ensure_state();
     const int F = M / 2 + 1; P.reserve((size_t) T * F); Rc.reserve((size_t) T * F); O.reserve((size_t) T * F);
     op_pack_bins(ups[0]->d<double2>(), T, F, M, P.p, S0); op_pack_bins(ups[1]->d<double2>(), T, F, M, Rc.p, S0); nf.upload(&T, 1);
-    ok(dsr_aec_set_frame_mode(aec, dsr_aec_kind(aec) == DSR_AEC_DTD ? frameMode : 0));
+    ok(dsr_aec_set_frame_mode(aec, dsr_aec_kind(aec) >= DSR_AEC_DTD ? frameMode : 0));      // DTD and the information kinds: _updateBand reads frameX
     ok(dsr_aec_apply(aec, (const float*) P.p, (const float*) Rc.p, nf.p, 1, T, 0, (float*) O.p, state.p, S0));
     op_expand_bins(O.p, T, F, M, d<double2>(), S0);
   }
@@ -1133,7 +1133,8 @@ dsr_status dsr_aec_stream_get(dsr_stream* s, int what, double* out, size_t outDo
     AecOp* q = dynamic_cast<AecOp*>(s); if (!q || !out) throw Error(DSR_E_PARAMETER, "not an echo cancellation stream");
     require_device(); q->ensure_state();
     const size_t F = (size_t) q->M / 2 + 1, L = (size_t) dsr_aec_sample_n(q->aec);
-    const size_t cnt = what == DSR_AEC_STATE_K ? F * L * L * 2 : what == DSR_AEC_STATE_SIGMA2V ? F : what == DSR_AEC_STATE_DTD ? 3 : F * L * 2;
+    const size_t cnt = what == DSR_AEC_STATE_K ? F * L * L * 2 : what == DSR_AEC_STATE_SIGMA2V ? F : what == DSR_AEC_STATE_DTD ? 3 : what == DSR_AEC_STATE_BAND ? F * 3 :
+                       (what == DSR_AEC_STATE_SKIPPED || what == DSR_AEC_STATE_RESETS) ? 1 : F * L * 2;
     ok(dsr_aec_state_read(q->aec, q->state.p, 1, what, out, outDoubles));
     if (n) *n = cnt;
   });

@@ -488,16 +488,20 @@ def wpe_multi(Y, fftLen, lowerN, upperN, iterationsN=2, loadDb=-20.0, bandWidth=
 
 
 class Aec:
-    """Subband echo cancellers of btk/cancelVP (include/dsr.h section 2d): kind "nlms", "kalman", "block" or "dtd".  The handle holds the
+    """Subband echo cancellers of btk/cancelVP (include/dsr.h section 2d): kind "nlms", "kalman", "block", "dtd", "info" (the information filter)
+    or "sqrtinfo" (its square-root form).  The handle holds the
     parameters (SWIG defaults of cancelVP.i unless given); the adaptive state is a device buffer of the caller (newState) that apply()
     continues from and leaves behind.  played, recorded: cuda complex64 [U][T][M/2+1]."""
-    KINDS = {"nlms": 0, "kalman": 1, "block": 2, "dtd": 3}
-    FILTER, K, SIGMA2V, DTD, HISTORY = 0, 1, 2, 3, 4
+    KINDS = {"nlms": 0, "kalman": 1, "block": 2, "dtd": 3, "info": 8, "sqrtinfo": 9}
+    FILTER, K, SIGMA2V, DTD, HISTORY, BAND, INFO, SKIPPED, RESETS = 0, 1, 2, 3, 4, 5, 6, 7, 8
 
     def __init__(self, kind, fftLen, sampleN=1, delta=100.0, epsilon=1.0e-4, threshold=100.0, beta=0.95, sigma2=5.0, sigmau2=10e-4, sigmak2=5.0,
-                 amp4play=1.0, snrTh=2.0, engTh=100.0, smooth=0.9, frameMode=0):
+                 amp4play=1.0, snrTh=2.0, engTh=100.0, smooth=0.9, frameMode=0, loading=1.0e-2):
         L = load(); self.h = vp(); self.kind = self.KINDS[kind] if isinstance(kind, str) else int(kind); self.M = int(fftLen)
-        check(L.dsr_aec_create(self.kind, int(fftLen), int(sampleN), C.byref(self.h)))
+        if self.kind in (8, 9):
+            check(L.dsr_aec_create_info(int(self.kind == 9), int(fftLen), int(sampleN), C.byref(self.h)))
+        else:
+            check(L.dsr_aec_create(self.kind, int(fftLen), int(sampleN), C.byref(self.h)))
         self.L = L.dsr_aec_sample_n(self.h); self.F = self.M // 2 + 1
         if self.kind == 0:
             check(L.dsr_aec_set_nlms(self.h, float(delta), float(epsilon), float(threshold)))
@@ -507,6 +511,9 @@ class Aec:
             check(L.dsr_aec_set_block(self.h, float(beta), float(sigmau2), float(sigmak2), float(threshold), float(amp4play)))
         if self.kind == 3:
             check(L.dsr_aec_set_dtd(self.h, float(snrTh), float(engTh), float(smooth)))
+            check(L.dsr_aec_set_frame_mode(self.h, int(frameMode)))
+        if self.kind in (8, 9):
+            check(L.dsr_aec_set_info(self.h, float(snrTh), float(engTh), float(smooth), float(loading)))
             check(L.dsr_aec_set_frame_mode(self.h, int(frameMode)))
 
     def __del__(self):
@@ -538,9 +545,10 @@ class Aec:
 
     def read(self, state, U, what):
         F, L = self.F, self.L
-        shape = {0: (U, F, L), 1: (U, F, L, L), 2: (U, F), 3: (U, 3), 4: (U, F, L)}[what]
-        out = np.zeros(shape, np.float64 if what in (2, 3) else np.complex128)
-        check(_lib.dsr_aec_state_read(self.h, _dev(state), int(U), int(what), _ptr(out), out.size * (1 if what in (2, 3) else 2)))
+        shape = {0: (U, F, L), 1: (U, F, L, L), 2: (U, F), 3: (U, 3), 4: (U, F, L), 5: (U, F, 3), 6: (U, F, L), 7: (U,), 8: (U,)}[what]
+        real = what in (2, 3, 5, 7, 8)
+        out = np.zeros(shape, np.float64 if real else np.complex128)
+        check(_lib.dsr_aec_state_read(self.h, _dev(state), int(U), int(what), _ptr(out), out.size * (1 if real else 2)))
         return out
 
     def resetFilter(self, state, U):

@@ -1,9 +1,11 @@
 """btk.cancelVP: NLMSAcousticEchoCancellationFeaturePtr, KalmanFilterEchoCancellationFeaturePtr, BlockKalmanFilterEchoCancellationFeaturePtr,
-DTDBlockKalmanFilterEchoCancellationFeaturePtr (cancelVP.i:62-254) -- constructor signatures and defaults of the SWIG interface.
+InformationFilterEchoCancellationFeaturePtr, SquareRootInformationFilterEchoCancellationFeaturePtr, DTDBlockKalmanFilterEchoCancellationFeaturePtr
+(cancelVP.i:62-254) -- constructor signatures, defaults and inheritance of the SWIG interface.
 
 As in the reference the adaptive state outlives reset(): NLMS and Kalman zero their filter coefficients (cancelVP.h:60, :98), the block variants
-keep filter, covariance and played history (:134-142), DTD also its three smoothed scalars.  InformationFilterEchoCancellationFeaturePtr and
-SquareRootInformationFilterEchoCancellationFeaturePtr are not provided."""
+keep filter, covariance and played history (:134-142), DTD also its three smoothed scalars, the information filters their per-bin scalars, the
+plain one its count of skipped (frame, bin) pairs, the square-root one its information state.  The reference fixes the information filter's
+diagonal load at the first call in the process (a function-static, cancelVP.cc:610); here every object uses its own `loading`."""
 import numpy as np
 
 from .. import _capi as K
@@ -52,6 +54,38 @@ class BlockKalmanFilterEchoCancellationFeaturePtr(KalmanFilterEchoCancellationFe
 
     def covariance(self):
         return self._get(K.Aec.K, (self._aec.F, self._aec.L, self._aec.L), np.complex128)
+
+
+class InformationFilterEchoCancellationFeaturePtr(BlockKalmanFilterEchoCancellationFeaturePtr):
+    _KIND = "info"
+
+    def __init__(self, played, recorded, sampleN=1, beta=0.95, sigmau2=10e-4, sigmak2=5.0, snrTh=2.0, engTh=100.0, smooth=0.9, loading=1.0e-02, amp4play=1.0,
+                 nm="DTDBlockKFEchoCanceller"):
+        self._make(K.Aec(self._KIND, played.size(), sampleN, beta=beta, sigmau2=sigmau2, sigmak2=sigmak2, amp4play=amp4play, snrTh=snrTh, engTh=engTh,
+                         smooth=smooth, loading=loading), played, recorded, nm)
+
+    def bandScalars(self):
+        """[fftLen/2+1][3]: _EkEnergy, _SkEnergy, _snr of every bin"""
+        return self._get(K.Aec.BAND, (self._aec.F, 3), np.float64)
+
+    def skippedN(self):
+        """_skippedN, and how often the reset rule fired (cancelVP.cc:550-560)"""
+        return int(self._get(K.Aec.SKIPPED, (1,), np.float64)[0]), int(self._get(K.Aec.RESETS, (1,), np.float64)[0])
+
+
+class SquareRootInformationFilterEchoCancellationFeaturePtr(InformationFilterEchoCancellationFeaturePtr):
+    """covariance() is the inverse Cholesky factor the reference keeps in _K_k (lower triangular)."""
+    _KIND = "sqrtinfo"
+
+    def __init__(self, played, recorded, sampleN=1, beta=0.95, sigmau2=10e-4, sigmak2=5.0, snrTh=2.0, engTh=100.0, smooth=0.9, loading=1.0e-02, amp4play=1.0,
+                 nm="Square Root Information Filter Echo Cancellation Feature"):
+        InformationFilterEchoCancellationFeaturePtr.__init__(self, played, recorded, sampleN, beta, sigmau2, sigmak2, snrTh, engTh, smooth, loading, amp4play, nm)
+
+    def informationState(self):
+        return self._get(K.Aec.INFO, (self._aec.F, self._aec.L), np.complex128)
+
+    def skippedN(self):
+        raise AttributeError("the square-root information filter does not count skipped frames (cancelVP.cc:781)")
 
 
 class DTDBlockKalmanFilterEchoCancellationFeaturePtr(BlockKalmanFilterEchoCancellationFeaturePtr):

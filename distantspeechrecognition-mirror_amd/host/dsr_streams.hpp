@@ -739,6 +739,43 @@ class MultiChannelWPEDereverberationFeature : public VectorComplexFeatureStream 
  private: MultiChannelWPEDereverberationPtr _source; int _channelX;
 };
 
+// ---- btk/cancelVP/cancelVP.h:264-339, defaults of cancelVP.i:161-165, :195-199.  The adaptive state outlives reset() (cancelVP.h:134-142).
+// In the reference the base is BlockKalmanFilterEchoCancellationFeature, which this header does not carry.
+class InformationFilterEchoCancellationFeature : public VectorComplexFeatureStream {
+ public:
+  InformationFilterEchoCancellationFeature(const VectorComplexFeatureStreamPtr& played, const VectorComplexFeatureStreamPtr& recorded, unsigned sampleN = 1,
+                                           double beta = 0.95, double sigmau2 = 10e-4, double sigmak2 = 5.0, double snrTh = 2.0, double engTh = 100.0, double smooth = 0.9,
+                                           double loading = 1.0e-02, double amp4play = 1.0, const String& nm = "DTDBlockKFEchoCanceller")
+  : _aec(0), _played(played), _recorded(recorded) { create(0, sampleN, beta, sigmau2, sigmak2, snrTh, engTh, smooth, loading, amp4play, nm); }
+  ~InformationFilterEchoCancellationFeature() { if (_h) { dsr_stream_release(_h); _h = 0; } if (_aec) dsr_aec_destroy(_aec); }
+  // [fftLen/2+1][sampleN] complex
+  std::vector<std::complex<double> > filterCoefficients() {
+    std::vector<std::complex<double> > r((size_t) (size() / 2 + 1) * dsr_aec_sample_n(_aec)); size_t n = 0;
+    dsr_throw(dsr_aec_stream_get(_h, DSR_AEC_STATE_FILTER, (double*) r.data(), r.size() * 2, &n)); return r;
+  }
+ protected:
+  InformationFilterEchoCancellationFeature(const VectorComplexFeatureStreamPtr& played, const VectorComplexFeatureStreamPtr& recorded, int)
+  : _aec(0), _played(played), _recorded(recorded) {}
+  void create(int squareRoot, unsigned sampleN, double beta, double sigmau2, double sigmak2, double snrTh, double engTh, double smooth, double loading, double amp4play,
+              const String& nm) {
+    dsr_throw(dsr_aec_create_info(squareRoot, (int) _played->size(), (int) sampleN, &_aec));
+    dsr_throw(dsr_aec_set_block(_aec, beta, sigmau2, sigmak2, snrTh, amp4play));
+    dsr_throw(dsr_aec_set_info(_aec, snrTh, engTh, smooth, loading));
+    DSR_OP(InformationFilterEchoCancellationFeature, cplx, dsr_aec_stream_create(_aec, _played->handle(), _recorded->handle(), nm.c_str(), &h))
+  }
+  dsr_aec* _aec; VectorComplexFeatureStreamPtr _played, _recorded;
+};
+typedef std::shared_ptr<InformationFilterEchoCancellationFeature> InformationFilterEchoCancellationFeaturePtr;
+class SquareRootInformationFilterEchoCancellationFeature : public InformationFilterEchoCancellationFeature {
+ public:
+  SquareRootInformationFilterEchoCancellationFeature(const VectorComplexFeatureStreamPtr& played, const VectorComplexFeatureStreamPtr& recorded, unsigned sampleN = 1,
+                                                     double beta = 0.95, double sigmau2 = 10e-4, double sigmak2 = 5.0, double snrTh = 2.0, double engTh = 100.0,
+                                                     double smooth = 0.9, double loading = 1.0e-02, double amp4play = 1.0,
+                                                     const String& nm = "Square Root Information Filter Echo Cancellation Feature")
+  : InformationFilterEchoCancellationFeature(played, recorded, 0) { create(1, sampleN, beta, sigmau2, sigmak2, snrTh, engTh, smooth, loading, amp4play, nm); }
+};
+typedef std::shared_ptr<SquareRootInformationFilterEchoCancellationFeature> SquareRootInformationFilterEchoCancellationFeaturePtr;
+
 // ---- btk/modulated/modulated.h
 class NormalFFTAnalysisBank : public VectorComplexFeatureStream {
  public:

@@ -484,18 +484,30 @@ dsr_status dsr_pws_apply(const double* coef_dev, int chanN, const float* src_dev
  * Host-side pieces (create, setters, sizes, errors) need no GPU.  Initial state: NLMS R = 0 (the reference allocates it uninitialised and
  * relies on __iter__'s reset()); Kalman sigma2_v = K = sigma2 and sigma2_u = sigma2 (cancelVP.cc:109-122); block variants sigma2_v = sigmau2,
  * K = sigmak2 I, Sigma_u = sigmau2 I, R = 0, history zero (:216-247); DTD scalars zero (:1062).  Not reproduced: the printf dumps at bin 20,
- * the DTD constructor's debug file (:1065, :1102-1107).  InformationFilter... and SquareRootInformationFilter... are not provided.
+ * the DTD constructor's debug file (:1065, :1102-1107).
+ * The same handle also serves InformationFilterEchoCancellationFeature and SquareRootInformationFilterEchoCancellationFeature (cancelVP.h:264-339,
+ * cancelVP.i:156-222, cancelVP.cc:386-1053): kinds DSR_AEC_INFO and DSR_AEC_SQRT_INFO, made by dsr_aec_create_info.  Initial state of both:
+ * R = (1, 0, ...) (:405-407), sigma2_v = sigmau2, history zero, the per-bin _EkEnergy, _SkEnergy, _snr zero; plain kind K = sigmak2 I,
+ * Sigma_u = sigmau2 I, skip counter 0; square-root kind K = Sigma_u = I / sqrt(sigmau2) (inverse Cholesky factors; sigmak2 is not used, :670-677),
+ * information state zero.  Kept: the floor rule of the plain kind (a residual with |E| < 0.01 leaves as E / |E|, so a residual of exactly 0 is
+ * NaN in that bin, :533-535), its reset rule (a skipped (frame, bin) pair that finds 30 counted sets that bin's filter back to (1, 0, ...),
+ * :550-560), the first-100-frames branch of _updateBand (:449-475).  Deviation: the reference fixes the diagonal load at the first call in the
+ * process (a function-static, :610); here every handle uses its own loading.  The two agree when a process uses one loading value.
  * ===================================================================================== */
 typedef struct dsr_aec dsr_aec;
 #define DSR_AEC_NLMS   0
 #define DSR_AEC_KALMAN 1
 #define DSR_AEC_BLOCK  2
 #define DSR_AEC_DTD    3
+#define DSR_AEC_INFO      8   /* made by dsr_aec_create_info only: dsr_aec_create refuses every kind outside 0..3 */
+#define DSR_AEC_SQRT_INFO 9
 #define DSR_AEC_MAX_SAMPLE_N 32
 /* fftLen = played->size() (cancelVP.cc:41): odd or non-positive is DSR_E_PARAMETER (no power of two needed).  sampleN: the taps per bin of the
    block variants (cancelVP.i:141), 1..DSR_AEC_MAX_SAMPLE_N, otherwise DSR_E_PARAMETER (a covariance above 32 x 32 does not fit a wave's
    registers and there is no slower path); NLMS and Kalman take and ignore it (they have one tap). */
 dsr_status dsr_aec_create(int kind, int fftLen, int sampleN, dsr_aec** out);
+/* the information filter (squareRoot 0) or its square-root form (squareRoot != 0); fftLen and sampleN as for the block variants */
+dsr_status dsr_aec_create_info(int squareRoot, int fftLen, int sampleN, dsr_aec** out);
 void       dsr_aec_destroy(dsr_aec*);
 int        dsr_aec_kind(const dsr_aec*);
 int        dsr_aec_fft_len(const dsr_aec*);
@@ -511,7 +523,10 @@ dsr_status dsr_aec_set_kalman(dsr_aec*, double beta, double sigma2, double thres
 dsr_status dsr_aec_set_block(dsr_aec*, double beta, double sigmau2, double sigmak2, double threshold, double amp4play);
 /* DTD only (cancelVP.i:242-243): snrTh 2, engTh 100, smooth 0.9 */
 dsr_status dsr_aec_set_dtd(dsr_aec*, double snrTh, double engTh, double smooth);
-/* DTD only: which frameX _updateBand sees (cancelVP.cc:1077-1087, :1158).  0 (default) = the running frame index frame0 + t, a driver that
+/* the two information kinds only (cancelVP.i:162-163): snrTh 2, engTh 100, smooth 0.9, loading 1e-2; beta, sigmau2, sigmak2 and amp4play come
+   from dsr_aec_set_block, whose threshold these kinds ignore: snrTh is also the |v[0]|^2 gate (cancelVP.cc:392) */
+dsr_status dsr_aec_set_info(dsr_aec*, double snrTh, double engTh, double smooth, double loading);
+/* DTD and the information kinds: which frameX _updateBand sees (cancelVP.cc:1077-1087, :1158).  0 (default) = the running frame index frame0 + t, a driver that
    calls next(t); 1 = the constant -5 of a driver that iterates (`for x in aec`), which stays in the first-100-frames branch for ever */
 dsr_status dsr_aec_set_frame_mode(dsr_aec*, int mode);
 /* the caller's state for U utterances: bytes to allocate (0 for a bad argument), and the initial state written into it */
@@ -520,8 +535,10 @@ dsr_status dsr_aec_state_init(const dsr_aec*, void* state_dev, int U, void* stre
 /* next() over a batch: played_dev, recorded_dev [U][Tmax][fftLen/2+1] complex64, nframes_dev (optional) [U] -> out_dev same shape, the residual
  * E.  Frames from nframes[u] on are written as zero and do not touch the state.  state_dev: the state the call continues from and leaves
  * behind -- block-wise processing gives the bits of one call; NULL = a fresh initial state, discarded.  frame0: the index of the call's first
- * frame (DTD, frame mode 0).  The block variants' reset() resets nothing, so carrying the state from utterance to utterance is the reference's
- * behaviour; starting afresh is state_init.  DTD: fftLen above 2046 is DSR_E_DIMENSION (one workgroup keeps a frame's per-bin scalars in LDS). */
+ * frame (DTD and the information kinds, frame mode 0).  The block variants' reset() resets nothing, so carrying the state from utterance to utterance is the reference's
+ * behaviour; starting afresh is state_init.  DTD and the plain information filter: fftLen above 2046 is DSR_E_DIMENSION (one workgroup keeps a frame's per-bin scalars in LDS).
+ * The square-root information filter: a Givens rotation with a zero norm (the reference's jarithmetic_error, cancelVP.cc:699-700) is recorded
+ * per utterance and reported as DSR_E_ARITHMETIC after the launch, so the call waits for its kernel. */
 dsr_status dsr_aec_apply(const dsr_aec*, const float* played_dev, const float* recorded_dev, const int32_t* nframes_dev, int U, int Tmax, int frame0,
                          float* out_dev, void* state_dev, void* stream);
 /* read a part of the state back (synchronous): what FILTER [U][fftLen/2+1][L] complex128, K [U][fftLen/2+1][L][L] complex128, SIGMA2V
@@ -532,6 +549,13 @@ dsr_status dsr_aec_apply(const dsr_aec*, const float* played_dev, const float* r
 #define DSR_AEC_STATE_SIGMA2V 2
 #define DSR_AEC_STATE_DTD     3
 #define DSR_AEC_STATE_HISTORY 4
+/* the information kinds: BAND [U][fftLen/2+1][3] (_EkEnergy, _SkEnergy, _snr of every bin); INFO [U][fftLen/2+1][L] complex128, the
+   information state of the square-root kind, whose K is the inverse Cholesky factor the reference keeps in _K_k (lower triangular); SKIPPED [U]
+   the plain kind's _skippedN, RESETS [U] how often its reset rule fired since state_init.  DSR_AEC_STATE_DTD is not a part of theirs. */
+#define DSR_AEC_STATE_BAND    5
+#define DSR_AEC_STATE_INFO    6
+#define DSR_AEC_STATE_SKIPPED 7
+#define DSR_AEC_STATE_RESETS  8
 dsr_status dsr_aec_state_read(const dsr_aec*, const void* state_dev, int U, int what, double* host_out, size_t outDoubles);
 /* reset() of NLMS and Kalman (cancelVP.h:60, :98): the filter coefficients become zero, sigma2_v and K live on.  For the block variants it
    does nothing, as their reset() does (cancelVP.h:134-142). */

@@ -3,8 +3,9 @@ step (ms / frames: every (utterance, bin) chain walks the frames in order, all c
 (frame, bin) (played and recorded read, the residual written, complex64 each), and in the same run a copy_ of the same bytes for scale.
 One JSON line per shape, appended to profiles/aec.jsonl.
 
-  python tools/bench_aec.py                                    # the three one-tap kinds at 256,1257,256 and the block filter at L 4, 16, 32 for U 32 and 256
-  python tools/bench_aec.py --shape 256,1257,256,16 --kind block [--kind dtd] [--no-append]
+  python tools/bench_aec.py                                    # the three one-tap kinds at 256,1257,256; the block filter and the two information
+                                                               # filters at L 4, 16, 32 for U 32 and 256
+  python tools/bench_aec.py --shape 256,1257,256,16 --kind block [--kind dtd] [--kind info] [--kind sqrtinfo] [--no-append]
 """
 import argparse
 import json
@@ -59,7 +60,7 @@ def run(kind, U, T, M, L, warm, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", action="append", help="U,T,M,L")
-    ap.add_argument("--kind", action="append", help="nlms | kalman | block | dtd (default block)")
+    ap.add_argument("--kind", action="append", help="nlms | kalman | block | dtd | info | sqrtinfo (default block)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-append", action="store_true", help="do not append to profiles/aec.jsonl (e.g. under a profiler)")
@@ -67,7 +68,7 @@ def main():
     if a.shape:
         todo = [(k,) + tuple(int(v) for v in s.split(",")) for s in a.shape for k in (a.kind or ["block"])]
     else:
-        todo = [(k, 256, 1257, 256, 1) for k in ("nlms", "kalman", "block")] + [("block", U, 1257, 256, L) for U in (32, 256) for L in (4, 16, 32)]
+        todo = [(k, 256, 1257, 256, 1) for k in ("nlms", "kalman", "block")] + [(k, U, 1257, 256, L) for k in ("block", "info", "sqrtinfo") for U in (32, 256) for L in (4, 16, 32)]
     for kind, U, T, M, L in todo:
         res = run(kind, U, T, M, L, a.warmup, a.reps)
         if not a.no_append:

@@ -1,0 +1,152 @@
+"""asr.train: CodebookSetTrainPtr / CodebookTrainPtr / DistribSetTrainPtr / DistribTrainPtr (asr/train/codebookTrain.h, distribTrain.h) for 1:1
+diagonal models, over dsr_train_* (include/dsr.h section 9).
+
+The two sets share one training handle: the distribution set is built on the codebook set (as in the reference) and creates it; the codebook
+set's methods need that to have happened.  Frames come from the feature stream the codebook set names -- accumulate() pulls frames 0..len(path)-1
+through the stream protocol, puts them on the device once and runs the whole path as one batch -- or from `feats`, a cuda float32 [T][dimN]
+tensor handed to setFeatures() (what a pipeline that already holds its features on the device uses).
+
+    path = decoder.bestPath()                 # DecoderFlyWeightPtr.bestPath(): distribution names
+    dss.accumulate(path, 1.0)
+    cbs.update(); dss.update(); cbs.floorVariances(); cbs.fixGConsts(); cbs.invertVariances()
+    dss.save(cbkFile, distFile)
+"""
+import numpy as np
+
+from .. import _capi as K
+from .gaussian import CodebookSetBasicPtr, DistribSetBasicPtr
+
+
+class CodebookTrainPtr(object):
+    def __init__(self, cbs, cbX):
+        self._cbs, self._x = cbs, cbX
+
+    def name(self):
+        return K.load().dsr_gmm_codebook_name(self._cbs._need().gmm.h, self._x).decode()
+
+    def refN(self):
+        return int(self._cbs._need().gmm.params()["refN"][self._x])
+
+
+class CodebookSetTrainPtr(CodebookSetBasicPtr):
+    """CodebookSetTrain(descFile, fs, cbkFile, massThreshold) (codebookTrain.cc:586-599)"""
+
+    def __init__(self, descFile="", fs=None, cbkFile="", massThreshold=5.0):
+        CodebookSetBasicPtr.__init__(self, descFile, fs, cbkFile)
+        self._massThreshold = float(massThreshold); self._trainer = None; self.totalPr, self.totalT = 0.0, 0
+
+    def _need(self):
+        if self._trainer is None:
+            raise K.DsrError(K.E_CONSISTENCY, "Must allocate codebook accumulators before accumulating FB statistics: build the DistribSetTrainPtr first")
+        return self._trainer
+
+    def find(self, key):
+        t = self._need(); g = t.gmm
+        names = [K.load().dsr_gmm_codebook_name(g.h, k).decode() for k in range(g.K)]
+        x = names.index(key) if isinstance(key, str) else int(key)
+        return CodebookTrainPtr(self, x)
+
+    def allocAccus(self):
+        if self._trainer is not None:
+            self._trainer.zero(1)
+
+    def zeroAccus(self, nParts=1, part=1):
+        self._need().zero(1, nParts, part)
+
+    def saveAccus(self, fileName, totalPr=0.0, totalT=0, onlyCountsFlag=False):
+        self._need().save_codebook_accus(fileName, totalPr, totalT, onlyCountsFlag)
+
+    def loadAccus(self, fileName, factor=1.0, nParts=1, part=1):
+        self.totalPr, self.totalT = self._need().load_codebook_accus(fileName, factor, nParts, part)
+
+    def update(self, nParts=1, part=1, verbose=False):
+        self._need().update(1, nParts, part)
+
+    def updateMMI(self, nParts=1, part=1, E=1.0):
+        self._need().update_mmi(1, E, False, nParts, part)
+
+    def floorVariances(self, nParts=1, part=1):
+        total, floored = self._need().floor_variances(nParts, part)
+        print("Floored %d of %d total variance components." % (floored, total))
+        return total, floored
+
+    def fixGConsts(self, nParts=1, part=1):
+        self._need().fix_gconsts(nParts, part)
+
+    def invertVariances(self, nParts=1, part=1):
+        self._need().invert_variances(nParts, part)
+
+    def save(self, cbkFile, distFile):
+        self._need().gmm.save(cbkFile, distFile)
+
+
+class DistribTrainPtr(object):
+    def __init__(self, dss, distX):
+        self._dss, self._x = dss, distX
+
+    def name(self):
+        return K.load().dsr_gmm_dist_name(self._dss.gmm.h, self._x).decode()
+
+    def split(self, minCount=0.0, splitFactor=0.2):
+        """DistribTrain::split (distribTrain.cc:92-109)"""
+        self._dss._trainer.split(self._x, minCount, splitFactor)
+
+
+class DistribSetTrainPtr(DistribSetBasicPtr):
+    """DistribSetTrain(cbs, descFile, distFile) (distribTrain.cc:424-437)"""
+
+    def __init__(self, cbs, descFile="", distFile="", gmmMode=0):
+        DistribSetBasicPtr.__init__(self, cbs, descFile, distFile, gmmMode)
+        self._trainer = K.Trainer(self.gmm, getattr(cbs, "_massThreshold", 5.0)); cbs._trainer = self._trainer
+        self._feats = None
+
+    def find(self, key):
+        x = self.index(key) if isinstance(key, str) else int(key)
+        if not 0 <= x < self.gmm.K:
+            raise K.DsrError(K.E_INDEX, "distribution %d of %d" % (x, self.gmm.K))
+        return DistribTrainPtr(self, x)
+
+    def setFeatures(self, feats):
+        """frames already on the device: cuda float32 [T][dimN] (None: pull them from the feature stream again)"""
+        self._feats = feats
+
+    def _frames(self, T):
+        import torch
+        if self._feats is not None:
+            return self._feats
+        rows = [np.array(self._feat.next(t), np.float32) for t in range(T)]
+        return torch.from_numpy(np.stack(rows)).cuda().contiguous()
+
+    def accumulate(self, path, factor=1.0):
+        """DistribSetTrain::accumulate(path, factor) (distribTrain.cc:515-526): path = DecoderFlyWeightPtr.bestPath()"""
+        ids = [self.index(n) if isinstance(n, str) else int(n) for n in path]
+        score = self._trainer.accumulate_path(self._frames(len(ids)), ids, factor)
+        print("Finished accumulation for %d frames." % len(ids))
+        return score
+
+    def accumulateLattice(self, lat, factor=1.0):
+        """DistribSetTrain::accumulateLattice(lat, factor) (distribTrain.cc:528-561); lat: a LatticePtr after gammaProbs"""
+        L = getattr(lat, "_lat", lat)
+        ends = L.data["end"][L.data["in"] != 0]                 # epsilon links are skipped and may lie behind the last frame
+        T = int(ends.max()) + 1 if len(ends) else 0
+        n = self._trainer.accumulate_lattice(L, self._frames(T), factor)
+        print("Finished accumulation for %d links." % n)
+        return n
+
+    def zeroAccus(self, nParts=1, part=1):
+        self._trainer.zero(2, nParts, part)
+
+    def saveAccus(self, fileName):
+        self._trainer.save_distrib_accus(fileName)
+
+    def loadAccus(self, fileName, nParts=1, part=1):
+        self._trainer.load_distrib_accus(fileName, 1.0, nParts, part)
+
+    def update(self, nParts=1, part=1):
+        self._trainer.update(2, nParts, part)
+
+    def updateMMI(self, nParts=1, part=1, merialdo=False):
+        self._trainer.update_mmi(2, 1.0, merialdo, nParts, part)
+
+    def save(self, cbkFile, distFile):
+        self.gmm.save(cbkFile, distFile)

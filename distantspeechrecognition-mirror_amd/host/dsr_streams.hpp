@@ -1064,6 +1064,8 @@ class DistribSetBasic {
   void resetCache() { dsr_throw(dsr_distribset_reset_cache(_ds)); }
   void resetFeature() { dsr_throw(dsr_distribset_reset_feature(_ds)); }
   dsr_distribset* handle() const { return _ds; }
+  dsr_gmm* gmm() const { return _gmm; }
+  VectorFloatFeatureStreamPtr& featureStream() { return _feat; }
  private:
   DistribSetBasic(const DistribSetBasic&); DistribSetBasic& operator=(const DistribSetBasic&);
   CodebookSetBasicPtr _cbs; VectorFloatFeatureStreamPtr _feat; dsr_gmm* _gmm; dsr_distribset* _ds;
@@ -1256,3 +1258,86 @@ class DecoderWordTrace {
   DistribSetPtr _dist; WFSTFlyWeightSortedOutputPtr _wfst; String _sil, _eos; dsr_decoder* _h; std::vector<uint32_t> _words;
 };
 typedef std::shared_ptr<DecoderWordTrace> DecoderWordTracePtr;
+
+#include <cstdio>
+// ---- asr/train: CodebookSetTrain(descFile, fs, cbkFile, massThreshold) (codebookTrain.cc:586-599), DistribSetTrain(cbs, descFile, distFile)
+// (distribTrain.cc:424-437) over dsr_train_* (include/dsr.h section 9) for 1:1 diagonal models.  The two sets share one training handle, which
+// the distribution set creates (it owns the model); the codebook set's methods need that to have happened.  Frames are pulled through the
+// stream protocol (frames 0..T-1 of the feature the codebook set names) and run as one batch on the device.
+class DistribSetTrain;
+class CodebookSetTrain : public CodebookSetBasic {
+ public:
+  CodebookSetTrain(const String& descFile = "", FeatureSetPtr fs = FeatureSetPtr(), const String& cbkFile = "", double massThreshold = 5.0)
+    : CodebookSetBasic(descFile, fs, cbkFile), _massThreshold(massThreshold), _t(0), _totalPr(0.0f), _totalT(0) {}
+  void allocAccus() { if (_t) dsr_throw(dsr_train_zero(_t, 1, 1, 1)); }
+  void zeroAccus(unsigned nParts = 1, unsigned part = 1) { dsr_throw(dsr_train_zero(need(), 1, (int) nParts, (int) part)); }
+  void saveAccus(const String& fileName, float totalPr = 0.0f, unsigned totalT = 0, bool onlyCountsFlag = false) { dsr_throw(dsr_train_save_codebook_accus(need(), fileName.c_str(), totalPr, totalT, onlyCountsFlag)); }
+  void loadAccus(const String& fileName, float& totalPr, unsigned& totalT, float factor = 1.0f, unsigned nParts = 1, unsigned part = 1) {
+    dsr_throw(dsr_train_load_codebook_accus(need(), fileName.c_str(), &totalPr, &totalT, factor, (int) nParts, (int) part));
+  }
+  void loadAccus(const String& fileName) { loadAccus(fileName, _totalPr, _totalT); }
+  void update(int nParts = 1, int part = 1, bool verbose = false) { (void) verbose; dsr_throw(dsr_train_update(need(), 1, nParts, part)); }
+  void updateMMI(int nParts = 1, int part = 1, double E = 1.0) { dsr_throw(dsr_train_update_mmi(need(), 1, E, 0, nParts, part)); }
+  void floorVariances(unsigned nParts = 1, unsigned part = 1) {
+    unsigned total = 0, floored = 0; dsr_throw(dsr_train_floor_variances(need(), (int) nParts, (int) part, &total, &floored));
+    printf("Floored %d of %d total variance components.\n", floored, total); fflush(stdout);
+  }
+  void fixGConsts(unsigned nParts = 1, unsigned part = 1) { dsr_throw(dsr_train_fix_gconsts(need(), (int) nParts, (int) part)); }
+  void invertVariances(unsigned nParts = 1, unsigned part = 1) { dsr_throw(dsr_train_invert_variances(need(), (int) nParts, (int) part)); }
+  double massThreshold() const { return _massThreshold; }
+ private:
+  friend class DistribSetTrain;
+  dsr_train* need() const { if (!_t) throw jconsistency_error("Must allocate codebook accumulators before accumulating FB statistics: build the DistribSetTrain first"); return _t; }
+  double _massThreshold; dsr_train* _t; float _totalPr; unsigned _totalT;
+};
+typedef std::shared_ptr<CodebookSetTrain> CodebookSetTrainPtr;
+
+class DistribTrain {                                          // DistribTrain::split (distribTrain.cc:92-109)
+ public:
+  DistribTrain(dsr_train* t, dsr_gmm* g, int x) : _t(t), _g(g), _x(x) {}
+  String name() const { return dsr_gmm_dist_name(_g, _x); }
+  void split(float minCount = 0.0f, float splitFactor = 0.2f) { unsigned r = 0; dsr_throw(dsr_train_split(_t, _x, minCount, splitFactor, &r)); }
+ private:
+  dsr_train* _t; dsr_gmm* _g; int _x;
+};
+
+class DistribSetTrain : public DistribSetBasic {
+ public:
+  DistribSetTrain(CodebookSetTrainPtr& cbs, const String& descFile = "", const String& distFile = "")
+    : DistribSetBasic(base(cbs), descFile, distFile), _cbsT(cbs), _t(0) {
+    dsr_throw(dsr_train_create(gmm(), cbs->massThreshold(), &_t)); cbs->_t = _t;
+  }
+  ~DistribSetTrain() { _cbsT->_t = 0; dsr_train_destroy(_t); }
+  DistribTrain find(const String& key) { return DistribTrain(_t, gmm(), (int) index(key)); }
+  DistribTrain find(unsigned dsX) { if (dsX >= ndists()) throw jindex_error("distribution index out of range"); return DistribTrain(_t, gmm(), (int) dsX); }
+  double accumulate(const DistribPath& path, float factor = 1.0f) {      // distribTrain.cc:515-526
+    std::vector<int32_t> ids(path.size()); for (size_t i = 0; i < path.size(); i++) ids[i] = (int32_t) index(path[i]);
+    double score = 0.0;
+    dsr_throw(dsr_train_accumulate_path(_t, frames(path.size()), (int64_t) path.size(), ids.data(), factor, &score, 0));
+    printf("Finished accumulation for %d frames.\n", (int) path.size()); fflush(stdout);
+    return score;
+  }
+  void accumulateLattice(LatticePtr& lat, float factor = 1.0f) {        // distribTrain.cc:528-561
+    const int E = dsr_lattice_num_edges(lat->handle()); std::vector<int32_t> end((size_t) (E > 0 ? E : 1)); std::vector<uint32_t> in(end.size());
+    dsr_throw(dsr_lattice_get(lat->handle(), 0, 0, 0, in.data(), 0, 0, end.data(), 0, 0));
+    int T = 0; for (int e = 0; e < E; e++) if (in[(size_t) e] != 0 && end[(size_t) e] + 1 > T) T = end[(size_t) e] + 1;
+    unsigned n = 0; dsr_throw(dsr_train_accumulate_lattice(_t, lat->handle(), frames((size_t) T), T, factor, &n, 0));
+    printf("Finished accumulation for %d links.\n", n); fflush(stdout);
+  }
+  void zeroAccus(int nParts = 1, int part = 1) { dsr_throw(dsr_train_zero(_t, 2, nParts, part)); }
+  void saveAccus(const String& fileName) { dsr_throw(dsr_train_save_distrib_accus(_t, fileName.c_str())); }
+  void loadAccus(const String& fileName, unsigned nParts = 1, unsigned part = 1) { dsr_throw(dsr_train_load_distrib_accus(_t, fileName.c_str(), 1.0f, (int) nParts, (int) part)); }
+  void update(int nParts = 1, int part = 1) { dsr_throw(dsr_train_update(_t, 2, nParts, part)); }
+  void updateMMI(int nParts = 1, int part = 1, bool merialdo = false) { dsr_throw(dsr_train_update_mmi(_t, 2, 1.0, merialdo, nParts, part)); }
+  void save(const String& cbkFile, const String& distFile) { dsr_throw(dsr_gmm_save(gmm(), cbkFile.c_str(), distFile.c_str())); }
+  dsr_train* trainHandle() const { return _t; }
+ private:
+  static CodebookSetBasicPtr& base(CodebookSetTrainPtr& cbs) { static thread_local CodebookSetBasicPtr b; b = cbs; return b; }
+  const float* frames(size_t T) {                                        // frames 0..T-1 of the feature stream, on the device
+    const int D = dsr_gmm_dim(gmm()); std::vector<float> x(T * (size_t) D);
+    for (size_t t = 0; t < T; t++) { const float* p = featureStream()->next((int) t); for (int d = 0; d < D; d++) x[t * D + d] = p[d]; }
+    const float* dev = 0; dsr_throw(dsr_train_upload_features(_t, x.data(), (int64_t) T, &dev)); return dev;
+  }
+  CodebookSetTrainPtr _cbsT; dsr_train* _t;
+};
+typedef std::shared_ptr<DistribSetTrain> DistribSetTrainPtr;

@@ -1871,6 +1871,77 @@ dsr_status dsr_decoder_decode_stream(dsr_decoder*, dsr_distribset*, dsr_decode_r
 dsr_status dsr_lattice_gamma_probs_dist(dsr_lattice*, dsr_distribset*, double acScale, double lmScale, double lmPenalty, double silPenalty,
                                         unsigned silenceX, double* logProb);
 
+/* =====================================================================================
+ * 9. GMM training: ML / MMI accumulation, updates, accumulator files
+ *    replaces CodebookTrain / CodebookSetTrain (asr/train/codebookTrain.cc, "cT"), DistribTrain / DistribSetTrain / AccMap
+ *    (asr/train/distribTrain.cc, "dT") for the diagonal 1:1 models dsr_gmm holds.  One item = DistribTrain::accumulate(frameX, factor)
+ *    (dT:74-80): posteriors of the frame under the distribution (_scoreAll, codebookBasic.cc:645-766, then the normalisation of cT:100-105),
+ *    gamma = posterior * factor (float), then count / denCount / sumO / sumOsq of the codebook (cT:520-540, 354-358) and count / denCount of the
+ *    distribution (dT:133-142), all fp64.  The posteriors and gammas are computed per item exactly in the reference's order; the sums OVER
+ *    ITEMS are formed by an fp64 MFMA contraction in a fixed order (the same call twice gives the same bits; no atomics), so they differ from
+ *    the reference's sequential sums by fp64 reordering and by the float roundings of x*gamma and (gamma*x)*x, which the contraction skips.
+ *    Deviations: MinimumCount (cT:458,590: a process-wide static) belongs to the handle; an item whose posterior sum is zero or not finite --
+ *    the reference divides by it and accumulates NaN -- is refused like a NaN score; shared codebooks do not arise (1:1 models).
+ *    The handle keeps the dsr_gmm it was made from (which must outlive it) and CHANGES it in update / split; every such entry re-uploads the
+ *    device copies of the model, so scoring in any mode sees the new parameters, and dsr_gmm_save writes the trained model.
+ *    (nParts, part) select codebooks / distributions as List::Iterator(lst, nParts, part) does (btk/common/mlist.h:155-178); 1, 1 = all.
+ * ===================================================================================== */
+typedef struct dsr_train dsr_train;
+/* CodebookSetTrain(descFile, fs, cbkFile, massThreshold) (cT:586-599) + allocAccus (cT:617-623) + DistribSetTrain (dT:424-437): zeroed accumulators */
+dsr_status dsr_train_create(dsr_gmm*, double massThreshold, dsr_train** out);
+void       dsr_train_destroy(dsr_train*);
+/* zeroAccus (cT:688-694, dT:491-497); what: 1 codebook accumulators, 2 distribution accumulators, 3 both */
+dsr_status dsr_train_zero(dsr_train*, int what, int nParts, int part);
+int        dsr_train_num_gaussians(const dsr_train*);
+/* The batch entry: M items (frame[i], dist[i], factor[i]) over x_dev [N][dimN] fp32 (host index arrays).  score [M] or NULL: the float score of
+ * every item (cT:95).  DSR_E_INDEX: a frame outside [0, N) or a distribution outside the set; DSR_E_NUMERIC: an item's score is NaN (cT:97-98)
+ * or its posterior sum is zero / not finite -- nothing of the call is then applied.  The call returns when the sums are on the device. */
+dsr_status dsr_train_accumulate(dsr_train*, const float* x_dev, int64_t N, const int32_t* frame, const int32_t* dist, const float* factor, int64_t M,
+                                float* score, void* stream);
+/* DistribSetTrain::accumulate(path, factor) (dT:515-526): frame t with distribution distIds[t]; *score = the double sum of the float scores */
+dsr_status dsr_train_accumulate_path(dsr_train*, const float* x_dev, int64_t T, const int32_t* distIds, float factor, double* score, void* stream);
+/* DistribSetTrain::accumulateLattice(lat, factor) (dT:528-561) with the lattice's current gammas (call gamma_probs first): links with input 0 or
+ * gamma > 10 are skipped, the others give postProb = float(factor exp(-gamma)) for frames start..end of distribution input - 1; *linksN = the
+ * reference's "links" count.  DSR_E_INDEX: start < 0, end >= T or an input beyond the set. */
+dsr_status dsr_train_accumulate_lattice(dsr_train*, dsr_lattice*, const float* x_dev, int64_t T, float factor, unsigned* linksN, void* stream);
+/* for callers without a HIP binding of their own (host/dsr_streams.hpp): N frames of dimN floats from host memory into a buffer the handle
+ * owns; *x_dev stays valid until the next upload or the handle's end */
+dsr_status dsr_train_upload_features(dsr_train*, const float* x_host, int64_t N, const float** x_dev);
+/* The six accumulators as fp64 (any pointer may be NULL): count, denCount [G], sumO, sumOsq [G][dimN] of the codebooks, count, denCount [G] of the
+ * distributions; G = sum of refN, Gaussians in model order */
+dsr_status dsr_train_get(dsr_train*, double* count, double* denCount, double* sumO, double* sumOsq, double* distCount, double* distDenCount);
+dsr_status dsr_train_set(dsr_train*, const double* count, const double* denCount, const double* sumO, const double* sumOsq, const double* distCount,
+                         const double* distDenCount);
+/* Accu::add (cT:392-405: scaled by factor) and DistribTrain::Accu::add (dT:254-262: factor ignored, as written) */
+dsr_status dsr_train_add(dsr_train*, dsr_train* other, double factor);
+/* CodebookSetTrain::saveAccus / loadAccus (cT:625-678, Accu::save/load :299-433, AccMap dT:343-419) and DistribSetTrain::saveAccus / loadAccus
+ * (dT:439-489, Accu::save/load :239-312): big-endian; loading ADDS factor x the stored floats; names absent from the file's map are skipped;
+ * a size mismatch is DSR_E_DIMENSION, a wrong marker DSR_E_IO (codebooks) / DSR_E_ERROR (distributions) */
+dsr_status dsr_train_save_codebook_accus(dsr_train*, const char* fileName, float totalPr, unsigned totalT, int countsOnly);
+dsr_status dsr_train_load_codebook_accus(dsr_train*, const char* fileName, float* totalPr, unsigned* totalT, float factor, int nParts, int part);
+dsr_status dsr_train_save_distrib_accus(dsr_train*, const char* fileName);
+dsr_status dsr_train_load_distrib_accus(dsr_train*, const char* fileName, float factor, int nParts, int part);
+/* Updates of the model (host arithmetic in the reference's order and precision).  what: 1 codebooks, 2 distributions, 3 both.
+ *   update            Accu::update (cT:435-490: count, mean, then VARIANCES in the model's covariance slot) / DistribTrain::Accu::update (dT:146-156)
+ *   update_mmi        Accu::updateMMI (cT:442-446,492-518) / DistribTrain::Accu::updateMMI (dT:158-222; DSR_E_CONSISTENCY as the reference throws)
+ *   floor_variances   CodebookTrain::floorVariances (cT:786-798, floor 1e-4): adds to *total and *floored
+ *   fix_gconsts       GaussDensity::fixGConst (cT:228-241); DSR_E_CONSISTENCY when a determinant is NaN
+ *   invert_variances  CodebookTrain::invertVariance (cT:218-223)
+ *   split             DistribTrain::split (dT:92-109) -> CodebookTrain::split / _split (cT:122-198): the new Gaussian is appended to the codebook;
+ *                     DSR_E_PARAMETER when maxCount < minCount, DSR_E_DIMENSION at 256 Gaussians; that codebook's and distribution's accumulators
+ *                     start again at zero with the new size; *refX = the Gaussian that was split */
+dsr_status dsr_train_update(dsr_train*, int what, int nParts, int part);
+dsr_status dsr_train_update_mmi(dsr_train*, int what, double E, int merialdo, int nParts, int part);
+dsr_status dsr_train_floor_variances(dsr_train*, int nParts, int part, unsigned* total, unsigned* floored);
+dsr_status dsr_train_fix_gconsts(dsr_train*, int nParts, int part);
+dsr_status dsr_train_invert_variances(dsr_train*, int nParts, int part);
+dsr_status dsr_train_split(dsr_train*, int distX, float minCount, float splitFactor, unsigned* refX);
+/* the model's parameters as the updates left them (host copies; any pointer may be NULL): refN [K], mean, cv [G][dimN], det, val, count [G] */
+dsr_status dsr_gmm_get_params(const dsr_gmm*, int32_t* refN, float* mean, float* cv, float* det, float* val, float* count);
+/* milliseconds of the two kernels of the last dsr_train_accumulate (posterior, contraction + reduction); 0 until timing is switched on */
+dsr_status dsr_train_set_timing(dsr_train*, int on);
+dsr_status dsr_train_kernel_ms(const dsr_train*, float ms[2]);
+
 #ifdef __cplusplus
 }
 #endif

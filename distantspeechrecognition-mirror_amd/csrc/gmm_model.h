@@ -15,6 +15,7 @@ struct GmmModel {
   std::vector<int> refN, off;
   std::vector<float> mean, ivar, det, val, scale, pi, count;
   std::vector<std::string> cbNames, dsNames;
+  std::vector<uint16_t> regClass;    // [G] first regression class of each Gaussian (CodebookBasic::_regClass[refX][1]); empty: no table
   DevBuf<int> d_off;                 // [K+1]
   DevBuf<float> d_mean, d_ivar;      // [G][Dp]  (rows padded to Dp = multiple of 4)
   DevBuf<float> d_cst;               // [G] pi+det

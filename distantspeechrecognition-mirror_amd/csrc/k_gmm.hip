@@ -241,10 +241,17 @@ dsr_status dsr_gmm_load(const char* cbFile, const char* dsFile, dsr_gmm** out)
           for (int d = 0; d < dimN; d++) m->ivar.push_back(r.f32());
           m->det.push_back(r.f32());
         }
-        if (regP) for (int i = 0; i < refN; i++) { const int n = (unsigned short) r.i16(); for (int c = 0; c < n; c++) r.i16(); }
+        if (regP) {                                                  // :286-297; GaussDensity::regClass() (codebookBasic.h:275-280) is the FIRST class, 0 without one
+          m->regClass.resize(m->count.size(), 0);
+          for (int i = 0; i < refN; i++) {
+            const int n = (unsigned short) r.i16();
+            for (int c = 0; c < n; c++) { const unsigned short v = (unsigned short) r.i16(); if (c == 0) m->regClass[m->count.size() - refN + i] = v; }
+          }
+        }
         if (descP) for (int i = 0; i < refN; i++) for (int b = 0; b < nSub; b++) r.i16();
         if (r.i32() != 123456789) throw Error(DSR_E_ERROR, "CheckMarker: Marker expected in codebook file.");
       }
+      if (!m->regClass.empty()) m->regClass.resize(m->count.size(), 0);       // codebooks after the last one that carries a table
       fclose(fp); fp = nullptr;
       fp = fopen(dsFile, "rb"); if (!fp) throw Error(DSR_E_IO, "Could not open distribution set file %s.", dsFile);
       BE q{fp};
@@ -295,13 +302,15 @@ dsr_status dsr_gmm_save(const dsr_gmm* m, const char* cbFile, const char* dsFile
     BE w{fp};
     w.w32(64207531); w.w32(0); w.w32(m->K);                          // CodebookSetBasic::save :962-983
     for (int k = 0; k < m->K; k++) {
-      w.wstr(m->cbNames[k]); w.w32(m->refN[k]); w.w32(m->D); w.w32(m->D); w.w32(1); w.w32(2 /*COV_DIAGONAL*/); w.w32(0); w.w32(0);
+      const bool regP = !m->regClass.empty();                          // CodebookBasic::save :352-405
+      w.wstr(m->cbNames[k]); w.w32(m->refN[k]); w.w32(m->D); w.w32(m->D); w.w32(1); w.w32(2 /*COV_DIAGONAL*/); w.w32(regP ? 1 : 0); w.w32(0);
       for (int g = m->off[k]; g < m->off[k + 1]; g++) {
         w.wf(m->count[g]);
         for (int d = 0; d < m->D; d++) w.wf(m->mean[(size_t) g * m->D + d]);
         for (int d = 0; d < m->D; d++) w.wf(m->ivar[(size_t) g * m->D + d]);
         w.wf(m->det[g]);
       }
+      if (regP) for (int g = m->off[k]; g < m->off[k + 1]; g++) { w.w16(1); w.w16((short) m->regClass[g]); }   // one class per Gaussian (:388-395)
       w.w32(123456789);
     }
     fclose(fp);
@@ -315,6 +324,32 @@ dsr_status dsr_gmm_save(const dsr_gmm* m, const char* cbFile, const char* dsFile
     fclose(fp);
   });
 }
+
+// the regression-class table: CodebookBasic::setRegClasses(c) (codebookBasic.cc:213-223) on every codebook (:1002-1006), and one class per Gaussian
+dsr_status dsr_gmm_set_reg_class_all(dsr_gmm* m, unsigned c)
+{
+  return guard([&] {
+    if (!m) throw Error(DSR_E_PARAMETER, "null argument");
+    if (c > 0xffffu) throw Error(DSR_E_PARAMETER, "regression class %u does not fit UnShrt", c);
+    m->regClass.assign((size_t) m->G, (uint16_t) c);
+  });
+}
+dsr_status dsr_gmm_set_reg_classes(dsr_gmm* m, const uint16_t* perGaussian)
+{
+  return guard([&] {
+    if (!m || !perGaussian) throw Error(DSR_E_PARAMETER, "null argument");
+    m->regClass.assign(perGaussian, perGaussian + m->G);
+  });
+}
+dsr_status dsr_gmm_get_reg_classes(const dsr_gmm* m, uint16_t* perGaussian, int* present)
+{
+  return guard([&] {
+    if (!m) throw Error(DSR_E_PARAMETER, "null argument");
+    if (present) *present = m->regClass.empty() ? 0 : 1;
+    if (perGaussian) for (int g = 0; g < m->G; g++) perGaussian[g] = m->regClass.empty() ? 0 : m->regClass[g];
+  });
+}
+int dsr_gmm_num_gaussians(const dsr_gmm* m) { return m ? m->G : 0; }
 
 void dsr_gmm_destroy(dsr_gmm* m) { delete m; }
 int dsr_gmm_num_dists(const dsr_gmm* m) { return m->K; }

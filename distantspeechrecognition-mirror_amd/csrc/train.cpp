@@ -410,6 +410,7 @@ dsr_status dsr_train_split(dsr_train* t, int distX, float minCount, float splitF
     m.count[src] = half; m.count.insert(m.count.begin() + at, half);
     const float nval = (float) ((double) m.val[src] + log(2.0));               // dT:99-100
     m.val[src] = nval; m.val.insert(m.val.begin() + at, nval);
+    if (!m.regClass.empty()) m.regClass.insert(m.regClass.begin() + at, m.regClass[src]);       // the new Gaussian is of its parent's class
     m.refN[distX] = R + 1;
     reupload(m);                                            // offsets, G, device copies
     // fresh accumulators for this codebook and distribution (cT:183, dT:106), everybody else's rows move up

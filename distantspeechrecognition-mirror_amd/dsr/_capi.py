@@ -1954,6 +1954,24 @@ class Gmm:
         check(_lib.dsr_gmm_score(self.h, _dev(x), N, mode, _dev(sc), _dev(am) if am is not None else None, cur_stream()))
         return sc, am
 
+    @property
+    def G(self):
+        return _lib.dsr_gmm_num_gaussians(self.h)
+
+    def set_reg_classes(self, classes):
+        """one regression class per Gaussian [G], or one class for every Gaussian (CodebookSetBasic::setRegClasses)"""
+        if np.isscalar(classes):
+            check(_lib.dsr_gmm_set_reg_class_all(self.h, int(classes)))
+        else:
+            c = _np(classes, np.uint16); assert c.shape == (self.G,)
+            check(_lib.dsr_gmm_set_reg_classes(self.h, _ptr(c)))
+
+    def reg_classes(self):
+        """the classes [G] (0 where there is none), or None for a model without the table"""
+        c = np.zeros(self.G, np.uint16); present = C.c_int(0)
+        check(_lib.dsr_gmm_get_reg_classes(self.h, _ptr(c), C.byref(present)))
+        return c if present.value else None
+
     def params(self):
         """the model's host parameters as the training updates left them: refN [K], mean, cv [G][D], det, val, count [G]"""
         r = np.zeros(self.K, np.int32); check(_lib.dsr_gmm_get_params(self.h, _ptr(r), None, None, None, None, None))
@@ -2063,6 +2081,140 @@ class Trainer:
 
     def kernel_ms(self):
         ms = (C.c_float * 2)(); check(_lib.dsr_train_kernel_ms(self.h, ms)); return ms[0], ms[1]
+
+
+def is_ancestor(ancestor, child):
+    r = C.c_int(0); load(); check(_lib.dsr_is_ancestor(int(ancestor), int(child), C.byref(r))); return bool(r.value)
+
+
+class ParamTree:
+    """ParamTree of MLLR parameters (asr/adapt/transform.cc:789-950; include/dsr.h section 10).  Host only."""
+
+    def __init__(self, fileName="", handle=None, owner=None):
+        L = load(); self._owner = owner
+        if handle is not None:
+            self.h = handle; return
+        self.h = vp(); check(L.dsr_param_tree_create(fileName.encode(), C.byref(self.h)))
+
+    def __del__(self):
+        if _lib is not None and getattr(self, "h", None) and self._owner is None:
+            _lib.dsr_param_tree_destroy(self.h)
+
+    def clear(self):
+        check(_lib.dsr_param_tree_clear(self.h))
+
+    def read(self, fileName):
+        check(_lib.dsr_param_tree_read(self.h, fileName.encode()))
+
+    def write(self, fileName):
+        check(_lib.dsr_param_tree_write(self.h, fileName.encode()))
+
+    def copy_from(self, other):
+        check(_lib.dsr_param_tree_copy(self.h, other.h))
+
+    def type(self):
+        return _lib.dsr_param_tree_type(self.h)
+
+    def hasIndex(self, rc):
+        return bool(_lib.dsr_param_tree_has_index(self.h, int(rc)))
+
+    def indices(self):
+        n = _lib.dsr_param_tree_indices(self.h, None, 0); a = np.zeros(n, np.uint32)
+        _lib.dsr_param_tree_indices(self.h, _ptr(a), n); return [int(x) for x in a]
+
+    def _W(self, rc, size):
+        W = np.zeros((size, size + 1)); check(_lib.dsr_param_tree_get(self.h, int(rc), _ptr(W))); return W
+
+    def find(self, rc, useAncestor=True):
+        """-> W [size][size + 1] of the class, inserted as a copy of its nearest ancestor when missing"""
+        n = C.c_int(0); check(_lib.dsr_param_tree_find(self.h, int(rc), int(useAncestor), 0, C.byref(n))); return self._W(rc, n.value)
+
+    def findMLLR(self, rc, useAncestor=True):
+        n = C.c_int(0); check(_lib.dsr_param_tree_find(self.h, int(rc), int(useAncestor), 1, C.byref(n))); return self._W(rc, n.value)
+
+    def set(self, rc, W):
+        W = _np(W, np.float64); assert W.ndim == 2 and W.shape[1] == W.shape[0] + 1
+        check(_lib.dsr_param_tree_set(self.h, int(rc), W.shape[0], _ptr(W)))
+
+
+class Mllr:
+    """MLLR mean transforms for S speakers at once (csrc/k_mllr.hip; include/dsr.h section 10): statistics on fp64 MFMA, back-off on the host,
+    Jacobi solves and the transformed means on the device.  Made from a Gmm with regression classes (Gmm.set_reg_classes or a codebook file
+    that carries the table); the handle keeps that model's means as the originals."""
+
+    def __init__(self, gmm, S=1):
+        L = load(); self.h = vp(); self.gmm = gmm; self.D = gmm.D; self.G = gmm.G
+        check(L.dsr_mllr_create(gmm.h, int(S), C.byref(self.h))); self.S = L.dsr_mllr_num_speakers(self.h)
+
+    def __del__(self):
+        if _lib is not None and getattr(self, "h", None):
+            _lib.dsr_mllr_destroy(self.h)
+
+    def set_stats(self, s, trainer=None, c=None, sumO=None):
+        """the statistics of slot s: a Trainer (count - denCount and sumO, device to device) or host arrays c [G], sumO [G][D]"""
+        if trainer is not None:
+            check(_lib.dsr_mllr_set_stats(self.h, int(s), trainer.h)); return
+        c = _np(c, np.float64); sumO = _np(sumO, np.float64); assert c.shape == (self.G,) and sumO.shape == (self.G, self.D)
+        check(_lib.dsr_mllr_set_stats_arrays(self.h, int(s), _ptr(c), _ptr(sumO)))
+
+    def estimate(self, threshold=1500.0):
+        check(_lib.dsr_mllr_estimate(self.h, float(threshold), cur_stream()))
+
+    def speaker_status(self, s):
+        return _lib.dsr_mllr_speaker_status(self.h, int(s))
+
+    def plan(self):
+        """the steps of the last estimate: rows (speaker, node, leaf, copy)"""
+        n = C.c_int(0); check(_lib.dsr_mllr_get_plan(self.h, C.byref(n), None))
+        a = np.zeros((n.value, 4), np.int32); check(_lib.dsr_mllr_get_plan(self.h, C.byref(n), _ptr(a))); return a
+
+    def nodes(self):
+        n = C.c_int(0); check(_lib.dsr_mllr_get_nodes(self.h, C.byref(n), None, None))
+        a = np.zeros(n.value, np.uint32); leaf = np.zeros(n.value, np.int32); check(_lib.dsr_mllr_get_nodes(self.h, C.byref(n), _ptr(a), _ptr(leaf)))
+        return [int(x) for x in a], [bool(x) for x in leaf]
+
+    def stats(self, s, node, row):
+        """-> G_i [D + 1][D + 1], z_i [D + 1] of the last estimate"""
+        n = self.D + 1; Gi = np.zeros((n, n)); z = np.zeros(n)
+        check(_lib.dsr_mllr_get_stats(self.h, int(s), int(node), int(row), _ptr(Gi), _ptr(z))); return Gi, z
+
+    def ttl_frames(self, s, node):
+        t = C.c_double(0.0); check(_lib.dsr_mllr_ttl_frames(self.h, int(s), int(node), C.byref(t))); return t.value
+
+    def tree(self, s):
+        h = _lib.dsr_mllr_tree(self.h, int(s))
+        if not h:
+            raise DsrError(E_INDEX, "speaker %d of %d" % (s, self.S))
+        return ParamTree(handle=vp(h), owner=self)
+
+    def transform(self, s, rc):
+        W = np.zeros((self.D, self.D + 1)); check(_lib.dsr_mllr_get_transform(self.h, int(s), int(rc), _ptr(W))); return W
+
+    def write(self, s, fileName):
+        check(_lib.dsr_mllr_write(self.h, int(s), fileName.encode()))
+
+    def read(self, s, fileName):
+        check(_lib.dsr_mllr_read(self.h, int(s), fileName.encode()))
+
+    def adapt(self, s, target=None):
+        check(_lib.dsr_mllr_adapt(self.h, int(s), (target or self.gmm).h))
+
+    def adapt_all(self, out=None):
+        """-> cuda float32 [S][G][D]: every speaker's transformed means"""
+        import torch
+        if out is None:
+            out = torch.empty((self.S, self.G, self.D), dtype=torch.float32, device="cuda")
+        assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (self.S, self.G, self.D)
+        check(_lib.dsr_mllr_adapt_all(self.h, _dev(out), cur_stream())); return out
+
+    def reset_mean(self, target=None):
+        check(_lib.dsr_mllr_reset_mean(self.h, (target or self.gmm).h))
+
+    def set_timing(self, on=True):
+        check(_lib.dsr_mllr_set_timing(self.h, int(on)))
+
+    def kernel_ms(self):
+        ms = (C.c_float * 3)(); check(_lib.dsr_mllr_kernel_ms(self.h, ms)); return ms[0], ms[1], ms[2]
 
 
 class Wfst:

@@ -54,7 +54,7 @@ class DistribSetBasicPtr(object):
     def __init__(self, cbs, descFile="", distFile="", gmmMode=0):
         self._cbs = cbs; self._desc = _desc(descFile) if descFile else []
         self.names = [r[0] for r in self._desc]
-        self.gmm = K.Gmm(files=(cbs._cbkFile, distFile))
+        self.gmm = K.Gmm(files=(cbs._cbkFile, distFile)); cbs._gmm = self.gmm
         if self._desc and len(self._desc) != self.gmm.K:
             raise K.DsrError(4, "%d distributions described, %d in the file" % (len(self._desc), self.gmm.K))
         self._feat = cbs.feature(); self._ds = C.c_void_p()

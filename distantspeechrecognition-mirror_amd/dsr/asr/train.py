@@ -14,7 +14,8 @@ tensor handed to setFeatures() (what a pipeline that already holds its features 
 import numpy as np
 
 from .. import _capi as K
-from .gaussian import CodebookSetBasicPtr, DistribSetBasicPtr
+from .adapt import CodebookSetAdaptPtr, TransformerTreePtr
+from .gaussian import DistribSetBasicPtr
 
 
 class CodebookTrainPtr(object):
@@ -28,11 +29,11 @@ class CodebookTrainPtr(object):
         return int(self._cbs._need().gmm.params()["refN"][self._x])
 
 
-class CodebookSetTrainPtr(CodebookSetBasicPtr):
-    """CodebookSetTrain(descFile, fs, cbkFile, massThreshold) (codebookTrain.cc:586-599)"""
+class CodebookSetTrainPtr(CodebookSetAdaptPtr):
+    """CodebookSetTrain(descFile, fs, cbkFile, massThreshold) (codebookTrain.cc:586-599); a CodebookSetAdapt, as in the reference"""
 
     def __init__(self, descFile="", fs=None, cbkFile="", massThreshold=5.0):
-        CodebookSetBasicPtr.__init__(self, descFile, fs, cbkFile)
+        CodebookSetAdaptPtr.__init__(self, descFile, fs, cbkFile)
         self._massThreshold = float(massThreshold); self._trainer = None; self.totalPr, self.totalT = 0.0, 0
 
     def _need(self):
@@ -150,3 +151,40 @@ class DistribSetTrainPtr(DistribSetBasicPtr):
 
     def save(self, cbkFile, distFile):
         self.gmm.save(cbkFile, distFile)
+
+
+class EstimatorTreeMLLRPtr(TransformerTreePtr):
+    """EstimatorTreeMLLR(cbs, paramTree, trace = 1, threshold = 1500.0) (estimateAdapt.cc:3143-3165): the regression classes of the Gaussians of
+    `cbs` are the leaves; the statistics are the accumulators of the set's training handle"""
+
+    def __init__(self, cbs, paramTree, trace=1, threshold=1500.0):
+        TransformerTreePtr.__init__(self, cbs, paramTree)
+        self._trace, self._threshold = trace, float(threshold)
+        cls = cbs._model().reg_classes()
+        if cls is None or (cls == 0).any():
+            raise K.DsrError(K.E_INDEX, "Regression class index must be >= 1")
+        self._estimated = False
+
+    def _estimate(self):
+        m = self._cbs._adapter()
+        m.set_stats(0, self._cbs._need()); m.estimate(self._threshold)
+        self._paramTree.copy_from(m.tree(0)); self._estimated = True
+        if self._trace & 1:
+            for s, node, leaf, copy in m.plan():
+                print(("Copying parameters for node %d from node %d." % (leaf, node)) if copy else
+                      ("Backing off from node %d to node %d." % (leaf, node)) if leaf != node else ("Estimating Parameters for Regression Class %d" % leaf))
+
+    def writeParams(self, fileName):
+        self._paramTree.write(fileName)
+
+    def ttlFrames(self):
+        """EstimatorTree::ttlFrames (estimateAdapt.cc:3052-3062): the sum over ALL nodes of the tree"""
+        m = self._cbs._adapter()
+        if not self._estimated:
+            raise K.DsrError(K.E_CONSISTENCY, "ttlFrames is known after estimateAdaptationParameters")
+        return float(sum(m.ttl_frames(0, n) for n in m.nodes()[0]))
+
+
+def estimateAdaptationParameters(tree):
+    """estimateAdapt.cc:3064-3078: an MLLR parameter tree is cleared, then every leaf is estimated with back-off"""
+    tree._estimate()

@@ -1264,11 +1264,73 @@ typedef std::shared_ptr<DecoderWordTrace> DecoderWordTracePtr;
 // (distribTrain.cc:424-437) over dsr_train_* (include/dsr.h section 9) for 1:1 diagonal models.  The two sets share one training handle, which
 // the distribution set creates (it owns the model); the codebook set's methods need that to have happened.  Frames are pulled through the
 // stream protocol (frames 0..T-1 of the feature the codebook set names) and run as one batch on the device.
+// ---- asr/adapt: ParamTree (transform.h:520-552) and CodebookSetAdapt (codebookAdapt.h) over dsr_param_tree_* / dsr_mllr_* (include/dsr.h
+// section 10).  Only MLLR parameters.  A codebook set is bound to its model when its distribution set is built (the distribution set owns it).
+class ParamTree {
+ public:
+  ParamTree(const String& fileName = "") : _h(0) { dsr_throw(dsr_param_tree_create(fileName.c_str(), &_h)); }
+  ~ParamTree() { dsr_param_tree_destroy(_h); }
+  void write(const String& fileName) const { dsr_throw(dsr_param_tree_write(_h, fileName.c_str())); }
+  void read(const String& fileName) { dsr_throw(dsr_param_tree_read(_h, fileName.c_str())); }
+  void clear() { dsr_throw(dsr_param_tree_clear(_h)); }
+  int type() const { return dsr_param_tree_type(_h); }
+  bool hasIndex(unsigned index) const { return dsr_param_tree_has_index(_h, index) != 0; }
+  // find / findMLLR (transform.cc:835-860, 898-925): W [size][size + 1], the last column the bias
+  std::vector<double> find(unsigned rc, bool useAncestor = true) { return get(rc, useAncestor, 0); }
+  std::vector<double> findMLLR(unsigned rc, bool useAncestor = true) { return get(rc, useAncestor, 1); }
+  dsr_param_tree* handle() const { return _h; }
+ private:
+  ParamTree(const ParamTree&); ParamTree& operator=(const ParamTree&);
+  std::vector<double> get(unsigned rc, bool useAncestor, int mllr) {
+    int n = 0; dsr_throw(dsr_param_tree_find(_h, rc, useAncestor, mllr, &n));
+    std::vector<double> W((size_t) n * (n + 1) + 1); dsr_throw(dsr_param_tree_get(_h, rc, W.data())); W.resize((size_t) n * (n + 1)); return W;
+  }
+  dsr_param_tree* _h;
+};
+typedef std::shared_ptr<ParamTree> ParamTreePtr;
+
+class CodebookSetAdapt : public CodebookSetBasic {
+ public:
+  CodebookSetAdapt(const String& descFile = "", FeatureSetPtr fs = FeatureSetPtr(), const String& cbkFile = "")
+    : CodebookSetBasic(descFile, fs, cbkFile), _g(0), _m(0) {}
+  ~CodebookSetAdapt() { dsr_mllr_destroy(_m); }
+  void setRegClasses(unsigned c = 1) {
+    if (_m) throw jconsistency_error("regression classes are set before the first estimation or transform");
+    dsr_throw(dsr_gmm_set_reg_class_all(model(), c));
+  }
+  void resetMean() { if (_m) dsr_throw(dsr_mllr_reset_mean(_m, model())); }
+  dsr_gmm* model() const { if (!_g) throw jconsistency_error("the codebook set has no model yet: build its DistribSet first"); return _g; }
+  // the MLLR handle of this set, made on first use: its originals are the means the set was loaded with
+  dsr_mllr* adapter() { if (!_m) dsr_throw(dsr_mllr_create(model(), 1, &_m)); return _m; }
+  void bind(dsr_gmm* g) { _g = g; }
+ private:
+  dsr_gmm* _g; dsr_mllr* _m;
+};
+typedef std::shared_ptr<CodebookSetAdapt> CodebookSetAdaptPtr;
+
+class TransformerTree {                                       // TransformerTree(cbs, paramTree) (transform.cc:2122-2163)
+ public:
+  TransformerTree(CodebookSetAdaptPtr cbs, ParamTreePtr paramTree) : _cbs(cbs), _paramTree(paramTree) {}
+  virtual ~TransformerTree() {}
+  TransformerTree& transform() {
+    printf("\nTransforming Means\n"); fflush(stdout);
+    dsr_mllr* m = _cbs->adapter();
+    dsr_throw(dsr_param_tree_copy(dsr_mllr_tree(m, 0), _paramTree->handle())); dsr_throw(dsr_mllr_adapt(m, 0, _cbs->model()));
+    return *this;
+  }
+  ParamTreePtr& paramTree() { return _paramTree; }
+ protected:
+  CodebookSetAdaptPtr _cbs; ParamTreePtr _paramTree;
+};
+typedef std::shared_ptr<TransformerTree> TransformerTreePtr;
+inline void adaptCbk(CodebookSetAdaptPtr cbs, ParamTreePtr paramTree) { TransformerTree(cbs, paramTree).transform(); }
+
 class DistribSetTrain;
-class CodebookSetTrain : public CodebookSetBasic {
+class CodebookSetTrain : public CodebookSetAdapt {            // a CodebookSetAdapt, as in the reference
  public:
   CodebookSetTrain(const String& descFile = "", FeatureSetPtr fs = FeatureSetPtr(), const String& cbkFile = "", double massThreshold = 5.0)
-    : CodebookSetBasic(descFile, fs, cbkFile), _massThreshold(massThreshold), _t(0), _totalPr(0.0f), _totalT(0) {}
+    : CodebookSetAdapt(descFile, fs, cbkFile), _massThreshold(massThreshold), _t(0), _totalPr(0.0f), _totalT(0) {}
+  dsr_train* trainHandle() const { return need(); }
   void allocAccus() { if (_t) dsr_throw(dsr_train_zero(_t, 1, 1, 1)); }
   void zeroAccus(unsigned nParts = 1, unsigned part = 1) { dsr_throw(dsr_train_zero(need(), 1, (int) nParts, (int) part)); }
   void saveAccus(const String& fileName, float totalPr = 0.0f, unsigned totalT = 0, bool onlyCountsFlag = false) { dsr_throw(dsr_train_save_codebook_accus(need(), fileName.c_str(), totalPr, totalT, onlyCountsFlag)); }
@@ -1305,9 +1367,9 @@ class DistribSetTrain : public DistribSetBasic {
  public:
   DistribSetTrain(CodebookSetTrainPtr& cbs, const String& descFile = "", const String& distFile = "")
     : DistribSetBasic(base(cbs), descFile, distFile), _cbsT(cbs), _t(0) {
-    dsr_throw(dsr_train_create(gmm(), cbs->massThreshold(), &_t)); cbs->_t = _t;
+    dsr_throw(dsr_train_create(gmm(), cbs->massThreshold(), &_t)); cbs->_t = _t; cbs->bind(gmm());
   }
-  ~DistribSetTrain() { _cbsT->_t = 0; dsr_train_destroy(_t); }
+  ~DistribSetTrain() { _cbsT->_t = 0; _cbsT->bind(0); dsr_train_destroy(_t); }
   DistribTrain find(const String& key) { return DistribTrain(_t, gmm(), (int) index(key)); }
   DistribTrain find(unsigned dsX) { if (dsX >= ndists()) throw jindex_error("distribution index out of range"); return DistribTrain(_t, gmm(), (int) dsX); }
   double accumulate(const DistribPath& path, float factor = 1.0f) {      // distribTrain.cc:515-526
@@ -1341,3 +1403,39 @@ class DistribSetTrain : public DistribSetBasic {
   CodebookSetTrainPtr _cbsT; dsr_train* _t;
 };
 typedef std::shared_ptr<DistribSetTrain> DistribSetTrainPtr;
+
+// ---- asr/train/estimateAdapt.h:913-921, estimateAdapt.cc:3064-3165: EstimatorTreeMLLR(cbs, paramTree, trace, threshold) and
+// estimateAdaptationParameters(tree).  The statistics are the accumulators of the codebook set's training handle.
+class EstimatorTreeMLLR : public TransformerTree {
+ public:
+  EstimatorTreeMLLR(CodebookSetTrainPtr& cb, ParamTreePtr& paramTree, int trace = 1, float threshold = 1500.0f)
+    : TransformerTree(cb, paramTree), _cbsT(cb), _trace(trace), _threshold(threshold), _estimated(false) {
+    const int G = dsr_gmm_num_gaussians(cb->model()); std::vector<uint16_t> cls((size_t) (G > 0 ? G : 1)); int present = 0;
+    dsr_throw(dsr_gmm_get_reg_classes(cb->model(), cls.data(), &present));
+    for (int g = 0; g < G; g++) if (!present || cls[(size_t) g] == 0) throw jindex_error("Regression class index must be >= 1");
+  }
+  void estimate() {
+    dsr_mllr* m = _cbsT->adapter();
+    dsr_throw(dsr_mllr_set_stats(m, 0, _cbsT->trainHandle())); dsr_throw(dsr_mllr_estimate(m, _threshold, 0));
+    dsr_throw(dsr_param_tree_copy(_paramTree->handle(), dsr_mllr_tree(m, 0))); _estimated = true;
+    if (!(_trace & 1)) return;
+    int n = 0; dsr_throw(dsr_mllr_get_plan(m, &n, 0)); std::vector<int32_t> p((size_t) 4 * (n > 0 ? n : 1)); dsr_throw(dsr_mllr_get_plan(m, &n, p.data()));
+    for (int i = 0; i < n; i++) {
+      if (p[4 * i + 3]) printf("Copying parameters for node %d from node %d.\n", p[4 * i + 2], p[4 * i + 1]);
+      else if (p[4 * i + 1] != p[4 * i + 2]) printf("Backing off from node %d to node %d.\n", p[4 * i + 2], p[4 * i + 1]);
+    }
+    fflush(stdout);
+  }
+  void writeParams(const String& fileName) { _paramTree->write(fileName); }
+  double ttlFrames() {                                        // EstimatorTree::ttlFrames (estimateAdapt.cc:3052-3062): summed over ALL nodes
+    if (!_estimated) throw jconsistency_error("ttlFrames is known after estimateAdaptationParameters");
+    dsr_mllr* m = _cbsT->adapter(); int n = 0; dsr_throw(dsr_mllr_get_nodes(m, &n, 0, 0));
+    std::vector<uint32_t> nodes((size_t) (n > 0 ? n : 1)); dsr_throw(dsr_mllr_get_nodes(m, &n, nodes.data(), 0));
+    double ttl = 0.0; for (int k = 0; k < n; k++) { double t = 0.0; dsr_throw(dsr_mllr_ttl_frames(m, 0, nodes[(size_t) k], &t)); ttl += t; }
+    return ttl;
+  }
+ private:
+  CodebookSetTrainPtr _cbsT; int _trace; float _threshold; bool _estimated;
+};
+typedef std::shared_ptr<EstimatorTreeMLLR> EstimatorTreeMLLRPtr;
+inline void estimateAdaptationParameters(EstimatorTreeMLLRPtr& tree) { tree->estimate(); }

@@ -1942,6 +1942,92 @@ dsr_status dsr_gmm_get_params(const dsr_gmm*, int32_t* refN, float* mean, float*
 dsr_status dsr_train_set_timing(dsr_train*, int on);
 dsr_status dsr_train_kernel_ms(const dsr_train*, float ms[2]);
 
+/* =====================================================================================
+ * 10. MLLR speaker adaptation: regression classes, parameter trees, estimation, mean transforms
+ *    Replaces the MLLR branch of asr/adapt/transform.{h,cc} ("tr") and asr/train/estimateAdapt.{h,cc} ("eA"); the all-pass transforms
+ *    (RAPT, SLAPT, BLT), STC, LDA and asr/sat are not implemented.
+ * ===================================================================================== */
+/* The regression-class table of a model: CodebookBasic::_regClass (asr/gaussian/codebookBasic.cc:179-187).  dsr_gmm_load keeps the FIRST class
+ * of each Gaussian of a codebook file whose regClassPresent is set (:286-297) -- GaussDensity::regClass() (codebookBasic.h:275-280) -- and
+ * dsr_gmm_save writes the table as CodebookBasic::save does (:352-405), one class per Gaussian; a model without a table is saved as before.
+ *   set_reg_class_all   CodebookSetBasic::setRegClasses(c) (:213-223, 1002-1006)
+ *   set_reg_classes     one class per Gaussian [G], codebook after codebook
+ *   get_reg_classes     the classes (0 where there is none) and whether the model has a table; either pointer may be NULL */
+dsr_status dsr_gmm_set_reg_class_all(dsr_gmm*, unsigned c);
+dsr_status dsr_gmm_set_reg_classes(dsr_gmm*, const uint16_t* perGaussian);
+dsr_status dsr_gmm_get_reg_classes(const dsr_gmm*, uint16_t* perGaussian, int* present);
+int dsr_gmm_num_gaussians(const dsr_gmm*);
+
+/* ParamTree of MLLRParam (tr:520-552, 789-950; the text file of tr:203-407, 576-607).  Host only: needs no device.
+ *   create      ParamTree(fileName): "" or NULL is an empty tree
+ *   read        clear, then one parameter per <AdaptType> ... <EndClass> block; DSR_E_TYPE for a file of another adaptation type,
+ *               DSR_E_PARAMETER for RAPT / SLAPT symbols or a second type inside a class, DSR_E_CONSISTENCY for a file without parameters
+ *   write       the classes in index order, class 0 written as 1, numbers with " %g"
+ *   type        0 unspecified, 3 MLLR (AdaptationType)
+ *   find        mllr = 0: ParamTree::find (tr:835-860), 1: findMLLR (tr:898-925); with useAncestor a missing class becomes a copy of its
+ *               nearest ancestor (findMLLR: an empty parameter when there is none); DSR_E_INDEX otherwise and for class 0; *size = the order
+ *   get / set   W [size][size + 1], the last column the bias (MLLRParam::operator=(gsl_matrix*), tr:622-650); set goes through findMLLR
+ *   indices     the classes in order (at most cap are written); returns their number */
+typedef struct dsr_param_tree dsr_param_tree;
+dsr_status dsr_param_tree_create(const char* fileName, dsr_param_tree** out);
+void dsr_param_tree_destroy(dsr_param_tree*);
+dsr_status dsr_param_tree_clear(dsr_param_tree*);
+dsr_status dsr_param_tree_read(dsr_param_tree*, const char* fileName);
+dsr_status dsr_param_tree_write(const dsr_param_tree*, const char* fileName);
+dsr_status dsr_param_tree_copy(dsr_param_tree* dst, const dsr_param_tree* src);
+int dsr_param_tree_type(const dsr_param_tree*);
+int dsr_param_tree_has_index(const dsr_param_tree*, unsigned rc);
+int dsr_param_tree_indices(const dsr_param_tree*, unsigned* indices, int cap);
+dsr_status dsr_param_tree_find(dsr_param_tree*, unsigned rc, int useAncestor, int mllr, int* size);
+dsr_status dsr_param_tree_get(const dsr_param_tree*, unsigned rc, double* W);
+dsr_status dsr_param_tree_set(dsr_param_tree*, unsigned rc, int D, const double* W);
+/* isAncestor (tr:133-145); DSR_E_INDEX when either index is 0 */
+dsr_status dsr_is_ancestor(unsigned ancestor, unsigned child, int* result);
+
+/* MLLR for S speakers at once (csrc/k_mllr.hip).  The handle copies the model's means (CodebookAdapt::_origRV: estimation and the transforms
+ * always read these, codebookAdapt.h:99-104), inverse variances and regression classes when it is made; dimN <= 80.
+ *   set_stats          count - denCount (postProb(), codebookTrain.h:142-144) and sumO of a trainer into slot s, device to device
+ *   set_stats_arrays   the same from host arrays c [G], sumO [G][dimN]
+ *   estimate           EstimatorTreeMLLR (eA:3143-3165) + estimateAdaptationParameters (eA:3064-3078) for every slot: the statistics
+ *                      G_i = sum_g c iv_gi xi xi^T, z_i = sum_g sumO_gi iv_gi xi (xi = (mean, 1); _calcGi / _calcZ eA:2101-2153) of every node by an
+ *                      fp64 MFMA contraction summed in a fixed order (they differ from the reference's sums by its float roundings of the terms
+ *                      and by fp64 reordering; Gaussians whose count rounds to float 0 are skipped as there); LeafIterator::estimate's back-off
+ *                      (eA:3105-3133) on the host; w_i = pinv(G_i) z_i with singular values below 1e-7 of the largest dropped (eA:2156-2180) by
+ *                      a Jacobi eigen-decomposition.  Each slot's tree is replaced by the result.  DSR_E_INDEX for a Gaussian of class 0
+ *                      (_setNode, tr:2019-2023); DSR_E_CONSISTENCY when some slot's statistics are not finite or did not converge: those
+ *                      slots keep their trees (dsr_mllr_speaker_status), the others are done.
+ *   get_plan           the steps of the last estimate, [n][4] = speaker, node, leaf, copy (1: copied from the nearest ancestor)
+ *   get_nodes          the nodes of the regression tree in order and whether each is a leaf
+ *   get_stats          G_i [dimN + 1][dimN + 1] and z_i [dimN + 1] of the last estimate;  ttl_frames  EstimatorAdapt::ttlFrames (eA:1565-1572)
+ *   tree               the slot's parameter tree (owned by the handle)
+ *   adapt              TransformerTree::transform (tr:2149-2163) of slot s into `target` (a model of the same shape): every Gaussian takes the
+ *                      transform of node(regClass, useAncestor) -- DSR_E_KEY without one (tr:2030-2049) -- computed as MLLRTransformer::
+ *                      transform does (tr:1770-1785: a float that starts at the bias and is rounded after every term); the model is re-uploaded
+ *   adapt_all          the same for every slot into means_dev [S][G][dimN] (device)
+ *   reset_mean         CodebookAdapt::resetMean: the original means back into `target` */
+typedef struct dsr_mllr dsr_mllr;
+dsr_status dsr_mllr_create(const dsr_gmm*, int S, dsr_mllr** out);
+void dsr_mllr_destroy(dsr_mllr*);
+int dsr_mllr_num_speakers(const dsr_mllr*);
+dsr_status dsr_mllr_set_stats(dsr_mllr*, int s, dsr_train*);
+dsr_status dsr_mllr_set_stats_arrays(dsr_mllr*, int s, const double* c, const double* sumO);
+dsr_status dsr_mllr_estimate(dsr_mllr*, double threshold, void* stream);
+int dsr_mllr_speaker_status(const dsr_mllr*, int s);
+dsr_status dsr_mllr_get_plan(const dsr_mllr*, int* n, int32_t* steps);
+dsr_status dsr_mllr_get_nodes(const dsr_mllr*, int* n, uint32_t* nodes, int32_t* isLeaf);
+dsr_status dsr_mllr_get_stats(dsr_mllr*, int s, unsigned node, int row, double* G, double* z);
+dsr_status dsr_mllr_ttl_frames(const dsr_mllr*, int s, unsigned node, double* ttl);
+dsr_param_tree* dsr_mllr_tree(dsr_mllr*, int s);
+dsr_status dsr_mllr_get_transform(dsr_mllr*, int s, unsigned rc, double* W);
+dsr_status dsr_mllr_write(dsr_mllr*, int s, const char* fileName);
+dsr_status dsr_mllr_read(dsr_mllr*, int s, const char* fileName);
+dsr_status dsr_mllr_adapt(dsr_mllr*, int s, dsr_gmm* target);
+dsr_status dsr_mllr_adapt_all(dsr_mllr*, float* means_dev, void* stream);
+dsr_status dsr_mllr_reset_mean(dsr_mllr*, dsr_gmm* target);
+/* milliseconds of the last statistics + reduction, solve and transform kernels; 0 until timing is switched on */
+dsr_status dsr_mllr_set_timing(dsr_mllr*, int on);
+dsr_status dsr_mllr_kernel_ms(const dsr_mllr*, float ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

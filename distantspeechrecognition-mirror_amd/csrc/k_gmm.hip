@@ -18,6 +18,7 @@
 // This translation unit is compiled with -ffp-contract=off.
 #include "common.h"
 #include "gmm_model.h"
+#include "gmm_dist.h"
 #include <cmath>
 #include <string>
 
@@ -63,13 +64,9 @@ __global__ __launch_bounds__(256) void k_gmm_exact(const float* __restrict__ x, 
       const int a = off[kk] - g0, b = off[kk + 1] - g0;
       float minDist = 1E20f; int minIdx = 0;
       for (int g = a; g < b; g++) {
-        float dist = cst[g0 + g];
         const float* rv = sm + (size_t) g * DP; const float* cv = sv + (size_t) g * DP;
-#pragma unroll
-        for (int d = 0; d < DP; d++) {
-          // padded dimensions hold mu = x = iv = 0 and add exactly +0
-          { const float diff = __fsub_rn(rv[d], xr[d]); dist = __fadd_rn(dist, __fmul_rn(__fmul_rn(diff, diff), cv[d])); }
-        }
+        // padded dimensions hold mu = x = iv = 0 and add exactly +0
+        const float dist = gmm_dist_exact(cst[g0 + g], rv, cv, xr, DP);
         if (dist < minDist) { minDist = dist; minIdx = g - a; }
       }
       if (live) {

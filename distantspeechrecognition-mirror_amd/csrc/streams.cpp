@@ -2009,6 +2009,47 @@ dsr_status dsr_sad_hangover_decision_metric(dsr_stream* h, int* dm)
 { return guard([&] { HangoverOp* s = as_op<HangoverOp>(h, "hangover"); if (!dm) throw Error(DSR_E_PARAMETER, "null argument"); *dm = s->decision_metric(); }); }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// FeatureSpaceAdaptationFeature as a stream operator (asr/train/fsa.cc:247-280): every frame of the source under transform 0 of the adaptation
+// handle, which exists from distribSet() on.  The frames stay on the device, so a distribution set built on this stream decodes adapted
+// features without a host round trip.  A changed transform or shift shows after the next reset(), as every operator here recomputes then.
+namespace {
+struct FsaOp : dsr_stream {
+  int maxAccu = 1, maxTran = 1; dsr_fsa* h = nullptr;
+  ~FsaOp() override { dsr_fsa_destroy(h); }
+  void compute() override {
+    if (!h) throw Error(DSR_E_CONSISTENCY, "Must initialize the distribution set before using.");       // fsa.cc:251-252
+    alloc(ups[0]->nFrames);
+    ok(dsr_fsa_apply(h, ups[0]->d<float>(), nFrames, nullptr, dsr_fsa_shift(h), d<float>(), S0));
+  }
+  const void* next(int fx) override {
+    if (fx == frameX && frameX >= 0) return row(frameX);                                                // fsa.cc:249
+    if (!h) throw Error(DSR_E_CONSISTENCY, "Must initialize the distribution set before using.");
+    return dsr_stream::next(fx);
+  }
+};
+}  // namespace
+
+dsr_status dsr_fsa_feature_create(dsr_stream* src, int maxAccu, int maxTran, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    need(src, DSR_T_FLOAT, "FeatureSpaceAdaptationFeature");
+    if (!out) throw Error(DSR_E_PARAMETER, "null argument");
+    if (maxAccu < 1 || maxTran < 1) throw Error(DSR_E_PARAMETER, "%d accumulators, %d transformations", maxAccu, maxTran);
+    FsaOp* s = mk<FsaOp>(name, "FeatureSpaceAdaptationFeature", src->size_, DSR_T_FLOAT); s->maxAccu = maxAccu; s->maxTran = maxTran; s->add_up(src); *out = s;
+  });
+}
+dsr_status dsr_fsa_feature_distrib_set(dsr_stream* s, dsr_gmm* gmm)
+{
+  return guard([&] {
+    FsaOp* q = as_op<FsaOp>(s, "FeatureSpaceAdaptationFeature"); if (!gmm) throw Error(DSR_E_PARAMETER, "null argument");
+    if (q->size_ != dsr_gmm_dim(gmm)) throw Error(DSR_E_DIMENSION, "Feature and codebook dimensions (%d vs. %d) do not match.", q->size_, dsr_gmm_dim(gmm));
+    dsr_fsa* h = nullptr; ok(dsr_fsa_create(gmm, q->maxAccu, q->maxTran, &h));
+    dsr_fsa_destroy(q->h); q->h = h; q->ready = false;
+  });
+}
+dsr_fsa* dsr_fsa_feature_handle(dsr_stream* s) { FsaOp* q = dynamic_cast<FsaOp*>(s); return q ? q->h : nullptr; }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // ASR side of the boundary: the distribution set as the decoder sees it.  The reference decoder asks _dist->find(distX-1)->score(_frameX)
 // (asr/decoder/decoder.h:985); Distrib::score -> CodebookBasic::score pulls frame frameX of the feature stream and caches the codebook's
 // score for that frame (asr/gaussian/distribBasic.h:48-50,110-114, codebookBasic.cc:431-465).  Here a distribution set is a GMM model bound to

@@ -7,31 +7,13 @@
 // from the device, worked on and pushed back (csrc/train.h).  Compiled with -ffp-contract=off.
 #include "common.h"
 #include "train.h"
+#include "befile.h"
 #include <cmath>
 #include <map>
 
 using namespace dsr;
 
 namespace {
-
-// big-endian mach_ind_io (btk/common/mach_ind_io.cc:176-510)
-struct BEFile {
-  FILE* fp = nullptr;
-  BEFile(const char* name, const char* mode) { fp = fopen(name, mode); if (!fp) throw Error(DSR_E_IO, "Could not open file %s.", name); }
-  ~BEFile() { if (fp) fclose(fp); }
-  int i32() { unsigned char b[4] = {0, 0, 0, 0}; if (fread(b, 1, 4, fp) != 4) throw Error(DSR_E_IO, "premature end of file"); return (int) ((unsigned) b[0] << 24 | (unsigned) b[1] << 16 | (unsigned) b[2] << 8 | (unsigned) b[3]); }
-  float f32() { int i = i32(); float f; memcpy(&f, &i, 4); return f; }
-  std::string str()
-  {
-    unsigned char b[2] = {0, 0}; if (fread(b, 1, 2, fp) != 2) throw Error(DSR_E_IO, "premature end of file");
-    const int len = (short) ((unsigned) b[0] << 8 | (unsigned) b[1]); if (len < 0) throw Error(DSR_E_IO, "bad string length %d", len);
-    std::string s((size_t) len + 1, '\0'); if (fread(&s[0], (size_t) len + 1, 1, fp) != 1) throw Error(DSR_E_IO, "premature end of file");
-    s.resize(len); return s;
-  }
-  void w32(int v) { unsigned u = (unsigned) v; unsigned char b[4] = { (unsigned char) (u >> 24), (unsigned char) (u >> 16), (unsigned char) (u >> 8), (unsigned char) u }; fwrite(b, 1, 4, fp); }
-  void wf(float f) { int i; memcpy(&i, &f, 4); w32(i); }
-  void wstr(const std::string& s) { unsigned short u = (unsigned short) s.size(); unsigned char b[2] = { (unsigned char) (u >> 8), (unsigned char) u }; fwrite(b, 1, 2, fp); fwrite(s.c_str(), s.size() + 1, 1, fp); }
-};
 
 const char* kEndOfAccs = "EndOfAccumulators";              // distribTrain.h:230-233
 const int kCbMarker = 123456789, kDsMarker = 987654321;    // cT:309, dT:264

@@ -2217,6 +2217,151 @@ class Mllr:
         ms = (C.c_float * 3)(); check(_lib.dsr_mllr_kernel_ms(self.h, ms)); return ms[0], ms[1], ms[2]
 
 
+class Fsa:
+    """Feature-space adaptation (constrained MLLR) for several accumulators and transformations (csrc/k_fsa.hip, csrc/fsa.cpp; include/dsr.h
+    section 11): statistics on fp64 MFMA, Jacobi pseudo-inverses and the row updates on the device, the transform bit-exact.
+    Made from a Gmm, or around the handle a FeatureSpaceAdaptationFeature stream owns (handle=, owner=)."""
+
+    def __init__(self, gmm=None, nAccu=1, nTran=1, handle=None, owner=None):
+        L = load(); self._owner = owner
+        if handle is not None:
+            self.h = handle
+        else:
+            self.h = vp(); check(L.dsr_fsa_create(gmm.h, int(nAccu), int(nTran), C.byref(self.h)))
+        self.gmm = gmm; self.D = L.dsr_fsa_dim(self.h); self.nAccu = L.dsr_fsa_num_accus(self.h); self.nTran = L.dsr_fsa_num_transforms(self.h)
+
+    def __del__(self):
+        if _lib is not None and getattr(self, "h", None) and self._owner is None:
+            _lib.dsr_fsa_destroy(self.h)
+
+    def add(self, dsX):
+        check(_lib.dsr_fsa_add(self.h, int(dsX)))
+
+    def add_all(self):
+        check(_lib.dsr_fsa_add_all(self.h))
+
+    def set_top_n(self, topN):
+        check(_lib.dsr_fsa_set_top_n(self.h, int(topN)))
+
+    def top_n(self):
+        return _lib.dsr_fsa_top_n(self.h)
+
+    def set_shift(self, shift):
+        check(_lib.dsr_fsa_set_shift(self.h, float(shift)))
+
+    def shift(self):
+        return _lib.dsr_fsa_shift(self.h)
+
+    def count(self, accuX=0):
+        c = C.c_double(0.0); check(_lib.dsr_fsa_count(self.h, int(accuX), C.byref(c))); return c.value
+
+    def _frames(self, xScore, xSrc):
+        xSrc = xScore if xSrc is None else xSrc
+        for x in (xScore, xSrc):
+            assert x.is_cuda and x.is_contiguous() and x.dtype.is_floating_point and x.element_size() == 4 and x.shape[1] == self.D
+        assert xScore.shape[0] == xSrc.shape[0]
+        return xScore, xSrc
+
+    def accumulate(self, xScore, frame, dist, gamma, accu, xSrc=None, want_nearest=False):
+        """xScore, xSrc: cuda float32 [N][D] (xSrc None: the same frames); frame, dist, gamma, accu: host arrays [M] -> accepted items [nAccu]
+        (with want_nearest also the Gaussian each item chose inside its codebook, -1 for a distribution that is not switched on)"""
+        xScore, xSrc = self._frames(xScore, xSrc)
+        fr = _np(frame, np.int32); ds = _np(dist, np.int32); ga = _np(gamma, np.float32); ac = _np(accu, np.int32); M = len(fr)
+        assert len(ds) == M and len(ga) == M and len(ac) == M
+        acc = np.zeros(self.nAccu, np.int64); near = np.full(M, -1, np.int32) if want_nearest else None
+        check(_lib.dsr_fsa_accumulate(self.h, _dev(xScore), _dev(xSrc), xScore.shape[0], _ptr(fr), _ptr(ds), _ptr(ga), _ptr(ac), M, _ptr(acc),
+                                      _ptr(near) if want_nearest else None, cur_stream()))
+        return (acc, near) if want_nearest else acc
+
+    def accumulate_path(self, xScore, distIds, accuX=0, factor=1.0, xSrc=None):
+        """distIds: one distribution per frame, negative for a name the set does not know -> the frames the reference reports"""
+        xScore, xSrc = self._frames(xScore, xSrc); ids = _np(distIds, np.int32); n = C.c_uint(0)
+        check(_lib.dsr_fsa_accumulate_path(self.h, _dev(xScore), _dev(xSrc), xScore.shape[0], _ptr(ids), len(ids), int(accuX), float(factor), C.byref(n), cur_stream()))
+        return n.value
+
+    def accumulate_lattice(self, lattice, xScore, accuX=0, factor=1.0, xSrc=None):
+        """lattice: a Lattice (after gammaProbs) -> the number of links accumulated"""
+        xScore, xSrc = self._frames(xScore, xSrc); n = C.c_uint(0)
+        check(_lib.dsr_fsa_accumulate_lattice(self.h, lattice.h, _dev(xScore), _dev(xSrc), xScore.shape[0], int(accuX), float(factor), C.byref(n), cur_stream()))
+        return n.value
+
+    def zero(self, accuX=0):
+        check(_lib.dsr_fsa_zero(self.h, int(accuX)))
+
+    def scale(self, scale, accuX=0):
+        check(_lib.dsr_fsa_scale(self.h, float(scale), int(accuX)))
+
+    def add_accu(self, accuX, accuY, factor=1.0):
+        check(_lib.dsr_fsa_add_accu(self.h, int(accuX), int(accuY), float(factor)))
+
+    def get_accu(self, accuX=0):
+        """-> dict(count, beta (float32), z [D][D + 1], G [D][D + 1][D + 1] with the triangle as the reference holds it)"""
+        D = self.D; c = C.c_double(0.0); b = C.c_float(0.0); z = np.zeros((D, D + 1)); G = np.zeros((D, D + 1, D + 1))
+        check(_lib.dsr_fsa_get_accu(self.h, int(accuX), C.byref(c), C.byref(b), _ptr(z), _ptr(G)))
+        return dict(count=c.value, beta=np.float32(b.value), z=z, G=G)
+
+    def set_accu(self, accuX=0, count=None, beta=None, z=None, G=None):
+        D = self.D
+        c = C.byref(C.c_double(float(count))) if count is not None else None
+        b = C.byref(C.c_float(float(beta))) if beta is not None else None
+        if z is not None:
+            z = _np(z, np.float64); assert z.shape == (D, D + 1)
+        if G is not None:
+            G = _np(G, np.float64); assert G.shape == (D, D + 1, D + 1)
+        check(_lib.dsr_fsa_set_accu(self.h, int(accuX), c, b, _ptr(z) if z is not None else None, _ptr(G) if G is not None else None))
+
+    def save_accu(self, fileName, accuX=0):
+        check(_lib.dsr_fsa_save_accu(self.h, fileName.encode(), int(accuX)))
+
+    def load_accu(self, fileName, accuX=0, factor=1.0):
+        check(_lib.dsr_fsa_load_accu(self.h, fileName.encode(), int(accuX), float(factor)))
+
+    def estimate(self, iterN=1, accuX=0, tranX=0):
+        """accuX, tranX: ints or equally long lists: the pairs are estimated concurrently"""
+        a = _np(np.atleast_1d(accuX), np.int32); t = _np(np.atleast_1d(tranX), np.int32); assert len(a) == len(t)
+        check(_lib.dsr_fsa_estimate(self.h, int(iterN), _ptr(a), _ptr(t), len(a), cur_stream()))
+
+    def transform_status(self, tranX=0):
+        return _lib.dsr_fsa_transform_status(self.h, int(tranX))
+
+    def transform(self, tranX=0):
+        W = np.zeros((self.D, self.D + 1)); check(_lib.dsr_fsa_get_transform(self.h, int(tranX), _ptr(W))); return W
+
+    def set_transform(self, W, tranX=0):
+        W = _np(W, np.float64); assert W.shape == (self.D, self.D + 1)
+        check(_lib.dsr_fsa_set_transform(self.h, int(tranX), _ptr(W)))
+
+    def clear(self, tranX=0):
+        check(_lib.dsr_fsa_clear(self.h, int(tranX)))
+
+    def compare(self, tranX, tranY):
+        s = C.c_float(0.0); check(_lib.dsr_fsa_compare(self.h, int(tranX), int(tranY), C.byref(s))); return np.float32(s.value)
+
+    def save(self, fileName, tranX=0):
+        check(_lib.dsr_fsa_save(self.h, fileName.encode(), int(tranX)))
+
+    def load(self, fileName, tranX=0):
+        check(_lib.dsr_fsa_load(self.h, fileName.encode(), int(tranX)))
+
+    def apply(self, x, tranOfRow=None, shift=1.0, out=None):
+        """x: cuda float32 [N][D]; tranOfRow: cuda int32 [N] or None (transformation 0) -> cuda float32 [N][D]"""
+        import torch
+        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.shape[1] == self.D
+        if out is None:
+            out = torch.empty_like(x)
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.shape == x.shape
+        if tranOfRow is not None:
+            assert tranOfRow.is_cuda and tranOfRow.is_contiguous() and tranOfRow.dtype == torch.int32 and tranOfRow.shape[0] == x.shape[0]
+        check(_lib.dsr_fsa_apply(self.h, _dev(x), x.shape[0], _dev(tranOfRow) if tranOfRow is not None else None, float(shift), _dev(out), cur_stream()))
+        return out
+
+    def set_timing(self, on=True):
+        check(_lib.dsr_fsa_set_timing(self.h, int(on)))
+
+    def kernel_ms(self):
+        ms = (C.c_float * 5)(); check(_lib.dsr_fsa_kernel_ms(self.h, ms)); return tuple(ms)
+
+
 class Wfst:
     """WFSTFlyWeight (asr/decoder/wfstFlyWeight.h:47-119)."""
 

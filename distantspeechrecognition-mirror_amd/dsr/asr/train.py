@@ -14,6 +14,7 @@ tensor handed to setFeatures() (what a pipeline that already holds its features 
 import numpy as np
 
 from .. import _capi as K
+from ..btk.stream import FeatureStreamPtr, _new
 from .adapt import CodebookSetAdaptPtr, TransformerTreePtr
 from .gaussian import DistribSetBasicPtr
 
@@ -188,3 +189,127 @@ class EstimatorTreeMLLRPtr(TransformerTreePtr):
 def estimateAdaptationParameters(tree):
     """estimateAdapt.cc:3064-3078: an MLLR parameter tree is cleared, then every leaf is estimated with back-off"""
     tree._estimate()
+
+
+class FeatureSpaceAdaptationFeaturePtr(FeatureStreamPtr):
+    """FeatureSpaceAdaptationFeature(src, maxAccu = 1, maxTran = 1, nm) (asr/train/fsa.h, train.i:531-590) over dsr_fsa_* (include/dsr.h section
+    11): a feature stream that delivers src under transformation 0, and the estimator of such transformations (constrained MLLR).
+
+        fsa = FeatureSpaceAdaptationFeaturePtr(src); fsa.distribSet(dss); fsa.addAll()
+        fsa.accumulate(decoder.bestPath()); fsa.estimate(10)          # then decode again from a distribution set built on fsa
+
+    accumulate() takes the scoring frames from the feature stream of the distribution set's codebooks and the statistics' frames from src, both
+    pulled from frame 0 after a reset(); setFeatures() hands over frames that are on the device already."""
+
+    def __init__(self, src, maxAccu=1, maxTran=1, nm="FeatureSpaceAdaptationFeature"):
+        h, _ = _new(K.load().dsr_fsa_feature_create, src._h, int(maxAccu), int(maxTran), nm.encode())
+        FeatureStreamPtr.__init__(self, h, keep=(src,))
+        self._src, self._dss, self._fsa, self._feats = src, None, None, None
+
+    def _need(self):
+        if self._fsa is None:
+            raise K.DsrError(K.E_CONSISTENCY, "Must initialize the distribution set before using.")
+        return self._fsa
+
+    def distribSet(self, dss):
+        """distribSet(dssP) (fsa.h): the adaptation handle is made for the set's model"""
+        import ctypes as C
+        K.check(K.load().dsr_fsa_feature_distrib_set(self._h, dss.gmm.h))
+        self._dss = dss; self._fsa = K.Fsa(gmm=dss.gmm, handle=C.c_void_p(K.load().dsr_fsa_feature_handle(self._h)), owner=self)
+
+    def handle(self):
+        """the dsr._capi.Fsa of this stream (the batch entries: accumulate over items, estimate over pairs, apply with per-row transforms)"""
+        return self._need()
+
+    def topN(self):
+        return self._need().top_n()
+
+    def setTopN(self, topN):
+        self._need().set_top_n(topN)
+
+    def count(self, accuX=0):
+        return int(self._need().count(accuX))
+
+    def shift(self):
+        return self._need().shift()
+
+    def setShift(self, shift):
+        self._need().set_shift(shift)
+
+    def setFeatures(self, xScore, xSrc=None):
+        """frames already on the device, cuda float32 [T][dimN]: the codebooks' frames and src's (None, None: pull them from the streams again)"""
+        self._feats = None if xScore is None else (xScore, xScore if xSrc is None else xSrc)
+
+    def _frames(self, T):
+        import torch
+        if self._feats is not None:
+            return self._feats
+        def pull(s):
+            s.reset(); rows = [np.array(s.next(t), np.float32) for t in range(T)]
+            return torch.from_numpy(np.stack(rows) if rows else np.zeros((0, self.size()), np.float32)).cuda().contiguous()
+        xSrc = pull(self._src)
+        feat = self._dss._feat
+        return (xSrc if feat is self._src else pull(feat)), xSrc
+
+    def accumulate(self, path, accuX=0, factor=1.0):
+        """accumulate(path, accuX, factor) (fsa.cc:282-297): path = DecoderFlyWeightPtr.bestPath(); a name the set does not know is passed over
+        WITHOUT advancing the frame, as there"""
+        f = self._need(); ids = []
+        for n in path:
+            if isinstance(n, str):
+                try:
+                    ids.append(self._dss.index(n))
+                except K.DsrError:
+                    ids.append(-1)
+            else:
+                ids.append(int(n))
+        xScore, xSrc = self._frames(sum(1 for i in ids if i >= 0))
+        n = f.accumulate_path(xScore, ids, accuX, factor, xSrc=xSrc)
+        print("Accumulated %d frames." % n)
+        return n
+
+    def accumulateLattice(self, lat, accuX=0, factor=1.0):
+        """accumulateLattice(lat, accuX, factor) (fsa.cc:299-321): every second frame of a link, as there; lat: a LatticePtr after gammaProbs"""
+        f = self._need(); L = getattr(lat, "_lat", lat)
+        ends = L.data["end"][L.data["in"] != 0]
+        T = int(ends.max()) + 1 if len(ends) else 0
+        xScore, xSrc = self._frames(T)
+        n = f.accumulate_lattice(L, xScore, accuX, factor, xSrc=xSrc)
+        print("Finished accumulation for %d links." % n)
+        return n
+
+    def zeroAccu(self, accuX=0):
+        self._need().zero(accuX)
+
+    def scaleAccu(self, scale, accuX=0):
+        self._need().scale(scale, accuX)
+
+    def addAccu(self, accuX, accuY, factor=1.0):
+        self._need().add_accu(accuX, accuY, factor)
+
+    def add(self, dsX):
+        self._need().add(dsX)
+
+    def addAll(self):
+        self._need().add_all()
+
+    def estimate(self, iterN=1, accuX=0, tranX=0):
+        self._need().estimate(iterN, accuX, tranX)
+
+    def clear(self, tranX=0):
+        self._need().clear(tranX)
+
+    def compareTransform(self, tranX, tranY):
+        return float(self._need().compare(tranX, tranY))
+
+    def saveAccu(self, name, accuX=0):
+        self._need().save_accu(name, accuX)
+
+    def loadAccu(self, name, accuX=0, factor=1.0):
+        self._need().load_accu(name, accuX, factor)
+
+    def save(self, name, tranX=0):
+        self._need().save(name, tranX)
+
+    def load(self, name, tranX=0):
+        self._need().load(name, tranX)

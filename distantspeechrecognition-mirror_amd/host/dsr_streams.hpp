@@ -1439,3 +1439,61 @@ class EstimatorTreeMLLR : public TransformerTree {
 };
 typedef std::shared_ptr<EstimatorTreeMLLR> EstimatorTreeMLLRPtr;
 inline void estimateAdaptationParameters(EstimatorTreeMLLRPtr& tree) { tree->estimate(); }
+
+// ---- asr/train/fsa.h, train.i:531-590: FeatureSpaceAdaptationFeature(src, maxAccu, maxTran, nm), feature-space adaptation (constrained MLLR).
+// A feature stream that delivers src under transformation 0, and the estimator of such transformations over dsr_fsa_* (include/dsr.h section 11).
+// accumulate() pulls the scoring frames from the feature stream of the distribution set and the statistics' frames from src, both from frame 0
+// after a reset().
+class FeatureSpaceAdaptationFeature : public VectorFloatFeatureStream {
+ public:
+  FeatureSpaceAdaptationFeature(VectorFloatFeatureStreamPtr& src, unsigned maxAccu = 1, unsigned maxTran = 1, const String& nm = "FeatureSpaceAdaptationFeature")
+    : _s(src) { dsr_stream* h = 0; dsr_throw(dsr_fsa_feature_create(src->handle(), (int) maxAccu, (int) maxTran, nm.c_str(), &h)); this->adopt(h); }
+  void distribSet(DistribSetBasicPtr& dss) { dsr_throw(dsr_fsa_feature_distrib_set(_h, dss->gmm())); _dss = dss; }
+  dsr_fsa* fsaHandle() const { dsr_fsa* f = dsr_fsa_feature_handle(_h); if (!f) throw jconsistency_error("Must initialize the distribution set before using."); return f; }
+  unsigned topN() const { return dsr_fsa_top_n(fsaHandle()); }
+  void setTopN(unsigned topN) { dsr_throw(dsr_fsa_set_top_n(fsaHandle(), topN)); }
+  unsigned count(unsigned accuX = 0) const { double c = 0.0; dsr_throw(dsr_fsa_count(fsaHandle(), (int) accuX, &c)); return (unsigned) c; }
+  float shift() const { return dsr_fsa_shift(fsaHandle()); }
+  void setShift(float shift) { dsr_throw(dsr_fsa_set_shift(fsaHandle(), shift)); }
+  void accumulate(const DistribPath& path, unsigned accuX = 0, float factor = 1.0f) {        // fsa.cc:282-297: an unknown name does not advance the frame
+    dsr_fsa* f = fsaHandle(); std::vector<int32_t> ids(path.size()); size_t T = 0;
+    for (size_t i = 0; i < path.size(); i++) { int x = -1; if (dsr_distribset_find(_dss->handle(), path[i].c_str(), &x) != DSR_OK) x = -1; ids[i] = x; if (x >= 0) T++; }
+    const float *xs = 0, *xr = 0; frames(T, &xs, &xr);
+    unsigned n = 0; dsr_throw(dsr_fsa_accumulate_path(f, xs, xr, (int64_t) T, ids.data(), (int64_t) ids.size(), (int) accuX, factor, &n, 0));
+    printf("Accumulated %u frames.\n", n); fflush(stdout);
+  }
+  void accumulateLattice(LatticePtr& lat, unsigned accuX = 0, float factor = 1.0f) {         // fsa.cc:299-321: every second frame of a link
+    (void) fsaHandle(); const int E = dsr_lattice_num_edges(lat->handle()); std::vector<int32_t> end((size_t) (E > 0 ? E : 1)); std::vector<uint32_t> in(end.size());
+    dsr_throw(dsr_lattice_get(lat->handle(), 0, 0, 0, in.data(), 0, 0, end.data(), 0, 0));
+    int T = 0; for (int e = 0; e < E; e++) if (in[(size_t) e] != 0 && end[(size_t) e] + 1 > T) T = end[(size_t) e] + 1;
+    const float *xs = 0, *xr = 0; frames((size_t) T, &xs, &xr);
+    unsigned n = 0; dsr_throw(dsr_fsa_accumulate_lattice(fsaHandle(), lat->handle(), xs, xr, T, (int) accuX, factor, &n, 0));
+    printf("Finished accumulation for %d links.\n", n); fflush(stdout);
+  }
+  void zeroAccu(unsigned accuX = 0) { dsr_throw(dsr_fsa_zero(fsaHandle(), (int) accuX)); }
+  void scaleAccu(float scale, unsigned accuX = 0) { dsr_throw(dsr_fsa_scale(fsaHandle(), scale, (int) accuX)); }
+  void addAccu(unsigned accuX, unsigned accuY, float factor = 1.0f) { dsr_throw(dsr_fsa_add_accu(fsaHandle(), (int) accuX, (int) accuY, factor)); }
+  void add(unsigned dsX) { dsr_throw(dsr_fsa_add(fsaHandle(), (int) dsX)); }
+  void addAll() { dsr_throw(dsr_fsa_add_all(fsaHandle())); }
+  void estimate(unsigned iterN = 1, unsigned accuX = 0, unsigned tranX = 0) {
+    const int32_t a = (int32_t) accuX, t = (int32_t) tranX; dsr_throw(dsr_fsa_estimate(fsaHandle(), (int) iterN, &a, &t, 1, 0));
+  }
+  void clear(unsigned tranX = 0) { dsr_throw(dsr_fsa_clear(fsaHandle(), (int) tranX)); }
+  float compareTransform(unsigned tranX, unsigned tranY) { float s = 0.0f; dsr_throw(dsr_fsa_compare(fsaHandle(), (int) tranX, (int) tranY, &s)); return s; }
+  void saveAccu(const String& name, unsigned accuX = 0) { dsr_throw(dsr_fsa_save_accu(fsaHandle(), name.c_str(), (int) accuX)); }
+  void loadAccu(const String& name, unsigned accuX = 0, float factor = 1.0f) { dsr_throw(dsr_fsa_load_accu(fsaHandle(), name.c_str(), (int) accuX, factor)); }
+  void save(const String& name, unsigned tranX = 0) { dsr_throw(dsr_fsa_save(fsaHandle(), name.c_str(), (int) tranX)); }
+  void load(const String& name, unsigned tranX = 0) { dsr_throw(dsr_fsa_load(fsaHandle(), name.c_str(), (int) tranX)); }
+ private:
+  void frames(size_t T, const float** xs, const float** xr) {             // frames 0..T-1 of both streams, on the device
+    const size_t D = size(); std::vector<float> a(T * D + 1), b(T * D + 1);
+    _s->reset();
+    for (size_t t = 0; t < T; t++) { const float* p = _s->next((int) t); for (size_t d = 0; d < D; d++) b[t * D + d] = p[d]; }
+    VectorFloatFeatureStreamPtr& f = _dss->featureStream();
+    if (f.get() == _s.get()) a = b;
+    else { f->reset(); for (size_t t = 0; t < T; t++) { const float* p = f->next((int) t); for (size_t d = 0; d < D; d++) a[t * D + d] = p[d]; } }
+    dsr_throw(dsr_fsa_upload_features(fsaHandle(), a.data(), b.data(), (int64_t) T, xs, xr));
+  }
+  VectorFloatFeatureStreamPtr _s; DistribSetBasicPtr _dss;
+};
+typedef std::shared_ptr<FeatureSpaceAdaptationFeature> FeatureSpaceAdaptationFeaturePtr;

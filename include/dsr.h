@@ -2028,6 +2028,101 @@ dsr_status dsr_mllr_reset_mean(dsr_mllr*, dsr_gmm* target);
 dsr_status dsr_mllr_set_timing(dsr_mllr*, int on);
 dsr_status dsr_mllr_kernel_ms(const dsr_mllr*, float ms[3]);
 
+/* =====================================================================================
+ * 11. Feature-space adaptation (constrained MLLR)
+ *    Replaces FeatureSpaceAdaptationFeature (asr/train/fsa.{h,cc}, "fsa"; train.i:531-590): one affine transform W = (b | A) [dimN][dimN + 1] of
+ *    the features per transformation slot, estimated from statistics gathered with the nearest Gaussian of each (frame, distribution) item.
+ *    One item is _accuOne(dsX, frameX, accuX, gamma) (fsa:187-245): distributions not switched on by add / add_all are ignored before anything
+ *    is counted (nothing is on at first); count++ and the float sum beta += gamma in item order; g = the nearest Gaussian of the codebook under
+ *    the SCORING frame (the one-hot addCount of CodebookBasic::_scoreOpt, codebookBasic.cc:431-554: the argmin of scoring mode 0, found with the
+ *    model's scoring tables); with xi = (1, x) of the SOURCE frame (the untransformed _src, fsa:195)
+ *        z[i][.] += (gamma float(mean_gi iv_gi)) xi        G_i[j][k] += (gamma iv_gi) xi_j xi_k   for k <= j
+ *    in fp64.  Only the lower triangle and column 0 of G_i are written (fsa:235-241).  The sums over the items of a call are an fp64 MFMA
+ *    contraction in a fixed order (no atomics: the same call twice gives the same bits); they differ from the reference's sequential sums by
+ *    fp64 reordering and by its roundings of c xi_j and (c xi_j) xi_k, which the contraction skips.  The means and inverse variances of the
+ *    statistics are copied when the handle is made; the model must outlive the handle.  dimN <= 80.  _dimN, in the reference the feature
+ *    length of the codebook with the most Gaussians (fsa:48-54), is the model's dimN: the codebooks of a dsr_gmm share it, so the
+ *    jdimension_error of add (fsa:165-167) cannot arise.  The constructor's use of _maxAccu before it is set (fsa:36) is not reproduced.
+ *   create             FeatureSpaceAdaptationFeature(src, maxAccu, maxTran) + _initialize (fsa:32-112): zeroed accumulators, identity transforms
+ *   add / add_all      fsa:159-176; DSR_E_INDEX for a distribution outside the set
+ *   set_top_n          setTopN: kept for the interface; the entries after the first are ties at addCount 0 and add c = 0 terms (fsa:203-244).
+ *                      DSR_E_INDEX for topN beyond refN of the largest codebook, where the reference reads past its arrays
+ *   accumulate         M items over xScore_dev, xSrc_dev [N][dimN] fp32 (they may be the same array) with host arrays frame, dist, gamma, accu [M];
+ *                      accepted [nAccu] or NULL: the items each accumulator took; nearest [M] or NULL: the Gaussian (inside its codebook) each item
+ *                      chose, -1 for a distribution that is not switched on.  DSR_E_INDEX: a frame, distribution or accumulator out of range
+ *   accumulate_path    accumulate(path, accuX, factor) (fsa:282-297): distIds [pathLen], a negative id is a name that was not found and does NOT
+ *                      advance the frame index, as there; *framesN = the frames the reference reports ("Accumulated n frames.")
+ *   accumulate_lattice accumulateLattice(lat, accuX, factor) (fsa:299-321) with the lattice's current gammas, links in the order of
+ *                      dsr_train_accumulate_lattice: input 0 and gamma > 10 are skipped, postProb = float(factor exp(-gamma)), and -- the loop
+ *                      increments frameX in its header and again in the call (fsa:317-318) -- every SECOND frame start, start + 2, ... of a link
+ *   zero / scale / add_accu   zeroAccu, scaleAccu, addAccu (fsa:435-465, 637-650) as written
+ *   get_accu / set_accu       count, beta, z [dimN][dimN + 1], G [dimN][dimN + 1][dimN + 1] with the triangle as the reference holds it
+ *   save_accu / load_accu     magic "SAS", big-endian floats (fsa:505-583): count and every element rounded to float, the upper triangle as it
+ *                      stands; loading ADDS factor x the file.  DSR_E_CONSISTENCY without the magic, DSR_E_DIMENSION for another dimN
+ *   estimate           estimate(iterN, accuX, tranX) (fsa:363-433) for n (accumulator, transformation) pairs at once, each from its CURRENT
+ *                      transform: G_i^+ with singular values below 1e-7 of the largest dropped (a Jacobi eigen-decomposition), then iterN sweeps of
+ *                      row updates with p = det A . A^-1[:, i] (the reference takes |det| from an SVD of A per row; the sign cancels in w_i).
+ *                      DSR_E_PARAMETER when a transformation is named twice.  A pair whose statistics or result are not finite (fewer than
+ *                      dimN + 1 frames: the reference stores NaN), whose decomposition does not converge or whose ||A||_F ||A^-1||_F reaches 1e7
+ *                      (the reference's 1e-7 rule in _calcCofactor could then have dropped a singular value of A) keeps its transform and is
+ *                      flagged (transform_status); the others are done and the call returns DSR_E_CONSISTENCY, as dsr_mllr_estimate does
+ *   get / set_transform, clear (fsa:467-481), compare (compareTransform, fsa:483-503: squares over columns 0 .. dimN - 1 as written, float)
+ *   save / load        magic "SAW" (fsa:585-635); DSR_E_IO without the magic, DSR_E_DIMENSION for another dimN
+ *   apply              next (fsa:247-280) for N frames: out = float(shift w[d][0] + sum_i w[d][i + 1] x_i), a double sum with i ascending; for
+ *                      shift == -1 float(w[d][0] + x_d).  tranOfRow_dev int32 [N] (device) names each row's transformation -- what a batch of
+ *                      mixed speakers needs --, NULL is transformation 0; a row whose index is out of range becomes NaN
+ *   kernel_ms          milliseconds of the last nearest-Gaussian, statistics + reduction, eigen-decomposition, row-update and apply kernels
+ * ===================================================================================== */
+typedef struct dsr_fsa dsr_fsa;
+dsr_status dsr_fsa_create(dsr_gmm*, int nAccu, int nTran, dsr_fsa** out);
+void dsr_fsa_destroy(dsr_fsa*);
+int dsr_fsa_dim(const dsr_fsa*);
+int dsr_fsa_num_accus(const dsr_fsa*);
+int dsr_fsa_num_transforms(const dsr_fsa*);
+dsr_status dsr_fsa_add(dsr_fsa*, int dsX);
+dsr_status dsr_fsa_add_all(dsr_fsa*);
+dsr_status dsr_fsa_set_top_n(dsr_fsa*, unsigned topN);
+unsigned dsr_fsa_top_n(const dsr_fsa*);
+dsr_status dsr_fsa_set_shift(dsr_fsa*, float shift);
+float dsr_fsa_shift(const dsr_fsa*);
+dsr_status dsr_fsa_count(const dsr_fsa*, int accuX, double* count);
+dsr_status dsr_fsa_accumulate(dsr_fsa*, const float* xScore_dev, const float* xSrc_dev, int64_t N, const int32_t* frame, const int32_t* dist,
+                              const float* gamma, const int32_t* accu, int64_t M, int64_t* accepted, int32_t* nearest, void* stream);
+dsr_status dsr_fsa_accumulate_path(dsr_fsa*, const float* xScore_dev, const float* xSrc_dev, int64_t T, const int32_t* distIds, int64_t pathLen,
+                                   int accuX, float factor, unsigned* framesN, void* stream);
+dsr_status dsr_fsa_accumulate_lattice(dsr_fsa*, dsr_lattice*, const float* xScore_dev, const float* xSrc_dev, int64_t T, int accuX, float factor,
+                                      unsigned* linksN, void* stream);
+/* for callers without a HIP binding of their own (host/dsr_streams.hpp): N frames of dimN floats each from host memory into buffers the handle
+ * owns; the device pointers stay valid until the next upload or the handle's end */
+dsr_status dsr_fsa_upload_features(dsr_fsa*, const float* xScore_host, const float* xSrc_host, int64_t N, const float** xScore_dev, const float** xSrc_dev);
+dsr_status dsr_fsa_zero(dsr_fsa*, int accuX);
+dsr_status dsr_fsa_scale(dsr_fsa*, float scale, int accuX);
+dsr_status dsr_fsa_add_accu(dsr_fsa*, int accuX, int accuY, float factor);
+dsr_status dsr_fsa_get_accu(const dsr_fsa*, int accuX, double* count, float* beta, double* z, double* G);
+dsr_status dsr_fsa_set_accu(dsr_fsa*, int accuX, const double* count, const float* beta, const double* z, const double* G);
+dsr_status dsr_fsa_save_accu(const dsr_fsa*, const char* fileName, int accuX);
+dsr_status dsr_fsa_load_accu(dsr_fsa*, const char* fileName, int accuX, float factor);
+dsr_status dsr_fsa_estimate(dsr_fsa*, int iterN, const int32_t* accuX, const int32_t* tranX, int n, void* stream);
+int dsr_fsa_transform_status(const dsr_fsa*, int tranX);
+dsr_status dsr_fsa_get_transform(const dsr_fsa*, int tranX, double* W);
+dsr_status dsr_fsa_set_transform(dsr_fsa*, int tranX, const double* W);
+dsr_status dsr_fsa_clear(dsr_fsa*, int tranX);
+dsr_status dsr_fsa_compare(const dsr_fsa*, int tranX, int tranY, float* sumOfSquares);
+dsr_status dsr_fsa_save(const dsr_fsa*, const char* fileName, int tranX);
+dsr_status dsr_fsa_load(dsr_fsa*, const char* fileName, int tranX);
+dsr_status dsr_fsa_apply(dsr_fsa*, const float* x_dev, int64_t N, const int32_t* tranOfRow_dev, float shift, float* out_dev, void* stream);
+dsr_status dsr_fsa_set_timing(dsr_fsa*, int on);
+dsr_status dsr_fsa_kernel_ms(const dsr_fsa*, float ms[5]);
+/* The stream operator (a VectorFloatFeatureStream, fsa.h): src under transformation 0 and the handle's shift, frames kept on the device, so
+ * dsr_distribset_create(gmm, stream, ...) + dsr_decoder_decode_stream decode adapted frames without a host round trip.
+ *   distrib_set   distribSet(dss): makes the adaptation handle (zeroed accumulators, identity transforms) for the model
+ *   handle        the operator's dsr_fsa, owned by the stream; NULL before distrib_set
+ * next() before distrib_set is DSR_E_CONSISTENCY (fsa:251-252), an out-of-order frameX DSR_E_INDEX (fsa:254-255).  A new transform or shift
+ * shows after the next reset(). */
+dsr_status dsr_fsa_feature_create(dsr_stream* src, int maxAccu, int maxTran, const char* name, dsr_stream** out);
+dsr_status dsr_fsa_feature_distrib_set(dsr_stream*, dsr_gmm*);
+dsr_fsa* dsr_fsa_feature_handle(dsr_stream*);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,8 @@ struct DecoderState {
   DevBuf<long long> d_prof; DevBuf<dsr_decode_result> d_res; DevBuf<int> d_arcs; DevBuf<unsigned> d_words;
   long arenaCap = 0; int initial = 0; unsigned tokenMemoryLimit = 0;
   long lastPoolCap = 0;
+  hipEvent_t evTrace = nullptr;                                              // recorded behind this decoder's k_traceback (order_behind_last_traceback)
+  DevBuf<TraceHead> d_heads; DevBuf<int> d_hopRec, d_hopOff;                 // k_traceback: the head of every utterance's best path; its hop scratch, per utterance
   DevBuf<SegState> d_segState; DevBuf<int> d_segDone; DevBuf<unsigned long long> d_poolNext; DevBuf<TokA> d_saveA; DevBuf<TokB> d_saveB;   // time slicing (DecDev::segFrames)
   // DecoderWordTrace mode (cfg.wordTrace): scratch of k_wordtrace.hip
   DevBuf<WTok> w_tok; DevBuf<WCand> w_cand; DevBuf<int> w_tokOff, w_rank; DevBuf<unsigned long long> w_best; DevBuf<unsigned> w_first; DevBuf<int4> w_traces; size_t w_tablesFor = 0;
@@ -71,7 +73,48 @@ dsr_status dsr_decoder_create(const dsr_decoder_cfg* cfg, dsr_decoder** out)
     *out = d;
   });
 }
-void dsr_decoder_destroy(dsr_decoder* d) { if (d && d->evDone) (void) hipEventDestroy(d->evDone); delete d; }
+// A decode's workgroups take their CUs whole (registers and LDS), and a decode queued on another stream moves in as the one before frees them: by the time that
+// one has ended and its k_traceback may start, a grid of one workgroup per CU has left no room for even one small wave, and the finished decode's paths would wait
+// for the whole next decode (measured with two pipes: results 87 ms late on every other step).  So a decode kernel whose grid fills the device on its own -- at least
+// as many workgroups as the device has CUs -- is ordered behind the traceback launched last on the device, whichever decoder and stream it came from: it gives up the
+// start in the other decode's ragged end (decodes of that size on one device do not overlap any more), the traceback runs on an empty device for half a millisecond.
+// A smaller grid leaves CUs free, the traceback's waves find room there, and such decodes run side by side as before.  (The event may be this decoder's own, from a
+// launch on another stream: that decode has been collected, the event is complete, the wait is none.)
+namespace {
+std::mutex g_traceMu; std::map<int, std::pair<const dsr_decoder*, hipEvent_t>> g_lastTrace; std::map<int, int> g_cuCount;     // by device id
+void order_behind_last_traceback(int slots, hipStream_t st)
+{
+  std::lock_guard<std::mutex> lock(g_traceMu);
+  int dev = 0; DSR_HIP(hipGetDevice(&dev));
+  auto cu = g_cuCount.find(dev);
+  if (cu == g_cuCount.end()) { int n = 0; DSR_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev)); cu = g_cuCount.emplace(dev, n).first; }
+  if (slots < cu->second) return;
+  const auto it = g_lastTrace.find(dev);
+  if (it != g_lastTrace.end()) DSR_HIP(hipStreamWaitEvent(st, it->second.second, 0));
+}
+void publish_traceback(dsr_decoder* d, hipStream_t st)
+{
+  std::lock_guard<std::mutex> lock(g_traceMu);
+  if (!d->evTrace) DSR_HIP(hipEventCreateWithFlags(&d->evTrace, hipEventDisableTiming));
+  DSR_HIP(hipEventRecord(d->evTrace, st));
+  int dev = 0; DSR_HIP(hipGetDevice(&dev));
+  g_lastTrace[dev] = std::make_pair((const dsr_decoder*) d, d->evTrace);
+}
+void forget_traceback(const dsr_decoder* d)
+{
+  std::lock_guard<std::mutex> lock(g_traceMu);
+  for (auto it = g_lastTrace.begin(); it != g_lastTrace.end(); ) { if (it->second.first == d) it = g_lastTrace.erase(it); else ++it; }
+}
+}  // namespace
+
+void dsr_decoder_destroy(dsr_decoder* d)
+{
+  if (!d) return;
+  forget_traceback(d);
+  if (d->evDone) (void) hipEventDestroy(d->evDone);
+  if (d->evTrace) (void) hipEventDestroy(d->evTrace);
+  delete d;
+}
 
 dsr_status dsr_decoder_set(dsr_decoder* d, const dsr_wfst* g)
 {
@@ -306,6 +349,7 @@ static VitArgs fill_vit_args(dsr_decoder* d, const DecodePlan& P, const VitEnv& 
   d->d_res.reserve(U);
   if (wantPaths) { d->d_arcs.reserve((size_t) U * (maxPath > 0 ? maxPath : 1)); d->d_words.reserve((size_t) U * (maxPath > 0 ? maxPath : 1)); }
   DSR_HIP(hipMemsetAsync(d->d_queue.p, 0, 8 * sizeof(int), st));
+  d->d_heads.reserve(U); DSR_HIP(hipMemsetAsync(d->d_heads.p, 0xFF, sizeof(TraceHead) * (size_t) U, st));      // every head empty: one the kernel does not write is not followed
   if (d->dumpOn) {
     d->dumpCap = (long) d->cfg.maxActive * 64 < (long) 1 << 26 ? (long) 1 << 24 : (long) 1 << 26;
     d->d_dumpFrameOff.reserve(Tmax + 2); d->d_dumpCount.reserve(2);
@@ -353,6 +397,28 @@ static VitArgs fill_vit_args(dsr_decoder* d, const DecodePlan& P, const VitEnv& 
   A.scores = score; A.nframesArr = nframes; A.U = U; A.Tmax = Tmax; A.nDist = nDist; A.res = d->d_res.p;
   A.arcsOut = wantPaths ? d->d_arcs.p : nullptr; A.wordsOut = wantPaths ? d->d_words.p : nullptr; A.maxPath = maxPath;
   A.useLdsRow = P.useLdsRow; A.hashN = P.hashN; A.regionB = (int) (kSideLds * sizeof(Side)); A.cntCap = P.cntCap;
+  A.heads = d->d_heads.p;
+  // hop scratch of the traceback, per utterance.  A chain has at most one record per frame and the end expansion's, so min(2 x maxCand, Tmax + 2) entries hold it.
+  A.hopStride = std::max(1, std::min(2 * D.maxCand, Tmax + 2));
+  d->d_hopRec.reserve((size_t) U * A.hopStride); d->d_hopOff.reserve((size_t) U * A.hopStride); A.hopRec = d->d_hopRec.p;
+  // back-pointer records outlive their utterance in the pool of a time-sliced batch, in lattice mode (an arena per utterance), and where every workgroup decodes
+  // exactly one utterance: with as many workgroups as utterances the kernel binds utterance u to workgroup u instead of dealing them out from the queue (oneEach; from
+  // the queue, a workgroup that ends a short utterance before the whole grid is resident would take another into its arena).  Everywhere else -- run to completion
+  // with more utterances than workgroups -- a slot's arena is its next utterance's too, and the kernel follows the chain before it moves on.
+  A.oneEach = (P.segFrames == 0 && slots == U) ? 1 : 0;
+  A.walkHere = (P.segFrames == 0 && !latOn && !A.oneEach) ? 1 : 0;
+  return A;
+}
+
+// k_traceback's arguments from the decode's: the graph tables a path is spelled out with, the heads, the results, and the hop scratch (the status is judged by
+// 2 x maxCand hops as it always was).
+static TraceArgs fill_trace_args(dsr_decoder* d, const VitArgs& V)
+{
+  TraceArgs A; A.hopCap = 2 * V.D.maxCand; A.hopStride = V.hopStride;
+  A.heads = V.heads; A.arena = V.D.arena; A.arenaN = (unsigned long long) d->d_arena.n;
+  A.xrec = V.G.xrec; A.erec = V.G.erec; A.xarc = V.G.xarc; A.xpathOff = V.G.xpathOff; A.path = V.G.path; A.arcOut = V.G.arcOut;
+  A.hopRec = d->d_hopRec.p; A.hopOff = d->d_hopOff.p;
+  A.res = V.res; A.arcsOut = V.arcsOut; A.wordsOut = V.wordsOut; A.maxPath = V.maxPath; A.U = V.U;
   return A;
 }
 
@@ -381,7 +447,11 @@ dsr_status dsr_decoder_decode_launch(dsr_decoder* d, const float* score, const i
     if (maxPath < 0) maxPath = 0;
     const VitArgs A = fill_vit_args(d, P, env, score, nframes, U, Tmax, nDist, maxPath, want_paths != 0, st);
     if (env.segVerbose) fprintf(stderr, "[dsr viterbi] %d utterances on %d workgroups: %s, %s state table\n", U, P.slots, P.segFrames > 0 ? (P.segQueues == 8 ? "time-sliced, XCD-bound queues" : "time-sliced, one queue") : "run to completion", P.narrow ? "narrow" : "wide");
+    const TraceArgs TA = fill_trace_args(d, A);
+    order_behind_last_traceback(P.slots, st);
     viterbi_launch(P.modes, A, P.slots, P.ldsBytes, st);
+    traceback_launch(TA, st);                                             // the best paths, from the heads the decode leaves: directly behind it, before the copies
+    publish_traceback(d, st);
     enqueue_result_copies(d, U, want_paths ? (size_t) U * maxPath : 0, st);
     d->pendingSlots = P.slots; d->pendingProf = A.D.prof;
   });

@@ -2,8 +2,8 @@
 // utterances, bit-exact with the reference's sequential decoder.
 //
 // Replaces _Decoder::decode and everything under it (asr/decoder/decoder.h:488-737, 956-1015),
-// the _TokenList hash/list (decoder.h:48-320), _Token (asr/lattice/lattice.h:37-79) and
-// bestHypo (decoder.h:748-773) for DecoderFlyWeight (decoder.h:1127-1139).
+// the _TokenList hash/list (decoder.h:48-320) and _Token (asr/lattice/lattice.h:37-79) for DecoderFlyWeight
+// (decoder.h:1127-1139); bestHypo (decoder.h:748-773) is k_traceback.hip, launched behind this kernel from the heads it leaves.
 //
 // What "bit-exact" needs and how it is kept in a parallel kernel:
 //   * token scores live as two floats; every placement is computed in double from them and rounded on
@@ -201,7 +201,6 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
   __shared__ float s_waveMag[kWaves];
   __shared__ unsigned long long s_waveKey[kWaves];
   __shared__ int s_sideN;
-  __shared__ int s_tb[2];            // traceback: hops, words
   __shared__ unsigned s_bm[kFastC / 32];             // register path: slots where an expanding token's run starts
   // register path, per group of 64 slots: expanding tokens that start before the group (13 bits) | how far into its token's run the group's first slot is (19 bits)
   __shared__ unsigned s_gbase[kFastC / 64 + 4];
@@ -256,7 +255,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
   // there are none by then; this is the net under the one assumption the XCD-bound queues make (a queue whose XCD got no workgroup of the grid would otherwise
   // never be served): such an utterance is decoded here in one go -- no hand-over, so no coherence question -- and marked so that its own queue passes it by.
   // (the queue being served lives in LDS, the work item comes out of it as (utterance, segment): nothing of this rides in registers through the frame loop)
-  if (tid == 0) s_help = (nq == 8 && ((ka->D.segDrop >> xcd) & 1)) ? 1 : 0;
+  if (tid == 0) { s_help = (nq == 8 && ((ka->D.segDrop >> xcd) & 1)) ? 1 : 0; s_u = -2; }      // (s_u == -2: this workgroup has not asked for work yet)
   for (;;) {
     __syncthreads();
     if (tid == 0) {
@@ -264,7 +263,8 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
       for (;;) {
         const int qx = (xcd + help) & (nq - 1), Uq = (ka->U - qx + nq - 1) / nq;     // (nq is 1 or 8); utterances of this queue: u = qx mod nq
         int it = -1;
-        if (help == 0) { it = atomicAdd(ka->D.queue + qx, 1); if (it >= (segS0 > 0 ? ka->D.segCount * Uq : Uq)) it = -1; }
+        // (oneEach: as many workgroups as utterances, never sliced -- workgroup u decodes utterance u and is done, so that no slot's arena is used twice)
+        if (help == 0) { it = ka->oneEach ? (s_u == -2 ? slot : Uq) : atomicAdd(ka->D.queue + qx, 1); if (it >= (segS0 > 0 ? ka->D.segCount * Uq : Uq)) it = -1; }
         else {                                                                // first-segment items only, and only by compare-and-swap: a later item of that queue is not ours to take
           int c = ld_i32(ka->D.queue + qx);
           while (c < Uq) { const int prev = atomicCAS(ka->D.queue + qx, c, c + 1); if (prev == c) { it = c; break; } c = prev; }
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
       if (nq == 1) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       const SegState* const sst = ka->D.segState + u;
       status = ld_i32(&sst->status);
-      if (status != DSR_OK) continue;                                          // it failed there: its result is written
+      if (status != DSR_OK) continue;                                          // it failed there: its result and its trace head are written (or it is being decoded whole elsewhere, -2: not ours to touch)
       n = ld_i32(&sst->n); arenaOff = (long) ld_u64_dev(&sst->arenaOff); chunkEnd = (long) ld_u64_dev(&sst->chunkEnd); arenaUsed = (long) ld_u64_dev(&sst->arenaUsed); thresh = __longlong_as_double((long long) ld_u64_dev(&sst->thresh));
       if (tid == 0) { s_stat[0] = (long long) ld_u64_dev(&sst->stat[0]); s_stat[1] = (long long) ld_u64_dev(&sst->stat[1]); s_stat[2] = (long long) ld_u64_dev(&sst->stat[2]); s_maxActive = ld_i32(&sst->maxActive); s_latOff = 0; }
       const TokA* const svA = ka->D.saveA + (size_t) u * ka->D.maxTok; const TokB* const svB = ka->D.saveB + (size_t) u * ka->D.maxTok;
@@ -322,7 +322,10 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
     int preC = -1;                                                             // >= 0: the frame before has already laid out this frame's slots (bitmap, group table): preC placements
     const bool preRow = useLdsRow && nDist <= 2 * nthr;
     float rowNext[2] = {0.0f, 0.0f};
-    if (preRow && fr0 < T) { const float* r0 = sc + (size_t) fr0 * nDist; if (tid < nDist) rowNext[0] = r0[tid]; if (tid + nthr < nDist) rowNext[1] = r0[tid + nthr]; }
+    if (preRow && fr0 < T) {                                                   // (the thread index opaque here too: its byte offsets, hoisted to the kernel's start, were a spilled register per utterance)
+      const float* r0 = sc + (size_t) fr0 * nDist; int tidU = (int) threadIdx.x; asm volatile("" : "+v"(tidU));
+      if (tidU < nDist) rowNext[0] = r0[tidU]; if (tidU + nthr < nDist) rowNext[1] = r0[tidU + nthr];
+    }
     TICK(11);
     // frames 0..T-1 (mode 0), then the end expansion (mode 1) -- with time slicing: this segment's share of them
     int fr = fr0;
@@ -1279,79 +1282,29 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
           if (tid == 0) { int* li = ka->D.latInfo + 4 * (size_t) u; li[0] = cntL; li[1] = numNew > 0 ? 1 : 0; li[2] = (int) (arenaOff + (numNew > 0 ? numNew : 0)); li[3] = T; }
         }
         __syncthreads();
-        // traceback (bestHypo, decoder.h:748-773).  One thread follows the back pointers (one dependent 8-byte load per frame) and
-        // leaves the hop records in scratch memory; everything else -- arcs per hop, their places in the list, the word sequence --
-        // is done by the whole workgroup with two prefix sums.
-        int* hopRec = reinterpret_cast<int*>(cB); const int hopCap = 2 * ka->D.maxCand; int* hopOff = hopRec + hopCap;
-        // (the result record is written by thread 0 alone and lives in memory between its two steps: as a register struct of every thread it was
+        // The traceback itself (bestHypo, decoder.h:748-773) is k_traceback's: this workgroup holds a whole CU, and the walk is one thread waiting on a chain of
+        // dependent loads.  Thread 0 fills the result record up to the best token and leaves the head of the chain -- the token's back pointer and where this
+        // utterance's records start in D.arena -- by UTTERANCE (slots are reused).  Only where this slot's next utterance overwrites the records (walkHere: run to
+        // completion with more utterances than workgroups, outside lattice mode) the chain is followed here, into the hop scratch k_traceback works from.
+        // (the result record is written by thread 0 alone and lives in memory: as a register struct of every thread it was
         // a block of zeros carried -- and spilled -- through the whole kernel)
         if (tid == 0) {
           dsr_decode_result* const res = ka->res;
           clear_result(&res[u]); dsr_decode_result& r = res[u];
           unsigned long long k = ~0ull; for (int w = 0; w < nw; w++) if (s_waveKey[w] < k) k = s_waveKey[w];
           r.frames = T - 1; r.reachedFinal = numNew > 0 ? 1 : 0; r.finalStatesN = numNew; /* every token of _next after _expandToEnd sits in a final state */ r.activeHypos = (long) s_stat[0]; r.placements = (long) s_stat[1] + Cfr; r.registerFrames = (long) s_stat[2]; r.maxActiveSeen = s_maxActive; r.status = DSR_OK;
-          int nH = 0;
+          TraceHead hd; hd.arenaOff = (unsigned long long) ((size_t) ((EXTRA && ka->D.latOn) ? u : (ka->D.segFrames > 0 ? 0 : slot)) * ka->D.arenaCap); /* as the arena macro */ hd.bp = kNone; hd.hops = kNone;
           if (k != ~0ull) {
             const TokA bt = ld_tok(&lst[(unsigned) (k & 0xFFFFFFFFu)]);
             r.ac = bt.ac; r.lm = bt.lm; r.score = __dadd_rn((double) bt.ac, (double) bt.lm);
-            for (uint32_t bq = bt.bp; bq != kNone && nH < hopCap; ) {          // (time slicing: the records were written on other CUs -- read past this XCD's L2)
-              uint2 e; if (segS > 0) { const unsigned long long v = ld_u64_dev(&arena[bq]); e.x = (unsigned) v; e.y = (unsigned) (v >> 32); } else e = *reinterpret_cast<const uint2*>(&arena[bq]);
-              hopRec[nH++] = (int) e.y; bq = e.x;
+            hd.bp = bt.bp;
+            if (ka->walkHere) {
+              int* const hopRec = ka->hopRec + (size_t) u * ka->hopStride; const int walkCap = 2 * ka->D.maxCand < ka->hopStride ? 2 * ka->D.maxCand : ka->hopStride; int nH = 0;
+              for (uint32_t bq = bt.bp; bq != kNone && nH < walkCap; ) { const uint2 e = *reinterpret_cast<const uint2*>(&arena[bq]); hopRec[nH++] = (int) e.y; bq = e.x; }
+              hd.hops = (uint32_t) nH;
             }
           } else r.status = DSR_E_CONSISTENCY;
-          s_tb[0] = nH; s_tb[1] = 0;
-        }
-        __syncthreads();
-        const int nH = s_tb[0];
-        auto block_excl = [&](const int v, int& total) -> int {
-          const int incl = wave_incl_scan(v, lane);
-          if (lane == 63) s_waveTot[wave] = incl;
-          __syncthreads();
-          int base = 0, tot = 0;
-          for (int w = 0; w < nw; w++) { const int q = s_waveTot[w]; if (w < wave) base += q; tot += q; }
-          __syncthreads();
-          total = tot; return base + incl - v;
-        };
-        int nA = 0;
-        for (int b0 = 0; b0 < nH; b0 += nthr) {                                  // arcs per hop; hopOff = arcs of the hops walked before (= later in time)
-          const int i = b0 + tid; int len = 0;
-          if (i < nH) { const uint32_t rc = (uint32_t) hopRec[i]; len = (rc & kEndBit) ? ka->G.erec[rc & ~kEndBit].pathLen : (int) (ka->G.xrec[rc].meta & 0xFFFFu) + 1; }
-          int total; const int ex = block_excl(len, total);
-          if (i < nH) hopOff[i] = nA + ex;
-          nA += total;
-        }
-        int* const arcsOut = ka->arcsOut; unsigned* const wordsOut = ka->wordsOut; const int maxPath = ka->maxPath; dsr_decode_result* const res = ka->res;
-        int* ao = arcsOut ? arcsOut + (size_t) u * maxPath : nullptr;
-        int nWloc = 0;
-        for (int i = tid; i < nH; i += nthr) {                                   // every hop writes its arcs, first..last
-          const uint32_t rc = (uint32_t) hopRec[i]; int pos = nA - hopOff[i];
-          if (rc & kEndBit) {
-            const ERec e = ka->G.erec[rc & ~kEndBit];
-            for (int h = e.pathLen - 1; h >= 0; h--) { const int a = ka->G.path[e.pathOff + h]; pos--; if (ao && pos < maxPath) ao[pos] = a; if (ka->G.arcOut[a] != 0) nWloc++; }
-          } else {
-            const int a = ka->G.xarc[rc]; pos--; if (ao && pos < maxPath) ao[pos] = a; if (ka->G.arcOut[a] != 0) nWloc++;
-            const int pl = (int) (ka->G.xrec[rc].meta & 0xFFFFu); const int po = ka->G.xpathOff[rc];
-            for (int h = pl - 1; h >= 0; h--) { const int a2 = ka->G.path[po + h]; pos--; if (ao && pos < maxPath) ao[pos] = a2; if (ka->G.arcOut[a2] != 0) nWloc++; }
-          }
-        }
-        if (nWloc) atomicAdd(&s_tb[1], nWloc);
-        __syncthreads();
-        if (wordsOut && ao) {                                                    // the words of the arc list, in order
-          unsigned* wo = wordsOut + (size_t) u * maxPath; int q = 0;
-          const int lim = nA < maxPath ? nA : maxPath;
-          for (int b0 = 0; b0 < lim; b0 += nthr) {
-            const int i = b0 + tid; unsigned o = 0u;
-            if (i < lim) o = ka->G.arcOut[ao[i]];
-            int total; const int ex = block_excl(o != 0u ? 1 : 0, total);
-            if (o != 0u && q + ex < maxPath) wo[q + ex] = o;
-            q += total;
-          }
-        }
-        if (tid == 0) {
-          if (res[u].status == DSR_OK) {
-            res[u].nArcs = nA; res[u].nWords = s_tb[1];
-            if (nH >= hopCap) res[u].status = DSR_E_ALLOCATION; else if (nA > maxPath && arcsOut) res[u].status = DSR_E_DIMENSION;
-          }
+          ka->heads[u] = hd;
         }
         __syncthreads();
         TICK(9);
@@ -1380,6 +1333,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
       // abort: the tagged state table needs no cleaning
       if (tid == 0) {
         dsr_decode_result* const res = ka->res; clear_result(&res[u]); res[u].status = status; res[u].frames = T - 1;
+        { TraceHead hd; hd.arenaOff = 0ull; hd.bp = kNone; hd.hops = kNone; ka->heads[u] = hd; }                                   // nothing for k_traceback to follow
         if (segS > 0) { st_i32(&ka->D.segState[u].status, status); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); st_i32(&ka->D.segDone[u], 0x7FFFFFFF); }   // later segments pass by
       }
     }

@@ -19,8 +19,14 @@ struct Side { double ttl; float ac; float lm; int32_t rec; uint32_t prevBp; int3
 struct CandA { double ttl; float ac; float lm; };
 struct CandB { int32_t dst; int32_t next; int32_t rec; uint32_t prevBp; };   // rec bit30: the emitting arc's input is the silence symbol
 struct Bp { uint32_t prev; uint32_t rec; };
+// what k_viterbi leaves of an utterance for k_traceback: the best token's back pointer (0xFFFFFFFF: nothing to trace -- no best token, or the utterance failed)
+// and where the utterance's back-pointer records start in DecDev::arena, in records (its own arena in lattice mode, 0 = the pool of a time-sliced batch; its slot's arena otherwise, where the chain is followed at once: hops)
+// hops: 0xFFFFFFFF = the chain is k_traceback's to follow (time-sliced batches, lattice mode, a workgroup bound to each utterance).  Where the records do not outlive the utterance --
+// run to completion with more utterances than workgroups: a workgroup takes utterances from a queue and its slot's arena is its next utterance's too -- k_viterbi follows the chain itself before it moves on, into the utterance's hop scratch, and
+// leaves the number of hops here.
+struct TraceHead { unsigned long long arenaOff; uint32_t bp; uint32_t hops; };
 // (the LDS budget of decode_plan.h counts 32 bytes per side record; the 32-bit byte offsets of the register path rest on the other sizes)
-static_assert(sizeof(TokA) == 16 && sizeof(TokB) == 8 && sizeof(XRecD) == 32 && sizeof(Side) == 32 && sizeof(CandA) == 16 && sizeof(CandB) == 16 && sizeof(Bp) == 8,
+static_assert(sizeof(TokA) == 16 && sizeof(TokB) == 8 && sizeof(XRecD) == 32 && sizeof(Side) == 32 && sizeof(CandA) == 16 && sizeof(CandB) == 16 && sizeof(Bp) == 8 && sizeof(TraceHead) == 16,
               "record layouts shared by the host and k_viterbi");
 
 static constexpr int kThreads = 1024;             // 16 waves per CU at 128 VGPRs (measured in round 2: 512 x 256 VGPRs 22 % slower, 768 x 168 VGPRs 4 % slower; two 512-thread workgroups per CU 1.2x slower)
@@ -65,11 +71,23 @@ struct VitArgs {
   GraphDev G; DecDev D;
   const float* scores; const int* nframesArr; int U, Tmax, nDist;
   dsr_decode_result* res; int* arcsOut; unsigned* wordsOut; int maxPath, useLdsRow, hashN, regionB, cntCap;
+  TraceHead* heads;                      // [U] written at the end of every utterance, read by k_traceback
+  int* hopRec; int hopStride, walkHere;  // walkHere: the back-pointer records of an utterance are overwritten by the next one of its slot (TraceHead::hops); hopRec: TraceArgs
+  int oneEach;                           // as many workgroups as utterances, run to completion: workgroup u decodes utterance u and nothing else (no queue)
+};
+
+// k_traceback (k_traceback.hip): the best path of every utterance of a launch, from the heads k_viterbi left -- arcs, words, their counts and the two statuses a path can end in
+struct TraceArgs {
+  const TraceHead* heads; const Bp* arena; unsigned long long arenaN;       // arenaN: records in arena (the walk stops at its end whatever a record says)
+  const XRec* xrec; const ERec* erec; const int* xarc; const int* xpathOff; const int* path; const uint32_t* arcOut;
+  int* hopRec; int* hopOff; int hopStride, hopCap;       // hop scratch, hopStride entries per utterance; hopCap: the capacity the status is judged by (2 x maxCand)
+  dsr_decode_result* res; int* arcsOut; unsigned* wordsOut; int maxPath, U;
 };
 
 // modes: bit 0 per-phase ticks (DSR_VITERBI_PROF), bit 1 lattice bookkeeping / topN / token dump compiled in, bit 2 narrow state table
 size_t viterbi_static_lds(int modes);                                                     // static LDS of k_viterbi<modes>
 void viterbi_launch(int modes, const VitArgs& A, int slots, size_t ldsBytes, hipStream_t st);
+void traceback_launch(const TraceArgs& A, hipStream_t st);                                // k_traceback: one wave per utterance, directly behind k_viterbi on its stream
 void xcc_probe_launch(int* out64, hipStream_t st);                                        // k_xcc_probe: the XCD of each workgroup of a 64-workgroup grid
 
 }  // namespace dsr

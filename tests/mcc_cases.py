@@ -3,7 +3,18 @@
 A block holds a white source that reaches channel c with the integer sample delay tau[c] of one grid point (block_c[m] = s[m - tau[c]], so the
 candidate with that tau aligns the channels), on top of independent white noise a channel.  The noise level 0.3 against a unit source keeps
 the condition number of every candidate's covariance near C / 0.09 + 1, far below the 1e5 the GPU tolerances assume; L = 2 D cases, where R
-is estimated from D samples only, use few channels and a large array so that D stays well above C."""
+is estimated from D samples only, use few channels and a large array so that D stays well above C.
+
+k_mcc_cost<CT> and k_mcc_eig<CT> (csrc/k_mcc.hip) are instantiated for CT = ceil(C / 16) = 1..4 tiles of 16 channels, a matrix row taking
+RS = 16 CT + 1 doubles of LDS.  Which C of CASES launches which instantiation, and how full its last tile is:
+
+    CT  RS  C of the cases        last tile
+    1   17  2, 4, 8, 13           2, 4, 8, 13 of 16 rows live
+    2   33  17                    one live row (the first C past a tile edge)
+    2   33  32                    full
+    3   49  40                    half full (8 rows)
+    3   49  48                    full
+    4   65  64                    full"""
 import numpy as np
 
 from tests import mcc_np as M
@@ -30,6 +41,10 @@ CASES = [
     dict(kind="circular", C=8, geom=1000.0, L=1024, S=3, U=4, B=4),
     dict(kind="circular", C=64, geom=210.0, L=512, S=3, U=6, B=6),
     dict(kind="linear", C=4, geom=50.0, L=64, S=3, U=33, B=33),
+    # the instantiation of three channel tiles, and the partial-tile edges (the table in the module docstring)
+    dict(kind="circular", C=40, geom=180.0, L=1024, S=3, U=2, B=2),              # CT = 3, last tile half full
+    dict(kind="circular", C=48, geom=200.0, L=1024, S=1, U=2, B=2),              # CT = 3, every tile full
+    dict(kind="linear", C=17, geom=30.0, L=1024, S=3, U=2, B=2),                 # CT = 2 with one live row in the second tile
 ]
 MULTI_GROUP = (10, 11, 12)
 

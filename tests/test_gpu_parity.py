@@ -205,6 +205,29 @@ def test_beamformer_apply(dsr, oracle, cuda, mode):
         assert err < 2e-5, err
 
 
+def test_beamformer_apply_weights_above_64k_of_lds(dsr, oracle, cuda):
+    """k_bf_apply keeps the weight image in dynamic LDS: 129 bins x 64 channels x 8 bytes = 66 048 bytes, above the 64 KiB a kernel gets
+    without asking; 513 x 64 x 8 = 262 656 bytes are more than a workgroup can have and are refused"""
+    import torch
+    M, Cn, T = 256, 64, 8
+    mp = synth.linear_array(Cn)
+    delays = dsr.calcDelaysPolar2(np.float32(np.deg2rad(30.0)), np.float32(np.pi / 2), mp)
+    bf = dsr.Beamformer(M, Cn); bf.calcArrayManifoldVectors(16000.0, delays); bf.select("ds")
+    wq = oracle.calc_mainlobe(16000.0, delays, M)
+    rng = np.random.default_rng(5)
+    X = (rng.standard_normal((2, Cn, T, M // 2 + 1)) + 1j * rng.standard_normal((2, Cn, T, M // 2 + 1))).astype(np.complex64)
+    Y = bf.apply(torch.from_numpy(X).to(cuda)).cpu().numpy()
+    for u in range(2):
+        Xfull = np.zeros((Cn, T, M), np.complex128); Xfull[:, :, :M // 2 + 1] = X[u]
+        ref = oracle.beamform_apply(Xfull, wq[:M // 2 + 1])
+        err = np.abs(Y[u] - ref[:, :M // 2 + 1]).max() / np.sqrt(np.mean(np.abs(ref) ** 2))
+        assert err < 2e-5, err
+    big = dsr.Beamformer(1024, Cn); big.calcArrayManifoldVectors(16000.0, delays); big.select("ds")
+    with pytest.raises(dsr.DsrError) as e:
+        big.apply(torch.zeros((1, Cn, 1, 513), dtype=torch.complex64, device=cuda))
+    assert e.value.status == dsr.E_DIMENSION and "262656 bytes of LDS" in str(e.value)
+
+
 # ------------------------------------------------------------------------------------------- MFCC
 @pytest.mark.parametrize("stage,tol", [(4, 1e-5), (3, 1e-5), (1, 1e-4), (2, 1e-4), (0, 1e-4)])
 def test_mfcc_chain(dsr, oracle, cuda, headset, stage, tol):

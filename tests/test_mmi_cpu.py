@@ -9,6 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "distantspeechrecognition-mirror_amd"))
 from oracle import oracle as O
 import dsr._capi as K
+from tests import mmi_cases as Mc
 
 
 def _pair(M, Cn, hbs, nSource, NC, seed):
@@ -117,3 +118,24 @@ def test_pseudoinverse_wide_matrix():
     P = np.zeros((6, 2), np.complex128)
     L.orc_pseudoinverse_mn(O._p(np.ascontiguousarray(A)), 2, 6, O._p(P), O.C.c_float(1e-7))
     assert np.abs(A @ P - np.eye(2)).max() < 1e-5
+
+
+@pytest.mark.parametrize("i", Mc.MASKED, ids=[Mc.IDS[i] for i in Mc.MASKED])
+def test_shape_cases_masks_strike_some_high_bins(i):
+    """the masked cases of tests/test_gpu_mmi_shapes.py mean something past bin 255 only if the mask strikes some of the bins from 256 on and
+    spares others.  Which bins it strikes depends on the outputs' powers alone, not on what it puts in their place: the oracle with the case's
+    mask type set to write zeros, against the oracle without a mask, on the case's own input."""
+    case = Mc.CASES[i]; mask = case[8]
+    X, nfr, refs = Mc.reference(i)
+    struck = []
+    for u in range(X.shape[0]):
+        Xu = X[u, :, :nfr[u], :]
+        Ym = Mc.oracle_run(case, Xu, mask=(-1.0, 1, mask[2])); Y0 = Mc.oracle_run(case, Xu, mask=None)
+        s = (Ym == 0) & (Y0 != 0)
+        assert Y0[:, 256:].all()
+        if mask[2] == 0:                                                        # (type 1 runs the target's post-filter twice a frame: no bin equals the unmasked run)
+            assert np.array_equal(refs[u][~s], Y0[~s]) and np.all(refs[u][s] != Y0[s])
+        struck.append(s[:, 256:].ravel())
+    share = np.concatenate(struck).mean()
+    print("case %s: the mask strikes %.3f of %d values in bins >= 256" % (Mc.IDS[i], share, np.concatenate(struck).size))
+    assert 0.05 < share < 0.95

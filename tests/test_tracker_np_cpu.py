@@ -110,18 +110,28 @@ def test_case_is_well_conditioned(case):
     ref = Cs.reference(case)
     a, b = ref["ref"], ref["second"]
     assert np.array_equal(a["info"], b["info"])
-    Kn = case["useSubbandsN"] or Cs.F
-    for u in range(Cs.U):
-        assert len(a["logs"][u]) == Cs.NFRAMES[u]
+    _, F, U, _, frames = Cs.dims(case)
+    Kn = case["useSubbandsN"] or F
+    for u in range(U):
+        assert len(a["logs"][u]) == frames[u]
         for la, lb in zip(a["logs"][u], b["logs"][u]):
             assert la["sels"] == lb["sels"] and la["iters"] == lb["iters"] and la["clamp"] == lb["clamp"]
             for sa in la["sortedAbs"]:
                 top = sa[:Kn + 1]
+                if case["only"]:                                         # the source's bins apart from each other and from the rest, which is exactly zero on
+                    top = top[:len(case["only"]) + 1]                    # both sides (0 / delta): there the tie rule decides, not rounding
+                    assert not sa[len(case["only"]):].any()
                 assert ((top[:-1] - top[1:]) / top[:-1]).min() > 1e-9
             for ratio in la["ratios"]:
                 assert abs(ratio - T.TOLERANCE) >= 1e-3 * T.TOLERANCE
     if case["name"] == "modal-clamp":
         assert any(l["clamp"] for lg in a["logs"] for l in lg)
+    kept = [set(s) for lg in a["logs"] for l in lg for s in l["sels"]]
+    if case["name"] in ("modal-F257", "spatial-F257"):                   # a kept bin that is the second bin of a thread of k_trk_run (NT = 256)
+        assert F == 257 and any(max(s) >= 256 for s in kept), kept
+    if case["name"] == "modal-ties":                                     # the two live bins, then the lowest of the zeros
+        assert kept and all(s == {200, 256, 0, 1} for s in kept), kept
+        assert all(sorted(s[:2]) == [200, 256] and s[2:] == [0, 1] for lg in a["logs"] for l in lg for s in l["sels"])
     print("%s: s_case = %.3e (%s)" % (case["name"], ref["s_case"], "float64 vs long double" if Cs.WIDE else "float64 vs reversed sums"))
     assert ref["s_case"] < 1e-9                                           # the filter does not amplify rounding: the GPU bound stays meaningful
 
@@ -193,3 +203,24 @@ def test_facade_and_argument_errors(dsr):
     with pytest.raises(dsr.DsrError) as e:
         trk.setV(bad, 2)
     assert e.value.status == E_ARG and np.array_equal(trk._trk.getV(2), before)
+
+
+def test_create_refuses_one_bin_past_the_lds_row_limit(dsr):
+    """dsr_trk_create at the edge of dsr_trk_max_rows, modal order 2 (L = 9): the largest useSubbandsN whose 2 K L rows fit constructs, the
+    next one is an argument error.  The limit depends on K itself (the selected bins take K ints of the same LDS), so it is asked per K."""
+    L, fftLen = 9, 2048                                                    # 1025 bins: more than any K the limit admits
+    fits = [K_ for K_ in range(1, fftLen // 2 + 1) if 2 * K_ * L <= dsr.SphTracker.maxRows("modal", 2, K_)]
+    Kmax = fits[-1]
+    assert fits == list(range(1, Kmax + 1)) and Kmax + 1 <= fftLen // 2 + 1
+    lim = dsr.SphTracker.maxRows("modal", 2, Kmax)
+    # the figure itself: 160 KiB of doubles less the per-mode tables (8 x 9), the reduction scratch (256), 32 scalars, the K selected bins as ints
+    # and one spare, in three columns of 2N + 2 rows
+    assert lim == (160 * 1024 // 8 - (8 * 9 + 256 + 32 + (Kmax + 1) // 2 + 1)) // 3 - 2
+    assert 2 * Kmax * L <= lim < 2 * (Kmax + 1) * L
+    t = dsr.SphTracker("modal", 2, fftLen, Cs.A_MM, Cs.FS, Kmax)
+    assert (t.useSubbandsN, t.L) == (Kmax, L)
+    with pytest.raises(dsr.DsrError) as e:
+        dsr.SphTracker("modal", 2, fftLen, Cs.A_MM, Cs.FS, Kmax + 1)
+    assert e.value.status == dsr.E_PARAMETER and "rows exceed" in str(e.value)
+    # the spatial case of the GPU test that passes 64 KiB is inside the limit, and far from it
+    assert 2 * 41 * 32 <= dsr.SphTracker.maxRows("spatial", 2, 41)

@@ -1,5 +1,5 @@
 // csrc/fsa.h -- feature-space adaptation (constrained MLLR) as fsa.cpp (accumulator arithmetic, files, host), k_fsa.hip (nearest Gaussian,
-// statistics, estimation and the transform on the device) and streams.cpp (the stream operator) share it.
+// statistics, estimation and the transform on the device) and streams_asr.cpp (the stream operator) share it.
 // Replaces FeatureSpaceAdaptationFeature (asr/train/fsa.{h,cc}, "fsa").
 #pragma once
 #include "train.h"

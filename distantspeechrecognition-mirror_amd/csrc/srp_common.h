@@ -1,7 +1,7 @@
 // csrc/srp_common.h -- what the steered-response-power kernels share: k_doa.hip (linear array) and k_sph.hip (spherical array).
 // The workgroup tiling and the parts of the two SRP kernels that are the same (snapshot staging, the staged-chunk frame energy of calcEnergy,
 // beamformer.cc:3043-3074, the response-power accumulation and its epilogue), the N-best insertion of DOAEstimatorSRP*::next and
-// _getNBestHypothesesFromACCRP (also the stream operators', csrc/streams.cpp), the frequency-range check, the linear estimator's handle and its
+// _getNBestHypothesesFromACCRP (also the stream operators', csrc/streams_beamformer.cpp), the frequency-range check, the linear estimator's handle and its
 // launchers, which the spherical estimator's folded path drives with a table of its own.  Kernel files that include this are built with
 // -ffp-contract=off: the energy must stay the reference's float accumulation bit for bit.
 #pragma once

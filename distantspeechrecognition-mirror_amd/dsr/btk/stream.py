@@ -84,7 +84,7 @@ class _PySource(FeatureStreamPtr):
         self._src = src; sz = int(src.size())
         h, _ = _new(lib().dsr_frame_source_create, self._TYPE, sz, name.encode())
         FeatureStreamPtr.__init__(self, h); self._load()
-        # a reset() of any downstream operator cascades to this source in C++ (streams.cpp FrameSrc::reset): the refill callback then calls the
+        # a reset() of any downstream operator cascades to this source in C++ (csrc/streams.cpp FrameSrc::reset): the refill callback then calls the
         # Python iterable's reset() and drains it again before the next frame is served, as PyFeatureStream::reset does (pyStream.h:100-130)
         self._exc = None
         self._cb = _REFILL(self._refill)

@@ -263,3 +263,15 @@ def test_lexicon_container_through_the_boundary(tmp_path):
     assert open(tmp_path / "o.txt").read().splitlines()[1] == "%30s %10d" % ("A", 1)         # distribTree.cc:118
     l2 = LexiconPtr("u", str(tmp_path / "o.txt"))
     assert list(l2) == list(lx)
+
+
+def test_create_refuses_a_null_out(dsr):
+    # the front-end create functions once stored through `out` unchecked; every create now answers JPARAMETER "null argument"
+    L = dsr.load(); h = C.c_void_p()
+    assert L.dsr_sample_feature_create(320, 160, 0, b"", C.byref(h)) == 0
+    try:
+        for call in (lambda: L.dsr_preemphasis_create(h, 0.95, b"", None), lambda: L.dsr_hamming_create(h, b"", None),
+                     lambda: L.dsr_fft_create(h, 512, b"", None), lambda: L.dsr_cepstral_create(h, 13, 1, b"", None)):
+            assert call() == 13 and L.dsr_last_error() == b"null argument"
+    finally:
+        L.dsr_stream_release(h)

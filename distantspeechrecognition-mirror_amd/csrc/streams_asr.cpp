@@ -45,6 +45,69 @@ dsr_status dsr_fsa_feature_distrib_set(dsr_stream* s, dsr_gmm* gmm)
 dsr_fsa* dsr_fsa_feature_handle(dsr_stream* s) { FsaOp* q = dynamic_cast<FsaOp*>(s); return q ? q->h : nullptr; }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// STCTransformer / LDATransformer as stream operators (asr/adapt/transform.cc:1836-1850, 1937-1959): every frame of the source under matrix 0
+// of the operator's handle, the first size() rows of it for LDA.  The handle is a bare transformer (the identity, or a loaded matrix) until a
+// model is named; then it is an estimator that keeps the matrix.  The frames stay on the device, as FeatureSpaceAdaptationFeature's do.
+namespace {
+struct StcOp : dsr_stream {
+  dsr_stc* h = nullptr; int cascade = 0, mmi = 0;
+  ~StcOp() override { dsr_stc_destroy(h); }
+  void compute() override { alloc(ups[0]->nFrames); ok(dsr_stc_apply(h, ups[0]->d<float>(), nFrames, 0, d<float>(), S0)); }
+};
+struct LdaOp : dsr_stream {
+  dsr_lda* h = nullptr;
+  ~LdaOp() override { dsr_lda_destroy(h); }
+  void compute() override { alloc(ups[0]->nFrames); ok(dsr_lda_apply(h, ups[0]->d<float>(), nFrames, 0, size_, d<float>(), S0)); }
+};
+}
+
+dsr_status dsr_stc_feature_create(dsr_stream* src, int cascade, int mmiEstimation, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    need(src, DSR_T_FLOAT, "STCTransformer");
+    auto s = new_op<StcOp>(out, name, "STC Transformer", src->size_, DSR_T_FLOAT); s->cascade = cascade; s->mmi = mmiEstimation;
+    ok(dsr_stc_create_transformer(src->size_, &s->h));
+    hand_out(out, std::move(s), {src});
+  });
+}
+dsr_status dsr_stc_feature_distrib_set(dsr_stream* s, dsr_gmm* gmm)
+{
+  return guard([&] {
+    StcOp* q = as_op<StcOp>(s, "not an STCTransformer stream"); if (!gmm) throw Error(DSR_E_PARAMETER, "null argument");
+    if (q->size_ != dsr_gmm_dim(gmm)) throw Error(DSR_E_DIMENSION, "Feature and codebook dimensions (%d vs. %d) do not match.", q->size_, dsr_gmm_dim(gmm));
+    std::vector<double> A((size_t) q->size_ * q->size_); ok(dsr_stc_get_transform(q->h, 0, A.data(), nullptr));
+    dsr_stc* h = nullptr; ok(dsr_stc_create(gmm, 1, q->cascade, q->mmi, &h));
+    const dsr_status st = dsr_stc_set_transform(h, 0, A.data()); if (st) { dsr_stc_destroy(h); ok(st); }
+    dsr_stc_destroy(q->h); q->h = h; q->ready = false;
+  });
+}
+dsr_stc* dsr_stc_feature_handle(dsr_stream* s) { StcOp* q = dynamic_cast<StcOp*>(s); return q ? q->h : nullptr; }
+
+dsr_status dsr_lda_feature_create(dsr_stream* src, int outDim, const char* name, dsr_stream** out)
+{
+  return guard([&] {
+    need(src, DSR_T_FLOAT, "LDATransformer");
+    if (outDim < 1 || outDim > src->size_) throw Error(DSR_E_DIMENSION, "LDA output size %d of a %d-dimensional source", outDim, src->size_);
+    auto s = new_op<LdaOp>(out, name, "LDA Transformer", outDim, DSR_T_FLOAT);
+    ok(dsr_lda_create_transformer(src->size_, &s->h));
+    hand_out(out, std::move(s), {src});
+  });
+}
+dsr_status dsr_lda_feature_codebooks(dsr_stream* s, dsr_gmm* gmm, dsr_gmm* global)
+{
+  return guard([&] {
+    LdaOp* q = as_op<LdaOp>(s, "not an LDATransformer stream"); if (!gmm || !global) throw Error(DSR_E_PARAMETER, "null argument");
+    const int Din = q->ups[0]->size_;
+    if (Din != dsr_gmm_dim(gmm)) throw Error(DSR_E_DIMENSION, "Feature and codebook dimensions (%d vs. %d) do not match.", Din, dsr_gmm_dim(gmm));
+    std::vector<double> L((size_t) Din * Din); ok(dsr_lda_get_transform(q->h, 0, L.data()));
+    dsr_lda* h = nullptr; ok(dsr_lda_create(gmm, global, 1, &h));
+    const dsr_status st = dsr_lda_set_transform(h, 0, L.data()); if (st) { dsr_lda_destroy(h); ok(st); }
+    dsr_lda_destroy(q->h); q->h = h; q->ready = false;
+  });
+}
+dsr_lda* dsr_lda_feature_handle(dsr_stream* s) { LdaOp* q = dynamic_cast<LdaOp*>(s); return q ? q->h : nullptr; }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // ASR side of the boundary: the distribution set as the decoder sees it.  The reference decoder asks _dist->find(distX-1)->score(_frameX)
 // (asr/decoder/decoder.h:985); Distrib::score -> CodebookBasic::score pulls frame frameX of the feature stream and caches the codebook's
 // score for that frame (asr/gaussian/distribBasic.h:48-50,110-114, codebookBasic.cc:431-465).  Here a distribution set is a GMM model bound to

@@ -2362,6 +2362,226 @@ class Fsa:
         ms = (C.c_float * 5)(); check(_lib.dsr_fsa_kernel_ms(self.h, ms)); return tuple(ms)
 
 
+class _Estimators:
+    """what Stc and Lda share: frames, items, timing"""
+
+    def _frames(self, xScore, xSrc):
+        xSrc = xScore if xSrc is None else xSrc
+        for x in (xScore, xSrc):
+            assert x.is_cuda and x.is_contiguous() and x.dtype.is_floating_point and x.element_size() == 4 and x.shape[1] == self.D
+        assert xScore.shape[0] == xSrc.shape[0]
+        return xScore, xSrc
+
+    def _items(self, fn, xScore, frame, dist, factor, est, xSrc, want):
+        xScore, xSrc = self._frames(xScore, xSrc)
+        fr = _np(frame, np.int32); ds = _np(dist, np.int32); fa = _np(factor, np.float32); es = _np(est, np.int32); M = len(fr)
+        assert len(ds) == M and len(fa) == M and len(es) == M
+        near = np.full(M, -1, np.int32); score = np.zeros(M, np.float32)
+        check(fn(self.h, _dev(xScore), _dev(xSrc), xScore.shape[0], _ptr(fr), _ptr(ds), _ptr(fa), _ptr(es), M, _ptr(near), _ptr(score), cur_stream()))
+        return (near, score) if want else None
+
+    def _mat(self, M, shape):
+        M = _np(M, np.float64); assert M.shape == shape
+        return M
+
+    def kernel_ms(self):
+        ms = (C.c_float * 5)(); check(self._kernel_ms(self.h, ms)); return tuple(ms)
+
+
+class Stc(_Estimators):
+    """Semi-tied covariance transforms for nEst estimators over one Gmm (csrc/k_stc.hip, csrc/stc.cpp; include/dsr.h section 12): statistics
+    on fp64 MFMA, makePosDef's eigenvalues, the inverses and the row updates on the device, the transform bit-exact.  Made from a Gmm, as a
+    bare transformer (dimN=), or around the handle an STCTransformer stream owns (handle=, owner=)."""
+
+    def __init__(self, gmm=None, nEst=1, cascade=False, mmiEstimation=False, dimN=None, handle=None, owner=None):
+        L = load(); self._owner = owner
+        if handle is not None:
+            self.h = handle
+        elif gmm is not None:
+            self.h = vp(); check(L.dsr_stc_create(gmm.h, int(nEst), int(bool(cascade)), int(bool(mmiEstimation)), C.byref(self.h)))
+        else:
+            self.h = vp(); check(L.dsr_stc_create_transformer(int(dimN), C.byref(self.h)))
+        self.gmm = gmm; self.D = L.dsr_stc_dim(self.h); self.nEst = L.dsr_stc_num_estimators(self.h); self._kernel_ms = L.dsr_stc_kernel_ms
+
+    def __del__(self):
+        if _lib is not None and getattr(self, "h", None) and self._owner is None:
+            _lib.dsr_stc_destroy(self.h)
+
+    def accumulate(self, xScore, frame, dist, factor, est, xSrc=None, want_nearest=False):
+        """xScore, xSrc: cuda float32 [N][D] (xSrc None: the same frames); frame, dist, factor, est: host arrays [M]; with want_nearest ->
+        (the Gaussian each item chose inside its codebook, the distribution's score of each item)"""
+        return self._items(_lib.dsr_stc_accumulate, xScore, frame, dist, factor, est, xSrc, want_nearest)
+
+    def accumulate_path(self, xScore, distIds, estX=0, factor=1.0, xSrc=None):
+        """distIds: one distribution per frame -> the number of frames"""
+        xScore, xSrc = self._frames(xScore, xSrc); ids = _np(distIds, np.int32); n = C.c_uint(0)
+        check(_lib.dsr_stc_accumulate_path(self.h, _dev(xScore), _dev(xSrc), xScore.shape[0], _ptr(ids), len(ids), int(estX), float(factor), C.byref(n), cur_stream()))
+        return n.value
+
+    def increment(self, totalPr, totalT=0, estX=0):
+        check(_lib.dsr_stc_increment(self.h, int(estX), float(totalPr), int(totalT)))
+
+    def zero(self, estX=0):
+        check(_lib.dsr_stc_zero(self.h, int(estX)))
+
+    def get_accu(self, estX=0, through_accessor=False):
+        """-> dict(count, denCount, totalPr, totalT, sumOsq [D][D][D], regSq [D][D][D]); through_accessor: after copyUpperTriangle, as the
+        reference's sumOsq() / regSq() return them (and leave them); else the triangle as accumulation left it"""
+        D = self.D; c = C.c_double(0.0); dc = C.c_double(0.0); pr = C.c_double(0.0); T = C.c_uint(0); S = np.zeros((D, D, D)); R = np.zeros((D, D, D))
+        check(_lib.dsr_stc_get_accu(self.h, int(estX), int(bool(through_accessor)), C.byref(c), C.byref(dc), C.byref(pr), C.byref(T), _ptr(S), _ptr(R)))
+        return dict(count=c.value, denCount=dc.value, totalPr=pr.value, totalT=T.value, sumOsq=S, regSq=R)
+
+    def set_accu(self, estX=0, count=None, denCount=None, totalPr=None, totalT=None, sumOsq=None, regSq=None):
+        D = self.D; dbl = lambda v: C.byref(C.c_double(float(v))) if v is not None else None      # noqa: E731
+        S = self._mat(sumOsq, (D, D, D)) if sumOsq is not None else None; R = self._mat(regSq, (D, D, D)) if regSq is not None else None
+        check(_lib.dsr_stc_set_accu(self.h, int(estX), dbl(count), dbl(denCount), dbl(totalPr), C.byref(C.c_uint(int(totalT))) if totalT is not None else None,
+                                    _ptr(S) if S is not None else None, _ptr(R) if R is not None else None))
+
+    def save_accu(self, fileName, estX=0):
+        check(_lib.dsr_stc_save_accu(self.h, fileName.encode(), int(estX)))
+
+    def load_accu(self, fileName, estX=0):
+        check(_lib.dsr_stc_load_accu(self.h, fileName.encode(), int(estX)))
+
+    def estimate(self, estX=0, minE=1.0, multE=1.0):
+        """estX: an int or a list: the estimators are estimated concurrently"""
+        e = _np(np.atleast_1d(estX), np.int32)
+        check(_lib.dsr_stc_estimate(self.h, _ptr(e), len(e), float(minE), float(multE), cur_stream()))
+
+    def status(self, estX=0):
+        return _lib.dsr_stc_status(self.h, int(estX))
+
+    def E(self, estX=0):
+        e = C.c_double(0.0); check(_lib.dsr_stc_E(self.h, int(estX), C.byref(e))); return e.value
+
+    def aux(self, estX=0, A=None, E=None):
+        """the auxiliary function the row update maximises, of A (None: the estimator's matrix) at E (None: the last estimate's)"""
+        q = C.c_double(0.0); A = self._mat(A, (self.D, self.D)) if A is not None else None
+        check(_lib.dsr_stc_aux(self.h, int(estX), _ptr(A) if A is not None else None, float(self.E(estX) if E is None else E), C.byref(q))); return q.value
+
+    def transform(self, estX=0):
+        A = np.zeros((self.D, self.D)); check(_lib.dsr_stc_get_transform(self.h, int(estX), _ptr(A), None)); return A
+
+    def inverse(self, estX=0):
+        A = np.zeros((self.D, self.D)); check(_lib.dsr_stc_get_transform(self.h, int(estX), None, _ptr(A))); return A
+
+    def set_transform(self, A, estX=0):
+        check(_lib.dsr_stc_set_transform(self.h, int(estX), _ptr(self._mat(A, (self.D, self.D)))))
+
+    def trans_matrix(self, estX=0):
+        T = np.zeros((self.D, self.D), np.float32); check(_lib.dsr_stc_trans_matrix(self.h, int(estX), _ptr(T))); return T
+
+    def save(self, fileName, estX=0):
+        check(_lib.dsr_stc_save(self.h, fileName.encode(), int(estX)))
+
+    def load(self, fileName, estX=0):
+        check(_lib.dsr_stc_load(self.h, fileName.encode(), int(estX)))
+
+    def save_float(self, fileName, trans=None, estX=0):
+        if trans is not None:
+            trans = _np(trans, np.float32); assert trans.shape == (self.D, self.D)
+        check(_lib.dsr_stc_save_float(self.h, fileName.encode(), int(estX), _ptr(trans) if trans is not None else None))
+
+    def apply(self, x, estX=0, out=None):
+        """x: cuda float32 [N][D] -> cuda float32 [N][D]"""
+        import torch
+        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.shape[1] == self.D
+        if out is None:
+            out = torch.empty_like(x)
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.shape == x.shape
+        check(_lib.dsr_stc_apply(self.h, _dev(x), x.shape[0], int(estX), _dev(out), cur_stream()))
+        return out
+
+    def set_timing(self, on=True):
+        check(_lib.dsr_stc_set_timing(self.h, int(on)))
+
+
+class Lda(_Estimators):
+    """LDA matrices for nEst estimators over one Gmm (csrc/k_stc.hip, csrc/stc.cpp; include/dsr.h section 12): the three scatter matrices on
+    fp64 MFMA, the simultaneous diagonalisation by Jacobi on the device.  globalGmm: a Gmm whose codebook 0 is the global codebook.  Made
+    from two Gmms, as a bare transformer (dimN=), or around the handle an LDATransformer stream owns (handle=, owner=)."""
+
+    def __init__(self, gmm=None, globalGmm=None, nEst=1, dimN=None, handle=None, owner=None):
+        L = load(); self._owner = owner
+        if handle is not None:
+            self.h = handle
+        elif gmm is not None:
+            self.h = vp(); check(L.dsr_lda_create(gmm.h, globalGmm.h, int(nEst), C.byref(self.h)))
+        else:
+            self.h = vp(); check(L.dsr_lda_create_transformer(int(dimN), C.byref(self.h)))
+        self.gmm, self.globalGmm = gmm, globalGmm; self.D = L.dsr_lda_dim(self.h); self.nEst = L.dsr_lda_num_estimators(self.h); self._kernel_ms = L.dsr_lda_kernel_ms
+
+    def __del__(self):
+        if _lib is not None and getattr(self, "h", None) and self._owner is None:
+            _lib.dsr_lda_destroy(self.h)
+
+    def accumulate(self, xScore, frame, dist, factor, est, xSrc=None, want_nearest=False):
+        return self._items(_lib.dsr_lda_accumulate, xScore, frame, dist, factor, est, xSrc, want_nearest)
+
+    def accumulate_path(self, xScore, distIds, estX=0, factor=1.0, xSrc=None):
+        """-> the summed score of the path's distributions"""
+        xScore, xSrc = self._frames(xScore, xSrc); ids = _np(distIds, np.int32); s = C.c_double(0.0)
+        check(_lib.dsr_lda_accumulate_path(self.h, _dev(xScore), _dev(xSrc), xScore.shape[0], _ptr(ids), len(ids), int(estX), float(factor), C.byref(s), cur_stream()))
+        return s.value
+
+    def zero(self, estX=0):
+        check(_lib.dsr_lda_zero(self.h, int(estX)))
+
+    def get_accu(self, estX=0, through_accessor=False):
+        """-> dict(count, within, between, mixture [D][D])"""
+        D = self.D; c = C.c_double(0.0); W = np.zeros((D, D)); B = np.zeros((D, D)); M = np.zeros((D, D))
+        check(_lib.dsr_lda_get_accu(self.h, int(estX), int(bool(through_accessor)), C.byref(c), _ptr(W), _ptr(B), _ptr(M)))
+        return dict(count=c.value, within=W, between=B, mixture=M)
+
+    def set_accu(self, estX=0, count=None, within=None, between=None, mixture=None):
+        D = self.D; m = [self._mat(x, (D, D)) if x is not None else None for x in (within, between, mixture)]
+        check(_lib.dsr_lda_set_accu(self.h, int(estX), C.byref(C.c_double(float(count))) if count is not None else None,
+                                    *[_ptr(x) if x is not None else None for x in m]))
+
+    def save_accu(self, fileName, estX=0):
+        check(_lib.dsr_lda_save_accu(self.h, fileName.encode(), int(estX)))
+
+    def load_accu(self, fileName, estX=0):
+        check(_lib.dsr_lda_load_accu(self.h, fileName.encode(), int(estX)))
+
+    def estimate(self, estX=0):
+        e = _np(np.atleast_1d(estX), np.int32)
+        check(_lib.dsr_lda_estimate(self.h, _ptr(e), len(e), cur_stream()))
+
+    def status(self, estX=0):
+        return _lib.dsr_lda_status(self.h, int(estX))
+
+    def eigenvalues(self, estX=0):
+        """-> (eigenvalues of within as found, eigenvalues of the whitened between, descending) of the last estimate"""
+        w = np.zeros(self.D); b = np.zeros(self.D); check(_lib.dsr_lda_eigenvalues(self.h, int(estX), _ptr(w), _ptr(b))); return w, b
+
+    def transform(self, estX=0):
+        L = np.zeros((self.D, self.D)); check(_lib.dsr_lda_get_transform(self.h, int(estX), _ptr(L))); return L
+
+    def set_transform(self, L, estX=0):
+        check(_lib.dsr_lda_set_transform(self.h, int(estX), _ptr(self._mat(L, (self.D, self.D)))))
+
+    def save(self, fileName, estX=0):
+        check(_lib.dsr_lda_save(self.h, fileName.encode(), int(estX)))
+
+    def load(self, fileName, estX=0):
+        check(_lib.dsr_lda_load(self.h, fileName.encode(), int(estX)))
+
+    def apply(self, x, outDim=None, estX=0, out=None):
+        """x: cuda float32 [N][D] -> cuda float32 [N][outDim]: the first outDim rows of the matrix"""
+        import torch
+        outDim = self.D if outDim is None else int(outDim)
+        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.shape[1] == self.D
+        if out is None:
+            out = torch.empty((x.shape[0], outDim), dtype=torch.float32, device=x.device)
+        assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (x.shape[0], outDim)
+        check(_lib.dsr_lda_apply(self.h, _dev(x), x.shape[0], int(estX), outDim, _dev(out), cur_stream()))
+        return out
+
+    def set_timing(self, on=True):
+        check(_lib.dsr_lda_set_timing(self.h, int(on)))
+
+
 class Wfst:
     """WFSTFlyWeight (asr/decoder/wfstFlyWeight.h:47-119)."""
 

@@ -1,5 +1,6 @@
 """asr.adapt: ParamTreePtr, CodebookSetAdaptPtr, TransformerTreePtr and adaptCbk (asr/adapt/adapt.i) for MLLR mean transforms, over
-dsr_param_tree_* and dsr_mllr_* (include/dsr.h section 10).  The all-pass transforms (RAPT, SLAPT, BLT), STC and LDA are not implemented.
+dsr_param_tree_* and dsr_mllr_* (include/dsr.h section 10), and STCTransformerPtr / LDATransformerPtr over dsr_stc_* / dsr_lda_* (section 12).  The all-pass transforms (RAPT, SLAPT,
+BLT) are not implemented.
 
 The model lives with the distribution set (as everywhere in this package): a codebook set is bound to it when its DistribSet*Ptr is built.
 
@@ -9,7 +10,10 @@ The model lives with the distribution set (as everywhere in this package): a cod
     adaptCbk(cbs, paramTree)                             # the model's means move; every scoring mode follows
     cbs.resetMean()
 """
+import ctypes as C
+
 from .. import _capi as K
+from ..btk.stream import FeatureStreamPtr, _new
 from .gaussian import CodebookSetBasicPtr
 
 
@@ -69,3 +73,55 @@ class TransformerTreePtr(object):
 def adaptCbk(cbs, paramTree):
     """adapt.i: transform the means of `cbs` with the parameters of `paramTree`"""
     return TransformerTreePtr(cbs, paramTree).transform()
+
+
+class _MatrixStream(FeatureStreamPtr):
+    """what STCTransformerPtr and LDATransformerPtr share: the handle the stream owns (matrix 0 of it is the stream's transform)"""
+
+    def handle(self):
+        """the dsr._capi.Stc / Lda of this stream (the batch entries)"""
+        return self._xf
+
+    def matrix(self):
+        return self._xf.transform(0)
+
+    def setMatrix(self, M):
+        self._xf.set_transform(M, 0)
+
+    def save(self, fileName):
+        self._xf.save(fileName, 0)
+
+    def load(self, fileName):
+        self._xf.load(fileName, 0)
+
+
+class STCTransformerPtr(_MatrixStream):
+    """STCTransformer(src, sbFtSz = 0, nSubFt = 0, nm) (adapt.i:228-272, transform.cc:1788-1879) over dsr_stc_* (include/dsr.h section 12):
+    src under a square matrix, the identity until load() or an estimate.  One sub-feature: sbFtSz is src.size() (0: take it), nSubFt 0 or 1.
+    save / load: raw doubles."""
+
+    def __init__(self, src, sbFtSz=0, nSubFt=0, nm="STC Transformer", _cascade=False, _mmi=False):
+        if nSubFt not in (0, 1) or sbFtSz not in (0, src.size()):
+            raise K.DsrError(K.E_DIMENSION, "STCTransformer is built for one sub-feature of the source's size (%d), not %d x %d" % (src.size(), sbFtSz, nSubFt))
+        h, _ = _new(K.load().dsr_stc_feature_create, src._h, int(bool(_cascade)), int(bool(_mmi)), nm.encode())
+        FeatureStreamPtr.__init__(self, h, keep=(src,))
+        self._src = src; self._bind()
+
+    def _bind(self):
+        self._xf = K.Stc(handle=C.c_void_p(K.load().dsr_stc_feature_handle(self._h)), owner=self)
+
+
+class LDATransformerPtr(_MatrixStream):
+    """LDATransformer(src, sbFtSz = 0, nSubFt = 0, nm) (adapt.i:275-304, transform.cc:1882-1984): the first sbFtSz rows of a src.size() x
+    src.size() matrix, so the feature may shrink (0: src.size()).  save writes float32, load reads float64 -- the reference's own "HACK"
+    (transform.cc:1961-1984), kept: a saved matrix is not read back by load()."""
+
+    def __init__(self, src, sbFtSz=0, nSubFt=0, nm="LDA Transformer"):
+        if nSubFt not in (0, 1):
+            raise K.DsrError(K.E_DIMENSION, "LDATransformer is built for one sub-feature, not %d" % nSubFt)
+        h, _ = _new(K.load().dsr_lda_feature_create, src._h, int(sbFtSz) or src.size(), nm.encode())
+        FeatureStreamPtr.__init__(self, h, keep=(src,))
+        self._src = src; self._bind()
+
+    def _bind(self):
+        self._xf = K.Lda(handle=C.c_void_p(K.load().dsr_lda_feature_handle(self._h)), owner=self)

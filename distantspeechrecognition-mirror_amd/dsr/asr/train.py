@@ -15,7 +15,7 @@ import numpy as np
 
 from .. import _capi as K
 from ..btk.stream import FeatureStreamPtr, _new
-from .adapt import CodebookSetAdaptPtr, TransformerTreePtr
+from .adapt import CodebookSetAdaptPtr, LDATransformerPtr, STCTransformerPtr, TransformerTreePtr
 from .gaussian import DistribSetBasicPtr
 
 
@@ -189,6 +189,103 @@ class EstimatorTreeMLLRPtr(TransformerTreePtr):
 def estimateAdaptationParameters(tree):
     """estimateAdapt.cc:3064-3078: an MLLR parameter tree is cleared, then every leaf is estimated with back-off"""
     tree._estimate()
+
+
+class _PathEstimator(object):
+    """what STCEstimatorPtr and LDAEstimatorPtr share: the frames of a path.  accumulate() takes the scoring frames from the feature stream of
+    the distribution set's codebooks and the statistics' frames from src, both pulled from frame 0 after a reset(); setFeatures() hands over
+    frames that are on the device already."""
+    _feats = None
+
+    def setFeatures(self, xScore, xSrc=None):
+        """cuda float32 [T][dimN]: the codebooks' frames and src's (None, None: pull them from the streams again)"""
+        self._feats = None if xScore is None else (xScore, xScore if xSrc is None else xSrc)
+
+    def _frames(self, T):
+        import torch
+        if self._feats is not None:
+            return self._feats
+
+        def pull(s):
+            s.reset(); rows = [np.array(s.next(t), np.float32) for t in range(T)]
+            return torch.from_numpy(np.stack(rows) if rows else np.zeros((0, s.size()), np.float32)).cuda().contiguous()
+        xSrc = pull(self._src)
+        feat = self._dss._feat
+        return (xSrc if feat is self._src else pull(feat)), xSrc
+
+    def _ids(self, path):
+        return [self._dss.index(n) if isinstance(n, str) else int(n) for n in path]
+
+    def zeroAccu(self):
+        self._xf.zero(0)
+
+    def saveAccu(self, fileName):
+        self._xf.save_accu(fileName, 0)
+
+    def loadAccu(self, fileName):
+        self._xf.load_accu(fileName, 0)
+
+
+class STCEstimatorPtr(_PathEstimator, STCTransformerPtr):
+    """STCEstimator(src, pt, dss, idx = 0, bt = CepstralFeat, cascade = False, mmiEstimation = False, trace = 1, nm) (train.i:390-436,
+    estimateAdapt.cc:2203-2711) over dsr_stc_* (include/dsr.h section 12).  pt, idx, bt and trace are accepted and unused: the parameter-tree
+    path of this estimator ends in "Method not yet finished" in the reference (estimateAdapt.cc:2466-2469).
+
+        stc = STCEstimatorPtr(src, None, dss); stc.accumulate(decoder.bestPath()); stc.estimate(); stc.save("stc.mat")
+    """
+
+    def __init__(self, src, pt, dss, idx=0, bt=None, cascade=False, mmiEstimation=False, trace=1, nm="STC Estimator"):
+        STCTransformerPtr.__init__(self, src, 0, 0, nm, _cascade=cascade, _mmi=mmiEstimation)
+        K.check(K.load().dsr_stc_feature_distrib_set(self._h, dss.gmm.h))
+        self._dss, self._pt, self._idx, self._bt, self._trace = dss, pt, idx, bt, trace
+        self._bind(); self._xf.gmm = dss.gmm
+
+    def accumulate(self, path, factor=1.0):
+        """accumulate(path, factor) (estimateAdapt.cc:2265-2294): path = DecoderFlyWeightPtr.bestPath()"""
+        ids = self._ids(path); xScore, xSrc = self._frames(len(ids))
+        n = self._xf.accumulate_path(xScore, ids, 0, factor, xSrc=xSrc)
+        print("STCEstimator: accumulated %d %s frames." % (n, "numerator" if factor > 0.0 else "denominator"))
+
+    def estimate(self, rc=1, minE=1.0, multE=1.0):
+        self._xf.estimate(0, minE, multE)
+        print("Using E = %g" % self._xf.E(0))
+        return self
+
+    def transMatrix(self):
+        return self._xf.trans_matrix(0)
+
+    def save(self, fileName, trans=None):
+        """STCEstimator::save(fileName, trans) (estimateAdapt.cc:2327-2346): the float matrix, times `trans` (an LDA matrix in front) when given"""
+        self._xf.save_float(fileName, trans, 0)
+
+    def totalPr(self):
+        return self._xf.get_accu(0)["totalPr"]
+
+    def totalT(self):
+        return self._xf.get_accu(0)["totalT"]
+
+
+class LDAEstimatorPtr(_PathEstimator, LDATransformerPtr):
+    """LDAEstimator(src, pt, dss, globalCodebook, idx = 0, bt = CepstralFeat, trace = 1) (train.i:461-500, estimateAdapt.cc:2714-3036).
+    globalCodebook: a distribution or codebook set (or Gmm) whose codebook 0 is the global codebook.  pt, idx, bt and trace are accepted and
+    unused.  The output size is the model's dimN (LDATransformer(src, orgSubFeatLen, nSubFeat)); a narrower LDATransformerPtr takes the first
+    rows of the saved matrix."""
+
+    def __init__(self, src, pt, dss, globalCodebook, idx=0, bt=None, trace=1):
+        LDATransformerPtr.__init__(self, src, 0, 0)
+        g = globalCodebook if isinstance(globalCodebook, K.Gmm) else getattr(globalCodebook, "gmm", None) or globalCodebook._model()
+        K.check(K.load().dsr_lda_feature_codebooks(self._h, dss.gmm.h, g.h))
+        self._dss, self._global, self._pt, self._idx, self._bt, self._trace = dss, g, pt, idx, bt, trace
+        self._bind(); self._xf.gmm, self._xf.globalGmm = dss.gmm, g
+
+    def accumulate(self, path, factor=1.0):
+        """accumulate(path, factor) (estimateAdapt.cc:2761-2790) -> the summed score"""
+        ids = self._ids(path); xScore, xSrc = self._frames(len(ids))
+        return self._xf.accumulate_path(xScore, ids, 0, factor, xSrc=xSrc)
+
+    def estimate(self, rc=1):
+        self._xf.estimate(0)
+        return self
 
 
 class FeatureSpaceAdaptationFeaturePtr(FeatureStreamPtr):

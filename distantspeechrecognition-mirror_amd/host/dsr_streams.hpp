@@ -1497,3 +1497,106 @@ class FeatureSpaceAdaptationFeature : public VectorFloatFeatureStream {
   VectorFloatFeatureStreamPtr _s; DistribSetBasicPtr _dss;
 };
 typedef std::shared_ptr<FeatureSpaceAdaptationFeature> FeatureSpaceAdaptationFeaturePtr;
+
+// ---- asr/adapt/transform.h, adapt.i:228-304: STCTransformer / LDATransformer(src, sbFtSz, nSubFt, nm) over dsr_stc_* / dsr_lda_* (include/dsr.h
+// section 12), for one sub-feature: src under matrix 0 of the handle the stream owns -- the identity until load() or an estimate.
+class STCTransformer : public VectorFloatFeatureStream {
+ public:
+  STCTransformer(VectorFloatFeatureStreamPtr& src, unsigned sbFtSz = 0, unsigned nSubFt = 0, const String& nm = "STC Transformer") : _s(src) { make(sbFtSz, nSubFt, nm, false, false); }
+  dsr_stc* stcHandle() const { return dsr_stc_feature_handle(_h); }
+  virtual void save(const String& fileName) { dsr_throw(dsr_stc_save(stcHandle(), fileName.c_str(), 0)); }         // raw doubles, transform.cc:1852-1857
+  virtual void load(const String& fileName) { dsr_throw(dsr_stc_load(stcHandle(), fileName.c_str(), 0)); }
+  std::vector<double> matrix() const { const size_t D = size(); std::vector<double> A(D * D); dsr_throw(dsr_stc_get_transform(stcHandle(), 0, A.data(), 0)); return A; }
+ protected:
+  STCTransformer(VectorFloatFeatureStreamPtr& src, const String& nm, bool cascade, bool mmi) : _s(src) { make(0, 0, nm, cascade, mmi); }
+  VectorFloatFeatureStreamPtr _s;
+ private:
+  void make(unsigned sbFtSz, unsigned nSubFt, const String& nm, bool cascade, bool mmi) {
+    if (nSubFt > 1 || (sbFtSz != 0 && sbFtSz != _s->size())) throw jdimension_error("STCTransformer is built for one sub-feature of the source's size");
+    dsr_stream* h = 0; dsr_throw(dsr_stc_feature_create(_s->handle(), cascade, mmi, nm.c_str(), &h)); this->adopt(h);
+  }
+};
+typedef std::shared_ptr<STCTransformer> STCTransformerPtr;
+
+class LDATransformer : public VectorFloatFeatureStream {
+ public:
+  LDATransformer(VectorFloatFeatureStreamPtr& src, unsigned sbFtSz = 0, unsigned nSubFt = 0, const String& nm = "LDA Transformer") : _s(src) {
+    if (nSubFt > 1) throw jdimension_error("LDATransformer is built for one sub-feature");
+    dsr_stream* h = 0; dsr_throw(dsr_lda_feature_create(src->handle(), (int) (sbFtSz ? sbFtSz : src->size()), nm.c_str(), &h)); this->adopt(h);
+  }
+  dsr_lda* ldaHandle() const { return dsr_lda_feature_handle(_h); }
+  void save(const String& fileName) const { dsr_throw(dsr_lda_save(ldaHandle(), fileName.c_str(), 0)); }            // float32, transform.cc:1961-1977
+  void load(const String& fileName) { dsr_throw(dsr_lda_load(ldaHandle(), fileName.c_str(), 0)); }                  // float64, transform.cc:1979-1984
+  std::vector<double> matrix() const { const size_t D = _s->size(); std::vector<double> L(D * D); dsr_throw(dsr_lda_get_transform(ldaHandle(), 0, L.data())); return L; }
+ protected:
+  VectorFloatFeatureStreamPtr _s;
+};
+typedef std::shared_ptr<LDATransformer> LDATransformerPtr;
+
+// ---- asr/train/estimateAdapt.h, train.i:390-500: STCEstimator / LDAEstimator.  pt, idx, bt and trace are accepted and unused (the parameter-tree
+// path ends in "Method not yet finished" in the reference).  accumulate() pulls the scoring frames from the feature stream of the distribution
+// set and the statistics' frames from src, both from frame 0 after a reset().
+enum BiasType { CepstralFeat = 0, AllFeat = 1 };
+namespace dsr_detail {
+template <class Upload> void path_frames(VectorFloatFeatureStreamPtr& src, DistribSetBasic& dss, size_t T, Upload upload) {
+  const size_t D = src->size(); std::vector<float> a(T * D + 1), b(T * D + 1);
+  src->reset();
+  for (size_t t = 0; t < T; t++) { const float* p = src->next((int) t); for (size_t d = 0; d < D; d++) b[t * D + d] = p[d]; }
+  VectorFloatFeatureStreamPtr& f = dss.featureStream();
+  if (f.get() == src.get()) a = b;
+  else { f->reset(); for (size_t t = 0; t < T; t++) { const float* p = f->next((int) t); for (size_t d = 0; d < D; d++) a[t * D + d] = p[d]; } }
+  upload(a.data(), b.data());
+}
+}
+class STCEstimator : public STCTransformer {
+ public:
+  STCEstimator(VectorFloatFeatureStreamPtr& src, ParamTreePtr& pt, DistribSetTrainPtr& dss, unsigned idx = 0, BiasType bt = CepstralFeat, bool cascade = false,
+               bool mmiEstimation = false, int trace = 1, const String& nm = "STC Estimator")
+    : STCTransformer(src, nm, cascade, mmiEstimation), _dss(dss) { (void) pt; (void) idx; (void) bt; (void) trace; dsr_throw(dsr_stc_feature_distrib_set(_h, dss->gmm())); }
+  void accumulate(const DistribPath& path, float factor = 1.0f) {           // estimateAdapt.cc:2265-2294
+    std::vector<int32_t> ids(path.size()); for (size_t i = 0; i < path.size(); i++) ids[i] = (int32_t) _dss->index(path[i]);
+    const float *xs = 0, *xr = 0; dsr_stc* h = stcHandle(); const int64_t T = (int64_t) path.size();
+    dsr_detail::path_frames(_s, *_dss, path.size(), [&](const float* a, const float* b) { dsr_throw(dsr_stc_upload_features(h, a, b, T, &xs, &xr)); });
+    unsigned n = 0; dsr_throw(dsr_stc_accumulate_path(h, xs, xr, T, ids.data(), T, 0, factor, &n, 0));
+    printf("STCEstimator: accumulated %u %s frames.\n", n, factor > 0.0f ? "numerator" : "denominator"); fflush(stdout);
+  }
+  STCEstimator& estimate(unsigned rc = 1, double minE = 1.0, double multE = 1.0) {
+    (void) rc; const int32_t e = 0; dsr_throw(dsr_stc_estimate(stcHandle(), &e, 1, minE, multE, 0));
+    double E = 0.0; dsr_throw(dsr_stc_E(stcHandle(), 0, &E)); printf("Using E = %g\n", E); fflush(stdout); return *this;
+  }
+  std::vector<float> transMatrix() const { const size_t D = size(); std::vector<float> T(D * D); dsr_throw(dsr_stc_trans_matrix(stcHandle(), 0, T.data())); return T; }
+  // STCEstimator::save(fileName, trans) (estimateAdapt.cc:2327-2346): the float matrix, times trans [dimN][dimN] when given
+  void save(const String& fileName, const float* trans) { dsr_throw(dsr_stc_save_float(stcHandle(), fileName.c_str(), 0, trans)); }
+  virtual void save(const String& fileName) { save(fileName, 0); }
+  void zeroAccu() { dsr_throw(dsr_stc_zero(stcHandle(), 0)); }
+  void saveAccu(const String& fileName) const { dsr_throw(dsr_stc_save_accu(stcHandle(), fileName.c_str(), 0)); }
+  void loadAccu(const String& fileName) { dsr_throw(dsr_stc_load_accu(stcHandle(), fileName.c_str(), 0)); }
+  double totalPr() const { double p = 0.0; dsr_throw(dsr_stc_get_accu(stcHandle(), 0, 0, 0, 0, &p, 0, 0, 0)); return p; }
+  unsigned totalT() const { unsigned t = 0; dsr_throw(dsr_stc_get_accu(stcHandle(), 0, 0, 0, 0, 0, &t, 0, 0)); return t; }
+ private:
+  DistribSetTrainPtr _dss;
+};
+typedef std::shared_ptr<STCEstimator> STCEstimatorPtr;
+
+class LDAEstimator : public LDATransformer {
+ public:
+  // globalCodebook: a distribution set whose codebook 0 is the global codebook
+  LDAEstimator(VectorFloatFeatureStreamPtr& src, ParamTreePtr& pt, DistribSetTrainPtr& dss, const DistribSetBasicPtr& globalCodebook, unsigned idx = 0,
+               BiasType bt = CepstralFeat, int trace = 1)
+    : LDATransformer(src, 0, 0), _dss(dss), _global(globalCodebook) {
+    (void) pt; (void) idx; (void) bt; (void) trace; dsr_throw(dsr_lda_feature_codebooks(_h, dss->gmm(), globalCodebook->gmm()));
+  }
+  double accumulate(const DistribPath& path, float factor = 1.0f) {         // estimateAdapt.cc:2761-2790
+    std::vector<int32_t> ids(path.size()); for (size_t i = 0; i < path.size(); i++) ids[i] = (int32_t) _dss->index(path[i]);
+    const float *xs = 0, *xr = 0; dsr_lda* h = ldaHandle(); const int64_t T = (int64_t) path.size();
+    dsr_detail::path_frames(_s, *_dss, path.size(), [&](const float* a, const float* b) { dsr_throw(dsr_lda_upload_features(h, a, b, T, &xs, &xr)); });
+    double score = 0.0; dsr_throw(dsr_lda_accumulate_path(h, xs, xr, T, ids.data(), T, 0, factor, &score, 0)); return score;
+  }
+  LDAEstimator& estimate(unsigned rc = 1) { (void) rc; const int32_t e = 0; dsr_throw(dsr_lda_estimate(ldaHandle(), &e, 1, 0)); return *this; }
+  void zeroAccu() { dsr_throw(dsr_lda_zero(ldaHandle(), 0)); }
+  void saveAccu(const String& fileName) const { dsr_throw(dsr_lda_save_accu(ldaHandle(), fileName.c_str(), 0)); }
+  void loadAccu(const String& fileName) { dsr_throw(dsr_lda_load_accu(ldaHandle(), fileName.c_str(), 0)); }
+ private:
+  DistribSetTrainPtr _dss; DistribSetBasicPtr _global;
+};
+typedef std::shared_ptr<LDAEstimator> LDAEstimatorPtr;

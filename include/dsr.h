@@ -2123,6 +2123,139 @@ dsr_status dsr_fsa_feature_create(dsr_stream* src, int maxAccu, int maxTran, con
 dsr_status dsr_fsa_feature_distrib_set(dsr_stream*, dsr_gmm*);
 dsr_fsa* dsr_fsa_feature_handle(dsr_stream*);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------------
+ * 12. Semi-tied covariance (STC) and LDA transforms: estimation and application (csrc/k_stc.hip, csrc/stc.cpp, csrc/stc_rows.h)
+ *
+ *    Replaces STCTransformer / LDATransformer (asr/adapt/transform.cc:1788-1984, "tr") and STCEstimator / LDAEstimator
+ *    (asr/train/estimateAdapt.cc:2203-3036, "eA"; train.i:390-500) for models of one sub-feature (nSubFeat = 1, subFeatLen = dimN <= 64).
+ *    A handle holds nEst estimators over one model; one item is (frame, distribution, factor, estimator).  The Gaussian of an item is the
+ *    one-hot addCount of CodebookBasic::_scoreOpt under the SCORING frame, found with scoring mode 0's arithmetic; the statistics are made
+ *    from the SOURCE frame.  The sums over the items of a call are fp64 MFMA contractions cut into fixed chunks and reduced in a fixed order
+ *    (no floating-point atomics).  The means and inverse variances the statistics use are copied when the handle is created (as dsr_fsa does),
+ *    while the nearest Gaussian is found with the model's live tables: a handle is made after the model's last update; the model must outlive
+ *    it.  The host adds the sums to accumulators it holds as the reference does: the lower triangle is written, and
+ *    copyUpperTriangle runs on every read through the reference's accessors (estimateAdapt.h:688-689, 813-815) -- get_accu with
+ *    throughAccessor != 0, save_accu and estimate.
+ *
+ *  STC
+ *   create             STCEstimator(src, pt, dss, idx, bt, cascade, mmiEstimation, ...) (eA:2205-2235): zeroed accumulators, identity matrices
+ *   create_transformer STCTransformer(src, sbFtSz, nSubFt, nm) (tr:1790-1796): one matrix and no statistics: accumulate, estimate and every
+ *                      accumulator entry (increment, zero, get / set_accu, save / load_accu, aux) return DSR_E_CONSISTENCY; the same for LDA
+ *   accumulate         accumulateW1 / accumulateW2 (eA:2569-2651) over M items: o = float(x - mu_g), wgt_d = float(iv_gd float(addCount factor)),
+ *                      sumOsq[d][i][j] += (wgt_d o_i) o_j for j <= i; _count / _denCount per item as eA:2581-2584; for factor <= 0
+ *                      regSq[d] += iv_gd sum_col float(c / iv_g,col) a_col a_col^T with a_col the columns of _stcInv, summed as
+ *                      R[d][col] = sum_n iv[n,d] float(c_n / iv[n,col]) on the device and R[d][col] a_col a_col^T once on the host: the float
+ *                      roundings stand where the reference has them, only the order of the fp64 sum differs.  With cascade the source frame
+ *                      is first put under the estimator's current matrix (eA:2276-2278).  nearest [M] / score [M] (or NULL): the Gaussian
+ *                      inside its codebook and the distribution's mode 0 score of every item.
+ *   accumulate_path    accumulate(path, factor) (eA:2265-2294): distIds [pathLen], one distribution per frame from frame 0, then increment
+ *                      (eA:2284-2287).  A negative id is DSR_E_INDEX (DistribSet::find throws there).
+ *   increment, zero    Accu::increment (estimateAdapt.h:681), Accu::zero (eA:2511-2519)
+ *   get / set_accu     _count, _denCount, _totalPr, _totalT, sumOsq [dimN][dimN][dimN], regSq likewise
+ *   save / load_accu   Accu::save / load (eA:2521-2566): big-endian ints and floats (counts and totalPr rounded to float), matrices raw native
+ *                      doubles as gsl_matrix_fwrite writes them; loading ADDS; DSR_E_DIMENSION for another dimN or nSubFeat != 1
+ *   estimate           estimate(rc, minE, multE) (eA:2296-2316) for n estimators at once: makePosDef (eA:2689-2711), the inverses of
+ *                      sumOsq[d] + E regSq[d] (eA:2400-2410) and MaxItns = 10 sweeps of row updates (eA:2416-2448) on the device.  Only the
+ *                      sign of det A is carried.  With cascade the new matrix left-multiplies the old (eA:2298-2307); _stcInv is refreshed.
+ *                      An estimator whose statistics are not finite, cannot be made positive definite, whose inner product is <= 0 (the
+ *                      reference's jnumeric_error, eA:2434-2435) or whose matrix leaves ||A||_F ||A^-1||_F < 1e7 keeps its matrix; the others
+ *                      of the call are done and the call returns DSR_E_CONSISTENCY.  status: 0 or DSR_E_CONSISTENCY of the last estimate.
+ *   E                  Accu::E() of the last estimate
+ *   aux                2 gamma log |det A| - sum_d a_d (sumOsq[d] + E regSq[d]) a_d^T, gamma = count or denCount E: the function the row
+ *                      update maximises.  NOT calcAuxFunc's printed value (eA:2665-2686), whose E term stands outside the product.
+ *                      A == NULL: the estimator's matrix.
+ *   get / set_transform  matrix() and _stcInv as doubles; set refreshes _stcInv (DSR_E_CONSISTENCY for a singular matrix)
+ *   trans_matrix       transMatrix() (eA:2318-2325): the float copy
+ *   save / load        STCTransformer::save / load (tr:1852-1864): raw doubles; load refreshes _stcInv as STCEstimator::load (eA:2348-2356)
+ *   save_float         STCEstimator::save(fileName, trans) (eA:2327-2346): the float matrix, times trans [dimN][dimN] when given
+ *   apply              _transform (tr:1866-1879): out = float(sum_j double(x_j) A[i][j]), j ascending, no bias
+ *   kernel_ms          nearest, statistics + reduction, eigen-decompositions, rows, apply (after set_timing)
+ *
+ *  LDA
+ *   create             LDAEstimator(src, pt, dss, globalCodebook, ...) (eA:2716-2735): global = a model whose codebook 0 is the global codebook.
+ *                      The reference never zeroes its accumulators before use (eA:2877-2894); here they start from zero.
+ *   create_transformer LDATransformer(src, sbFtSz, nSubFt, nm) (tr:1884-1897)
+ *   accumulate         Accu::accumulate (eA:2989-3036): count = float(addCount factor); within += count oW oW^T, between += count oB oB^T,
+ *                      mixture += count oM oM^T over j <= i with the float differences oW = x - mu_g, oB = mu_g - mu_0, oM = x - mu_0, mu_0
+ *                      Gaussian 0 of the global codebook.  A codebook whose refN differs from the global codebook's is DSR_E_DIMENSION (eA:2995).
+ *   accumulate_path    accumulate(path, factor) (eA:2761-2790) -> the summed score
+ *   zero, get / set_accu, save / load_accu   eA:2908-2980: matrices raw doubles, the count last and as a float
+ *   estimate           estimate(rc) (eA:2752-2836): scaleScatterMatrices divides the accumulators IN PLACE (a second estimate divides again),
+ *                      then the simultaneous diagonalisation by two Jacobi eigen-decompositions on the device, n estimators a call
+ *   eigenvalues        of `within` (as found) and of the whitened `between` (descending) of the last estimate
+ *   get / set_transform, apply   the Din x Din matrix; apply writes the first outDim rows (tr:1948-1955)
+ *   save / load        LDATransformer::save writes float32, load reads float64 (tr:1961-1984, the reference's own "HACK"): kept as they are
+ */
+typedef struct dsr_stc dsr_stc;
+typedef struct dsr_lda dsr_lda;
+dsr_status dsr_stc_create(dsr_gmm*, int nEst, int cascade, int mmiEstimation, dsr_stc** out);
+dsr_status dsr_stc_create_transformer(int dimN, dsr_stc** out);
+void dsr_stc_destroy(dsr_stc*);
+int dsr_stc_dim(const dsr_stc*);
+int dsr_stc_num_estimators(const dsr_stc*);
+dsr_status dsr_stc_accumulate(dsr_stc*, const float* xScore_dev, const float* xSrc_dev, int64_t N, const int32_t* frame, const int32_t* dist,
+                              const float* factor, const int32_t* est, int64_t M, int32_t* nearest, float* score, void* stream);
+dsr_status dsr_stc_accumulate_path(dsr_stc*, const float* xScore_dev, const float* xSrc_dev, int64_t T, const int32_t* distIds, int64_t pathLen,
+                                   int estX, float factor, unsigned* framesN, void* stream);
+/* frames of a host program: copied to buffers the handle owns (valid until the next call) */
+dsr_status dsr_stc_upload_features(dsr_stc*, const float* xScore_host, const float* xSrc_host, int64_t N, const float** xScore_dev, const float** xSrc_dev);
+dsr_status dsr_stc_increment(dsr_stc*, int estX, double totalPr, unsigned totalT);
+dsr_status dsr_stc_zero(dsr_stc*, int estX);
+dsr_status dsr_stc_get_accu(dsr_stc*, int estX, int throughAccessor, double* count, double* denCount, double* totalPr, unsigned* totalT, double* sumOsq,
+                            double* regSq);
+dsr_status dsr_stc_set_accu(dsr_stc*, int estX, const double* count, const double* denCount, const double* totalPr, const unsigned* totalT,
+                            const double* sumOsq, const double* regSq);
+dsr_status dsr_stc_save_accu(dsr_stc*, const char* fileName, int estX);
+dsr_status dsr_stc_load_accu(dsr_stc*, const char* fileName, int estX);
+dsr_status dsr_stc_estimate(dsr_stc*, const int32_t* estX, int n, double minE, double multE, void* stream);
+int dsr_stc_status(const dsr_stc*, int estX);
+dsr_status dsr_stc_E(const dsr_stc*, int estX, double* E);
+dsr_status dsr_stc_aux(const dsr_stc*, int estX, const double* A, double E, double* aux);
+dsr_status dsr_stc_get_transform(const dsr_stc*, int estX, double* A, double* Ainv);
+dsr_status dsr_stc_set_transform(dsr_stc*, int estX, const double* A);
+dsr_status dsr_stc_trans_matrix(const dsr_stc*, int estX, float* out);
+dsr_status dsr_stc_save(const dsr_stc*, const char* fileName, int estX);
+dsr_status dsr_stc_load(dsr_stc*, const char* fileName, int estX);
+dsr_status dsr_stc_save_float(const dsr_stc*, const char* fileName, int estX, const float* trans);
+dsr_status dsr_stc_apply(dsr_stc*, const float* x_dev, int64_t N, int estX, float* out_dev, void* stream);
+dsr_status dsr_stc_set_timing(dsr_stc*, int on);
+dsr_status dsr_stc_kernel_ms(const dsr_stc*, float ms[5]);
+dsr_status dsr_lda_create(dsr_gmm*, dsr_gmm* global, int nEst, dsr_lda** out);
+dsr_status dsr_lda_create_transformer(int dimN, dsr_lda** out);
+void dsr_lda_destroy(dsr_lda*);
+int dsr_lda_dim(const dsr_lda*);
+int dsr_lda_num_estimators(const dsr_lda*);
+dsr_status dsr_lda_accumulate(dsr_lda*, const float* xScore_dev, const float* xSrc_dev, int64_t N, const int32_t* frame, const int32_t* dist,
+                              const float* factor, const int32_t* est, int64_t M, int32_t* nearest, float* score, void* stream);
+dsr_status dsr_lda_accumulate_path(dsr_lda*, const float* xScore_dev, const float* xSrc_dev, int64_t T, const int32_t* distIds, int64_t pathLen,
+                                   int estX, float factor, double* score, void* stream);
+dsr_status dsr_lda_upload_features(dsr_lda*, const float* xScore_host, const float* xSrc_host, int64_t N, const float** xScore_dev, const float** xSrc_dev);
+dsr_status dsr_lda_zero(dsr_lda*, int estX);
+dsr_status dsr_lda_get_accu(dsr_lda*, int estX, int throughAccessor, double* count, double* within, double* between, double* mixture);
+dsr_status dsr_lda_set_accu(dsr_lda*, int estX, const double* count, const double* within, const double* between, const double* mixture);
+dsr_status dsr_lda_save_accu(dsr_lda*, const char* fileName, int estX);
+dsr_status dsr_lda_load_accu(dsr_lda*, const char* fileName, int estX);
+dsr_status dsr_lda_estimate(dsr_lda*, const int32_t* estX, int n, void* stream);
+int dsr_lda_status(const dsr_lda*, int estX);
+dsr_status dsr_lda_eigenvalues(const dsr_lda*, int estX, double* withinEv, double* betweenEv);
+dsr_status dsr_lda_get_transform(const dsr_lda*, int estX, double* L);
+dsr_status dsr_lda_set_transform(dsr_lda*, int estX, const double* L);
+dsr_status dsr_lda_save(const dsr_lda*, const char* fileName, int estX);
+dsr_status dsr_lda_load(dsr_lda*, const char* fileName, int estX);
+dsr_status dsr_lda_apply(dsr_lda*, const float* x_dev, int64_t N, int estX, int outDim, float* out_dev, void* stream);
+dsr_status dsr_lda_set_timing(dsr_lda*, int on);
+dsr_status dsr_lda_kernel_ms(const dsr_lda*, float ms[5]);
+/* The stream operators (VectorFloatFeatureStreams): src under matrix 0 of the operator's handle -- for LDA its first outDim rows --, frames
+ * kept on the device, so dsr_distribset_create(gmm, stream, ...) + dsr_decoder_decode_stream decode transformed frames without a host round
+ * trip.  The handle is a bare transformer until distrib_set / codebooks names the model; it keeps its matrix then.  A new matrix shows after
+ * the next reset(). */
+dsr_status dsr_stc_feature_create(dsr_stream* src, int cascade, int mmiEstimation, const char* name, dsr_stream** out);
+dsr_status dsr_stc_feature_distrib_set(dsr_stream*, dsr_gmm*);
+dsr_stc* dsr_stc_feature_handle(dsr_stream*);
+dsr_status dsr_lda_feature_create(dsr_stream* src, int outDim, const char* name, dsr_stream** out);
+dsr_status dsr_lda_feature_codebooks(dsr_stream*, dsr_gmm*, dsr_gmm* global);
+dsr_lda* dsr_lda_feature_handle(dsr_stream*);
+
 #ifdef __cplusplus
 }
 #endif

@@ -504,6 +504,10 @@ dsr_status dsr_bf_get(const dsr_bf* cs, int kind, double* out, size_t nd)
 namespace dsr { bool bf_has_fixed_weights(const dsr_bf* s) { return s && !s->rlsOn && !s->halfBandShift; } }
 namespace dsr { const float2* bf_fixed_weights_dev(dsr_bf* s) { if (!bf_has_fixed_weights(s)) return nullptr; if (s->dirty) refresh_effective(*s); return s->d_wT.p; } }
 
+// the quiescent vectors [M][C] and blocking matrices [M][C][C-1] calcGSCWeights left, for the maximum-kurtosis estimator (k_mk.hip); false without them
+namespace dsr { bool bf_gsc_fixed_weights(const dsr_bf* s, int* M, int* C, int* halfBandShift, const zc** wq, const zc** B)
+{ if (!s || !s->haveWq || !s->haveB) return false; *M = s->M; *C = s->C; *halfBandShift = s->halfBandShift; *wq = s->wq.data(); *B = s->B.data(); return true; } }
+
 dsr_status dsr_bf_apply(dsr_bf* s, const float* X, int U, int Tmax, float* Y, void* stream)
 {
   return guard([&] {

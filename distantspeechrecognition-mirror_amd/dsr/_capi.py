@@ -1193,6 +1193,117 @@ def bf_rls_path(chanN):
     return tuple(out), tuple(lds)
 
 
+MK_PR, MK_NRM = 0, 1
+MK_EXIT_MAX_ITERATIONS, MK_EXIT_GRADIENT, MK_EXIT_DIFFERENCE, MK_EXIT_NO_PROGRESS, MK_EXIT_EVAL_CAP, MK_EXIT_SKIPPED = 0, 1, 2, 3, 4, 5
+MK_FRAMES_LDS, MK_FRAMES_STREAMED = 0, 1
+MK_EVAL_CAP = 2048
+
+
+def mk_path(chanN, Tsel):
+    """-> ((CT, residence), (frames that fit the LDS residence, dynamic LDS of the launch)): the k_mk_minimize<CT> dsr_mk_estimate launches for chanN
+    channels and Tsel selected frames, and where a problem's frames live; needs no device"""
+    L = load()
+    out = (C.c_int * 2)(); lds = (C.c_int64 * 2)()
+    check(L.dsr_mk_path(int(chanN), int(Tsel), out, lds))
+    return tuple(out), tuple(lds)
+
+
+class MkBeamformer:
+    """Maximum empirical kurtosis beamforming (btk/lib/mkBeamforming.py: MEKSubbandBeamformer_pr / _nrm) for a batch: every (utterance, bin) is one
+    problem, all of them minimised in one launch.  kind: MK_PR (conjugate gradient) or MK_NRM (steepest descent, |wa| clipped to |gamma|); the
+    defaults of alpha and DIFFSTOPTOLERANCE are the reference's for that kind."""
+
+    def __init__(self, fftLen, chanN, kind=MK_PR, alpha=None, beta=3.0, gamma=-1.0, NC=1, nSource=1, halfBandShift=False):
+        L = load()
+        self.h = vp(); self.M, self.C, self.F, self.kind = fftLen, chanN, fftLen // 2 + 1, kind
+        check(L.dsr_mk_create(fftLen, chanN, int(NC), int(nSource), int(bool(halfBandShift)), C.byref(self.h)))
+        self.config(kind, (1.0e-2 if kind == MK_PR else 0.1) if alpha is None else alpha, beta, gamma)
+        self.minimizer()
+
+    def __del__(self):
+        if _lib is not None and getattr(self, "h", None):
+            _lib.dsr_mk_destroy(self.h)
+
+    def config(self, kind, alpha, beta=3.0, gamma=-1.0):
+        check(_lib.dsr_mk_config(self.h, int(kind), alpha, beta, gamma)); self.kind, self.alpha = kind, alpha
+
+    def minimizer(self, MAXITNS=40, TOLERANCE=1.0e-3, STOPTOLERANCE=1.0e-2, DIFFSTOPTOLERANCE=None, STEPSIZE=0.01):
+        if DIFFSTOPTOLERANCE is None:
+            DIFFSTOPTOLERANCE = 1.0e-5 if self.kind == MK_PR else 1.0e-10
+        check(_lib.dsr_mk_minimizer(self.h, int(MAXITNS), TOLERANCE, STOPTOLERANCE, DIFFSTOPTOLERANCE, STEPSIZE))
+
+    def setFixedWeightsFromBeamformer(self, bf):
+        """the quiescent vectors and blocking matrices of a Beamformer after calcGSCWeights"""
+        check(_lib.dsr_mk_set_fixed_weights_from_bf(self.h, bf.h))
+
+    def setFixedWeights(self, wq, B=None):
+        """wq [F][C]; B [F][C][C-1] or None for the blocking matrices of wq"""
+        w = _np(wq, np.complex128)
+        if w.shape != (self.F, self.C):
+            raise DsrError(5, "wq must be %d x %d" % (self.F, self.C))
+        b = None
+        if B is not None:
+            b = _np(B, np.complex128)
+            if b.shape != (self.F, self.C, self.C - 1):
+                raise DsrError(5, "B must be %d x %d x %d" % (self.F, self.C, self.C - 1))
+        check(_lib.dsr_mk_set_fixed_weights(self.h, _ptr(w), _ptr(b) if b is not None else None))
+
+    def getFixedWeights(self):
+        wq = np.zeros((self.F, self.C), np.complex128); B = np.zeros((self.F, self.C, self.C - 1), np.complex128)
+        check(_lib.dsr_mk_get_fixed_weights(self.h, _ptr(wq), _ptr(B)))
+        return wq, B
+
+    def forceStreamed(self, on=True):
+        check(_lib.dsr_mk_force_streamed(self.h, int(bool(on))))
+
+    def _args(self, X, nframes, sFrame, eFrame, R, fbinX):
+        import torch
+        U, Cn, T, F = X.shape
+        if Cn != self.C or F != self.F or X.dtype != torch.complex64:
+            raise DsrError(5, "X must be complex64 [U][%d][T][%d]" % (self.C, self.F))
+        self._keep = (torch.view_as_real(X.contiguous()), nframes)
+        return (_dev(self._keep[0]), _dev(nframes) if nframes is not None else None, U, T, int(sFrame), int(T if eFrame is None else eFrame), int(R), int(fbinX))
+
+    def _wa(self, wa, X):
+        import torch
+        U, n = X.shape[0], self.C - 1
+        if wa is None:
+            return torch.zeros((U, self.F, n), dtype=torch.complex128, device=X.device)
+        wa = torch.as_tensor(wa).to(device=X.device, dtype=torch.complex128)
+        if tuple(wa.shape) != (U, self.F, n):
+            raise DsrError(5, "the active weights must be %d x %d x %d" % (U, self.F, n))
+        return wa.contiguous().clone()
+
+    def eval(self, X, wa, nframes=None, sFrame=0, eFrame=None, R=1, stats=None, fbinX=-1):
+        """X: cuda complex64 [U][C][T][F]; wa [U][F][C-1] complex128; nframes: cuda int32 [U]; stats: cuda fp64 [3][U][F]
+        -> (cost [U][F], packed gradient [U][F][2 (C-1)]) fp64"""
+        import torch
+        a = self._args(X, nframes, sFrame, eFrame, R, fbinX); w = self._wa(wa, X); U = X.shape[0]
+        cost = torch.zeros((U, self.F), dtype=torch.float64, device=X.device)
+        grad = torch.zeros((U, self.F, 2 * (self.C - 1)), dtype=torch.float64, device=X.device)
+        check(_lib.dsr_mk_eval(self.h, *a, _dev(torch.view_as_real(w)), _dev(stats) if stats is not None else None, _dev(cost), _dev(grad), cur_stream()))
+        return cost, grad
+
+    def estimate(self, X, wa=None, nframes=None, sFrame=0, eFrame=None, R=1, stats=None, fbinX=-1):
+        """-> (wa [U][F][C-1] complex128, info [U][F][4] int32: iterations, evaluations, failed trials, exit reason, final cost [U][F]).  wa: the
+        starting point (None: zero).  stats (cuda fp64 [3][U][F]: prevAvgY2, prevAvgY4, prevFrameN) is read, and for MK_NRM updated in place."""
+        import torch
+        a = self._args(X, nframes, sFrame, eFrame, R, fbinX); w = self._wa(wa, X); U = X.shape[0]
+        info = torch.zeros((U, self.F, 4), dtype=torch.int32, device=X.device)
+        cost = torch.zeros((U, self.F), dtype=torch.float64, device=X.device)
+        check(_lib.dsr_mk_estimate(self.h, *a, _dev(torch.view_as_real(w)), _dev(stats) if stats is not None else None, _dev(info), _dev(cost), cur_stream()))
+        return w, info, cost
+
+    def apply(self, X, wa):
+        """Y [U][T][F] = (wq - B wa[u][f])^H X, per-utterance active weights"""
+        import torch
+        U, Cn, T, F = X.shape
+        w = self._wa(wa, X)
+        Y = torch.empty((U, T, F, 2), dtype=torch.float32, device=X.device)
+        check(_lib.dsr_mk_apply(self.h, _dev(torch.view_as_real(X.contiguous())), U, T, _dev(torch.view_as_real(w)), _dev(Y), cur_stream()))
+        return torch.view_as_complex(Y)
+
+
 def zelinski_path(kind, chanN, bf=None):
     """-> (cell, template argument): the kernels a post-filter of that kind (0 Zelinski, 1 McCowan, 2 Lefkimmiatis) launches, behind the beamformer bf
     (apply_bf) or on its own (apply); PF_*; follows DSR_PF_SUM / DSR_PF_NOFUSE / DSR_PF_WAVE / DSR_PF_MEMSTATE; needs no device"""

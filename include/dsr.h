@@ -204,6 +204,62 @@ dsr_status dsr_bf_apply(dsr_bf*, const float* X_dev, int U, int Tmax, float* Y_d
 dsr_status dsr_bf_apply_frames(dsr_bf*, const float* X_dev, const int32_t* nframes_dev, int U, int Tmax, float* Y_dev, void* stream);
 
 /* =====================================================================================
+ * 2a. Maximum empirical kurtosis beamforming: the active weights of a GSC for a whole utterance
+ *     replaces MEKSubbandBeamformer_pr / MEKSubbandBeamformer_nrm (btk/lib/mkBeamforming.py:31-658) with the minimisers they call:
+ *     conjugate_pr (btk/minimizer/conjugate_pr.c, directional_minimize.c) and GSL's steepest_descent
+ * Scope: NC = 1, one source, half spectrum (F = fftLen/2+1 bins).  create refuses halfBandShift and NC != 1 with DSR_E_ERROR (the reference prints
+ * and exits), nSource != 1 with DSR_E_PARAMETER, chanN outside [2, DSR_MK_MAX_CHAN] with DSR_E_DIMENSION.
+ * Every (utterance, bin) is one problem: minimise  -(E|Y|^4 - beta (E|Y|^2)^2) + alpha |wa|^2,  Y_t = (wq - B wa)^H X_t, over the frames
+ * accumObservations(sFrame, eFrame, R) keeps: s with sFrame <= s < min(eFrame, nframes[u], Tmax) and s % R == 0.  All scalars fp64.  The packed
+ * gradient is the derivative with respect to conj(wa): half the real gradient of the cost in the packed variables, as in the reference.
+ * Reduction order (tests/mk_np.py restates it): 64 partial sums, partial p adds frames p, p + 64, ... in increasing order, a fixed binary
+ * tree combines them, the sum is divided by N afterwards; |v| of a packed vector is the square root of the sequential sum of squares.
+ * ===================================================================================== */
+typedef struct dsr_mk dsr_mk;
+#define DSR_MK_MAX_CHAN 64
+#define DSR_MK_EVAL_CAP 2048              /* evaluations within one iteration after which a problem stops with DSR_MK_EXIT_EVAL_CAP */
+enum { DSR_MK_PR = 0,                    /* MEKSubbandBeamformer_pr: conjugate gradient (Polak-Ribiere), weights as they are */
+       DSR_MK_NRM = 1 };                 /* MEKSubbandBeamformer_nrm: steepest descent, |wa| clipped to |gamma| (gamma < 0: |wq|) */
+enum { DSR_MK_EXIT_MAX_ITERATIONS = 0, DSR_MK_EXIT_GRADIENT = 1,   /* |g| < STOPTOLERANCE */
+       DSR_MK_EXIT_DIFFERENCE = 2,       /* |cost before - cost| < DIFFSTOPTOLERANCE */
+       DSR_MK_EXIT_NO_PROGRESS = 3,      /* GSL_ENOPROG */
+       DSR_MK_EXIT_EVAL_CAP = 4,
+       DSR_MK_EXIT_SKIPPED = 5 };        /* no selected frame, or a starting cost that is not finite: weights and statistics unchanged */
+enum { DSR_MK_FRAMES_LDS = 0,            /* a problem's y0 and Z (16 chanN bytes a frame) are copied into LDS once */
+       DSR_MK_FRAMES_STREAMED = 1 };     /* read from the scratch array at every evaluation */
+dsr_status dsr_mk_create(int fftLen, int chanN, int NC, int nSource, int halfBandShift, dsr_mk** out);
+void       dsr_mk_destroy(dsr_mk*);
+/* the quiescent vectors and blocking matrices of a dsr_bf after dsr_bf_calc_gsc_weights (same fftLen and chanN, DSR_E_DIMENSION otherwise;
+   DSR_E_ERROR before calc_gsc_weights): the weights found are then the ones dsr_bf_set_active_weights of that object applies */
+dsr_status dsr_mk_set_fixed_weights_from_bf(dsr_mk*, const dsr_bf*);
+/* wq [F][chanN], B [F][chanN][chanN-1] complex128 (host); B == NULL: the blocking matrices of _calcBlockingMatrix (beamformer.cc:398-479) */
+dsr_status dsr_mk_set_fixed_weights(dsr_mk*, const double* wq, const double* B);
+dsr_status dsr_mk_get_fixed_weights(const dsr_mk*, double* wq, double* B);      /* either may be NULL */
+/* defaults of create: DSR_MK_PR, alpha 1e-2, beta 3, gamma -1; MAXITNS 40, TOLERANCE 1e-3, STOPTOLERANCE 1e-2, DIFFSTOPTOLERANCE 1e-5, STEPSIZE 0.01
+   (the reference's _nrm defaults: alpha 0.1, DIFFSTOPTOLERANCE 1e-10) */
+dsr_status dsr_mk_config(dsr_mk*, int kind, double alpha, double beta, double gamma);
+dsr_status dsr_mk_minimizer(dsr_mk*, int maxItns, double tolerance, double stopTolerance, double diffStopTolerance, double stepSize);
+/* X_dev [U][chanN][Tmax][F] complex64; nframes_dev (optional) [U]; fbinX: one bin, or -1 for every bin (the arrays keep their [U][F] shape; only
+ * the problems run are read and written).  wa_dev [U][F][chanN-1] complex128; stats_dev (optional) [3][U][F] fp64: the carried prevAvgY2,
+ * prevAvgY4, prevFrameN (storeStatistics :410-420).
+ *   eval:     cost_dev [U][F], grad_dev [U][F][2 (chanN-1)] at wa_dev; a problem without a selected frame gets NaN
+ *   estimate: wa_dev in (starting point) and out; info_dev [U][F][4] int32: iterations, evaluations (passes over the frames for a cost, a gradient
+ *             or both), failed trials (_pr: retries of intermediate_point; _nrm: rejected trial points), exit reason; cost_dev [U][F] the final cost.
+ *             DSR_MK_NRM: the weights come back clipped and stats_dev, when given, is updated (prevFrameN is advanced before it divides the new
+ *             terms, as there); DSR_MK_PR: weights as the minimiser left them, stats_dev read only. */
+dsr_status dsr_mk_eval(dsr_mk*, const float* X_dev, const int32_t* nframes_dev, int U, int Tmax, int sFrame, int eFrame, int R, int fbinX,
+                       const double* wa_dev, const double* stats_dev, double* cost_dev, double* grad_dev, void* stream);
+dsr_status dsr_mk_estimate(dsr_mk*, const float* X_dev, const int32_t* nframes_dev, int U, int Tmax, int sFrame, int eFrame, int R, int fbinX,
+                           double* wa_dev, double* stats_dev, int32_t* info_dev, double* cost_dev, void* stream);
+/* Y_dev [U][Tmax][F] = (wq - B wa[u][f])^H X[u][:][t][f] for every bin, weights rounded to fp32 as dsr_bf_apply's are */
+dsr_status dsr_mk_apply(dsr_mk*, const float* X_dev, int U, int Tmax, const double* wa_dev, float* Y_dev, void* stream);
+/* which k_mk_minimize<CT> runs for chanN channels and Tsel selected frames (path[0] = CT: 4, 6, 8, or 0 for the run-time count) and where the
+   frames live (path[1]); lds (optional): lds[0] the frames that fit the LDS residence, lds[1] the dynamic LDS of the launch.  Needs no device.
+   force_streamed(1) takes the LDS residence out for that handle. */
+dsr_status dsr_mk_path(int chanN, int Tsel, int path[2], int64_t lds[2]);
+dsr_status dsr_mk_force_streamed(dsr_mk*, int on);
+
+/* =====================================================================================
  * 2b. Steered-response-power direction of arrival for a linear array
  *     replaces DOAEstimatorSRPDSBLA (btk/beamformer/beamformer.h:462-560, beamformer.i:479-513,
  *     beamformer.cc:2920-3283)

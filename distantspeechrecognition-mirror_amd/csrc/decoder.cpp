@@ -474,6 +474,12 @@ static void report_profile(const long long* prof, int slots)
     for (int c = 0; c < 4; c++) if (h[c] > 0) fprintf(stderr, "[dsr viterbi prof] frames with %s placements: %.1f %% of the frames, %.1f %% of the frame time, %.1f us per frame, %.2f ns per placement\n",
                                                       cn[c], 100.0 * h[c] / nf, 100.0 * h[4 + c] / tk, h[4 + c] / 100.0 / h[c], h[4 + c] * 10.0 / h[8 + c]);
   }
+  {                                                             // register-path frames: laid out by the frame before, or through P1 and P2
+    double a = 0, b = 0; for (int s2 = 0; s2 < slots; s2++) { a += (double) hp[(size_t) s2 * kProfN + 44]; b += (double) hp[(size_t) s2 * kProfN + 45]; }
+    if (a + b > 0) fprintf(stderr, "[dsr viterbi prof] register-path frames: %.1f %% start laid out, %.1f %% run P1/P2\n", 100.0 * a / (a + b), 100.0 * b / (a + b));
+    double m1 = 0, m2 = 0, mAll = 0; for (int s2 = 0; s2 < slots; s2++) { m1 += (double) hp[(size_t) s2 * kProfN + 46]; m2 += (double) hp[(size_t) s2 * kProfN + 47]; mAll += (double) hp[(size_t) s2 * kProfN + 32 + 3]; }
+    if (mAll > 0) fprintf(stderr, "[dsr viterbi prof] memory-path frames: %.0f, of them %.1f %% with at most 28672 placements, %.1f %% with at most 32767\n", mAll, 100.0 * m1 / mAll, 100.0 * m2 / mAll);
+  }
   fprintf(stderr, "[dsr viterbi prof] busy us per slot: mean %.0f min %.0f max %.0f\n", tsum / slots, tmin, tmax);
   if (slots >= 64 && slots % 8 == 0) {                       // by XCD (workgroup i runs on XCD i mod 8): how even the eight queues of the time-sliced decode come out
     double bx[8] = {0}; for (int s2 = 0; s2 < slots; s2++) { double t = 0.0; for (int i = 0; i < 32; i++) if (i != 15) t += (double) hp[(size_t) s2 * kProfN + i]; bx[s2 & 7] += t / 100.0; }
@@ -495,6 +501,11 @@ dsr_status dsr_decoder_decode_collect(dsr_decoder* d, dsr_decode_result* res, in
     if (read_vit_env().segVerbose && d->d_poolNext.p && d->lastPoolCap > 0) {
       unsigned long long used = 0; DSR_HIP(hipMemcpy(&used, d->d_poolNext.p, sizeof(used), hipMemcpyDeviceToHost));
       fprintf(stderr, "[dsr viterbi] pool of back-pointer records: %.1f M of %.1f M taken\n", used / 1e6, d->lastPoolCap / 1e6);
+    }
+    if (read_vit_env().segVerbose) {                            // which path the frames of the batch took (utterances decoded to their end; DSR_E_DIMENSION: only the path did not fit)
+      long long laid = 0, reg = 0, all = 0;
+      for (int u = 0; u < U; u++) if (res[u].status == DSR_OK || res[u].status == DSR_E_DIMENSION) { laid += res[u].laidOutFrames_; reg += res[u].registerFrames; all += res[u].frames + 1; }
+      fprintf(stderr, "[dsr viterbi] frames: %lld laid out by the frame before, %lld through P1/P2, %lld on the memory path\n", laid, reg - laid, all - reg);
     }
     if (prof) report_profile(prof, slots);
     if (d->dumpOn) {

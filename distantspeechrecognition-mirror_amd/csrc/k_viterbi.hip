@@ -208,12 +208,13 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
   __shared__ int s_err;             // register path: first arrivals per (k, wave) group, then their exclusive prefix
   __shared__ long long s_prof[32]; __shared__ long long s_tlast;
   // profiling build: the frames by size class -- at most 8 192 placements (all in registers), up to 12 288, more (register path), memory path: frames [0..3], ticks [4..7], placements [8..11]
-  __shared__ long long s_hist[PROF ? 12 : 1]; __shared__ long long s_tfr;
+  // [12], [13]: register-path frames that started laid out by the frame before / that ran P1 and P2; [14], [15]: memory-path frames of at most 28 672 / 32 767 placements
+  __shared__ long long s_hist[PROF ? 16 : 1]; __shared__ long long s_tfr;
   // per-utterance statistics and the cold loop state (thread 0 updates them once per frame; they used to ride in scalar registers through every phase)
-  __shared__ long long s_stat[3];    // activeHypos, placements, registerFrames
+  __shared__ long long s_stat[3];    // activeHypos, placements, registerFrames (low word) | those of them that started laid out (high word)
   __shared__ int s_maxActive; __shared__ unsigned s_tag; __shared__ long long s_latOff;
   if (PROF && threadIdx.x < 32) s_prof[threadIdx.x] = 0;
-  if (PROF && threadIdx.x < 12) s_hist[threadIdx.x] = 0;
+  if (PROF && threadIdx.x < 16) s_hist[threadIdx.x] = 0;
 #define TICK(ix) do { if (PROF && tid == 0) { const long long tn = (long long) wall_clock64(); s_prof[ix] += tn - s_tlast; s_tlast = tn; } } while (0)
   constexpr int nthr = kThreads, nw = kWaves;
   __shared__ int s_u, s_seg, s_help; __shared__ long long s_chunk;
@@ -444,6 +445,8 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
           const TokA* __restrict__ ctk = ident ? curA : ctok;
           TICK(1);
           Cfr = C;
+          if (pre && tid == nthr - 1) s_stat[2] += 1ll << 32;                  // (the thread that counts the frame below)
+          if (PROF && tid == 0) s_hist[pre ? 12 : 13] += 1;
           RELOAD();
           // (tq/lq/wq = tid/lane/wave behind an opaque copy: keeps the per-slot address arithmetic of the unrolled phases inside
           // the frame loop -- hoisted out of it, those hundred-odd invariants would live in scratch memory)
@@ -923,10 +926,10 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
             __syncthreads();
             TICK(21);
             const int q4 = hashN >> 2;
-            const bool layNext = prune && numNew <= 2 * nthr;                  // (one round of the loop below)
+            const bool layNext = prune && numNew <= 4 * nthr;                  // (at most two rounds of two list entries per thread)
             preC = -1;
-            for (int f0 = 0; f0 < numNew; f0 += 2 * nthr) {
-              uint4 en[2]; int4 dx[2]; uint32_t pv[2];
+            // one round of the dense write, two list entries per thread: the loads ...
+            auto denseLoad = [&](const int f0, uint4* en, int4* dx, uint32_t* pv) __attribute__((always_inline)) {
 #pragma unroll
               for (int i = 0; i < 2; i++) {
                 const int f = f0 + i * nthr + tq; const bool on = f < numNew;
@@ -942,35 +945,9 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
                 pv[i] = *pb;
                 if (sw && si < (unsigned) sideLds) pv[i] = sideL[si].prevBp;
               }
-              // The list this loop writes is the list the next frame expands, every token of it (pruning on: all pass the beam).  A token's first slot
-              // there is the sum of the expansion counts of the tokens before it in the list = after it in rank: one block-wide sum over the counts the
-              // loop has in hand anyway gives every token its slot offset, and the bitmap of run starts and the per-group table -- what P1 and P2 of the
-              // next frame would rebuild from the list -- are written here.  That frame then starts at P3 (one barrier for its score row).
-              if (layNext) {
-                const int cA0 = (tq < numNew) ? dx[0].w : 0, cB0 = (nthr + tq < numNew) ? dx[1].w : 0;
-                const int inA = wave_incl_scan(cA0, lq), inB = wave_incl_scan(cB0, lq);
-                const bool bad = (tq < numNew && cA0 == 0) || (nthr + tq < numNew && cB0 == 0);     // a token without arcs: the list is not its own compact list
-                const int badW = __any(bad) ? 1 : 0;
-                if (lq == 63) { s_waveTot[wq] = inA; s_waveTotE[wq] = inB | (badW << 30); }
-                __syncthreads();
-                const int ta = (lq < nw) ? s_waveTot[lq] : 0, tbv = (lq < nw) ? s_waveTotE[lq] : 0, tb = tbv & 0x3FFFFFFF;
-                const int sa = wave_incl_scan(ta, lq), sb = wave_incl_scan(tb, lq);
-                const int totA = __builtin_amdgcn_readlane(sa, 63), totB = __builtin_amdgcn_readlane(sb, 63), wu = uni(wq);
-                const int total = totA + totB;
-                const int offA = total - (__builtin_amdgcn_readlane(sa - ta, wu) + inA), offB = total - (totA + __builtin_amdgcn_readlane(sb - tb, wu) + inB);
-                const bool anyBad = __any((tbv >> 30) & 1);
-#pragma unroll
-                for (int i = 0; i < 2; i++) {
-                  const int f = i * nthr + tq; const int off = i ? offB : offA, cn = i ? cB0 : cA0;
-                  if (f < numNew && cn > 0) {
-                    const int e = numNew - 1 - f;
-                    atomicOr(&s_bm[off >> 5], 1u << (off & 31));
-                    for (int g = (off >> 6) + 1; g <= ((off + cn) >> 6); g++) s_gbase[g] = (unsigned) (e + 1) | ((unsigned) (64 * g - off) << 13);
-                  }
-                }
-                if (tq == 0) { s_sideN = 0; s_gbase[0] = 0; s_err = 0; }
-                preC = anyBad ? -1 : total;
-              }
+            };
+            // ... and the stores
+            auto denseStore = [&](const int f0, const uint4* en, const int4* dx, const uint32_t* pv) __attribute__((always_inline)) {
 #pragma unroll
               for (int i = 0; i < 2; i++) {
                 const int f = f0 + i * nthr + tq;
@@ -982,6 +959,67 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
                   outA[pos] = na; outB[pos] = nb; outBp[pos] = bp;
                   if (pos < cntCap) cntL[pos] = (unsigned short) dx[i].w;
                 }
+              }
+            };
+            // The list this loop writes is the list the next frame expands, every token of it (pruning on: all pass the beam).  A token's first slot
+            // there is the sum of the expansion counts of the tokens before it in the list = after it in rank: one block-wide sum over the counts the
+            // loop has in hand anyway gives every token its slot offset, and the bitmap of run starts and the per-group table -- what P1 and P2 of the
+            // next frame would rebuild from the list -- are written here.  That frame then starts at P3 (one barrier for its score row).
+            // cn[i]: the expansion count of list entry f = i * nthr + tq (0 past the list's end), NE = 2 or 4 entries per thread.  The sum runs over the
+            // (entry, wave) groups of 64 ranks in rank order -- at most 4 x 16 of them: one wave-wide scan of their totals.
+            // A list with more placements than the register path takes is not laid out (the bitmap ends at kFastC): the next frame's P1 sends it to the memory path.
+            auto layOut = [&](auto NE_, const int* cn) __attribute__((always_inline)) {
+              constexpr int NE = decltype(NE_)::value;
+              int in[NE]; bool bad = false;
+#pragma unroll
+              for (int i = 0; i < NE; i++) {
+                in[i] = wave_incl_scan(cn[i], lq);
+                bad = bad || (i * nthr + tq < numNew && cn[i] == 0);           // a token without arcs: the list is not its own compact list
+              }
+              const int badW = __any(bad) ? 1 : 0;
+              if (lq == 63) {
+#pragma unroll
+                for (int i = 0; i < NE; i++) s_cnt[i * nw + wq] = in[i];
+                s_waveTotE[wq] = badW;
+              }
+              __syncthreads();
+              const int tg = (lq < NE * nw) ? s_cnt[lq] : 0;
+              const int sg = wave_incl_scan(tg, lq);
+              const int total = __builtin_amdgcn_readlane(sg, 63), wu = uni(wq);
+              const bool anyBad = __any(((lq < nw) ? s_waveTotE[lq] : 0) != 0);
+              const bool fits = total <= fastCapC;
+#pragma unroll
+              for (int i = 0; i < NE; i++) {
+                const int f = i * nthr + tq; const int off = total - (__builtin_amdgcn_readlane(sg - tg, i * nw + wu) + in[i]);
+                if (fits && f < numNew && cn[i] > 0) {
+                  const int e = numNew - 1 - f;
+                  atomicOr(&s_bm[off >> 5], 1u << (off & 31));
+                  for (int g = (off >> 6) + 1; g <= ((off + cn[i]) >> 6); g++) s_gbase[g] = (unsigned) (e + 1) | ((unsigned) (64 * g - off) << 13);
+                }
+              }
+              if (tq == 0) { s_sideN = 0; s_gbase[0] = 0; s_err = 0; }
+              preC = (anyBad || !fits) ? -1 : total;
+            };
+            if (layNext && numNew > 2 * nthr) {
+              // two rounds, then the layout over the four counts a thread has kept (holding the four entries themselves across the layout's barrier cost scratch memory)
+              int cn[4];
+#pragma unroll
+              for (int h = 0; h < 2; h++) {
+                uint4 en[2]; int4 dx[2]; uint32_t pv[2];
+                denseLoad(h * 2 * nthr, en, dx, pv); denseStore(h * 2 * nthr, en, dx, pv);
+#pragma unroll
+                for (int i = 0; i < 2; i++) cn[2 * h + i] = ((2 * h + i) * nthr + tq < numNew) ? dx[i].w : 0;
+              }
+              layOut(std::integral_constant<int, 4>{}, cn);
+            } else {
+              for (int f0 = 0; f0 < numNew; f0 += 2 * nthr) {
+                uint4 en[2]; int4 dx[2]; uint32_t pv[2];
+                denseLoad(f0, en, dx, pv);
+                if (layNext) {                                                 // (one round; its stores drain under the layout's scan)
+                  const int cn[2] = { (tq < numNew) ? dx[0].w : 0, (nthr + tq < numNew) ? dx[1].w : 0 };
+                  layOut(std::integral_constant<int, 2>{}, cn);
+                }
+                denseStore(f0, en, dx, pv);
               }
             }
             TICK(22);
@@ -1246,7 +1284,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
       }   // memory path
       __syncthreads();
       TICK(fast ? 7 : 8);
-      if (PROF && tid == 0 && mode == 0) { const int cls = !fast ? 3 : Cfr <= kFastK * nthr ? 0 : Cfr <= 12288 ? 1 : 2; s_hist[cls] += 1; s_hist[4 + cls] += s_tlast - s_tfr; s_hist[8 + cls] += Cfr; }
+      if (PROF && tid == 0 && mode == 0) { const int cls = !fast ? 3 : Cfr <= kFastK * nthr ? 0 : Cfr <= 12288 ? 1 : 2; s_hist[cls] += 1; s_hist[4 + cls] += s_tlast - s_tfr; s_hist[8 + cls] += Cfr; if (!fast && Cfr <= 28672) s_hist[14] += 1; if (!fast && Cfr <= 32767) s_hist[15] += 1; }
       RELOAD();
       if (mode == 0) {
         if (dump) {
@@ -1292,7 +1330,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
           dsr_decode_result* const res = ka->res;
           clear_result(&res[u]); dsr_decode_result& r = res[u];
           unsigned long long k = ~0ull; for (int w = 0; w < nw; w++) if (s_waveKey[w] < k) k = s_waveKey[w];
-          r.frames = T - 1; r.reachedFinal = numNew > 0 ? 1 : 0; r.finalStatesN = numNew; /* every token of _next after _expandToEnd sits in a final state */ r.activeHypos = (long) s_stat[0]; r.placements = (long) s_stat[1] + Cfr; r.registerFrames = (long) s_stat[2]; r.maxActiveSeen = s_maxActive; r.status = DSR_OK;
+          r.frames = T - 1; r.reachedFinal = numNew > 0 ? 1 : 0; r.finalStatesN = numNew; /* every token of _next after _expandToEnd sits in a final state */ r.activeHypos = (long) s_stat[0]; r.placements = (long) s_stat[1] + Cfr; r.registerFrames = (long) (s_stat[2] & 0xFFFFFFFFll); r.laidOutFrames_ = (int) (s_stat[2] >> 32); r.maxActiveSeen = s_maxActive; r.status = DSR_OK;
           TraceHead hd; hd.arenaOff = (unsigned long long) ((size_t) ((EXTRA && ka->D.latOn) ? u : (ka->D.segFrames > 0 ? 0 : slot)) * ka->D.arenaCap); /* as the arena macro */ hd.bp = kNone; hd.hops = kNone;
           if (k != ~0ull) {
             const TokA bt = ld_tok(&lst[(unsigned) (k & 0xFFFFFFFFu)]);
@@ -1341,7 +1379,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
   RELOAD();
   if (tid == 0) ka->D.tags[slot] = s_tag;
   if (PROF && tid < 32) ka->D.prof[slot * kProfN + tid] = s_prof[tid];
-  if (PROF && tid < 12) ka->D.prof[slot * kProfN + 32 + tid] = s_hist[tid];
+  if (PROF && tid < 16) ka->D.prof[slot * kProfN + 32 + tid] = s_hist[tid];
 #undef TICK
 #undef RELOAD
 #undef TOKA

@@ -31,7 +31,7 @@ static_assert(sizeof(TokA) == 16 && sizeof(TokB) == 8 && sizeof(XRecD) == 32 && 
 
 static constexpr int kThreads = 1024;             // 16 waves per CU at 128 VGPRs (measured in round 2: 512 x 256 VGPRs 22 % slower, 768 x 168 VGPRs 4 % slower; two 512-thread workgroups per CU 1.2x slower)
 static constexpr int kFastC = 24576;               // most placements per frame on the register path (those beyond kFastK per thread are parked in memory)
-static constexpr int kProfN = 48;                  // profiling words per slot: 32 phase ticks + 12 of the size-class histogram
+static constexpr int kProfN = 48;                  // profiling words per slot: 32 phase ticks + 12 of the size-class histogram + 4 frame counts (laid out / through P1 and P2, memory-path frames below two sizes)
 static constexpr int kSideLds = 496;               // later arrivals kept in LDS (the rest go to memory)
 
 struct GraphDev {

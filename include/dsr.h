@@ -1024,7 +1024,8 @@ typedef struct {
   int64_t placements;   /* calls of _placeOnList over the utterance (expanded arcs incl. the end expansion) */
   int64_t registerFrames; /* diagnostics: frames that ran on the decoder kernel's register path (rest: memory path) */
   int32_t finalStatesN; /* finalStatesN() (decoder.h:598-608): tokens of _next in a final state after _expandToEnd */
-  int32_t reserved_;
+  int32_t laidOutFrames_; /* diagnostics, no part of the result: register-path frames whose placement slots the frame before had laid out
+                           * (the other register-path frames built the layout themselves, in the kernel's phases P1 and P2) */
 } dsr_decode_result;
 /* Batched decode.  score_dev [U][Tmax][nDist] fp32 costs (row t = Distrib::score(t)), nframes_dev [U].
  * Host outputs: res[U]; arcs_out [U][maxPath] (export arc ids, first..last), words_out [U][maxPath]

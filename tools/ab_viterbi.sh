@@ -1,6 +1,6 @@
 #!/bin/bash
 # Decoder micro benchmark over the library variants in lib/var/<name>/ (tools/build_variants.sh): same box, same inputs, two rounds.
-# The variant is selected through DSR_LIB_VARIANT (dsr/_capi.py); the shipped library is never touched.
+# The variant is selected through DSR_LIB_VARIANT (dsr/_capi/_core.py); the shipped library is never touched.
 cd $GRAFT_REPO_ROOT
 ARGS="--utts 1024 --frames 100 --reps 3 --beam 53.79"
 for round in 1 2; do

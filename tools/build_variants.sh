@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: [OBJ=k_viterbi] tools/build_variants.sh name1 "-DFLAGS" name2 "-DFLAGS" ...   -> distantspeechrecognition-mirror_amd/lib/var/<name>/libdsr_hip.so
 # OBJ: the translation unit the variants rebuild (default k_viterbi); a name of the form name=path/to/source.hip builds that source file instead of csrc/$OBJ.hip.
-# Variants are selected at run time through DSR_LIB_VARIANT (dsr/_capi.py); the shipped library is never touched.
+# Variants are selected at run time through DSR_LIB_VARIANT (dsr/_capi/_core.py); the shipped library is never touched.
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $R/distantspeechrecognition-mirror_amd
 OBJ=${OBJ:-k_viterbi}

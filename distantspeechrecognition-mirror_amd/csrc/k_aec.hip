@@ -14,6 +14,8 @@
 // The covariance update is the rank-1 form K = K- - s s^H / sigma2_s with s = K- conj(v): K stays exactly Hermitian (s_i conj(s_j) and
 // s_j conj(s_i) are exact conjugates without FMA contraction), so v^T K- = s^H needs no second reduction.
 // The two information filters of the same directory are k_aec_info.hip; the C entries at the end of this file hand their kinds on (aec.h).
+#include "launch.h"
+#include "dev_math.h"
 #include "aec.h"
 
 using namespace dsr;
@@ -36,14 +38,6 @@ St carve(const dsr_aec& a, void* base, int U)
   return St{(double2*) (b + l.oR), (double2*) (b + l.oK), (double*) (b + l.oSv), (double2*) (b + l.oH), (double*) (b + l.oD)};
 }
 
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ double2 cmulc(double2 a, double2 b) { return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }     // a conj(b)
-__device__ __forceinline__ double2 z2() { return make_double2(0.0, 0.0); }
-__device__ __forceinline__ double abs2(double2 a) { return a.x * a.x + a.y * a.y; }
-// gsl_complex_div (GSL complex/math.c): scale by 1/|b| first
-__device__ __forceinline__ double2 gsl_div(double2 a, double2 b)
-{ const double s = 1.0 / hypot(b.x, b.y); const double sbr = s * b.x, sbi = s * b.y; return make_double2((a.x * sbr + a.y * sbi) * s, (a.y * sbr - a.x * sbi) * s); }
-__device__ __forceinline__ double2 shfl2(double2 a, int src) { return make_double2(__shfl(a.x, src), __shfl(a.y, src)); }
 // butterfly sum over W consecutive lanes (W a power of two): every lane ends with the same bits, because x + y == y + x
 template <int W> __device__ __forceinline__ double bsum(double x)
 {
@@ -129,7 +123,7 @@ template <int LP> __device__ __forceinline__ void aec_update(double2 (&K)[Geo<LP
 #pragma unroll
   for (int c = 0; c < CH; c++) {
     if (row == col0 + c && row < L) K[c].x = suS + K[c].x;                           // K- = Sigma_u + K (:326-327)
-    const double2 pr = cmulc(K[c], vcol[c]); s.x += pr.x; s.y += pr.y;               // s = K- conj(v) (:329-330)
+    const double2 pr = cmul_conj(K[c], vcol[c]); s.x += pr.x; s.y += pr.y;               // s = K- conj(v) (:329-330)
   }
   s = bsum2<LPR>(s);
   const double sig = bsum<LPC>(leader ? vrow.x * s.x - vrow.y * s.y : 0.0) + sv;     // sigma2_s = Re(v^T s) + sigma2_v (:331-338)
@@ -138,7 +132,7 @@ template <int LP> __device__ __forceinline__ void aec_update(double2 (&K)[Geo<LP
   Rrow = make_double2(Rrow.x + EG.x, Rrow.y + EG.y);
 #pragma unroll
   for (int c = 0; c < CH; c++) {                                                     // K = (I - G v^T) K- = K- - s s^H / sigma2_s (:346-354)
-    const double2 sc = shfl2(s, chainBase + (col0 + c) * LPR), P = cmulc(s, sc);
+    const double2 sc = shfl2(s, chainBase + (col0 + c) * LPR), P = cmul_conj(s, sc);
     K[c] = make_double2(K[c].x - P.x * inv, K[c].y - P.y * inv);
   }
 }
@@ -300,17 +294,16 @@ void init_state(const dsr_aec& a, void* state, int U, hipStream_t st)
 {
   const St s = carve(a, state, U); const long n = (long) U * (a.M / 2 + 1);
   const double k0 = a.kind == 0 ? 0.0 : (a.kind == 1 ? a.sigma2 : a.sigmak2), sv0 = a.kind == 1 ? a.sigma2 : a.sigmau2;      // :117-121, :233-246
-  hipLaunchKernelGGL(k_aec_init, dim3(cdiv(n > (long) U * 4 ? n : (long) U * 4, 256)), dim3(256), 0, st, s, n, a.L, U, k0, sv0);
-  DSR_HIP(hipGetLastError());
+  launch(k_aec_init, dim3(cdiv(n > (long) U * 4 ? n : (long) U * 4, 256)), dim3(256), 0, st, s, n, a.L, U, k0, sv0);
 }
 
 template <int LP> void launch_block(const dsr_aec& a, const float2* V, const float2* A, const int* nf, int U, int Tmax, int F, const Par& p, const St& s, float2* out,
                                     int frame0, hipStream_t st)
 {
   if (a.kind == 3) {
-    hipLaunchKernelGGL(k_aec_dtd<LP>, dim3(U), dim3(DtdNT<LP>::v), (size_t) 8 * F * sizeof(double), st, V, A, nf, U, Tmax, F, a.L, p, s, out, frame0, a.frameMode);
+    launch(k_aec_dtd<LP>, dim3(U), dim3(DtdNT<LP>::v), (size_t) 8 * F * sizeof(double), st, V, A, nf, U, Tmax, F, a.L, p, s, out, frame0, a.frameMode);
   } else {
-    hipLaunchKernelGGL(k_aec_block<LP>, dim3(cdiv((long) U * F, Geo<LP>::CPW)), dim3(64), 0, st, V, A, nf, U, Tmax, F, a.L, p, s, out);
+    launch(k_aec_block<LP>, dim3(cdiv((long) U * F, Geo<LP>::CPW)), dim3(64), 0, st, V, A, nf, U, Tmax, F, a.L, p, s, out);
   }
 }
 
@@ -422,16 +415,15 @@ dsr_status dsr_aec_apply(const dsr_aec* a, const float* played_dev, const float*
     Par p{a->delta, a->epsilon, a->threshold, a->beta, a->kind == DSR_AEC_KALMAN ? a->sigma2 : a->sigmau2, a->amp, a->engTh, a->smooth};
     const float2* V = (const float2*) played_dev; const float2* A = (const float2*) recorded_dev; float2* out = (float2*) out_dev;
     if (a->kind == DSR_AEC_NLMS)
-      hipLaunchKernelGGL(k_aec_scalar<0>, dim3(cdiv((long) U * F, 256)), dim3(256), 0, st, V, A, nframes_dev, U, Tmax, F, p, s, out);
+      launch(k_aec_scalar<0>, dim3(cdiv((long) U * F, 256)), dim3(256), 0, st, V, A, nframes_dev, U, Tmax, F, p, s, out);
     else if (a->kind == DSR_AEC_KALMAN)
-      hipLaunchKernelGGL(k_aec_scalar<1>, dim3(cdiv((long) U * F, 256)), dim3(256), 0, st, V, A, nframes_dev, U, Tmax, F, p, s, out);
+      launch(k_aec_scalar<1>, dim3(cdiv((long) U * F, 256)), dim3(256), 0, st, V, A, nframes_dev, U, Tmax, F, p, s, out);
     else if (a->L == 1) launch_block<1>(*a, V, A, nframes_dev, U, Tmax, F, p, s, out, frame0, st);
     else if (a->L == 2) launch_block<2>(*a, V, A, nframes_dev, U, Tmax, F, p, s, out, frame0, st);
     else if (a->L <= 4) launch_block<4>(*a, V, A, nframes_dev, U, Tmax, F, p, s, out, frame0, st);
     else if (a->L <= 8) launch_block<8>(*a, V, A, nframes_dev, U, Tmax, F, p, s, out, frame0, st);
     else if (a->L <= 16) launch_block<16>(*a, V, A, nframes_dev, U, Tmax, F, p, s, out, frame0, st);
     else launch_block<32>(*a, V, A, nframes_dev, U, Tmax, F, p, s, out, frame0, st);
-    DSR_HIP(hipGetLastError());
   });
 }
 

@@ -16,6 +16,8 @@
 //               the reference's _invert is exact (its eigenvalue threshold is commented out, :496), so each is a Cholesky factorisation,
 //               a forward substitution and the product Linv^H Linv, in the wave's LDS scratch.
 // Nothing waits on another workgroup.
+#include "launch.h"
+#include "dev_math.h"
 #include "aec.h"
 
 using namespace dsr;
@@ -39,18 +41,7 @@ ISt icarve(const dsr_aec& a, void* base, int U)
   return ISt{(double2*) (b + l.oR), (double2*) (b + l.oK), (double*) (b + l.oSv), (double2*) (b + l.oH), (double*) (b + l.oB), (double2*) (b + l.oI), (int*) (b + l.oC)};
 }
 
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ double2 cj(double2 a) { return make_double2(a.x, -a.y); }
-__device__ __forceinline__ double2 z2() { return make_double2(0.0, 0.0); }
-__device__ __forceinline__ double abs2(double2 a) { return a.x * a.x + a.y * a.y; }
-// gsl_complex_div (GSL complex/math.c): scale by 1/|b| first
-__device__ __forceinline__ double2 gsl_div(double2 a, double2 b)
-{ const double s = 1.0 / hypot(b.x, b.y); const double sbr = s * b.x, sbi = s * b.y; return make_double2((a.x * sbr + a.y * sbi) * s, (a.y * sbr - a.x * sbi) * s); }
-__device__ __forceinline__ double2 shfl2(double2 a, int src) { return make_double2(__shfl(a.x, src), __shfl(a.y, src)); }
 
-// what one wave wrote to LDS becomes readable by its other lanes: LDS runs a wave's accesses in order, the compiler has to keep them so
-__device__ __forceinline__ void wave_sync()
-{ __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
 
 // sqrtKind: K = Sigma_u = I / sqrt(sigmau2) and the information state zero (:670-680), else K = sigmak2 I (:243); R = (1, 0, ...) (:405-407)
 __global__ void k_aec_info_init(ISt s, long nChain, int L, int U, double k0, double sv0, int sqrtKind)
@@ -342,9 +333,8 @@ void init_state(const dsr_aec& a, void* state, int U, hipStream_t st)
 {
   const ISt s = icarve(a, state, U); const long n = (long) U * (a.M / 2 + 1);
   const bool sq = a.kind == DSR_AEC_SQRT_INFO;
-  hipLaunchKernelGGL(k_aec_info_init, dim3(cdiv(n > (long) U * 4 ? n : (long) U * 4, 256)), dim3(256), 0, st, s, n, a.L, U, sq ? 1.0 / sqrt(a.sigmau2) : a.sigmak2,
+  launch(k_aec_info_init, dim3(cdiv(n > (long) U * 4 ? n : (long) U * 4, 256)), dim3(256), 0, st, s, n, a.L, U, sq ? 1.0 / sqrt(a.sigmau2) : a.sigmak2,
                      a.sigmau2, sq ? 1 : 0);
-  DSR_HIP(hipGetLastError());
 }
 
 void apply(const dsr_aec& a, const float2* V, const float2* A, const int* nf, int U, int Tmax, int frame0, float2* out, void* state, hipStream_t st)
@@ -358,9 +348,7 @@ void apply(const dsr_aec& a, const float2* V, const float2* A, const int* nf, in
   if (sq) {
     int LPC = 2; while (LPC < 2 * L) LPC *= 2;                                       // 2 .. 64 lanes a chain
     const size_t lds = sqrt_lds(L, LPC);
-    if (lds > 64 * 1024) DSR_HIP(hipFuncSetAttribute((const void*) k_aec_sqrt, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    hipLaunchKernelGGL(k_aec_sqrt, dim3(cdiv((long) U * F, 64 / LPC)), dim3(64), lds, st, V, A, nf, U, Tmax, F, L, LPC, p, s, out, frame0, a.frameMode);
-    DSR_HIP(hipGetLastError());
+    launch(k_aec_sqrt, dim3(cdiv((long) U * F, 64 / LPC)), dim3(64), lds, st, V, A, nf, U, Tmax, F, L, LPC, p, s, out, frame0, a.frameMode);
     // _calcGivensRotation's jarithmetic_error (:699-700): the kernel records a zero norm per utterance
     std::vector<int> cnt((size_t) U * 4);
     DSR_HIP(hipMemcpyAsync(cnt.data(), s.cnt, cnt.size() * 4, hipMemcpyDeviceToHost, st));
@@ -368,9 +356,7 @@ void apply(const dsr_aec& a, const float2* V, const float2* A, const int* nf, in
     for (int u = 0; u < U; u++) if (cnt[(size_t) u * 4 + 2]) throw Error(DSR_E_ARITHMETIC, "calcGivensRotation: Norm is zero (utterance %d).", u);
   } else {
     const size_t lds = info_lds(F, L);
-    if (lds > 64 * 1024) DSR_HIP(hipFuncSetAttribute((const void*) k_aec_info, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    hipLaunchKernelGGL(k_aec_info, dim3(U), dim3(INFO_NT), lds, st, V, A, nf, U, Tmax, F, L, p, s, out, frame0, a.frameMode);
-    DSR_HIP(hipGetLastError());
+    launch(k_aec_info, dim3(U), dim3(INFO_NT), lds, st, V, A, nf, U, Tmax, F, L, p, s, out, frame0, a.frameMode);
   }
 }
 

@@ -9,7 +9,8 @@
 // The hot loop -- SnapShotArray::update + one zdotc per bin per frame (:76-90, :2609-2631) -- is
 // k_bf_apply: one thread per (frame, bin), channel spectra read coalesced along the bin axis from the
 // [chan][frame][bin] layout the analysis kernel writes, weights staged in LDS.
-#include "common.h"
+#include "launch.h"
+#include "dev_math.h"
 #include "svd_linpack.h"
 #include "gsc_weights.h"
 #include <complex>
@@ -160,10 +161,6 @@ using namespace dsr;
 // frame's output with the weights as they stand, then Z = B^H X, the gain vector, the precision matrix and the active weights (quadratic
 // constraint optional), all fp64 in the reference's order of operations; precision matrix and active weights live in a state array
 // [entry][utterance x bin] (coalesced across the threads of a wave).  Every utterance starts from P0 and wa = 0.
-__device__ __forceinline__ double2 cdiv_gsl2(double ar, double ai, double br, double bi)
-{ const double s = 1.0 / hypot(br, bi); const double sbr = s * br, sbi = s * bi; return make_double2((ar * sbr + ai * sbi) * s, (ai * sbr - ar * sbi) * s); }
-__device__ __forceinline__ double2 cmul2(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ double2 cmulc2(double2 a, double2 b) { return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }     // a conj(b)
 
 // (CT: compile-time channel count -- the small vectors then live in registers and the loops unroll; 0: run-time count, arrays in scratch)
 // nframesArr (optional): utterance u is adapted over its first nframesArr[u] frames only and the rest of its rows is zero filled -- the reference
@@ -206,29 +203,29 @@ __global__ __launch_bounds__(64) void k_gsc_rls(const float2* __restrict__ X, co
   for (int t = 0; t < Tu; t++) {
     for (int c = 0; c < C; c++) { const float2 v = Xu[((long) c * Tmax + t) * F + f]; x[c] = make_double2((double) v.x, (double) v.y); }
     double2 y = make_double2(0.0, 0.0);
-    if (f == 0) { for (int c = 0; c < C; c++) { const double2 q = cmulc2(x[c], wqf[c]); y.x += q.x; y.y += q.y; } }
+    if (f == 0) { for (int c = 0; c < C; c++) { const double2 q = cmul_conj(x[c], wqf[c]); y.x += q.x; y.y += q.y; } }
     else {
       double nrm = 0.0;
       for (int i = 0; i < C; i++) {
         double2 wl = make_double2(0.0, 0.0);
-        for (int j = 0; j < n; j++) { const double2 q = cmul2(Bf[i * n + j], WA(j)); wl.x += q.x; wl.y += q.y; }
+        for (int j = 0; j < n; j++) { const double2 q = cmul(Bf[i * n + j], WA(j)); wl.x += q.x; wl.y += q.y; }
         w[i] = make_double2(wqf[i].x - wl.x, wqf[i].y - wl.y); nrm += w[i].x * w[i].x + w[i].y * w[i].y;
       }
       if (normalize) { nrm = sqrt(nrm) * (double) C; for (int i = 0; i < C; i++) { w[i].x /= nrm; w[i].y /= nrm; } }
-      for (int c = 0; c < C; c++) { const double2 q = cmulc2(x[c], w[c]); y.x += q.x; y.y += q.y; }
+      for (int c = 0; c < C; c++) { const double2 q = cmul_conj(x[c], w[c]); y.x += q.x; y.y += q.y; }
     }
     Yu[(long) t * F + f] = make_float2((float) y.x, (float) y.y);
     if (f == 0 || !adapt) continue;
-    for (int j = 0; j < n; j++) { double2 a = make_double2(0.0, 0.0); for (int c = 0; c < C; c++) { const double2 q = cmulc2(x[c], Bf[c * n + j]); a.x += q.x; a.y += q.y; } Z[j] = a; }
-    for (int j = 0; j < n; j++) { double2 a = make_double2(0.0, 0.0); for (int i = 0; i < n; i++) { const double2 q = cmulc2(Z[i], PX(i, j)); a.x += q.x; a.y += q.y; } PH[j] = a; }
-    for (int i = 0; i < n; i++) { double2 a = make_double2(0.0, 0.0); for (int j = 0; j < n; j++) { const double2 q = cmul2(PX(i, j), Z[j]); a.x += q.x; a.y += q.y; } g[i] = make_double2(a.x * rmu, a.y * rmu); }
+    for (int j = 0; j < n; j++) { double2 a = make_double2(0.0, 0.0); for (int c = 0; c < C; c++) { const double2 q = cmul_conj(x[c], Bf[c * n + j]); a.x += q.x; a.y += q.y; } Z[j] = a; }
+    for (int j = 0; j < n; j++) { double2 a = make_double2(0.0, 0.0); for (int i = 0; i < n; i++) { const double2 q = cmul_conj(Z[i], PX(i, j)); a.x += q.x; a.y += q.y; } PH[j] = a; }
+    for (int i = 0; i < n; i++) { double2 a = make_double2(0.0, 0.0); for (int j = 0; j < n; j++) { const double2 q = cmul(PX(i, j), Z[j]); a.x += q.x; a.y += q.y; } g[i] = make_double2(a.x * rmu, a.y * rmu); }
     double2 de = make_double2(0.0, 0.0);
-    for (int j = 0; j < n; j++) { const double2 q = cmulc2(Z[j], PH[j]); de.x += q.x; de.y += q.y; }
+    for (int j = 0; j < n; j++) { const double2 q = cmul_conj(Z[j], PH[j]); de.x += q.x; de.y += q.y; }
     de = make_double2(de.x * rmu + 1.0, de.y * rmu);
-    for (int i = 0; i < n; i++) g[i] = cdiv_gsl2(g[i].x, g[i].y, de.x, de.y);
+    for (int i = 0; i < n; i++) g[i] = gsl_div(g[i], de);
     for (int i = 0; i < n; i++)
       for (int j = 0; j < n; j++) {
-        const double2 o = PX(i, j), q = cmulc2(g[i], PH[j]);
+        const double2 o = PX(i, j), q = cmul_conj(g[i], PH[j]);
         PX(i, j) = make_double2((o.x - q.x) * rmu, (o.y - q.y) * rmu);
       }
     const double2 epA = make_double2(y.x, -y.y);
@@ -236,9 +233,9 @@ __global__ __launch_bounds__(64) void k_gsc_rls(const float2* __restrict__ X, co
       double2 a = make_double2(0.0, 0.0);
       for (int j = 0; j < n; j++) {
         const double2 p = PX(i, j); double2 m1 = make_double2(p.x * (-dw), p.y * (-dw)); if (i == j) m1.x += 1.0;
-        const double2 q = cmul2(m1, WA(j)); a.x += q.x; a.y += q.y;
+        const double2 q = cmul(m1, WA(j)); a.x += q.x; a.y += q.y;
       }
-      const double2 q = cmul2(g[i], epA); wn[i] = make_double2(a.x + q.x, a.y + q.y);
+      const double2 q = cmul(g[i], epA); wn[i] = make_double2(a.x + q.x, a.y + q.y);
     }
     if (qctype == 1 || qctype == 2) {
       double nr = 0.0; for (int i = 0; i < n; i++) nr += wn[i].x * wn[i].x + wn[i].y * wn[i].y;
@@ -262,18 +259,15 @@ struct dsr_bf : BfState {};
 
 // The dispatch of gsc_rls_apply, in one place: the launch below switches on it and dsr_bf_rls_path reports it.  n = C - 1; the precision matrix and the
 // active weights of a thread are n^2 + n complex fp64 values: in registers for the channel counts k_gsc_rls is instantiated for with a compile-time
-// count (RLS_CT_LIST), else in LDS ([entry][lane]) when the 64 lanes' values fit 150 KB (C <= 12), else in memory, in place.  The vectors of a thread
+// count (RlsCt), else in LDS ([entry][lane]) when the 64 lanes' values fit 150 KB (C <= 12), else in memory, in place.  The vectors of a thread
 // have room for 16 channels, or 64 above that.  DSR_RLS_NOREGS / DSR_RLS_MEMSTATE (set to anything) take the first / the first two residences out;
 // both are read on every call.
-#define RLS_CT_LIST(DO) DO(4) DO(6) DO(8)
+using RlsCt = ints<4, 6, 8>;
 struct RlsPath { int ct, cap, residence; size_t stateBytes, ldsBytes; };
 static RlsPath rls_path(int C)
 {
   RlsPath r; const int n = C - 1;
-  r.ct = 0;
-#define RLS_CT_IS(CTV) if (C == CTV) r.ct = CTV;
-  RLS_CT_LIST(RLS_CT_IS)
-#undef RLS_CT_IS
+  r.ct = has_value(RlsCt{}, C) ? C : 0;
   r.cap = C <= 16 ? 16 : 64;
   r.stateBytes = (size_t) (n * n + n) * 16 * 64;
   const bool lds = r.stateBytes <= 150 * 1024 && !getenv("DSR_RLS_MEMSTATE");
@@ -314,23 +308,13 @@ static void gsc_rls_apply(BfState& s, const float* X, const int32_t* nframes, in
   double2* work = memInPlace ? (s.rlsCarry ? s.d_carry.p : s.d_state.p) : (s.d_state.reserve(16), s.d_state.p);
   // in-place memory variant with carry: the working array IS the carried one: reading "carry" at start and writing it at the end are no-ops on the
   // same addresses (same [entry][U x F] layout), so the flags are passed as they are.
-#define RLS_ARGS (const float2*) X, s.d_wq.p, s.d_B.p, s.d_P0.p, s.d_diag.p, work, (float2*) Y, (double2*) waOut, U, C, Tmax, F, 1.0 / s.rlsMyu, s.rlsAlpha, s.rlsQc, \
-                 s.rlsAdapt ? 1 : 0, s.mode == 3 ? 1 : 0
-#define RLS_TAIL nframes, carry, carryIn, carryOut
-#define RLS_LAUNCH(CTV, CAPV) { if (ldsState) DSR_HIP(hipFuncSetAttribute((const void*) k_gsc_rls<CTV, false, CAPV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsB)); \
-  hipLaunchKernelGGL((k_gsc_rls<CTV, false, CAPV>), dim3((unsigned) ((S + 63) / 64)), dim3(64), ldsState ? ldsB : 0, st, RLS_ARGS, ldsState, RLS_TAIL); }
-#define RLS_LAUNCH_REG(CTV) hipLaunchKernelGGL((k_gsc_rls<CTV, true, 16>), dim3((unsigned) ((S + 63) / 64)), dim3(64), 0, st, RLS_ARGS, 0, RLS_TAIL);
-  bool launched = false;
-#define RLS_CT_GO(CTV) if (!launched && pa.ct == CTV) { if (regs) { RLS_LAUNCH_REG(CTV) } else RLS_LAUNCH(CTV, 16) launched = true; }
-  RLS_CT_LIST(RLS_CT_GO)
-#undef RLS_CT_GO
-  if (!launched && pa.ct == 0) { if (pa.cap == 16) RLS_LAUNCH(0, 16) else RLS_LAUNCH(0, 64) launched = true; }
+  auto go = [&](auto kernel) {
+    launch(kernel, dim3((unsigned) ((S + 63) / 64)), dim3(64), ldsState ? ldsB : 0, st, (const float2*) X, s.d_wq.p, s.d_B.p, s.d_P0.p, s.d_diag.p, work, (float2*) Y,
+           (double2*) waOut, U, C, Tmax, F, 1.0 / s.rlsMyu, s.rlsAlpha, s.rlsQc, s.rlsAdapt ? 1 : 0, s.mode == 3 ? 1 : 0, ldsState, nframes, carry, carryIn, carryOut);
+  };
+  const bool launched = pa.ct != 0 ? for_value(RlsCt{}, pa.ct, [&](auto ct) { if (regs) go(k_gsc_rls<ct(), true, 16>); else go(k_gsc_rls<ct(), false, 16>); })
+                                   : for_value(ints<16, 64>{}, pa.cap, [&](auto cap) { go(k_gsc_rls<0, false, cap()>); });
   if (!launched) throw Error(DSR_E_ERROR, "SubbandGSCRLS: no kernel k_gsc_rls<%d, %d, %d>", pa.ct, regs ? 1 : 0, pa.cap);
-#undef RLS_LAUNCH_REG
-#undef RLS_LAUNCH
-#undef RLS_ARGS
-#undef RLS_TAIL
-  DSR_HIP(hipGetLastError());
   if (s.rlsCarry) { s.rlsHaveState = true; s.rlsStateU = U; }
 }
 
@@ -445,9 +429,10 @@ dsr_status dsr_bf_calc_mvdr_weights(dsr_bf* s, double fs, double thr)
       for (int i = 0; i < C; i++) { zc acc(0, 0); for (int j = 0; j < C; j++) acc += std::conj(invR[(size_t) j * C + i]) * d[j]; tmpH[i] = acc; }
       zc Lambda(0, 0); for (int i = 0; i < C; i++) Lambda += std::conj(tmpH[i]) * d[i];
       const zc norm = Lambda * (double) C;
-      // gsl_complex_div (GSL complex/math.c): scale by 1/|b| first -- restated so that the last bit does not depend on a runtime's __divdc3
-      const double sN = 1.0 / std::hypot(norm.real(), norm.imag()), sbr = sN * norm.real(), sbi = sN * norm.imag();
-      for (int c = 0; c < C; c++) s->mvdr[(size_t) f * C + c] = zc((tmpH[c].real() * sbr + tmpH[c].imag() * sbi) * sN, (tmpH[c].imag() * sbr - tmpH[c].real() * sbi) * sN);
+      for (int c = 0; c < C; c++) {
+        const double2 q = gsl_div(make_double2(tmpH[c].real(), tmpH[c].imag()), make_double2(norm.real(), norm.imag()));
+        s->mvdr[(size_t) f * C + c] = zc(q.x, q.y);
+      }
     }
     s->haveMvdr = true; s->dirty = true;
   });
@@ -519,11 +504,9 @@ dsr_status dsr_bf_apply(dsr_bf* s, const float* X, int U, int Tmax, float* Y, vo
     const int F = s->halfBandShift ? s->M : s->M / 2 + 1; const long perUtt = (long) Tmax * F;
     const size_t lds = sizeof(float2) * (size_t) F * s->C;
     if (lds > 160 * 1024) throw Error(DSR_E_DIMENSION, "beamformer weights need %zu bytes of LDS", lds);
-    DSR_HIP(hipFuncSetAttribute((const void*) k_bf_apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
     int gx = cdiv(perUtt, 256 * 4); if (gx < 1) gx = 1; if (gx > 4096) gx = 4096;
-    hipLaunchKernelGGL(k_bf_apply, dim3(gx, U), dim3(256), lds, (hipStream_t) stream, (const float2*) X, s->d_w.p, (float2*) Y,
+    launch(k_bf_apply, dim3(gx, U), dim3(256), lds, (hipStream_t) stream, (const float2*) X, s->d_w.p, (float2*) Y,
                        s->C, Tmax, F, perUtt);
-    DSR_HIP(hipGetLastError());
   });
 }
 
@@ -649,10 +632,8 @@ dsr_status dsr_bf_blocking_matrix_output(dsr_bf* s, const float* X, int U, int T
     for (int f = 0; f < F; f++) for (int c = 0; c < C; c++) { const zc b = s->B[((size_t) f * C + c) * bs + outChanX]; w[(size_t) f * C + c] = make_float2((float) b.real(), (float) b.imag()); }
     DevBuf<float2>& dW = s->d_wB.at((hipStream_t) stream); dW.upload(w, (hipStream_t) stream);
     const long perUtt = (long) Tmax * F; const size_t lds = sizeof(float2) * (size_t) F * C;
-    DSR_HIP(hipFuncSetAttribute((const void*) k_bf_apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
     int gx = cdiv(perUtt, 256 * 4); if (gx < 1) gx = 1; if (gx > 4096) gx = 4096;
-    hipLaunchKernelGGL(k_bf_apply, dim3(gx, U), dim3(256), lds, (hipStream_t) stream, (const float2*) X, dW.p, (float2*) Y, C, Tmax, F, perUtt);
-    DSR_HIP(hipGetLastError());
+    launch(k_bf_apply, dim3(gx, U), dim3(256), lds, (hipStream_t) stream, (const float2*) X, dW.p, (float2*) Y, C, Tmax, F, perUtt);
   });
 }
 

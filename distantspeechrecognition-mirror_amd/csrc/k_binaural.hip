@@ -16,7 +16,7 @@
 //                of LDS; Kim scans and applies pow() per frame, IID (linear in the items) scans once per slice and side.
 //                Slice partials go to a workspace and k_est_reduce adds them to the caller's accumulators in slice order.
 //   k_est_fd     FDIID: a workgroup takes one bin of an utterance over all frames, scans once, and owns its accumulators.
-#include "common.h"
+#include "launch.h"
 #include <cmath>
 
 using namespace dsr;
@@ -283,7 +283,7 @@ dsr_status dsr_binmask_reset_state(const dsr_binmask* h, void* state_dev, int U,
   return guard([&] {
     if (!h || !state_dev || U <= 0) throw Error(DSR_E_PARAMETER, "null argument");
     require_device(); const size_t n = (size_t) U * h->F;
-    hipLaunchKernelGGL(k_fill_f, dim3(cdiv((long) n, 256)), dim3(256), 0, (hipStream_t) stream, (float*) state_dev, n, 1.0f); DSR_HIP(hipGetLastError());
+    launch(k_fill_f, dim3(cdiv((long) n, 256)), dim3(256), 0, (hipStream_t) stream, (float*) state_dev, n, 1.0f);
   });
 }
 dsr_status dsr_binmask_state_init(const dsr_binmask* h, void* state_dev, int U, void* stream) { return dsr_binmask_reset_state(h, state_dev, U, stream); }
@@ -298,9 +298,8 @@ dsr_status dsr_binmask_apply(dsr_binmask* h, const float* L_dev, const float* R_
     if (h->haveThr && h->dirty) { h->d_thr.upload(h->thr, st); h->dirty = false; }
     MkPar p{h->kind, h->chanX, U, Tmax, h->F, h->M, outBins, outIsDouble, h->carry, h->threshold, h->alpha, h->dEta};
     if (outBins == h->M) DSR_HIP(hipMemsetAsync(out_dev, 0, (size_t) U * Tmax * outBins * (outIsDouble ? 16 : 8), st));
-    hipLaunchKernelGGL(k_mask, dim3(cdiv(h->F, 64), U), dim3(64), 0, st, (const float2*) L_dev, (const float2*) R_dev, nframes_dev, h->haveThr ? h->d_thr.p : nullptr,
+    launch(k_mask, dim3(cdiv(h->F, 64), U), dim3(64), 0, st, (const float2*) L_dev, (const float2*) R_dev, nframes_dev, h->haveThr ? h->d_thr.p : nullptr,
                        (float*) state_dev, out_dev, mu_dev, itd_dev, p);
-    DSR_HIP(hipGetLastError());
     if (h->kind == 2 && h->haveThr) h->threshold = (float) h->thr[h->F - 1];   // the scalar is overwritten bin by bin (:456-457): the last bin's value stays
   });
 }
@@ -383,17 +382,16 @@ dsr_status dsr_thest_run(dsr_thest* h, const float* L_dev, const float* R_dev, c
     EsPar q{h->kind, U, Tmax, h->F, h->M, h->nCand, nC, h->f0, h->f1, 32, cdiv(Tmax, 32), (double) h->dEta, (double) h->dPowerCoeff};
     const EsPar& p = q;
     if (h->kind == 2) {
-      hipLaunchKernelGGL(k_est_fd, dim3(h->F - 1, U), dim3(BS), 0, st, (const float2*) L_dev, (const float2*) R_dev, nframes_dev, h->d_cand.p,
+      launch(k_est_fd, dim3(h->F - 1, U), dim3(BS), 0, st, (const float2*) L_dev, (const float2*) R_dev, nframes_dev, h->d_cand.p,
                          (double*) state_dev, q, h->per_u());
     } else {
       const int n = h->nacc() * h->nCand;
       EstScratch& sc = g_est.at(st); sc.part.reserve((size_t) U * p.G * n);
       if (nC < h->nCand) DSR_HIP(hipMemsetAsync(sc.part.p, 0, (size_t) U * p.G * n * 8, st));
-      if (h->kind == 0) hipLaunchKernelGGL(k_est_band<0>, dim3(p.G, U), dim3(BS), 0, st, (const float2*) L_dev, (const float2*) R_dev, nframes_dev, h->d_cand.p, sc.part.p, q);
-      else hipLaunchKernelGGL(k_est_band<1>, dim3(p.G, U), dim3(BS), 0, st, (const float2*) L_dev, (const float2*) R_dev, nframes_dev, h->d_cand.p, sc.part.p, q);
-      hipLaunchKernelGGL(k_est_reduce, dim3(cdiv((long) U * (n + 1), 256)), dim3(256), 0, st, sc.part.p, nframes_dev, (double*) state_dev, U, p.G, n, Tmax, h->per_u());
+      if (h->kind == 0) launch(k_est_band<0>, dim3(p.G, U), dim3(BS), 0, st, (const float2*) L_dev, (const float2*) R_dev, nframes_dev, h->d_cand.p, sc.part.p, q);
+      else launch(k_est_band<1>, dim3(p.G, U), dim3(BS), 0, st, (const float2*) L_dev, (const float2*) R_dev, nframes_dev, h->d_cand.p, sc.part.p, q);
+      launch(k_est_reduce, dim3(cdiv((long) U * (n + 1), 256)), dim3(256), 0, st, sc.part.p, nframes_dev, (double*) state_dev, U, p.G, n, Tmax, h->per_u());
     }
-    DSR_HIP(hipGetLastError());
   });
 }
 dsr_status dsr_thest_state_read(const dsr_thest* h, const void* state_dev, int U, int u, double* host_out, size_t outDoubles)

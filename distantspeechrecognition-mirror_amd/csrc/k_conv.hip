@@ -15,7 +15,8 @@
 //                 sample, oldest block first, rounded to fp32 after every add.  One more row per (utterance, channel) is the buffer the next
 //                 call starts from.
 //   k_fir_frames  FilterFeature: a thread per (utterance, frame, coefficient), fp64 accumulator over the taps in ascending order.
-#include "common.h"
+#include "launch.h"
+#include "dev_math.h"
 #include "fft_lds.h"
 #include <cmath>
 #include <complex>
@@ -38,7 +39,6 @@ constexpr int CONV_GRID_LDS = 16384, CONV_GRID_SPEC = 1024, CONV_GRID_GLOBAL = 8
 
 struct CPar { int kind, U, C, T, L, P, N, S; };     // S = L+P-1, the samples of a section that the fold reads
 
-__device__ __forceinline__ int clampT(const int* nf, int u, int Tmax) { int T = nf ? nf[u] : Tmax; return T < 0 ? 0 : (T > Tmax ? Tmax : T); }
 
 // bin k (0 <= k <= n) of the real transform of 2n points from Z = FFT_n(x[2m] + i x[2m+1]): X[k] = E + e^{-2 pi i k / 2n} O with
 // E = (Z[k] + conj Z[n-k]) / 2, O = -i (Z[k] - conj Z[n-k]) / 2; (cs, sn) = cos, sin of pi k / n
@@ -251,8 +251,7 @@ dsr_status dsr_conv_state_init(const dsr_conv* q, void* state_dev, int U, void* 
     if (n == 0) return;
     if (!state_dev) throw Error(DSR_E_PARAMETER, "null argument");
     require_device();
-    hipLaunchKernelGGL(k_conv_zero, dim3(cdiv((long) n, 256)), dim3(256), 0, (hipStream_t) stream, (float*) state_dev, n);
-    DSR_HIP(hipGetLastError());
+    launch(k_conv_zero, dim3(cdiv((long) n, 256)), dim3(256), 0, (hipStream_t) stream, (float*) state_dev, n);
   });
 }
 
@@ -279,28 +278,25 @@ dsr_status dsr_conv_apply(dsr_conv* q, const float* x_dev, const int32_t* nframe
     if (q->timed) DSR_HIP(hipEventRecord(q->ev[0], st));
     if (mode == 0) {
       const size_t ldsBytes = ((size_t) 4 * n + 2 * tw) * 8;
-      if (ldsBytes > 64 * 1024) DSR_HIP(hipFuncSetAttribute((const void*) k_conv_fft<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes));
-      hipLaunchKernelGGL(k_conv_fft<0>, dim3(grid), dim3(B), ldsBytes, st, x_dev, nframes_dev, q->dH.p, p, sc.sec.p, y_dev, (double*) nullptr, items);
+      launch(k_conv_fft<0>, dim3(grid), dim3(B), ldsBytes, st, x_dev, nframes_dev, q->dH.p, p, sc.sec.p, y_dev, (double*) nullptr, items);
     } else if (mode == 1) {
       const size_t ldsBytes = ((size_t) 2 * n + 2 * tw) * 8;
-      DSR_HIP(hipFuncSetAttribute((const void*) k_conv_fft<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes));
       sc.work.reserve((size_t) grid * 2 * n);
-      hipLaunchKernelGGL(k_conv_fft<1>, dim3(grid), dim3(B), ldsBytes, st, x_dev, nframes_dev, q->dH.p, p, sc.sec.p, y_dev, sc.work.p, items);
+      launch(k_conv_fft<1>, dim3(grid), dim3(B), ldsBytes, st, x_dev, nframes_dev, q->dH.p, p, sc.sec.p, y_dev, sc.work.p, items);
     } else {
       sc.work.reserve((size_t) grid * ((size_t) 4 * n + 2 * (size_t) tw));
-      hipLaunchKernelGGL(k_conv_fft<2>, dim3(grid), dim3(B), 0, st, x_dev, nframes_dev, q->dH.p, p, sc.sec.p, y_dev, sc.work.p, items);
+      launch(k_conv_fft<2>, dim3(grid), dim3(B), 0, st, x_dev, nframes_dev, q->dH.p, p, sc.sec.p, y_dev, sc.work.p, items);
     }
     if (q->timed) DSR_HIP(hipEventRecord(q->ev[1], st));
     if (q->kind == 0) {
       const size_t stateN = (size_t) U * q->C * keep;
       sc.newState.reserve(stateN ? stateN : 1);
       const int width = q->L > keep ? q->L : keep;
-      hipLaunchKernelGGL(k_conv_fold, dim3((unsigned) (U * q->C * (Tmax + 1)), cdiv(width, 256)), dim3(256), 0, st, sc.sec.p, nframes_dev, p, (const float*) state_dev,
+      launch(k_conv_fold, dim3((unsigned) (U * q->C * (Tmax + 1)), cdiv(width, 256)), dim3(256), 0, st, sc.sec.p, nframes_dev, p, (const float*) state_dev,
                          sc.newState.p, y_dev);
       if (stateN) DSR_HIP(hipMemcpyAsync(state_dev, sc.newState.p, stateN * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     if (q->timed) DSR_HIP(hipEventRecord(q->ev[2], st));
-    DSR_HIP(hipGetLastError());
   });
 }
 
@@ -337,8 +333,7 @@ dsr_status dsr_fir_frames_run(const float* x_dev, const int32_t* nframes_dev, co
     CScratch& sc = c_scratch.at(st);
     sc.a.upload(a_host, (size_t) lenA, st);
     const size_t total = (size_t) U * Tout * dim;
-    hipLaunchKernelGGL(k_fir_frames, dim3(cdiv((long) total, 256)), dim3(256), 0, st, x_dev, nframes_dev, sc.a.p, lenA, U, Tmax, Tout, dim, y_dev);
-    DSR_HIP(hipGetLastError());
+    launch(k_fir_frames, dim3(cdiv((long) total, 256)), dim3(256), 0, st, x_dev, nframes_dev, sc.a.p, lenA, U, Tmax, Tout, dim, y_dev);
   });
 }
 

@@ -18,6 +18,7 @@
 //   k_doa_frame  per frame: the energy gate and the frame's N-best (strict >: on a tie the earlier theta wins; :3207-3239)
 //   k_doa_acc    acc[u][theta] += rp of every ungated frame, frame by frame in order (caller-owned: block streaming carries it)
 // The MFMA's lane map: csrc/mfma64.h.
+#include "launch.h"
 #include "srp_common.h"
 #include <algorithm>
 #include <cmath>
@@ -189,9 +190,8 @@ void launch_srp(const dsr_doa& s, const float* X, const int* nf, int U, int Tmax
   const int BC = bin_chunk(s.C), F = s.M / 2 + 1;
   const size_t lds = (size_t) s.C * FB * bin_pitch(BC) * sizeof(float2);
   dim3 grid((s.NT + TG - 1) / TG, (Tmax + FB - 1) / FB, U);
-  hipLaunchKernelGGL(k_doa_srp<TG>, grid, dim3(256), lds, st, (const float2*) X, nf, s.dW.p, s.C, Tmax, F, s.M / 2, s.fbinMin, s.fbinMax,
+  launch(k_doa_srp<TG>, grid, dim3(256), lds, st, (const float2*) X, nf, s.dW.p, s.C, Tmax, F, s.M / 2, s.fbinMin, s.fbinMax,
                      s.nTheta, s.NT, s.KS, BC, rp, en, (float2*) Y);
-  DSR_HIP(hipGetLastError());
 }
 
 }  // namespace
@@ -209,8 +209,7 @@ void doa_launch_rp(dsr_doa& s, const float* X, const int* nf, int U, int Tmax, d
 
 void doa_launch_acc(const double* rp, const float* en, const int* nf, int U, int Tmax, int nUnits, float thr, double* acc, hipStream_t st)
 {
-  hipLaunchKernelGGL(k_doa_acc, dim3(cdiv((long) U * nUnits, 256)), dim3(256), 0, st, rp, en, nf, U, Tmax, nUnits, thr, acc);
-  DSR_HIP(hipGetLastError());
+  launch(k_doa_acc, dim3(cdiv((long) U * nUnits, 256)), dim3(256), 0, st, rp, en, nf, U, Tmax, nUnits, thr, acc);
 }
 
 }  // namespace dsr
@@ -319,9 +318,8 @@ dsr_status dsr_doa_srp(dsr_doa* s, const float* X_dev, const int32_t* nframes_de
     if (!rp) { DevBuf<double>& w = s->ws.at(st); w.reserve((size_t) U * Tmax * s->nTheta); rp = w.p; }
     doa_launch_rp(*s, X_dev, nframes_dev, U, Tmax, rp, energy_dev, Y_dev, st);
     const long nfT = (long) U * Tmax;
-    hipLaunchKernelGGL(k_doa_frame, dim3(cdiv(nfT, 256)), dim3(256), 0, st, rp, energy_dev, nframes_dev, U, Tmax, s->nTheta, s->nBest, s->threshold,
+    launch(k_doa_frame, dim3(cdiv(nfT, 256)), dim3(256), 0, st, rp, energy_dev, nframes_dev, U, Tmax, s->nTheta, s->nBest, s->threshold,
                        nbest_rp_dev, nbest_idx_dev, gated_dev);
-    DSR_HIP(hipGetLastError());
     doa_launch_acc(rp, energy_dev, nframes_dev, U, Tmax, s->nTheta, s->threshold, acc_dev, st);
   });
 }

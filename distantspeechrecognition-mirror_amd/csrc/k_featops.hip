@@ -16,7 +16,7 @@
 //   k_minmax        the running / whole-utterance minimum and maximum of ALog and Normalize: contiguous segments a lane, combined in index
 //                   order with the reference's strict comparisons (the first of two equal values stays, which decides the sign of a zero).
 //   the others      one thread per frame (serial fp64 / fp32 sums of SignalPower and the zero-crossing rate) or per output element.
-#include "common.h"
+#include "launch.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -25,6 +25,7 @@ using namespace dsr;
 
 namespace {
 
+// (clampT of dev_math.h in the spelling these kernels were compiled with: the other one changes their instruction schedule)
 __device__ __forceinline__ int clampT(const int* nf, int u, int Tmax) { if (!nf) return Tmax; const int t = nf[u]; return t < 0 ? 0 : (t > Tmax ? Tmax : t); }
 
 // ---- SignalPowerFeature::next (feature.cc:1360-1378): fp64 sum of squares, i ascending, / N / range, one rounding to fp32
@@ -336,10 +337,10 @@ const double* minmax(FScratch& sc, const float* x, const int32_t* nf, int U, int
 {
   if (!state) {
     sc.state.reserve((size_t) 2 * U); state = sc.state.p;
-    hipLaunchKernelGGL(k_minmax_init, dim3(cdiv(U, 64)), dim3(64), 0, st, state, U);
+    launch(k_minmax_init, dim3(cdiv(U, 64)), dim3(64), 0, st, state, U);
   }
   sc.mm.reserve((size_t) 2 * U * (Tmax > 0 ? Tmax : 1));
-  hipLaunchKernelGGL(k_minmax, dim3(U), dim3(64), 0, st, x, nf, Tmax, dim, runon, state, sc.mm.p);
+  launch(k_minmax, dim3(U), dim3(64), 0, st, x, nf, Tmax, dim, runon, state, sc.mm.p);
   return sc.mm.p;
 }
 
@@ -372,8 +373,7 @@ dsr_status dsr_signal_power_run(const float* x_dev, const int32_t* nframes_dev, 
     batch(x_dev, y_dev, U, Tmax, dim);
     if (Tmax == 0) return;
     const double range = float(65536) * float(65536) / 4.0;                                                 // feature.h:629-634
-    hipLaunchKernelGGL(k_signal_power, grid256((size_t) U * Tmax), dim3(256), 0, (hipStream_t) stream, x_dev, nframes_dev, U, Tmax, dim, range, y_dev);
-    DSR_HIP(hipGetLastError());
+    launch(k_signal_power, grid256((size_t) U * Tmax), dim3(256), 0, (hipStream_t) stream, x_dev, nframes_dev, U, Tmax, dim, range, y_dev);
   });
 }
 
@@ -390,8 +390,7 @@ dsr_status dsr_zcr_hamming_run(const float* x_dev, const int32_t* nframes_dev, i
       for (int i = 0; i < dim; i++) w[i] = 0.54 - 0.46 * cos(temp * i);
       sc.wN = -1; sc.w.upload(w, st); sc.wN = dim;
     }
-    hipLaunchKernelGGL(k_zcr, grid256((size_t) U * Tmax), dim3(256), 0, st, x_dev, nframes_dev, sc.w.p, U, Tmax, dim, y_dev);
-    DSR_HIP(hipGetLastError());
+    launch(k_zcr, grid256((size_t) U * Tmax), dim3(256), 0, st, x_dev, nframes_dev, sc.w.p, U, Tmax, dim, y_dev);
   });
 }
 
@@ -411,13 +410,12 @@ dsr_status dsr_yin_pitch_run(const float* x_dev, const int32_t* nframes_dev, int
     if (wpb) {
       int NQ = dim / 4 + 2; NQ += (4 - NQ % 16 + 16) % 16;                                                   // copies 16 banks apart: the four lanes of an address group never meet
       const size_t lds = (size_t) wpb * 4 * NQ * sizeof(float4);
-      hipLaunchKernelGGL(k_yin<true>, dim3((unsigned) ((F + wpb - 1) / wpb)), dim3(64 * wpb), lds, st, x_dev, nframes_dev, U, Tmax, dim, NQ, samplerate, threshold,
+      launch(k_yin<true>, dim3((unsigned) ((F + wpb - 1) / wpb)), dim3(64 * wpb), lds, st, x_dev, nframes_dev, U, Tmax, dim, NQ, samplerate, threshold,
                          pitch_dev, value_dev, chunks_dev);
     } else {
-      hipLaunchKernelGGL(k_yin<false>, dim3((unsigned) ((F + 3) / 4)), dim3(256), 0, st, x_dev, nframes_dev, U, Tmax, dim, 0, samplerate, threshold, pitch_dev,
+      launch(k_yin<false>, dim3((unsigned) ((F + 3) / 4)), dim3(256), 0, st, x_dev, nframes_dev, U, Tmax, dim, 0, samplerate, threshold, pitch_dev,
                          value_dev, chunks_dev);
     }
-    DSR_HIP(hipGetLastError());
   });
 }
 
@@ -436,8 +434,7 @@ dsr_status dsr_spike_filter_run(const float* x_dev, const int32_t* nframes_dev, 
     batch(x_dev, y_dev, U, Tmax, dim);
     if (dsr_spike_filter_check(dim, tapN)) throw Error(DSR_E_DIMENSION, "%s", dsr_last_error());
     if (Tmax == 0) return;
-    hipLaunchKernelGGL(k_spike, grid256((size_t) U * Tmax * dim), dim3(256), 0, (hipStream_t) stream, x_dev, nframes_dev, U, Tmax, dim, tapN, y_dev);
-    DSR_HIP(hipGetLastError());
+    launch(k_spike, grid256((size_t) U * Tmax * dim), dim3(256), 0, (hipStream_t) stream, x_dev, nframes_dev, U, Tmax, dim, tapN, y_dev);
   });
 }
 
@@ -450,9 +447,8 @@ dsr_status dsr_spike_filter2_run(const float* x_dev, const int32_t* nframes_dev,
     if (dim > 16000) throw Error(DSR_E_DIMENSION, "SpikeFilter2 stages a block in LDS: %d samples exceed 16000.", dim);
     if (Tmax == 0) return;
     const float beta = 1.0 - alpha;                                                                          // feature.cc:3704
-    hipLaunchKernelGGL(k_spike2, dim3(U), dim3(64), (size_t) dim * sizeof(float), (hipStream_t) stream, x_dev, nframes_dev, Tmax, dim, width, maxslope, thresh, alpha,
+    launch(k_spike2, dim3(U), dim3(64), (size_t) dim * sizeof(float), (hipStream_t) stream, x_dev, nframes_dev, Tmax, dim, width, maxslope, thresh, alpha,
                        beta, meanslope_dev, count_dev, y_dev);
-    DSR_HIP(hipGetLastError());
   });
 }
 
@@ -461,8 +457,7 @@ dsr_status dsr_minmax_state_init(double* state_dev, int U, void* stream)
   return guard([&] {
     if (!state_dev || U < 1) throw Error(DSR_E_PARAMETER, "bad argument");
     require_device();
-    hipLaunchKernelGGL(k_minmax_init, dim3(cdiv(U, 64)), dim3(64), 0, (hipStream_t) stream, state_dev, U);
-    DSR_HIP(hipGetLastError());
+    launch(k_minmax_init, dim3(cdiv(U, 64)), dim3(64), 0, (hipStream_t) stream, state_dev, U);
   });
 }
 
@@ -475,8 +470,7 @@ dsr_status dsr_alog_run(const float* x_dev, const int32_t* nframes_dev, int U, i
     FScratch& sc = f_scratch.at(st);
     const double* mm = minmax(sc, x_dev, nframes_dev, U, Tmax, dim, runon, state_dev, st);
     if (Tmax > 0)
-      hipLaunchKernelGGL(k_alog, grid256((size_t) U * Tmax), dim3(256), 0, st, x_dev, nframes_dev, U, Tmax, dim, m, pow(10.0, a), runon, state_dev, mm, y_dev);
-    DSR_HIP(hipGetLastError());
+      launch(k_alog, grid256((size_t) U * Tmax), dim3(256), 0, st, x_dev, nframes_dev, U, Tmax, dim, m, pow(10.0, a), runon, state_dev, mm, y_dev);
   });
 }
 
@@ -489,9 +483,8 @@ dsr_status dsr_normalize_run(const float* x_dev, const int32_t* nframes_dev, int
     FScratch& sc = f_scratch.at(st);
     const double* mm = minmax(sc, x_dev, nframes_dev, U, Tmax, dim, runon, state_dev, st);
     if (Tmax > 0)
-      hipLaunchKernelGGL(k_normalize, grid256((size_t) U * Tmax * dim), dim3(256), 0, st, x_dev, nframes_dev, U, Tmax, dim, ymin, ymax - ymin, runon, state_dev, mm,
+      launch(k_normalize, grid256((size_t) U * Tmax * dim), dim3(256), 0, st, x_dev, nframes_dev, U, Tmax, dim, ymin, ymax - ymin, runon, state_dev, mm,
                          y_dev);
-    DSR_HIP(hipGetLastError());
   });
 }
 
@@ -512,8 +505,7 @@ dsr_status dsr_threshold_run(const float* x_dev, const int32_t* nframes_dev, int
     batch(x_dev, y_dev, U, Tmax, dim);
     if (compare < -1 || compare > 1) throw Error(DSR_E_KEY, "Mode %d is not supported", compare);
     if (Tmax == 0) return;
-    hipLaunchKernelGGL(k_thresh_amp, grid256((size_t) U * Tmax * dim), dim3(256), 0, (hipStream_t) stream, x_dev, nframes_dev, U, Tmax, dim, value, thresh, compare, y_dev);
-    DSR_HIP(hipGetLastError());
+    launch(k_thresh_amp, grid256((size_t) U * Tmax * dim), dim3(256), 0, (hipStream_t) stream, x_dev, nframes_dev, U, Tmax, dim, value, thresh, compare, y_dev);
   });
 }
 
@@ -522,8 +514,7 @@ dsr_status dsr_amplify_run(const float* x_dev, const int32_t* nframes_dev, int U
   return guard([&] {
     batch(x_dev, y_dev, U, Tmax, dim);
     if (Tmax == 0) return;
-    hipLaunchKernelGGL(k_thresh_amp, grid256((size_t) U * Tmax * dim), dim3(256), 0, (hipStream_t) stream, x_dev, nframes_dev, U, Tmax, dim, amplify, 0.0, 2, y_dev);
-    DSR_HIP(hipGetLastError());
+    launch(k_thresh_amp, grid256((size_t) U * Tmax * dim), dim3(256), 0, (hipStream_t) stream, x_dev, nframes_dev, U, Tmax, dim, amplify, 0.0, 2, y_dev);
   });
 }
 
@@ -545,8 +536,7 @@ dsr_status dsr_spectral_resample_run(const double* x_dev, const int32_t* nframes
     FScratch& sc = f_scratch.at(st);
     sc.low.upload(low, st); sc.wgt.upload(wgt, st);
     const int outN = (int) low.size();
-    hipLaunchKernelGGL(k_resample, grid256((size_t) U * Tmax * outN), dim3(256), 0, st, x_dev, nframes_dev, sc.low.p, sc.wgt.p, U, Tmax, srcN, outN, y_dev);
-    DSR_HIP(hipGetLastError());
+    launch(k_resample, grid256((size_t) U * Tmax * outN), dim3(256), 0, st, x_dev, nframes_dev, sc.low.p, sc.wgt.p, U, Tmax, srcN, outN, y_dev);
   });
 }
 
@@ -594,8 +584,7 @@ dsr_status dsr_sphinx_mel_apply(dsr_sphinx_mel* q, const double* x_dev, const in
     if (Tmax == 0) return;
     hipStream_t st = (hipStream_t) stream;
     if (!q->up) { q->dA.upload(q->A, st); q->up = true; }
-    hipLaunchKernelGGL(k_sphinx_mel, grid256((size_t) U * Tmax * q->filterN), dim3(256), 0, st, x_dev, nframes_dev, q->dA.p, U, Tmax, q->powerN, q->filterN, y_dev);
-    DSR_HIP(hipGetLastError());
+    launch(k_sphinx_mel, grid256((size_t) U * Tmax * q->filterN), dim3(256), 0, st, x_dev, nframes_dev, q->dA.p, U, Tmax, q->powerN, q->filterN, y_dev);
   });
 }
 

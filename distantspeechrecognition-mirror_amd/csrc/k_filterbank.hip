@@ -12,7 +12,8 @@
 //   analysis : u_t[k] = sum_q h[k+qM] x[n_t-k-qM],  n_t = (t+laN+1)D-1,   X_t[f] = sum_k u_t[k] e^{+2 pi j fk/M}
 //   synthesis: v_tau[k] = Re sum_f Y_tau[f] e^{-2 pi j fk/M} (Hermitian extension, DC/Nyquist imaginary parts dropped)
 //              out_t[D-1-d] = sum_{i<R, t-R+1+i>=0} sum_q g[(M-1-k)+qM] v_{t-R+1+i+pd-Rq}[k],  k = d+iD
-#include "common.h"
+#include "launch.h"
+#include "dev_math.h"
 #include <cmath>
 
 namespace dsr {
@@ -158,7 +159,6 @@ __global__ __launch_bounds__(256) void k_analysis(const float* __restrict__ x, c
 // the spectrum in natural order for the even/odd split.  No workgroup barrier after the window is staged,
 // prototype taps live in registers, rows of M/2+1 complex64 leave as contiguous 8-byte-per-lane stores.
 // LDS layout: [tw: M float2][win: winLen float][zb: waves x N float2]
-__device__ __forceinline__ void wave_lds_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 __device__ __forceinline__ float2 cmulf(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 // lane exchange by a DPP control word (row-local: quad_perm / row_half_mirror / row_ror -- no LDS traffic)
 template <int CTRL> __device__ __forceinline__ float dpp_f(float v)
@@ -392,11 +392,9 @@ template <int M> static void launch_analysis(const FbPlan& p, const FbCall& k, c
   const int winLen = (TF - 1) * D + p.m * M;
   size_t lds = sizeof(float2) * M + sizeof(float) * ((size_t) p.m * M + ((winLen + 3) & ~3) + 2 * (size_t) FB * M);
   if (lds > 160 * 1024) throw Error(DSR_E_DIMENSION, "analysis bank M=%d m=%d needs %zu bytes of LDS", M, p.m, lds);
-  DSR_HIP(hipFuncSetAttribute((const void*) k_analysis<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
   dim3 grid(cdiv(Tmax, TF), C, U);
-  hipLaunchKernelGGL(k_analysis<M>, grid, dim3(256), lds, st, x, nsamp, p.d_proto.p, p.d_tw.p, (float2*) X, C,
+  launch(k_analysis<M>, grid, dim3(256), lds, st, x, nsamp, p.d_proto.p, p.d_tw.p, (float2*) X, C,
                      sampStride, Tmax, p.m, p.r, k.pd, k.laN, p.gain, TF, FB, k.hist, k.histN);
-  DSR_HIP(hipGetLastError());
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -756,15 +754,13 @@ template <int M> static void launch_synthesis(const FbPlan& p, const FbCall& k, 
   const int NV = TO + p.R * p.m - 1;
   size_t lds = sizeof(float2) * M + sizeof(float) * ((size_t) p.m * M + (size_t) NV * M + 2 * (size_t) FB * M);
   if (lds > 160 * 1024) throw Error(DSR_E_DIMENSION, "synthesis bank M=%d m=%d needs %zu bytes of LDS", M, p.m, lds);
-  DSR_HIP(hipFuncSetAttribute((const void*) k_synthesis<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
   const int nblkMax = (int) (outStride / p.D);
   dim3 grid(cdiv(nblkMax > 0 ? nblkMax : 1, TO), U);
   // 1024 threads: the kernel is a chain of barrier-separated LDS phases (build, four FFT stages, copy, per batch of FB frames) and two workgroups of
   // four waves per CU left it latency-bound -- 512 utterances: 1.59 ms at 256 threads, 1.08 at 512, 0.92 at 1024 (TO 32 / FB 16 stay the best shape)
   int synThr = 1024; if (const char* e = getenv("DSR_SYN_THREADS")) { const int v = atoi(e); if (v == 256 || v == 512 || v == 1024) synThr = v; }
-  hipLaunchKernelGGL(k_synthesis<M>, grid, dim3(synThr), lds, st, (const float2*) Y, nframes, p.d_proto.p, p.d_tw.p, y,
+  launch(k_synthesis<M>, grid, dim3(synThr), lds, st, (const float2*) Y, nframes, p.d_proto.p, p.d_tw.p, y,
                      Tmax, outStride, p.m, p.r, k.pd, p.gain, TO, FB, (const float2*) k.hist, k.histN, k.tsMin);
-  DSR_HIP(hipGetLastError());
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -900,10 +896,11 @@ __global__ void k_pr_synth_out(const float* __restrict__ V, const int* __restric
   y[(long) u * outStride + j] = o;
 }
 
-#define DSR_M_DISPATCH(M_, CALL) switch (M_) { \
-  case 16: CALL(16); break; case 32: CALL(32); break; case 64: CALL(64); break; case 128: CALL(128); break; \
-  case 256: CALL(256); break; case 512: CALL(512); break; case 1024: CALL(1024); break; case 2048: CALL(2048); break; \
-  default: throw Error(DSR_E_DIMENSION, "unsupported number of subbands M=%d (power of two in [16,2048])", M_); }
+// the subband counts the generic kernels are instantiated for: f(std::integral_constant<int, M>) for the one that M is
+template <class F> static void for_subbands(int M, F&& f)
+{
+  if (!for_value(ints<16, 32, 64, 128, 256, 512, 1024, 2048>{}, M, f)) throw Error(DSR_E_DIMENSION, "unsupported number of subbands M=%d (power of two in [16,2048])", M);
+}
 
 template <int M, int MT> static void launch_analysis_w(const FbPlan& p, const FbCall& k, const float* x, const int* nsamp, int U, int C,
                                                        long sampStride, int Tmax, float* X, hipStream_t st)
@@ -918,11 +915,9 @@ template <int M, int MT> static void launch_analysis_w(const FbPlan& p, const Fb
   size_t lds = ldsOf(TF);
   if (lds > 160 * 1024) throw Error(DSR_E_DIMENSION, "analysis bank M=%d m=%d needs %zu bytes of LDS", M, MT, lds);
   if (const char* e = getenv("DSR_FB_PADLDS")) lds += (size_t) atoi(e);          // occupancy experiments
-  DSR_HIP(hipFuncSetAttribute((const void*) k_analysis_w<M, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
   dim3 grid(cdiv(Tmax, TF), C, U);
-  hipLaunchKernelGGL((k_analysis_w<M, MT>), grid, dim3(64 * waves), lds, st, x, nsamp, p.d_proto.p, p.d_tw.p, (float2*) X, C,
+  launch(k_analysis_w<M, MT>, grid, dim3(64 * waves), lds, st, x, nsamp, p.d_proto.p, p.d_tw.p, (float2*) X, C,
                      sampStride, Tmax, p.r, k.pd, k.laN, p.gain, TF, k.hist, k.histN);
-  DSR_HIP(hipGetLastError());
 }
 
 template <int MT> static void launch_analysis_q256(const FbPlan& p, const FbCall& k, const float* x, const int* nsamp, int U, int C,
@@ -936,70 +931,52 @@ template <int MT> static void launch_analysis_q256(const FbPlan& p, const FbCall
   size_t lds = sizeof(float2) * M + sizeof(float) * ((winPhys + 3) & ~3) + sizeof(float2) * (size_t) (M / 2) * MT + sizeof(float2) * (size_t) waves * 1 * 4 * 146;
   if (const char* e = getenv("DSR_FB_PADLDS")) lds += (size_t) atoi(e);          // occupancy experiments
   dim3 grid((unsigned) U * (unsigned) C, 1, 1);
-  if (TF == 16) {
-    DSR_HIP(hipFuncSetAttribute((const void*) k_analysis_q256<MT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    hipLaunchKernelGGL((k_analysis_q256<MT, 2>), grid, dim3(64 * waves), lds, st, x, nsamp, p.d_proto.p, p.d_tw.p, (float2*) X, C, sampStride, Tmax, k.pd, k.laN, p.gain, TF, k.hist, k.histN);
-  } else {
-    DSR_HIP(hipFuncSetAttribute((const void*) k_analysis_q256<MT, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    hipLaunchKernelGGL((k_analysis_q256<MT, 4>), grid, dim3(64 * waves), lds, st, x, nsamp, p.d_proto.p, p.d_tw.p, (float2*) X, C, sampStride, Tmax, k.pd, k.laN, p.gain, TF, k.hist, k.histN);
-  }
-  DSR_HIP(hipGetLastError());
+  for_value(ints<2, 4>{}, TF / 8, [&](auto passes) {          // TF is 16 or 32
+    launch(k_analysis_q256<MT, passes()>, grid, dim3(64 * waves), lds, st, x, nsamp, p.d_proto.p, p.d_tw.p, (float2*) X, C, sampStride, Tmax, k.pd, k.laN, p.gain, TF, k.hist, k.histN); });
 }
 
 void fb_analysis(const FbPlan& p, const FbCall& k, const float* x, const int* nsamp, int U, int C, long sampStride, int Tmax, float* X, hipStream_t st)
 {
-  if (!getenv("DSR_FB_GENERIC") && !getenv("DSR_FB_WAVE")) {
-    if (p.M == 256 && p.m == 2 && p.r == 1) { launch_analysis_q256<2>(p, k, x, nsamp, U, C, sampStride, Tmax, X, st); return; }
-    if (p.M == 256 && p.m == 4 && p.r == 1) { launch_analysis_q256<4>(p, k, x, nsamp, U, C, sampStride, Tmax, X, st); return; }
-  }
+  using Taps = ints<2, 4>;                                     // the m the streaming and the wave kernels are instantiated for
+  if (!getenv("DSR_FB_GENERIC") && !getenv("DSR_FB_WAVE") && p.M == 256 && p.r == 1 &&
+      for_value(Taps{}, p.m, [&](auto mt) { launch_analysis_q256<mt()>(p, k, x, nsamp, U, C, sampStride, Tmax, X, st); })) return;
   if (!getenv("DSR_FB_GENERIC")) {
-#define W(MM, TT) if (p.M == MM && p.m == TT) { launch_analysis_w<MM, TT>(p, k, x, nsamp, U, C, sampStride, Tmax, X, st); return; }
-    W(128, 2) W(128, 4) W(256, 2) W(256, 4) W(512, 2) W(512, 4) W(1024, 2) W(1024, 4)
-#undef W
+    bool done = false;
+    for_value(ints<128, 256, 512, 1024>{}, p.M, [&](auto M) {
+      done = for_value(Taps{}, p.m, [&](auto mt) { launch_analysis_w<decltype(M)::value, mt()>(p, k, x, nsamp, U, C, sampStride, Tmax, X, st); }); });
+    if (done) return;
   }
-#define CALL(MM) launch_analysis<MM>(p, k, x, nsamp, U, C, sampStride, Tmax, X, st)
-  DSR_M_DISPATCH(p.M, CALL)
-#undef CALL
+  for_subbands(p.M, [&](auto M) { launch_analysis<M()>(p, k, x, nsamp, U, C, sampStride, Tmax, X, st); });
 }
 template <int M> static void launch_normal_fft(const float* x, const int* nsamp, const float* win, const float2* tw, int U, int C, long sampStride,
                                                int Tmax, int D, float* X, hipStream_t st)
 {
   int FB = 2048 / M; if (FB < 1) FB = 1;
   const size_t lds = sizeof(float2) * ((size_t) M + 2 * (size_t) FB * M);
-  DSR_HIP(hipFuncSetAttribute((const void*) k_normal_fft<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
   dim3 grid(cdiv(Tmax, FB), C, U);
-  hipLaunchKernelGGL(k_normal_fft<M>, grid, dim3(256), lds, st, x, nsamp, win, tw, (float2*) X, C, sampStride, Tmax, D, FB);
-  DSR_HIP(hipGetLastError());
+  launch(k_normal_fft<M>, grid, dim3(256), lds, st, x, nsamp, win, tw, (float2*) X, C, sampStride, Tmax, D, FB);
 }
 void fb_normal_fft(int M, const float* x, const int* nsamp, const float* win, const float2* tw, int U, int C, long sampStride, int Tmax, int D,
                    float* X, hipStream_t st)
 {
-#define CALL(MM) launch_normal_fft<MM>(x, nsamp, win, tw, U, C, sampStride, Tmax, D, X, st)
-  DSR_M_DISPATCH(M, CALL)
-#undef CALL
+  for_subbands(M, [&](auto m) { launch_normal_fft<m()>(x, nsamp, win, tw, U, C, sampStride, Tmax, D, X, st); });
 }
 struct PrPlan { int M, m, r, D; DevBuf<float> h; DevBuf<float2> tw, wA, wS; DevBuf<float> V; };
 template <int M2> static void launch_pr_analysis(const PrPlan& p, const float* x, const int* nsamp, int U, int C, long sampStride, int Tmax, float* X, hipStream_t st)
 {
   int FB = 2048 / M2; if (FB < 1) FB = 1;
   const size_t lds = sizeof(float2) * ((size_t) M2 + 2 * (size_t) FB * M2);
-  DSR_HIP(hipFuncSetAttribute((const void*) k_pr_analysis<M2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-  hipLaunchKernelGGL(k_pr_analysis<M2>, dim3(cdiv(Tmax, FB), C, U), dim3(256), lds, st, x, nsamp, p.h.p, p.tw.p, p.wA.p, (float2*) X, C, sampStride, Tmax, p.D, p.m, p.r, FB);
-  DSR_HIP(hipGetLastError());
+  launch(k_pr_analysis<M2>, dim3(cdiv(Tmax, FB), C, U), dim3(256), lds, st, x, nsamp, p.h.p, p.tw.p, p.wA.p, (float2*) X, C, sampStride, Tmax, p.D, p.m, p.r, FB);
 }
 template <int M2> static void launch_pr_synth_fft(PrPlan& p, const float* Y, const int* nframes, int U, int Tmax, hipStream_t st)
 {
   int FB = 2048 / M2; if (FB < 1) FB = 1;
   const size_t lds = sizeof(float2) * ((size_t) M2 + 2 * (size_t) FB * M2);
-  DSR_HIP(hipFuncSetAttribute((const void*) k_pr_synth_fft<M2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-  hipLaunchKernelGGL(k_pr_synth_fft<M2>, dim3(cdiv(Tmax, FB), U), dim3(256), lds, st, (const float2*) Y, nframes, p.tw.p, p.wS.p, p.V.p, Tmax, FB);
-  DSR_HIP(hipGetLastError());
+  launch(k_pr_synth_fft<M2>, dim3(cdiv(Tmax, FB), U), dim3(256), lds, st, (const float2*) Y, nframes, p.tw.p, p.wS.p, p.V.p, Tmax, FB);
 }
 void fb_synthesis(const FbPlan& p, const FbCall& k, const float* Y, const int* nframes, int U, int Tmax, long outStride, float* y, hipStream_t st)
 {
-#define CALL(MM) launch_synthesis<MM>(p, k, Y, nframes, U, Tmax, outStride, y, st)
-  DSR_M_DISPATCH(p.M, CALL)
-#undef CALL
+  for_subbands(p.M, [&](auto M) { launch_synthesis<M()>(p, k, Y, nframes, U, Tmax, outStride, y, st); });
 }
 
 // carried history of a stream after a block: the last H items of (old history ++ the block's n valid items), item = one sample of a
@@ -1062,9 +1039,7 @@ dsr_status dsr_prfb_analysis(const dsr_prfb* p, const float* x, const int32_t* n
     if (!p || !x || !nsamp_dev || !X) throw Error(DSR_E_PARAMETER, "null argument");
     if (U <= 0 || C <= 0 || Tmax <= 0) return;
     hipStream_t st = (hipStream_t) stream;
-#define CALL(MM) launch_pr_analysis<MM>(*p, x, nsamp_dev, U, C, sampStride, Tmax, X, st)
-    DSR_M_DISPATCH(2 * p->M, CALL)
-#undef CALL
+    for_subbands(2 * p->M, [&](auto M2) { launch_pr_analysis<M2()>(*p, x, nsamp_dev, U, C, sampStride, Tmax, X, st); });
   });
 }
 dsr_status dsr_prfb_synthesis(dsr_prfb* p, const float* Y, const int32_t* nframes_dev, int U, int Tmax, int64_t outStride, float* y, void* stream)
@@ -1074,12 +1049,9 @@ dsr_status dsr_prfb_synthesis(dsr_prfb* p, const float* Y, const int32_t* nframe
     if (U <= 0 || Tmax <= 0 || outStride <= 0) return;
     hipStream_t st = (hipStream_t) stream;
     p->V.reserve((size_t) U * Tmax * 2 * p->M);
-#define CALL(MM) launch_pr_synth_fft<MM>(*p, Y, nframes_dev, U, Tmax, st)
-    DSR_M_DISPATCH(2 * p->M, CALL)
-#undef CALL
-    hipLaunchKernelGGL(k_pr_synth_out, dim3((unsigned) ((outStride + 255) / 256), U), dim3(256), 0, st, p->V.p, nframes_dev, p->h.p, y, Tmax, 2 * p->M, p->D, p->m,
+    for_subbands(2 * p->M, [&](auto M2) { launch_pr_synth_fft<M2()>(*p, Y, nframes_dev, U, Tmax, st); });
+    launch(k_pr_synth_out, dim3((unsigned) ((outStride + 255) / 256), U), dim3(256), 0, st, p->V.p, nframes_dev, p->h.p, y, Tmax, 2 * p->M, p->D, p->m,
                        p->r, (long) outStride);
-    DSR_HIP(hipGetLastError());
   });
 }
 
@@ -1191,11 +1163,9 @@ dsr_status dsr_fb_analysis_beamform(const dsr_fb* p, dsr_bf* bf, const float* x,
     const int winLen = (TF - 1) * p->D + MT * M, winPhys = winLen + 32 * ((winLen + 127) >> 7);
     const size_t lds = sizeof(float2) * M + sizeof(float) * ((winPhys + 3) & ~3) + sizeof(float2) * (size_t) (M / 2) * MT + sizeof(float2) * (size_t) NW * 4 * 146;
     dim3 grid((unsigned) cdiv(Tmax, TF), (unsigned) U);
-#define LFB(MT_, NW_) { DSR_HIP(hipFuncSetAttribute((const void*) k_analysis_bf_q256<MT_, NW_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); \
-      hipLaunchKernelGGL((k_analysis_bf_q256<MT_, NW_>), grid, dim3(64 * NW_), lds, st, x, nsamp, p->d_proto.p, p->d_tw.p, W, (float2*) Y, C, (long) sampStride, Tmax, p->pd, p->laN, p->gain); }
-    if (MT == 4) { if (NW == 8) LFB(4, 8) else LFB(4, 4) } else { if (NW == 8) LFB(2, 8) else LFB(2, 4) }
-#undef LFB
-    DSR_HIP(hipGetLastError());
+    for_value(ints<4, 2>{}, MT, [&](auto mt) { for_value(ints<8, 4>{}, NW, [&](auto nw) {      // dsr_fb_analysis_beamform_supported: m is 2 or 4
+      launch(k_analysis_bf_q256<decltype(mt)::value, nw()>, grid, dim3(64 * nw()), lds, st, x, nsamp, p->d_proto.p, p->d_tw.p, W, (float2*) Y, C, (long) sampStride, Tmax, p->pd,
+             p->laN, p->gain); }); });
   });
 }
 dsr_status dsr_fb_synthesis(const dsr_fb* p, const float* Y, const int32_t* nframes, int U, int Tmax,
@@ -1254,9 +1224,8 @@ dsr_status dsr_fb_analysis_block(const dsr_fb* p, dsr_fb_state* s, const float* 
     fb_analysis(*p, k, x, nsamp_dev, U, C, (long) sampStride, Tmax, X, st);
     if (s->H > 0) {
       int gx = cdiv(s->H, 256); if (gx < 1) gx = 1;
-      hipLaunchKernelGGL(k_hist_update, dim3(gx, (unsigned) U * C), dim3(256), 0, st, s->hist[s->cur].p, s->hist[s->cur ^ 1].p, x, nsamp_dev, C, (long) sampStride,
+      launch(k_hist_update, dim3(gx, (unsigned) U * C), dim3(256), 0, st, s->hist[s->cur].p, s->hist[s->cur ^ 1].p, x, nsamp_dev, C, (long) sampStride,
                          s->H, 1, s->started ? 1 : 0, 1);
-      DSR_HIP(hipGetLastError());
       s->cur ^= 1;
     }
     s->started = true;
@@ -1285,9 +1254,8 @@ dsr_status dsr_fb_synthesis_block(const dsr_fb* p, dsr_fb_state* s, const float*
     fb_synthesis(*p, k, Y, nframes_dev, U, Tmax, (long) outStride, y, st);
     if (s->H > 0) {
       int gx = cdiv((long) s->H * s->rowLen, 256); if (gx < 1) gx = 1; if (gx > 64) gx = 64;
-      hipLaunchKernelGGL(k_hist_update, dim3(gx, (unsigned) U), dim3(256), 0, st, s->hist[s->cur].p, s->hist[s->cur ^ 1].p, Y, nframes_dev, 1, (long) Tmax * s->rowLen,
+      launch(k_hist_update, dim3(gx, (unsigned) U), dim3(256), 0, st, s->hist[s->cur].p, s->hist[s->cur ^ 1].p, Y, nframes_dev, 1, (long) Tmax * s->rowLen,
                          s->H, s->rowLen, s->started ? 1 : 0, 1);
-      DSR_HIP(hipGetLastError());
       s->cur ^= 1;
     }
     s->started = true;

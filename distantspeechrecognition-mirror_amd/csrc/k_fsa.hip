@@ -20,7 +20,7 @@
 //                  shift == -1 float(w[d][0] + x_d).
 // The pair indexing and tile walk of k_fsa_stats restate k_mllr_stats': k_mllr.hip is left as it is, so its object code does not change.
 // This translation unit is compiled with -ffp-contract=off.
-#include "common.h"
+#include "launch.h"
 #include "fsa.h"
 #include "lattice.h"
 #include "mfma64.h"
@@ -216,17 +216,15 @@ void fsa_accumulate(FsaHandle& h, const float* xScore, const float* xSrc, long N
   h.d_gsel.reserve((size_t) A); h.d_part.reserve((size_t) nCh * sz); h.d_stats.reserve((size_t) nSlot * sz);
   {
     Timer tm(h.timing, st, &h.ms[0]);
-    hipLaunchKernelGGL(k_fsa_nearest, dim3(cdiv(A, 256)), dim3(256), 0, st, xScore, D, m.Dp, m.d_off.p, m.d_mean.p, m.d_ivar.p, m.d_cst.p, h.d_frame.p, h.d_dist.p, A,
+    launch(k_fsa_nearest, dim3(cdiv(A, 256)), dim3(256), 0, st, xScore, D, m.Dp, m.d_off.p, m.d_mean.p, m.d_ivar.p, m.d_cst.p, h.d_frame.p, h.d_dist.p, A,
                        h.d_gsel.p);
-    DSR_HIP(hipGetLastError());
     tm.stop();
   }
   {
     Timer tm(h.timing, st, &h.ms[1]);
-    hipLaunchKernelGGL(k_fsa_stats, dim3(nCh), dim3(256), 0, st, D, h.NCp, h.PZ, xSrc, h.d_mean.p, h.d_ivar.p, h.d_frame.p, h.d_gamma.p, h.d_gsel.p, h.d_chunk.p,
+    launch(k_fsa_stats, dim3(nCh), dim3(256), 0, st, D, h.NCp, h.PZ, xSrc, h.d_mean.p, h.d_ivar.p, h.d_frame.p, h.d_gamma.p, h.d_gsel.p, h.d_chunk.p,
                        h.d_pq.p, h.d_part.p);
-    hipLaunchKernelGGL(k_fsa_reduce, dim3(cdiv((long) sz, 256), nSlot), dim3(256), 0, st, (long) sz, h.d_accChunk.p, h.d_part.p, h.d_stats.p);
-    DSR_HIP(hipGetLastError());
+    launch(k_fsa_reduce, dim3(cdiv((long) sz, 256), nSlot), dim3(256), 0, st, (long) sz, h.d_accChunk.p, h.d_part.p, h.d_stats.p);
     tm.stop();
   }
   std::vector<double> stats((size_t) nSlot * sz); std::vector<int> gsel(nearest ? A : 0);
@@ -271,18 +269,14 @@ void fsa_estimate(FsaHandle& h, int iterN, const int* accuX, const int* tranX, i
   {
     const int m = (N1 + 1) & ~1;
     const size_t lds = ((size_t) 2 * N1 * N1 + N1 + m + 2 * kEigThreads) * sizeof(double);
-    DSR_HIP(hipFuncSetAttribute((const void*) k_fsa_eig, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
     Timer tm(h.timing, st, &h.ms[2]);
-    hipLaunchKernelGGL(k_fsa_eig, dim3(n * D), dim3(kEigThreads), lds, st, D, h.d_G.p, h.d_Ginv.p, h.d_flag.p);
-    DSR_HIP(hipGetLastError());
+    launch(k_fsa_eig, dim3(n * D), dim3(kEigThreads), lds, st, D, h.d_G.p, h.d_Ginv.p, h.d_flag.p);
     tm.stop();
   }
   {
     const size_t lds = FsaWork::doubles(D, kRowThreads) * sizeof(double) + (size_t) D * sizeof(int);
-    DSR_HIP(hipFuncSetAttribute((const void*) k_fsa_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
     Timer tm(h.timing, st, &h.ms[3]);
-    hipLaunchKernelGGL(k_fsa_rows, dim3(n), dim3(kRowThreads), lds, st, D, iterN, h.d_Ginv.p, h.d_z.p, h.d_beta.p, h.d_W.p, h.d_flag.p);
-    DSR_HIP(hipGetLastError());
+    launch(k_fsa_rows, dim3(n), dim3(kRowThreads), lds, st, D, iterN, h.d_Ginv.p, h.d_z.p, h.d_beta.p, h.d_W.p, h.d_flag.p);
     tm.stop();
   }
   std::vector<int> flag(n);
@@ -309,8 +303,7 @@ void fsa_apply(FsaHandle& h, const float* x, const int* tranOfRow, long N, float
   if ((long) N * h.D > 0x7fffffffL * 256L) throw Error(DSR_E_DIMENSION, "%ld frames in one call", N);
   if (h.wDirty) { h.d_Wall.upload(h.W, st); h.wDirty = false; }
   Timer tm(h.timing, st, &h.ms[4]);
-  hipLaunchKernelGGL(k_fsa_apply, dim3(cdiv(N * h.D, 256)), dim3(256), 0, st, h.D, N, h.nTran, x, tranOfRow, h.d_Wall.p, shift, out);
-  DSR_HIP(hipGetLastError());
+  launch(k_fsa_apply, dim3(cdiv(N * h.D, 256)), dim3(256), 0, st, h.D, N, h.nTran, x, tranOfRow, h.d_Wall.p, shift, out);
   tm.stop();
 }
 

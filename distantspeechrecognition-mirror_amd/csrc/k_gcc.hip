@@ -25,7 +25,8 @@
 // row per ds_read_b64; twiddles of the two longest stages come from one table (stride 1 and 2), every shorter stage has a contiguous table
 // of its own, because a power-of-two stride into one table would put a half-wave's twiddles on one bank.  The bit-reversed store that loads
 // the data is conflicted (DESIGN 4.4j gives its cost).
-#include "common.h"
+#include "launch.h"
+#include "dev_math.h"
 #include "fft_lds.h"
 #include <cmath>
 
@@ -71,7 +72,6 @@ __device__ __forceinline__ double2 ldx(const void* X, size_t i, int dbl)
 }
 // gsl_complex_mul(a, conj(b))
 __device__ __forceinline__ double2 mulc(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * (-b.y), a.x * (-b.y) + a.y * b.x); }
-__device__ __forceinline__ int clampT(const int* nf, int u, int Tmax) { int T = nf ? nf[u] : Tmax; return T < 0 ? 0 : (T > Tmax ? Tmax : T); }
 
 // NoisePowerSpectrum::add (localization.cc:1163-1183)
 __device__ __forceinline__ void noise_power(double2 x, double stamp, double alpha, double& N, double& has, double& ts)
@@ -440,21 +440,20 @@ void gcc_run(dsr_gcc* g, const void* X_dev, int xIsDouble, const int32_t* nframe
     const GPar p = gpar(*g, U, Tmax, xIsDouble != 0, smooth != 0, minDelay, maxDelay, active, ac1, ac2);
     DSR_HIP(hipMemsetAsync(sc.err.p, 0, sizeof(int), st));
     // the answer this call's leading non-speech frames repeat, from the carried correlation, before anything rewrites it
-    hipLaunchKernelGGL(k_gcc_find_state, dim3(U * g->P), dim3(256), 0, st, p, s, sc.prevRes.p, sc.prevValid.p);
+    launch(k_gcc_find_state, dim3(U * g->P), dim3(256), 0, st, p, s, sc.prevRes.p, sc.prevValid.p);
     const int bs = g->len >= 256 ? 256 : ((g->len + 63) / 64) * 64;
     if (g->timed) DSR_HIP(hipEventRecord(g->ev[0], st));
-    hipLaunchKernelGGL(k_gcc_spectrum, dim3(U * g->P), dim3(bs), 0, st, X_dev, nframes_dev, sad_dev, timestamp_dev, g->d_pairs.p, p, s, xs, sc.err.p);
+    launch(k_gcc_spectrum, dim3(U * g->P), dim3(bs), 0, st, X_dev, nframes_dev, sad_dev, timestamp_dev, g->d_pairs.p, p, s, xs, sc.err.p);
     if (g->timed) DSR_HIP(hipEventRecord(g->ev[1], st));
-    hipLaunchKernelGGL(k_gcc_chan, dim3(U * g->C), dim3(bs), 0, st, X_dev, nframes_dev, sad_dev, timestamp_dev, g->d_inPair.p, p, s, sc.last.p);
+    launch(k_gcc_chan, dim3(U * g->C), dim3(bs), 0, st, X_dev, nframes_dev, sad_dev, timestamp_dev, g->d_inPair.p, p, s, sc.last.p);
     const int n = g->N / 2, B = fft_block(n / 2);
     const size_t ldsBytes = ((size_t) 2 * n + 2 * fft_tw_entries(n) + 2 * B) * 8 + (size_t) B * 4;
     const int grid = (int) (items < 16384 ? items : 16384);
-    hipLaunchKernelGGL(k_gcc_fill, dim3(cdiv(items, 256)), dim3(256), 0, st, sc.last.p, p, sc.prevRes.p, sc.prevValid.p, result_dev, valid_dev, corr_dev, s, items, 0);
+    launch(k_gcc_fill, dim3(cdiv(items, 256)), dim3(256), 0, st, sc.last.p, p, sc.prevRes.p, sc.prevValid.p, result_dev, valid_dev, corr_dev, s, items, 0);
     if (g->timed) DSR_HIP(hipEventRecord(g->ev[2], st));
-    hipLaunchKernelGGL(k_gcc_corr, dim3(grid), dim3(B), ldsBytes, st, xs, nframes_dev, sc.last.p, p, s, result_dev, valid_dev, corr_dev, items);
+    launch(k_gcc_corr, dim3(grid), dim3(B), ldsBytes, st, xs, nframes_dev, sc.last.p, p, s, result_dev, valid_dev, corr_dev, items);
     if (g->timed) DSR_HIP(hipEventRecord(g->ev[3], st));
-    hipLaunchKernelGGL(k_gcc_fill, dim3(cdiv(items, 256)), dim3(256), 0, st, sc.last.p, p, sc.prevRes.p, sc.prevValid.p, result_dev, valid_dev, corr_dev, s, items, 1);
-    DSR_HIP(hipGetLastError());
+    launch(k_gcc_fill, dim3(cdiv(items, 256)), dim3(256), 0, st, sc.last.p, p, sc.prevRes.p, sc.prevValid.p, result_dev, valid_dev, corr_dev, s, items, 1);
     if (g->kind == DSR_GCC_GNNSUB) {                                                                    // the reference dereferences a null noise cross-spectrum here
       int e = 0; DSR_HIP(hipMemcpyAsync(&e, sc.err.p, sizeof(int), hipMemcpyDeviceToHost, st)); DSR_HIP(hipStreamSynchronize(st));
       if (e) throw Error(DSR_E_ERROR, "GCCGnnSub: a speech frame came before any noise frame of its pair (no noise cross-spectrum to subtract)");
@@ -519,8 +518,7 @@ dsr_status dsr_gcc_state_init(const dsr_gcc* g, void* state_dev, int U, void* st
     if (!g || !state_dev || U < 1) throw Error(DSR_E_PARAMETER, "null argument");
     require_device();
     const size_t n = glayout(*g, U).doubles;
-    hipLaunchKernelGGL(k_gcc_state_init, dim3(cdiv((long) n, 256)), dim3(256), 0, (hipStream_t) stream, (double*) state_dev, n);
-    DSR_HIP(hipGetLastError());
+    launch(k_gcc_state_init, dim3(cdiv((long) n, 256)), dim3(256), 0, (hipStream_t) stream, (double*) state_dev, n);
   });
 }
 
@@ -530,8 +528,7 @@ dsr_status dsr_gcc_find_maximum(dsr_gcc* g, double minDelay, double maxDelay, in
     if (!g || !state_dev || !result_dev || !valid_dev || U < 1) throw Error(DSR_E_PARAMETER, "null argument");
     require_device();
     const GState s = gcarve(*g, (void*) state_dev, U);
-    hipLaunchKernelGGL(k_gcc_find_state, dim3(U * g->P), dim3(256), 0, (hipStream_t) stream, gpar(*g, U, 1, 0, 0, minDelay, maxDelay), s, result_dev, valid_dev);
-    DSR_HIP(hipGetLastError());
+    launch(k_gcc_find_state, dim3(U * g->P), dim3(256), 0, (hipStream_t) stream, gpar(*g, U, 1, 0, 0, minDelay, maxDelay), s, result_dev, valid_dev);
   });
 }
 
@@ -686,17 +683,15 @@ dsr_status dsr_cctde_run(const float* a_dev, const float* b_dev, int nItems, int
     const int B = fft_block(fftLen / 2);
     if (fftLen <= CC_LDS_MAX) {
       const size_t ldsBytes = ((size_t) 2 * fftLen + 2 * fft_tw_entries(fftLen) + B) * 8 + (size_t) B * 4;
-      if (ldsBytes > 64 * 1024) DSR_HIP(hipFuncSetAttribute((const void*) k_cctde<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes));
       const int grid = nItems < 16384 ? nItems : 16384;
-      hipLaunchKernelGGL(k_cctde<false>, dim3(grid), dim3(B), ldsBytes, st, a_dev, b_dev, sc.win.p, nItems, blockLen, fftLen, nHeldMaxCC, sampleRate, delays_dev, args_dev,
+      launch(k_cctde<false>, dim3(grid), dim3(B), ldsBytes, st, a_dev, b_dev, sc.win.p, nItems, blockLen, fftLen, nHeldMaxCC, sampleRate, delays_dev, args_dev,
                          values_dev, (double*) nullptr);
     } else {                                                                                           // a recording at once (allsamples): few items, long transforms
       const int grid = nItems < 8 ? nItems : 8;
       sc.work.reserve(cc_work_doubles(fftLen) * grid);
-      hipLaunchKernelGGL(k_cctde<true>, dim3(grid), dim3(B), (size_t) B * 12, st, a_dev, b_dev, sc.win.p, nItems, blockLen, fftLen, nHeldMaxCC, sampleRate, delays_dev,
+      launch(k_cctde<true>, dim3(grid), dim3(B), (size_t) B * 12, st, a_dev, b_dev, sc.win.p, nItems, blockLen, fftLen, nHeldMaxCC, sampleRate, delays_dev,
                          args_dev, values_dev, sc.work.p);
     }
-    DSR_HIP(hipGetLastError());
   });
 }
 

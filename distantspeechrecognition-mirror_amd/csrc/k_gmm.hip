@@ -16,7 +16,7 @@
 //           mode 0's on every frame; a re-scored entry carries mode 0's score bits, every other score
 //           lies within the rounding bound of mode 0's (k_gmm_mfma.hip header) -- NOT bit-identical.
 // This translation unit is compiled with -ffp-contract=off.
-#include "common.h"
+#include "launch.h"
 #include "gmm_model.h"
 #include "gmm_dist.h"
 #include <cmath>
@@ -382,16 +382,13 @@ static dsr_status gmm_score_impl(dsr_gmm* m, const float* x, int64_t N, int mode
       const size_t lds = (size_t) chunkG * m->Dp * 2 * sizeof(float) + (size_t) 256 * (kTW + 1) * sizeof(float) + (argmin ? (size_t) 256 * (kTW + 4) : 0);     // (the index tile only when indices are asked for: it costs a workgroup per CU)
       if (lds > 160 * 1024) throw Error(DSR_E_DIMENSION, "codebook too large for LDS staging");
       dim3 grid(cdiv(N, 256));
-#define LAUNCH(DPV) { DSR_HIP(hipFuncSetAttribute((const void*) k_gmm_exact<DPV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); \
-      hipLaunchKernelGGL(k_gmm_exact<DPV>, grid, dim3(256), lds, st, x, (long) N, m->D, m->K, m->d_off.p, m->d_mean.p, m->d_ivar.p, \
-                         m->d_cst.p, m->d_val.p, m->d_scale.p, score, argmin, chunkG, finish); }
-      if (m->Dp == 16) LAUNCH(16) else if (m->Dp == 40) LAUNCH(40) else if (m->Dp == 64) LAUNCH(64) else LAUNCH(128)
-#undef LAUNCH
-      DSR_HIP(hipGetLastError());
+      using ExactDp = ints<16, 40, 64, 128>;                       // the padded widths k_gmm_exact is instantiated for; any other runs the widest
+      for_value(ExactDp{}, has_value(ExactDp{}, m->Dp) ? m->Dp : 128, [&](auto dp) {
+        launch(k_gmm_exact<dp()>, grid, dim3(256), lds, st, x, (long) N, m->D, m->K, m->d_off.p, m->d_mean.p, m->d_ivar.p, m->d_cst.p, m->d_val.p, m->d_scale.p, score, argmin,
+               chunkG, finish); });
     } else if (mode == 1) {
-      hipLaunchKernelGGL(k_gmm_all, dim3(cdiv(N * m->K, 256)), dim3(256), 0, st, x, (long) N, m->D, m->Dp, m->K, m->d_off.p, m->d_mean.p,
+      launch(k_gmm_all, dim3(cdiv(N * m->K, 256)), dim3(256), 0, st, x, (long) N, m->D, m->Dp, m->K, m->d_off.p, m->d_mean.p,
                          m->d_ivar.p, m->d_cst.p, m->d_val.p, m->d_scale.p, score);
-      DSR_HIP(hipGetLastError());
     } else if (mode == 2) {
       gmm_score_mfma(*m, x, (long) N, score, argmin, st);
     } else throw Error(DSR_E_PARAMETER, "unknown scoring mode %d", mode);

@@ -21,7 +21,8 @@
 // Argmin = mode 0's on every frame; re-scored entries carry mode 0's score bits, the others lie within (2 dimN + 3) 2^-24 S of mode 0's distance
 // (half of that, times the codebook scale, in the score; tests/test_gpu_gmm_shapes.py asserts both at every instantiated depth), i.e. rel 2e-6 on
 // well-conditioned models (tests/test_gpu_parity.py) and 1e-3 by construction.  Mode 0 stays the bit-exact path.
-#include "common.h"
+#include "launch.h"
+#include "dev_math.h"
 #include "gmm_model.h"
 #include <algorithm>
 #include <cmath>
@@ -366,7 +367,7 @@ __global__ __launch_bounds__(256, 2) void k_gmm_mfma_reg(const float* __restrict
   constexpr int NSRCH = 2 * (R == 4 ? 4 : CPC);                  // search groups per chunk (two tiles)
   auto flush = [&](const int ch) __attribute__((always_inline)) {     // after chunk ch has been searched
     if (((ch + 1) % FLUSH) == 0 || ch + 1 == nChunks) {          // the wave's own strip: 64 frames x <= 32 codebooks leave as 128-byte runs
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+      wave_lds_sync();
       const int staged = (ch + 1) * CPC - kFlush0;
       const int cnt = (kFlush0 + staged < K ? staged : K - kFlush0);
       if (!(dbg & 4)) for (int f = kh; f < 64; f += 2) {
@@ -374,7 +375,7 @@ __global__ __launch_bounds__(256, 2) void k_gmm_mfma_reg(const float* __restrict
         if (n < N && col < cnt) { score[n * K + kFlush0 + col] = sbuf[f * SCP + col]; if (argmin) argmin[n * K + kFlush0 + col] = abuf[f * 32 + col]; }
       }
       kFlush0 += staged;
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+      wave_lds_sync();
     }
   };
   // Per chunk: the contraction (the next chunk's operand loads in flight), then the search of its accumulators.  Two waves share a SIMD: one's
@@ -481,17 +482,12 @@ void gmm_score_mfma(GmmModel& m, const float* x, long N, float* score, unsigned 
     if (getenv("DSR_GMM_TIECAP")) cap = std::min<unsigned>(cap, (unsigned) atoi(getenv("DSR_GMM_TIECAP")));   // (tests: a list that fills up, entries settled in place)
     dim3 gridR(nBlk);
     const int dbg = getenv("DSR_GMM_DBG") ? atoi(getenv("DSR_GMM_DBG")) : 0;
-#define LR(SS, RR) { DSR_HIP(hipFuncSetAttribute((const void*) k_gmm_mfma_reg<SS, RR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsR)); \
-  hipLaunchKernelGGL((k_gmm_mfma_reg<SS, RR>), gridR, dim3(256), ldsR, st, x, N, m.D, m.Dp, m.K, m.G, m.GT, m.d_bn.p, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, m.d_scale.p, unitScale, \
-                     score, argmin, tieList.p, tieCount.p, cap, valInLds, dbg, 2.0f * m.ivMax, m.termMax, rad); }
-#define LRS(RR) switch (S4) { case 4: LR(4, RR) break; case 5: LR(5, RR) break; case 9: LR(9, RR) break; case 10: LR(10, RR) break; case 12: LR(12, RR) break; default: LR(17, RR) break; }
+    using RegDepth = ints<4, 5, 9, 10, 12, 17>;                   // the S4 k_gmm_mfma_reg is instantiated for; any other depth runs the deepest
     if (sp && gmm_sp_launch(m, R, x, N, score, argmin, ts.masks, tieList.p, tieCount.p, cap, st)) { }
-    else if (R == 4) LRS(4) else if (R == 8) LRS(8) else if (R == 16) LRS(16) else LRS(32)
-#undef LRS
-#undef LR
-    DSR_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_gmm_ties, dim3(nBlk), dim3(256), 0, st, tieList.p, tieCount.p, cap, x, m.D, m.Dp, m.K, R, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, m.d_scale.p, score, argmin);
-    DSR_HIP(hipGetLastError());
+    else for_value(ints<4, 8, 16, 32>{}, R, [&](auto r) { for_value(RegDepth{}, has_value(RegDepth{}, S4) ? S4 : 17, [&](auto s4) {
+      launch(k_gmm_mfma_reg<s4(), decltype(r)::value>, gridR, dim3(256), ldsR, st, x, N, m.D, m.Dp, m.K, m.G, m.GT, m.d_bn.p, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, m.d_scale.p,
+             unitScale, score, argmin, tieList.p, tieCount.p, cap, valInLds, dbg, 2.0f * m.ivMax, m.termMax, rad); }); });
+    launch(k_gmm_ties, dim3(nBlk), dim3(256), 0, st, tieList.p, tieCount.p, cap, x, m.D, m.Dp, m.K, R, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, m.d_scale.p, score, argmin);
     if (getenv("DSR_GMM_TIES")) {
       std::vector<unsigned> c(nBlk); DSR_HIP(hipStreamSynchronize(st)); DSR_HIP(hipMemcpy(c.data(), tieCount.p, 4 * (size_t) nBlk, hipMemcpyDeviceToHost));
       size_t tot = 0; unsigned mx = 0; for (unsigned v : c) { tot += v; if (v > mx) mx = v; }
@@ -501,14 +497,10 @@ void gmm_score_mfma(GmmModel& m, const float* x, long N, float* score, unsigned 
   }
   const size_t lds = sizeof(float) * ((size_t) 2 * S2 * 64 + (size_t) FT * TS + (size_t) FT * SC) + (size_t) FT * SC;
   dim3 grid(cdiv(N, FT));
-#define LAUNCH(SS) { DSR_HIP(hipFuncSetAttribute((const void*) k_gmm_mfma<SS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); \
-  hipLaunchKernelGGL(k_gmm_mfma<SS>, grid, dim3(256), lds, st, x, N, m.D, m.Dp, m.K, m.G, m.GT, m.d_off.p, m.d_A.p, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, m.d_scale.p, score, argmin, 2.0f * m.ivMax, m.termMax, rad); }
-  switch (S2) {
-    case 16: LAUNCH(16) break; case 20: LAUNCH(20) break; case 36: LAUNCH(36) break;
-    case 40: LAUNCH(40) break; case 48: LAUNCH(48) break; default: LAUNCH(68) break;
-  }
-#undef LAUNCH
-  DSR_HIP(hipGetLastError());
+  using ScanDepth = ints<16, 20, 36, 40, 48, 68>;                 // the S2 k_gmm_mfma is instantiated for; any other depth runs the deepest
+  for_value(ScanDepth{}, has_value(ScanDepth{}, S2) ? S2 : 68, [&](auto s2) {
+    launch(k_gmm_mfma<s2()>, grid, dim3(256), lds, st, x, N, m.D, m.Dp, m.K, m.G, m.GT, m.d_off.p, m.d_A.p, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, m.d_scale.p, score, argmin,
+           2.0f * m.ivMax, m.termMax, rad); });
 }
 
 }  // namespace dsr

@@ -17,7 +17,8 @@
 // Measured at 1 005 600 frames x 1024 codebooks x 4 (rocprofv3, profiles/r03_gmm_sp.txt): 6.62 ms against k_gmm_mfma_reg's 8.95 ms;
 // SQ_VALU_MFMA_BUSY_CYCLES / SQ_BUSY_CYCLES = 0.68 (was 0.52); VALU instructions other than MFMAs 0.48e9 a launch (was 1.0e9).
 // Reference: CodebookBasic::_scoreOpt (asr/gaussian/codebookBasic.cc:509-535).
-#include "common.h"
+#include "launch.h"
+#include "dev_math.h"
 #include "gmm_model.h"
 #include <type_traits>
 
@@ -222,7 +223,7 @@ __global__ __launch_bounds__(256, 1) void k_gmm_mfma_sp(const float* __restrict_
     tieMask = 0u;
     // ---- the strip is complete (32 codebooks staged, or the last chunk): 128-byte runs of scores, 32-byte runs of argmins
     if (!(DBG & 2) && (c4 == SPC - 1 || ch + 1 == nChunks)) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+      wave_lds_sync();
       const int kF = st * CPS; const int cnt = K - kF < (ch - st + 1) * CPS ? K - kF : (ch - st + 1) * CPS;
       const unsigned o = (unsigned) (kF + col + kh * K);
       const unsigned sOff = col < cnt ? o * 4u : INV, aOff = col < cnt ? o : INV;      // (the whole offset in the VGPR: the range check does not see an SGPR offset)
@@ -250,7 +251,7 @@ __global__ __launch_bounds__(256, 1) void k_gmm_mfma_sp(const float* __restrict_
         __builtin_amdgcn_raw_buffer_store_b8(a, ra, aOff + (unsigned) (2 * i * K), 0, 0);
       }
       }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+      wave_lds_sync();
     }
   }
 }
@@ -302,7 +303,10 @@ int gmm_sp_frames() { return 4 * 32 * kSpNT; }
 size_t gmm_sp_lds(const GmmModel& m) { return sizeof(float) * ((size_t) ((m.G + 3) & ~3) + (size_t) 4 * 32 * kSpNT * 36) + (size_t) 4 * 32 * kSpNT * 36 + 16; }
 
 // the shapes there is an instantiation for: four Gaussians a codebook at every contraction depth, 8 / 16 / 32 at the depths of 13- and 39-dimensional features
-bool gmm_sp_has(int S4, int R) { return (R == 4 && (S4 == 4 || S4 == 5 || S4 == 9 || S4 == 10 || S4 == 12 || S4 == 17)) || ((R == 8 || R == 16 || R == 32) && (S4 == 4 || S4 == 10)); }
+using SpDepth4 = ints<4, 5, 9, 10, 12, 17>;   // S4 at R = 4
+using SpWide = ints<8, 16, 32>;               // the other R ...
+using SpDepth = ints<4, 10>;                  // ... and their S4
+bool gmm_sp_has(int S4, int R) { return (R == 4 && has_value(SpDepth4{}, S4)) || (has_value(SpWide{}, R) && has_value(SpDepth{}, S4)); }
 
 // launches the scoring kernel (the caller runs k_gmm_ties over the list afterwards); false when the model's shape has no instantiation
 bool gmm_sp_launch(GmmModel& m, int R, const float* x, long N, float* score, unsigned char* argmin, DevBuf<unsigned>& masks, unsigned long long* tieList, unsigned* tieCount, unsigned cap, hipStream_t st)
@@ -313,22 +317,17 @@ bool gmm_sp_launch(GmmModel& m, int R, const float* x, long N, float* score, uns
   const float rad = gmm_trust_radius(m.D, 1.1e-5f, R == 4 ? 4 : R / 2), radK = gmm_trust_radius(m.D, 1e-5f, 0);   // (thrK multiplies radK by 1000 in the kernel)
   const int stagger = getenv("DSR_GMM_STAGGER") ? atoi(getenv("DSR_GMM_STAGGER")) : 1;
   masks.reserve((size_t) grid.x * 4 * (size_t) m.GT * 64);       // one flag word per lane and chunk
-#define LSD(SS, RR, DD) { DSR_HIP(hipFuncSetAttribute((const void*) k_gmm_mfma_sp<SS, kSpNT, RR, DD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); \
-  hipLaunchKernelGGL((k_gmm_mfma_sp<SS, kSpNT, RR, DD>), grid, dim3(256), lds, st, x, N, m.D, m.Dp, m.K, m.G, m.GT, m.d_bn.p, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, \
-                     score, argmin, masks.p, 2.0f * m.ivMax, m.termMax, rad, radK, stagger); }
+  auto go = [&](auto kernel) {
+    launch(kernel, grid, dim3(256), lds, st, x, N, m.D, m.Dp, m.K, m.G, m.GT, m.d_bn.p, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, score, argmin, masks.p, 2.0f * m.ivMax,
+           m.termMax, rad, radK, stagger); };
   const int dbg = (S4 == 10 && R == 4 && getenv("DSR_GMM_SPDBG")) ? atoi(getenv("DSR_GMM_SPDBG")) : 0;
   if (dbg) {
     if (dbg & 4) DSR_HIP(hipMemsetAsync(masks.p, 0, sizeof(unsigned) * (size_t) grid.x * 4 * (size_t) m.GT * 64, st));   // (no flag words written)
-    switch (dbg) { case 1: LSD(10, 4, 1) break; case 2: LSD(10, 4, 2) break; case 4: LSD(10, 4, 4) break; case 6: LSD(10, 4, 6) break; case 7: LSD(10, 4, 7) break; default: LSD(10, 4, 0) break; }
-  } else if (R == 4) {
-    switch (S4) { case 4: LSD(4, 4, 0) break; case 5: LSD(5, 4, 0) break; case 9: LSD(9, 4, 0) break; case 10: LSD(10, 4, 0) break; case 12: LSD(12, 4, 0) break; default: LSD(17, 4, 0) break; }
-  } else if (R == 8) { if (S4 == 4) LSD(4, 8, 0) else LSD(10, 8, 0) }
-  else if (R == 16) { if (S4 == 4) LSD(4, 16, 0) else LSD(10, 16, 0) }
-  else { if (S4 == 4) LSD(4, 32, 0) else LSD(10, 32, 0) }
-#undef LSD
-  DSR_HIP(hipGetLastError());
-  hipLaunchKernelGGL((k_gmm_tie_compact<kSpNT>), grid, dim3(256), 0, st, masks.p, m.GT, N, m.D, m.Dp, m.K, R, x, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, score, argmin, tieList, tieCount, cap);
-  DSR_HIP(hipGetLastError());
+    using SpDbg = ints<1, 2, 4, 6, 7, 0>;                        // any other value runs the plain kernel
+    for_value(SpDbg{}, has_value(SpDbg{}, dbg) ? dbg : 0, [&](auto d) { go(k_gmm_mfma_sp<10, kSpNT, 4, d()>); });
+  } else if (R == 4) for_value(SpDepth4{}, S4, [&](auto s4) { go(k_gmm_mfma_sp<s4(), kSpNT, 4, 0>); });
+  else for_value(SpWide{}, R, [&](auto r) { for_value(SpDepth{}, S4, [&](auto s4) { go(k_gmm_mfma_sp<s4(), kSpNT, decltype(r)::value, 0>); }); });
+  launch(k_gmm_tie_compact<kSpNT>, grid, dim3(256), 0, st, masks.p, m.GT, N, m.D, m.Dp, m.K, R, x, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, score, argmin, tieList, tieCount, cap);
   return true;
 }
 

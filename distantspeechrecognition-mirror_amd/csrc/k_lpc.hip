@@ -10,7 +10,7 @@
 // one thread per frame, every per-frame array stored [index][frame] so that a wave's accesses are contiguous.
 // The spectrum of the (short) coefficient sequence is a direct fp64 DFT on the reference's 2^ceil(log2 dim)-point grid,
 // of which -- as in the reference -- the first dim/2+1 bins are the output.  Compiled with -ffp-contract=off.
-#include "common.h"
+#include "launch.h"
 #include <cmath>
 
 namespace dsr {
@@ -174,25 +174,24 @@ dsr_status dsr_lpc_run(dsr_lpc* p, const float* frames_dev, int64_t T, double* o
       const int Tc = (int) ((T - t0 < chunk) ? T - t0 : chunk);
       const size_t S = (size_t) Tc;
       p->xt.reserve(S * dim); p->s1.reserve(S * dim); p->e0.reserve(S); p->lp.reserve(S * (order + 1));
-      hipLaunchKernelGGL(k_lpc_transpose, dim3(cdiv(dim, 32), cdiv(Tc, 32)), dim3(32, 8), 0, st, frames_dev + t0 * dim, Tc, dim, p->xt.p);
+      launch(k_lpc_transpose, dim3(cdiv(dim, 32), cdiv(Tc, 32)), dim3(32, 8), 0, st, frames_dev + t0 * dim, Tc, dim, p->xt.p);
       const int nb = cdiv(Tc, 64);
       if (p->method == 0) {
         p->r.reserve(S * (order + 1)); p->a0.reserve(S * (order + 1)); p->a1.reserve(S * (order + 1));
-        hipLaunchKernelGGL(k_lpc_warp, dim3(nb), dim3(64), 0, st, p->xt.p, Tc, dim, order, p->warp, p->s1.p, p->r.p, p->a0.p, p->a1.p, p->lp.p, p->e0.p);
+        launch(k_lpc_warp, dim3(nb), dim3(64), 0, st, p->xt.p, Tc, dim, order, p->warp, p->s1.p, p->r.p, p->a0.p, p->a1.p, p->lp.p, p->e0.p);
       } else {
         p->s2.reserve(S * dim); p->a0.reserve(S * (order + 1));
-        hipLaunchKernelGGL(k_lpc_burg, dim3(nb), dim3(64), 0, st, p->xt.p, Tc, dim, order, p->s1.p, p->s2.p, p->lp.p, p->a0.p, p->e0.p);
+        launch(k_lpc_burg, dim3(nb), dim3(64), 0, st, p->xt.p, Tc, dim, order, p->s1.p, p->s2.p, p->lp.p, p->a0.p, p->e0.p);
       }
       const float* coef = p->lp.p;
       if (p->kind == 0) {
         p->v.reserve(S * (order + 1));
-        hipLaunchKernelGGL(k_lpc_mvdr_pc, dim3(nb), dim3(64), 0, st, p->lp.p, p->e0.p, Tc, order, p->v.p);
+        launch(k_lpc_mvdr_pc, dim3(nb), dim3(64), 0, st, p->lp.p, p->e0.p, Tc, order, p->v.p);
         coef = p->v.p;
       }
       const long n = (long) Tc * outN;
-      hipLaunchKernelGGL(k_lpc_envelope, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, coef, p->e0.p, Tc, dim, order, p->N, p->kind,
+      launch(k_lpc_envelope, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, coef, p->e0.p, Tc, dim, order, p->N, p->kind,
                          p->tw.p, out_dev + t0 * outN);
-      DSR_HIP(hipGetLastError());
     }
   });
 }
@@ -407,8 +406,6 @@ dsr_status dsr_wtmvdr_run(dsr_wtmvdr* p, const float* frames_dev, const float* w
     // rule for both kernels: LDS where the larger fits a CU's 160 KiB (order <= 211), global scratch otherwise.
     const size_t lds1 = (size_t) 3 * (order + 2) * 64 * sizeof(float), lds2 = (size_t) tim * 64 * sizeof(float);
     const bool lds = lds1 <= 160 * 1024;
-    if (lds && lds1 > 64 * 1024) DSR_HIP(hipFuncSetAttribute((const void*) k_wt_lp<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds1));
-    if (lds && lds2 > 64 * 1024) DSR_HIP(hipFuncSetAttribute((const void*) k_wt_chain<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds2));
     // the transform: twiddles and F frames of PA as doubles in at most 64 KiB of LDS, else read from global memory
     int F = (int) (((long) 64 * 1024 - (long) N * 16) / ((long) dim * 8));
     const bool ldsE = F >= 1;
@@ -424,26 +421,25 @@ dsr_status dsr_wtmvdr_run(dsr_wtmvdr* p, const float* frames_dev, const float* w
       p->xt.reserve(S * dim); p->pat.reserve(S * dim); p->e0.reserve(S); p->rw.reserve(S); p->v.reserve(S * (order + 1));
       if (!lds) p->st.reserve(S * 3 * (order + 2));
       mark(0);
-      hipLaunchKernelGGL(k_lpc_transpose, dim3(cdiv(dim, 32), cdiv(Tc, 32)), dim3(32, 8), 0, st, frames_dev + t0 * dim, Tc, dim, p->xt.p);
+      launch(k_lpc_transpose, dim3(cdiv(dim, 32), cdiv(Tc, 32)), dim3(32, 8), 0, st, frames_dev + t0 * dim, Tc, dim, p->xt.p);
       mark(1);
       const int nb = cdiv(Tc, 64);
       const float* wd = warp_dev ? warp_dev + t0 : nullptr;
       float* pa = pa_dev ? pa_dev + t0 * (dim + 1) : nullptr;
       if (lds) {
-        hipLaunchKernelGGL(k_wt_lp<true>, dim3(nb), dim3(64), lds1, st, p->xt.p, wd, Tc, dim, order, p->correlate, p->warp, p->fixed, p->sens, (float*) nullptr, p->v.p, p->e0.p, p->rw.p);
+        launch(k_wt_lp<true>, dim3(nb), dim3(64), lds1, st, p->xt.p, wd, Tc, dim, order, p->correlate, p->warp, p->fixed, p->sens, (float*) nullptr, p->v.p, p->e0.p, p->rw.p);
         mark(2);
-        hipLaunchKernelGGL(k_wt_chain<true>, dim3(nb), dim3(64), lds2, st, p->v.p, p->rw.p, Tc, dim, order, (float*) nullptr, p->pat.p, pa);
+        launch(k_wt_chain<true>, dim3(nb), dim3(64), lds2, st, p->v.p, p->rw.p, Tc, dim, order, (float*) nullptr, p->pat.p, pa);
       } else {
-        hipLaunchKernelGGL(k_wt_lp<false>, dim3(nb), dim3(64), 0, st, p->xt.p, wd, Tc, dim, order, p->correlate, p->warp, p->fixed, p->sens, p->st.p, p->v.p, p->e0.p, p->rw.p);
+        launch(k_wt_lp<false>, dim3(nb), dim3(64), 0, st, p->xt.p, wd, Tc, dim, order, p->correlate, p->warp, p->fixed, p->sens, p->st.p, p->v.p, p->e0.p, p->rw.p);
         mark(2);
-        hipLaunchKernelGGL(k_wt_chain<false>, dim3(nb), dim3(64), 0, st, p->v.p, p->rw.p, Tc, dim, order, p->st.p, p->pat.p, pa);
+        launch(k_wt_chain<false>, dim3(nb), dim3(64), 0, st, p->v.p, p->rw.p, Tc, dim, order, p->st.p, p->pat.p, pa);
       }
       mark(3);
-      if (ldsE) hipLaunchKernelGGL(k_wt_envelope<true>, dim3(cdiv(Tc, F)), dim3(256), lds3, st, p->pat.p, p->e0.p, Tc, dim, N, F, p->tw.p, out_dev + t0 * outN);
-      else hipLaunchKernelGGL(k_wt_envelope<false>, dim3(cdiv(Tc, F)), dim3(256), 0, st, p->pat.p, p->e0.p, Tc, dim, N, F, p->tw.p, out_dev + t0 * outN);
+      if (ldsE) launch(k_wt_envelope<true>, dim3(cdiv(Tc, F)), dim3(256), lds3, st, p->pat.p, p->e0.p, Tc, dim, N, F, p->tw.p, out_dev + t0 * outN);
+      else launch(k_wt_envelope<false>, dim3(cdiv(Tc, F)), dim3(256), 0, st, p->pat.p, p->e0.p, Tc, dim, N, F, p->tw.p, out_dev + t0 * outN);
       mark(4);
       if (rewarp_dev) DSR_HIP(hipMemcpyAsync(rewarp_dev + t0, p->rw.p, S * sizeof(float), hipMemcpyDeviceToDevice, st));
-      DSR_HIP(hipGetLastError());
       if (p->timing) {
         DSR_HIP(hipEventSynchronize(ev[4]));
         for (int i = 0; i < 4; i++) { float ms = 0.f; DSR_HIP(hipEventElapsedTime(&ms, ev[i], ev[i + 1])); p->kms[i] += (double) ms; }
@@ -464,8 +460,7 @@ dsr_status dsr_specsmooth_run(const double* adjust_to_dev, const double* adjust_
     if (!adjust_to_dev || !adjust_from_dev || !out_dev) throw Error(DSR_E_PARAMETER, "null argument");
     if (T <= 0) return;
     if (T > 0x7fffffff) throw Error(DSR_E_PARAMETER, "too many frames");
-    hipLaunchKernelGGL(k_specsmooth, dim3((unsigned) T), dim3(64), 0, (hipStream_t) stream, adjust_to_dev, adjust_from_dev, size, out_dev);
-    DSR_HIP(hipGetLastError());
+    launch(k_specsmooth, dim3((unsigned) T), dim3(64), 0, (hipStream_t) stream, adjust_to_dev, adjust_from_dev, size, out_dev);
   });
 }
 

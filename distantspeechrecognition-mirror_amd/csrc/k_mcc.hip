@@ -17,7 +17,8 @@
 // LDS: a channel's row of the sample tile has a stride S = 2 (mod 32) floats, so the 32 lanes that ds_read_b32 serves in one cycle
 // (16 channels x 2 consecutive samples) fall on 32 banks when the shifts are equal; unequal shifts conflict as the data dictates.  The
 // matrices have a row stride of 16 ceil(C/16) + 1 doubles: a lane per row, and 32 lanes fall on 64 banks of ds_read_b64.
-#include "common.h"
+#include "launch.h"
+#include "dev_math.h"
 #include "mfma64.h"
 #include <cmath>
 
@@ -184,7 +185,6 @@ template <int CT> __device__ void mcc_store(const d4* acc, const MPar& p, double
       }
 }
 
-__device__ __forceinline__ double wave_sum(double v) { for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64); return v; }
 
 // dynamic LDS: max(sample tile C x S floats, MCC_WAVES matrices of CP x (CP + 1) doubles)
 template <int CT> __global__ __launch_bounds__(64 * MCC_WAVES) void k_mcc_cost(const float* __restrict__ x, const int* __restrict__ ns, const int* __restrict__ tau, MPar p,
@@ -371,23 +371,20 @@ void mcc_launch(dsr_mcc* m, const float* x, const int32_t* ns, int U, int N, int
   const int gPer = cdiv(groups, split) * MCC_WAVES; split = cdiv(G, gPer);
   if (o.R) DSR_HIP(hipMemsetAsync(o.R, 0, (size_t) UB * C * C * 8, st));
   if (m->timed) DSR_HIP(hipEventRecord(m->ev[0], st));
-#define MCC_COST(T) { if (ldsCost > 65536) DSR_HIP(hipFuncSetAttribute((const void*) k_mcc_cost<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsCost)); \
-    hipLaunchKernelGGL(k_mcc_cost<T>, dim3((unsigned) UB, split), dim3(64 * MCC_WAVES), ldsCost, st, x, ns, d_tau, p, gPer, o.costMap, o.R); }
-  switch (CT) { case 1: MCC_COST(1) break; case 2: MCC_COST(2) break; case 3: MCC_COST(3) break; default: MCC_COST(4) break; }
-#undef MCC_COST
+  using MccCt = ints<1, 2, 3, 4>;                                  // channel tiles of 16 the two MFMA kernels are instantiated for; any other count runs the widest
+  const int ct = has_value(MccCt{}, CT) ? CT : 4;
+  for_value(MccCt{}, ct, [&](auto t) {
+    launch(k_mcc_cost<t()>, dim3((unsigned) UB, split), dim3(64 * MCC_WAVES), ldsCost, st, x, ns, d_tau, p, gPer, o.costMap, o.R); });
   if (m->timed) DSR_HIP(hipEventRecord(m->ev[1], st));
-  hipLaunchKernelGGL(k_mcc_nbest, dim3((unsigned) UB), dim3(256), 0, st, o.costMap, ns, d_tau, d_pos, p, o.valid, o.index, o.cost, o.tau, o.pos);
+  launch(k_mcc_nbest, dim3((unsigned) UB), dim3(256), 0, st, o.costMap, ns, d_tau, d_pos, p, o.valid, o.index, o.cost, o.tau, o.pos);
   if (m->timed) DSR_HIP(hipEventRecord(m->ev[2], st));
   if (o.eig) {
     MPar pe = p; pe.S = le.S; pe.K = le.K;
     const size_t tileDoubles = (le.lds + 7) / 8, ldsEig = tileDoubles * 8 + matBytes + (size_t) CP * 8;
-#define MCC_EIG(T) { if (ldsEig > 65536) DSR_HIP(hipFuncSetAttribute((const void*) k_mcc_eig<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsEig)); \
-    hipLaunchKernelGGL(k_mcc_eig<T>, dim3((unsigned) (UB * maxSource)), dim3(64), ldsEig, st, x, ns, d_tau, pe, o.index, o.eig, tileDoubles); }
-    switch (CT) { case 1: MCC_EIG(1) break; case 2: MCC_EIG(2) break; case 3: MCC_EIG(3) break; default: MCC_EIG(4) break; }
-#undef MCC_EIG
+    for_value(MccCt{}, ct, [&](auto t) {
+      launch(k_mcc_eig<t()>, dim3((unsigned) (UB * maxSource)), dim3(64), ldsEig, st, x, ns, d_tau, pe, o.index, o.eig, tileDoubles); });
   }
   if (m->timed) DSR_HIP(hipEventRecord(m->ev[3], st));
-  DSR_HIP(hipGetLastError());
 }
 
 void mcc_validate(const dsr_sgb* g, int maxSource, int* Gout, int* Dout, std::vector<int>* tau, std::vector<double>* pos)

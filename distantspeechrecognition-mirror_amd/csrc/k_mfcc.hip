@@ -13,7 +13,8 @@
 // reference loop), so the chain agrees with the CPU path to rounding of libm/FFT ordering only.
 // Tables (Hamming, VTLN interval weights, mel triangles, DCT) are built on the host with the
 // reference's own formulas, including its quirks (mel v1 evaluates the triangle one bin late).
-#include "common.h"
+#include "launch.h"
+#include "dev_math.h"
 #include "ops.h"
 #include <cmath>
 
@@ -41,7 +42,7 @@ struct MfccPlan {
 // (a wavefront's LDS instructions execute in issue order: when the buffers belong to one wavefront a compiler fence is all a stage boundary needs)
 template <bool WAVE> __device__ __forceinline__ void stage_sync()
 {
-  if (WAVE) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
+  if (WAVE) wave_sync();
   else __syncthreads();
 }
 
@@ -672,7 +673,7 @@ void build_dct(int ncep, int nmel, int type, std::vector<float>& dct)
   } else throw Error(DSR_E_INDEX, "Unknown DCT type");
 }
 void op_cmn(const float* in, int T, int N, int mode, double devNormFactor, float* out, hipStream_t st, const float* wgt, int wStride)
-{ if (T > 0) hipLaunchKernelGGL(k_cmn, dim3(cdiv(N, 64)), dim3(64), 0, st, in, (const int*) nullptr, 1, T, N, mode, devNormFactor, out, wgt, wStride); }
+{ if (T > 0) launch(k_cmn, dim3(cdiv(N, 64)), dim3(64), 0, st, in, (const int*) nullptr, 1, T, N, mode, devNormFactor, out, wgt, wStride); }
 
 // The three dispatch decisions of dsr_mfcc_run and the sizes they rest on, in one place: dsr_mfcc_run launches what this returns and
 // dsr_mfcc_paths / dsr_mfcc_cfg_paths report it.  The DSR_*_PLAIN switches are read on every call.
@@ -684,6 +685,7 @@ struct MfccPaths {
 };
 constexpr size_t kCuLds = 160 * 1024;   // LDS of a CU: the most one workgroup can ask for
 constexpr int kLdaFT = 8;               // frames a thread of k_splice_lda_b owns
+using MfccWaveFft = ints<256, 512>;     // the FFT lengths k_mfcc_frames_w is instantiated for
 
 static MfccPaths mfcc_paths(const dsr_mfcc_cfg& c, int melCoefN, int Tmax)
 {
@@ -696,7 +698,7 @@ static MfccPaths mfcc_paths(const dsr_mfcc_cfg& c, int melCoefN, int Tmax)
   r.ldsW = (size_t) c.fftLen * sizeof(double2) * (1 + 4) + (size_t) c.blockLen * sizeof(double)
            + ((size_t) melCoefN + (size_t) c.ncep * c.filterN + 3 * (size_t) c.filterN) * sizeof(float);
   const bool plainOnly = getenv("DSR_MFCC_PLAIN") != nullptr;
-  r.frames = (!plainOnly && r.ldsW <= 52 * 1024 && (c.fftLen == 256 || c.fftLen == 512)) ? DSR_MFCC_FRAMES_W : DSR_MFCC_FRAMES_PLAIN;
+  r.frames = (!plainOnly && r.ldsW <= 52 * 1024 && has_value(MfccWaveFft{}, c.fftLen)) ? DSR_MFCC_FRAMES_W : DSR_MFCC_FRAMES_PLAIN;
   r.ldsC = sizeof(float) * (size_t) Tmax * c.ncep;
   const bool plainCmn = getenv("DSR_CMN_PLAIN") != nullptr;
   if (c.cmnMode == 0) r.cmn = DSR_MFCC_CMN_NONE;
@@ -813,7 +815,7 @@ dsr_status dsr_mfcc_run(dsr_mfcc* p, const float* y, const int32_t* nsamp, int U
     const dsr_mfcc_cfg& c = p->c;
     const size_t nT = (size_t) U * Tmax;
     p->d_T.reserve(U);
-    hipLaunchKernelGGL(k_frame_counts, dim3(cdiv(U, 256)), dim3(256), 0, st, nsamp, U, c.blockLen, c.shiftLen, c.padZeros, p->d_T.p);
+    launch(k_frame_counts, dim3(cdiv(U, 256)), dim3(256), 0, st, nsamp, U, c.blockLen, c.shiftLen, c.padZeros, p->d_T.p);
     float* cepOut = (stage == 1) ? feat : (p->w_cep.reserve(nT * c.ncep), p->w_cep.p);
     MfccDev P;
     P.blockLen = c.blockLen; P.shiftLen = c.shiftLen; P.padZeros = c.padZeros; P.fftLen = c.fftLen; P.powN = c.powN;
@@ -827,8 +829,6 @@ dsr_status dsr_mfcc_run(dsr_mfcc* p, const float* y, const int32_t* nsamp, int U
     const size_t lds = pa.lds;
     dim3 grid(cdiv(Tmax, FPB), U);
     float* powOut = stage == 4 ? feat : nullptr; float* lmOut = stage == 3 ? feat : nullptr;
-#define LAUNCH(FN) { DSR_HIP(hipFuncSetAttribute((const void*) k_mfcc_frames<FN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); \
-    hipLaunchKernelGGL(k_mfcc_frames<FN>, grid, dim3(64 * FPB), lds, st, P, y, nsamp, (long) sampStride, Tmax, cepOut, powOut, lmOut); }
 #ifndef DSR_MFCC_FW
 #define DSR_MFCC_FW 8
 #endif
@@ -836,27 +836,20 @@ dsr_status dsr_mfcc_run(dsr_mfcc* p, const float* y, const int32_t* nsamp, int U
     const size_t ldsW = pa.ldsW;
     if (pa.frames == DSR_MFCC_FRAMES_W) {
       dim3 gridW(cdiv(Tmax, 4 * FW), U);
-#define LAUNCHW(FN) { DSR_HIP(hipFuncSetAttribute((const void*) k_mfcc_frames_w<FN, FW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsW)); \
-    hipLaunchKernelGGL((k_mfcc_frames_w<FN, FW>), gridW, dim3(256), ldsW, st, P, p->melCoefN, y, nsamp, (long) sampStride, Tmax, cepOut, powOut, lmOut); }
-      if (c.fftLen == 256) LAUNCHW(256) else LAUNCHW(512)
-#undef LAUNCHW
-    } else
-    switch (c.fftLen) { case 32: LAUNCH(32) break; case 64: LAUNCH(64) break; case 128: LAUNCH(128) break; case 256: LAUNCH(256) break;
-      case 512: LAUNCH(512) break; case 1024: LAUNCH(1024) break; case 2048: LAUNCH(2048) break; case 4096: LAUNCH(4096) break;
-      default: throw Error(DSR_E_DIMENSION, "unsupported fftLen"); }
-#undef LAUNCH
-    DSR_HIP(hipGetLastError());
+      for_value(MfccWaveFft{}, c.fftLen, [&](auto fn) {
+        launch(k_mfcc_frames_w<fn(), FW>, gridW, dim3(256), ldsW, st, P, p->melCoefN, y, nsamp, (long) sampStride, Tmax, cepOut, powOut, lmOut); });
+    } else if (!for_value(ints<32, 64, 128, 256, 512, 1024, 2048, 4096>{}, c.fftLen, [&](auto fn) {
+                 launch(k_mfcc_frames<fn()>, grid, dim3(64 * FPB), lds, st, P, y, nsamp, (long) sampStride, Tmax, cepOut, powOut, lmOut); }))
+      throw Error(DSR_E_DIMENSION, "unsupported fftLen");
     if (stage == 1 || stage == 3 || stage == 4) return;
     float* cmnOut = cepOut;
     if (c.cmnMode != 0) {
       cmnOut = (stage == 2) ? feat : (p->w_cmn.reserve(nT * c.ncep), p->w_cmn.p);
       const size_t ldsC = pa.ldsC;
       if (pa.cmn == DSR_MFCC_CMN_LDS) {
-        DSR_HIP(hipFuncSetAttribute((const void*) k_cmn_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsC));
-        hipLaunchKernelGGL(k_cmn_lds, dim3(U), dim3(256), ldsC, st, cepOut, p->d_T.p, Tmax, c.ncep, c.devNormFactor, cmnOut);
+        launch(k_cmn_lds, dim3(U), dim3(256), ldsC, st, cepOut, p->d_T.p, Tmax, c.ncep, c.devNormFactor, cmnOut);
       } else
-      hipLaunchKernelGGL(k_cmn, dim3(cdiv((long) U * c.ncep, 64)), dim3(64), 0, st, cepOut, p->d_T.p, U, Tmax, c.ncep, c.cmnMode, c.devNormFactor, cmnOut, (const float*) nullptr, 0);
-      DSR_HIP(hipGetLastError());
+      launch(k_cmn, dim3(cdiv((long) U * c.ncep, 64)), dim3(64), 0, st, cepOut, p->d_T.p, U, Tmax, c.ncep, c.cmnMode, c.devNormFactor, cmnOut, (const float*) nullptr, 0);
     } else if (stage == 2) { DSR_HIP(hipMemcpyAsync(feat, cepOut, nT * c.ncep * sizeof(float), hipMemcpyDeviceToDevice, st)); }
     if (stage == 2) return;
     if (pa.lda == DSR_MFCC_LDA_TOO_LARGE) throw Error(DSR_E_DIMENSION, "linear transform needs %zu bytes of LDS", pa.lds2);
@@ -864,14 +857,11 @@ dsr_status dsr_mfcc_run(dsr_mfcc* p, const float* y, const int32_t* nsamp, int U
     const int FB = pa.FB, nG = pa.nG; const size_t lds2 = pa.lds2, ldsB = pa.ldsB;
     if (pa.lda == DSR_MFCC_LDA_B) {
       const int FBb = nG * FT; const int NB = 4;
-      DSR_HIP(hipFuncSetAttribute((const void*) k_splice_lda_b<FT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsB));
-      hipLaunchKernelGGL(k_splice_lda_b<FT>, dim3(cdiv(Tmax, FBb * NB), U), dim3(256), ldsB, st, cmnOut, p->d_T.p, Tmax, c.ncep, c.delta, c.outDim, p->d_lda.p, feat, nG, NB);
+      launch(k_splice_lda_b<FT>, dim3(cdiv(Tmax, FBb * NB), U), dim3(256), ldsB, st, cmnOut, p->d_T.p, Tmax, c.ncep, c.delta, c.outDim, p->d_lda.p, feat, nG, NB);
     } else {
-      DSR_HIP(hipFuncSetAttribute((const void*) k_splice_lda, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds2));
-      hipLaunchKernelGGL(k_splice_lda, dim3(cdiv(Tmax, FB), U), dim3(256), lds2, st, cmnOut, p->d_T.p, Tmax, c.ncep, c.delta, c.outDim,
+      launch(k_splice_lda, dim3(cdiv(Tmax, FB), U), dim3(256), lds2, st, cmnOut, p->d_T.p, Tmax, c.ncep, c.delta, c.outDim,
                          c.outDim > 0 ? p->d_lda.p : nullptr, feat, FB);
     }
-    DSR_HIP(hipGetLastError());
   });
 }
 

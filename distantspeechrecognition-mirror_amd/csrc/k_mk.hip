@@ -15,7 +15,7 @@
 //
 // One wave (64 lanes) owns a problem.  Every lane carries the same scalars (the butterfly leaves the same sum in every lane), so control flow
 // is uniform; the minimiser's vectors (x, g, trial points, direction) live in LDS and are updated lane-parallel.
-#include "common.h"
+#include "launch.h"
 #include "gsc_weights.h"
 #include <complex>
 #include <cmath>
@@ -93,6 +93,7 @@ struct MkCtx {
   double S2, S4;                                                     // sums of |Y|^2, |Y|^4 of the last evaluation
 };
 
+// (not wave_sum of dev_math.h: this butterfly runs from distance 1 up, the other from 32 down, and the two round differently)
 __device__ __forceinline__ double mk_wsum(double v) { for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m); return v; }
 __device__ __forceinline__ double2 mk_ld(const MkCtx& c, int t, int e) { return c.resident ? c.zs[(long) e * c.Tn + t] : c.scr[(long) t * c.C + e]; }
 
@@ -371,14 +372,12 @@ __global__ __launch_bounds__(256) void k_mk_apply(const float2* __restrict__ X, 
 }
 
 // ---- dispatch, in one place: the launches below and dsr_mk_path read it
-#define MK_CT_LIST(DO) DO(4) DO(6) DO(8)
+using MkCt = ints<4, 6, 8>;                                          // the channel counts k_mk_* are instantiated for besides the run-time 0
+using MkCtAll = ints<4, 6, 8, 0>;
 struct MkPath { int ct, residence, tcap; size_t ldsBytes; };
 static MkPath mk_path(int C, int Tsel, bool forceStreamed)
 {
-  MkPath r; r.ct = 0;
-#define MK_CT_IS(CTV) if (C == CTV) r.ct = CTV;
-  MK_CT_LIST(MK_CT_IS)
-#undef MK_CT_IS
+  MkPath r; r.ct = has_value(MkCt{}, C) ? C : 0;
   r.tcap = MK_FRAME_LDS / (16 * C);
   r.residence = (Tsel <= r.tcap && !forceStreamed) ? DSR_MK_FRAMES_LDS : DSR_MK_FRAMES_STREAMED;
   const size_t vb = ((size_t) MK_NVEC * 2 * (C - 1) * sizeof(double) + 15) & ~(size_t) 15;
@@ -422,24 +421,16 @@ static void mk_run(MkState& s, const float* X, const int32_t* nframes, int U, in
     const size_t lds = (size_t) 64 * (TK * C + 1) * 16;
     const dim3 grid((unsigned) cdiv(F, 64), (unsigned) cdiv(Tsel, TK), (unsigned) U);
     if (grid.y > 65535) throw Error(DSR_E_DIMENSION, "too many frames (%d)", Tsel);
-    bool launched = false;
-#define MK_PREP(CTV) if (!launched && pa.ct == CTV) { DSR_HIP(hipFuncSetAttribute((const void*) k_mk_prepare<CTV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds)); \
-      hipLaunchKernelGGL((k_mk_prepare<CTV>), grid, dim3(64), lds, st, (const float2*) X, s.d_wq.p, s.d_B.p, nframes, s.d_scr.p, C, Tmax, F, Tsel, first, R, eLim, TK); launched = true; }
-    MK_CT_LIST(MK_PREP) MK_PREP(0)
-#undef MK_PREP
-    if (!launched) throw Error(DSR_E_ERROR, "MKSubbandBeamformer: no kernel k_mk_prepare<%d>", pa.ct);
-    DSR_HIP(hipGetLastError());
+    if (!for_value(MkCtAll{}, pa.ct, [&](auto ct) {
+          launch(k_mk_prepare<ct()>, grid, dim3(64), lds, st, (const float2*) X, s.d_wq.p, s.d_B.p, nframes, s.d_scr.p, C, Tmax, F, Tsel, first, R, eLim, TK); }))
+      throw Error(DSR_E_ERROR, "MKSubbandBeamformer: no kernel k_mk_prepare<%d>", pa.ct);
   }
   const unsigned blocks = fbin < 0 ? (unsigned) ((long) U * F) : (unsigned) U;
   const int resident = pa.residence == DSR_MK_FRAMES_LDS ? 1 : 0;
-  bool launched = false;
-#define MK_MIN(CTV) if (!launched && pa.ct == CTV) { DSR_HIP(hipFuncSetAttribute((const void*) k_mk_minimize<CTV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) pa.ldsBytes)); \
-    hipLaunchKernelGGL((k_mk_minimize<CTV>), dim3(blocks), dim3(64), pa.ldsBytes, st, s.d_scr.p, s.d_gam.p, nframes, wa, stats, info, cost, grad, s.p, C, U, F, fbin, Tsel, first, R, \
-                       eLim, resident, evalOnly ? 1 : 0); launched = true; }
-  MK_CT_LIST(MK_MIN) MK_MIN(0)
-#undef MK_MIN
-  if (!launched) throw Error(DSR_E_ERROR, "MKSubbandBeamformer: no kernel k_mk_minimize<%d>", pa.ct);
-  DSR_HIP(hipGetLastError());
+  if (!for_value(MkCtAll{}, pa.ct, [&](auto ct) {
+        launch(k_mk_minimize<ct()>, dim3(blocks), dim3(64), pa.ldsBytes, st, s.d_scr.p, s.d_gam.p, nframes, wa, stats, info, cost, grad, s.p, C, U, F, fbin, Tsel, first, R,
+               eLim, resident, evalOnly ? 1 : 0); }))
+    throw Error(DSR_E_ERROR, "MKSubbandBeamformer: no kernel k_mk_minimize<%d>", pa.ct);
 }
 
 }  // namespace dsr
@@ -557,12 +548,9 @@ dsr_status dsr_mk_apply(dsr_mk* s, const float* X, int U, int Tmax, const double
     const size_t lds = sizeof(float2) * (size_t) F * C;
     if (lds > 160 * 1024) throw Error(DSR_E_DIMENSION, "beamformer weights need %zu bytes of LDS", lds);
     s->d_w.reserve((size_t) nw);
-    hipLaunchKernelGGL(k_mk_weff, dim3((unsigned) cdiv(nw, 256)), dim3(256), 0, (hipStream_t) stream, s->d_wq.p, s->d_B.p, wa, s->d_w.p, U, C, F);
-    DSR_HIP(hipGetLastError());
-    DSR_HIP(hipFuncSetAttribute((const void*) k_mk_apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+    launch(k_mk_weff, dim3((unsigned) cdiv(nw, 256)), dim3(256), 0, (hipStream_t) stream, s->d_wq.p, s->d_B.p, wa, s->d_w.p, U, C, F);
     int gx = cdiv(perUtt, 256 * 4); if (gx < 1) gx = 1; if (gx > 4096) gx = 4096;
-    hipLaunchKernelGGL(k_mk_apply, dim3(gx, U), dim3(256), lds, (hipStream_t) stream, (const float2*) X, s->d_w.p, (float2*) Y, C, F, perUtt);
-    DSR_HIP(hipGetLastError());
+    launch(k_mk_apply, dim3(gx, U), dim3(256), lds, (hipStream_t) stream, (const float2*) X, s->d_w.p, (float2*) Y, C, F, perUtt);
   });
 }
 

@@ -18,7 +18,7 @@
 //   k_mllr_apply   thread per (speaker, Gaussian, row): float comp = bias; comp = float(double(comp) + A[m][n] double(mu[n])), n ascending.
 // The back-off over the tree is a few integers per speaker and runs on the host between k_mllr_reduce and k_mllr_solve.
 // This translation unit is compiled with -ffp-contract=off.
-#include "common.h"
+#include "launch.h"
 #include "adapt.h"
 #include "train.h"
 #include "mfma64.h"
@@ -279,11 +279,10 @@ void mllr_estimate(MllrHandle& h, double threshold, hipStream_t st)
   h.d_part.reserve((size_t) S * nCh * sz); h.d_partTtl.reserve((size_t) S * nCh); h.d_stats.reserve((size_t) S * NN * sz); h.d_ttl.reserve((size_t) S * NN);
   {
     Timer tm(h.timing, st, &h.ms[0]);
-    hipLaunchKernelGGL(k_mllr_stats, dim3(nCh, S), dim3(256), 0, st, D, G, h.NCp, h.PZ, h.d_mean.p, h.d_ivar.p, h.d_c.p, h.d_sumO.p, h.d_gidx.p, h.d_chunk.p,
+    launch(k_mllr_stats, dim3(nCh, S), dim3(256), 0, st, D, G, h.NCp, h.PZ, h.d_mean.p, h.d_ivar.p, h.d_c.p, h.d_sumO.p, h.d_gidx.p, h.d_chunk.p,
                        h.d_pq.p, h.d_part.p, h.d_partTtl.p);
-    hipLaunchKernelGGL(k_mllr_reduce, dim3(NN, S), dim3(256), 0, st, D, h.NCp, nCh, h.d_leafChunk.p, h.d_nodeLeafStart.p, h.d_nodeLeaf.p, h.d_part.p,
+    launch(k_mllr_reduce, dim3(NN, S), dim3(256), 0, st, D, h.NCp, nCh, h.d_leafChunk.p, h.d_nodeLeafStart.p, h.d_nodeLeaf.p, h.d_part.p,
                        h.d_partTtl.p, h.d_stats.p, h.d_ttl.p);
-    DSR_HIP(hipGetLastError());
     tm.stop();
   }
   h.ttl.assign((size_t) S * NN, 0.0);
@@ -310,10 +309,8 @@ void mllr_estimate(MllrHandle& h, double threshold, hipStream_t st)
     const size_t lds = ((size_t) 2 * N1 * N1 + 2 * N1 + m + 2 * kSolveThreads) * sizeof(double);
     h.d_solve.upload(solve, st); h.d_W.reserve(W.size()); h.d_flag.reserve(nSolve);
     DSR_HIP(hipMemsetAsync(h.d_flag.p, 0, nSolve * sizeof(int), st));
-    DSR_HIP(hipFuncSetAttribute((const void*) k_mllr_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
     Timer tm(h.timing, st, &h.ms[1]);
-    hipLaunchKernelGGL(k_mllr_solve, dim3(nSolve * D), dim3(kSolveThreads), lds, st, D, NN, h.NCp, h.PZ, h.d_solve.p, h.d_stats.p, h.d_W.p, h.d_flag.p);
-    DSR_HIP(hipGetLastError());
+    launch(k_mllr_solve, dim3(nSolve * D), dim3(kSolveThreads), lds, st, D, NN, h.NCp, h.PZ, h.d_solve.p, h.d_stats.p, h.d_W.p, h.d_flag.p);
     tm.stop();
     DSR_HIP(hipMemcpyAsync(W.data(), h.d_W.p, W.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     DSR_HIP(hipMemcpyAsync(flag.data(), h.d_flag.p, nSolve * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -339,8 +336,7 @@ void run_apply(MllrHandle& h, int s0, int s1, float* out, hipStream_t st)
   std::vector<double> tab; std::vector<int> map; build_tables(h, s0, s1, tab, map);
   h.d_Wtab.upload(tab, st); h.d_map.upload(map, st);
   Timer tm(h.timing, st, &h.ms[2]);
-  hipLaunchKernelGGL(k_mllr_apply, dim3(cdiv((long) h.G * h.D, 256), s1 - s0), dim3(256), 0, st, h.D, h.G, h.d_mean.p, h.d_map.p, h.d_Wtab.p, out);
-  DSR_HIP(hipGetLastError());
+  launch(k_mllr_apply, dim3(cdiv((long) h.G * h.D, 256), s1 - s0), dim3(256), 0, st, h.D, h.G, h.d_mean.p, h.d_map.p, h.d_Wtab.p, out);
   tm.stop();
 }
 
@@ -384,9 +380,9 @@ dsr_status dsr_mllr_set_stats(dsr_mllr* h, int s, dsr_train* t)
     if (!h || !t) throw Error(DSR_E_PARAMETER, "null argument");
     check_slot(*h, s);
     if (t->G != h->G || t->D != h->D) throw Error(DSR_E_DIMENSION, "accumulators of %d Gaussians x %d for a model of %d x %d", t->G, t->D, h->G, h->D);
-    hipLaunchKernelGGL(k_mllr_take, dim3(cdiv((long) h->G * (h->D + 1), 256)), dim3(256), 0, nullptr, t->d_acc.p, h->G, h->D, h->d_c.p + (size_t) s * h->G,
+    launch(k_mllr_take, dim3(cdiv((long) h->G * (h->D + 1), 256)), dim3(256), 0, nullptr, t->d_acc.p, h->G, h->D, h->d_c.p + (size_t) s * h->G,
                        h->d_sumO.p + (size_t) s * h->G * h->D);
-    DSR_HIP(hipGetLastError()); DSR_HIP(hipDeviceSynchronize());
+    DSR_HIP(hipDeviceSynchronize());
   });
 }
 

@@ -16,7 +16,7 @@
 // is not conjugate-symmetric, so in that configuration the kernel writes all fftLen bins of a frame (dsr_mmi_out_bins) -- the upper ones as the
 // reference leaves them: the conjugate of the UNFILTERED lower bin, or, where the mask struck, the mask's value itself, unconjugated (:2302-2304).
 // In every other configuration the half spectrum is handed on and the mask's averaged value lands in bin k only.
-#include "common.h"
+#include "launch.h"
 #include "svd_linpack.h"
 #include "gsc_weights.h"
 #include <complex>
@@ -470,16 +470,8 @@ dsr_status dsr_mmi_apply(dsr_mmi* m, const float* X, const int32_t* nframes_dev,
     if (C > 16) m->d_ta.reserve((size_t) U * F * C);
     const size_t lds = (size_t) F * (3 * sizeof(double2) + sizeof(int));
     if (lds > 150 * 1024) throw Error(DSR_E_DIMENSION, "SubbandMMI: %d bins need %zu bytes of LDS", F, lds);
-#define MMI_ARGS (const float2*) X, nframes_dev, m->d_weff.p, m->d_wup.p, m->d_mani.p, m->d_csd.p, m->d_ta.p, (float2*) Y, U, C, Tmax, F, S, m->target, m->hbs, \
-                 m->pfType, m->alpha, m->useMask ? 1 : 0, (int) m->maskType, m->avgFactor, (int) m->fwidth, M, dsr_mmi_out_bins(m)
-    if (C <= 16) {
-      DSR_HIP(hipFuncSetAttribute((const void*) k_mmi<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-      hipLaunchKernelGGL(k_mmi<16>, dim3(U), dim3(256), lds, st, MMI_ARGS);
-    } else {
-      DSR_HIP(hipFuncSetAttribute((const void*) k_mmi<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-      hipLaunchKernelGGL(k_mmi<0>, dim3(U), dim3(256), lds, st, MMI_ARGS);
-    }
-#undef MMI_ARGS
-    DSR_HIP(hipGetLastError());
+    for_value(ints<16, 0>{}, C <= 16 ? 16 : 0, [&](auto cap) {   // a thread's vectors in registers up to 16 channels
+      launch(k_mmi<cap()>, dim3(U), dim3(256), lds, st, (const float2*) X, nframes_dev, m->d_weff.p, m->d_wup.p, m->d_mani.p, m->d_csd.p, m->d_ta.p, (float2*) Y, U, C, Tmax, F, S,
+             m->target, m->hbs, m->pfType, m->alpha, m->useMask ? 1 : 0, (int) m->maskType, m->avgFactor, (int) m->fwidth, M, dsr_mmi_out_bins(m)); });
   });
 }

@@ -3,7 +3,7 @@
 // arbitrary operator chains built through the reference's own interface (btk/feature/feature.h), one
 // utterance at a time, with every operator's output type and precision as in the reference.
 // Compiled with -ffp-contract=off.
-#include "common.h"
+#include "launch.h"
 #include "ops.h"
 #include <cmath>
 
@@ -161,7 +161,11 @@ __global__ void k_op_pack_hermitian(const double2* in, int T, int M, float2* out
   out[idx] = make_float2((float) ((a.x + b.x) * 0.5), (float) ((a.y - b.y) * 0.5));
 }
 
-#define GRID(n) dim3((unsigned) (((n) + 255) / 256)), dim3(256), 0, st
+// one thread per item, 256 a block
+template <class... P, class... A> static void launch_n(void (*kernel)(P...), long n, hipStream_t st, A&&... args)
+{
+  launch(kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, std::forward<A>(args)...);
+}
 // Lattice::_updateAcNode (asr/lattice/lattice.cc:392-409): a link's acoustic score = the sum over its frames of its distribution's score, a double
 // accumulator over float scores in frame order.  One thread per link walking a column of the score matrix [T][K]: a gather, a few KB per lattice.
 __global__ void k_op_link_ac(const float* __restrict__ scores, int K, const int* __restrict__ dist, const int* __restrict__ start,
@@ -175,32 +179,30 @@ __global__ void k_op_link_ac(const float* __restrict__ scores, int K, const int*
   out[i] = sum;
 }
 
-void op_frames(const float* x, int nsamp, int T, int L, int shift, float* out, hipStream_t st) { if (T > 0) hipLaunchKernelGGL(k_op_frames, GRID((long) T * L), x, nsamp, T, L, shift, out); }
-void op_preemph(const float* in, int T, int L, double mu, float* out, hipStream_t st) { if (T > 0) hipLaunchKernelGGL(k_op_preemph, GRID((long) T * L), in, T, L, mu, out); }
-void op_hamming_f(const float* in, int T, int L, const double* w, float* out, hipStream_t st) { if (T > 0) hipLaunchKernelGGL(k_op_hamming_f, GRID((long) T * L), in, T, L, w, out); }
-void op_hamming_s(const short* in, int T, int L, const double* w, float* out, hipStream_t st) { if (T > 0) hipLaunchKernelGGL(k_op_hamming_s, GRID((long) T * L), in, T, L, w, out); }
+void op_frames(const float* x, int nsamp, int T, int L, int shift, float* out, hipStream_t st) { if (T > 0) launch_n(k_op_frames, (long) T * L, st, x, nsamp, T, L, shift, out); }
+void op_preemph(const float* in, int T, int L, double mu, float* out, hipStream_t st) { if (T > 0) launch_n(k_op_preemph, (long) T * L, st, in, T, L, mu, out); }
+void op_hamming_f(const float* in, int T, int L, const double* w, float* out, hipStream_t st) { if (T > 0) launch_n(k_op_hamming_f, (long) T * L, st, in, T, L, w, out); }
+void op_hamming_s(const short* in, int T, int L, const double* w, float* out, hipStream_t st) { if (T > 0) launch_n(k_op_hamming_s, (long) T * L, st, in, T, L, w, out); }
 void op_fft(const float* in, int T, int L, int fftLen, const double2* tw, double2* out, hipStream_t st)
 {
   if (T <= 0) return;
   const size_t lds = 2 * (size_t) fftLen * sizeof(double2);
-  DSR_HIP(hipFuncSetAttribute((const void*) k_op_fft, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-  hipLaunchKernelGGL(k_op_fft, dim3(T), dim3(64), lds, st, in, T, L, fftLen, tw, out);
+  launch(k_op_fft, dim3(T), dim3(64), lds, st, in, T, L, fftLen, tw, out);
 }
-void op_power(const double2* in, int T, int fftLen, int powN, double* out, hipStream_t st) { if (T > 0) hipLaunchKernelGGL(k_op_power, GRID((long) T * powN), in, T, fftLen, powN, out); }
+void op_power(const double2* in, int T, int fftLen, int powN, double* out, hipStream_t st) { if (T > 0) launch_n(k_op_power, (long) T * powN, st, in, T, fftLen, powN, out); }
 void op_vtln(const double* in, int T, int N, const int* s, const int* c, const int* o, const double* coef, const double* div, int rf, double* out, hipStream_t st)
-{ if (T > 0) hipLaunchKernelGGL(k_op_vtln, GRID((long) T * N), in, T, N, s, c, o, coef, div, rf, out); }
+{ if (T > 0) launch_n(k_op_vtln, (long) T * N, st, in, T, N, s, c, o, coef, div, rf, out); }
 void op_mel(const double* in, int T, int N, int filterN, const int* s, const int* c, const int* o, const float* coef, double* out, hipStream_t st)
-{ if (T > 0) hipLaunchKernelGGL(k_op_mel, GRID((long) T * filterN), in, T, N, filterN, s, c, o, coef, out); }
-void op_log(const double* in, long n, double m, double a, int sphinx, float* out, hipStream_t st) { if (n > 0) hipLaunchKernelGGL(k_op_log, GRID(n), in, n, m, a, sphinx, out); }
-void op_sgemv(const float* in, int T, int cols, int rows, const float* A, float* out, hipStream_t st) { if (T > 0) hipLaunchKernelGGL(k_op_sgemv, GRID((long) T * rows), in, T, cols, rows, A, out); }
-void op_adjacent(const float* in, int T, int N, int delta, float* out, hipStream_t st) { if (T > 0) hipLaunchKernelGGL(k_op_adjacent, GRID((long) T * (2 * delta + 1) * N), in, T, N, delta, out); }
-void op_expand_bins(const float2* in, int T, int F, int M, double2* out, hipStream_t st) { if (T > 0) hipLaunchKernelGGL(k_op_expand_bins, GRID((long) T * M), in, T, F, M, out); }
-void op_highpass(const double2* in, int T, int M, int cutBin, double2* out, hipStream_t st) { if (T > 0) hipLaunchKernelGGL(k_op_highpass, GRID((long) T * M), in, T, M, cutBin, out); }
-void op_orth_assemble(const float2* low, const double2* full, int T, int F, int M, double2* out, hipStream_t st) { if (T > 0) hipLaunchKernelGGL(k_op_orth_assemble, GRID((long) T * M), low, full, T, F, M, out); }
+{ if (T > 0) launch_n(k_op_mel, (long) T * filterN, st, in, T, N, filterN, s, c, o, coef, out); }
+void op_log(const double* in, long n, double m, double a, int sphinx, float* out, hipStream_t st) { if (n > 0) launch_n(k_op_log, n, st, in, n, m, a, sphinx, out); }
+void op_sgemv(const float* in, int T, int cols, int rows, const float* A, float* out, hipStream_t st) { if (T > 0) launch_n(k_op_sgemv, (long) T * rows, st, in, T, cols, rows, A, out); }
+void op_adjacent(const float* in, int T, int N, int delta, float* out, hipStream_t st) { if (T > 0) launch_n(k_op_adjacent, (long) T * (2 * delta + 1) * N, st, in, T, N, delta, out); }
+void op_expand_bins(const float2* in, int T, int F, int M, double2* out, hipStream_t st) { if (T > 0) launch_n(k_op_expand_bins, (long) T * M, st, in, T, F, M, out); }
+void op_highpass(const double2* in, int T, int M, int cutBin, double2* out, hipStream_t st) { if (T > 0) launch_n(k_op_highpass, (long) T * M, st, in, T, M, cutBin, out); }
+void op_orth_assemble(const float2* low, const double2* full, int T, int F, int M, double2* out, hipStream_t st) { if (T > 0) launch_n(k_op_orth_assemble, (long) T * M, st, low, full, T, F, M, out); }
 void op_link_ac(const float* scores, int K, const int* dist, const int* start, const int* end, int n, double* out, hipStream_t st)
-{ if (n > 0) hipLaunchKernelGGL(k_op_link_ac, GRID((long) n), scores, K, dist, start, end, n, out); }
-void op_pack_hermitian(const double2* in, int T, int M, float2* out, hipStream_t st) { if (T > 0) hipLaunchKernelGGL(k_op_pack_hermitian, GRID((long) T * (M / 2 + 1)), in, T, M, out); }
-void op_pack_bins(const double2* in, int T, int F, int M, float2* out, hipStream_t st) { if (T > 0) hipLaunchKernelGGL(k_op_pack_bins, GRID((long) T * F), in, T, F, M, out); }
-#undef GRID
+{ if (n > 0) launch_n(k_op_link_ac, (long) n, st, scores, K, dist, start, end, n, out); }
+void op_pack_hermitian(const double2* in, int T, int M, float2* out, hipStream_t st) { if (T > 0) launch_n(k_op_pack_hermitian, (long) T * (M / 2 + 1), st, in, T, M, out); }
+void op_pack_bins(const double2* in, int T, int F, int M, float2* out, hipStream_t st) { if (T > 0) launch_n(k_op_pack_bins, (long) T * F, st, in, T, F, M, out); }
 
 }  // namespace dsr

@@ -8,7 +8,8 @@
 // (utterance, bin) and walks the frames; its C(C+1)/2 densities live in a state array laid out [entry][utterance*F + bin],
 // so that a wave's accesses to one entry are contiguous.  Arithmetic is fp64 in the reference's order (this file is
 // compiled with -ffp-contract=off); the snapshots and the beamformer output are the pipe's complex64 arrays.
-#include "common.h"
+#include "launch.h"
+#include "dev_math.h"
 #include "svd_linpack.h"
 #include <complex>
 #include <cmath>
@@ -157,6 +158,7 @@ __global__ __launch_bounds__(1024) void k_zel_recur(const double2* __restrict__ 
 
 // McCowanPostFilter (postfilter.cc:706-744,789-826,833-945): the same recursions, then the noise-coherence corrected estimate of the
 // clean-signal PSD averaged over the microphone pairs.  R: [F][C][C] noise coherence (fp64 complex), thr = _thresholdOfRij.
+// (gsl_div of dev_math.h on four scalars: k_pf_wave schedules differently when the operands are packed into double2 first, so this form stays)
 __device__ __forceinline__ double2 cdiv_gsl(double ar, double ai, double br, double bi)
 { const double s = 1.0 / hypot(br, bi); const double sbr = s * br, sbi = s * bi; return make_double2((ar * sbr + ai * sbi) * s, (ai * sbr - ar * sbi) * s); }
 
@@ -343,12 +345,6 @@ __global__ __launch_bounds__(64) void k_zelinski_reg(const float2* __restrict__ 
 // lane, in registers together with the pair's noise coherence); the time-aligned snapshot of the frame goes through a 1.5 KB LDS strip of the
 // wave; the sums over pairs and channels are wave reductions (fp64 adds in a tree, not in the reference's pair order: 1e-15 relative).
 // One kernel for the three filters: kind 0 Zelinski, 1 McCowan, 2 Lefkimmiatis (lambda != nullptr).
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 template <int KIND>
 __global__ __launch_bounds__(64) void k_pf_wave(const float2* __restrict__ X, const float2* __restrict__ Y, const int* __restrict__ nframesArr,
                                                 const double2* __restrict__ wq, const double2* __restrict__ R, const unsigned short* __restrict__ pairIJ,
@@ -574,8 +570,8 @@ dsr_status dsr_mccowan_divide_nondiagonal(dsr_zelinski* p, float myu)
     const int C = p->C, F = p->M / 2 + 1; const double br = 1.0 + (double) myu;
     for (int f = 0; f < F; f++) for (int a = 0; a < C; a++) for (int b = 0; b < C; b++) if (a != b) {
       double* z = &p->h_R[((size_t) f * C * C + a * C + b) * 2];
-      const double s = 1.0 / hypot(br, 0.0), sbr = s * br, sbi = s * 0.0; const double zr = (z[0] * sbr + z[1] * sbi) * s, zi = (z[1] * sbr - z[0] * sbi) * s;
-      z[0] = zr; z[1] = zi;
+      const double2 q = gsl_div(make_double2(z[0], z[1]), make_double2(br, 0.0));
+      z[0] = q.x; z[1] = q.y;
     }
     p->dirtyR = true;
   });
@@ -591,17 +587,14 @@ dsr_status dsr_zelinski_set_manifold(dsr_zelinski* p, int fbinX, const double* v
 }
 namespace dsr { const float2* bf_fixed_weights_dev(dsr_bf* s); bool bf_has_fixed_weights(const dsr_bf* s); }
 
-// The dispatch of the post-filters, in one place: the launches below switch on it and dsr_zelinski_path reports it.  PF_REG_LIST: the channel counts
+// The dispatch of the post-filters, in one place: the launches below switch on it and dsr_zelinski_path reports it.  PfReg: the channel counts
 // k_zelinski_reg and k_mccowan are instantiated for with the densities in registers.  kind 0 Zelinski, 1 McCowan, 2 Lefkimmiatis; behindFixedBf: the call
 // is dsr_zelinski_apply_bf with a beamformer of fixed weights.  DSR_PF_SUM, DSR_PF_NOFUSE, DSR_PF_WAVE and DSR_PF_MEMSTATE (set to anything) are read on every call.
-#define PF_REG_LIST(DO) DO(2) DO(3) DO(4) DO(6) DO(8)
+using PfReg = ints<2, 3, 4, 6, 8>;
 struct PfPath { int cell, targ; };
 static PfPath pf_path(int kind, int C, bool behindFixedBf)
 {
-  bool inSet = false;
-#define PF_REG_IS(CC) if (C == CC) inSet = true;
-  PF_REG_LIST(PF_REG_IS)
-#undef PF_REG_IS
+  const bool inSet = has_value(PfReg{}, C);
   // Zelinski: the register kernel for the small arrays it is instantiated for, the two streaming kernels for every other size (and on request)
   const bool zsum = kind == 0 && (!inSet || getenv("DSR_PF_SUM"));
   if (zsum) return PfPath{ (behindFixedBf && !getenv("DSR_PF_NOFUSE")) ? DSR_PF_ZEL_SUM_BF : DSR_PF_ZEL_SUM, 0 };
@@ -649,49 +642,39 @@ static void zelinski_apply_impl(dsr_zelinski* p, const PfPath pa, const float* X
         p->lambda.upload(lam); p->dirtyL = false;
       }
     }
-#define PF_TAIL seenIn, seenOut, carryIn, carryOut
     if (zsum) {
       if (!p->carry) p->state.reserve(16);
       ZelinskiPlan::PE& pe = p->pe.at(st); const size_t TF = (size_t) Tmax * F;
       pe.P.reserve((size_t) U * TF); pe.E.reserve((size_t) U * TF);
       if (bfW) {
         float2* Yw = (float2*) Ykeep; if (!Yw) { pe.Y.reserve((size_t) U * TF); Yw = pe.Y.p; }
-        hipLaunchKernelGGL(k_zel_pairs<true>, dim3((unsigned) (((size_t) ((Tmax + 1) / 2) * F + 255) / 256), (unsigned) U), dim3(256), 0, st, (const float2*) X, nframes_dev, p->wqT.p, pe.P.p, pe.E.p, C, Tmax, F, bfW, F + 1, Yw);
+        launch(k_zel_pairs<true>, dim3((unsigned) (((size_t) ((Tmax + 1) / 2) * F + 255) / 256), (unsigned) U), dim3(256), 0, st, (const float2*) X, nframes_dev, p->wqT.p, pe.P.p, pe.E.p, C, Tmax, F, bfW, F + 1, Yw);
         Y = (const float*) Yw;
       } else
-      hipLaunchKernelGGL(k_zel_pairs<false>, dim3((unsigned) (((size_t) ((Tmax + 1) / 2) * F + 255) / 256), (unsigned) U), dim3(256), 0, st, (const float2*) X, nframes_dev, p->wqT.p, pe.P.p, pe.E.p, C, Tmax, F, (const float2*) nullptr, 0, (float2*) nullptr);
-      hipLaunchKernelGGL(k_zel_recur, dim3((unsigned) ((S + 63) / 64)), dim3(1024), 0, st, pe.P.p, pe.E.p, (const float2*) Y, nframes_dev, p->state.p, (float2*) out, wp1,
-                         U, C, Tmax, F, p->alpha, p->type, p->minFrames, PF_TAIL);
+      launch(k_zel_pairs<false>, dim3((unsigned) (((size_t) ((Tmax + 1) / 2) * F + 255) / 256), (unsigned) U), dim3(256), 0, st, (const float2*) X, nframes_dev, p->wqT.p, pe.P.p, pe.E.p, C, Tmax, F, (const float2*) nullptr, 0, (float2*) nullptr);
+      launch(k_zel_recur, dim3((unsigned) ((S + 63) / 64)), dim3(1024), 0, st, pe.P.p, pe.E.p, (const float2*) Y, nframes_dev, p->state.p, (float2*) out, wp1,
+                         U, C, Tmax, F, p->alpha, p->type, p->minFrames, seenIn, seenOut, carryIn, carryOut);
     } else if (wave) {
       const size_t ldsPf = p->kind ? sizeof(double2) * (size_t) C * (C - 1) / 2 : 0;
-#define PFW(K) hipLaunchKernelGGL((k_pf_wave<K>), dim3((unsigned) S), dim3(64), ldsPf, st, (const float2*) X, (const float2*) Y, nframes_dev, p->wq.p, p->R.p, p->pairIJ.p, p->state.p, \
-                                  (float2*) out, wp1, U, C, Tmax, F, p->alpha, p->type, p->minFrames, p->threshold, p->kind == 2 ? p->lambda.p : nullptr, p->fbinX1, PF_TAIL)
-      if (p->kind == 0) PFW(0); else if (p->kind == 1) PFW(1); else PFW(2);
-#undef PFW
+      if (!for_value(ints<0, 1, 2>{}, pa.targ, [&](auto kind) {
+            launch(k_pf_wave<kind()>, dim3((unsigned) S), dim3(64), ldsPf, st, (const float2*) X, (const float2*) Y, nframes_dev, p->wq.p, p->R.p, p->pairIJ.p, p->state.p, (float2*) out,
+                   wp1, U, C, Tmax, F, p->alpha, p->type, p->minFrames, p->threshold, p->kind == 2 ? p->lambda.p : nullptr, p->fbinX1, seenIn, seenOut, carryIn, carryOut); }))
+        throw Error(DSR_E_ERROR, "post-filter: no kernel k_pf_wave<%d>", pa.targ);
     } else if (p->kind >= 1) {
       const bool regsM = pa.cell == DSR_PF_MCCOWAN_REG;
       if (!p->carry) p->state.reserve(regsM ? 16 : S * NE);
       // (state in memory: the working array is the carried one, in place -- the recursions restart by themselves on a stream's first two frames)
-#define MC_LAUNCH(CTV) hipLaunchKernelGGL((k_mccowan<CTV>), dim3((unsigned) ((S + 127) / 128)), dim3(128), 0, st, (const float2*) X, (const float2*) Y, nframes_dev, p->wq.p, p->R.p, p->state.p, \
-                         (float2*) out, wp1, U, C, Tmax, F, p->alpha, p->type, p->minFrames, p->threshold, p->kind == 2 ? p->lambda.p : nullptr, p->fbinX1, PF_TAIL);
-      bool launched = false;
-      if (pa.targ == 0) { MC_LAUNCH(0) launched = true; }
-#define PF_REG_GO(CC) if (!launched && pa.targ == CC) { MC_LAUNCH(CC) launched = true; }
-      PF_REG_LIST(PF_REG_GO)
-#undef PF_REG_GO
-#undef MC_LAUNCH
-      if (!launched) throw Error(DSR_E_ERROR, "post-filter: no kernel k_mccowan<%d>", pa.targ);
+      if (!for_value(ints<0, 2, 3, 4, 6, 8>{}, pa.targ, [&](auto ct) {
+            launch(k_mccowan<ct()>, dim3((unsigned) ((S + 127) / 128)), dim3(128), 0, st, (const float2*) X, (const float2*) Y, nframes_dev, p->wq.p, p->R.p, p->state.p, (float2*) out,
+                   wp1, U, C, Tmax, F, p->alpha, p->type, p->minFrames, p->threshold, p->kind == 2 ? p->lambda.p : nullptr, p->fbinX1, seenIn, seenOut, carryIn, carryOut); }))
+        throw Error(DSR_E_ERROR, "post-filter: no kernel k_mccowan<%d>", pa.targ);
     } else {
       if (!p->carry) p->state.reserve(16);
-      bool launched = false;
-#define ZREG(CC) if (!launched && pa.targ == CC) { hipLaunchKernelGGL(k_zelinski_reg<CC>, dim3((unsigned) ((S + 63) / 64)), dim3(64), 0, st, (const float2*) X, (const float2*) Y, \
-      nframes_dev, p->wq.p, (float2*) out, wp1, U, Tmax, F, p->alpha, p->type, p->minFrames, seenIn, seenOut, p->state.p, carryIn, carryOut); launched = true; }
-      PF_REG_LIST(ZREG)
-#undef ZREG
-      if (!launched) throw Error(DSR_E_ERROR, "post-filter: no kernel k_zelinski_reg<%d>", pa.targ);
+      if (!for_value(PfReg{}, pa.targ, [&](auto cc) {
+            launch(k_zelinski_reg<cc()>, dim3((unsigned) ((S + 63) / 64)), dim3(64), 0, st, (const float2*) X, (const float2*) Y, nframes_dev, p->wq.p, (float2*) out, wp1, U, Tmax, F,
+                   p->alpha, p->type, p->minFrames, seenIn, seenOut, p->state.p, carryIn, carryOut); }))
+        throw Error(DSR_E_ERROR, "post-filter: no kernel k_zelinski_reg<%d>", pa.targ);
     }
-#undef PF_TAIL
-    DSR_HIP(hipGetLastError());
     if (p->carry) { p->haveState = true; p->stateU = U; p->seenCur ^= 1; }
   }
 }

@@ -21,7 +21,7 @@
 //   k_gg             the generalised-Gaussian metrics (negentropy, mutual information, likelihood ratio): a workgroup per utterance, a thread per
 //                    bin, frames in chunks; the per-bin fp64 terms go through LDS to an ordered bin sum a frame.
 //   k_shape          the four spectral-shape operators of sadFeature.cc, a thread per frame.
-#include "common.h"
+#include "launch.h"
 #include "fft_lds.h"
 #include <algorithm>
 #include <cmath>
@@ -30,6 +30,7 @@ using namespace dsr;
 
 namespace {
 
+// (clampT of dev_math.h in the spelling these kernels were compiled with: the other one changes their instruction schedule)
 __device__ __forceinline__ int clampT(const int* nf, int u, int Tmax) { if (!nf) return Tmax; const int t = nf[u]; return t < 0 ? 0 : (t > Tmax ? Tmax : t); }
 
 // ---- EnergyVADMetric::_aboveThreshold (sad.cc:486-490) and SimpleEnergyVAD::next (sad.cc:184-186): the frame's energy
@@ -436,8 +437,7 @@ dsr_status dsr_sad_energy_state_init(double* hist_dev, int32_t* counters_dev, in
     if (!hist_dev || !counters_dev || U < 1 || energiesN < 1) throw Error(DSR_E_PARAMETER, "bad argument");
     require_device();
     const size_t n = std::max((size_t) U * energiesN, (size_t) U);
-    hipLaunchKernelGGL(k_energy_init, grid256(n), dim3(256), 0, (hipStream_t) stream, hist_dev, counters_dev, U, energiesN, initialEnergy, countersOnly);
-    DSR_HIP(hipGetLastError());
+    launch(k_energy_init, grid256(n), dim3(256), 0, (hipStream_t) stream, hist_dev, counters_dev, U, energiesN, initialEnergy, countersOnly);
   });
 }
 
@@ -450,10 +450,9 @@ dsr_status dsr_sad_energy_run(const float* x_dev, const int32_t* nframes_dev, in
     const unsigned mi = median_index(threshold, energiesN);
     hipStream_t st = (hipStream_t) stream;
     if (Tmax > 0)
-      hipLaunchKernelGGL(k_frame_energy<float>, grid256((size_t) U * Tmax), dim3(256), 0, st, x_dev, nframes_dev, U, Tmax, dim, score_dev);
-    hipLaunchKernelGGL(k_energy_walk, dim3(U), dim3(64), (size_t) energiesN * sizeof(double), st, score_dev, nframes_dev, Tmax, energiesN, mi, headN, tailN, hist_dev,
+      launch(k_frame_energy<float>, grid256((size_t) U * Tmax), dim3(256), 0, st, x_dev, nframes_dev, U, Tmax, dim, score_dev);
+    launch(k_energy_walk, dim3(U), dim3(64), (size_t) energiesN * sizeof(double), st, score_dev, nframes_dev, Tmax, energiesN, mi, headN, tailN, hist_dev,
                        counters_dev, decision_dev, updates_dev);
-    DSR_HIP(hipGetLastError());
   });
 }
 
@@ -480,9 +479,8 @@ dsr_status dsr_sad_simple_energy_run(const void* X_dev, const int32_t* nframes_d
     hipStream_t st = (hipStream_t) stream;
     SScratch& sc = s_scratch.at(st);
     sc.e.reserve((size_t) U * Tmax);
-    hipLaunchKernelGGL(k_frame_energy<double2>, grid256((size_t) U * Tmax), dim3(256), 0, st, (const double2*) X_dev, nframes_dev, U, Tmax, fftLen, sc.e.p);
-    hipLaunchKernelGGL(k_simple_walk, dim3(cdiv(U, 64)), dim3(64), 0, st, sc.e.p, nframes_dev, U, Tmax, threshold, gamma, E_dev, decision_dev, score_dev);
-    DSR_HIP(hipGetLastError());
+    launch(k_frame_energy<double2>, grid256((size_t) U * Tmax), dim3(256), 0, st, (const double2*) X_dev, nframes_dev, U, Tmax, fftLen, sc.e.p);
+    launch(k_simple_walk, dim3(cdiv(U, 64)), dim3(64), 0, st, sc.e.p, nframes_dev, U, Tmax, threshold, gamma, E_dev, decision_dev, score_dev);
   });
 }
 
@@ -517,9 +515,8 @@ dsr_status dsr_sad_power_run(const float* P_dev, const int32_t* nframes_dev, int
     if (lowX > highX || highX >= (unsigned) F) throw Error(DSR_E_DIMENSION, "Bins %u .. %u lie outside a spectrum of %d bins.", lowX, highX, F);
     if (Tmax == 0) return;
     hipStream_t st = (hipStream_t) stream;
-    hipLaunchKernelGGL(k_band_power, grid256((size_t) U * Tmax * C), dim3(256), 0, st, P_dev, nframes_dev, U, C, Tmax, F, (int) lowX, (int) highX, fftLen, powers_dev);
-    hipLaunchKernelGGL(k_power_decide, grid256((size_t) U * Tmax), dim3(256), 0, st, powers_dev, nframes_dev, U, C, Tmax, kind, E0, decision_dev, score_dev);
-    DSR_HIP(hipGetLastError());
+    launch(k_band_power, grid256((size_t) U * Tmax * C), dim3(256), 0, st, P_dev, nframes_dev, U, C, Tmax, F, (int) lowX, (int) highX, fftLen, powers_dev);
+    launch(k_power_decide, grid256((size_t) U * Tmax), dim3(256), 0, st, powers_dev, nframes_dev, U, C, Tmax, kind, E0, decision_dev, score_dev);
   });
 }
 
@@ -539,12 +536,11 @@ static dsr_status ccc_run(const void* X_dev, int isDouble, const int32_t* nframe
     const dim3 grid((unsigned) ((size_t) U * Tmax)), block(fft_block(N / 2));
     hipStream_t st = (hipStream_t) stream;
     if (isDouble)
-      hipLaunchKernelGGL(k_ccc<double2>, grid, block, lds, st, (const double2*) X_dev, nframes_dev, U, C, Tmax, N, logN, (int) lowX, (int) highX, (int) nCand, threshold,
+      launch(k_ccc<double2>, grid, block, lds, st, (const double2*) X_dev, nframes_dev, U, C, Tmax, N, logN, (int) lowX, (int) highX, (int) nCand, threshold,
                          decision_dev, score_dev, cands_dev, nbest);
     else
-      hipLaunchKernelGGL(k_ccc<float2>, grid, block, lds, st, (const float2*) X_dev, nframes_dev, U, C, Tmax, N, logN, (int) lowX, (int) highX, (int) nCand, threshold,
+      launch(k_ccc<float2>, grid, block, lds, st, (const float2*) X_dev, nframes_dev, U, C, Tmax, N, logN, (int) lowX, (int) highX, (int) nCand, threshold,
                          decision_dev, score_dev, cands_dev, nbest);
-    DSR_HIP(hipGetLastError());
   });
 }
 
@@ -567,9 +563,8 @@ dsr_status dsr_sad_hangover_run(const double* decisions_dev, const int32_t* nfra
     if (kind == 1 && K != 3) throw Error(DSR_E_DIMENSION, "HangoverMIVADFeature takes 3 metrics, got %d.", K);
     if (headN < 1) throw Error(DSR_E_DIMENSION, "headN = 0: the reference's ring of buffered frames would be empty.");
     HangArgs a; for (int k = 0; k < 8; k++) a.thr[k] = k < K ? thresholds[k] : 0.0;
-    hipLaunchKernelGGL(k_hangover, dim3(cdiv(U, 64)), dim3(64), 0, (hipStream_t) stream, decisions_dev, nframes_dev, K, U, Tmax, kind, a, headN, tailN, start_dev,
+    launch(k_hangover, dim3(cdiv(U, 64)), dim3(64), 0, (hipStream_t) stream, decisions_dev, nframes_dev, K, U, Tmax, kind, a, headN, tailN, start_dev,
                        length_dev, consumed_dev, decision_metric_dev);
-    DSR_HIP(hipGetLastError());
   });
 }
 
@@ -579,8 +574,7 @@ dsr_status dsr_sad_gather_run(const float* x_dev, const int32_t* start_dev, cons
     batch(x_dev, U, Tmax, dim);
     if (!start_dev || !length_dev || !y_dev) throw Error(DSR_E_PARAMETER, "null argument");
     if (Tmax == 0) return;
-    hipLaunchKernelGGL(k_gather, grid256((size_t) U * Tmax * dim), dim3(256), 0, (hipStream_t) stream, x_dev, start_dev, length_dev, U, Tmax, dim, y_dev);
-    DSR_HIP(hipGetLastError());
+    launch(k_gather, grid256((size_t) U * Tmax * dim), dim3(256), 0, (hipStream_t) stream, x_dev, start_dev, length_dev, U, Tmax, dim, y_dev);
   });
 }
 
@@ -604,8 +598,7 @@ dsr_status dsr_sad_shape_run(const float* x_dev, const int32_t* nframes_dev, int
     int tx = 0;
     if (op == 1 && dsr_sad_band_ratio_index(dim, sampleRate, thresh, &tx)) throw Error(DSR_E_DIMENSION, "%s", dsr_last_error());
     if (Tmax == 0) return;
-    hipLaunchKernelGGL(k_shape, grid256((size_t) U * Tmax), dim3(256), 0, (hipStream_t) stream, x_dev, nframes_dev, U, Tmax, dim, op, tx, thresh, y_dev);
-    DSR_HIP(hipGetLastError());
+    launch(k_shape, grid256((size_t) U * Tmax), dim3(256), 0, (hipStream_t) stream, x_dev, nframes_dev, U, Tmax, dim, op, tx, thresh, y_dev);
   });
 }
 
@@ -712,10 +705,9 @@ dsr_status dsr_sad_gg_run(dsr_sad_gg* g, int kind, const void* X1_dev, const voi
     if (!g->up) { g->dTab.upload(g->tab, st); g->up = true; }
     int TC = 4096 / g->F; TC = TC < 1 ? 1 : (TC > 16 ? 16 : TC);
     const size_t lds = (size_t) 2 * TC * g->F * sizeof(double);
-    hipLaunchKernelGGL(k_gg, dim3(U), dim3(256), lds, st, (const double2*) X1_dev, (const double2*) X2_dev, env1_dev, env2_dev, nframes_dev, Tmax, (int) g->fftLen, g->F,
+    launch(k_gg, dim3(U), dim3(256), lds, st, (const double2*) X1_dev, (const double2*) X2_dev, env1_dev, env2_dev, nframes_dev, Tmax, (int) g->fftLen, g->F,
                        envDim, (int) g->lowX, (int) g->highX, g->binN, kind, TC, g->dTab.p, 2.0, g->gBc, g->gNm, g->fixedThr, twiddle, threshold, beta, (double2*) rho_dev,
                        decision_dev, score_dev, threshold_dev);
-    DSR_HIP(hipGetLastError());
   });
 }
 

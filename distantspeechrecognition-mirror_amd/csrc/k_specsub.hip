@@ -10,7 +10,7 @@
 // by their dependent chain per frame (k_wiener's time does not move when the bins double; k_ss_train pays 0.65 us per frame and channel for the
 // read-modify-write of its estimates), k_ss_apply by the fp64 atan2/sincos/sqrt per channel and bin at 1.0-1.2 TB/s on the snapshots.
 // Built with -ffp-contract=off: the reference's expressions are evaluated as written.
-#include "common.h"
+#include "launch.h"
 #include <cmath>
 
 using namespace dsr;
@@ -209,8 +209,7 @@ static void ss_state_op(dsr_specsub* h, void* state_dev, int U, int what, void* 
   const int C = (int) h->alphas.size(); if (C == 0) return;
   h->sync_alphas();
   const size_t n = (size_t) U * C * ss_chan_doubles(h->F);
-  hipLaunchKernelGGL(k_ss_state_op, dim3(cdiv((long) n, 256)), dim3(256), 0, (hipStream_t) stream, (double*) state_dev, h->d_alphas.p, U * C, C, h->F, what);
-  DSR_HIP(hipGetLastError());
+  launch(k_ss_state_op, dim3(cdiv((long) n, 256)), dim3(256), 0, (hipStream_t) stream, (double*) state_dev, h->d_alphas.p, U * C, C, h->F, what);
 }
 dsr_status dsr_specsub_state_init(dsr_specsub* h, void* state_dev, int U, void* stream) { return guard([&] { ss_state_op(h, state_dev, U, 3, stream); }); }
 dsr_status dsr_specsub_clear_noise_samples(dsr_specsub* h, void* state_dev, int U, void* stream) { return guard([&] { ss_state_op(h, state_dev, U, 1, stream); }); }
@@ -249,11 +248,10 @@ dsr_status dsr_specsub_apply(dsr_specsub* h, const float* X_dev, const int32_t* 
     SsPar p{U, C, Tmax, h->F, h->M, out_dev ? outBins : h->F, outIsDouble, h->training, h->subtract, (double) h->ft, (double) h->floorV};
     if (out_dev && outBins == h->M) DSR_HIP(hipMemsetAsync(out_dev, 0, out_bytes(U, Tmax, outBins, outIsDouble), st));
     if (h->training) {
-      hipLaunchKernelGGL(k_ss_train, dim3(cdiv(h->F, 64), U), dim3(64), 0, st, (const float2*) X_dev, nframes_dev, h->d_alphas.p, (double*) state_dev, out_dev, p);
-      hipLaunchKernelGGL(k_ss_seen, dim3(cdiv(U * C, 64)), dim3(64), 0, st, nframes_dev, h->d_alphas.p, (double*) state_dev, p);
+      launch(k_ss_train, dim3(cdiv(h->F, 64), U), dim3(64), 0, st, (const float2*) X_dev, nframes_dev, h->d_alphas.p, (double*) state_dev, out_dev, p);
+      launch(k_ss_seen, dim3(cdiv(U * C, 64)), dim3(64), 0, st, nframes_dev, h->d_alphas.p, (double*) state_dev, p);
     } else
-      hipLaunchKernelGGL(k_ss_apply, dim3(cdiv((long) U * Tmax * h->F, 256)), dim3(256), 0, st, (const float2*) X_dev, nframes_dev, (const double*) state_dev, out_dev, p);
-    DSR_HIP(hipGetLastError());
+      launch(k_ss_apply, dim3(cdiv((long) U * Tmax * h->F, 256)), dim3(256), 0, st, (const float2*) X_dev, nframes_dev, (const double*) state_dev, out_dev, p);
   });
 }
 dsr_status dsr_specsub_state_read(const dsr_specsub* h, const void* state_dev, int U, int what, int u, int chan, double* host_out, size_t outDoubles)
@@ -339,8 +337,7 @@ dsr_status dsr_wiener_apply(dsr_wiener* h, const float* S_dev, const float* N_de
     hipStream_t st = (hipStream_t) stream;
     WnPar p{U, Tmax, h->F, h->M, outBins, outIsDouble, h->carry, h->update, (double) h->alpha, (double) h->floorV, (double) h->beta};
     if (outBins == h->M) DSR_HIP(hipMemsetAsync(out_dev, 0, out_bytes(U, Tmax, outBins, outIsDouble), st));
-    hipLaunchKernelGGL(k_wiener, dim3(cdiv(h->F, 64), U), dim3(64), 0, st, (const float2*) S_dev, (const float2*) N_dev, nframes_dev, (double*) state_dev, out_dev, p);
-    DSR_HIP(hipGetLastError());
+    launch(k_wiener, dim3(cdiv(h->F, 64), U), dim3(64), 0, st, (const float2*) S_dev, (const float2*) N_dev, nframes_dev, (double*) state_dev, out_dev, p);
   });
 }
 dsr_status dsr_wiener_state_read(const dsr_wiener* h, const void* state_dev, int U, int what, int u, double* host_out, size_t outDoubles)

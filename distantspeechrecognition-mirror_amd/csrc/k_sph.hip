@@ -30,6 +30,7 @@
 // The further kinds (SphericalHWNCBeamformer :1387-1478, SphericalGSCBeamformer :1483-1594, SphericalHWNCGSCBeamformer :1599-1713,
 // SphericalMOENBeamformer :1804-2099, SphericalSpatialDSBeamformer :2106-2270) are host weight designs below; all of them run on the beams kernels.
 // The MFMA's lane map: csrc/mfma64.h; the frame tiling (FB, bin_chunk) and the shared kernel parts: csrc/srp_common.h.
+#include "launch.h"
 #include "srp_common.h"
 #include "sph_math.h"
 #include "gsc_weights.h"
@@ -751,18 +752,16 @@ void launch_beams_valu(const dsr_sph& s, const float* X, const int* nf, int U, i
   int CC = (int) (BEAMS_LDS / ((size_t) NBT * F * sizeof(double2))); if (CC > s.C) CC = s.C;
   if (CC < 1) throw Error(DSR_E_DIMENSION, "%d beams x %d bins do not fit the kernel's %zu bytes of LDS", NBT, F, BEAMS_LDS);
   const size_t lds = (size_t) CC * NBT * F * sizeof(double2);
-  hipLaunchKernelGGL((k_sph_beams_valu<NBT, E>), dim3(cdiv((long) Tmax * F, 256 * E), U), dim3(256), lds, st, (const float2*) X, nf, s.dV.p, s.C, Tmax, F, CC, NB,
+  launch(k_sph_beams_valu<NBT, E>, dim3(cdiv((long) Tmax * F, 256 * E), U), dim3(256), lds, st, (const float2*) X, nf, s.dV.p, s.C, Tmax, F, CC, NB,
                      (float2*) Y);
-  DSR_HIP(hipGetLastError());
 }
 
 template <int BCT>
 void launch_beams_mfma(const dsr_sph& s, const float* X, const int* nf, int U, int Tmax, int NB, float* Y, hipStream_t st)
 {
   const size_t lds = (size_t) s.C * FB * bin_pitch(BCT) * sizeof(float2);
-  hipLaunchKernelGGL((k_sph_beams_mfma<BCT>), dim3((Tmax + FB - 1) / FB, U), dim3(256), lds, st, (const float2*) X, nf, s.dV.p, s.C, Tmax, s.M / 2 + 1, NB,
+  launch(k_sph_beams_mfma<BCT>, dim3((Tmax + FB - 1) / FB, U), dim3(256), lds, st, (const float2*) X, nf, s.dV.p, s.C, Tmax, s.M / 2 + 1, NB,
                      (s.C + 3) / 4, (float2*) Y);
-  DSR_HIP(hipGetLastError());
 }
 
 int valu_rows(int NB) { return NB <= 4 ? NB : NB <= 8 ? 8 : 16; }   // the VALU kernel's instantiations: 1..4 exact, above that zero-padded rows
@@ -889,9 +888,8 @@ void launch_fused(const dsr_sph& s, const float* X, const int* nf, int U, int Tm
   const int BC = bin_chunk(s.C), F = s.M / 2 + 1;
   const size_t lds = (size_t) s.C * FB * bin_pitch(BC) * sizeof(float2);
   dim3 grid((s.NT + TG - 1) / TG, (Tmax + FB - 1) / FB, U);
-  hipLaunchKernelGGL((k_sph_srp<TG, DT>), grid, dim3(256), lds, st, (const float2*) X, nf, s.dSp.p, s.dWp.p, s.C, Tmax, F, s.M / 2, s.fbinMin, s.fbinMax,
+  launch(k_sph_srp<TG, DT>, grid, dim3(256), lds, st, (const float2*) X, nf, s.dSp.p, s.dWp.p, s.C, Tmax, F, s.M / 2, s.fbinMin, s.fbinMax,
                      units(s), s.NT, s.KS, BC, rp, en, (float2*) Y);
-  DSR_HIP(hipGetLastError());
 }
 
 template <int DT>
@@ -1120,9 +1118,8 @@ dsr_status dsr_sph_apply(dsr_sph* s, const float* X_dev, const int32_t* nframes_
     }
     const int F = s->M / 2 + 1;
     if ((long) Tmax * F > 0x7fffffffL) throw Error(DSR_E_DIMENSION, "Tmax %d x %d bins", Tmax, F);
-    hipLaunchKernelGGL(k_sph_apply, dim3(cdiv((long) Tmax * F, 256), U), dim3(256), 0, st, (const float2*) X_dev, nframes_dev, s->dS.p, s->dLook.p,
+    launch(k_sph_apply, dim3(cdiv((long) Tmax * F, 256), U), dim3(256), 0, st, (const float2*) X_dev, nframes_dev, s->dS.p, s->dLook.p,
                        s->C, Tmax, F, s->dim, (float2*) Y_dev, (float2*) F_dev);
-    DSR_HIP(hipGetLastError());
   });
 }
 
@@ -1339,9 +1336,8 @@ dsr_status dsr_sph_srp(dsr_sph* s, const float* X_dev, const int32_t* nframes_de
       else launch_fused_tg<4>(*s, X_dev, nframes_dev, U, Tmax, rp, energy_dev, Y_dev, st);
     }
     const long nfT = (long) U * Tmax;
-    hipLaunchKernelGGL(k_sph_frame, dim3(cdiv(nfT, 4)), dim3(256), 0, st, rp, energy_dev, nframes_dev, U, Tmax, nU, s->nBest, s->threshold,
+    launch(k_sph_frame, dim3(cdiv(nfT, 4)), dim3(256), 0, st, rp, energy_dev, nframes_dev, U, Tmax, nU, s->nBest, s->threshold,
                        nbest_rp_dev, nbest_idx_dev, gated_dev);
-    DSR_HIP(hipGetLastError());
     doa_launch_acc(rp, energy_dev, nframes_dev, U, Tmax, nU, s->threshold, acc_dev, st);
   });
 }

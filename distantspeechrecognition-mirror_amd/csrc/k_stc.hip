@@ -24,7 +24,7 @@
 //   k_stc_apply    thread per (frame, output dimension): float(sum_j double(x_j) M[i][j]), j ascending, no bias; outDim <= Din rows.
 // The pair indexing and tile walk restate k_fsa_stats': k_fsa.hip and k_mllr.hip are left as they are, so their object code does not change.
 // This translation unit is compiled with -ffp-contract=off.
-#include "common.h"
+#include "launch.h"
 #include "stc.h"
 #include "mfma64.h"
 #include "gmm_dist.h"
@@ -291,9 +291,8 @@ void plan_items(XfBase& h, const float* xScore, long N, const int* frame, const 
   h.d_gsel.reserve((size_t) M); h.d_score.reserve((size_t) M);
   {
     Timer tm(h.timing, st, &h.ms[0]);
-    hipLaunchKernelGGL(k_stc_nearest, dim3(cdiv(M, 256)), dim3(256), 0, st, xScore, h.D, m.Dp, m.d_off.p, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, m.d_scale.p,
+    launch(k_stc_nearest, dim3(cdiv(M, 256)), dim3(256), 0, st, xScore, h.D, m.Dp, m.d_off.p, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, m.d_scale.p,
                        h.d_frame.p, h.d_dist.p, M, h.d_gsel.p, h.d_score.p);
-    DSR_HIP(hipGetLastError());
     tm.stop();
   }
   p.gsel.resize((size_t) M); p.score.resize((size_t) M);
@@ -325,10 +324,9 @@ void stc_accumulate(StcHandle& h, const float* xScore, const float* xSrc, long N
   if (h.cascade && h.aDirty) { h.d_Aall.upload(h.A, st); h.aDirty = false; }
   {
     Timer tm(h.timing, st, &h.ms[1]);
-    hipLaunchKernelGGL(k_stc_stats, dim3(p.nCh), dim3(256), 0, st, D, h.NCp, h.PZ, xSrc, h.cascade ? h.d_Aall.p : (const double*) nullptr, h.d_mean.p, h.d_ivar.p,
+    launch(k_stc_stats, dim3(p.nCh), dim3(256), 0, st, D, h.NCp, h.PZ, xSrc, h.cascade ? h.d_Aall.p : (const double*) nullptr, h.d_mean.p, h.d_ivar.p,
                        h.d_frame.p, h.d_fac.p, h.d_gsel.p, h.d_chunk.p, h.d_pq.p, h.d_part.p);
-    hipLaunchKernelGGL(k_stc_reduce, dim3(cdiv((long) sz, 256), p.nSlot), dim3(256), 0, st, (long) sz, 0, h.d_accChunk.p, h.d_part.p, h.d_stats.p);
-    DSR_HIP(hipGetLastError());
+    launch(k_stc_reduce, dim3(cdiv((long) sz, 256), p.nSlot), dim3(256), 0, st, (long) sz, 0, h.d_accChunk.p, h.d_part.p, h.d_stats.p);
     tm.stop();
   }
   std::vector<double> stats((size_t) p.nSlot * sz);
@@ -375,9 +373,8 @@ void lda_accumulate(LdaHandle& h, const float* xScore, const float* xSrc, long N
   h.d_part.reserve((size_t) p.nCh * sz); h.d_stats.reserve((size_t) p.nSlot * sz);
   {
     Timer tm(h.timing, st, &h.ms[1]);
-    hipLaunchKernelGGL(k_lda_stats, dim3(p.nCh), dim3(256), 0, st, D, xSrc, h.d_mean.p, h.d_mu0.p, h.d_frame.p, h.d_fac.p, h.d_gsel.p, h.d_chunk.p, h.d_part.p);
-    hipLaunchKernelGGL(k_stc_reduce, dim3(cdiv((long) sz, 256), p.nSlot), dim3(256), 0, st, (long) sz, D, h.d_accChunk.p, h.d_part.p, h.d_stats.p);
-    DSR_HIP(hipGetLastError());
+    launch(k_lda_stats, dim3(p.nCh), dim3(256), 0, st, D, xSrc, h.d_mean.p, h.d_mu0.p, h.d_frame.p, h.d_fac.p, h.d_gsel.p, h.d_chunk.p, h.d_part.p);
+    launch(k_stc_reduce, dim3(cdiv((long) sz, 256), p.nSlot), dim3(256), 0, st, (long) sz, D, h.d_accChunk.p, h.d_part.p, h.d_stats.p);
     tm.stop();
   }
   std::vector<double> stats((size_t) p.nSlot * sz);
@@ -415,7 +412,6 @@ void stc_estimate(StcHandle& h, const int* estX, int n, double minE, double mult
   std::vector<double> G((size_t) n * ss), E(n, minE), ev((size_t) n * D * 2); std::vector<int> flag(n, 0), done(n, 0);
   h.d_Ginv.reserve((size_t) n * ss); h.d_ev.reserve(ev.size()); h.d_flag.reserve((size_t) n);
   const size_t ldsE = ((size_t) 2 * D * D + D + ((D + 1) & ~1) + 2 * kEigThreads) * sizeof(double);
-  DSR_HIP(hipFuncSetAttribute((const void*) k_stc_eig, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsE));
   {
     // makePosDef (eA:2689-2711): E doubles until every sumOsq[d] + E regSq[d] is positive definite.  An estimator that is not and whose regSq is
     // zero, or that is still not after 64 doublings, can never be (the reference would not return): it is flagged.
@@ -430,8 +426,7 @@ void stc_estimate(StcHandle& h, const int* estX, int n, double minE, double mult
       DSR_HIP(hipMemsetAsync(h.d_flag.p, 0, (size_t) n * sizeof(int), st));
       {
         float ms = 0.0f; Timer tm(h.timing, st, &ms);
-        hipLaunchKernelGGL(k_stc_eig, dim3(n * D), dim3(kEigThreads), ldsE, st, D, h.d_G.p, h.d_Ginv.p, h.d_ev.p, h.d_flag.p);
-        DSR_HIP(hipGetLastError());
+        launch(k_stc_eig, dim3(n * D), dim3(kEigThreads), ldsE, st, D, h.d_G.p, h.d_Ginv.p, h.d_ev.p, h.d_flag.p);
         tm.stop(); h.ms[2] += ms;
       }
       std::vector<int> f(n);
@@ -470,8 +465,7 @@ void stc_estimate(StcHandle& h, const int* estX, int n, double minE, double mult
     DSR_HIP(hipMemsetAsync(h.d_flag.p, 0, (size_t) n * sizeof(int), st));
     {
       float ms = 0.0f; Timer tm(h.timing, st, &ms);
-      hipLaunchKernelGGL(k_stc_eig, dim3(n * D), dim3(kEigThreads), ldsE, st, D, h.d_G.p, h.d_Ginv.p, h.d_ev.p, h.d_flag.p);
-      DSR_HIP(hipGetLastError());
+      launch(k_stc_eig, dim3(n * D), dim3(kEigThreads), ldsE, st, D, h.d_G.p, h.d_Ginv.p, h.d_ev.p, h.d_flag.p);
       tm.stop(); h.ms[2] += ms;
     }
     DSR_HIP(hipMemcpyAsync(ev.data(), h.d_ev.p, ev.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -486,10 +480,8 @@ void stc_estimate(StcHandle& h, const int* estX, int n, double minE, double mult
   h.d_flag.upload(flag, st);
   {
     const size_t lds = StcWork::doubles(D, kRowThreads) * sizeof(double) + (size_t) D * sizeof(int);
-    DSR_HIP(hipFuncSetAttribute((const void*) k_stc_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
     Timer tm(h.timing, st, &h.ms[3]);
-    hipLaunchKernelGGL(k_stc_rows, dim3(n), dim3(kRowThreads), lds, st, D, kStcMaxItns, h.d_Ginv.p, h.d_gamma.p, h.d_A.p, h.d_Ai.p, h.d_flag.p);
-    DSR_HIP(hipGetLastError());
+    launch(k_stc_rows, dim3(n), dim3(kRowThreads), lds, st, D, kStcMaxItns, h.d_Ginv.p, h.d_gamma.p, h.d_A.p, h.d_Ai.p, h.d_flag.p);
     tm.stop();
   }
   std::vector<double> Anew((size_t) n * ms), Ainew((size_t) n * ms);
@@ -545,10 +537,8 @@ void lda_estimate(LdaHandle& h, const int* estX, int n, hipStream_t st)
   DSR_HIP(hipMemsetAsync(h.d_flag.p, 0, (size_t) n * sizeof(int), st));
   {
     const size_t lds = ((size_t) 3 * D * D + 2 * D + ((D + 1) & ~1) + 2 * kRowThreads) * sizeof(double) + (size_t) D * sizeof(int);
-    DSR_HIP(hipFuncSetAttribute((const void*) k_lda_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
     Timer tm(h.timing, st, &h.ms[2]);
-    hipLaunchKernelGGL(k_lda_solve, dim3(n), dim3(kRowThreads), lds, st, D, h.d_W.p, h.d_B.p, h.d_L.p, h.d_ev.p, h.d_flag.p);
-    DSR_HIP(hipGetLastError());
+    launch(k_lda_solve, dim3(n), dim3(kRowThreads), lds, st, D, h.d_W.p, h.d_B.p, h.d_L.p, h.d_ev.p, h.d_flag.p);
     tm.stop();
   }
   std::vector<double> L((size_t) n * ms), ev((size_t) n * 2 * D); std::vector<int> flag(n);
@@ -575,8 +565,7 @@ static void apply_matrix(XfBase& h, const double* M, int Din, int outDim, const 
   if (!x || !out) throw Error(DSR_E_PARAMETER, "null argument");
   if ((long) N * outDim > 0x7fffffffL * 256L) throw Error(DSR_E_DIMENSION, "%ld frames in one call", N);
   Timer tm(h.timing, st, &h.ms[4]);
-  hipLaunchKernelGGL(k_stc_apply, dim3(cdiv(N * outDim, 256)), dim3(256), 0, st, Din, outDim, N, x, M, out);
-  DSR_HIP(hipGetLastError());
+  launch(k_stc_apply, dim3(cdiv(N * outDim, 256)), dim3(256), 0, st, Din, outDim, N, x, M, out);
   tm.stop();
 }
 

@@ -16,6 +16,7 @@
 // (kEndBit) stands for its epsilon path into the final state, an expansion record for its emitting arc and the epsilon path behind it --, places them with a
 // prefix sum (arcsOut is in time order, cut at maxPath), counts the arcs with an output symbol, and writes the word sequence of the arc list with a second
 // prefix sum.  Utterances whose head is empty (no best token, or a failed decode) are left as k_viterbi wrote them.
+#include "launch.h"
 #include "viterbi.h"
 
 namespace dsr {
@@ -106,8 +107,7 @@ __global__ __launch_bounds__(kTraceThreads) void k_traceback(const TraceArgs A)
 void traceback_launch(const TraceArgs& A, hipStream_t st)
 {
   if (A.U <= 0) return;
-  hipLaunchKernelGGL(k_traceback, dim3(A.U), dim3(kTraceThreads), 0, st, A);
-  DSR_HIP(hipGetLastError());
+  launch(k_traceback, dim3(A.U), dim3(kTraceThreads), 0, st, A);
 }
 
 }  // namespace dsr

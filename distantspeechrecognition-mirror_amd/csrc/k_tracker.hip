@@ -18,7 +18,9 @@
 //               and a step costs one barrier (the pivot row's owner computes both rotations and A11^-1 r's entry and broadcasts them).
 //               The rotation order and every operand are the reference's.
 //   k_pws_apply PlaneWaveSimulator::next (:1474-1488) element-wise: coefficient x source spectrum, optionally the conjugate mirror.
+#include "launch.h"
 #include "sph_math.h"
+#include "dev_math.h"
 #include <algorithm>
 
 using namespace dsr;
@@ -151,9 +153,7 @@ struct TrkP {
   const double2* bn; const double2* sc; const double* norm; const double* absbn; const double* Vt;
 };
 
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ double2 cmulc(double2 a, double2 b) { return make_double2(a.x * b.x + a.y * b.y, a.x * b.y - a.y * b.x); }   // conj(a) b
 
 // the sum of every thread's v in a fixed tree (the same for every launch shape); all threads get it
 __device__ double block_sum(double v, double* red)
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(NT) void k_trk_run(TrkP p, const float2* __restrict
       if (p.spatial) { const float2 x = X[(((size_t) u * CHAN + l) * p.Tmax + t) * F + f]; v = make_double2(x.x, x.y); }
       else {
         v = make_double2(0, 0);
-        for (int s = 0; s < CHAN; s++) { const float2 x = X[(((size_t) u * CHAN + s) * p.Tmax + t) * F + f]; v = cadd(v, cmulc(p.sc[l * CHAN + s], make_double2(x.x, x.y))); }
+        for (int s = 0; s < CHAN; s++) { const float2 x = X[(((size_t) u * CHAN + s) * p.Tmax + t) * F + f]; v = cadd(v, conj_mul(p.sc[l * CHAN + s], make_double2(x.x, x.y))); }
       }
       Vobs[i] = v;
     }
@@ -287,8 +287,8 @@ __global__ __launch_bounds__(NT) void k_trk_run(TrkP p, const float2* __restrict
         double2 eta = make_double2(0, 0), dt = eta, dp = eta; double delta = 0.0;
         for (int l = 0; l < L; l++) {
           const double2 g = G[(size_t) f * L + l], v = Vobs[(size_t) f * L + l];
-          eta = cadd(eta, cmulc(g, v)); delta += g.x * g.x + g.y * g.y;
-          if (!p.spatial) { dt = cadd(dt, cmulc(G[(size_t) F * L + (size_t) f * L + l], v)); dp = cadd(dp, cmulc(G[2 * (size_t) F * L + (size_t) f * L + l], v)); }
+          eta = cadd(eta, conj_mul(g, v)); delta += g.x * g.x + g.y * g.y;
+          if (!p.spatial) { dt = cadd(dt, conj_mul(G[(size_t) F * L + (size_t) f * L + l], v)); dp = cadd(dp, conj_mul(G[2 * (size_t) F * L + (size_t) f * L + l], v)); }
         }
         const double2 B = make_double2(eta.x / delta, eta.y / delta);
         Bk[f] = B; absB[f] = hypot(B.x, B.y);
@@ -559,8 +559,7 @@ dsr_status dsr_trk_init_state(dsr_trk* s, double* state_dev, int U, int position
   return guard([&] {
     if (!s || !state_dev || U <= 0) throw Error(DSR_E_ARG, "null argument or U <= 0");
     require_device();
-    hipLaunchKernelGGL(k_trk_init, dim3(cdiv(U, NT)), dim3(NT), 0, (hipStream_t) stream, state_dev, U, s->th0, s->ph0, std::sqrt(std::sqrt(s->s2init)), positionOnly);
-    DSR_HIP(hipGetLastError());
+    launch(k_trk_init, dim3(cdiv(U, NT)), dim3(NT), 0, (hipStream_t) stream, state_dev, U, s->th0, s->ph0, std::sqrt(std::sqrt(s->s2init)), positionOnly);
   });
 }
 
@@ -630,9 +629,7 @@ dsr_status dsr_trk_run(dsr_trk* s, const float* X_dev, const int32_t* nframes_de
     p.spatial = s->spatial; p.orderN = s->orderN; p.modesN = s->modesN; p.F = s->F; p.L = s->L; p.K = s->K; p.N = s->N; p.maxLocalN = s->maxLocalN;
     p.Tmax = Tmax; p.hasV = s->V.empty() ? 0 : 1; p.su = std::sqrt(s->s2u); p.sv = std::sqrt(s->s2v);
     p.bn = s->dBn.p; p.sc = s->dSc.p; p.norm = s->dNorm.p; p.absbn = s->dAbs.p; p.Vt = s->dVt.p;
-    if (s->lds > 64 * 1024) DSR_HIP(hipFuncSetAttribute((const void*) k_trk_run, hipFuncAttributeMaxDynamicSharedMemorySize, (int) s->lds));
-    hipLaunchKernelGGL(k_trk_run, dim3(U), dim3(NT), s->lds, st, p, (const float2*) X_dev, nframes_dev, state_dev, ws.p, wsStride, pos_dev, pos64_dev, info_dev);
-    DSR_HIP(hipGetLastError());
+    launch(k_trk_run, dim3(U), dim3(NT), s->lds, st, p, (const float2*) X_dev, nframes_dev, state_dev, ws.p, wsStride, pos_dev, pos64_dev, info_dev);
   });
 }
 
@@ -666,9 +663,8 @@ dsr_status dsr_pws_apply(const double* coef_dev, int chanN, const float* src_dev
     require_device();
     const size_t total = (size_t) U * chanN * Tmax * (fftLen / 2 + 1);
     const int blocks = (int) std::min<size_t>((total + NT - 1) / NT, 65535);
-    hipLaunchKernelGGL(k_pws_apply, dim3(blocks), dim3(NT), 0, (hipStream_t) stream, (const double2*) coef_dev, chanN, (const float2*) src_dev, nframes_dev, U, Tmax,
+    launch(k_pws_apply, dim3(blocks), dim3(NT), 0, (hipStream_t) stream, (const double2*) coef_dev, chanN, (const float2*) src_dev, nframes_dev, U, Tmax,
                        fftLen, full, (float2*) out_dev);
-    DSR_HIP(hipGetLastError());
   });
 }
 

@@ -14,7 +14,7 @@
 //   k_train_reduce  workgroup per codebook: the chunk partials are summed in chunk order and added to the accumulator rows, unless the flag
 //                   is set.  No floating-point atomics anywhere: the same call twice gives the same bits.
 // This translation unit is compiled with -ffp-contract=off.
-#include "common.h"
+#include "launch.h"
 #include "train.h"
 #include "lattice.h"
 #include "mfma64.h"
@@ -178,14 +178,13 @@ void train_accumulate(TrainAccu& t, const float* x, long N, const int* frame, co
   DSR_HIP(hipMemsetAsync(t.d_flag.p, 0, sizeof(int), st));
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   if (t.timing) { for (int i = 0; i < 3; i++) DSR_HIP(hipEventCreate(&ev[i])); DSR_HIP(hipEventRecord(ev[0], st)); }
-  hipLaunchKernelGGL(k_train_post, dim3(cdiv(M, 256)), dim3(256), 0, st, x, m.D, m.Dp, m.d_off.p, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, m.d_scale.p,
+  launch(k_train_post, dim3(cdiv(M, 256)), dim3(256), 0, st, x, m.D, m.Dp, m.d_off.p, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, m.d_scale.p,
                      t.d_frame.p, t.d_dist.p, t.d_factor.p, t.d_start.p, t.d_gbase.p, M, t.d_gamma.p, t.d_score.p, t.d_flag.p);
   if (t.timing) DSR_HIP(hipEventRecord(ev[1], st));
-  hipLaunchKernelGGL(k_train_acc, dim3(nChunks), dim3(256), 0, st, x, m.D, m.d_off.p, t.d_frame.p, t.d_factor.p, t.d_start.p, t.d_gbase.p, t.d_chunk.p,
+  launch(k_train_acc, dim3(nChunks), dim3(256), 0, st, x, m.D, m.d_off.p, t.d_frame.p, t.d_factor.p, t.d_start.p, t.d_gbase.p, t.d_chunk.p,
                      t.d_gamma.p, t.d_part.p);
-  hipLaunchKernelGGL(k_train_reduce, dim3(K), dim3(256), 0, st, m.D, m.d_off.p, t.d_cstart.p, t.d_pbase.p, t.d_part.p, t.d_flag.p, t.d_acc.p);
+  launch(k_train_reduce, dim3(K), dim3(256), 0, st, m.D, m.d_off.p, t.d_cstart.p, t.d_pbase.p, t.d_part.p, t.d_flag.p, t.d_acc.p);
   if (t.timing) DSR_HIP(hipEventRecord(ev[2], st));
-  DSR_HIP(hipGetLastError());
   int flag = 0; std::vector<float> ss(score ? M : 0);
   DSR_HIP(hipMemcpyAsync(&flag, t.d_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
   if (score) DSR_HIP(hipMemcpyAsync(ss.data(), t.d_score.p, M * sizeof(float), hipMemcpyDeviceToHost, st));

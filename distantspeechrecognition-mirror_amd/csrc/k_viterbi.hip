@@ -22,6 +22,7 @@
 // One workgroup (1024 threads) owns one utterance at a time and loops over its frames; workgroups pull
 // utterances from a queue.  All arithmetic that decides a comparison is done with explicit
 // non-contracted IEEE operations (this file is compiled with -ffp-contract=off).
+#include "launch.h"
 #include "viterbi.h"
 #include <algorithm>
 #include <cmath>
@@ -1406,7 +1407,7 @@ extern "C" __global__ void k_xcc_probe(int* out) { if (threadIdx.x == 0) out[blo
 
 namespace dsr {
 
-void xcc_probe_launch(int* out64, hipStream_t st) { hipLaunchKernelGGL(k_xcc_probe, dim3(64), dim3(64), 0, st, out64); }
+void xcc_probe_launch(int* out64, hipStream_t st) { launch(k_xcc_probe, dim3(64), dim3(64), 0, st, out64); }
 
 // modes -> instantiation (viterbi.h: bit 0 ticks, bit 1 lattice / topN / dump, bit 2 narrow table)
 typedef void (*VitKernel)(const VitArgs);
@@ -1420,9 +1421,7 @@ size_t viterbi_static_lds(int modes)
 void viterbi_launch(int modes, const VitArgs& A, int slots, size_t ldsBytes, hipStream_t st)
 {
   const VitKernel k = kVitKernels[modes & 7];
-  DSR_HIP(hipFuncSetAttribute((const void*) k, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes));
-  hipLaunchKernelGGL(k, dim3(slots), dim3(kThreads), ldsBytes, st, A);
-  DSR_HIP(hipGetLastError());
+  launch(k, dim3(slots), dim3(kThreads), ldsBytes, st, A);
 }
 
 }  // namespace dsr

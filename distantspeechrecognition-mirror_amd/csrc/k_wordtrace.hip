@@ -16,7 +16,7 @@
 // by two atomic minima.  Feature parity, not speed: the reference ships this class without a driver.  generateLattice = true is refused by the caller
 // (undefined in the reference on any graph whose first arcs carry no output symbol: _placeOnList dereferences a null word trace, :239).
 // Compiled with -ffp-contract=off.
-#include "common.h"
+#include "launch.h"
 #include "wfst_graph.h"
 #include "wordtrace.h"
 #include <cmath>
@@ -239,8 +239,7 @@ __global__ __launch_bounds__(kWT) void k_wordtrace(const WtArgs A)
 
 void wordtrace_launch(const WtArgs& A, int slots, hipStream_t st)
 {
-  hipLaunchKernelGGL(k_wordtrace, dim3(slots), dim3(kWT), 0, st, A);
-  DSR_HIP(hipGetLastError());
+  launch(k_wordtrace, dim3(slots), dim3(kWT), 0, st, A);
 }
 
 }  // namespace dsr

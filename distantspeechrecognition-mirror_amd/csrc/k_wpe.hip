@@ -10,7 +10,7 @@
 // are weighted with the reciprocal of theta_n (one division per frame instead of one per term); agreement with the oracle is
 // 1e-9 relative.  The filters start from zero for every utterance (the reference's reset() keeps them from the previous
 // one; nextSpeaker() zeroes them, :283-290).
-#include "common.h"
+#include "launch.h"
 #include <cmath>
 
 namespace dsr {
@@ -312,10 +312,8 @@ static dsr_status wpe_single_impl(const float* Y_dev, const int32_t* nframes_dev
     const int lowerBW = (bandWidth == 0.0) ? fftLen / 2 : (int) (unsigned) ((bandWidth / (sampleRate / 2.0)) * (fftLen / 2));
     const size_t lds = (size_t) Nmax * 24 + (size_t) (P * P + 2 * P) * 16;
     if (lds > 150 * 1024) throw Error(DSR_E_DIMENSION, "WPE: %d frames x %d taps do not fit the LDS working set", Nmax, P);
-    DSR_HIP(hipFuncSetAttribute((const void*) k_wpe, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    hipLaunchKernelGGL(k_wpe, dim3(F, U), dim3(256), lds, (hipStream_t) stream, (const float2*) Y_dev, nframes_dev, (float2*) out_dev, (double2*) gn_dev,
+    launch(k_wpe, dim3(F, U), dim3(256), lds, (hipStream_t) stream, (const float2*) Y_dev, nframes_dev, (float2*) out_dev, (double2*) gn_dev,
                        U, Nmax, F, fftLen, lowerN, P, iterationsN, pow(10.0, loadDb / 10.0), lowerBW, warm ? (const double2*) gn_dev : nullptr);
-    DSR_HIP(hipGetLastError());
   });
 }
 
@@ -358,8 +356,7 @@ static dsr_status wpe_multi_impl(const float* Y_dev, const int32_t* nframes_dev,
       if (PT > 1024) throw Error(DSR_E_DIMENSION, "WPE: %d channels x %d taps = %d stacked lags; the multi-channel WPE handles at most 1024", chanN, P, PT);
       float2* Yt = nullptr;
       DSR_HIP(hipMallocAsync((void**) &Yt, sizeof(float2) * (size_t) U * F * chanN * Nmax, st));
-      hipLaunchKernelGGL(k_wpe_series, dim3((F + 31) / 32, (Nmax + 31) / 32, U * chanN), dim3(256), 0, st, (const float2*) Y_dev, Yt, chanN, Nmax, F);
-      DSR_HIP(hipGetLastError());
+      launch(k_wpe_series, dim3((F + 31) / 32, (Nmax + 31) / 32, U * chanN), dim3(256), 0, st, (const float2*) Y_dev, Yt, chanN, Nmax, F);
       wpe_multi_tiled(Yt, nframes_dev, U, chanN, Nmax, fftLen, lowerN, P, iterationsN, pow(10.0, loadDb / 10.0), lowerBW, filterChan, (float2*) out_dev,
                       (double2*) gn_dev, warm, st);
       DSR_HIP(hipFreeAsync(Yt, st));
@@ -368,23 +365,19 @@ static dsr_status wpe_multi_impl(const float* Y_dev, const int32_t* nframes_dev,
     const bool yLds = ldsCore + ldsSeries <= ldsCap && !getenv("DSR_WPE_SERIES_MEM");
     if (yLds) {
       const size_t lds = ldsCore + ldsSeries;
-      DSR_HIP(hipFuncSetAttribute((const void*) k_wpe_multi<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-      hipLaunchKernelGGL(k_wpe_multi<true>, dim3(F, chanN, U), dim3(256), lds, st, (const float2*) Y_dev, (const float2*) nullptr, nframes_dev, (double2*) gn_dev,
+      launch(k_wpe_multi<true>, dim3(F, chanN, U), dim3(256), lds, st, (const float2*) Y_dev, (const float2*) nullptr, nframes_dev, (double2*) gn_dev,
                          U, chanN, Nmax, F, fftLen, lowerN, P, iterationsN, pow(10.0, loadDb / 10.0), lowerBW, gnIn);
     } else {
       float2* Yt = nullptr;                                          // stream-ordered scratch: lives from here to the end of the estimation kernel on this stream
       DSR_HIP(hipMallocAsync((void**) &Yt, sizeof(float2) * (size_t) U * F * chanN * Nmax, st));
-      hipLaunchKernelGGL(k_wpe_series, dim3((F + 31) / 32, (Nmax + 31) / 32, U * chanN), dim3(256), 0, st, (const float2*) Y_dev, Yt, chanN, Nmax, F);
-      DSR_HIP(hipFuncSetAttribute((const void*) k_wpe_multi<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsCore));
-      hipLaunchKernelGGL(k_wpe_multi<false>, dim3(F, chanN, U), dim3(256), ldsCore, st, (const float2*) Y_dev, (const float2*) Yt, nframes_dev, (double2*) gn_dev,
+      launch(k_wpe_series, dim3((F + 31) / 32, (Nmax + 31) / 32, U * chanN), dim3(256), 0, st, (const float2*) Y_dev, Yt, chanN, Nmax, F);
+      launch(k_wpe_multi<false>, dim3(F, chanN, U), dim3(256), ldsCore, st, (const float2*) Y_dev, (const float2*) Yt, nframes_dev, (double2*) gn_dev,
                          U, chanN, Nmax, F, fftLen, lowerN, P, iterationsN, pow(10.0, loadDb / 10.0), lowerBW, gnIn);
       DSR_HIP(hipFreeAsync(Yt, st));
     }
-    DSR_HIP(hipGetLastError());
     const long tot = (long) U * chanN * Nmax * F;
-    hipLaunchKernelGGL(k_wpe_multi_out, dim3((unsigned) ((tot + 255) / 256)), dim3(256), 0, st, (const float2*) Y_dev, nframes_dev, (const double2*) gn_dev,
+    launch(k_wpe_multi_out, dim3((unsigned) ((tot + 255) / 256)), dim3(256), 0, st, (const float2*) Y_dev, nframes_dev, (const double2*) gn_dev,
                        (float2*) out_dev, U, chanN, Nmax, F, fftLen, lowerN, P, lowerBW, filterChan);
-    DSR_HIP(hipGetLastError());
   });
 }
 

@@ -17,7 +17,7 @@
 // for its (utterance, channel, subband) and nothing else.
 //
 // The fp64 MFMA helpers and the instruction's lane map: csrc/mfma64.h.
-#include "common.h"
+#include "launch.h"
 #include "mfma64.h"
 #include <cmath>
 
@@ -326,20 +326,18 @@ void wpe_multi_tiled(const float2* Yt, const int32_t* nframes, int U, int C, int
     for (int it = 0; it < iterationsN; it++)
       for (int ub0 = 0; ub0 < UF; ub0 += nub) {
         const int n = UF - ub0 < nub ? UF - ub0 : nub;
-        hipLaunchKernelGGL(k_wt_resid<false>, dim3((Npad + 63) / 64, (C + 15) / 16, n), dim3(256), 0, st, Yt, nframes, (const double2*) gn, rth, (float2*) nullptr,
+        launch(k_wt_resid<false>, dim3((Npad + 63) / 64, (C + 15) / 16, n), dim3(256), 0, st, Yt, nframes, (const double2*) gn, rth, (float2*) nullptr,
                            ub0, C, Nmax, Npad, F, fftLen, lowerN, P, lowerBW, -1);
-        hipLaunchKernelGGL(k_wt_gram, dim3(T * (T + 1) / 2, (C + WT_CG - 1) / WT_CG, n), dim3(256), 0, st, Yt, nframes, (const double*) rth, Rws,
+        launch(k_wt_gram, dim3(T * (T + 1) / 2, (C + WT_CG - 1) / WT_CG, n), dim3(256), 0, st, Yt, nframes, (const double*) rth, Rws,
                            ub0, C, Nmax, Npad, F, fftLen, lowerN, P, lowerBW);
-        hipLaunchKernelGGL(k_wt_rvec, dim3((PT + 63) / 64, (C + 15) / 16, n), dim3(256), 0, st, Yt, nframes, (const double*) rth, rv,
+        launch(k_wt_rvec, dim3((PT + 63) / 64, (C + 15) / 16, n), dim3(256), 0, st, Yt, nframes, (const double*) rth, rv,
                            ub0, C, Nmax, Npad, F, fftLen, lowerN, P, lowerBW);
-        hipLaunchKernelGGL(k_wt_chol, dim3(C, n), dim3(256), 0, st, Rws, (const double2*) rv, gn, ub0, C, F, fftLen, P, lowerBW, loadFactor);
+        launch(k_wt_chol, dim3(C, n), dim3(256), 0, st, Rws, (const double2*) rv, gn, ub0, C, F, fftLen, P, lowerBW, loadFactor);
       }
-    DSR_HIP(hipGetLastError());
     DSR_HIP(hipFreeAsync(Rws, st));
   }
-  hipLaunchKernelGGL(k_wt_resid<true>, dim3((Nmax + 63) / 64, (C + 15) / 16, UF), dim3(256), 0, st, Yt, nframes, (const double2*) gn, (double*) nullptr, out,
+  launch(k_wt_resid<true>, dim3((Nmax + 63) / 64, (C + 15) / 16, UF), dim3(256), 0, st, Yt, nframes, (const double2*) gn, (double*) nullptr, out,
                      0, C, Nmax, Npad, F, fftLen, lowerN, P, lowerBW, filterChan);
-  DSR_HIP(hipGetLastError());
 }
 
 }  // namespace dsr

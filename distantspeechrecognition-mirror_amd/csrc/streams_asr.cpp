@@ -202,7 +202,6 @@ dsr_status dsr_lattice_gamma_probs_dist(dsr_lattice* L, dsr_distribset* d, doubl
       ok(dsr_gmm_score(d->gmm, reinterpret_cast<const float*>(d->feat->dev.p), (int64_t) T, d->mode, d->d_scores.p, nullptr, S0));
       DevBuf<int> dd, ds, de; DevBuf<double> dout; dd.upload(dist); ds.upload(start); de.upload(end); dout.reserve(link.size());
       op_link_ac(d->d_scores.p, K, dd.p, ds.p, de.p, (int) link.size(), dout.p, S0);
-      DSR_HIP(hipGetLastError());
       std::vector<double> sums(link.size());
       DSR_HIP(hipMemcpy(sums.data(), dout.p, sizeof(double) * link.size(), hipMemcpyDeviceToHost));
       for (size_t i = 0; i < link.size(); i++) {

@@ -260,6 +260,65 @@ dsr_status dsr_mk_path(int chanN, int Tsel, int path[2], int64_t lds[2]);
 dsr_status dsr_mk_force_streamed(dsr_mk*, int on);
 
 /* =====================================================================================
+ * 2a'. Maximum negentropy beamforming under a generalised Gaussian (GG) model, and the GG model's training
+ *     replaces MNSubbandBeamformerGGDc_pr / MNSubbandBeamformerGGDc_nrm (btk/lib/mnBeamforming.py:33-792) and CGGaussianD / MLE4CGGaussianD
+ *     (btk/lib/GGDcEst.py:24-293)
+ * Scope, refusals, frame selection, array shapes, the packed gradient's convention, the reduction order and the exit reasons (DSR_MK_EXIT_*) are
+ * those of section 2a; one source only (the reference allows two).  Every (utterance, bin) minimises, with the bin's shape f,
+ *   -[ (log sigma2 + 1 + log pi) - beta (NgConst + log(f Sf) / f - log Bc) ] + alpha |wa|^2,   sigma2 = mean |Y|^2, Sf = mean |Y|^(2f),
+ * by conjugate_pr.  The gradient's sums and divisor run over the frames with |Y| > 0 (:506-513).  normalizeWeight is the identity in both reference
+ * classes (the clipping is commented out, :515-528 and :693-706): _pr and _nrm differ in the default beta only (0.5, 1.0) and gamma has no effect.
+ * A problem without a selected frame, with all-zero outputs at the start or a starting cost that is not finite is DSR_MK_EXIT_SKIPPED.
+ * log, exp and pow on this path are the deterministic fp64 functions of csrc/det_math.h (tests/mn_np.py restates them bit for bit):
+ * at most 4 2^-53 relative for log, 4 (|f ln x| + 2) 2^-53 for pow.
+ * ===================================================================================== */
+typedef struct dsr_mn dsr_mn;
+dsr_status dsr_mn_create(int fftLen, int chanN, int NC, int nSource, int halfBandShift, dsr_mn** out);          /* mnBeamforming.py:34-71 */
+void       dsr_mn_destroy(dsr_mn*);
+dsr_status dsr_mn_set_fixed_weights_from_bf(dsr_mn*, const dsr_bf*);                                            /* calcFixedWeights :266-307 */
+dsr_status dsr_mn_set_fixed_weights(dsr_mn*, const double* wq, const double* B);                                /* setFixedWeights :236-264 */
+dsr_status dsr_mn_get_fixed_weights(const dsr_mn*, double* wq, double* B);                                      /* getWq, getB :227-231 */
+/* the GG model ggdL: shape [F] (host), each > 0 and finite (DSR_E_PARAMETER otherwise); the per-bin constants are fixConst's (GGDcEst.py:45-61) */
+dsr_status dsr_mn_set_ggd(dsr_mn*, const double* shape);
+dsr_status dsr_mn_get_constants(const dsr_mn*, double* Bc, double* NgConst, double* logBc);                     /* [F] each (host), any may be NULL */
+/* defaults of create: alpha 1e-2, beta 0.5, gamma -1 (:432; _nrm: beta 1.0, :610); MAXITNS 40, TOLERANCE 1e-3, STOPTOLERANCE 1e-2,
+   DIFFSTOPTOLERANCE 1e-5, STEPSIZE 0.2 (:537) */
+dsr_status dsr_mn_config(dsr_mn*, double alpha, double beta, double gamma);
+dsr_status dsr_mn_minimizer(dsr_mn*, int maxItns, double tolerance, double stopTolerance, double diffStopTolerance, double stepSize);
+/* as dsr_mk_eval / dsr_mk_estimate / dsr_mk_apply without carried statistics (fun_MN, dfun_MN :331-416; estimateActiveWeights :537-599) */
+dsr_status dsr_mn_eval(dsr_mn*, const float* X_dev, const int32_t* nframes_dev, int U, int Tmax, int sFrame, int eFrame, int R, int fbinX,
+                       const double* wa_dev, double* cost_dev, double* grad_dev, void* stream);
+dsr_status dsr_mn_estimate(dsr_mn*, const float* X_dev, const int32_t* nframes_dev, int U, int Tmax, int sFrame, int eFrame, int R, int fbinX,
+                           double* wa_dev, int32_t* info_dev, double* cost_dev, void* stream);
+dsr_status dsr_mn_apply(dsr_mn*, const float* X_dev, int U, int Tmax, const double* wa_dev, float* Y_dev, void* stream);
+dsr_status dsr_mn_force_streamed(dsr_mn*, int on);                                                              /* dsr_mk_path names the kernel */
+/* MLE4CGGaussianD.acc (GGDcEst.py:218-237) over a batch of one-channel subband samples X_dev [U][Tmax][F] complex64, nframes_dev (optional) [U],
+ * with the current model p [F], sa [F] (host, each > 0).  acc [5][F] fp64 (host) = acc_in (host, may be NULL) + acc1S, acc1P, acc2P, nSample,
+ * totalL.  Per sample, v2 = |X|^2: l = log v2; acc1S += exp(p l); la = l - log(Bc sa); tmp = exp(p la); acc1P += tmp la where v2 > 1e-22;
+ * acc2P += tmp; totalL += (LlConst - log sa) - tmp; v2 == 0 adds to nSample and totalL only.  Order: per (utterance, bin) 64 partial sums
+ * (partial q adds frames q, q + 64, ...) and a fixed binary tree, then acc_in and the utterances in increasing order: a call repeats bit for bit.
+ * Zero mean only.  Returns after the stream has finished. */
+dsr_status dsr_ggd_accumulate(const float* X_dev, const int32_t* nframes_dev, int U, int Tmax, int F, const double* p, const double* sa,
+                              const double* acc_in, double* acc, void* stream);
+/* fixConst (:45-61) for F shape parameters: B = Gamma(1/p)/Gamma(2/p), lNF, NgConst, LlConst; any output may be NULL.  Host. */
+dsr_status dsr_ggd_constants(const double* p, int F, double* Bc, double* lNF, double* NgConst, double* LlConst);
+/* update (:246-293) for F bins from acc [5][F]: the scaling parameter, the gradient step on p (step alpha / (1 + nItr)), both floors, the
+   convergence flag |newP - p| < thresh; sigmaOnly keeps p.  A bin without a sample keeps its parameters.  Host. */
+dsr_status dsr_ggd_update(const double* acc, int F, const double* p, const double* sa, int nItr, double alpha, double thresh, double floorV,
+                          double floorP, int sigmaOnly, double* newSa, double* newP, int32_t* converged);
+/* writeParam / readParam (:118-152): "sa p mean\nB lNF\n" with %e; out = sa, p, mean, B, lNF.  A mean that is not zero is DSR_E_PARAMETER. */
+dsr_status dsr_ggd_write_param(const char* path, double sa, double p, double mean);
+dsr_status dsr_ggd_read_param(const char* path, double out[5]);
+/* writeAccs (:176-189): ten lines.  readAccs (:191-216) cannot run in the reference (float() of a list); its evident intent is implemented:
+   a file whose nItr is not 1 is ignored (used = 0), otherwise its five statistics are added to acc. */
+dsr_status dsr_ggd_write_accs(const char* path, const double acc[5], double alpha, int nItr, double thresh, double floorV, double floorP);
+dsr_status dsr_ggd_read_accs(const char* path, double acc[5], int* used);
+/* the deterministic fp64 log, exp and digamma of csrc/det_math.h on host arrays (test hooks; need no device) */
+dsr_status dsr_det_log(const double* x, double* y, int n);
+dsr_status dsr_det_exp(const double* x, double* y, int n);
+dsr_status dsr_det_psi(const double* x, double* y, int n);
+
+/* =====================================================================================
  * 2b. Steered-response-power direction of arrival for a linear array
  *     replaces DOAEstimatorSRPDSBLA (btk/beamformer/beamformer.h:462-560, beamformer.i:479-513,
  *     beamformer.cc:2920-3283)

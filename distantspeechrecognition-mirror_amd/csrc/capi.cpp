@@ -21,7 +21,7 @@ void require_device()
 
 using namespace dsr;
 
-// the plan objects are defined in their kernels' translation units
+// the plan objects are defined with their units: dsr_bf in beamformer.h, dsr_decoder in decoder.cpp, the others in their kernels' translation units
 struct dsr_fb; struct dsr_bf; struct dsr_mfcc; struct dsr_gmm; struct dsr_decoder;
 
 struct dsr_pipe {

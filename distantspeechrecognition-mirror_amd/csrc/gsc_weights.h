@@ -1,5 +1,5 @@
 // csrc/gsc_weights.h -- the host-side generalized-sidelobe-canceller weight pieces of beamformerWeights that more than one file needs
-// (k_beamform.hip, k_mmi.hip, k_sph.hip): the blocking matrix of a quiescent vector (_calcBlockingMatrix, beamformer.cc:398-479, any NC) and
+// (beamformer.cpp, mmi.cpp, sph.cpp): the blocking matrix of a quiescent vector (_calcBlockingMatrix, beamformer.cc:398-479, any NC) and
 // the sidelobe canceller's wl = B wa (calcSidelobeCancellerP_f / U_f, :761-799).  GSL's complex product, so that values agree with the
 // reference to rounding.
 #pragma once

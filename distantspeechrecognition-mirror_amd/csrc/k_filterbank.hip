@@ -14,6 +14,7 @@
 //              out_t[D-1-d] = sum_{i<R, t-R+1+i>=0} sum_q g[(M-1-k)+qM] v_{t-R+1+i+pd-Rq}[k],  k = d+iD
 #include "launch.h"
 #include "dev_math.h"
+#include "beamformer.h"
 #include <cmath>
 
 namespace dsr {
@@ -1136,7 +1137,6 @@ dsr_status dsr_fb_analysis(const dsr_fb* p, const float* x, const int32_t* nsamp
     fb_analysis(*p, k, x, nsamp, U, C, (long) sampStride, Tmax, X, (hipStream_t) stream);
   });
 }
-namespace dsr { const float2* bf_fixed_weights_dev(dsr_bf* s); }
 int dsr_fb_analysis_beamform_supported(const dsr_fb* p, const dsr_bf* bf)
 {
   if (!p || !bf || p->synthesis || getenv("DSR_FB_GENERIC") || getenv("DSR_FB_WAVE") || getenv("DSR_FB_NOFUSE")) return 0;

@@ -10,6 +10,7 @@
 // compiled with -ffp-contract=off); the snapshots and the beamformer output are the pipe's complex64 arrays.
 #include "launch.h"
 #include "dev_math.h"
+#include "beamformer.h"
 #include "svd_linpack.h"
 #include <complex>
 #include <cmath>
@@ -585,7 +586,6 @@ dsr_status dsr_zelinski_set_manifold(dsr_zelinski* p, int fbinX, const double* v
     memcpy(&p->h_wq[(size_t) fbinX * p->C * 2], vec, sizeof(double) * 2 * p->C); p->dirty = true;
   });
 }
-namespace dsr { const float2* bf_fixed_weights_dev(dsr_bf* s); bool bf_has_fixed_weights(const dsr_bf* s); }
 
 // The dispatch of the post-filters, in one place: the launches below switch on it and dsr_zelinski_path reports it.  PfReg: the channel counts
 // k_zelinski_reg and k_mccowan are instantiated for with the densities in registers.  kind 0 Zelinski, 1 McCowan, 2 Lefkimmiatis; behindFixedBf: the call

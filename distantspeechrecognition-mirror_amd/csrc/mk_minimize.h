@@ -21,12 +21,10 @@
 #pragma once
 #include "launch.h"
 #include "gsc_weights.h"
+#include "beamformer.h"
 #include <complex>
 #include <cmath>
 #include <vector>
-
-// k_beamform.hip defines it inside its extern "C" block, so it has C linkage
-extern "C" { namespace dsr { bool bf_gsc_fixed_weights(const dsr_bf* s, int* M, int* C, int* halfBandShift, const std::complex<double>** wq, const std::complex<double>** B); } }
 
 namespace dsr {
 typedef std::complex<double> zc;

@@ -1,6 +1,6 @@
-// csrc/sph_math.h -- what the spherical-array files share (k_sph.hip, k_tracker.hip): the EigenMike's capsule table, the GSL-shaped complex
+// csrc/sph_math.h -- what the spherical-array files share (sph.cpp, k_tracker.hip): the EigenMike's capsule table, the GSL-shaped complex
 // arithmetic that keeps the reference's order of operations, the normalised Legendre recurrence (host and device) and the spherical Bessel
-// functions of k_sph.hip.
+// functions of sph.cpp.
 #pragma once
 #include "common.h"
 #include <cmath>
@@ -74,7 +74,7 @@ DSR_HD inline double legendre_plm(int l, int m, double x)
   return p;
 }
 
-double sph_jl(int l, double x);                              // k_sph.hip
+double sph_jl(int l, double x);                              // sph.cpp
 double sph_yl(int l, double x);
 
 }  // namespace dsr

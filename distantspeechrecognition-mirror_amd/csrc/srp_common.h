@@ -2,7 +2,7 @@
 // The workgroup tiling and the parts of the two SRP kernels that are the same (snapshot staging, the staged-chunk frame energy of calcEnergy,
 // beamformer.cc:3043-3074, the response-power accumulation and its epilogue), the N-best insertion of DOAEstimatorSRP*::next and
 // _getNBestHypothesesFromACCRP (also the stream operators', csrc/streams_beamformer.cpp), the frequency-range check, the linear estimator's handle and its
-// launchers, which the spherical estimator's folded path drives with a table of its own.  Kernel files that include this are built with
+// launchers, which the spherical estimator's folded path (sph.cpp) drives with a table of its own.  Kernel files that include this are built with
 // -ffp-contract=off: the energy must stay the reference's float accumulation bit for bit.
 #pragma once
 #include "common.h"

@@ -1,5 +1,5 @@
 """Inputs shared by tests/test_rls_cases_cpu.py and tests/test_gpu_rls_kernels.py: one case for every cell the dispatch of SubbandGSCRLS
-(gsc_rls_apply, csrc/k_beamform.hip) can select, on both sides of its two gates, and the ragged batch each runs on.
+(bf_launch_rls, csrc/k_beamform.hip) can select, on both sides of its two gates, and the ragged batch each runs on.
 
 A case is a dict:
   name     its id, after the cell: where the state lives, the channel count

@@ -1,7 +1,8 @@
 """The host half of the kernel units without a device.  csrc/value_list.h: ints<...> states the values a template is instantiated for once,
 has_value asks whether a run-time value is one of them, for_value hands the matching one to a callback as a compile-time constant (a small main,
 plain g++ -std=c++17, prints what the callback saw).  csrc/launch.h: the only file of csrc/ that launches a kernel or raises a kernel's dynamic-LDS
-limit, and no macro wraps it."""
+limit, and no macro wraps it.  The beamformer family's kernel units (k_sph, k_beamform, k_mmi) hold no C entries, and no file restates another unit's
+declaration by hand."""
 import glob
 import os
 import re
@@ -81,6 +82,17 @@ def test_kernels_are_launched_in_launch_h_only():
     kernel_units = [f for f in _sources() if os.path.basename(f).startswith("k_") and f.endswith(".hip")]
     assert len(kernel_units) == 32
     assert [os.path.basename(f) for f in kernel_units if not re.search(r"\blaunch(_n)?\(", open(f).read())] == []
+
+
+def test_beamformer_kernel_units_hold_no_entries_and_no_unit_restates_a_declaration():
+    for name in ("k_sph.hip", "k_beamform.hip", "k_mmi.hip"):
+        text = open(os.path.join(CSRC, name)).read()
+        assert [s for s in ('extern "C"', "dsr_status") if s in text] == [], name
+    restated = re.compile(r'^namespace dsr \{ .*\); *\}|extern "C" \{ namespace dsr \{')   # a one-line declaration of another unit's function
+    bad = []
+    for f in _sources():
+        bad += [(os.path.basename(f), n + 1) for n, l in enumerate(open(f).read().split("\n")) if restated.search(l)]
+    assert bad == []
 
 
 def test_no_macro_wraps_launch():

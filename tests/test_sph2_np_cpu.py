@@ -1,4 +1,4 @@
-"""The further spherical-array beamformers' host math (dsr_sph kinds HWNC, GSC, HWNCGSC, SPATIALDS, MOEN; csrc/k_sph.hip) without a GPU: every
+"""The further spherical-array beamformers' host math (dsr_sph kinds HWNC, GSC, HWNCGSC, SPATIALDS, MOEN; csrc/sph.cpp) without a GPU: every
 host table through the C-ABI against the restatement tests/sph2_np.py to 1e-12 of the table row's largest entry, properties that do not pass
 through the restatement, the error paths and the Python constructors' defaults (read from beamformer.i:651, :680, :709, :764, :997)."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""The spherical-array host math (dsr_sph, csrc/k_sph.hip) without a GPU: the restatement tests/sph_np.py against scipy where scipy is
+"""The spherical-array host math (dsr_sph, csrc/sph.cpp) without a GPU: the restatement tests/sph_np.py against scipy where scipy is
 importable, every host table read through the C-ABI against the restatement, the (theta, phi) grid rules, the N-best tie rule and the
 error paths."""
 import math

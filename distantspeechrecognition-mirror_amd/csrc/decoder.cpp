@@ -21,7 +21,7 @@ struct DecoderState {
   WfstGraph::Csr csr; WfstGraph::Tables tab;
   DevBuf<int> d_xoff, d_xarc, d_xpathOff, d_eoff, d_path, d_nodeFinal, d_queue; DevBuf<float> d_pathCost;
   DevBuf<XRec> d_xrec; DevBuf<ERec> d_erec; DevBuf<float> d_arcCost, d_nodeCost; DevBuf<uint32_t> d_arcOut, d_arcIn;
-  DevBuf<TokA> d_tokA, d_ctok; DevBuf<TokB> d_tokB; DevBuf<Side> d_side; DevBuf<XRecD> d_xrecD; int fastOK = 0; int maxCnt = 0; DevBuf<int> d_tokOff, d_tokCnt, d_owner, d_rank, d_chead; DevBuf<unsigned> d_tags; DevBuf<CandA> d_cA; DevBuf<CandB> d_cB; DevBuf<unsigned> d_first; DevBuf<Bp> d_arena;
+  DevBuf<TokA> d_tokA, d_ctok; DevBuf<TokB> d_tokB; DevBuf<Side> d_side; DevBuf<XRecD> d_xrecD; DevBuf<XRecC> d_xrecC; double recLmScale = 0.0; /* the lmScale the records' costs were scaled with */ int fastOK = 0; int maxCnt = 0; DevBuf<int> d_tokOff, d_tokCnt, d_owner, d_rank, d_chead; DevBuf<unsigned> d_tags; DevBuf<CandA> d_cA; DevBuf<CandB> d_cB; DevBuf<unsigned> d_first; DevBuf<Bp> d_arena;
   DevBuf<long long> d_prof; DevBuf<dsr_decode_result> d_res; DevBuf<int> d_arcs; DevBuf<unsigned> d_words;
   long arenaCap = 0; int initial = 0; unsigned tokenMemoryLimit = 0;
   long lastPoolCap = 0;
@@ -129,24 +129,30 @@ dsr_status dsr_decoder_set(dsr_decoder* d, const dsr_wfst* g)
     if (d->tab.xrec.empty()) throw Error(DSR_E_CONSISTENCY, "the transducer has no emitting arcs");
     d->d_xrec.upload(d->tab.xrec); d->d_xarc.upload(d->tab.xarc); d->d_xpathOff.upload(d->tab.xpathOff);
     {
-      // expansion records with the destination's own expansion range folded in (the register path never reads xoff)
-      const size_t nx = d->tab.xrec.size(); std::vector<XRecD> xd(nx); int maxCnt = 0; std::vector<float> pc(1, 0.0f);
+      // expansion records of the register path (viterbi.h): the hot record with the two costs scaled by this decoder's lmScale -- the products the expansion formed
+      // for every placement are constants of (decoder, graph) -- and the cold record with the destination's own expansion range folded in (the register path
+      // never reads xoff).  Both are this decoder's own: two decoders of different lmScale made from one transducer share nothing.
+      const size_t nx = d->tab.xrec.size(); std::vector<XRecD> xd(nx); std::vector<XRecC> xc(nx); int maxCnt = 0; std::vector<float> pc(1, 0.0f);
+      const double lmS = d->cfg.lmScale; d->recLmScale = lmS;
       for (size_t r = 0; r < nx; r++) {
-        const XRec& x = d->tab.xrec[r]; XRecD& o = xd[r];
-        o.dst = x.dst; o.dist = x.dist; o.cost = x.cost; o.meta = x.meta; o.dstXoff = d->tab.xoff[x.dst]; o.dstCnt = d->tab.xoff[x.dst + 1] - d->tab.xoff[x.dst];
-        const int po = d->tab.xpathOff[r], plen = (int) (x.meta & 0xFFFFu); o.p2 = 0; o.eps1 = 0.0f;
+        const XRec& x = d->tab.xrec[r]; XRecD& o = xd[r]; XRecC& oc = xc[r];
+        o.dst = x.dst; o.dist = x.dist; o.lmCost = lmS * (double) x.cost; o.meta = x.meta;
+        oc.dst = x.dst; oc.dstXoff = d->tab.xoff[x.dst]; oc.dstCnt = d->tab.xoff[x.dst + 1] - d->tab.xoff[x.dst]; oc.pad = 0;
+        const int po = d->tab.xpathOff[r], plen = (int) (x.meta & 0xFFFFu); o.p2 = 0; float eps1 = 0.0f;
         if (x.meta >> 18) throw Error(DSR_E_CONSISTENCY, "expansion record %zu: meta bits above 17 are in use", r);
-        if (plen) { const int a0 = d->tab.path[po]; o.eps1 = d->csr.cost[a0]; if (d->csr.out[a0] != 0) o.meta |= 0x20000u; }
+        if (plen) { const int a0 = d->tab.path[po]; eps1 = d->csr.cost[a0]; if (d->csr.out[a0] != 0) o.meta |= 0x20000u; }
+        o.lmEps1 = lmS * (double) eps1;
         if (plen > 14) o.meta |= 0x80000000u;
         else if (plen > 1) {
           if (plen == 2) { const float c1 = d->csr.cost[d->tab.path[po + 1]]; memcpy(&o.p2, &c1, 4); }
           else { o.p2 = (int) pc.size(); for (int h = 1; h < plen; h++) pc.push_back(d->csr.cost[d->tab.path[po + h]]); }
           for (int h = 1; h < plen; h++) if (d->csr.out[d->tab.path[po + h]] != 0) o.meta |= 1u << (17 + h);
         }
-        if (o.dstCnt > maxCnt) maxCnt = o.dstCnt;
+        if (oc.dstCnt > maxCnt) maxCnt = oc.dstCnt;
       }
-      d->d_xrecD.upload(xd); d->d_pathCost.upload(pc);
-      d->fastOK = (maxCnt < (1 << 19) && nx < ((size_t) 1 << 27)) ? 1 : 0; d->maxCnt = maxCnt;       // (2^27 records x 32 bytes: the register path addresses them with 32-bit byte offsets)
+      d->d_xrecD.upload(xd); d->d_xrecC.upload(xc); d->d_pathCost.upload(pc);
+      // (the register path addresses both record arrays with 32-bit byte offsets: 2^27 records x 32 bytes of the hot record is the bound, the 16-byte cold records end below 2^31)
+      d->fastOK = (maxCnt < (1 << 19) && nx < ((size_t) 1 << 27)) ? 1 : 0; d->maxCnt = maxCnt;
       if (read_vit_env().noFast) d->fastOK = 0;
     }
     { std::vector<ERec> e = d->tab.erec; if (e.empty()) e.push_back(ERec{0, 0, 0, 0}); d->d_erec.upload(e); }
@@ -357,9 +363,11 @@ static VitArgs fill_vit_args(dsr_decoder* d, const DecodePlan& P, const VitEnv& 
     DSR_HIP(hipMemsetAsync(d->d_dumpCount.p, 0, 2 * sizeof(long), st));
   }
   VitArgs A; GraphDev& G = A.G; DecDev& D = A.D;
-  G.nNodes = d->nNodes; G.initial = d->initial; G.xoff = d->d_xoff.p; G.xrec = d->d_xrec.p; G.xrecD = d->d_xrecD.p; G.xarc = d->d_xarc.p;
+  G.nNodes = d->nNodes; G.initial = d->initial; G.xoff = d->d_xoff.p; G.xrec = d->d_xrec.p; G.xrecD = d->d_xrecD.p; G.xrecC = d->d_xrecC.p; G.xarc = d->d_xarc.p;
   G.xpathOff = d->d_xpathOff.p; G.eoff = d->d_eoff.p; G.erec = d->d_erec.p; G.path = d->d_path.p; G.pathCost = d->d_pathCost.p; G.arcCost = d->d_arcCost.p;
   G.arcOut = d->d_arcOut.p; G.arcIn = d->d_arcIn.p; G.nodeFinal = d->d_nodeFinal.p; G.nodeCost = d->d_nodeCost.p;
+  // (the records carry lmScale x cost: nothing changes the scale after dsr_decoder_set today; should that ever be added, the records have to be rebuilt with it)
+  if (memcmp(&d->recLmScale, &d->cfg.lmScale, sizeof(double)) != 0) throw Error(DSR_E_CONSISTENCY, "lmScale changed after the transducer was set");
   D.beam = d->cfg.beam; D.lmScale = d->cfg.lmScale; D.lmPenalty = d->cfg.lmPenalty; D.silPenalty = d->cfg.silPenalty;
   // penalty-free expansion (k_viterbi, expandR): both penalty products zero, and no placement's lm can be -0.0 -- lmScale > 0, no arc cost of -0.0, and every
   // non-zero lmScale x cost at least 2^-60 in magnitude (a sum float + double of that size is 0 or at least 2^-112: it cannot round to -0.0f)

@@ -534,20 +534,18 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
             // NP: both penalty products are zero and no placement's lm can be -0.0 (checked on the host, DecoderState::noPen): "l + 0.0" is then
             // the identity and the four conditional additions of a placement -- an add and two selects each -- are left out
             constexpr bool NP = decltype(NOPEN)::value;
-            int4 xr[kB]; int2 xd[kB]; bool tsil[kB];
-#pragma unroll
-            for (int i = 0; i < kB; i++) { tsil[i] = (ek8[i] >> 29) & 1u; ek8[i] &= 0x1FFFu; }
+            int4 xr[kB]; double2 xl[kB];                  // the hot record: {dist, meta, dst, p2} and {lmCost, lmEps1} = lmScale x the record's two costs (viterbi.h)
 #pragma unroll
             for (int i = 0; i < kB; i++) {                                      // eight record loads in flight
-              xr[i] = *at32<int4>(xrecD, (uint32_t) rec8[i] * 32u); xd[i] = *at32<int2>(xrecD, (uint32_t) rec8[i] * 32u + 16u);
+              xr[i] = *at32<int4>(xrecD, (uint32_t) rec8[i] * 32u); xl[i] = *at32<double2>(xrecD, (uint32_t) rec8[i] * 32u + 16u);
             }
             if (PROF) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); TICK(28); }
 #pragma unroll
             for (int i = 0; i < kB; i++) {
               const int c = (g8 + i) * nthr + tq;
+              const bool tsil = (ek8[i] >> 29) & 1u; ek8[i] &= 0x1FFFu;       // (taken out of ek here, behind the loads: a flag per placement held across them cost scratch memory)
               if (c < C) {
-                const int xdist = xr[i].x; const float xcost = __int_as_float(xr[i].y); const uint32_t xmeta = (uint32_t) xr[i].z;
-                const float e1 = __int_as_float(xr[i].w);
+                const int xdist = xr[i].x; const uint32_t xmeta = (uint32_t) xr[i].y; const int xdst = xr[i].z, xp2 = xr[i].w;
                 const int plen = (int) (xmeta & 0xFFFFu);
                 // selects in place of branches: the additions that may not apply are computed and dropped (same values, one
                 // basic block -- the scalar operands are fetched once per placement instead of once per branch)
@@ -555,21 +553,21 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
                 const bool has = plen != 0;
                 double lmNode;
                 {                                                              // first epsilon hop (decoder.h:979-983): its cost travels with the record
-                  double l = __dadd_rn(lm0, __dmul_rn(lmS, (double) e1));
+                  double l = __dadd_rn(lm0, xl[i].y);
                   if (!NP) {
                     const double l1 = __dadd_rn(l, lsPen); l = (xmeta & 0x20000u) ? l1 : l;
-                    const double l2 = __dadd_rn(l, lsSil); l = (sil0 && (prevNull0 || !tsil[i])) ? l2 : l;   // prevIn != silenceX <=> the token's edge was no silence edge
+                    const double l2 = __dadd_rn(l, lsSil); l = (sil0 && (prevNull0 || !tsil)) ? l2 : l;   // prevIn != silenceX <=> the token's edge was no silence edge
                   }
                   lmNode = has ? (double) (float) l : lm0;
                 }
                 const bool pnull = has ? false : prevNull0;
-                const bool pinSil = has ? sil0 : tsil[i];                      // after an epsilon hop the edge input is 0
+                const bool pinSil = has ? sil0 : tsil;                         // after an epsilon hop the edge input is 0
                 if (plen > 1) {
                   if (!(xmeta & 0x80000000u)) {
                     float hc0 = 0.0f, hc1 = 0.0f, hc2 = 0.0f;                  // three and four hops (and the head of longer paths): their costs in flight together
-                    if (plen > 2) { const float* pc = pathCost + xd[i].y; hc0 = pc[0]; hc1 = pc[1]; hc2 = pc[(plen > 3) ? 2 : 1]; }
+                    if (plen > 2) { const float* pc = pathCost + xp2; hc0 = pc[0]; hc1 = pc[1]; hc2 = pc[(plen > 3) ? 2 : 1]; }
                     for (int h = 1; h < plen; h++) {                           // hop costs: inline (two hops) or one independent load per hop
-                      const float ch = (plen == 2) ? __int_as_float(xd[i].y) : (h == 1 ? hc0 : h == 2 ? hc1 : h == 3 ? hc2 : pathCost[xd[i].y + h - 1]);
+                      const float ch = (plen == 2) ? __int_as_float(xp2) : (h == 1 ? hc0 : h == 2 ? hc1 : h == 3 ? hc2 : pathCost[xp2 + h - 1]);
                       double l = __dadd_rn(lmNode, __dmul_rn(lmS, (double) ch));
                       if (!NP && ((xmeta >> (17 + h)) & 1u)) l = __dadd_rn(l, lsPen);
                       lmNode = (double) (float) l;                              // (the edge before is an epsilon edge: no silence penalty possible here)
@@ -584,7 +582,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
                     }
                   }
                 }
-                double lm = __dadd_rn(lmNode, __dmul_rn(lmS, (double) xcost));
+                double lm = __dadd_rn(lmNode, xl[i].x);
                 if (!NP) { const double lm1 = __dadd_rn(lm, lsPen); lm = (xmeta & 0x10000u) ? lm1 : lm; }
                 const bool silArc = ((uint32_t) (xdist + 1) == silenceX);
                 if (!NP) { const double lm2 = __dadd_rn(lm, lsSil); lm = (silArc && (pnull || !pinSil)) ? lm2 : lm; }
@@ -597,9 +595,9 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
                 locMag = fmaxf(locMag, __fadd_rn(fabsf(ac8[i]), fabsf(lm8[i])));
                 // state table: claim the bucket, keep the smallest slot (with two passes, the other half of the states waits)
                 if (PROF) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); TICK(29); }
-                const unsigned prod = (unsigned) xd[i].x * 2654435761u;
+                const unsigned prod = (unsigned) xdst * 2654435761u;
                 if (!NARROW && nPass > 1 && (prod >> 31)) ek8[i] |= 1u << 27;
-                else ek8[i] |= (table_insert((unsigned) xd[i].x, prod, c) << 13) | (1u << 28);      // bit28: in the table, not folded yet
+                else ek8[i] |= (table_insert((unsigned) xdst, prod, c) << 13) | (1u << 28);      // bit28: in the table, not folded yet
                 if (PROF) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); TICK(30); }
               }
             }
@@ -710,6 +708,10 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
             const bool mine = ((firstMask >> k) & 1ull) && !(ekk & 0x80000000u) && (ekk & (1u << 28)) && in_pass(ekk, pass);
             if (mine) {
               const unsigned head = chain_head((ekk >> 13) & ekBucket);
+              // narrow table: the owner wipes its bucket.  After the barrier that ends P4 nothing but a bucket's own first arrival reads or writes the bucket's word (the
+              // later arrivals' status reads and pushes are before that barrier, the replays walk side records), every occupied word was claimed by a key, and every key has
+              // exactly one smallest slot -- whose placement, doomed or pruned or neither, comes through here.  So every word is zero again at the barrier after the fold.
+              if (NARROW) tab[(ekk >> 13) & ekBucket] = 0u;
               ekk &= 0x1FFFu;
               if (head & 0x80000000u) {
                 int wIdx = -1;
@@ -731,7 +733,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
           auto insert8 = [&](const int g8, const int* rec8, unsigned* ek8) __attribute__((always_inline)) {
             int xd[kB];
 #pragma unroll
-            for (int i = 0; i < kB; i++) xd[i] = ka->G.xrecD[rec8[i] & 0x3FFFFFFF].dst;
+            for (int i = 0; i < kB; i++) xd[i] = ka->G.xrecC[rec8[i] & 0x3FFFFFFF].dst;     // (the cold record: half the bytes per line of the gather)
 #pragma unroll
             for (int i = 0; i < kB; i++) {
               const int c = (g8 + i) * nthr + tq;
@@ -847,9 +849,12 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
           TICK(13);
           __syncthreads();
           TICK(14);
-          {                                                                    // every chain has been folded: the state table is dead.  Wiped here, under wave 0's prefix sum
+          // every chain has been folded: the state table is dead.  The wide table is wiped here, under wave 0's prefix sum; the narrow one is clean already -- its first
+          // arrivals zeroed their own words in the fold (fold1), ~5 k words a frame instead of 128 KB.  A frame that leaves the loop before this point or below (s_err above,
+          // the allocation statuses below) ends its utterance or segment: the next work item of this workgroup starts with the full wipe at the head of the item loop.
+          if (!NARROW) {
             uint4* h4 = reinterpret_cast<uint4*>(hkey); const int q4 = hashN >> 2;
-            for (int i = tq; i < 2 * q4; i += nthr) { unsigned wv = (NARROW || i < q4) ? 0u : 0xFFFFFFFFu; asm volatile("" : "+v"(wv)); h4[i] = make_uint4(wv, wv, wv, wv); }
+            for (int i = tq; i < 2 * q4; i += nthr) { unsigned wv = (i < q4) ? 0u : 0xFFFFFFFFu; asm volatile("" : "+v"(wv)); h4[i] = make_uint4(wv, wv, wv, wv); }
           }
           if (wq == 0) {                                                       // exclusive prefix over (k, wave) = slot order of the groups
             const int nG = K * nw;                                             // <= 6 * 64
@@ -875,15 +880,15 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
             arenaOff = (long) s_chunk; chunkEnd = arenaOff + need;
             if (chunkEnd > ka->D.poolCap) { status = DSR_E_ALLOCATION; break; }
           }
-          const XRecD* const xrecW = ka->G.xrecD; TokA* const outA = nxtA; TokB* const outB = nxtB; Bp* const outBp = arena + arenaOff;
-          // ---- P6: the new list in reverse first-arrival order + back pointers; the state table is wiped for the next frame
+          const XRecC* const xrecW = ka->G.xrecC; TokA* const outA = nxtA; TokB* const outB = nxtB; Bp* const outBp = arena + arenaOff;
+          // ---- P6: the new list in reverse first-arrival order + back pointers (the cold records: destination and its expansion range); the state table is clean for the next frame
           auto write4 = [&](auto NB, const int g4, const float* ac4, const float* lm4, const int* rec4, const unsigned* ek4) __attribute__((always_inline)) {
             constexpr int nb = decltype(NB)::value;
             int4 dx[nb]; uint32_t pv[nb];
 #pragma unroll
             for (int i = 0; i < nb; i++) {                                      // unconditional loads (every index is in bounds), in flight together;
               const bool kp = (keepMask >> (g4 + i)) & 1ull;                   // placements that are not written all read record 0 / token 0 (one line)
-              dx[i] = *reinterpret_cast<const int4*>(&xrecW[kp ? (rec4[i] & 0x3FFFFFFF) : 0].dst);       // same state for every arrival
+              dx[i] = *reinterpret_cast<const int4*>(&xrecW[kp ? (rec4[i] & 0x3FFFFFFF) : 0]);       // same state for every arrival
               const bool sw = kp && (ek4[i] & 0x80000000u) != 0u; const unsigned si = ek4[i] & 0x7FFFFFFFu;
               const uint32_t* pb = (sw && si >= (unsigned) sideLds) ? &side[si].prevBp : &ctk[(sw || !kp) ? 0u : (ek4[i] & 0x1FFFu)].bp;
               pv[i] = *pb;
@@ -897,11 +902,11 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
                 const unsigned long long bal = __ballot(isFirst);
                 if (isFirst) {
                   const int pos = numNew - 1 - (s_cnt[k * nw + wq] + __popcll(bal & ((1ull << lq) - 1ull)));
-                  TokA na; na.ac = ac4[i]; na.lm = lm4[i]; na.bp = (uint32_t) (arenaOff + pos); na.xs = (uint32_t) dx[i].z | ((rec4[i] & 0x40000000) ? 0x80000000u : 0u);
-                  TokB nb; nb.node = dx[i].x; nb.cnt = dx[i].w;
+                  TokA na; na.ac = ac4[i]; na.lm = lm4[i]; na.bp = (uint32_t) (arenaOff + pos); na.xs = (uint32_t) dx[i].y | ((rec4[i] & 0x40000000) ? 0x80000000u : 0u);
+                  TokB nb; nb.node = dx[i].x; nb.cnt = dx[i].z;
                   Bp bp; bp.prev = pv[i]; bp.rec = (uint32_t) (rec4[i] & 0x3FFFFFFF);
                   outA[pos] = na; outB[pos] = nb; outBp[pos] = bp;
-                  if (pos < cntCap) cntL[pos] = (unsigned short) dx[i].w;
+                  if (pos < cntCap) cntL[pos] = (unsigned short) dx[i].z;
                 }
               }
             }
@@ -909,6 +914,8 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
           // Three placements in four are not written (pruned, or later arrivals): the ones that are go through the (wiped) state table as a dense
           // list -- {ac, lm, record, where the parent's back pointer is} at its rank -- and the loads and stores of the write run over that list,
           // every lane at work, instead of over all slots with a quarter of the lanes.  A thread restores the table words it has read.
+          // (more than 8 192 new tokens -- a list of at most kFastE tokens can fan out to that many states; the frame behind it then takes the memory path -- are written from the
+          // slots: nothing is staged, so the table stays as the fold left it, clean)
           const bool dense = numNew <= (hashN >> 1);
           if (dense) {
             uint4* const stage = reinterpret_cast<uint4*>(hkey);
@@ -940,7 +947,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
 #pragma unroll
               for (int i = 0; i < 2; i++) {
                 const bool on = f0 + i * nthr + tq < numNew;
-                dx[i] = *at32<int4>(xrecW, (on ? (en[i].z & 0x3FFFFFFFu) : 0u) * 32u + 16u);
+                dx[i] = *at32<int4>(xrecW, (on ? (en[i].z & 0x3FFFFFFFu) : 0u) * 16u);
                 const bool sw = on && (en[i].w & 0x80000000u) != 0u; const unsigned si = en[i].w & 0x7FFFFFFFu;
                 const uint32_t* pb = (sw && si >= (unsigned) sideLds) ? &side[si].prevBp : &ctk[(sw || !on) ? 0u : (en[i].w & 0x1FFFu)].bp;
                 pv[i] = *pb;
@@ -954,11 +961,11 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
                 const int f = f0 + i * nthr + tq;
                 if (f < numNew) {
                   const int pos = numNew - 1 - f;
-                  TokA na; na.ac = __uint_as_float(en[i].x); na.lm = __uint_as_float(en[i].y); na.bp = (uint32_t) (arenaOff + pos); na.xs = (uint32_t) dx[i].z | ((en[i].z & 0x40000000u) ? 0x80000000u : 0u);
-                  TokB nb; nb.node = dx[i].x; nb.cnt = dx[i].w;
+                  TokA na; na.ac = __uint_as_float(en[i].x); na.lm = __uint_as_float(en[i].y); na.bp = (uint32_t) (arenaOff + pos); na.xs = (uint32_t) dx[i].y | ((en[i].z & 0x40000000u) ? 0x80000000u : 0u);
+                  TokB nb; nb.node = dx[i].x; nb.cnt = dx[i].z;
                   Bp bp; bp.prev = pv[i]; bp.rec = (uint32_t) (en[i].z & 0x3FFFFFFFu);
                   outA[pos] = na; outB[pos] = nb; outBp[pos] = bp;
-                  if (pos < cntCap) cntL[pos] = (unsigned short) dx[i].w;
+                  if (pos < cntCap) cntL[pos] = (unsigned short) dx[i].z;
                 }
               }
             };
@@ -1009,7 +1016,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
                 uint4 en[2]; int4 dx[2]; uint32_t pv[2];
                 denseLoad(h * 2 * nthr, en, dx, pv); denseStore(h * 2 * nthr, en, dx, pv);
 #pragma unroll
-                for (int i = 0; i < 2; i++) cn[2 * h + i] = ((2 * h + i) * nthr + tq < numNew) ? dx[i].w : 0;
+                for (int i = 0; i < 2; i++) cn[2 * h + i] = ((2 * h + i) * nthr + tq < numNew) ? dx[i].z : 0;
               }
               layOut(std::integral_constant<int, 4>{}, cn);
             } else {
@@ -1017,7 +1024,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
                 uint4 en[2]; int4 dx[2]; uint32_t pv[2];
                 denseLoad(f0, en, dx, pv);
                 if (layNext) {                                                 // (one round; its stores drain under the layout's scan)
-                  const int cn[2] = { (tq < numNew) ? dx[0].w : 0, (nthr + tq < numNew) ? dx[1].w : 0 };
+                  const int cn[2] = { (tq < numNew) ? dx[0].z : 0, (nthr + tq < numNew) ? dx[1].z : 0 };
                   layOut(std::integral_constant<int, 2>{}, cn);
                 }
                 denseStore(f0, en, dx, pv);

@@ -10,11 +10,16 @@ struct Tok { int32_t node; float ac; float lm; uint32_t bp; };        // registe
 // token lists in memory: what a frame's beam test and expansion need (TokA) apart from what only the end phase needs (TokB)
 struct TokA { float ac; float lm; uint32_t bp; uint32_t xs; };        // xs: first expansion record of the node | bit31: edge input == silenceX
 struct TokB { int32_t node; int32_t cnt; };                           // cnt: number of expansion records of the node
-// expansion record as the register path reads it: what the expansion needs in the first 16 bytes, what the new token needs in the second
+// expansion record as the register path reads it, in two parts.  The hot record is what the expansion (P3) loads: 16 bytes of fields and the record's two language-model
+// costs ALREADY SCALED -- lmCost = lmScale * (double) cost and lmEps1 = lmScale * (double) eps1, formed once on the host when the graph is set (dsr_decoder_set; lmScale is
+// fixed when the decoder is created).  Exactness: decoder.cpp is built with -ffp-contract=off, and an IEEE-754 double product of the same two operands, rounded to nearest,
+// is the device's __dmul_rn(lmScale, (double) cost) bit for bit -- the expansion adds the very double it used to compute per placement.
 // eps1: cost of the first epsilon hop (meta bit17: it has an output).  Further hops (meta bits 18..30: hop h = 1..13 has an output):
-// a two-hop path carries the second cost in p2 (float bits), longer ones the offset of their hop costs in GraphDev::pathCost;
+// a two-hop path carries the second cost in p2 (float bits, scaled on the device), longer ones the offset of their hop costs in GraphDev::pathCost;
 // meta bit31: more than 14 hops, walked through the path/arc arrays instead.
-struct XRecD { int32_t dist; float cost; uint32_t meta; float eps1; int32_t dst; int32_t p2; int32_t dstXoff; int32_t dstCnt; };
+// The cold record is what the new token needs (P6 gathers it by record): the destination and its own expansion range.
+struct XRecD { int32_t dist; uint32_t meta; int32_t dst; int32_t p2; double lmCost; double lmEps1; };
+struct XRecC { int32_t dst; int32_t dstXoff; int32_t dstCnt; int32_t pad; };
 struct Side { double ttl; float ac; float lm; int32_t rec; uint32_t prevBp; int32_t c; uint32_t next; };   // a later arrival at an occupied state
 struct CandA { double ttl; float ac; float lm; };
 struct CandB { int32_t dst; int32_t next; int32_t rec; uint32_t prevBp; };   // rec bit30: the emitting arc's input is the silence symbol
@@ -26,7 +31,7 @@ struct Bp { uint32_t prev; uint32_t rec; };
 // leaves the number of hops here.
 struct TraceHead { unsigned long long arenaOff; uint32_t bp; uint32_t hops; };
 // (the LDS budget of decode_plan.h counts 32 bytes per side record; the 32-bit byte offsets of the register path rest on the other sizes)
-static_assert(sizeof(TokA) == 16 && sizeof(TokB) == 8 && sizeof(XRecD) == 32 && sizeof(Side) == 32 && sizeof(CandA) == 16 && sizeof(CandB) == 16 && sizeof(Bp) == 8 && sizeof(TraceHead) == 16,
+static_assert(sizeof(TokA) == 16 && sizeof(TokB) == 8 && sizeof(XRecD) == 32 && sizeof(XRecC) == 16 && sizeof(Side) == 32 && sizeof(CandA) == 16 && sizeof(CandB) == 16 && sizeof(Bp) == 8 && sizeof(TraceHead) == 16,
               "record layouts shared by the host and k_viterbi");
 
 static constexpr int kThreads = 1024;             // 16 waves per CU at 128 VGPRs (measured in round 2: 512 x 256 VGPRs 22 % slower, 768 x 168 VGPRs 4 % slower; two 512-thread workgroups per CU 1.2x slower)
@@ -36,7 +41,7 @@ static constexpr int kSideLds = 496;               // later arrivals kept in LDS
 
 struct GraphDev {
   int nNodes, initial;
-  const int* xoff; const XRec* xrec; const XRecD* xrecD; const int* xarc; const int* xpathOff;
+  const int* xoff; const XRec* xrec; const XRecD* xrecD; const XRecC* xrecC; const int* xarc; const int* xpathOff;
   const int* eoff; const ERec* erec; const int* path; const float* pathCost;
   const float* arcCost; const uint32_t* arcOut; const uint32_t* arcIn;
   const int* nodeFinal; const float* nodeCost;

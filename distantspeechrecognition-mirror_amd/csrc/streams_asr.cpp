@@ -2,6 +2,7 @@
 // posteriors straight from a feature stream (see stream_op.h).
 #include "stream_op.h"
 #include "lattice.h"
+#include "multistream.h"
 
 extern "C" {
 
@@ -114,7 +115,60 @@ dsr_lda* dsr_lda_feature_handle(dsr_stream* s) { LdaOp* q = dynamic_cast<LdaOp*>
 // a feature stream handle: score(distX, frameX) scores ALL distributions of that frame on the device at the first request and serves the rest
 // of the frame's requests from the host copy; decode_stream() keeps everything on the device (features -> scores -> token passing), no host
 // round trip.
-struct dsr_distribset { dsr_gmm* gmm = nullptr; dsr_stream* feat = nullptr; int mode = 0; int cachedFrame = -1; std::vector<float> row; DevBuf<float> d_row, d_scores; DevBuf<int> d_T; };
+// A multi-stream set (include/dsr.h section 8b; the struct is multistream.h's) has two such sets as children and asks both, then combines.
+namespace {
+void null_check(const void* d) { if (!d) throw Error(DSR_E_PARAMETER, "null argument"); }
+const dsr_gmm* names_of(const dsr_distribset* d) { return d->ms ? d->audio->gmm : d->gmm; }
+int ndists(const dsr_distribset* d) { return dsr_gmm_num_dists(names_of(d)); }
+void reset_cache(dsr_distribset* d) { d->cachedFrame = -1; if (d->ms) { reset_cache(d->audio); reset_cache(d->video); } }
+void reset_feature(dsr_distribset* d) { d->cachedFrame = -1; if (d->ms) { reset_feature(d->audio); reset_feature(d->video); } else d->feat->reset(); }
+// every distribution's score of frame frameX in d->d_row, on the device: the frame is pulled through the stream protocol (jiterator_error at
+// the end of the stream, jindex_error out of order) unless the row is the cached one
+void frame_row(dsr_distribset* d, int frameX)
+{
+  if (frameX == d->cachedFrame && frameX >= 0) return;
+  const int K = ndists(d);
+  d->d_row.reserve((size_t) K); d->hostRow = false;
+  if (d->ms) {
+    frame_row(d->audio, frameX); frame_row(d->video, frameX);
+    ms_combine(d->audio->d_row.p, d->video->d_row.p, d->ms->d_table.p, 1, d->ms->KA, d->ms->KV, d->ms->wA, d->ms->wV, d->d_row.p, S0);
+    d->cachedFrame = d->audio->cachedFrame;
+    return;
+  }
+  (void) d->feat->next(frameX);
+  const int t = d->feat->frameX;
+  const float* x = reinterpret_cast<const float*>(d->feat->dev.p) + (size_t) t * d->feat->size_;
+  ok(dsr_gmm_score(d->gmm, x, 1, d->mode, d->d_row.p, nullptr, S0));
+  d->cachedFrame = t;
+}
+// the score matrix [T][ndists] of the utterance the stream(s) hold, on the device: a multi-stream set scores T = min frames of each child in the
+// child's own mode and combines in place in the audio child's matrix
+const float* score_matrix(dsr_distribset* d, int* T)
+{
+  if (d->ms) {
+    int Ta = 0, Tv = 0;
+    const float* sA = score_matrix(d->audio, &Ta); const float* sV = score_matrix(d->video, &Tv);
+    *T = Ta < Tv ? Ta : Tv;
+    if (*T > 0) ms_combine(sA, sV, d->ms->d_table.p, *T, d->ms->KA, d->ms->KV, d->ms->wA, d->ms->wV, d->audio->d_scores.p, S0);
+    return d->audio->d_scores.p;
+  }
+  d->feat->materialize();
+  *T = d->feat->nFrames;
+  if (*T > 0) {
+    const int K = ndists(d);
+    d->d_scores.reserve((size_t) *T * K);
+    ok(dsr_gmm_score(d->gmm, reinterpret_cast<const float*>(d->feat->dev.p), (int64_t) *T, d->mode, d->d_scores.p, nullptr, S0));
+  }
+  return d->d_scores.p;
+}
+// the reference has pulled the stream(s) to the end
+void at_end(dsr_distribset* d, int T)
+{
+  if (d->ms) { at_end(d->audio, T); at_end(d->video, T); return; }
+  if (T > 0) d->feat->frameX = T - 1;
+  d->feat->endOfSamples = true;
+}
+}  // namespace
 
 dsr_status dsr_distribset_create(dsr_gmm* gmm, dsr_stream* feature, int gmmMode, dsr_distribset** out)
 {
@@ -126,27 +180,30 @@ dsr_status dsr_distribset_create(dsr_gmm* gmm, dsr_stream* feature, int gmmMode,
     auto d = std::make_unique<dsr_distribset>(); d->gmm = gmm; d->feat = feature; d->mode = gmmMode; dsr_stream_retain(feature); *out = d.release();
   });
 }
-void dsr_distribset_destroy(dsr_distribset* d) { if (d) { dsr_stream_release(d->feat); delete d; } }
-int dsr_distribset_ndists(const dsr_distribset* d) { return d ? dsr_gmm_num_dists(d->gmm) : 0; }
+void dsr_distribset_destroy(dsr_distribset* d)
+{
+  if (!d || --d->refs > 0) return;
+  if (d->ms) { dsr_ms_destroy(d->ms); dsr_distribset_destroy(d->audio); dsr_distribset_destroy(d->video); }
+  else dsr_stream_release(d->feat);
+  delete d;
+}
+int dsr_distribset_ndists(const dsr_distribset* d) { return d ? ndists(d) : 0; }
 dsr_status dsr_distribset_find(const dsr_distribset* d, const char* name, int* distX)
-{ if (!d) return guard([&] { throw Error(DSR_E_PARAMETER, "null argument"); }); return dsr_gmm_find_dist(d->gmm, name, distX); }
-const char* dsr_distribset_name(const dsr_distribset* d, int distX) { return d ? dsr_gmm_dist_name(d->gmm, distX) : ""; }
-dsr_status dsr_distribset_reset_cache(dsr_distribset* d) { return guard([&] { if (!d) throw Error(DSR_E_PARAMETER, "null argument"); d->cachedFrame = -1; }); }      // codebookBasic.cc:414-420
-dsr_status dsr_distribset_reset_feature(dsr_distribset* d) { return guard([&] { if (!d) throw Error(DSR_E_PARAMETER, "null argument"); d->feat->reset(); d->cachedFrame = -1; }); }
+{ if (!d) return guard([&] { throw Error(DSR_E_PARAMETER, "null argument"); }); return dsr_gmm_find_dist(names_of(d), name, distX); }
+const char* dsr_distribset_name(const dsr_distribset* d, int distX) { return d ? dsr_gmm_dist_name(names_of(d), distX) : ""; }
+dsr_status dsr_distribset_reset_cache(dsr_distribset* d) { return guard([&] { null_check(d); reset_cache(d); }); }      // codebookBasic.cc:414-420
+dsr_status dsr_distribset_reset_feature(dsr_distribset* d) { return guard([&] { null_check(d); reset_feature(d); }); }
 dsr_status dsr_distribset_score(dsr_distribset* d, int distX, int frameX, float* score)
 {
   return guard([&] {
     if (!d || !score) throw Error(DSR_E_PARAMETER, "null argument");
-    const int K = dsr_gmm_num_dists(d->gmm);
+    const int K = ndists(d);
     if (distX < 0 || distX >= K) throw Error(DSR_E_INDEX, "distribution %d of %d", distX, K);
-    if (frameX != d->cachedFrame || frameX < 0) {
-      (void) d->feat->next(frameX);                                       // jiterator_error at the end of the stream, jindex_error out of order
-      const int t = d->feat->frameX;
-      d->d_row.reserve((size_t) K); d->row.resize((size_t) K);
-      const float* x = reinterpret_cast<const float*>(d->feat->dev.p) + (size_t) t * d->feat->size_;
-      ok(dsr_gmm_score(d->gmm, x, 1, d->mode, d->d_row.p, nullptr, S0));
+    frame_row(d, frameX);
+    if (!d->hostRow) {
+      d->row.resize((size_t) K);
       DSR_HIP(hipMemcpy(d->row.data(), d->d_row.p, sizeof(float) * (size_t) K, hipMemcpyDeviceToHost));
-      d->cachedFrame = t;
+      d->hostRow = true;
     }
     *score = d->row[(size_t) distX];
   });
@@ -157,14 +214,12 @@ dsr_status dsr_decoder_decode_stream(dsr_decoder* dec, dsr_distribset* d, dsr_de
 {
   return guard([&] {
     if (!dec || !d || !res) throw Error(DSR_E_PARAMETER, "null argument");
-    d->cachedFrame = -1; d->feat->reset();
-    d->feat->materialize();
-    const int T = d->feat->nFrames, K = dsr_gmm_num_dists(d->gmm);
-    if (T <= 0) { d->feat->endOfSamples = true; throw Error(DSR_E_ITERATOR, "end of samples!"); }
-    d->d_scores.reserve((size_t) T * K); d->d_T.upload(&T, 1);
-    ok(dsr_gmm_score(d->gmm, reinterpret_cast<const float*>(d->feat->dev.p), (int64_t) T, d->mode, d->d_scores.p, nullptr, S0));
-    ok(dsr_decoder_decode_batch(dec, d->d_scores.p, d->d_T.p, 1, T, K, res, arcs_out, words_out, maxPath, S0));
-    d->feat->frameX = T - 1; d->feat->endOfSamples = true;                   // the reference has pulled the stream to its end
+    reset_feature(d);
+    int T = 0; const float* scores = score_matrix(d, &T); const int K = ndists(d);
+    if (T <= 0) { at_end(d, 0); throw Error(DSR_E_ITERATOR, "end of samples!"); }
+    d->d_T.upload(&T, 1);
+    ok(dsr_decoder_decode_batch(dec, scores, d->d_T.p, 1, T, K, res, arcs_out, words_out, maxPath, S0));
+    at_end(d, T);
     if (res->status != DSR_OK) throw Error(res->status, "decode failed (status %d)", res->status);
   });
 }
@@ -178,10 +233,11 @@ dsr_status dsr_lattice_gamma_probs_dist(dsr_lattice* L, dsr_distribset* d, doubl
 {
   return guard([&] {
     if (!L || !d) throw Error(DSR_E_PARAMETER, "null argument");
-    d->cachedFrame = -1;                                                     // dss->resetCache()
+    reset_cache(d);                                                          // dss->resetCache()
     L->ensure_ops(); L->sorted.clear();                                      // _clearSorted()
-    d->feat->materialize();
-    const int T = d->feat->nFrames, K = dsr_gmm_num_dists(d->gmm);
+    const bool plain = !d->ms; if (plain) d->feat->materialize();
+    int T = plain ? d->feat->nFrames : 0; const int K = ndists(d);
+    const float* scores = plain ? nullptr : score_matrix(d, &T);             // a multi-stream set knows its frame count from the matrix
     std::vector<int> link, dist, start, end;
     auto take = [&](int node) {
       for (size_t k = 0; k < L->adj[(size_t) node].size(); k++) {
@@ -198,10 +254,9 @@ dsr_status dsr_lattice_gamma_probs_dist(dsr_lattice* L, dsr_distribset* d, doubl
     for (size_t p = 0; p < L->slots.size(); p++) if (L->slots[p] >= 0) take(L->slots[p]);
     if (!link.empty()) {
       if (T <= 0) throw Error(DSR_E_ITERATOR, "end of samples!");
-      d->d_scores.reserve((size_t) T * K);
-      ok(dsr_gmm_score(d->gmm, reinterpret_cast<const float*>(d->feat->dev.p), (int64_t) T, d->mode, d->d_scores.p, nullptr, S0));
+      if (plain) scores = score_matrix(d, &T);
       DevBuf<int> dd, ds, de; DevBuf<double> dout; dd.upload(dist); ds.upload(start); de.upload(end); dout.reserve(link.size());
-      op_link_ac(d->d_scores.p, K, dd.p, ds.p, de.p, (int) link.size(), dout.p, S0);
+      op_link_ac(scores, K, dd.p, ds.p, de.p, (int) link.size(), dout.p, S0);
       std::vector<double> sums(link.size());
       DSR_HIP(hipMemcpy(sums.data(), dout.p, sizeof(double) * link.size(), hipMemcpyDeviceToHost));
       for (size_t i = 0; i < link.size(); i++) {

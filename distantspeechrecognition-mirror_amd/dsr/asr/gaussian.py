@@ -1,5 +1,6 @@
 """asr.gaussian: CodebookSetBasicPtr / DistribSetBasicPtr (gaussian.i:281-283,465-467) for 1:1 distribution/codebook models, over dsr_gmm_* and
-dsr_distribset_* (include/dsr.h sections 4 and 8)."""
+dsr_distribset_* (include/dsr.h sections 4 and 8); DistribMapPtr / DistribMultiStreamPtr / DistribSetMultiStreamPtr (distribBasic.h:135-158, 390-408)
+over section 8b."""
 import ctypes as C
 
 import numpy as np
@@ -89,3 +90,87 @@ class DistribSetBasicPtr(object):
     def score_all_frames(self, feats, mode=0):
         """feats: cuda float32 [T][dimN] -> costs [T][ndists] (row t = Distrib::score(t) of every distribution)."""
         return self.gmm.score(feats, mode=mode, want_argmin=False)[0]
+
+
+class DistribMapPtr(object):
+    """DistribMap (distribBasic.h:390-408, gaussian.i): add / mapped / read / write over dsr_distribmap_* (include/dsr.h section 8b)"""
+
+    def __init__(self):
+        from .. import _ms
+        self._map = _ms.DistribMap()
+
+    def add(self, fromName, toName):
+        self._map.add(fromName, toName)
+
+    def mapped(self, name):
+        return self._map.mapped(name)
+
+    __getitem__ = mapped
+
+    def __len__(self):
+        return len(self._map)
+
+    def read(self, fileName):
+        self._map.read(fileName)
+
+    def write(self, fileName):
+        self._map.write(fileName)
+
+
+class DistribMultiStreamPtr(DistribBasicPtr):
+    """DistribMultiStream (distribBasic.h:135-158): score(frameX) = audioWeight * audio score + videoWeight * video score"""
+
+    def audioWeight(self):
+        return self._dss.weights()[0]
+
+    def videoWeight(self):
+        return self._dss.weights()[1]
+
+
+class DistribSetMultiStreamPtr(object):
+    """DistribSetMultiStream(audioDistSet, videoDistSet[, distribMap], audioWeight, videoWeight) (distribBasic.cc:381-410): the audio set's
+    distributions, names and order; the partner of `name` is videoDistSet.find(name), or videoDistSet.find(distribMap.mapped(name)).  Decoders and
+    lattices take it wherever they take a DistribSetBasicPtr."""
+
+    def __init__(self, audioDss, videoDss, distribMap=None, audioWeight=0.95, videoWeight=0.05):
+        self._audio, self._video, self._map = audioDss, videoDss, distribMap          # kept: the set's children outlive it
+        self.names = [audioDss.find(k).name() for k in range(audioDss.ndists())]
+        self._ds = C.c_void_p()
+        K.check(K.load().dsr_distribset_create_multistream(audioDss._ds, videoDss._ds, distribMap._map.h if distribMap is not None else None,
+                                                           float(audioWeight), float(videoWeight), C.byref(self._ds)))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_ds", None):
+                K.load().dsr_distribset_destroy(self._ds)
+        except Exception:
+            pass
+
+    def ndists(self):
+        return K.load().dsr_distribset_ndists(self._ds)
+
+    def index(self, name):
+        x = C.c_int(); K.check(K.load().dsr_distribset_find(self._ds, name.encode(), C.byref(x))); return x.value
+
+    def find(self, key):
+        x = self.index(key) if isinstance(key, str) else int(key)
+        if not 0 <= x < self.ndists():
+            raise K.DsrError(6, "distribution %d of %d" % (x, self.ndists()))
+        return DistribMultiStreamPtr(self, x)
+
+    __getitem__ = find
+
+    def __iter__(self):
+        return (self.find(k) for k in range(self.ndists()))
+
+    def weights(self):
+        a, v = C.c_double(), C.c_double(); K.check(K.load().dsr_distribset_get_weights(self._ds, C.byref(a), C.byref(v))); return a.value, v.value
+
+    def setWeights(self, audioWeight, videoWeight):
+        K.check(K.load().dsr_distribset_set_weights(self._ds, float(audioWeight), float(videoWeight)))
+
+    def resetCache(self):
+        K.check(K.load().dsr_distribset_reset_cache(self._ds))
+
+    def resetFeature(self):
+        K.check(K.load().dsr_distribset_reset_feature(self._ds))

@@ -970,7 +970,7 @@ typedef std::shared_ptr<PlaneWaveSimulator> PlaneWaveSimulatorPtr;
 
 // ======================================================================================================================
 // ASR side (asr/dictionary, asr/gaussian, asr/decoder): the classes decoder.i:52-199 and gaussian.i:281-283,465-467 wrap, with
-// their constructor argument order, over include/dsr.h sections 4, 5 and 8.
+// their constructor argument order, over include/dsr.h sections 4, 5, 8 and 8b.
 // ======================================================================================================================
 #include <fstream>
 #include <map>
@@ -1066,12 +1066,66 @@ class DistribSetBasic {
   dsr_distribset* handle() const { return _ds; }
   dsr_gmm* gmm() const { return _gmm; }
   VectorFloatFeatureStreamPtr& featureStream() { return _feat; }
+ protected:
+  explicit DistribSetBasic(dsr_distribset* ds) : _gmm(0), _ds(ds) {}                              // a set that is no model of its own (multi-stream)
  private:
   DistribSetBasic(const DistribSetBasic&); DistribSetBasic& operator=(const DistribSetBasic&);
   CodebookSetBasicPtr _cbs; VectorFloatFeatureStreamPtr _feat; dsr_gmm* _gmm; dsr_distribset* _ds;
 };
 typedef std::shared_ptr<DistribSetBasic> DistribSetBasicPtr;
 typedef DistribSetBasicPtr DistribSetPtr;
+
+// ---- multi-stream decoding (include/dsr.h section 8b): DistribMap (distribBasic.h:390-408), DistribMultiStream (:135-158) and
+// DistribSetMultiStream(audioDistSet, videoDistSet[, distribMap], audioWeight, videoWeight) (distribBasic.cc:381-410).  A DistribSetMultiStreamPtr
+// converts to DistribSetPtr, so it is what DecoderFlyWeight and Lattice::gammaProbsDist take.
+class DistribMap {
+ public:
+  DistribMap() : _h(0) { dsr_throw(dsr_distribmap_create(&_h)); }
+  ~DistribMap() { dsr_distribmap_destroy(_h); }
+  void add(const String& fromName, const String& toName) { dsr_throw(dsr_distribmap_add(_h, fromName.c_str(), toName.c_str())); }
+  String mapped(const String& name) const { const char* to = 0; dsr_throw(dsr_distribmap_mapped(_h, name.c_str(), &to)); return to; }
+  unsigned size() const { return (unsigned) dsr_distribmap_size(_h); }
+  void read(const String& fileName) { dsr_throw(dsr_distribmap_read(_h, fileName.c_str())); }
+  void write(const String& fileName) const { dsr_throw(dsr_distribmap_write(_h, fileName.c_str())); }
+  dsr_distribmap* handle() const { return _h; }
+ private:
+  DistribMap(const DistribMap&); DistribMap& operator=(const DistribMap&);
+  dsr_distribmap* _h;
+};
+typedef std::shared_ptr<DistribMap> DistribMapPtr;
+
+class DistribMultiStream : public DistribBasic {
+ public:
+  DistribMultiStream(dsr_distribset* ds, int x) : DistribBasic(ds, x), _set(ds) {}
+  double audioWeight() const { double a = 0.0, v = 0.0; dsr_throw(dsr_distribset_get_weights(_set, &a, &v)); return a; }
+  double videoWeight() const { double a = 0.0, v = 0.0; dsr_throw(dsr_distribset_get_weights(_set, &a, &v)); return v; }
+ private:
+  dsr_distribset* _set;
+};
+class DistribSetMultiStream : public DistribSetBasic {
+ public:
+  DistribSetMultiStream(DistribSetBasicPtr& audioDistSet, DistribSetBasicPtr& videoDistSet, double audioWeight = 0.95, double videoWeight = 0.05)
+    : DistribSetBasic(make(audioDistSet, videoDistSet, 0, audioWeight, videoWeight)), _audio(audioDistSet), _video(videoDistSet) {}
+  DistribSetMultiStream(DistribSetBasicPtr& audioDistSet, DistribSetBasicPtr& videoDistSet, DistribMapPtr& distribMap, double audioWeight = 0.95, double videoWeight = 0.05)
+    : DistribSetBasic(make(audioDistSet, videoDistSet, distribMap ? distribMap->handle() : 0, audioWeight, videoWeight)), _audio(audioDistSet), _video(videoDistSet) {}
+  DistribMultiStream find(const String& key) { return DistribMultiStream(handle(), (int) index(key)); }
+  DistribMultiStream find(unsigned dsX) { if (dsX >= ndists()) throw jindex_error("distribution index out of range"); return DistribMultiStream(handle(), (int) dsX); }
+  void setWeights(double audioWeight, double videoWeight) { dsr_throw(dsr_distribset_set_weights(handle(), audioWeight, videoWeight)); }
+ private:
+  static dsr_distribset* make(DistribSetBasicPtr& a, DistribSetBasicPtr& v, const dsr_distribmap* m, double wA, double wV) {
+    if (!a || !v) throw jparameter_error("null argument");
+    dsr_distribset* ds = 0; dsr_throw(dsr_distribset_create_multistream(a->handle(), v->handle(), m, wA, wV, &ds)); return ds;
+  }
+  DistribSetBasicPtr _audio, _video;
+};
+class DistribSetMultiStreamPtr : public std::shared_ptr<DistribSetMultiStream> {
+ public:
+  DistribSetMultiStreamPtr() {}
+  explicit DistribSetMultiStreamPtr(DistribSetMultiStream* p) : std::shared_ptr<DistribSetMultiStream>(p), _base(*this) {}
+  operator DistribSetPtr&() { return _base; }                                                     // the first argument of DecoderFlyWeight
+ private:
+  DistribSetPtr _base;
+};
 
 // ---- asr/decoder: WFSTFlyWeight(statelex, inlex, outlex, name) (decoder.i:52-70)
 class WFSTFlyWeight {

@@ -1988,6 +1988,65 @@ dsr_status dsr_lattice_gamma_probs_dist(dsr_lattice*, dsr_distribset*, double ac
                                         unsigned silenceX, double* logProb);
 
 /* =====================================================================================
+ * 8b. Multi-stream decoding: two acoustic models at once (csrc/ms_kernels.hip, csrc/multistream.cpp)
+ *    replaces DistribMultiStream (asr/gaussian/distribBasic.h:135-158), DistribMap (distribBasic.h:390-408, distribBasic.cc:326-376) and
+ *    DistribSetMultiStream (distribBasic.cc:381-417).  Every state's cost is
+ *        float(audioWeight * double(audio score) + videoWeight * double(video score))         (distribBasic.h:148-152)
+ *    -- two fp64 products, one fp64 sum, one rounding, no fused multiply-add -- where the video state of audio state `name` is
+ *    videoSet.find(name), or videoSet.find(map.mapped(name)) with a map; many audio states may share one video state.  The two streams need not
+ *    be audio and video: MFCC plus warped-MVDR cepstra, array output plus a close-talk channel.  More than two streams, weight estimation and
+ *    training through a multi-stream set are not built.
+ * ===================================================================================== */
+/* DistribMap (distribBasic.h:390-408): names of the first model -> names of the second.  Host only, needs no device.  The reference reads names into
+ * char[20] (distribBasic.cc:338-339): a name of more than 19 characters is DSR_E_PARAMETER on add, read and write instead of an overflow. */
+typedef struct dsr_distribmap dsr_distribmap;
+dsr_status dsr_distribmap_create(dsr_distribmap** out);
+void       dsr_distribmap_destroy(dsr_distribmap*);
+dsr_status dsr_distribmap_add(dsr_distribmap*, const char* from, const char* to);                /* distribBasic.h:398: a later add overwrites */
+/* distribBasic.cc:349-357: DSR_E_INDEX "No mapping for %s"; *to is valid until the map changes */
+dsr_status dsr_distribmap_mapped(const dsr_distribmap*, const char* name, const char** to);
+int        dsr_distribmap_size(const dsr_distribmap*);
+/* distribBasic.cc:326-347, 359-376 with read_string / write_string (btk/common/mach_ind_io.cc:490-500, 1009-1021): a big-endian int32 count, then
+ * per pair two strings, each a big-endian int16 length and length + 1 bytes, in std::map key order.  read clears the map first.  An empty file
+ * name is DSR_E_ERROR "Distribution map file name is null.", a file that cannot be opened DSR_E_IO. */
+dsr_status dsr_distribmap_read(dsr_distribmap*, const char* fileName);
+dsr_status dsr_distribmap_write(const dsr_distribmap*, const char* fileName);
+
+/* The combiner of two models' score matrices.  create resolves every audio name to the index of its video state once -- the constructors'
+ * loops, distribBasic.cc:385-391, 400-409: DSR_E_KEY for a name the video model lacks, DSR_E_INDEX for a name the map lacks (map NULL: by name)
+ * -- and keeps the table [KA] on the device.  Default weights of the reference: 0.95 / 0.05 (distribBasic.h:137); they need not sum to one. */
+typedef struct dsr_ms dsr_ms;
+dsr_status dsr_ms_create(const dsr_gmm* audio, const dsr_gmm* video, const dsr_distribmap* map, double audioWeight, double videoWeight, dsr_ms** out);
+void       dsr_ms_destroy(dsr_ms*);
+dsr_status dsr_ms_set_weights(dsr_ms*, double audioWeight, double videoWeight);                   /* distribBasic.h:142-145, for the next combine */
+dsr_status dsr_ms_get_weights(const dsr_ms*, double* audioWeight, double* videoWeight);           /* distribBasic.h:140-141 */
+dsr_status dsr_ms_table(const dsr_ms*, int32_t* table /* host [KA] */);
+/* DistribMultiStream::_score (distribBasic.h:148-152) for N frames x KA states: sA_dev [N][KA], sV_dev [N][KV] fp32 costs (dsr_gmm_score of the two
+ * models) -> out_dev [N][KA].  out_dev may be sA_dev itself; otherwise it is disjoint from both inputs, and it never aliases sV_dev.  N == 0 does
+ * nothing. */
+dsr_status dsr_ms_combine(dsr_ms*, const float* sA_dev, const float* sV_dev, int64_t N, float* out_dev, void* stream);
+/* Which k_ms_combine the call launches, a pure function of the shapes and of whether sA_dev and out_dev are both 16-byte aligned; the launch asks
+ * the same helper.  rowsPerTile consecutive rows are one workgroup's tile, ldsBytes its dynamic LDS.  Needs no device. */
+enum { DSR_MS_VECTOR_LDS = 0,          /* KA % 4 == 0 and aligned: float4 audio accesses, the tile's video rows in LDS */
+       DSR_MS_SCALAR_LDS = 1,          /* any KA, any 4-byte alignment: 4-byte audio accesses, the video rows still in LDS */
+       DSR_MS_GATHER = 2 };            /* 4 KV > DSR_MS_LDS_BUDGET, one video row alone exceeds the budget: sV[n][map[k]] read from memory */
+enum { DSR_MS_LDS_BUDGET = 32768 };    /* bytes of LDS a tile's video rows may take */
+dsr_status dsr_ms_combine_path(int KA, int KV, int aligned16, int* path, int* rowsPerTile, int64_t* ldsBytes);
+
+/* DistribSetMultiStream(audioDistSet, videoDistSet[, distribMap], audioWeight, videoWeight) (distribBasic.cc:381-410) as a dsr_distribset that every
+ * entry of section 8 accepts.  ndists / find / name are the audio set's; reset_cache / reset_feature reach both children; score(distX, frameX)
+ * pulls frame frameX of BOTH children through the stream protocol (DSR_E_ITERATOR when either stream has ended, DSR_E_INDEX out of order) and
+ * combines the two rows with dsr_ms_combine's kernel; decode_stream materialises both streams, scores T = min(T_audio, T_video) frames of each in
+ * the child's own mode, combines on the device in place and decodes (T == 0: DSR_E_ITERATOR); gamma_probs_dist uses the combined matrix.  Each
+ * child keeps its own feature stream, dimension and scoring mode.  The children are plain sets (DSR_E_TYPE otherwise); the new set retains them,
+ * destroying it releases them, and they stay usable on their own.  The constructor errors are dsr_ms_create's. */
+dsr_status dsr_distribset_create_multistream(dsr_distribset* audioSet, dsr_distribset* videoSet, const dsr_distribmap* map /* NULL: by name */,
+                                             double audioWeight, double videoWeight, dsr_distribset** out);
+/* DistribSetMultiStream::setWeights (distribBasic.cc:412-417); DSR_E_TYPE on a plain set */
+dsr_status dsr_distribset_set_weights(dsr_distribset*, double audioWeight, double videoWeight);
+dsr_status dsr_distribset_get_weights(const dsr_distribset*, double* audioWeight, double* videoWeight);
+
+/* =====================================================================================
  * 9. GMM training: ML / MMI accumulation, updates, accumulator files
  *    replaces CodebookTrain / CodebookSetTrain (asr/train/codebookTrain.cc, "cT"), DistribTrain / DistribSetTrain / AccMap
  *    (asr/train/distribTrain.cc, "dT") for the diagonal 1:1 models dsr_gmm holds.  One item = DistribTrain::accumulate(frameX, factor)

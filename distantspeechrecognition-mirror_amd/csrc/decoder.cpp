@@ -284,7 +284,8 @@ static void ensure_scratch(dsr_decoder* d, int slots, int Tmax, int arenas)
   const dsr_decoder_cfg& c = d->cfg;
   long arena = c.arenaTokens > 0 ? (long) c.arenaTokens : (long) 8192 * (long) (Tmax + 2);
   if (arena > 0x7FFFFFF0L) arena = 0x7FFFFFF0L;
-  if (slots <= d->nSlots && arena <= d->arenaCap && (size_t) (arenas > slots ? arenas : slots) * (size_t) arena <= d->d_arena.n) return;
+  // (the kernel strides the arenas, and sizes a sliced batch's pool, by d->arenaCap -- the largest arena so far, not this batch's: that is what has to fit)
+  if (slots <= d->nSlots && arena <= d->arenaCap && (size_t) (arenas > slots ? arenas : slots) * (size_t) d->arenaCap <= d->d_arena.n) return;
   if (slots < d->nSlots) slots = d->nSlots;
   if (arena < d->arenaCap) arena = d->arenaCap;
   const size_t S = (size_t) slots;

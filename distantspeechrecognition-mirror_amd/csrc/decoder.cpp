@@ -489,6 +489,12 @@ static void report_profile(const long long* prof, int slots)
     double m1 = 0, m2 = 0, mAll = 0; for (int s2 = 0; s2 < slots; s2++) { m1 += (double) hp[(size_t) s2 * kProfN + 46]; m2 += (double) hp[(size_t) s2 * kProfN + 47]; mAll += (double) hp[(size_t) s2 * kProfN + 32 + 3]; }
     if (mAll > 0) fprintf(stderr, "[dsr viterbi prof] memory-path frames: %.0f, of them %.1f %% with at most 28672 placements, %.1f %% with at most 32767\n", mAll, 100.0 * m1 / mAll, 100.0 * m2 / mAll);
   }
+  {                                                             // the epsilon hops behind the first (tick p31), per wave and placement of P3 (k_viterbi: s_hop)
+    double h[6] = {0}; for (int s2 = 0; s2 < slots; s2++) for (int i = 0; i < 6; i++) h[i] += (double) hp[(size_t) s2 * kProfN + 48 + i];
+    if (h[0] > 0) fprintf(stderr, "[dsr viterbi prof] hops behind the first: %.0f wave-placements, %.1f %% with a path of two or more hops, %.1f %% load hop costs, %.1f %% run the hop loop; "
+                                  "%.3f hop iterations per wave-placement for %.3f hops per lane (x 64: %.2f)\n",
+                          h[0], 100.0 * h[1] / h[0], 100.0 * h[2] / h[0], 100.0 * h[3] / h[0], h[4] / h[0], h[5] / h[0] / 64.0, h[5] / h[0]);
+  }
   fprintf(stderr, "[dsr viterbi prof] busy us per slot: mean %.0f min %.0f max %.0f\n", tsum / slots, tmin, tmax);
   if (slots >= 64 && slots % 8 == 0) {                       // by XCD (workgroup i runs on XCD i mod 8): how even the eight queues of the time-sliced decode come out
     double bx[8] = {0}; for (int s2 = 0; s2 < slots; s2++) { double t = 0.0; for (int i = 0; i < 32; i++) if (i != 15) t += (double) hp[(size_t) s2 * kProfN + i]; bx[s2 & 7] += t / 100.0; }

@@ -211,11 +211,15 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
   // profiling build: the frames by size class -- at most 8 192 placements (all in registers), up to 12 288, more (register path), memory path: frames [0..3], ticks [4..7], placements [8..11]
   // [12], [13]: register-path frames that started laid out by the frame before / that ran P1 and P2; [14], [15]: memory-path frames of at most 28 672 / 32 767 placements
   __shared__ long long s_hist[PROF ? 16 : 1]; __shared__ long long s_tfr;
+  // profiling build: the hops of an epsilon path behind the first (tick p31), counted per wave and placement of P3: [0] wave-placements, [1] those with a path of two or more hops,
+  // [2] those that load hop costs (three or more hops), [3] those that run the generic hop loop, [4] hop iterations the waves execute, [5] hops their lanes need
+  __shared__ unsigned long long s_hop[PROF ? 8 : 1];
   // per-utterance statistics and the cold loop state (thread 0 updates them once per frame; they used to ride in scalar registers through every phase)
   __shared__ long long s_stat[3];    // activeHypos, placements, registerFrames (low word) | those of them that started laid out (high word)
   __shared__ int s_maxActive; __shared__ unsigned s_tag; __shared__ long long s_latOff;
   if (PROF && threadIdx.x < 32) s_prof[threadIdx.x] = 0;
   if (PROF && threadIdx.x < 16) s_hist[threadIdx.x] = 0;
+  if (PROF && threadIdx.x < 8) s_hop[threadIdx.x] = 0ull;
 #define TICK(ix) do { if (PROF && tid == 0) { const long long tn = (long long) wall_clock64(); s_prof[ix] += tn - s_tlast; s_tlast = tn; } } while (0)
   constexpr int nthr = kThreads, nw = kWaves;
   __shared__ int s_u, s_seg, s_help; __shared__ long long s_chunk;
@@ -540,49 +544,95 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
               xr[i] = *at32<int4>(xrecD, (uint32_t) rec8[i] * 32u); xl[i] = *at32<double2>(xrecD, (uint32_t) rec8[i] * 32u + 16u);
             }
             if (PROF) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); TICK(28); }
+            // The epsilon path (decoder.h:979-983) of both placements ahead of everything else of them, in one basic block: hops 2 to 4 are computed for every lane and
+            // dropped by select where the path is shorter, as the first hop is.  The costs of hops 2.. of a path of three or more hops are loaded here for both placements,
+            // as soon as the records are there, and first used behind the first hops (a two-hop path has its second cost in p2).  pls: hops whose costs are in
+            // p2 / pathCost (0: slot beyond the frame, or a path of more than 14 hops -- those are walked through the arc arrays below).
+            float hc[kB][3]; int pls[kB]; bool more[kB];
+#pragma unroll
+            for (int i = 0; i < kB; i++) {
+              const int c = (g8 + i) * nthr + tq; const uint32_t xmeta = (uint32_t) xr[i].y;
+              const int pl = (c < C) ? (int) (xmeta & 0xFFFFu) : 0;
+              pls[i] = (xmeta & 0x80000000u) ? 0 : pl; more[i] = pl > 4;
+              // (hops 3 and 4 of a shorter path are dropped below whatever their costs: p2 rather than a constant, which would draw the conversions -- and a wait -- into the branch)
+              hc[i][0] = hc[i][1] = hc[i][2] = __int_as_float(xr[i].w);
+              if (pls[i] > 2) {
+                const uint32_t o = (uint32_t) xr[i].w * 4u;
+                hc[i][0] = *at32<float>(pathCost, o); hc[i][1] = *at32<float>(pathCost, o + 4u); hc[i][2] = *at32<float>(pathCost, o + (pls[i] > 3 ? 8u : 4u));
+              }
+            }
+            if (PROF) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); TICK(31); }
+#pragma unroll
+            for (int i = 0; i < kB; i++) {
+              const uint32_t xmeta = (uint32_t) xr[i].y; const bool tsil = (ek8[i] >> 29) & 1u;
+              // selects in place of branches: the additions that may not apply are computed and dropped (same values, one
+              // basic block -- the scalar operands are fetched once per placement instead of once per branch)
+              float lmNode;                                                    // (every hop ends in a float: the node's lm stays in the placement's own register)
+              {                                                                // first epsilon hop: its cost travels with the record
+                double l = __dadd_rn((double) lm8[i], xl[i].y);
+                if (!NP) {
+                  const double l1 = __dadd_rn(l, lsPen); l = (xmeta & 0x20000u) ? l1 : l;
+                  const double l2 = __dadd_rn(l, lsSil); l = (sil0 && (prevNull0 || !tsil)) ? l2 : l;   // prevIn != silenceX <=> the token's edge was no silence edge
+                }
+                lmNode = (xmeta & 0xFFFFu) ? (float) l : lm8[i];
+              }
+              if (PROF) {                                                      // what the hops behind the first cost this wave (s_hop), and their own tick
+                unsigned long long iters = 0ull, need = 0ull; const int pl = more[i] ? (int) (xmeta & 0xFFFFu) : pls[i];
+                for (int k = 1; k < 0x10000; k++) { const unsigned long long b = __ballot(pl > k); if (!b) break; if (k > 3) iters++; need += (unsigned long long) __popcll(b); }
+                const unsigned long long act = __ballot((g8 + i) * nthr + tq < C); const bool loads = __ballot(pls[i] > 2) != 0ull;
+                if (act && lq == __ffsll((long long) act) - 1) {
+                  atomicAdd(&s_hop[0], 1ull); if (need) { atomicAdd(&s_hop[1], 1ull); atomicAdd(&s_hop[5], need); }
+                  if (loads) atomicAdd(&s_hop[2], 1ull);
+                  if (iters) { atomicAdd(&s_hop[3], 1ull); atomicAdd(&s_hop[4], iters); }
+                }
+                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); TICK(29);
+              }
+#pragma unroll
+              for (int h = 1; h < 4; h++) {                                    // (the edge before is an epsilon edge: no silence penalty possible here)
+                double l = __dadd_rn((double) lmNode, __dmul_rn(lmS, (double) hc[i][h - 1]));
+                if (!NP) { const double l1 = __dadd_rn(l, lsPen); l = ((xmeta >> (17 + h)) & 1u) ? l1 : l; }
+                lmNode = (pls[i] > h) ? (float) l : lmNode;
+              }
+              if (PROF) TICK(31);
+              lm8[i] = lmNode;
+            }
+            bool anyMore = false;
+#pragma unroll
+            for (int i = 0; i < kB; i++) anyMore = anyMore || more[i];
+            if (__any(anyMore)) {                                              // a path of more than four hops in the wave: its further hops, one independent load each
+#pragma unroll
+              for (int i = 0; i < kB; i++) if (more[i]) {
+                const uint32_t xmeta = (uint32_t) xr[i].y; const int plen = (int) (xmeta & 0xFFFFu), xp2 = xr[i].w;
+                double lmNode = (double) lm8[i];
+                if (!(xmeta & 0x80000000u)) {
+                  for (int h = 4; h < plen; h++) {
+                    double l = __dadd_rn(lmNode, __dmul_rn(lmS, (double) pathCost[xp2 + h - 1]));
+                    if (!NP && ((xmeta >> (17 + h)) & 1u)) l = __dadd_rn(l, lsPen);
+                    lmNode = (double) (float) l;
+                  }
+                } else {
+                  const int* pp = ka->G.path + ka->G.xpathOff[rec8[i]];
+                  for (int h = 1; h < plen; h++) {
+                    const int a = pp[h];
+                    double l = __dadd_rn(lmNode, __dmul_rn(lmS, (double) ka->G.arcCost[a]));
+                    if (!NP && ka->G.arcOut[a] != 0) l = __dadd_rn(l, lsPen);
+                    lmNode = (double) (float) l;
+                  }
+                }
+                lm8[i] = (float) lmNode;
+              }
+            }
+            if (PROF) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); TICK(31); }
 #pragma unroll
             for (int i = 0; i < kB; i++) {
               const int c = (g8 + i) * nthr + tq;
               const bool tsil = (ek8[i] >> 29) & 1u; ek8[i] &= 0x1FFFu;       // (taken out of ek here, behind the loads: a flag per placement held across them cost scratch memory)
               if (c < C) {
-                const int xdist = xr[i].x; const uint32_t xmeta = (uint32_t) xr[i].y; const int xdst = xr[i].z, xp2 = xr[i].w;
-                const int plen = (int) (xmeta & 0xFFFFu);
-                // selects in place of branches: the additions that may not apply are computed and dropped (same values, one
-                // basic block -- the scalar operands are fetched once per placement instead of once per branch)
-                const double lm0 = (double) lm8[i];
-                const bool has = plen != 0;
-                double lmNode;
-                {                                                              // first epsilon hop (decoder.h:979-983): its cost travels with the record
-                  double l = __dadd_rn(lm0, xl[i].y);
-                  if (!NP) {
-                    const double l1 = __dadd_rn(l, lsPen); l = (xmeta & 0x20000u) ? l1 : l;
-                    const double l2 = __dadd_rn(l, lsSil); l = (sil0 && (prevNull0 || !tsil)) ? l2 : l;   // prevIn != silenceX <=> the token's edge was no silence edge
-                  }
-                  lmNode = has ? (double) (float) l : lm0;
-                }
+                const int xdist = xr[i].x; const uint32_t xmeta = (uint32_t) xr[i].y; const int xdst = xr[i].z;
+                const bool has = (xmeta & 0xFFFFu) != 0u;
                 const bool pnull = has ? false : prevNull0;
                 const bool pinSil = has ? sil0 : tsil;                         // after an epsilon hop the edge input is 0
-                if (plen > 1) {
-                  if (!(xmeta & 0x80000000u)) {
-                    float hc0 = 0.0f, hc1 = 0.0f, hc2 = 0.0f;                  // three and four hops (and the head of longer paths): their costs in flight together
-                    if (plen > 2) { const float* pc = pathCost + xp2; hc0 = pc[0]; hc1 = pc[1]; hc2 = pc[(plen > 3) ? 2 : 1]; }
-                    for (int h = 1; h < plen; h++) {                           // hop costs: inline (two hops) or one independent load per hop
-                      const float ch = (plen == 2) ? __int_as_float(xp2) : (h == 1 ? hc0 : h == 2 ? hc1 : h == 3 ? hc2 : pathCost[xp2 + h - 1]);
-                      double l = __dadd_rn(lmNode, __dmul_rn(lmS, (double) ch));
-                      if (!NP && ((xmeta >> (17 + h)) & 1u)) l = __dadd_rn(l, lsPen);
-                      lmNode = (double) (float) l;                              // (the edge before is an epsilon edge: no silence penalty possible here)
-                    }
-                  } else {
-                    const int* pp = ka->G.path + ka->G.xpathOff[rec8[i]];
-                    for (int h = 1; h < plen; h++) {
-                      const int a = pp[h];
-                      double l = __dadd_rn(lmNode, __dmul_rn(lmS, (double) ka->G.arcCost[a]));
-                      if (!NP && ka->G.arcOut[a] != 0) l = __dadd_rn(l, lsPen);
-                      lmNode = (double) (float) l;
-                    }
-                  }
-                }
-                double lm = __dadd_rn(lmNode, xl[i].x);
+                double lm = __dadd_rn((double) lm8[i], xl[i].x);
                 if (!NP) { const double lm1 = __dadd_rn(lm, lsPen); lm = (xmeta & 0x10000u) ? lm1 : lm; }
                 const bool silArc = ((uint32_t) (xdist + 1) == silenceX);
                 if (!NP) { const double lm2 = __dadd_rn(lm, lsSil); lm = (silArc && (pnull || !pinSil)) ? lm2 : lm; }
@@ -1388,6 +1438,7 @@ __global__ __launch_bounds__(kThreads) void k_viterbi(const VitArgs argsInKernar
   if (tid == 0) ka->D.tags[slot] = s_tag;
   if (PROF && tid < 32) ka->D.prof[slot * kProfN + tid] = s_prof[tid];
   if (PROF && tid < 16) ka->D.prof[slot * kProfN + 32 + tid] = s_hist[tid];
+  if (PROF && tid < 8) ka->D.prof[slot * kProfN + 48 + tid] = (long long) s_hop[tid];
 #undef TICK
 #undef RELOAD
 #undef TOKA

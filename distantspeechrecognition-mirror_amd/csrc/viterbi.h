@@ -15,7 +15,9 @@ struct TokB { int32_t node; int32_t cnt; };                           // cnt: nu
 // fixed when the decoder is created).  Exactness: decoder.cpp is built with -ffp-contract=off, and an IEEE-754 double product of the same two operands, rounded to nearest,
 // is the device's __dmul_rn(lmScale, (double) cost) bit for bit -- the expansion adds the very double it used to compute per placement.
 // eps1: cost of the first epsilon hop (meta bit17: it has an output).  Further hops (meta bits 18..30: hop h = 1..13 has an output):
-// a two-hop path carries the second cost in p2 (float bits, scaled on the device), longer ones the offset of their hop costs in GraphDev::pathCost;
+// a two-hop path carries the second cost in p2 (float bits, scaled on the device), longer ones the offset of their hop costs in GraphDev::pathCost
+// (floats, hops 2.. in order; entry 0 belongs to no path).  The expansion loads the costs of hops 2 to 4 for both placements of a pair as soon as the records
+// are there and applies them in straight line, dropped by select where the path is shorter; only a wave that holds a path of more than four hops loops over the rest;
 // meta bit31: more than 14 hops, walked through the path/arc arrays instead.
 // The cold record is what the new token needs (P6 gathers it by record): the destination and its own expansion range.
 struct XRecD { int32_t dist; uint32_t meta; int32_t dst; int32_t p2; double lmCost; double lmEps1; };
@@ -36,7 +38,7 @@ static_assert(sizeof(TokA) == 16 && sizeof(TokB) == 8 && sizeof(XRecD) == 32 && 
 
 static constexpr int kThreads = 1024;             // 16 waves per CU at 128 VGPRs (measured in round 2: 512 x 256 VGPRs 22 % slower, 768 x 168 VGPRs 4 % slower; two 512-thread workgroups per CU 1.2x slower)
 static constexpr int kFastC = 24576;               // most placements per frame on the register path (those beyond kFastK per thread are parked in memory)
-static constexpr int kProfN = 48;                  // profiling words per slot: 32 phase ticks + 12 of the size-class histogram + 4 frame counts (laid out / through P1 and P2, memory-path frames below two sizes)
+static constexpr int kProfN = 56;                  // profiling words per slot: 32 phase ticks + 12 of the size-class histogram + 4 frame counts (laid out / through P1 and P2, memory-path frames below two sizes) + 8 hop counters (k_viterbi: s_hop)
 static constexpr int kSideLds = 496;               // later arrivals kept in LDS (the rest go to memory)
 
 struct GraphDev {

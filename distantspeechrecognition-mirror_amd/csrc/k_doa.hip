@@ -170,7 +170,7 @@ void build_table(dsr_doa& s)                                 // _calcSteeringUni
 void upload_table(dsr_doa& s, hipStream_t st)
 {
   if (!s.dDirty) return;
-  const int F = s.M / 2 + 1, C = s.C, nT = s.nTheta; s.NT = (nT + 15) / 16; s.KS = (C + 3) / 4;
+  const int F = s.M / 2 + 1, C = s.C, nT = s.nTheta; s.NT = srp_tiles(nT); s.KS = srp_ksteps(C);
   std::vector<double2> h((size_t) F * s.NT * s.KS * 64, make_double2(0.0, 0.0));
   for (int f = 0; f <= s.tblFbinMax; f++)
     for (int th = 0; th < s.NT; th++)
@@ -185,13 +185,12 @@ void upload_table(dsr_doa& s, hipStream_t st)
 }
 
 template <int TG>
-void launch_srp(const dsr_doa& s, const float* X, const int* nf, int U, int Tmax, double* rp, float* en, float* Y, hipStream_t st)
+void launch_srp(const dsr_doa& s, const SrpCell& c, const float* X, const int* nf, int U, int Tmax, double* rp, float* en, float* Y, hipStream_t st)
 {
-  const int BC = bin_chunk(s.C), F = s.M / 2 + 1;
-  const size_t lds = (size_t) s.C * FB * bin_pitch(BC) * sizeof(float2);
+  const int F = s.M / 2 + 1;
   dim3 grid((s.NT + TG - 1) / TG, (Tmax + FB - 1) / FB, U);
-  launch(k_doa_srp<TG>, grid, dim3(256), lds, st, (const float2*) X, nf, s.dW.p, s.C, Tmax, F, s.M / 2, s.fbinMin, s.fbinMax,
-                     s.nTheta, s.NT, s.KS, BC, rp, en, (float2*) Y);
+  launch(k_doa_srp<TG>, grid, dim3(256), c.ldsBytes, st, (const float2*) X, nf, s.dW.p, s.C, Tmax, F, s.M / 2, s.fbinMin, s.fbinMax,
+                     s.nTheta, s.NT, c.KS, c.BC, rp, en, (float2*) Y);
 }
 
 }  // namespace
@@ -201,10 +200,10 @@ namespace dsr {
 void doa_launch_rp(dsr_doa& s, const float* X, const int* nf, int U, int Tmax, double* rp, float* en, float* Y, hipStream_t st)
 {
   upload_table(s, st);
-  const int ng = s.NT;
-  if (ng >= 4) launch_srp<4>(s, X, nf, U, Tmax, rp, en, Y, st);
-  else if (ng >= 2) launch_srp<2>(s, X, nf, U, Tmax, rp, en, Y, st);
-  else launch_srp<1>(s, X, nf, U, Tmax, rp, en, Y, st);
+  const SrpCell c = doa_srp_cell(s.nTheta, s.C);             // what dsr_doa_srp_cell reports
+  if (c.TG == 4) launch_srp<4>(s, c, X, nf, U, Tmax, rp, en, Y, st);
+  else if (c.TG == 2) launch_srp<2>(s, c, X, nf, U, Tmax, rp, en, Y, st);
+  else launch_srp<1>(s, c, X, nf, U, Tmax, rp, en, Y, st);
 }
 
 void doa_launch_acc(const double* rp, const float* en, const int* nf, int U, int Tmax, int nUnits, float thr, double* acc, hipStream_t st)
@@ -287,6 +286,16 @@ dsr_status dsr_doa_look_delays(dsr_doa* s, double theta, double* delays)
 { return guard([&] { if (!s || !delays) throw Error(DSR_E_PARAMETER, "null argument"); look_delays(*s, theta, delays); }); }
 dsr_status dsr_doa_build_table(dsr_doa* s)
 { return guard([&] { if (!s) throw Error(DSR_E_PARAMETER, "null argument"); build_table(*s); }); }
+dsr_status dsr_doa_srp_cell(dsr_doa* s, int cell[3], int64_t* ldsBytes)
+{
+  return guard([&] {
+    if (!s || !cell) throw Error(DSR_E_PARAMETER, "null argument");
+    build_table(*s);
+    const SrpCell c = doa_srp_cell(s->nTheta, s->C);
+    cell[0] = c.TG; cell[1] = c.BC; cell[2] = c.KS;
+    if (ldsBytes) *ldsBytes = (int64_t) c.ldsBytes;
+  });
+}
 dsr_status dsr_doa_steering(dsr_doa* s, int thetaX, double* out, size_t outDoubles)
 {
   return guard([&] {

@@ -294,23 +294,27 @@ int beams_bin_chunk(int C)                                   // the staged chunk
 
 constexpr size_t BEAMS_LDS = 48 * 1024;                      // the VALU kernel's staged conj(v): CC channels x NBT beams x F bins
 
+int valu_chunk(int NBT, int F, int C)                        // CC: the channels whose staged conj(v) (NBT rows x F bins each) fit BEAMS_LDS at a time
+{
+  int CC = (int) (BEAMS_LDS / ((size_t) NBT * F * sizeof(double2))); if (CC > C) CC = C;
+  if (CC < 1) throw Error(DSR_E_DIMENSION, "%d beams x %d bins do not fit the kernel's %zu bytes of LDS", NBT, F, BEAMS_LDS);
+  return CC;
+}
+size_t valu_lds_bytes(int NBT, int F, int CC) { return (size_t) CC * NBT * F * sizeof(double2); }
+
 template <int NBT, int E>
 void launch_beams_valu(const dsr_sph& s, const float* X, const int* nf, int U, int Tmax, int NB, float* Y, hipStream_t st)
 {
-  const int F = s.M / 2 + 1;
-  int CC = (int) (BEAMS_LDS / ((size_t) NBT * F * sizeof(double2))); if (CC > s.C) CC = s.C;
-  if (CC < 1) throw Error(DSR_E_DIMENSION, "%d beams x %d bins do not fit the kernel's %zu bytes of LDS", NBT, F, BEAMS_LDS);
-  const size_t lds = (size_t) CC * NBT * F * sizeof(double2);
-  launch(k_sph_beams_valu<NBT, E>, dim3(cdiv((long) Tmax * F, 256 * E), U), dim3(256), lds, st, (const float2*) X, nf, s.dV.p, s.C, Tmax, F, CC, NB,
-                     (float2*) Y);
+  const int F = s.M / 2 + 1, CC = valu_chunk(NBT, F, s.C);
+  launch(k_sph_beams_valu<NBT, E>, dim3(cdiv((long) Tmax * F, 256 * E), U), dim3(256), valu_lds_bytes(NBT, F, CC), st, (const float2*) X, nf, s.dV.p,
+                     s.C, Tmax, F, CC, NB, (float2*) Y);
 }
 
 template <int BCT>
 void launch_beams_mfma(const dsr_sph& s, const float* X, const int* nf, int U, int Tmax, int NB, float* Y, hipStream_t st)
 {
-  const size_t lds = (size_t) s.C * FB * bin_pitch(BCT) * sizeof(float2);
-  launch(k_sph_beams_mfma<BCT>, dim3((Tmax + FB - 1) / FB, U), dim3(256), lds, st, (const float2*) X, nf, s.dV.p, s.C, Tmax, s.M / 2 + 1, NB,
-                     (s.C + 3) / 4, (float2*) Y);
+  launch(k_sph_beams_mfma<BCT>, dim3((Tmax + FB - 1) / FB, U), dim3(256), srp_lds_bytes(s.C, BCT), st, (const float2*) X, nf, s.dV.p, s.C, Tmax,
+                     s.M / 2 + 1, NB, srp_ksteps(s.C), (float2*) Y);
 }
 
 int valu_rows(int NB) { return NB <= 4 ? NB : NB <= 8 ? 8 : 16; }   // the VALU kernel's instantiations: 1..4 exact, above that zero-padded rows
@@ -319,7 +323,7 @@ void upload_beams(dsr_sph& s, int NB, int path, hipStream_t st)   // conj(v): la
 {
   const int layout = path == 1 ? 0 : valu_rows(NB);
   if (!s.dVDirty && s.dVLayout == layout) return;
-  const int F = s.M / 2 + 1, C = s.C, KS = (C + 3) / 4;
+  const int F = s.M / 2 + 1, C = s.C, KS = srp_ksteps(C);
   std::vector<double2> h;
   if (layout == 0) {
     h.assign((size_t) F * KS * 64, make_double2(0.0, 0.0));
@@ -343,6 +347,9 @@ void upload_beams(dsr_sph& s, int NB, int path, hipStream_t st)   // conj(v): la
   s.dV.upload(h, st); s.dVLayout = layout; s.dVDirty = false;
 }
 
+int fused_dim_tiles(int dim) { return dim <= 16 ? 1 : dim <= 32 ? 2 : 4; }           // DT: the fused kernel's 16-row eigenbeam tiles (rows past dim zero)
+int fused_tile_group(int NT) { return NT >= 8 ? 8 : NT >= 4 ? 4 : NT >= 2 ? 2 : 1; }   // TG: its unit tiles per workgroup
+
 const char* forced_path()
 {
   const char* e = getenv("DSR_SPH_SRP_PATH");
@@ -352,7 +359,7 @@ const char* forced_path()
 void upload_s(dsr_sph& s, hipStream_t st)                    // S [dim][C] (apply) and Sp [DT][KS][64] (the fused kernel's A operand)
 {
   if (!s.dSDirty) return;
-  const int D = s.dim, C = s.C; s.DT = D <= 16 ? 1 : D <= 32 ? 2 : 4; s.KS = (C + 3) / 4;   // the kernel's dim tiles: 1, 2 or 4 (rows past dim zero)
+  const int D = s.dim, C = s.C; s.DT = fused_dim_tiles(D); s.KS = srp_ksteps(C);
   std::vector<double2> h((size_t) D * C), hp((size_t) s.DT * s.KS * 64, make_double2(0.0, 0.0));
   for (int d = 0; d < D; d++)
     for (int c = 0; c < C; c++) h[(size_t) d * C + c] = make_double2(s.SH[(size_t) d * C + c].real(), s.SH[(size_t) d * C + c].imag());
@@ -368,7 +375,7 @@ void upload_s(dsr_sph& s, hipStream_t st)                    // S [dim][C] (appl
 void upload_fused_table(dsr_sph& s, hipStream_t st)
 {
   if (!s.dWDirty) return;
-  const int F = s.M / 2 + 1, D = s.dim, nU = units(s); s.NT = (nU + 15) / 16;
+  const int F = s.M / 2 + 1, D = s.dim, nU = units(s); s.NT = srp_tiles(nU);
   const int DT4 = s.DT;
   std::vector<double2> h((size_t) F * s.NT * DT4 * 256, make_double2(0.0, 0.0));
   for (int f = 0; f <= s.tblFbinMax; f++)
@@ -385,22 +392,21 @@ void upload_fused_table(dsr_sph& s, hipStream_t st)
 }
 
 template <int TG, int DT>
-void launch_fused(const dsr_sph& s, const float* X, const int* nf, int U, int Tmax, double* rp, float* en, float* Y, hipStream_t st)
+void launch_fused(const dsr_sph& s, const SphSrpCell& c, const float* X, const int* nf, int U, int Tmax, double* rp, float* en, float* Y, hipStream_t st)
 {
-  const int BC = bin_chunk(s.C), F = s.M / 2 + 1;
-  const size_t lds = (size_t) s.C * FB * bin_pitch(BC) * sizeof(float2);
+  const int F = s.M / 2 + 1;
   dim3 grid((s.NT + TG - 1) / TG, (Tmax + FB - 1) / FB, U);
-  launch(k_sph_srp<TG, DT>, grid, dim3(256), lds, st, (const float2*) X, nf, s.dSp.p, s.dWp.p, s.C, Tmax, F, s.M / 2, s.fbinMin, s.fbinMax,
-                     units(s), s.NT, s.KS, BC, rp, en, (float2*) Y);
+  launch(k_sph_srp<TG, DT>, grid, dim3(256), c.ldsBytes, st, (const float2*) X, nf, s.dSp.p, s.dWp.p, s.C, Tmax, F, s.M / 2, s.fbinMin, s.fbinMax,
+                     units(s), s.NT, c.KS, c.BC, rp, en, (float2*) Y);
 }
 
 template <int DT>
-void launch_fused_tg(const dsr_sph& s, const float* X, const int* nf, int U, int Tmax, double* rp, float* en, float* Y, hipStream_t st)
+void launch_fused_tg(const dsr_sph& s, const SphSrpCell& c, const float* X, const int* nf, int U, int Tmax, double* rp, float* en, float* Y, hipStream_t st)
 {
-  if (s.NT >= 8) launch_fused<8, DT>(s, X, nf, U, Tmax, rp, en, Y, st);
-  else if (s.NT >= 4) launch_fused<4, DT>(s, X, nf, U, Tmax, rp, en, Y, st);
-  else if (s.NT >= 2) launch_fused<2, DT>(s, X, nf, U, Tmax, rp, en, Y, st);
-  else launch_fused<1, DT>(s, X, nf, U, Tmax, rp, en, Y, st);
+  if (c.TG == 8) launch_fused<8, DT>(s, c, X, nf, U, Tmax, rp, en, Y, st);
+  else if (c.TG == 4) launch_fused<4, DT>(s, c, X, nf, U, Tmax, rp, en, Y, st);
+  else if (c.TG == 2) launch_fused<2, DT>(s, c, X, nf, U, Tmax, rp, en, Y, st);
+  else launch_fused<1, DT>(s, c, X, nf, U, Tmax, rp, en, Y, st);
 }
 
 }  // namespace
@@ -439,6 +445,20 @@ int sph_srp_path(const dsr_sph& s)                           // 0 fused, 1 folde
   return (long) s.dim * (s.C + nU) >= (long) s.C * nU ? 1 : 0;
 }
 
+SphSrpCell sph_fused_cell(const dsr_sph& s)                  // the fused launch of s's table: what sph_srp_fused switches on and dsr_sph_srp_cell reports
+{
+  const int BC = bin_chunk(s.C);
+  return SphSrpCell{0, fused_tile_group(srp_tiles(units(s))), fused_dim_tiles(s.dim), BC, srp_ksteps(s.C), srp_lds_bytes(s.C, BC)};
+}
+
+SphBeamsCell sph_beams_cell(int NB, int C, int F)            // the launch of one dsr_sph_beams call: what sph_beams switches on and dsr_sph_beams_cell reports
+{
+  SphBeamsCell c{sph_beams_path_for(NB, F), 0, 0, 0, 0, 0};
+  if (c.kernel == 1) { c.BCT = beams_bin_chunk(C); c.KS = srp_ksteps(C); c.ldsBytes = srp_lds_bytes(C, c.BCT); }
+  else { c.rows = valu_rows(NB); c.CC = valu_chunk(c.rows, F, C); c.ldsBytes = valu_lds_bytes(c.rows, F, c.CC); }
+  return c;
+}
+
 void sph_apply(dsr_sph& s, const float* X, const int* nf, int U, int Tmax, float* Y, float* Fo, hipStream_t st)
 {
   upload_s(s, st);
@@ -452,13 +472,13 @@ void sph_beams(dsr_sph& s, const float* X, const int* nf, int U, int Tmax, int N
 {
   upload_beams(s, NB, path, st);
   if (path == 1) {
-    const int BC = beams_bin_chunk(s.C);
+    const int BC = sph_beams_cell(NB, s.C, s.M / 2 + 1).BCT;
     if (BC == 8) launch_beams_mfma<8>(s, X, nf, U, Tmax, NB, Y, st);
     else if (BC == 4) launch_beams_mfma<4>(s, X, nf, U, Tmax, NB, Y, st);
     else if (BC == 2) launch_beams_mfma<2>(s, X, nf, U, Tmax, NB, Y, st);
     else launch_beams_mfma<1>(s, X, nf, U, Tmax, NB, Y, st);
   } else {
-    switch (valu_rows(NB)) {
+    switch (sph_beams_cell(NB, s.C, s.M / 2 + 1).rows) {
     case 1: launch_beams_valu<1, 4>(s, X, nf, U, Tmax, NB, Y, st); break;
     case 2: launch_beams_valu<2, 4>(s, X, nf, U, Tmax, NB, Y, st); break;
     case 3: launch_beams_valu<3, 4>(s, X, nf, U, Tmax, NB, Y, st); break;
@@ -472,9 +492,10 @@ void sph_beams(dsr_sph& s, const float* X, const int* nf, int U, int Tmax, int N
 void sph_srp_fused(dsr_sph& s, const float* X, const int* nf, int U, int Tmax, double* rp, float* en, float* Y, hipStream_t st)
 {
   upload_s(s, st); upload_fused_table(s, st);
-  if (s.DT == 1) launch_fused_tg<1>(s, X, nf, U, Tmax, rp, en, Y, st);
-  else if (s.DT == 2) launch_fused_tg<2>(s, X, nf, U, Tmax, rp, en, Y, st);
-  else launch_fused_tg<4>(s, X, nf, U, Tmax, rp, en, Y, st);
+  const SphSrpCell c = sph_fused_cell(s);                    // c.DT is the s.DT the tables above were laid out for
+  if (c.DT == 1) launch_fused_tg<1>(s, c, X, nf, U, Tmax, rp, en, Y, st);
+  else if (c.DT == 2) launch_fused_tg<2>(s, c, X, nf, U, Tmax, rp, en, Y, st);
+  else launch_fused_tg<4>(s, c, X, nf, U, Tmax, rp, en, Y, st);
 }
 
 void sph_frame(const dsr_sph& s, const double* rp, const float* en, const int* nf, int U, int Tmax, double* nbRp, int* nbIdx, int* gated, hipStream_t st)

@@ -626,6 +626,20 @@ int dsr_sph_srp_path(dsr_sph* s)
   if (!s->tbl) { if (dsr_sph_build_table(s)) return -1; }
   try { return sph_srp_path(*s); } catch (const Error& e) { set_last_error(e.msg); return -1; }
 }
+dsr_status dsr_sph_srp_cell(dsr_sph* s, int cell[5], int64_t* ldsBytes)
+{
+  return guard([&] {
+    if (!s || !cell) throw Error(DSR_E_PARAMETER, "null argument");
+    build_table(*s);
+    SphSrpCell c = sph_fused_cell(*s);
+    if (sph_srp_path(*s) == 1) {                             // the folded table [units][C] through doa_launch_rp
+      const SrpCell l = doa_srp_cell(units(*s), s->C);
+      c = SphSrpCell{1, l.TG, 0, l.BC, l.KS, l.ldsBytes};
+    }
+    cell[0] = c.path; cell[1] = c.TG; cell[2] = c.DT; cell[3] = c.BC; cell[4] = c.KS;
+    if (ldsBytes) *ldsBytes = (int64_t) c.ldsBytes;
+  });
+}
 
 dsr_status dsr_sph_apply(dsr_sph* s, const float* X_dev, const int32_t* nframes_dev, int U, int Tmax, float* Y_dev, float* F_dev, void* stream)
 {
@@ -759,6 +773,18 @@ dsr_status dsr_sph_sensor_weights(dsr_sph* s, double* out, size_t outDoubles)
 int dsr_sph_beams_path(int NB)
 {
   try { return sph_beams_path(NB); } catch (const Error& e) { set_last_error(e.msg); return -1; }
+}
+dsr_status dsr_sph_beams_cell(int NB, int chanN, int bins, int cell[3], int64_t* ldsBytes)
+{
+  return guard([&] {
+    if (!cell) throw Error(DSR_E_PARAMETER, "null argument");
+    if (NB < 1 || NB > MAX_BEAMS) throw Error(DSR_E_DIMENSION, "%d beams (1..%d supported)", NB, MAX_BEAMS);
+    if (chanN < 1 || chanN > 128) throw Error(DSR_E_DIMENSION, "%d channels (1..128 supported)", chanN);
+    if (bins < 2) throw Error(DSR_E_DIMENSION, "%d bins", bins);
+    const SphBeamsCell c = sph_beams_cell(NB, chanN, bins);
+    cell[0] = c.kernel; cell[1] = c.kernel == 1 ? c.BCT : c.rows; cell[2] = c.kernel == 1 ? c.KS : c.CC;
+    if (ldsBytes) *ldsBytes = (int64_t) c.ldsBytes;
+  });
 }
 dsr_status dsr_sph_beam_pattern_n(double minTheta, double maxTheta, double minPhi, double maxPhi, double widthTheta, double widthPhi, int* nTheta, int* nPhi)
 {

@@ -51,6 +51,11 @@ inline int units(const dsr_sph& s) { return s.nTheta * s.nPhi; }
 int sph_beams_path(int NB);                                  // 0 VALU, 1 MFMA, as NB and DSR_SPH_BEAMS_PATH say
 int sph_beams_path_for(int NB, int F);                       // the kernel of one call: sph_beams_path unless the VALU kernel's table does not fit
 int sph_srp_path(const dsr_sph& s);                          // 0 fused, 1 folded, as the flop count and DSR_SPH_SRP_PATH say
+// the launches as the queries report them (dsr_sph_srp_cell, dsr_sph_beams_cell); the launchers switch on the same values
+struct SphSrpCell { int path, TG, DT, BC, KS; size_t ldsBytes; };             // path 0: k_sph_srp<TG, DT>; path 1: k_doa_srp<TG> on the folded table, DT 0
+struct SphBeamsCell { int kernel, rows, CC, BCT, KS; size_t ldsBytes; };      // kernel 0: k_sph_beams_valu<rows, .>, CC channels staged; 1: k_sph_beams_mfma<BCT>
+SphSrpCell sph_fused_cell(const dsr_sph& s);                 // needs the steering table's grid (units)
+SphBeamsCell sph_beams_cell(int NB, int C, int F);           // follows DSR_SPH_BEAMS_PATH; DSR_E_DIMENSION where a forced VALU table does not fit
 // Y [U][Tmax][F] = w^H (S X) with the weights in s.dLook, Fo (optional) [U][Tmax][F][dim] = S X; uploads S when it moved
 void sph_apply(dsr_sph& s, const float* X, const int* nf, int U, int Tmax, float* Y, float* Fo, hipStream_t st);
 // Y [U][NB][Tmax][F] = v_b^H X for the beams of s.V, on the kernel of `path`; uploads the vectors in that kernel's layout when they moved

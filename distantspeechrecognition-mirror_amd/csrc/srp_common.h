@@ -36,6 +36,17 @@ inline int bin_chunk(int C)
   for (int BC = 16; BC > 1; BC >>= 1) if (C * bin_pitch(BC) <= LDS_ROWS) return BC;   // C * pitch * FB * 8 bytes <= LDS_ROWS / 2 KB
   return 1;
 }
+// The launch shape of an SRP call, in one place: the uploads, the launches and the queries (dsr_doa_srp_cell, dsr_sph_srp_cell) all take it from here.
+inline int srp_tiles(int nUnits) { return (nUnits + 15) / 16; }          // NT: 16-unit row tiles, the last one zero padded
+inline int srp_ksteps(int C) { return (C + 3) / 4; }                     // KS: K steps of 4 channels, the last one masked
+inline size_t srp_lds_bytes(int C, int BC) { return (size_t) C * FB * bin_pitch(BC) * sizeof(float2); }   // the staged snapshots [C][FB][pitch]
+struct SrpCell { int TG, BC, KS; size_t ldsBytes; };                     // k_doa_srp<TG> (k_sph_srp<TG, DT>) staging BC bins a chunk
+inline int doa_tile_group(int NT) { return NT >= 4 ? 4 : NT >= 2 ? 2 : 1; }   // k_doa_srp's unit tiles per workgroup
+inline SrpCell doa_srp_cell(int nUnits, int C)
+{
+  const int BC = bin_chunk(C);
+  return SrpCell{doa_tile_group(srp_tiles(nUnits)), BC, srp_ksteps(C), srp_lds_bytes(C, BC)};
+}
 
 // The N-best of next() (beamformer.cc:3223-3245, modalBeamformer.cc:922-946) and of _getNBestHypothesesFromACCRP (beamformer.cc:2986-3025):
 // R descending, I the unit of each rank; an empty rank is rp -10e10, unit -1 (DOA (-pi, -pi)).  Strict >: on a tie the earlier unit wins.

@@ -14,7 +14,7 @@ from ._core import (C, os, re, np, _HERE, _LIBPATH, _HEADER, _SCALARS, _ctype_of
                     DecodeResult, vp, i32, i64, f32, f64, u32, _np, _ptr, _dev, _nf, _state, _batch)
 from .modulated import (FilterBank, FilterBankState, PrFilterBank, NormalFFTBank)
 from .beamformer import (Beamformer, calcDelaysPolar2, RLS_STATE_REGS, RLS_STATE_LDS, RLS_STATE_MEM, bf_rls_path, SubbandMMI, DoaSRP, _Sph,
-                         SphBeamformer, SphDoaSRP, SphTracker, PlaneWaveSim, MK_PR, MK_NRM, MK_EXIT_MAX_ITERATIONS, MK_EXIT_GRADIENT,
+                         SphBeamformer, SphDoaSRP, sph_beams_cell, SphTracker, PlaneWaveSim, MK_PR, MK_NRM, MK_EXIT_MAX_ITERATIONS, MK_EXIT_GRADIENT,
                          MK_EXIT_DIFFERENCE, MK_EXIT_NO_PROGRESS, MK_EXIT_EVAL_CAP, MK_EXIT_SKIPPED, MK_FRAMES_LDS, MK_FRAMES_STREAMED, MK_EVAL_CAP,
                          mk_path, MkBeamformer)
 from .localization import (Gcc, cctde, SearchGrid, mcc_check, MccLocalizer, MccCalculator)

@@ -251,6 +251,10 @@ class DoaSRP(Handle):
         out = np.zeros((self.M // 2 + 1, self.C), np.complex128)
         check(_core._lib.dsr_doa_steering(self.h, int(thetaX), _ptr(out), out.size * 2)); return out
 
+    def cell(self):
+        """-> ((TG, BC, KS), dynamic LDS bytes): the k_doa_srp<TG> srp() launches and its staging (dsr_doa_srp_cell); needs no device"""
+        c = (C.c_int * 3)(); b = C.c_int64(); check(_core._lib.dsr_doa_srp_cell(self.h, c, C.byref(b))); return tuple(c), b.value
+
     def srp(self, X, nframes=None, acc=None, want_rp=False, want_y=False):
         """X cuda complex64 [U][C][T][M/2+1] -> dict(energy [U][T] f32, nbest_rp [U][T][nBest] f64, nbest_idx [U][T][nBest] i32, gated [U][T] i32,
         acc [U][nTheta] f64 (the one passed in, added to), rp [U][T][nTheta] f64 and y [U][T][M/2+1] complex64 on request).  Frames past
@@ -446,6 +450,10 @@ class SphDoaSRP(_Sph):
             raise DsrError(1, (_core._lib.dsr_last_error() or b"").decode(errors="replace"))
         return ("fused", "folded")[p]
 
+    def cell(self):
+        """-> ((path 0 fused / 1 folded, TG, DT or 0, BC, KS), dynamic LDS bytes) of the kernel srp() launches (dsr_sph_srp_cell); needs no device"""
+        c = (C.c_int * 5)(); b = C.c_int64(); check(_core._lib.dsr_sph_srp_cell(self.h, c, C.byref(b))); return tuple(c), b.value
+
     def srp(self, X, nframes=None, acc=None, want_rp=False, want_y=False):
         """as DoaSRP.srp, units in place of theta: dict(energy, nbest_rp, nbest_idx, gated, acc [U][units], rp, y)"""
         U, Cn, T, F = X.shape
@@ -471,6 +479,11 @@ class SphDoaSRP(_Sph):
         R = np.zeros((U, self.nBest), np.float64); I = np.zeros((U, self.nBest), np.int32)
         check(_core._lib.dsr_sph_final_nbest(self.h, _ptr(a), U, _ptr(R), _ptr(I)))
         return R, I
+
+
+def sph_beams_cell(NB, chanN, bins):
+    """-> ((0 valu, rows, CC) or (1 mfma, BCT, KS), dynamic LDS bytes) of one beams() call (dsr_sph_beams_cell); needs no device"""
+    c = (C.c_int * 3)(); b = C.c_int64(); check(load().dsr_sph_beams_cell(int(NB), int(chanN), int(bins), c, C.byref(b))); return tuple(c), b.value
 
 
 class SphTracker(Handle):

@@ -360,6 +360,12 @@ dsr_status dsr_doa_build_table(dsr_doa*);
 /* steering weights of direction thetaX: out [fftLen/2+1][chanN] complex128 = wq_f for the table's bins, (1, 0) at bin 0 unless the table was
    built with fbinMin = 0, zero elsewhere (:3138-3146) */
 dsr_status dsr_doa_steering(dsr_doa*, int thetaX, double* out, size_t outDoubles);
+/* Which k_doa_srp<TG> dsr_doa_srp launches for this handle's grid and channel count (the table is built when needed): cell[0] = TG, the 16-direction
+   tiles a workgroup owns (4, 2, 1 for NT = ceil(nTheta / 16) >= 4, >= 2, 1); cell[1] = BC, the bins staged in LDS at a time (16, 8, 4, 2, 1: the
+   largest whose chanN rows of BC bins, padded by one from 4 up, are at most 128); cell[2] = KS = ceil(chanN / 4), the MFMA's K steps;
+   ldsBytes (optional): the dynamic LDS of the launch, chanN x 64 frames x pitch x 8.  The launch takes its decisions from the same helper.  Needs
+   no device. */
+dsr_status dsr_doa_srp_cell(dsr_doa*, int cell[3], int64_t* ldsBytes);
 /* next() over a batch (:3188-3245).  X_dev [U][chanN][Tmax][fftLen/2+1] complex64, nframes_dev [U]; per frame t < nframes[u]:
  *   energy_dev [U][Tmax] float: calcEnergy (:3043-3074), the reference's float accumulation bit for bit
  *   rp_dev (optional) [U][Tmax][nTheta] double: the response power of every direction, written for gated frames too
@@ -458,6 +464,11 @@ dsr_status dsr_sph_build_table(dsr_sph*);
 dsr_status dsr_sph_steering(dsr_sph*, int unit, double* out, size_t outDoubles);
 /* the SRP path dsr_sph_srp takes: 0 the fused kernel, 1 the folded table through the linear estimator's kernel; -1 on error */
 int        dsr_sph_srp_path(dsr_sph*);
+/* The kernel of that path for this handle (the table is built when needed): cell[0] = the path; fused: cell[1] = TG (8, 4, 2, 1 for NT =
+   ceil(units / 16) >= 8, >= 4, >= 2, 1), cell[2] = DT, the 16-row eigenbeam tiles (1, 2, 4 for dim <= 16, <= 32, above) of k_sph_srp<TG, DT>;
+   folded: the linear estimator's cell for the [units][chanN] table (dsr_doa_srp_cell), cell[2] = 0; cell[3] = BC, cell[4] = KS and ldsBytes
+   (optional) as dsr_doa_srp_cell has them.  The launch takes its decisions from the same helpers; follows DSR_SPH_SRP_PATH.  Needs no device. */
+dsr_status dsr_sph_srp_cell(dsr_sph*, int cell[5], int64_t* ldsBytes);
 /* the beamformer's next() (:347-399) over a batch: X_dev [U][chanN][Tmax][fftLen/2+1] complex64, nframes_dev [U] ->
  *   Y_dev [U][Tmax][fftLen/2+1] complex64: y = w_f^H (sh_s X_f), bin 0 with the DC weights
  *   F_dev (optional) [U][Tmax][fftLen/2+1][dim] complex64: the eigenbeams (getSnapShotArray, modalBeamformer.h:126)
@@ -518,6 +529,11 @@ dsr_status dsr_sph_beam_weights(dsr_sph*, int NB, double* out, size_t outDoubles
    does not fit the kernel's LDS (beams x (fftLen/2+1) > 3072) runs on the MFMA kernel too. */
 dsr_status dsr_sph_beams(dsr_sph*, const float* X_dev, const int32_t* nframes_dev, int U, int Tmax, int NB, float* Y_dev, void* stream);
 int        dsr_sph_beams_path(int NB);
+/* The kernel of one dsr_sph_beams call with NB beams, chanN channels and `bins` = fftLen/2+1 bins: cell[0] = 0 VALU / 1 MFMA (dsr_sph_beams_path,
+   and the MFMA kernel where the VALU table does not fit); VALU: cell[1] = the row instantiation (NB up to 4, then 8, 16), cell[2] = CC, the channels
+   whose conj(v) is staged at a time; MFMA: cell[1] = BCT = min(8, BC of dsr_doa_srp_cell), cell[2] = KS; ldsBytes (optional): the dynamic LDS of the
+   launch.  The launch takes its decisions from the same helper.  Needs no device. */
+dsr_status dsr_sph_beams_cell(int NB, int chanN, int bins, int cell[3], int64_t* ldsBytes);
 /* getBeamPattern(fbinX, theta, phi, minTheta, maxTheta, minPhi, maxPhi, widthTheta, widthPhi): the grid is (int)(float)((max - min) / width +
    1.5) a side, theta and phi accumulated by addition; out [nTheta][nPhi] = |wq^H SHT(p)| of a unit plane wave p on the sphere (modal kinds,
    :756-787), |sum w p| unconjugated (MOEN, :2068-2099), |w^H p| (SPATIALDS: the inherited code dots a chanN-long with a dim-long vector).  It

@@ -36,7 +36,7 @@ BEAM_SHAPES = [
     (32, 5, "mfma", "MOEN", 4, 40),       # first NB on the MFMA path, 11 padded rows
     (32, 16, "mfma", "HWNCGSC", 4, 40),
     (64, 16, "mfma", "DS", 3, 40),
-    (6, 7, "mfma", "EB", 2, 40),          # C is no multiple of the MFMA's K step
+    (6, 7, "mfma", "EB", 2, 40),          # BCT 8 with a masked K step; the channel counts that are no multiple of 4: tests/srp_cases.py
     (32, 9, "mfma", "HWNC", 3, 17),       # T is no multiple of the 16-frame tile
     (32, 2, "valu", "MOEN", 3, 17),
 ]

@@ -24,6 +24,7 @@ def test_library_exports_every_declared_symbol():
     assert len(declared) > 80
     assert {"dsr_mfcc_run", "dsr_mfcc_paths", "dsr_mfcc_cfg_paths"} <= declared          # the dispatch query the MFCC kernel tests assert through
     assert {"dsr_bf_rls_path", "dsr_zelinski_path"} <= declared                          # the same for SubbandGSCRLS and the post-filters
+    assert {"dsr_doa_srp_cell", "dsr_sph_srp_cell", "dsr_sph_beams_cell"} <= declared          # and for the SRP kernels and the multi-beam apply
     assert declared - exported == set(), sorted(declared - exported)
     L = C.CDLL(LIB)
     for name in declared:

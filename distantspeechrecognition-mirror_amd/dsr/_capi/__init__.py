@@ -38,4 +38,6 @@ from .decoder import (Wfst, Decoder, _lexh, Lattice, Pipe)
 def __getattr__(name):
     if name == "_lib":                                 # the loaded library, live: _core owns it, load() rebinds it
         return _core._lib
+    if name == "AdaptiveBeamformer":                   # include/dsr.h section 2a'': dsr/_abf.py, on the common handle base
+        from .._abf import AdaptiveBeamformer; return AdaptiveBeamformer
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -319,6 +319,64 @@ dsr_status dsr_det_exp(const double* x, double* y, int n);
 dsr_status dsr_det_psi(const double* x, double* y, int n);
 
 /* =====================================================================================
+ * 2a''. The data-adaptive subband beamformers of btk/lib/subbandBeamforming.py (all line numbers below are that file's)
+ *     replaces SubbandBeamformerDS (:350-436), SubbandBeamformerGSC (:549-676), SubbandBeamformerGriffithsJim (:982-1104),
+ *     SubbandBeamformerMVDR (:1107-1183, sample matrix inversion) and SubbandBeamformerMPDR (:1185-1265) with the helpers they call
+ * Scope: the code as shipped, one constraint (the static GSC also two), no halfBandShift, half spectrum (F = fftLen/2+1 bins; the reference's
+ * MPDR loops over all fftLen bins independently, its upper half equals the conjugate mirror up to rounding).  create refuses halfBandShift and
+ * any other NC with DSR_E_CONSISTENCY, chanN outside [1 + NC, DSR_ABF_MAX_CHAN] with DSR_E_DIMENSION.  All arithmetic fp64.
+ * Not built: SubbandBeamformerRLS (:679-804, multiplies a C x (C-1) matrix by a C-vector at :716), SubbandBeamformerCovarSqRoot (:807-829, no
+ * __iter__), SubbandBeamformerInfoSqRoot (:831-979, calls an undefined isSilence).
+ * ===================================================================================== */
+typedef struct dsr_abf dsr_abf;
+#define DSR_ABF_MAX_CHAN 64
+enum { DSR_ABF_DS = 0,                   /* SubbandBeamformerDS: conj(v) . x */
+       DSR_ABF_GSC = 1,                  /* SubbandBeamformerGSC: conj(x^H wq - (x^H B) wa), wa set from outside */
+       DSR_ABF_GJ = 2,                   /* SubbandBeamformerGriffithsJim: normalised LMS, silence gate, norm constraint */
+       DSR_ABF_MVDR = 3,                 /* SubbandBeamformerMVDR: w = (Sx + diagLoad I)^-1 v / (v^H (Sx + diagLoad I)^-1 v) */
+       DSR_ABF_MPDR = 4 };               /* SubbandBeamformerMPDR: wa = conj(L R^-1), R = B^H Sx B + diagLoad I, L = wq^H Sx B */
+enum { DSR_ABF_STATE_REGS = 0,           /* state in registers (chanN 4, 6, 8), the Cholesky factor in LDS */
+       DSR_ABF_STATE_LDS = 1,            /* state and factor in dynamic LDS, [entry][lane] */
+       DSR_ABF_STATE_MEM = 2 };          /* state and factor in memory, [entry][utterance x bin] */
+dsr_status dsr_abf_create(int kind, int fftLen, int chanN, int NC, int halfBandShift, dsr_abf** out);           /* the constructors :356, :550, :989, :1110, :1188 */
+void       dsr_abf_destroy(dsr_abf*);
+/* the constructor parameters of the three adaptive classes (:989-1005, :1110-1121, :1188-1198); defaults of create: beta 0.999, gamma 0.0005,
+   initDiagLoad 1e10, floorSubBandSigmaK 2e7, silThresh 1e10, alpha2 0.001, staticAfter 1000; diagLoad 0.001, forgetFactor 0.99, end 20.
+   diagLoad <= 0 is DSR_E_PARAMETER for MVDR / MPDR: the loaded matrix is Cholesky factorised (the reference inverts it, :1140, :1257). */
+dsr_status dsr_abf_config(dsr_abf*, double beta, double gamma, double initDiagLoad, double floorSubBandSigmaK, double silThresh, double alpha2,
+                          int staticAfter, double diagLoad, double forgetFactor, int end);
+/* _arrayManifold and _blockingMatrix (:386-420, :603-657), bins 0..fftLen/2: wq [F][chanN], B [F][chanN][chanN-NC] complex128 (host);
+   B == NULL: calcBlockingMatrix(wq[f], NC) (:249-277) */
+dsr_status dsr_abf_set_fixed_weights(dsr_abf*, const double* wq, const double* B);
+dsr_status dsr_abf_get_fixed_weights(const dsr_abf*, double* wq, double* B);                                      /* either may be NULL */
+/* calcBlockingMatrix(vs, NC) (:249-277): B [chanN][chanN-NC]; calcNullBeamformer(w_t, w_j, NC) with getInverseMat22 (:495-546): wq [chanN];
+   calcArrayManifold_f / calcArrayManifoldWoNorm_f (:438-493; normalize != 0: divided by chanN): vs [chanN].  Host, complex128, no device. */
+dsr_status dsr_abf_blocking_matrix(const double* vs, int chanN, int NC, double* B);
+dsr_status dsr_abf_null_beamformer(const double* w_t, const double* w_j, int chanN, int NC, double* wq);
+dsr_status dsr_abf_manifold(int fbinX, int fftLen, int chanN, double sampleRate, const double* delays, int halfBandShift, int normalize, double* vs);
+/* setWa (:659-676), the static GSC: wa [F][chanN-NC] complex128 (host) */
+dsr_status dsr_abf_set_active_weights(dsr_abf*, const double* wa);
+/* __iter__ (:363-384, :564-601, :1007-1090, :1123-1168, :1200-1238) for a batch.  X_dev [U][chanN][Tmax][F] complex64 -> Y_dev [U][Tmax][F] complex64.
+ * nframes_dev (optional) [U]: utterance u has nframes[u] frames; the rest of its rows is zero and nothing adapts on them.  wp_dev (optional)
+ * [U][Tmax][F] fp32: the post-filter weights _wp / wp1L, row t scales frame t of this call while t < wpFrames_dev[u] (NULL: every row).
+ * wOut_dev (optional, adaptive kinds): the final weights, complex128 -- _waHK [U][F][chanN-1] (Griffiths-Jim), conj(_wH) = w [U][F][chanN]
+ * (MVDR), _waK [U][F][chanN-1] (MPDR): what saveWeights pickles.  Griffiths-Jim needs dsr_abf_reset once before the first call (:1092-1104
+ * create the state; iterating before nextSpkr() fails in the reference too). */
+dsr_status dsr_abf_run(dsr_abf*, const float* X_dev, const int32_t* nframes_dev, int U, int Tmax, const float* wp_dev, const int32_t* wpFrames_dev,
+                       float* Y_dev, double* wOut_dev, void* stream);
+/* carry = 1: every run of the same U continues from the state the previous one left, frame counter, gamma and average power included (the
+ * reference between two iterations without nextSpkr()); carry = 0 (default): every run starts new streams.  The carried state has one layout
+ * whatever the residence.  reset is nextSpkr() (:1092-1104, :1177-1183): the next run starts new streams.  A carried state of another U is
+ * DSR_E_CONSISTENCY. */
+dsr_status dsr_abf_set_carry(dsr_abf*, int on);
+dsr_status dsr_abf_reset(dsr_abf*);
+/* Which kernel dsr_abf_run launches for an adaptive kind and chanN channels: path[0] = CT, the compile-time channel count (4, 6, 8; 0: run-time
+ * count), path[1] = the capacity of a thread's vectors (16; 64 above 16 channels), path[2] = the residence.  lds (optional): lds[0] the bytes the
+ * 64 lanes' state and Cholesky factor take, which the 150 KB gate compares; lds[1] the dynamic LDS of the launch.  The launch takes its decisions
+ * from the same helper.  The switches DSR_ABF_NOREGS and DSR_ABF_MEMSTATE, set to anything, are read on every call.  Needs no device. */
+dsr_status dsr_abf_path(int kind, int chanN, int path[3], int64_t lds[2]);
+
+/* =====================================================================================
  * 2b. Steered-response-power direction of arrival for a linear array
  *     replaces DOAEstimatorSRPDSBLA (btk/beamformer/beamformer.h:462-560, beamformer.i:479-513,
  *     beamformer.cc:2920-3283)

@@ -225,6 +225,28 @@ dsr_status dsr_merge_feature_create(dsr_stream* stat, dsr_stream* delta, dsr_str
     hand_out(out, new_op<MergeOp>(out, name, "Merge", stat->size_ + delta->size_ + deltaDelta->size_, DSR_T_FLOAT), {stat, delta, deltaDelta});
   });
 }
+namespace { struct SrcOp : dsr_stream {         // SamplerateConversionFeature (feature.h:794-816, feature.cc:1607-1699)
+  dsr_src* plan = nullptr;
+  ~SrcOp() override { if (plan) dsr_src_destroy(plan); }
+  void compute() override {
+    const int64_t n = (int64_t) ups[0]->nFrames * ups[0]->size_, m = dsr_src_out_samples(plan, n);
+    dev.reserve((size_t) (m > 0 ? m : 1) * sizeof(float)); alloc((int) (m / size_));
+    if (m > 0) ok(dsr_src_apply(plan, ups[0]->d<float>(), nullptr, 1, 1, n, nullptr, 1, d<float>(), nullptr, m, S0));
+  }
+}; }
+dsr_status dsr_src_stream_create(dsr_stream* src, unsigned srcRate, unsigned dstRate, unsigned len, const char* method, const char* name,
+                                 dsr_stream** out)
+{
+  return guard([&] {
+    need(src, DSR_T_FLOAT, "SamplerateConversionFeature");
+    if (!method) throw Error(DSR_E_PARAMETER, "null argument");
+    const unsigned size = len ? len : (unsigned) (unsigned) ((float) src->size_ * (float) dstRate / (float) srcRate);   // feature.cc:1612
+    if (size < 1 || size > 0x7fffffffu) throw Error(DSR_E_DIMENSION, "SamplerateConversionFeature: blocks of %u samples", size);
+    auto s = new_op<SrcOp>(out, name, "SamplerateConversion", (int) size, DSR_T_FLOAT);
+    ok(dsr_src_create(srcRate, dstRate, method, &s->plan));
+    hand_out(out, std::move(s), {src});
+  });
+}
 
 // ---- btk/lpc
 namespace { struct LpcOp : dsr_stream {         // WarpMVDR/BurgMVDR/WarpLPC/BurgLPC features (lpc.h:86-195,262-331)

@@ -40,4 +40,6 @@ def __getattr__(name):
         return _core._lib
     if name == "AdaptiveBeamformer":                   # include/dsr.h section 2a'': dsr/_abf.py, on the common handle base
         from .._abf import AdaptiveBeamformer; return AdaptiveBeamformer
+    if name == "SampleRateConverter":                  # include/dsr.h section 6d: dsr/_src.py, on the common handle base
+        from .._src import SampleRateConverter; return SampleRateConverter
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

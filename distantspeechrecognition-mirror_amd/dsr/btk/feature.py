@@ -149,6 +149,16 @@ class FilterFeaturePtr(FeatureStreamPtr):
         FeatureStreamPtr.__init__(self, h, keep=(src,))
 
 
+class SamplerateConversionFeaturePtr(FeatureStreamPtr):
+    """feature.h:794-816, feature.i: the source's blocks resampled from sourcerate to destrate and served in blocks of len samples (0: the source's
+    size times the ratio, in float arithmetic).  method: "best", "medium", "fastest", "zoh" or "linear".  The converter is the library's own
+    (include/dsr.h section 6d), not libsamplerate."""
+
+    def __init__(self, src, sourcerate=22050, destrate=16000, len=0, method="fastest", nm="SamplerateConversion"):
+        h, _ = _new(lib().dsr_src_stream_create, src._h, int(sourcerate), int(destrate), int(len), _b(method), _b(nm))
+        FeatureStreamPtr.__init__(self, h, keep=(src,))
+
+
 class MergeFeaturePtr(FeatureStreamPtr):
     """feature.h:1423-1441: static, delta and delta-delta features side by side."""
 

@@ -180,6 +180,14 @@ class FilterFeature : public VectorFloatFeatureStream {
   : _s(src) { DSR_OP(FilterFeature, float, dsr_filter_feature_create(src->handle(), coeffA, (int) lenA, nm.c_str(), &h)) }
  private: VectorFloatFeatureStreamPtr _s;
 };
+// SamplerateConversionFeature (feature.h:794-816): include/dsr.h section 6d, the library's own converter under libsamplerate's method names
+class SamplerateConversionFeature : public VectorFloatFeatureStream {
+ public: SamplerateConversionFeature(const VectorFloatFeatureStreamPtr& src, unsigned sourcerate = 22050, unsigned destrate = 16000, unsigned len = 0,
+                                     const String& method = "fastest", const String& nm = "SamplerateConversion")
+  : _s(src) { DSR_OP(SamplerateConversionFeature, float, dsr_src_stream_create(src->handle(), sourcerate, destrate, len, method.c_str(), nm.c_str(), &h)) }
+ private: VectorFloatFeatureStreamPtr _s;
+};
+typedef std::shared_ptr<SamplerateConversionFeature> SamplerateConversionFeaturePtr;
 class MergeFeature : public VectorFloatFeatureStream {
  public: MergeFeature(const VectorFloatFeatureStreamPtr& stat, const VectorFloatFeatureStreamPtr& delta, const VectorFloatFeatureStreamPtr& deltaDelta, const String& nm = "Merge")
   : _a(stat), _b(delta), _c(deltaDelta) { DSR_OP(MergeFeature, float, dsr_merge_feature_create(stat->handle(), delta->handle(), deltaDelta->handle(), nm.c_str(), &h)) }

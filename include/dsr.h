@@ -1647,6 +1647,59 @@ dsr_status dsr_sphinx_mel_filters(const dsr_sphinx_mel*, double* A_host /* [filt
 dsr_status dsr_sphinx_mel_apply(dsr_sphinx_mel*, const double* x_dev, const int32_t* nframes_dev, int U, int Tmax, double* y_dev, void* stream);
 
 /* =====================================================================================
+ * 6d. Sample-rate conversion (csrc/src_kernels.hip, csrc/src.cpp)
+ *     stands for SamplerateConversionFeature (btk/feature/feature.h:794-816, feature.cc:1607-1699), which wraps libsamplerate.  libsamplerate is
+ *     not reproduced: the converter is defined here, band-limited interpolation with a Kaiser-windowed sinc, and its output bits are its own.
+ * Rates are unsigned integers; g = gcd(src, dst), L = dst/g, M = src/g, s = min(1, L/M).  Output n sits at input time n M / L:
+ * base = floor(n M / L) in 64-bit integers, phase p = (n M) mod L, frac = p / L.  N input samples give floor(N L / M) outputs; the input is zero
+ * before sample 0 and after sample N-1.
+ *   "fastest", "medium", "best" (the reference's names, feature.cc:1615-1626): Z = 10, 16, 32 zero crossings, Kaiser beta = 7.0, 9.5, 12.0,
+ *   cutoff c = 0.84, 0.90, 0.95; K = ceil(Z / s); y[n] = sum_{j=-K+1..K} h_p[j] x[base + j], h_p[j] = s c sinc(s c d) w(d s / Z), d = frac - j,
+ *   sinc(v) = sin(pi v) / (pi v), w(v) = I0(beta sqrt(1 - v^2)) / I0(beta) for |v| < 1, else 0; each phase's 2K taps are divided by their sum (DC
+ *   passes exactly).  The table [L][2K] is computed on the host in fp64 at create, rounded to fp32 and uploaded once; the device sums in fp32: two
+ *   chains acc = fmaf(h, x, acc) from 0, over every other tap each with j ascending, and their rounded sum -- the same on every path and for every
+ *   split of the work.
+ *   "zoh": y[n] = x[base] (K = 0).  "linear": y[n] = x[base] + f (x[base+1] - x[base]), f = float(p) / float(L), each operation rounded to
+ *   fp32 and none fused (K = 1).
+ * create refuses any other name with the reference's "Cannot recognize type (%s) of sample rate converter." (DSR_E_CONSISTENCY), a zero rate
+ * and a table 2K L above 2^22 entries (DSR_E_PARAMETER).  Equal rates are a copy, whatever the method (K = 0).
+ * ===================================================================================== */
+typedef struct dsr_src dsr_src;
+enum { DSR_SRC_TABLE_LDS = 0,            /* the coefficient table sits in LDS beside the input tile */
+       DSR_SRC_TABLE_MEM = 1,            /* it does not fit (or DSR_SRC_TABLE=mem): read through the cache */
+       DSR_SRC_TABLE_UNIFORM = 2,        /* L = 1, integer decimation: one row, read with wave-uniform addresses */
+       DSR_SRC_TABLE_NONE = 3 };         /* zoh, linear, equal rates */
+enum { DSR_SRC_INPUT_LDS = 0,            /* a workgroup stages the input span of a run of outputs in LDS */
+       DSR_SRC_INPUT_DIRECT = 1 };       /* straight from memory: zoh, linear, and ratios whose 2K taps alone exceed a tile */
+dsr_status dsr_src_create(unsigned srcRate, unsigned dstRate, const char* method, dsr_src** out);
+void       dsr_src_destroy(dsr_src*);
+dsr_status dsr_src_ratio(const dsr_src*, int32_t ratio[3] /* L, M, K */);
+int64_t    dsr_src_out_samples(const dsr_src*, int64_t nIn);            /* floor(nIn L / M): what a one-shot call, or a flushed stream, gives */
+/* the most outputs one call with carried state gives for nIn input samples (outputs held back by earlier blocks included): the least outStride */
+int64_t    dsr_src_block_out_bound(const dsr_src*, int64_t nIn);
+/* the fp32 table of a sinc method as the definition orders it: table [L][2K], row p = phase p, j = -K+1 .. K (host) */
+dsr_status dsr_src_table(const dsr_src*, float* table);
+/* Carried state (the caller's device memory): per utterance the 64-bit counts of inputs consumed and outputs produced, per (u, c) the last 2K
+ * input samples (zoh and linear: ceil(M / L) more, because the count floor(b L / M) can hold back an output whose taps were all there).  init zeroes it and notes its shape in the handle; apply with a state of another shape is DSR_E_CONSISTENCY. */
+size_t     dsr_src_state_bytes(const dsr_src*, int U, int C);
+dsr_status dsr_src_state_init(dsr_src*, void* state_dev, int U, int C, void* stream);
+/* x_dev float [U][C][inStride], nsamp_dev int32 [U] (NULL: inStride each) -> y_dev float [U][C][outStride], nout_dev int32 [U] (optional): the
+ * outputs of this call; the rest of a row comes out zero.  state_dev NULL: a one-shot call, floor(nsamp L / M) outputs, outStride at least
+ * dsr_src_out_samples(inStride).  With a state the call delivers inputs [a, b) of every stream and produces exactly the outputs not yet produced
+ * whose last tap base + K is below b; flush != 0 produces the rest, up to floor(b L / M), with zeros past the end (initialise the state again
+ * before the next stream); outStride at least dsr_src_block_out_bound(inStride).  Block by block with a final flush equals the one-shot call bit
+ * for bit, whatever the block lengths.  DSR_SRC_TABLE=mem in the environment, read on every call, forces DSR_SRC_TABLE_MEM;
+ * DSR_SRC_RUN=n caps the outputs of a tile (256 at the least) and DSR_SRC_TILES=n (1 to 16) sets the tiles a workgroup walks: the tests' switches. */
+dsr_status dsr_src_apply(dsr_src*, const float* x_dev, const int32_t* nsamp_dev, int U, int C, int64_t inStride, void* state_dev, int flush,
+                         float* y_dev, int32_t* nout_dev, int64_t outStride, void* stream);
+/* the cell apply takes: path[0] DSR_SRC_TABLE_*, path[1] DSR_SRC_INPUT_*, path[2] the outputs of a tile, path[3] the launch's dynamic LDS in
+ * bytes, path[4] the pitch between the outputs of neighbouring lanes (odd; it spreads their LDS reads over the banks).  The launch takes its decisions from the same helper.  Needs no device. */
+dsr_status dsr_src_path(const dsr_src*, int32_t path[5]);
+/* measurement (tools/bench_src.py): with timing on, apply brackets its launches with events; kernel_ms waits for them: the last call's ms */
+dsr_status dsr_src_set_timing(dsr_src*, int on);
+dsr_status dsr_src_kernel_ms(const dsr_src*, double* ms);
+
+/* =====================================================================================
  * 7. Stream/feature-operator API  (FeatureStream<Type,item>::next/reset/size/name/current/isEnd,
  *    btk/stream/stream.h:36-75).  Operators are reference counted handles that hold their
  *    upstream(s); next() returns a pointer to the operator's own output buffer (host memory),
@@ -1848,6 +1901,12 @@ dsr_status dsr_spectral_smoothing_create(dsr_stream* adjustTo, dsr_stream* adjus
 dsr_status dsr_filter_feature_create(dsr_stream* src, const double* a, int lenA, const char* name, dsr_stream** out);
 /* MergeFeature(stat, delta, deltaDelta, nm = "Merge") (feature.h:1423-1441): the three float rows one after the other; ends with the shortest */
 dsr_status dsr_merge_feature_create(dsr_stream* stat, dsr_stream* delta, dsr_stream* deltaDelta, const char* name, dsr_stream** out);
+/* SamplerateConversionFeature(src, sourcerate = 22050, destrate = 16000, len = 0, method = "fastest", nm = "SamplerateConversion")
+ * (feature.h:794-816, feature.cc:1607-1699) over section 6d.  size() is len or, for len 0, unsigned(src.size() * float(destrate) /
+ * float(sourcerate)) in float arithmetic (feature.cc:1612).  The source's blocks, one after the other, are the input; the converter is flushed once
+ * at the source's end, and the outputs are served in blocks of size(): a last block that cannot be filled is not delivered. */
+dsr_status dsr_src_stream_create(dsr_stream* src, unsigned srcRate, unsigned dstRate, unsigned len, const char* method, const char* name,
+                                 dsr_stream** out);
 /* OverlapAdd(samp, impulseResponse, fftLen = 0, nm = "Overlap Add") / OverlapSave(samp, impulseResponse, nm = "Overlap Save")
  * (convolution.h:40-104): section 2g with C = 1 over the source's blocks; reset() zeroes OverlapAdd's buffer.  update: delta complex[n], n must
  * be L (DSR_E_DIMENSION otherwise, as there); it holds for the utterances materialised after it. */

@@ -29,13 +29,10 @@ void MLLRParam::assign(int D, const double* W)
   }
 }
 
-namespace {
-
 // ParamBase::_symMap / _adaptMap (tr:203-208)
-enum Symbol { SymRegClass = 0, SymRAPT, SymSLAPT, SymMLLR, SymSTC, SymLDA, SymBias, SymEndClass, SymAdaptType, SymEOF, SymNull };
 const char* kSymMap[] = { "RegClass", "RAPTParam", "SLAPTParam", "MLLRParam", "STCParam", "LDAParam", "BiasOffset", "EndClass", "AdaptType", "EOF", "" };
-const char* kAdaptMap[] = { "RAPT", "SLAPT", "MLLR", "STC", "LDA", "" };
-const unsigned kMaxSymbolLength = 16;
+static const char* kAdaptMap[] = { "RAPT", "SLAPT", "MLLR", "STC", "LDA", "" };
+static const unsigned kMaxSymbolLength = 16;
 
 Symbol getSymbol(FILE* fp)                                // tr:219-242
 {
@@ -66,6 +63,8 @@ int getAdaptType(FILE* fp)                                // tr:244-267: 0 RAPT,
   for (int as = 0; as <= 2; as++) if (strcmp(kAdaptMap[as], buf) == 0) return as;
   throw Error(DSR_E_ERROR, "Invalid adaptation type %s", buf);
 }
+
+namespace {
 
 void readParams(FILE* fp, MLLRParam& par)                 // ParamBase::_readParams tr:374-407 for _type() == MLLR
 {

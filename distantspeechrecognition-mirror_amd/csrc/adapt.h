@@ -11,6 +11,12 @@ namespace dsr {
 
 bool isAncestor(unsigned ancestor, unsigned child);      // tr:133-145
 
+// the symbols of a speaker parameter file, shared with apt.cpp: ParamBase::_symMap (tr:203-208), _getSymbol (tr:219-242), _getAdaptType (tr:244-267)
+enum Symbol { SymRegClass = 0, SymRAPT, SymSLAPT, SymMLLR, SymSTC, SymLDA, SymBias, SymEndClass, SymAdaptType, SymEOF, SymNull };
+extern const char* kSymMap[];
+Symbol getSymbol(FILE* fp);
+int getAdaptType(FILE* fp);                              // 0 RAPT, 1 SLAPT, 2 MLLR
+
 // MLLRParam (tr:556-650): the size x size matrix and the bias (W's last column), both double
 struct MLLRParam {
   unsigned regClass = 0; int size = 0;
@@ -62,3 +68,9 @@ struct MllrHandle {
 }  // namespace dsr
 
 struct dsr_mllr : dsr::MllrHandle {};
+struct dsr_train;
+
+namespace dsr {
+// count - denCount and sumO of a trainer's accumulator rows into device arrays c [G], sumO [G][D] (k_mllr_take); dsr_apt_set_stats shares it
+void take_stats(const dsr_train& t, int G, int D, double* c, double* sumO);
+}  // namespace dsr

@@ -194,6 +194,13 @@ __global__ __launch_bounds__(256) void k_mllr_apply(int D, int G, const float* _
   out[((long) sp * G + g) * D + m] = comp;
 }
 
+void take_stats(const dsr_train& t, int G, int D, double* c, double* sumO)
+{
+  if (t.G != G || t.D != D) throw Error(DSR_E_DIMENSION, "accumulators of %d Gaussians x %d for a model of %d x %d", t.G, t.D, G, D);
+  launch(k_mllr_take, dim3(cdiv((long) G * (D + 1), 256)), dim3(256), 0, nullptr, t.d_acc.p, G, D, c, sumO);
+  DSR_HIP(hipDeviceSynchronize());
+}
+
 namespace {
 
 struct Timer {
@@ -379,10 +386,7 @@ dsr_status dsr_mllr_set_stats(dsr_mllr* h, int s, dsr_train* t)
   return guard([&] {
     if (!h || !t) throw Error(DSR_E_PARAMETER, "null argument");
     check_slot(*h, s);
-    if (t->G != h->G || t->D != h->D) throw Error(DSR_E_DIMENSION, "accumulators of %d Gaussians x %d for a model of %d x %d", t->G, t->D, h->G, h->D);
-    launch(k_mllr_take, dim3(cdiv((long) h->G * (h->D + 1), 256)), dim3(256), 0, nullptr, t->d_acc.p, h->G, h->D, h->d_c.p + (size_t) s * h->G,
-                       h->d_sumO.p + (size_t) s * h->G * h->D);
-    DSR_HIP(hipDeviceSynchronize());
+    take_stats(*t, h->G, h->D, h->d_c.p + (size_t) s * h->G, h->d_sumO.p + (size_t) s * h->G * h->D);
   });
 }
 

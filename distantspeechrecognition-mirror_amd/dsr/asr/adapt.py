@@ -1,6 +1,7 @@
 """asr.adapt: ParamTreePtr, CodebookSetAdaptPtr, TransformerTreePtr and adaptCbk (asr/adapt/adapt.i) for MLLR mean transforms, over
-dsr_param_tree_* and dsr_mllr_* (include/dsr.h section 10), and STCTransformerPtr / LDATransformerPtr over dsr_stc_* / dsr_lda_* (section 12).  The all-pass transforms (RAPT, SLAPT,
-BLT) are not implemented.
+dsr_param_tree_* and dsr_mllr_* (include/dsr.h section 10), STCTransformerPtr / LDATransformerPtr over dsr_stc_* / dsr_lda_* (section 12), and the
+all-pass transforms -- APTParamTreePtr, RAPTParam, SLAPTParam, BLTTransformer, SLAPTTransformer -- over dsr_apt_* (section 13): the bilinear
+transform and the sine-log all-pass transform; RAPT with more than one parameter is refused.
 
 The model lives with the distribution set (as everywhere in this package): a codebook set is bound to it when its DistribSet*Ptr is built.
 
@@ -9,6 +10,10 @@ The model lives with the distribution set (as everywhere in this package): a cod
     estimateAdaptationParameters(tree); tree.writeParams("spk.mllr")
     adaptCbk(cbs, paramTree)                             # the model's means move; every scoring mode follows
     cbs.resetMean()
+
+    cbs.setSubFeatures(13, 3); params = APTParamTreePtr()
+    tree = EstimatorTreeSLAPTPtr(cbs, params, "CepstraOnly", paramN=1)      # dsr.asr.train; EstimatorTreeBLTPtr for the bilinear transform
+    estimateAdaptationParameters(tree); tree.writeParams("spk.slapt"); adaptCbk(cbs, params)
 """
 import ctypes as C
 
@@ -24,12 +29,92 @@ class ParamTreePtr(K.ParamTree):
         K.ParamTree.__init__(self, fileName)
 
 
+class APTParamTreePtr(K.AptParams):
+    """ParamTree(fileName = "") holding RAPT or SLAPT parameters: read / write / clear / findAPT / type (1 RAPT, 2 SLAPT)"""
+
+    def __init__(self, fileName=""):
+        K.AptParams.__init__(self, fileName)
+
+
+class _APTParam(object):
+    """APTParamBase (transform.h:307-346): _conf, the bias and the regression class of one block of a parameter file"""
+
+    def __init__(self, conf=(), bias=(), regClass=0):
+        import numpy as np
+        self.conf = np.array(np.atleast_1d(conf), np.float64); self.bias = np.array(np.atleast_1d(bias), np.float32); self._rc = int(regClass)
+
+    def size(self):
+        return len(self.conf)
+
+    def __getitem__(self, i):
+        return float(self.conf[i])
+
+    def regClass(self):
+        return self._rc
+
+    def isZero(self):
+        return len(self.conf) == 0
+
+    def write(self, fileName):
+        t = K.AptParams(); t.set(self._rc or 1, self._type, self.conf, self.bias); t.write(fileName)
+
+    def transformer(self, sbFtSz, nSubFt):
+        return (BLTTransformer if self._type == K.APT_RAPT else SLAPTTransformer)(self, sbFtSz, nSubFt)
+
+
+class RAPTParam(_APTParam):
+    """RAPTParam(alpha, bias, rc) (transform.h:350-375).  Its transformer is the BLTTransformer: more than one parameter is refused"""
+    _type = K.APT_RAPT
+
+
+class SLAPTParam(_APTParam):
+    """SLAPTParam(seq, bias, rc) (transform.h:379-404)"""
+    _type = K.APT_SLAPT
+
+
+class _APTTransformer(object):
+    """APTTransformerBase for one parameter block: matrix() is _calcTransMatrix of the block's series, transform(rows) the transformed
+    means of rows [N][sbFtSz nSubFt] with the bias (transform.cc:1212-1242, 1295-1337); both are made on the device"""
+
+    def __init__(self, par, sbFtSz, nSubFt=1):
+        self._par = par if isinstance(par, _APTParam) else type(self)._param(par)
+        self._L, self._nSub = int(sbFtSz), int(nSubFt)
+        K.apt_transform_rows(self._kind, self._L, self._nSub, self._par.conf)             # the reference's jparameter_error comes at once
+
+    def matrix(self):
+        return K.apt_transform_rows(self._kind, self._L, self._nSub, self._par.conf)[0]
+
+    def transform(self, rows, useBias=True):
+        return K.apt_transform_rows(self._kind, self._L, self._nSub, self._par.conf, self._par.bias if useBias else (), rows)[1]
+
+
+class BLTTransformer(_APTTransformer):
+    """BLTTransformer(par or alpha, sbFtSz, nSubFt) (transform.cc:1366-1430)"""
+    _kind, _param = K.APT_RAPT, RAPTParam
+
+
+class SLAPTTransformer(_APTTransformer):
+    """SLAPTTransformer(par or parameters, sbFtSz, nSubFt) (transform.cc:1636-1741)"""
+    _kind, _param = K.APT_SLAPT, SLAPTParam
+
+
 class CodebookSetAdaptPtr(CodebookSetBasicPtr):
     """CodebookSetAdapt(descFile, fs, cbkFile) (codebookAdapt.h): keeps the original means once a transform has been applied"""
 
     def __init__(self, descFile="", fs=None, cbkFile=""):
         CodebookSetBasicPtr.__init__(self, descFile, fs, cbkFile)
-        self._mllr = None
+        self._mllr = None; self._apt = {}; self._sub = None
+
+    def setSubFeatures(self, subFeatLen, nSubFeat=1):
+        """the sub-feature layout the all-pass transforms work on (CodebookSetBasic::subFeatLen / nSubFeat): nSubFeat blocks of subFeatLen"""
+        self._sub = (int(subFeatLen), int(nSubFeat))
+
+    def _apt_adapter(self, kind, biasType=0):
+        """the all-pass handle of this set for one kind and bias type: made on first use, as _adapter"""
+        if (kind, biasType) not in self._apt:
+            g = self._model(); L, nSub = self._sub or (g.D, 1)
+            self._apt[(kind, biasType)] = K.Apt(g, 1, kind, L, nSub, biasType)
+        return self._apt[(kind, biasType)]
 
     def _model(self):
         g = getattr(self, "_gmm", None)
@@ -44,13 +129,14 @@ class CodebookSetAdaptPtr(CodebookSetBasicPtr):
         return self._mllr
 
     def setRegClasses(self, c=1):
-        if self._mllr is not None:
+        if self._mllr is not None or self._apt:
             raise K.DsrError(K.E_CONSISTENCY, "regression classes are set before the first estimation or transform")
         self._model().set_reg_classes(int(c))
 
     def resetMean(self):
-        if self._mllr is not None:
-            self._mllr.reset_mean(self._model())
+        for h in [self._mllr] + list(self._apt.values()):
+            if h is not None:
+                h.reset_mean(self._model()); break
 
 
 class TransformerTreePtr(object):
@@ -64,6 +150,10 @@ class TransformerTreePtr(object):
 
     def transform(self):
         print("\nTransforming Means")
+        if isinstance(self._paramTree, K.AptParams):                  # BLTTransformer / SLAPTTransformer per class
+            m = self._cbs._apt_adapter(self._paramTree.type() or K.APT_SLAPT)
+            m.store(0).copy_from(self._paramTree); m.adapt(0, self._cbs._model())
+            return self
         m = self._cbs._adapter()
         m.tree(0).copy_from(self._paramTree)
         m.adapt(0, self._cbs._model())

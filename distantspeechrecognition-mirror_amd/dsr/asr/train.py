@@ -186,8 +186,56 @@ class EstimatorTreeMLLRPtr(TransformerTreePtr):
         return float(sum(m.ttl_frames(0, n) for n in m.nodes()[0]))
 
 
+class EstimatorTreeSLAPTPtr(EstimatorTreeMLLRPtr):
+    """EstimatorTreeSLAPT(cbs, paramTree, biasType = "CepstraOnly", paramN, noItns = 10, trace = 1, threshold = 150.0) (train.i:366-386) over
+    dsr_apt_* (include/dsr.h section 13).  paramTree: an APTParamTreePtr.  Only paramN = 1 -- the line search of the reference's one-parameter
+    branch -- is implemented; the reference's default of 9 parameters (its Newton search) is refused with DSR_E_PARAMETER.  The sub-feature
+    layout is the codebook set's (setSubFeatures)."""
+    _kind = K.APT_SLAPT
+
+    def __init__(self, cbs, paramTree, biasType="CepstraOnly", paramN=1, noItns=10, trace=1, threshold=150.0):
+        if not isinstance(paramTree, K.AptParams):
+            raise K.DsrError(K.E_CONSISTENCY, "Tree not instantiated with %s parameters." % ("RAPT" if self._kind == K.APT_RAPT else "SLAPT"))
+        if biasType not in K.APT_BIAS:
+            raise K.DsrError(15, "Unrecognized bias type %s" % biasType)            # jtype_error (getBiasType)
+        EstimatorTreeMLLRPtr.__init__(self, cbs, paramTree, trace, threshold)
+        self._bias = K.APT_BIAS[biasType]
+        self._handle().set_param_n(paramN)
+
+    def _handle(self):
+        return self._cbs._apt_adapter(self._kind, self._bias)
+
+    def _adapter(self):
+        return self._handle()
+
+    def _estimate(self):
+        m = self._handle()
+        m.store(0).copy_from(self._paramTree)                                     # not cleared: a tree that is not MLLR keeps its other classes
+        m.set_stats(0, self._cbs._need()); m.estimate(self._threshold)
+        self._paramTree.copy_from(m.store(0)); self._estimated = True
+        if self._trace & 1:
+            for s, node, leaf in m.plan():
+                print(("Backing off from node %d to node %d." % (leaf, node)) if leaf != node else ("Estimating Parameters for Regression Class %d" % leaf))
+
+    def ttlFrames(self):
+        m = self._handle()
+        if not self._estimated:
+            raise K.DsrError(K.E_CONSISTENCY, "ttlFrames is known after estimateAdaptationParameters")
+        return float(sum(m.ttl_frames(0, n) for n in m.nodes()[0]))
+
+
+class EstimatorTreeBLTPtr(EstimatorTreeSLAPTPtr):
+    """the same tree of BLTEstimatorAdapt nodes (estimateAdapt.cc:1623-1690; the reference's train.i does not expose one): one bilinear
+    parameter alpha per regression class"""
+    _kind = K.APT_RAPT
+
+    def __init__(self, cbs, paramTree, biasType="CepstraOnly", trace=1, threshold=150.0):
+        EstimatorTreeSLAPTPtr.__init__(self, cbs, paramTree, biasType, 1, 10, trace, threshold)
+
+
 def estimateAdaptationParameters(tree):
-    """estimateAdapt.cc:3064-3078: an MLLR parameter tree is cleared, then every leaf is estimated with back-off"""
+    """estimateAdapt.cc:3064-3078: an MLLR parameter tree is cleared, then every leaf is estimated with back-off; a tree of all-pass
+    parameters is not cleared and nothing is copied"""
     tree._estimate()
 
 

@@ -1327,7 +1327,7 @@ typedef std::shared_ptr<DecoderWordTrace> DecoderWordTracePtr;
 // the distribution set creates (it owns the model); the codebook set's methods need that to have happened.  Frames are pulled through the
 // stream protocol (frames 0..T-1 of the feature the codebook set names) and run as one batch on the device.
 // ---- asr/adapt: ParamTree (transform.h:520-552) and CodebookSetAdapt (codebookAdapt.h) over dsr_param_tree_* / dsr_mllr_* (include/dsr.h
-// section 10).  Only MLLR parameters.  A codebook set is bound to its model when its distribution set is built (the distribution set owns it).
+// section 10).  MLLR parameters; the all-pass parameters have a tree of their own below.  A codebook set is bound to its model when its distribution set is built (the distribution set owns it).
 class ParamTree {
  public:
   ParamTree(const String& fileName = "") : _h(0) { dsr_throw(dsr_param_tree_create(fileName.c_str(), &_h)); }
@@ -1351,22 +1351,108 @@ class ParamTree {
 };
 typedef std::shared_ptr<ParamTree> ParamTreePtr;
 
+// ---- asr/adapt, the all-pass transforms over dsr_apt_* (include/dsr.h section 13): the ParamTree of RAPTParam or SLAPTParam blocks, the
+// blocks themselves, and BLTTransformer / SLAPTTransformer (transform.h:350-404, transform.cc:1366-1430, 1636-1741).  RAPT with more than one
+// parameter is refused by the library.  type: 1 RAPT, 2 SLAPT.
+enum { APT_RAPT = 1, APT_SLAPT = 2 };
+class APTParamTree {
+ public:
+  APTParamTree(const String& fileName = "") : _h(0) { dsr_throw(dsr_apt_params_create(fileName.c_str(), &_h)); }
+  ~APTParamTree() { dsr_apt_params_destroy(_h); }
+  void write(const String& fileName) const { dsr_throw(dsr_apt_params_write(_h, fileName.c_str())); }
+  void read(const String& fileName) { dsr_throw(dsr_apt_params_read(_h, fileName.c_str())); }
+  void clear() { dsr_throw(dsr_apt_params_clear(_h)); }
+  int type() const { return dsr_apt_params_type(_h); }
+  // findAPT (transform.cc:862-896): _conf and the bias of the class, a copy of its nearest ancestor when missing
+  void findAPT(unsigned rc, int typ, std::vector<double>& conf, std::vector<float>& bias, bool useAncestor = true) {
+    int nc = 0, nb = 0; dsr_throw(dsr_apt_params_find(_h, rc, typ, useAncestor, &nc, &nb));
+    conf.assign((size_t) nc + 1, 0.0); bias.assign((size_t) nb + 1, 0.0f); dsr_throw(dsr_apt_params_get(_h, rc, conf.data(), bias.data()));
+    conf.resize((size_t) nc); bias.resize((size_t) nb);
+  }
+  void set(unsigned rc, int typ, const std::vector<double>& conf, const std::vector<float>& bias = std::vector<float>()) {
+    dsr_throw(dsr_apt_params_set(_h, rc, typ, (int) conf.size(), conf.data(), (int) bias.size(), bias.data()));
+  }
+  dsr_apt_params* handle() const { return _h; }
+ private:
+  APTParamTree(const APTParamTree&); APTParamTree& operator=(const APTParamTree&);
+  dsr_apt_params* _h;
+};
+typedef std::shared_ptr<APTParamTree> APTParamTreePtr;
+
+class APTParamBase {                                          // transform.h:307-346
+ public:
+  APTParamBase(int typ, const std::vector<double>& conf, const std::vector<float>& bias, unsigned rc) : _type(typ), _conf(conf), _bias(bias), _rc(rc) {}
+  unsigned size() const { return (unsigned) _conf.size(); }
+  double operator[](unsigned i) const { return _conf[i]; }
+  unsigned regClass() const { return _rc; }
+  const std::vector<double>& conf() const { return _conf; }
+  const std::vector<float>& bias() const { return _bias; }
+  int type() const { return _type; }
+  void write(const String& fileName) const { APTParamTree t; t.set(_rc ? _rc : 1, _type, _conf, _bias); t.write(fileName); }
+ private:
+  int _type; std::vector<double> _conf; std::vector<float> _bias; unsigned _rc;
+};
+class RAPTParam : public APTParamBase {
+ public:
+  RAPTParam(double alpha, const std::vector<float>& bias = std::vector<float>(), unsigned rc = 0) : APTParamBase(APT_RAPT, std::vector<double>(1, alpha), bias, rc) {}
+};
+class SLAPTParam : public APTParamBase {
+ public:
+  SLAPTParam(const std::vector<double>& seq, const std::vector<float>& bias = std::vector<float>(), unsigned rc = 0) : APTParamBase(APT_SLAPT, seq, bias, rc) {}
+};
+
+class APTTransformerBase {                                    // the matrix and transform(from, to) of one block, both made on the device
+ public:
+  APTTransformerBase(const APTParamBase& par, unsigned sbFtSz, unsigned nSubFt) : _par(par), _L((int) sbFtSz), _nSub((int) nSubFt) { matrix(); }
+  std::vector<double> matrix() const {                        // _calcTransMatrix (transform.cc:1212-1242): [sbFtSz][sbFtSz]
+    std::vector<double> A((size_t) _L * _L + 1);
+    dsr_throw(dsr_apt_transform_rows(_par.type(), _L, _nSub, (int) _par.size(), _par.conf().data(), 0, 0, 0, 0, A.data(), 0)); A.resize((size_t) _L * _L); return A;
+  }
+  std::vector<float> transform(const std::vector<float>& from, bool useBias = true) const {      // transform.cc:1295-1337, one mean
+    std::vector<float> to(from.size());
+    dsr_throw(dsr_apt_transform_rows(_par.type(), _L, _nSub, (int) _par.size(), _par.conf().data(), useBias ? (int) _par.bias().size() : 0,
+                                     _par.bias().data(), from.data(), 1, 0, to.data()));
+    return to;
+  }
+ private:
+  APTParamBase _par; int _L, _nSub;
+};
+class BLTTransformer : public APTTransformerBase {
+ public:
+  BLTTransformer(const RAPTParam& par, unsigned sbFtSz, unsigned nSubFt = 1) : APTTransformerBase(par, sbFtSz, nSubFt) {}
+};
+class SLAPTTransformer : public APTTransformerBase {
+ public:
+  SLAPTTransformer(const SLAPTParam& par, unsigned sbFtSz, unsigned nSubFt = 1) : APTTransformerBase(par, sbFtSz, nSubFt) {}
+};
+
 class CodebookSetAdapt : public CodebookSetBasic {
  public:
   CodebookSetAdapt(const String& descFile = "", FeatureSetPtr fs = FeatureSetPtr(), const String& cbkFile = "")
-    : CodebookSetBasic(descFile, fs, cbkFile), _g(0), _m(0) {}
-  ~CodebookSetAdapt() { dsr_mllr_destroy(_m); }
+    : CodebookSetBasic(descFile, fs, cbkFile), _g(0), _m(0), _subLen(0), _nSub(1) {}
+  ~CodebookSetAdapt() { dsr_mllr_destroy(_m); for (std::map<int, dsr_apt*>::iterator it = _apt.begin(); it != _apt.end(); ++it) dsr_apt_destroy(it->second); }
   void setRegClasses(unsigned c = 1) {
-    if (_m) throw jconsistency_error("regression classes are set before the first estimation or transform");
+    if (_m || !_apt.empty()) throw jconsistency_error("regression classes are set before the first estimation or transform");
     dsr_throw(dsr_gmm_set_reg_class_all(model(), c));
   }
-  void resetMean() { if (_m) dsr_throw(dsr_mllr_reset_mean(_m, model())); }
+  void resetMean() {
+    if (_m) dsr_throw(dsr_mllr_reset_mean(_m, model()));
+    else if (!_apt.empty()) dsr_throw(dsr_apt_reset_mean(_apt.begin()->second, model()));
+  }
+  // the sub-feature layout the all-pass transforms work on (CodebookSetBasic::subFeatLen / nSubFeat); one sub-feature of dimN until set
+  void setSubFeatures(unsigned subFeatLen, unsigned nSubFeat = 1) { _subLen = (int) subFeatLen; _nSub = (int) nSubFeat; }
+  // the all-pass handle of this set for one kind and bias type, made on first use
+  dsr_apt* aptAdapter(int kind, int biasType = 0) {
+    dsr_apt*& h = _apt[kind * 4 + biasType];
+    if (!h) { const int L = _subLen ? _subLen : dsr_gmm_dim(model()) / _nSub; dsr_throw(dsr_apt_create(model(), 1, kind, L, _nSub, biasType, &h)); }
+    return h;
+  }
   dsr_gmm* model() const { if (!_g) throw jconsistency_error("the codebook set has no model yet: build its DistribSet first"); return _g; }
   // the MLLR handle of this set, made on first use: its originals are the means the set was loaded with
   dsr_mllr* adapter() { if (!_m) dsr_throw(dsr_mllr_create(model(), 1, &_m)); return _m; }
   void bind(dsr_gmm* g) { _g = g; }
  private:
-  dsr_gmm* _g; dsr_mllr* _m;
+  dsr_gmm* _g; dsr_mllr* _m; std::map<int, dsr_apt*> _apt; int _subLen, _nSub;
 };
 typedef std::shared_ptr<CodebookSetAdapt> CodebookSetAdaptPtr;
 
@@ -1386,6 +1472,11 @@ class TransformerTree {                                       // TransformerTree
 };
 typedef std::shared_ptr<TransformerTree> TransformerTreePtr;
 inline void adaptCbk(CodebookSetAdaptPtr cbs, ParamTreePtr paramTree) { TransformerTree(cbs, paramTree).transform(); }
+inline void adaptCbk(CodebookSetAdaptPtr cbs, APTParamTreePtr paramTree) {      // BLTTransformer / SLAPTTransformer per class
+  printf("\nTransforming Means\n"); fflush(stdout);
+  dsr_apt* m = cbs->aptAdapter(paramTree->type() ? paramTree->type() : (int) APT_SLAPT);
+  dsr_throw(dsr_apt_params_copy(dsr_apt_store(m, 0), paramTree->handle())); dsr_throw(dsr_apt_adapt(m, 0, cbs->model()));
+}
 
 class DistribSetTrain;
 class CodebookSetTrain : public CodebookSetAdapt {            // a CodebookSetAdapt, as in the reference
@@ -1501,6 +1592,48 @@ class EstimatorTreeMLLR : public TransformerTree {
 };
 typedef std::shared_ptr<EstimatorTreeMLLR> EstimatorTreeMLLRPtr;
 inline void estimateAdaptationParameters(EstimatorTreeMLLRPtr& tree) { tree->estimate(); }
+
+// ---- train.i:366-386: EstimatorTreeSLAPT(cbs, paramTree, biasType, paramN, noItns, trace, threshold), and the same tree of BLTEstimatorAdapt
+// nodes (estimateAdapt.cc:1623-1690).  Only paramN = 1, the line search of the reference's one-parameter branch, is implemented: the
+// reference's default of 9 parameters is a jparameter_error here.  The tree is not cleared and nothing is copied (estimateAdapt.cc:3064-3133).
+class EstimatorTreeSLAPT {
+ public:
+  EstimatorTreeSLAPT(CodebookSetTrainPtr& cb, APTParamTreePtr& paramTree, const String& biasType = "CepstraOnly", unsigned paramN = 1,
+                     unsigned noItns = 10, int trace = 1, float threshold = 150.0f, int kind = APT_SLAPT)
+    : _cbsT(cb), _paramTree(paramTree), _kind(kind), _trace(trace), _threshold(threshold) {
+    (void) noItns;
+    if (biasType == "NONE" || biasType == "None") _bias = 0;                    // getBiasType (estimateAdapt.cc:49-63)
+    else if (biasType == "CEPSTRAONLY" || biasType == "CepstraOnly") _bias = 1;
+    else if (biasType == "ALLCOMPONENTS" || biasType == "AllComponents") _bias = 2;
+    else throw jtype_error("Unrecognized bias type " + biasType);
+    dsr_throw(dsr_apt_set_param_n(cb->aptAdapter(_kind, _bias), (int) paramN));
+  }
+  virtual ~EstimatorTreeSLAPT() {}
+  void estimate() {
+    dsr_apt* m = _cbsT->aptAdapter(_kind, _bias);
+    dsr_throw(dsr_apt_params_copy(dsr_apt_store(m, 0), _paramTree->handle()));
+    dsr_throw(dsr_apt_set_stats(m, 0, _cbsT->trainHandle())); dsr_throw(dsr_apt_estimate(m, _threshold, 0));
+    dsr_throw(dsr_apt_params_copy(_paramTree->handle(), dsr_apt_store(m, 0)));
+    if (!(_trace & 1)) return;
+    int n = 0; dsr_throw(dsr_apt_get_plan(m, &n, 0)); std::vector<int32_t> p((size_t) 3 * (n > 0 ? n : 1)); dsr_throw(dsr_apt_get_plan(m, &n, p.data()));
+    for (int i = 0; i < n; i++) if (p[3 * i + 1] != p[3 * i + 2]) printf("Backing off from node %d to node %d.\n", p[3 * i + 2], p[3 * i + 1]);
+    fflush(stdout);
+  }
+  void writeParams(const String& fileName) { _paramTree->write(fileName); }
+  APTParamTreePtr& paramTree() { return _paramTree; }
+  void transform() { adaptCbk(_cbsT, _paramTree); }
+ private:
+  CodebookSetTrainPtr _cbsT; APTParamTreePtr _paramTree; int _kind, _bias, _trace; float _threshold;
+};
+typedef std::shared_ptr<EstimatorTreeSLAPT> EstimatorTreeSLAPTPtr;
+class EstimatorTreeBLT : public EstimatorTreeSLAPT {
+ public:
+  EstimatorTreeBLT(CodebookSetTrainPtr& cb, APTParamTreePtr& paramTree, const String& biasType = "CepstraOnly", int trace = 1, float threshold = 150.0f)
+    : EstimatorTreeSLAPT(cb, paramTree, biasType, 1, 10, trace, threshold, APT_RAPT) {}
+};
+typedef std::shared_ptr<EstimatorTreeBLT> EstimatorTreeBLTPtr;
+inline void estimateAdaptationParameters(EstimatorTreeSLAPTPtr& tree) { tree->estimate(); }
+inline void estimateAdaptationParameters(EstimatorTreeBLTPtr& tree) { tree->estimate(); }
 
 // ---- asr/train/fsa.h, train.i:531-590: FeatureSpaceAdaptationFeature(src, maxAccu, maxTran, nm), feature-space adaptation (constrained MLLR).
 // A feature stream that delivers src under transformation 0, and the estimator of such transformations over dsr_fsa_* (include/dsr.h section 11).

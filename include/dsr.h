@@ -2252,8 +2252,9 @@ dsr_status dsr_train_kernel_ms(const dsr_train*, float ms[2]);
 
 /* =====================================================================================
  * 10. MLLR speaker adaptation: regression classes, parameter trees, estimation, mean transforms
- *    Replaces the MLLR branch of asr/adapt/transform.{h,cc} ("tr") and asr/train/estimateAdapt.{h,cc} ("eA"); the all-pass transforms
- *    (RAPT, SLAPT, BLT), STC, LDA and asr/sat are not implemented.
+ *    Replaces the MLLR branch of asr/adapt/transform.{h,cc} ("tr") and asr/train/estimateAdapt.{h,cc} ("eA").  The all-pass transforms
+ *    are section 13 (BLT and SLAPT with one estimated parameter; RAPT with more parameters and the multi-parameter Newton search are not
+ *    implemented), STC and LDA section 12; asr/sat is not implemented.
  * ===================================================================================== */
 /* The regression-class table of a model: CodebookBasic::_regClass (asr/gaussian/codebookBasic.cc:179-187).  dsr_gmm_load keeps the FIRST class
  * of each Gaussian of a codebook file whose regClassPresent is set (:286-297) -- GaussDensity::regClass() (codebookBasic.h:275-280) -- and
@@ -2563,6 +2564,109 @@ dsr_stc* dsr_stc_feature_handle(dsr_stream*);
 dsr_status dsr_lda_feature_create(dsr_stream* src, int outDim, const char* name, dsr_stream** out);
 dsr_status dsr_lda_feature_codebooks(dsr_stream*, dsr_gmm*, dsr_gmm* global);
 dsr_lda* dsr_lda_feature_handle(dsr_stream*);
+
+/* ---------------------------------------------------------------------------------------------------------------------------------------
+ * 13. All-pass transform (APT) speaker adaptation: the bilinear transform (BLT) and the sine-log all-pass transform (SLAPT)
+ *     (csrc/apt_kernels.hip, csrc/apt.cpp)
+ *
+ *    Replaces LaurentSeries, APTParamBase / RAPTParam / SLAPTParam, ParamTree::findAPT, BLTTransformer and SLAPTTransformer
+ *    (asr/adapt/transform.cc, "tr": 39-101, 410-551, 862-896, 1199-1430, 1636-1741) and BLTEstimatorAdapt, SLAPTEstimatorAdapt with one
+ *    parameter, EstimatorBase::bracket / brentsMethod (asr/train/estimateAdapt.cc, "eA": 81-255, 821-830, 1544-1690, 1851-1929, 2026-2045).
+ *    A cepstral mean of nSubFeat sub-features of subFeatLen (flat index isub subFeatLen + n) is mapped by one subFeatLen x subFeatLen
+ *    matrix per regression class, read off the powers of a Laurent series Q(z) of 150 coefficients a side, plus an optional bias.
+ *    Not implemented, and refused: RAPT with more than one parameter, estimation of more than one parameter (the Newton search with
+ *    gradient and Hessian matrices), an ldaFile, extended means (orgSubFeatLen != subFeatLen), asr/sat.
+ *
+ *  Parameters (host only: needs no device).  A dsr_apt_params is the ParamTree of one speaker, of RAPTParam or of SLAPTParam; dsr_param_tree
+ *  keeps refusing these files.  type: 0 unspecified, 1 RAPT, 2 SLAPT (AdaptationType + 1).
+ *   create / read   one parameter per <AdaptType> ... <EndClass> block (tr:339-407, 430-441, 927-950), numbers read with fscanf; DSR_E_TYPE for
+ *                   a file that does not start with <AdaptType>, DSR_E_PARAMETER for an MLLR block, for the other type's symbol inside a
+ *                   class or a second type inside a class (the jparameter_errors of _readParams), DSR_E_CONSISTENCY for blocks of both types
+ *                   or a file without parameters.  "" or NULL is an empty store
+ *   write           the classes in index order, class 0 written as 1, numbers with " %g"; RAPT writes fabs of its even-indexed parameters
+ *                   from index 2 on (tr:490-501)
+ *   find            ParamTree::findAPT (tr:862-896): DSR_E_CONSISTENCY for a store of the other type, DSR_E_INDEX for class 0 or a missing
+ *                   class without useAncestor; with it a missing class becomes a copy of its nearest ancestor (an empty one without)
+ *   get / set       _conf as doubles and the bias as floats; set goes through findAPT; sizes come from find
+ *   line_search     EstimatorBase::bracket + brentsMethod (eA:109-240) replayed on the n values lhood[] = calcLogLhood of the points it asked
+ *                   for so far; kind 1: b = 0, a = 0.1, range +-0.899 (BLT, eA:252-255, 1659-1665), 2: a = -0.05, b = 0, range +-100 (SLAPT,
+ *                   eA:821-826, 1544-1548).  *state = 0: *point is the next point to evaluate; 1: done, *point = alpha / xmin; 2: bracket met
+ *                   a NaN (eA:122-130) or Brent's method ran 100 iterations.  points [*nPoints] (or NULL): the points evaluated so far */
+typedef struct dsr_apt_params dsr_apt_params;
+dsr_status dsr_apt_params_create(const char* fileName, dsr_apt_params** out);
+void dsr_apt_params_destroy(dsr_apt_params*);
+dsr_status dsr_apt_params_clear(dsr_apt_params*);
+dsr_status dsr_apt_params_read(dsr_apt_params*, const char* fileName);
+dsr_status dsr_apt_params_write(const dsr_apt_params*, const char* fileName);
+dsr_status dsr_apt_params_copy(dsr_apt_params* dst, const dsr_apt_params* src);
+int dsr_apt_params_type(const dsr_apt_params*);
+int dsr_apt_params_indices(const dsr_apt_params*, unsigned* indices, int cap);
+dsr_status dsr_apt_params_find(dsr_apt_params*, unsigned rc, int type, int useAncestor, int* nConf, int* nBias);
+dsr_status dsr_apt_params_get(const dsr_apt_params*, unsigned rc, double* conf, float* bias);
+dsr_status dsr_apt_params_set(dsr_apt_params*, unsigned rc, int type, int nConf, const double* conf, int nBias, const float* bias);
+dsr_status dsr_apt_line_search(int kind, const double* lhood, int n, int* state, double* point, int* nPoints, double* points);
+
+/* APT for S speakers at once.  The handle copies the model's means (CodebookAdapt::_origRV), inverse variances and regression classes.
+ *   create             kind 1 (BLT: a RAPTParam of one parameter) or 2 (SLAPT); subFeatLen nSubFeat == dimN, nSubFeat <= 3, subFeatLen <= 48;
+ *                      biasType 0 NONE, 1 CepstraOnly (subFeatLen entries), 2 AllComponents (dimN entries) (eA:49-63, 1553-1563)
+ *   set_param_n        the number of parameters to estimate: DSR_E_PARAMETER unless 1
+ *   set_stats(_arrays) as dsr_mllr_set_stats(_arrays)
+ *   set / get_params   (conf [nConf], bias [nBias]) of slot s and class rc; get with NULL arrays returns the sizes
+ *   estimate           for every slot LeafIterator::estimate (eA:3105-3133) over the regression tree: a leaf whose ttlFrames (a double sum in
+ *                      model order) does not exceed `threshold` backs off to its nearest ancestor that does (node 1 at last); that node's
+ *                      Gaussians (class equal to it or below it) are searched and the result is stored under the LEAF's class.  There is no
+ *                      copying for a tree that is not MLLR, and a slot's other classes stay.  The search does not start from what is
+ *                      stored, so each (slot, node) is searched once.  The line searches run on the host; every round evaluates the trial
+ *                      points of all running searches in one launch each of k_apt_matrix and k_apt_lhood.  calcLogLhood (eA:1638-1657,
+ *                      1851-1884) is the reference's except that the bias sums of _calcBias and the sum over the Gaussians of _calcMixLhood
+ *                      are fp64 sums in a fixed order (the same call twice gives the same bits).  Stored: _conf = alpha (BLT) or xmin
+ *                      (SLAPT); the bias of _calcBias under the matrix at alpha (BLT, eA:1667-1668) or under the matrix of the LAST
+ *                      EVALUATED trial point (SLAPT, eA:1926: the series still in _laurentCoeffs), not xmin.  DSR_E_INDEX for a Gaussian of
+ *                      class 0; DSR_E_CONSISTENCY for a slot that holds parameters of the other type or (BLT) more than one; DSR_E_DIMENSION
+ *                      (SLAPT) for a stored bias of another size: nothing is estimated then.  A slot whose search met a NaN in bracket or
+ *                      ran 100 Brent iterations keeps its parameters and is flagged (speaker_status); the others are done and the call
+ *                      returns DSR_E_CONSISTENCY
+ *   get_plan           [n][3] = speaker, node, leaf;  get_nodes, ttl_frames as dsr_mllr;  rounds  the launches of each kernel in the last estimate
+ *   get_trace          the (point, logLhood) pairs, in order, that the last estimate evaluated for (slot, node), and the bias [n][bias size] of
+ *                      _calcBias at each; any array may be NULL.  DSR_E_KEY for a pair that was not searched
+ *   get_matrix         the subFeatLen x subFeatLen matrix of the parameters node(rc, useAncestor) of slot s holds (_calcTransMatrix,
+ *                      tr:1212-1242, of bilinear tr:1404-1414 or _calcSequence tr:1716-1741; any number <= 32 of SLAPT parameters): bit for
+ *                      bit the reference's arithmetic.  DSR_E_PARAMETER for |mu| >= 1, RAPT parameters other than one, no SLAPT parameters
+ *   adapt              TransformerTree::transform (tr:2149-2163) of slot s into `target`: every Gaussian takes node(regClass, useAncestor) --
+ *                      DSR_E_KEY without one -- and component (isub, n) becomes float(sum_m A[n][m] double(mean(isub, m))), m ascending, plus
+ *                      the float bias where it has an entry (tr:1295-1337).  A bias of another size than 0, subFeatLen or dimN is
+ *                      DSR_E_CONSISTENCY.  adapt_all: every slot into means_dev [S][G][dimN] (device);  reset_mean: the original means back
+ *   kernel_ms          milliseconds of k_apt_matrix and k_apt_lhood summed over the rounds of the last estimate, and of the last k_apt_apply */
+typedef struct dsr_apt dsr_apt;
+dsr_status dsr_apt_create(const dsr_gmm*, int S, int kind, int subFeatLen, int nSubFeat, int biasType, dsr_apt** out);
+void dsr_apt_destroy(dsr_apt*);
+int dsr_apt_num_speakers(const dsr_apt*);
+dsr_status dsr_apt_set_param_n(dsr_apt*, int paramN);
+dsr_status dsr_apt_set_stats(dsr_apt*, int s, dsr_train*);
+dsr_status dsr_apt_set_stats_arrays(dsr_apt*, int s, const double* c, const double* sumO);
+dsr_apt_params* dsr_apt_store(dsr_apt*, int s);
+dsr_status dsr_apt_set_params(dsr_apt*, int s, unsigned rc, int nConf, const double* conf, int nBias, const float* bias);
+dsr_status dsr_apt_get_params(const dsr_apt*, int s, unsigned rc, int* nConf, double* conf, int* nBias, float* bias);
+dsr_status dsr_apt_estimate(dsr_apt*, double threshold, void* stream);
+int dsr_apt_speaker_status(const dsr_apt*, int s);
+int dsr_apt_rounds(const dsr_apt*);
+dsr_status dsr_apt_get_plan(const dsr_apt*, int* n, int32_t* steps);
+dsr_status dsr_apt_get_nodes(const dsr_apt*, int* n, uint32_t* nodes, int32_t* isLeaf);
+dsr_status dsr_apt_ttl_frames(const dsr_apt*, int s, unsigned node, double* ttl);
+dsr_status dsr_apt_get_trace(const dsr_apt*, int s, unsigned node, int* n, double* points, double* lhood, float* bias);
+dsr_status dsr_apt_get_matrix(dsr_apt*, int s, unsigned rc, double* A);
+dsr_status dsr_apt_write(dsr_apt*, int s, const char* fileName);
+dsr_status dsr_apt_read(dsr_apt*, int s, const char* fileName);
+dsr_status dsr_apt_adapt(dsr_apt*, int s, dsr_gmm* target);
+dsr_status dsr_apt_adapt_all(dsr_apt*, float* means_dev, void* stream);
+dsr_status dsr_apt_reset_mean(dsr_apt*, dsr_gmm* target);
+dsr_status dsr_apt_set_timing(dsr_apt*, int on);
+dsr_status dsr_apt_kernel_ms(const dsr_apt*, float ms[3]);
+/* A transformer on its own (BLTTransformer(par, sbFtSz, nSubFt) / SLAPTTransformer(par, ...), tr:1379-1392, 1678-1698): the matrix of the
+ * parameters (A [subFeatLen][subFeatLen], or NULL) and transform(from, to) (tr:1295-1337) of N host rows [subFeatLen nSubFeat] into out, both
+ * computed on the device by k_apt_matrix and k_apt_apply.  The errors of get_matrix and adapt */
+dsr_status dsr_apt_transform_rows(int kind, int subFeatLen, int nSubFeat, int nConf, const double* conf, int nBias, const float* bias,
+                                  const float* rows, int N, double* A, float* out);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 // csrc/beamformer.h -- what the linear-array subband beamformer's files share: the handle dsr_bf (BfState), the functions through which the host
 // side (beamformer.cpp: weight design, the dsr_bf_* entries) reaches the kernels (k_beamform.hip), and what other units read of a beamformer:
-// the fused analysis + beamformer kernel (k_filterbank.hip), the post-filter behind a beamformer (k_postfilter.hip) and the maximum-kurtosis /
+// the fused analysis + beamformer entry (filterbank.cpp), the post-filter behind a beamformer (k_postfilter.hip) and the maximum-kurtosis /
 // maximum-negentropy estimators (mk_minimize.h).
 #pragma once
 #include "common.h"
@@ -41,7 +41,7 @@ struct dsr_bf : dsr::BfState {};
 namespace dsr {
 
 // ---- beamformer.cpp ----
-// the weights k_bf_apply would use, channel-major [C][M/2+2] on the device, for the fused analysis + beamformer kernel (k_filterbank.hip); null when the output is
+// the weights k_bf_apply would use, channel-major [C][M/2+2] on the device, for the fused analysis + beamformer kernel (dsr_fb_analysis_beamform, filterbank.cpp, hands them to k_filterbank.hip); null when the output is
 // not a fixed linear combination of the channels (SubbandGSCRLS adapting) or when all M bins are computed (halfBandShift)
 bool bf_has_fixed_weights(const dsr_bf* s);
 const float2* bf_fixed_weights_dev(dsr_bf* s);

@@ -12,23 +12,14 @@
 //   analysis : u_t[k] = sum_q h[k+qM] x[n_t-k-qM],  n_t = (t+laN+1)D-1,   X_t[f] = sum_k u_t[k] e^{+2 pi j fk/M}
 //   synthesis: v_tau[k] = Re sum_f Y_tau[f] e^{-2 pi j fk/M} (Hermitian extension, DC/Nyquist imaginary parts dropped)
 //              out_t[D-1-d] = sum_{i<R, t-R+1+i>=0} sum_q g[(M-1-k)+qM] v_{t-R+1+i+pd-Rq}[k],  k = d+iD
+//
+// This file holds the kernels, their launch arithmetic and the dispatch; the plans and the launchers' declarations are in filterbank.h, plan
+// construction and the C entries in filterbank.cpp.
 #include "launch.h"
 #include "dev_math.h"
-#include "beamformer.h"
-#include <cmath>
+#include "filterbank.h"
 
 namespace dsr {
-
-struct FbPlan {
-  int M, m, r, R, D, synthesis, dctype, gain, pd, laN;
-  std::vector<double> proto;
-  DevBuf<float> d_proto;     // [m*M] taps as fp32
-  DevBuf<float2> d_tw;       // tw[k] = e^{+2 pi j k / M}
-};
-
-// per-call frame bookkeeping: a whole-utterance call uses the plan's look-ahead and tail (laN, pd) and no history; a block of a longer stream
-// (dsr_fb_analysis_block / dsr_fb_synthesis_block) carries the samples / subband frames that came before it
-struct FbCall { int pd, laN; const float* hist; int histN; int tsMin; };
 
 // ---------------------------------------------------------------------------------------------
 // Stockham autosort FFT of `nfft` independent length-N sequences living in LDS (sequence f at
@@ -105,8 +96,7 @@ __global__ __launch_bounds__(256) void k_analysis(const float* __restrict__ x, c
   const int tile = blockIdx.x, c = blockIdx.y, u = blockIdx.z;
   const int t0 = tile * TF;
   const int nsamp = nsampArr[u];
-  const int nblk = (nsamp + D - 1) / D;
-  const int Tu = (nblk < laN) ? 0 : (nblk - laN + pd);
+  const int Tu = fb_frames(nsamp, D, laN, pd);
   const float* xs = x + ((long) u * C + c) * sampStride;
   float2* Xo = X + ((long) u * C + c) * (long) Tmax * (N + 1);
 
@@ -183,8 +173,7 @@ __global__ __launch_bounds__(256) void k_analysis_w(const float* __restrict__ x,
   const int tile = blockIdx.x, c = blockIdx.y, u = blockIdx.z;
   const int t0 = tile * TF;
   const int nsamp = nsampArr[u];
-  const int nblk = (nsamp + D - 1) / D;
-  const int Tu = (nblk < laN) ? 0 : (nblk - laN + pd);
+  const int Tu = fb_frames(nsamp, D, laN, pd);
   const float* xs = x + ((long) u * C + c) * sampStride;
   float2* Xo = X + ((long) u * C + c) * (long) Tmax * (N + 1);
 
@@ -413,7 +402,7 @@ template <int M> static void launch_analysis(const FbPlan& p, const FbCall& k, c
 //           lane + 64 leave as two contiguous 512-byte stores per row.
 // Per frame that is about a third of the vector instructions of the wave-per-frame kernel, which was bound by
 // instruction issue (wave64 on SIMD16: 4 cycles per instruction), not by memory.
-// LDS layout: [tw: M float2][win: winLen float][strip: waves x 576 float2]
+// LDS layout: q256_lds
 __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
 // V[k] = sum_e v[e] w8^(e k), w8 = exp(+2 pi j / 8); result in bit-reversed positions: V[k] = v[br3(k)]
@@ -435,34 +424,114 @@ __device__ __forceinline__ void fft8_pos(float2 (&v)[8])
   for (int h = 0; h < 8; h += 2) { const float2 a = cadd(v[h], v[h + 1]), b = csub(v[h], v[h + 1]); v[h] = a; v[h + 1] = b; }
 }
 
+// Sizes the two M = 256 kernels (k_analysis_q256, k_analysis_bf_q256) and their launchers share.  The window is stored with 32 floats of padding
+// after every 128 samples: consecutive frames (the 16-lane quarters of a wave) then start 160 floats apart and read from opposite halves of the
+// 64 LDS banks.  LDS: [tw: M float2][win, padded][hT: taps as pairs, hT[n + 128 qq] = (h[2n + qq M], h[2n + 1 + qq M])][strip: waves x SZ float2]
+struct Q256 {
+  static constexpr int M = 256, N = 128, D = 128;              // r = 1
+  static constexpr int SQ = 146, SK = 18, SZ = 4 * SQ;         // strip pitches: per frame / per k1 row (conflict-free both ways); strip size
+};
+#define DSR_Q256_WINLEN(MT, TF) (((TF) - 1) * Q256::D + (MT) * Q256::M)            /* logical samples of a tile's window */
+#define DSR_Q256_PADDED(n) ((n) + 32 * (((n) + 127) >> 7))                        /* floats they take */
+static size_t q256_lds(int MT, int TF, int waves)
+{
+  return sizeof(float2) * Q256::M + sizeof(float) * ((DSR_Q256_PADDED(DSR_Q256_WINLEN(MT, TF)) + 3) & ~3) + sizeof(float2) * (size_t) (Q256::M / 2) * MT +
+         sizeof(float2) * (size_t) waves * Q256::SZ;
+}
+
+// Even/odd split of frame fq of a wave's strip (natural-order Z, 144 float2 per frame): X[f] = (E + w O) g  with  E = (Z[f] + conj Z[N-f]) / 2,
+// O = -j (Z[f] - conj Z[N-f]) / 2  -- the halves and the gain are one exact scale factor gh, zero for the rows past the end of the utterance.
+// Returns the lane's bins 2 lane and 2 lane + 1: iz is their strip index, ic0 / ic1 those of the mirror bins, wf0 / wf1 = tw[2 lane], tw[2 lane + 1].
+// xN is bin N, X = Re(Z0) - Im(Z0) with imaginary part 0: read from Z[0] by every lane, or (LANE0) right only in lane 0, whose first bin is Z0.
+template <bool LANE0>
+__device__ __forceinline__ float4 q256_split(const float2* strip, int fq, int iz, int ic0, int ic1, float2 wf0, float2 wf1, float gh, float& xN)
+{
+  const float2* Z = strip + fq * 144;
+  const float4 zz = *reinterpret_cast<const float4*>(Z + iz);
+  const float2 zf0 = make_float2(zz.x, zz.y), zf1 = make_float2(zz.z, zz.w), zc0 = Z[ic0], zc1 = Z[ic1];
+  const float2 s0 = make_float2(zf0.x + zc0.x, zf0.y - zc0.y), d0 = make_float2(zf0.x - zc0.x, zf0.y + zc0.y);
+  const float2 s1 = make_float2(zf1.x + zc1.x, zf1.y - zc1.y), d1 = make_float2(zf1.x - zc1.x, zf1.y + zc1.y);
+  float4 o4;
+  o4.x = (s0.x + wf0.x * d0.y + wf0.y * d0.x) * gh; o4.y = (s0.y - wf0.x * d0.x + wf0.y * d0.y) * gh;
+  o4.z = (s1.x + wf1.x * d1.y + wf1.y * d1.x) * gh; o4.w = (s1.y - wf1.x * d1.x + wf1.y * d1.y) * gh;
+  const float2 Z0 = LANE0 ? zf0 : Z[0];
+  xN = (Z0.x - Z0.y) * 2.0f * gh;
+  return o4;
+}
+
+// The statements the two kernels share word for word are macros, as DSR_STAGE of k_analysis_w is, and not functions: the compiler simplifies a
+// function on its own before it inlines it, a force-inlined one too, and both kernels then compile to other code than they have.
+// A lane's constants.  l, q: point l + 16 e of frame q of the wave's four.  Twiddles: after pass 1  w_128^(l k1) = tw[2 l k1];  joining the halves of
+// pass 2  w_16^(k2) = tw[16 k2] on the odd half (read from the LDS table where they are used: sixteen complex constants per lane would cost registers
+// the taps need).  The even/odd split: the lane owns the adjacent bins 2 lane, 2 lane + 1; ic0, ic1: strip index of their mirror bins, iz: of bin 2 lane.
+#define DSR_Q256_POINT(lane) const int l = (lane) & 15, q = (lane) >> 4;
+#define DSR_Q256_LANE(lane, tw, gain) \
+  const int k1p = l >> 1, rr = l & 1; \
+  const int l2 = 2 * l, rr16 = rr ? 16 : 0; \
+  const float sgn = rr ? -1.f : 1.f; \
+  const float2 wf0 = (tw)[2 * (lane)], wf1 = (tw)[2 * (lane) + 1]; \
+  const int fc0 = (Q256::N - 2 * (lane)) & (Q256::N - 1), fc1 = (Q256::N - 2 * (lane) - 1) & (Q256::N - 1); \
+  const int ic0 = fc0 + 8 * (fc0 >> 6), ic1 = fc1 + 8 * (fc1 >> 6); \
+  const int iz = 2 * (lane) + 8 * ((lane) >> 5); \
+  const float g = ((gain) > 0) ? (float) (gain) : 1.0f;
+// v4 = samples n .. n + 3 of a row of nsamp samples, zero outside it; one 16-byte load where the row allows it (vec: base and pitch 16-byte aligned)
+#define DSR_LD_SAMPLE4(v4, xs, n, nsamp, vec) \
+  if ((vec) && (n) >= 0 && (n) + 3 < (nsamp)) v4 = *reinterpret_cast<const float4*>((xs) + (n)); \
+  else { v4.x = ((n) >= 0 && (n) < (nsamp)) ? (xs)[(n)] : 0.f; v4.y = ((n) + 1 >= 0 && (n) + 1 < (nsamp)) ? (xs)[(n) + 1] : 0.f; \
+         v4.z = ((n) + 2 >= 0 && (n) + 2 < (nsamp)) ? (xs)[(n) + 2] : 0.f; v4.w = ((n) + 3 >= 0 && (n) + 3 < (nsamp)) ? (xs)[(n) + 3] : 0.f; }
+// The wave's four frames tl .. tl + 3 of the padded window win -> their packed transforms Z in natural order, frame fq at strip + 144 fq.
+// pass 1: polyphase sums (wp: padded index of sample 128 (tl + q) - 2l; A: sample n_t - k0 - 1 - qq M relative to the frame's first block;
+// pr = (x[n_t-k0-1-qM], x[n_t-k0-qM])), 8-point DFT over e, turn.  pass 2: 8-point DFT over m (points l = 2m + rr), then the halves are joined
+// with the neighbouring lane (quad_perm [1,0,3,2]: lane ^ 1; tw[0] = 1 on the even half; even half: A0 + B, odd half: A0 - B).
+#define DSR_Q256_TRANSFORM(MT, win, tl, hT, tw, strip) \
+  constexpr int BR[8] = {0, 4, 2, 6, 1, 5, 3, 7}; \
+  float2 v[8]; \
+  const float* wp = (win) + ((tl) + q) * 160 - 2 * l; \
+  _Pragma("unroll") for (int e = 0; e < 8; e++) { \
+    float s0 = 0.f, s1 = 0.f; \
+    _Pragma("unroll") for (int qq = 0; qq < MT; qq++) { \
+      const int A = MT * Q256::M - 2 - 32 * e - 256 * qq; \
+      const float2 pr = *reinterpret_cast<const float2*>(wp + (A + 32 * (A >> 7))); \
+      const float2 hp = (hT)[l + 16 * e + (Q256::M / 2) * qq]; \
+      s0 += hp.x * pr.y; s1 += hp.y * pr.x; \
+    } \
+    v[e] = make_float2(s0, s1); \
+  } \
+  fft8_pos(v); \
+  _Pragma("unroll") for (int k = 0; k < 8; k++) (strip)[q * Q256::SQ + k * Q256::SK + l] = (k == 0) ? v[0] : cmulf(v[BR[k]], (tw)[(l2 * k) & (Q256::M - 1)]); \
+  wave_lds_sync(); \
+  _Pragma("unroll") for (int m2 = 0; m2 < 8; m2++) v[m2] = (strip)[q * Q256::SQ + k1p * Q256::SK + 2 * m2 + rr]; \
+  fft8_pos(v); \
+  wave_lds_sync(); \
+  _Pragma("unroll") for (int k = 0; k < 8; k++) { \
+    const float2 b = (k == 0) ? v[0] : cmulf(v[BR[k]], (tw)[rr16 * k]); \
+    const float ox = dpp_f<0xB1>(b.x), oy = dpp_f<0xB1>(b.y); \
+    const int f = k1p + 8 * k + 64 * rr; \
+    (strip)[q * 144 + f + 8 * rr] = make_float2(ox + sgn * b.x, oy + sgn * b.y); \
+  } \
+  wave_lds_sync();
+
 template <int MT, int PF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_analysis_q256(const float* __restrict__ x, const int* __restrict__ nsampArr,
                                                        const float* __restrict__ proto, const float2* __restrict__ twG,
                                                        float2* __restrict__ X, int C, long sampStride, int Tmax,
                                                        int pd, int laN, int gain, int TF, const float* __restrict__ hist, int histN)
 {
-  constexpr int M = 256, N = 128, D = 128;                     // r = 1
-  constexpr int NQ = 1;                                        // quads of frames a wave works on side by side (independent chains to interleave)
-  constexpr int SQ = 146, SK = 18, SZ = 4 * SQ;                // strip pitches: per frame / per k1 row (conflict-free both ways); strip size
-  constexpr int BR[8] = {0, 4, 2, 6, 1, 5, 3, 7};
+  constexpr int M = Q256::M, N = Q256::N, D = Q256::D;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  // The window is stored with 32 floats of padding after every 128 samples: consecutive frames (the 16-lane quarters of a
-  // wave) then start 160 floats apart and read from opposite halves of the 64 LDS banks.
-  const int winLen = (TF - 1) * D + MT * M;                    // logical samples
-  const int winPhys = winLen + 32 * ((winLen + 127) >> 7);
+  const int winLen = DSR_Q256_WINLEN(MT, TF), winPhys = DSR_Q256_PADDED(winLen);
   float2* tw = reinterpret_cast<float2*>(smem);
   float* win = reinterpret_cast<float*>(tw + M);
   const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, nwv = nthr >> 6;
-  float2* hT = reinterpret_cast<float2*>(win + ((winPhys + 3) & ~3));                      // taps as pairs: hT[n + 128 qq] = (h[2n + qq M], h[2n + 1 + qq M])
-  float2* strip = hT + (M / 2) * MT + wave * (NQ * SZ);
+  float2* hT = reinterpret_cast<float2*>(win + ((winPhys + 3) & ~3));
+  float2* strip = hT + (M / 2) * MT + wave * Q256::SZ;
   // A workgroup streams one (utterance, channel) row from start to end, TF frames at a time: taps and twiddles are set up
   // once per row, the samples of the next TF frames are fetched into registers while the current ones are transformed,
   // and the MT*M - D samples two tiles share stay in LDS.  (Workgroups that run at the same time work on different rows:
   // their addresses differ by the row pitches, not by a power-of-two tile pitch.)
   const int c = (int) (blockIdx.x % (unsigned) C), u = (int) (blockIdx.x / (unsigned) C);
   const int nsamp = nsampArr[u];
-  const int nblk = (nsamp + D - 1) / D;
-  const int Tu = (nblk < laN) ? 0 : (nblk - laN + pd);
+  const int Tu = fb_frames(nsamp, D, laN, pd);
   const float* xs = x + ((long) u * C + c) * sampStride;
   float2* Xo = X + ((long) u * C + c) * (long) Tmax * (N + 1);
 
@@ -474,21 +543,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   const int stepPhys = step + 32 * (step >> 7), keepPhys = keep + 32 * (keep >> 7);
   const bool vec = ((((uintptr_t) xs) | (uintptr_t) (sampStride * 4)) & 15) == 0;
   // PF float4 per thread bring in the next tile: step = TF D = 4 * PF * nthr samples (TF = 8 PF frames, 256 threads)
-  const int l = lane & 15, q = lane >> 4;
-  // prototype taps of this lane's points: h[2(l + 16e) + {0,1} + qq M]
+  DSR_Q256_POINT(lane)
+  // prototype taps as pairs, a lane's points: h[2(l + 16e) + {0,1} + qq M]
   for (int i = tid; i < (M / 2) * MT; i += nthr) hT[i] = *reinterpret_cast<const float2*>(proto + 2 * i);   // 2 (n + 128 qq) = 2n + qq M
   __syncthreads();
-  // twiddles: after pass 1  w_128^(l k1) = tw[2 l k1];  joining the halves of pass 2  w_16^(k2) = tw[16 k2] on the odd half
-  // (read from the LDS table where they are used: sixteen complex constants per lane would cost registers the taps need)
-  const int k1p = l >> 1, rr = l & 1;
-  const int l2 = 2 * l, rr16 = rr ? 16 : 0;
-  const float sgn = rr ? -1.f : 1.f;
-  // the even/odd split: lane owns the adjacent bins 2 lane, 2 lane + 1 (one 16-byte store per row and lane)
-  const float2 wf0 = tw[2 * lane], wf1 = tw[2 * lane + 1];
-  const int fc0 = (N - 2 * lane) & (N - 1), fc1 = (N - 2 * lane - 1) & (N - 1);
-  const int ic0 = fc0 + 8 * (fc0 >> 6), ic1 = fc1 + 8 * (fc1 >> 6);      // strip index of the mirror bins
-  const int iz = 2 * lane + 8 * (lane >> 5);                              // strip index of bin 2 lane (bin 2 lane + 1 follows)
-  const float g = (gain > 0) ? (float) gain : 1.0f;
+  DSR_Q256_LANE(lane, tw, gain)
 
   const int nTiles = (Tmax + TF - 1) / TF;
   for (int tile = 0; tile < nTiles; tile++) {
@@ -502,83 +561,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       for (int j = 0; j < PF; j++) {
         const int i4 = (j * nthr + tid) * 4; const long n = nlo + i4;
         float4 v4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i4 < step) {
-          if (vec && n >= 0 && n + 3 < nsamp) v4 = *reinterpret_cast<const float4*>(xs + n);
-          else { v4.x = (n >= 0 && n < nsamp) ? xs[n] : 0.f; v4.y = (n + 1 >= 0 && n + 1 < nsamp) ? xs[n + 1] : 0.f;
-                 v4.z = (n + 2 >= 0 && n + 2 < nsamp) ? xs[n + 2] : 0.f; v4.w = (n + 3 >= 0 && n + 3 < nsamp) ? xs[n + 3] : 0.f; }
-        }
+        if (i4 < step) { DSR_LD_SAMPLE4(v4, xs, n, nsamp, vec) }
         pf[j] = v4;
       }
     }
-    for (int tl = 4 * NQ * wave; tl < TF; tl += 4 * NQ * nwv) {
+    for (int tl = 4 * wave; tl < TF; tl += 4 * nwv) {
       if (t0 + tl >= Tmax) break;
-      // ---- pass 1: polyphase sums + 8-point DFT over e + turn
-      float2 v[NQ][8];
-#pragma unroll
-      for (int h = 0; h < NQ; h++) {
-        const float* wp = win + (tl + 4 * h + q) * 160 - 2 * l;          // padded index of sample  128 (tl + q) - 2l
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-          float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-          for (int qq = 0; qq < MT; qq++) {
-            const int A = MT * M - 2 - 32 * e - 256 * qq;                // sample n_t - k0 - 1 - qq M relative to the frame's first block
-            const float2 pr = *reinterpret_cast<const float2*>(wp + (A + 32 * (A >> 7)));     // (x[n_t-k0-1-qM], x[n_t-k0-qM])
-            const float2 hp = hT[l + 16 * e + (M / 2) * qq];
-            s0 += hp.x * pr.y; s1 += hp.y * pr.x;
-          }
-          v[h][e] = make_float2(s0, s1);
-        }
-      }
-#pragma unroll
-      for (int h = 0; h < NQ; h++) fft8_pos(v[h]);
-#pragma unroll
-      for (int h = 0; h < NQ; h++)
-#pragma unroll
-        for (int k = 0; k < 8; k++) strip[h * SZ + q * SQ + k * SK + l] = (k == 0) ? v[h][0] : cmulf(v[h][BR[k]], tw[(l2 * k) & (M - 1)]);
-      wave_lds_sync();
-      // ---- pass 2: 8-point DFT over m (points l = 2m + rr), join the halves with the neighbouring lane
-#pragma unroll
-      for (int h = 0; h < NQ; h++)
-#pragma unroll
-        for (int m2 = 0; m2 < 8; m2++) v[h][m2] = strip[h * SZ + q * SQ + k1p * SK + 2 * m2 + rr];
-#pragma unroll
-      for (int h = 0; h < NQ; h++) fft8_pos(v[h]);
-      wave_lds_sync();
-#pragma unroll
-      for (int h = 0; h < NQ; h++)
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-          const float2 b = (k == 0) ? v[h][0] : cmulf(v[h][BR[k]], tw[rr16 * k]);        // tw[0] = 1 on the even half
-          const float ox = dpp_f<0xB1>(b.x), oy = dpp_f<0xB1>(b.y);                      // quad_perm [1,0,3,2]: lane ^ 1
-          const int f = k1p + 8 * k + 64 * rr;                                           // even half: A0 + B, odd half: A0 - B
-          strip[h * SZ + q * 144 + f + 8 * rr] = make_float2(ox + sgn * b.x, oy + sgn * b.y);
-        }
-      wave_lds_sync();
-      // ---- even/odd split, one frame at a time: bins lane, lane + 64 (+ bin N by lane 0).
-      // X[f] = (E + w O) g  with  E = (Z[f] + conj Z[N-f]) / 2,  O = -j (Z[f] - conj Z[N-f]) / 2  -- the halves and the gain are
-      // one exact scale factor, zero for the rows past the end of the utterance.
+      DSR_Q256_TRANSFORM(MT, win, tl, hT, tw, strip)
+      // ---- even/odd split (q256_split), one frame at a time: bins 2 lane, 2 lane + 1 (+ bin N by lane 0).
       // (Measured and dropped, round 3: the quad's four rows packed in the strip and stored as ONE 16-byte-aligned run of 4128 bytes instead of four
       // 8-byte-aligned rows + four single-lane stores of bin N -- exact, 4.30 against 4.06 ms: the extra LDS traffic costs more than the aligned stores
       // save.  The kernel is LDS-bound: SQ_LDS_IDX_ACTIVE = 72 % of the CU-busy cycles, SQ_WAIT_INST_LDS = 18 % of the wave cycles (profiles/r03_fb_pmc.txt).)
 #pragma unroll
-      for (int fq = 0; fq < 4 * NQ; fq++) {
+      for (int fq = 0; fq < 4; fq++) {
         const int t = t0 + tl + fq;
         if (t < Tmax && tl + fq < TF) {
           float2* row = Xo + (long) t * (N + 1);
           const float gh = (t < Tu) ? 0.5f * g : 0.0f;
-          const float2* Z = strip + (fq >> 2) * SZ + (fq & 3) * 144;
-          const float4 zz = *reinterpret_cast<const float4*>(Z + iz);
-          const float2 zf0 = make_float2(zz.x, zz.y), zf1 = make_float2(zz.z, zz.w), zc0 = Z[ic0], zc1 = Z[ic1];
-          const float2 s0 = make_float2(zf0.x + zc0.x, zf0.y - zc0.y), d0 = make_float2(zf0.x - zc0.x, zf0.y + zc0.y);
-          const float2 s1 = make_float2(zf1.x + zc1.x, zf1.y - zc1.y), d1 = make_float2(zf1.x - zc1.x, zf1.y + zc1.y);
-          float4 o4;
-          o4.x = (s0.x + wf0.x * d0.y + wf0.y * d0.x) * gh; o4.y = (s0.y - wf0.x * d0.x + wf0.y * d0.y) * gh;
-          o4.z = (s1.x + wf1.x * d1.y + wf1.y * d1.x) * gh; o4.w = (s1.y - wf1.x * d1.x + wf1.y * d1.y) * gh;
+          float xN; const float4 o4 = q256_split<true>(strip, fq, iz, ic0, ic1, wf0, wf1, gh, xN);
           typedef float f4a8 __attribute__((ext_vector_type(4), aligned(8)));             // rows are 8-byte aligned: dwordx4 store, dword alignment suffices
           f4a8 ov = {o4.x, o4.y, o4.z, o4.w};
           __builtin_nontemporal_store(ov, reinterpret_cast<f4a8*>(reinterpret_cast<char*>(row) + 16 * lane));   // written once, read by the next kernel
-          if (lane == 0) row[N] = make_float2((zf0.x - zf0.y) * 2.0f * gh, 0.f);        // bin N: X = Re(Z0) - Im(Z0)
+          if (lane == 0) row[N] = make_float2(xN, 0.f);        // bin N: X = Re(Z0) - Im(Z0)
         }
       }
       wave_lds_sync();
@@ -604,32 +608,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 // X_c -- 2 x 10.4 GB of HBM traffic at 1000 utterances x 8 channels, written by one kernel and read back by the next -- never leave the chip.
 // A workgroup owns 16 frames of one utterance (4 waves x 4 frames, the shape of k_analysis_q256) and walks the channels: a channel's window (the
 // 16 frames' 2944 samples; consecutive tiles re-read the 896 they share) comes in through registers while the channel before is transformed,
-// passes and even/odd split are those of k_analysis_q256 operation for operation, and what that kernel stores as row t of channel c is weighted
+// passes and even/odd split are those of k_analysis_q256 (DSR_Q256_TRANSFORM, q256_split), and what that kernel stores as row t of channel c is weighted
 // and added, channel after channel in the order of k_bf_apply's loop, to accumulators of the lane's two bins (bin N: every lane, redundantly).
 // The weights come channel-major, WT[c][N + 2] (the beamformer object keeps that copy), straight from memory: a 16-byte load per lane and channel, issued a whole transform
-// ahead of its use (in LDS they cost the fourth workgroup per CU).
-// LDS: [tw: M float2][win][hT][strip: waves x 576 float2]
+// ahead of its use (in LDS they cost the fourth workgroup per CU).  LDS: q256_lds.
 template <int MT, int NW>
 __global__ __launch_bounds__(64 * NW) void k_analysis_bf_q256(const float* __restrict__ x, const int* __restrict__ nsampArr,
                                                           const float* __restrict__ proto, const float2* __restrict__ twG, const float2* __restrict__ WT,
                                                           float2* __restrict__ Y, int C, long sampStride, int Tmax, int pd, int laN, int gain)
 {
-  constexpr int M = 256, N = 128, D = 128, TF = 4 * NW, NT = 64 * NW;
-  constexpr int SQ = 146, SK = 18, SZ = 4 * SQ;
-  constexpr int BR[8] = {0, 4, 2, 6, 1, 5, 3, 7};
-  constexpr int winLen = (TF - 1) * D + MT * M;                // logical samples of a tile's window
-  constexpr int winPhys = winLen + 32 * ((winLen + 127) >> 7);
+  constexpr int M = Q256::M, N = Q256::N, D = Q256::D, TF = 4 * NW, NT = 64 * NW;
+  constexpr int winLen = DSR_Q256_WINLEN(MT, TF), winPhys = DSR_Q256_PADDED(winLen);
   constexpr int NL = (winLen / 4 + NT - 1) / NT;                 // float4 per thread that bring a window in
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float2* tw = reinterpret_cast<float2*>(smem);
   float* win = reinterpret_cast<float*>(tw + M);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float2* hT = reinterpret_cast<float2*>(win + ((winPhys + 3) & ~3));
-  float2* strip = hT + (M / 2) * MT + wave * SZ;
+  float2* strip = hT + (M / 2) * MT + wave * Q256::SZ;
   const int u = blockIdx.y, t0 = blockIdx.x * TF;
   const int nsamp = nsampArr[u];
-  const int nblk = (nsamp + D - 1) / D;
-  const int Tu = (nblk < laN) ? 0 : (nblk - laN + pd);
+  const int Tu = fb_frames(nsamp, D, laN, pd);
   const long lo = (long) (laN + 1) * D - (long) MT * M + (long) t0 * D;      // first sample of this tile's window (negative: zeros)
   const bool vec = ((((uintptr_t) x) | (uintptr_t) (sampStride * 4)) & 15) == 0;
 
@@ -639,11 +638,7 @@ __global__ __launch_bounds__(64 * NW) void k_analysis_bf_q256(const float* __res
     for (int j = 0; j < NL; j++) {
       const int i4 = (j * NT + tid) * 4; const long n = lo + i4;
       float4 v4 = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (i4 < winLen) {
-        if (vec && n >= 0 && n + 3 < nsamp) v4 = *reinterpret_cast<const float4*>(xs + n);
-        else { v4.x = (n >= 0 && n < nsamp) ? xs[n] : 0.f; v4.y = (n + 1 >= 0 && n + 1 < nsamp) ? xs[n + 1] : 0.f;
-               v4.z = (n + 2 >= 0 && n + 2 < nsamp) ? xs[n + 2] : 0.f; v4.w = (n + 3 >= 0 && n + 3 < nsamp) ? xs[n + 3] : 0.f; }
-      }
+      if (i4 < winLen) { DSR_LD_SAMPLE4(v4, xs, n, nsamp, vec) }
       pf[j] = v4;
     }
   };
@@ -652,15 +647,8 @@ __global__ __launch_bounds__(64 * NW) void k_analysis_bf_q256(const float* __res
   for (int i = tid; i < M; i += NT) tw[i] = twG[i];
   for (int i = tid; i < (M / 2) * MT; i += NT) hT[i] = *reinterpret_cast<const float2*>(proto + 2 * i);
   __syncthreads();
-  const int l = lane & 15, q = lane >> 4;
-  const int k1p = l >> 1, rr = l & 1;
-  const int l2 = 2 * l, rr16 = rr ? 16 : 0;
-  const float sgn = rr ? -1.f : 1.f;
-  const float2 wf0 = tw[2 * lane], wf1 = tw[2 * lane + 1];
-  const int fc0 = (N - 2 * lane) & (N - 1), fc1 = (N - 2 * lane - 1) & (N - 1);
-  const int ic0 = fc0 + 8 * (fc0 >> 6), ic1 = fc1 + 8 * (fc1 >> 6);
-  const int iz = 2 * lane + 8 * (lane >> 5);
-  const float g = (gain > 0) ? (float) gain : 1.0f;
+  DSR_Q256_POINT(lane)
+  DSR_Q256_LANE(lane, tw, gain)
   const int tl = 4 * wave;
 
   float4 acc[4]; float2 accN[4];
@@ -676,54 +664,13 @@ __global__ __launch_bounds__(64 * NW) void k_analysis_bf_q256(const float* __res
     const float4 w4 = *reinterpret_cast<const float4*>(WT + c * (N + 2) + 2 * lane);         // w[2 lane][c], w[2 lane + 1][c]
     const float2 wN = WT[c * (N + 2) + N];
     if (t0 + tl < Tmax) {
-      // ---- pass 1: polyphase sums + 8-point DFT over e + turn (k_analysis_q256)
-      float2 v[8];
-      {
-        const float* wp = win + (tl + q) * 160 - 2 * l;
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-          float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-          for (int qq = 0; qq < MT; qq++) {
-            const int A = MT * M - 2 - 32 * e - 256 * qq;
-            const float2 pr = *reinterpret_cast<const float2*>(wp + (A + 32 * (A >> 7)));
-            const float2 hp = hT[l + 16 * e + (M / 2) * qq];
-            s0 += hp.x * pr.y; s1 += hp.y * pr.x;
-          }
-          v[e] = make_float2(s0, s1);
-        }
-      }
-      fft8_pos(v);
-#pragma unroll
-      for (int k = 0; k < 8; k++) strip[q * SQ + k * SK + l] = (k == 0) ? v[0] : cmulf(v[BR[k]], tw[(l2 * k) & (M - 1)]);
-      wave_lds_sync();
-#pragma unroll
-      for (int m2 = 0; m2 < 8; m2++) v[m2] = strip[q * SQ + k1p * SK + 2 * m2 + rr];
-      fft8_pos(v);
-      wave_lds_sync();
-#pragma unroll
-      for (int k = 0; k < 8; k++) {
-        const float2 b = (k == 0) ? v[0] : cmulf(v[BR[k]], tw[rr16 * k]);
-        const float ox = dpp_f<0xB1>(b.x), oy = dpp_f<0xB1>(b.y);
-        const int f = k1p + 8 * k + 64 * rr;
-        strip[q * 144 + f + 8 * rr] = make_float2(ox + sgn * b.x, oy + sgn * b.y);
-      }
-      wave_lds_sync();
+      DSR_Q256_TRANSFORM(MT, win, tl, hT, tw, strip)
       // ---- even/odd split of one frame at a time, then conj(w) x as k_bf_apply adds it
 #pragma unroll
       for (int fq = 0; fq < 4; fq++) {
         const int t = t0 + tl + fq;
         const float gh = (t < Tu) ? 0.5f * g : 0.0f;
-        const float2* Z = strip + fq * 144;
-        const float4 zz = *reinterpret_cast<const float4*>(Z + iz);
-        const float2 zf0 = make_float2(zz.x, zz.y), zf1 = make_float2(zz.z, zz.w), zc0 = Z[ic0], zc1 = Z[ic1];
-        const float2 s0 = make_float2(zf0.x + zc0.x, zf0.y - zc0.y), d0 = make_float2(zf0.x - zc0.x, zf0.y + zc0.y);
-        const float2 s1 = make_float2(zf1.x + zc1.x, zf1.y - zc1.y), d1 = make_float2(zf1.x - zc1.x, zf1.y + zc1.y);
-        float4 o4;
-        o4.x = (s0.x + wf0.x * d0.y + wf0.y * d0.x) * gh; o4.y = (s0.y - wf0.x * d0.x + wf0.y * d0.y) * gh;
-        o4.z = (s1.x + wf1.x * d1.y + wf1.y * d1.x) * gh; o4.w = (s1.y - wf1.x * d1.x + wf1.y * d1.y) * gh;
-        const float2 Z0 = Z[0];
-        const float xN = (Z0.x - Z0.y) * 2.0f * gh;                                           // bin N: X = Re(Z0) - Im(Z0), imaginary part 0
+        float xN; const float4 o4 = q256_split<false>(strip, fq, iz, ic0, ic1, wf0, wf1, gh, xN);
         acc[fq].x += w4.x * o4.x + w4.y * o4.y; acc[fq].y += w4.x * o4.y - w4.y * o4.x;
         acc[fq].z += w4.z * o4.z + w4.w * o4.w; acc[fq].w += w4.z * o4.w - w4.w * o4.z;
         accN[fq].x += wN.x * xN + wN.y * 0.f; accN[fq].y += wN.x * 0.f - wN.y * xN;
@@ -924,12 +871,11 @@ template <int M, int MT> static void launch_analysis_w(const FbPlan& p, const Fb
 template <int MT> static void launch_analysis_q256(const FbPlan& p, const FbCall& k, const float* x, const int* nsamp, int U, int C,
                                                    long sampStride, int Tmax, float* X, hipStream_t st)
 {
-  constexpr int M = 256;
+  constexpr int M = Q256::M;
   int TF = 16; const int waves = 4;                            // TF = 16: one pass of the workgroup (4 waves x 4 frames) per tile, 4 workgroups per CU
   if (const char* e = getenv("DSR_FB_TF")) { const int v = atoi(e); if (v == 16 || v == 32) TF = v; }
   { const int keep = MT * M - p.D, keepPhys = keep + 32 * (keep >> 7); if (keepPhys > 2 * 4 * 64 * waves || TF * p.D > (TF / 8) * 4 * 64 * waves) throw Error(DSR_E_DIMENSION, "analysis tile does not fit the streaming kernel"); }
-  const int winLen = (TF - 1) * p.D + MT * M, winPhys = winLen + 32 * ((winLen + 127) >> 7);
-  size_t lds = sizeof(float2) * M + sizeof(float) * ((winPhys + 3) & ~3) + sizeof(float2) * (size_t) (M / 2) * MT + sizeof(float2) * (size_t) waves * 1 * 4 * 146;
+  size_t lds = q256_lds(MT, TF, waves);
   if (const char* e = getenv("DSR_FB_PADLDS")) lds += (size_t) atoi(e);          // occupancy experiments
   dim3 grid((unsigned) U * (unsigned) C, 1, 1);
   for_value(ints<2, 4>{}, TF / 8, [&](auto passes) {          // TF is 16 or 32
@@ -949,35 +895,44 @@ void fb_analysis(const FbPlan& p, const FbCall& k, const float* x, const int* ns
   }
   for_subbands(p.M, [&](auto M) { launch_analysis<M()>(p, k, x, nsamp, U, C, sampStride, Tmax, X, st); });
 }
-template <int M> static void launch_normal_fft(const float* x, const int* nsamp, const float* win, const float2* tw, int U, int C, long sampStride,
-                                               int Tmax, int D, float* X, hipStream_t st)
+
+// the whole-M FFT kernels (k_normal_fft, k_pr_analysis, k_pr_synth_fft): FB frames per workgroup, LDS [tw: M][bufA, bufB: FB x M] float2
+struct FftTile { int FB; size_t lds; explicit FftTile(int M) : FB(2048 / M < 1 ? 1 : 2048 / M), lds(sizeof(float2) * ((size_t) M + 2 * (size_t) FB * M)) {} };
+
+// (The launchers stand in the order in which the unit has always requested its instantiations -- analysis, STFT, synthesis, PR, fused last: that is
+// the kernels' order in the code object, and a kernel descriptor holds the distance to its code, so tools/kernel_bytes.py sees a reordering.)
+void fb_normal_fft(const StftPlan& p, const float* x, const int* nsamp, int U, int C, long sampStride, int Tmax, float* X, hipStream_t st)
 {
-  int FB = 2048 / M; if (FB < 1) FB = 1;
-  const size_t lds = sizeof(float2) * ((size_t) M + 2 * (size_t) FB * M);
-  dim3 grid(cdiv(Tmax, FB), C, U);
-  launch(k_normal_fft<M>, grid, dim3(256), lds, st, x, nsamp, win, tw, (float2*) X, C, sampStride, Tmax, D, FB);
-}
-void fb_normal_fft(int M, const float* x, const int* nsamp, const float* win, const float2* tw, int U, int C, long sampStride, int Tmax, int D,
-                   float* X, hipStream_t st)
-{
-  for_subbands(M, [&](auto m) { launch_normal_fft<m()>(x, nsamp, win, tw, U, C, sampStride, Tmax, D, X, st); });
-}
-struct PrPlan { int M, m, r, D; DevBuf<float> h; DevBuf<float2> tw, wA, wS; DevBuf<float> V; };
-template <int M2> static void launch_pr_analysis(const PrPlan& p, const float* x, const int* nsamp, int U, int C, long sampStride, int Tmax, float* X, hipStream_t st)
-{
-  int FB = 2048 / M2; if (FB < 1) FB = 1;
-  const size_t lds = sizeof(float2) * ((size_t) M2 + 2 * (size_t) FB * M2);
-  launch(k_pr_analysis<M2>, dim3(cdiv(Tmax, FB), C, U), dim3(256), lds, st, x, nsamp, p.h.p, p.tw.p, p.wA.p, (float2*) X, C, sampStride, Tmax, p.D, p.m, p.r, FB);
-}
-template <int M2> static void launch_pr_synth_fft(PrPlan& p, const float* Y, const int* nframes, int U, int Tmax, hipStream_t st)
-{
-  int FB = 2048 / M2; if (FB < 1) FB = 1;
-  const size_t lds = sizeof(float2) * ((size_t) M2 + 2 * (size_t) FB * M2);
-  launch(k_pr_synth_fft<M2>, dim3(cdiv(Tmax, FB), U), dim3(256), lds, st, (const float2*) Y, nframes, p.tw.p, p.wS.p, p.V.p, Tmax, FB);
+  for_subbands(p.M, [&](auto M) { const FftTile t(M());
+    launch(k_normal_fft<M()>, dim3(cdiv(Tmax, t.FB), C, U), dim3(256), t.lds, st, x, nsamp, p.win.p, p.tw.p, (float2*) X, C, sampStride, Tmax, p.D, t.FB); });
 }
 void fb_synthesis(const FbPlan& p, const FbCall& k, const float* Y, const int* nframes, int U, int Tmax, long outStride, float* y, hipStream_t st)
 {
   for_subbands(p.M, [&](auto M) { launch_synthesis<M()>(p, k, Y, nframes, U, Tmax, outStride, y, st); });
+}
+void fb_pr_analysis(const PrPlan& p, const float* x, const int* nsamp, int U, int C, long sampStride, int Tmax, float* X, hipStream_t st)
+{
+  for_subbands(2 * p.M, [&](auto M2) { const FftTile t(M2());
+    launch(k_pr_analysis<M2()>, dim3(cdiv(Tmax, t.FB), C, U), dim3(256), t.lds, st, x, nsamp, p.h.p, p.tw.p, p.wA.p, (float2*) X, C, sampStride, Tmax, p.D, p.m, p.r, t.FB); });
+}
+void fb_pr_synthesis(PrPlan& p, const float* Y, const int* nframes, int U, int Tmax, long outStride, float* y, hipStream_t st)
+{
+  p.V.reserve((size_t) U * Tmax * 2 * p.M);
+  for_subbands(2 * p.M, [&](auto M2) { const FftTile t(M2());
+    launch(k_pr_synth_fft<M2()>, dim3(cdiv(Tmax, t.FB), U), dim3(256), t.lds, st, (const float2*) Y, nframes, p.tw.p, p.wS.p, p.V.p, Tmax, t.FB); });
+  launch(k_pr_synth_out, dim3((unsigned) ((outStride + 255) / 256), U), dim3(256), 0, st, p.V.p, nframes, p.h.p, y, Tmax, 2 * p.M, p.D, p.m, p.r, outStride);
+}
+
+// the caller has checked that the plan is one k_analysis_bf_q256 is built for (M = 256, r = 1, m 2 or 4)
+void fb_analysis_beamform(const FbPlan& p, const float2* WT, const float* x, const int* nsamp, int U, int C, long sampStride, int Tmax, float* Y, hipStream_t st)
+{
+  int NW = 4; if (const char* e = getenv("DSR_FB_FUSED_WAVES")) { const int v = atoi(e); if (v == 4 || v == 8) NW = v; }
+  const int TF = 4 * NW;
+  const size_t lds = q256_lds(p.m, TF, NW);
+  dim3 grid((unsigned) cdiv(Tmax, TF), (unsigned) U);
+  for_value(ints<4, 2>{}, p.m, [&](auto mt) { for_value(ints<8, 4>{}, NW, [&](auto nw) {
+    launch(k_analysis_bf_q256<decltype(mt)::value, nw()>, grid, dim3(64 * nw()), lds, st, x, nsamp, p.d_proto.p, p.d_tw.p, WT, (float2*) Y, C, sampStride, Tmax, p.pd,
+           p.laN, p.gain); }); });
 }
 
 // carried history of a stream after a block: the last H items of (old history ++ the block's n valid items), item = one sample of a
@@ -998,268 +953,12 @@ __global__ void k_hist_update(const float* __restrict__ oldH, float* __restrict_
     newH[row * total + i] = v;
   }
 }
+void fb_hist_update(const float* oldH, float* newH, const float* blk, const int* n, int rows, int rowsPerStream, long blkRowStride, int H, int rowLen,
+                    bool haveOld, int gxMax, hipStream_t st)
+{
+  int gx = cdiv((long) H * rowLen, 256); if (gx < 1) gx = 1; if (gxMax && gx > gxMax) gx = gxMax;
+  launch(k_hist_update, dim3(gx, (unsigned) rows), dim3(256), 0, st, oldH, newH, blk, n, rowsPerStream, blkRowStride, H, rowLen, haveOld ? 1 : 0, 1);
+}
 
 }  // namespace dsr
 
-using namespace dsr;
-struct dsr_fb : FbPlan {};
-// state a filter bank carries from one block of a stream to the next (dsr_fb_analysis_block / dsr_fb_synthesis_block)
-struct dsr_fb_state { int U = 0, C = 0, H = 0, rowLen = 1; bool synthesis = false, started = false; long emitted = 0; int cur = 0; DevBuf<float> hist[2]; };
-
-extern "C" {
-
-// PerfectReconstructionFFTAnalysisBank / SynthesisBank (modulated.cc:686-970)
-struct dsr_prfb : PrPlan {};
-dsr_status dsr_prfb_create(const double* prototype, int M, int m, int r, dsr_prfb** out)
-{
-  return guard([&] {
-    if (!out || !prototype) throw Error(DSR_E_PARAMETER, "null argument");
-    if (!is_pow2((unsigned) M) || M < 8 || M > 1024) throw Error(DSR_E_DIMENSION, "M=%d must be a power of two in [8,1024]", M);
-    if (m < 1 || r < 0 || (M >> r) < 1) throw Error(DSR_E_DIMENSION, "bad m=%d r=%d", m, r);
-    require_device();
-    dsr_prfb* p = new dsr_prfb(); p->M = M; p->m = m; p->r = r; p->D = M >> r;
-    const int M2 = 2 * M;
-    std::vector<float> h((size_t) M2 * m); for (size_t i = 0; i < h.size(); i++) h[i] = (float) prototype[i];
-    std::vector<float2> tw(M2), wA(M2), wS(M2);
-    for (int i = 0; i < M2; i++) {
-      const double a = 2.0 * M_PI * (double) i / (double) M2, b = M_PI * (double) i / (double) M2;
-      tw[i] = make_float2((float) cos(a), (float) sin(a)); wA[i] = make_float2((float) cos(b), (float) -sin(b)); wS[i] = make_float2((float) cos(b), (float) sin(b));
-    }
-    p->h.upload(h); p->tw.upload(tw); p->wA.upload(wA); p->wS.upload(wS);
-    *out = p;
-  });
-}
-void dsr_prfb_destroy(dsr_prfb* p) { delete p; }
-int dsr_prfb_fft_len(const dsr_prfb* p) { return p ? 2 * p->M : 0; }
-int dsr_prfb_block_len(const dsr_prfb* p) { return p ? p->D : 0; }
-int dsr_prfb_analysis_frames(const dsr_prfb* p, int nsamp) { return p ? (nsamp + p->D - 1) / p->D + 2 * p->m - 1 : 0; }
-int dsr_prfb_synthesis_blocks(const dsr_prfb* p, int nframes) { return (p && nframes > 2 * p->m - 1) ? nframes - (2 * p->m - 1) : 0; }
-dsr_status dsr_prfb_analysis(const dsr_prfb* p, const float* x, const int32_t* nsamp_dev, int U, int C, int64_t sampStride, int Tmax, float* X, void* stream)
-{
-  return guard([&] {
-    if (!p || !x || !nsamp_dev || !X) throw Error(DSR_E_PARAMETER, "null argument");
-    if (U <= 0 || C <= 0 || Tmax <= 0) return;
-    hipStream_t st = (hipStream_t) stream;
-    for_subbands(2 * p->M, [&](auto M2) { launch_pr_analysis<M2()>(*p, x, nsamp_dev, U, C, sampStride, Tmax, X, st); });
-  });
-}
-dsr_status dsr_prfb_synthesis(dsr_prfb* p, const float* Y, const int32_t* nframes_dev, int U, int Tmax, int64_t outStride, float* y, void* stream)
-{
-  return guard([&] {
-    if (!p || !Y || !nframes_dev || !y) throw Error(DSR_E_PARAMETER, "null argument");
-    if (U <= 0 || Tmax <= 0 || outStride <= 0) return;
-    hipStream_t st = (hipStream_t) stream;
-    p->V.reserve((size_t) U * Tmax * 2 * p->M);
-    for_subbands(2 * p->M, [&](auto M2) { launch_pr_synth_fft<M2()>(*p, Y, nframes_dev, U, Tmax, st); });
-    launch(k_pr_synth_out, dim3((unsigned) ((outStride + 255) / 256), U), dim3(256), 0, st, p->V.p, nframes_dev, p->h.p, y, Tmax, 2 * p->M, p->D, p->m,
-                       p->r, (long) outStride);
-  });
-}
-
-// NormalFFTAnalysisBank (modulated.cc:121-257): windowType 0 rectangle, 1 Hamming (default), 2 Hanning (getWindow, :72-97)
-struct dsr_stft { int M, r, D, winType; DevBuf<float> win; DevBuf<float2> tw; };
-dsr_status dsr_stft_create(int M, int r, int windowType, dsr_stft** out)
-{
-  return guard([&] {
-    if (!out) throw Error(DSR_E_PARAMETER, "null argument");
-    if (!is_pow2((unsigned) M) || M < 16 || M > 2048) throw Error(DSR_E_DIMENSION, "M=%d must be a power of two in [16,2048]", M);
-    if (r < 0 || (M >> r) < 1) throw Error(DSR_E_DIMENSION, "bad r=%d", r);
-    require_device();
-    dsr_stft* p = new dsr_stft(); p->M = M; p->r = r; p->D = M >> r; p->winType = windowType;
-    std::vector<float> w(M); std::vector<float2> tw(M);
-    for (int i = 0; i < M; i++) {
-      double v;
-      switch (windowType) {
-      case 0: v = 1.0; break;
-      case 2: v = 0.5 * (1 - cos((2.0 * M_PI * i) / (double) (M - 1))); break;
-      default: { const double temp = 2. * M_PI / (double) (M - 1); v = 0.54 - 0.46 * cos(temp * i); } break;
-      }
-      w[i] = (float) v;
-      const double a = 2.0 * M_PI * (double) i / (double) M; tw[i] = make_float2((float) cos(a), (float) sin(a));
-    }
-    p->win.upload(w); p->tw.upload(tw);
-    *out = p;
-  });
-}
-void dsr_stft_destroy(dsr_stft* p) { delete p; }
-int dsr_stft_frames(const dsr_stft* p, int nsamp) { return p ? (nsamp + p->D - 1) / p->D + 1 : 0; }
-int dsr_stft_block_len(const dsr_stft* p) { return p ? p->D : 0; }
-dsr_status dsr_stft_analysis(const dsr_stft* p, const float* x, const int32_t* nsamp_dev, int U, int C, int64_t sampStride, int Tmax,
-                             float* X, void* stream)
-{
-  return guard([&] {
-    if (!p || !x || !nsamp_dev || !X) throw Error(DSR_E_PARAMETER, "null argument");
-    if (U <= 0 || C <= 0 || Tmax <= 0) return;
-    fb_normal_fft(p->M, x, nsamp_dev, p->win.p, p->tw.p, U, C, sampStride, Tmax, p->D, X, (hipStream_t) stream);
-  });
-}
-
-dsr_status dsr_fb_create(const double* prototype, int M, int m, int r, int synthesis, int dctype, int gain, dsr_fb** out)
-{
-  return guard([&] {
-    if (!out || !prototype) throw Error(DSR_E_PARAMETER, "null argument");
-    if (!is_pow2((unsigned) M) || M < 16 || M > 2048) throw Error(DSR_E_DIMENSION, "M=%d must be a power of two in [16,2048]", M);
-    if (m < 1 || r < 0 || (M >> r) < 1) throw Error(DSR_E_DIMENSION, "bad m=%d r=%d", m, r);
-    require_device();
-    dsr_fb* p = new dsr_fb();
-    p->M = M; p->m = m; p->r = r; p->R = 1 << r; p->D = M >> r; p->synthesis = synthesis; p->dctype = dctype; p->gain = gain;
-    // modulated.cc:279-296
-    p->laN = 0;
-    switch (dctype) {
-    case 1: p->pd = m * p->R - 1; break;
-    case 2: if (synthesis) p->pd = m * p->R / 2; else { p->pd = m * p->R - 1; p->laN = m * p->R / 2 - 1; } break;
-    default: p->pd = 2 * m - 1; break;
-    }
-    p->proto.assign(prototype, prototype + (size_t) m * M);
-    std::vector<float> pf((size_t) m * M); for (size_t i = 0; i < pf.size(); i++) pf[i] = (float) prototype[i];
-    std::vector<float2> tw(M);
-    for (int k = 0; k < M; k++) { double a = 2.0 * M_PI * k / M; tw[k] = make_float2((float) cos(a), (float) sin(a)); }
-    p->d_proto.upload(pf); p->d_tw.upload(tw);
-    *out = p;
-  });
-}
-void dsr_fb_destroy(dsr_fb* p) { delete p; }
-int dsr_fb_analysis_frames(const dsr_fb* p, int nsamp)
-{ int nblk = (nsamp + p->D - 1) / p->D; return nblk < p->laN ? 0 : nblk - p->laN + p->pd; }
-int dsr_fb_synthesis_blocks(const dsr_fb* p, int nframes) { return nframes - p->pd > 0 ? nframes - p->pd : 0; }
-int dsr_fb_processing_delay(const dsr_fb* p) { return p->pd; }
-int dsr_fb_block_len(const dsr_fb* p) { return p->D; }
-
-dsr_status dsr_fb_analysis(const dsr_fb* p, const float* x, const int32_t* nsamp, int U, int C, int64_t sampStride,
-                           int Tmax, float* X, void* stream)
-{
-  return guard([&] {
-    if (!p || !x || !nsamp || !X) throw Error(DSR_E_PARAMETER, "null argument");
-    if (p->synthesis) throw Error(DSR_E_CONSISTENCY, "plan was created for synthesis");
-    if (U <= 0 || C <= 0 || Tmax <= 0) return;
-    if (C > 65535 || U > 65535) throw Error(DSR_E_DIMENSION, "U and C must be <= 65535 per call");
-    const FbCall k = { p->pd, p->laN, nullptr, 0, 0 };
-    fb_analysis(*p, k, x, nsamp, U, C, (long) sampStride, Tmax, X, (hipStream_t) stream);
-  });
-}
-int dsr_fb_analysis_beamform_supported(const dsr_fb* p, const dsr_bf* bf)
-{
-  if (!p || !bf || p->synthesis || getenv("DSR_FB_GENERIC") || getenv("DSR_FB_WAVE") || getenv("DSR_FB_NOFUSE")) return 0;
-  if (!(p->M == 256 && p->r == 1 && (p->m == 2 || p->m == 4))) return 0;
-  const int C = dsr_bf_chan_n(bf);
-  return (dsr_bf_fft_len(bf) == p->M && !dsr_bf_half_band_shift(bf) && !dsr_bf_is_adaptive(bf) && C >= 1 && C <= 16) ? 1 : 0;
-}
-dsr_status dsr_fb_analysis_beamform(const dsr_fb* p, dsr_bf* bf, const float* x, const int32_t* nsamp, int U, int C, int64_t sampStride,
-                                    int Tmax, float* Y, void* stream)
-{
-  return guard([&] {
-    if (!p || !bf || !x || !nsamp || !Y) throw Error(DSR_E_PARAMETER, "null argument");
-    if (!dsr_fb_analysis_beamform_supported(p, bf)) throw Error(DSR_E_PARAMETER, "analysis + beamformer in one pass needs M = 256, r = 1, m in {2, 4}, at most 16 channels and fixed weights");
-    if (C != dsr_bf_chan_n(bf)) throw Error(DSR_E_DIMENSION, "beamformer has %d channels, input has %d", dsr_bf_chan_n(bf), C);
-    if (U <= 0 || Tmax <= 0) return;
-    if (U > 65535) throw Error(DSR_E_DIMENSION, "U must be <= 65535 per call");
-    const float2* W = bf_fixed_weights_dev(bf);
-    if (!W) throw Error(DSR_E_CONSISTENCY, "the beamformer has no fixed weights");
-    hipStream_t st = (hipStream_t) stream;
-    constexpr int M = 256;
-    const int MT = p->m;
-    int NW = 4; if (const char* e = getenv("DSR_FB_FUSED_WAVES")) { const int v = atoi(e); if (v == 4 || v == 8) NW = v; }
-    const int TF = 4 * NW;
-    const int winLen = (TF - 1) * p->D + MT * M, winPhys = winLen + 32 * ((winLen + 127) >> 7);
-    const size_t lds = sizeof(float2) * M + sizeof(float) * ((winPhys + 3) & ~3) + sizeof(float2) * (size_t) (M / 2) * MT + sizeof(float2) * (size_t) NW * 4 * 146;
-    dim3 grid((unsigned) cdiv(Tmax, TF), (unsigned) U);
-    for_value(ints<4, 2>{}, MT, [&](auto mt) { for_value(ints<8, 4>{}, NW, [&](auto nw) {      // dsr_fb_analysis_beamform_supported: m is 2 or 4
-      launch(k_analysis_bf_q256<decltype(mt)::value, nw()>, grid, dim3(64 * nw()), lds, st, x, nsamp, p->d_proto.p, p->d_tw.p, W, (float2*) Y, C, (long) sampStride, Tmax, p->pd,
-             p->laN, p->gain); }); });
-  });
-}
-dsr_status dsr_fb_synthesis(const dsr_fb* p, const float* Y, const int32_t* nframes, int U, int Tmax,
-                            int64_t outStride, float* y, void* stream)
-{
-  return guard([&] {
-    if (!p || !Y || !nframes || !y) throw Error(DSR_E_PARAMETER, "null argument");
-    if (!p->synthesis) throw Error(DSR_E_CONSISTENCY, "plan was created for analysis");
-    if (U <= 0 || Tmax <= 0 || outStride <= 0) return;
-    if (U > 65535) throw Error(DSR_E_DIMENSION, "U must be <= 65535 per call");
-    const FbCall k = { p->pd, 0, nullptr, 0, 0 };
-    fb_synthesis(*p, k, Y, nframes, U, Tmax, (long) outStride, y, (hipStream_t) stream);
-  });
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// Block-wise processing of long streams (BASELINE configs[4]: 10-minute streams in 10-second blocks).  The reference operators keep ring buffers
-// of the last m*M samples (analysis, modulated.h:79-163, modulated.cc:400-452) and of the last R*m subband frames (synthesis, :586-664); here
-// a state object carries exactly those between calls: m*M - D samples per (stream, channel), R*m - 1 subband frames per stream.
-dsr_status dsr_fb_state_create(const dsr_fb* p, int U, int C, dsr_fb_state** out)
-{
-  return guard([&] {
-    if (!p || !out || U < 1 || (!p->synthesis && C < 1)) throw Error(DSR_E_PARAMETER, "bad argument");
-    require_device();
-    dsr_fb_state* s = new dsr_fb_state(); s->U = U; s->synthesis = p->synthesis != 0;
-    if (p->synthesis) { s->C = 1; s->H = p->R * p->m - 1; s->rowLen = 2 * (p->M / 2 + 1); }
-    else { s->C = C; s->H = p->m * p->M - p->D; s->rowLen = 1; }
-    const size_t n = (size_t) U * s->C * (s->H > 0 ? s->H : 1) * s->rowLen;
-    s->hist[0].reserve(n); s->hist[1].reserve(n);
-    *out = s;
-  });
-}
-void dsr_fb_state_destroy(dsr_fb_state* s) { delete s; }
-dsr_status dsr_fb_state_reset(dsr_fb_state* s)
-{ return guard([&] { if (!s) throw Error(DSR_E_PARAMETER, "null argument"); s->started = false; s->emitted = 0; }); }
-
-// frames a block of nsampBlock new samples yields: the stream's first block spends the look-ahead (laN source blocks, delayCompensationType 2,
-// modulated.cc:467-474), its last one adds the processingDelay zero-input frames (:493-501)
-int dsr_fb_analysis_block_frames(const dsr_fb* p, const dsr_fb_state* s, int nsampBlock, int last)
-{
-  if (!p || !s) return 0;
-  const int nblk = (nsampBlock + p->D - 1) / p->D, la = s->started ? 0 : p->laN;
-  return nblk < la ? 0 : nblk - la + (last ? p->pd : 0);
-}
-dsr_status dsr_fb_analysis_block(const dsr_fb* p, dsr_fb_state* s, const float* x, const int32_t* nsamp_dev, int U, int C, int64_t sampStride,
-                                 int last, int Tmax, float* X, void* stream)
-{
-  return guard([&] {
-    if (!p || !s || !x || !nsamp_dev || !X) throw Error(DSR_E_PARAMETER, "null argument");
-    if (p->synthesis || s->synthesis) throw Error(DSR_E_CONSISTENCY, "plan / state were created for synthesis");
-    if (U != s->U || C != s->C) throw Error(DSR_E_DIMENSION, "state holds %d x %d rows, call has %d x %d", s->U, s->C, U, C);
-    if (s->H != p->m * p->M - p->D) throw Error(DSR_E_CONSISTENCY, "state belongs to another filter bank");
-    if (Tmax <= 0) return;
-    hipStream_t st = (hipStream_t) stream;
-    const FbCall k = { last ? p->pd : 0, s->started ? 0 : p->laN, s->started ? s->hist[s->cur].p : nullptr, s->H, 0 };
-    fb_analysis(*p, k, x, nsamp_dev, U, C, (long) sampStride, Tmax, X, st);
-    if (s->H > 0) {
-      int gx = cdiv(s->H, 256); if (gx < 1) gx = 1;
-      launch(k_hist_update, dim3(gx, (unsigned) U * C), dim3(256), 0, st, s->hist[s->cur].p, s->hist[s->cur ^ 1].p, x, nsamp_dev, C, (long) sampStride,
-                         s->H, 1, s->started ? 1 : 0, 1);
-      s->cur ^= 1;
-    }
-    s->started = true;
-  });
-}
-// output blocks a call with nframesBlock new subband frames yields: the first call keeps processingDelay frames of look-ahead back (modulated.cc:631-634)
-int dsr_fb_synthesis_block_blocks(const dsr_fb* p, const dsr_fb_state* s, int nframesBlock)
-{
-  if (!p || !s) return 0;
-  if (s->started) return nframesBlock;
-  return nframesBlock - p->pd > 0 ? nframesBlock - p->pd : 0;
-}
-dsr_status dsr_fb_synthesis_block(const dsr_fb* p, dsr_fb_state* s, const float* Y, const int32_t* nframes_dev, int nframesHostMax, int U, int Tmax,
-                                  int64_t outStride, float* y, void* stream)
-{
-  return guard([&] {
-    if (!p || !s || !Y || !nframes_dev || !y) throw Error(DSR_E_PARAMETER, "null argument");
-    if (!p->synthesis || !s->synthesis) throw Error(DSR_E_CONSISTENCY, "plan / state were created for analysis");
-    if (U != s->U) throw Error(DSR_E_DIMENSION, "state holds %d streams, call has %d", s->U, U);
-    if (s->H != p->R * p->m - 1) throw Error(DSR_E_CONSISTENCY, "state belongs to another filter bank");
-    if (Tmax <= 0 || outStride <= 0) return;
-    if (!s->started && nframesHostMax < p->pd + p->R * p->m) throw Error(DSR_E_DIMENSION, "the first block of a stream must hold at least %d subband frames", p->pd + p->R * p->m);
-    hipStream_t st = (hipStream_t) stream;
-    // later calls: local frame tau = absolute frame minus the frames of the calls before; the look-ahead is already inside the history shift
-    const FbCall k = { s->started ? 0 : p->pd, 0, s->started ? s->hist[s->cur].p : nullptr, s->H, s->started ? -(p->R - 1) : 0 };
-    fb_synthesis(*p, k, Y, nframes_dev, U, Tmax, (long) outStride, y, st);
-    if (s->H > 0) {
-      int gx = cdiv((long) s->H * s->rowLen, 256); if (gx < 1) gx = 1; if (gx > 64) gx = 64;
-      launch(k_hist_update, dim3(gx, (unsigned) U), dim3(256), 0, st, s->hist[s->cur].p, s->hist[s->cur ^ 1].p, Y, nframes_dev, 1, (long) Tmax * s->rowLen,
-                         s->H, s->rowLen, s->started ? 1 : 0, 1);
-      s->cur ^= 1;
-    }
-    s->started = true;
-  });
-}
-
-}  // extern "C"

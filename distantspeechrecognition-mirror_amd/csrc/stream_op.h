@@ -7,7 +7,8 @@
 // The reference pulls one frame at a time through virtual calls; here an operator materialises its whole
 // utterance on the device at the first next() after a reset() (every source of the path holds the full
 // utterance in memory: SampleFeature::_samples, feature.cc:300-340) and then serves rows of its own
-// host-side output buffer.  Compute always runs on the GPU (k_ops.hip / k_filterbank.hip / k_beamform.hip).
+// host-side output buffer.  Compute always runs on the GPU (k_ops.hip / k_filterbank.hip / k_beamform.hip, reached through the entries of
+// capi.cpp, filterbank.cpp and beamformer.cpp).
 //
 // One file per reference module, as dsr/btk/*.py and dsr/asr/*.py; an operator's struct is local to its file and followed by its entry points:
 //   streams.cpp               retain/release/size/type/name/next/current/reset, SampleFeature (with the RIFF reader), the frame source

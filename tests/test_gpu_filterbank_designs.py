@@ -1,4 +1,5 @@
-"""Every oversampled-DFT filter-bank kernel and design the dispatch of csrc/k_filterbank.hip can select, against the CPU oracle.
+"""Every oversampled-DFT filter-bank kernel and design the dispatch of csrc/k_filterbank.hip can select, through the entries and the block
+state of csrc/filterbank.cpp, against the CPU oracle.
 
 The rest of the GPU suite builds its FilterBank objects from the three prototypes the reference ships, which reach 2 of the 20 analysis
 instantiations, 1 of the 4 fused ones and 2 of the 8 synthesis ones.  Here a sweep of designs (tests/fb_np.py: one list per kernel family; the

@@ -1,8 +1,8 @@
 """The host half of the kernel units without a device.  csrc/value_list.h: ints<...> states the values a template is instantiated for once,
 has_value asks whether a run-time value is one of them, for_value hands the matching one to a callback as a compile-time constant (a small main,
 plain g++ -std=c++17, prints what the callback saw).  csrc/launch.h: the only file of csrc/ that launches a kernel or raises a kernel's dynamic-LDS
-limit, and no macro wraps it.  The beamformer family's kernel units (k_sph, k_beamform, k_mmi) hold no C entries, and no file restates another unit's
-declaration by hand."""
+limit, and no macro wraps it.  The beamformer family's kernel units (k_sph, k_beamform, k_mmi) and the filter bank's (k_filterbank) hold no C
+entries, and no file restates another unit's declaration by hand."""
 import glob
 import os
 import re
@@ -85,7 +85,7 @@ def test_kernels_are_launched_in_launch_h_only():
 
 
 def test_beamformer_kernel_units_hold_no_entries_and_no_unit_restates_a_declaration():
-    for name in ("k_sph.hip", "k_beamform.hip", "k_mmi.hip"):
+    for name in ("k_sph.hip", "k_beamform.hip", "k_mmi.hip", "k_filterbank.hip"):
         text = open(os.path.join(CSRC, name)).read()
         assert [s for s in ('extern "C"', "dsr_status") if s in text] == [], name
     restated = re.compile(r'^namespace dsr \{ .*\); *\}|extern "C" \{ namespace dsr \{')   # a one-line declaration of another unit's function

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $R/distantspeechrecognition-mirror_amd
 OBJ=${OBJ:-k_viterbi}
 OTHERS=$(ls lib/*.o | grep -v "/$OBJ.o")
-EXACT="-ffp-contract=off"; case $OBJ in k_filterbank|k_beamform) EXACT="";; esac
+EXACT="-ffp-contract=off"; case $OBJ in k_filterbank|k_beamform) EXACT="";; esac      # the Makefile's HIP_PLAIN units (host sides such as filterbank.cpp are not rebuilt here)
 while [ $# -gt 1 ]; do
   n=$1; fl=$2; shift 2; src=csrc/$OBJ.hip
   case $n in *=*) src=${n#*=}; n=${n%%=*};; esac

@@ -193,14 +193,6 @@ __global__ __launch_bounds__(256) void k_apt_apply(int L, int D, int G, const fl
 
 namespace {
 
-// device events around a launch; adds to *ms (the kernels of an estimate run once per round)
-struct Timer {
-  hipEvent_t a = nullptr, b = nullptr; bool on; hipStream_t st; float* ms;
-  Timer(bool on_, hipStream_t st_, float* ms_) : on(on_), st(st_), ms(ms_) { if (on) { DSR_HIP(hipEventCreate(&a)); DSR_HIP(hipEventCreate(&b)); DSR_HIP(hipEventRecord(a, st)); } }
-  void stop() { if (on) { float t = 0.f; DSR_HIP(hipEventRecord(b, st)); DSR_HIP(hipEventSynchronize(b)); DSR_HIP(hipEventElapsedTime(&t, a, b)); *ms += t; } }
-  ~Timer() { if (a) (void) hipEventDestroy(a); if (b) (void) hipEventDestroy(b); }
-};
-
 void check_slot(const AptHandle& h, int s) { if (s < 0 || s >= h.S) throw Error(DSR_E_INDEX, "speaker %d of %d", s, h.S); }
 
 int node_index(const AptHandle& h, unsigned node)
@@ -237,9 +229,9 @@ void run_matrix(AptHandle& h, int rapt, const std::vector<double>& conf, const s
 {
   const int n = (int) nPar.size();
   h.d_conf.upload(conf, st); h.d_nPar.upload(nPar, st); h.d_A.reserve((size_t) n * h.L * h.L);
-  Timer tm(h.timing, st, &h.ms[0]);
+  ScopedTimer tm(h.timing, st);
   launch(k_apt_matrix, dim3(n), dim3(kMatrixThreads), 0, st, rapt, h.L, h.d_conf.p, h.d_nPar.p, h.d_ecoef.p, h.d_A.p);
-  tm.stop();
+  h.ms[0] += tm.stop();
 }
 
 struct SearchState { int s, nodeIdx, state; double point; AptTrace tr; };
@@ -315,10 +307,10 @@ void apt_estimate(AptHandle& h, double threshold, hipStream_t st)
     run_matrix(h, h.kind == kAptRAPT, conf, nPar, st);
     h.d_trial.upload(trial, st); h.d_lhood.reserve(nA); h.d_bias.reserve((size_t) nA * std::max(bSize, 1));
     {
-      Timer tm(h.timing, st, &h.ms[1]);
+      ScopedTimer tm(h.timing, st);
       launch(k_apt_lhood, dim3(nA), dim3(kLhoodThreads), lds, st, L, D, G, bSize, h.d_trial.p, h.d_gidx.p, h.d_nodeStart.p, h.d_mean.p, h.d_ivar.p,
                           h.d_c.p, h.d_sumO.p, h.d_A.p, h.d_lhood.p, h.d_bias.p);
-      tm.stop();
+      h.ms[1] += tm.stop();
     }
     lh.resize(nA); bias.resize((size_t) nA * bSize);
     DSR_HIP(hipMemcpyAsync(lh.data(), h.d_lhood.p, nA * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -379,9 +371,9 @@ void run_apply(AptHandle& h, int s0, int s1, float* out, hipStream_t st)
   run_matrix(h, rapt == 1, conf, nPar, st);
   h.ms[0] = keep;                                         // ms[0] is the estimate's
   h.d_map.upload(map, st); h.d_tabBias.upload(tabBias, st); h.d_tabBsz.upload(bsz, st);
-  h.ms[2] = 0.f; Timer tm(h.timing, st, &h.ms[2]);
+  h.ms[2] = 0.f; ScopedTimer tm(h.timing, st);
   launch(k_apt_apply, dim3(cdiv((long) G * D, 256), s1 - s0), dim3(256), 0, st, h.L, D, G, h.d_mean.p, h.d_map.p, h.d_A.p, h.d_tabBias.p, h.d_tabBsz.p, out);
-  tm.stop();
+  h.ms[2] += tm.stop();
 }
 
 // the means, inverse variances and classes the handle works on ([G][subFeatLen nSubFeat]), zeroed statistics, eCoefficients (tr:1640-1650)

@@ -83,6 +83,28 @@ template <class T> struct PinBuf {
   }
 };
 
+// Kernel timing with HIP events, held in a handle (dsr_*_set_timing / dsr_*_kernel_ms): N events created by the first enable(true), recorded by
+// mark() around the launches while timing is on.
+template <int N> struct EventTimes {
+  bool on = false; hipEvent_t ev[N] = {};
+  EventTimes() = default; EventTimes(const EventTimes&) = delete; EventTimes& operator=(const EventTimes&) = delete;
+  ~EventTimes() { for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e); }
+  void enable(bool want) { if (want) { require_device(); for (hipEvent_t& e : ev) if (!e) DSR_HIP(hipEventCreate(&e)); } on = want; }
+  void mark(int i, hipStream_t st) const { if (on) DSR_HIP(hipEventRecord(ev[i], st)); }
+  void wait(int i) const { DSR_HIP(hipEventSynchronize(ev[i])); }
+  double ms(int a, int b) const { float t = 0; DSR_HIP(hipEventElapsedTime(&t, ev[a], ev[b])); return t; }      // both events reached (wait)
+};
+
+// Kernel timing of one scope: the events live from the constructor to the destructor; stop() waits for the stream and returns the milliseconds
+// since the constructor, 0 when timing is off.
+struct ScopedTimer {
+  hipEvent_t a = nullptr, b = nullptr; bool on; hipStream_t st;
+  ScopedTimer(bool on_, hipStream_t st_) : on(on_), st(st_) { if (on) { DSR_HIP(hipEventCreate(&a)); DSR_HIP(hipEventCreate(&b)); DSR_HIP(hipEventRecord(a, st)); } }
+  ScopedTimer(const ScopedTimer&) = delete; ScopedTimer& operator=(const ScopedTimer&) = delete;
+  float stop() { float t = 0.f; if (on) { DSR_HIP(hipEventRecord(b, st)); DSR_HIP(hipEventSynchronize(b)); DSR_HIP(hipEventElapsedTime(&t, a, b)); } return t; }
+  ~ScopedTimer() { if (a) (void) hipEventDestroy(a); if (b) (void) hipEventDestroy(b); }
+};
+
 #ifdef __HIPCC__
 // one complex value of a kernel's output row: complex128 when isDouble (the stream operators' rows), else complex64
 __device__ __forceinline__ void store_c(void* out, size_t i, double re, double im, int isDouble)

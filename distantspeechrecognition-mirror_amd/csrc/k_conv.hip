@@ -27,8 +27,7 @@ struct dsr_conv {
   int kind, L, P, N, C, size;
   std::vector<double> H;                            // [C][N/2+1] complex: the responses' half spectra
   DevBuf<double2> dH; bool haveH = false, uploaded = false;
-  bool timed = false; hipEvent_t ev[3] = {nullptr, nullptr, nullptr};                                      // dsr_conv_set_timing: around k_conv_fft and k_conv_fold
-  ~dsr_conv() { for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e); }
+  EventTimes<3> tm;                                 // dsr_conv_set_timing: around k_conv_fft and k_conv_fold
 };
 
 namespace {
@@ -275,7 +274,7 @@ dsr_status dsr_conv_apply(dsr_conv* q, const float* x_dev, const int32_t* nframe
     if (q->kind == 0) sc.sec.reserve((size_t) items * q->C * p.S);
     const int cap = mode == 0 ? CONV_GRID_LDS : (mode == 1 ? CONV_GRID_SPEC : CONV_GRID_GLOBAL);
     const int grid = (int) (items < cap ? items : cap);
-    if (q->timed) DSR_HIP(hipEventRecord(q->ev[0], st));
+    q->tm.mark(0, st);
     if (mode == 0) {
       const size_t ldsBytes = ((size_t) 4 * n + 2 * tw) * 8;
       launch(k_conv_fft<0>, dim3(grid), dim3(B), ldsBytes, st, x_dev, nframes_dev, q->dH.p, p, sc.sec.p, y_dev, (double*) nullptr, items);
@@ -287,7 +286,7 @@ dsr_status dsr_conv_apply(dsr_conv* q, const float* x_dev, const int32_t* nframe
       sc.work.reserve((size_t) grid * ((size_t) 4 * n + 2 * (size_t) tw));
       launch(k_conv_fft<2>, dim3(grid), dim3(B), 0, st, x_dev, nframes_dev, q->dH.p, p, sc.sec.p, y_dev, sc.work.p, items);
     }
-    if (q->timed) DSR_HIP(hipEventRecord(q->ev[1], st));
+    q->tm.mark(1, st);
     if (q->kind == 0) {
       const size_t stateN = (size_t) U * q->C * keep;
       sc.newState.reserve(stateN ? stateN : 1);
@@ -296,7 +295,7 @@ dsr_status dsr_conv_apply(dsr_conv* q, const float* x_dev, const int32_t* nframe
                          sc.newState.p, y_dev);
       if (stateN) DSR_HIP(hipMemcpyAsync(state_dev, sc.newState.p, stateN * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
-    if (q->timed) DSR_HIP(hipEventRecord(q->ev[2], st));
+    q->tm.mark(2, st);
   });
 }
 
@@ -304,17 +303,14 @@ dsr_status dsr_conv_set_timing(dsr_conv* q, int on)
 {
   return guard([&] {
     if (!q) throw Error(DSR_E_PARAMETER, "null argument");
-    if (on) { require_device(); for (hipEvent_t& e : q->ev) if (!e) DSR_HIP(hipEventCreate(&e)); }
-    q->timed = on != 0;
+    q->tm.enable(on != 0);
   });
 }
 dsr_status dsr_conv_kernel_ms(const dsr_conv* q, double* ms2)
 {
   return guard([&] {
-    if (!q || !ms2 || !q->timed) throw Error(DSR_E_PARAMETER, "timing is off");
-    float a = 0, b = 0;
-    DSR_HIP(hipEventSynchronize(q->ev[2])); DSR_HIP(hipEventElapsedTime(&a, q->ev[0], q->ev[1])); DSR_HIP(hipEventElapsedTime(&b, q->ev[1], q->ev[2]));
-    ms2[0] = a; ms2[1] = b;
+    if (!q || !ms2 || !q->tm.on) throw Error(DSR_E_PARAMETER, "timing is off");
+    q->tm.wait(2); ms2[0] = q->tm.ms(0, 1); ms2[1] = q->tm.ms(1, 2);
   });
 }
 

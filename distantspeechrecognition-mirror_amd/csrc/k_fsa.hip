@@ -165,13 +165,6 @@ __global__ __launch_bounds__(256) void k_fsa_apply(int D, long N, int nTran, con
 
 namespace {
 
-struct Timer {
-  hipEvent_t a = nullptr, b = nullptr; bool on; hipStream_t st; float* ms;
-  Timer(bool on_, hipStream_t st_, float* ms_) : on(on_), st(st_), ms(ms_) { if (on) { DSR_HIP(hipEventCreate(&a)); DSR_HIP(hipEventCreate(&b)); DSR_HIP(hipEventRecord(a, st)); } }
-  void stop() { if (on) { DSR_HIP(hipEventRecord(b, st)); DSR_HIP(hipEventSynchronize(b)); DSR_HIP(hipEventElapsedTime(ms, a, b)); } }
-  ~Timer() { if (a) (void) hipEventDestroy(a); if (b) (void) hipEventDestroy(b); }
-};
-
 struct Item { int accu, dist, frame; float gamma; long idx; };
 
 // M items of _accuOne (fsa:187-245).  accepted [nAccu] or nullptr: the items each accumulator took in this call; nearest [M] or nullptr: the
@@ -215,17 +208,17 @@ void fsa_accumulate(FsaHandle& h, const float* xScore, const float* xSrc, long N
   h.d_frame.upload(sFrame, st); h.d_dist.upload(sDist, st); h.d_gamma.upload(sGamma, st); h.d_chunk.upload(chunk, st); h.d_accChunk.upload(accChunk, st);
   h.d_gsel.reserve((size_t) A); h.d_part.reserve((size_t) nCh * sz); h.d_stats.reserve((size_t) nSlot * sz);
   {
-    Timer tm(h.timing, st, &h.ms[0]);
+    ScopedTimer tm(h.timing, st);
     launch(k_fsa_nearest, dim3(cdiv(A, 256)), dim3(256), 0, st, xScore, D, m.Dp, m.d_off.p, m.d_mean.p, m.d_ivar.p, m.d_cst.p, h.d_frame.p, h.d_dist.p, A,
                        h.d_gsel.p);
-    tm.stop();
+    h.ms[0] = tm.stop();
   }
   {
-    Timer tm(h.timing, st, &h.ms[1]);
+    ScopedTimer tm(h.timing, st);
     launch(k_fsa_stats, dim3(nCh), dim3(256), 0, st, D, h.NCp, h.PZ, xSrc, h.d_mean.p, h.d_ivar.p, h.d_frame.p, h.d_gamma.p, h.d_gsel.p, h.d_chunk.p,
                        h.d_pq.p, h.d_part.p);
     launch(k_fsa_reduce, dim3(cdiv((long) sz, 256), nSlot), dim3(256), 0, st, (long) sz, h.d_accChunk.p, h.d_part.p, h.d_stats.p);
-    tm.stop();
+    h.ms[1] = tm.stop();
   }
   std::vector<double> stats((size_t) nSlot * sz); std::vector<int> gsel(nearest ? A : 0);
   DSR_HIP(hipMemcpyAsync(stats.data(), h.d_stats.p, stats.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -269,15 +262,15 @@ void fsa_estimate(FsaHandle& h, int iterN, const int* accuX, const int* tranX, i
   {
     const int m = (N1 + 1) & ~1;
     const size_t lds = ((size_t) 2 * N1 * N1 + N1 + m + 2 * kEigThreads) * sizeof(double);
-    Timer tm(h.timing, st, &h.ms[2]);
+    ScopedTimer tm(h.timing, st);
     launch(k_fsa_eig, dim3(n * D), dim3(kEigThreads), lds, st, D, h.d_G.p, h.d_Ginv.p, h.d_flag.p);
-    tm.stop();
+    h.ms[2] = tm.stop();
   }
   {
     const size_t lds = FsaWork::doubles(D, kRowThreads) * sizeof(double) + (size_t) D * sizeof(int);
-    Timer tm(h.timing, st, &h.ms[3]);
+    ScopedTimer tm(h.timing, st);
     launch(k_fsa_rows, dim3(n), dim3(kRowThreads), lds, st, D, iterN, h.d_Ginv.p, h.d_z.p, h.d_beta.p, h.d_W.p, h.d_flag.p);
-    tm.stop();
+    h.ms[3] = tm.stop();
   }
   std::vector<int> flag(n);
   DSR_HIP(hipMemcpyAsync(W0.data(), h.d_W.p, W0.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -302,9 +295,9 @@ void fsa_apply(FsaHandle& h, const float* x, const int* tranOfRow, long N, float
   if (!x || !out) throw Error(DSR_E_PARAMETER, "null argument");
   if ((long) N * h.D > 0x7fffffffL * 256L) throw Error(DSR_E_DIMENSION, "%ld frames in one call", N);
   if (h.wDirty) { h.d_Wall.upload(h.W, st); h.wDirty = false; }
-  Timer tm(h.timing, st, &h.ms[4]);
+  ScopedTimer tm(h.timing, st);
   launch(k_fsa_apply, dim3(cdiv(N * h.D, 256)), dim3(256), 0, st, h.D, N, h.nTran, x, tranOfRow, h.d_Wall.p, shift, out);
-  tm.stop();
+  h.ms[4] = tm.stop();
 }
 
 }  // namespace dsr

@@ -203,13 +203,6 @@ void take_stats(const dsr_train& t, int G, int D, double* c, double* sumO)
 
 namespace {
 
-struct Timer {
-  hipEvent_t a = nullptr, b = nullptr; bool on; hipStream_t st; float* ms;
-  Timer(bool on_, hipStream_t st_, float* ms_) : on(on_), st(st_), ms(ms_) { if (on) { DSR_HIP(hipEventCreate(&a)); DSR_HIP(hipEventCreate(&b)); DSR_HIP(hipEventRecord(a, st)); } }
-  void stop() { if (on) { DSR_HIP(hipEventRecord(b, st)); DSR_HIP(hipEventSynchronize(b)); DSR_HIP(hipEventElapsedTime(ms, a, b)); } }
-  ~Timer() { if (a) (void) hipEventDestroy(a); if (b) (void) hipEventDestroy(b); }
-};
-
 void check_slot(const MllrHandle& h, int s) { if (s < 0 || s >= h.S) throw Error(DSR_E_INDEX, "speaker %d of %d", s, h.S); }
 
 int node_index(const MllrHandle& h, unsigned node)
@@ -285,12 +278,12 @@ void mllr_estimate(MllrHandle& h, double threshold, hipStream_t st)
   const size_t sz = (size_t) D * h.NCp;
   h.d_part.reserve((size_t) S * nCh * sz); h.d_partTtl.reserve((size_t) S * nCh); h.d_stats.reserve((size_t) S * NN * sz); h.d_ttl.reserve((size_t) S * NN);
   {
-    Timer tm(h.timing, st, &h.ms[0]);
+    ScopedTimer tm(h.timing, st);
     launch(k_mllr_stats, dim3(nCh, S), dim3(256), 0, st, D, G, h.NCp, h.PZ, h.d_mean.p, h.d_ivar.p, h.d_c.p, h.d_sumO.p, h.d_gidx.p, h.d_chunk.p,
                        h.d_pq.p, h.d_part.p, h.d_partTtl.p);
     launch(k_mllr_reduce, dim3(NN, S), dim3(256), 0, st, D, h.NCp, nCh, h.d_leafChunk.p, h.d_nodeLeafStart.p, h.d_nodeLeaf.p, h.d_part.p,
                        h.d_partTtl.p, h.d_stats.p, h.d_ttl.p);
-    tm.stop();
+    h.ms[0] = tm.stop();
   }
   h.ttl.assign((size_t) S * NN, 0.0);
   DSR_HIP(hipMemcpyAsync(h.ttl.data(), h.d_ttl.p, h.ttl.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -316,9 +309,9 @@ void mllr_estimate(MllrHandle& h, double threshold, hipStream_t st)
     const size_t lds = ((size_t) 2 * N1 * N1 + 2 * N1 + m + 2 * kSolveThreads) * sizeof(double);
     h.d_solve.upload(solve, st); h.d_W.reserve(W.size()); h.d_flag.reserve(nSolve);
     DSR_HIP(hipMemsetAsync(h.d_flag.p, 0, nSolve * sizeof(int), st));
-    Timer tm(h.timing, st, &h.ms[1]);
+    ScopedTimer tm(h.timing, st);
     launch(k_mllr_solve, dim3(nSolve * D), dim3(kSolveThreads), lds, st, D, NN, h.NCp, h.PZ, h.d_solve.p, h.d_stats.p, h.d_W.p, h.d_flag.p);
-    tm.stop();
+    h.ms[1] = tm.stop();
     DSR_HIP(hipMemcpyAsync(W.data(), h.d_W.p, W.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     DSR_HIP(hipMemcpyAsync(flag.data(), h.d_flag.p, nSolve * sizeof(int), hipMemcpyDeviceToHost, st));
     DSR_HIP(hipStreamSynchronize(st));
@@ -342,9 +335,9 @@ void run_apply(MllrHandle& h, int s0, int s1, float* out, hipStream_t st)
 {
   std::vector<double> tab; std::vector<int> map; build_tables(h, s0, s1, tab, map);
   h.d_Wtab.upload(tab, st); h.d_map.upload(map, st);
-  Timer tm(h.timing, st, &h.ms[2]);
+  ScopedTimer tm(h.timing, st);
   launch(k_mllr_apply, dim3(cdiv((long) h.G * h.D, 256), s1 - s0), dim3(256), 0, st, h.D, h.G, h.d_mean.p, h.d_map.p, h.d_Wtab.p, out);
-  tm.stop();
+  h.ms[2] = tm.stop();
 }
 
 void check_target(const MllrHandle& h, const dsr_gmm* g)

@@ -245,13 +245,6 @@ __global__ __launch_bounds__(256) void k_stc_apply(int Din, int outDim, long N, 
 
 namespace {
 
-struct Timer {
-  hipEvent_t a = nullptr, b = nullptr; bool on; hipStream_t st; float* ms;
-  Timer(bool on_, hipStream_t st_, float* ms_) : on(on_), st(st_), ms(ms_) { if (on) { DSR_HIP(hipEventCreate(&a)); DSR_HIP(hipEventCreate(&b)); DSR_HIP(hipEventRecord(a, st)); } }
-  void stop() { if (on) { DSR_HIP(hipEventRecord(b, st)); DSR_HIP(hipEventSynchronize(b)); DSR_HIP(hipEventElapsedTime(ms, a, b)); } }
-  ~Timer() { if (a) (void) hipEventDestroy(a); if (b) (void) hipEventDestroy(b); }
-};
-
 struct Item { int est, dist, frame; float fac; long idx; };
 struct Plan {
   std::vector<Item> items;                                // sorted by estimator, then codebook
@@ -290,10 +283,10 @@ void plan_items(XfBase& h, const float* xScore, long N, const int* frame, const 
   h.d_frame.upload(sFrame, st); h.d_dist.upload(sDist, st); h.d_fac.upload(sFac, st); h.d_chunk.upload(p.chunk, st); h.d_accChunk.upload(p.accChunk, st);
   h.d_gsel.reserve((size_t) M); h.d_score.reserve((size_t) M);
   {
-    Timer tm(h.timing, st, &h.ms[0]);
+    ScopedTimer tm(h.timing, st);
     launch(k_stc_nearest, dim3(cdiv(M, 256)), dim3(256), 0, st, xScore, h.D, m.Dp, m.d_off.p, m.d_mean.p, m.d_ivar.p, m.d_cst.p, m.d_val.p, m.d_scale.p,
                        h.d_frame.p, h.d_dist.p, M, h.d_gsel.p, h.d_score.p);
-    tm.stop();
+    h.ms[0] = tm.stop();
   }
   p.gsel.resize((size_t) M); p.score.resize((size_t) M);
   DSR_HIP(hipMemcpyAsync(p.gsel.data(), h.d_gsel.p, (size_t) M * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -323,11 +316,11 @@ void stc_accumulate(StcHandle& h, const float* xScore, const float* xSrc, long N
   h.d_part.reserve((size_t) p.nCh * sz); h.d_stats.reserve((size_t) p.nSlot * sz);
   if (h.cascade && h.aDirty) { h.d_Aall.upload(h.A, st); h.aDirty = false; }
   {
-    Timer tm(h.timing, st, &h.ms[1]);
+    ScopedTimer tm(h.timing, st);
     launch(k_stc_stats, dim3(p.nCh), dim3(256), 0, st, D, h.NCp, h.PZ, xSrc, h.cascade ? h.d_Aall.p : (const double*) nullptr, h.d_mean.p, h.d_ivar.p,
                        h.d_frame.p, h.d_fac.p, h.d_gsel.p, h.d_chunk.p, h.d_pq.p, h.d_part.p);
     launch(k_stc_reduce, dim3(cdiv((long) sz, 256), p.nSlot), dim3(256), 0, st, (long) sz, 0, h.d_accChunk.p, h.d_part.p, h.d_stats.p);
-    tm.stop();
+    h.ms[1] = tm.stop();
   }
   std::vector<double> stats((size_t) p.nSlot * sz);
   DSR_HIP(hipMemcpyAsync(stats.data(), h.d_stats.p, stats.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -372,10 +365,10 @@ void lda_accumulate(LdaHandle& h, const float* xScore, const float* xSrc, long N
   const size_t sz = (size_t) 3 * D * D;
   h.d_part.reserve((size_t) p.nCh * sz); h.d_stats.reserve((size_t) p.nSlot * sz);
   {
-    Timer tm(h.timing, st, &h.ms[1]);
+    ScopedTimer tm(h.timing, st);
     launch(k_lda_stats, dim3(p.nCh), dim3(256), 0, st, D, xSrc, h.d_mean.p, h.d_mu0.p, h.d_frame.p, h.d_fac.p, h.d_gsel.p, h.d_chunk.p, h.d_part.p);
     launch(k_stc_reduce, dim3(cdiv((long) sz, 256), p.nSlot), dim3(256), 0, st, (long) sz, D, h.d_accChunk.p, h.d_part.p, h.d_stats.p);
-    tm.stop();
+    h.ms[1] = tm.stop();
   }
   std::vector<double> stats((size_t) p.nSlot * sz);
   DSR_HIP(hipMemcpyAsync(stats.data(), h.d_stats.p, stats.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -425,9 +418,9 @@ void stc_estimate(StcHandle& h, const int* estX, int n, double minE, double mult
       h.d_G.upload(G, st);
       DSR_HIP(hipMemsetAsync(h.d_flag.p, 0, (size_t) n * sizeof(int), st));
       {
-        float ms = 0.0f; Timer tm(h.timing, st, &ms);
+        ScopedTimer tm(h.timing, st);
         launch(k_stc_eig, dim3(n * D), dim3(kEigThreads), ldsE, st, D, h.d_G.p, h.d_Ginv.p, h.d_ev.p, h.d_flag.p);
-        tm.stop(); h.ms[2] += ms;
+        h.ms[2] += tm.stop();
       }
       std::vector<int> f(n);
       DSR_HIP(hipMemcpyAsync(ev.data(), h.d_ev.p, ev.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -464,9 +457,9 @@ void stc_estimate(StcHandle& h, const int* estX, int n, double minE, double mult
     std::vector<int> f(n);
     DSR_HIP(hipMemsetAsync(h.d_flag.p, 0, (size_t) n * sizeof(int), st));
     {
-      float ms = 0.0f; Timer tm(h.timing, st, &ms);
+      ScopedTimer tm(h.timing, st);
       launch(k_stc_eig, dim3(n * D), dim3(kEigThreads), ldsE, st, D, h.d_G.p, h.d_Ginv.p, h.d_ev.p, h.d_flag.p);
-      tm.stop(); h.ms[2] += ms;
+      h.ms[2] += tm.stop();
     }
     DSR_HIP(hipMemcpyAsync(ev.data(), h.d_ev.p, ev.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     DSR_HIP(hipMemcpyAsync(f.data(), h.d_flag.p, (size_t) n * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -480,9 +473,9 @@ void stc_estimate(StcHandle& h, const int* estX, int n, double minE, double mult
   h.d_flag.upload(flag, st);
   {
     const size_t lds = StcWork::doubles(D, kRowThreads) * sizeof(double) + (size_t) D * sizeof(int);
-    Timer tm(h.timing, st, &h.ms[3]);
+    ScopedTimer tm(h.timing, st);
     launch(k_stc_rows, dim3(n), dim3(kRowThreads), lds, st, D, kStcMaxItns, h.d_Ginv.p, h.d_gamma.p, h.d_A.p, h.d_Ai.p, h.d_flag.p);
-    tm.stop();
+    h.ms[3] = tm.stop();
   }
   std::vector<double> Anew((size_t) n * ms), Ainew((size_t) n * ms);
   DSR_HIP(hipMemcpyAsync(Anew.data(), h.d_A.p, Anew.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -537,9 +530,9 @@ void lda_estimate(LdaHandle& h, const int* estX, int n, hipStream_t st)
   DSR_HIP(hipMemsetAsync(h.d_flag.p, 0, (size_t) n * sizeof(int), st));
   {
     const size_t lds = ((size_t) 3 * D * D + 2 * D + ((D + 1) & ~1) + 2 * kRowThreads) * sizeof(double) + (size_t) D * sizeof(int);
-    Timer tm(h.timing, st, &h.ms[2]);
+    ScopedTimer tm(h.timing, st);
     launch(k_lda_solve, dim3(n), dim3(kRowThreads), lds, st, D, h.d_W.p, h.d_B.p, h.d_L.p, h.d_ev.p, h.d_flag.p);
-    tm.stop();
+    h.ms[2] = tm.stop();
   }
   std::vector<double> L((size_t) n * ms), ev((size_t) n * 2 * D); std::vector<int> flag(n);
   DSR_HIP(hipMemcpyAsync(L.data(), h.d_L.p, L.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -564,9 +557,9 @@ static void apply_matrix(XfBase& h, const double* M, int Din, int outDim, const 
   if (N == 0) return;
   if (!x || !out) throw Error(DSR_E_PARAMETER, "null argument");
   if ((long) N * outDim > 0x7fffffffL * 256L) throw Error(DSR_E_DIMENSION, "%ld frames in one call", N);
-  Timer tm(h.timing, st, &h.ms[4]);
+  ScopedTimer tm(h.timing, st);
   launch(k_stc_apply, dim3(cdiv(N * outDim, 256)), dim3(256), 0, st, Din, outDim, N, x, M, out);
-  tm.stop();
+  h.ms[4] = tm.stop();
 }
 
 void stc_apply(StcHandle& h, const float* x, long N, int estX, float* out, hipStream_t st)

@@ -2,9 +2,7 @@
 // ModalSphericalArrayTracker, SpatialSphericalArrayTracker (an iterated extended Kalman filter in square-root form on (theta, phi)) and
 // PlaneWaveSimulator.  Line numbers are tracker.cc's.
 //
-// Host side (set-up work, as in the reference): the EigenMike geometry (:195-297, the table of csrc/sph_math.h), _bn = 4 pi i^n b_n(ka) with
-// modalCoefficient's own closed forms (:474-628), the conjugated harmonics at the sensors (:117-130), _calculateNormalization per mode, the
-// per-bin observation-noise Cholesky blocks (setV :961-981) and the plane-wave coefficients (:1453-1465).
+// Host side (the set-up work, the dsr_trk_* / dsr_pws_* entries): csrc/tracker.cpp; what the two share: csrc/tracker.h.
 //
 // Device side, a batch X [U][32][Tmax][M/2+1] complex64 (the layout dsr_fb_analysis writes):
 //   k_trk_run   one workgroup per utterance, the frames in order (the filter is sequential in time); within a frame the work is spread over
@@ -19,133 +17,21 @@
 //               The rotation order and every operand are the reference's.
 //   k_pws_apply PlaneWaveSimulator::next (:1474-1488) element-wise: coefficient x source spectrum, optionally the conjugate mirror.
 #include "launch.h"
-#include "sph_math.h"
+#include "tracker.h"
 #include "dev_math.h"
 #include <algorithm>
 
 using namespace dsr;
 
-typedef std::complex<double> zc;
-
 namespace {
 
-constexpr double SSPEED = 343740.0;                          // BaseDecomposition::_SpeedOfSound (:86)
-constexpr int CHAN = 32;                                     // _ChannelsN (:85)
-constexpr int MAX_ORDER_N = 8;                               // 81 modes: the per-mode tables of the kernel
-constexpr int STATE_DOUBLES = 8;                             // theta, phi, K (row major), frames seen, error flag
 constexpr int NT = 256;
 constexpr size_t LDS_BUDGET = 160 * 1024;                    // per workgroup on gfx950
 constexpr double EPSILON = 0.01, TOLERANCE = 1.0e-04;        // _Epsilon, _Tolerance (:878-879)
 
-// _calculatePnm (:421-437): the unnormalised Legendre function with the negative-degree scaling loop; x = cos(theta)
-DSR_HD inline double trk_pnm(int order, int degree, double x)
-{
-  double result = legendre_plm(order, degree < 0 ? -degree : degree, x);
-  if (degree < 0) {
-    int m = -degree; double factor = 1.0;
-    while (m > degree) { factor *= (order + m); m--; }
-    result /= factor;
-    if (((-degree) % 2) == 1) result *= -1;
-  }
-  return result;
-}
-// _calculate_dPnm_dtheta (:440-449): dP/dx in fact; the (degree - order - 1) factor is kept for negative degree, as written
-DSR_HD inline double trk_dpnm(int order, int degree, double x)
-{
-  const double x2 = x * x;
-  return ((degree - order - 1) * trk_pnm(order + 1, degree, x) + (order + 1) * x * trk_pnm(order, degree, x)) / (1.0 - x2);
-}
-// _calculateNormalization (:381-403)
-double trk_norm(int order, int degree)
-{
-  double norm = std::sqrt((2 * order + 1) / (4.0 * M_PI)), factor = 1.0;
-  if (degree >= 0) { int m = degree; while (m > -degree) { factor *= (order + m); m--; } norm /= std::sqrt(factor); }
-  else { int m = -degree; while (m > degree) { factor *= (order + m); m--; } norm *= std::sqrt(factor); }
-  return norm;
-}
-// harmonic (:319-339) and the two derivatives (:452-472) from cos / sin of theta and the mode's normalisation: host and device
-struct Harm { double yr, yi, tr, ti, pr, pi, P, dP; };
-DSR_HD inline Harm trk_harm(int n, int m, double ct, double st, double phi, double norm)
-{
-  Harm h;
-  double p = sph_plm(n, m >= 0 ? m : -m, ct);
-  if (m < 0 && ((-m) % 2) == 1) p = -p;
-  const double ang = -m * phi, er = cos(ang), ei = sin(ang);
-  h.yr = er * p; h.yi = ei * p;
-  h.P = trk_pnm(n, m, ct); h.dP = trk_dpnm(n, m, ct);
-  const double factor = -norm * h.dP * st;
-  h.tr = er * factor; h.ti = ei * factor;
-  const double qr = h.yr * 0.0 - h.yi * -1.0, qi = h.yr * -1.0 + h.yi * 0.0;    // gsl_complex_mul(Ynm, (0, -1))
-  h.pr = qr * m; h.pi = qi * m;
-  return h;
-}
-
-zc modal_coefficient(unsigned order, double ka)              // :474-628
-{
-  if (ka == 0.0) return zc(1.0, 0.0);
-  const double c = std::cos(ka), s = std::sin(ka);
-  const double ka2 = ka * ka, ka3 = ka2 * ka, ka4 = ka2 * ka2, ka5 = ka4 * ka, ka6 = ka5 * ka, ka7 = ka6 * ka, ka8 = ka7 * ka, ka9 = ka8 * ka;
-  auto mul_imag = [](zc a, double y) { return zc(-y * a.imag(), y * a.real()); };
-  switch (order) {
-  case 0: {
-    const double j0 = gsinc(ka / M_PI);
-    const zc h0(j0, -c / ka);
-    const double val1 = ka * c - s;
-    const zc val2 = gmul(zc(ka, 1), zc(c, s));
-    const zc grad = gdiv(zc(val1, 0), val2), g = gmul(grad, h0);
-    return zc(j0 - g.real(), 0.0 - g.imag());
-  }
-  case 1: return gmulr(gdiv(zc(-c, s), zc(ka2 - 2, 2 * ka)), ka);
-  case 2: return mul_imag(gdiv(zc(c, -s), zc(ka3 - 9 * ka, 4 * ka2 - 9)), ka2);
-  case 3: return gmulr(gdiv(zc(c, -s), zc(ka4 - 27 * ka2 + 60, 7 * ka3 - 60 * ka)), ka3);
-  case 4: return gmulr(gdiv(zc(s, c), zc(ka5 - 65 * ka3 + 525 * ka, 11 * ka4 - 240 * ka2 + 525)), ka4);
-  case 5: return gmulr(gdiv(zc(c, -s), zc(ka6 - 135 * ka4 + 2625 * ka2 - 5670, 16 * ka5 - 735 * ka3 + 5670 * ka)), ka5);
-  case 6: return mul_imag(gdiv(zc(c, -s), zc(ka7 - 252 * ka5 + 9765 * ka3 - 72765 * ka, 22 * ka6 - 1890 * ka4 + 34020 * ka2 - 72765)), ka6);
-  case 7: return gmulr(gdiv(zc(c, -s), zc(1081080 - 509355 * ka2 + 29925 * ka4 - 434 * ka6 + ka8, -1081080 * ka + 148995 * ka3 - 4284 * ka5 + 29 * ka7)), ka7);
-  case 8: return gmulr(gdiv(zc(s, c), zc(18243225 * ka - 2567565 * ka3 + 79695 * ka5 - 702 * ka7 + ka9,
-                                         18243225 - 8648640 * ka2 + 530145 * ka4 - 8820 * ka6 + 37 * ka8)), ka8);
-  default: {
-    const double jn = sph_jl(order, ka), yn = sph_yl(order, ka);
-    const double jp = sph_jl(order - 1, ka), jnn = sph_jl(order + 1, ka), yp = sph_yl(order - 1, ka), ynn = sph_yl(order + 1, ka);
-    const double djn = (jp - jnn) / 2;
-    const zc hn(jn, yn), hp(jp, yp), hnn(jnn, ynn);
-    const zc val = gdivr(hn + gmulr(hnn, ka), ka);
-    const zc dhn = gmulr(hp - val, 0.5);
-    const zc grad = gdiv(zc(djn, 0), dhn), g = gmul(grad, hn);
-    return zc(-g.real() + jn, -g.imag());
-  }
-  }
-}
-
-zc host_harmonic(int n, int m, double theta, double phi)
-{
-  const Harm h = trk_harm(n, m, std::cos(theta), std::sin(theta), phi, trk_norm(n, m));
-  return zc(h.yr, h.yi);
-}
-
-}  // namespace
-
-struct dsr_trk {
-  int spatial = 0, orderN = 0, modesN = 1, M = 0, F = 0, K = 0, L = 0, N = 0, maxLocalN = 1;
-  double a = 0, fs = 0, s2u = 10, s2v = 10, s2init = 10, th0 = 0.5, ph0 = 0.0;
-  std::vector<zc> bn, sc;                                    // _bn [F][orderN+1]; _sphericalComponent [modesN][32] = conj(Y) at the sensors
-  std::vector<double> norm, absbn;                           // [modesN]; |_bn| [F][orderN+1]
-  std::vector<double> V; bool vDirty = true;                 // setV's blocks [F][2L][2L] (empty until the first setV: sqrt(sigma2_v) I)
-  DevBuf<double2> dBn, dSc; DevBuf<double> dNorm, dAbs, dVt; bool tablesUp = false;
-  PerStream<DevBuf<double>> ws;
-  size_t lds = 0;
-};
-
-namespace {
-
 // the kernel's LDS in doubles: per-mode tables 8 modesN, the spatial kind's per-(sensor, order) sums 6 x 32 x (orderN+1), the reduction
 // scratch NT, 32 of pivots and scalars, the selected bins (K ints), then three columns of 2N+2 rows (two of A12 | A22, the innovation)
 size_t lds_fixed_doubles(int modesN, int orderN, int spatial, int K) { return 8 * (size_t) modesN + (spatial ? 6 * CHAN * (size_t) (orderN + 1) : 0) + NT + 32 + (size_t) (K + 1) / 2 + 1; }
-size_t lds_bytes(const dsr_trk& s) { return 8 * (lds_fixed_doubles(s.modesN, s.orderN, s.spatial, s.K) + 3 * (size_t) (2 * s.N + 2)); }
-long max_rows(int modesN, int orderN, int spatial, int K)      // the largest 2N the LDS budget admits
-{
-  return ((long) (LDS_BUDGET / 8) - (long) lds_fixed_doubles(modesN, orderN, spatial, K)) / 3 - 2;
-}
 
 struct TrkP {
   int spatial, orderN, modesN, F, L, K, N, maxLocalN, Tmax, hasV;
@@ -451,221 +337,36 @@ void upload_tables(dsr_trk& s, hipStream_t st)
 
 }  // namespace
 
-extern "C" {
+namespace dsr {
 
-dsr_status dsr_trk_create(int kind, int orderN, int fftLen, double a, double sampleRate, int useSubbandsN, double sigma2_u, double sigma2_v, double sigma2_init,
-                          int maxLocalN, int chanN, dsr_trk** out)
+long trk_max_rows(int modesN, int orderN, int spatial, int K)
 {
-  return guard([&] {
-    if (!out) throw Error(DSR_E_ARG, "out is null");
-    *out = nullptr;
-    if (chanN != CHAN) throw Error(DSR_E_ARG, "the trackers are built for the EigenMike's %d channels, not %d", CHAN, chanN);
-    if (kind != DSR_TRK_MODAL && kind != DSR_TRK_SPATIAL) throw Error(DSR_E_ARG, "kind %d: DSR_TRK_MODAL or DSR_TRK_SPATIAL", kind);
-    if (orderN < 0 || orderN > MAX_ORDER_N) throw Error(DSR_E_ARG, "orderN %d outside [0, %d]", orderN, MAX_ORDER_N);
-    if (fftLen < 2 || (fftLen & 1)) throw Error(DSR_E_ARG, "fftLen %d: an even length >= 2", fftLen);
-    const int F = fftLen / 2 + 1;
-    if (useSubbandsN < 0 || useSubbandsN > F) throw Error(DSR_E_ARG, "useSubbandsN %d outside [0, %d]", useSubbandsN, F);
-    if (maxLocalN < 1 || maxLocalN > 255) throw Error(DSR_E_ARG, "maxLocalN %d outside [1, 255]", maxLocalN);
-    if (!(sigma2_u >= 0.0) || !(sigma2_v >= 0.0) || !(sigma2_init >= 0.0)) throw Error(DSR_E_ARG, "negative variance");
-    std::unique_ptr<dsr_trk> s(new dsr_trk());
-    s->spatial = kind == DSR_TRK_SPATIAL; s->orderN = orderN; s->modesN = (orderN + 1) * (orderN + 1); s->M = fftLen; s->F = F;
-    s->K = useSubbandsN == 0 ? F : useSubbandsN; s->L = s->spatial ? CHAN : s->modesN; s->N = s->K * s->L; s->maxLocalN = maxLocalN;
-    s->a = a; s->fs = sampleRate; s->s2u = sigma2_u; s->s2v = sigma2_v; s->s2init = sigma2_init;
-    const long lim = max_rows(s->modesN, orderN, s->spatial, s->K);
-    if (2L * s->N > lim) throw Error(DSR_E_ARG, "2N = 2 x %d x %d = %ld rows exceed the %ld the workgroup's LDS holds", s->K, s->L, 2L * s->N, lim);
-    s->lds = lds_bytes(*s);
-    const int O1 = orderN + 1;
-    s->bn.resize((size_t) F * O1); s->absbn.resize((size_t) F * O1);
-    static const zc IN[4] = {zc(1, 0), zc(0, 1), zc(-1, 0), zc(0, -1)};      // _calc_in (:299-312)
-    for (int f = 0; f < F; f++) {
-      const double ka = 2.0 * M_PI * f * a * sampleRate / (fftLen * SSPEED);
-      for (int n = 0; n < O1; n++) {
-        const zc b = gmul(gmul(zc(4.0 * M_PI, 0.0), IN[n % 4]), modal_coefficient(n, ka));
-        s->bn[(size_t) f * O1 + n] = b; s->absbn[(size_t) f * O1 + n] = std::hypot(b.real(), b.imag());
-      }
-    }
-    s->sc.resize((size_t) s->modesN * CHAN); s->norm.resize(s->modesN);
-    int idx = 0;
-    for (int n = 0; n <= orderN; n++)
-      for (int m = -n; m <= n; m++, idx++) {
-        s->norm[idx] = trk_norm(n, m);
-        for (int c = 0; c < CHAN; c++) s->sc[(size_t) idx * CHAN + c] = std::conj(host_harmonic(n, m, EM_THETA[c] * M_PI / 180.0, EM_PHI[c] * M_PI / 180.0));
-      }
-    *out = s.release();
-  });
+  return ((long) (LDS_BUDGET / 8) - (long) lds_fixed_doubles(modesN, orderN, spatial, K)) / 3 - 2;
+}
+size_t trk_lds_bytes(const dsr_trk& s) { return 8 * (lds_fixed_doubles(s.modesN, s.orderN, s.spatial, s.K) + 3 * (size_t) (2 * s.N + 2)); }
+
+void trk_launch_init(double* state, int U, double th, double ph, double k0, int keepK, hipStream_t st)
+{
+  launch(k_trk_init, dim3(cdiv(U, NT)), dim3(NT), 0, st, state, U, th, ph, k0, keepK);
 }
 
-void dsr_trk_destroy(dsr_trk* s) { delete s; }
-int dsr_trk_state_doubles(const dsr_trk*) { return STATE_DOUBLES; }
-int dsr_trk_modes_n(const dsr_trk* s) { return s ? s->modesN : 0; }
-int dsr_trk_subband_length(const dsr_trk* s) { return s ? s->L : 0; }
-int dsr_trk_use_subbands_n(const dsr_trk* s) { return s ? s->K : 0; }
-int dsr_trk_fft_len(const dsr_trk* s) { return s ? s->M : 0; }
-int64_t dsr_trk_max_rows(int kind, int orderN, int useSubbandsN) { return max_rows((orderN + 1) * (orderN + 1), orderN, kind == DSR_TRK_SPATIAL, useSubbandsN); }
-
-dsr_status dsr_trk_set_v(dsr_trk* s, const double* Vk, size_t nDoubles, unsigned subbandX)
+void trk_launch_run(dsr_trk& s, const float* X, const int32_t* nframes, int U, int Tmax, double* state, float* pos, double* pos64, int32_t* info, hipStream_t st)
 {
-  return guard([&] {
-    if (!s || !Vk) throw Error(DSR_E_ARG, "null argument");
-    const int L = s->L, L2 = 2 * L;
-    if ((int) subbandX >= s->F) throw Error(DSR_E_ARG, "subband %u outside [0, %d)", subbandX, s->F);
-    if (nDoubles != (size_t) 2 * L * L) throw Error(DSR_E_ARG, "Vk: %d x %d complex values expected", L, L);
-    std::vector<double> B((size_t) L2 * L2, 0.0);
-    if (!s->V.empty()) std::copy(s->V.begin() + (size_t) subbandX * L2 * L2, s->V.begin() + (size_t) (subbandX + 1) * L2 * L2, B.begin());
-    else for (int n = 0; n < L2; n++) B[(size_t) n * L2 + n] = std::sqrt(s->s2v);
-    for (int m = 0; m < L; m++)                              // :965-974: the lower triangle only; (m + L, n) with n > m keeps its contents
-      for (int n = 0; n <= m; n++) {
-        const double c = Vk[2 * ((size_t) m * L + n)], sg = Vk[2 * ((size_t) m * L + n) + 1];
-        B[(size_t) m * L2 + n] = c; B[(size_t) (m + L) * L2 + n + L] = c; B[(size_t) (m + L) * L2 + n] = sg;
-      }
-    std::vector<double> C((size_t) L2 * L2, 0.0);            // the Cholesky factor of the lower triangle, row by row; the strict upper part zero
-    for (int i = 0; i < L2; i++) {
-      for (int j = 0; j < i; j++) {
-        double sum = 0.0; for (int k = 0; k < j; k++) sum += C[(size_t) i * L2 + k] * C[(size_t) j * L2 + k];
-        C[(size_t) i * L2 + j] = (B[(size_t) i * L2 + j] - sum) / C[(size_t) j * L2 + j];
-      }
-      double sum = 0.0; for (int k = 0; k < i; k++) sum += C[(size_t) i * L2 + k] * C[(size_t) i * L2 + k];
-      const double d = B[(size_t) i * L2 + i] - sum;
-      if (!(d > 0.0)) throw Error(DSR_E_ARG, "setV: the block of subband %u is not positive definite", subbandX);
-      C[(size_t) i * L2 + i] = std::sqrt(d);
-    }
-    if (s->V.empty()) {
-      s->V.assign((size_t) s->F * L2 * L2, 0.0);
-      for (int f = 0; f < s->F; f++) for (int n = 0; n < L2; n++) s->V[((size_t) f * L2 + n) * L2 + n] = std::sqrt(s->s2v);
-    }
-    std::copy(C.begin(), C.end(), s->V.begin() + (size_t) subbandX * L2 * L2);
-    s->vDirty = true;
-  });
+  upload_tables(s, st);
+  const size_t FL = (size_t) s.F * s.L, wsStride = (8 * FL + 7 * (size_t) s.F + 1) / 2 * 2;   // doubles, even: the complex tables stay 16-byte aligned
+  DevBuf<double>& ws = s.ws.at(st); ws.reserve((size_t) U * wsStride);
+  TrkP p;
+  p.spatial = s.spatial; p.orderN = s.orderN; p.modesN = s.modesN; p.F = s.F; p.L = s.L; p.K = s.K; p.N = s.N; p.maxLocalN = s.maxLocalN;
+  p.Tmax = Tmax; p.hasV = s.V.empty() ? 0 : 1; p.su = std::sqrt(s.s2u); p.sv = std::sqrt(s.s2v);
+  p.bn = s.dBn.p; p.sc = s.dSc.p; p.norm = s.dNorm.p; p.absbn = s.dAbs.p; p.Vt = s.dVt.p;
+  launch(k_trk_run, dim3(U), dim3(NT), s.lds, st, p, (const float2*) X, nframes, state, ws.p, wsStride, pos, pos64, info);
 }
 
-dsr_status dsr_trk_get_v(const dsr_trk* s, unsigned subbandX, double* out, size_t outDoubles)
+void pws_launch_apply(const double* coef, int C, const float* src, const int32_t* nframes, int U, int Tmax, int M, int full, float* out, hipStream_t st)
 {
-  return guard([&] {
-    if (!s || !out) throw Error(DSR_E_ARG, "null argument");
-    const int L2 = 2 * s->L;
-    if ((int) subbandX >= s->F || outDoubles != (size_t) L2 * L2) throw Error(DSR_E_ARG, "subband %u, %d x %d doubles expected", subbandX, L2, L2);
-    if (s->V.empty()) { std::fill(out, out + outDoubles, 0.0); for (int n = 0; n < L2; n++) out[(size_t) n * L2 + n] = std::sqrt(s->s2v); }
-    else std::copy(s->V.begin() + (size_t) subbandX * L2 * L2, s->V.begin() + (size_t) (subbandX + 1) * L2 * L2, out);
-  });
+  const size_t total = (size_t) U * C * Tmax * (M / 2 + 1);
+  const int blocks = (int) std::min<size_t>((total + NT - 1) / NT, 65535);
+  launch(k_pws_apply, dim3(blocks), dim3(NT), 0, st, (const double2*) coef, C, (const float2*) src, nframes, U, Tmax, M, full, (float2*) out);
 }
 
-dsr_status dsr_trk_set_initial_position(dsr_trk* s, double theta, double phi)
-{ return guard([&] { if (!s) throw Error(DSR_E_ARG, "null handle"); s->th0 = theta; s->ph0 = phi; }); }
-dsr_status dsr_trk_next_speaker(dsr_trk* s)
-{ return guard([&] { if (!s) throw Error(DSR_E_ARG, "null handle"); s->th0 = 0.5; s->ph0 = 0.0; }); }
-
-dsr_status dsr_trk_init_state(dsr_trk* s, double* state_dev, int U, int positionOnly, void* stream)
-{
-  return guard([&] {
-    if (!s || !state_dev || U <= 0) throw Error(DSR_E_ARG, "null argument or U <= 0");
-    require_device();
-    launch(k_trk_init, dim3(cdiv(U, NT)), dim3(NT), 0, (hipStream_t) stream, state_dev, U, s->th0, s->ph0, std::sqrt(std::sqrt(s->s2init)), positionOnly);
-  });
-}
-
-dsr_status dsr_trk_bn(const dsr_trk* s, double* out, size_t outDoubles)
-{
-  return guard([&] {
-    if (!s || !out || outDoubles != 2 * s->bn.size()) throw Error(DSR_E_ARG, "bn: [fftLen/2+1][orderN+1] complex128 expected");
-    memcpy(out, s->bn.data(), sizeof(double) * outDoubles);
-  });
-}
-dsr_status dsr_trk_sensor_harmonics(const dsr_trk* s, double* out, size_t outDoubles)
-{
-  return guard([&] {
-    if (!s || !out || outDoubles != 2 * s->sc.size()) throw Error(DSR_E_ARG, "sensor harmonics: [modesN][32] complex128 expected");
-    memcpy(out, s->sc.data(), sizeof(double) * outDoubles);
-  });
-}
-dsr_status dsr_trk_geometry(double* theta_s, double* phi_s, int n)
-{
-  return guard([&] {
-    if (!theta_s || !phi_s || n != CHAN) throw Error(DSR_E_ARG, "the geometry has %d sensors", CHAN);
-    for (int c = 0; c < CHAN; c++) { theta_s[c] = EM_THETA[c] * M_PI / 180.0; phi_s[c] = EM_PHI[c] * M_PI / 180.0; }
-  });
-}
-
-dsr_status dsr_trk_harmonic(int order, int degree, double theta, double phi, double* out2)
-{
-  return guard([&] {
-    if (!out2 || order < 0 || degree > order || -degree > order) throw Error(DSR_E_ARG, "|degree| <= order expected");
-    const zc y = host_harmonic(order, degree, theta, phi); out2[0] = y.real(); out2[1] = y.imag();
-  });
-}
-dsr_status dsr_trk_harmonic_deriv_polar(int order, int degree, double theta, double phi, double* out2)
-{
-  return guard([&] {
-    if (!out2 || order < 0 || degree > order || -degree > order) throw Error(DSR_E_ARG, "|degree| <= order expected");
-    const Harm h = trk_harm(order, degree, std::cos(theta), std::sin(theta), phi, trk_norm(order, degree)); out2[0] = h.tr; out2[1] = h.ti;
-  });
-}
-dsr_status dsr_trk_harmonic_deriv_azimuth(int order, int degree, double theta, double phi, double* out2)
-{
-  return guard([&] {
-    if (!out2 || order < 0 || degree > order || -degree > order) throw Error(DSR_E_ARG, "|degree| <= order expected");
-    const Harm h = trk_harm(order, degree, std::cos(theta), std::sin(theta), phi, trk_norm(order, degree)); out2[0] = h.pr; out2[1] = h.pi;
-  });
-}
-dsr_status dsr_trk_modal_coefficient(unsigned order, double ka, double* out2)
-{
-  return guard([&] {
-    if (!out2) throw Error(DSR_E_ARG, "null argument");
-    const zc b = modal_coefficient(order, ka); out2[0] = b.real(); out2[1] = b.imag();
-  });
-}
-
-dsr_status dsr_trk_run(dsr_trk* s, const float* X_dev, const int32_t* nframes_dev, int U, int Tmax, double* state_dev, float* pos_dev, double* pos64_dev,
-                       int32_t* info_dev, void* stream)
-{
-  return guard([&] {
-    if (!s || !X_dev || !nframes_dev || !state_dev || !pos_dev || !pos64_dev || !info_dev) throw Error(DSR_E_ARG, "null argument");
-    if (U <= 0 || Tmax <= 0) throw Error(DSR_E_ARG, "U and Tmax must be positive");
-    require_device();
-    hipStream_t st = (hipStream_t) stream;
-    upload_tables(*s, st);
-    const size_t FL = (size_t) s->F * s->L, wsStride = (8 * FL + 7 * (size_t) s->F + 1) / 2 * 2;   // doubles, even: the complex tables stay 16-byte aligned
-    DevBuf<double>& ws = s->ws.at(st); ws.reserve((size_t) U * wsStride);
-    TrkP p;
-    p.spatial = s->spatial; p.orderN = s->orderN; p.modesN = s->modesN; p.F = s->F; p.L = s->L; p.K = s->K; p.N = s->N; p.maxLocalN = s->maxLocalN;
-    p.Tmax = Tmax; p.hasV = s->V.empty() ? 0 : 1; p.su = std::sqrt(s->s2u); p.sv = std::sqrt(s->s2v);
-    p.bn = s->dBn.p; p.sc = s->dSc.p; p.norm = s->dNorm.p; p.absbn = s->dAbs.p; p.Vt = s->dVt.p;
-    launch(k_trk_run, dim3(U), dim3(NT), s->lds, st, p, (const float2*) X_dev, nframes_dev, state_dev, ws.p, wsStride, pos_dev, pos64_dev, info_dev);
-  });
-}
-
-dsr_status dsr_pws_coefficients(const dsr_trk* s, double theta, double phi, double* out, size_t outDoubles)
-{
-  return guard([&] {
-    if (!s || !out || outDoubles != (size_t) 2 * CHAN * s->F) throw Error(DSR_E_ARG, "coefficients: [32][fftLen/2+1] complex128 expected");
-    const int O1 = s->orderN + 1;
-    std::vector<zc> Y(s->modesN);
-    int idx = 0;
-    for (int n = 0; n <= s->orderN; n++) for (int m = -n; m <= n; m++) Y[idx++] = host_harmonic(n, m, theta, phi);
-    for (int c = 0; c < CHAN; c++)
-      for (int f = 0; f < s->F; f++) {                       // :1453-1465
-        zc coefficient(0, 0);
-        for (int n = 0; n < O1; n++) {
-          zc coeff_n(0, 0);
-          for (int i = n * n; i < (n + 1) * (n + 1); i++) coeff_n += gmul(s->sc[(size_t) i * CHAN + c], Y[i]);
-          coefficient += gmul(s->bn[(size_t) f * O1 + n], coeff_n);
-        }
-        out[2 * ((size_t) c * s->F + f)] = coefficient.real(); out[2 * ((size_t) c * s->F + f) + 1] = coefficient.imag();
-      }
-  });
-}
-
-dsr_status dsr_pws_apply(const double* coef_dev, int chanN, const float* src_dev, const int32_t* nframes_dev, int U, int Tmax, int fftLen, int full, float* out_dev,
-                         void* stream)
-{
-  return guard([&] {
-    if (!coef_dev || !src_dev || !nframes_dev || !out_dev) throw Error(DSR_E_ARG, "null argument");
-    if (chanN <= 0 || U <= 0 || Tmax <= 0 || fftLen < 2 || (fftLen & 1)) throw Error(DSR_E_ARG, "chanN, U, Tmax positive and fftLen even expected");
-    require_device();
-    const size_t total = (size_t) U * chanN * Tmax * (fftLen / 2 + 1);
-    const int blocks = (int) std::min<size_t>((total + NT - 1) / NT, 65535);
-    launch(k_pws_apply, dim3(blocks), dim3(NT), 0, (hipStream_t) stream, (const double2*) coef_dev, chanN, (const float2*) src_dev, nframes_dev, U, Tmax,
-                       fftLen, full, (float2*) out_dev);
-  });
-}
-
-}  // extern "C"
+}  // namespace dsr

@@ -129,9 +129,9 @@ dsr_status dsr_src_apply(dsr_src* s, const float* x_dev, const int32_t* nsamp_de
     if (U == 0 || C == 0) return;
     hipStream_t st = (hipStream_t) stream;
     if (!s->uploaded && s->method <= SRC_BEST && !s->copy) { s->d_table.upload(s->table, st); s->uploaded = true; }
-    if (s->timed) DSR_HIP(hipEventRecord(s->ev[0], st));
+    s->tm.mark(0, st);
     src_launch(*s, x_dev, nsamp_dev, U, C, (long) inStride, state_dev, flush, y_dev, nout_dev, (long) outStride, st);
-    if (s->timed) DSR_HIP(hipEventRecord(s->ev[1], st));
+    s->tm.mark(1, st);
   });
 }
 
@@ -148,15 +148,14 @@ dsr_status dsr_src_set_timing(dsr_src* s, int on)
 {
   return guard([&] {
     if (!s) throw Error(DSR_E_PARAMETER, "null argument");
-    if (on) { require_device(); for (hipEvent_t& e : s->ev) if (!e) DSR_HIP(hipEventCreate(&e)); }
-    s->timed = on != 0;
+    s->tm.enable(on != 0);
   });
 }
 dsr_status dsr_src_kernel_ms(const dsr_src* s, double* ms)
 {
   return guard([&] {
-    if (!s || !ms || !s->timed) throw Error(DSR_E_PARAMETER, "timing is off");
-    float a = 0; DSR_HIP(hipEventSynchronize(s->ev[1])); DSR_HIP(hipEventElapsedTime(&a, s->ev[0], s->ev[1])); *ms = a;
+    if (!s || !ms || !s->tm.on) throw Error(DSR_E_PARAMETER, "timing is off");
+    s->tm.wait(1); *ms = s->tm.ms(0, 1);
   });
 }
 

@@ -17,8 +17,7 @@ struct SrcState {
   std::vector<float> table;                           // [L][stride]: row q holds the taps of phase (q M) mod L, j = -K+1 .. K, the rest of the row zero
   DevBuf<float> d_table; bool uploaded = false;
   int stateU = -1, stateC = -1;                       // the shape dsr_src_state_init saw last
-  bool timed = false; hipEvent_t ev[2] = {nullptr, nullptr};
-  ~SrcState() { for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e); }
+  EventTimes<2> tm;                                   // dsr_src_set_timing: around the launch
   // the samples a row keeps: 2K for a sinc method.  zoh and linear keep ceil(M / L) more: the count floor(b L / M) can hold back an output whose taps
   // were all there (never with a sinc method, whose K L / M is at least 10), and its base lies up to ceil(M / L) samples back
   int hist() const { return copy ? 0 : method <= SRC_BEST ? 2 * K : 2 * K + (M + L - 1) / L; }

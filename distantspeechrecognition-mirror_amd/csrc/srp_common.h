@@ -1,7 +1,7 @@
 // csrc/srp_common.h -- what the steered-response-power kernels share: k_doa.hip (linear array) and k_sph.hip (spherical array).
 // The workgroup tiling and the parts of the two SRP kernels that are the same (snapshot staging, the staged-chunk frame energy of calcEnergy,
 // beamformer.cc:3043-3074, the response-power accumulation and its epilogue), the N-best insertion of DOAEstimatorSRP*::next and
-// _getNBestHypothesesFromACCRP (also the stream operators', csrc/streams_beamformer.cpp), the frequency-range check, the linear estimator's handle and its
+// _getNBestHypothesesFromACCRP (also the stream operators', csrc/streams_beamformer.cpp), the frequency-range check, the linear estimator's handle (host side: doa.cpp) and its
 // launchers, which the spherical estimator's folded path (sph.cpp) drives with a table of its own.  Kernel files that include this are built with
 // -ffp-contract=off: the energy must stay the reference's float accumulation bit for bit.
 #pragma once
@@ -136,9 +136,13 @@ __device__ __forceinline__ void srp_write_rp(const d4 (&rp)[TG], int th0, int NT
   }
 }
 
+// ---- k_doa.hip ----
 // k_doa_srp over s's table (uploaded when dirty): rp [U][Tmax][nTheta], energy [U][Tmax], Y (optional) the last unit's bins
 void doa_launch_rp(dsr_doa& s, const float* X, const int* nf, int U, int Tmax, double* rp, float* en, float* Y, hipStream_t st);
 // k_doa_acc: acc[u][k] += rp of every frame t < nframes[u] with energy >= thr, in frame order
 void doa_launch_acc(const double* rp, const float* en, const int* nf, int U, int Tmax, int nUnits, float thr, double* acc, hipStream_t st);
+// k_doa_frame: the energy gate (gated, optional) and the N-best nbRp, nbIdx [U][Tmax][nBest] of every frame t < nframes[u]
+void doa_launch_frame(const double* rp, const float* en, const int* nf, int U, int Tmax, int nUnits, int nBest, float thr, double* nbRp, int* nbIdx,
+                      int* gated, hipStream_t st);
 
 }  // namespace dsr

@@ -1,8 +1,9 @@
 """The host half of the kernel units without a device.  csrc/value_list.h: ints<...> states the values a template is instantiated for once,
 has_value asks whether a run-time value is one of them, for_value hands the matching one to a callback as a compile-time constant (a small main,
 plain g++ -std=c++17, prints what the callback saw).  csrc/launch.h: the only file of csrc/ that launches a kernel or raises a kernel's dynamic-LDS
-limit, and no macro wraps it.  The beamformer family's kernel units (k_sph, k_beamform, k_mmi) and the filter bank's (k_filterbank) hold no C
-entries, and no file restates another unit's declaration by hand."""
+limit, and no macro wraps it.  The beamformer family's kernel units (k_sph, k_beamform, k_mmi), the filter bank's (k_filterbank) and the
+localization family's (k_doa, k_gcc, k_mcc, k_tracker) hold no C entries, and no file restates another unit's declaration by hand.  Timing events are
+created by the two helpers of csrc/common.h."""
 import glob
 import os
 import re
@@ -84,8 +85,8 @@ def test_kernels_are_launched_in_launch_h_only():
     assert [os.path.basename(f) for f in kernel_units if not re.search(r"\blaunch(_n)?\(", open(f).read())] == []
 
 
-def test_beamformer_kernel_units_hold_no_entries_and_no_unit_restates_a_declaration():
-    for name in ("k_sph.hip", "k_beamform.hip", "k_mmi.hip", "k_filterbank.hip"):
+def test_split_kernel_units_hold_no_entries_and_no_unit_restates_a_declaration():
+    for name in ("k_sph.hip", "k_beamform.hip", "k_mmi.hip", "k_filterbank.hip", "k_doa.hip", "k_gcc.hip", "k_mcc.hip", "k_tracker.hip"):
         text = open(os.path.join(CSRC, name)).read()
         assert [s for s in ('extern "C"', "dsr_status") if s in text] == [], name
     restated = re.compile(r'^namespace dsr \{ .*\); *\}|extern "C" \{ namespace dsr \{')   # a one-line declaration of another unit's function
@@ -93,6 +94,12 @@ def test_beamformer_kernel_units_hold_no_entries_and_no_unit_restates_a_declarat
     for f in _sources():
         bad += [(os.path.basename(f), n + 1) for n, l in enumerate(open(f).read().split("\n")) if restated.search(l)]
     assert bad == []
+
+
+def test_timing_events_are_created_in_common_h():
+    # k_lpc.hip and k_train.hip create their events per call; capi.cpp and decoder.cpp hold the pipe's and the decoder's own
+    hits = sorted(os.path.basename(f) for f in _sources() if "hipEventCreate" in open(f).read())
+    assert hits == ["capi.cpp", "common.h", "decoder.cpp", "k_lpc.hip", "k_train.hip"]
 
 
 def test_no_macro_wraps_launch():

@@ -6,7 +6,7 @@ dsr_gcc_set_timing, in a pass of its own so that the whole-call time is taken wi
 on X (read once by k_gcc_spectrum per pair side) and on the cross-spectrum intermediate (written by k_gcc_spectrum, read by k_gcc_corr),
 each over the time of the kernels that move it."""
 import argparse
-import ctypes as C
+import ctypes
 import json
 import os
 import sys
@@ -55,7 +55,7 @@ def main():
         times.sort(); ms = times[len(times) // 2]
         dsr.check(dsr._lib.dsr_gcc_set_timing(g.h, 1)); kms = []
         for _ in range(a.steps):
-            call(); two = (C.c_double * 2)(); dsr.check(dsr._lib.dsr_gcc_kernel_ms(g.h, two)); kms.append((two[0], two[1]))
+            call(); two = (ctypes.c_double * 2)(); dsr.check(dsr._lib.dsr_gcc_kernel_ms(g.h, two)); kms.append((two[0], two[1]))
         dsr.check(dsr._lib.dsr_gcc_set_timing(g.h, 0))
         ms_spec = sorted(k[0] for k in kms)[len(kms) // 2]; ms_corr = sorted(k[1] for k in kms)[len(kms) // 2]
         nSpeech = int(sad.sum().item()) * P

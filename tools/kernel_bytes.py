@@ -23,7 +23,8 @@ for m in re.finditer(r"^\s*\d+:\s+([0-9a-f]{16})\s+(\d+)\s+(\S+)\s+\S+\s+\S+\s+(
 notes = run("--notes")
 kernels = [n for n in syms if syms[n][3] == "FUNC" and n + ".kd" in syms]
 shown = subprocess.run([CXXFILT, *kernels], capture_output=True, text=True, check=True).stdout.split("\n") if CXXFILT else kernels
-shown = {n: re.sub(r"^void |\bdsr::", "", d).split("(")[0] for n, d in zip(kernels, shown)}      # k_viterbi<0>, not void dsr::k_viterbi<0>(dsr::VitArgs)
+# k_viterbi<0>, not void dsr::k_viterbi<0>(dsr::VitArgs); k_mcc_cost<1>, not void (anonymous namespace)::k_mcc_cost<1>(...)
+shown = {n: re.sub(r"^void |\bdsr::|\(anonymous namespace\)::", "", d).split("(")[0] for n, d in zip(kernels, shown)}
 for name in sorted(kernels, key=lambda n: shown[n]):
     if only not in shown[name]:
         continue

@@ -73,4 +73,6 @@ struct dsr_train;
 namespace dsr {
 // count - denCount and sumO of a trainer's accumulator rows into device arrays c [G], sumO [G][D] (k_mllr_take); dsr_apt_set_stats shares it
 void take_stats(const dsr_train& t, int G, int D, double* c, double* sumO);
+// the same with sumOsq [G][D] (or NULL); dsr_sat_set_stats uses it
+void take_stats_sq(const dsr_train& t, int G, int D, double* c, double* sumO, double* sumOsq);
 }  // namespace dsr

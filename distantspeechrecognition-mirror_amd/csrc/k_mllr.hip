@@ -33,13 +33,15 @@ static constexpr int kChunk = 64;                         // Gaussians per workg
 static constexpr int kMaxD = 80;                          // two (D + 1)^2 fp64 matrices of k_mllr_solve fit the LDS
 static constexpr int kSolveThreads = 128;
 
-__global__ __launch_bounds__(256) void k_mllr_take(const double* __restrict__ acc, int G, int D, double* __restrict__ c, double* __restrict__ sumO)
+// sumOsq: NULL, or where the squared sums go (take_stats_sq)
+__global__ __launch_bounds__(256) void k_mllr_take(const double* __restrict__ acc, int G, int D, double* __restrict__ c, double* __restrict__ sumO,
+                                                   double* __restrict__ sumOsq)
 {
   const long idx = (long) blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long) G * (D + 1)) return;
   const int g = (int) (idx / (D + 1)), d = (int) (idx - (long) g * (D + 1));
   const double* row = acc + (long) g * (2 * D + 4);
-  if (d < D) sumO[(long) g * D + d] = row[d]; else c[g] = __dsub_rn(row[2 * D], row[2 * D + 1]);
+  if (d < D) { sumO[(long) g * D + d] = row[d]; if (sumOsq) sumOsq[(long) g * D + d] = row[D + d]; } else c[g] = __dsub_rn(row[2 * D], row[2 * D + 1]);
 }
 
 // chunk[3 k] = { leaf, first sorted Gaussian, Gaussians }; pq[col] = p | q << 16 of a G column, n of a z column, -1 of padding
@@ -194,12 +196,13 @@ __global__ __launch_bounds__(256) void k_mllr_apply(int D, int G, const float* _
   out[((long) sp * G + g) * D + m] = comp;
 }
 
-void take_stats(const dsr_train& t, int G, int D, double* c, double* sumO)
+void take_stats_sq(const dsr_train& t, int G, int D, double* c, double* sumO, double* sumOsq)
 {
   if (t.G != G || t.D != D) throw Error(DSR_E_DIMENSION, "accumulators of %d Gaussians x %d for a model of %d x %d", t.G, t.D, G, D);
-  launch(k_mllr_take, dim3(cdiv((long) G * (D + 1), 256)), dim3(256), 0, nullptr, t.d_acc.p, G, D, c, sumO);
+  launch(k_mllr_take, dim3(cdiv((long) G * (D + 1), 256)), dim3(256), 0, nullptr, t.d_acc.p, G, D, c, sumO, sumOsq);
   DSR_HIP(hipDeviceSynchronize());
 }
+void take_stats(const dsr_train& t, int G, int D, double* c, double* sumO) { take_stats_sq(t, G, D, c, sumO, nullptr); }
 
 namespace {
 

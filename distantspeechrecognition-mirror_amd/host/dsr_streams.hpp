@@ -1441,6 +1441,7 @@ class CodebookSetAdapt : public CodebookSetBasic {
   }
   // the sub-feature layout the all-pass transforms work on (CodebookSetBasic::subFeatLen / nSubFeat); one sub-feature of dimN until set
   void setSubFeatures(unsigned subFeatLen, unsigned nSubFeat = 1) { _subLen = (int) subFeatLen; _nSub = (int) nSubFeat; }
+  int nSubFeat() const { return _nSub; }
   // the all-pass handle of this set for one kind and bias type, made on first use
   dsr_apt* aptAdapter(int kind, int biasType = 0) {
     dsr_apt*& h = _apt[kind * 4 + biasType];
@@ -1795,3 +1796,57 @@ class LDAEstimator : public LDATransformer {
   DistribSetTrainPtr _dss; DistribSetBasicPtr _global;
 };
 typedef std::shared_ptr<LDAEstimator> LDAEstimatorPtr;
+
+// ---- asr/sat over dsr_sat_* (include/dsr.h section 14): SpeakerList (transform.cc:1989-1998), MeanSAT and VarianceSAT = SAT<SATBase::MeanAcc>,
+// SAT<SATBase::VarianceAcc> (sat.h:736-800, sat.cc:1763-1855).  The ML slice: a likelihood threshold, extended means and the fast,
+// regression-class and MMI accumulators are refused by the library.
+class SpeakerList {
+ public:
+  SpeakerList(const String& spkrList) : _fileName(spkrList) {
+    int n = 0, bytes = 0; dsr_throw(dsr_speaker_list_read(spkrList.c_str(), 0, 0, &n, &bytes));
+    std::vector<char> buf((size_t) bytes + 1, '\0'); dsr_throw(dsr_speaker_list_read(spkrList.c_str(), buf.data(), bytes, &n, &bytes));
+    const String all(buf.data(), (size_t) bytes);
+    for (size_t p = 0; (int) _slist.size() < n; p = all.find('\n', p) + 1) _slist.push_back(all.substr(p, all.find('\n', p) - p));
+  }
+  const std::vector<String>& speakers() const { return _slist; }
+  const String& fileName() const { return _fileName; }
+ private:
+  String _fileName; std::vector<String> _slist;
+};
+typedef std::shared_ptr<SpeakerList> SpeakerListPtr;
+
+class SATBase {
+ public:
+  virtual ~SATBase() { dsr_sat_destroy(_h); }
+  void zero() { dsr_throw(dsr_sat_zero(_h)); }
+  // SATBase::estimate (sat.cc:1802-1839): <meanVarsStats><spkr>.cbs.accu and <spkrAdaptParms><spkr> of every speaker, then the update
+  double estimate(const SpeakerListPtr& sList, const String& spkrAdaptParms, const String& meanVarsStats) {
+    double r = 0.0; dsr_throw(dsr_sat_estimate_files(_h, _what, sList->fileName().c_str(), spkrAdaptParms.c_str(), meanVarsStats.c_str(), &r)); return r;
+  }
+  dsr_sat* satHandle() const { return _h; }
+ protected:
+  SATBase(CodebookSetTrainPtr& cbs, int what, int kind, unsigned meanLen, double lhoodThreshhold, double massThreshhold, unsigned nParts, unsigned part, double mmiMultiplier, bool meanOnly, int slots)
+    : _cbs(cbs), _h(0), _what(what) {
+    if (mmiMultiplier != 1.0 || meanOnly) throw jparameter_error("mmiMultiplier and meanOnly act in the MMI-SAT accumulators only, which are not implemented");
+    dsr_throw(dsr_sat_check((int) meanLen, dsr_gmm_dim(cbs->model()), lhoodThreshhold, kind));
+    dsr_throw(dsr_sat_create(cbs->trainHandle(), slots, massThreshhold, (int) nParts, (int) part, &_h));
+    const dsr_status st = dsr_sat_set_apt_sub_features(_h, cbs->nSubFeat()); if (st) { dsr_sat_destroy(_h); _h = 0; dsr_throw(st); }
+  }
+ private:
+  SATBase(const SATBase&); SATBase& operator=(const SATBase&);
+  CodebookSetTrainPtr _cbs; dsr_sat* _h; int _what;
+};
+class MeanSAT : public SATBase {
+ public:
+  MeanSAT(CodebookSetTrainPtr& cbs, unsigned meanLen = 0, double lhoodThreshhold = 0.0, double massThreshhold = 0.0, unsigned nParts = 1, unsigned part = 1,
+          double mmiMultiplier = 1.0, bool meanOnly = false, int slots = 16)
+    : SATBase(cbs, 1, 0, meanLen, lhoodThreshhold, massThreshhold, nParts, part, mmiMultiplier, meanOnly, slots) {}
+};
+class VarianceSAT : public SATBase {
+ public:
+  VarianceSAT(CodebookSetTrainPtr& cbs, unsigned meanLen = 0, double lhoodThreshhold = 0.0, double massThreshhold = 0.0, unsigned nParts = 1, unsigned part = 1,
+              double mmiMultiplier = 1.0, bool meanOnly = false, int slots = 16)
+    : SATBase(cbs, 2, 1, meanLen, lhoodThreshhold, massThreshhold, nParts, part, mmiMultiplier, meanOnly, slots) {}
+};
+typedef std::shared_ptr<MeanSAT> MeanSATPtr;
+typedef std::shared_ptr<VarianceSAT> VarianceSATPtr;

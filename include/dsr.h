@@ -2254,7 +2254,7 @@ dsr_status dsr_train_kernel_ms(const dsr_train*, float ms[2]);
  * 10. MLLR speaker adaptation: regression classes, parameter trees, estimation, mean transforms
  *    Replaces the MLLR branch of asr/adapt/transform.{h,cc} ("tr") and asr/train/estimateAdapt.{h,cc} ("eA").  The all-pass transforms
  *    are section 13 (BLT and SLAPT with one estimated parameter; RAPT with more parameters and the multi-parameter Newton search are not
- *    implemented), STC and LDA section 12; asr/sat is not implemented.
+ *    implemented), STC and LDA section 12, the ML slice of asr/sat section 14.
  * ===================================================================================== */
 /* The regression-class table of a model: CodebookBasic::_regClass (asr/gaussian/codebookBasic.cc:179-187).  dsr_gmm_load keeps the FIRST class
  * of each Gaussian of a codebook file whose regClassPresent is set (:286-297) -- GaussDensity::regClass() (codebookBasic.h:275-280) -- and
@@ -2575,7 +2575,7 @@ dsr_lda* dsr_lda_feature_handle(dsr_stream*);
  *    A cepstral mean of nSubFeat sub-features of subFeatLen (flat index isub subFeatLen + n) is mapped by one subFeatLen x subFeatLen
  *    matrix per regression class, read off the powers of a Laurent series Q(z) of 150 coefficients a side, plus an optional bias.
  *    Not implemented, and refused: RAPT with more than one parameter, estimation of more than one parameter (the Newton search with
- *    gradient and Hessian matrices), an ldaFile, extended means (orgSubFeatLen != subFeatLen), asr/sat.
+ *    gradient and Hessian matrices), an ldaFile, extended means (orgSubFeatLen != subFeatLen).
  *
  *  Parameters (host only: needs no device).  A dsr_apt_params is the ParamTree of one speaker, of RAPTParam or of SLAPTParam; dsr_param_tree
  *  keeps refusing these files.  type: 0 unspecified, 1 RAPT, 2 SLAPT (AdaptationType + 1).
@@ -2667,6 +2667,98 @@ dsr_status dsr_apt_kernel_ms(const dsr_apt*, float ms[3]);
  * computed on the device by k_apt_matrix and k_apt_apply.  The errors of get_matrix and adapt */
 dsr_status dsr_apt_transform_rows(int kind, int subFeatLen, int nSubFeat, int nConf, const double* conf, int nBias, const float* bias,
                                   const float* rows, int N, double* A, float* out);
+
+/* ---------------------------------------------------------------------------------------------------------------------------------------
+ * 14. Speaker-adaptive training (ML-SAT): the canonical means and variances given every speaker's transform and statistics
+ *     (csrc/sat_kernels.hip, csrc/sat.cpp)
+ *
+ *    Replaces SATMean (asr/sat/sat.cc, "sat": 54-342), SATVariance (sat:686-760), SATBase::MeanAcc (sat:999-1025), SATBase::VarianceAcc
+ *    (sat:1194-1246), SATBase and SAT<Type> = MeanSAT / VarianceSAT (sat:1763-1855, sat.h:736-800), TransformerTreeList::getTree
+ *    (sat:1884-1896) and SpeakerList (asr/adapt/transform.cc, "tr": 1989-1998) for the diagonal 1:1 models of dsr_gmm with
+ *    orgFeatLen == featLen, under MLLR transforms (one block dimN x dimN, tr:1746-1785) and BLT / SLAPT transforms (nSubFeat blocks of
+ *    subFeatLen^2 holding the same matrix, the bias as the block offsets, tr:1339-1363).
+ *    Not implemented, and refused by dsr_sat_check: MDLSATMean (a likelihood threshold), FastSAT / FastAcc and the CodebookFastSAT
+ *    accumulators, RegClassAcc / MMIRegClassAcc, FastMMISAT, SATMeanFullCovar, cluster.cc, extended means, an ldaFile; STC / LDA blocks in a
+ *    speaker file are refused by the parameter readers.
+ *
+ *   check              the options of SAT<Type>(cbs, meanLen, lhoodThreshhold, massThreshhold, ...): DSR_E_PARAMETER for an accumulator kind
+ *                      other than 0 (MeanAcc) or 1 (VarianceAcc) and for lhoodThreshold != 0, DSR_E_DIMENSION for meanLen != 0 and
+ *                      != featLen (extended means).  Host only
+ *   speaker_list_read  SpeakerList (tr:1989-1998): one label a line, read with fgets into 128 bytes (a longer line arrives in pieces);
+ *                      labels [*bytes] receives them joined by '\n' when cap suffices; DSR_E_PARSE for an empty line.  Host only
+ *   create             S speaker slots over the trainer's model; massThreshold 0 means 10 (sat:1768); (nParts, part) pick the codebooks
+ *                      as dsr_train_update does.  The trainer and its dsr_gmm must outlive the handle
+ *   zero               SATMean::zero / SATVariance::zero of every Gaussian: the sums and occupancies; allocated blocks stay allocated
+ *   set_stats          count - denCount, sumO and sumOsq of a trainer's accumulators into slot s (device to device);  set_stats_arrays
+ *                      the same from host arrays c [G], sumO, sumOsq [G][dimN];  clear_slot  zero statistics and no transforms
+ *   set_tree           the slot's transforms from an MLLR parameter tree, class by class (tr:2125-2135): DSR_E_DIMENSION for a matrix or
+ *                      bias of another size (tr:1757-1761);  set_apt  from slot aptSlot of an APT handle through k_apt_matrix (the errors of
+ *                      dsr_apt_get_matrix);  set_transform  from arrays: kind 1 (MLLR: the float chain of tr:1777-1784 in the variance
+ *                      accumulator) or 2 (APT: the double sum stored to float, then the float bias, tr:1300-1336), A [nBlocks][bl][bl] with
+ *                      bl = dimN / nBlocks, b [dimN] or NULL.  DSR_E_INDEX for class 0 (tr:2021-2022), DSR_E_DIMENSION for a block count that
+ *                      does not divide dimN (sat:63-65) or bl > 81 (two bl^2 fp64 matrices in LDS).  set_tree and set_apt replace the
+ *                      slot's transforms, set_transform adds or replaces one class
+ *   set_apt_sub_features  nSubFeat of the RAPT / SLAPT files estimate_files reads (default 1)
+ *   accumulate         what 1: SATMean::accumulate (sat:171-218), what 2: SATVariance::accumulate (sat:704-729), of slots 0 .. nSlots - 1 in
+ *                      order for every Gaussian of the part, with the slot's transformer of exactly the Gaussian's class
+ *                      (tr:2165-2173): DSR_E_INDEX for class 0, DSR_E_KEY for a missing class, DSR_E_CONSISTENCY for a class with a
+ *                      descendant in the slot (not a leaf), DSR_E_DIMENSION for transforms of different block counts or another count than
+ *                      an earlier batch's (sat:57-59; one count per handle, where the reference keeps one per Gaussian); nothing is
+ *                      accumulated then.  float c = float(count - denCount); c == 0 contributes nothing and allocates no blocks.  The mean
+ *                      sums are fp64 on v_mfma_f64_16x16x4_f64 in a fixed order (the same calls twice give the same bits), occ the
+ *                      sequential double sum in slot order; the variance sums are the reference's arithmetic bit for bit
+ *   update             what 1: MeanAcc::update (sat:1010-1023, 288-342): a Gaussian with occ < massThreshold is left alone; occ == 0 with
+ *                      blocks zeroes the mean; otherwise per block auxOld, the solve (sat:257-274, component k kept when
+ *                      |l_k| / max |l| >= 1e-7), auxNew, and the block kept as it was when auxOld < auxNew.  info [4] = ttlBlocks,
+ *                      ttlBlocksUpdated, ttlDimensions, ttlDimensionsUpdated of this call (sat:304, 324, 339, 267, 273), totals [2] =
+ *                      _TotalGaussians, _TotalUpdatedGaussians, *aux the sum of the per-block auxiliary values in model order.  A Gaussian
+ *                      whose statistics are not finite or whose eigen-decomposition did not converge keeps its mean and is flagged
+ *                      (gaussian_status); the others are done and the call returns DSR_E_CONSISTENCY; a NaN solution DSR_E_NUMERIC
+ *                      what 2: VarianceAcc::update (sat:1233-1244, 731-756): below the threshold var = 1 / var (fixup), occ == 0 zeros,
+ *                      otherwise float(vec / occ), a NaN DSR_E_NUMERIC.  The covariance slot holds VARIANCES afterwards: call
+ *                      dsr_train_invert_variances and dsr_train_fix_gconsts.  Any of info, totals, aux may be NULL
+ *   estimate_files     SATBase::estimate (sat:1802-1839): for every label of the list, in order, <accuPrefix><label>.cbs.accu is loaded
+ *                      into the trainer (factor 1, the handle's nParts and part), <paramPrefix><label> (no separator, sat:1890) is read
+ *                      as an MLLR tree or as RAPT / SLAPT parameters, S speakers are accumulated a batch, the trainer's accumulators are
+ *                      zeroed; then update.  *ret = (sum totalPr) / (sum totalT).  The SAT accumulators are not zeroed first
+ *   get_mean_accu      mat [bl][bl], vec [bl], scalar and occ of (Gaussian, block);  get_mean_accus  all [G][nBlocks][bl^2 + bl + 1], occ [G]
+ *                      and the blocks-allocated flags [G];  get_var_accu(s)  vec [dimN] and occ.  Any pointer may be NULL
+ *   keep_transformed   the next variance accumulations keep transform(origMean) of their slots;  get_transformed  [G][dimN] of slot s
+ *   get_records        of the last mean update, [G][nBlocks]: kept dimensions, decision (0 left alone, 1 updated, 2 old mean kept,
+ *                      3 zeroed, 4 flagged, 5 NaN), auxOld, auxNew;  get_solution  [G][dimN]: the solved means in double, before the
+ *                      decision and the store to float (0 where nothing was solved);  gaussian_status  0, DSR_E_CONSISTENCY or DSR_E_NUMERIC
+ *   kernel_ms          milliseconds of the last k_sat_mean_acc, k_sat_var_acc and k_sat_solve */
+typedef struct dsr_sat dsr_sat;
+dsr_status dsr_sat_check(int meanLen, int featLen, double lhoodThreshold, int accKind);
+dsr_status dsr_speaker_list_read(const char* fileName, char* labels, int cap, int* n, int* bytes);
+dsr_status dsr_sat_create(dsr_train*, int S, double massThreshold, int nParts, int part, dsr_sat** out);
+void dsr_sat_destroy(dsr_sat*);
+int dsr_sat_num_slots(const dsr_sat*);
+int dsr_sat_num_blocks(const dsr_sat*);
+dsr_status dsr_sat_set_apt_sub_features(dsr_sat*, int nSubFeat);
+dsr_status dsr_sat_zero(dsr_sat*);
+dsr_status dsr_sat_set_stats(dsr_sat*, int s, dsr_train*);
+dsr_status dsr_sat_set_stats_arrays(dsr_sat*, int s, const double* c, const double* sumO, const double* sumOsq);
+dsr_status dsr_sat_set_tree(dsr_sat*, int s, const dsr_param_tree*);
+dsr_status dsr_sat_set_apt(dsr_sat*, int s, dsr_apt*, int aptSlot);
+dsr_status dsr_sat_set_transform(dsr_sat*, int s, unsigned rc, int kind, int nBlocks, const double* A, const double* b);
+dsr_status dsr_sat_get_transform(const dsr_sat*, int s, unsigned rc, int* kind, int* nBlocks, int* bSize, double* A, double* b);
+int dsr_sat_slot_classes(const dsr_sat*, int s, unsigned* classes, int cap);
+dsr_status dsr_sat_clear_slot(dsr_sat*, int s);
+dsr_status dsr_sat_accumulate(dsr_sat*, int what, int nSlots, void* stream);
+dsr_status dsr_sat_update(dsr_sat*, int what, unsigned info[4], unsigned totals[2], double* aux);
+dsr_status dsr_sat_estimate_files(dsr_sat*, int what, const char* speakerList, const char* paramPrefix, const char* accuPrefix, double* ret);
+dsr_status dsr_sat_get_mean_accu(dsr_sat*, int g, int block, double* mat, double* vec, double* scalar, double* occ);
+dsr_status dsr_sat_get_mean_accus(dsr_sat*, double* acc, double* occ, int32_t* has);
+dsr_status dsr_sat_get_var_accu(dsr_sat*, int g, double* vec, double* occ);
+dsr_status dsr_sat_get_var_accus(dsr_sat*, double* vec, double* occ);
+dsr_status dsr_sat_keep_transformed(dsr_sat*, int on);
+dsr_status dsr_sat_get_transformed(dsr_sat*, int s, float* means);
+dsr_status dsr_sat_get_records(const dsr_sat*, int32_t* kept, int32_t* decision, double* auxOld, double* auxNew);
+dsr_status dsr_sat_get_solution(const dsr_sat*, double* means);
+int dsr_sat_gaussian_status(const dsr_sat*, int g);
+dsr_status dsr_sat_set_timing(dsr_sat*, int on);
+dsr_status dsr_sat_kernel_ms(const dsr_sat*, float ms[3]);
 
 #ifdef __cplusplus
 }

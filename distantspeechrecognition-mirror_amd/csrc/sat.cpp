@@ -30,6 +30,12 @@ std::vector<std::string> read_speaker_list(const char* fileName)
   return list;
 }
 
+void sat_part_gaussians(const SatHandle& h, int& g0, int& g1)
+{
+  int k0, k1; part_range(h.g->K, h.nParts, h.part, k0, k1);
+  g0 = h.g->off[k0]; g1 = h.g->off[k1];
+}
+
 namespace {
 
 void check_slot(const SatHandle& h, int s) { if (s < 0 || s >= h.S) throw Error(DSR_E_INDEX, "slot %d of %d", s, h.S); }
@@ -40,11 +46,7 @@ void check_model(const SatHandle& h)
   if (h.g->G != h.G || h.g->D != h.D || h.tr->G != h.G) throw Error(DSR_E_DIMENSION, "the model changed shape under the SAT handle (%d x %d, now %d x %d)", h.G, h.D, h.g->G, h.g->D);
 }
 
-void part_gaussians(const SatHandle& h, int& g0, int& g1)
-{
-  int k0, k1; part_range(h.g->K, h.nParts, h.part, k0, k1);
-  g0 = h.g->off[k0]; g1 = h.g->off[k1];
-}
+void part_gaussians(const SatHandle& h, int& g0, int& g1) { sat_part_gaussians(h, g0, g1); }
 
 void put_xform(SatHandle& h, int s, unsigned rc, SatXform& x)
 {
@@ -97,14 +99,11 @@ void sat_zero(SatHandle& h)
   DSR_HIP(hipMemset(h.d_vocc.p, 0, (size_t) h.G * sizeof(double)));                                   // the blocks stay allocated: d_has is kept (sat:240-253)
 }
 
-void sat_accumulate(SatHandle& h, int what, int nSlots, hipStream_t st)
+}  // namespace
+
+void sat_tables(SatHandle& h, int nSlots, int g0, int g1, SatCall& c, std::vector<int>& gidx, std::vector<int>& tile, hipStream_t st)
 {
-  if (what != kSatMean && what != kSatVariance) throw Error(DSR_E_PARAMETER, "accumulate %d: 1 (means) or 2 (variances)", what);
-  if (nSlots < 1 || nSlots > h.S) throw Error(DSR_E_INDEX, "%d slots of %d", nSlots, h.S);
-  check_model(h);
   const GmmModel& m = *h.g; const int D = h.D, G = h.G;
-  int g0, g1; part_gaussians(h, g0, g1);
-  if (g0 == g1) return;
   std::vector<unsigned> classes;
   for (int g = g0; g < g1; g++) {
     const unsigned rc = m.regClass.empty() ? 0u : m.regClass[g];
@@ -124,7 +123,6 @@ void sat_accumulate(SatHandle& h, int what, int nSlots, hipStream_t st)
       if (nB == 0) nB = it->second.nBlocks;
       else if (nB != it->second.nBlocks) throw Error(DSR_E_DIMENSION, "Block sizes (%d vs %d) are not equivalent.", it->second.nBlocks, nB);
     }
-  if (what == kSatMean && h.nBlocks && nB != h.nBlocks) throw Error(DSR_E_DIMENSION, "Block sizes (%d vs %d) are not equivalent.", nB, h.nBlocks);   // sat:57-59
   const int bl = D / nB;
   // the tables [slot][class]
   std::vector<double> A((size_t) nSlots * NC * D * bl), b((size_t) nSlots * NC * D); std::vector<int> kind((size_t) nSlots * NC), bsz((size_t) nSlots * NC);
@@ -135,16 +133,30 @@ void sat_accumulate(SatHandle& h, int what, int nSlots, hipStream_t st)
       kind[tab] = x.kind; bsz[tab] = x.bSize;
     }
   // the Gaussians sorted by class (stable), cut into tiles that do not cross a class
-  std::vector<int> cls(G, 0), gidx, tile; std::vector<std::vector<int>> of(NC);
+  std::vector<int> cls(G, 0); std::vector<std::vector<int>> of(NC); gidx.clear(); tile.clear();
   for (int g = g0; g < g1; g++) { cls[g] = (int) (std::lower_bound(classes.begin(), classes.end(), (unsigned) m.regClass[g]) - classes.begin()); of[cls[g]].push_back(g); }
   for (int k = 0; k < NC; k++)
     for (size_t i0 = 0; i0 < of[k].size(); i0 += kSatTileG) {
       tile.push_back(k); tile.push_back((int) gidx.size()); tile.push_back((int) std::min((size_t) kSatTileG, of[k].size() - i0));
       gidx.insert(gidx.end(), of[k].begin() + i0, of[k].begin() + i0 + tile.back());
     }
-  SatCall c; c.nSlots = nSlots; c.NC = NC; c.nB = nB; c.bl = bl; c.g0 = g0; c.g1 = g1; c.nTiles = (int) (tile.size() / 3);
-  const int P = bl * (bl + 1) / 2; c.PZ = (P + 15) & ~15; c.NCp = (c.PZ + bl + 15) & ~15;
+  c.nSlots = nSlots; c.NC = NC; c.nB = nB; c.bl = bl; c.g0 = g0; c.g1 = g1; c.nTiles = (int) (tile.size() / 3); c.PZ = c.NCp = 0;
   h.d_A.upload(A, st); h.d_b.upload(b, st); h.d_kind.upload(kind, st); h.d_bsz.upload(bsz, st); h.d_cls.upload(cls, st);
+}
+
+void sat_accumulate(SatHandle& h, int what, bool matOnly, int nSlots, hipStream_t st)
+{
+  if (what != kSatMean && what != kSatVariance) throw Error(DSR_E_PARAMETER, "accumulate %d: 1 (means) or 2 (variances)", what);
+  if (nSlots < 1 || nSlots > h.S) throw Error(DSR_E_INDEX, "%d slots of %d", nSlots, h.S);
+  check_model(h);
+  const GmmModel& m = *h.g; const int D = h.D, G = h.G;
+  int g0, g1; sat_part_gaussians(h, g0, g1);
+  if (g0 == g1) return;
+  SatCall c; std::vector<int> gidx, tile;
+  sat_tables(h, nSlots, g0, g1, c, gidx, tile, st);
+  const int nB = c.nB, bl = c.bl;
+  if (what == kSatMean && h.nBlocks && nB != h.nBlocks) throw Error(DSR_E_DIMENSION, "Block sizes (%d vs %d) are not equivalent.", nB, h.nBlocks);   // sat:57-59
+  const int P = bl * (bl + 1) / 2; c.PZ = (P + 15) & ~15; c.NCp = matOnly ? c.PZ : (c.PZ + bl + 15) & ~15;
   if (what == kSatMean) {
     if (!h.nBlocks) {                                     // SATMean::_checkBlocks, sat:63-81
       h.d_macc.reserve((size_t) G * nB * ((size_t) bl * bl + bl + 1));
@@ -152,9 +164,9 @@ void sat_accumulate(SatHandle& h, int what, int nSlots, hipStream_t st)
       h.nBlocks = nB; h.bl = bl;
     }
     std::vector<int> pq(c.NCp, -1);
-    { int col = 0; for (int p = 0; p < bl; p++) for (int q = p; q < bl; q++) pq[col++] = p | (q << 16); for (int n = 0; n < bl; n++) pq[c.PZ + n] = n; }
+    { int col = 0; for (int p = 0; p < bl; p++) for (int q = p; q < bl; q++) pq[col++] = p | (q << 16); if (!matOnly) for (int n = 0; n < bl; n++) pq[c.PZ + n] = n; }
     h.d_pq.upload(pq, st); h.d_gidx.upload(gidx, st); h.d_tile.upload(tile, st); h.d_ivar.upload(m.ivar, st);
-    sat_mean_acc(h, c, st);
+    sat_mean_acc(h, c, matOnly, st);
   } else {
     h.d_mean.upload(m.mean, st);
     if (h.keepTrn) { h.d_trn.reserve((size_t) nSlots * G * D); DSR_HIP(hipMemsetAsync(h.d_trn.p, 0, (size_t) nSlots * G * D * sizeof(float), st)); h.trnSlots = nSlots; }
@@ -162,6 +174,8 @@ void sat_accumulate(SatHandle& h, int what, int nSlots, hipStream_t st)
   }
   DSR_HIP(hipStreamSynchronize(st));
 }
+
+namespace {
 
 void update_means(SatHandle& h, unsigned info[4], unsigned totals[2], double* aux)
 {
@@ -258,7 +272,11 @@ void take_into_slot(SatHandle& h, int s, dsr_train& t)
 }
 
 // the parameter file of one speaker into a slot: an MLLR tree, or RAPT / SLAPT parameters through the APT matrix kernel
-void read_params(SatHandle& h, int s, const std::string& fileName)
+void read_params(SatHandle& h, int s, const std::string& fileName) { sat_read_params(h, s, fileName); }
+
+}  // namespace
+
+void sat_read_params(SatHandle& h, int s, const std::string& fileName)
 {
   { FILE* fp = fopen(fileName.c_str(), "r"); if (!fp) throw Error(DSR_E_IO, "Could not open file %s.", fileName.c_str()); fclose(fp); }
   ParamTree t; bool mllr = true;
@@ -271,6 +289,8 @@ void read_params(SatHandle& h, int s, const std::string& fileName)
     if (st) throw Error(st, "%s", dsr_last_error());
   });
 }
+
+namespace {
 
 double estimate_files(SatHandle& h, int what, const char* speakerList, const char* paramPrefix, const char* accuPrefix)
 {
@@ -287,7 +307,7 @@ double estimate_files(SatHandle& h, int what, const char* speakerList, const cha
     read_params(h, filled, std::string(paramPrefix) + list[i]);                                       // no separator, sat:1890
     take_into_slot(h, filled, *h.tr);
     st = dsr_train_zero(h.tr, 1, h.nParts, h.part); if (st) throw Error(st, "%s", dsr_last_error());
-    if (++filled == h.S || i + 1 == list.size()) { sat_accumulate(h, what, filled, nullptr); filled = 0; }
+    if (++filled == h.S || i + 1 == list.size()) { sat_accumulate(h, what, false, filled, nullptr); filled = 0; }
   }
   sat_update(h, what, nullptr, nullptr, nullptr);
   return totalPr / totalT;
@@ -438,7 +458,7 @@ dsr_status dsr_sat_clear_slot(dsr_sat* h, int s)
 }
 
 dsr_status dsr_sat_accumulate(dsr_sat* h, int what, int nSlots, void* stream)
-{ return guard([&] { if (!h) throw Error(DSR_E_PARAMETER, "null argument"); sat_accumulate(*h, what, nSlots, (hipStream_t) stream); }); }
+{ return guard([&] { if (!h) throw Error(DSR_E_PARAMETER, "null argument"); sat_accumulate(*h, what, false, nSlots, (hipStream_t) stream); }); }
 
 dsr_status dsr_sat_update(dsr_sat* h, int what, unsigned info[4], unsigned totals[2], double* aux)
 { return guard([&] { if (!h) throw Error(DSR_E_PARAMETER, "null argument"); sat_update(*h, what, info, totals, aux); }); }

@@ -46,11 +46,19 @@ struct SatHandle {
 // what one accumulate call hands the kernels: the Gaussians [g0, g1) sorted by class and cut into tiles, and the table sizes
 struct SatCall { int nSlots, NC, nB, bl, g0, g1, nTiles, PZ, NCp; };
 
-void sat_mean_acc(SatHandle& h, const SatCall& c, hipStream_t st);
+void sat_mean_acc(SatHandle& h, const SatCall& c, bool matOnly, hipStream_t st);   // matOnly: FastSAT::accumulate, mat and occ alone
 void sat_var_acc(SatHandle& h, const SatCall& c, hipStream_t st);
 void sat_solve(SatHandle& h, int nSolve, hipStream_t st);
 
 std::vector<std::string> read_speaker_list(const char* fileName);      // tr:1989-1998
+
+// sat.cpp, as fsat.cpp uses them on the SatHandle it owns.
+// sat_tables: the transformer of every (slot, class of a Gaussian in [g0, g1)) checked (tr:2165-2173) and uploaded with the class of every
+// Gaussian; gidx / tile: the Gaussians sorted by class and cut into tiles of kSatTileG that do not cross a class
+void sat_tables(SatHandle& h, int nSlots, int g0, int g1, SatCall& c, std::vector<int>& gidx, std::vector<int>& tile, hipStream_t st);
+void sat_accumulate(SatHandle& h, int what, bool matOnly, int nSlots, hipStream_t st);
+void sat_read_params(SatHandle& h, int s, const std::string& fileName);
+void sat_part_gaussians(const SatHandle& h, int& g0, int& g1);
 
 }  // namespace dsr
 

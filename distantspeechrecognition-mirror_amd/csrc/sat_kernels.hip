@@ -22,7 +22,7 @@
 #include "launch.h"
 #include "sat.h"
 #include "mfma64.h"
-#include "mllr_jacobi.h"
+#include "sat_dev.h"
 #include <cmath>
 
 namespace dsr {
@@ -30,7 +30,9 @@ namespace dsr {
 static constexpr int kSolveThreads = 128;
 static constexpr int kTilesPerWave = kSatColGroup / 64;
 
-// tile[3 t] = { class index, first sorted Gaussian, Gaussians }; pq[col] = p | q << 16 of a mat column, p of a vec column, -1 of padding
+// tile[3 t] = { class index, first sorted Gaussian, Gaussians }; pq[col] = p | q << 16 of a mat column, p of a vec column, -1 of padding.
+// kVec false is FastSAT::accumulate (sat:501-528): mat and occ only -- no vec columns (NCp == PZ), no scalar pass, sumO never read
+template <bool kVec>
 __global__ __launch_bounds__(256) void k_sat_mean_acc(int nSlots, int NC, int nB, int bl, int D, int G, int PZ, int NCp, const float* __restrict__ ivar,
                                                       const double* __restrict__ cnt, const double* __restrict__ sumO, const double* __restrict__ Atab,
                                                       const double* __restrict__ btab, const int* __restrict__ gidx, const int* __restrict__ tile,
@@ -75,7 +77,7 @@ __global__ __launch_bounds__(256) void k_sat_mean_acc(int nSlots, int NC, int nB
       if (cf != 0.0f && m < bl) {                         // sat:180
         const double iv = (double) ivs[lo * blp + m];
         aG = __dmul_rn(cd, iv);                           // exact
-        if (anyZ) aZ = __dmul_rn(iv, __dsub_rn(so[m], __dmul_rn(cd, bs[m])));
+        if (kVec && anyZ) aZ = __dmul_rn(iv, __dsub_rn(so[m], __dmul_rn(cd, bs[m])));
       }
 #pragma unroll
       for (int u = 0; u < kTilesPerWave; u++) {
@@ -103,7 +105,7 @@ __global__ __launch_bounds__(256) void k_sat_mean_acc(int nSlots, int NC, int nB
   // scalar: 16 lanes a Gaussian, lane l the rows m = l, l + 16, .. of every slot in order; the 16 partial sums added in lane order
   const int j = tid >> 4, l = tid & 15;
   double sum = 0.0;
-  if (j < n) {
+  if (kVec && j < n) {
     const int g = sg[j];
     for (int s = 0; s < nSlots; s++) {
       const float cf = (float) cnt[(long) s * G + g]; if (cf == 0.0f) continue;
@@ -123,7 +125,7 @@ __global__ __launch_bounds__(256) void k_sat_mean_acc(int nSlots, int NC, int nB
     double tot = 0.0;
     for (int k = 0; k < 16; k++) tot = __dadd_rn(tot, part[j * 16 + k]);
     double* base = macc + ((long) g * nB + nb) * stride;
-    base[bl * bl + bl] = __dadd_rn(base[bl * bl + bl], tot);
+    if (kVec) base[bl * bl + bl] = __dadd_rn(base[bl * bl + bl], tot);
     if (nb == 0) {
       double occ = mocc[g]; int seen = has[g];
       for (int s = 0; s < nSlots; s++) { const float cf = (float) cnt[(long) s * G + g]; if (cf == 0.0f) continue; occ = __dadd_rn(occ, (double) cf); seen = 1; }
@@ -149,20 +151,10 @@ __global__ __launch_bounds__(256) void k_sat_var_acc(int nSlots, int NC, int nB,
     const double cd = (double) cf;
     const long tab = (long) s * NC + cls[g];
     const double* a = Atab + ((tab * nB + nb) * bl + n) * bl;
-    float comp;
-    if (kind[tab] == kSatMLLR) {                          // tr:1777-1784
-      comp = k < bsz[tab] ? (float) btab[tab * D + k] : 0.0f;
-      for (int j = 0; j < bl; j++) comp = (float) __dadd_rn((double) comp, __dmul_rn(a[j], (double) mu[j]));
-    } else {                                              // tr:1300-1336
-      double sum = 0.0;
-      for (int j = 0; j < bl; j++) sum = __dadd_rn(sum, __dmul_rn(a[j], (double) mu[j]));
-      comp = (float) sum;
-      if (k < bsz[tab]) comp = __fadd_rn(comp, (float) btab[tab * D + k]);
-    }
+    const float comp = sat_transform_comp(kind[tab], k < bsz[tab], btab[tab * D + k], a, mu, bl);
     if (trn) trn[((long) s * G + g) * D + k] = comp;
-    const double tr = (double) comp, sqr = __dmul_rn(tr, tr);
     const long e = ((long) s * G + g) * D + k;
-    vec = __dadd_rn(__dsub_rn(__dadd_rn(vec, sumOsq[e]), __dmul_rn(__dmul_rn(2.0, tr), sumO[e])), __dmul_rn(cd, sqr));    // sat:723-724
+    vec = sat_var_term(vec, sumOsq[e], sumO[e], (double) comp, cd);                    // sat:723-724
     occ = __dadd_rn(occ, cd);
   }
   vvec[(long) g * D + k] = vec;
@@ -191,33 +183,11 @@ __global__ __launch_bounds__(kSolveThreads) void k_sat_solve(int nB, int bl, int
   for (int e = tid; e < n * n; e += nt) { a[e] = src[e]; v[e] = (e / n == e % n) ? 1.0 : 0.0; }
   for (int e = tid; e < n; e += nt) { z[e] = src[n * n + e]; x[e] = (double) mean[(long) g * D + nb * n + e]; }
   __syncthreads();
-  // _auxFunc (sat:276-286): 0.5 (mean^T (M mean) + scalar) - mean^T vec
-  for (int e = tid; e < n; e += nt) { double s = 0.0; for (int j = 0; j < n; j++) s = __dadd_rn(s, __dmul_rn(a[e * n + j], x[j])); t[e] = s; }
+  sat_rows_times(a, x, t, n, tid, nt);                   // _auxFunc (sat:276-286) at the current mean
   __syncthreads();
-  if (tid == 0) {
-    double ip1 = 0.0, ip2 = 0.0;
-    for (int e = 0; e < n; e++) { ip1 = __dadd_rn(ip1, __dmul_rn(t[e], x[e])); ip2 = __dadd_rn(ip2, __dmul_rn(x[e], z[e])); }
-    sh[0] = __dsub_rn(__dmul_rn(0.5, __dadd_rn(ip1, scalar)), ip2);
-  }
+  if (tid == 0) sh[0] = sat_aux_value(t, x, z, scalar, n);
   __syncthreads();
-  bool ok = false;
-  for (int sweep = 0; sweep <= kJacobiSweeps; sweep++) {
-    mj_norms(a, n, sq, tid, nt);
-    __syncthreads();
-    double off, all; mj_norms_done(sq, nt, off, all);
-    __syncthreads();
-    if (!(all <= 1.7E308)) break;                         // NaN or infinite
-    if (mj_converged(off, all, n)) { ok = true; break; }
-    if (sweep == kJacobiSweeps) break;
-    for (int r = 0; r < m - 1; r++) {
-      mj_angles(a, n, m, r, cs, tid, nt);
-      __syncthreads();
-      mj_rows(a, n, m, r, cs, tid, nt);
-      __syncthreads();
-      mj_cols(a, v, n, m, r, cs, tid, nt);
-      __syncthreads();
-    }
-  }
+  bool ok = sat_jacobi(a, v, n, m, cs, sq, tid, nt);
   for (int e = tid; e < n; e += nt) if (!(fabs(z[e]) <= 1.7E308)) ok = false;
   if (!(fabs(scalar) <= 1.7E308)) ok = false;
   ok = __syncthreads_and(ok);
@@ -239,12 +209,10 @@ __global__ __launch_bounds__(kSolveThreads) void k_sat_solve(int nB, int bl, int
     x[e] = sum; sol[(long) g * D + nb * n + e] = sum;
   }
   __syncthreads();
-  for (int e = tid; e < n; e += nt) { double s = 0.0; for (int j = 0; j < n; j++) s = __dadd_rn(s, __dmul_rn(src[e * n + j], x[j])); t[e] = s; }
+  sat_rows_times(src, x, t, n, tid, nt);
   __syncthreads();
   if (tid == 0) {
-    double ip1 = 0.0, ip2 = 0.0;
-    for (int e = 0; e < n; e++) { ip1 = __dadd_rn(ip1, __dmul_rn(t[e], x[e])); ip2 = __dadd_rn(ip2, __dmul_rn(x[e], z[e])); }
-    const double auxOld = sh[0], auxNew = __dsub_rn(__dmul_rn(0.5, __dadd_rn(ip1, scalar)), ip2);
+    const double auxOld = sh[0], auxNew = sat_aux_value(t, x, z, scalar, n);
     int decision = kSatUpdated;
     if (auxOld < auxNew) decision = kSatKeptOld;          // sat:322
     else for (int e = 0; e < n; e++) if (x[e] != x[e]) decision = kSatNaN;             // sat:330
@@ -255,12 +223,12 @@ __global__ __launch_bounds__(kSolveThreads) void k_sat_solve(int nB, int bl, int
   if ((int) sh[1] == kSatUpdated) for (int e = tid; e < n; e += nt) newMean[(long) g * D + nb * n + e] = (float) x[e];
 }
 
-void sat_mean_acc(SatHandle& h, const SatCall& c, hipStream_t st)
+void sat_mean_acc(SatHandle& h, const SatCall& c, bool matOnly, hipStream_t st)
 {
   const int blp = (c.bl + 3) & ~3;
   const size_t lds = ((size_t) blp * c.bl + blp + 256) * sizeof(double) + (size_t) kSatTileG * blp * sizeof(float);
   ScopedTimer tm(h.timing, st);
-  launch(k_sat_mean_acc, dim3(c.nTiles, cdiv(c.NCp, kSatColGroup), c.nB), dim3(256), lds, st, c.nSlots, c.NC, c.nB, c.bl, h.D, h.G, c.PZ, c.NCp, h.d_ivar.p,
+  launch(matOnly ? k_sat_mean_acc<false> : k_sat_mean_acc<true>, dim3(c.nTiles, cdiv(c.NCp, kSatColGroup), c.nB), dim3(256), lds, st, c.nSlots, c.NC, c.nB, c.bl, h.D, h.G, c.PZ, c.NCp, h.d_ivar.p,
          h.d_c.p, h.d_sumO.p, h.d_A.p, h.d_b.p, h.d_gidx.p, h.d_tile.p, h.d_pq.p, h.d_macc.p, h.d_mocc.p, h.d_has.p);
   h.ms[0] = tm.stop();
 }

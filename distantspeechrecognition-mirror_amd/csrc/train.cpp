@@ -15,26 +15,6 @@ using namespace dsr;
 
 namespace {
 
-const char* kEndOfAccs = "EndOfAccumulators";              // distribTrain.h:230-233
-const int kCbMarker = 123456789, kDsMarker = 987654321;    // cT:309, dT:264
-const int kCovDiagonal = 2;
-
-std::map<std::string, long> read_map(BEFile& f)            // AccMap::AccMap(FILE*), dT:343-355
-{
-  std::map<std::string, long> m;
-  for (;;) {
-    const std::string name = f.str(); if (name == kEndOfAccs) break;
-    if (m.count(name)) throw Error(DSR_E_KEY, "State map name %s is not unique.", name.c_str());
-    m[name] = f.i32();
-  }
-  return m;
-}
-void write_map(BEFile& f, const std::map<std::string, long>& m)   // AccMap::write, dT:400-411: std::map order
-{
-  for (std::map<std::string, long>::const_iterator it = m.begin(); it != m.end(); ++it) { f.wstr(it->first); f.w32((int) it->second); }
-  f.wstr(kEndOfAccs);
-}
-
 struct Rows {                                              // the columns of an accumulator row (csrc/train.h)
   int D;
   double* sumO(double* r) const { return r; }

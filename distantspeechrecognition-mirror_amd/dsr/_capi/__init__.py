@@ -33,11 +33,11 @@ from .sad import (_sad_out, sad_energy_state, sad_energy_reset, sad_energy, sad_
 from .gaussian import (Gmm, Trainer)
 from .adapt import (is_ancestor, ParamTree, Mllr, Fsa, _Estimators, Stc, Lda)
 from .decoder import (Wfst, Decoder, _lexh, Lattice, Pipe)
-_LAZY = dict(AdaptiveBeamformer="_abf", SampleRateConverter="_src", AptParams="_apt", Apt="_apt", apt_line_search="_apt", apt_transform_rows="_apt", APT_BIAS="_apt", APT_RAPT="_apt", APT_SLAPT="_apt", Sat="_sat", speaker_list_read="_sat", sat_check="_sat", SAT_MEAN="_sat", SAT_VARIANCE="_sat", SAT_MLLR="_sat", SAT_APT="_sat")
+_LAZY = dict(AdaptiveBeamformer="_abf", SampleRateConverter="_src", AptParams="_apt", Apt="_apt", apt_line_search="_apt", apt_transform_rows="_apt", APT_BIAS="_apt", APT_RAPT="_apt", APT_SLAPT="_apt", Sat="_sat", speaker_list_read="_sat", sat_check="_sat", SAT_MEAN="_sat", SAT_VARIANCE="_sat", SAT_MLLR="_sat", SAT_APT="_sat", FastSat="_fsat", fsat_check="_fsat")
 
 def __getattr__(name):
     if name == "_lib":                                 # the loaded library, live: _core owns it, load() rebinds it
         return _core._lib
-    if name in _LAZY:                                  # include/dsr.h sections 2a'', 6d, 13, 14: dsr/_abf.py, _src.py, _apt.py, _sat.py, on the common handle base
+    if name in _LAZY:                                  # include/dsr.h sections 2a'', 6d, 13, 14, 14b: dsr/_abf.py, _src.py, _apt.py, _sat.py, _fsat.py, on the common handle base
         import importlib; return getattr(importlib.import_module(".." + _LAZY[name], __name__), name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

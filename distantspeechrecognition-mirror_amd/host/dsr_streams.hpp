@@ -1850,3 +1850,73 @@ class VarianceSAT : public SATBase {
 };
 typedef std::shared_ptr<MeanSAT> MeanSATPtr;
 typedef std::shared_ptr<VarianceSAT> VarianceSATPtr;
+
+// ---- the fast form over dsr_fsat_* (include/dsr.h section 14b): CodebookSetFastSAT (codebookFastSAT.cc:571-717) and FastMeanVarianceSAT =
+// SATFast<SATBase::FastAcc> (sat.h:803-844, sat.i:164-190).  The regression-class and MMI variants are not built: their constructors throw.
+class CodebookSetFastSAT : public CodebookSetTrain {          // a CodebookSetTrain that keeps one fast accumulator per Gaussian
+ public:
+  CodebookSetFastSAT(const String& descFile = "", FeatureSetPtr fs = FeatureSetPtr(), const String& cbkFile = "", double massThreshold = 5.0)
+    : CodebookSetTrain(descFile, fs, cbkFile, massThreshold), _f(0) {}
+  ~CodebookSetFastSAT() { dsr_fsat_destroy(_f); }
+  // normFastAccus(transTree, olen): the accumulators of the current speaker, adapted by the MLLR parameters pt, folded into the fast accumulators
+  void normFastAccus(const ParamTreePtr& pt, unsigned olen = 0) {
+    if (olen != 0 && (int) olen != dsr_gmm_dim(model())) throw jdimension_error("olen for extended means is not implemented");
+    dsr_fsat* f = fastHandle();
+    dsr_throw(dsr_fsat_set_tree(f, 0, pt->handle())); dsr_throw(dsr_fsat_set_stats(f, 0, trainHandle())); dsr_throw(dsr_fsat_norm(f, 1, 0));
+  }
+  void saveFastAccus(const String& fileName) { dsr_throw(dsr_fsat_save_fast(fastHandle(), fileName.c_str())); }
+  void loadFastAccus(const String& fileName, unsigned nParts = 1, unsigned part = 1) { dsr_throw(dsr_fsat_load_fast(fastHandle(), fileName.c_str(), (int) nParts, (int) part)); }
+  void zeroFastAccus(unsigned nParts = 1, unsigned part = 1) { (void) nParts; (void) part; dsr_throw(dsr_fsat_zero_fast(fastHandle())); }
+  unsigned descLength() { unsigned dl = 0; dsr_throw(dsr_fsat_desc_length(fastHandle(), &dl)); return dl; }
+  void setRegClassesToOne() { dsr_throw(dsr_fsat_set_reg_classes_to_one(fastHandle())); }
+  dsr_fsat* fastHandle() {                                    // made on first use, one slot
+    if (!_f) {
+      dsr_throw(dsr_fsat_create(trainHandle(), 1, 0.0, 0.0, 1, 1, 0, &_f));
+      const dsr_status st = dsr_sat_set_apt_sub_features(dsr_fsat_sat(_f), nSubFeat()); if (st) { dsr_fsat_destroy(_f); _f = 0; dsr_throw(st); }
+    }
+    return _f;
+  }
+ private:
+  CodebookSetFastSAT(const CodebookSetFastSAT&); CodebookSetFastSAT& operator=(const CodebookSetFastSAT&);
+  dsr_fsat* _f;
+};
+typedef std::shared_ptr<CodebookSetFastSAT> CodebookSetFastSATPtr;
+
+class FastMeanVarianceSAT {
+ public:
+  FastMeanVarianceSAT(CodebookSetFastSATPtr& cbs, unsigned meanLen = 0, double lhoodThreshhold = 0.1, double massThreshhold = 10.0, unsigned nParts = 1,
+                      unsigned part = 1, double mmiMultiplier = 1.0, bool meanOnly = false, unsigned maxNoRegClass = 1, int slots = 16)
+    : _cbs(cbs), _h(0) {
+    dsr_throw(dsr_fsat_check((int) meanLen, dsr_gmm_dim(cbs->model()), massThreshhold, mmiMultiplier, meanOnly, (int) maxNoRegClass));
+    dsr_throw(dsr_fsat_create(cbs->trainHandle(), slots, lhoodThreshhold, massThreshhold, (int) nParts, (int) part, meanOnly, &_h));
+    const dsr_status st = dsr_sat_set_apt_sub_features(dsr_fsat_sat(_h), cbs->nSubFeat()); if (st) { dsr_fsat_destroy(_h); _h = 0; dsr_throw(st); }
+  }
+  ~FastMeanVarianceSAT() { dsr_fsat_destroy(_h); }
+  void zero() { dsr_throw(dsr_fsat_zero(_h)); }
+  // SATFast::estimate (sat.h:825-831): the fast accumulators and description lengths are the codebook set's; the lengths the update leaves go back
+  double estimate(const SpeakerListPtr& sList, const String& spkrAdaptParms, const String& meanVarsStats) {
+    dsr_fsat* src = _cbs->fastHandle(); const int nB = dsr_fsat_fast_blocks(src);
+    if (!nB) throw jconsistency_error("no fast accumulators: normFastAccus or loadFastAccus first");
+    const size_t G = (size_t) dsr_gmm_num_gaussians(_cbs->model()), D = (size_t) dsr_gmm_dim(_cbs->model());
+    std::vector<double> c(G), d(G), m(G * D), v(G * D), sc(G * nB); std::vector<uint16_t> dl(G * nB);
+    dsr_throw(dsr_fsat_get_fast(src, c.data(), d.data(), m.data(), v.data(), sc.data()));
+    dsr_throw(dsr_fsat_set_fast(_h, nB, c.data(), d.data(), m.data(), v.data(), sc.data()));
+    dsr_throw(dsr_fsat_get_desc_len(src, dl.data())); dsr_throw(dsr_fsat_set_desc_len(_h, nB, dl.data()));
+    double r = 0.0; dsr_throw(dsr_fsat_estimate_files(_h, sList->fileName().c_str(), spkrAdaptParms.c_str(), meanVarsStats.c_str(), &r));
+    dsr_throw(dsr_fsat_get_desc_len(_h, dl.data())); dsr_throw(dsr_fsat_set_desc_len(src, nB, dl.data()));
+    return r;
+  }
+  dsr_fsat* fsatHandle() const { return _h; }
+ private:
+  FastMeanVarianceSAT(const FastMeanVarianceSAT&); FastMeanVarianceSAT& operator=(const FastMeanVarianceSAT&);
+  CodebookSetFastSATPtr _cbs; dsr_fsat* _h;
+};
+typedef std::shared_ptr<FastMeanVarianceSAT> FastMeanVarianceSATPtr;
+
+#define DSR_SAT_NOT_BUILT(Name) \
+  class Name { public: template <class... A> explicit Name(A&&...) { throw jparameter_error(#Name " is not built"); } }; \
+  typedef std::shared_ptr<Name> Name##Ptr;
+DSR_SAT_NOT_BUILT(FastRegClassSAT)                            // SATFast<RegClassAcc>: fast accumulators of several classes per Gaussian
+DSR_SAT_NOT_BUILT(FastMaxMutualInfoSAT)                       // SATFast<MMIAcc>
+DSR_SAT_NOT_BUILT(FastMMIRegClassSAT)                         // SATFast<MMIRegClassAcc>
+#undef DSR_SAT_NOT_BUILT

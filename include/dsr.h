@@ -2254,7 +2254,7 @@ dsr_status dsr_train_kernel_ms(const dsr_train*, float ms[2]);
  * 10. MLLR speaker adaptation: regression classes, parameter trees, estimation, mean transforms
  *    Replaces the MLLR branch of asr/adapt/transform.{h,cc} ("tr") and asr/train/estimateAdapt.{h,cc} ("eA").  The all-pass transforms
  *    are section 13 (BLT and SLAPT with one estimated parameter; RAPT with more parameters and the multi-parameter Newton search are not
- *    implemented), STC and LDA section 12, the ML slice of asr/sat section 14.
+ *    implemented), STC and LDA section 12, the ML slice of asr/sat sections 14 and 14b.
  * ===================================================================================== */
 /* The regression-class table of a model: CodebookBasic::_regClass (asr/gaussian/codebookBasic.cc:179-187).  dsr_gmm_load keeps the FIRST class
  * of each Gaussian of a codebook file whose regClassPresent is set (:286-297) -- GaussDensity::regClass() (codebookBasic.h:275-280) -- and
@@ -2677,9 +2677,10 @@ dsr_status dsr_apt_transform_rows(int kind, int subFeatLen, int nSubFeat, int nC
  *    (sat:1884-1896) and SpeakerList (asr/adapt/transform.cc, "tr": 1989-1998) for the diagonal 1:1 models of dsr_gmm with
  *    orgFeatLen == featLen, under MLLR transforms (one block dimN x dimN, tr:1746-1785) and BLT / SLAPT transforms (nSubFeat blocks of
  *    subFeatLen^2 holding the same matrix, the bias as the block offsets, tr:1339-1363).
- *    Not implemented, and refused by dsr_sat_check: MDLSATMean (a likelihood threshold), FastSAT / FastAcc and the CodebookFastSAT
- *    accumulators, RegClassAcc / MMIRegClassAcc, FastMMISAT, SATMeanFullCovar, cluster.cc, extended means, an ldaFile; STC / LDA blocks in a
- *    speaker file are refused by the parameter readers.
+ *    MDLSATMean (a likelihood threshold), FastSAT / FastAcc and the CodebookFastSAT accumulators are section 14b (dsr_fsat_*); dsr_sat_check
+ *    and the two classes of this section keep refusing them.  Not implemented, here or there: RegClassAcc / MMIRegClassAcc, MMIAcc /
+ *    FastMMISAT, SATMeanFullCovar, cluster.cc, extended means, an ldaFile; STC / LDA blocks in a speaker file are refused by the parameter
+ *    readers.
  *
  *   check              the options of SAT<Type>(cbs, meanLen, lhoodThreshhold, massThreshhold, ...): DSR_E_PARAMETER for an accumulator kind
  *                      other than 0 (MeanAcc) or 1 (VarianceAcc) and for lhoodThreshold != 0, DSR_E_DIMENSION for meanLen != 0 and
@@ -2759,6 +2760,110 @@ dsr_status dsr_sat_get_solution(const dsr_sat*, double* means);
 int dsr_sat_gaussian_status(const dsr_sat*, int g);
 dsr_status dsr_sat_set_timing(dsr_sat*, int on);
 dsr_status dsr_sat_kernel_ms(const dsr_sat*, float ms[3]);
+
+/* ---------------------------------------------------------------------------------------------------------------------------------------
+ * 14b. Fast speaker-adaptive training: fast accumulators, MDL means and the joint variance update (csrc/fsat_kernels.hip, csrc/fsat.cpp)
+ *
+ *    Replaces CodebookFastSAT::FastAccu, GaussDensity::normFastAccu / descLen and CodebookSetFastSAT (asr/sat/codebookFastSAT.cc, "cfs":
+ *    135-254, 346-418, 523-539, 597-717), MDLSATMean (asr/sat/sat.cc, "sat": 383-493), FastSAT (sat:496-587), SATBase::FastAcc
+ *    (sat:1028-1104) and SATFast<FastAcc> = FastMeanVarianceSAT (sat.h:803-844) for the model scope of section 14.  A dsr_fsat owns a
+ *    dsr_sat: its S speaker slots and transform tables are those of section 14, and the SAT sums (mat, vec, scalar, occ, varVec) live in it.
+ *    The training pass folds every speaker's sumO / sumOsq into one speaker-independent fast accumulator per Gaussian (norm), kept in one file
+ *    that shards can sum (save_fast / load_fast); the estimation pass then needs only every speaker's counts and transforms (accumulate) and
+ *    re-estimates means and variances together (update).
+ *    Not implemented: fast accumulators of more than one class per Gaussian (subN > 1: replaceRegClass, ClassTotals, RegClassAcc /
+ *    MMIRegClassAcc), MMIAcc / FastMMISAT, SATMeanFullCovar, cluster.cc, extended means (olen != featLen), an ldaFile.
+ *
+ *   check              the options of FastMeanVarianceSAT(cbs, meanLen, lhoodThreshhold, massThreshhold, nParts, part, mmiMultiplier,
+ *                      meanOnly, maxNoRegClass) (sat.i:164-190): DSR_E_DIMENSION for extended means, DSR_E_PARAMETER for mmiMultiplier != 1
+ *                      and maxNoRegClass != 1, which FastAcc ignores: refused rather than ignored.  Host only
+ *   create             S speaker slots over the trainer's model; lhoodThreshold may be 0, massThreshold 0 means 10 (sat:1768), meanOnly is
+ *                      SATBase::MeanOnly (sat:555-558).  The trainer and its dsr_gmm must outlive the handle.  sat: the dsr_sat inside,
+ *                      borrowed: its transforms, sums, records, solution, statuses, timing and dsr_sat_set_apt_sub_features are read and set
+ *                      through section 14; statistics go into a slot through the entries below only, which also keep numProb and denProb
+ *   set_stats          count, denCount, sumO and sumOsq of a trainer's accumulators into slot s (device to device);  set_counts  the counts
+ *                      alone (what a countsOnly accumulator file holds): enough for accumulate, refused by norm;  set_stats_arrays  from
+ *                      host arrays count, denCount [G] and sumO, sumOsq [G][dimN], or both NULL for counts alone
+ *   set_tree, set_apt, set_transform, clear_slot   as dsr_sat_* on the slot
+ *   set_reg_classes_to_one   CodebookSetFastSAT::setRegClassesToOne (cfs:708-717): a Gaussian of class 0, or a model without classes,
+ *                      gets class 1
+ *   norm               CodebookSetFastSAT::normFastAccus (cfs:677-705) of slots 0 .. nSlots - 1 in order, for every Gaussian of the model:
+ *                      set_reg_classes_to_one; the first call after creation or zero_fast allocates and zeroes the fast accumulators
+ *                      (_zeroFastAccs); then GaussDensity::normFastAccu (cfs:346-418) with the slot's transformer of exactly the Gaussian's
+ *                      class: count += numProb and denCount += denProb unless both are zero; unless |ck| < 1e-6 (ck = numProb - denProb, a
+ *                      double), per block fastMean += (A o iv)^T (sumO - ck b), scalar += sum_m iv v^2 / ck, fastVar += sumOsq - 2 trn sumO
+ *                      + ck trn^2 with trn = transform(origMean) in the transform's own types.  Sequential fp64 in the reference's order:
+ *                      bit for bit.  One fast accumulator per Gaussian (subN == 1): DSR_E_KEY for a missing class, DSR_E_CONSISTENCY for a
+ *                      class with a descendant in the slot (not a leaf) and for a slot that holds counts only, DSR_E_DIMENSION for
+ *                      transforms of different block counts or another count than the accumulators'; nothing is added then.
+ *                      DSR_E_NUMERIC ("Scalar is NaN.", cfs:407-408) after the fold
+ *   zero_fast          the next norm, load_fast or set_fast allocates and zeroes;  fast_blocks  nblks of the fast accumulators, 0: none
+ *   save_fast          CodebookSetFastSAT::saveFastAccus (cfs:597-617): the AccMap directory, then per codebook with a non-zero count the
+ *                      Accu record of codebookTrain.cc:299-346 with countsOnly = 0 (name, refN, dimN, subN = 1, type, 0), orgDimN, nblks,
+ *                      per Gaussian count, denCount, fastMean, fastVar, then the scalars [refN][nblks], the marker: big-endian floats
+ *   load_fast          CodebookSetFastSAT::loadFastAccus (cfs:619-644) for the codebooks of (nParts, part): the file is ADDED.  A handle
+ *                      without fast accumulators takes the file's nblks.  DSR_E_DIMENSION for another refN, dimN, subN, type, orgDimN or
+ *                      nblks, DSR_E_CONSISTENCY for a counts-only record, DSR_E_IO for a truncated file or a missing marker; a refused
+ *                      file leaves the accumulators as they were
+ *   get_fast, set_fast count, denCount [G], fastMean, fastVar [G][dimN], scalar [G][nblks] in double; get: any pointer may be NULL
+ *   add_fast           SATFast::addFastAccs (sat.h:833-842) for the Gaussians of the part: vec += fastMean, varVec += fastVar, scalar +=
+ *                      fastScalar; every block counts as allocated afterwards
+ *   accumulate         FastAcc::accumulate / FastSAT::accumulate (sat:1067-1077, 501-528) of slots 0 .. nSlots - 1: mat += c (A o iv)^T A
+ *                      and occ += c with float c = float(count - denCount); sumO is never read.  The refusals of dsr_sat_accumulate.  It is
+ *                      k_sat_mean_acc without its vec columns and its scalar pass: mat and occ have the bits dsr_sat_accumulate(1) gives
+ *   update             FastAcc::update (sat:1079-1099): occ < massThreshold: var = 1 / var, the mean stays.  Otherwise the variances first
+ *                      (float(varVec / occ), a NaN keeps 1 / var; 1 / var under meanOnly), then MDLSATMean::update (sat:395-493) per block:
+ *                      auxOld = aux(mean) + thr descLen; M = V diag(l) V^T; t = V^T vec; component k kept when 0.5 t_k^2 / l_k > thr and
+ *                      l_k / max(0, max l) >= 1e-7; x = V t'; auxNew = aux(x) + thr kept; auxOld < auxNew keeps the block and its descLen,
+ *                      otherwise descLen = kept and the mean becomes float(x).  occ == 0 zeroes the mean.  info, totals, aux as
+ *                      dsr_sat_update(1).  A Gaussian without blocks (nothing accumulated, no add_fast) is left as it is.  A Gaussian whose
+ *                      statistics are not finite or whose eigen-decomposition did not converge keeps its mean and description lengths and
+ *                      is flagged, its covariance slot becomes 1 / var like the rest; the others are done and the call returns
+ *                      DSR_E_CONSISTENCY.  The covariance slot holds VARIANCES afterwards: call dsr_train_invert_variances and
+ *                      dsr_train_fix_gconsts
+ *   zero               dsr_sat_zero of the SAT sums (the fast accumulators and description lengths stay)
+ *   desc_length        CodebookSetFastSAT::descLength (cfs:654-673): the sum over every (Gaussian, block); every block starts at 1
+ *                      (cfs:523-539).  desc_blocks: the block count they are kept for, fixed by the first norm, load_fast, set_fast,
+ *                      add_fast, accumulate or set_desc_len; 0 before (desc_length is then G x nSubFeat);  get_desc_len / set_desc_len
+ *                      [G][nBlocks]
+ *   estimate_files     SATFast::estimate (sat.h:825-831): add_fast, then SATBase::estimate (sat:1802-1839) as dsr_sat_estimate_files with
+ *                      the matrix-only accumulate and this update; the speaker files may be counts-only or full (only the counts are
+ *                      read).  *ret = (lhoodThreshold desc_length() + sum totalPr) / (sum totalT), desc_length taken before the update.  The
+ *                      SAT sums are not zeroed first
+ *   get_records        dsr_sat_get_records of the last update, and descLen [G][nBlocks] as that update left them
+ *   kernel_ms          milliseconds of the last k_fsat_norm, matrix-only k_sat_mean_acc and k_fsat_solve (dsr_sat_set_timing on sat) */
+typedef struct dsr_fsat dsr_fsat;
+dsr_status dsr_fsat_check(int meanLen, int featLen, double massThreshold, double mmiMultiplier, int meanOnly, int maxNoRegClass);
+dsr_status dsr_fsat_create(dsr_train*, int S, double lhoodThreshold, double massThreshold, int nParts, int part, int meanOnly, dsr_fsat** out);
+void dsr_fsat_destroy(dsr_fsat*);
+dsr_sat* dsr_fsat_sat(dsr_fsat*);
+int dsr_fsat_fast_blocks(const dsr_fsat*);
+int dsr_fsat_desc_blocks(const dsr_fsat*);
+dsr_status dsr_fsat_set_stats(dsr_fsat*, int s, dsr_train*);
+dsr_status dsr_fsat_set_counts(dsr_fsat*, int s, dsr_train*);
+dsr_status dsr_fsat_set_stats_arrays(dsr_fsat*, int s, const double* count, const double* denCount, const double* sumO, const double* sumOsq);
+dsr_status dsr_fsat_set_tree(dsr_fsat*, int s, const dsr_param_tree*);
+dsr_status dsr_fsat_set_apt(dsr_fsat*, int s, dsr_apt*, int aptSlot);
+dsr_status dsr_fsat_set_transform(dsr_fsat*, int s, unsigned rc, int kind, int nBlocks, const double* A, const double* b);
+dsr_status dsr_fsat_clear_slot(dsr_fsat*, int s);
+dsr_status dsr_fsat_set_reg_classes_to_one(dsr_fsat*);
+dsr_status dsr_fsat_norm(dsr_fsat*, int nSlots, void* stream);
+dsr_status dsr_fsat_zero_fast(dsr_fsat*);
+dsr_status dsr_fsat_save_fast(dsr_fsat*, const char* fileName);
+dsr_status dsr_fsat_load_fast(dsr_fsat*, const char* fileName, int nParts, int part);
+dsr_status dsr_fsat_get_fast(dsr_fsat*, double* count, double* denCount, double* fastMean, double* fastVar, double* scalar);
+dsr_status dsr_fsat_set_fast(dsr_fsat*, int nBlocks, const double* count, const double* denCount, const double* fastMean, const double* fastVar,
+                             const double* scalar);
+dsr_status dsr_fsat_add_fast(dsr_fsat*);
+dsr_status dsr_fsat_accumulate(dsr_fsat*, int nSlots, void* stream);
+dsr_status dsr_fsat_update(dsr_fsat*, unsigned info[4], unsigned totals[2], double* aux);
+dsr_status dsr_fsat_zero(dsr_fsat*);
+dsr_status dsr_fsat_desc_length(const dsr_fsat*, unsigned* dl);
+dsr_status dsr_fsat_get_desc_len(const dsr_fsat*, uint16_t* descLen);
+dsr_status dsr_fsat_set_desc_len(dsr_fsat*, int nBlocks, const uint16_t* descLen);
+dsr_status dsr_fsat_estimate_files(dsr_fsat*, const char* speakerList, const char* paramPrefix, const char* accuPrefix, double* ret);
+dsr_status dsr_fsat_get_records(const dsr_fsat*, int32_t* kept, int32_t* decision, double* auxOld, double* auxNew, int32_t* descLen);
+dsr_status dsr_fsat_kernel_ms(const dsr_fsat*, float ms[3]);
 
 #ifdef __cplusplus
 }
